@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — HiFi-CAR EMA->waveform synthesis throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,20 +12,33 @@ PastFCEncoder and the sample feedback included.  Inputs and weights are resident
 region.  With N > 1 every rank synthesises its own 64 utterances (weak scaling, no data-path collective)
 and the step ends with the one RCCL all-gather that collects the waveforms.
 
-The headline (`value`, `dtype: "fp32"`, `roofline`) is the reference's arithmetic: exact IEEE fp32 products on
-v_mfma_f32_32x32x2_f32.  The split-bf16 fast mode (`--precision bf16x3`, 16-bit-significand products, 1.5e-5 of
-max|y| from fp32) is opt-in and reported as the labelled secondary leg `fast_bf16x3` with the same steps / warm-up
-and its own roofline block.  `batch_sweep` repeats the fp32 measurement at batch 1 and 8 (north_star: 1/8/64).
+The headline (`value`, `dtype: "fp32"`) is the reference's arithmetic: exact IEEE fp32 products on
+v_mfma_f32_32x32x2_f32.  A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps
+(`ms_per_step` = the wall time of one of them), the outputs of the last timed step if `--dump-outputs DIR` is given,
+and the result line.
+
+`--full` adds everything else the benchmark measures, each after the headline and outside its timed steps (`--no-*`
+leave single legs out of a full run):
+  roofline      a second pass of the same K steps with every kernel launch bracketed by HIP events on the launch stream
+                (libhificar's profile hooks), so that the event traffic does not perturb `value`
+  fast_bf16x3   the split-bf16 fast mode (16-bit-significand products, 1.5e-5 of max|y| from fp32, opt-in as
+                `--precision bf16x3`) with the same steps / warm-up and its own roofline block
+  batch_sweep   the fp32 measurement at batch 1 and 8 (north_star: 1/8/64)
+  nonar         BASELINE config 2: HiFi-GAN non-AR 12-dim EMA, batch 1 / 8 / 64 — north_star's literal sweep; roofline on
+                config 2's batch 8
+  gblock        the reference's other a2w generator, GBlockGenerator, batch 64 AR synthesis, with its own roofline block
+  training      BASELINE config 5's GAN iteration (training_leg)
+  cpu_baseline  the CPU oracle on a bounded sample
+(the legs after `roofline` at N = 1 only).
+
+`--dump-outputs DIR` writes the waveforms the last timed step returned (all ranks' at N > 1) as DIR/waveform.npy, float32,
+at most 64 MB (a larger output: a fixed, seeded sample of its utterances).  Weights and inputs are seeded, so two runs
+with the same arguments see the same inputs, and two builds can be compared output for output.
 
 A plain `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) launches its own N ranks through
 torch.distributed.run on 127.0.0.1 and forwards rank 0's line; under an outer torchrun it is one of the ranks.
 
-The N = 1 line also carries `nonar` (BASELINE config 2: HiFi-GAN non-AR 12-dim EMA, batch 1 / 8 / 64 — north_star's literal sweep; roofline on
-config 2's batch 8) and `gblock` (the reference's other a2w generator, GBlockGenerator, batch 64 AR synthesis), each with its own roofline block.
-
-Prints ONE JSON line on rank 0.  `roofline` is measured in a second pass of the same K steps with every
-kernel launch bracketed by HIP events on the launch stream (libhificar's profile hooks) so that the
-event traffic does not perturb `value`; `cpu_baseline` times the CPU oracle on a bounded sample.
+Prints ONE JSON line on rank 0.
 """
 
 import argparse
@@ -53,6 +66,25 @@ PEAK_TFLOPS = {"f32": 157.3, "bf16x3": 2500.0}  # /opt/skills/guides/MI355X_MICR
 PEAK_HBM_GBS = 8000.0                              # same guide: HBM3E 8 TB/s spec
 DTYPE_NAME = {"f32": "fp32", "bf16x3": "bf16x3"}
 MFMA_PER_MAC = {"f32": 1, "bf16x3": 3}             # bf16x3 issues 3 bf16 MFMAs per algorithmic MAC
+DUMP_MAX_BYTES = 64 * 10**6                        # --dump-outputs: at most 64 MB in all
+
+
+def dump_waveforms(out_dir, y):
+    """--dump-outputs: `y` (utterances x samples) as out_dir/waveform.npy in float32.  Larger than DUMP_MAX_BYTES: a fixed, seeded sample of
+    its utterances (rows), and if one utterance alone is larger, its leading samples.  Returns what was written, for the result line."""
+    import numpy as np
+
+    a = y.detach().cpu().numpy().astype(np.float32) if hasattr(y, "detach") else np.asarray(y, dtype=np.float32)
+    a = a.reshape(a.shape[0], -1)
+    budget = (DUMP_MAX_BYTES - 4096) // 4  # (floats; 4 KB for the .npy header)
+    rows = None
+    if a.size > budget:
+        keep = max(1, budget // a.shape[1])
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+        a = a[rows, :budget // keep]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "waveform.npy"), a)
+    return {"waveform": {"shape": list(a.shape), "of": list(y.shape), "sampled_rows_seed": None if rows is None else 0}}
 
 
 def cpu_baseline(params, sd, chunk_frames, feats8):
@@ -482,14 +514,22 @@ def main(argv=None, synth_factory=None):
                     help="conv arithmetic of the headline: f32 = the reference's IEEE fp32 products (default)")
     ap.add_argument("--gather", default="f32", choices=["f32", "pcm16"],
                     help="N > 1: collect float waveforms (default) or PCM_16 converted on the device (half the bytes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fast-leg", action="store_true", help="skip the secondary bf16x3 leg (N=1 only)")
-    ap.add_argument("--no-batch-sweep", action="store_true", help="skip the batch 1 / 8 legs (N=1 only)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-training", action="store_true", help="skip the training leg (N=1 only): generator train step and GAN iteration")
-    ap.add_argument("--no-nonar", action="store_true", help="skip the non-AR leg (N=1 only): BASELINE config 2, batch 1 / 8 / 64")
-    ap.add_argument("--no-gblock", action="store_true", help="skip the GBlockGenerator leg (N=1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the waveforms of the last timed step as DIR/waveform.npy (float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: roofline, bf16x3 leg, batch sweep, non-AR, GBlock, training, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-fast-leg", action="store_true", help="--full: skip the secondary bf16x3 leg (N=1 only)")
+    ap.add_argument("--no-batch-sweep", action="store_true", help="--full: skip the batch 1 / 8 legs (N=1 only)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the event-bracketed roofline passes")
+    ap.add_argument("--no-training", action="store_true", help="--full: skip the training leg (N=1 only): generator train step and GAN iteration")
+    ap.add_argument("--no-nonar", action="store_true", help="--full: skip the non-AR leg (N=1 only): BASELINE config 2, batch 1 / 8 / 64")
+    ap.add_argument("--no-gblock", action="store_true", help="--full: skip the GBlockGenerator leg (N=1 only)")
     args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run is the headline alone: set-up, warm-up, the timed steps, the optional dump, the result line
+        args.no_cpu_baseline = args.no_fast_leg = args.no_batch_sweep = args.no_roofline = True
+        args.no_training = args.no_nonar = args.no_gblock = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the driver's command is a plain `python3 bench.py --gpus N ...`: become the launcher of N ranks (one process per GPU)
         raise SystemExit(self_launch(args.gpus, sys.argv[1:] if argv is None else argv))
@@ -579,6 +619,10 @@ def main(argv=None, synth_factory=None):
         mine = gstate["gathered"][rank * B:(rank + 1) * B]
         assert torch.equal(mine, pcm16(y) if args.gather == "pcm16" else y), "all-gather returned a different waveform"
     assert bool(torch.isfinite(y).all()), "non-finite output"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the waveforms, every rank's once they are gathered
+        dumped = dump_waveforms(args.dump_outputs, gstate["gathered"] if use_dist else y)
 
     ms_per_step = dt / args.steps * 1e3
     value = world * n_samples * args.steps / dt
@@ -620,6 +664,8 @@ def main(argv=None, synth_factory=None):
         # rank 0's average time inside the waveform all-gather per step (device events under RCCL): ms_per_step - gather_ms is synthesis
         out["gather_ms"] = None if gather_ms is None else round(gather_ms, 3)
         out["gather_bytes_per_rank"] = int(n_samples * (2 if args.gather == "pcm16" else 4))
+    if dumped:
+        out["dumped_outputs"] = dumped
     if not on_gpu:
         # a stand-in synthesis ran (HIFICAR_BENCH_STANDIN / the synth_factory test hook): plumbing only, and the line says so
         out["standin"] = True

@@ -169,6 +169,49 @@ def test_bench_gpus_8_as_the_driver_launches_it():
         assert f"({n // 8} of {n})" in aff  # rank 0's own eighth of the cores
 
 
+def test_bench_dump_outputs_writes_the_last_steps_gathered_waveforms(tmp_path):
+    """`--dump-outputs DIR`: the waveforms of the last timed step (every rank's, as gathered) in DIR/waveform.npy, float32, the same from run to
+    run with the same arguments (seeded weights and features), and the result line says what was written."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--seconds", "0.25",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=_bench_env(repo, "factory_light"), cwd=repo)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert d["steps"] == 3 and d["dumped_outputs"] == {"waveform": {"shape": [4, 4000], "of": [4, 4000], "sampled_rows_seed": None}}
+        assert sorted(os.listdir(out)) == ["waveform.npy"]
+        got.append(np.load(out / "waveform.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (4, 4000) and np.isfinite(got[0]).all()
+    assert np.array_equal(got[0], got[1])
+    assert not np.array_equal(got[0][:2], got[0][2:])  # the two ranks' own utterances (seeded per rank), rank 0's first
+
+
+def test_bench_dump_outputs_samples_utterances_beyond_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 4 * 1000)  # room for 1000 floats
+    y = torch.arange(10 * 300, dtype=torch.float64).reshape(10, 300)
+    info = bench.dump_waveforms(str(tmp_path / "a"), y)
+    a = np.load(tmp_path / "a" / "waveform.npy")
+    assert a.dtype == np.float32 and a.shape == (3, 300) and info["waveform"] == {"shape": [3, 300], "of": [10, 300], "sampled_rows_seed": 0}
+    rows = a[:, 0] / 300
+    assert np.array_equal(rows, np.sort(rows)) and len(set(rows)) == 3 and np.array_equal(a, y.numpy()[rows.astype(int)])
+    bench.dump_waveforms(str(tmp_path / "b"), y)
+    assert np.array_equal(np.load(tmp_path / "b" / "waveform.npy"), a)  # a fixed sample
+    bench.dump_waveforms(str(tmp_path / "c"), torch.ones(2, 5000))  # one utterance alone over the budget: its leading samples
+    assert np.load(tmp_path / "c" / "waveform.npy").shape == (1, 1000)
+
+
 def test_bench_gpus_8_propagates_a_failing_rank():
     import subprocess
     import sys

@@ -108,18 +108,17 @@ def test_dump_dir_pairs_hdf5_and_npy(tmp_path):
         assert feats.shape == (20, 4) and len(audio) == 200 and audio[7] == 7
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/egs"), reason="the reference's YAML files only exist in the build container")
 @pytest.mark.parametrize("recipe,path", [("car", "egs/ema/voc1/conf/e2w_hifigan_car.yaml"), ("e2w", "egs/ema/voc1/conf/e2w_hifigan.yaml"),
                                          ("mri", "egs/mri/voc1/conf/mri2w_hifigan_car.yaml")])
-def test_recipe_values_equal_the_shipped_yaml(recipe, path):
-    """articulatory_amd/utils/recipes.py restates the shipped YAMLs as values (they do not travel to the GPU box): every key the Trainer
-    reads equals the file's."""
-    import yaml
+def test_recipe_values_equal_the_shipped_yaml(recipe, path, golden_dir):
+    """articulatory_amd/utils/recipes.py restates the shipped YAMLs as values (they live in the reference repository): every key the Trainer
+    reads equals the file's.  The files' values are pinned in tests/golden/gold_recipe_yaml.json (oracle/make_golden_recipes.py)."""
+    import json
 
     from articulatory_amd.utils.recipes import recipe_train_config
 
-    with open(os.path.join("/root/reference", path)) as f:
-        ref = yaml.safe_load(f)
+    with open(os.path.join(golden_dir, "gold_recipe_yaml.json")) as f:
+        ref = json.load(f)[path]
     mine = recipe_train_config(recipe)
     for k, v in mine.items():
         if k in ("distributed", "fused_optimizers", "stft_loss_params"):

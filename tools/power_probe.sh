@@ -10,7 +10,7 @@ echo "=== samples while python bench.py --steps 8 runs (idle first, then the war
   done ) &
 smp=$!
 sleep 1
-python bench.py --steps 8 --no-cpu-baseline --no-fast-leg --no-batch-sweep --no-training > ${out%.txt}_bench.json 2>/dev/null
+python bench.py --full --steps 8 --no-cpu-baseline --no-fast-leg --no-batch-sweep --no-training > ${out%.txt}_bench.json 2>/dev/null
 kill $smp 2>/dev/null
 tail -c 400 ${out%.txt}_bench.json
 wc -l $out

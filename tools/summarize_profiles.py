@@ -59,8 +59,8 @@ def stamp(key):
 
 
 # (file prefix / directory key, key in hbm_traffic.json, the profiled command): the two arithmetics of the headline leg, then the secondary legs
-LEGS = [("f32", "f32", "python bench.py --precision f32 --steps 3 --warmup 1 --no-cpu-baseline --no-fast-leg --no-batch-sweep --no-training --no-nonar --no-gblock"),
-        ("bf16x3", "bf16x3", "python bench.py --precision bf16x3 --steps 3 --warmup 1 --no-cpu-baseline --no-fast-leg --no-batch-sweep --no-training --no-nonar --no-gblock"),
+LEGS = [("f32", "f32", "python bench.py --full --precision f32 --steps 3 --warmup 1 --no-cpu-baseline --no-fast-leg --no-batch-sweep --no-training --no-nonar --no-gblock"),
+        ("bf16x3", "bf16x3", "python bench.py --full --precision bf16x3 --steps 3 --warmup 1 --no-cpu-baseline --no-fast-leg --no-batch-sweep --no-training --no-nonar --no-gblock"),
         ("nonar", "nonar_f32", "python tools/leg_bench.py --leg nonar --steps 3 --warmup 1  (BASELINE config 2: non-AR 12-dim, batch 8)"),
         ("gblock", "gblock_f32", "python tools/leg_bench.py --leg gblock --steps 3 --warmup 1  (GBlockGenerator, batch 64, chunk 25)")]
 for prec, tkey, cmd in LEGS:
