@@ -37,32 +37,8 @@ struct hificar_disc {
     bool col2im_vec4 = true;  // HIFICAR_COL2IM_VEC4=0: the scalar col2im_mask_kernel everywhere (A/B runs)
     hificar_handle* eng = nullptr;
     std::vector<DiscSub> subs;
-    struct Slot {
-        std::string name;
-        std::vector<int64_t> shape;
-        int64_t offset, numel;
-    };
-    std::vector<Slot> params;  // folded parameters, state_dict order
-    std::map<std::string, int> param_index;
-    int64_t grad_total = 0;
-    float* d_folded = nullptr;
-    PackParams* d_pack_jobs = nullptr;
-    int* d_pack_start = nullptr;
-    int n_pack_jobs = 0, n_pack_wgs = 0;
-    ParamJob* d_param_jobs = nullptr;
-    int* d_param_start = nullptr;
-    ParamJob* pin_param_jobs = nullptr;
-    int* pin_param_start = nullptr;
-    std::vector<ParamJob> param_jobs;
-    std::vector<std::string> raw_names;
-    int n_param_wgs = 0;
-    int64_t raw_total = 0;
-    bool have_params = false;
-    // gradient buckets: one per sub-discriminator (their parameters are contiguous in state_dict order, raw and folded alike)
-    std::vector<int> bucket_job_lo;  // [sub] first ParamJob; [n_subs] = number of jobs
-    std::vector<int> raw_bucket;     // [raw parameter of the last hand-over]
-    hificar_bucket_fn bucket_fn = nullptr;
-    void* bucket_user = nullptr;
+    // folded parameters in state_dict order; gradient buckets: one per sub-discriminator (its parameters are contiguous, raw and folded alike)
+    RawParamSet raw;
     bool grad_accumulate = false;        // hificar_disc_set_grad_accumulate
     const float* grad_scale = nullptr;   // hificar_disc_set_grad_scale
     // the sub-discriminators are independent networks of small launches: each runs on its own stream between a fork and a join on the
@@ -310,13 +286,7 @@ static int disc_add_layer(hificar_disc* d, DiscSub& s, const std::string& base, 
             P.d_bias = bbase + (size_t)gi * be;
         }
     }
-    auto slot = [&](const std::string& name, std::vector<int64_t> shape) {
-        int64_t n = 1;
-        for (auto v : shape) n *= v;
-        d->param_index[name] = (int)d->params.size();
-        d->params.push_back({name, shape, d->grad_total, n});
-        d->grad_total += (n + 3) & ~(int64_t)3;
-    };
+    auto slot = [&](const std::string& name, const std::vector<int64_t>& shape) { d->raw.add(name, shape, (int)d->subs.size()); };
     // state_dict order: a weight-normed Conv2d lists bias first (bias, weight_g, weight_v); a plain Conv1d weight, bias
     if (conv2d) {
         slot(base + ".bias", {cout});
@@ -394,6 +364,10 @@ extern "C" int hificar_disc_create(const hificar_disc_config* cfg, hificar_disc*
         }
         d->subs.push_back(s);
     }
+    d->raw.n_buckets = (int)d->subs.size();
+    for (size_t j = 1; j < d->raw.slots.size(); ++j)  // (hificar_disc_bucket_folded_range and the job order rely on it)
+        if (d->raw.slots[j].bucket < d->raw.slots[j - 1].bucket)
+            return bail(fail(HIFICAR_E_INVALID, "internal: sub-discriminator parameters are not contiguous"));
     d->sub_stream.resize(d->subs.size());
     for (size_t i = 0; i < d->subs.size(); ++i) d->sub_stream[i] = (int)i;
     *out = d;
@@ -402,8 +376,6 @@ extern "C" int hificar_disc_create(const hificar_disc_config* cfg, hificar_disc*
 
 extern "C" void hificar_disc_destroy(hificar_disc* d) {
     if (!d) return;
-    if (d->pin_param_jobs) (void)hipHostFree(d->pin_param_jobs);
-    if (d->pin_param_start) (void)hipHostFree(d->pin_param_start);
     for (hipStream_t s : d->side) (void)hipStreamDestroy(s);
     for (hipEvent_t e : d->join_ev) (void)hipEventDestroy(e);
     if (d->fork_ev) (void)hipEventDestroy(d->fork_ev);
@@ -412,11 +384,11 @@ extern "C" void hificar_disc_destroy(hificar_disc* d) {
 }
 
 extern "C" hificar_handle* hificar_disc_engine(hificar_disc* d) { return d ? d->eng : nullptr; }
-extern "C" int hificar_disc_param_count(const hificar_disc* d) { return d ? (int)d->params.size() : -1; }
+extern "C" int hificar_disc_param_count(const hificar_disc* d) { return d ? (int)d->raw.slots.size() : -1; }
 
 extern "C" int hificar_disc_param_info(const hificar_disc* d, int i, char* name96, int64_t* shape4, int* ndim, int64_t* offset) {
-    if (!d || i < 0 || i >= (int)d->params.size() || !name96) return fail(HIFICAR_E_INVALID, "hificar_disc_param_info: bad argument");
-    const auto& s = d->params[(size_t)i];
+    if (!d || i < 0 || i >= (int)d->raw.slots.size() || !name96) return fail(HIFICAR_E_INVALID, "hificar_disc_param_info: bad argument");
+    const auto& s = d->raw.slots[(size_t)i];
     snprintf(name96, 96, "%s", s.name.c_str());
     if (shape4)
         for (size_t k = 0; k < 4; ++k) shape4[k] = k < s.shape.size() ? s.shape[k] : 1;
@@ -425,207 +397,81 @@ extern "C" int hificar_disc_param_info(const hificar_disc* d, int i, char* name9
     return HIFICAR_OK;
 }
 
-extern "C" int64_t hificar_disc_grad_floats(const hificar_disc* d) { return d ? d->grad_total : -1; }
-extern "C" int64_t hificar_disc_raw_grad_floats(const hificar_disc* d) { return d && d->have_params ? d->raw_total : -1; }
+extern "C" int64_t hificar_disc_grad_floats(const hificar_disc* d) { return d ? d->raw.total : -1; }
+extern "C" int64_t hificar_disc_raw_grad_floats(const hificar_disc* d) { return d && d->raw.have_params ? d->raw.raw_total : -1; }
+
+// Every pack of the discriminators (forward + data gradient of each group's GEMM, modes 8-11), its sources inside the master copy.
+static int disc_pack_jobs(const hificar_disc* d, std::vector<PackParams>& jobs) {
+    for (const DiscSub& s : d->subs)
+        for (const DiscLayer& L : s.layers) {
+            const float* w = d->raw.d_folded + d->raw.offset(L.base + ".weight");
+            const float* b = L.has_bias ? d->raw.d_folded + d->raw.offset(L.base + ".bias") : nullptr;
+            for (const DiscGroup& G : L.g) {
+                PackParams pp;
+                fill_pack(pp, G.F, G.F.chunk16);
+                pp.src = w + (size_t)G.co0 * L.cin_g * L.k;
+                pp.dst = G.F.d_w32;
+                pp.mode = 8;
+                pp.cin = L.cin_g;
+                pp.K = L.k;
+                pp.cout = L.cout_g;
+                pp.cout_pack = L.cout_g;
+                pp.cin_pack = L.Kg;
+                jobs.push_back(pp);
+                fill_pack(pp, G.D, G.D.chunk16);
+                pp.src = w + (size_t)G.co0 * L.cin_g * L.k;
+                pp.dst = G.D.d_w32;
+                pp.mode = 9;
+                pp.cin = L.cin_g;
+                pp.K = L.k;
+                pp.cout = L.cout_g;
+                pp.cout_pack = L.Kg;
+                pp.cin_pack = L.cout_g;
+                jobs.push_back(pp);
+                if (L.can_window) {  // polyphase-input form: the forward pack (mode 10) and its data gradient's (mode 11)
+                    fill_pack(pp, G.P, G.P.chunk16);
+                    pp.src = w + (size_t)G.co0 * L.cin_g * L.k;
+                    pp.dst = G.P.d_w32;
+                    pp.mode = 10;
+                    pp.cin = L.cin_g;
+                    pp.K = L.k;
+                    pp.cout = L.cout_g;
+                    pp.stride = L.stride;
+                    pp.cout_pack = L.cout_g;
+                    pp.cin_pack = L.stride * L.cin_g;
+                    jobs.push_back(pp);
+                    fill_pack(pp, G.Q, G.Q.chunk16);
+                    pp.src = w + (size_t)G.co0 * L.cin_g * L.k;
+                    pp.dst = G.Q.d_w32;
+                    pp.mode = 11;
+                    pp.cin = L.cin_g;
+                    pp.K = L.k;
+                    pp.cout = L.cout_g;
+                    pp.stride = L.stride;
+                    pp.cout_pack = L.stride * L.cin_g;
+                    pp.cin_pack = L.cout_g;
+                    jobs.push_back(pp);
+                    if (b) jobs.push_back(simple_pack(7, b + G.co0, G.P.d_bias, L.cout_g));
+                }
+                if (b) jobs.push_back(simple_pack(7, b + G.co0, G.F.d_bias, L.cout_g));
+            }
+        }
+    return HIFICAR_OK;
+}
 
 // Every parameter in its RAW state_dict form from device memory (weight_g / weight_v of the weight-normed period discriminators, plain
 // weights of the scale discriminators — hifigan.py:645-663 never norms those —, biases): weight norm folded on the device into a master
 // copy, every GEMM pack (forward + data gradient) refreshed from it.  Two launches.  Same contract as hificar_set_parameters_device.
 extern "C" int hificar_disc_set_parameters_device(hificar_disc* d, const char* const* names, const float* const* data, int n, void* stream_) {
     if (!d || !names || !data || n < 1) return fail(HIFICAR_E_INVALID, "hificar_disc_set_parameters_device: null argument");
-    hificar_handle* h = d->eng;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc;
-    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
-    if (!d->d_folded) {
-        void* p = nullptr;
-        HIP_TRY(hipMalloc(&p, (size_t)d->grad_total * sizeof(float)));
-        h->allocs.push_back(p);
-        d->d_folded = static_cast<float*>(p);
-        std::vector<PackParams> jobs;
-        for (const DiscSub& s : d->subs)
-            for (const DiscLayer& L : s.layers) {
-                const float* w = d->d_folded + d->params[(size_t)d->param_index.at(L.base + ".weight")].offset;
-                const float* b = L.has_bias ? d->d_folded + d->params[(size_t)d->param_index.at(L.base + ".bias")].offset : nullptr;
-                for (const DiscGroup& G : L.g) {
-                    PackParams pp;
-                    fill_pack(pp, G.F, G.F.chunk16);
-                    pp.src = w + (size_t)G.co0 * L.cin_g * L.k;
-                    pp.dst = G.F.d_w32;
-                    pp.mode = 8;
-                    pp.cin = L.cin_g;
-                    pp.K = L.k;
-                    pp.cout = L.cout_g;
-                    pp.cout_pack = L.cout_g;
-                    pp.cin_pack = L.Kg;
-                    jobs.push_back(pp);
-                    fill_pack(pp, G.D, G.D.chunk16);
-                    pp.src = w + (size_t)G.co0 * L.cin_g * L.k;
-                    pp.dst = G.D.d_w32;
-                    pp.mode = 9;
-                    pp.cin = L.cin_g;
-                    pp.K = L.k;
-                    pp.cout = L.cout_g;
-                    pp.cout_pack = L.Kg;
-                    pp.cin_pack = L.cout_g;
-                    jobs.push_back(pp);
-                    if (L.can_window) {  // polyphase-input form: the forward pack (mode 10) and its data gradient's (mode 11)
-                        fill_pack(pp, G.P, G.P.chunk16);
-                        pp.src = w + (size_t)G.co0 * L.cin_g * L.k;
-                        pp.dst = G.P.d_w32;
-                        pp.mode = 10;
-                        pp.cin = L.cin_g;
-                        pp.K = L.k;
-                        pp.cout = L.cout_g;
-                        pp.stride = L.stride;
-                        pp.cout_pack = L.cout_g;
-                        pp.cin_pack = L.stride * L.cin_g;
-                        jobs.push_back(pp);
-                        fill_pack(pp, G.Q, G.Q.chunk16);
-                        pp.src = w + (size_t)G.co0 * L.cin_g * L.k;
-                        pp.dst = G.Q.d_w32;
-                        pp.mode = 11;
-                        pp.cin = L.cin_g;
-                        pp.K = L.k;
-                        pp.cout = L.cout_g;
-                        pp.stride = L.stride;
-                        pp.cout_pack = L.stride * L.cin_g;
-                        pp.cin_pack = L.cout_g;
-                        jobs.push_back(pp);
-                        if (b) jobs.push_back(simple_pack(7, b + G.co0, G.P.d_bias, L.cout_g));
-                    }
-                    if (b) jobs.push_back(simple_pack(7, b + G.co0, G.F.d_bias, L.cout_g));
-                }
-            }
-        std::vector<int> start(jobs.size() + 1, 0);
-        for (size_t j = 0; j < jobs.size(); ++j)
-            start[j + 1] = start[j] + (int)std::max<long long>(1, std::min<long long>((jobs[j].total + 1023) / 1024, 256));
-        d->n_pack_jobs = (int)jobs.size();
-        d->n_pack_wgs = start.back();
-        if ((rc = device_table(h, jobs, &d->d_pack_jobs)) != HIFICAR_OK) return rc;
-        if ((rc = device_table(h, start, &d->d_pack_start)) != HIFICAR_OK) return rc;
-        const size_t cap = d->params.size();
-        HIP_TRY(hipMalloc(&p, cap * sizeof(ParamJob)));
-        h->allocs.push_back(p);
-        d->d_param_jobs = static_cast<ParamJob*>(p);
-        HIP_TRY(hipMalloc(&p, (cap + 1) * sizeof(int)));
-        h->allocs.push_back(p);
-        d->d_param_start = static_cast<int*>(p);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->pin_param_jobs), cap * sizeof(ParamJob), hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->pin_param_start), (cap + 1) * sizeof(int), hipHostMallocDefault));
-    }
-    std::map<std::string, int> where;
-    std::vector<std::string> raw_names((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        if (!names[i] || !data[i]) return fail(HIFICAR_E_INVALID, "hificar_disc_set_parameters_device: entry %d is null", i);
-        raw_names[(size_t)i] = names[i];
-        if (!where.emplace(raw_names[(size_t)i], i).second) return fail(HIFICAR_E_INVALID, "parameter '%s' given twice", names[i]);
-    }
-    std::vector<ParamJob> jobs;
-    std::vector<int64_t> numel((size_t)n, -1), raw_off((size_t)n);
-    for (const auto& gs : d->params) {
-        ParamJob q;
-        memset(&q, 0, sizeof(q));
-        q.dst = gs.offset;
-        auto plain = where.find(gs.name);
-        auto wg = where.find(gs.name + "_g"), wv = where.find(gs.name + "_v");
-        if (plain != where.end()) {
-            q.v = data[plain->second];
-            q.cols = (int)gs.numel;
-            q.rows = (int)((gs.numel + 1023) / 1024);
-            q.dv = plain->second;
-            numel[(size_t)plain->second] = gs.numel;
-        } else if (wg != where.end() && wv != where.end() && gs.shape.size() >= 2) {
-            q.v = data[wv->second];
-            q.g = data[wg->second];
-            q.rows = (int)gs.shape[0];
-            q.cols = (int)(gs.numel / gs.shape[0]);
-            q.dv = wv->second;
-            q.dg = wg->second;
-            numel[(size_t)wv->second] = gs.numel;
-            numel[(size_t)wg->second] = gs.shape[0];
-        } else {
-            return fail(HIFICAR_E_INVALID, "parameter '%s' (or its weight_g / weight_v pair) is missing", gs.name.c_str());
-        }
-        jobs.push_back(q);
-    }
-    {   // buckets = sub-discriminators: d->params is in state_dict order, so a sub's jobs are one contiguous range
-        const int nb = (int)d->subs.size();
-        std::vector<int> lo((size_t)nb + 1, (int)jobs.size()), raw_bucket((size_t)n, 0);
-        for (size_t j = 0; j < jobs.size(); ++j) {
-            int b = -1;
-            for (int si = 0; si < nb && b < 0; ++si)
-                for (const DiscLayer& L : d->subs[(size_t)si].layers)
-                    if (d->params[j].name.compare(0, L.base.size() + 1, L.base + ".") == 0) {
-                        b = si;
-                        break;
-                    }
-            if (b < 0) return fail(HIFICAR_E_INVALID, "internal: parameter '%s' belongs to no sub-discriminator", d->params[j].name.c_str());
-            lo[(size_t)b] = std::min(lo[(size_t)b], (int)j);
-            raw_bucket[(size_t)jobs[j].dv] = b;
-            if (jobs[j].g) raw_bucket[(size_t)jobs[j].dg] = b;
-        }
-        for (int b = nb - 1; b >= 0; --b) lo[(size_t)b] = std::min(lo[(size_t)b], lo[(size_t)b + 1]);
-        for (size_t j = 0; j + 1 < jobs.size(); ++j)
-            if (raw_bucket[(size_t)jobs[j].dv] > raw_bucket[(size_t)jobs[j + 1].dv])
-                return fail(HIFICAR_E_INVALID, "internal: sub-discriminator parameters are not contiguous");
-        d->bucket_job_lo = lo;
-        d->raw_bucket = raw_bucket;
-    }
-    int64_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        if (numel[(size_t)i] < 0) return fail(HIFICAR_E_INVALID, "unexpected parameter '%s' for this discriminator", names[i]);
-        raw_off[(size_t)i] = off;
-        off += (numel[(size_t)i] + 3) & ~(int64_t)3;
-    }
-    for (ParamJob& q : jobs) {
-        q.dv = raw_off[(size_t)q.dv];
-        if (q.g) q.dg = raw_off[(size_t)q.dg];
-    }
-    const bool same = d->have_params && jobs.size() == d->param_jobs.size() && raw_names == d->raw_names &&
-                      memcmp(jobs.data(), d->param_jobs.data(), jobs.size() * sizeof(ParamJob)) == 0;
-    if (!same) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        d->param_jobs = jobs;
-        d->raw_names = raw_names;
-        d->raw_total = off;
-        int wgs = 0;
-        for (size_t j = 0; j < jobs.size(); ++j) {
-            d->pin_param_jobs[j] = jobs[j];
-            d->pin_param_start[j] = wgs;
-            wgs += jobs[j].rows;
-        }
-        d->pin_param_start[jobs.size()] = wgs;
-        d->n_param_wgs = wgs;
-        HIP_TRY(hipMemcpyAsync(d->d_param_jobs, d->pin_param_jobs, jobs.size() * sizeof(ParamJob), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d->d_param_start, d->pin_param_start, (jobs.size() + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-        d->have_params = true;
-    }
-    {
-        ProfScope prof(h, stream, "param_gather_kernel", 0.0, 8.0 * d->grad_total);
-        hipLaunchKernelGGL(param_gather_kernel, dim3(d->n_param_wgs), dim3(256), 0, stream, d->d_param_jobs, d->d_param_start,
-                           (int)d->param_jobs.size(), d->d_folded);
-    }
-    HIP_TRY(hipGetLastError());
-    {
-        ProfScope prof(h, stream, "pack_all_kernel", 0.0, 12.0 * d->grad_total);
-        hipLaunchKernelGGL(pack_all_kernel, dim3(d->n_pack_wgs), dim3(256), 0, stream, d->d_pack_jobs, d->d_pack_start, d->n_pack_jobs);
-    }
-    HIP_TRY(hipGetLastError());
-    return HIFICAR_OK;
+    return raw_set_parameters(d->eng, d->raw, "hificar_disc_set_parameters_device", names, data, n, static_cast<hipStream_t>(stream_),
+                              [d](std::vector<PackParams>& jobs) { return disc_pack_jobs(d, jobs); });
 }
 
 extern "C" int hificar_disc_weight_norm_backward(hificar_disc* d, const float* grads, float* raw_grads, void* stream_) {
     if (!d || !grads || !raw_grads) return fail(HIFICAR_E_INVALID, "hificar_disc_weight_norm_backward: null argument");
-    if (!d->have_params) return fail(HIFICAR_E_STATE, "hificar_disc_weight_norm_backward needs hificar_disc_set_parameters_device first");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc;
-    if ((rc = enter_stream(d->eng, stream)) != HIFICAR_OK) return rc;
-    ProfScope prof(d->eng, stream, "wn_backward_kernel", 0.0, 16.0 * d->grad_total);
-    hipLaunchKernelGGL(wn_backward_kernel, dim3(d->n_param_wgs), dim3(256), 0, stream, d->d_param_jobs, d->d_param_start,
-                       (int)d->param_jobs.size(), grads, raw_grads, 0, d->grad_scale);
-    HIP_TRY(hipGetLastError());
-    return HIFICAR_OK;
+    if (!d->raw.have_params) return fail(HIFICAR_E_STATE, "hificar_disc_weight_norm_backward needs hificar_disc_set_parameters_device first");
+    return raw_weight_norm_backward(d->eng, d->raw, grads, raw_grads, -1, d->grad_scale, static_cast<hipStream_t>(stream_));
 }
 
 // Two switches for the criterion's backward (include/hificar.h): the second pass of a discriminator update adds its parameter gradients
@@ -646,42 +492,32 @@ extern "C" int hificar_disc_set_grad_scale(hificar_disc* d, const float* scale_d
 // ---- gradient buckets: one per sub-discriminator (include/hificar.h: "data-parallel training") ----
 extern "C" int hificar_disc_grad_bucket_count(const hificar_disc* d) { return d ? (int)d->subs.size() : -1; }
 
-extern "C" int hificar_disc_raw_param_bucket(const hificar_disc* d, int i) {
-    if (!d || i < 0 || i >= (int)d->raw_bucket.size()) return -1;
-    return d->raw_bucket[(size_t)i];
-}
+extern "C" int hificar_disc_raw_param_bucket(const hificar_disc* d, int i) { return raw_param_bucket(d ? &d->raw : nullptr, i); }
 
 // the bucket's slice of the FOLDED gradient buffer (hificar_disc_backward's `grads`): floats [*offset, *offset + *numel)
 extern "C" int hificar_disc_bucket_folded_range(const hificar_disc* d, int bucket, int64_t* offset, int64_t* numel) {
-    if (!d || !offset || !numel || !d->have_params || bucket < 0 || bucket >= (int)d->subs.size())
+    if (!d || !offset || !numel || !d->raw.have_params || bucket < 0 || bucket >= (int)d->subs.size())
         return fail(HIFICAR_E_INVALID, "hificar_disc_bucket_folded_range: bad argument (or no parameters handed over yet)");
-    const int lo = d->bucket_job_lo[(size_t)bucket], hi = d->bucket_job_lo[(size_t)bucket + 1];
-    *offset = lo < (int)d->params.size() ? d->params[(size_t)lo].offset : d->grad_total;
-    *numel = (hi < (int)d->params.size() ? d->params[(size_t)hi].offset : d->grad_total) - *offset;
+    const RawParamSet& r = d->raw;
+    const int lo = r.bucket_job_lo[(size_t)bucket], hi = r.bucket_job_lo[(size_t)bucket + 1];
+    *offset = lo < (int)r.slots.size() ? r.slots[(size_t)lo].offset : r.total;
+    *numel = (hi < (int)r.slots.size() ? r.slots[(size_t)hi].offset : r.total) - *offset;
     return HIFICAR_OK;
 }
 
 extern "C" int hificar_disc_set_bucket_callback(hificar_disc* d, hificar_bucket_fn fn, void* user) {
     if (!d) return fail(HIFICAR_E_INVALID, "null handle");
-    d->bucket_fn = fn;
-    d->bucket_user = user;
+    d->raw.bucket_fn = fn;
+    d->raw.bucket_user = user;
     return HIFICAR_OK;
 }
 
 // hificar_disc_weight_norm_backward for ONE sub-discriminator; called from the bucket callback on the stream it hands over.
 extern "C" int hificar_disc_weight_norm_backward_bucket(hificar_disc* d, const float* grads, float* raw_grads, int bucket, void* stream_) {
     if (!d || !grads || !raw_grads) return fail(HIFICAR_E_INVALID, "hificar_disc_weight_norm_backward_bucket: null argument");
-    if (!d->have_params) return fail(HIFICAR_E_STATE, "hificar_disc_weight_norm_backward_bucket needs hificar_disc_set_parameters_device first");
-    if (bucket < 0 || bucket >= (int)d->subs.size()) return fail(HIFICAR_E_INVALID, "bucket %d out of range", bucket);
-    const int lo = d->bucket_job_lo[(size_t)bucket], hi = d->bucket_job_lo[(size_t)bucket + 1];
-    if (hi <= lo) return HIFICAR_OK;
-    const int wg0 = d->pin_param_start[lo], wg1 = d->pin_param_start[hi];
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ProfScope prof(d->eng, stream, "wn_backward_kernel", 0.0, 0.0);
-    hipLaunchKernelGGL(wn_backward_kernel, dim3(wg1 - wg0), dim3(256), 0, stream, d->d_param_jobs, d->d_param_start, (int)d->param_jobs.size(), grads,
-                       raw_grads, wg0, d->grad_scale);
-    HIP_TRY(hipGetLastError());
-    return HIFICAR_OK;
+    if (!d->raw.have_params) return fail(HIFICAR_E_STATE, "hificar_disc_weight_norm_backward_bucket needs hificar_disc_set_parameters_device first");
+    if (bucket < 0 || bucket >= d->raw.n_buckets) return fail(HIFICAR_E_INVALID, "bucket %d out of range", bucket);
+    return raw_weight_norm_backward(d->eng, d->raw, grads, raw_grads, bucket, d->grad_scale, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" size_t hificar_disc_tape_bytes(const hificar_disc* d, int B, int T) {
@@ -749,7 +585,7 @@ static unsigned ew_blocks(const hificar_handle* h, long long n) { return (unsign
 // x (B, 1, T) -> every layer output of every sub-discriminator, kept in `tape` (hificar_disc_output_info locates them).
 extern "C" int hificar_disc_forward(hificar_disc* d, const float* x, int B, int T, void* tape_, size_t tape_bytes, void* stream_) {
     if (!d || !x || !tape_) return fail(HIFICAR_E_INVALID, "hificar_disc_forward: null argument");
-    if (!d->have_params) return fail(HIFICAR_E_STATE, "hificar_disc_forward needs hificar_disc_set_parameters_device first");
+    if (!d->raw.have_params) return fail(HIFICAR_E_STATE, "hificar_disc_forward needs hificar_disc_set_parameters_device first");
     if (B < 1 || T < 2) return fail(HIFICAR_E_INVALID, "hificar_disc_forward: B=%d T=%d", B, T);
     for (const DiscSub& s : d->subs)
         if (s.period > 0 && (s.period - T % s.period) % s.period >= T)
@@ -886,7 +722,7 @@ extern "C" int hificar_disc_forward(hificar_disc* d, const float* x, int B, int 
 extern "C" int hificar_disc_backward(hificar_disc* d, const float* const* douts, int B, int T, const void* tape_, size_t tape_bytes, float* grads,
                                      float* dx, void* ws_, size_t ws_bytes, void* stream_) {
     if (!d || !douts || !tape_ || !ws_) return fail(HIFICAR_E_INVALID, "hificar_disc_backward: null argument");
-    if (!d->have_params) return fail(HIFICAR_E_STATE, "hificar_disc_backward needs hificar_disc_set_parameters_device first");
+    if (!d->raw.have_params) return fail(HIFICAR_E_STATE, "hificar_disc_backward needs hificar_disc_set_parameters_device first");
     const DiscPlan p = disc_plan(d, B, T);
     if (tape_bytes < p.tape_floats * sizeof(float) || ws_bytes < p.ws_floats * sizeof(float))
         return fail(HIFICAR_E_WORKSPACE, "discriminator backward: tape / workspace too small");
@@ -982,8 +818,8 @@ extern "C" int hificar_disc_backward(hificar_disc* d, const float* const* douts,
             }
             // ---- weight / bias gradients
             if (grads) {
-                float* dW = grads + d->params[(size_t)d->param_index.at(L.base + ".weight")].offset;
-                float* dB = L.has_bias ? grads + d->params[(size_t)d->param_index.at(L.base + ".bias")].offset : nullptr;
+                float* dW = grads + d->raw.offset(L.base + ".weight");
+                float* dB = L.has_bias ? grads + d->raw.offset(L.base + ".bias") : nullptr;
                 const DiscGroup& G = L.g[0];
                 WgradJob job;
                 job.L = &G.F;
@@ -1046,7 +882,7 @@ extern "C" int hificar_disc_backward(hificar_disc* d, const float* const* douts,
             }
         }
         if ((rc = flush_reduce(h, pending, stream)) != HIFICAR_OK) return rc;  // every weight / bias gradient reduction of this sub-discriminator
-        if (grads && d->bucket_fn) d->bucket_fn((int)si, stream, d->bucket_user);  // this sub-discriminator's parameter gradients are enqueued
+        if (grads && d->raw.bucket_fn) d->raw.bucket_fn((int)si, stream, d->raw.bucket_user);  // this sub-discriminator's parameter gradients are enqueued
         if (!dx) continue;
         // ---- gradient of this sub-discriminator's input signal
         const DiscLayer& L0 = s.layers[0];

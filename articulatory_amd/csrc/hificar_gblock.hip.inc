@@ -292,7 +292,7 @@ __global__ __launch_bounds__(256) static void gblock_down_kernel(const float* __
 static int gblock_backward(hificar_handle* h, TrainState* ts, const Tape& tp, BwdWs& bw, DeferredReduce& pending, const float* dout, const float* out,
                            const int32_t* spk_id, int B, int T, float* grads, float* dc, float* dar, hipStream_t stream) {
     int rc;
-    auto G = [&](const std::string& name) { return grads + ts->grad_off.at(name); };
+    auto G = [&](const std::string& name) { return grads + ts->raw.offset(name); };
     Ragged rg;  // dense
     rg.frames = T;
     const int nb = (int)h->gb.size();
@@ -349,13 +349,13 @@ static int gblock_backward(hificar_handle* h, TrainState* ts, const Tape& tp, Bw
             rows = rows_in;
         }
         cur ^= 1;
-        if (ts->bucket_fn) {  // every gradient of GBlock i (and, for the last one, the output conv's) is enqueued: bucket done
+        if (ts->raw.bucket_fn) {  // every gradient of GBlock i (and, for the last one, the output conv's) is enqueued: bucket done
             if ((rc = flush_reduce(h, pending, stream)) != HIFICAR_OK) return rc;
-            ts->bucket_fn(nb - 1 - i, stream, ts->bucket_user);
+            ts->raw.bucket_fn(nb - 1 - i, stream, ts->raw.bucket_user);
         }
     }
     if ((rc = bwd_front(h, ts, tp, bw, grads, dc, dar, spk_id, nullptr, B, T, stream)) != HIFICAR_OK) return rc;
     if ((rc = flush_reduce(h, pending, stream)) != HIFICAR_OK) return rc;
-    if (ts->bucket_fn) ts->bucket_fn(nb, stream, ts->bucket_user);  // the "front" bucket
+    if (ts->raw.bucket_fn) ts->raw.bucket_fn(nb, stream, ts->raw.bucket_user);  // the "front" bucket
     return HIFICAR_OK;
 }

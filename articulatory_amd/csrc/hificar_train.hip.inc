@@ -2,22 +2,22 @@
 // backward pass.  Reference: the generator half of articulatory/bin/train.py:241-440 (PyTorch autograd through
 // articulatory/models/hifigan.py:198-239).  Kernels: hificar_backward.hip.h.  Exact-fp32 arithmetic only.
 
-struct TrainState {
-    // data-gradient layers (a Conv1d each) of every forward conv, in the forward lists' order
-    ConvLayer dg_input;
-    std::vector<ConvLayer> dg_ups, dg_c1, dg_c2;
-    std::vector<ConvLayer> dg_gb;  // GBlockGenerator: [block][c1a, c1b, res, c2a, c2b]
-    int up_jmin[HIFICAR_MAX_STAGES] = {};
-    std::map<std::string, std::pair<ConvLayer*, ConvLayer*>> by_name;  // "input_conv" -> (forward layer, its dgrad layer)
-    struct GradSlot {
+// The raw parameters of one engine (the generator's TrainState, the discriminators' hificar_disc) and their batched hand-over
+// (raw_set_parameters): the folded master copy in the gradient layout, the static table of every pack (sources inside the master copy) and
+// the per-call table of fold / copy jobs (re-sent when a pointer moves).  Gradient buckets (data-parallel training: a bucket's gradients
+// are complete, and can be all-reduced, while the rest of the backward pass still runs): every folded slot's bucket is fixed when the
+// slot is added, and the ParamJob table is ordered by bucket.
+struct RawParamSet {
+    struct Slot {
         std::string name;
+        std::vector<int64_t> shape;
         int64_t offset, numel;
+        int bucket;
     };
-    std::vector<GradSlot> grads;  // folded parameters in the order of hificar_handle::expected (sorted by name)
-    std::map<std::string, int64_t> grad_off;
-    int64_t grad_total = 0;
-    // batched hand-over of the raw parameters (hificar_set_parameters_device): the folded master copy in the gradient layout, the static
-    // table of every pack (sources inside the master copy) and the per-call table of fold / copy jobs (re-sent when a pointer moves)
+    std::vector<Slot> slots;           // folded parameters in master-copy (= folded gradient buffer) order
+    std::map<std::string, int> index;  // name -> slot
+    int64_t total = 0;                 // floats of the master copy
+    int n_buckets = 0;
     float* d_folded = nullptr;
     PackParams* d_pack_jobs = nullptr;
     int* d_pack_start = nullptr;
@@ -30,13 +30,41 @@ struct TrainState {
     std::vector<std::string> raw_names;
     int n_param_wgs = 0;
     int64_t raw_total = 0;
-    // gradient buckets (data-parallel training: a bucket's gradients are complete, and can be all-reduced, while the rest of the backward
-    // pass still runs).  Bucket b < n_stages: the ResBlocks of stage n_stages - 1 - b (+ the output conv and the phoneme head in bucket 0);
-    // bucket n_stages ("front"): input conv, upsamplers, PastFCEncoder, conditioning tensors.  The ParamJob table is ordered by bucket.
+    bool have_params = false;
+    std::vector<int> job_slot;        // [job] its slot (slots stably sorted by bucket)
     std::vector<int> bucket_job_lo;   // [bucket] first job; bucket_job_lo[n_buckets] = number of jobs
     std::vector<int> raw_bucket;      // [raw parameter of the last hand-over] its bucket
     hificar_bucket_fn bucket_fn = nullptr;
     void* bucket_user = nullptr;
+
+    RawParamSet() = default;
+    RawParamSet(const RawParamSet&) = delete;
+    RawParamSet& operator=(const RawParamSet&) = delete;
+    ~RawParamSet() {
+        if (pin_param_jobs) (void)hipHostFree(pin_param_jobs);
+        if (pin_param_start) (void)hipHostFree(pin_param_start);
+    }
+    void add(const std::string& name, const std::vector<int64_t>& shape, int bucket) {
+        int64_t n = 1;
+        for (auto v : shape) n *= v;
+        index[name] = (int)slots.size();
+        slots.push_back({name, shape, total, n, bucket});
+        total += (n + 3) & ~(int64_t)3;  // 16-byte aligned slots
+    }
+    int64_t offset(const std::string& name) const { return slots[(size_t)index.at(name)].offset; }
+};
+
+struct TrainState {
+    // data-gradient layers (a Conv1d each) of every forward conv, in the forward lists' order
+    ConvLayer dg_input;
+    std::vector<ConvLayer> dg_ups, dg_c1, dg_c2;
+    std::vector<ConvLayer> dg_gb;  // GBlockGenerator: [block][c1a, c1b, res, c2a, c2b]
+    int up_jmin[HIFICAR_MAX_STAGES] = {};
+    std::map<std::string, std::pair<ConvLayer*, ConvLayer*>> by_name;  // "input_conv" -> (forward layer, its dgrad layer)
+    // folded parameters in the order of hificar_handle::expected (sorted by name).  Bucket b < n_stages: the ResBlocks of stage
+    // n_stages - 1 - b (+ the output conv and the phoneme head in bucket 0); bucket n_stages ("front"): input conv, upsamplers,
+    // PastFCEncoder, conditioning tensors (gen_bucket_of)
+    RawParamSet raw;
 };
 
 // number of gradient buckets of the generator: one per stage (HiFi-GAN) / per GBlock, last first, + the "front" bucket
@@ -118,10 +146,6 @@ static int wgrad_setup() {
 }
 
 static void train_free_impl(hificar_handle* h) {
-    if (TrainState* ts = train_state(h)) {
-        if (ts->pin_param_jobs) (void)hipHostFree(ts->pin_param_jobs);
-        if (ts->pin_param_start) (void)hipHostFree(ts->pin_param_start);
-    }
     delete train_state(h);
     h->train = nullptr;
 }
@@ -161,13 +185,8 @@ static int train_init(hificar_handle* h) {
             ts->by_name[fw[q]->name] = {fw[q], &ts->dg_gb[i * 5 + q]};
         }
     }
-    for (auto& kv : h->expected) {
-        int64_t n = 1;
-        for (auto v : kv.second) n *= v;
-        ts->grads.push_back({kv.first, ts->grad_total, n});
-        ts->grad_off[kv.first] = ts->grad_total;
-        ts->grad_total += (n + 3) & ~(int64_t)3;  // 16-byte aligned slots
-    }
+    for (auto& kv : h->expected) ts->raw.add(kv.first, kv.second, gen_bucket_of(h, kv.first));
+    ts->raw.n_buckets = gen_bucket_count(h);
     if (!h->d_out_bias) {
         void* p = nullptr;
         HIP_TRY(hipMalloc(&p, 256));
@@ -344,163 +363,180 @@ static int device_table(hificar_handle* h, const std::vector<T>& host, T** dev) 
     return HIFICAR_OK;
 }
 
-// EVERY parameter in its RAW form from device memory, in one call (two kernel launches): names[i] is a reference state_dict key —
-// "<conv>.weight_g" + "<conv>.weight_v" for a weight-normed conv (hifigan.py:268-278), "<conv>.weight" for a plain one, biases, the
-// PastFCEncoder's Linear tensors.  The weight norm is folded on the device into a master copy, every pack is refreshed from it.
-// The raw-gradient buffer of hificar_weight_norm_backward has one slot per entry, in this order, each rounded up to 4 floats.
+// First hand-over of a raw-parameter set: the master copy, the static pack table (`packs` appends every pack of the engine, its sources
+// inside r.d_folded), the job order (slots stably sorted by bucket) and the job tables with their pinned mirrors.
+static int raw_setup(hificar_handle* h, RawParamSet& r, const std::function<int(std::vector<PackParams>&)>& packs) {
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, (size_t)r.total * sizeof(float)));
+    h->allocs.push_back(p);
+    r.d_folded = static_cast<float*>(p);
+    std::vector<PackParams> jobs;
+    int rc;
+    if ((rc = packs(jobs)) != HIFICAR_OK) return rc;
+    std::vector<int> start(jobs.size() + 1, 0);
+    for (size_t j = 0; j < jobs.size(); ++j)
+        start[j + 1] = start[j] + (int)std::max<long long>(1, std::min<long long>((jobs[j].total + 1023) / 1024, 256));
+    r.n_pack_jobs = (int)jobs.size();
+    r.n_pack_wgs = start.back();
+    if ((rc = device_table(h, jobs, &r.d_pack_jobs)) != HIFICAR_OK) return rc;
+    if ((rc = device_table(h, start, &r.d_pack_start)) != HIFICAR_OK) return rc;
+    const size_t cap = r.slots.size();
+    r.job_slot.resize(cap);
+    for (size_t j = 0; j < cap; ++j) r.job_slot[j] = (int)j;
+    std::stable_sort(r.job_slot.begin(), r.job_slot.end(), [&](int a, int b) { return r.slots[(size_t)a].bucket < r.slots[(size_t)b].bucket; });
+    r.bucket_job_lo.assign((size_t)r.n_buckets + 1, (int)cap);
+    for (size_t k = cap; k-- > 0;) r.bucket_job_lo[(size_t)r.slots[(size_t)r.job_slot[k]].bucket] = (int)k;
+    for (int b = r.n_buckets - 1; b >= 0; --b) r.bucket_job_lo[(size_t)b] = std::min(r.bucket_job_lo[(size_t)b], r.bucket_job_lo[(size_t)b + 1]);
+    HIP_TRY(hipMalloc(&p, cap * sizeof(ParamJob)));
+    h->allocs.push_back(p);
+    r.d_param_jobs = static_cast<ParamJob*>(p);
+    HIP_TRY(hipMalloc(&p, (cap + 1) * sizeof(int)));
+    h->allocs.push_back(p);
+    r.d_param_start = static_cast<int*>(p);
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r.pin_param_jobs), cap * sizeof(ParamJob), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r.pin_param_start), (cap + 1) * sizeof(int), hipHostMallocDefault));
+    return HIFICAR_OK;
+}
+
+// EVERY raw parameter of a set from device memory, in one call (two kernel launches): names[i] is a reference state_dict key —
+// "<conv>.weight_g" + "<conv>.weight_v" for a weight-normed conv, "<conv>.weight" for a plain one, biases, Linear tensors.  The weight
+// norm is folded on the device into the master copy, every pack is refreshed from it.  The raw-gradient buffer of
+// raw_weight_norm_backward has one slot per entry, in this order, each rounded up to 4 floats.  `fn` names the entry point in messages.
+static int raw_set_parameters(hificar_handle* h, RawParamSet& r, const char* fn, const char* const* names, const float* const* data, int n,
+                              hipStream_t stream, const std::function<int(std::vector<PackParams>&)>& packs) {
+    int rc;
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    if (!r.d_folded && (rc = raw_setup(h, r, packs)) != HIFICAR_OK) return rc;
+    // raw slots in the caller's order; one job per folded slot
+    std::map<std::string, int> where;
+    std::vector<std::string> raw_names((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (!names[i] || !data[i]) return fail(HIFICAR_E_INVALID, "%s: entry %d is null", fn, i);
+        raw_names[(size_t)i] = names[i];
+        if (!where.emplace(raw_names[(size_t)i], i).second) return fail(HIFICAR_E_INVALID, "%s: parameter '%s' given twice", fn, names[i]);
+    }
+    std::vector<ParamJob> slot_job;
+    std::vector<int64_t> numel((size_t)n, -1), raw_off((size_t)n);
+    std::vector<int> raw_bucket((size_t)n);
+    for (const RawParamSet::Slot& s : r.slots) {
+        ParamJob q;
+        memset(&q, 0, sizeof(q));
+        q.dst = s.offset;
+        auto plain = where.find(s.name);
+        auto wg = where.find(s.name + "_g"), wv = where.find(s.name + "_v");
+        if (plain != where.end()) {
+            q.v = data[plain->second];
+            q.cols = (int)s.numel;
+            q.rows = (int)((s.numel + 1023) / 1024);
+            q.dv = plain->second;  // (raw index for now)
+            numel[(size_t)plain->second] = s.numel;
+        } else if (wg != where.end() && wv != where.end() && s.shape.size() >= 2) {
+            q.v = data[wv->second];
+            q.g = data[wg->second];
+            q.rows = (int)s.shape[0];
+            q.cols = (int)(s.numel / s.shape[0]);
+            q.dv = wv->second;
+            q.dg = wg->second;
+            numel[(size_t)wv->second] = s.numel;
+            numel[(size_t)wg->second] = s.shape[0];
+            raw_bucket[(size_t)q.dg] = s.bucket;
+        } else {
+            return fail(HIFICAR_E_INVALID, "%s: parameter '%s' (or its weight_g / weight_v pair) is missing", fn, s.name.c_str());
+        }
+        raw_bucket[(size_t)q.dv] = s.bucket;
+        slot_job.push_back(q);
+    }
+    int64_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        if (numel[(size_t)i] < 0) return fail(HIFICAR_E_INVALID, "%s: unexpected parameter '%s'", fn, names[i]);
+        raw_off[(size_t)i] = off;
+        off += (numel[(size_t)i] + 3) & ~(int64_t)3;
+    }
+    std::vector<ParamJob> jobs(slot_job.size());  // bucket order
+    for (size_t k = 0; k < jobs.size(); ++k) {
+        ParamJob& q = jobs[k] = slot_job[(size_t)r.job_slot[k]];
+        q.dv = raw_off[(size_t)q.dv];
+        if (q.g) q.dg = raw_off[(size_t)q.dg];
+    }
+    r.raw_bucket = raw_bucket;
+    const bool same = r.have_params && jobs.size() == r.param_jobs.size() && raw_names == r.raw_names &&
+                      memcmp(jobs.data(), r.param_jobs.data(), jobs.size() * sizeof(ParamJob)) == 0;
+    if (!same) {  // first call, or a parameter's storage moved: re-send the table (the pinned mirror may still be in flight)
+        HIP_TRY(hipStreamSynchronize(stream));
+        r.param_jobs = jobs;
+        r.raw_names = raw_names;
+        r.raw_total = off;
+        int wgs = 0;
+        for (size_t j = 0; j < jobs.size(); ++j) {
+            r.pin_param_jobs[j] = jobs[j];
+            r.pin_param_start[j] = wgs;
+            wgs += jobs[j].rows;
+        }
+        r.pin_param_start[jobs.size()] = wgs;
+        r.n_param_wgs = wgs;
+        HIP_TRY(hipMemcpyAsync(r.d_param_jobs, r.pin_param_jobs, jobs.size() * sizeof(ParamJob), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(r.d_param_start, r.pin_param_start, (jobs.size() + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+        r.have_params = true;
+    }
+    {
+        ProfScope prof(h, stream, "param_gather_kernel", 0.0, 8.0 * r.total);
+        hipLaunchKernelGGL(param_gather_kernel, dim3(r.n_param_wgs), dim3(256), 0, stream, r.d_param_jobs, r.d_param_start,
+                           (int)r.param_jobs.size(), r.d_folded);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        ProfScope prof(h, stream, "pack_all_kernel", 0.0, 12.0 * r.total);
+        hipLaunchKernelGGL(pack_all_kernel, dim3(r.n_pack_wgs), dim3(256), 0, stream, r.d_pack_jobs, r.d_pack_start, r.n_pack_jobs);
+    }
+    HIP_TRY(hipGetLastError());
+    return HIFICAR_OK;
+}
+
+// Folded gradients -> gradients of the raw parameters last handed over, in that call's order (weight_g: dim-0 floats, weight_v: the
+// weight's shape; every slot rounded up to 4 floats).  One launch: every job (bucket < 0), or the jobs of one bucket — meant to be called
+// from the bucket callback on the stream it hands over (no cross-stream ordering is added).  grad_scale: a device scalar, or null.
+// The caller checks r.have_params and the bucket's range.
+static int raw_weight_norm_backward(hificar_handle* h, const RawParamSet& r, const float* grads, float* raw_grads, int bucket,
+                                    const float* grad_scale, hipStream_t stream) {
+    const bool all = bucket < 0;
+    int rc;
+    if (all && (rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    const int lo = all ? 0 : r.bucket_job_lo[(size_t)bucket], hi = all ? (int)r.param_jobs.size() : r.bucket_job_lo[(size_t)bucket + 1];
+    if (!all && hi <= lo) return HIFICAR_OK;
+    const int wg0 = r.pin_param_start[lo], wg1 = r.pin_param_start[hi];
+    ProfScope prof(h, stream, "wn_backward_kernel", 0.0, all ? 16.0 * r.total : 0.0);
+    hipLaunchKernelGGL(wn_backward_kernel, dim3(wg1 - wg0), dim3(256), 0, stream, r.d_param_jobs, r.d_param_start, (int)r.param_jobs.size(),
+                       grads, raw_grads, wg0, grad_scale);
+    HIP_TRY(hipGetLastError());
+    return HIFICAR_OK;
+}
+
+static int raw_param_bucket(const RawParamSet* r, int i) { return r && i >= 0 && i < (int)r->raw_bucket.size() ? r->raw_bucket[(size_t)i] : -1; }
+
+// The generator's raw parameters (hifigan.py:268-278 for the weight norm; the PastFCEncoder and the conditioning tensors included).
 extern "C" int hificar_set_parameters_device(hificar_handle* h, const char* const* names, const float* const* data, int n, void* stream_) {
     if (!h || !names || !data || n < 1) return fail(HIFICAR_E_INVALID, "hificar_set_parameters_device: null argument");
     int rc = train_init(h);
     if (rc != HIFICAR_OK) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
-    TrainState* ts = train_state(h);
-    if (!ts->d_folded) {  // first call: the master copy and the static pack table
-        void* p = nullptr;
-        HIP_TRY(hipMalloc(&p, (size_t)ts->grad_total * sizeof(float)));
-        h->allocs.push_back(p);
-        ts->d_folded = static_cast<float*>(p);
-        std::vector<PackParams> jobs;
-        for (const auto& gs : ts->grads)
-            if ((rc = pack_jobs_for(h, gs.name, ts->d_folded + gs.offset, jobs)) != HIFICAR_OK) return rc;
-        std::vector<int> start(jobs.size() + 1, 0);
-        for (size_t j = 0; j < jobs.size(); ++j)
-            start[j + 1] = start[j] + (int)std::max<long long>(1, std::min<long long>((jobs[j].total + 1023) / 1024, 256));
-        ts->n_pack_jobs = (int)jobs.size();
-        ts->n_pack_wgs = start.back();
-        if ((rc = device_table(h, jobs, &ts->d_pack_jobs)) != HIFICAR_OK) return rc;
-        if ((rc = device_table(h, start, &ts->d_pack_start)) != HIFICAR_OK) return rc;
-        const size_t cap = ts->grads.size();
-        HIP_TRY(hipMalloc(&p, cap * sizeof(ParamJob)));
-        h->allocs.push_back(p);
-        ts->d_param_jobs = static_cast<ParamJob*>(p);
-        HIP_TRY(hipMalloc(&p, (cap + 1) * sizeof(int)));
-        h->allocs.push_back(p);
-        ts->d_param_start = static_cast<int*>(p);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ts->pin_param_jobs), cap * sizeof(ParamJob), hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ts->pin_param_start), (cap + 1) * sizeof(int), hipHostMallocDefault));
-    }
-    // raw slots in the caller's order; one job per folded tensor
-    std::map<std::string, int> where;
-    std::vector<int64_t> raw_off((size_t)n);
-    std::vector<std::string> raw_names((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        if (!names[i] || !data[i]) return fail(HIFICAR_E_INVALID, "hificar_set_parameters_device: entry %d is null", i);
-        raw_names[i] = names[i];
-        if (!where.emplace(raw_names[i], i).second) return fail(HIFICAR_E_INVALID, "parameter '%s' given twice", names[i]);
-    }
-    std::vector<ParamJob> jobs;
-    std::vector<int64_t> numel((size_t)n, -1);
-    for (const auto& gs : ts->grads) {
-        const std::vector<int64_t>& shape = h->expected.at(gs.name);
-        ParamJob q;
-        memset(&q, 0, sizeof(q));
-        q.dst = gs.offset;
-        auto plain = where.find(gs.name);
-        auto wg = where.find(gs.name + "_g"), wv = where.find(gs.name + "_v");
-        if (plain != where.end()) {
-            q.v = data[plain->second];
-            q.cols = (int)gs.numel;
-            q.rows = (int)((gs.numel + 1023) / 1024);
-            q.dv = plain->second;  // (slot index for now)
-            numel[plain->second] = gs.numel;
-        } else if (wg != where.end() && wv != where.end() && shape.size() >= 2) {
-            q.v = data[wv->second];
-            q.g = data[wg->second];
-            q.rows = (int)shape[0];
-            q.cols = (int)(gs.numel / shape[0]);
-            q.dv = wv->second;
-            q.dg = wg->second;
-            numel[wv->second] = gs.numel;
-            numel[wg->second] = shape[0];
-        } else {
-            return fail(HIFICAR_E_INVALID, "parameter '%s' (or its weight_g / weight_v pair) is missing", gs.name.c_str());
-        }
-        jobs.push_back(q);
-    }
-    int64_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        if (numel[i] < 0) return fail(HIFICAR_E_INVALID, "unexpected parameter '%s' for this configuration", names[i]);
-        raw_off[i] = off;
-        off += (numel[i] + 3) & ~(int64_t)3;
-    }
-    {   // order the jobs by gradient bucket (stable: name order inside a bucket) and note each raw parameter's bucket
-        const int nb = gen_bucket_count(h);
-        std::vector<int> jb(jobs.size()), order(jobs.size());
-        std::vector<int> raw_bucket((size_t)n, nb - 1);
-        for (size_t j = 0; j < jobs.size(); ++j) {
-            jb[j] = gen_bucket_of(h, ts->grads[j].name);
-            order[j] = (int)j;
-            raw_bucket[(size_t)jobs[j].dv] = jb[j];
-            if (jobs[j].g) raw_bucket[(size_t)jobs[j].dg] = jb[j];
-        }
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return jb[(size_t)a] < jb[(size_t)b]; });
-        std::vector<ParamJob> sorted(jobs.size());
-        std::vector<int> lo((size_t)nb + 1, (int)jobs.size());
-        for (size_t k = 0; k < order.size(); ++k) {
-            sorted[k] = jobs[(size_t)order[k]];
-            lo[(size_t)jb[(size_t)order[k]]] = std::min(lo[(size_t)jb[(size_t)order[k]]], (int)k);
-        }
-        for (int b = nb - 1; b >= 0; --b) lo[(size_t)b] = std::min(lo[(size_t)b], lo[(size_t)b + 1]);
-        jobs.swap(sorted);
-        ts->bucket_job_lo = lo;
-        ts->raw_bucket = raw_bucket;
-    }
-    for (ParamJob& q : jobs) {
-        q.dv = raw_off[(size_t)q.dv];
-        if (q.g) q.dg = raw_off[(size_t)q.dg];
-    }
-    const bool same = jobs.size() == ts->param_jobs.size() && raw_names == ts->raw_names &&
-                      memcmp(jobs.data(), ts->param_jobs.data(), jobs.size() * sizeof(ParamJob)) == 0;
-    if (!same) {  // first call, or a parameter's storage moved: re-send the table (the pinned mirror may still be in flight)
-        HIP_TRY(hipStreamSynchronize(stream));
-        ts->param_jobs = jobs;
-        ts->raw_names = raw_names;
-        ts->raw_total = off;
-        int wgs = 0;
-        for (size_t j = 0; j < jobs.size(); ++j) {
-            ts->pin_param_jobs[j] = jobs[j];
-            ts->pin_param_start[j] = wgs;
-            wgs += jobs[j].rows;
-        }
-        ts->pin_param_start[jobs.size()] = wgs;
-        ts->n_param_wgs = wgs;
-        HIP_TRY(hipMemcpyAsync(ts->d_param_jobs, ts->pin_param_jobs, jobs.size() * sizeof(ParamJob), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(ts->d_param_start, ts->pin_param_start, (jobs.size() + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-    }
-    {
-        ProfScope prof(h, stream, "param_gather_kernel", 0.0, 8.0 * ts->grad_total);
-        hipLaunchKernelGGL(param_gather_kernel, dim3(ts->n_param_wgs), dim3(256), 0, stream, ts->d_param_jobs, ts->d_param_start,
-                           (int)ts->param_jobs.size(), ts->d_folded);
-    }
-    HIP_TRY(hipGetLastError());
-    {
-        ProfScope prof(h, stream, "pack_all_kernel", 0.0, 12.0 * ts->grad_total);
-        hipLaunchKernelGGL(pack_all_kernel, dim3(ts->n_pack_wgs), dim3(256), 0, stream, ts->d_pack_jobs, ts->d_pack_start, ts->n_pack_jobs);
-    }
-    HIP_TRY(hipGetLastError());
-    return HIFICAR_OK;
+    RawParamSet& r = train_state(h)->raw;
+    auto packs = [&](std::vector<PackParams>& jobs) -> int {
+        for (const RawParamSet::Slot& s : r.slots)
+            if ((rc = pack_jobs_for(h, s.name, r.d_folded + s.offset, jobs)) != HIFICAR_OK) return rc;
+        return HIFICAR_OK;
+    };
+    return raw_set_parameters(h, r, "hificar_set_parameters_device", names, data, n, static_cast<hipStream_t>(stream_), packs);
 }
 
 extern "C" int64_t hificar_raw_grad_floats(const hificar_handle* h) {
     if (!h || !h->train) return -1;
-    return static_cast<const TrainState*>(h->train)->raw_total;
+    return static_cast<const TrainState*>(h->train)->raw.raw_total;
 }
 
-// Folded gradients (hificar_backward's buffer) -> gradients of the raw parameters last handed to hificar_set_parameters_device, in that
-// call's order (weight_g: dim-0 floats, weight_v: the weight's shape; every slot rounded up to 4 floats).  One launch.
 extern "C" int hificar_weight_norm_backward(hificar_handle* h, const float* grads, float* raw_grads, void* stream_) {
     if (!h || !grads || !raw_grads) return fail(HIFICAR_E_INVALID, "hificar_weight_norm_backward: null argument");
     TrainState* ts = train_state(h);
-    if (!ts || ts->param_jobs.empty()) return fail(HIFICAR_E_STATE, "hificar_weight_norm_backward needs hificar_set_parameters_device first");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc;
-    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
-    ProfScope prof(h, stream, "wn_backward_kernel", 0.0, 16.0 * ts->grad_total);
-    hipLaunchKernelGGL(wn_backward_kernel, dim3(ts->n_param_wgs), dim3(256), 0, stream, ts->d_param_jobs, ts->d_param_start,
-                       (int)ts->param_jobs.size(), grads, raw_grads, 0, nullptr);
-    HIP_TRY(hipGetLastError());
-    return HIFICAR_OK;
+    if (!ts || !ts->raw.have_params) return fail(HIFICAR_E_STATE, "hificar_weight_norm_backward needs hificar_set_parameters_device first");
+    return raw_weight_norm_backward(h, ts->raw, grads, raw_grads, -1, nullptr, static_cast<hipStream_t>(stream_));
 }
 
 // ---- gradient buckets (include/hificar.h: "data-parallel training") ----
@@ -511,35 +547,24 @@ extern "C" int hificar_grad_bucket_count(hificar_handle* h) {
 
 extern "C" int hificar_raw_param_bucket(const hificar_handle* h, int i) {
     const TrainState* ts = h ? static_cast<const TrainState*>(h->train) : nullptr;
-    if (!ts || i < 0 || i >= (int)ts->raw_bucket.size()) return -1;
-    return ts->raw_bucket[(size_t)i];
+    return raw_param_bucket(ts ? &ts->raw : nullptr, i);
 }
 
 extern "C" int hificar_set_bucket_callback(hificar_handle* h, hificar_bucket_fn fn, void* user) {
     if (!h) return fail(HIFICAR_E_INVALID, "null handle");
     int rc = train_init(h);
     if (rc != HIFICAR_OK) return rc;
-    train_state(h)->bucket_fn = fn;
-    train_state(h)->bucket_user = user;
+    train_state(h)->raw.bucket_fn = fn;
+    train_state(h)->raw.bucket_user = user;
     return HIFICAR_OK;
 }
 
-// hificar_weight_norm_backward for the parameters of ONE bucket.  Meant to be called from the bucket callback on the stream it hands over
-// (no cross-stream ordering is added here).
 extern "C" int hificar_weight_norm_backward_bucket(hificar_handle* h, const float* grads, float* raw_grads, int bucket, void* stream_) {
     if (!h || !grads || !raw_grads) return fail(HIFICAR_E_INVALID, "hificar_weight_norm_backward_bucket: null argument");
     TrainState* ts = train_state(h);
-    if (!ts || ts->param_jobs.empty()) return fail(HIFICAR_E_STATE, "hificar_weight_norm_backward_bucket needs hificar_set_parameters_device first");
-    if (bucket < 0 || bucket + 1 >= (int)ts->bucket_job_lo.size()) return fail(HIFICAR_E_INVALID, "bucket %d out of range", bucket);
-    const int lo = ts->bucket_job_lo[(size_t)bucket], hi = ts->bucket_job_lo[(size_t)bucket + 1];
-    if (hi <= lo) return HIFICAR_OK;
-    const int wg0 = ts->pin_param_start[lo], wg1 = ts->pin_param_start[hi];
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ProfScope prof(h, stream, "wn_backward_kernel", 0.0, 0.0);
-    hipLaunchKernelGGL(wn_backward_kernel, dim3(wg1 - wg0), dim3(256), 0, stream, ts->d_param_jobs, ts->d_param_start, (int)ts->param_jobs.size(), grads,
-                       raw_grads, wg0, nullptr);
-    HIP_TRY(hipGetLastError());
-    return HIFICAR_OK;
+    if (!ts || !ts->raw.have_params) return fail(HIFICAR_E_STATE, "hificar_weight_norm_backward_bucket needs hificar_set_parameters_device first");
+    if (bucket < 0 || bucket >= ts->raw.n_buckets) return fail(HIFICAR_E_INVALID, "bucket %d out of range", bucket);
+    return raw_weight_norm_backward(h, ts->raw, grads, raw_grads, bucket, nullptr, static_cast<hipStream_t>(stream_));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -855,7 +880,7 @@ extern "C" size_t hificar_backward_workspace_bytes(const hificar_handle* h, int 
 
 extern "C" int hificar_grad_count(hificar_handle* h) {
     if (!h || train_init(h) != HIFICAR_OK) return -1;
-    return (int)train_state(h)->grads.size();
+    return (int)train_state(h)->raw.slots.size();
 }
 
 extern "C" int hificar_grad_info(hificar_handle* h, int i, char* name96, int64_t* offset, int64_t* numel) {
@@ -863,16 +888,17 @@ extern "C" int hificar_grad_info(hificar_handle* h, int i, char* name96, int64_t
     int rc = train_init(h);
     if (rc != HIFICAR_OK) return rc;
     TrainState* ts = train_state(h);
-    if (i < 0 || i >= (int)ts->grads.size()) return fail(HIFICAR_E_INVALID, "gradient index %d out of range", i);
-    snprintf(name96, 96, "%s", ts->grads[i].name.c_str());
-    *offset = ts->grads[i].offset;
-    *numel = ts->grads[i].numel;
+    if (i < 0 || i >= (int)ts->raw.slots.size()) return fail(HIFICAR_E_INVALID, "gradient index %d out of range", i);
+    const RawParamSet::Slot& s = ts->raw.slots[(size_t)i];
+    snprintf(name96, 96, "%s", s.name.c_str());
+    *offset = s.offset;
+    *numel = s.numel;
     return HIFICAR_OK;
 }
 
 extern "C" int64_t hificar_grad_floats(hificar_handle* h) {
     if (!h || train_init(h) != HIFICAR_OK) return -1;
-    return train_state(h)->grad_total;
+    return train_state(h)->raw.total;
 }
 
 // Forward in training mode: as hificar_forward, and every activation the backward pass needs is kept in `tape`
@@ -1163,7 +1189,7 @@ static int launch_wgrad(hificar_handle* h, const ConvLayer& L, const float* g, i
 static int bwd_output_conv(hificar_handle* h, TrainState* ts, const Tape& tp, const BwdWs& bw, const float* dout, const float* out, int B, int T, int rows,
                            int nin, float* grads, hipStream_t stream) {
     const hificar_config& cfg = h->cfg;
-    auto G = [&](const std::string& name) { return grads + ts->grad_off.at(name); };
+    auto G = [&](const std::string& name) { return grads + ts->raw.offset(name); };
         OutBwdParams op;
         memset(&op, 0, sizeof(op));
         op.x0 = tp.fin[0];
@@ -1219,7 +1245,7 @@ static int bwd_output_conv(hificar_handle* h, TrainState* ts, const Tape& tp, co
 static int bwd_front(hificar_handle* h, TrainState* ts, const Tape& tp, const BwdWs& bw, float* grads, float* dc, float* dar, const int32_t* spk_id,
                      const int32_t* ph, int B, int T, hipStream_t stream) {
     const hificar_config& cfg = h->cfg;
-    auto G = [&](const std::string& name) { return grads + ts->grad_off.at(name); };
+    auto G = [&](const std::string& name) { return grads + ts->raw.offset(name); };
     const float slope = cfg.lrelu_slope;
     Ragged rg;  // dense
     rg.frames = T;
@@ -1329,7 +1355,7 @@ extern "C" int hificar_backward_cond(hificar_handle* h, const float* dout, const
     if (h->arch == 1) return gblock_backward(h, ts, tp, bw, pending, dout, out, spk_id, B, T, grads, dc, dar, stream);
     const int nbk = cfg.n_blocks;
     const float slope = cfg.lrelu_slope;
-    auto G = [&](const std::string& name) { return grads + ts->grad_off.at(name); };
+    auto G = [&](const std::string& name) { return grads + ts->raw.offset(name); };
     Ragged rg;  // dense
     rg.frames = T;
     int order[kMaxBlk];
@@ -1456,9 +1482,9 @@ extern "C" int hificar_backward_cond(hificar_handle* h, const float* dout, const
             for (int q = 0; q < n; ++q) dsrc[jn[q]] = dst1[q];
         }
         // every ResBlock gradient of stage i (and, for the last stage, the output conv's and the phoneme head's) is enqueued: bucket done
-        if (ts->bucket_fn) {
+        if (ts->raw.bucket_fn) {
             if ((rc = flush_reduce(h, pending, stream)) != HIFICAR_OK) return rc;
-            ts->bucket_fn(cfg.n_stages - 1 - i, stream, ts->bucket_user);
+            ts->raw.bucket_fn(cfg.n_stages - 1 - i, stream, ts->raw.bucket_user);
         }
         // gradient of the upsample output: the sum over the ResBlocks
         {
@@ -1485,7 +1511,7 @@ extern "C" int hificar_backward_cond(hificar_handle* h, const float* dout, const
     }
     if ((rc = bwd_front(h, ts, tp, bw, grads, dc, dar, spk_id, ph, B, T, stream)) != HIFICAR_OK) return rc;
     if ((rc = flush_reduce(h, pending, stream)) != HIFICAR_OK) return rc;
-    if (ts->bucket_fn) ts->bucket_fn(cfg.n_stages, stream, ts->bucket_user);  // the "front" bucket: everything else
+    if (ts->raw.bucket_fn) ts->raw.bucket_fn(cfg.n_stages, stream, ts->raw.bucket_user);  // the "front" bucket: everything else
     return HIFICAR_OK;
 }
 

@@ -9,12 +9,12 @@ conv group, ``[nseq][rows][pitch]`` with ``channels`` valid columns) without any
 ``articulatory_amd.losses`` consume (means over elements do not depend on the order of the elements)."""
 import ctypes
 
-import numpy as np
 import torch
 
 from .. import _native
+from ..utils.buckets import raw_grad_views
 from ..utils.synth import disc_params, period_disc_layers, scale_disc_layers
-from .hifigan import _ConvParams
+from .hifigan import _ConvParams, _send_parameters
 
 
 class DiscOutput:
@@ -41,23 +41,6 @@ class DiscOutput:
         return x.view(self.B, self.period, rows, C).permute(0, 3, 2, 1).contiguous()
 
 
-def _send(module, names, tensors, stream):
-    """Hand the raw parameters over (weight norm folded, every pack refreshed: ~0.9 ms for the 70 M-parameter discriminator) — skipped
-    when nothing changed since the last hand-over: the generator part and the discriminator part of one iteration see the same weights."""
-    sig = (names, tuple(t.data_ptr() for t in tensors), tuple(t._version for t in tensors))
-    if module.__dict__.get("_sent_sig") == sig and all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
-        return module.__dict__["_sent_held"]
-    held = [t.detach() if (t.dtype == torch.float32 and t.is_contiguous()) else t.detach().to(torch.float32).contiguous() for t in tensors]
-    cn = getattr(module, "_raw_cnames", None)
-    if cn is None or cn[0] != names:
-        cn = module._raw_cnames = (names, (ctypes.c_char_p * len(names))(*[n.encode() for n in names]))
-    ptrs = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
-    _native.check(module._lib.hificar_disc_set_parameters_device(module._handle, cn[1], ptrs, len(held), stream),
-                  "hificar_disc_set_parameters_device")
-    module.__dict__["_sent_sig"], module.__dict__["_sent_held"] = sig, held
-    return held
-
-
 class _DiscFunction(torch.autograd.Function):
     """Autograd node of the native discriminators: forward = hificar_disc_forward (every layer output, tape kept), backward =
     hificar_disc_backward + hificar_disc_weight_norm_backward.  Inputs after (module, x, names): the module's RAW parameters."""
@@ -70,7 +53,7 @@ class _DiscFunction(torch.autograd.Function):
         x = x.detach().to(torch.float32).contiguous()
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            held = _send(module, names, params, stream)
+            held = _send_parameters(module, "hificar_disc_set_parameters_device", names, params, stream)
             nbytes = int(lib.hificar_disc_tape_bytes(handle, B, T))
             tape = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device=dev)
             toff = ((-tape.data_ptr()) % 256) // 4
@@ -120,11 +103,7 @@ class _DiscFunction(torch.autograd.Function):
                     dist.all_reduce(raw, group=group)  # one bucket: every discriminator gradient (RCCL under "nccl")
                     if average:
                         raw.div_(dist.get_world_size(group))
-                off = 0
-                for i, shape in enumerate(ctx.shapes):
-                    n = int(np.prod(shape))
-                    gw[i] = raw[off:off + n].view(shape)
-                    off += (n + 3) & ~3
+                gw = raw_grad_views(raw, ctx.shapes)
         ctx.tape = ctx.held = ctx.params = None
         return (None, dx, None, *gw)
 
@@ -174,7 +153,7 @@ class _GeneratorLossFunction(torch.autograd.Function):
         dev = y_fake.device
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _send(module, names, params, stream)
+            _send_parameters(module, "hificar_disc_set_parameters_device", names, params, stream)
             fake = _Pass(module, y_fake, stream)
             real = module._real_pass(y_real, params, stream) if y_real is not None else None
             douts, doff = _aligned(int(lib.hificar_disc_dout_floats(handle, B, T)), dev)
@@ -226,7 +205,7 @@ class _DiscriminatorLossFunction(torch.autograd.Function):
         dev = y_fake.device
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            held = _send(module, names, params, stream)
+            held = _send_parameters(module, "hificar_disc_set_parameters_device", names, params, stream)
             passes, douts, vals = [], [], []
             for mode, y in ((1, y_fake), (2, y_real)):
                 ps = _Pass(module, y, stream) if mode == 1 else module._real_pass(y, params, stream)
@@ -281,21 +260,17 @@ class _DiscriminatorLossFunction(torch.autograd.Function):
                     # data-parallel training: one gradient bucket per sub-discriminator.  During the LAST pass libhificar calls back as
                     # each sub-network's gradients (both passes' sum by then) are enqueued on its side stream: there the weight-norm chain
                     # rule runs and the bucket's all-reduce (RCCL over xGMI) starts while the other sub-networks still compute.
-                    from ..utils.buckets import BucketHook, BucketReducer, bucket_ranges
+                    from ..utils.buckets import bucket_hook
 
-                    group, average = module._grad_sync
-                    nb = int(lib.hificar_disc_grad_bucket_count(handle))
                     ids = [int(lib.hificar_disc_raw_param_bucket(handle, i)) for i in range(len(ctx.shapes))]
-                    ranges, total = bucket_ranges(ids, [int(np.prod(sh)) for sh in ctx.shapes], nb)
-                    assert total == raw.numel()
 
                     def chain_rule(bucket, bstream):
                         _native.check(lib.hificar_disc_weight_norm_backward_bucket(handle, g.data_ptr(), raw.data_ptr(), bucket, ctypes.c_void_p(bstream)),
                                       "hificar_disc_weight_norm_backward_bucket")
 
                     # (the sub-network's side stream becomes torch's current stream inside the callback: the collective orders itself behind it)
-                    reducer = BucketHook(BucketReducer(raw, ranges, group, average), chain_rule,
-                                         lambda bstream: torch.cuda.stream(torch.cuda.ExternalStream(bstream, device=dev)))
+                    reducer = bucket_hook(raw, ctx.shapes, ids, int(lib.hificar_disc_grad_bucket_count(handle)), module._grad_sync, chain_rule,
+                                          lambda bstream: torch.cuda.stream(torch.cuda.ExternalStream(bstream, device=dev)))
                     cb = _native.BUCKET_FN(reducer)
                     _native.check(lib.hificar_disc_set_bucket_callback(handle, cb, None), "hificar_disc_set_bucket_callback")
                 try:
@@ -318,11 +293,7 @@ class _DiscriminatorLossFunction(torch.autograd.Function):
                     _native.check(lib.hificar_disc_weight_norm_backward(handle, g.data_ptr(), raw.data_ptr(), stream), "hificar_disc_weight_norm_backward")
                 finally:
                     lib.hificar_disc_set_grad_scale(handle, None)
-        gw, off = [], 0
-        for shape in ctx.shapes:
-            n = int(np.prod(shape))
-            gw.append(raw[off:off + n].view(shape))
-            off += (n + 3) & ~3
+        gw = raw_grad_views(raw, ctx.shapes)
         ctx.passes = ctx.douts = ctx.held = ctx.params = None
         return (None, None, None, None, None, *gw)
 

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from ..utils.buckets import raw_grad_views
 
 
 def _fold(v: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
@@ -116,13 +117,15 @@ class _PastFCParams(torch.nn.Module):
         self.model = torch.nn.Sequential(*mods)
 
 
-def _send_parameters(module, names, tensors, stream):
-    """Hand every RAW parameter over in one call (hificar_set_parameters_device: weight norm folded and every pack refreshed on the
-    device, two launches).  Returns the tensors actually read (kept alive by the caller until the stream has consumed them)."""
+def _send_parameters(module, entry, names, tensors, stream):
+    """Hand every RAW parameter over in one call to the C entry point ``entry`` (hificar_set_parameters_device /
+    hificar_disc_set_parameters_device: weight norm folded and every pack refreshed on the device, two launches).  Returns the tensors
+    actually read (kept alive by the caller until the stream has consumed them)."""
     lib, handle = module._lib, module._handle
     # Nothing changed since the last hand-over to THIS handle (same tensors at the same addresses with the same version counters, and no
-    # invalidate_parameters() in between — which is what a fused optimizer's step triggers): skip the fold + 166 packs.  The graph forward of an
-    # iteration sees the weights the previous iteration's second (no-graph) forward already sent (train.py:389: "re-compute y_").
+    # invalidate_parameters() in between — which is what a fused optimizer's step triggers): skip the fold + every pack.  The generator's graph
+    # forward of an iteration sees the weights the previous iteration's second (no-graph) forward already sent (train.py:389: "re-compute y_");
+    # the generator part and the discriminator part of one iteration hand the discriminators the same weights.
     direct = all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors)
     sig = (id(handle), names, tuple(t.data_ptr() for t in tensors), tuple(t._version for t in tensors))
     if direct and module.__dict__.get("_sent_sig") == sig:
@@ -134,7 +137,7 @@ def _send_parameters(module, names, tensors, stream):
         arr = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
         cnames = module._raw_cnames = (names, arr)
     ptrs = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
-    _native.check(lib.hificar_set_parameters_device(handle, cnames[1], ptrs, len(held), stream), "hificar_set_parameters_device")
+    _native.check(getattr(lib, entry)(handle, cnames[1], ptrs, len(held), stream), entry)
     if direct:
         module.__dict__["_sent_sig"], module.__dict__["_sent_held"] = sig, held
     else:
@@ -158,7 +161,7 @@ class _GeneratorFunction(torch.autograd.Function):
         dev = c.device
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            held = _send_parameters(module, names, params, stream)
+            held = _send_parameters(module, "hificar_set_parameters_device", names, params, stream)
             tape = torch.empty(lib.hificar_tape_bytes(handle, B, T) + 256, dtype=torch.uint8, device=dev)
             toff = (-tape.data_ptr()) % 256
             out = torch.empty((B, 1, T * module.hop), dtype=torch.float32, device=dev)
@@ -208,19 +211,15 @@ class _GeneratorFunction(torch.autograd.Function):
                 # data-parallel training: the gradients are all-reduced bucket by bucket (RCCL over xGMI under the "nccl" backend) WHILE
                 # the backward pass still runs — libhificar calls back when a bucket's gradient kernels are enqueued (last stage first),
                 # the bucket's weight-norm chain rule runs right behind them and its collective starts on the communication stream
-                from ..utils.buckets import BucketHook, BucketReducer, bucket_ranges
+                from ..utils.buckets import bucket_hook
 
-                group, average = module._grad_sync
-                nb = int(lib.hificar_grad_bucket_count(handle))
                 ids = [int(lib.hificar_raw_param_bucket(handle, i)) for i in range(len(ctx.shapes))]
-                ranges, total = bucket_ranges(ids, [int(np.prod(sh)) for sh in ctx.shapes], nb)
-                assert total == raw.numel()
 
                 def chain_rule(bucket, bstream):  # (bstream is the current stream here: the generator's backward runs on one stream)
                     _native.check(lib.hificar_weight_norm_backward_bucket(handle, grads.data_ptr(), raw.data_ptr(), bucket, ctypes.c_void_p(bstream)),
                                   "hificar_weight_norm_backward_bucket")
 
-                reducer = BucketHook(BucketReducer(raw, ranges, group, average), chain_rule)
+                reducer = bucket_hook(raw, ctx.shapes, ids, int(lib.hificar_grad_bucket_count(handle)), module._grad_sync, chain_rule)
                 cb = _native.BUCKET_FN(reducer)
                 _native.check(lib.hificar_set_bucket_callback(handle, cb, None), "hificar_set_bucket_callback")
             try:
@@ -237,11 +236,7 @@ class _GeneratorFunction(torch.autograd.Function):
                 reducer.finish()  # (re-raises what a bucket callback caught)
             else:
                 _native.check(lib.hificar_weight_norm_backward(handle, grads.data_ptr(), raw.data_ptr(), stream), "hificar_weight_norm_backward")
-        gw, off = [], 0
-        for shape in ctx.shapes:
-            n = int(np.prod(shape))
-            gw.append(raw[off:off + n].view(shape))
-            off += (n + 3) & ~3
+        gw = raw_grad_views(raw, ctx.shapes)
         ctx.tape = ctx.held = ctx.params = ctx.cond = None
         return (None, dc, dar, None, None, None, *gw)
 
@@ -421,7 +416,7 @@ class _NativeGenerator(torch.nn.Module):
                     names, tensors = self._raw_parameters()
                     dev = self._device()
                     with torch.no_grad(), torch.cuda.device(dev):
-                        _send_parameters(self, names, tensors, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+                        _send_parameters(self, "hificar_set_parameters_device", names, tensors, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
                     self._param_sig = self._param_signature()
                     return self._handle
                 self._invalidate()

@@ -8,7 +8,25 @@ pass; ``finish()`` waits for every collective (making the current stream wait, n
 
 Pure torch.distributed logic (no native code): tests/test_distributed_gloo.py runs it at world size 2 on CPU tensors over gloo and checks
 it against ONE all-reduce of the whole buffer."""
+import math
+
 import torch.distributed as dist
+
+
+def _slot(n):
+    """Floats of one raw parameter's slot in the raw-gradient buffer: its element count rounded up to 4 (16-byte aligned slots)."""
+    return (int(n) + 3) & ~3
+
+
+def raw_grad_views(raw, shapes):
+    """Per-parameter views of a flat raw-gradient buffer (hificar_weight_norm_backward / hificar_disc_weight_norm_backward): parameter i has
+    shape shapes[i], the parameters lie back to back, every slot rounded up to 4 floats."""
+    views, off = [], 0
+    for shape in shapes:
+        n = math.prod(shape)
+        views.append(raw[off:off + n].view(shape))
+        off += _slot(n)
+    return views
 
 
 def bucket_ranges(raw_buckets, numels, n_buckets):
@@ -18,7 +36,7 @@ def bucket_ranges(raw_buckets, numels, n_buckets):
     ranges = [[] for _ in range(n_buckets)]
     off = 0
     for b, n in zip(raw_buckets, numels):
-        n4 = (int(n) + 3) & ~3
+        n4 = _slot(n)
         r = ranges[b]
         if r and r[-1][0] + r[-1][1] == off:
             r[-1] = (r[-1][0], r[-1][1] + n4)
@@ -87,3 +105,12 @@ class BucketHook:
                 w.wait()
             raise self.errors[0]
         return self.reducer.finish()
+
+
+def bucket_hook(raw, shapes, raw_buckets, n_buckets, grad_sync, chain_rule, stream_ctx=None):
+    """The BucketHook of one backward pass over the raw-gradient buffer ``raw`` of parameters of ``shapes`` (raw_buckets[i]: parameter i's
+    bucket); grad_sync = (process group, average)."""
+    ranges, total = bucket_ranges(raw_buckets, [math.prod(s) for s in shapes], n_buckets)
+    assert total == raw.numel()
+    group, average = grad_sync
+    return BucketHook(BucketReducer(raw, ranges, group, average), chain_rule, stream_ctx)

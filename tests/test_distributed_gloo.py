@@ -316,6 +316,19 @@ def test_bucket_ranges_merge_adjacent_slots():
     assert ranges[1] == [(72, 12)] and ranges[0] == [(84, 28)]
 
 
+def test_raw_grad_views_follow_the_slot_layout():
+    from articulatory_amd.utils.buckets import bucket_ranges, raw_grad_views
+
+    shapes = [(5, 1, 1), (5, 2, 4), (5,), (13,), ()]
+    _, total = bucket_ranges([0] * len(shapes), [int(np.prod(s)) for s in shapes], 1)
+    raw = torch.arange(float(total))
+    views = raw_grad_views(raw, shapes)
+    assert [tuple(v.shape) for v in views] == shapes
+    assert [int(v.reshape(-1)[0]) for v in views] == [0, 8, 48, 56, 72]   # slots rounded up to 4 floats
+    views[1][0, 0, 0] = -1.0  # views, not copies
+    assert raw[8] == -1.0
+
+
 def _bucket_worker(rank, world, port, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
