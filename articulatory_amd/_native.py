@@ -34,6 +34,7 @@ SYMBOLS = (
     "hificar_forward_cond",
     "hificar_ar_loop_ragged",
     "hificar_ar_loop_packed",
+    "hificar_ar_step",
     "hificar_macs",
     "hificar_pcm16",
     "hificar_profile_begin",
@@ -279,6 +280,9 @@ def load_library():
     lib.hificar_ar_loop_ragged.restype = ctypes.c_int
     lib.hificar_ar_loop_packed.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
     lib.hificar_ar_loop_packed.restype = ctypes.c_int
+    lib.hificar_ar_step.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp,
+                                    ctypes.c_size_t, vp]
+    lib.hificar_ar_step.restype = ctypes.c_int
     lib.hificar_macs.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     lib.hificar_macs.restype = ctypes.c_double
     lib.hificar_pcm16.argtypes = [vp, vp, ctypes.c_size_t, vp]

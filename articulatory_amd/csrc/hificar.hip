@@ -131,6 +131,19 @@ struct hificar_handle {
     void* h_tab = nullptr;
     size_t tab_bytes = 0;
     hipEvent_t tab_copied = nullptr;  // recorded behind the last upload: the staging copy may be rewritten once it has fired
+    // step tables of hificar_ar_step: a ring of slots of mapped pinned host memory that front_kernel reads directly (no upload), one
+    // per step in flight, each with the event recorded behind its step; a step only waits on the host when the ring has wrapped onto
+    // a slot whose step is still queued.  step_d: the device copy front_kernel publishes for the step's later launches
+    struct StepSlot {
+        hipEvent_t done = nullptr;
+        bool used = false;
+    };
+    std::vector<StepSlot> step_ring;
+    char* step_d = nullptr;
+    char* step_h = nullptr;
+    char* step_hd = nullptr;  // step_h as the device sees it
+    size_t step_cap = 0;      // table entries per slot
+    unsigned step_next = 0;
     // tile schedules (LPT assignment of tiles to workgroups), cached per launch shape.  They live in append-only arenas: a
     // device block plus a pinned host mirror, filled on the host and uploaded with ONE hipMemcpyAsync on the launch stream, so
     // the first use of a new launch shape neither allocates nor synchronises (the first arena is allocated in hificar_finalize)
@@ -472,6 +485,10 @@ extern "C" void hificar_destroy(hificar_handle* h) {
     if (h->tap_scratch) (void)hipFree(h->tap_scratch);
     if (h->train_free) h->train_free(h);
     if (h->tab_copied) (void)hipEventDestroy(h->tab_copied);
+    if (h->step_d) (void)hipFree(h->step_d);
+    if (h->step_h) (void)hipHostFree(h->step_h);
+    for (auto& st : h->step_ring)
+        if (st.done) (void)hipEventDestroy(st.done);
     for (auto& a : h->arenas) {
         (void)hipFree(a.d);
         (void)hipHostFree(a.h);
@@ -855,6 +872,12 @@ struct Cond {
     int ph_stride = 0;
     float* ph_out = nullptr;
     int ph_out_T = 0;
+    // streaming steps (hificar_ar_step): the caller's AR context arena (one row of ar_input samples per session) that replaces prev,
+    // the step table {row, frame, valid, first} as the device reads it, and where front_kernel publishes its slots / valid frames
+    float* ctx = nullptr;
+    const int4* seqs = nullptr;
+    int2* seqs_slots = nullptr;
+    int* seqs_valid = nullptr;
 };
 
 struct Ragged {
@@ -862,6 +885,7 @@ struct Ragged {
     int const_len = -1;  // >= 0 (and seq_len null): every utterance has this many frames, fewer than the launch covers (bucketed lengths)
     int f0 = 0;
     int frames = 0;
+    float* ctx = nullptr;  // streaming steps (Cond::ctx): the output conv writes out densely by sequence and refreshes the context rows
 };
 
 // Launch geometry of a non-AR forward is rounded up to a bucket of frames (the extra frames are masked exactly like the tail of a
@@ -1483,6 +1507,8 @@ static int launch_output_conv(hificar_handle* h, const float* const* fin, int ni
     op.len_max = T;
     op.len_mul = rows / T;
     op.slots = slots;
+    op.ctx = rg.ctx;
+    op.ar_input = cfg.ar_input;
     op.hop = h->hop;
     // samples per workgroup: 256, or what a 64-KB LDS tile of (TR + K - 1) rows x (C + 1) floats + the weights allows
     const long long fit = ((long long)64 * 1024 / 4 - (long long)op.K * op.C) / (op.C + 1) - (op.K - 1);
@@ -1530,6 +1556,14 @@ static int forward_impl(hificar_handle* h, const float* c, int64_t c_bstride, in
     fp.prev_bstride = prev_bstride;
     fp.slots = slots;
     fp.valid = seq_len;
+    if (cond.ctx) {
+        fp.prev = cond.ctx;
+        fp.prev_bstride = cfg.ar_input;
+        fp.seqs = cond.seqs;
+        fp.seqs_slots = cond.seqs_slots;
+        fp.seqs_valid = cond.seqs_valid;
+        rg.ctx = cond.ctx;
+    }
     fp.hop = h->hop;
     const bool f32 = h->precision == HIFICAR_PREC_F32;
     fp.xin = f32 ? (tp ? tp->xin : ws.xin) : nullptr;
@@ -2040,6 +2074,91 @@ extern "C" int hificar_ar_loop_packed(hificar_handle* h, const float* c, const i
 extern "C" int hificar_ar_loop(hificar_handle* h, const float* c, float* out, int B, int T_total, int chunk_frames,
                                void* workspace, size_t workspace_bytes, void* stream) {
     return hificar_ar_loop_ragged(h, c, nullptr, nullptr, out, B, T_total, chunk_frames, workspace, workspace_bytes, stream);
+}
+
+// One step of the AR loop for n sessions whose context outlives the call (streaming synthesis).  It is the packed loop's step in
+// context mode: the same launches over a full chunk, short last chunks masked per sequence on the device, the AR input read from /
+// written back to the caller's context arena by front_kernel / output_conv_kernel (FrontParams::seqs, OutConvParams::ctx).  The step
+// table is written into a ring of mapped pinned slots that front_kernel reads where they are (an upload would put a DMA transfer in
+// front of every step's launches), so the host never waits for earlier steps unless kStepRing of them are queued.
+static constexpr int kStepRing = 32;
+extern "C" int hificar_ar_step(hificar_handle* h, const float* c, int64_t c_bstride, int64_t c_cstride, const int32_t* seqs_host, int n,
+                               int chunk_frames, float* ctx, int ctx_rows, float* out, void* workspace, size_t workspace_bytes,
+                               void* stream_) {
+    // every argument is checked before the handle's state (finalize, workspace): nothing is enqueued for a bad table
+    if (!h) return fail(HIFICAR_E_INVALID, "null handle");
+    if (!h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_step on a model built with use_ar=false");
+    if (h->cfg.use_spk_id || h->cfg.use_ph)  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
+        return fail(HIFICAR_E_INVALID, "hificar_ar_step: speaker / phoneme conditioned models are driven through hificar_forward_cond");
+    if (n < 1 || chunk_frames < 1 || ctx_rows < 1)
+        return fail(HIFICAR_E_INVALID, "hificar_ar_step: n=%d, chunk_frames=%d, ctx_rows=%d must be positive", n, chunk_frames, ctx_rows);
+    if (!c || !seqs_host || !ctx || !out) return fail(HIFICAR_E_INVALID, "hificar_ar_step: null argument");
+    if (h->cfg.ar_input > h->hop * chunk_frames)
+        return fail(HIFICAR_E_INVALID, "ar_input (%d) > chunk audio length (%d): the reference loop (decode.py:79-81) is ill-formed there",
+                    h->cfg.ar_input, h->hop * chunk_frames);
+    if (c_bstride < 0 || c_cstride < 1) return fail(HIFICAR_E_INVALID, "hificar_ar_step: strides %lld / %lld", (long long)c_bstride, (long long)c_cstride);
+    if (n > ctx_rows) return fail(HIFICAR_E_INVALID, "hificar_ar_step: %d sequences for %d context rows", n, ctx_rows);
+    std::vector<char> seen((size_t)ctx_rows, 0);
+    bool all_full = true;
+    for (int b = 0; b < n; ++b) {
+        const int32_t* e = seqs_host + 4 * (size_t)b;
+        if (e[0] < 0 || e[0] >= ctx_rows) return fail(HIFICAR_E_INVALID, "hificar_ar_step: sequence %d: row %d outside [0, %d)", b, e[0], ctx_rows);
+        if (seen[(size_t)e[0]]) return fail(HIFICAR_E_INVALID, "hificar_ar_step: row %d appears twice in one step", e[0]);
+        seen[(size_t)e[0]] = 1;
+        if (e[2] < 1 || e[2] > chunk_frames)
+            return fail(HIFICAR_E_INVALID, "hificar_ar_step: sequence %d: valid frames %d outside [1, %d]", b, e[2], chunk_frames);
+        all_full = all_full && e[2] == chunk_frames;
+        if (e[1] < 0 || (int64_t)e[1] + e[2] > c_cstride)
+            return fail(HIFICAR_E_INVALID, "hificar_ar_step: sequence %d: frames [%d, %d) outside the feature rows (%lld)", b, e[1], e[1] + e[2],
+                        (long long)c_cstride);
+    }
+    int rc = check_ready(h, n, chunk_frames, workspace, workspace_bytes);
+    if (rc != HIFICAR_OK) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    const size_t cap = ((size_t)ctx_rows + 1) & ~(size_t)1;  // entries: any valid table of this arena fits (n <= ctx_rows)
+    if (cap > h->step_cap) {
+        for (auto& st : h->step_ring)  // the old slots may still be read by queued steps
+            if (st.used) HIP_TRY(hipEventSynchronize(st.done));
+        if (h->step_d) HIP_TRY(hipFree(h->step_d));
+        if (h->step_h) HIP_TRY(hipHostFree(h->step_h));
+        h->step_d = h->step_h = h->step_hd = nullptr;
+        h->step_cap = 0;
+        HIP_TRY(hipMalloc(&h->step_d, cap * (sizeof(int2) + sizeof(int))));
+        HIP_TRY(hipHostMalloc(&h->step_h, cap * sizeof(int4) * kStepRing, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->step_hd), h->step_h, 0));
+        h->step_cap = cap;
+        h->step_ring.resize(kStepRing);
+        for (auto& st : h->step_ring) {
+            if (!st.done) HIP_TRY(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+            st.used = false;
+        }
+    }
+    const unsigned k = h->step_next++ % kStepRing;
+    auto& slot = h->step_ring[k];
+    if (slot.used) HIP_TRY(hipEventSynchronize(slot.done));  // fired long ago unless kStepRing steps are queued
+    int4* hs = reinterpret_cast<int4*>(h->step_h) + (size_t)k * h->step_cap;
+    for (int b = 0; b < n; ++b) {
+        const int32_t* e = seqs_host + 4 * (size_t)b;
+        hs[b] = int4{e[0], e[1], e[2], e[3] != 0};
+    }
+    // the device table front_kernel publishes: slots (row, frame) | valid frames (int2 rows 16-byte aligned: cap is even).  One copy
+    // serves every step: a step's launches are done with it before the next step's front_kernel runs (one stream, enter_stream)
+    int2* d_slots = reinterpret_cast<int2*>(h->step_d);
+    int* d_valid = reinterpret_cast<int*>(d_slots + h->step_cap);
+    Cond cond;
+    cond.ctx = ctx;
+    cond.seqs = reinterpret_cast<const int4*>(h->step_hd) + (size_t)k * h->step_cap;
+    cond.seqs_slots = d_slots;
+    cond.seqs_valid = d_valid;
+    // a step of full chunks only (every step but a session's last) runs the launches unmasked, as an ar_synthesis step does: the masked
+    // form's per-tile length loads cost ~1 us per launch, and for full chunks both forms compute the same values
+    rc = forward_impl(h, c, c_bstride, c_cstride, nullptr, 0, out, (int64_t)h->hop * chunk_frames, n, chunk_frames,
+                      plan_workspace(h, n, chunk_frames, workspace), stream, all_full ? nullptr : d_valid, 0, d_slots, -1, cond);
+    // (also behind a failed step: what it did enqueue may read the slot)
+    if (hipEventRecord(slot.done, stream) == hipSuccess) slot.used = true;
+    else if (rc == HIFICAR_OK) rc = fail(HIFICAR_E_HIP, "hificar_ar_step: recording the step's event failed");
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -102,6 +102,14 @@ struct FrontParams {
     // pitch prev_bstride, hop samples per frame): its AR context are the ar_input samples before hop * frame.
     const int2* slots;
     const int* valid;
+    // context mode (hificar_ar_step): seqs[b] = {row, frame, valid, first} of sequence b, read where the host wrote it (mapped pinned
+    // memory: the step table needs no upload); workgroup b publishes (row, frame) / valid as seqs_slots[b] / seqs_valid[b] on the device
+    // for the step's later launches.  Its features are row `row` of c from frame `frame` (valid frames); its AR input is row `row` of
+    // the caller's context arena prev (prev_bstride floats per row), or zeros where `first` is set (the session's first chunk: a reused
+    // row never leaks the previous session's context)
+    const int4* seqs;
+    int2* seqs_slots;
+    int* seqs_valid;
     int hop;
     int t_valid;          // frames that exist in c (<= T): later frames read as zeros (bucketed launch lengths)
     // speaker conditioning (hifigan.py:212-216): spk_fc(spk_emb_mat[spk_id[b]]) is added to channels [0, cf + ar_output)
@@ -129,9 +137,19 @@ __global__ __launch_bounds__(kFrontThreads) void front_kernel(const FrontParams 
     const int lane = tid & 63;
     const int ks = tid >> 6;  // wave index = K slice: each wave reduces an eighth of the input dimension
     int cur = 0;
+    int4 seq = {0, 0, 0, 0};
+    if (p.seqs) {
+        seq = p.seqs[b];
+        if (tid == 0) {
+            p.seqs_slots[b] = int2{seq.x, seq.y};
+            p.seqs_valid[b] = seq.z;
+        }
+    }
     if (p.use_ar) {
         const float* prevp = p.prev ? p.prev + (size_t)b * p.prev_bstride : nullptr;
-        if (p.slots) {
+        if (p.seqs) {
+            prevp = seq.w ? nullptr : p.prev + (size_t)seq.x * p.prev_bstride;
+        } else if (p.slots) {
             const int2 sl = p.slots[b];
             prevp = sl.y > 0 ? p.prev + (size_t)sl.x * p.prev_bstride + (size_t)p.hop * sl.y - p.ar_input : nullptr;
         }
@@ -199,7 +217,10 @@ __global__ __launch_bounds__(kFrontThreads) void front_kernel(const FrontParams 
     const int n = p.T * p.cin_pad;
     size_t cbase = (size_t)b * p.c_bstride;
     int tmax = p.t_valid;
-    if (p.slots) {
+    if (p.seqs) {
+        cbase = (size_t)seq.x * p.c_bstride + seq.y;
+        tmax = seq.z;
+    } else if (p.slots) {
         cbase = (size_t)p.slots[b].x * p.c_bstride + p.slots[b].y;
         tmax = p.valid[b];  // frames past the utterance's end may lie outside the packed tensor
     }
@@ -247,6 +268,11 @@ struct OutConvParams {
     int len_const;
     int len_f0, len_max, len_mul;
     const int2* slots;   // packed mode, as in FrontParams: sequence -> (utterance, first frame); out is the packed waveform
+    // context mode (hificar_ar_step, with slots): out is dense by sequence (out + seq * out_bstride), and a sequence whose chunk is full
+    // (Ls == L) also stores its last ar_input samples into row slots[seq].x of the context arena ctx (ar_input floats per row), the
+    // reference's prev = cout[:, :, -ar_input:] (decode.py:77-78) that the next step's front_kernel reads
+    float* ctx;
+    int ar_input;
     int hop;
     int TR;              // output samples per workgroup (<= 256; fewer when C is wide, so that the LDS tile fits)
 };
@@ -304,8 +330,10 @@ __global__ __launch_bounds__(256) void output_conv_kernel(const OutConvParams p)
             const float* wk = &ws[k * p.C];
             for (int ch = 0; ch < p.C; ++ch) s = fmaf(xr[ch], wk[ch], s);
         }
-        const size_t obase = p.slots ? (size_t)p.slots[seq].x * p.out_bstride + (size_t)p.hop * p.slots[seq].y : (size_t)seq * p.out_bstride;
-        p.out[obase + t] = p.use_tanh ? tanhf(s) : s;
+        const size_t obase = p.slots && !p.ctx ? (size_t)p.slots[seq].x * p.out_bstride + (size_t)p.hop * p.slots[seq].y : (size_t)seq * p.out_bstride;
+        const float y = p.use_tanh ? tanhf(s) : s;
+        p.out[obase + t] = y;
+        if (p.ctx && Ls == p.L && t >= p.L - p.ar_input) p.ctx[(size_t)p.slots[seq].x * p.ar_input + (t - (p.L - p.ar_input))] = y;
     }
 }
 

@@ -19,6 +19,8 @@
  *                           (a batch of utterances of DIFFERENT lengths in one call; results per utterance are those of
  *                           the one-at-a-time loop, bit for bit)
  *   hificar_ar_loop_packed  the same dataset loop, continuously batched (a finished utterance's place is taken by the next)
+ *   hificar_ar_step         one chunk of ar_loop (decode.py:54-83) for each of n live sessions; the AR context  articulatory/bin/decode.py:54-83
+ *                           (prev = cout[:, :, -ar_input:], decode.py:77-78) persists between calls in a caller-owned arena
  *   hificar_pcm16           sf.write(..., "PCM_16") sample conversion articulatory/bin/decode.py:319-324
  *   hificar_workspace_bytes (torch's caching allocator does this implicitly in the reference)
  *   hificar_last_error      Python exceptions / assert           articulatory/models/hifigan.py:78-80
@@ -197,6 +199,22 @@ int hificar_ar_loop_ragged(hificar_handle* h, const float* c, const int32_t* len
  * articulatory/bin/decode.py:292-351 / egs/ema/voc1/local/predict_wav.py:124-137. */
 int hificar_ar_loop_packed(hificar_handle* h, const float* c, const int32_t* lengths_host, float* out, int N, int T_max,
                            int chunk_frames, int batch, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Streaming synthesis: ONE step of the reference's AR loop (articulatory/bin/decode.py:54-83) for n sessions, each advancing by one chunk,
+ * with the AR context of every session kept between calls in the caller's arena ctx: (ctx_rows, ar_input) device fp32, one row per
+ * session.  seqs_host: n HOST rows of four int32 {row, frame, valid, first}:
+ *   row    the session's context row in [0, ctx_rows), at most once per step; also its feature row in c
+ *   frame  first frame of the chunk in c: element (row, ch, t) at c[row*c_bstride + ch*c_cstride + t]; frame + valid <= c_cstride
+ *   valid  frames of this chunk, 1..chunk_frames (fewer: the session's last chunk, decode.py:56)
+ *   first  nonzero: the session's first chunk — its AR input is zeros, whatever the row holds (no memset of a reused row needed)
+ * out: (n, hop*chunk_frames) device fp32, dense by sequence; out[b, hop*valid:] is left untouched.  A full chunk also writes its
+ * last ar_input samples into its ctx row, which the session's next step reads (decode.py:77-78).  Per session the concatenated
+ * output is hificar_ar_loop's on the concatenated frames.  Launches exactly the kernels of one hificar_ar_loop step of n utterances
+ * (one chunk), and no copy: the table goes into a ring of mapped pinned slots that the first kernel reads in place, so the call
+ * does not wait for device work (unless 32 steps of this handle are still queued).  workspace: hificar_workspace_bytes(h, n, chunk_frames).  Requires use_ar, no speaker /
+ * phoneme conditioning, ar_input <= hop*chunk_frames; the table is checked on the host before anything is enqueued. */
+int hificar_ar_step(hificar_handle* h, const float* c, int64_t c_bstride, int64_t c_cstride, const int32_t* seqs_host, int n,
+                    int chunk_frames, float* ctx, int ctx_rows, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* float waveform in [-1, 1] -> 16-bit PCM on the device: y = clip(round_half_even(x *_f32 32767.f), -32768, 32767) — the product in
  * float32, as libsndfile's f2s_array computes it (lrintf(src * 32767.f)); libsndfile wraps outside [-1, 1] where this clips.
