@@ -81,6 +81,29 @@ struct GBlockLayers {
     int cin = 0, cout = 0;
 };
 
+// A launch shape of the conv engine: what a ConvPlan is a function of, besides the handle's fixed switches.  A layer is identified by its
+// address: every engine (generator, GBlock generator, their TrainState's data-gradient layers, the discriminators' per-group layers, mel)
+// builds its ConvLayers once, in create / train_init, into storage it owns and never resizes afterwards.
+struct PlanKey {
+    const ConvLayer* layers[6];  // launch_conv: the branches' layers; launch_pair: conv1 of every branch, from [3] on conv2; null: no such branch
+    int nseq, rows, zrep;
+    int flags;                   // 1: exact fp32, 2: training (device-resident weights), 4: shared_chip, 8: launch_pair
+    bool operator<(const PlanKey& o) const { return memcmp(this, &o, sizeof(PlanKey)) < 0; }  // (six pointers, four ints: no padding)
+};
+
+// Everything about a launch of launch_conv / launch_pair that its shape decides: computed on the first launch of that shape
+// (build_conv_plan / build_pair_plan), looked up afterwards.
+struct ConvPlan {
+    ConvShape shape;
+    unsigned grid = 0;
+    size_t lds = 0;
+    std::string name;  // kernel name for ProfScope ("kernel|layer xN" with profile_detail)
+    // the kernel's parameter block with what the shape decides filled in — tile counts, LDS bytes, xcd_order, stage_cached and the plan's
+    // own tile schedule in the arenas (null: the kernel's round-robin walk) — and the rest zero: a launch copies it and adds the call's IO
+    MultiConvParams conv = {};  // launch_conv
+    PairParams pair = {};       // launch_pair
+};
+
 struct hificar_handle {
     hificar_config cfg;
     int arch = 0;                  // 0: HiFiGANGenerator (hificar_create); 1: GBlockGenerator (hificar_gblock_create, hificar_gblock.hip.inc)
@@ -90,13 +113,11 @@ struct hificar_handle {
     int precision = HIFICAR_PREC_F32;
     bool profile_detail = false;   // HIFICAR_PROFILE_DETAIL=1: profile rows carry the layer name
     bool use_pair = true;          // HIFICAR_PAIR=0: run narrow stages layer by layer (A/B runs)
-    bool use_lpt = true;           // false: round-robin tile walk instead of the host LPT schedule
     double mi1_penalty = 1.05;     // cost factor of 32-row tiles in the exact-fp32 tile choice (they re-stream the weights most often: L2-bound when
                                    // K is long).  The discriminator engine raises it: its launches overlap on several streams, so a nearly
                                    // empty last round of taller tiles costs little there, while the L2 traffic of short tiles is shared by all
     int pick_throughput = 0;       // > 0: launches of at least this many tiles choose their tile shape by workgroup-time instead of makespan (set by
-                                   // the discriminator engine, whose sub-networks run on eight streams; HIFICAR_DISC_PICK overrides, 0 = off)
-    bool xcd_order = true;         // XCD-contiguous tile order for one-round launches that stream more weights than activations
+                                   // the discriminator engine, whose sub-networks run on eight streams; 0 = off)
     bool pair_small = true;        // HIFICAR_PAIR_SMALL: 128-row fused pair tiles at C = 32 for mid-size launches (pair_small_tiles)
     int ksplit = 1;                // HIFICAR_KSPLIT: 0 = never use the split-K conv form, 1 = when it is estimated faster (default), 2 = always
     int cf = 0;       // feature channels = in_channels - ar_output*use_ar
@@ -144,15 +165,10 @@ struct hificar_handle {
     char* step_hd = nullptr;  // step_h as the device sees it
     size_t step_cap = 0;      // table entries per slot
     unsigned step_next = 0;
-    // tile schedules (LPT assignment of tiles to workgroups), cached per launch shape.  They live in append-only arenas: a
-    // device block plus a pinned host mirror, filled on the host and uploaded with ONE hipMemcpyAsync on the launch stream, so
-    // the first use of a new launch shape neither allocates nor synchronises (the first arena is allocated in hificar_finalize)
-    struct Sched {
-        int* d_start = nullptr;
-        int* d_tiles = nullptr;
-    };
-    std::map<std::string, Sched> scheds;
-    std::map<std::string, int> tile_picks;  // launch shape -> index into kTileCfgs (launch_conv's choice, cached: it simulates the LPT assignment)
+    // launch plans, one per launch shape (get_plan), each with the tile schedule it built.  The schedules live in append-only arenas: a
+    // device block plus a pinned host mirror, filled on the host and uploaded with ONE hipMemcpyAsync on the launch stream, so the first use of
+    // a new launch shape neither allocates nor synchronises (the first arena is allocated in hificar_finalize).  Dropped only together: evict_plans
+    std::map<PlanKey, ConvPlan> plans;
     struct Arena {
         char* d = nullptr;
         char* h = nullptr;
@@ -182,7 +198,7 @@ struct hificar_handle {
     int ar_dual_min = 17, ar_dual_max = 62;  // HIFICAR_AR_DUAL_MIN / _MAX: the batch sizes the loop splits (max 0: never)
     hipStream_t ar_side = nullptr;
     hipEvent_t ar_ev[2] = {nullptr, nullptr};
-    unsigned long long sched_up_seq = 0;  // schedule uploads so far (get_schedule): a schedule is uploaded on the stream that first needs it
+    unsigned long long sched_up_seq = 0;  // schedule uploads so far (upload_schedule): a schedule is uploaded on the stream that first needs it
     hipEvent_t done_ev = nullptr;  // recorded at the END of the last call on done_stream (calls that mark their end: the discriminators' backward)
     bool done_valid = false;
     hipStream_t done_stream = nullptr;
@@ -235,12 +251,13 @@ struct ProfScope {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     std::string name;
     double flops, bytes;
-    ProfScope(hificar_handle* h_, hipStream_t s_, const std::string& n, double f, double b) : h(h_), s(s_), name(n), flops(f), bytes(b) {
+    ProfScope(hificar_handle* h_, hipStream_t s_, const std::string& n, double f, double b) : h(h_), s(s_), flops(f), bytes(b) {
         if (g_launch_log) {
             fprintf(g_launch_log, "%s\t%.0f\t%.0f\n", n.c_str(), f, b);
             fflush(g_launch_log);
         }
         if (!h->profiling) return;
+        name = n;
         (void)hipEventCreate(&e0);
         (void)hipEventCreate(&e1);
         (void)hipEventRecord(e0, s);
@@ -934,95 +951,94 @@ static int arena_add(hificar_handle* h, size_t min_bytes) {
     return HIFICAR_OK;
 }
 
-// `bytes` of arena space: device pointer + the pinned host mirror to fill before the upload
-static int arena_take(hificar_handle* h, size_t bytes, char** d, char** hm) {
-    bytes = round_up_sz(bytes, 256);
-    if (h->arenas.empty() || h->arenas.back().used + bytes > h->arenas.back().cap) {
-        if (h->arenas.size() >= kMaxArenas) {
-            // a very large number of distinct launch shapes: recycle.  Kernels in flight may still read old schedules, so drain
-            // the device first (rare, off the hot path; hificar_forward buckets non-AR lengths so that keys repeat)
-            HIP_TRY(hipDeviceSynchronize());
-            h->scheds.clear();
-            for (auto& a : h->arenas) a.used = 0;
-            std::sort(h->arenas.begin(), h->arenas.end(), [](const hificar_handle::Arena& x, const hificar_handle::Arena& y) { return x.cap < y.cap; });
-            if (bytes > h->arenas.back().cap) return fail(HIFICAR_E_INVALID, "tile schedule of %zu bytes exceeds the arena", bytes);
-        } else {
-            int rc = arena_add(h, bytes);  // allocates: only when the pre-allocated arena is full
-            if (rc != HIFICAR_OK) return rc;
-        }
-    }
-    hificar_handle::Arena& a = h->arenas.back();
-    *d = a.d + a.used;
-    *hm = a.h + a.used;
-    a.used += bytes;
+// Drops every launch plan together with the schedules they point to, and recycles the arenas: the one place either goes (a very
+// large number of distinct launch shapes; rare, off the hot path: hificar_forward buckets non-AR lengths so that shapes repeat).
+// Kernels in flight may still read old schedules, so the device is drained first.
+static int evict_plans(hificar_handle* h) {
+    HIP_TRY(hipDeviceSynchronize());
+    h->plans.clear();
+    for (auto& a : h->arenas) a.used = 0;
+    std::sort(h->arenas.begin(), h->arenas.end(), [](const hificar_handle::Arena& x, const hificar_handle::Arena& y) { return x.cap < y.cap; });
     return HIFICAR_OK;
 }
+
+typedef std::vector<std::vector<int>> TileLists;  // an explicit tile list per workgroup, walked in the order given
 
 // Longest-processing-time-first assignment of `costs.size()` tiles to G workgroups; each workgroup's list is then
-// ordered light -> heavy (the kernel walks it in that order).  Built once per launch shape, uploaded asynchronously on the
-// launch stream (the launch that follows is ordered behind the copy) and cached.
-static int put_schedule(hificar_handle* h, const std::string& key, const std::vector<std::vector<int>>& lists, int n, hipStream_t stream,
-                        const int** d_start, const int** d_tiles);
-
-static int get_schedule(hificar_handle* h, const std::string& key, const std::vector<double>& costs, int G, hipStream_t stream,
-                        const int** d_start, const int** d_tiles) {
-    auto it = h->scheds.find(key);
-    if (it == h->scheds.end()) {
-        const int n = (int)costs.size();
-        std::vector<int> order(n);
-        for (int i = 0; i < n; ++i) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return costs[a] > costs[b]; });
-        std::vector<std::vector<int>> lists(G);
-        // min-heap of (load, workgroup)
-        std::vector<std::pair<double, int>> heap;
-        for (int w = 0; w < G; ++w) heap.push_back({0.0, w});
-        auto cmp = [](const std::pair<double, int>& a, const std::pair<double, int>& b) {
-            return a.first > b.first || (a.first == b.first && a.second > b.second);
-        };
-        std::make_heap(heap.begin(), heap.end(), cmp);
-        for (int t : order) {
-            std::pop_heap(heap.begin(), heap.end(), cmp);
-            auto& top = heap.back();
-            lists[top.second].push_back(t);
-            top.first += costs[t];
-            std::push_heap(heap.begin(), heap.end(), cmp);
-        }
-        for (auto& l : lists) std::reverse(l.begin(), l.end());  // heavy-first insertion order -> light first
-        return put_schedule(h, key, lists, n, stream, d_start, d_tiles);
+// ordered light -> heavy (the kernel walks it in that order).
+static TileLists lpt_lists(const std::vector<double>& costs, int G) {
+    const int n = (int)costs.size();
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return costs[a] > costs[b]; });
+    TileLists lists(G);
+    typedef std::pair<double, int> Load;  // (load, workgroup): least loaded first, ties to the lower workgroup
+    std::priority_queue<Load, std::vector<Load>, std::greater<Load>> heap;
+    for (int w = 0; w < G; ++w) heap.push({0.0, w});
+    for (int t : order) {
+        Load top = heap.top();
+        heap.pop();
+        lists[top.second].push_back(t);
+        top.first += costs[t];
+        heap.push(top);
     }
-    *d_start = it->second.d_start;
-    *d_tiles = it->second.d_tiles;
-    return HIFICAR_OK;
+    for (auto& l : lists) std::reverse(l.begin(), l.end());  // heavy-first insertion order -> light first
+    return lists;
 }
 
-// An explicit tile list per workgroup (walked in the order given), uploaded asynchronously on the launch stream and cached under `key`.
-static int put_schedule(hificar_handle* h, const std::string& key, const std::vector<std::vector<int>>& lists, int n, hipStream_t stream,
-                        const int** d_start, const int** d_tiles) {
-    auto it = h->scheds.find(key);
-    if (it == h->scheds.end()) {
-        const int G = (int)lists.size();
-        const size_t n_start = (size_t)G + 1;
-        const size_t bytes = (round_up_sz(n_start, 4) + (size_t)std::max(n, 1)) * sizeof(int);
-        char *dp = nullptr, *hp = nullptr;
-        int rc = arena_take(h, bytes, &dp, &hp);
-        if (rc != HIFICAR_OK) return rc;
-        int* start = reinterpret_cast<int*>(hp);
-        int* tiles = start + round_up_sz(n_start, 4);
-        int pos = 0;
-        for (int w = 0; w < G; ++w) {
-            start[w] = pos;
-            for (int t : lists[w]) tiles[pos++] = t;
-        }
-        start[G] = pos;
-        HIP_TRY(hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, stream));  // pinned source, never rewritten while cached
-        ++h->sched_up_seq;
-        hificar_handle::Sched sc;
-        sc.d_start = reinterpret_cast<int*>(dp);
-        sc.d_tiles = sc.d_start + round_up_sz(n_start, 4);
-        it = h->scheds.emplace(key, sc).first;
+// One round of tiles of ONE layer whose weights do not fit an XCD's 4-MB L2 (the discriminators' 1024-wide GEMM-form layers: 21 MB of weights,
+// 17 row tiles x 8 channel groups): dealt out round-robin every XCD streams ALL the weights through its L2 (335 MB per launch); here every XCD
+// gets a BLOCK of (row tiles x channel groups), so that both operands are re-used inside the XCD by workgroups that run in lock step — the
+// split of the 8 XCDs into (pr x pg) that minimises row tiles / pr + channel groups / pg.  Workgroup w is dispatched to XCD w % 8
+// (MI355X_MICROARCH.md: round-robin; an assumption for speed only — any mapping is correct).
+// R row tiles x Gc channel groups, tile id = channel group * R + row tile; XCD x's l-th tile goes to workgroup 8 l + x.  Empty: no split is worth
+// it, or the blocks need more than num_cus workgroups.
+static TileLists xcd_block_lists(int R, int Gc, int num_cus) {
+    int bpr = 1, bpg = 8;
+    double bcost = 1e300;
+    for (int pr = 1; pr <= 8; pr *= 2) {
+        const int pg = 8 / pr;
+        if (pr > R || pg > Gc) continue;
+        const double c = (double)((R + pr - 1) / pr) + (double)((Gc + pg - 1) / pg);
+        if (c < bcost) bcost = c, bpr = pr, bpg = pg;
     }
-    *d_start = it->second.d_start;
-    *d_tiles = it->second.d_tiles;
+    const size_t maxblock = (size_t)((R + bpr - 1) / bpr) * ((Gc + bpg - 1) / bpg);
+    if (maxblock * 8 > (size_t)num_cus || bcost >= (double)(R + 1)) return TileLists();
+    TileLists lists(maxblock * 8);
+    for (int x = 0; x < 8; ++x) {
+        const int xr = x / bpg, xg = x % bpg;
+        size_t l = 0;
+        for (int g2 = Gc * xg / bpg; g2 < Gc * (xg + 1) / bpg; ++g2)
+            for (int r2 = R * xr / bpr; r2 < R * (xr + 1) / bpr; ++r2) lists[l++ * 8 + (size_t)x].push_back(g2 * R + r2);
+    }
+    return lists;
+}
+
+// The schedule `lists` of n tiles into the arenas (device block + the pinned host mirror it is filled in), uploaded asynchronously on the
+// launch stream: the launch that follows is ordered behind the copy, hificar_ar_loop's second stream behind sched_up_seq.
+static int upload_schedule(hificar_handle* h, const TileLists& lists, int n, hipStream_t stream, const int** d_start, const int** d_tiles) {
+    const int G = (int)lists.size();
+    const size_t n_start = round_up_sz((size_t)G + 1, 4);
+    const size_t bytes = (n_start + (size_t)std::max(n, 1)) * sizeof(int), take = round_up_sz(bytes, 256);
+    if (h->arenas.empty() || h->arenas.back().used + take > h->arenas.back().cap) {
+        int rc = h->arenas.size() >= kMaxArenas ? evict_plans(h) : arena_add(h, take);  // (allocates: only when the pre-allocated arena is full)
+        if (rc != HIFICAR_OK) return rc;
+        if (take > h->arenas.back().cap) return fail(HIFICAR_E_INVALID, "tile schedule of %zu bytes exceeds the arena", take);
+    }
+    hificar_handle::Arena& a = h->arenas.back();
+    int* start = reinterpret_cast<int*>(a.h + a.used);
+    int* tiles = start + n_start;
+    int pos = 0;
+    for (int w = 0; w < G; ++w) {
+        start[w] = pos;
+        for (int t : lists[w]) tiles[pos++] = t;
+    }
+    start[G] = pos;
+    *d_start = reinterpret_cast<int*>(a.d + a.used);
+    *d_tiles = *d_start + n_start;
+    a.used += take;
+    HIP_TRY(hipMemcpyAsync(const_cast<int*>(*d_start), start, bytes, hipMemcpyHostToDevice, stream));  // pinned source, never rewritten while its plan lives
+    ++h->sched_up_seq;
     return HIFICAR_OK;
 }
 
@@ -1080,39 +1096,21 @@ struct ConvRep {
     long long zs_x = 0, zs_w = 0, zs_y = 0, zs_b = 0;
 };
 
-static int launch_conv(hificar_handle* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, const ConvIO* io,
-                              float slope_out, const Ragged& rg, hipStream_t stream, const ConvRep& zr = ConvRep()) {
+// Tile shape of a launch_conv launch: simulate the kernel's tile walk and take the shape with the smallest makespan.  A tile costs its
+// MFMA issue cycles (all four MFMA waves run in lock step: 3*MI MFMAs of 32 cycles per 16-channel K slab) plus a fixed per-tile and
+// per-item overhead.  Pure host arithmetic on the launch shape and the handle's fixed switches.
+static TileCfg pick_tile(const hificar_handle* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, int zrep) {
     const ConvLayer& L0 = *layers[0];
     const bool f32 = h->precision == HIFICAR_PREC_F32;  // rows are plain fp32 LeakyReLU(x) instead of split rows
     int halo_all = 0;
     for (int b = 0; b < nbr; ++b) halo_all = std::max(halo_all, layers[b]->off_max - layers[b]->off_min);
-    // Tile shape: simulate the kernel's static tile walk (workgroup w takes tiles w, w+G, ...; branch-major order) and
-    // take the shape with the smallest makespan.  A tile costs its MFMA issue cycles (all four MFMA waves run in
-    // lock step: 3*MI MFMAs of 32 cycles per 16-channel K slab) plus a fixed per-tile and per-item overhead.
     TileCfg tc = {1, 4, 1, 1, 1};
     double best = 1e300;
-    int best_ti = 11;  // {1, 4, 1, 1, 1}
     // The dense exact-fp32 launches are direct-output (conv_f32do_kernel): tiles stored straight from the MFMA waves' accumulators, no LDS out-buffer
     // (its bytes are free for taller tiles / wider halos below).  The register-blocked (NB = 2) wave tiles exist in bf16x3 only, where the cost model
     // may prefer them (+1.3 %; in exact fp32 they measured -1.0 %: profiles/r04_nb_register_blocking.txt).
-    const int nsteps_min = [&] {
-        int m = 1 << 30;
-        for (int b = 0; b < nbr; ++b) m = std::min(m, layers[b]->ntaps * (L0.chunk16 / 16));
-        return m;
-    }();
-    std::string pick_key;
-    pick_key.reserve(160);
-    pick_key += f32 ? 'f' : 'c';
-    pick_key += h->train ? 't' : 'i';
-    if (h->shared_chip) pick_key += 's';  // (launches that share the chip with another stream's: hificar_ar_loop on two streams)
-    for (int b = 0; b < nbr; ++b) {
-        pick_key += '|';
-        pick_key += layers[b]->name;
-    }
-    pick_key += '|' + std::to_string(nseq) + 'x' + std::to_string(rows) + 'z' + std::to_string(zr.n);
-    const auto cached_pick = h->tile_picks.find(pick_key);
-    if (cached_pick != h->tile_picks.end()) tc = kTileCfgs[cached_pick->second];
-    else
+    int nsteps_min = 1 << 30;
+    for (int b = 0; b < nbr; ++b) nsteps_min = std::min(nsteps_min, layers[b]->ntaps * (L0.chunk16 / 16));
     for (int ti = 0; ti < kNumTileCfgs; ++ti) {
         const TileCfg& t = kTileCfgs[ti];
         const int TM = t.WM * t.MI * 32;
@@ -1128,7 +1126,7 @@ static int launch_conv(hificar_handle* h, const ConvLayer* const* layers, int nb
         if (t.KS == 4 && (h->ksplit == 0 || nsteps_min < 2)) continue;
         if (t.KS == 1 && h->ksplit == 2 && nsteps_min >= 2) continue;
         const long long tiles_per_branch = (long long)nseq * ((rows + TM - 1) / TM) * ((L0.n_blocks32 + t.WN * t.NB - 1) / (t.WN * t.NB));
-        const long long total = tiles_per_branch * nbr * zr.n;
+        const long long total = tiles_per_branch * nbr * zrep;
         const int G = (int)std::min<long long>(total, h->num_cus);
         const int nchunks = L0.cin_pad / chunk;
         // LPT makespan estimate: max(heaviest tile, total / G), plus one light tile when the count does not divide
@@ -1143,14 +1141,14 @@ static int launch_conv(hificar_handle* h, const ConvLayer* const* layers, int nb
                 const int steps = layers[b]->ntaps * (chunk / 16);
                 c = (double)((steps + 3) / 4) * nchunks * slab * t.MI + 4000.0 + 600.0 * nchunks;
             }
-            total_cost += c * tiles_per_branch * zr.n;
+            total_cost += c * tiles_per_branch * zrep;
             heaviest = std::max(heaviest, c);
             lightest = std::min(lightest, c);
             cb[b] = c;
         }
         double worst = std::max(heaviest, total_cost / G);
-        if (h->use_lpt && !h->shared_chip && total > G && total <= 4096) {
-            // the makespan of the assignment the kernel will actually walk (get_schedule: longest tile first onto the least loaded workgroup).
+        if (!h->shared_chip && total > G && total <= 4096) {
+            // the makespan of the assignment the kernel will actually walk (lpt_lists: longest tile first onto the least loaded workgroup).
             // Round 4: the closed form below charged "+ half a light tile" whenever the tile count is not a multiple of the workgroups — 384
             // tiles of weight 12 : 8 : 4 on 256 workgroups balance exactly (12 | 8 + 4), and the 128-row tile it ruled out at C = 256 is 1.1 %
             // faster end to end than the 64-row one it picked.
@@ -1159,7 +1157,7 @@ static int launch_conv(hificar_handle* h, const ConvLayer* const* layers, int nb
             for (int w = 0; w < G; ++w) load.push(0.0);
             worst = 0.0;
             for (int b = 0; b < nbr; ++b)
-                for (long long i = 0; i < tiles_per_branch * zr.n; ++i) {
+                for (long long i = 0; i < tiles_per_branch * zrep; ++i) {
                     const double v = load.top() + cb[b];
                     load.pop();
                     load.push(v);
@@ -1181,146 +1179,65 @@ static int launch_conv(hificar_handle* h, const ConvLayer* const* layers, int nb
         if (worst < best * 0.98) {  // near-ties keep the earlier (taller) shape
             best = worst;
             tc = t;
-            best_ti = ti;
         }
     }
-    if (cached_pick == h->tile_picks.end()) {
-        if (h->tile_picks.size() > 20000) h->tile_picks.clear();  // (a very large number of distinct launch shapes: start over)
-        h->tile_picks.emplace(pick_key, best_ti);
-    }
-    const int TM = tc.WM * tc.MI * 32;
-    const int chunk_sel = L0.chunk16, RB = chunk_sel * 4;
-    const int nc16 = chunk_sel / 16;
-    MultiConvParams mp;
-    memset(&mp, 0, sizeof(mp));
-    double flops = 0.0, bytes = 0.0;
-    for (int b = 0; b < nbr; ++b) {
-        const ConvLayer& Lb = *layers[b];
-        if (Lb.n_blocks32 != L0.n_blocks32 || Lb.chunk16 != L0.chunk16 || Lb.cin_pad != L0.cin_pad)
-            return fail(HIFICAR_E_INVALID, "internal: branch shape mismatch");
-        fill_params(mp.p[b], Lb, rows, TM, io[b].res, io[b].y, rg);
-        mp.p[b].xs = io[b].xs;
-        mp.p[b].ys = io[b].ys;
-        if (io[b].x_slope >= 0.f) {
-            if (!f32) return fail(HIFICAR_E_INVALID, "internal: pre-activation input rows of %s outside the exact-fp32 layer-by-layer launches", Lb.name.c_str());
-            if (io[b].x_n < 1 || io[b].x_n > 4) return fail(HIFICAR_E_INVALID, "internal: %d input streams of %s", io[b].x_n, Lb.name.c_str());
-            mp.p[b].act_in = io[b].x_n;
-            for (int q = 0; q + 1 < io[b].x_n; ++q) mp.p[b].xs_more[q] = reinterpret_cast<const char*>(io[b].x_more[q]);
-            mp.p[b].slope_in = io[b].x_slope;
-        }
-        mp.p[b].mask_src = io[b].mask_src;
-        mp.p[b].mask_slope = io[b].mask_slope;
-        mp.p[b].x_seq_bytes = io[b].x_seq_bytes;
-        mp.p[b].x_row_bytes = io[b].x_row_bytes;
-        mp.p[b].x_rows = io[b].x_rows;
-        if (io[b].x_up > 1) {
-            if (rows % io[b].x_up != 0 || io[b].x_seq_bytes != 0 || io[b].x_row_bytes != 0)
-                return fail(HIFICAR_E_INVALID, "internal: upsampled input rows of %s", Lb.name.c_str());
-            mp.p[b].x_up = io[b].x_up;
-            mp.p[b].x_up_rcp = (unsigned)(0x100000000ull / (unsigned)io[b].x_up) + 1u;
-            mp.p[b].x_seq_bytes = (long long)(rows / io[b].x_up) * Lb.cin_pad * 4;
-        }
-        mp.p[b].zeros = h->d_zeros;
-        mp.p[b].slope_out = slope_out;
-        mp.p[b].cout_real = Lb.cout_pad;
-        if (f32) mp.p[b].w16 = reinterpret_cast<const bf16x8*>(Lb.d_w32);
-        const double pos = (double)nseq * rows;
-        flops += 2.0 * pos * Lb.cin * Lb.cout * Lb.K * zr.n;
-        bytes += 4.0 * (pos * Lb.cin_pad * (io[b].x_slope >= 0.f ? io[b].x_n : 1) / std::max(1, io[b].x_up) + pos * Lb.cout_total * ((io[b].res ? 1 : 0) + (io[b].y ? 1 : 0) + (io[b].ys ? 1 : 0)) +
-                        (double)Lb.cin * Lb.cout * Lb.K);
-    }
-    const size_t buf_bytes = round_up_sz((size_t)(TM + halo_all) * RB, 1024);
+    return tc;
+}
+
+// Kernel name of a plan as ProfScope wants it: the instantiation (hificar_launch.h), + "|layer xN" for per-layer rows in the profile (tools/layer_profile.py)
+static std::string plan_name(const hificar_handle* h, const ConvShape& s, const ConvLayer& L0, int nbr) {
+    static const char* const family[] = {"conv_f32do_kernel", "conv_bf16x3_kernel", "conv_bf16x3nb_kernel", "conv_sk_f32_kernel", "conv_sk_bf16x3_kernel",
+                                         "conv_pair_f32_kernel", "conv_pair_bf16x3_kernel"};
+    char kname[96];
+    int n = s.family == kConvSkF32 || s.family == kConvSkBf16x3 ? snprintf(kname, sizeof(kname), "%s<%d,%d>", family[s.family], s.mi, s.nc16)
+                                                                : snprintf(kname, sizeof(kname), "%s<%d,%d,%d,%d>", family[s.family], s.mi, s.wm, s.wn, s.nc16);
+    if (h->profile_detail) snprintf(kname + n, sizeof(kname) - n, "|%s x%d", L0.name.c_str(), nbr);
+    return kname;
+}
+
+static int build_conv_plan(hificar_handle* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, int zrep, hipStream_t stream, ConvPlan& pl) {
+    const ConvLayer& L0 = *layers[0];
+    const bool f32 = h->precision == HIFICAR_PREC_F32;
+    MultiConvParams& mp = pl.conv;
+    const TileCfg tc = pick_tile(h, layers, nbr, nseq, rows, zrep);
+    int halo_all = 0;
+    for (int b = 0; b < nbr; ++b) halo_all = std::max(halo_all, layers[b]->off_max - layers[b]->off_min);
+    const int TM = tc.WM * tc.MI * 32, nc16 = L0.chunk16 / 16;
+    const size_t buf_bytes = round_up_sz((size_t)(TM + halo_all) * L0.chunk16 * 4, 1024);
     const bool dout = f32 && tc.KS == 1;
-    const size_t lds = 2 * buf_bytes + (dout ? 0 : out_buf_bytes(tc));
+    pl.shape = {dout ? kConvF32do : tc.KS == 4 ? (f32 ? kConvSkF32 : kConvSkBf16x3) : tc.NB == 2 ? kConvBf16x3nb : kConvBf16x3, tc.MI, tc.WM, tc.WN, nc16};
+    pl.lds = 2 * buf_bytes + (dout ? 0 : out_buf_bytes(tc));
+    mp.buf_bytes = (int)buf_bytes;
     mp.n_branches = nbr;
     mp.nseq_tiles = nseq * ((rows + TM - 1) / TM);
     mp.ngroups = (L0.n_blocks32 + tc.WN * tc.NB - 1) / (tc.WN * tc.NB);
-    mp.total_tiles = nbr * zr.n * mp.ngroups * mp.nseq_tiles;
-    mp.buf_bytes = (int)buf_bytes;
-    mp.trace = nullptr;
-    mp.zrep = zr.n;
-    mp.zs_x = zr.zs_x;
-    mp.zs_w = zr.zs_w;
-    mp.zs_y = zr.zs_y;
-    mp.zs_b = zr.zs_b;
-    dim3 grid((unsigned)std::min(mp.total_tiles, h->num_cus), 1, 1);  // persistent: one workgroup per CU walks its tile list
+    mp.total_tiles = nbr * zrep * mp.ngroups * mp.nseq_tiles;
+    pl.grid = (unsigned)std::min(mp.total_tiles, h->num_cus);  // persistent: one workgroup per CU walks its tile list
     {   // one round of tiles and at least twice the activations in weight bytes (batch 8 measured neutral at 1.8 x): XCD-contiguous tile order (MultiConvParams::xcd_order)
         double wbytes = 0.0;
-        for (int b = 0; b < nbr; ++b) wbytes += 4.0 * layers[b]->cin_pad * layers[b]->cout_total * layers[b]->ntaps * zr.n;
-        const double abytes = 4.0 * nseq * rows * L0.cin_pad * nbr * zr.n;
-        mp.xcd_order = (h->xcd_order && mp.total_tiles <= h->num_cus && mp.total_tiles >= 16 && wbytes > 2.0 * abytes) ? 1 : 0;
+        for (int b = 0; b < nbr; ++b) wbytes += 4.0 * layers[b]->cin_pad * layers[b]->cout_total * layers[b]->ntaps * zrep;
+        const double abytes = 4.0 * nseq * rows * L0.cin_pad * nbr * zrep;
+        mp.xcd_order = (mp.total_tiles <= h->num_cus && mp.total_tiles >= 16 && wbytes > 2.0 * abytes) ? 1 : 0;
     }
     // every input row is staged once per channel group: more than two groups (upsampler 0's ten, a 1024-wide GEMM's eight) re-read it from the L2
     // instead of streaming it past the cache (r06a: 2.7 x / 3-7 x the algorithmic bytes fetched by those launches with non-temporal loads)
     mp.stage_cached = mp.ngroups > 2 ? 1 : 0;
-    // One round of tiles of ONE layer whose weights do not fit an XCD's 4-MB L2 (the discriminators' 1024-wide GEMM-form layers: 21 MB of weights,
-    // 17 row tiles x 8 channel groups): dealt out round-robin every XCD streams ALL the weights through its L2 (335 MB per launch); here every XCD
-    // gets a BLOCK of (row tiles x channel groups), so that both operands are re-used inside the XCD by workgroups that run in lock step — the
-    // split of the 8 XCDs into (pr x pg) that minimises row tiles / pr + channel groups / pg.  Workgroup w is dispatched to XCD w % 8
-    // (MI355X_MICROARCH.md: round-robin; an assumption for speed only — any mapping is correct).
-    if (mp.total_tiles <= h->num_cus && nbr == 1 && zr.n == 1 && mp.ngroups >= 2 && mp.nseq_tiles >= 8 && !h->shared_chip) {
-        const double wbytes1 = 4.0 * L0.cin_pad * L0.cout_total * L0.ntaps;
-        if (wbytes1 > 6.0e6) {
-            const int R = mp.nseq_tiles, Gc = mp.ngroups;
-            int bpr = 1, bpg = 8;
-            double bcost = 1e300;
-            for (int pr = 1; pr <= 8; pr *= 2) {
-                const int pg = 8 / pr;
-                if (pr > R || pg > Gc) continue;
-                const double c = (double)((R + pr - 1) / pr) + (double)((Gc + pg - 1) / pg);
-                if (c < bcost) bcost = c, bpr = pr, bpg = pg;
-            }
-            std::vector<std::vector<int>> per_xcd(8);
-            size_t maxblock = 0;
-            for (int x = 0; x < 8; ++x) {
-                const int xr = x / bpg, xg = x % bpg;
-                const int r0 = R * xr / bpr, r1 = R * (xr + 1) / bpr, g0 = Gc * xg / bpg, g1 = Gc * (xg + 1) / bpg;
-                for (int g2 = g0; g2 < g1; ++g2)
-                    for (int r2 = r0; r2 < r1; ++r2) per_xcd[(size_t)x].push_back(g2 * R + r2);  // tile id = channel group * row tiles + row tile
-                maxblock = std::max(maxblock, per_xcd[(size_t)x].size());
-            }
-            if (maxblock * 8 <= (size_t)h->num_cus && bcost < (double)(R + 1)) {
-                std::vector<std::vector<int>> lists(maxblock * 8);
-                for (int x = 0; x < 8; ++x)
-                    for (size_t l = 0; l < per_xcd[(size_t)x].size(); ++l) lists[l * 8 + (size_t)x].push_back(per_xcd[(size_t)x][l]);
-                const std::string key = std::string(f32 ? "f" : "c") + "|x2d|" + L0.name + "|" + std::to_string(R) + "x" + std::to_string(Gc) + "t" + std::to_string(TM) +
-                                        "w" + std::to_string(tc.WN) + "k" + std::to_string(tc.KS) + (tc.NB == 2 ? "b" : "");
-                grid = dim3((unsigned)lists.size(), 1, 1);
-                mp.xcd_order = 0;
-                int rc2 = put_schedule(h, key, lists, mp.total_tiles, stream, &mp.sched_start, &mp.sched_tiles);
-                if (rc2 != HIFICAR_OK) return rc2;
-            }
-        }
-    }
-    if (!mp.sched_start && h->use_lpt && mp.total_tiles > (int)grid.x) {
+    pl.name = plan_name(h, pl.shape, L0, nbr);
+    TileLists lists;
+    if (mp.total_tiles <= h->num_cus && nbr == 1 && zrep == 1 && mp.ngroups >= 2 && mp.nseq_tiles >= 8 && !h->shared_chip &&
+        4.0 * L0.cin_pad * L0.cout_total * L0.ntaps > 6.0e6)  // (one layer's weights well beyond an XCD's L2)
+        lists = xcd_block_lists(mp.nseq_tiles, mp.ngroups, h->num_cus);
+    if (!lists.empty()) {
+        pl.grid = (unsigned)lists.size();
+        mp.xcd_order = 0;
+    } else if (mp.total_tiles > (int)pl.grid) {
         std::vector<double> costs((size_t)mp.total_tiles);
-        const int tpb = mp.ngroups * mp.nseq_tiles;
-        std::string key = f32 ? "f" : "c";
-        for (int b = 0; b < nbr; ++b) {
-            key += "|" + layers[b]->name;
-            for (int i = 0; i < tpb * zr.n; ++i) costs[(size_t)b * tpb * zr.n + i] = layers[b]->ntaps + 1.0;  // + fixed per-tile overhead
-        }
-        if (zr.n > 1) key += "z" + std::to_string(zr.n);
-        key += "|" + std::to_string(nseq) + "x" + std::to_string((rows + TM - 1) / TM) + "t" + std::to_string(TM) + "w" + std::to_string(tc.WN) +
-               "k" + std::to_string(tc.KS) + (tc.NB == 2 ? "b" : "");
-        int rc2 = get_schedule(h, key, costs, (int)grid.x, stream, &mp.sched_start, &mp.sched_tiles);
-        if (rc2 != HIFICAR_OK) return rc2;
+        const int tpb = mp.ngroups * mp.nseq_tiles * zrep;
+        for (int b = 0; b < nbr; ++b)
+            for (int i = 0; i < tpb; ++i) costs[(size_t)b * tpb + i] = layers[b]->ntaps + 1.0;  // + fixed per-tile overhead
+        lists = lpt_lists(costs, (int)pl.grid);
     }
-    char kname[96];
-    if (dout) snprintf(kname, sizeof(kname), "conv_f32do_kernel<%d,%d,%d,%d>", tc.MI, tc.WM, tc.WN, nc16);
-    else if (tc.KS == 4) snprintf(kname, sizeof(kname), "%s<%d,%d>", f32 ? "conv_sk_f32_kernel" : "conv_sk_bf16x3_kernel", tc.MI, nc16);
-    else if (tc.NB == 2) snprintf(kname, sizeof(kname), "conv_bf16x3nb_kernel<%d,%d,%d,%d>", tc.MI, tc.WM, tc.WN, nc16);
-    else snprintf(kname, sizeof(kname), "conv_bf16x3_kernel<%d,%d,%d,%d>", tc.MI, tc.WM, tc.WN, nc16);
-    if (h->profile_detail) {  // per-layer rows in the profile (tools/layer_profile.py)
-        const size_t n = strlen(kname);
-        snprintf(kname + n, sizeof(kname) - n, "|%s x%d", L0.name.c_str(), nbr);
-    }
-    ProfScope prof(h, stream, kname, flops, bytes);
-    const ConvShape shape = {dout ? kConvF32do : tc.KS == 4 ? (f32 ? kConvSkF32 : kConvSkBf16x3) : tc.NB == 2 ? kConvBf16x3nb : kConvBf16x3,
-                             tc.MI, tc.WM, tc.WN, nc16};
-    const hipError_t e = conv_launch(shape, &mp, grid, lds, stream);
-    if (e != hipSuccess) return fail(HIFICAR_E_HIP, "conv launch (%s, %s) failed: %s", L0.name.c_str(), kname, hipGetErrorString(e));
-    return HIFICAR_OK;
+    return lists.empty() ? HIFICAR_OK : upload_schedule(h, lists, mp.total_tiles, stream, &mp.sched_start, &mp.sched_tiles);
 }
 
 // Fused conv1 -> LeakyReLU -> conv2 (+ residual) for C = 32 / 64 (conv_pair_bf16x3_kernel / conv_pair_f32_kernel).
@@ -1368,19 +1285,127 @@ static bool pair_eligible(const hificar_handle* h, const ConvLayer& a, const Con
     return true;
 }
 
-static int launch_pair(hificar_handle* h, const ConvLayer* const* l1, const ConvLayer* const* l2, int nbr, int nseq, int rows,
-                              const PairIOB* io, float slope, const Ragged& rg, hipStream_t stream) {
+static int build_pair_plan(hificar_handle* h, const ConvLayer* const* l1, const ConvLayer* const* l2, int nbr, int nseq, int rows, hipStream_t stream,
+                           ConvPlan& pl) {
     const int C = l1[0]->cin;
     bool small = true;
     for (int b = 0; b < nbr; ++b) small = small && pair_small_tiles(h, C, l2[b]->ntaps, nseq, rows);
     const int MI = small ? 1 : 4, WM = C == 64 ? 2 : 4;
     const int TMc = WM * MI * 32, RB = C * 4;
     const bool f32 = h->precision == HIFICAR_PREC_F32;
-    PairParams pp;
-    memset(&pp, 0, sizeof(pp));
-    int halo_max = 0;
+    PairParams& pp = pl.pair;
+    int halo_max = 0, tile = 0;
+    for (int b = 0; b < nbr; ++b) {
+        halo_max = std::max(halo_max, l1[b]->off_max - l1[b]->off_min);
+        const int tmo = TMc - (l2[b]->ntaps - 1);
+        pp.tiles_per_seq[b] = (rows + tmo - 1) / tmo;
+        pp.tile_start[b] = tile;
+        tile += nseq * pp.tiles_per_seq[b];
+    }
+    pp.tile_start[nbr] = tile;
+    pp.n_branches = nbr;
+    pp.nseq = nseq;
+    pp.in_bytes = (int)round_up_sz((size_t)(TMc + halo_max) * RB, 1024);
+    pp.ts_bytes = (int)std::max<size_t>((size_t)(TMc + 16) * RB, (size_t)TMc * (C + 4) * sizeof(float));  // TS and out-buffer alias
+    pl.lds = (size_t)pp.in_bytes + pp.ts_bytes;
+    if (pl.lds > 160 * 1024) return fail(HIFICAR_E_INVALID, "internal: pair kernel LDS too large (%zu)", pl.lds);
+    pl.grid = (unsigned)std::min(tile, h->num_cus);
+    pl.shape = {f32 ? kPairF32 : kPairBf16x3, MI, WM, 4 / WM, C / 16};
+    pl.name = plan_name(h, pl.shape, *l1[0], nbr);
+    if (tile <= (int)pl.grid) return HIFICAR_OK;
+    std::vector<double> costs((size_t)tile);
+    for (int b = 0; b < nbr; ++b)
+        for (int i = pp.tile_start[b]; i < pp.tile_start[b + 1]; ++i) costs[i] = l1[b]->ntaps + l2[b]->ntaps + 2.0;
+    return upload_schedule(h, lpt_lists(costs, (int)pl.grid), tile, stream, &pp.sched_start, &pp.sched_tiles);
+}
+
+// The plan of a launch of layers `a` (launch_pair: conv1 `a`, conv2 `b` of every branch), built on the first launch of that shape — only that
+// touches vectors, strings or the arenas — on the launch's stream: a new schedule is uploaded on the stream that first needs it (publish()
+// in hificar_ar_loop).  Null: failed, *rc says how.
+static const ConvPlan* get_plan(hificar_handle* h, const ConvLayer* const* a, const ConvLayer* const* b, int nbr, int nseq, int rows, int zrep,
+                                hipStream_t stream, int* rc) {
+    *rc = HIFICAR_OK;
+    PlanKey k = {{}, nseq, rows, zrep, (h->precision == HIFICAR_PREC_F32 ? 1 : 0) | (h->train ? 2 : 0) | (h->shared_chip ? 4 : 0) | (b ? 8 : 0)};
+    for (int i = 0; i < nbr; ++i) k.layers[i] = a[i];
+    for (int i = 0; b && i < nbr; ++i) k.layers[3 + i] = b[i];
+    auto it = h->plans.find(k);
+    if (it == h->plans.end()) {
+        ConvPlan pl;
+        if (h->plans.size() > 20000) *rc = evict_plans(h);  // (a very large number of distinct launch shapes: start over)
+        if (*rc == HIFICAR_OK)
+            *rc = b ? build_pair_plan(h, a, b, nbr, nseq, rows, stream, pl) : build_conv_plan(h, a, nbr, nseq, rows, zrep, stream, pl);
+        if (*rc != HIFICAR_OK) return nullptr;
+        it = h->plans.emplace(k, std::move(pl)).first;
+    }
+    return &it->second;
+}
+
+static int launch_conv(hificar_handle* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, const ConvIO* io,
+                              float slope_out, const Ragged& rg, hipStream_t stream, const ConvRep& zr = ConvRep()) {
+    int rc;
+    const ConvPlan* const pl = get_plan(h, layers, nullptr, nbr, nseq, rows, zr.n, stream, &rc);
+    if (!pl) return rc;
+    const int TM = pl->shape.wm * pl->shape.mi * 32;
+    const ConvLayer& L0 = *layers[0];
+    const bool f32 = h->precision == HIFICAR_PREC_F32;  // rows are plain fp32 LeakyReLU(x) instead of split rows
+    MultiConvParams mp = pl->conv;
     double flops = 0.0, bytes = 0.0;
-    int tile = 0;
+    for (int b = 0; b < nbr; ++b) {
+        const ConvLayer& Lb = *layers[b];
+        if (Lb.n_blocks32 != L0.n_blocks32 || Lb.chunk16 != L0.chunk16 || Lb.cin_pad != L0.cin_pad)
+            return fail(HIFICAR_E_INVALID, "internal: branch shape mismatch");
+        fill_params(mp.p[b], Lb, rows, TM, io[b].res, io[b].y, rg);
+        mp.p[b].xs = io[b].xs;
+        mp.p[b].ys = io[b].ys;
+        if (io[b].x_slope >= 0.f) {
+            if (!f32) return fail(HIFICAR_E_INVALID, "internal: pre-activation input rows of %s outside the exact-fp32 layer-by-layer launches", Lb.name.c_str());
+            if (io[b].x_n < 1 || io[b].x_n > 4) return fail(HIFICAR_E_INVALID, "internal: %d input streams of %s", io[b].x_n, Lb.name.c_str());
+            mp.p[b].act_in = io[b].x_n;
+            for (int q = 0; q + 1 < io[b].x_n; ++q) mp.p[b].xs_more[q] = reinterpret_cast<const char*>(io[b].x_more[q]);
+            mp.p[b].slope_in = io[b].x_slope;
+        }
+        mp.p[b].mask_src = io[b].mask_src;
+        mp.p[b].mask_slope = io[b].mask_slope;
+        mp.p[b].x_seq_bytes = io[b].x_seq_bytes;
+        mp.p[b].x_row_bytes = io[b].x_row_bytes;
+        mp.p[b].x_rows = io[b].x_rows;
+        if (io[b].x_up > 1) {
+            if (rows % io[b].x_up != 0 || io[b].x_seq_bytes != 0 || io[b].x_row_bytes != 0)
+                return fail(HIFICAR_E_INVALID, "internal: upsampled input rows of %s", Lb.name.c_str());
+            mp.p[b].x_up = io[b].x_up;
+            mp.p[b].x_up_rcp = (unsigned)(0x100000000ull / (unsigned)io[b].x_up) + 1u;
+            mp.p[b].x_seq_bytes = (long long)(rows / io[b].x_up) * Lb.cin_pad * 4;
+        }
+        mp.p[b].zeros = h->d_zeros;
+        mp.p[b].slope_out = slope_out;
+        mp.p[b].cout_real = Lb.cout_pad;
+        if (f32) mp.p[b].w16 = reinterpret_cast<const bf16x8*>(Lb.d_w32);
+        const double pos = (double)nseq * rows;
+        flops += 2.0 * pos * Lb.cin * Lb.cout * Lb.K * zr.n;
+        bytes += 4.0 * (pos * Lb.cin_pad * (io[b].x_slope >= 0.f ? io[b].x_n : 1) / std::max(1, io[b].x_up) + pos * Lb.cout_total * ((io[b].res ? 1 : 0) + (io[b].y ? 1 : 0) + (io[b].ys ? 1 : 0)) +
+                        (double)Lb.cin * Lb.cout * Lb.K);
+    }
+    mp.zrep = zr.n;
+    mp.zs_x = zr.zs_x;
+    mp.zs_w = zr.zs_w;
+    mp.zs_y = zr.zs_y;
+    mp.zs_b = zr.zs_b;
+    ProfScope prof(h, stream, pl->name, flops, bytes);
+    const hipError_t e = conv_launch(pl->shape, &mp, dim3(pl->grid, 1, 1), pl->lds, stream);
+    if (e != hipSuccess) return fail(HIFICAR_E_HIP, "conv launch (%s, %s) failed: %s", L0.name.c_str(), pl->name.c_str(), hipGetErrorString(e));
+    return HIFICAR_OK;
+}
+
+static int launch_pair(hificar_handle* h, const ConvLayer* const* l1, const ConvLayer* const* l2, int nbr, int nseq, int rows,
+                              const PairIOB* io, float slope, const Ragged& rg, hipStream_t stream) {
+    int rc;
+    const ConvPlan* const pl = get_plan(h, l1, l2, nbr, nseq, rows, 1, stream, &rc);
+    if (!pl) return rc;
+    const int TMc = pl->shape.wm * pl->shape.mi * 32;
+    const int C = l1[0]->cin;
+    const bool f32 = h->precision == HIFICAR_PREC_F32;
+    PairParams pp = pl->pair;
+    double flops = 0.0, bytes = 0.0;
     for (int b = 0; b < nbr; ++b) {
         const ConvLayer& A = *l1[b];
         const ConvLayer& B = *l2[b];
@@ -1395,46 +1420,13 @@ static int launch_pair(hificar_handle* h, const ConvLayer* const* l1, const Conv
         pp.p2[b].ys = io[b].ys;
         pp.p2[b].slope_out = slope;
         pp.p2[b].cout_real = C;
-        halo_max = std::max(halo_max, A.off_max - A.off_min);
-        const int tmo = TMc - (B.ntaps - 1);
-        pp.tiles_per_seq[b] = (rows + tmo - 1) / tmo;
-        pp.tile_start[b] = tile;
-        tile += nseq * pp.tiles_per_seq[b];
         const double pos = (double)nseq * rows;
         flops += 2.0 * pos * C * C * (A.K + B.K);
         bytes += 4.0 * (pos * C * (3 + (io[b].ys ? 1 : 0)) + (double)C * C * (A.K + B.K));
     }
-    pp.tile_start[nbr] = tile;
-    pp.n_branches = nbr;
-    pp.nseq = nseq;
-    pp.in_bytes = (int)round_up_sz((size_t)(TMc + halo_max) * RB, 1024);
-    pp.ts_bytes = (int)std::max<size_t>((size_t)(TMc + 16) * RB, (size_t)TMc * (C + 4) * sizeof(float));  // TS and out-buffer alias
     pp.slope_mid = slope;
-    pp.trace = nullptr;
-    const size_t lds = (size_t)pp.in_bytes + pp.ts_bytes;
-    if (lds > 160 * 1024) return fail(HIFICAR_E_INVALID, "internal: pair kernel LDS too large (%zu)", lds);
-    dim3 grid((unsigned)std::min(tile, h->num_cus), 1, 1);
-    if (h->use_lpt && tile > (int)grid.x) {
-        std::vector<double> costs((size_t)tile);
-        std::string key = "p";
-        for (int b = 0; b < nbr; ++b) {
-            key += "|" + l1[b]->name;
-            for (int i = pp.tile_start[b]; i < pp.tile_start[b + 1]; ++i) costs[i] = l1[b]->ntaps + l2[b]->ntaps + 2.0;
-        }
-        key += "|" + std::to_string(nseq);
-        for (int b = 0; b < nbr; ++b) key += "x" + std::to_string(pp.tiles_per_seq[b]);
-        int rc2 = get_schedule(h, key, costs, (int)grid.x, stream, &pp.sched_start, &pp.sched_tiles);
-        if (rc2 != HIFICAR_OK) return rc2;
-    }
-    char kname[96];
-    snprintf(kname, sizeof(kname), "%s<%d,%d,%d,%d>", f32 ? "conv_pair_f32_kernel" : "conv_pair_bf16x3_kernel", MI, WM, 4 / WM, C / 16);
-    if (h->profile_detail) {
-        const size_t n = strlen(kname);
-        snprintf(kname + n, sizeof(kname) - n, "|%s x%d", l1[0]->name.c_str(), nbr);
-    }
-    ProfScope prof(h, stream, kname, flops, bytes);
-    const ConvShape shape = {f32 ? kPairF32 : kPairBf16x3, MI, WM, 4 / WM, C / 16};
-    const hipError_t e = conv_launch(shape, &pp, grid, lds, stream);
+    ProfScope prof(h, stream, pl->name, flops, bytes);
+    const hipError_t e = conv_launch(pl->shape, &pp, dim3(pl->grid, 1, 1), pl->lds, stream);
     if (e != hipSuccess) return fail(HIFICAR_E_HIP, "pair launch (%s) failed: %s", l1[0]->name.c_str(), hipGetErrorString(e));
     return HIFICAR_OK;
 }
