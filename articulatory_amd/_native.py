@@ -35,6 +35,9 @@ SYMBOLS = (
     "hificar_ar_loop_ragged",
     "hificar_ar_loop_packed",
     "hificar_ar_step",
+    "hificar_ar_loop_cond",
+    "hificar_ar_loop_packed_cond",
+    "hificar_ar_step_cond",
     "hificar_macs",
     "hificar_pcm16",
     "hificar_profile_begin",
@@ -283,6 +286,14 @@ def load_library():
     lib.hificar_ar_step.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp,
                                     ctypes.c_size_t, vp]
     lib.hificar_ar_step.restype = ctypes.c_int
+    lib.hificar_ar_loop_cond.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
+    lib.hificar_ar_loop_cond.restype = ctypes.c_int
+    lib.hificar_ar_loop_packed_cond.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp,
+                                                ctypes.c_size_t, vp]
+    lib.hificar_ar_loop_packed_cond.restype = ctypes.c_int
+    lib.hificar_ar_step_cond.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int, vp,
+                                         ctypes.c_int, vp, vp, ctypes.c_size_t, vp]
+    lib.hificar_ar_step_cond.restype = ctypes.c_int
     lib.hificar_macs.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     lib.hificar_macs.restype = ctypes.c_double
     lib.hificar_pcm16.argtypes = [vp, vp, ctypes.c_size_t, vp]

@@ -8,7 +8,9 @@
   side by side and ``ar_loop_ragged`` B utterances of different lengths (each exactly as if it were alone),
   which the reference cannot.  The WSOLA variant (``do_wsola``: half-overlapping chunks,
   decode.py:84-100) is a per-chunk loop over ``model.forward`` as in the reference, since each chunk's
-  context comes from the *middle* of the previous chunk.
+  context comes from the *middle* of the previous chunk.  Speaker- / phoneme-conditioned models (``spk_id=`` / ``ph=``; the
+  reference's loop has neither and cannot run one) go through the same calls: every chunk's forward is the reference's
+  ``forward(c, spk_id=, ar=prev, ph=)`` (hifigan.py:212-220) with the utterance's speaker and the chunk's slice of its phoneme row.
 * ``main`` (reference decode.py:103-358, console script ``articulatory-decode``): same flags, config
   merge, scp / dump-dir inputs (``.npy`` features), ``--normalize-before``, PCM_16 ``<utt>_gen.wav``
   outputs and RTF report, for the a2w dataset modes of the HiFi-GAN / HiFi-CAR generator.
@@ -33,9 +35,32 @@ def _chunk_frames(config, params_key="generator_params"):
     return in_chunk_len, past_out_len
 
 
-def ar_loop(model, x, config, do_wsola=False, modality=None, generator2=False):
+def _given(**kw):
+    """The keyword arguments that were given: an unconditioned model is called exactly as before."""
+    return {k: v for k, v in kw.items() if v is not None}
+
+
+def _spk_tensor(spk_ids, device):
+    return None if spk_ids is None else torch.as_tensor([int(s) for s in spk_ids], dtype=torch.int64, device=device)
+
+
+def _ph_tensor(phs, lens, device):
+    """list of (T_i,) phoneme rows -> (B, T_max) zero-padded, like the features."""
+    if phs is None:
+        return None
+    out = torch.zeros((len(phs), max(lens)), dtype=torch.int64, device=device)
+    for i, p in enumerate(phs):
+        p = torch.as_tensor(p).reshape(-1)
+        if p.shape[0] != lens[i]:
+            raise ValueError(f"utterance {i}: {p.shape[0]} phoneme indices for {lens[i]} frames")
+        out[i, :lens[i]] = p.to(device)
+    return out
+
+
+def ar_loop(model, x, config, do_wsola=False, modality=None, generator2=False, spk_id=None, ph=None):
     """x: (art_len, num_feats) tensor on the model's device -> (audio_len,) tensor
-    (``do_wsola``: -> (list of chunk waveforms, list of chunk inputs), as the reference returns)."""
+    (``do_wsola``: -> (list of chunk waveforms, list of chunk inputs), as the reference returns).
+    ``spk_id``: the utterance's speaker index (use_spk_id models); ``ph``: its (art_len,) phoneme indices (use_ph models)."""
     if modality is not None or generator2:
         raise NotImplementedError("ar_loop: multi-modality / generator2 variants are not built (SURVEY.md §8 f3)")
     if config.get("dataset_mode", "a2w") == "w2a":
@@ -45,17 +70,26 @@ def ar_loop(model, x, config, do_wsola=False, modality=None, generator2=False):
         x = x.unsqueeze(1)
     if not do_wsola:
         c = x.transpose(0, 1).unsqueeze(0)  # (1, num_feats, art_len)
-        return model.ar_synthesis(c, in_chunk_len)[0]
+        return model.ar_synthesis(c, in_chunk_len, **_given(spk_id=None if spk_id is None else _spk_tensor([spk_id], x.device),
+                                                            ph=_ph_tensor(None if ph is None else [ph], [x.shape[0]], x.device)))[0]
 
     # decode.py:84-100: chunks start every in_chunk_len/2 frames and are in_chunk_len (+ extra_art) long
     extra_art = config["generator_params"]["extra_art"]
     audio_chunk_len = config["batch_max_steps"]
     assert in_chunk_len % 2 == 0
-    ins = [x[i:i + in_chunk_len + int(extra_art)] for i in range(0, len(x), int(in_chunk_len / 2))]
+    starts = list(range(0, len(x), int(in_chunk_len / 2)))
+    ins = [x[i:i + in_chunk_len + int(extra_art)] for i in starts]
+    cond = {}
+    if spk_id is not None:
+        cond["spk_id"] = _spk_tensor([spk_id], x.device)
+    if ph is not None:
+        ph = _ph_tensor([ph], [x.shape[0]], x.device)
     prev_samples = torch.zeros((1, 1, past_out_len), dtype=x.dtype, device=x.device)
     outs = []
     for art_i, art in enumerate(ins):
-        signal = model(art.unsqueeze(0).permute(0, 2, 1), ar=prev_samples)  # (1, 1, audio_chunk_length)
+        if ph is not None:
+            cond["ph"] = ph[:, starts[art_i]:starts[art_i] + len(art)]
+        signal = model(art.unsqueeze(0).permute(0, 2, 1), ar=prev_samples, **cond)  # (1, 1, audio_chunk_length)
         outs.append(signal[0][0])
         if art_i < len(ins) - 1:
             prev_samples = signal[:, :, int(audio_chunk_len / 2) - past_out_len:int(audio_chunk_len / 2)]
@@ -63,10 +97,10 @@ def ar_loop(model, x, config, do_wsola=False, modality=None, generator2=False):
     return outs, ins
 
 
-def ar_loop_batch(model, xs, config):
-    """xs: (B, art_len, num_feats) equal-length utterances -> (B, audio_len)."""
+def ar_loop_batch(model, xs, config, spk_id=None, ph=None):
+    """xs: (B, art_len, num_feats) equal-length utterances -> (B, audio_len).  ``spk_id`` (B,) / ``ph`` (B, art_len) as in ``ar_loop``."""
     in_chunk_len, _ = _chunk_frames(config)
-    return model.ar_synthesis(xs.permute(0, 2, 1), in_chunk_len)
+    return model.ar_synthesis(xs.permute(0, 2, 1), in_chunk_len, **_given(spk_id=spk_id, ph=ph))
 
 
 def pad_utterances(xs):
@@ -78,14 +112,17 @@ def pad_utterances(xs):
     return out, lens
 
 
-def ar_loop_ragged(model, xs, config, batch=64):
+def ar_loop_ragged(model, xs, config, batch=64, spk_id=None, ph=None):
     """xs: list of (T_i, num_feats) tensors of any lengths -> list of (hop * T_i,) waveforms; every utterance gets the
     result of ``ar_loop`` on it alone (its own short tail chunk included).  One device call for the whole list: at most
-    ``batch`` utterances are in flight and a finished one is replaced by the next (longest first, so the tail is short)."""
+    ``batch`` utterances are in flight and a finished one is replaced by the next (longest first, so the tail is short).
+    ``spk_id``: list of speaker indices, ``ph``: list of (T_i,) phoneme rows, one per utterance."""
     in_chunk_len, _ = _chunk_frames(config)
     order = sorted(range(len(xs)), key=lambda i: -int(xs[i].shape[0]))
     padded, lens = pad_utterances([xs[i] for i in order])
-    y = model.ar_synthesis_packed(padded.permute(0, 2, 1), in_chunk_len, lens, batch=batch)
+    y = model.ar_synthesis_packed(padded.permute(0, 2, 1), in_chunk_len, lens, batch=batch,
+                                  **_given(spk_id=None if spk_id is None else _spk_tensor([spk_id[i] for i in order], padded.device),
+                                           ph=None if ph is None else _ph_tensor([ph[i] for i in order], lens, padded.device)))
     hop = y.shape[1] // padded.shape[1]
     out = [None] * len(xs)
     for k, i in enumerate(order):
@@ -177,6 +214,60 @@ def iter_features(feats_scp=None, dumpdir=None, fmt="npy"):
     return load_features(list_features(feats_scp, dumpdir, fmt))
 
 
+def add_conditioning_arguments(parser):
+    """--utt2spk / --spk-list / --ph-scp: who speaks / which phoneme each frame carries, for use_spk_id / use_ph checkpoints (not in the
+    reference, whose decoders cannot run such a model)."""
+    parser.add_argument("--utt2spk", default=None, type=str, help="'utt_id speaker' lines: the speaker of every utterance (use_spk_id models)")
+    parser.add_argument("--spk-list", default=None, type=str,
+                        help="one speaker per line, in the training set's order (the index is the model's spk_id); "
+                             "default: the sorted speakers of --utt2spk, as training derives them")
+    parser.add_argument("--ph-scp", default=None, type=str,
+                        help="'utt_id path.npy' lines: one phoneme index per feature frame (use_ph models)")
+
+
+def load_conditioning(config, utts, utt2spk=None, spk_list=None, ph_scp=None):
+    """The tables a conditioned checkpoint needs, checked against the model's configuration and the utterance list without touching the
+    GPU: a ``Conditioning`` (articulatory_amd/bin/train.py), or None for an unconditioned model."""
+    gp = config.get("generator_params", {})
+    use_spk, use_ph = bool(gp.get("use_spk_id", False)), bool(gp.get("use_ph", False))
+    if use_spk and not utt2spk:
+        raise ValueError("the checkpoint is speaker-conditioned (use_spk_id): --utt2spk is required")
+    if use_ph and not ph_scp:
+        raise ValueError("the checkpoint is phoneme-conditioned (use_ph): --ph-scp is required")
+    if (utt2spk or spk_list) and not use_spk:
+        raise ValueError("--utt2spk / --spk-list given, but the checkpoint is not speaker-conditioned (use_spk_id)")
+    if ph_scp and not use_ph:
+        raise ValueError("--ph-scp given, but the checkpoint is not phoneme-conditioned (use_ph)")
+    if not (use_spk or use_ph):
+        return None
+    from articulatory_amd.bin.train import Conditioning
+
+    spks = None
+    if spk_list:
+        with open(spk_list) as f:
+            spks = [line.strip() for line in f if line.strip()]
+    cond = Conditioning(utt2spk=utt2spk, ph_scp=ph_scp, spks=spks)
+    if use_spk and len(cond.spks) > int(gp["num_spk"]):
+        raise ValueError(f"{len(cond.spks)} speakers for a model with num_spk={gp['num_spk']}: pass the training set's --spk-list")
+    for utt in utts:
+        if use_spk and utt not in cond.utt2spk:
+            raise ValueError(f"utterance {utt!r} is missing from --utt2spk")
+        if use_ph and utt not in cond.ph:
+            raise ValueError(f"utterance {utt!r} is missing from --ph-scp")
+    return cond
+
+
+def utterance_conditioning(cond, utt_id, frames):
+    """(spk_id or None, (frames,) phoneme indices or None) of one utterance."""
+    if cond is None:
+        return None, None
+    e = cond.extras(utt_id, frames)
+    ph = e.get("ph")
+    if ph is not None and len(ph) != frames:
+        raise ValueError(f"utterance {utt_id!r}: {len(ph)} phoneme indices for {frames} frames")
+    return e.get("spk_id"), (None if ph is None else torch.as_tensor(np.asarray(ph, dtype=np.int64)))
+
+
 def get_parser():
     parser = argparse.ArgumentParser(description="Decode dumped features with trained generator.")
     parser.add_argument("--feats-scp", "--scp", default=None, type=str,
@@ -195,18 +286,36 @@ def get_parser():
                         help="utterances synthesised per device call (any lengths; not in the reference, which is batch-1)")
     parser.add_argument("--dry-run", default=False, action="store_true",
                         help="print this rank's share of the utterance list as one JSON line and exit (no GPU needed; not in the reference)")
+    add_conditioning_arguments(parser)
     return parser
 
 
-def decode_dataset(model, items, config, device, outdir, normalize_before=False, writer=None, batch_size=1):
+def decode_dataset(model, items, config, device, outdir, normalize_before=False, writer=None, batch_size=1, cond=None):
     """The generation loop of decode.py:292-351 for the a2w modes.  Returns (n_utterances, average RTF).
-    ``batch_size`` > 1: ragged batches of utterances per device call (RTF = batch time / batch audio)."""
+    ``batch_size`` > 1: ragged batches of utterances per device call (RTF = batch time / batch audio).
+    ``cond``: the ``Conditioning`` of a speaker- / phoneme-conditioned model (``load_conditioning``)."""
     from articulatory_amd.bin.predict_wav import write_wav
 
     writer = writer or write_wav
     use_ar = bool(config["generator_params"].get("use_ar", False))
     do_wsola = bool(config.get("wsola", False))
     total_rtf, n = 0.0, 0
+    has_spk = cond is not None and cond.utt2spk is not None
+    has_ph = cond is not None and cond.ph is not None
+
+    def batch_cond(batch):
+        """(list of speaker indices or None, list of phoneme rows or None) of a batch of (utt_id, features)."""
+        pairs = [utterance_conditioning(cond, u, int(c.shape[0])) for u, c in batch]
+        return [p[0] for p in pairs] if has_spk else None, [p[1] for p in pairs] if has_ph else None
+
+    def forward_cond(spks, phs, lens):
+        kw = {}
+        if spks is not None:
+            kw["spk_id"] = _spk_tensor(spks, device)
+        if phs is not None:
+            kw["ph"] = _ph_tensor(phs, lens, device)
+        return kw
+
     if batch_size > 1 and not do_wsola:
         with torch.no_grad():
             feats = ((u, torch.tensor(c, dtype=torch.float).to(device)) for u, c in items)
@@ -214,13 +323,15 @@ def decode_dataset(model, items, config, device, outdir, normalize_before=False,
             for batch in (windows(feats, 8 * batch_size) if use_ar else length_batches(feats, batch_size)):
                 start = time.time()
                 xs = [c for _, c in batch]
+                spks, phs = batch_cond(batch)
                 if use_ar:
-                    ys = ar_loop_ragged(model, xs, config, batch=batch_size)
+                    ys = ar_loop_ragged(model, xs, config, batch=batch_size, spk_id=spks, ph=phs)
                 else:
                     if normalize_before:
                         xs = [(c - model.mean) / model.scale for c in xs]
                     padded, lens = pad_utterances(xs)
-                    yb = model(padded.permute(0, 2, 1), lengths=lens)
+                    yb = model(padded.permute(0, 2, 1), lengths=lens, **forward_cond(spks, phs, lens))
+                    yb = yb[0] if isinstance(yb, tuple) else yb  # (use_ph_loss: (out, ph_out))
                     hop = yb.shape[2] // padded.shape[1]
                     ys = [yb[i, 0, :hop * m] for i, m in enumerate(lens)]
                 ys = [y.cpu().numpy() for y in ys]  # device -> host: the synchronisation point the RTF needs
@@ -234,8 +345,14 @@ def decode_dataset(model, items, config, device, outdir, normalize_before=False,
         for utt_id, c in items:
             c = torch.tensor(c, dtype=torch.float).to(device)
             start = time.time()
+            spk, ph = utterance_conditioning(cond, utt_id, int(c.shape[0]))
             if use_ar:
-                y = ar_loop(model, c, config, do_wsola=do_wsola)
+                y = ar_loop(model, c, config, do_wsola=do_wsola, spk_id=spk, ph=ph)
+            elif cond is not None:  # inference() has no way to say who speaks (hifigan.py:298-314): the forward it wraps
+                x = (c - model.mean) / model.scale if normalize_before else c
+                y = model(x.transpose(1, 0).unsqueeze(0), **forward_cond(None if spk is None else [spk], None if ph is None else [ph],
+                                                                       [int(c.shape[0])]))
+                y = (y[0] if isinstance(y, tuple) else y).view(-1)
             else:
                 y = model.inference(c, normalize_before=normalize_before).view(-1)
             if not do_wsola:
@@ -280,6 +397,8 @@ def main(argv=None):
         raise NotImplementedError("feature transforms are not built")
     pairs = list_features(args.feats_scp, args.dumpdir, config.get("format", "npy"))
     logging.info(f"The number of features to be decoded = {len(pairs)}.")
+    # a conditioned checkpoint: its tables are read and checked against the whole list here, before any GPU is touched
+    cond = load_conditioning(config, [u for u, _ in pairs], args.utt2spk, args.spk_list, args.ph_scp)
 
     # under torchrun (one process per GPU) every rank decodes its own share of the list and writes its own files
     from articulatory_amd.bin.shard import shard_items
@@ -307,7 +426,7 @@ def main(argv=None):
     model = model.eval().to(device)
     print(sum(p.numel() for p in model.parameters() if p.requires_grad))
     n, rtf = decode_dataset(model, items, config, device, config["outdir"], normalize_before=args.normalize_before,
-                            batch_size=args.batch_size)
+                            batch_size=args.batch_size, cond=cond)
     logging.info(f"Finished generation of {n} utterances (RTF = {rtf:.03f}).")
 
 

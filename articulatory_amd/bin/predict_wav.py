@@ -18,7 +18,8 @@ import numpy as np
 import torch
 import yaml
 
-from articulatory_amd.bin.decode import ar_loop, ar_loop_ragged, windows
+from articulatory_amd.bin.decode import (add_conditioning_arguments, ar_loop, ar_loop_ragged, load_conditioning, utterance_conditioning,
+                                         windows)
 from articulatory_amd.utils import load_model
 from articulatory_amd.utils.scp import load_scp_value
 
@@ -65,14 +66,23 @@ def get_parser():
     parser.add_argument("--verbose", type=int, default=1, help="logging level. higher is more logging. (default=1)")
     parser.add_argument("--batch-size", type=int, default=1,
                         help="synthesise up to this many utterances (any lengths) per device call (extension; default=1)")
+    add_conditioning_arguments(parser)
     return parser
 
 
-def synthesize_file_list(model, fids, featps, config, device, outdir, batch_size=1, writer=write_wav):
+def synthesize_file_list(model, fids, featps, config, device, outdir, batch_size=1, writer=write_wav, cond=None):
     """The generation loop of predict_wav.py:124-137.  ``batch_size`` > 1 (not in the reference): AR utterances are
-    synthesised ``batch_size`` at a time, whatever their lengths — each exactly as if it were alone."""
+    synthesised ``batch_size`` at a time, whatever their lengths — each exactly as if it were alone.
+    ``cond``: the ``Conditioning`` of a speaker- / phoneme-conditioned AR model (decode.load_conditioning)."""
     use_ar = bool(config["generator_params"].get("use_ar", False))
     written = []
+    if cond is not None and not use_ar:
+        raise NotImplementedError("predict_wav: conditioned models are synthesised through the AR loop only (use decode)")
+
+    def conds(batch):
+        pairs = [utterance_conditioning(cond, fid, int(c.shape[0])) for fid, c in batch]
+        return dict(spk_id=[p[0] for p in pairs] if cond is not None and cond.utt2spk is not None else None,
+                    ph=[p[1] for p in pairs] if cond is not None and cond.ph is not None else None)
 
     def kept():
         for fid, featp in zip(fids, featps):
@@ -83,14 +93,19 @@ def synthesize_file_list(model, fids, featps, config, device, outdir, batch_size
     with torch.no_grad():
         if use_ar and batch_size > 1:
             for batch in windows(kept(), 8 * batch_size):  # one device call per window, batch_size utterances in flight
-                ys = [ar_loop(model, batch[0][1], config)] if len(batch) == 1 else ar_loop_ragged(model, [c for _, c in batch], config, batch=batch_size)
+                kw = conds(batch)
+                if len(batch) == 1:
+                    ys = [ar_loop(model, batch[0][1], config, spk_id=kw["spk_id"] and kw["spk_id"][0], ph=kw["ph"] and kw["ph"][0])]
+                else:
+                    ys = ar_loop_ragged(model, [c for _, c in batch], config, batch=batch_size, **kw)
                 for (fid, _), y in zip(batch, ys):
                     writer(os.path.join(outdir, fid + ".wav"), y.cpu().numpy(), config["sampling_rate"])
                     written.append(fid)
             return written
         for fid, c in kept():
             if use_ar:
-                y = ar_loop(model, c, config)
+                spk, ph = utterance_conditioning(cond, fid, int(c.shape[0]))
+                y = ar_loop(model, c, config, spk_id=spk, ph=ph)
             else:
                 if len(c.shape) == 1:
                     c = c.long()
@@ -114,6 +129,7 @@ def main(argv=None):
         config = yaml.load(f, Loader=yaml.Loader)
     config.update(vars(args))
     fids, featps = read_scp(args.feats_scp)
+    cond = load_conditioning(config, fids, args.utt2spk, args.spk_list, args.ph_scp)  # checked before the GPU is touched
 
     if not torch.cuda.is_available():
         raise RuntimeError("predict_wav: no GPU visible; this package has no CPU synthesis path")
@@ -128,7 +144,7 @@ def main(argv=None):
     model.remove_weight_norm()
     model = model.eval().to(device)
     print(sum(p.numel() for p in model.parameters() if p.requires_grad))
-    synthesize_file_list(model, fids, featps, config, device, config["outdir"], batch_size=args.batch_size)
+    synthesize_file_list(model, fids, featps, config, device, config["outdir"], batch_size=args.batch_size, cond=cond)
 
 
 if __name__ == "__main__":

@@ -1874,12 +1874,20 @@ extern "C" int hificar_forward(hificar_handle* h, const float* c, const float* a
     return hificar_forward_ragged(h, c, ar, nullptr, out, B, T, workspace, workspace_bytes, stream);
 }
 
-extern "C" int hificar_ar_loop_ragged(hificar_handle* h, const float* c, const int32_t* lengths, const int32_t* lengths_host,
-                                      float* out, int B, int T_total, int chunk_frames, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
+// The conditioning pointers of a *_cond AR entry point against the model: each is needed exactly when the model uses it.
+static int check_cond_args(const hificar_handle* h, const char* who, const void* spk, const void* ph) {
+    if (h->cfg.use_spk_id && !spk) return fail(HIFICAR_E_INVALID, "%s: use_spk_id model needs spk_id (got NULL)", who);
+    if (h->cfg.use_ph && !ph) return fail(HIFICAR_E_INVALID, "%s: use_ph model needs ph (got NULL)", who);
+    if (!h->cfg.use_spk_id && spk) return fail(HIFICAR_E_INVALID, "%s: spk_id given to a model built with use_spk_id=false", who);
+    if (!h->cfg.use_ph && ph) return fail(HIFICAR_E_INVALID, "%s: ph given to a model built with use_ph=false", who);
+    return HIFICAR_OK;
+}
+
+extern "C" int hificar_ar_loop_cond(hificar_handle* h, const float* c, const int32_t* spk_id, const int32_t* ph, const int32_t* lengths,
+                                    const int32_t* lengths_host, float* out, int B, int T_total, int chunk_frames, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
     if (h && !h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_loop on a model built with use_ar=false");
-    if (h && (h->cfg.use_spk_id || h->cfg.use_ph))  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
-        return fail(HIFICAR_E_INVALID, "hificar_ar_loop: speaker / phoneme conditioned models are driven through hificar_forward_cond");
+    if (h && check_cond_args(h, "hificar_ar_loop", spk_id, ph) != HIFICAR_OK) return HIFICAR_E_INVALID;
     if (chunk_frames < 1) return fail(HIFICAR_E_INVALID, "chunk_frames=%d must be positive", chunk_frames);
     int rc = check_ready(h, B, std::min(chunk_frames, std::max(T_total, 1)), workspace, workspace_bytes);
     if (rc != HIFICAR_OK) return rc;
@@ -1934,18 +1942,25 @@ extern "C" int hificar_ar_loop_ragged(hificar_handle* h, const float* c, const i
             return HIFICAR_OK;
         };
         const float* const c1 = c + (size_t)B0 * h->cf * T_total;
+        // chunk f0 of utterance b reads spk_id[b] and ph[b, f0 + t]: the second half's rows start at B0
+        Cond cond0, cond1;
+        cond0.spk_id = spk_id;
+        cond1.spk_id = spk_id ? spk_id + B0 : nullptr;
+        cond0.ph_stride = cond1.ph_stride = T_total;
         float* const out1 = out + (size_t)B0 * out_bstride;
         char* const wsp1 = static_cast<char*>(workspace) + ws0_bytes;
         for (int f0 = 0; f0 < T_total && rc == HIFICAR_OK; f0 += chunk_frames) {
             const int Tn = std::min(chunk_frames, T_total - f0);
             const int64_t pos = (int64_t)h->hop * f0;
             const int64_t back = f0 == 0 ? 0 : pos - h->cfg.ar_input;
+            cond0.ph = ph ? ph + f0 : nullptr;
+            cond1.ph = ph ? ph + (size_t)B0 * T_total + f0 : nullptr;
             rc = forward_impl(h, c + f0, (int64_t)h->cf * T_total, T_total, f0 == 0 ? nullptr : out + back, out_bstride, out + pos, out_bstride, B0, Tn,
-                              plan_workspace(h, B0, Tn, workspace), s0, nullptr, f0);
+                              plan_workspace(h, B0, Tn, workspace), s0, nullptr, f0, nullptr, -1, cond0);
             if (rc == HIFICAR_OK) rc = publish(s0, s1, h->ar_ev[0]);
             if (rc == HIFICAR_OK)
                 rc = forward_impl(h, c1 + f0, (int64_t)h->cf * T_total, T_total, f0 == 0 ? nullptr : out1 + back, out_bstride, out1 + pos, out_bstride, B1, Tn,
-                                  plan_workspace(h, B1, Tn, wsp1), s1, nullptr, f0);
+                                  plan_workspace(h, B1, Tn, wsp1), s1, nullptr, f0, nullptr, -1, cond1);
             if (rc == HIFICAR_OK) rc = publish(s1, s0, h->ar_ev[1]);
         }
         h->shared_chip = false;
@@ -1954,8 +1969,12 @@ extern "C" int hificar_ar_loop_ragged(hificar_handle* h, const float* c, const i
             return rc != HIFICAR_OK ? rc : fail(HIFICAR_E_HIP, "hificar_ar_loop: joining the side stream failed");
         return rc;
     }
+    Cond cond;
+    cond.spk_id = spk_id;
+    cond.ph_stride = T_total;
     for (int f0 = 0; f0 < T_total; f0 += chunk_frames) {
         const int Tn = std::min(chunk_frames, T_total - f0);
+        cond.ph = ph ? ph + f0 : nullptr;
         // With the host copy of the lengths the step only covers the utterances still running: the batch prefix up to the
         // last one longer than f0 (all of them when the batch is sorted longest first).
         int Bn = B;
@@ -1969,20 +1988,29 @@ extern "C" int hificar_ar_loop_ragged(hificar_handle* h, const float* c, const i
         // prev = last ar_input samples already written for this utterance (zeros for the first chunk)
         const float* prev = f0 == 0 ? nullptr : out + pos - h->cfg.ar_input;
         rc = forward_impl(h, c + f0, (int64_t)h->cf * T_total, T_total, prev, out_bstride, out + pos, out_bstride, Bn, Tn,
-                          plan_workspace(h, Bn, Tn, workspace), static_cast<hipStream_t>(stream), lengths, f0);
+                          plan_workspace(h, Bn, Tn, workspace), static_cast<hipStream_t>(stream), lengths, f0, nullptr, -1, cond);
         if (rc != HIFICAR_OK) return rc;
     }
     return HIFICAR_OK;
 }
 
-// Packed (continuously batched) AR synthesis: N utterances, at most `batch` of them in flight; as soon as one finishes the
-// next one takes its place, so every step but the last few runs a full batch whatever the lengths are.  The AR state of
-// an utterance is its own waveform so far, so a "slot" exists only in the host-side step table uploaded here.
-extern "C" int hificar_ar_loop_packed(hificar_handle* h, const float* c, const int32_t* lengths_host, float* out, int N, int T_max,
-                                      int chunk_frames, int batch, void* workspace, size_t workspace_bytes, void* stream_) {
+extern "C" int hificar_ar_loop_ragged(hificar_handle* h, const float* c, const int32_t* lengths, const int32_t* lengths_host,
+                                      float* out, int B, int T_total, int chunk_frames, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
     if (h && !h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_loop on a model built with use_ar=false");
     if (h && (h->cfg.use_spk_id || h->cfg.use_ph))  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
         return fail(HIFICAR_E_INVALID, "hificar_ar_loop: speaker / phoneme conditioned models are driven through hificar_forward_cond");
+    return hificar_ar_loop_cond(h, c, nullptr, nullptr, lengths, lengths_host, out, B, T_total, chunk_frames, workspace, workspace_bytes, stream);
+}
+
+// Packed (continuously batched) AR synthesis: N utterances, at most `batch` of them in flight; as soon as one finishes the
+// next one takes its place, so every step but the last few runs a full batch whatever the lengths are.  The AR state of
+// an utterance is its own waveform so far, so a "slot" exists only in the host-side step table uploaded here.
+extern "C" int hificar_ar_loop_packed_cond(hificar_handle* h, const float* c, const int32_t* spk_id, const int32_t* ph,
+                                           const int32_t* lengths_host, float* out, int N, int T_max, int chunk_frames, int batch,
+                                           void* workspace, size_t workspace_bytes, void* stream_) {
+    if (h && !h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_loop on a model built with use_ar=false");
+    if (h && check_cond_args(h, "hificar_ar_loop_packed", spk_id, ph) != HIFICAR_OK) return HIFICAR_E_INVALID;
     if (chunk_frames < 1 || batch < 1 || N < 1 || T_max < 1)
         return fail(HIFICAR_E_INVALID, "hificar_ar_loop_packed: N=%d, T_max=%d, chunk_frames=%d, batch=%d must be positive", N, T_max,
                     chunk_frames, batch);
@@ -2054,13 +2082,25 @@ extern "C" int hificar_ar_loop_packed(hificar_handle* h, const float* c, const i
     HIP_TRY(hipEventRecord(h->tab_copied, stream));
     const int64_t out_bstride = (int64_t)h->hop * T_max;
     size_t row = 0;
+    Cond cond;  // indexed by utterance / (utterance, frame) through the slots, like the features
+    cond.spk_id = spk_id;
+    cond.ph = ph;
+    cond.ph_stride = T_max;
     for (const Step& st : steps) {
         rc = forward_impl(h, c, (int64_t)h->cf * T_max, T_max, out, out_bstride, out, out_bstride, st.n, st.frames,
-                          plan_workspace(h, st.n, st.frames, workspace), stream, d_valid + row, 0, d_slots + row);
+                          plan_workspace(h, st.n, st.frames, workspace), stream, d_valid + row, 0, d_slots + row, -1, cond);
         if (rc != HIFICAR_OK) return rc;
         row += ((size_t)st.n + 1) & ~(size_t)1;
     }
     return HIFICAR_OK;
+}
+
+extern "C" int hificar_ar_loop_packed(hificar_handle* h, const float* c, const int32_t* lengths_host, float* out, int N, int T_max,
+                                      int chunk_frames, int batch, void* workspace, size_t workspace_bytes, void* stream) {
+    if (h && !h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_loop on a model built with use_ar=false");
+    if (h && (h->cfg.use_spk_id || h->cfg.use_ph))  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
+        return fail(HIFICAR_E_INVALID, "hificar_ar_loop: speaker / phoneme conditioned models are driven through hificar_forward_cond");
+    return hificar_ar_loop_packed_cond(h, c, nullptr, nullptr, lengths_host, out, N, T_max, chunk_frames, batch, workspace, workspace_bytes, stream);
 }
 
 extern "C" int hificar_ar_loop(hificar_handle* h, const float* c, float* out, int B, int T_total, int chunk_frames,
@@ -2074,14 +2114,15 @@ extern "C" int hificar_ar_loop(hificar_handle* h, const float* c, float* out, in
 // table is written into a ring of mapped pinned slots that front_kernel reads where they are (an upload would put a DMA transfer in
 // front of every step's launches), so the host never waits for earlier steps unless kStepRing of them are queued.
 static constexpr int kStepRing = 32;
-extern "C" int hificar_ar_step(hificar_handle* h, const float* c, int64_t c_bstride, int64_t c_cstride, const int32_t* seqs_host, int n,
-                               int chunk_frames, float* ctx, int ctx_rows, float* out, void* workspace, size_t workspace_bytes,
-                               void* stream_) {
+extern "C" int hificar_ar_step_cond(hificar_handle* h, const float* c, int64_t c_bstride, int64_t c_cstride, const int32_t* spk_rows,
+                                    const int32_t* ph, int64_t ph_bstride, const int32_t* seqs_host, int n, int chunk_frames, float* ctx,
+                                    int ctx_rows, float* out, void* workspace, size_t workspace_bytes, void* stream_) {
     // every argument is checked before the handle's state (finalize, workspace): nothing is enqueued for a bad table
     if (!h) return fail(HIFICAR_E_INVALID, "null handle");
     if (!h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_step on a model built with use_ar=false");
-    if (h->cfg.use_spk_id || h->cfg.use_ph)  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
-        return fail(HIFICAR_E_INVALID, "hificar_ar_step: speaker / phoneme conditioned models are driven through hificar_forward_cond");
+    if (check_cond_args(h, "hificar_ar_step", spk_rows, ph) != HIFICAR_OK) return HIFICAR_E_INVALID;
+    if (ph && (ph_bstride < 1 || ph_bstride > INT32_MAX))
+        return fail(HIFICAR_E_INVALID, "hificar_ar_step: phoneme ring row pitch %lld outside [1, 2^31)", (long long)ph_bstride);
     if (n < 1 || chunk_frames < 1 || ctx_rows < 1)
         return fail(HIFICAR_E_INVALID, "hificar_ar_step: n=%d, chunk_frames=%d, ctx_rows=%d must be positive", n, chunk_frames, ctx_rows);
     if (!c || !seqs_host || !ctx || !out) return fail(HIFICAR_E_INVALID, "hificar_ar_step: null argument");
@@ -2103,6 +2144,9 @@ extern "C" int hificar_ar_step(hificar_handle* h, const float* c, int64_t c_bstr
         if (e[1] < 0 || (int64_t)e[1] + e[2] > c_cstride)
             return fail(HIFICAR_E_INVALID, "hificar_ar_step: sequence %d: frames [%d, %d) outside the feature rows (%lld)", b, e[1], e[1] + e[2],
                         (long long)c_cstride);
+        if (ph && (int64_t)e[1] + e[2] > ph_bstride)
+            return fail(HIFICAR_E_INVALID, "hificar_ar_step: sequence %d: frames [%d, %d) outside the phoneme ring's rows (%lld)", b, e[1],
+                        e[1] + e[2], (long long)ph_bstride);
     }
     int rc = check_ready(h, n, chunk_frames, workspace, workspace_bytes);
     if (rc != HIFICAR_OK) return rc;
@@ -2143,6 +2187,9 @@ extern "C" int hificar_ar_step(hificar_handle* h, const float* c, int64_t c_bstr
     cond.seqs = reinterpret_cast<const int4*>(h->step_hd) + (size_t)k * h->step_cap;
     cond.seqs_slots = d_slots;
     cond.seqs_valid = d_valid;
+    cond.spk_id = spk_rows;  // one speaker per session row: front_kernel indexes both by the table's row
+    cond.ph = ph;
+    cond.ph_stride = (int)ph_bstride;
     // a step of full chunks only (every step but a session's last) runs the launches unmasked, as an ar_synthesis step does: the masked
     // form's per-tile length loads cost ~1 us per launch, and for full chunks both forms compute the same values
     rc = forward_impl(h, c, c_bstride, c_cstride, nullptr, 0, out, (int64_t)h->hop * chunk_frames, n, chunk_frames,
@@ -2151,6 +2198,15 @@ extern "C" int hificar_ar_step(hificar_handle* h, const float* c, int64_t c_bstr
     if (hipEventRecord(slot.done, stream) == hipSuccess) slot.used = true;
     else if (rc == HIFICAR_OK) rc = fail(HIFICAR_E_HIP, "hificar_ar_step: recording the step's event failed");
     return rc;
+}
+
+extern "C" int hificar_ar_step(hificar_handle* h, const float* c, int64_t c_bstride, int64_t c_cstride, const int32_t* seqs_host, int n,
+                               int chunk_frames, float* ctx, int ctx_rows, float* out, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    if (h && h->cfg.use_ar && (h->cfg.use_spk_id || h->cfg.use_ph))  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
+        return fail(HIFICAR_E_INVALID, "hificar_ar_step: speaker / phoneme conditioned models are driven through hificar_forward_cond");
+    return hificar_ar_step_cond(h, c, c_bstride, c_cstride, nullptr, nullptr, 0, seqs_host, n, chunk_frames, ctx, ctx_rows, out, workspace,
+                                workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

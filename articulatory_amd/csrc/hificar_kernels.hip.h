@@ -112,14 +112,17 @@ struct FrontParams {
     int* seqs_valid;
     int hop;
     int t_valid;          // frames that exist in c (<= T): later frames read as zeros (bucketed launch lengths)
-    // speaker conditioning (hifigan.py:212-216): spk_fc(spk_emb_mat[spk_id[b]]) is added to channels [0, cf + ar_output)
-    const int* spk_id;    // (B) or null
+    // speaker conditioning (hifigan.py:212-216): spk_fc(spk_emb_mat[spk_id[u]]) is added to channels [0, cf + ar_output); u is the
+    // launch's own row b, the utterance slots[b].x (packed mode) or the session row seqs[b].x (context mode: spk_id is the caller's
+    // arena of one speaker per session row)
+    const int* spk_id;    // (B) / (utterances) / (session rows), or null
     const float* spk_emb; // (num_spk, spk_e)
     const float* spk_w;   // spk_fc.weight (cf + ar_output, spk_e)
     const float* spk_b;   // spk_fc.bias
     int spk_e;
-    // phoneme conditioning (hifigan.py:217-220): channels [cf + ar_output, + ph_e) of frame t hold ph_emb[ph[b, t]]
-    const int* ph;        // (B, ph_stride) or null
+    // phoneme conditioning (hifigan.py:217-220): channels [cf + ar_output, + ph_e) of frame t hold ph_emb[ph[u, frame + t]], (u, frame)
+    // as for the features: (b, 0) with the chunk offset already in the pointer, slots[b] or seqs[b].xy (ph is then the caller's ring)
+    const int* ph;        // (rows, ph_stride) or null
     int ph_stride;
     const float* ph_emb;  // (num_ph, ph_e)
     int ph_e;
@@ -137,21 +140,31 @@ __global__ __launch_bounds__(kFrontThreads) void front_kernel(const FrontParams 
     const int lane = tid & 63;
     const int ks = tid >> 6;  // wave index = K slice: each wave reduces an eighth of the input dimension
     int cur = 0;
-    int4 seq = {0, 0, 0, 0};
+    // (row, first frame) of this sequence in the caller's tensors (features, waveform / context, speaker ids, phonemes) and its frames
+    int urow = b, uframe = 0, tmax = p.t_valid;
+    bool first = false;
     if (p.seqs) {
-        seq = p.seqs[b];
+        const int4 seq = p.seqs[b];
         if (tid == 0) {
             p.seqs_slots[b] = int2{seq.x, seq.y};
             p.seqs_valid[b] = seq.z;
         }
+        urow = seq.x;
+        uframe = seq.y;
+        tmax = seq.z;
+        first = seq.w != 0;
+    } else if (p.slots) {
+        const int2 sl = p.slots[b];
+        urow = sl.x;
+        uframe = sl.y;
+        tmax = p.valid[b];  // frames past the utterance's end may lie outside the packed tensor
     }
     if (p.use_ar) {
         const float* prevp = p.prev ? p.prev + (size_t)b * p.prev_bstride : nullptr;
         if (p.seqs) {
-            prevp = seq.w ? nullptr : p.prev + (size_t)seq.x * p.prev_bstride;
+            prevp = first ? nullptr : p.prev + (size_t)urow * p.prev_bstride;
         } else if (p.slots) {
-            const int2 sl = p.slots[b];
-            prevp = sl.y > 0 ? p.prev + (size_t)sl.x * p.prev_bstride + (size_t)p.hop * sl.y - p.ar_input : nullptr;
+            prevp = uframe > 0 ? p.prev + (size_t)urow * p.prev_bstride + (size_t)p.hop * uframe - p.ar_input : nullptr;
         }
         for (int i = tid; i < p.ar_input; i += NT) {
             const float v = prevp ? prevp[i] : 0.f;
@@ -206,7 +219,7 @@ __global__ __launch_bounds__(kFrontThreads) void front_kernel(const FrontParams 
     const int c_ar = p.use_ar ? p.ar_output : 0;
     float* spk_vec = act[cur ^ 1];  // free once the MLP is done (in_channels <= 1024 with use_spk_id, hificar_create)
     if (p.spk_id) {  // per-utterance speaker vector for channels [0, cf + ar_output)
-        const float* e = p.spk_emb + (size_t)p.spk_id[b] * p.spk_e;
+        const float* e = p.spk_emb + (size_t)p.spk_id[urow] * p.spk_e;
         for (int ch = tid; ch < p.cf + c_ar; ch += NT) {
             float v = p.spk_b[ch];
             for (int k = 0; k < p.spk_e; ++k) v = fmaf(p.spk_w[(size_t)ch * p.spk_e + k], e[k], v);
@@ -215,22 +228,15 @@ __global__ __launch_bounds__(kFrontThreads) void front_kernel(const FrontParams 
         __syncthreads();
     }
     const int n = p.T * p.cin_pad;
-    size_t cbase = (size_t)b * p.c_bstride;
-    int tmax = p.t_valid;
-    if (p.seqs) {
-        cbase = (size_t)seq.x * p.c_bstride + seq.y;
-        tmax = seq.z;
-    } else if (p.slots) {
-        cbase = (size_t)p.slots[b].x * p.c_bstride + p.slots[b].y;
-        tmax = p.valid[b];  // frames past the utterance's end may lie outside the packed tensor
-    }
+    const size_t cbase = (size_t)urow * p.c_bstride + uframe;
+    const int* phrow = p.ph ? p.ph + (size_t)urow * p.ph_stride + uframe : nullptr;  // read behind t < tmax only, like the features
     for (int idx = tid; idx < n; idx += NT) {
         const int t = idx / p.cin_pad;
         const int ch = idx - t * p.cin_pad;
         float v = 0.f;
         if (ch < p.cf) v = t < tmax ? p.c[cbase + (size_t)ch * p.c_cstride + t] : 0.f;
         else if (ch < p.cf + c_ar) v = feats[ch - p.cf];
-        else if (p.ph && ch < p.cf + c_ar + p.ph_e) v = t < tmax ? p.ph_emb[(size_t)p.ph[(size_t)b * p.ph_stride + t] * p.ph_e + (ch - p.cf - c_ar)] : 0.f;
+        else if (p.ph && ch < p.cf + c_ar + p.ph_e) v = t < tmax ? p.ph_emb[(size_t)phrow[t] * p.ph_e + (ch - p.cf - c_ar)] : 0.f;
         if (p.spk_id && ch < p.cf + c_ar && t < tmax) v += spk_vec[ch];
         if (p.xin) p.xin[(size_t)b * n + idx] = v;
         if (p.xin_s) {

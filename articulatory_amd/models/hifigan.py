@@ -653,7 +653,26 @@ class _NativeGenerator(torch.nn.Module):
             out = _NoGraph.apply(out, type(self).__name__, next(p for p in self._plist() if p.requires_grad))
         return (out, ph_out) if self.use_ph_loss else out
 
-    def ar_synthesis(self, c, chunk_frames, lengths=None):
+    def _cond_args(self, spk_id, ph, B, T, device):
+        """spk_id (B,) / ph (B, T) of the AR loops -> int32 device tensors (None where not given), shape- and range-checked as
+        ``forward`` checks them (a device tensor costs one reduction and a wait).  Which of them the model needs is the C ABI's check."""
+        if spk_id is not None:
+            spk_id = torch.as_tensor(spk_id)
+            if spk_id.numel() != B:
+                raise RuntimeError(f"spk_id has {spk_id.numel()} entries for a batch of {B}: ar_synthesis needs spk_id=(B,) speaker indices")
+            if self.use_spk_id and B and (int(spk_id.min()) < 0 or int(spk_id.max()) >= self._params["num_spk"]):
+                raise IndexError("index out of range in self")  # torch.nn.Embedding's message
+            spk_id = spk_id.reshape(-1).to(device=device, dtype=torch.int32).contiguous()
+        if ph is not None:
+            ph = torch.as_tensor(ph)
+            if tuple(ph.shape) != (B, T):
+                raise RuntimeError(f"ar_synthesis needs ph=(B, T)=({B}, {T}) phoneme indices, got {tuple(ph.shape)}")
+            if self.use_ph and ph.numel() and (int(ph.min()) < 0 or int(ph.max()) >= self._params["num_ph"]):
+                raise IndexError("index out of range in self")
+            ph = ph.to(device=device, dtype=torch.int32).contiguous()
+        return spk_id, ph
+
+    def ar_synthesis(self, c, chunk_frames, lengths=None, spk_id=None, ph=None):
         """Batched autoregressive synthesis on device.
 
         c: (B, C, T_total) features; returns (B, hop*T_total).  Per utterance this equals the
@@ -661,12 +680,17 @@ class _NativeGenerator(torch.nn.Module):
         ``chunk_frames = batch_max_steps // hop_size``; the reference driver is batch-1 only.
         ``lengths``: frame counts of a padded batch of utterances of different lengths (see ``forward``); each utterance's
         last chunk is then its own shorter tail chunk, as in the reference loop.
+        ``spk_id`` (B,) / ``ph`` (B, T_total): speaker and phoneme indices of a use_spk_id / use_ph model (C ABI:
+        hificar_ar_loop_cond).  The reference's loop has no such arguments; every chunk's forward is then the reference's
+        ``forward(c, spk_id=, ar=prev, ph=)`` (hifigan.py:212-220) with the utterance's speaker and the chunk's slice of its phoneme
+        row (entries past an utterance's length are not used but must be valid indices).  Waveform only, also with use_ph_loss.
         """
         if not self.use_ar:
             raise RuntimeError("ar_synthesis needs a use_ar=True generator")
         self._check_input(c)
         c = c.to(torch.float32).contiguous()
         B, _, T = c.shape
+        spk_id, ph = self._cond_args(spk_id, ph, B, T, c.device)
         handle = self._native_handle()
         if lengths is None:
             out = torch.empty((B, T * self.hop), dtype=torch.float32, device=c.device)
@@ -676,23 +700,30 @@ class _NativeGenerator(torch.nn.Module):
         with torch.cuda.device(c.device):
             ws_ptr, ws_bytes = self._workspace(B, min(int(chunk_frames), T))
             stream = torch.cuda.current_stream().cuda_stream
-            rc = self._lib.hificar_ar_loop_ragged(handle, c.data_ptr(), lengths.data_ptr() if lengths is not None else None,
-                                                  lengths_host.data_ptr() if lengths is not None else None,
-                                                  out.data_ptr(), B, T, int(chunk_frames), ws_ptr, ws_bytes, ctypes.c_void_p(stream))
+            lens = (lengths.data_ptr(), lengths_host.data_ptr()) if lengths is not None else (None, None)
+            if spk_id is None and ph is None:  # (a conditioned model is refused here: its error names hificar_forward_cond)
+                rc = self._lib.hificar_ar_loop_ragged(handle, c.data_ptr(), *lens, out.data_ptr(), B, T, int(chunk_frames), ws_ptr,
+                                                      ws_bytes, ctypes.c_void_p(stream))
+            else:
+                rc = self._lib.hificar_ar_loop_cond(handle, c.data_ptr(), spk_id.data_ptr() if spk_id is not None else None,
+                                                    ph.data_ptr() if ph is not None else None, *lens, out.data_ptr(), B, T,
+                                                    int(chunk_frames), ws_ptr, ws_bytes, ctypes.c_void_p(stream))
         _native.check(rc, "hificar_ar_loop")
         return out
 
-    def ar_synthesis_packed(self, c, chunk_frames, lengths, batch=64):
+    def ar_synthesis_packed(self, c, chunk_frames, lengths, batch=64, spk_id=None, ph=None):
         """Continuously batched autoregressive synthesis of a list of utterances (C ABI: hificar_ar_loop_packed).
 
         c: (N, C, T_max) zero-padded features, ``lengths`` their N frame counts; at most ``batch`` utterances are in flight
         and a finished one is replaced by the next of the list.  Returns (N, hop*T_max) with zeros past each utterance's
-        end; per utterance the reference's ``ar_loop`` result (articulatory/bin/decode.py:54-83)."""
+        end; per utterance the reference's ``ar_loop`` result (articulatory/bin/decode.py:54-83).  ``spk_id`` (N,) / ``ph`` (N, T_max)
+        as in ``ar_synthesis`` (C ABI: hificar_ar_loop_packed_cond): they follow their utterance into whichever slot it takes."""
         if not self.use_ar:
             raise RuntimeError("ar_synthesis needs a use_ar=True generator")
         self._check_input(c)
         c = c.to(torch.float32).contiguous()
         N, _, T = c.shape
+        spk_id, ph = self._cond_args(spk_id, ph, N, T, c.device)
         lengths_host, _ = self._lengths_arg(lengths, N, T, c.device)
         handle = self._native_handle()
         out = torch.zeros((N, T * self.hop), dtype=torch.float32, device=c.device)
@@ -700,8 +731,14 @@ class _NativeGenerator(torch.nn.Module):
         with torch.cuda.device(c.device):
             ws_ptr, ws_bytes = self._workspace(batch, min(int(chunk_frames), T))
             stream = torch.cuda.current_stream().cuda_stream
-            rc = self._lib.hificar_ar_loop_packed(handle, c.data_ptr(), lengths_host.data_ptr(), out.data_ptr(), N, T,
-                                                  int(chunk_frames), batch, ws_ptr, ws_bytes, ctypes.c_void_p(stream))
+            if spk_id is None and ph is None:
+                rc = self._lib.hificar_ar_loop_packed(handle, c.data_ptr(), lengths_host.data_ptr(), out.data_ptr(), N, T,
+                                                      int(chunk_frames), batch, ws_ptr, ws_bytes, ctypes.c_void_p(stream))
+            else:
+                rc = self._lib.hificar_ar_loop_packed_cond(handle, c.data_ptr(), spk_id.data_ptr() if spk_id is not None else None,
+                                                           ph.data_ptr() if ph is not None else None, lengths_host.data_ptr(),
+                                                           out.data_ptr(), N, T, int(chunk_frames), batch, ws_ptr, ws_bytes,
+                                                           ctypes.c_void_p(stream))
         _native.check(rc, "hificar_ar_loop_packed")
         return out
 

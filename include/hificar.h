@@ -21,6 +21,9 @@
  *   hificar_ar_loop_packed  the same dataset loop, continuously batched (a finished utterance's place is taken by the next)
  *   hificar_ar_step         one chunk of ar_loop (decode.py:54-83) for each of n live sessions; the AR context  articulatory/bin/decode.py:54-83
  *                           (prev = cout[:, :, -ar_input:], decode.py:77-78) persists between calls in a caller-owned arena
+ *   hificar_ar_loop_cond, hificar_ar_loop_packed_cond, hificar_ar_step_cond
+ *                           the same three loops for speaker- / phoneme-conditioned models: every chunk's forward is
+ *                           forward(c, spk_id=, ar=prev, ph=)                    articulatory/bin/decode.py:54-83 + hifigan.py:212-220
  *   hificar_pcm16           sf.write(..., "PCM_16") sample conversion articulatory/bin/decode.py:319-324
  *   hificar_workspace_bytes (torch's caching allocator does this implicitly in the reference)
  *   hificar_last_error      Python exceptions / assert           articulatory/models/hifigan.py:78-80
@@ -212,9 +215,41 @@ int hificar_ar_loop_packed(hificar_handle* h, const float* c, const int32_t* len
  * output is hificar_ar_loop's on the concatenated frames.  Launches exactly the kernels of one hificar_ar_loop step of n utterances
  * (one chunk), and no copy: the table goes into a ring of mapped pinned slots that the first kernel reads in place, so the call
  * does not wait for device work (unless 32 steps of this handle are still queued).  workspace: hificar_workspace_bytes(h, n, chunk_frames).  Requires use_ar, no speaker /
- * phoneme conditioning, ar_input <= hop*chunk_frames; the table is checked on the host before anything is enqueued. */
+ * phoneme conditioning (hificar_ar_step_cond takes those), ar_input <= hop*chunk_frames; the table is checked on the host before anything is enqueued. */
 int hificar_ar_step(hificar_handle* h, const float* c, int64_t c_bstride, int64_t c_cstride, const int32_t* seqs_host, int n,
                     int chunk_frames, float* ctx, int ctx_rows, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The AR loops for speaker- / phoneme-conditioned models.  The reference's ar_loop calls model(cin, ar=prev_samples) only (decode.py:72)
+ * and cannot run such a model; these entry points keep its chunking and feedback (articulatory/bin/decode.py:54-83) and make every chunk's
+ * forward the reference's forward(c, spk_id=, ar=prev, ph=) (hifigan.py:212-220) with the utterance's own speaker and the chunk's slice of
+ * its phoneme row, so an utterance's result is that of the one-at-a-time loop of hificar_forward_cond calls on its chunks (bit for bit
+ * with HIFICAR_KSPLIT=0).  Waveform only: no ph_out (use_ph_loss models return the first output).  Each conditioning pointer is required
+ * exactly when the model uses it (use_spk_id / use_ph) and must be NULL otherwise; with both NULL these ARE hificar_ar_loop_ragged /
+ * _packed / hificar_ar_step.  The library reads the indices on the device and cannot check them: the CALLER guarantees
+ * 0 <= spk_id < num_spk and 0 <= ph < num_ph for every element of the tensors described below (padding included). */
+
+/* hificar_ar_loop_ragged with spk_id: device (B) int32, one speaker per utterance, and ph: device (B, T_total) int32, frame-aligned
+ * with c (entries at or past lengths[b] are not used but must be valid indices).  decode.py:54-83 + hifigan.py:212-220. */
+int hificar_ar_loop_cond(hificar_handle* h, const float* c, const int32_t* spk_id, const int32_t* ph, const int32_t* lengths,
+                         const int32_t* lengths_host, float* out, int B, int T_total, int chunk_frames, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* hificar_ar_loop_packed with spk_id: device (N) int32 and ph: device (N, T_max) int32, indexed by utterance like c: a slot taken over
+ * by the next utterance of the list takes that utterance's speaker and phonemes with it.  decode.py:54-83 + hifigan.py:212-220. */
+int hificar_ar_loop_packed_cond(hificar_handle* h, const float* c, const int32_t* spk_id, const int32_t* ph, const int32_t* lengths_host,
+                                float* out, int N, int T_max, int chunk_frames, int batch, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
+/* hificar_ar_step with per-session conditioning (decode.py:54-83 + hifigan.py:212-220), both in caller-owned device memory addressed by
+ * the table's row like ctx and c:
+ *   spk_rows  (ctx_rows) int32: element `row` is the speaker of the session on that row
+ *   ph        phoneme ring: frame t of the chunk of a sequence {row, frame, ...} is ph[row*ph_bstride + frame + t]; frame + valid <=
+ *             ph_bstride is checked with the table
+ * The step reads both when it RUNS, and up to 32 steps may be queued: write a session's speaker and its phonemes on the stream the
+ * steps are given (as its features are), never from the host behind a queued step's back. */
+int hificar_ar_step_cond(hificar_handle* h, const float* c, int64_t c_bstride, int64_t c_cstride, const int32_t* spk_rows,
+                         const int32_t* ph, int64_t ph_bstride, const int32_t* seqs_host, int n, int chunk_frames, float* ctx,
+                         int ctx_rows, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* float waveform in [-1, 1] -> 16-bit PCM on the device: y = clip(round_half_even(x *_f32 32767.f), -32768, 32767) — the product in
  * float32, as libsndfile's f2s_array computes it (lrintf(src * 32767.f)); libsndfile wraps outside [-1, 1] where this clips.
