@@ -92,6 +92,13 @@ SYMBOLS = (
     "hificar_disc_weight_norm_backward_bucket",
     "hificar_disc_set_grad_accumulate",
     "hificar_disc_set_grad_scale",
+    "hificar_bigru_create",
+    "hificar_bigru_set_weight",
+    "hificar_bigru_finalize",
+    "hificar_bigru_workspace_bytes",
+    "hificar_bigru_forward",
+    "hificar_bigru_engine",
+    "hificar_bigru_destroy",
     "hificar_destroy",
     "hificar_last_error",
     "hificar_version",
@@ -153,6 +160,18 @@ class HificarGBlockConfig(ctypes.Structure):
         ("num_spk", ctypes.c_int32),
         ("spk_emb_size", ctypes.c_int32),
         ("precision", ctypes.c_int32),
+    ]
+
+
+class HificarBigruConfig(ctypes.Structure):
+    """hificar_bigru_config (include/hificar.h): the keyword arguments of the reference's BiGRU.__init__ (pytorch_models.py:23-25) that
+    affect eval-mode inference."""
+
+    _fields_ = [
+        ("in_channels", ctypes.c_int32),
+        ("hidden_size", ctypes.c_int32),
+        ("out_channels", ctypes.c_int32),
+        ("use_tanh", ctypes.c_int32),
     ]
 
 
@@ -403,6 +422,20 @@ def load_library():
     lib.hificar_disc_set_grad_accumulate.restype = ctypes.c_int
     lib.hificar_disc_set_grad_scale.argtypes = [vp, vp]
     lib.hificar_disc_set_grad_scale.restype = ctypes.c_int
+    lib.hificar_bigru_create.argtypes = [ctypes.POINTER(HificarBigruConfig), ctypes.POINTER(vp)]
+    lib.hificar_bigru_create.restype = ci
+    lib.hificar_bigru_set_weight.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(c64), ci]
+    lib.hificar_bigru_set_weight.restype = ci
+    lib.hificar_bigru_finalize.argtypes = [vp]
+    lib.hificar_bigru_finalize.restype = ci
+    lib.hificar_bigru_workspace_bytes.argtypes = [vp, ci, ci]
+    lib.hificar_bigru_workspace_bytes.restype = cs
+    lib.hificar_bigru_forward.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]
+    lib.hificar_bigru_forward.restype = ci
+    lib.hificar_bigru_engine.argtypes = [vp]
+    lib.hificar_bigru_engine.restype = vp
+    lib.hificar_bigru_destroy.argtypes = [vp]
+    lib.hificar_bigru_destroy.restype = None
     lib.hificar_destroy.argtypes = [vp]
     lib.hificar_destroy.restype = None
     lib.hificar_last_error.argtypes = []
@@ -514,4 +547,32 @@ def make_gblock_config(params: dict, precision: int) -> HificarGBlockConfig:
     cfg.num_spk = int(params.get("num_spk") or 0)
     cfg.spk_emb_size = int(params.get("spk_emb_size") or 0)
     cfg.precision = precision
+    return cfg
+
+
+# what hificar_bigru_create accepts (csrc/hificar_bigru.hip.inc; HIFICAR_BIGRU_MAX_* of include/hificar.h); BiGRU.__init__ checks the same
+# numbers so that an unsupported configuration fails at construction, not at the first forward on the device
+BIGRU_MAX_IN = 4096
+BIGRU_MAX_HIDDEN = 256   # one workgroup holds one direction's W_hh in registers + LDS + a streamed remainder
+BIGRU_MAX_OUT = 32       # fc2's rows in the head kernel's LDS
+
+
+def check_bigru_params(params: dict):
+    """ValueError for a BiGRU configuration libhificar's engine rejects."""
+    h = params["hidden_size"]
+    if not 1 <= params["in_channels"] <= BIGRU_MAX_IN:
+        raise ValueError(f"in_channels={params['in_channels']} out of range (1 .. {BIGRU_MAX_IN})")
+    if h < 64 or h > BIGRU_MAX_HIDDEN or h % 64:
+        raise ValueError(f"hidden_size={h} unsupported (multiples of 64 up to {BIGRU_MAX_HIDDEN}: one workgroup holds a direction's W_hh)")
+    if not 1 <= params["out_channels"] <= BIGRU_MAX_OUT:
+        raise ValueError(f"out_channels={params['out_channels']} out of range (1 .. {BIGRU_MAX_OUT})")
+
+
+def make_bigru_config(params: dict) -> HificarBigruConfig:
+    """BiGRU keyword arguments (reference names) -> hificar_bigru_config."""
+    cfg = HificarBigruConfig()
+    cfg.in_channels = params["in_channels"]
+    cfg.hidden_size = params["hidden_size"]
+    cfg.out_channels = params["out_channels"]
+    cfg.use_tanh = int(params["use_tanh"])
     return cfg

@@ -13,7 +13,8 @@
   ``forward(c, spk_id=, ar=prev, ph=)`` (hifigan.py:212-220) with the utterance's speaker and the chunk's slice of its phoneme row.
 * ``main`` (reference decode.py:103-358, console script ``articulatory-decode``): same flags, config
   merge, scp / dump-dir inputs (``.npy`` features), ``--normalize-before``, PCM_16 ``<utt>_gen.wav``
-  outputs and RTF report, for the a2w dataset modes of the HiFi-GAN / HiFi-CAR generator.
+  outputs and RTF report, for the a2w dataset modes of the HiFi-GAN / HiFi-CAR generator — and, for the feature-to-feature modes
+  ``art`` / ``a2m`` of a non-AR model (the BiGRU inversion model), ``model.inference`` saved as ``<utt>_gen.npy`` (decode.py:338-350).
 """
 
 import argparse
@@ -163,6 +164,7 @@ def length_batches(items, batch_size, window=8):
 # articulatory-decode counterpart
 # ----------------------------------------------------------------------------------------------
 _A2W_MODES = ("default", "m2w", "a2w", "a2w_pcd")
+_FEAT_MODES = ("art", "a2m")  # feature -> feature (decode.py:338-350), non-AR models only; w2a / ph2m / ph2a are not built
 
 
 def list_features(feats_scp=None, dumpdir=None, fmt="npy"):
@@ -372,6 +374,36 @@ def decode_dataset(model, items, config, device, outdir, normalize_before=False,
     return n, (total_rtf / n if n else float("nan"))
 
 
+def decode_features(model, items, config, device, outdir, normalize_before=False, batch_size=1):
+    """The generation loop of decode.py:292-351 for the feature-to-feature modes (``art``, ``a2m``) of a non-AR model:
+    ``model.inference(c, normalize_before=...)`` saved as ``<utt_id>_gen.npy`` with shape (T, out_channels) (decode.py:348-350).
+    ``batch_size`` > 1: ragged batches of similar lengths through ``model(..., lengths=)``, every utterance computed as if alone.
+    Returns (n_utterances, average seconds per utterance)."""
+    total, n = 0.0, 0
+    with torch.no_grad():
+        if batch_size > 1:
+            feats = ((u, torch.tensor(c, dtype=torch.float).to(device)) for u, c in items)
+            for batch in length_batches(feats, batch_size):
+                start = time.time()
+                xs = [(c - model.mean) / model.scale if normalize_before else c for _, c in batch]
+                padded, lens = pad_utterances(xs)
+                yb = model(padded.permute(0, 2, 1), lengths=lens)  # (B, out_channels, T_max)
+                ys = [yb[i, :, :m].transpose(0, 1).cpu().numpy() for i, m in enumerate(lens)]  # device -> host: the synchronisation point
+                total += time.time() - start
+                for (utt_id, _), y in zip(batch, ys):
+                    np.save(os.path.join(outdir, f"{utt_id}_gen.npy"), y)
+                    n += 1
+        else:
+            for utt_id, c in items:
+                c = torch.tensor(c, dtype=torch.float).to(device)
+                start = time.time()
+                y = model.inference(c, normalize_before=normalize_before).cpu().numpy()
+                total += time.time() - start
+                np.save(os.path.join(outdir, f"{utt_id}_gen.npy"), y)
+                n += 1
+    return n, (total / n if n else float("nan"))
+
+
 def main(argv=None):
     from articulatory_amd.utils import load_model
 
@@ -390,9 +422,11 @@ def main(argv=None):
     if (args.feats_scp is not None and args.dumpdir is not None) or (args.feats_scp is None and args.dumpdir is None):
         raise ValueError("Please specify either --dumpdir or --feats-scp.")
     dataset_mode = config.setdefault("dataset_mode", "default")
-    if dataset_mode not in _A2W_MODES:
-        raise NotImplementedError(f"dataset_mode {dataset_mode!r}: only the articulatory/mel -> waveform modes "
-                                  f"{_A2W_MODES} are built (SURVEY.md §8 f3)")
+    if dataset_mode not in _A2W_MODES + _FEAT_MODES:
+        raise NotImplementedError(f"dataset_mode {dataset_mode!r}: only the articulatory/mel -> waveform modes {_A2W_MODES} and the "
+                                  f"feature -> feature modes {_FEAT_MODES} are built (SURVEY.md §8 f3)")
+    if dataset_mode in _FEAT_MODES and config.get("generator_params", {}).get("use_ar", False):
+        raise NotImplementedError(f"dataset_mode {dataset_mode!r} with use_ar: ar_loop's feature branches are not built")
     if config.get("transform") or config.get("input_transform"):
         raise NotImplementedError("feature transforms are not built")
     pairs = list_features(args.feats_scp, args.dumpdir, config.get("format", "npy"))
@@ -425,6 +459,11 @@ def main(argv=None):
     model.remove_weight_norm()
     model = model.eval().to(device)
     print(sum(p.numel() for p in model.parameters() if p.requires_grad))
+    if dataset_mode in _FEAT_MODES:
+        n, sec = decode_features(model, items, config, device, config["outdir"], normalize_before=args.normalize_before,
+                                 batch_size=args.batch_size)
+        logging.info(f"Finished generation of {n} utterances ({sec:.03f} s per utterance).")
+        return
     n, rtf = decode_dataset(model, items, config, device, config["outdir"], normalize_before=args.normalize_before,
                             batch_size=args.batch_size, cond=cond)
     logging.info(f"Finished generation of {n} utterances (RTF = {rtf:.03f}).")

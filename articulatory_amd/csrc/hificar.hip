@@ -6,6 +6,7 @@
 #include "hificar_launch.h"
 #include "hificar_backward.hip.h"
 #include "hificar_disc_kernels.hip.h"
+#include "hificar_bigru_kernels.hip.h"
 
 #include "../../include/hificar.h"
 
@@ -230,6 +231,7 @@ struct hificar_handle {
 //   HIFICAR_PAIR=0             narrow stages layer by layer instead of the fused pair kernels;  HIFICAR_PAIR_SMALL=0: no 128-row pair tiles at C = 32
 //   HIFICAR_AR_DUAL_MIN / _MAX the batch sizes hificar_ar_loop runs as two halves on two streams (default 17..62; MAX=0: never)
 // hificar_disc.hip.inc adds HIFICAR_DISC_STREAMS=0 (sub-discriminators on the caller's stream: per-launch counters) and HIFICAR_COL2IM_VEC4=0.
+// hificar_bigru.hip.inc adds HIFICAR_BIGRU_NS=1|2 (sequences per workgroup of the recurrent kernel, A/B runs) and always runs with KSPLIT off.
 static FILE* g_launch_log = nullptr;
 static void read_env_switches(hificar_handle* h) {
     if (const char* e = getenv("HIFICAR_PROFILE_DETAIL")) h->profile_detail = atoi(e) != 0;
@@ -2267,3 +2269,4 @@ extern "C" int hificar_pcm16(const float* x, int16_t* y, size_t n, void* stream)
 #include "hificar_gblock.hip.inc"
 #include "hificar_disc.hip.inc"
 #include "hificar_mel.hip.inc"
+#include "hificar_bigru.hip.inc"

@@ -1,0 +1,336 @@
+// The BiGRU articulatory-inversion model (articulatory/models/pytorch_models.py:22-123): features (B, in_channels, T) -> EMA (B, out_channels, T).
+//   rows      (B, C, T) -> channels-last rows                                   bigru_rows_kernel
+//   gru1/2    pre-gates  X W_ih^T + b_ih, both directions in one GEMM (N = 6H)   conv engine, one-tap launch (as the discriminators' GEMMs)
+//             the recurrent sweep, one workgroup per (direction, sequence tile)  bigru_rec_kernel
+//   fc1 + bn  Linear(2H, 128) with the eval-mode BatchNorm1d folded in           conv engine
+//   fc2       Linear(128, out) (+ tanh), written as (B, out, T)                  bigru_head_kernel
+// Workspace: one pre-gate buffer [B T][6H] shared by the two layers (and by fc1's output), one row buffer [B T][max(Cin, 2H)] shared by
+// the input rows and the two layers' hidden states.  Exact fp32.
+
+struct hificar_bigru {
+    hificar_bigru_config cfg;
+    hificar_handle* eng = nullptr;
+    std::map<std::string, std::vector<int64_t>> expected;
+    std::map<std::string, HostTensor> tensors;
+    ConvLayer proj[2], fc1;
+    float4* d_whh[2] = {nullptr, nullptr};  // [dir][3 * H/8][2H] float4 per layer (BigruSplit)
+    float* d_bhh[2] = {nullptr, nullptr};   // [dir][3H] per layer
+    float* d_w2 = nullptr;
+    float* d_b2 = nullptr;
+    int cin_pad = 0;
+    bool finalized = false;
+};
+
+static std::string bigru_fc2_name(const hificar_bigru* g) { return g->cfg.use_tanh ? "fc2.0" : "fc2"; }
+
+extern "C" int hificar_bigru_create(const hificar_bigru_config* cfg, hificar_bigru** out) {
+    if (!cfg || !out) return fail(HIFICAR_E_INVALID, "hificar_bigru_create: null argument");
+    const hificar_bigru_config& c = *cfg;
+    if (c.in_channels < 1 || c.in_channels > HIFICAR_BIGRU_MAX_IN)
+        return fail(HIFICAR_E_INVALID, "BiGRU: in_channels=%d out of range (1 .. %d)", c.in_channels, HIFICAR_BIGRU_MAX_IN);
+    if (c.hidden_size < 64 || c.hidden_size > HIFICAR_BIGRU_MAX_HIDDEN || c.hidden_size % 64 != 0)
+        return fail(HIFICAR_E_INVALID, "BiGRU: hidden_size=%d unsupported (multiples of 64 up to %d: one workgroup holds a direction's W_hh)",
+                    c.hidden_size, HIFICAR_BIGRU_MAX_HIDDEN);
+    if (c.out_channels < 1 || c.out_channels > HIFICAR_BIGRU_MAX_OUT)
+        return fail(HIFICAR_E_INVALID, "BiGRU: out_channels=%d out of range (1 .. %d)", c.out_channels, HIFICAR_BIGRU_MAX_OUT);
+    static_assert(HIFICAR_BIGRU_MAX_OUT == kBigruMaxOut, "head kernel's LDS table");
+    hificar_bigru* g = new hificar_bigru();
+    g->cfg = c;
+    g->eng = new hificar_handle();
+    hificar_handle* h = g->eng;
+    read_env_switches(h);
+    {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+            h->num_cus = prop.multiProcessorCount;
+    }
+    h->precision = HIFICAR_PREC_F32;
+    h->use_pair = false;
+    h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's result does not depend on what it is batched with, bit
+                    // for bit (the GEMMs are a few percent of a forward next to the sweeps, so the split-K form has nothing to win here)
+    const int64_t H = c.hidden_size, C = c.in_channels, O = c.out_channels;
+    g->cin_pad = round_up(c.in_channels, 32);
+    for (int l = 1; l <= 2; ++l)
+        for (const char* sfx : {"", "_reverse"}) {
+            const std::string b = "gru" + std::to_string(l) + ".";
+            g->expected[b + "weight_ih_l0" + sfx] = {3 * H, l == 1 ? C : 2 * H};
+            g->expected[b + "weight_hh_l0" + sfx] = {3 * H, H};
+            g->expected[b + "bias_ih_l0" + sfx] = {3 * H};
+            g->expected[b + "bias_hh_l0" + sfx] = {3 * H};
+        }
+    g->expected["fc1.0.weight"] = {kBigruFc1, 2 * H};
+    g->expected["fc1.0.bias"] = {kBigruFc1};
+    for (const char* n : {"bn.weight", "bn.bias", "bn.running_mean", "bn.running_var"}) g->expected[n] = {kBigruFc1};
+    g->expected[bigru_fc2_name(g) + ".weight"] = {O, kBigruFc1};
+    g->expected[bigru_fc2_name(g) + ".bias"] = {O};
+    int rc = HIFICAR_OK;
+    for (int l = 0; l < 2 && rc == HIFICAR_OK; ++l) {
+        ConvLayer& P = g->proj[l];
+        P.name = "gru" + std::to_string(l + 1) + "#proj";
+        P.cin = l == 0 ? c.in_channels : 2 * c.hidden_size;
+        P.cin_pad = l == 0 ? g->cin_pad : 2 * c.hidden_size;
+        P.cout = 6 * c.hidden_size;
+        P.K = 1;
+        rc = plan_layer(P);
+    }
+    if (rc == HIFICAR_OK) {
+        ConvLayer& F = g->fc1;
+        F.name = "fc1#bn";
+        F.cin = F.cin_pad = 2 * c.hidden_size;
+        F.cout = kBigruFc1;
+        F.K = 1;
+        rc = plan_layer(F);
+    }
+    if (rc != HIFICAR_OK) {
+        hificar_destroy(g->eng);
+        delete g;
+        return rc;
+    }
+    *out = g;
+    return HIFICAR_OK;
+}
+
+extern "C" void hificar_bigru_destroy(hificar_bigru* g) {
+    if (!g) return;
+    hificar_destroy(g->eng);
+    delete g;
+}
+
+extern "C" hificar_handle* hificar_bigru_engine(hificar_bigru* g) { return g ? g->eng : nullptr; }
+
+extern "C" int hificar_bigru_set_weight(hificar_bigru* g, const char* name, const float* data, const int64_t* shape, int ndim) {
+    if (!g || !name || !data || !shape) return fail(HIFICAR_E_INVALID, "hificar_bigru_set_weight: null argument");
+    if (g->finalized) return fail(HIFICAR_E_STATE, "hificar_bigru_set_weight(%s) after hificar_bigru_finalize", name);
+    auto it = g->expected.find(name);
+    if (it == g->expected.end()) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", name);
+    std::vector<int64_t> s(shape, shape + ndim);
+    if (s != it->second) {
+        std::string want, got;
+        for (auto v : it->second) want += std::to_string(v) + ",";
+        for (auto v : s) got += std::to_string(v) + ",";
+        return fail(HIFICAR_E_INVALID, "size mismatch for %s: expected (%s) got (%s)", name, want.c_str(), got.c_str());
+    }
+    size_t n = 1;
+    for (auto v : s) n *= (size_t)v;
+    HostTensor t;
+    t.shape = s;
+    t.data.assign(data, data + n);
+    g->tensors[name] = std::move(t);
+    return HIFICAR_OK;
+}
+
+// W_hh of both directions in the recurrent kernel's order: [dir][gate * H/8 + column][thread 2 i + q] float4 = W_hh[gate H + i][q H/2 + 4 column ..]
+static std::vector<float> bigru_pack_whh(const HostTensor& fwd, const HostTensor& rev, int H) {
+    const int NT = 2 * H, KH = H / 2, CH = KH / 4;
+    std::vector<float> w((size_t)2 * 3 * CH * NT * 4);
+    for (int dir = 0; dir < 2; ++dir) {
+        const std::vector<float>& src = (dir ? rev : fwd).data;
+        for (int gt = 0; gt < 3; ++gt)
+            for (int c = 0; c < CH; ++c)
+                for (int tid = 0; tid < NT; ++tid) {
+                    const int i = tid >> 1, q = tid & 1;
+                    float* dst = &w[((((size_t)dir * 3 + gt) * CH + c) * NT + tid) * 4];
+                    for (int e = 0; e < 4; ++e) dst[e] = src[(size_t)(gt * H + i) * H + q * KH + 4 * c + e];
+                }
+    }
+    return w;
+}
+
+template <int H, int NS>
+static hipError_t bigru_rec_attr() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&bigru_rec_kernel<H, NS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)BigruSplit<H, NS>::lds_bytes);
+}
+
+template <int H, int NS>
+static hipError_t bigru_rec_launch_one(const BigruRecParams& p, hipStream_t stream) {
+    const dim3 grid((unsigned)((p.B + NS - 1) / NS), 2, 1);
+    constexpr size_t lds = BigruSplit<H, NS>::lds_bytes;
+    hipLaunchKernelGGL((bigru_rec_kernel<H, NS>), grid, dim3(2 * H), lds, stream, p);
+    return hipGetLastError();
+}
+
+template <int NS>
+static hipError_t bigru_rec_launch_h(int H, const BigruRecParams& p, hipStream_t stream) {
+    switch (H) {
+        case 64: return bigru_rec_launch_one<64, NS>(p, stream);
+        case 128: return bigru_rec_launch_one<128, NS>(p, stream);
+        case 192: return bigru_rec_launch_one<192, NS>(p, stream);
+        case 256: return bigru_rec_launch_one<256, NS>(p, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+// Sequences per workgroup: one while 2 B workgroups fit the chip (a sequence alone is the fastest sweep: most of W_hh in registers), two beyond.
+static int bigru_tile_height(const hificar_bigru* g, int B) {
+    if (const char* e = getenv("HIFICAR_BIGRU_NS")) {  // A/B runs of the choice (tools/bigru_bench.py)
+        const int v = atoi(e);
+        if (v == 1 || v == 2) return v;
+    }
+    return 2 * B <= g->eng->num_cus ? 1 : 2;
+}
+
+extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
+    if (!g) return fail(HIFICAR_E_INVALID, "hificar_bigru_finalize: null handle");
+    if (g->finalized) return HIFICAR_OK;
+    for (auto& kv : g->expected)
+        if (!g->tensors.count(kv.first)) return fail(HIFICAR_E_STATE, "Missing key(s) in state_dict: \"%s\"", kv.first.c_str());
+    hificar_handle* h = g->eng;
+    const int H = g->cfg.hidden_size, O = g->cfg.out_channels;
+    int rc;
+    for (int l = 0; l < 2; ++l) {
+        const std::string b = "gru" + std::to_string(l + 1) + ".";
+        ConvLayer& P = g->proj[l];
+        HostTensor W, Bv;  // (6H, Cin, 1): forward rows, then reverse rows
+        W.shape = {6 * H, P.cin, 1};
+        for (const char* sfx : {"", "_reverse"}) {
+            const HostTensor& wi = g->tensors.at(b + "weight_ih_l0" + sfx);
+            const HostTensor& bi = g->tensors.at(b + "bias_ih_l0" + sfx);
+            W.data.insert(W.data.end(), wi.data.begin(), wi.data.end());
+            Bv.data.insert(Bv.data.end(), bi.data.begin(), bi.data.end());
+        }
+        Bv.shape = {6 * H};
+        h->tensors[P.name + ".weight"] = std::move(W);
+        h->tensors[P.name + ".bias"] = std::move(Bv);
+        if ((rc = pack_conv(h, P)) != HIFICAR_OK) return rc;
+        float* whh = nullptr;
+        if ((rc = upload(h, bigru_pack_whh(g->tensors.at(b + "weight_hh_l0"), g->tensors.at(b + "weight_hh_l0_reverse"), H), &whh)) != HIFICAR_OK) return rc;
+        g->d_whh[l] = reinterpret_cast<float4*>(whh);
+        std::vector<float> bhh = g->tensors.at(b + "bias_hh_l0").data;
+        const std::vector<float>& br = g->tensors.at(b + "bias_hh_l0_reverse").data;
+        bhh.insert(bhh.end(), br.begin(), br.end());
+        if ((rc = upload(h, bhh, &g->d_bhh[l])) != HIFICAR_OK) return rc;
+    }
+    {   // fc1 with the eval-mode batch norm folded in: y = (W x + b - mean) * gamma / sqrt(var + 1e-5) + beta  (pytorch_models.py:68-70)
+        const HostTensor& W = g->tensors.at("fc1.0.weight");
+        const std::vector<float>&b1 = g->tensors.at("fc1.0.bias").data, &gm = g->tensors.at("bn.weight").data, &bt = g->tensors.at("bn.bias").data,
+                         &mu = g->tensors.at("bn.running_mean").data, &var = g->tensors.at("bn.running_var").data;
+        HostTensor Wf, Bf;
+        Wf.shape = {kBigruFc1, 2 * H, 1};
+        Wf.data.resize(W.data.size());
+        Bf.shape = {kBigruFc1};
+        Bf.data.resize(kBigruFc1);
+        for (int o = 0; o < kBigruFc1; ++o) {
+            const double s = (double)gm[o] / std::sqrt((double)var[o] + 1e-5);
+            for (int k = 0; k < 2 * H; ++k) Wf.data[(size_t)o * 2 * H + k] = (float)((double)W.data[(size_t)o * 2 * H + k] * s);
+            Bf.data[o] = (float)(((double)b1[o] - (double)mu[o]) * s + (double)bt[o]);
+        }
+        h->tensors[g->fc1.name + ".weight"] = std::move(Wf);
+        h->tensors[g->fc1.name + ".bias"] = std::move(Bf);
+        if ((rc = pack_conv(h, g->fc1)) != HIFICAR_OK) return rc;
+    }
+    if ((rc = upload(h, g->tensors.at(bigru_fc2_name(g) + ".weight").data, &g->d_w2)) != HIFICAR_OK) return rc;
+    if ((rc = upload(h, g->tensors.at(bigru_fc2_name(g) + ".bias").data, &g->d_b2)) != HIFICAR_OK) return rc;
+    (void)O;
+    HIP_TRY((bigru_rec_attr<64, 1>()));
+    HIP_TRY((bigru_rec_attr<64, 2>()));
+    HIP_TRY((bigru_rec_attr<128, 1>()));
+    HIP_TRY((bigru_rec_attr<128, 2>()));
+    HIP_TRY((bigru_rec_attr<192, 1>()));
+    HIP_TRY((bigru_rec_attr<192, 2>()));
+    HIP_TRY((bigru_rec_attr<256, 1>()));
+    HIP_TRY((bigru_rec_attr<256, 2>()));
+    if ((rc = engine_setup(h)) != HIFICAR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    h->tensors.clear();
+    g->tensors.clear();
+    h->finalized = true;
+    g->finalized = true;
+    return HIFICAR_OK;
+}
+
+struct BigruWorkspace {
+    float* gates;  // [rows][6H]; fc1's output [rows][128] after the second sweep
+    float* rows;   // [rows][max(cin_pad, 2H)]: input rows, then the layers' hidden states
+    size_t bytes;
+};
+
+static BigruWorkspace bigru_plan_workspace(const hificar_bigru* g, int B, int T, void* base) {
+    const size_t rows = round_up_sz((size_t)std::max(B, 0) * (size_t)std::max(T, 0), 256);  // whole tiles of slack behind the last row
+    const size_t gb = round_up_sz(rows * 6 * g->cfg.hidden_size * sizeof(float), 256);
+    const size_t rb = round_up_sz(rows * std::max(g->cin_pad, 2 * g->cfg.hidden_size) * sizeof(float), 256);
+    BigruWorkspace w;
+    char* p = static_cast<char*>(base);
+    w.gates = reinterpret_cast<float*>(p);
+    w.rows = reinterpret_cast<float*>(p + gb);
+    w.bytes = gb + rb;
+    return w;
+}
+
+extern "C" size_t hificar_bigru_workspace_bytes(const hificar_bigru* g, int B, int T) {
+    if (!g || B < 1 || T < 1) return 0;
+    return bigru_plan_workspace(g, B, T, nullptr).bytes;
+}
+
+extern "C" int hificar_bigru_forward(hificar_bigru* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int T,
+                                     void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!g || !x || !out) return fail(HIFICAR_E_INVALID, "hificar_bigru_forward: null argument");
+    if (!g->finalized) return fail(HIFICAR_E_STATE, "hificar_bigru_forward before hificar_bigru_finalize");
+    if (B < 1 || T < 1 || B > 65535 || (long long)B * T > (1LL << 30) / 8)
+        return fail(HIFICAR_E_INVALID, "hificar_bigru_forward: B=%d, T=%d out of range", B, T);
+    if (lengths_host && !lengths) return fail(HIFICAR_E_INVALID, "hificar_bigru_forward: lengths_host without the device copy");
+    if (lengths_host)
+        for (int b = 0; b < B; ++b)
+            if (lengths_host[b] < 0 || lengths_host[b] > T)
+                return fail(HIFICAR_E_INVALID, "hificar_bigru_forward: lengths[%d]=%d outside 0 .. T=%d", b, lengths_host[b], T);
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
+    const BigruWorkspace ws = bigru_plan_workspace(g, B, T, workspace);
+    if (workspace_bytes < ws.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
+    hificar_handle* h = g->eng;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc;
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    const int H = g->cfg.hidden_size, C = g->cfg.in_channels, O = g->cfg.out_channels, M = B * T;
+    const Ragged rg;
+    {
+        ProfScope prof(h, stream, "bigru_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
+        hipLaunchKernelGGL(bigru_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, ws.rows, C,
+                           g->cin_pad, T);
+        HIP_TRY(hipGetLastError());
+    }
+    const int NS = bigru_tile_height(g, B);
+    for (int l = 0; l < 2; ++l) {
+        const ConvLayer* ls[1] = {&g->proj[l]};
+        ConvIO io[1];
+        io[0] = ConvIO();
+        io[0].xs = reinterpret_cast<const char*>(ws.rows);
+        io[0].y = ws.gates;
+        if ((rc = launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+        BigruRecParams p;
+        p.g = ws.gates;
+        p.w = g->d_whh[l];
+        p.bhh = g->d_bhh[l];
+        p.lengths = lengths;
+        p.y = ws.rows;  // (the projection that read the rows is complete: same stream)
+        p.B = B;
+        p.T = T;
+        ProfScope prof(h, stream, "bigru_rec_kernel", 2.0 * M * 2 * 3 * H * H, 4.0 * M * 8 * H);
+        const hipError_t e = NS == 1 ? bigru_rec_launch_h<1>(H, p, stream) : bigru_rec_launch_h<2>(H, p, stream);
+        if (e != hipSuccess) return fail(HIFICAR_E_HIP, "bigru_rec_kernel launch failed: %s", hipGetErrorString(e));
+    }
+    {
+        const ConvLayer* ls[1] = {&g->fc1};
+        ConvIO io[1];
+        io[0] = ConvIO();
+        io[0].xs = reinterpret_cast<const char*>(ws.rows);
+        io[0].y = ws.gates;
+        if ((rc = launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+    }
+    {
+        BigruHeadParams p;
+        p.f = ws.gates;
+        p.w2 = g->d_w2;
+        p.b2 = g->d_b2;
+        p.lengths = lengths;
+        p.out = out;
+        p.B = B;
+        p.T = T;
+        p.O = O;
+        p.use_tanh = g->cfg.use_tanh;
+        ProfScope prof(h, stream, "bigru_head_kernel", 2.0 * M * kBigruFc1 * O, 4.0 * M * (kBigruFc1 + O));
+        hipLaunchKernelGGL(bigru_head_kernel, dim3((unsigned)((T + 63) / 64), (unsigned)B), dim3(256), 0, stream, p);
+        HIP_TRY(hipGetLastError());
+    }
+    return HIFICAR_OK;
+}

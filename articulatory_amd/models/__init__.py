@@ -10,8 +10,9 @@ from .discriminator import (  # noqa: F401
     HiFiGANPeriodDiscriminator,
     HiFiGANScaleDiscriminator,
 )
+from .bigru import BiGRU  # noqa: F401
 from .gblock import GBlockGenerator  # noqa: F401
 from .hifigan import HiFiGANGenerator  # noqa: F401
 
-__all__ = ["HiFiGANGenerator", "GBlockGenerator", "HiFiGANMultiScaleMultiPeriodDiscriminator", "HiFiGANMultiScaleDiscriminator", "HiFiGANMultiPeriodDiscriminator",
+__all__ = ["HiFiGANGenerator", "GBlockGenerator", "BiGRU", "HiFiGANMultiScaleMultiPeriodDiscriminator", "HiFiGANMultiScaleDiscriminator", "HiFiGANMultiPeriodDiscriminator",
            "HiFiGANScaleDiscriminator", "HiFiGANPeriodDiscriminator"]

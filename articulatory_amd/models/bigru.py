@@ -1,0 +1,248 @@
+"""``BiGRU`` — the speech-to-EMA (articulatory inversion) model behind the reference's ``generator_type`` plugin surface.
+
+Drop-in for ``articulatory.models.BiGRU`` (reference articulatory/models/pytorch_models.py:22-123) in eval mode: same class name,
+constructor keywords and defaults, the same state_dict keys, shapes and order — ``gru{1,2}.{weight,bias}_{ih,hh}_l0[_reverse]``,
+``fc1.0.*``, ``bn.*`` (``num_batches_tracked`` included), ``fc2.*`` / ``fc2.0.*`` — and the same ``forward`` / ``inference`` /
+``register_stats`` / ``remove_weight_norm``.  The modules below only HOLD parameters; the arithmetic runs in ``libhificar.so``
+(``hificar_bigru_*`` of include/hificar.h): no PyTorch-operator implementation, no CPU fallback.
+
+Not built, refused with ``NotImplementedError``: ``use_ar`` (the reference's own driver for it is broken: predict_ema.py:92 passes a
+keyword ``ar_loop`` does not take), ``use_spk_emb``, and a forward in ``train()`` mode (dropout, batch-statistics BatchNorm, autograd).
+``lengths=`` is this package's addition: a ragged batch in which every utterance's result is that of running it alone.
+"""
+
+import ctypes
+import logging
+import math
+
+import numpy as np
+import torch
+
+from .. import _native
+
+FC1_DIM = 128  # pytorch_models.py:32-33
+
+
+class _GRUParams(torch.nn.Module):
+    """Parameter holder with torch.nn.GRU's names and registration order (one bidirectional layer, pytorch_models.py:27-30)."""
+
+    def __init__(self, input_size, hidden_size):
+        super().__init__()
+        k = 1.0 / math.sqrt(hidden_size)  # torch.nn.GRU.reset_parameters
+        for sfx in ("", "_reverse"):
+            for name, shape in (("weight_ih_l0", (3 * hidden_size, input_size)), ("weight_hh_l0", (3 * hidden_size, hidden_size)),
+                                ("bias_ih_l0", (3 * hidden_size,)), ("bias_hh_l0", (3 * hidden_size,))):
+                setattr(self, name + sfx, torch.nn.Parameter(torch.empty(shape).uniform_(-k, k)))
+
+
+class _LinearParams(torch.nn.Module):
+    def __init__(self, in_features, out_features):
+        super().__init__()
+        k = 1.0 / math.sqrt(in_features)  # torch.nn.Linear.reset_parameters
+        self.weight = torch.nn.Parameter(torch.empty(out_features, in_features).uniform_(-k, k))
+        self.bias = torch.nn.Parameter(torch.empty(out_features).uniform_(-k, k))
+
+
+class _BatchNormParams(torch.nn.Module):
+    """torch.nn.BatchNorm1d's parameters and buffers (pytorch_models.py:33); only the running statistics are ever used."""
+
+    def __init__(self, n):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.ones(n))
+        self.bias = torch.nn.Parameter(torch.zeros(n))
+        self.register_buffer("running_mean", torch.zeros(n))
+        self.register_buffer("running_var", torch.ones(n))
+        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+
+
+class BiGRU(torch.nn.Module):
+    """Two bidirectional GRU layers -> Linear(2H, 128) -> BatchNorm1d(128) -> Linear(128, out) (-> tanh); MI355X-native, inference only."""
+
+    def __init__(self, in_channels=80, hidden_size=256, dropout=0.3, out_channels=1,
+                 use_ar=False, ar_input=512, ar_hidden=256, ar_output=128, ar_channels=None, use_tanh=False,
+                 use_spk_emb=False, spk_emb_size=32, spk_emb_hidden=32):
+        super().__init__()
+        if use_ar:
+            raise NotImplementedError("BiGRU(use_ar=True) is not built (the reference's own driver for it cannot run: "
+                                      "egs/ema/voc1/local/predict_ema.py:92 passes a keyword ar_loop does not take)")
+        if use_spk_emb:
+            raise NotImplementedError("BiGRU(use_spk_emb=True) is not built")
+        self.use_ar = False
+        self.use_spk_emb = False
+        self._params = dict(in_channels=in_channels, hidden_size=hidden_size, dropout=dropout, out_channels=out_channels, use_tanh=use_tanh)
+        _native.check_bigru_params(self._params)  # libhificar's own limits: fail here, not at the first forward on the device
+        self.gru1 = _GRUParams(in_channels, hidden_size)
+        self.gru2 = _GRUParams(hidden_size * 2, hidden_size)
+        self.fc1 = torch.nn.Sequential(_LinearParams(hidden_size * 2, FC1_DIM))  # (+ Dropout in the reference: no parameters)
+        self.bn = _BatchNormParams(FC1_DIM)
+        self.fc2 = torch.nn.Sequential(_LinearParams(FC1_DIM, out_channels)) if use_tanh else _LinearParams(FC1_DIM, out_channels)
+        self._handle = None
+        self._lib = None
+        self._workspace_buf = None
+        self._sig = None
+
+    # ------------------------------------------------------------------ reference surface
+    def remove_weight_norm(self):
+        """Nothing carries weight norm (pytorch_models.py:74-84 finds none either); articulatory_amd.bin.decode calls it on every model."""
+
+    def register_stats(self, stats):
+        """Register mean/scale buffers for input normalisation (pytorch_models.py:107-123)."""
+        assert stats.endswith(".h5") or stats.endswith(".npy")
+        if stats.endswith(".h5"):
+            from ..utils.hdf5 import read_hdf5
+
+            mean = read_hdf5(stats, "mean").reshape(-1)
+            scale = read_hdf5(stats, "scale").reshape(-1)
+        else:
+            arr = np.load(stats)
+            mean = arr[0].reshape(-1)
+            scale = arr[1].reshape(-1)
+        self.register_buffer("mean", torch.from_numpy(np.asarray(mean)).float())
+        self.register_buffer("scale", torch.from_numpy(np.asarray(scale)).float())
+        logging.info("Successfully registered stats as buffer.")
+
+    def inference(self, c, normalize_before=True, ar=None, spk=None):
+        """(T, in_channels) tensor or ndarray -> (T, out_channels), pytorch_models.py:86-105 statement for statement (a 3-D input is
+        taken as (1, in_channels, T); ``normalize_before`` defaults to True here, unlike the generators)."""
+        if len(c.shape) == 3:
+            c = c.transpose(1, 2)
+            c = c[0]
+        if not isinstance(c, torch.Tensor):
+            c = torch.tensor(c, dtype=torch.float).to(self._device())
+        if normalize_before:
+            c = (c - self.mean) / self.scale
+        c = self.forward(c.unsqueeze(0).transpose(1, 2), ar=ar, spk=spk)
+        return c.transpose(1, 2).squeeze(0)
+
+    # ------------------------------------------------------------------ native handle
+    def _device(self):
+        return self.gru1.weight_ih_l0.device
+
+    def native_state(self):
+        """{reference state_dict key: fp32 CPU tensor} of what the C ABI consumes (every float tensor but the input statistics)."""
+        out = {}
+        for k, v in self.state_dict().items():
+            if k in ("mean", "scale") or k.endswith("num_batches_tracked"):
+                continue
+            out[k] = v.detach().float().cpu().contiguous()
+        return out
+
+    def _signature(self):
+        ts = list(self.parameters()) + [self.bn.running_mean, self.bn.running_var]
+        return tuple((t.data_ptr(), t._version) for t in ts)
+
+    def _invalidate(self):
+        h = self.__dict__.get("_handle")
+        if h is not None and self._lib is not None:
+            self._lib.hificar_bigru_destroy(h)
+        self._handle = None
+        self._workspace_buf = None
+        self._sig = None
+
+    def __del__(self):
+        try:
+            self._invalidate()
+        except Exception:
+            pass
+
+    def __getstate__(self):  # copies and pickles never share a native handle
+        state = self.__dict__.copy()
+        for k in ("_handle", "_lib", "_workspace_buf", "_sig"):
+            state[k] = None
+        return state
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        out = super().load_state_dict(state_dict, strict=strict, **kw)
+        self._invalidate()
+        return out
+
+    def _apply(self, fn, *a, **kw):
+        out = super()._apply(fn, *a, **kw)
+        self._invalidate()
+        return out
+
+    def refresh_native(self):
+        """Re-upload the weights after an in-place parameter edit that the version counters do not show (``p.data.copy_``)."""
+        self._invalidate()
+
+    def _native_handle(self):
+        if self._handle is not None and self._sig == self._signature():
+            return self._handle
+        self._invalidate()
+        dev = self._device()
+        if dev.type != "cuda":
+            raise RuntimeError("BiGRU: parameters are on %s; the forward only exists as HIP kernels (move the model to a MI355X with "
+                               ".to('cuda')). There is no CPU fallback." % (dev,))
+        lib = _native.load_library()
+        self._lib = lib
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(dev):
+            cfg = _native.make_bigru_config(self._params)
+            _native.check(lib.hificar_bigru_create(ctypes.byref(cfg), ctypes.byref(handle)), "hificar_bigru_create")
+            try:
+                for name, t in self.native_state().items():
+                    shape = (ctypes.c_int64 * t.dim())(*t.shape)
+                    _native.check(lib.hificar_bigru_set_weight(handle, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim()),
+                                  "hificar_bigru_set_weight")
+                _native.check(lib.hificar_bigru_finalize(handle), "hificar_bigru_finalize")
+            except Exception:
+                lib.hificar_bigru_destroy(handle)
+                raise
+        self._handle = handle
+        self._sig = self._signature()
+        return handle
+
+    def _workspace(self, B, T):
+        """One grow-only scratch buffer per model (pre-gates of B x T frames + one row buffer: hificar_bigru_workspace_bytes)."""
+        n = self._lib.hificar_bigru_workspace_bytes(self._handle, B, T) + 256
+        ws = self._workspace_buf
+        if ws is None or ws.numel() < n:
+            # work already enqueued on the old buffer keeps it alive through the caching allocator's stream ordering
+            ws = torch.empty(int(n * 1.25) if ws is not None else n, dtype=torch.uint8, device=self._device())
+            self._workspace_buf = ws
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
+    def engine(self):
+        """The engine handle for ``hificar_profile_begin`` / ``hificar_profile_end`` (per-kernel device times; tools/bigru_bench.py)."""
+        return ctypes.c_void_p(self._lib.hificar_bigru_engine(self._native_handle()))
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, mels, mask=None, spk_id=None, spk=None, ar=None, ph=None, lengths=None):
+        """mels: (B, in_channels, T) -> EMA (B, out_channels, T)  (pytorch_models.py:45-72, eval mode).  ``mask``, ``spk_id``, ``ph`` (and,
+        without use_ar / use_spk_emb, ``ar`` and ``spk``) are accepted and ignored, as in the reference.  ``lengths`` (B frame counts): a
+        ragged batch — utterance b is computed as if it were alone with lengths[b] frames (its reverse direction starts at its own last
+        frame; zero padding would not be equivalent) and out[b, :, lengths[b]:] is zero."""
+        if self.training:
+            raise NotImplementedError("BiGRU.forward in train() mode is not built (dropout, batch-statistics BatchNorm and autograd): "
+                                      "call .eval() — training a BiGRU is out of scope")
+        if not isinstance(mels, torch.Tensor) or mels.device.type != "cuda":
+            raise RuntimeError("BiGRU.forward needs a CUDA/HIP tensor; there is no CPU fallback")
+        if mels.dim() != 3 or mels.shape[1] != self._params["in_channels"]:
+            raise RuntimeError(f"BiGRU.forward: expected (B, {self._params['in_channels']}, T), got {tuple(mels.shape)}")
+        handle = self._native_handle()
+        if mels.device != self._device():
+            raise RuntimeError(f"BiGRU.forward: input on {mels.device}, parameters on {self._device()}")
+        c = mels.detach().to(torch.float32).contiguous()
+        B, _, T = c.shape
+        if B < 1 or T < 1:
+            raise RuntimeError(f"BiGRU.forward: empty input {tuple(c.shape)}")
+        lens = (None, None)
+        keep = None
+        if lengths is not None:
+            host = (lengths.detach().to("cpu", torch.int32) if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths, dtype=torch.int32))
+            host = host.reshape(-1).contiguous()
+            if host.numel() != B:
+                raise RuntimeError(f"lengths has {host.numel()} entries for a batch of {B}")
+            if int(host.min()) < 0 or int(host.max()) > T:
+                raise RuntimeError(f"lengths must lie in [0, {T}]")
+            keep = (host, host.to(c.device).contiguous())
+            lens = (keep[1].data_ptr(), keep[0].data_ptr())
+        out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=c.device)
+        with torch.cuda.device(c.device):
+            ws_ptr, ws_bytes = self._workspace(B, T)
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = self._lib.hificar_bigru_forward(handle, c.data_ptr(), lens[0], lens[1], out.data_ptr(), B, T, ws_ptr, ws_bytes,
+                                                 ctypes.c_void_p(stream))
+        _native.check(rc, "hificar_bigru_forward")
+        return out

@@ -437,3 +437,54 @@ def synth_disc_state_dict(discriminator_params: dict, seed: int = 4321, gain: fl
             norm = np.sqrt((v.reshape(v.shape[0], -1) ** 2).sum(axis=1)).reshape(shape)
             out[name] = (norm * uniform(seed, name, shape, 0.8, 1.2).astype(np.float64)).astype(np.float32)
     return OrderedDict((k, out[k]) for k in spec)
+
+
+# ------------------------------------------------------------------------------------------------
+# BiGRU, the speech-to-EMA inversion model (reference articulatory/models/pytorch_models.py:22-123)
+# ------------------------------------------------------------------------------------------------
+def bigru_param_spec(in_channels=80, hidden_size=256, out_channels=1, use_tanh=False, **_ignored):
+    """Ordered {state_dict key: shape} of the reference's ``BiGRU(**kwargs)`` without use_ar / use_spk_emb: torch.nn.GRU lists a
+    direction's weight_ih, weight_hh, bias_ih, bias_hh and then the reverse direction's; BatchNorm1d its parameters, then its buffers.
+    Checked key-for-key against the real class by tools/make_golden_bigru.py (tests/golden/gold_bigru_keys.txt)."""
+    spec = OrderedDict()
+    H = hidden_size
+    for name, cin in (("gru1", in_channels), ("gru2", 2 * H)):
+        for sfx in ("", "_reverse"):
+            spec[f"{name}.weight_ih_l0{sfx}"] = (3 * H, cin)
+            spec[f"{name}.weight_hh_l0{sfx}"] = (3 * H, H)
+            spec[f"{name}.bias_ih_l0{sfx}"] = (3 * H,)
+            spec[f"{name}.bias_hh_l0{sfx}"] = (3 * H,)
+    spec["fc1.0.weight"] = (128, 2 * H)
+    spec["fc1.0.bias"] = (128,)
+    spec["bn.weight"] = (128,)
+    spec["bn.bias"] = (128,)
+    spec["bn.running_mean"] = (128,)
+    spec["bn.running_var"] = (128,)
+    spec["bn.num_batches_tracked"] = ()
+    fc2 = "fc2.0" if use_tanh else "fc2"
+    spec[fc2 + ".weight"] = (out_channels, 128)
+    spec[fc2 + ".bias"] = (out_channels,)
+    return spec
+
+
+def synth_bigru_state_dict(params: dict, seed: int = 1234, gain: float = 1.0) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic reference-layout state_dict of a BiGRU from the same name-keyed generator as the other specs: matrices
+    U(+-gain * sqrt(3 / fan_in)), biases U(+-0.05), a batch norm that is not the identity (running_var in [0.5, 1.5], weight in
+    [0.8, 1.2], running_mean and bias in +-0.3), num_batches_tracked an int64 scalar.  gain 1 keeps the recurrence well conditioned:
+    at gain 2 an fp32 and a float64 run of the reference already differ by 3e-6 .. 8e-6 of max|y|, at gain 4 completely."""
+    out = OrderedDict()
+    for name, shape in bigru_param_spec(**params).items():
+        if name == "bn.num_batches_tracked":
+            out[name] = np.array(1000, dtype=np.int64)
+        elif name == "bn.running_var":
+            out[name] = uniform(seed, name, shape, 0.5, 1.5)
+        elif name == "bn.weight":
+            out[name] = uniform(seed, name, shape, 0.8, 1.2)
+        elif name in ("bn.running_mean", "bn.bias"):
+            out[name] = uniform(seed, name, shape, -0.3, 0.3)
+        elif len(shape) == 2:
+            b = gain * np.sqrt(3.0 / shape[1])
+            out[name] = uniform(seed, name, shape, -b, b)
+        else:
+            out[name] = uniform(seed, name, shape, -0.05, 0.05)
+    return out

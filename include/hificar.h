@@ -24,6 +24,8 @@
  *   hificar_ar_loop_cond, hificar_ar_loop_packed_cond, hificar_ar_step_cond
  *                           the same three loops for speaker- / phoneme-conditioned models: every chunk's forward is
  *                           forward(c, spk_id=, ar=prev, ph=)                    articulatory/bin/decode.py:54-83 + hifigan.py:212-220
+ *   hificar_bigru_*         BiGRU (the speech-to-EMA inversion model): __init__, load_state_dict, eval().to(device), forward
+ *                                                                articulatory/models/pytorch_models.py:22-72 (declared at the end of this file)
  *   hificar_pcm16           sf.write(..., "PCM_16") sample conversion articulatory/bin/decode.py:319-324
  *   hificar_workspace_bytes (torch's caching allocator does this implicitly in the reference)
  *   hificar_last_error      Python exceptions / assert           articulatory/models/hifigan.py:78-80
@@ -493,6 +495,59 @@ int hificar_stft_loss_backward(hificar_mel* m, int B, int T, const float* gweigh
                                void* stream);
 int hificar_mel_loss(hificar_mel* m, const float* y_hat, const float* y, int B, int T, float* value, float* dy_hat, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Articulatory inversion: the BiGRU speech-to-EMA model (articulatory/models/pytorch_models.py:22-123) in eval mode — two bidirectional
+ * GRU layers (torch.nn.GRU, gate order r, z, n, h0 = 0), Linear(2H, 128), BatchNorm1d(128) on running statistics, Linear(128, out) and an
+ * optional tanh.  The reference has no native boundary here either (torch.nn modules; driven by model.inference, articulatory/bin/decode.py:338-350).
+ * Exact fp32.  Errors as everywhere: a negative HIFICAR_E_* code and hificar_last_error().
+ * --------------------------------------------------------------------------------------------------------------------------- */
+#define HIFICAR_BIGRU_MAX_IN 4096
+#define HIFICAR_BIGRU_MAX_HIDDEN 256
+#define HIFICAR_BIGRU_MAX_OUT 32
+
+/* Mirrors the keyword arguments of BiGRU.__init__ (pytorch_models.py:23-25) that affect eval-mode inference; use_ar and use_spk_emb
+ * models are not built (the binding refuses them). */
+typedef struct hificar_bigru_config {
+    int32_t in_channels;  /* 1 .. HIFICAR_BIGRU_MAX_IN */
+    int32_t hidden_size;  /* a multiple of 64, at most HIFICAR_BIGRU_MAX_HIDDEN: one workgroup holds one direction's W_hh */
+    int32_t out_channels; /* 1 .. HIFICAR_BIGRU_MAX_OUT */
+    int32_t use_tanh;     /* fc2 = Sequential(Linear, Tanh): its tensors are then named "fc2.0.*" (pytorch_models.py:34-37) */
+} hificar_bigru_config;
+
+typedef struct hificar_bigru hificar_bigru;
+
+/* BiGRU.__init__ (pytorch_models.py:23-43): an empty model for these hyper-parameters on the current HIP device. */
+int hificar_bigru_create(const hificar_bigru_config* cfg, hificar_bigru** out);
+
+/* load_state_dict (articulatory/utils/utils.py:340-342), one tensor at a time by its reference state_dict name: "gru1.weight_ih_l0"
+ * (3H, in_channels), "gru2.weight_ih_l0" (3H, 2H), "gru<l>.weight_hh_l0" (3H, H), "gru<l>.bias_ih_l0" / "gru<l>.bias_hh_l0" (3H), each also
+ * with the suffix "_reverse"; "fc1.0.weight" (128, 2H), "fc1.0.bias"; "bn.weight", "bn.bias", "bn.running_mean", "bn.running_var" (128);
+ * "fc2.weight" (out, 128), "fc2.bias" — "fc2.0.*" with use_tanh.  data: HOST pointer to contiguous fp32; the caller keeps ownership. */
+int hificar_bigru_set_weight(hificar_bigru* h, const char* name, const float* data, const int64_t* shape, int ndim);
+
+/* model.eval().to(device) (decode.py:276-277): checks that every tensor arrived, folds the batch norm into fc1, repacks, uploads.
+ * Synchronises the device once. */
+int hificar_bigru_finalize(hificar_bigru* h);
+
+/* Bytes of device scratch hificar_bigru_forward needs for B sequences of T frames: the pre-gate buffer (B T 6H floats, shared by the two
+ * GRU layers) and one row buffer (B T max(in_channels, 2H) floats).  (torch's caching allocator does this implicitly in the reference.) */
+size_t hificar_bigru_workspace_bytes(const hificar_bigru* h, int B, int T);
+
+/* BiGRU.forward in eval mode (pytorch_models.py:45-72): x (B, in_channels, T) device fp32 -> out (B, out_channels, T) device fp32.
+ * lengths: DEVICE pointer to B int32 frame counts (0 <= lengths[b] <= T) or NULL (all T): sequence b is computed exactly as if it were alone
+ * with lengths[b] frames — its reverse direction starts at its own last frame — and out[b, :, lengths[b]:] is written as zeros.  The
+ * reference has no such batches: this is its per-utterance loop (decode.py:292-351) run B utterances at a time.  lengths_host: optional HOST
+ * copy of the same values (NULL = unknown to the host), checked against T before anything is enqueued.  workspace: 256-byte aligned,
+ * hificar_bigru_workspace_bytes(h, B, T) bytes.  Stream rules as in the conventions at the top. */
+int hificar_bigru_forward(hificar_bigru* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int T,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* The engine handle, for hificar_profile_begin / hificar_profile_end (the reference times whole utterances, decode.py:302-318). */
+hificar_handle* hificar_bigru_engine(hificar_bigru* h);
+
+/* del model */
+void hificar_bigru_destroy(hificar_bigru* h);
 
 #ifdef __cplusplus
 }
