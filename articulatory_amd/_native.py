@@ -40,6 +40,7 @@ SYMBOLS = (
     "hificar_ar_step_cond",
     "hificar_macs",
     "hificar_pcm16",
+    "hificar_engine_of",
     "hificar_profile_begin",
     "hificar_profile_end",
     "hificar_debug_tap",
@@ -317,6 +318,8 @@ def load_library():
     lib.hificar_macs.restype = ctypes.c_double
     lib.hificar_pcm16.argtypes = [vp, vp, ctypes.c_size_t, vp]
     lib.hificar_pcm16.restype = ctypes.c_int
+    lib.hificar_engine_of.argtypes = [vp]
+    lib.hificar_engine_of.restype = vp
     lib.hificar_profile_begin.argtypes = [vp]
     lib.hificar_profile_begin.restype = ctypes.c_int
     lib.hificar_profile_end.argtypes = [vp, ctypes.POINTER(HificarKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]

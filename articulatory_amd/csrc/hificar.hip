@@ -82,7 +82,7 @@ struct GBlockLayers {
     int cin = 0, cout = 0;
 };
 
-// A launch shape of the conv engine: what a ConvPlan is a function of, besides the handle's fixed switches.  A layer is identified by its
+// A launch shape of the conv engine: what a ConvPlan is a function of, besides the engine's fixed switches.  A layer is identified by its
 // address: every engine (generator, GBlock generator, their TrainState's data-gradient layers, the discriminators' per-group layers, mel)
 // builds its ConvLayers once, in create / train_init, into storage it owns and never resizes afterwards.
 struct PlanKey {
@@ -105,26 +105,77 @@ struct ConvPlan {
     PairParams pair = {};       // launch_pair
 };
 
-struct hificar_handle {
-    hificar_config cfg;
-    int arch = 0;                  // 0: HiFiGANGenerator (hificar_create); 1: GBlockGenerator (hificar_gblock_create, hificar_gblock.hip.inc)
-    std::vector<GBlockLayers> gb;  // arch 1
-    int c_last = 0;                // channels in front of the output conv
-    bool finalized = false;
+// The conv engine: everything a launch needs whatever network owns it.  Every model type holds one — the generators by inheritance
+// (hificar_handle below), hificar_disc / hificar_mel / hificar_bigru as a member — opened by engine_open, closed by engine_close.
+struct hificar_engine {
     int precision = HIFICAR_PREC_F32;
+    int num_cus = 256;
+    bool training = false;         // weights are device-resident (the generator sets it where it creates its TrainState): part of the plan key
     bool profile_detail = false;   // HIFICAR_PROFILE_DETAIL=1: profile rows carry the layer name
     bool use_pair = true;          // HIFICAR_PAIR=0: run narrow stages layer by layer (A/B runs)
+    bool pair_small = true;        // HIFICAR_PAIR_SMALL: 128-row fused pair tiles at C = 32 for mid-size launches (pair_small_tiles)
+    int ksplit = 1;                // HIFICAR_KSPLIT: 0 = never use the split-K conv form, 1 = when it is estimated faster (default), 2 = always
     double mi1_penalty = 1.05;     // cost factor of 32-row tiles in the exact-fp32 tile choice (they re-stream the weights most often: L2-bound when
                                    // K is long).  The discriminator engine raises it: its launches overlap on several streams, so a nearly
                                    // empty last round of taller tiles costs little there, while the L2 traffic of short tiles is shared by all
     int pick_throughput = 0;       // > 0: launches of at least this many tiles choose their tile shape by workgroup-time instead of makespan (set by
                                    // the discriminator engine, whose sub-networks run on eight streams; 0 = off)
-    bool pair_small = true;        // HIFICAR_PAIR_SMALL: 128-row fused pair tiles at C = 32 for mid-size launches (pair_small_tiles)
-    int ksplit = 1;                // HIFICAR_KSPLIT: 0 = never use the split-K conv form, 1 = when it is estimated faster (default), 2 = always
+    bool shared_chip = false;      // set while hificar_ar_loop runs two halves of a batch on two streams (launch_conv's tile choice)
+    std::vector<void*> allocs;     // device memory the engine's owner uploaded through it (upload, pack_w16 / pack_w32): freed by engine_close
+    char* d_zeros = nullptr;       // 256 bytes of zeros: source of padding rows for the LDS DMA
+    // launch plans, one per launch shape (get_plan), each with the tile schedule it built.  The schedules live in append-only arenas: a
+    // device block plus a pinned host mirror, filled on the host and uploaded with ONE hipMemcpyAsync on the launch stream, so the first use of
+    // a new launch shape neither allocates nor synchronises (the first arena is allocated by engine_open).  Dropped only together: evict_plans
+    std::map<PlanKey, ConvPlan> plans;
+    struct Arena {
+        char* d = nullptr;
+        char* h = nullptr;
+        size_t cap = 0, used = 0;
+    };
+    std::vector<Arena> arenas;
+    unsigned long long sched_up_seq = 0;  // schedule uploads so far (upload_schedule): a schedule is uploaded on the stream that first needs it
+    // device copies of the batched-reduction tables of the backward passes (flush_reduce, hificar_train.hip.inc), cached by content: in steady
+    // state a training iteration re-uses the tables of the iteration before (same buffers from the caller's caching allocator) without any upload
+    struct ReduceSlot {
+        char* d = nullptr;
+        char* h = nullptr;
+        size_t bytes = 0;
+        unsigned long long hash = 0, stamp = 0;
+        hipEvent_t ev = nullptr;  // recorded behind the last launch that reads the slot
+        hipEvent_t up = nullptr;  // recorded behind the upload
+        hipStream_t up_stream = nullptr;
+    };
+    std::vector<ReduceSlot> rslots;
+    unsigned long long rstamp = 0;
+    // every call's work is ordered behind the previous call's even when the caller switches streams (the schedules and, for a generator,
+    // the packed step table and the workspace are shared state)
+    hipStream_t last_stream = nullptr;
+    bool have_last_stream = false;
+    hipEvent_t xstream_ev = nullptr;
+    hipEvent_t done_ev = nullptr;  // recorded at the END of the last call on done_stream (calls that mark their end: the discriminators' backward)
+    bool done_valid = false;
+    hipStream_t done_stream = nullptr;
+    // profiling (hificar_profile_begin/end)
+    bool profiling = false;
+    struct ProfRec {
+        hipEvent_t e0, e1;
+        std::string name;
+        double flops, bytes;
+    };
+    std::vector<ProfRec> prof;
+    hipStream_t prof_stream = nullptr;
+};
+
+// The generator (HiFiGANGenerator or GBlockGenerator) on top of its engine: configuration, layers, AR step tables, taps, TrainState.
+struct hificar_handle : hificar_engine {
+    hificar_config cfg;
+    int arch = 0;                  // 0: HiFiGANGenerator (hificar_create); 1: GBlockGenerator (hificar_gblock_create, hificar_gblock.hip.inc)
+    std::vector<GBlockLayers> gb;  // arch 1
+    int c_last = 0;                // channels in front of the output conv
+    bool finalized = false;
     int cf = 0;       // feature channels = in_channels - ar_output*use_ar
     int cin_pad = 0;  // padded input-conv channels
     int hop = 1;
-    int num_cus = 256;
     std::map<std::string, std::vector<int64_t>> expected;  // name -> shape
     std::map<std::string, HostTensor> tensors;
     ConvLayer input_conv;
@@ -147,8 +198,6 @@ struct hificar_handle {
     float* d_ph_emb = nullptr;
     float* d_phfc_w = nullptr;
     float* d_phfc_b = nullptr;
-    std::vector<void*> allocs;
-    char* d_zeros = nullptr;  // 256 bytes of zeros: source of padding rows for the LDS DMA
     void* d_tab = nullptr;    // step table of hificar_ar_loop_packed (grown on demand) and its pinned host staging copy
     void* h_tab = nullptr;
     size_t tab_bytes = 0;
@@ -166,43 +215,10 @@ struct hificar_handle {
     char* step_hd = nullptr;  // step_h as the device sees it
     size_t step_cap = 0;      // table entries per slot
     unsigned step_next = 0;
-    // launch plans, one per launch shape (get_plan), each with the tile schedule it built.  The schedules live in append-only arenas: a
-    // device block plus a pinned host mirror, filled on the host and uploaded with ONE hipMemcpyAsync on the launch stream, so the first use of
-    // a new launch shape neither allocates nor synchronises (the first arena is allocated in hificar_finalize).  Dropped only together: evict_plans
-    std::map<PlanKey, ConvPlan> plans;
-    struct Arena {
-        char* d = nullptr;
-        char* h = nullptr;
-        size_t cap = 0, used = 0;
-    };
-    std::vector<Arena> arenas;
-    // device copies of the batched-reduction tables of the backward passes (flush_reduce, hificar_train.hip.inc), cached by content: in steady
-    // state a training iteration re-uses the tables of the iteration before (same buffers from the caller's caching allocator) without any upload
-    struct ReduceSlot {
-        char* d = nullptr;
-        char* h = nullptr;
-        size_t bytes = 0;
-        unsigned long long hash = 0, stamp = 0;
-        hipEvent_t ev = nullptr;  // recorded behind the last launch that reads the slot
-        hipEvent_t up = nullptr;  // recorded behind the upload
-        hipStream_t up_stream = nullptr;
-    };
-    std::vector<ReduceSlot> rslots;
-    unsigned long long rstamp = 0;
-    // every call's work is ordered behind the previous call's even when the caller switches streams (the schedules, the packed
-    // step table and the workspace are shared state of the handle)
-    hipStream_t last_stream = nullptr;
-    bool have_last_stream = false;
-    hipEvent_t xstream_ev = nullptr;
     // AR loop of a small batch on two streams (hificar_ar_loop_ragged): the second stream, fork / join / schedule-upload events
-    bool shared_chip = false;      // set while hificar_ar_loop runs two halves of a batch on two streams (launch_conv's tile choice)
     int ar_dual_min = 17, ar_dual_max = 62;  // HIFICAR_AR_DUAL_MIN / _MAX: the batch sizes the loop splits (max 0: never)
     hipStream_t ar_side = nullptr;
     hipEvent_t ar_ev[2] = {nullptr, nullptr};
-    unsigned long long sched_up_seq = 0;  // schedule uploads so far (upload_schedule): a schedule is uploaded on the stream that first needs it
-    hipEvent_t done_ev = nullptr;  // recorded at the END of the last call on done_stream (calls that mark their end: the discriminators' backward)
-    bool done_valid = false;
-    hipStream_t done_stream = nullptr;
     // debug taps (hificar_debug_tap): name -> (destination, capacity in floats); scratch for pre-activation copies
     struct Tap {
         float* dst;
@@ -211,29 +227,22 @@ struct hificar_handle {
     std::map<std::string, Tap> taps;
     float* tap_scratch = nullptr;
     size_t tap_scratch_elems = 0;
-    // profiling (hificar_profile_begin/end)
-    bool profiling = false;
-    struct ProfRec {
-        hipEvent_t e0, e1;
-        std::string name;
-        double flops, bytes;
-    };
-    std::vector<ProfRec> prof;
-    hipStream_t prof_stream = nullptr;
 };
 
-// The library's environment switches — all of them, read once per handle (generator, GBlock generator, the discriminators' engine):
+// The library's environment switches — all of them.  engine_open reads the engine's own, once per engine: the generators' (in hificar_finalize),
+// the discriminators' and the BiGRU's; the mel / STFT loss engine runs with the defaults.
 //   HIFICAR_PROFILE_DETAIL=1   rows of hificar_profile_end carry the layer name ("kernel|layer xN")
 //   HIFICAR_LAUNCH_LOG=<path>  every kernel launch of the library is appended to <path> in enqueue order as "kernel|layer<TAB>flops<TAB>algorithmic bytes":
 //                              joined with rocprofv3's per-dispatch rows by tools/pmc_by_layer.py (implies PROFILE_DETAIL)
 //   HIFICAR_KSPLIT=0|1|2       split-K conv form: never / when estimated faster (default) / always.  0 makes every launch shape use one accumulation
 //                              order, so results are bit-identical across batch compositions (tests/test_gpu_parity.py)
 //   HIFICAR_PAIR=0             narrow stages layer by layer instead of the fused pair kernels;  HIFICAR_PAIR_SMALL=0: no 128-row pair tiles at C = 32
-//   HIFICAR_AR_DUAL_MIN / _MAX the batch sizes hificar_ar_loop runs as two halves on two streams (default 17..62; MAX=0: never)
+//                              (the GBlock generator, the discriminators and the BiGRU have no such stages: they switch the pair kernels off)
+// The generators add HIFICAR_AR_DUAL_MIN / _MAX: the batch sizes hificar_ar_loop runs as two halves on two streams (default 17..62; MAX=0: never).
 // hificar_disc.hip.inc adds HIFICAR_DISC_STREAMS=0 (sub-discriminators on the caller's stream: per-launch counters) and HIFICAR_COL2IM_VEC4=0.
 // hificar_bigru.hip.inc adds HIFICAR_BIGRU_NS=1|2 (sequences per workgroup of the recurrent kernel, A/B runs) and always runs with KSPLIT off.
 static FILE* g_launch_log = nullptr;
-static void read_env_switches(hificar_handle* h) {
+static void read_env_switches(hificar_engine* h) {
     if (const char* e = getenv("HIFICAR_PROFILE_DETAIL")) h->profile_detail = atoi(e) != 0;
     if (const char* e = getenv("HIFICAR_LAUNCH_LOG")) {
         if (!g_launch_log && *e) g_launch_log = fopen(e, "a");
@@ -242,18 +251,16 @@ static void read_env_switches(hificar_handle* h) {
     if (const char* e = getenv("HIFICAR_KSPLIT")) h->ksplit = atoi(e);
     if (const char* e = getenv("HIFICAR_PAIR")) h->use_pair = atoi(e) != 0;
     if (const char* e = getenv("HIFICAR_PAIR_SMALL")) h->pair_small = atoi(e) != 0;
-    if (const char* e = getenv("HIFICAR_AR_DUAL_MIN")) h->ar_dual_min = atoi(e);
-    if (const char* e = getenv("HIFICAR_AR_DUAL_MAX")) h->ar_dual_max = atoi(e);
 }
 
 // RAII bracket around one kernel launch: the launch log, and an event before and after while profiling is on.
 struct ProfScope {
-    hificar_handle* h;
+    hificar_engine* h;
     hipStream_t s;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     std::string name;
     double flops, bytes;
-    ProfScope(hificar_handle* h_, hipStream_t s_, const std::string& n, double f, double b) : h(h_), s(s_), flops(f), bytes(b) {
+    ProfScope(hificar_engine* h_, hipStream_t s_, const std::string& n, double f, double b) : h(h_), s(s_), flops(f), bytes(b) {
         if (g_launch_log) {
             fprintf(g_launch_log, "%s\t%.0f\t%.0f\n", n.c_str(), f, b);
             fflush(g_launch_log);
@@ -273,7 +280,8 @@ struct ProfScope {
 };
 
 static size_t round_up_sz(size_t x, size_t m) { return (x + m - 1) / m * m; }
-static int arena_add(hificar_handle* h, size_t min_bytes);
+static int arena_add(hificar_engine* h, size_t min_bytes);
+static void engine_close(hificar_engine* h);
 static int bucket_frames(int T);
 
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -360,13 +368,6 @@ extern "C" int hificar_create(const hificar_config* cfg, hificar_handle** out) {
 
     hificar_handle* h = new hificar_handle();
     h->cfg = c;
-    read_env_switches(h);
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            h->num_cus = prop.multiProcessorCount;
-    }
     h->precision = c.precision;
     if (c.use_spk_id && (c.num_spk < 1 || c.spk_emb_size < 1 || c.in_channels > 1024)) {
         delete h;
@@ -498,7 +499,6 @@ extern "C" int hificar_create(const hificar_config* cfg, hificar_handle** out) {
 
 extern "C" void hificar_destroy(hificar_handle* h) {
     if (!h) return;
-    for (void* p : h->allocs) (void)hipFree(p);
     if (h->d_tab) (void)hipFree(h->d_tab);
     if (h->h_tab) (void)hipHostFree(h->h_tab);
     if (h->tap_scratch) (void)hipFree(h->tap_scratch);
@@ -508,21 +508,10 @@ extern "C" void hificar_destroy(hificar_handle* h) {
     if (h->step_h) (void)hipHostFree(h->step_h);
     for (auto& st : h->step_ring)
         if (st.done) (void)hipEventDestroy(st.done);
-    for (auto& a : h->arenas) {
-        (void)hipFree(a.d);
-        (void)hipHostFree(a.h);
-    }
-    if (h->xstream_ev) (void)hipEventDestroy(h->xstream_ev);
     if (h->ar_side) (void)hipStreamDestroy(h->ar_side);
     for (hipEvent_t e : h->ar_ev)
         if (e) (void)hipEventDestroy(e);
-    if (h->done_ev) (void)hipEventDestroy(h->done_ev);
-    for (auto& r : h->rslots) {
-        if (r.d) (void)hipFree(r.d);
-        if (r.h) (void)hipHostFree(r.h);
-        if (r.ev) (void)hipEventDestroy(r.ev);
-        if (r.up) (void)hipEventDestroy(r.up);
-    }
+    engine_close(h);
     delete h;
 }
 
@@ -550,7 +539,7 @@ extern "C" int hificar_set_weight(hificar_handle* h, const char* name, const flo
 // ------------------------------------------------------------------------------------------------
 // finalize: repack + upload
 // ------------------------------------------------------------------------------------------------
-static int upload(hificar_handle* h, const std::vector<float>& v, float** dptr) {
+static int upload(hificar_engine* h, const std::vector<float>& v, float** dptr) {
     void* p = nullptr;
     HIP_TRY(hipMalloc(&p, std::max<size_t>(v.size(), 1) * sizeof(float)));
     h->allocs.push_back(p);
@@ -573,7 +562,7 @@ static inline float bf16_to_f32(uint16_t b) {
 }
 
 // bf16x3 path: weight fragments in MFMA lane order, [n_block32][chunk][tap][c16][hi|lo][lane][8]
-static int pack_w16(hificar_handle* h, const ConvLayer& L, const HostTensor& W, int chunk, uint16_t** out) {
+static int pack_w16(hificar_engine* h, const ConvLayer& L, const HostTensor& W, int chunk, uint16_t** out) {
     const int nc16 = chunk / 16, nchunk = L.cin_pad / chunk;
     const size_t frag = 64 * 8;  // bf16 elements per fragment
     std::vector<uint16_t> w16(((size_t)L.n_blocks32 * nchunk * L.ntaps * nc16 * 2 + 4 * nc16) * frag, 0);
@@ -613,7 +602,7 @@ static int pack_w16(hificar_handle* h, const ConvLayer& L, const HostTensor& W, 
 
 // exact-fp32 arithmetic: fp32 weight fragments, [n_block32][chunk][tap][c16][half][lane][4]: lane (n = lane & 31, g = lane >> 5)
 // holds channels 16*c16 + 8*half + 4*g + {0..3} of output channel n (one v_mfma_f32_32x32x2_f32 step per element)
-static int pack_w32(hificar_handle* h, const ConvLayer& L, const HostTensor& W, int chunk, float** out) {
+static int pack_w32(hificar_engine* h, const ConvLayer& L, const HostTensor& W, int chunk, float** out) {
     const int nc16 = chunk / 16, nchunk = L.cin_pad / chunk;
     const size_t frag = 64 * 4;  // floats per fragment
     std::vector<float> w32(((size_t)L.n_blocks32 * nchunk * L.ntaps * nc16 * 2 + 4 * nc16) * frag, 0.f);
@@ -643,14 +632,11 @@ static int pack_w32(hificar_handle* h, const ConvLayer& L, const HostTensor& W, 
     return upload(h, w32, out);
 }
 
-static int pack_conv(hificar_handle* h, ConvLayer& L) {
-    const HostTensor& W = h->tensors.at(L.name + ".weight");
+// W: the layer's folded weight; Bv: its bias (null: none, zeros are uploaded)
+static int pack_conv(hificar_engine* h, ConvLayer& L, const HostTensor& W, const HostTensor* Bv) {
     std::vector<float> bias((size_t)L.cout_total, 0.f);
-    if (L.has_bias) {
-        const HostTensor& Bv = h->tensors.at(L.name + ".bias");
-        for (int r = 0; r < L.n_phase; ++r)
-            for (int co = 0; co < L.cout; ++co) bias[(size_t)r * L.cout_pad + co] = Bv.data[co];
-    }
+    for (int r = 0; Bv && r < L.n_phase; ++r)
+        for (int co = 0; co < L.cout; ++co) bias[(size_t)r * L.cout_pad + co] = Bv->data[co];
     int rc = upload(h, bias, &L.d_bias);
     if (rc != HIFICAR_OK) return rc;
 
@@ -686,22 +672,42 @@ hipError_t hificar::conv_set_lds_attributes() {
     return e;
 }
 
-// Device-side state every launch needs, whatever network the handle holds (the generator, or the discriminators' engine handle):
-// the zero page of the LDS DMA, the kernels' dynamic-LDS attributes, the first schedule arena.
-static int engine_setup(hificar_handle* h) {
-    {
-        void* z = nullptr;
-        HIP_TRY(hipMalloc(&z, 256));
-        h->allocs.push_back(z);
-        HIP_TRY(hipMemset(z, 0, 256));
-        h->d_zeros = static_cast<char*>(z);
-    }
+// Opens an engine: the chip's size, the environment switches (read_env; its owner's overrides come after), and the device-side state every
+// launch needs — the zero page of the LDS DMA, the kernels' dynamic-LDS attributes, the first schedule arena.
+static int engine_open(hificar_engine* h, bool read_env) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+        h->num_cus = prop.multiProcessorCount;
+    if (read_env) read_env_switches(h);
+    void* z = nullptr;
+    HIP_TRY(hipMalloc(&z, 256));
+    h->allocs.push_back(z);
+    HIP_TRY(hipMemset(z, 0, 256));
+    h->d_zeros = static_cast<char*>(z);
     HIP_TRY(conv_set_lds_attributes());
-    if (h->arenas.empty()) {
-        int rca = arena_add(h, 0);
-        if (rca != HIFICAR_OK) return rca;
+    return h->arenas.empty() ? arena_add(h, 0) : HIFICAR_OK;
+}
+
+// Frees what the engine owns (opened or not: uploads may precede engine_open).
+static void engine_close(hificar_engine* h) {
+    for (void* p : h->allocs) (void)hipFree(p);
+    for (auto& a : h->arenas) {
+        (void)hipFree(a.d);
+        (void)hipHostFree(a.h);
     }
-    return HIFICAR_OK;
+    if (h->xstream_ev) (void)hipEventDestroy(h->xstream_ev);
+    if (h->done_ev) (void)hipEventDestroy(h->done_ev);
+    for (auto& r : h->rslots) {
+        if (r.d) (void)hipFree(r.d);
+        if (r.h) (void)hipHostFree(r.h);
+        if (r.ev) (void)hipEventDestroy(r.ev);
+        if (r.up) (void)hipEventDestroy(r.up);
+    }
+    for (auto& r : h->prof) {
+        (void)hipEventDestroy(r.e0);
+        (void)hipEventDestroy(r.e1);
+    }
 }
 
 extern "C" int hificar_finalize(hificar_handle* h) {
@@ -710,16 +716,17 @@ extern "C" int hificar_finalize(hificar_handle* h) {
     for (auto& kv : h->expected)
         if (!h->tensors.count(kv.first)) return fail(HIFICAR_E_STATE, "Missing key(s) in state_dict: \"%s\"", kv.first.c_str());
     int rc;
-    if ((rc = pack_conv(h, h->input_conv)) != HIFICAR_OK) return rc;
+    auto pack = [&](ConvLayer& L) { return pack_conv(h, L, h->tensors.at(L.name + ".weight"), L.has_bias ? &h->tensors.at(L.name + ".bias") : nullptr); };
+    if ((rc = pack(h->input_conv)) != HIFICAR_OK) return rc;
     for (auto& l : h->ups)
-        if ((rc = pack_conv(h, l)) != HIFICAR_OK) return rc;
+        if ((rc = pack(l)) != HIFICAR_OK) return rc;
     for (auto& l : h->convs1)
-        if ((rc = pack_conv(h, l)) != HIFICAR_OK) return rc;
+        if ((rc = pack(l)) != HIFICAR_OK) return rc;
     for (auto& l : h->convs2)
-        if ((rc = pack_conv(h, l)) != HIFICAR_OK) return rc;
+        if ((rc = pack(l)) != HIFICAR_OK) return rc;
     for (auto& g : h->gb)
         for (ConvLayer* l : {&g.c1a, &g.c1b, &g.res, &g.c2a, &g.c2b})
-            if ((rc = pack_conv(h, *l)) != HIFICAR_OK) return rc;
+            if ((rc = pack(*l)) != HIFICAR_OK) return rc;
     {   // output conv weight (1, C, K) -> [k][C]
         const HostTensor& W = h->tensors.at("output_conv.1.weight");
         const int C = (int)W.shape[1], K = (int)W.shape[2], Cp = round_up(C, 32);  // [k][padded channels]
@@ -750,7 +757,11 @@ extern "C" int hificar_finalize(hificar_handle* h) {
         if ((rc = upload(h, h->tensors.at("ph_fc.weight").data, &h->d_phfc_w)) != HIFICAR_OK) return rc;
         if ((rc = upload(h, h->tensors.at("ph_fc.bias").data, &h->d_phfc_b)) != HIFICAR_OK) return rc;
     }
-    if ((rc = engine_setup(h)) != HIFICAR_OK) return rc;
+    // the engine opens here, not in hificar_create / hificar_gblock_create: a handle can be created and described without a device
+    if ((rc = engine_open(h, true)) != HIFICAR_OK) return rc;
+    if (h->arch == 1) h->use_pair = false;  // (the fused conv1 -> conv2 kernel is the HiFi-GAN ResBlock's)
+    if (const char* e = getenv("HIFICAR_AR_DUAL_MIN")) h->ar_dual_min = atoi(e);
+    if (const char* e = getenv("HIFICAR_AR_DUAL_MAX")) h->ar_dual_max = atoi(e);
     HIP_TRY(hipDeviceSynchronize());
     h->tensors.clear();  // host copies no longer needed
     h->finalized = true;
@@ -937,8 +948,8 @@ static void fill_params(ConvParams& p, const ConvLayer& L, int rows, int TM, con
 static constexpr size_t kArenaBytes = 16u << 20;
 static constexpr size_t kMaxArenas = 8;
 
-static int arena_add(hificar_handle* h, size_t min_bytes) {
-    hificar_handle::Arena a;
+static int arena_add(hificar_engine* h, size_t min_bytes) {
+    hificar_engine::Arena a;
     a.cap = std::max(kArenaBytes, round_up_sz(min_bytes, 4096));
     void* p = nullptr;
     HIP_TRY(hipMalloc(&p, a.cap));
@@ -956,11 +967,11 @@ static int arena_add(hificar_handle* h, size_t min_bytes) {
 // Drops every launch plan together with the schedules they point to, and recycles the arenas: the one place either goes (a very
 // large number of distinct launch shapes; rare, off the hot path: hificar_forward buckets non-AR lengths so that shapes repeat).
 // Kernels in flight may still read old schedules, so the device is drained first.
-static int evict_plans(hificar_handle* h) {
+static int evict_plans(hificar_engine* h) {
     HIP_TRY(hipDeviceSynchronize());
     h->plans.clear();
     for (auto& a : h->arenas) a.used = 0;
-    std::sort(h->arenas.begin(), h->arenas.end(), [](const hificar_handle::Arena& x, const hificar_handle::Arena& y) { return x.cap < y.cap; });
+    std::sort(h->arenas.begin(), h->arenas.end(), [](const hificar_engine::Arena& x, const hificar_engine::Arena& y) { return x.cap < y.cap; });
     return HIFICAR_OK;
 }
 
@@ -1018,7 +1029,7 @@ static TileLists xcd_block_lists(int R, int Gc, int num_cus) {
 
 // The schedule `lists` of n tiles into the arenas (device block + the pinned host mirror it is filled in), uploaded asynchronously on the
 // launch stream: the launch that follows is ordered behind the copy, hificar_ar_loop's second stream behind sched_up_seq.
-static int upload_schedule(hificar_handle* h, const TileLists& lists, int n, hipStream_t stream, const int** d_start, const int** d_tiles) {
+static int upload_schedule(hificar_engine* h, const TileLists& lists, int n, hipStream_t stream, const int** d_start, const int** d_tiles) {
     const int G = (int)lists.size();
     const size_t n_start = round_up_sz((size_t)G + 1, 4);
     const size_t bytes = (n_start + (size_t)std::max(n, 1)) * sizeof(int), take = round_up_sz(bytes, 256);
@@ -1027,7 +1038,7 @@ static int upload_schedule(hificar_handle* h, const TileLists& lists, int n, hip
         if (rc != HIFICAR_OK) return rc;
         if (take > h->arenas.back().cap) return fail(HIFICAR_E_INVALID, "tile schedule of %zu bytes exceeds the arena", take);
     }
-    hificar_handle::Arena& a = h->arenas.back();
+    hificar_engine::Arena& a = h->arenas.back();
     int* start = reinterpret_cast<int*>(a.h + a.used);
     int* tiles = start + n_start;
     int pos = 0;
@@ -1046,7 +1057,7 @@ static int upload_schedule(hificar_handle* h, const TileLists& lists, int n, hip
 
 // Order this call's work behind the previous call's when the caller changed streams (shared handle state: schedules, step
 // table, workspace).  Same stream: nothing to do.
-static int enter_stream(hificar_handle* h, hipStream_t stream) {
+static int enter_stream(hificar_engine* h, hipStream_t stream) {
     if (h->have_last_stream && h->last_stream != stream) {
         if (h->done_valid && h->done_stream == h->last_stream) {  // the previous call marked its own end: wait for that, not for later work
             HIP_TRY(hipStreamWaitEvent(stream, h->done_ev, 0));
@@ -1100,8 +1111,8 @@ struct ConvRep {
 
 // Tile shape of a launch_conv launch: simulate the kernel's tile walk and take the shape with the smallest makespan.  A tile costs its
 // MFMA issue cycles (all four MFMA waves run in lock step: 3*MI MFMAs of 32 cycles per 16-channel K slab) plus a fixed per-tile and
-// per-item overhead.  Pure host arithmetic on the launch shape and the handle's fixed switches.
-static TileCfg pick_tile(const hificar_handle* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, int zrep) {
+// per-item overhead.  Pure host arithmetic on the launch shape and the engine's fixed switches.
+static TileCfg pick_tile(const hificar_engine* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, int zrep) {
     const ConvLayer& L0 = *layers[0];
     const bool f32 = h->precision == HIFICAR_PREC_F32;  // rows are plain fp32 LeakyReLU(x) instead of split rows
     int halo_all = 0;
@@ -1187,7 +1198,7 @@ static TileCfg pick_tile(const hificar_handle* h, const ConvLayer* const* layers
 }
 
 // Kernel name of a plan as ProfScope wants it: the instantiation (hificar_launch.h), + "|layer xN" for per-layer rows in the profile (tools/layer_profile.py)
-static std::string plan_name(const hificar_handle* h, const ConvShape& s, const ConvLayer& L0, int nbr) {
+static std::string plan_name(const hificar_engine* h, const ConvShape& s, const ConvLayer& L0, int nbr) {
     static const char* const family[] = {"conv_f32do_kernel", "conv_bf16x3_kernel", "conv_bf16x3nb_kernel", "conv_sk_f32_kernel", "conv_sk_bf16x3_kernel",
                                          "conv_pair_f32_kernel", "conv_pair_bf16x3_kernel"};
     char kname[96];
@@ -1197,7 +1208,7 @@ static std::string plan_name(const hificar_handle* h, const ConvShape& s, const 
     return kname;
 }
 
-static int build_conv_plan(hificar_handle* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, int zrep, hipStream_t stream, ConvPlan& pl) {
+static int build_conv_plan(hificar_engine* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, int zrep, hipStream_t stream, ConvPlan& pl) {
     const ConvLayer& L0 = *layers[0];
     const bool f32 = h->precision == HIFICAR_PREC_F32;
     MultiConvParams& mp = pl.conv;
@@ -1255,7 +1266,7 @@ struct PairIOB {
 // — a tile's serial MFMA chain is a quarter as long and four times as many workgroups have work, so the fused pair beats two dependent
 // launches there (measured batch 8: +2.7 % end to end).  Below ~8000 rows (batch 1: 2000) the split-K layer-by-layer launches, whose chains
 // are shorter still, stay ahead (measured batch 1: -3.6 % with the fused form), so those keep running layer by layer.
-static bool pair_small_tiles(const hificar_handle* h, int C, int k2, int nseq, int rows) {
+static bool pair_small_tiles(const hificar_engine* h, int C, int k2, int nseq, int rows) {
     // (HIFICAR_KSPLIT=0, the batch-invariant mode: no launch-size-dependent forms at small sizes)
     if (!h->pair_small || h->ksplit == 0 || C != 32 || h->precision != HIFICAR_PREC_F32 || nseq <= 0 || (long long)nseq * rows < 8000) return false;
     const int tmo = 4 * 4 * 32 - (k2 - 1);
@@ -1263,7 +1274,7 @@ static bool pair_small_tiles(const hificar_handle* h, int C, int k2, int nseq, i
 }
 
 // nseq / rows: the launch the pair would run in (0 / 0: only the static conditions)
-static bool pair_eligible(const hificar_handle* h, const ConvLayer& a, const ConvLayer& b, int nseq = 0, int rows = 0) {
+static bool pair_eligible(const hificar_engine* h, const ConvLayer& a, const ConvLayer& b, int nseq = 0, int rows = 0) {
     if (!(h->use_pair && a.d_w16c && b.d_w16c && a.d_w32c && b.d_w32c && a.cin == b.cin && a.ntaps >= 2 &&
           b.ntaps >= 2 && b.dilation == 1 && a.K == b.K))
         return false;
@@ -1287,7 +1298,7 @@ static bool pair_eligible(const hificar_handle* h, const ConvLayer& a, const Con
     return true;
 }
 
-static int build_pair_plan(hificar_handle* h, const ConvLayer* const* l1, const ConvLayer* const* l2, int nbr, int nseq, int rows, hipStream_t stream,
+static int build_pair_plan(hificar_engine* h, const ConvLayer* const* l1, const ConvLayer* const* l2, int nbr, int nseq, int rows, hipStream_t stream,
                            ConvPlan& pl) {
     const int C = l1[0]->cin;
     bool small = true;
@@ -1324,10 +1335,10 @@ static int build_pair_plan(hificar_handle* h, const ConvLayer* const* l1, const 
 // The plan of a launch of layers `a` (launch_pair: conv1 `a`, conv2 `b` of every branch), built on the first launch of that shape — only that
 // touches vectors, strings or the arenas — on the launch's stream: a new schedule is uploaded on the stream that first needs it (publish()
 // in hificar_ar_loop).  Null: failed, *rc says how.
-static const ConvPlan* get_plan(hificar_handle* h, const ConvLayer* const* a, const ConvLayer* const* b, int nbr, int nseq, int rows, int zrep,
+static const ConvPlan* get_plan(hificar_engine* h, const ConvLayer* const* a, const ConvLayer* const* b, int nbr, int nseq, int rows, int zrep,
                                 hipStream_t stream, int* rc) {
     *rc = HIFICAR_OK;
-    PlanKey k = {{}, nseq, rows, zrep, (h->precision == HIFICAR_PREC_F32 ? 1 : 0) | (h->train ? 2 : 0) | (h->shared_chip ? 4 : 0) | (b ? 8 : 0)};
+    PlanKey k = {{}, nseq, rows, zrep, (h->precision == HIFICAR_PREC_F32 ? 1 : 0) | (h->training ? 2 : 0) | (h->shared_chip ? 4 : 0) | (b ? 8 : 0)};
     for (int i = 0; i < nbr; ++i) k.layers[i] = a[i];
     for (int i = 0; b && i < nbr; ++i) k.layers[3 + i] = b[i];
     auto it = h->plans.find(k);
@@ -1342,7 +1353,7 @@ static const ConvPlan* get_plan(hificar_handle* h, const ConvLayer* const* a, co
     return &it->second;
 }
 
-static int launch_conv(hificar_handle* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, const ConvIO* io,
+static int launch_conv(hificar_engine* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, const ConvIO* io,
                               float slope_out, const Ragged& rg, hipStream_t stream, const ConvRep& zr = ConvRep()) {
     int rc;
     const ConvPlan* const pl = get_plan(h, layers, nullptr, nbr, nseq, rows, zr.n, stream, &rc);
@@ -1398,7 +1409,7 @@ static int launch_conv(hificar_handle* h, const ConvLayer* const* layers, int nb
     return HIFICAR_OK;
 }
 
-static int launch_pair(hificar_handle* h, const ConvLayer* const* l1, const ConvLayer* const* l2, int nbr, int nseq, int rows,
+static int launch_pair(hificar_engine* h, const ConvLayer* const* l1, const ConvLayer* const* l2, int nbr, int nseq, int rows,
                               const PairIOB* io, float slope, const Ragged& rg, hipStream_t stream) {
     int rc;
     const ConvPlan* const pl = get_plan(h, l1, l2, nbr, nseq, rows, 1, stream, &rc);
@@ -2214,7 +2225,9 @@ extern "C" int hificar_ar_step(hificar_handle* h, const float* c, int64_t c_bstr
 // ------------------------------------------------------------------------------------------------
 // per-kernel event timing
 // ------------------------------------------------------------------------------------------------
-extern "C" int hificar_profile_begin(hificar_handle* h) {
+extern "C" hificar_engine* hificar_engine_of(hificar_handle* h) { return h; }
+
+extern "C" int hificar_profile_begin(hificar_engine* h) {
     if (!h) return fail(HIFICAR_E_INVALID, "null handle");
     for (auto& r : h->prof) {
         (void)hipEventDestroy(r.e0);
@@ -2225,7 +2238,7 @@ extern "C" int hificar_profile_begin(hificar_handle* h) {
     return HIFICAR_OK;
 }
 
-extern "C" int hificar_profile_end(hificar_handle* h, hificar_kernel_stat* stats, int max_stats, int* n_stats) {
+extern "C" int hificar_profile_end(hificar_engine* h, hificar_kernel_stat* stats, int max_stats, int* n_stats) {
     if (!h || !n_stats) return fail(HIFICAR_E_INVALID, "null argument");
     h->profiling = false;
     if (!h->prof.empty()) HIP_TRY(hipStreamSynchronize(h->prof_stream));

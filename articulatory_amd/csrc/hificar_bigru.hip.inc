@@ -9,7 +9,7 @@
 
 struct hificar_bigru {
     hificar_bigru_config cfg;
-    hificar_handle* eng = nullptr;
+    hificar_engine eng;
     std::map<std::string, std::vector<int64_t>> expected;
     std::map<std::string, HostTensor> tensors;
     ConvLayer proj[2], fc1;
@@ -36,19 +36,6 @@ extern "C" int hificar_bigru_create(const hificar_bigru_config* cfg, hificar_big
     static_assert(HIFICAR_BIGRU_MAX_OUT == kBigruMaxOut, "head kernel's LDS table");
     hificar_bigru* g = new hificar_bigru();
     g->cfg = c;
-    g->eng = new hificar_handle();
-    hificar_handle* h = g->eng;
-    read_env_switches(h);
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            h->num_cus = prop.multiProcessorCount;
-    }
-    h->precision = HIFICAR_PREC_F32;
-    h->use_pair = false;
-    h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's result does not depend on what it is batched with, bit
-                    // for bit (the GEMMs are a few percent of a forward next to the sweeps, so the split-K form has nothing to win here)
     const int64_t H = c.hidden_size, C = c.in_channels, O = c.out_channels;
     g->cin_pad = round_up(c.in_channels, 32);
     for (int l = 1; l <= 2; ++l)
@@ -83,7 +70,6 @@ extern "C" int hificar_bigru_create(const hificar_bigru_config* cfg, hificar_big
         rc = plan_layer(F);
     }
     if (rc != HIFICAR_OK) {
-        hificar_destroy(g->eng);
         delete g;
         return rc;
     }
@@ -93,11 +79,11 @@ extern "C" int hificar_bigru_create(const hificar_bigru_config* cfg, hificar_big
 
 extern "C" void hificar_bigru_destroy(hificar_bigru* g) {
     if (!g) return;
-    hificar_destroy(g->eng);
+    engine_close(&g->eng);
     delete g;
 }
 
-extern "C" hificar_handle* hificar_bigru_engine(hificar_bigru* g) { return g ? g->eng : nullptr; }
+extern "C" hificar_engine* hificar_bigru_engine(hificar_bigru* g) { return g ? &g->eng : nullptr; }
 
 extern "C" int hificar_bigru_set_weight(hificar_bigru* g, const char* name, const float* data, const int64_t* shape, int ndim) {
     if (!g || !name || !data || !shape) return fail(HIFICAR_E_INVALID, "hificar_bigru_set_weight: null argument");
@@ -168,7 +154,7 @@ static int bigru_tile_height(const hificar_bigru* g, int B) {
         const int v = atoi(e);
         if (v == 1 || v == 2) return v;
     }
-    return 2 * B <= g->eng->num_cus ? 1 : 2;
+    return 2 * B <= g->eng.num_cus ? 1 : 2;
 }
 
 extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
@@ -176,7 +162,7 @@ extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
     if (g->finalized) return HIFICAR_OK;
     for (auto& kv : g->expected)
         if (!g->tensors.count(kv.first)) return fail(HIFICAR_E_STATE, "Missing key(s) in state_dict: \"%s\"", kv.first.c_str());
-    hificar_handle* h = g->eng;
+    hificar_engine* h = &g->eng;
     const int H = g->cfg.hidden_size, O = g->cfg.out_channels;
     int rc;
     for (int l = 0; l < 2; ++l) {
@@ -191,9 +177,7 @@ extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
             Bv.data.insert(Bv.data.end(), bi.data.begin(), bi.data.end());
         }
         Bv.shape = {6 * H};
-        h->tensors[P.name + ".weight"] = std::move(W);
-        h->tensors[P.name + ".bias"] = std::move(Bv);
-        if ((rc = pack_conv(h, P)) != HIFICAR_OK) return rc;
+        if ((rc = pack_conv(h, P, W, &Bv)) != HIFICAR_OK) return rc;
         float* whh = nullptr;
         if ((rc = upload(h, bigru_pack_whh(g->tensors.at(b + "weight_hh_l0"), g->tensors.at(b + "weight_hh_l0_reverse"), H), &whh)) != HIFICAR_OK) return rc;
         g->d_whh[l] = reinterpret_cast<float4*>(whh);
@@ -216,9 +200,7 @@ extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
             for (int k = 0; k < 2 * H; ++k) Wf.data[(size_t)o * 2 * H + k] = (float)((double)W.data[(size_t)o * 2 * H + k] * s);
             Bf.data[o] = (float)(((double)b1[o] - (double)mu[o]) * s + (double)bt[o]);
         }
-        h->tensors[g->fc1.name + ".weight"] = std::move(Wf);
-        h->tensors[g->fc1.name + ".bias"] = std::move(Bf);
-        if ((rc = pack_conv(h, g->fc1)) != HIFICAR_OK) return rc;
+        if ((rc = pack_conv(h, g->fc1, Wf, &Bf)) != HIFICAR_OK) return rc;
     }
     if ((rc = upload(h, g->tensors.at(bigru_fc2_name(g) + ".weight").data, &g->d_w2)) != HIFICAR_OK) return rc;
     if ((rc = upload(h, g->tensors.at(bigru_fc2_name(g) + ".bias").data, &g->d_b2)) != HIFICAR_OK) return rc;
@@ -231,11 +213,14 @@ extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
     HIP_TRY((bigru_rec_attr<192, 2>()));
     HIP_TRY((bigru_rec_attr<256, 1>()));
     HIP_TRY((bigru_rec_attr<256, 2>()));
-    if ((rc = engine_setup(h)) != HIFICAR_OK) return rc;
+    // the engine opens here, not in hificar_bigru_create: a handle can be created and described without a device
+    if ((rc = engine_open(h, true)) != HIFICAR_OK) return rc;
+    h->precision = HIFICAR_PREC_F32;
+    h->use_pair = false;
+    h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's result does not depend on what it is batched with, bit
+                    // for bit (the GEMMs are a few percent of a forward next to the sweeps, so the split-K form has nothing to win here)
     HIP_TRY(hipDeviceSynchronize());
-    h->tensors.clear();
     g->tensors.clear();
-    h->finalized = true;
     g->finalized = true;
     return HIFICAR_OK;
 }
@@ -277,7 +262,7 @@ extern "C" int hificar_bigru_forward(hificar_bigru* g, const float* x, const int
     if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
     const BigruWorkspace ws = bigru_plan_workspace(g, B, T, workspace);
     if (workspace_bytes < ws.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
-    hificar_handle* h = g->eng;
+    hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;

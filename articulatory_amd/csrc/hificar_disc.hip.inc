@@ -35,7 +35,7 @@ struct DiscSub {
 struct hificar_disc {
     hificar_disc_config cfg;
     bool col2im_vec4 = true;  // HIFICAR_COL2IM_VEC4=0: the scalar col2im_mask_kernel everywhere (A/B runs)
-    hificar_handle* eng = nullptr;
+    hificar_engine eng;
     std::vector<DiscSub> subs;
     // folded parameters in state_dict order; gradient buckets: one per sub-discriminator (its parameters are contiguous, raw and folded alike)
     RawParamSet raw;
@@ -175,8 +175,8 @@ static DiscPlan disc_plan(const hificar_disc* d, int B, int T) {
             tl.push_back(t);
             bl.push_back(b);
             // (every layer its own piece of the scratch: the sub-discriminator's reductions run as one launch at the end of its pass)
-            pe += (size_t)L.groups * (t.Lp ? wgrad_partial_elems(d->eng, L.g[0].P, g.nseq, g.L[l + 1]) : wgrad_partial_elems(d->eng, L.g[0].F, 1, (int)t.M));
-            ce += (size_t)L.groups * (t.Lp ? wgrad_colsum_elems(d->eng, L.g[0].P, g.nseq, g.L[l + 1]) : wgrad_colsum_elems(d->eng, L.g[0].F, 1, (int)t.M));
+            pe += (size_t)L.groups * (t.Lp ? wgrad_partial_elems(&d->eng, L.g[0].P, g.nseq, g.L[l + 1]) : wgrad_partial_elems(&d->eng, L.g[0].F, 1, (int)t.M));
+            ce += (size_t)L.groups * (t.Lp ? wgrad_colsum_elems(&d->eng, L.g[0].P, g.nseq, g.L[l + 1]) : wgrad_colsum_elems(&d->eng, L.g[0].F, 1, (int)t.M));
         }
         p.tape.push_back(tl);
         p.bwd.push_back(bl);
@@ -211,7 +211,7 @@ static int disc_add_layer(hificar_disc* d, DiscSub& s, const std::string& base, 
     L.Kg_pad = round_up(L.Kg, 32);
     L.Np = round_up(L.cout_g, 32);
     L.g.resize((size_t)groups);
-    hificar_handle* h = d->eng;
+    hificar_engine* h = &d->eng;
     for (int gi = 0; gi < groups; ++gi) {
         DiscGroup& G = L.g[(size_t)gi];
         G.co0 = gi * L.cout_g;
@@ -311,15 +311,8 @@ extern "C" int hificar_disc_create(const hificar_disc_config* cfg, hificar_disc*
         return fail(HIFICAR_E_INVALID, "discriminator: bad AvgPool1d parameters");
     hificar_disc* d = new hificar_disc();
     d->cfg = c;
-    d->eng = new hificar_handle();
-    hificar_handle* h = d->eng;
-    read_env_switches(h);
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            h->num_cus = prop.multiProcessorCount;
-    }
+    hificar_engine* h = &d->eng;
+    int rc = engine_open(h, true);
     h->precision = HIFICAR_PREC_F32;
     h->use_pair = false;
     // HIFICAR_DISC_STREAMS=0: every sub-discriminator on the caller's stream (launches do not overlap: per-launch counters, tools/collect_profiles.sh);
@@ -328,11 +321,9 @@ extern "C" int hificar_disc_create(const hificar_disc_config* cfg, hificar_disc*
     if (const char* e = getenv("HIFICAR_COL2IM_VEC4")) d->col2im_vec4 = atoi(e) != 0;
     h->pick_throughput = 64;
     h->mi1_penalty = 1.3;
-    int rc = engine_setup(h);
     if (rc == HIFICAR_OK) rc = wgrad_setup();
-    h->finalized = true;
     auto bail = [&](int code) {
-        hificar_destroy(d->eng);
+        engine_close(h);
         delete d;
         return code;
     };
@@ -379,11 +370,11 @@ extern "C" void hificar_disc_destroy(hificar_disc* d) {
     for (hipStream_t s : d->side) (void)hipStreamDestroy(s);
     for (hipEvent_t e : d->join_ev) (void)hipEventDestroy(e);
     if (d->fork_ev) (void)hipEventDestroy(d->fork_ev);
-    hificar_destroy(d->eng);
+    engine_close(&d->eng);
     delete d;
 }
 
-extern "C" hificar_handle* hificar_disc_engine(hificar_disc* d) { return d ? d->eng : nullptr; }
+extern "C" hificar_engine* hificar_disc_engine(hificar_disc* d) { return d ? &d->eng : nullptr; }
 extern "C" int hificar_disc_param_count(const hificar_disc* d) { return d ? (int)d->raw.slots.size() : -1; }
 
 extern "C" int hificar_disc_param_info(const hificar_disc* d, int i, char* name96, int64_t* shape4, int* ndim, int64_t* offset) {
@@ -464,14 +455,14 @@ static int disc_pack_jobs(const hificar_disc* d, std::vector<PackParams>& jobs) 
 // copy, every GEMM pack (forward + data gradient) refreshed from it.  Two launches.  Same contract as hificar_set_parameters_device.
 extern "C" int hificar_disc_set_parameters_device(hificar_disc* d, const char* const* names, const float* const* data, int n, void* stream_) {
     if (!d || !names || !data || n < 1) return fail(HIFICAR_E_INVALID, "hificar_disc_set_parameters_device: null argument");
-    return raw_set_parameters(d->eng, d->raw, "hificar_disc_set_parameters_device", names, data, n, static_cast<hipStream_t>(stream_),
+    return raw_set_parameters(&d->eng, d->raw, "hificar_disc_set_parameters_device", names, data, n, static_cast<hipStream_t>(stream_),
                               [d](std::vector<PackParams>& jobs) { return disc_pack_jobs(d, jobs); });
 }
 
 extern "C" int hificar_disc_weight_norm_backward(hificar_disc* d, const float* grads, float* raw_grads, void* stream_) {
     if (!d || !grads || !raw_grads) return fail(HIFICAR_E_INVALID, "hificar_disc_weight_norm_backward: null argument");
     if (!d->raw.have_params) return fail(HIFICAR_E_STATE, "hificar_disc_weight_norm_backward needs hificar_disc_set_parameters_device first");
-    return raw_weight_norm_backward(d->eng, d->raw, grads, raw_grads, -1, d->grad_scale, static_cast<hipStream_t>(stream_));
+    return raw_weight_norm_backward(&d->eng, d->raw, grads, raw_grads, -1, d->grad_scale, static_cast<hipStream_t>(stream_));
 }
 
 // Two switches for the criterion's backward (include/hificar.h): the second pass of a discriminator update adds its parameter gradients
@@ -517,7 +508,7 @@ extern "C" int hificar_disc_weight_norm_backward_bucket(hificar_disc* d, const f
     if (!d || !grads || !raw_grads) return fail(HIFICAR_E_INVALID, "hificar_disc_weight_norm_backward_bucket: null argument");
     if (!d->raw.have_params) return fail(HIFICAR_E_STATE, "hificar_disc_weight_norm_backward_bucket needs hificar_disc_set_parameters_device first");
     if (bucket < 0 || bucket >= d->raw.n_buckets) return fail(HIFICAR_E_INVALID, "bucket %d out of range", bucket);
-    return raw_weight_norm_backward(d->eng, d->raw, grads, raw_grads, bucket, d->grad_scale, static_cast<hipStream_t>(stream_));
+    return raw_weight_norm_backward(&d->eng, d->raw, grads, raw_grads, bucket, d->grad_scale, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" size_t hificar_disc_tape_bytes(const hificar_disc* d, int B, int T) {
@@ -580,7 +571,7 @@ extern "C" int hificar_disc_output_info(const hificar_disc* d, int B, int T, int
     return fail(HIFICAR_E_INVALID, "hificar_disc_output_info: index %d out of range", i);
 }
 
-static unsigned ew_blocks(const hificar_handle* h, long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 16LL * h->num_cus)); }
+static unsigned ew_blocks(const hificar_engine* h, long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 16LL * h->num_cus)); }
 
 // x (B, 1, T) -> every layer output of every sub-discriminator, kept in `tape` (hificar_disc_output_info locates them).
 extern "C" int hificar_disc_forward(hificar_disc* d, const float* x, int B, int T, void* tape_, size_t tape_bytes, void* stream_) {
@@ -593,7 +584,7 @@ extern "C" int hificar_disc_forward(hificar_disc* d, const float* x, int B, int 
     const DiscPlan p = disc_plan(d, B, T);
     if (tape_bytes < p.tape_floats * sizeof(float)) return fail(HIFICAR_E_WORKSPACE, "discriminator tape too small: %zu < %zu", tape_bytes, p.tape_floats * sizeof(float));
     if (reinterpret_cast<uintptr_t>(tape_) % 256) return fail(HIFICAR_E_INVALID, "discriminator tape must be 256-byte aligned");
-    hificar_handle* h = d->eng;
+    hificar_engine* h = &d->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
@@ -727,7 +718,7 @@ extern "C" int hificar_disc_backward(hificar_disc* d, const float* const* douts,
     if (tape_bytes < p.tape_floats * sizeof(float) || ws_bytes < p.ws_floats * sizeof(float))
         return fail(HIFICAR_E_WORKSPACE, "discriminator backward: tape / workspace too small");
     if (reinterpret_cast<uintptr_t>(ws_) % 256) return fail(HIFICAR_E_INVALID, "discriminator workspace must be 256-byte aligned");
-    hificar_handle* h = d->eng;
+    hificar_engine* h = &d->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
@@ -995,7 +986,7 @@ extern "C" size_t hificar_disc_dout_floats(const hificar_disc* d, int B, int T) 
 extern "C" int hificar_disc_loss(hificar_disc* d, const hificar_gan_loss_config* cfg, int mode, const void* tape_, const void* tape_ref_, int B, int T,
                                  float* values3, float* douts, void* stream_) {
     if (!d || !cfg || !tape_ || !values3 || !douts || mode < 0 || mode > 2) return fail(HIFICAR_E_INVALID, "hificar_disc_loss: bad argument");
-    hificar_handle* h = d->eng;
+    hificar_engine* h = &d->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;

@@ -68,14 +68,6 @@ extern "C" int hificar_gblock_create(const hificar_gblock_config* gc, hificar_ha
     g.use_spk_id = c.use_spk_id;
     g.num_spk = c.num_spk;
     g.spk_emb_size = c.spk_emb_size;
-    read_env_switches(h);
-    h->use_pair = false;  // (the fused conv1 -> conv2 kernel is the HiFi-GAN ResBlock's)
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            h->num_cus = prop.multiProcessorCount;
-    }
     h->precision = HIFICAR_PREC_F32;
     h->cf = c.in_channels - (c.use_ar ? c.ar_output : 0);
     if (h->cf < 1) {

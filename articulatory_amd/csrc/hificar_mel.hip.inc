@@ -4,12 +4,12 @@
 
 struct hificar_mel {
     hificar_mel_config cfg;
-    hificar_handle* eng = nullptr;
+    hificar_engine eng;
     ConvLayer Fdft, Ddft, Fmel, Dmel;
     int nf = 0, nfp = 0, mp = 0;
 };
 
-static int mel_make_layer(hificar_handle* h, ConvLayer& L, const char* name, int cin, int cin_pad, int cout, const std::vector<float>& w_ref /* (cout, cin) */,
+static int mel_make_layer(hificar_engine* h, ConvLayer& L, const char* name, int cin, int cin_pad, int cout, const std::vector<float>& w_ref /* (cout, cin) */,
                           bool transpose_src, int src_cin, int src_cout) {
     L = ConvLayer();
     L.name = name;
@@ -57,20 +57,12 @@ extern "C" int hificar_mel_create(const hificar_mel_config* cfg, const float* me
     if (c.log_base != 0 && c.log_base != 2 && c.log_base != 10) return fail(HIFICAR_E_INVALID, "log_base: %d is not supported.", c.log_base);
     hificar_mel* m = new hificar_mel();
     m->cfg = c;
-    m->eng = new hificar_handle();
-    hificar_handle* h = m->eng;
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            h->num_cus = prop.multiProcessorCount;
-    }
+    hificar_engine* h = &m->eng;
+    int rc = engine_open(h, false);  // (this engine has never read the environment switches: inherited behaviour, not a decision)
     h->precision = HIFICAR_PREC_F32;
     h->use_pair = false;
-    int rc = engine_setup(h);
-    h->finalized = true;
     auto bail = [&](int code) {
-        hificar_destroy(m->eng);
+        engine_close(h);
         delete m;
         return code;
     };
@@ -109,7 +101,7 @@ extern "C" int hificar_mel_create(const hificar_mel_config* cfg, const float* me
 
 extern "C" void hificar_mel_destroy(hificar_mel* m) {
     if (!m) return;
-    hificar_destroy(m->eng);
+    engine_close(&m->eng);
     delete m;
 }
 
@@ -162,7 +154,7 @@ extern "C" int hificar_mel_loss(hificar_mel* m, const float* y_hat, const float*
     const MelPlan p = mel_plan(m, B, T);
     if (ws_bytes < p.floats * sizeof(float)) return fail(HIFICAR_E_WORKSPACE, "mel loss workspace too small");
     if (reinterpret_cast<uintptr_t>(ws_) % 256) return fail(HIFICAR_E_INVALID, "mel loss workspace must be 256-byte aligned");
-    hificar_handle* h = m->eng;
+    hificar_engine* h = &m->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
@@ -276,7 +268,7 @@ extern "C" int hificar_stft_loss_forward(hificar_mel* m, const float* y_hat, con
     const MelPlan p = mel_plan(m, B, T);
     if (ws_bytes < p.floats * sizeof(float)) return fail(HIFICAR_E_WORKSPACE, "STFT loss workspace too small");
     if (reinterpret_cast<uintptr_t>(ws_) % 256) return fail(HIFICAR_E_INVALID, "STFT loss workspace must be 256-byte aligned");
-    hificar_handle* h = m->eng;
+    hificar_engine* h = &m->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
@@ -327,7 +319,7 @@ extern "C" int hificar_stft_loss_backward(hificar_mel* m, int B, int T, const fl
     if (c.mode != 1) return fail(HIFICAR_E_STATE, "hificar_stft_loss_backward needs a handle created with mode = 1");
     const MelPlan p = mel_plan(m, B, T);
     if (ws_bytes < p.floats * sizeof(float)) return fail(HIFICAR_E_WORKSPACE, "STFT loss workspace too small");
-    hificar_handle* h = m->eng;
+    hificar_engine* h = &m->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;

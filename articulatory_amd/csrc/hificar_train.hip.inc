@@ -89,7 +89,7 @@ static size_t pack_w32_elems(const ConvLayer& L, int chunk) {
     return ((size_t)L.n_blocks32 * nchunk * L.ntaps * nc16 * 2 + 4 * nc16) * 256;
 }
 
-static int make_dgrad_layer(hificar_handle* h, const ConvLayer& L, ConvLayer& D, int* jmin_out) {
+static int make_dgrad_layer(hificar_engine* h, const ConvLayer& L, ConvLayer& D, int* jmin_out) {
     D = ConvLayer();
     D.name = L.name + "#dgrad";
     D.transposed = false;
@@ -158,6 +158,7 @@ static int train_init(hificar_handle* h) {
         return fail(HIFICAR_E_INVALID, "use_ph training: ph_emb_size <= 256 (got %d)", h->cfg.ph_emb_size);
     TrainState* ts = new TrainState();
     h->train = ts;
+    h->training = true;
     h->train_free = train_free_impl;
     int rc;
     if ((rc = make_dgrad_layer(h, h->input_conv, ts->dg_input, nullptr)) != HIFICAR_OK) return rc;
@@ -354,7 +355,7 @@ extern "C" int hificar_set_weight_device(hificar_handle* h, const char* name, co
 }
 
 template <typename T>
-static int device_table(hificar_handle* h, const std::vector<T>& host, T** dev) {
+static int device_table(hificar_engine* h, const std::vector<T>& host, T** dev) {
     void* p = nullptr;
     HIP_TRY(hipMalloc(&p, std::max<size_t>(host.size(), 1) * sizeof(T)));
     h->allocs.push_back(p);
@@ -365,7 +366,7 @@ static int device_table(hificar_handle* h, const std::vector<T>& host, T** dev) 
 
 // First hand-over of a raw-parameter set: the master copy, the static pack table (`packs` appends every pack of the engine, its sources
 // inside r.d_folded), the job order (slots stably sorted by bucket) and the job tables with their pinned mirrors.
-static int raw_setup(hificar_handle* h, RawParamSet& r, const std::function<int(std::vector<PackParams>&)>& packs) {
+static int raw_setup(hificar_engine* h, RawParamSet& r, const std::function<int(std::vector<PackParams>&)>& packs) {
     void* p = nullptr;
     HIP_TRY(hipMalloc(&p, (size_t)r.total * sizeof(float)));
     h->allocs.push_back(p);
@@ -402,7 +403,7 @@ static int raw_setup(hificar_handle* h, RawParamSet& r, const std::function<int(
 // "<conv>.weight_g" + "<conv>.weight_v" for a weight-normed conv, "<conv>.weight" for a plain one, biases, Linear tensors.  The weight
 // norm is folded on the device into the master copy, every pack is refreshed from it.  The raw-gradient buffer of
 // raw_weight_norm_backward has one slot per entry, in this order, each rounded up to 4 floats.  `fn` names the entry point in messages.
-static int raw_set_parameters(hificar_handle* h, RawParamSet& r, const char* fn, const char* const* names, const float* const* data, int n,
+static int raw_set_parameters(hificar_engine* h, RawParamSet& r, const char* fn, const char* const* names, const float* const* data, int n,
                               hipStream_t stream, const std::function<int(std::vector<PackParams>&)>& packs) {
     int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
@@ -496,7 +497,7 @@ static int raw_set_parameters(hificar_handle* h, RawParamSet& r, const char* fn,
 // weight's shape; every slot rounded up to 4 floats).  One launch: every job (bucket < 0), or the jobs of one bucket — meant to be called
 // from the bucket callback on the stream it hands over (no cross-stream ordering is added).  grad_scale: a device scalar, or null.
 // The caller checks r.have_params and the bucket's range.
-static int raw_weight_norm_backward(hificar_handle* h, const RawParamSet& r, const float* grads, float* raw_grads, int bucket,
+static int raw_weight_norm_backward(hificar_engine* h, const RawParamSet& r, const float* grads, float* raw_grads, int bucket,
                                     const float* grad_scale, hipStream_t stream) {
     const bool all = bucket < 0;
     int rc;
@@ -655,7 +656,7 @@ struct DeferredReduce {
 static constexpr size_t kReduceSlotBytes = 128 * 1024;
 static constexpr size_t kReduceSlots = 48;
 
-static int flush_reduce(hificar_handle* h, DeferredReduce& dr, hipStream_t stream) {
+static int flush_reduce(hificar_engine* h, DeferredReduce& dr, hipStream_t stream) {
     if (dr.w.empty() && dr.b.empty()) {
         dr.poff = dr.coff = 0;
         return HIFICAR_OK;
@@ -693,12 +694,12 @@ static int flush_reduce(hificar_handle* h, DeferredReduce& dr, hipStream_t strea
         memcpy(&v, blob.data() + i, 8);
         hash = (hash ^ v) * 1099511628211ull;
     }
-    hificar_handle::ReduceSlot* slot = nullptr;
+    hificar_engine::ReduceSlot* slot = nullptr;
     for (auto& r : h->rslots)
         if (r.hash == hash && r.bytes == bytes && memcmp(r.h, blob.data(), bytes) == 0) slot = &r;
     if (!slot) {
         if (h->rslots.size() < kReduceSlots) {
-            hificar_handle::ReduceSlot r;
+            hificar_engine::ReduceSlot r;
             void* p = nullptr;
             HIP_TRY(hipMalloc(&p, kReduceSlotBytes));
             r.d = static_cast<char*>(p);
@@ -766,7 +767,7 @@ static int wgrad_chunk_rows(const ConvLayer& L, int rows) {
     return 64;
 }
 
-static int wgrad_split(const hificar_handle* h, const ConvLayer& L, int nseq, int rows) {
+static int wgrad_split(const hificar_engine* h, const ConvLayer& L, int nseq, int rows) {
     if (wgrad_gemm_form(L)) {
         const int aw = wgrad_gemm_wide(L) ? 8 : 4;  // 32-blocks along a per tile
         const long long tiles = (long long)((L.n_blocks32 + 3) / 4) * (((L.cin_pad + 31) / 32 + aw - 1) / aw);
@@ -804,14 +805,14 @@ static int wgrad_row_split(const ConvLayer& L) {
     return nblk >= 4 ? 1 : nblk >= 2 ? 2 : 4;
 }
 
-static size_t wgrad_partial_elems(const hificar_handle* h, const ConvLayer& L, int nseq, int rows) {
+static size_t wgrad_partial_elems(const hificar_engine* h, const ConvLayer& L, int nseq, int rows) {
     // (room for two layers at half the split each: launch_wgrad_n)
     const size_t s2 = 2 * (size_t)std::max(1, wgrad_split(h, L, nseq, rows) / 2);
     return std::max<size_t>(s2, (size_t)wgrad_split(h, L, nseq, rows)) * L.ntaps * ((size_t)L.n_blocks32 * 32) * ((size_t)((L.cin_pad + 31) / 32) * 32);
 }
 
 // bias partials of one layer: one row of padded channels per row split (room for two layers of a paired launch, as above)
-static size_t wgrad_colsum_elems(const hificar_handle* h, const ConvLayer& L, int nseq, int rows) {
+static size_t wgrad_colsum_elems(const hificar_engine* h, const ConvLayer& L, int nseq, int rows) {
     const size_t s2 = 2 * (size_t)std::max(1, wgrad_split(h, L, nseq, rows) / 2);
     return std::max<size_t>(s2, (size_t)wgrad_split(h, L, nseq, rows)) * (size_t)L.n_blocks32 * 32;
 }
@@ -959,7 +960,7 @@ struct WgradJob {
 
 // Weight (and bias) gradients of n = 1 or 2 layers over the same rows.  Two layers share one launch of each kernel when both take the
 // all-taps kernel with the same tap count (conv2 + conv1 of a ResBlock slot): half the row splits each.
-static int launch_wgrad_n(hificar_handle* h, const WgradJob* jobs, int n, int nseq, int rows, const BwdWs& bw, hipStream_t stream) {
+static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int nseq, int rows, const BwdWs& bw, hipStream_t stream) {
     if (n == 2 && !(wgrad_all_taps(*jobs[0].L) && wgrad_all_taps(*jobs[1].L) && jobs[0].L->ntaps == jobs[1].L->ntaps)) {
         int rc = launch_wgrad_n(h, jobs, 1, nseq, rows, bw, stream);
         return rc != HIFICAR_OK ? rc : launch_wgrad_n(h, jobs + 1, 1, nseq, rows, bw, stream);
@@ -1178,7 +1179,7 @@ static int launch_wgrad_n(hificar_handle* h, const WgradJob* jobs, int n, int ns
     return HIFICAR_OK;
 }
 
-static int launch_wgrad(hificar_handle* h, const ConvLayer& L, const float* g, int gpitch, const float* a, int apitch, int nseq, int rows,
+static int launch_wgrad(hificar_engine* h, const ConvLayer& L, const float* g, int gpitch, const float* a, int apitch, int nseq, int rows,
                         float* dW, const BwdWs& bw, hipStream_t stream, float* db = nullptr) {
     const WgradJob job = {&L, g, gpitch, a, apitch, dW, db};
     return launch_wgrad_n(h, &job, 1, nseq, rows, bw, stream);

@@ -205,7 +205,8 @@ class BiGRU(torch.nn.Module):
 
     def engine(self):
         """The engine handle for ``hificar_profile_begin`` / ``hificar_profile_end`` (per-kernel device times; tools/bigru_bench.py)."""
-        return ctypes.c_void_p(self._lib.hificar_bigru_engine(self._native_handle()))
+        handle = self._native_handle()  # first: it is what loads self._lib
+        return ctypes.c_void_p(self._lib.hificar_bigru_engine(handle))
 
     # ------------------------------------------------------------------ forward
     def forward(self, mels, mask=None, spk_id=None, spk=None, ar=None, ph=None, lengths=None):

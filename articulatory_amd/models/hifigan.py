@@ -465,13 +465,13 @@ class _NativeGenerator(torch.nn.Module):
     def profile_begin(self):
         """Start bracketing every kernel launch with HIP events (bench.py roofline leg)."""
         self._native_handle()
-        _native.check(self._lib.hificar_profile_begin(self._handle), "hificar_profile_begin")
+        _native.check(self._lib.hificar_profile_begin(self._lib.hificar_engine_of(self._handle)), "hificar_profile_begin")
 
     def profile_end(self):
         """Stop profiling; returns [{name, launches, total_ms, flops, bytes}], slowest kernel first."""
         stats = (_native.HificarKernelStat * 96)()
         n = ctypes.c_int(0)
-        _native.check(self._lib.hificar_profile_end(self._handle, stats, 96, ctypes.byref(n)), "hificar_profile_end")
+        _native.check(self._lib.hificar_profile_end(self._lib.hificar_engine_of(self._handle), stats, 96, ctypes.byref(n)), "hificar_profile_end")
         return [dict(name=stats[i].name.decode(), launches=int(stats[i].launches), total_ms=float(stats[i].total_ms),
                      flops=float(stats[i].flops), bytes=float(stats[i].bytes)) for i in range(min(n.value, 96))]
 

@@ -71,6 +71,10 @@ extern "C" {
 #define HIFICAR_PREC_BF16X3 1      /* fp32 operands split hi+lo bf16, 3 bf16 MFMAs, fp32 accumulate */
 
 typedef struct hificar_handle hificar_handle;
+/* The conv engine every model of the library launches through (plans, schedules, stream ordering, profiling).  A generator handle
+ * has one (hificar_engine_of), so do the discriminators (hificar_disc_engine) and the BiGRU (hificar_bigru_engine); it lives and
+ * dies with its model.  Only the profiling calls take it: the generator's entry points do not accept another model's engine. */
+typedef struct hificar_engine hificar_engine;
 
 /* Mirrors the keyword arguments of HiFiGANGenerator.__init__ (hifigan.py:24-50) that affect
  * inference.  in_channels keeps the reference's meaning: feature dims + ar_output when use_ar. */
@@ -266,7 +270,7 @@ double hificar_macs(const hificar_handle* h, int B, int T);
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's roofline leg; no reference
  * counterpart — the reference times whole utterances with time.time(), articulatory/bin/decode.py:302-318).
- * Between hificar_profile_begin and hificar_profile_end every kernel launch of this handle is bracketed
+ * Between hificar_profile_begin and hificar_profile_end every kernel launch of this engine's model is bracketed
  * by two hipEvents.  hificar_profile_end synchronises the stream used, then fills up to `max_stats`
  * entries (one per distinct kernel) and writes the number of distinct kernels to *n_stats. */
 typedef struct hificar_kernel_stat {
@@ -276,8 +280,9 @@ typedef struct hificar_kernel_stat {
     double flops;      /* algorithmic FLOPs (2 x MACs) of those launches */
     double bytes;      /* algorithmic bytes (inputs + outputs + weights read once) of those launches */
 } hificar_kernel_stat;
-int hificar_profile_begin(hificar_handle* h);
-int hificar_profile_end(hificar_handle* h, hificar_kernel_stat* stats, int max_stats, int* n_stats);
+hificar_engine* hificar_engine_of(hificar_handle* h); /* the generator's own engine (NULL for NULL) */
+int hificar_profile_begin(hificar_engine* e);
+int hificar_profile_end(hificar_engine* e, hificar_kernel_stat* stats, int max_stats, int* n_stats);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Training: the generator half of the reference's train step (articulatory/bin/train.py:241-440: y_ = generator(x, ar=ar) under
@@ -393,7 +398,7 @@ const char* hificar_version(void);
  *                                        parameters, hificar_disc_grad_floats, offsets from hificar_disc_param_info) or NULL,
  *                                        dx (B, T) or NULL
  *   hificar_disc_weight_norm_backward    folded gradients -> raw parameter gradients (as hificar_weight_norm_backward)
- *   hificar_disc_engine                  the engine handle, for hificar_profile_begin / hificar_profile_end
+ *   hificar_disc_engine                  the discriminators' engine, for hificar_profile_begin / hificar_profile_end
  * --------------------------------------------------------------------------------------------------------------------------- */
 #define HIFICAR_DISC_MAX_SUBS 8
 #define HIFICAR_DISC_MAX_LAYERS 12
@@ -441,7 +446,7 @@ int hificar_disc_backward_flat(hificar_disc* d, const float* douts, int mode, in
                                void* stream);
 int hificar_disc_create(const hificar_disc_config* cfg, hificar_disc** out);
 void hificar_disc_destroy(hificar_disc* d);
-hificar_handle* hificar_disc_engine(hificar_disc* d);
+hificar_engine* hificar_disc_engine(hificar_disc* d);
 int hificar_disc_param_count(const hificar_disc* d);
 int hificar_disc_param_info(const hificar_disc* d, int i, char* name96, int64_t* shape4, int* ndim, int64_t* offset);
 int64_t hificar_disc_grad_floats(const hificar_disc* d);
@@ -543,8 +548,8 @@ size_t hificar_bigru_workspace_bytes(const hificar_bigru* h, int B, int T);
 int hificar_bigru_forward(hificar_bigru* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int T,
                           void* workspace, size_t workspace_bytes, void* stream);
 
-/* The engine handle, for hificar_profile_begin / hificar_profile_end (the reference times whole utterances, decode.py:302-318). */
-hificar_handle* hificar_bigru_engine(hificar_bigru* h);
+/* The model's engine, for hificar_profile_begin / hificar_profile_end (the reference times whole utterances, decode.py:302-318). */
+hificar_engine* hificar_bigru_engine(hificar_bigru* h);
 
 /* del model */
 void hificar_bigru_destroy(hificar_bigru* h);

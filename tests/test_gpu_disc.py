@@ -433,3 +433,50 @@ def test_single_scale_and_period_discriminator_classes(which):
     assert len(outs) == len(ref)
     for t, tr in zip(outs, ref):
         assert tuple(t.shape) == tuple(tr.shape) and float((t.detach().cpu() - tr).abs().max()) < 2e-5 * float(tr.abs().max())
+
+
+@pytest.mark.parametrize("kind", ["generator", "discriminator", "bigru"])
+def test_profiling_through_an_engine_of_every_kind(kind):
+    """hificar_profile_begin / hificar_profile_end take the conv engine of any model: the generator's own (hificar_engine_of), the
+    discriminators' and the BiGRU's.  One forward at B = 1 and the shortest length each model's tests use: every launch is a row with a
+    count and a device time, and the shared conv kernels are among them."""
+    import ctypes
+
+    from conftest import E2W_PARAMS
+    from articulatory_amd import _native
+    from articulatory_amd.models import BiGRU, HiFiGANGenerator
+    from articulatory_amd.utils.synth import synth_bigru_state_dict, synth_features, synth_state_dict
+
+    assert torch.cuda.is_available()
+    with torch.no_grad():
+        if kind == "generator":
+            m = HiFiGANGenerator(**E2W_PARAMS)
+            m.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(dict(E2W_PARAMS), seed=1234).items()})
+            m.remove_weight_norm()
+            m = m.eval().to("cuda:0")
+            c = torch.from_numpy(synth_features(1, 10, 13, seed=5)).permute(0, 2, 1).contiguous().cuda()
+            m.profile_begin()
+            m(c, ar=torch.zeros(1, 1, 512, device="cuda:0"))
+            rows = m.profile_end()
+        elif kind == "discriminator":
+            m, _ = build(case_params("small"), 77)
+            m.profile_begin()
+            m(torch.from_numpy(uniform(5, "fake", (1, 1, 700), -0.5, 0.5)).cuda())
+            torch.cuda.synchronize()  # (the sub-discriminators run on side streams; profile_end waits for the last one used only)
+            rows = m.profile_end()
+        else:
+            params = dict(in_channels=80, hidden_size=64, out_channels=12, use_tanh=False)
+            m = BiGRU(**params)
+            m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synth_bigru_state_dict(params, seed=3).items()}, strict=True)
+            m = m.eval().to("cuda:0")
+            x = torch.from_numpy(uniform(3, "x", (1, 80, 1), -1.0, 1.0)).cuda()
+            lib, eng = _native.load_library(), m.engine()
+            _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
+            m(x)
+            stats, n = (_native.HificarKernelStat * 32)(), ctypes.c_int()
+            _native.check(lib.hificar_profile_end(eng, stats, 32, ctypes.byref(n)), "hificar_profile_end")
+            rows = [dict(name=stats[i].name.decode(), launches=int(stats[i].launches), total_ms=float(stats[i].total_ms)) for i in range(n.value)]
+    print(kind, [(r["name"], r["launches"], round(r["total_ms"], 4)) for r in rows])
+    assert len(rows) >= 1
+    assert all(r["launches"] >= 1 and r["total_ms"] > 0 for r in rows), rows
+    assert any(r["name"].startswith("conv_") for r in rows), rows

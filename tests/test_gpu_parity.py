@@ -488,7 +488,7 @@ def test_fused_pair_kernel_matches_layer_by_layer(monkeypatch, prec):
     outs, ragged = {}, {}
     kernel = "conv_pair_f32_kernel" if prec == "f32" else "conv_pair_bf16x3_kernel"
     for flag in ("1", "0"):
-        monkeypatch.setenv("HIFICAR_PAIR", flag)  # read by hificar_create
+        monkeypatch.setenv("HIFICAR_PAIR", flag)  # read when the native handle is built (hificar_finalize)
         g, w = make(params, prec)
         with torch.no_grad():
             outs[flag] = g(c, ar=ar).cpu()
@@ -524,7 +524,7 @@ def test_small_tile_fused_pair_at_mid_size_launches(monkeypatch):
     lens = [T, 9, 1, 0, 25, 13, 24, 2]
     outs, ragged = {}, {}
     for flag in ("1", "0"):
-        monkeypatch.setenv("HIFICAR_PAIR_SMALL", flag)  # read by hificar_create
+        monkeypatch.setenv("HIFICAR_PAIR_SMALL", flag)  # read when the native handle is built (hificar_finalize)
         g, w = make(params, "f32")
         with torch.no_grad():
             outs[flag] = g(c, ar=ar).cpu()
