@@ -226,6 +226,8 @@ class Trainer:
     def __init__(self, config, device, distributed=False):
         self.config, self.device, self.distributed = config, device, distributed
         gtype_name = config.get("generator_type", "HiFiGANGenerator")
+        if gtype_name == "BiGRU":
+            raise NotImplementedError("generator_type BiGRU trains with InversionTrainer (dataset_mode art / a2m / m2a), not with the GAN Trainer")
         if gtype_name not in ("HiFiGANGenerator", "GBlockGenerator"):
             raise NotImplementedError(f"generator_type {gtype_name} is not built")
         import articulatory_amd.models as models
@@ -500,6 +502,185 @@ class Trainer:
                 self.scheduler[k].load_state_dict(state["scheduler"][k])
 
 
+INVERSION_MODES = ("art", "a2m", "m2a")  # the reference's dataset modes whose criterion is F.l1_loss on feature frames (train.py:1706-1709)
+
+
+class WindowPairs(torch.utils.data.Dataset):
+    """(input frames (T, Cin), target frames (T, Cout)) pairs for an inversion model: two aligned ``.npy`` scp files, or ``n`` synthetic
+    utterances.  ``swap`` (dataset_mode m2a) exchanges the two sides, as CollaterMelArt does (train.py:855-859)."""
+
+    def __init__(self, x_scp=None, y_scp=None, min_frames=1, swap=False, synthetic=0, frames=0, dims=(1, 1), seed=0):
+        if synthetic:
+            rng = np.random.default_rng(seed)
+            self.items = [(rng.standard_normal((frames, dims[0])).astype(np.float32), np.tanh(rng.standard_normal((frames, dims[1]))).astype(np.float32))
+                          for _ in range(synthetic)]
+            return
+
+        def read(p):
+            with open(p) as f:
+                return dict(line.split(None, 1) for line in f.read().splitlines() if line.strip())
+
+        xs, ys = read(x_scp), read(y_scp)
+        self.items = []
+        for utt in sorted(set(xs) & set(ys)):
+            a, b = np.load(xs[utt].strip()).astype(np.float32), np.load(ys[utt].strip()).astype(np.float32)
+            n = min(len(a), len(b))
+            if n > min_frames:
+                self.items.append((b[:n], a[:n]) if swap else (a[:n], b[:n]))
+
+    def __len__(self):
+        return len(self.items)
+
+    def __getitem__(self, i):
+        return self.items[i]
+
+
+class FrameWindowCollater:
+    """CollaterMelArt (train.py:780-862): equal windows of batch_max_frames + 2 aux_context_window frames cut at one random start per
+    utterance from both sides -> {"x": (B, Cin, T), "y": (B, Cout, T)}."""
+
+    def __init__(self, batch_max_frames, aux_context_window=0, seed=None):
+        self.frames, self.ctx = batch_max_frames, aux_context_window
+        self.rng = np.random.default_rng(seed)
+
+    def __call__(self, items):
+        n = self.frames + 2 * self.ctx
+        xs, ys = [], []
+        for a, b in items:
+            start = int(self.rng.integers(0, len(a) - n + 1))
+            xs.append(a[start:start + n])
+            ys.append(b[start:start + n])
+        return {"x": torch.from_numpy(np.stack(xs)).transpose(2, 1).contiguous(), "y": torch.from_numpy(np.stack(ys)).transpose(2, 1).contiguous()}
+
+
+class InversionTrainer:
+    """The reference's training step for ``generator_type: BiGRU`` (dataset_mode art / a2m / m2a): the generator half of ``_train_step``
+    (train.py:268-383) with ``criterion["mel"] = F.l1_loss`` — forward in train() mode, L1 * lambda_aux, zero_grad, backward, gradient
+    clipping, optimizer step, scheduler step.  No discriminator: the reference would start an adversarial phase on the trajectories at
+    discriminator_train_start_steps, which is not built, so a config that reaches it is refused."""
+
+    def __init__(self, config, device):
+        self.config, self.device = config, device
+        gtype = config.get("generator_type", "HiFiGANGenerator")
+        if gtype != "BiGRU":
+            raise NotImplementedError(f"InversionTrainer trains generator_type BiGRU (got {gtype})")
+        mode = config.get("dataset_mode", "default")
+        if mode not in INVERSION_MODES:
+            raise NotImplementedError(f"generator_type BiGRU trains with dataset_mode in {' / '.join(INVERSION_MODES)} (got {mode!r})")
+        if "train_max_steps" not in config:
+            raise ValueError("the config has no train_max_steps")
+        if config.get("discriminator_train_start_steps", 0) < config["train_max_steps"]:
+            raise NotImplementedError(
+                f"discriminator_train_start_steps = {config.get('discriminator_train_start_steps', 0)} is below train_max_steps = "
+                f"{config['train_max_steps']}: the adversarial phase of an inversion model is not built (set discriminator_train_start_steps "
+                "to train_max_steps or more)")
+        for flag in ("use_stft_loss", "use_subband_stft_loss", "use_inter_loss", "use_ph_loss", "use_pcd"):
+            if config.get(flag, False):
+                raise NotImplementedError(f"{flag} is not built for inversion models (their criterion is F.l1_loss, config key use_mel_loss)")
+        import articulatory_amd.models as models
+
+        self.G = models.BiGRU(**config["generator_params"]).to(device).train()
+        self.optimizer = {"generator": _optimizer(config.get("generator_optimizer_type", "Adam"), self.G.parameters(),
+                                                  config["generator_optimizer_params"], config.get("fused_optimizers", True))}
+        self.scheduler = {"generator": getattr(torch.optim.lr_scheduler, config.get("generator_scheduler_type", "StepLR"))(
+            optimizer=self.optimizer["generator"], **config["generator_scheduler_params"])}
+        self.steps = self.epochs = 0
+        self.total_train_loss = defaultdict(float)
+
+    def train_step(self, batch):
+        cfg = self.config
+        x = batch["x"].to(self.device, non_blocking=True)
+        y = batch["y"].to(self.device, non_blocking=True)
+        log = {}
+        if self.steps > cfg.get("generator_train_start_steps", 0):  # train.py:268
+            y_ = self.G(x)
+            mel_loss = torch.nn.functional.l1_loss(y_, y)  # criterion["mel"] = F.l1_loss (train.py:1706-1709)
+            gen_loss = mel_loss * cfg.get("lambda_aux", 1.0)
+            log["train/mel_loss"] = mel_loss.detach()
+            log["train/generator_loss"] = gen_loss.detach()
+            self.optimizer["generator"].zero_grad(set_to_none=True)
+            gen_loss.backward()
+            if cfg.get("generator_grad_norm", -1) > 0:
+                torch.nn.utils.clip_grad_norm_(self.G.parameters(), cfg["generator_grad_norm"])
+            self.optimizer["generator"].step()
+            if cfg.get("generator_scheduler_type", "StepLR") == "ReduceLROnPlateau":
+                self.scheduler["generator"].step(gen_loss.detach())
+            else:
+                self.scheduler["generator"].step()
+        self.steps += 1
+        return log
+
+    # ------------------------------------------------------------------ checkpoints (train.py:140-238: the reference's dict layout)
+    def save_checkpoint(self, path):
+        state = {
+            "optimizer": {"generator": self.optimizer["generator"].state_dict()},
+            "scheduler": {"generator": self.scheduler["generator"].state_dict()},
+            "steps": self.steps,
+            "epochs": self.epochs,
+            "model": {"generator": self.G.state_dict()},
+            # this package's addition: where the dropout generator stands, so that a resumed run draws the masks the unbroken one would
+            "dropout": {"seed": self.G._dropout_seed, "calls": self.G._calls},
+        }
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        torch.save(state, path)
+
+    def load_checkpoint(self, path, load_only_params=False):
+        state = torch.load(path, map_location="cpu")
+        self.G.load_state_dict(state["model"]["generator"])
+        if not load_only_params:
+            self.steps, self.epochs = state["steps"], state["epochs"]
+            self.optimizer["generator"].load_state_dict(state["optimizer"]["generator"])
+            self.scheduler["generator"].load_state_dict(state["scheduler"]["generator"])
+            if "dropout" in state:
+                self.G.set_dropout_seed(state["dropout"]["seed"], state["dropout"]["calls"])
+
+
+def _main_inversion(a, config, device, rank):
+    """``main`` for generator_type BiGRU: input / target ``.npy`` scp pairs (--feats-scp: the model's input side, --audio-scp: its target
+    side; dataset_mode m2a swaps them) or --synthetic N, cut into equal windows of batch_max_frames + 2 aux_context_window frames."""
+    gp = config["generator_params"]
+    hop = int(config.get("hop_size", 1))
+    ctx = int(config.get("aux_context_window", gp.get("aux_context_window", 0)))
+    frames = config["batch_max_steps"] // hop  # CollaterMelArt: batch_max_frames
+    window = frames + 2 * ctx
+    if a.synthetic:
+        data = WindowPairs(synthetic=a.synthetic, frames=4 * window, dims=(gp.get("in_channels", 80), gp.get("out_channels", 1)), seed=rank)
+    else:
+        if not (a.audio_scp and a.feats_scp):
+            raise SystemExit("generator_type BiGRU: give --feats-scp (input frames) and --audio-scp (target frames) of .npy files, or --synthetic N")
+        data = WindowPairs(a.feats_scp, a.audio_scp, min_frames=window, swap=config.get("dataset_mode") == "m2a")
+    loader = torch.utils.data.DataLoader(data, batch_size=config["batch_size"], shuffle=True, drop_last=True,
+                                         collate_fn=FrameWindowCollater(frames, ctx, seed=1234 + rank), num_workers=config.get("num_workers", 0))
+    if len(loader) == 0:
+        raise SystemExit(f"fewer utterances ({len(data)}) than one batch ({config['batch_size']})")
+    if a.max_steps is not None:  # the refusal of a reachable adversarial phase looks at the steps this run will take
+        config = dict(config, train_max_steps=a.max_steps)
+    trainer = InversionTrainer(config, device)
+    if a.resume:
+        trainer.load_checkpoint(a.resume)
+        logging.info(f"Successfully resumed from {a.resume}.")
+    max_steps = config["train_max_steps"]
+    t0, n0, pending = time.time(), trainer.steps, []
+    while trainer.steps < max_steps:
+        for batch in loader:
+            pending.append(trainer.train_step(batch))
+            n = config.get("log_interval_steps", 100)
+            if trainer.steps % n == 0 or trainer.steps >= max_steps:
+                for log in pending:
+                    for k, v in log.items():
+                        trainer.total_train_loss[k] += float(v)
+                logging.info(f"(Steps: {trainer.steps}) " + ", ".join(f"{k} = {v / max(len(pending), 1):.4f}" for k, v in sorted(trainer.total_train_loss.items()))
+                             + f", {(time.time() - t0) / max(trainer.steps - n0, 1) * 1e3:.1f} ms/step")
+                pending, trainer.total_train_loss = [], defaultdict(float)
+            if trainer.steps % config.get("save_interval_steps", 10 ** 9) == 0:
+                trainer.save_checkpoint(os.path.join(a.outdir, f"checkpoint-{trainer.steps}steps.pkl"))
+            if trainer.steps >= max_steps:
+                break
+        trainer.epochs += 1
+    trainer.save_checkpoint(os.path.join(a.outdir, f"checkpoint-{trainer.steps}steps.pkl"))
+    logging.info(f"Finished training: {trainer.steps} steps, {(time.time() - t0) / max(trainer.steps - n0, 1) * 1e3:.1f} ms/step.")
+
+
 def hop_of(config):
     return int(np.prod(config["generator_params"]["upsample_scales"]))
 
@@ -547,6 +728,10 @@ def main(argv=None):
             raise SystemExit(f"WORLD_SIZE={world} but the process group has {torch.distributed.get_world_size()} ranks")
         logging.info(f"rank {rank}/{world}: {pinned or 'host affinity unchanged'}")
     config["distributed"] = world > 1
+    if config.get("generator_type", "HiFiGANGenerator") == "BiGRU":
+        if world > 1:
+            raise SystemExit("generator_type BiGRU trains on one GPU (multi-GPU training of the inversion model is not built)")
+        return _main_inversion(a, config, device, rank)
     hop = hop_of(config)
     frames = config["batch_max_steps"] // hop
     gp = config["generator_params"]

@@ -7,17 +7,20 @@
 #include "hificar_backward.hip.h"
 #include "hificar_disc_kernels.hip.h"
 #include "hificar_bigru_kernels.hip.h"
+#include "hificar_bigru_train_kernels.hip.h"
 
 #include "../../include/hificar.h"
 
 #include <algorithm>
 #include <queue>
+#include <set>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -2283,3 +2286,4 @@ extern "C" int hificar_pcm16(const float* x, int16_t* y, size_t n, void* stream)
 #include "hificar_disc.hip.inc"
 #include "hificar_mel.hip.inc"
 #include "hificar_bigru.hip.inc"
+#include "hificar_bigru_train.hip.inc"

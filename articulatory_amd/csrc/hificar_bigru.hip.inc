@@ -7,6 +7,8 @@
 // Workspace: one pre-gate buffer [B T][6H] shared by the two layers (and by fc1's output), one row buffer [B T][max(Cin, 2H)] shared by
 // the input rows and the two layers' hidden states.  Exact fp32.
 
+struct BigruTrain;  // training state (hificar_bigru_train.hip.inc): made by the first training entry point
+
 struct hificar_bigru {
     hificar_bigru_config cfg;
     hificar_engine eng;
@@ -19,7 +21,11 @@ struct hificar_bigru {
     float* d_b2 = nullptr;
     int cin_pad = 0;
     bool finalized = false;
+    BigruTrain* train = nullptr;
+    int train_failed = HIFICAR_OK;  // the error of a failed set-up of the training state: it is not tried again on this handle
 };
+
+static void bigru_train_free(hificar_bigru* g);
 
 static std::string bigru_fc2_name(const hificar_bigru* g) { return g->cfg.use_tanh ? "fc2.0" : "fc2"; }
 
@@ -79,6 +85,7 @@ extern "C" int hificar_bigru_create(const hificar_bigru_config* cfg, hificar_big
 
 extern "C" void hificar_bigru_destroy(hificar_bigru* g) {
     if (!g) return;
+    bigru_train_free(g);
     engine_close(&g->eng);
     delete g;
 }

@@ -33,6 +33,7 @@ struct BigruRecParams {
     const int* lengths;   // B frame counts on the device, or null: all T
     float* y;             // [B * T][2H]: forward | reverse hidden states; rows at or past a sequence's length are not written
     int B, T;
+    float* tape = nullptr;  // TAPE instantiations (training): [B * T][2][4H], r | z | n | W_hn h + b_hn of every (frame, direction)
 };
 
 __device__ __forceinline__ void bigru_fma4(bigru_f2& acc, const float4& w, const float4& h) {
@@ -45,8 +46,9 @@ __device__ __forceinline__ float bigru_sigmoid(float x) { return 1.f / (1.f + ex
 // One workgroup sweeps NS sequences of one direction from their first step to their last; nothing is shared between workgroups.  PyTorch's
 // GRU cell (gate order r, z, n; h0 = 0):  r = s(gx_r + W_hr h + b_hr), z = s(gx_z + W_hz h + b_hz), n = tanh(gx_n + r (W_hn h + b_hn)),
 // h' = (1 - z) n + z h.  The reverse direction starts at each sequence's own last frame.  A sequence's arithmetic does not depend on NS or on
-// its neighbours in the tile: every dot product is summed in the same order.
-template <int H, int NS>
+// its neighbours in the tile: every dot product is summed in the same order.  TAPE: the same sweep, and what the backward sweep reads per
+// (direction, frame) is kept (hificar_bigru_train_kernels.hip.h); the arithmetic of h is the same statement for statement.
+template <int H, int NS, bool TAPE = false>
 __global__ __launch_bounds__(2 * H) void bigru_rec_kernel(const BigruRecParams p) {
     using S = BigruSplit<H, NS>;
     constexpr int NT = S::NT, CH = S::CH, CR = S::CR, CL = S::CL, CG = S::CG;
@@ -160,6 +162,15 @@ __global__ __launch_bounds__(2 * H) void bigru_rec_kernel(const BigruRecParams p
                 const float c = tanhf(gx[s][2] + r * d[2]);
                 hown[s] = (1.f - z) * c + z * hown[s];
                 if (q == 0) p.y[((size_t)(s0 + s) * p.T + frame(s, n)) * (2 * H) + dir * H + i] = hown[s];
+                if constexpr (TAPE) {
+                    if (q == 0) {
+                        float* tp = p.tape + (((size_t)(s0 + s) * p.T + frame(s, n)) * 2 + dir) * (4 * H) + i;
+                        tp[0] = r;
+                        tp[H] = z;
+                        tp[2 * H] = c;
+                        tp[3 * H] = d[2];
+                    }
+                }
             }
             if (q == 0) hnext[s * H + i] = hown[s];
 #pragma unroll

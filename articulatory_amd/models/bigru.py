@@ -6,9 +6,14 @@ constructor keywords and defaults, the same state_dict keys, shapes and order â€
 ``register_stats`` / ``remove_weight_norm``.  The modules below only HOLD parameters; the arithmetic runs in ``libhificar.so``
 (``hificar_bigru_*`` of include/hificar.h): no PyTorch-operator implementation, no CPU fallback.
 
+In ``train()`` mode the forward is the reference's training-mode forward â€” ``Dropout(p)`` behind each GRU layer and fc1, ``BatchNorm1d`` on
+batch statistics with the running-statistics update â€” under autograd: ``_BiGRUFunction`` keeps a tape in ``hificar_bigru_forward_train`` and
+routes ``hificar_bigru_backward``'s gradients to every parameter (and to the input when it requires grad).  Dropout masks come from the
+package's own counter-based generator (``set_dropout_seed``; numpy restatement: ``utils.synth.bigru_dropout_mask``).
+
 Not built, refused with ``NotImplementedError``: ``use_ar`` (the reference's own driver for it is broken: predict_ema.py:92 passes a
-keyword ``ar_loop`` does not take), ``use_spk_emb``, and a forward in ``train()`` mode (dropout, batch-statistics BatchNorm, autograd).
-``lengths=`` is this package's addition: a ragged batch in which every utterance's result is that of running it alone.
+keyword ``ar_loop`` does not take) and ``use_spk_emb``.  ``lengths=`` is this package's addition for eval mode: a ragged batch in which
+every utterance's result is that of running it alone (training takes equal-length batches, as the reference's collater makes them).
 """
 
 import ctypes
@@ -55,8 +60,65 @@ class _BatchNormParams(torch.nn.Module):
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
 
 
+def _grad_layout(module):
+    """[(state_dict key, offset, numel)] of the native gradient buffer (hificar_bigru_grad_info), cached per handle."""
+    cached = module.__dict__.get("_grad_info")
+    if cached is not None and cached[0] == id(module._handle):
+        return cached[1]
+    lib, handle = module._lib, module._handle
+    out = []
+    name = ctypes.create_string_buffer(96)
+    off, num = ctypes.c_int64(), ctypes.c_int64()
+    for i in range(lib.hificar_bigru_grad_count(handle)):
+        _native.check(lib.hificar_bigru_grad_info(handle, i, name, ctypes.byref(off), ctypes.byref(num)), "hificar_bigru_grad_info")
+        out.append((name.value.decode(), off.value, num.value))
+    module.__dict__["_grad_info"] = (id(module._handle), out)
+    return out
+
+
+class _BiGRUFunction(torch.autograd.Function):
+    """Autograd node of the native BiGRU in train() mode: forward = hificar_bigru_forward_train (keeps a tape), backward =
+    hificar_bigru_backward.  Inputs after (module, x, p, seed, offset, names) are the module's parameters in ``names`` order.  Returns
+    (out, batch statistics (2, 128): mean | biased variance of the batch norm's input); the statistics carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, module, x, p, seed, offset, names, *params):
+        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True)
+        B, _, T = x.shape
+        ctx.module, ctx.names, ctx.tape, ctx.toff, ctx.BT = module, names, tape, toff, (B, T)
+        ctx.save_for_backward(*params)  # torch's own version check covers an in-place edit that bumps Parameter._version ...
+        ctx.steps_seen = module._steps_seen  # ... and this one a fused optimizer step, which does not
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, dout, _dstats=None):
+        module = ctx.module
+        lib, handle = module._lib, module._handle
+        B, T = ctx.BT
+        params = ctx.saved_tensors
+        if handle is None or ctx.steps_seen != module._steps_seen:
+            raise RuntimeError("a BiGRU parameter was modified between forward and backward (the backward pass reads the weights the "
+                               "forward used)")
+        dev = ctx.tape.device
+        dout = dout.to(torch.float32).contiguous()
+        p = module._params
+        dx = torch.empty((B, p["in_channels"], T), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            grads = torch.empty(int(lib.hificar_bigru_grad_floats(handle)), dtype=torch.float32, device=dev)
+            ws_ptr, ws_bytes = module._train_workspace(B, T)
+            rc = lib.hificar_bigru_backward(handle, dout.data_ptr(), B, T, ctx.tape.data_ptr() + ctx.toff, ctx.tape.numel() - ctx.toff,
+                                            grads.data_ptr(), dx.data_ptr() if dx is not None else None, ws_ptr, ws_bytes, stream)
+        _native.check(rc, "hificar_bigru_backward")
+        views = {name: grads[off:off + num] for name, off, num in _grad_layout(module)}
+        gw = tuple(views[n].view(t.shape) if need else None for n, t, need in zip(ctx.names, params, ctx.needs_input_grad[6:]))
+        ctx.tape = None
+        return (None, dx, None, None, None, None, *gw)
+
+
 class BiGRU(torch.nn.Module):
-    """Two bidirectional GRU layers -> Linear(2H, 128) -> BatchNorm1d(128) -> Linear(128, out) (-> tanh); MI355X-native, inference only."""
+    """Two bidirectional GRU layers -> Linear(2H, 128) -> BatchNorm1d(128) -> Linear(128, out) (-> tanh); MI355X-native, eval and train()."""
 
     def __init__(self, in_channels=80, hidden_size=256, dropout=0.3, out_channels=1,
                  use_ar=False, ar_input=512, ar_hidden=256, ar_output=128, ar_channels=None, use_tanh=False,
@@ -80,6 +142,28 @@ class BiGRU(torch.nn.Module):
         self._lib = None
         self._workspace_buf = None
         self._sig = None
+        self._train_ws_buf = None
+        self._on_device = False  # the handle's weights are refreshed from device tensors (set once a training forward ran on it)
+        self._dirty = False      # an optimizer stepped since the last hand-over (fused optimizers do not bump Parameter._version)
+        self._steps_seen = 0     # optimizer steps noticed so far
+        self._calls = 0          # training forwards so far: the dropout generator's offset
+        # drawn from torch's generator (after the parameters): torch.manual_seed makes a training run repeatable
+        self._dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        from ..utils.optim_hook import watch
+
+        watch(self)  # fused optimizers do not bump Parameter._version: every optimizer.step() over these parameters marks them stale
+
+    # ------------------------------------------------------------------ training surface
+    def set_dropout_seed(self, seed, offset=0):
+        """Seed of the dropout masks; the count of training forwards (the generator's offset) restarts at ``offset``."""
+        self._dropout_seed = int(seed) & (2 ** 64 - 1)
+        self._calls = int(offset)
+
+    def invalidate_parameters(self):
+        """The parameters changed in place without their version counters showing it (what ``utils.optim_hook`` calls after every
+        ``optimizer.step()``): the next forward hands them to the native handle again."""
+        self._dirty = True
+        self._steps_seen += 1
 
     # ------------------------------------------------------------------ reference surface
     def remove_weight_norm(self):
@@ -137,7 +221,10 @@ class BiGRU(torch.nn.Module):
             self._lib.hificar_bigru_destroy(h)
         self._handle = None
         self._workspace_buf = None
+        self._train_ws_buf = None
         self._sig = None
+        self._on_device = False
+        self._dirty = False
 
     def __del__(self):
         try:
@@ -147,9 +234,17 @@ class BiGRU(torch.nn.Module):
 
     def __getstate__(self):  # copies and pickles never share a native handle
         state = self.__dict__.copy()
-        for k in ("_handle", "_lib", "_workspace_buf", "_sig"):
+        for k in ("_handle", "_lib", "_workspace_buf", "_sig", "_train_ws_buf"):
             state[k] = None
+        state["_on_device"] = state["_dirty"] = False
+        state.pop("_grad_info", None)
         return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        from ..utils.optim_hook import watch
+
+        watch(self)  # a copy trains with its own optimizer
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         out = super().load_state_dict(state_dict, strict=strict, **kw)
@@ -165,8 +260,35 @@ class BiGRU(torch.nn.Module):
         """Re-upload the weights after an in-place parameter edit that the version counters do not show (``p.data.copy_``)."""
         self._invalidate()
 
-    def _native_handle(self):
-        if self._handle is not None and self._sig == self._signature():
+    def _send_parameters(self):
+        """Every float tensor of the state_dict from device memory into the handle (hificar_bigru_set_parameters_device): nothing goes
+        through the host.  The tensors are read on the current stream, in stream order with the optimizer step that wrote them."""
+        names, held = [], []
+        for k, v in self.state_dict(keep_vars=True).items():
+            if k in ("mean", "scale") or k.endswith("num_batches_tracked"):
+                continue
+            names.append(k)
+            held.append(v if (v.dtype == torch.float32 and v.is_contiguous()) else v.detach().to(torch.float32).contiguous())
+        arr = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
+        ptrs = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
+        with torch.cuda.device(self._device()):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _native.check(self._lib.hificar_bigru_set_parameters_device(self._handle, arr, ptrs, len(held), stream),
+                          "hificar_bigru_set_parameters_device")
+        self._on_device = True
+        self._dirty = False
+        self._sig = self._signature()
+
+    def _native_handle(self, train=False):
+        if self._handle is not None and self._on_device:
+            # a handle that has trained: its weights follow the parameters on the device (eval after training sees the updated weights and
+            # running statistics without a trip through the host)
+            if self._dirty or self._sig != self._signature():
+                self._send_parameters()
+            return self._handle
+        if self._handle is not None and self._sig == self._signature() and not self._dirty:
+            if train:
+                self._send_parameters()
             return self._handle
         self._invalidate()
         dev = self._device()
@@ -190,7 +312,39 @@ class BiGRU(torch.nn.Module):
                 raise
         self._handle = handle
         self._sig = self._signature()
+        if train:
+            self._send_parameters()
         return handle
+
+    def _train_workspace(self, B, T):
+        """One grow-only scratch buffer shared by the training forward and the backward pass (hificar_bigru_train_workspace_bytes)."""
+        n = self._lib.hificar_bigru_train_workspace_bytes(self._handle, B, T) + 256
+        ws = self._train_ws_buf
+        if ws is None or ws.numel() < n:
+            ws = torch.empty(int(n * 1.25) if ws is not None else n, dtype=torch.uint8, device=self._device())
+            self._train_ws_buf = ws
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
+    def _run_forward_train(self, x, p, seed, offset, keep_tape):
+        """hificar_bigru_forward_train on the current stream: (out, batch statistics, tape or None, the tape's alignment offset)."""
+        lib, handle = self._lib, self._handle
+        B, _, T = x.shape
+        dev = x.device
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            tape, toff = None, 0
+            if keep_tape:
+                tape = torch.empty(lib.hificar_bigru_tape_bytes(handle, B, T) + 256, dtype=torch.uint8, device=dev)
+                toff = (-tape.data_ptr()) % 256
+            out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=dev)
+            stats = torch.empty((2, FC1_DIM), dtype=torch.float32, device=dev)
+            ws_ptr, ws_bytes = self._train_workspace(B, T)
+            rc = lib.hificar_bigru_forward_train(handle, x.data_ptr(), out.data_ptr(), stats.data_ptr(), B, T, float(p), seed, offset,
+                                                 tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
+                                                 ws_ptr, ws_bytes, stream)
+        _native.check(rc, "hificar_bigru_forward_train")
+        return out, stats, tape, toff
 
     def _workspace(self, B, T):
         """One grow-only scratch buffer per model (pre-gates of B x T frames + one row buffer: hificar_bigru_workspace_bytes)."""
@@ -215,8 +369,7 @@ class BiGRU(torch.nn.Module):
         ragged batch â€” utterance b is computed as if it were alone with lengths[b] frames (its reverse direction starts at its own last
         frame; zero padding would not be equivalent) and out[b, :, lengths[b]:] is zero."""
         if self.training:
-            raise NotImplementedError("BiGRU.forward in train() mode is not built (dropout, batch-statistics BatchNorm and autograd): "
-                                      "call .eval() â€” training a BiGRU is out of scope")
+            return self._forward_train(mels, lengths)
         if not isinstance(mels, torch.Tensor) or mels.device.type != "cuda":
             raise RuntimeError("BiGRU.forward needs a CUDA/HIP tensor; there is no CPU fallback")
         if mels.dim() != 3 or mels.shape[1] != self._params["in_channels"]:
@@ -246,4 +399,41 @@ class BiGRU(torch.nn.Module):
             rc = self._lib.hificar_bigru_forward(handle, c.data_ptr(), lens[0], lens[1], out.data_ptr(), B, T, ws_ptr, ws_bytes,
                                                  ctypes.c_void_p(stream))
         _native.check(rc, "hificar_bigru_forward")
+        return out
+
+    def _forward_train(self, mels, lengths):
+        """train() mode (pytorch_models.py:45-72 with its three nn.Dropout active and the batch norm on batch statistics): with grad enabled
+        the output is part of the autograd graph; without, the same arithmetic runs and its tape is dropped.  Every call â€” either way â€”
+        advances the dropout generator's offset and updates bn.running_mean / running_var / num_batches_tracked as torch.nn.BatchNorm1d does."""
+        if lengths is not None:
+            raise NotImplementedError("BiGRU.forward(lengths=...) in train() mode is not built: training takes equal-length batches "
+                                      "(the reference's collater cuts equal windows); call .eval() for ragged batches")
+        if not isinstance(mels, torch.Tensor) or mels.device.type != "cuda":
+            raise NotImplementedError("BiGRU.forward in train() mode needs a CUDA/HIP tensor: the training path only exists as HIP kernels "
+                                      "(there is no CPU fallback)")
+        if mels.dim() != 3 or mels.shape[1] != self._params["in_channels"]:
+            raise RuntimeError(f"BiGRU.forward: expected (B, {self._params['in_channels']}, T), got {tuple(mels.shape)}")
+        B, _, T = mels.shape
+        if B < 1 or T < 1:
+            raise RuntimeError(f"BiGRU.forward: empty input {tuple(mels.shape)}")
+        if B * T == 1:  # torch.nn.functional.batch_norm's own refusal
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, FC1_DIM, T]}")
+        self._native_handle(train=True)
+        if mels.device != self._device():
+            raise RuntimeError(f"BiGRU.forward: input on {mels.device}, parameters on {self._device()}")
+        x = mels.to(torch.float32).contiguous()
+        named = list(self.named_parameters())
+        names, params = tuple(n for n, _ in named), [p for _, p in named]
+        offset = self._calls
+        self._calls += 1
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            out, stats = _BiGRUFunction.apply(self, x, self._params["dropout"], self._dropout_seed, offset, names, *params)
+        else:  # no graph: the same arithmetic without a tape (tape = NULL)
+            out, stats, _, _ = self._run_forward_train(x.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False)
+        with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance
+            n = B * T
+            self.bn.running_mean.mul_(0.9).add_(stats[0], alpha=0.1)
+            self.bn.running_var.mul_(0.9).add_(stats[1], alpha=0.1 * n / (n - 1))
+            self.bn.num_batches_tracked += 1
+        # (the running statistics only enter the eval path: its fold is refreshed when an eval forward next asks for the handle)
         return out

@@ -488,3 +488,27 @@ def synth_bigru_state_dict(params: dict, seed: int = 1234, gain: float = 1.0) ->
         else:
             out[name] = uniform(seed, name, shape, -0.05, 0.05)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# BiGRU training: the dropout masks of libhificar's counter-based generator (csrc/hificar_bigru_train_kernels.hip.h: BigruDrop)
+# ------------------------------------------------------------------------------------------------
+BIGRU_DROPOUT_SITES = {"gru1": 0, "gru2": 1, "fc1": 2}  # the output each nn.Dropout of the reference acts on (pytorch_models.py:65-68)
+
+
+def bigru_dropout_mask(seed: int, offset: int, site, shape, p: float) -> np.ndarray:
+    """The factor (0, or 1 / (1 - p) in float32) of every element of the (B, T, C) tensor at ``site`` for training forward number ``offset``
+    of a model seeded with ``seed``: element e (row-major index) is kept when u(seed, offset, site, e) >= p, u = the top 24 bits of
+    splitmix64(key + e) / 2^24 with key = splitmix64(seed ^ splitmix64(4 offset + site)).  ``p = 0`` gives all ones and draws nothing."""
+    site = BIGRU_DROPOUT_SITES[site] if isinstance(site, str) else int(site)
+    n = int(np.prod(shape))
+    p32 = np.float32(p)
+    if not p32 > 0:
+        return np.ones(shape, dtype=np.float32)
+    inner = _splitmix64(np.array([(4 * int(offset) + site) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))
+    key = _splitmix64(np.array([int(seed) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64) ^ inner)
+    with np.errstate(over="ignore"):
+        bits = _splitmix64((np.arange(n, dtype=np.uint64) + key) & _MASK)
+    u = (bits >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    scale = np.float32(1.0) / (np.float32(1.0) - p32)
+    return np.where(u >= p32, scale, np.float32(0.0)).astype(np.float32).reshape(shape)

@@ -554,6 +554,44 @@ hificar_engine* hificar_bigru_engine(hificar_bigru* h);
 /* del model */
 void hificar_bigru_destroy(hificar_bigru* h);
 
+/* ---- BiGRU training: the reference's step for dataset_mode art / a2m / m2a (articulatory/bin/train.py:241-383), the model in train() mode:
+ * Dropout(p) behind each GRU layer and fc1, BatchNorm1d on batch statistics.  Exact fp32, deterministic (fixed-order reductions).
+ * Equal-length batches only (the reference's CollaterMelArt cuts equal windows): there is no `lengths` here.  All of these may be called
+ * after hificar_bigru_finalize; the first one builds the training state. ---- */
+
+/* Every float tensor of the state_dict (reference names and layouts, bn.running_mean / bn.running_var included; n = all of them, each
+ * once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs, W_hh and
+ * its transpose in the recurrent kernels' orders, and the eval-mode fold of the batch norm into fc1 — hificar_bigru_forward sees the
+ * new weights too.  Call it after every optimizer step (and before the first hificar_bigru_forward_train). */
+int hificar_bigru_set_parameters_device(hificar_bigru* h, const char* const* names, const float* const* data, int n, void* stream);
+
+/* The gradient buffer: hificar_bigru_grad_floats(h) floats; tensor i of hificar_bigru_grad_count(h) has the reference's state_dict name
+ * (name96: at least 96 bytes) and layout, at `offset` floats, `numel` long.  Same contract as hificar_grad_info. */
+int hificar_bigru_grad_count(hificar_bigru* h);
+int hificar_bigru_grad_info(hificar_bigru* h, int i, char* name96, int64_t* offset, int64_t* numel);
+int64_t hificar_bigru_grad_floats(hificar_bigru* h);
+
+/* Bytes of the tape (what a training forward keeps for its backward pass: the input rows, both layers' hidden states and per-step gate
+ * values r, z, n, W_hn h + b_hn, the raw fc1 rows, the batch statistics, the output; dropout masks are regenerated, not stored) and of
+ * the scratch shared by hificar_bigru_forward_train and hificar_bigru_backward. */
+size_t hificar_bigru_tape_bytes(const hificar_bigru* h, int B, int T);
+size_t hificar_bigru_train_workspace_bytes(hificar_bigru* h, int B, int T);
+
+/* BiGRU.forward in train() mode: x (B, in_channels, T) -> out (B, out_channels, T), device fp32.  Dropout: element e of site s (0: gru1's
+ * output, 1: gru2's, 2: fc1's; e = the element's index in the (B, T, C) tensor) is kept when u(seed, offset, s, e) >= dropout_p and scaled
+ * by 1 / (1 - dropout_p); u is a counter-based generator (numpy restatement: articulatory_amd.utils.synth.bigru_dropout_mask), `offset`
+ * the caller's count of training forwards.  dropout_p = 0 is the identity.  bn_batch_stats: 2 x 128 device floats, this batch's
+ * per-channel mean and BIASED variance (the caller updates running_mean / running_var as torch.nn.BatchNorm1d does).  B * T >= 2.
+ * tape / workspace: 256-byte aligned device memory of at least the sizes above; the tape is the caller's until hificar_bigru_backward ran.
+ * tape = NULL (tape_bytes ignored): the same arithmetic and outputs without a tape, for a training-mode forward that no backward follows. */
+int hificar_bigru_forward_train(hificar_bigru* h, const float* x, float* out, float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed,
+                                uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dout (B, out_channels, T) -> grads (hificar_bigru_grad_floats floats: written, not accumulated) and, with dx non-NULL, the input's
+ * gradient (B, in_channels, T).  The weights must be those of the forward that filled the tape. */
+int hificar_bigru_backward(hificar_bigru* h, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

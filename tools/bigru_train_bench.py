@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""One training step of the BiGRU inversion model (forward in train() mode + L1 loss + backward + fused Adam) on the native kernels
+(libhificar.so: hificar_bigru_forward_train / hificar_bigru_backward / hificar_bigru_set_parameters_device) next to the same step of the
+same model from stock PyTorch-ROCm modules, on the same GPU in the same process.
+   python tools/bigru_train_bench.py [--shapes full mfcc] [--batches 8 32] [--frames 200 500] [--window 0.3] [--out profiles/bigru_train.txt]
+
+Shapes: full (1024, 256, 18) and mfcc (13, 256, 12, tanh).  Per (shape, B, T): device time from events, both warmed up, windows of at least
+--window seconds alternated native / stock / native / stock (the two native windows run on unchanged code: their difference is the spread a
+ratio has to exceed).  --limit seconds per step is checked from the events after each block of up to 16 steps and ends the run: it
+cannot stop a step that hangs, so run the tool under an outer `timeout`.  Then one native step under hificar_profile_begin / hificar_profile_end:
+time per kernel, the forward and the backward sweep's microseconds per step (kernel time / (2 layers * T)), and the tape / workspace bytes.
+The stock model's dropout masks are torch's own (another random stream: the two steps are timed, not compared).
+Prints one JSON line per case; --out also appends them to a file."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from articulatory_amd import _native  # noqa: E402
+from articulatory_amd.models import BiGRU  # noqa: E402
+from articulatory_amd.utils.synth import synth_bigru_state_dict, uniform  # noqa: E402
+
+SHAPES = {"full": dict(in_channels=1024, hidden_size=256, out_channels=18, use_tanh=False),
+          "mfcc": dict(in_channels=13, hidden_size=256, out_channels=12, use_tanh=True)}
+DROPOUT = 0.3
+
+
+class StockBiGRU(torch.nn.Module):
+    """The reference's module graph (pytorch_models.py:27-37, 62-72) from stock torch.nn modules, dropout included."""
+
+    def __init__(self, in_channels, hidden_size, out_channels, use_tanh):
+        super().__init__()
+        self.gru1 = torch.nn.GRU(input_size=in_channels, hidden_size=hidden_size, num_layers=1, batch_first=True, bidirectional=True)
+        self.dropout1 = torch.nn.Dropout(DROPOUT)
+        self.gru2 = torch.nn.GRU(input_size=hidden_size * 2, hidden_size=hidden_size, num_layers=1, batch_first=True, bidirectional=True)
+        self.dropout2 = torch.nn.Dropout(DROPOUT)
+        self.fc1 = torch.nn.Sequential(torch.nn.Linear(hidden_size * 2, 128), torch.nn.Dropout(DROPOUT))
+        self.bn = torch.nn.BatchNorm1d(128)
+        self.fc2 = torch.nn.Sequential(torch.nn.Linear(128, out_channels), torch.nn.Tanh()) if use_tanh else torch.nn.Linear(128, out_channels)
+
+    def forward(self, mels):
+        y, _ = self.gru1(mels.transpose(1, 2))
+        y, _ = self.gru2(self.dropout1(y))
+        y = self.fc1(self.dropout2(y)).transpose(1, 2)
+        y = self.bn(y).transpose(1, 2)
+        return self.fc2(y).transpose(1, 2)
+
+
+def make_step(model, x, t):
+    opt = torch.optim.Adam(model.parameters(), lr=1e-4, fused=True)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        F.l1_loss(model(x), t).backward()
+        opt.step()
+
+    return step
+
+
+def window(fn, seconds, limit):
+    """Mean device milliseconds per call over a window of at least `seconds` (events around blocks of calls)."""
+    total_ms, calls, n = 0.0, 0, 1
+    while total_ms < seconds * 1e3:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        e1.synchronize()
+        ms = e0.elapsed_time(e1)
+        if ms / n > limit * 1e3:
+            raise SystemExit(f"a step took {ms / n:.0f} ms, over the limit of {limit} s")
+        total_ms += ms
+        calls += n
+        n = min(n * 2, 16)
+    return total_ms / calls
+
+
+def kernel_profile(m, fn):
+    lib, eng = m._lib, m.engine()
+    _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
+    fn()
+    stats = (_native.HificarKernelStat * 64)()
+    n = ctypes.c_int()
+    _native.check(lib.hificar_profile_end(eng, stats, 64, ctypes.byref(n)), "hificar_profile_end")
+    return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(n.value)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES))
+    ap.add_argument("--batches", type=int, nargs="+", default=[8, 32])
+    ap.add_argument("--frames", type=int, nargs="+", default=[200, 500])
+    ap.add_argument("--window", type=float, default=0.3)
+    ap.add_argument("--limit", type=float, default=5.0, help="seconds a single step may take")
+    ap.add_argument("--no-stock", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    lines = []
+    for shape in a.shapes:
+        params = SHAPES[shape]
+        tsd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth_bigru_state_dict(params, seed=5101).items()}
+        for B in a.batches:
+            for T in a.frames:
+                native = BiGRU(**params, dropout=DROPOUT)
+                native.load_state_dict(tsd, strict=True)
+                native = native.cuda().train()
+                x = torch.from_numpy(uniform(1, f"x.{B}.{T}", (B, params["in_channels"], T), -1.0, 1.0)).cuda()
+                t = torch.from_numpy(uniform(1, f"t.{B}.{T}", (B, params["out_channels"], T), -1.0, 1.0)).cuda()
+                nstep = make_step(native, x, t)
+                sstep = None
+                if not a.no_stock:
+                    stock = StockBiGRU(**params)
+                    stock.load_state_dict(tsd, strict=True)
+                    sstep = make_step(stock.cuda().train(), x, t)
+                for _ in range(3):
+                    nstep()
+                    if sstep:
+                        sstep()
+                torch.cuda.synchronize()
+                n1 = window(nstep, a.window, a.limit)
+                s1 = window(sstep, a.window, a.limit) if sstep else None
+                n2 = window(nstep, a.window, a.limit)
+                s2 = window(sstep, a.window, a.limit) if sstep else None
+                res = {"shape": shape, "B": B, "T": T, "native_step_ms": [round(n1, 3), round(n2, 3)],
+                       "native_spread": round(abs(n1 - n2) / min(n1, n2), 4)}
+                if sstep:
+                    res["stock_step_ms"] = [round(s1, 3), round(s2, 3)]
+                    res["stock_spread"] = round(abs(s1 - s2) / min(s1, s2), 4)
+                    res["stock_over_native"] = round(min(s1, s2) / max(n1, n2), 3)  # the conservative ratio: slowest native, fastest stock
+                prof = kernel_profile(native, nstep)
+                res["kernels_ms"] = {k: round(ms, 4) for k, (_, ms) in sorted(prof.items())}
+                res["kernels_total_ms"] = round(sum(ms for _, ms in prof.values()), 3)
+                res["fwd_sweep_us_per_step"] = round(prof.get("bigru_rec_kernel", (0, 0.0))[1] * 1e3 / (2 * T), 3)
+                res["bwd_sweep_us_per_step"] = round(prof.get("bigru_rec_bwd_kernel", (0, 0.0))[1] * 1e3 / (2 * T), 3)
+                res["tape_bytes"] = int(native._lib.hificar_bigru_tape_bytes(native._handle, B, T))
+                res["workspace_bytes"] = int(native._lib.hificar_bigru_train_workspace_bytes(native._handle, B, T))
+                lines.append(json.dumps(res))
+                print(lines[-1], flush=True)
+                del native, nstep, sstep
+                torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
