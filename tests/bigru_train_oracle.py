@@ -26,6 +26,76 @@ STEPS = dict(n=5, lr=1e-3, grad_norm=10.0, step_size=1, gamma=0.5, lambda_aux=1.
 FULL_LIMIT = 8192           # gradients up to this many elements are stored whole, larger ones packed (sum, |.|-sum, 64 samples)
 
 
+# Shapes where the training kernels change form beyond what the golden cases and tests/test_gpu_bigru_train.py's SHAPES reach, against the
+# float64 restatement: name -> (Cin, H, out, B, T, p, sequences per workgroup or None, tanh).  Each is admitted on the CPU first
+# (tests/test_bigru_train_host.py): the restatement's own float32 run must be within half of every bar the device is held to.
+EDGE_SHAPES = OrderedDict([
+    ("t64", (8, 64, 12, 2, 64, 0.3, None, False)),          # the head's 64-frame tile exactly full
+    ("t65", (8, 64, 12, 2, 65, 0.3, None, False)),          # ... a second tile of one frame
+    ("t129", (8, 64, 12, 2, 129, 0.3, None, False)),        # ... three tiles, a one-frame tail
+    ("t63_b1", (8, 64, 12, 1, 63, 0.3, None, False)),       # one short tile alone
+    ("o32", (8, 64, 32, 2, 65, 0.3, None, False)),          # kBigruMaxOut output channels
+    ("o32_tanh", (8, 64, 32, 2, 65, 0.3, None, True)),      # ... through tanh'
+    ("o1_tanh", (8, 64, 1, 3, 70, 0.3, None, True)),        # one output row, tail tile
+    ("h128_ns2", (24, 128, 18, 3, 5, 0.3, 2, False)),       # the <128, 2> sweeps, an odd tail tile of sequences
+    ("h192_ns2", (24, 192, 18, 3, 5, 0.3, 2, False)),       # the <192, 2> sweeps
+    ("t500", (24, 64, 12, 2, 500, 0.3, None, False)),       # the recurrence at the workload's length
+    ("t300_h256", (24, 256, 18, 1, 300, 0.3, None, False)), # a long sweep with the L2-streamed columns of W_hh^T
+    ("p05", (24, 64, 12, 3, 40, 0.5, None, False)),         # other dropout probabilities
+    ("p09", (24, 64, 12, 3, 40, 0.9, None, False)),         # ... kept values scaled by 10
+    # every grid-stride loop's second trip: B T = 8580 > 8192 rows, B T 2H = 4 392 960 > 4 194 304 elements; three head tiles with a 2-frame
+    # tail, 269 rows per batch-norm lane.  B 66 stays at one sequence per workgroup (2 B <= the chip's 256 CUs), unlike SHAPES' b130.
+    ("stride", (24, 256, 18, 66, 130, 0.3, None, False)),
+])
+EDGE_SEEDS = {name: 7100 + i for i, name in enumerate(EDGE_SHAPES)}
+EDGE_BARS = dict(out=2e-5, loss=1e-5, grad=2e-4)  # the device's bars (tests/test_gpu_bigru_train.py: TOL_OUT, TOL_LOSS, TOL_GRAD)
+KINK_MARGIN = 1e-4
+
+
+def edge_case(name):
+    """(model params, state_dict, x (B, in, T), target (B, out, T), sequences per workgroup or None) of an EDGE_SHAPES entry."""
+    cin, H, out, B, T, p, ns, tanh = EDGE_SHAPES[name]
+    seed = EDGE_SEEDS[name]
+    params = dict(in_channels=cin, hidden_size=H, out_channels=out, use_tanh=tanh, dropout=p)
+    x = uniform(seed, "x", (B, cin, T), -1.0, 1.0)
+    # |y| is a few tenths without tanh and below 1 with it: targets in +-[4, 5] keep every |y - target| off the L1 kink
+    t = uniform(seed, "t", (B, out, T), 4.0, 5.0) * np.where(uniform(seed, "s", (B, out, T), -1.0, 1.0) >= 0, 1.0, -1.0).astype(np.float32)
+    return params, synth_bigru_state_dict(params, seed=seed), x, t, ns
+
+
+def edge_restatement(name, dtype):
+    """One step of the restatement on an EDGE_SHAPES entry: dict(y, loss, dx, running_mean, running_var, kink, grad.<key> ...)."""
+    params, sd, x, t, _ = edge_case(name)
+    o = BiGRUTrainOracle(sd, use_tanh=params["use_tanh"], dropout=params["dropout"], dtype=dtype)
+    y, loss, grads, dx = o.loss_and_grads(x, t)
+    res = dict(y=y, loss=loss, dx=dx, running_mean=o.running_mean, running_var=o.running_var,
+               kink=float((y - torch.from_numpy(t).to(dtype)).abs().min() / y.abs().max()))
+    for k, g in grads.items():
+        res["grad." + k] = g
+    return res
+
+
+def edge_errors(got, ref, p):
+    """{quantity: (deviation of ``got`` from the float64 results ``ref``, its bar)} for everything the device test checks: y and the running
+    statistics relative to the tensor's max, the loss relative, every gradient relative to its own max (fc1.0.bias at p = 0, which is
+    mathematically zero, to fc1.0.weight's)."""
+    def rel(a, b):
+        return float((torch.as_tensor(a).detach().cpu().double() - b).abs().max() / max(float(b.abs().max()), 1e-30))
+
+    out = {"y": (rel(got["y"], ref["y"]), EDGE_BARS["out"]),
+           "loss": (abs(float(got["loss"]) - float(ref["loss"])) / abs(float(ref["loss"])), EDGE_BARS["loss"]),
+           "running_mean": (rel(got["running_mean"], ref["running_mean"]), EDGE_BARS["out"]),
+           "running_var": (rel(got["running_var"], ref["running_var"]), EDGE_BARS["out"])}
+    if got.get("dx") is not None:
+        out["dx"] = (rel(got["dx"], ref["dx"]), EDGE_BARS["grad"])
+    for k, r in ref.items():
+        if not k.startswith("grad."):
+            continue
+        scale = ref["grad.fc1.0.weight"].abs().max() if (k == "grad.fc1.0.bias" and p == 0) else r.abs().max()
+        out[k] = (float((torch.as_tensor(got[k]).detach().cpu().double() - r).abs().max() / scale), EDGE_BARS["grad"])
+    return out
+
+
 def case_params(tag):
     cin, H, out, tanh, B, T, p, seed = GOLD_CASES[tag]
     return dict(in_channels=cin, hidden_size=H, out_channels=out, use_tanh=tanh, dropout=p), B, T, seed

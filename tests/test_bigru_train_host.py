@@ -81,6 +81,109 @@ def test_mask_generator():
     assert BIGRU_DROPOUT_SITES == {"gru1": 0, "gru2": 1, "fc1": 2}
 
 
+@pytest.mark.parametrize("name", list(O.EDGE_SHAPES))
+def test_edge_shape_is_admitted_by_the_restatements_own_float32_run(name):
+    """The device's bars are exact-fp32 bars: a shape of tests/test_gpu_bigru_train_edges.py is a yardstick only if the restatement's own
+    float32 arithmetic is within HALF of every bar against its float64 run, on the scales the device test uses, and the case is kink-free."""
+    r32 = O.edge_restatement(name, torch.float32)
+    r64 = O.edge_restatement(name, torch.float64)
+    assert min(r32["kink"], r64["kink"]) > O.KINK_MARGIN
+    errs = O.edge_errors(r32, r64, O.EDGE_SHAPES[name][5])
+    assert {"y", "loss", "dx", "running_mean", "running_var"} <= set(errs) and sum(k.startswith("grad.") for k in errs) == 22
+    for k, (e, bar) in errs.items():
+        assert e <= 0.5 * bar, (k, e)
+
+
+def test_edge_shapes_reach_what_they_are_there_for():
+    """Pure arithmetic on the table: the sizes at which the training kernels' loops and tiles change form (csrc/hificar_bigru_train*.h*)."""
+    S = O.EDGE_SHAPES
+    tiles = {n: -(-s[4] // 64) for n, s in S.items()}
+    assert (tiles["t64"], tiles["t65"], tiles["t129"], tiles["t63_b1"]) == (1, 2, 3, 1) and S["t65"][4] % 64 == S["t129"][4] % 64 == 1
+    assert S["o32"][2] == S["o32_tanh"][2] == 32 and S["o32_tanh"][7] and S["o1_tanh"][7] and S["o1_tanh"][2] == 1 and tiles["o1_tanh"] == 2
+    assert (S["h128_ns2"][1], S["h192_ns2"][1]) == (128, 192) and all(S[n][6] == 2 and S[n][3] % 2 == 1 for n in ("h128_ns2", "h192_ns2"))
+    cin, H, out, B, T, p, ns, tanh = S["stride"]
+    assert B * T > 4096 * 256 // 128          # bigru_bn_bwd_dx_kernel: 4096 blocks x 256 elements of B T x 128
+    assert B * T * 2 * H > 4096 * 1024        # bigru_dropout_kernel (1024 elements per block) and bigru_hprev_kernel (256 float4)
+    assert tiles["stride"] == 3 and T % 64 == 2 and -(-B * T // 32) == 269 and ns is None and 2 * B <= 256
+    assert sorted({S[n][5] for n in S}) == [0.3, 0.5, 0.9]
+    assert len(set(O.EDGE_SEEDS.values())) == len(S)
+
+
+# ------------------------------------------------------------------------------------------------
+# the mask generator against what dropout is supposed to be (the bounds are binomial, five standard deviations, not measurements)
+# ------------------------------------------------------------------------------------------------
+MASK_N = 1 << 20
+MASK_PS = (0.1, 0.3, 0.5, 0.9)
+MASK_SEEDS = (11, 2 ** 61 + 12345)
+MASK_OFFSETS = (0, 1, 2 ** 32)
+
+
+def kept(seed, offset, site, p, n=MASK_N):
+    return bigru_dropout_mask(seed, offset, site, (n,), p) > 0
+
+
+def five_sigma(q, n):
+    return 5.0 * np.sqrt(q * (1.0 - q) / n)
+
+
+@pytest.mark.parametrize("p", MASK_PS)
+def test_mask_keep_rate_and_kept_value(p):
+    q = 1.0 - float(np.float32(p))
+    value = np.float32(1) / (np.float32(1) - np.float32(p))
+    for seed in MASK_SEEDS:
+        for offset in MASK_OFFSETS:
+            for site in BIGRU_DROPOUT_SITES:
+                m = bigru_dropout_mask(seed, offset, site, (MASK_N,), p)
+                assert m.dtype == np.float32 and set(np.unique(m)) == {np.float32(0), value}, (seed, offset, site)
+                assert abs(float((m > 0).mean()) - q) <= five_sigma(q, MASK_N), (seed, offset, site)
+
+
+@pytest.mark.parametrize("p", MASK_PS)
+def test_masks_of_different_streams_are_independent(p):
+    """Two masks that differ only in site, only in offset or only in seed: both keep a position with probability (1 - p)^2."""
+    q2 = (1.0 - float(np.float32(p))) ** 2
+    base = (MASK_SEEDS[0], 0, 0)
+    pairs = [((s, 0, a), (s, 0, b)) for s in MASK_SEEDS for a, b in ((0, 1), (0, 2), (1, 2))]
+    pairs += [((s, a, 2), (s, b, 2)) for s in MASK_SEEDS for a, b in ((0, 1), (0, 2 ** 32), (1, 2 ** 32), (1, 2))]
+    pairs += [(base, (MASK_SEEDS[1], 0, 0)), (base, (MASK_SEEDS[0] + 1, 0, 0)), (base, (MASK_SEEDS[0] ^ (1 << 63), 0, 0))]
+    for u, v in pairs:
+        both = float((kept(*u, p) & kept(*v, p)).mean())
+        assert abs(both - q2) <= five_sigma(q2, MASK_N), (u, v, both)
+
+
+@pytest.mark.parametrize("p", MASK_PS)
+def test_mask_is_independent_along_the_stream(p):
+    """Positions e and e + k are both kept with probability (1 - p)^2, at the lags of the float4 lanes (1, 2), the next float4 (4) and the
+    row strides 128 (fc1) and 2H = 512.  (Overlapping pairs share elements, so the share's true deviation is up to 1.4 binomial ones: the
+    bound is tighter than five of its own.)"""
+    q2 = (1.0 - float(np.float32(p))) ** 2
+    for seed in MASK_SEEDS:
+        for site in BIGRU_DROPOUT_SITES:
+            k0 = kept(seed, 0, site, p)
+            for lag in (1, 2, 4, 128, 512):
+                both = float((k0[:-lag] & k0[lag:]).mean())
+                assert abs(both - q2) <= five_sigma(q2, MASK_N - lag), (seed, site, lag, both)
+
+
+def test_mask_at_degenerate_probabilities():
+    """p = 0 (and anything not above it) is the identity and draws nothing.  u is a multiple of 2^-24, and an element is kept when u >= p in
+    float32: for 0 < p <= 2^-24 exactly the elements whose 24 bits are all zero (u = 0) are dropped — the keep set of p = 2^-24 — and below
+    2^-25 the kept value 1 / (1 - p) is exactly 1 in float32."""
+    for p in (0.0, -0.0, -0.5):
+        assert np.array_equal(bigru_dropout_mask(3, 7, "gru2", (5, 4, 3), p), np.ones((5, 4, 3), np.float32))
+    tiny = bigru_dropout_mask(11, 0, "fc1", (MASK_N,), 1e-8)
+    edge = bigru_dropout_mask(11, 0, "fc1", (MASK_N,), 2.0 ** -24)
+    assert set(np.unique(tiny)) <= {np.float32(0), np.float32(1)}
+    assert np.array_equal(tiny > 0, edge > 0)
+    assert set(np.unique(edge)) <= {np.float32(0), np.float32(1) / (np.float32(1) - np.float32(2.0 ** -24))}
+    dropped = int((tiny == 0).sum())  # expected MASK_N / 2^24 = 1 / 16 of an element; five deviations (0.25 each) above that is below 2
+    assert dropped <= 1
+    # ... and a stretch that does hold such an element: the first u = 0 of this stream, found through p = 2^-23 (drops u in {0, 2^-24})
+    wide = bigru_dropout_mask(11, 0, "fc1", (1 << 24,), 2.0 ** -23) == 0
+    low = bigru_dropout_mask(11, 0, "fc1", (1 << 24,), 1e-8) == 0
+    assert not (low & ~wide).any() and 0 < int(wide.sum()) < 40 and int(low.sum()) <= int(wide.sum())
+
+
 def test_key_list_is_the_references():
     keys = open(os.path.join(GOLDEN, "gold_bigru_train_keys.txt")).read().split()
     assert keys == open(os.path.join(GOLDEN, "gold_bigru_keys.txt")).read().split()
