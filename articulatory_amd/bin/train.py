@@ -30,7 +30,7 @@ import numpy as np
 import torch
 import yaml
 
-from articulatory_amd.losses import MelSpectrogramLoss, MultiResolutionSTFTLoss
+from articulatory_amd.losses import MelSpectrogramLoss, MultiResolutionSTFTLoss, masked_l1_loss
 from articulatory_amd.models import HiFiGANGenerator
 
 
@@ -509,11 +509,15 @@ class WindowPairs(torch.utils.data.Dataset):
     """(input frames (T, Cin), target frames (T, Cout)) pairs for an inversion model: two aligned ``.npy`` scp files, or ``n`` synthetic
     utterances.  ``swap`` (dataset_mode m2a) exchanges the two sides, as CollaterMelArt does (train.py:855-859)."""
 
-    def __init__(self, x_scp=None, y_scp=None, min_frames=1, swap=False, synthetic=0, frames=0, dims=(1, 1), seed=0):
+    def __init__(self, x_scp=None, y_scp=None, min_frames=1, swap=False, synthetic=0, frames=0, dims=(1, 1), seed=0, frames_range=None):
         if synthetic:
             rng = np.random.default_rng(seed)
-            self.items = [(rng.standard_normal((frames, dims[0])).astype(np.float32), np.tanh(rng.standard_normal((frames, dims[1]))).astype(np.float32))
-                          for _ in range(synthetic)]
+            if frames_range is not None:  # utterances of unequal lengths (package_mode pad): uniform in [lo, hi], drawn before the data
+                counts = [int(n) for n in rng.integers(frames_range[0], frames_range[1] + 1, size=synthetic)]
+            else:
+                counts = [frames] * synthetic
+            self.items = [(rng.standard_normal((n, dims[0])).astype(np.float32), np.tanh(rng.standard_normal((n, dims[1]))).astype(np.float32))
+                          for n in counts]
             return
 
         def read(p):
@@ -553,11 +557,91 @@ class FrameWindowCollater:
         return {"x": torch.from_numpy(np.stack(xs)).transpose(2, 1).contiguous(), "y": torch.from_numpy(np.stack(ys)).transpose(2, 1).contiguous()}
 
 
+class PadCollater:
+    """``package_mode: pad`` (the reference's key, train.py:909-913, 1036-1063): whole utterances, zero-padded to the batch's longest ->
+    {"x": (B, Cin, T), "y": (B, Cout, T), "lengths": (B,) int32}.  Unlike the reference, which trains on the padding as if it were speech,
+    the padded frames take no part in the batch statistics, the loss or the gradients (``BiGRU.forward_padded`` + ``masked_l1_loss``).
+    ``pad_max_frames`` (this package's key, optional): a longer utterance is cut to a random window of that many frames."""
+
+    def __init__(self, pad_max_frames=None, seed=None):
+        self.max_frames = int(pad_max_frames) if pad_max_frames else None
+        self.rng = np.random.default_rng(seed)
+
+    def __call__(self, items):
+        xs, ys = [], []
+        for a, b in items:
+            n = min(len(a), len(b))
+            start = 0
+            if self.max_frames is not None and n > self.max_frames:
+                start = int(self.rng.integers(0, n - self.max_frames + 1))
+                n = self.max_frames
+            xs.append(np.asarray(a[start:start + n], np.float32))
+            ys.append(np.asarray(b[start:start + n], np.float32))
+        lengths = [len(a) for a in xs]
+        T = max(lengths)
+        if T < 1:
+            raise ValueError("a batch of empty utterances")
+        x = np.zeros((len(xs), xs[0].shape[1], T), np.float32)
+        y = np.zeros((len(ys), ys[0].shape[1], T), np.float32)
+        for i, (a, b) in enumerate(zip(xs, ys)):
+            x[i, :, :len(a)] = a.T
+            y[i, :, :len(b)] = b.T
+        return {"x": torch.from_numpy(x), "y": torch.from_numpy(y), "lengths": torch.tensor(lengths, dtype=torch.int32)}
+
+
+def padded_share(lengths, batches):
+    """The share of padded frames when every batch (a list of indices into ``lengths``) is padded to its own longest utterance."""
+    total = sum(len(b) * max(lengths[i] for i in b) for b in batches)
+    return 1.0 - sum(lengths[i] for b in batches for i in b) / max(total, 1)
+
+
+class LengthBucketBatchSampler(torch.utils.data.Sampler):
+    """Batches of utterances of similar lengths for ``package_mode: pad``: shuffle, sort pools of ``bucket_batches`` batches by length, cut
+    the batches, shuffle the batches.  Every utterance once per epoch (the last, short batch is dropped with ``drop_last``); seeded: epoch e
+    of two samplers built alike is the same list (``set_epoch``; without it the epoch counts up by itself)."""
+
+    def __init__(self, lengths, batch_size, bucket_batches=16, seed=0, drop_last=True, max_frames=None):
+        self.lengths = [min(int(n), int(max_frames)) if max_frames else int(n) for n in lengths]
+        self.batch_size, self.pool = int(batch_size), int(batch_size) * max(int(bucket_batches), 1)
+        self.seed, self.drop_last, self.epoch = int(seed), drop_last, 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def batches(self, epoch):
+        rng = np.random.default_rng([self.seed, int(epoch)])
+        order = [int(i) for i in rng.permutation(len(self.lengths))]
+        out = []
+        for p in range(0, len(order), self.pool):
+            pool = sorted(order[p:p + self.pool], key=lambda i: self.lengths[i])  # (stable: ties keep the shuffled order)
+            out += [pool[k:k + self.batch_size] for k in range(0, len(pool), self.batch_size)]
+        if self.drop_last:
+            out = [b for b in out if len(b) == self.batch_size]
+        return [out[int(i)] for i in rng.permutation(len(out))]
+
+    def __iter__(self):
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        return iter(self.batches(epoch))
+
+    def __len__(self):
+        n = len(self.lengths)
+        if not self.drop_last:
+            return -(-n // self.batch_size)
+        return sum(min(self.pool, n - p) // self.batch_size for p in range(0, n, self.pool))
+
+
+PACKAGE_MODES = ("random_window", "pad")
+
+
 class InversionTrainer:
     """The reference's training step for ``generator_type: BiGRU`` (dataset_mode art / a2m / m2a): the generator half of ``_train_step``
     (train.py:268-383) with ``criterion["mel"] = F.l1_loss`` — forward in train() mode, L1 * lambda_aux, zero_grad, backward, gradient
     clipping, optimizer step, scheduler step.  No discriminator: the reference would start an adversarial phase on the trajectories at
-    discriminator_train_start_steps, which is not built, so a config that reaches it is refused."""
+    discriminator_train_start_steps, which is not built, so a config that reaches it is refused.
+
+    ``package_mode: pad`` (batches of ``PadCollater``: whole utterances with their lengths): the step is ``forward_padded`` ->
+    ``masked_l1_loss`` * lambda_aux, the rest as above; the padding takes no part in statistics, loss or gradients (the reference's pad mode
+    trains on it).  ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval mode, under ``masked_l1_loss``."""
 
     def __init__(self, config, device):
         self.config, self.device = config, device
@@ -577,6 +661,9 @@ class InversionTrainer:
         for flag in ("use_stft_loss", "use_subband_stft_loss", "use_inter_loss", "use_ph_loss", "use_pcd"):
             if config.get(flag, False):
                 raise NotImplementedError(f"{flag} is not built for inversion models (their criterion is F.l1_loss, config key use_mel_loss)")
+        self.package_mode = config.get("package_mode", "random_window")
+        if self.package_mode not in PACKAGE_MODES:
+            raise NotImplementedError(f"package_mode {self.package_mode!r} is not built for inversion models (one of {' / '.join(PACKAGE_MODES)})")
         import articulatory_amd.models as models
 
         self.G = models.BiGRU(**config["generator_params"]).to(device).train()
@@ -592,9 +679,15 @@ class InversionTrainer:
         x = batch["x"].to(self.device, non_blocking=True)
         y = batch["y"].to(self.device, non_blocking=True)
         log = {}
+        if self.package_mode == "pad" and "lengths" not in batch:
+            raise ValueError(f"package_mode pad: the batch has no lengths (batch keys {sorted(batch)}); build it with PadCollater")
         if self.steps > cfg.get("generator_train_start_steps", 0):  # train.py:268
-            y_ = self.G(x)
-            mel_loss = torch.nn.functional.l1_loss(y_, y)  # criterion["mel"] = F.l1_loss (train.py:1706-1709)
+            if self.package_mode == "pad":
+                y_ = self.G.forward_padded(x, batch["lengths"])
+                mel_loss = masked_l1_loss(y_, y, batch["lengths"])
+            else:
+                y_ = self.G(x)
+                mel_loss = torch.nn.functional.l1_loss(y_, y)  # criterion["mel"] = F.l1_loss (train.py:1706-1709)
             gen_loss = mel_loss * cfg.get("lambda_aux", 1.0)
             log["train/mel_loss"] = mel_loss.detach()
             log["train/generator_loss"] = gen_loss.detach()
@@ -609,6 +702,38 @@ class InversionTrainer:
                 self.scheduler["generator"].step()
         self.steps += 1
         return log
+
+    # ------------------------------------------------------------------ evaluation (the GAN Trainer's eval_step / eval_epoch for this model)
+    @torch.no_grad()
+    def eval_step(self, batch):
+        """The masked L1 loss of one dev batch of whole utterances ({"x", "y", "lengths"}) with the model in eval mode: no update."""
+        x = batch["x"].to(self.device, non_blocking=True)
+        y = batch["y"].to(self.device, non_blocking=True)
+        assert not self.G.training, "eval_step runs in eval mode (eval_epoch switches)"
+        mel_loss = masked_l1_loss(self.G(x, lengths=batch["lengths"]), y, batch["lengths"])
+        return {"eval/mel_loss": mel_loss, "eval/generator_loss": mel_loss * self.config.get("lambda_aux", 1.0)}
+
+    def eval_epoch(self, loader, outdir=None):
+        """Average dev losses; the best ``eval/mel_loss`` so far keeps ``best_mel_ckpt.pkl`` / ``best_mel_step.txt``, as Trainer.eval_epoch."""
+        self.G.eval()
+        totals, n = defaultdict(float), 0
+        try:
+            for batch in loader:
+                for k, v in self.eval_step(batch).items():
+                    totals[k] += float(v)
+                n += 1
+        finally:
+            self.G.train()
+        if n == 0:
+            return {}
+        avg = {k: v / n for k, v in totals.items()}
+        if outdir is not None and avg["eval/mel_loss"] < getattr(self, "best_mel_loss", float("inf")):
+            self.best_mel_loss = avg["eval/mel_loss"]
+            os.makedirs(outdir, exist_ok=True)
+            with open(os.path.join(outdir, "best_mel_step.txt"), "w+") as f:
+                f.write("%d\n" % self.steps)
+            self.save_checkpoint(os.path.join(outdir, "best_mel_ckpt.pkl"))
+        return avg
 
     # ------------------------------------------------------------------ checkpoints (train.py:140-238: the reference's dict layout)
     def save_checkpoint(self, path):
@@ -637,22 +762,41 @@ class InversionTrainer:
 
 def _main_inversion(a, config, device, rank):
     """``main`` for generator_type BiGRU: input / target ``.npy`` scp pairs (--feats-scp: the model's input side, --audio-scp: its target
-    side; dataset_mode m2a swaps them) or --synthetic N, cut into equal windows of batch_max_frames + 2 aux_context_window frames."""
+    side; dataset_mode m2a swaps them) or --synthetic N, cut into equal windows of batch_max_frames + 2 aux_context_window frames
+    (package_mode random_window, the default) or taken whole in length-bucketed, zero-padded batches (package_mode pad; config keys
+    pad_max_frames, pad_bucket_batches; --synthetic then draws each utterance's length uniformly from one to four windows).
+    --dev-feats-scp / --dev-audio-scp: a dev set, evaluated whole every eval_interval_steps in either mode."""
     gp = config["generator_params"]
     hop = int(config.get("hop_size", 1))
     ctx = int(config.get("aux_context_window", gp.get("aux_context_window", 0)))
     frames = config["batch_max_steps"] // hop  # CollaterMelArt: batch_max_frames
     window = frames + 2 * ctx
+    pad = config.get("package_mode", "random_window") == "pad"
+    swap = config.get("dataset_mode") == "m2a"
     if a.synthetic:
-        data = WindowPairs(synthetic=a.synthetic, frames=4 * window, dims=(gp.get("in_channels", 80), gp.get("out_channels", 1)), seed=rank)
+        data = WindowPairs(synthetic=a.synthetic, frames=4 * window, dims=(gp.get("in_channels", 80), gp.get("out_channels", 1)), seed=rank,
+                           frames_range=(window, 4 * window) if pad else None)
     else:
         if not (a.audio_scp and a.feats_scp):
             raise SystemExit("generator_type BiGRU: give --feats-scp (input frames) and --audio-scp (target frames) of .npy files, or --synthetic N")
-        data = WindowPairs(a.feats_scp, a.audio_scp, min_frames=window, swap=config.get("dataset_mode") == "m2a")
-    loader = torch.utils.data.DataLoader(data, batch_size=config["batch_size"], shuffle=True, drop_last=True,
-                                         collate_fn=FrameWindowCollater(frames, ctx, seed=1234 + rank), num_workers=config.get("num_workers", 0))
+        data = WindowPairs(a.feats_scp, a.audio_scp, min_frames=0 if pad else window, swap=swap)
+    sampler = None
+    if pad:
+        sampler = LengthBucketBatchSampler([len(it[0]) for it in data.items], config["batch_size"], config.get("pad_bucket_batches", 16), seed=1234 + rank,
+                                           max_frames=config.get("pad_max_frames"))
+        loader = torch.utils.data.DataLoader(data, batch_sampler=sampler, collate_fn=PadCollater(config.get("pad_max_frames"), seed=1234 + rank),
+                                             num_workers=config.get("num_workers", 0))
+    else:
+        loader = torch.utils.data.DataLoader(data, batch_size=config["batch_size"], shuffle=True, drop_last=True,
+                                             collate_fn=FrameWindowCollater(frames, ctx, seed=1234 + rank), num_workers=config.get("num_workers", 0))
     if len(loader) == 0:
         raise SystemExit(f"fewer utterances ({len(data)}) than one batch ({config['batch_size']})")
+    dev_loader = None
+    if bool(a.dev_feats_scp) != bool(a.dev_audio_scp):
+        raise SystemExit("give both --dev-feats-scp and --dev-audio-scp, or neither")
+    if a.dev_feats_scp and rank == 0:  # whole utterances in file order, in either package mode
+        dev = WindowPairs(a.dev_feats_scp, a.dev_audio_scp, min_frames=0, swap=swap)
+        dev_loader = torch.utils.data.DataLoader(dev, batch_size=config["batch_size"], shuffle=False, drop_last=False, collate_fn=PadCollater())
     if a.max_steps is not None:  # the refusal of a reachable adversarial phase looks at the steps this run will take
         config = dict(config, train_max_steps=a.max_steps)
     trainer = InversionTrainer(config, device)
@@ -661,17 +805,28 @@ def _main_inversion(a, config, device, rank):
         logging.info(f"Successfully resumed from {a.resume}.")
     max_steps = config["train_max_steps"]
     t0, n0, pending = time.time(), trainer.steps, []
+    valid_frames = all_frames = 0
     while trainer.steps < max_steps:
+        if sampler is not None:
+            sampler.set_epoch(trainer.epochs)
         for batch in loader:
             pending.append(trainer.train_step(batch))
+            if pad:
+                valid_frames += int(batch["lengths"].sum())
+                all_frames += batch["x"].shape[0] * batch["x"].shape[2]
             n = config.get("log_interval_steps", 100)
             if trainer.steps % n == 0 or trainer.steps >= max_steps:
                 for log in pending:
                     for k, v in log.items():
                         trainer.total_train_loss[k] += float(v)
                 logging.info(f"(Steps: {trainer.steps}) " + ", ".join(f"{k} = {v / max(len(pending), 1):.4f}" for k, v in sorted(trainer.total_train_loss.items()))
+                             + (f", padded frames = {1.0 - valid_frames / max(all_frames, 1):.1%}" if pad else "")
                              + f", {(time.time() - t0) / max(trainer.steps - n0, 1) * 1e3:.1f} ms/step")
                 pending, trainer.total_train_loss = [], defaultdict(float)
+                valid_frames = all_frames = 0
+            if dev_loader is not None and trainer.steps % config.get("eval_interval_steps", 10 ** 9) == 0:
+                avg = trainer.eval_epoch(dev_loader, a.outdir)
+                logging.info(f"(Steps: {trainer.steps}) " + ", ".join(f"{k} = {v:.4f}" for k, v in sorted(avg.items())))
             if trainer.steps % config.get("save_interval_steps", 10 ** 9) == 0:
                 trainer.save_checkpoint(os.path.join(a.outdir, f"checkpoint-{trainer.steps}steps.pkl"))
             if trainer.steps >= max_steps:
@@ -699,6 +854,8 @@ def main(argv=None):
     ap.add_argument("--feats-scp")
     ap.add_argument("--train-dumpdir", help="dump directory of <utt>.h5 (wave + feats) or <utt>-wave.npy / <utt>-feats.npy files (config: format)")
     ap.add_argument("--dev-dumpdir", help="dev-set dump directory: evaluated every eval_interval_steps (rank 0)")
+    ap.add_argument("--dev-feats-scp", help="generator_type BiGRU: the dev set's input frames (.npy scp), evaluated whole every eval_interval_steps")
+    ap.add_argument("--dev-audio-scp", help="generator_type BiGRU: the dev set's target frames (.npy scp)")
     ap.add_argument("--synthetic", type=int, default=0, help="train on this many random utterances instead of a dataset")
     ap.add_argument("--utt2spk", help="'utt spk' lines (use_spk_id: speaker ids are ranks in the sorted speaker list)")
     ap.add_argument("--ph-scp", help="'utt path.npy' lines: one phoneme index per feature frame (use_ph / use_ph_loss)")

@@ -5,7 +5,9 @@
 //   backward  head (tanh', dW_fc2, db_fc2) -> batch norm + dropout -> fc1 (dW, db, dY2) -> [dropout mask -> backward sweep -> dW_ih, db_ih,
 //             dW_hh, db_hh, dX] x 2 -> dx
 // The GEMMs are the conv engine's one-tap launches (forward and data gradients) and the weight-gradient kernels of hificar_train.hip.inc.
-// Equal-length batches only.  Kernels: hificar_bigru_train_kernels.hip.h.
+// Ragged batches (hificar_bigru_forward_train_ragged): every sequence is swept over its own frame count, the batch statistics and every
+// gradient take the valid frames only; the GEMMs still run over all B T rows, and zeros in the padded rows of their operands mask them.
+// Kernels: hificar_bigru_train_kernels.hip.h.
 
 struct BigruTrain {
     struct Slot {
@@ -258,6 +260,9 @@ extern "C" int hificar_bigru_set_parameters_device(hificar_bigru* g, const char*
 // ------------------------------------------------------------------------------------------------
 static size_t bigru_train_rows(int B, int T) { return round_up_sz((size_t)B * (size_t)T + 64, 256); }  // slack behind the last row for whole GEMM tiles
 
+// bigru_train_rows leaves at least 64 slack rows of 8H >= 512 floats behind a layer's gate values: room for this many frame counts
+constexpr int kBigruRaggedMaxB = 32768;
+
 struct BigruTape {
     BigruTapeHeader* hdr;
     float* x0;       // [rows][cin_pad] input rows
@@ -266,6 +271,8 @@ struct BigruTape {
     float* f1;       // [rows][128] raw fc1
     float* stats;    // [3][128]
     float* out;      // (B, O, T)
+    int* lens;       // [B] frame counts of a ragged forward (the header says whether they hold): in the slack rows behind the first layer's
+                     // gate values, which no kernel reads or writes (the tape's size is that of a dense one); a tape-less forward: a piece of its own
     size_t bytes;
 };
 
@@ -286,6 +293,7 @@ static BigruTape bigru_plan_tape(const hificar_bigru* g, int B, int T, void* bas
     t.f1 = reinterpret_cast<float*>(take(rows * kBigruFc1 * 4));
     t.stats = reinterpret_cast<float*>(take(3 * kBigruFc1 * 4));
     t.out = reinterpret_cast<float*>(take((size_t)B * T * g->cfg.out_channels * 4));
+    t.lens = with_gates ? reinterpret_cast<int*>(t.gates[0] + (base ? (size_t)B * T * 8 * H : 0)) : reinterpret_cast<int*>(take((size_t)B * 4));
     t.bytes = off;
     return t;
 }
@@ -391,6 +399,7 @@ static void bigru_head_params(const hificar_bigru* g, const BigruTape& tp, int B
     p.w2 = ts->d_master + ts->offset.at(bigru_fc2_name(g) + ".weight");
     p.b2 = ts->d_master + ts->offset.at(bigru_fc2_name(g) + ".bias");
     p.hdr = tp.hdr;
+    p.lens = tp.lens;
     p.out_keep = tp.out;
     p.B = B;
     p.T = T;
@@ -402,12 +411,12 @@ static void bigru_head_params(const hificar_bigru* g, const BigruTape& tp, int B
 // training forwards), batch norm on this batch's statistics, which come back in bn_batch_stats (mean | biased variance, 2 x 128 floats on the
 // device).  Everything the backward pass needs stays in `tape` (hificar_bigru_tape_bytes), owned by the caller until hificar_bigru_backward ran.
 // tape = NULL: the same arithmetic without a tape (no gate values are written; the rows live in the workspace): no backward pass can follow.
-extern "C" int hificar_bigru_forward_train(hificar_bigru* g, const float* x, float* out, float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed,
-                                           uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
-    int rc = bigru_train_check(g, "hificar_bigru_forward_train", B, T, tape, tape_bytes, workspace, workspace_bytes, true);
-    if (rc != HIFICAR_OK) return rc;
-    if (!x || !out || !bn_batch_stats) return fail(HIFICAR_E_INVALID, "hificar_bigru_forward_train: null tensor");
-    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HIFICAR_E_INVALID, "hificar_bigru_forward_train: dropout_p=%g outside [0, 1)", (double)dropout_p);
+// lengths = null: the dense form.  Otherwise B frame counts on the device and their sum (checked by the caller): the ragged form.
+static int bigru_forward_train_impl(hificar_bigru* g, const char* what, const float* x, const int* lengths, int valid, float* out, float* bn_batch_stats, int B,
+                                    int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape, void* workspace, void* stream_) {
+    if (!x || !out || !bn_batch_stats) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HIFICAR_E_INVALID, "%s: dropout_p=%g outside [0, 1)", what, (double)dropout_p);
+    int rc;
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
@@ -415,22 +424,35 @@ extern "C" int hificar_bigru_forward_train(hificar_bigru* g, const float* x, flo
     const BigruTrainWs ws = bigru_plan_train_ws(g, B, T, workspace);
     const BigruTape tp = tape ? bigru_plan_tape(g, B, T, tape) : bigru_plan_tape(g, B, T, ws.light, false);
     const int H = g->cfg.hidden_size, C = g->cfg.in_channels, O = g->cfg.out_channels, M = B * T;
-    hipLaunchKernelGGL(bigru_header_kernel, dim3(1), dim3(1), 0, stream, tp.hdr, (unsigned long long)seed, (unsigned long long)offset, dropout_p, B, T);
+    hipLaunchKernelGGL(bigru_header_kernel, dim3(1), dim3(1), 0, stream, tp.hdr, (unsigned long long)seed, (unsigned long long)offset, dropout_p, B, T,
+                       lengths ? valid : M, lengths ? 1 : 0);
     HIP_TRY(hipGetLastError());
+    if (lengths) HIP_TRY(hipMemcpyAsync(tp.lens, lengths, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    // the frames a ragged sweep does not write are operands of the GEMMs behind it (0 * NaN is NaN): zeros, written by this call
+    auto zero_pad = [&](float* rows, int width) -> int {
+        if (!lengths) return HIFICAR_OK;
+        ProfScope prof(h, stream, "bigru_zero_pad_kernel", 0.0, 4.0 * (M - valid) * width);
+        hipLaunchKernelGGL(bigru_zero_pad_kernel, dim3((unsigned)std::min<long long>(((long long)T * (width / 4) + 255) / 256, 8), (unsigned)B), dim3(256), 0,
+                           stream, rows, width, tp.lens, T);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    };
     {
         ProfScope prof(h, stream, "bigru_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
         hipLaunchKernelGGL(bigru_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, tp.x0, C,
                            g->cin_pad, T);
         HIP_TRY(hipGetLastError());
     }
+    if ((rc = zero_pad(tp.x0, g->cin_pad)) != HIFICAR_OK) return rc;
     const int NS = bigru_tile_height(g, B);
     for (int l = 0; l < 2; ++l) {
         if ((rc = bigru_gemm(h, g->proj[l], l == 0 ? tp.x0 : ws.a, ws.gx, M, stream)) != HIFICAR_OK) return rc;
+        if ((rc = zero_pad(tp.y[l], 2 * H)) != HIFICAR_OK) return rc;  // (the sweep writes the other rows: no order between the two)
         BigruRecParams p;
         p.g = ws.gx;
         p.w = g->d_whh[l];
         p.bhh = g->d_bhh[l];
-        p.lengths = nullptr;
+        p.lengths = lengths ? tp.lens : nullptr;  // (the gate values of padded rows are never written and never read)
         p.y = tp.y[l];
         p.B = B;
         p.T = T;
@@ -446,7 +468,7 @@ extern "C" int hificar_bigru_forward_train(hificar_bigru* g, const float* x, flo
     if ((rc = bigru_gemm(h, ts->fc1_raw, ws.a, tp.f1, M, stream)) != HIFICAR_OK) return rc;
     {
         ProfScope prof(h, stream, "bigru_bn_stats_kernel", 0.0, 8.0 * M * kBigruFc1);
-        hipLaunchKernelGGL(bigru_bn_stats_kernel, dim3(kBigruFc1 / 32), dim3(1024), 0, stream, tp.f1, M, tp.hdr, tp.stats, bn_batch_stats);
+        hipLaunchKernelGGL(bigru_bn_stats_kernel, dim3(kBigruFc1 / 32), dim3(1024), 0, stream, tp.f1, M, tp.hdr, tp.lens, tp.stats, bn_batch_stats);
         HIP_TRY(hipGetLastError());
     }
     {
@@ -460,8 +482,40 @@ extern "C" int hificar_bigru_forward_train(hificar_bigru* g, const float* x, flo
     return HIFICAR_OK;
 }
 
+extern "C" int hificar_bigru_forward_train(hificar_bigru* g, const float* x, float* out, float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed,
+                                           uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
+    const int rc = bigru_train_check(g, "hificar_bigru_forward_train", B, T, tape, tape_bytes, workspace, workspace_bytes, true);
+    if (rc != HIFICAR_OK) return rc;
+    return bigru_forward_train_impl(g, "hificar_bigru_forward_train", x, nullptr, B * T, out, bn_batch_stats, B, T, dropout_p, seed, offset, tape, workspace,
+                                    stream_);
+}
+
+// The same step on a ragged batch: sequence b has lengths[b] (0 .. T) frames of x (B, in_channels, T); what x holds past them is not used.
+// Each sequence is swept over its own frames (the reverse direction starts at its own last one), the batch statistics are taken over the
+// M = sum of lengths valid frames (M >= 2), out is zero past a length.  The dropout masks are those of the padded (B, T, C) tensor.  The tape
+// keeps the lengths and M: hificar_bigru_backward on it ignores dout past a length, writes dx = 0 there and sums valid frames only.
+// lengths: device int32[B]; lengths_host: the same values on the host (required: checked before anything is enqueued).
+// All lengths = T: every result is bitwise that of hificar_bigru_forward_train.
+extern "C" int hificar_bigru_forward_train_ragged(hificar_bigru* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out,
+                                                  float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape,
+                                                  size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hificar_bigru_forward_train_ragged";
+    const int rc = bigru_train_check(g, what, B, T, tape, tape_bytes, workspace, workspace_bytes, true);
+    if (rc != HIFICAR_OK) return rc;
+    if (!lengths || !lengths_host) return fail(HIFICAR_E_INVALID, "%s: lengths and lengths_host are both required", what);
+    if (B > kBigruRaggedMaxB) return fail(HIFICAR_E_INVALID, "%s: B=%d above %d (what the tape's slack rows hold of lengths)", what, B, kBigruRaggedMaxB);
+    long long valid = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths_host[b] < 0 || lengths_host[b] > T) return fail(HIFICAR_E_INVALID, "%s: lengths[%d]=%d outside [0, %d]", what, b, (int)lengths_host[b], T);
+        valid += lengths_host[b];
+    }
+    if (valid < 2) return fail(HIFICAR_E_INVALID, "%s: batch statistics need more than one valid frame (sum of lengths = %lld)", what, valid);
+    return bigru_forward_train_impl(g, what, x, lengths, (int)valid, out, bn_batch_stats, B, T, dropout_p, seed, offset, tape, workspace, stream_);
+}
+
 // dout (B, O, T) -> the gradient of every parameter in `grads` (hificar_bigru_grad_floats floats, laid out as hificar_bigru_grad_info says;
-// written, not accumulated) and, with dx non-null, of the input (B, in_channels, T).
+// written, not accumulated) and, with dx non-null, of the input (B, in_channels, T).  The tape says whether its forward was ragged and with
+// which lengths: then dout past a length is not read, dx is zero there and every gradient sums valid frames only.
 extern "C" int hificar_bigru_backward(hificar_bigru* g, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
                                       void* workspace, size_t workspace_bytes, void* stream_) {
     int rc = bigru_train_check(g, "hificar_bigru_backward", B, T, const_cast<void*>(tape), tape_bytes, workspace, workspace_bytes);
@@ -504,9 +558,10 @@ extern "C" int hificar_bigru_backward(hificar_bigru* g, const float* dout, int B
     {   // batch norm (batch statistics) and the dropout in front of it
         const float* gamma = ts->d_master + ts->offset.at("bn.weight");
         ProfScope prof(h, stream, "bigru_bn_bwd_kernels", 0.0, 20.0 * M * kBigruFc1);
-        hipLaunchKernelGGL(bigru_bn_bwd_sums_kernel, dim3(kBigruFc1 / 32), dim3(1024), 0, stream, tp.f1, ws.dbn, M, tp.hdr, tp.stats, G("bn.weight"), G("bn.bias"));
+        hipLaunchKernelGGL(bigru_bn_bwd_sums_kernel, dim3(kBigruFc1 / 32), dim3(1024), 0, stream, tp.f1, ws.dbn, M, tp.hdr, tp.lens, tp.stats, G("bn.weight"),
+                           G("bn.bias"));
         hipLaunchKernelGGL(bigru_bn_bwd_dx_kernel, dim3((unsigned)std::min<size_t>(((size_t)M * kBigruFc1 + 255) / 256, 4096)), dim3(256), 0, stream, tp.f1, ws.dbn,
-                           M, tp.hdr, tp.stats, gamma, G("bn.weight"), G("bn.bias"));
+                           M, tp.hdr, tp.lens, tp.stats, gamma, G("bn.weight"), G("bn.bias"));
         HIP_TRY(hipGetLastError());
     }
     // fc1: its input was dropout(y2)
@@ -526,6 +581,8 @@ extern "C" int hificar_bigru_backward(hificar_bigru* g, const float* dout, int B
         p.dgh = ws.gh;
         p.B = B;
         p.T = T;
+        p.hdr = tp.hdr;
+        p.lens = tp.lens;
         {
             ProfScope prof(h, stream, "bigru_rec_bwd_kernel", 2.0 * M * 2 * 3 * H * H, 4.0 * M * 26 * H);
             const hipError_t e = HIFICAR_BIGRU_BY_SHAPE(bigru_rec_bwd_launch_one, H, NS, p, stream);
@@ -534,7 +591,7 @@ extern "C" int hificar_bigru_backward(hificar_bigru* g, const float* dout, int B
         {
             const long long n4 = (long long)M * 2 * H / 4;
             ProfScope prof(h, stream, "bigru_hprev_kernel", 0.0, 16.0 * M * H);
-            hipLaunchKernelGGL(bigru_hprev_kernel, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 4096)), dim3(256), 0, stream, tp.y[l], ws.b, H, T, n4);
+            hipLaunchKernelGGL(bigru_hprev_kernel, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 4096)), dim3(256), 0, stream, tp.y[l], ws.b, H, T, n4, tp.hdr, tp.lens);
             HIP_TRY(hipGetLastError());
         }
         for (int dir = 0; dir < 2; ++dir)  // dW_hh = dGH^T H_prev, db_hh: one direction's (3H, H) block at a time
@@ -552,6 +609,7 @@ extern "C" int hificar_bigru_backward(hificar_bigru* g, const float* dout, int B
         if (l == 1) {
             if ((rc = bigru_gemm(h, ts->dg_proj[1], ws.gx, ws.a, M, stream)) != HIFICAR_OK) return rc;  // d(dropout(y1))
         } else if (dx) {
+            // (ragged: the padded rows of dgx are zeros, so those of dxr are sums of 0 * w: zeros, and bigru_unrows_kernel needs no mask)
             if ((rc = bigru_gemm(h, ts->dg_proj[0], ws.gx, ws.dxr, M, stream)) != HIFICAR_OK) return rc;
             ProfScope prof(h, stream, "bigru_unrows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
             hipLaunchKernelGGL(bigru_unrows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, ws.dxr, dx, C,

@@ -56,6 +56,22 @@ def feature_match_loss(feats_hat, feats, average_by_layers=True, average_by_disc
     return total / (i + 1) if average_by_discriminators else total
 
 
+def masked_l1_loss(y_hat, y, lengths):
+    """L1 loss of a zero-padded batch of whole utterances (``BiGRU.forward_padded``): the sum of |y_hat - y| over the valid frames
+    t < lengths[b] of (B, C, T) tensors, divided by M C with M = sum(lengths).  Padded frames enter neither the value nor the gradient,
+    whatever they hold.  With every length equal to T it is ``F.l1_loss``'s mean (up to the rounding of the summation order)."""
+    if y_hat.dim() != 3 or y_hat.shape != y.shape:
+        raise RuntimeError(f"masked_l1_loss: expected two (B, C, T) tensors of one shape, got {tuple(y_hat.shape)} and {tuple(y.shape)}")
+    B, C, T = y_hat.shape
+    lens = torch.as_tensor(lengths).reshape(-1)
+    if lens.numel() != B:
+        raise RuntimeError(f"lengths has {lens.numel()} entries for a batch of {B}")
+    lens = lens.to(device=y_hat.device, dtype=torch.long).clamp(0, T)
+    valid = (torch.arange(T, device=y_hat.device)[None, :] < lens[:, None])[:, None, :]
+    diff = torch.where(valid, y_hat - y, torch.zeros((), dtype=y_hat.dtype, device=y_hat.device))  # (a NaN in the padding stops here)
+    return diff.abs().sum() / (lens.sum() * C).to(y_hat.dtype)
+
+
 # ------------------------------------------------------------------------------------------------
 # Mel-spectrogram loss (mel_loss.py:114-166) on libhificar: value and gradient in one native call
 # ------------------------------------------------------------------------------------------------

@@ -13,7 +13,9 @@ package's own counter-based generator (``set_dropout_seed``; numpy restatement: 
 
 Not built, refused with ``NotImplementedError``: ``use_ar`` (the reference's own driver for it is broken: predict_ema.py:92 passes a
 keyword ``ar_loop`` does not take) and ``use_spk_emb``.  ``lengths=`` is this package's addition for eval mode: a ragged batch in which
-every utterance's result is that of running it alone (training takes equal-length batches, as the reference's collater makes them).
+every utterance's result is that of running it alone.  ``forward`` in train() mode takes equal-length batches, as the reference's collater
+makes them; ``forward_padded(mels, lengths)`` trains on whole utterances of unequal lengths (this package's definition, the reference never
+masks: each sequence swept over its own frames, batch statistics, loss and gradients over the valid frames only).
 """
 
 import ctypes
@@ -79,11 +81,12 @@ def _grad_layout(module):
 class _BiGRUFunction(torch.autograd.Function):
     """Autograd node of the native BiGRU in train() mode: forward = hificar_bigru_forward_train (keeps a tape), backward =
     hificar_bigru_backward.  Inputs after (module, x, p, seed, offset, names) are the module's parameters in ``names`` order.  Returns
-    (out, batch statistics (2, 128): mean | biased variance of the batch norm's input); the statistics carry no gradient."""
+    (out, batch statistics (2, 128): mean | biased variance of the batch norm's input); the statistics carry no gradient.  ``module._lens``
+    (None, or the (host, device) int32 lengths of a ragged batch) is read at forward time; the tape keeps the lengths for the backward."""
 
     @staticmethod
     def forward(ctx, module, x, p, seed, offset, names, *params):
-        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True)
+        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True, lens=module._lens)
         B, _, T = x.shape
         ctx.module, ctx.names, ctx.tape, ctx.toff, ctx.BT = module, names, tape, toff, (B, T)
         ctx.save_for_backward(*params)  # torch's own version check covers an in-place edit that bumps Parameter._version ...
@@ -147,6 +150,7 @@ class BiGRU(torch.nn.Module):
         self._dirty = False      # an optimizer stepped since the last hand-over (fused optimizers do not bump Parameter._version)
         self._steps_seen = 0     # optimizer steps noticed so far
         self._calls = 0          # training forwards so far: the dropout generator's offset
+        self._lens = None        # the lengths of the ragged training forward under way (forward_padded)
         # drawn from torch's generator (after the parameters): torch.manual_seed makes a training run repeatable
         self._dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         from ..utils.optim_hook import watch
@@ -326,8 +330,9 @@ class BiGRU(torch.nn.Module):
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
 
-    def _run_forward_train(self, x, p, seed, offset, keep_tape):
-        """hificar_bigru_forward_train on the current stream: (out, batch statistics, tape or None, the tape's alignment offset)."""
+    def _run_forward_train(self, x, p, seed, offset, keep_tape, lens=None):
+        """hificar_bigru_forward_train (lens = (host, device) int32 lengths: hificar_bigru_forward_train_ragged) on the current stream: (out,
+        batch statistics, tape or None, the tape's alignment offset)."""
         lib, handle = self._lib, self._handle
         B, _, T = x.shape
         dev = x.device
@@ -340,10 +345,14 @@ class BiGRU(torch.nn.Module):
             out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=dev)
             stats = torch.empty((2, FC1_DIM), dtype=torch.float32, device=dev)
             ws_ptr, ws_bytes = self._train_workspace(B, T)
-            rc = lib.hificar_bigru_forward_train(handle, x.data_ptr(), out.data_ptr(), stats.data_ptr(), B, T, float(p), seed, offset,
-                                                 tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
-                                                 ws_ptr, ws_bytes, stream)
-        _native.check(rc, "hificar_bigru_forward_train")
+            tail = (B, T, float(p), seed, offset, tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
+                    ws_ptr, ws_bytes, stream)
+            if lens is None:
+                rc = lib.hificar_bigru_forward_train(handle, x.data_ptr(), out.data_ptr(), stats.data_ptr(), *tail)
+            else:
+                rc = lib.hificar_bigru_forward_train_ragged(handle, x.data_ptr(), lens[1].data_ptr(), lens[0].data_ptr(), out.data_ptr(),
+                                                            stats.data_ptr(), *tail)
+        _native.check(rc, "hificar_bigru_forward_train" if lens is None else "hificar_bigru_forward_train_ragged")
         return out, stats, tape, toff
 
     def _workspace(self, B, T):
@@ -384,13 +393,7 @@ class BiGRU(torch.nn.Module):
         lens = (None, None)
         keep = None
         if lengths is not None:
-            host = (lengths.detach().to("cpu", torch.int32) if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths, dtype=torch.int32))
-            host = host.reshape(-1).contiguous()
-            if host.numel() != B:
-                raise RuntimeError(f"lengths has {host.numel()} entries for a batch of {B}")
-            if int(host.min()) < 0 or int(host.max()) > T:
-                raise RuntimeError(f"lengths must lie in [0, {T}]")
-            keep = (host, host.to(c.device).contiguous())
+            keep = self._check_lengths(lengths, B, T, c.device)
             lens = (keep[1].data_ptr(), keep[0].data_ptr())
         out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=c.device)
         with torch.cuda.device(c.device):
@@ -401,13 +404,40 @@ class BiGRU(torch.nn.Module):
         _native.check(rc, "hificar_bigru_forward")
         return out
 
-    def _forward_train(self, mels, lengths):
+    @staticmethod
+    def _check_lengths(lengths, B, T, device):
+        """(host int32 tensor, its copy on ``device``) of B frame counts in 0 .. T."""
+        host = (lengths.detach().to("cpu", torch.int32) if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths, dtype=torch.int32))
+        host = host.reshape(-1).contiguous()
+        if host.numel() != B:
+            raise RuntimeError(f"lengths has {host.numel()} entries for a batch of {B}")
+        if int(host.min()) < 0 or int(host.max()) > T:
+            raise RuntimeError(f"lengths must lie in [0, {T}]")
+        return host, host.to(device).contiguous()
+
+    def forward_padded(self, mels, lengths):
+        """A batch of whole utterances, zero-padded to (B, in_channels, T), with their frame counts ``lengths`` (B values in 0 .. T).
+        eval(): ``forward(mels, lengths=lengths)``.  train(): the training step on the ragged batch, under autograd — this package's
+        definition, the reference never masks: sequence b is swept over its own lengths[b] frames (the reverse direction from its own last
+        frame), dropout masks are those of the padded tensors (they depend on T), the batch norm takes mean and biased variance over the
+        M = sum(lengths) valid frames (running variance: M / (M - 1)), ``out[b, :, lengths[b]:]`` is exactly zero; backwards, the output
+        gradient on padded frames is ignored whatever it holds, the input gradient is zero there, and every parameter gradient sums valid
+        frames only.  With every length equal to T all results are bitwise those of ``forward``.  What ``mels`` holds in padded frames is
+        never used."""
+        if not self.training:
+            return self.forward(mels, lengths=lengths)
+        if lengths is None:
+            raise RuntimeError("BiGRU.forward_padded needs lengths")
+        return self._forward_train(mels, lengths, padded=True)
+
+    def _forward_train(self, mels, lengths, padded=False):
         """train() mode (pytorch_models.py:45-72 with its three nn.Dropout active and the batch norm on batch statistics): with grad enabled
         the output is part of the autograd graph; without, the same arithmetic runs and its tape is dropped.  Every call — either way —
         advances the dropout generator's offset and updates bn.running_mean / running_var / num_batches_tracked as torch.nn.BatchNorm1d does."""
-        if lengths is not None:
-            raise NotImplementedError("BiGRU.forward(lengths=...) in train() mode is not built: training takes equal-length batches "
-                                      "(the reference's collater cuts equal windows); call .eval() for ragged batches")
+        if lengths is not None and not padded:
+            raise NotImplementedError("BiGRU.forward(lengths=...) in train() mode is refused: masked batch statistics are this package's "
+                                      "definition, not the reference's, so asking for them is explicit: call forward_padded(mels, lengths) "
+                                      "to train on a ragged batch (or .eval() for ragged inference)")
         if not isinstance(mels, torch.Tensor) or mels.device.type != "cuda":
             raise NotImplementedError("BiGRU.forward in train() mode needs a CUDA/HIP tensor: the training path only exists as HIP kernels "
                                       "(there is no CPU fallback)")
@@ -416,8 +446,13 @@ class BiGRU(torch.nn.Module):
         B, _, T = mels.shape
         if B < 1 or T < 1:
             raise RuntimeError(f"BiGRU.forward: empty input {tuple(mels.shape)}")
-        if B * T == 1:  # torch.nn.functional.batch_norm's own refusal
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, FC1_DIM, T]}")
+        n = B * T
+        lens = None
+        if padded:
+            lens = self._check_lengths(lengths, B, T, mels.device)
+            n = int(lens[0].sum())
+        if n < 2:  # torch.nn.functional.batch_norm's own refusal
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, FC1_DIM, T] if lens is None else [n, FC1_DIM]}")
         self._native_handle(train=True)
         if mels.device != self._device():
             raise RuntimeError(f"BiGRU.forward: input on {mels.device}, parameters on {self._device()}")
@@ -426,12 +461,15 @@ class BiGRU(torch.nn.Module):
         names, params = tuple(n for n, _ in named), [p for _, p in named]
         offset = self._calls
         self._calls += 1
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            out, stats = _BiGRUFunction.apply(self, x, self._params["dropout"], self._dropout_seed, offset, names, *params)
-        else:  # no graph: the same arithmetic without a tape (tape = NULL)
-            out, stats, _, _ = self._run_forward_train(x.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False)
-        with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance
-            n = B * T
+        self._lens = lens
+        try:
+            if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+                out, stats = _BiGRUFunction.apply(self, x, self._params["dropout"], self._dropout_seed, offset, names, *params)
+            else:  # no graph: the same arithmetic without a tape (tape = NULL)
+                out, stats, _, _ = self._run_forward_train(x.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False, lens=lens)
+        finally:
+            self._lens = None
+        with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance (n: the valid frames)
             self.bn.running_mean.mul_(0.9).add_(stats[0], alpha=0.1)
             self.bn.running_var.mul_(0.9).add_(stats[1], alpha=0.1 * n / (n - 1))
             self.bn.num_batches_tracked += 1

@@ -556,8 +556,10 @@ void hificar_bigru_destroy(hificar_bigru* h);
 
 /* ---- BiGRU training: the reference's step for dataset_mode art / a2m / m2a (articulatory/bin/train.py:241-383), the model in train() mode:
  * Dropout(p) behind each GRU layer and fc1, BatchNorm1d on batch statistics.  Exact fp32, deterministic (fixed-order reductions).
- * Equal-length batches only (the reference's CollaterMelArt cuts equal windows): there is no `lengths` here.  All of these may be called
- * after hificar_bigru_finalize; the first one builds the training state. ---- */
+ * hificar_bigru_forward_train takes equal-length batches (the reference's CollaterMelArt cuts equal windows);
+ * hificar_bigru_forward_train_ragged takes whole utterances of unequal lengths (this library's definition: the reference never masks).
+ * All of these may be called after hificar_bigru_finalize; the first one builds the training state.
+ * Not built: multi-GPU BiGRU training, packed (padding-free) GEMMs for ragged batches, use_ar, use_spk_emb. ---- */
 
 /* Every float tensor of the state_dict (reference names and layouts, bn.running_mean / bn.running_var included; n = all of them, each
  * once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs, W_hh and
@@ -572,7 +574,8 @@ int hificar_bigru_grad_info(hificar_bigru* h, int i, char* name96, int64_t* offs
 int64_t hificar_bigru_grad_floats(hificar_bigru* h);
 
 /* Bytes of the tape (what a training forward keeps for its backward pass: the input rows, both layers' hidden states and per-step gate
- * values r, z, n, W_hn h + b_hn, the raw fc1 rows, the batch statistics, the output; dropout masks are regenerated, not stored) and of
+ * values r, z, n, W_hn h + b_hn, the raw fc1 rows, the batch statistics, the output, a ragged forward's lengths (in rows a dense tape
+ * leaves unused: both forms take the same size) and their sum; dropout masks are regenerated, not stored) and of
  * the scratch shared by hificar_bigru_forward_train and hificar_bigru_backward. */
 size_t hificar_bigru_tape_bytes(const hificar_bigru* h, int B, int T);
 size_t hificar_bigru_train_workspace_bytes(hificar_bigru* h, int B, int T);
@@ -587,8 +590,26 @@ size_t hificar_bigru_train_workspace_bytes(hificar_bigru* h, int B, int T);
 int hificar_bigru_forward_train(hificar_bigru* h, const float* x, float* out, float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed,
                                 uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same step on a ragged batch of whole utterances: sequence b has lengths[b] frames (0 .. T; M = their sum >= 2) of x (B, in_channels, T);
+ * what x holds past them is never used (NaN included).
+ *   GRU layers   sequence b is swept over its own lengths[b] frames; the reverse direction starts at its own last frame (as
+ *                hificar_bigru_forward does in eval mode)
+ *   dropout      element e is the index in the PADDED (B, T, C) tensor, as above: the masks depend on T, not only on the lengths
+ *   batch norm   mean and biased variance over the M valid rows; bn_batch_stats as above (the caller's running variance takes M / (M - 1))
+ *   out          out[b, :, lengths[b]:] is exactly zero
+ * lengths: device int32[B], B <= 32768.  lengths_host: the same values on the host, required: each is checked against 0 .. T and their sum against >= 2
+ * before anything is enqueued (HIFICAR_E_INVALID otherwise).  The tape records the lengths and M, so hificar_bigru_backward takes no new
+ * argument and cannot be run with other lengths than its forward: on such a tape it ignores dout on padded frames, whatever it holds, writes
+ * dx = 0 there, and every weight and bias gradient sums valid frames only.  With all lengths = T every result is bitwise that of
+ * hificar_bigru_forward_train.  Deterministic (no atomics).  tape = NULL: the forward-only form, as above.
+ * The GEMMs still run over all B T rows (zeros in the padded rows mask them): padding costs time, not correctness. */
+int hificar_bigru_forward_train_ragged(hificar_bigru* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out,
+                                       float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape,
+                                       size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* dout (B, out_channels, T) -> grads (hificar_bigru_grad_floats floats: written, not accumulated) and, with dx non-NULL, the input's
- * gradient (B, in_channels, T).  The weights must be those of the forward that filled the tape. */
+ * gradient (B, in_channels, T).  The weights must be those of the forward that filled the tape.  A tape of
+ * hificar_bigru_forward_train_ragged: see there. */
 int hificar_bigru_backward(hificar_bigru* h, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
                            void* workspace, size_t workspace_bytes, void* stream);
 

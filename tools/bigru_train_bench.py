@@ -10,7 +10,14 @@ ratio has to exceed).  --limit seconds per step is checked from the events after
 cannot stop a step that hangs, so run the tool under an outer `timeout`.  Then one native step under hificar_profile_begin / hificar_profile_end:
 time per kernel, the forward and the backward sweep's microseconds per step (kernel time / (2 layers * T)), and the tape / workspace bytes.
 The stock model's dropout masks are torch's own (another random stream: the two steps are timed, not compared).
-Prints one JSON line per case; --out also appends them to a file."""
+Prints one JSON line per case; --out also appends them to a file.
+
+--ragged: one batch of whole utterances instead — the published shape (1024, 256, 18), B 32, padded to T 500, lengths uniform in 100 .. 500
+from --seed — and three legs in alternated windows: the native ragged step (BiGRU.forward_padded + masked_l1_loss), the native dense step on
+the same padded batch (every frame counted, as the reference's pad mode trains), and a stock PyTorch-ROCm ragged step (pack_padded_sequence
+through nn.GRU, batch norm and L1 on the valid rows, the same optimizer).  Reports the padded-frame share and both native steps' kernel
+and per-step sweep times.
+   python tools/bigru_train_bench.py --ragged --out profiles/bigru_train_ragged.txt"""
 import argparse
 import ctypes
 import json
@@ -23,7 +30,10 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
+from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence  # noqa: E402
+
 from articulatory_amd import _native  # noqa: E402
+from articulatory_amd.losses import masked_l1_loss  # noqa: E402
 from articulatory_amd.models import BiGRU  # noqa: E402
 from articulatory_amd.utils.synth import synth_bigru_state_dict, uniform  # noqa: E402
 
@@ -52,6 +62,17 @@ class StockBiGRU(torch.nn.Module):
         y = self.bn(y).transpose(1, 2)
         return self.fc2(y).transpose(1, 2)
 
+    def forward_rows(self, mels, lengths, valid):
+        """The ragged step's forward from stock parts: each GRU layer over the packed sequences, fc1 / batch norm / fc2 on the valid rows
+        only -> (M, out) in (b, t) order.  lengths: CPU int64; valid: (B, T) bool on the device."""
+        T = mels.shape[2]
+        y = mels.transpose(1, 2)
+        for gru, drop in ((self.gru1, self.dropout1), (self.gru2, self.dropout2)):
+            y, _ = gru(pack_padded_sequence(y, lengths, batch_first=True, enforce_sorted=False))
+            y, _ = pad_packed_sequence(y, batch_first=True, total_length=T)
+            y = drop(y)
+        return self.fc2(self.bn(self.fc1(y[valid])))
+
 
 def make_step(model, x, t):
     opt = torch.optim.Adam(model.parameters(), lr=1e-4, fused=True)
@@ -62,6 +83,71 @@ def make_step(model, x, t):
         opt.step()
 
     return step
+
+
+def ragged_main(a):
+    """--ragged: see the module docstring."""
+    params, B, T = SHAPES["full"], 32, 500
+    lengths = torch.from_numpy(np.random.default_rng(a.seed).integers(100, T + 1, size=B)).to(torch.int64)
+    M = int(lengths.sum())
+    tsd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth_bigru_state_dict(params, seed=5101).items()}
+    valid_cpu = torch.arange(T)[None, :] < lengths[:, None]
+    valid = valid_cpu.cuda()
+    x = torch.from_numpy(uniform(1, f"x.{B}.{T}", (B, params["in_channels"], T), -1.0, 1.0)) * valid_cpu[:, None, :]
+    t = torch.from_numpy(uniform(1, f"t.{B}.{T}", (B, params["out_channels"], T), -1.0, 1.0)) * valid_cpu[:, None, :]
+    x, t = x.cuda().contiguous(), t.cuda().contiguous()
+    t_rows = t.transpose(1, 2)[valid].contiguous()
+    lens32 = lengths.to(torch.int32)
+
+    def native_model():
+        m = BiGRU(**params, dropout=DROPOUT)
+        m.load_state_dict(tsd, strict=True)
+        return m.cuda().train()
+
+    def make(model, loss_fn):
+        opt = torch.optim.Adam(model.parameters(), lr=1e-4, fused=True)
+
+        def step():
+            opt.zero_grad(set_to_none=True)
+            loss_fn(model).backward()
+            opt.step()
+
+        return step
+
+    nr, nd = native_model(), native_model()
+    legs = {"native_ragged": make(nr, lambda m: masked_l1_loss(m.forward_padded(x, lens32), t, lens32)),
+            "native_dense": make(nd, lambda m: F.l1_loss(m(x), t))}
+    if not a.no_stock:
+        stock = StockBiGRU(**params)
+        stock.load_state_dict(tsd, strict=True)
+        legs["stock_ragged"] = make(stock.cuda().train(), lambda m: F.l1_loss(m.forward_rows(x, lengths, valid), t_rows))
+    for _ in range(3):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(2):
+        for k, fn in legs.items():
+            ms[k].append(window(fn, a.window, a.limit))
+    res = {"case": "ragged", "shape": "full", "B": B, "T": T, "seed": a.seed, "valid_frames": M, "padded_share": round(1.0 - M / (B * T), 4)}
+    for k, v in ms.items():
+        res[k + "_step_ms"] = [round(u, 3) for u in v]
+        res[k + "_spread"] = round(abs(v[0] - v[1]) / min(v), 4)
+    res["dense_over_ragged"] = round(min(ms["native_dense"]) / max(ms["native_ragged"]), 3)
+    if "stock_ragged" in ms:
+        res["stock_over_native_ragged"] = round(min(ms["stock_ragged"]) / max(ms["native_ragged"]), 3)  # slowest native, fastest stock
+    for tag, m in (("ragged", nr), ("dense", nd)):
+        prof = kernel_profile(m, legs["native_" + tag])
+        res[tag + "_kernels_ms"] = {k: round(v, 4) for k, (_, v) in sorted(prof.items())}
+        res[tag + "_kernels_total_ms"] = round(sum(v for _, v in prof.values()), 3)
+        res[tag + "_fwd_sweep_us_per_step"] = round(prof.get("bigru_rec_kernel", (0, 0.0))[1] * 1e3 / (2 * T), 3)
+        res[tag + "_bwd_sweep_us_per_step"] = round(prof.get("bigru_rec_bwd_kernel", (0, 0.0))[1] * 1e3 / (2 * T), 3)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
 
 
 def window(fn, seconds, limit):
@@ -102,7 +188,11 @@ def main():
     ap.add_argument("--limit", type=float, default=5.0, help="seconds a single step may take")
     ap.add_argument("--no-stock", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ragged", action="store_true", help="the ragged batch's three legs instead of the dense grid")
+    ap.add_argument("--seed", type=int, default=0, help="--ragged: seed of the lengths")
     a = ap.parse_args()
+    if a.ragged:
+        return ragged_main(a)
     lines = []
     for shape in a.shapes:
         params = SHAPES[shape]
