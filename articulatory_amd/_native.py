@@ -44,6 +44,7 @@ SYMBOLS = (
     "hificar_profile_begin",
     "hificar_profile_end",
     "hificar_debug_tap",
+    "hificar_debug_force_tile",
     "hificar_set_weight_device",
     "hificar_set_parameters_device",
     "hificar_raw_grad_floats",
@@ -335,6 +336,8 @@ def load_library():
     lib.hificar_profile_end.restype = ctypes.c_int
     lib.hificar_debug_tap.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_size_t]
     lib.hificar_debug_tap.restype = ctypes.c_int
+    lib.hificar_debug_force_tile.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.hificar_debug_force_tile.restype = ctypes.c_int
     lib.hificar_set_weight_device.argtypes = [vp, ctypes.c_char_p, vp, vp]
     lib.hificar_set_weight_device.restype = ctypes.c_int
     lib.hificar_set_parameters_device.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, vp]

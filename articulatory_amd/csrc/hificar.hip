@@ -124,6 +124,7 @@ struct hificar_engine {
     int pick_throughput = 0;       // > 0: launches of at least this many tiles choose their tile shape by workgroup-time instead of makespan (set by
                                    // the discriminator engine, whose sub-networks run on eight streams; 0 = off)
     bool shared_chip = false;      // set while hificar_ar_loop runs two halves of a batch on two streams (launch_conv's tile choice)
+    int force_tile[5] = {0, 0, 0, 0, 0};  // hificar_debug_force_tile: {MI, WM, WN, KS, NB} every launch_conv launch takes where it is admissible (MI = 0: none)
     std::vector<void*> allocs;     // device memory the engine's owner uploaded through it (upload, pack_w16 / pack_w32): freed by engine_close
     char* d_zeros = nullptr;       // 256 bytes of zeros: source of padding rows for the LDS DMA
     // launch plans, one per launch shape (get_plan), each with the tile schedule it built.  The schedules live in append-only arenas: a
@@ -1112,6 +1113,25 @@ struct ConvRep {
     long long zs_x = 0, zs_w = 0, zs_y = 0, zs_b = 0;
 };
 
+// Whether a launch of these branches can run tile shape t at all: the instantiations that exist, the LDS budget, and what the register-blocked
+// and split-K forms need of the layers.  halo_all: the widest branch's off_max - off_min; nsteps_min: the shortest branch's (tap, slab) steps
+// per K chunk.  Shared by the cost loop of pick_tile and by a forced shape (hificar_debug_force_tile).
+static bool tile_admissible(const hificar_engine* h, const ConvLayer* const* layers, int nbr, const TileCfg& t, int halo_all, int nsteps_min) {
+    const ConvLayer& L0 = *layers[0];
+    const bool f32 = h->precision == HIFICAR_PREC_F32;
+    const int TM = t.WM * t.MI * 32, RB = L0.chunk16 * 4;
+    if (t.NB == 2 && (f32 || L0.chunk16 == 16)) return false;  // (not instantiated)
+    const size_t obuf = (f32 && t.KS == 1) ? 0 : out_buf_bytes(t);
+    if (2 * round_up_sz((size_t)(TM + halo_all) * RB, 1024) + obuf > 160 * 1024) return false;
+    if (t.NB == 2) {  // a wave's two channel blocks share the activation fragments: same phase of a polyphase (transposed) conv
+        bool ok = L0.n_blocks32 >= 2;
+        for (int b = 0; b < nbr; ++b) ok = ok && (layers[b]->n_phase == 1 || layers[b]->nb32_per_phase % 2 == 0);
+        if (!ok) return false;
+    }
+    if (t.KS == 4 && (h->ksplit == 0 || nsteps_min < 2)) return false;
+    return true;
+}
+
 // Tile shape of a launch_conv launch: simulate the kernel's tile walk and take the shape with the smallest makespan.  A tile costs its
 // MFMA issue cycles (all four MFMA waves run in lock step: 3*MI MFMAs of 32 cycles per 16-channel K slab) plus a fixed per-tile and
 // per-item overhead.  Pure host arithmetic on the launch shape and the engine's fixed switches.
@@ -1127,19 +1147,15 @@ static TileCfg pick_tile(const hificar_engine* h, const ConvLayer* const* layers
     // may prefer them (+1.3 %; in exact fp32 they measured -1.0 %: profiles/r04_nb_register_blocking.txt).
     int nsteps_min = 1 << 30;
     for (int b = 0; b < nbr; ++b) nsteps_min = std::min(nsteps_min, layers[b]->ntaps * (L0.chunk16 / 16));
+    if (h->force_tile[0] != 0) {  // a test's forced shape (hificar_debug_force_tile), where this launch can run it; otherwise the normal choice below
+        const TileCfg t = {h->force_tile[0], h->force_tile[1], h->force_tile[2], h->force_tile[3], h->force_tile[4]};
+        if (tile_admissible(h, layers, nbr, t, halo_all, nsteps_min)) return t;
+    }
     for (int ti = 0; ti < kNumTileCfgs; ++ti) {
         const TileCfg& t = kTileCfgs[ti];
         const int TM = t.WM * t.MI * 32;
-        const int chunk = L0.chunk16, RB = chunk * 4;
-        if (t.NB == 2 && (f32 || L0.chunk16 == 16)) continue;  // (not instantiated)
-        const size_t obuf = (f32 && t.KS == 1) ? 0 : out_buf_bytes(t);
-        if (2 * round_up_sz((size_t)(TM + halo_all) * RB, 1024) + obuf > 160 * 1024) continue;
-        if (t.NB == 2) {  // a wave's two channel blocks share the activation fragments: same phase of a polyphase (transposed) conv
-            bool ok = L0.n_blocks32 >= 2;
-            for (int b = 0; b < nbr; ++b) ok = ok && (layers[b]->n_phase == 1 || layers[b]->nb32_per_phase % 2 == 0);
-            if (!ok) continue;
-        }
-        if (t.KS == 4 && (h->ksplit == 0 || nsteps_min < 2)) continue;
+        const int chunk = L0.chunk16;
+        if (!tile_admissible(h, layers, nbr, t, halo_all, nsteps_min)) continue;
         if (t.KS == 1 && h->ksplit == 2 && nsteps_min >= 2) continue;
         const long long tiles_per_branch = (long long)nseq * ((rows + TM - 1) / TM) * ((L0.n_blocks32 + t.WN * t.NB - 1) / (t.WN * t.NB));
         const long long total = tiles_per_branch * nbr * zrep;
@@ -1461,6 +1477,22 @@ extern "C" int hificar_debug_tap(hificar_handle* h, const char* name, float* dst
         return HIFICAR_OK;
     }
     h->taps[name] = {dst, capacity};
+    return HIFICAR_OK;
+}
+
+// Test aid: every launch_conv launch of this engine takes tile shape (mi, wm, wn, ks, nb) — one of kTileCfgs — where tile_admissible lets it, and
+// the planner's own choice elsewhere; mi = 0 gives every launch back to the planner.  Drops all plans, so the next launch of every shape is planned anew.
+extern "C" int hificar_debug_force_tile(hificar_engine* e, int mi, int wm, int wn, int ks, int nb) {
+    if (!e) return fail(HIFICAR_E_INVALID, "null engine");
+    if (mi != 0) {
+        bool known = false;
+        for (const TileCfg& t : kTileCfgs) known = known || (t.MI == mi && t.WM == wm && t.WN == wn && t.KS == ks && t.NB == nb);
+        if (!known) return fail(HIFICAR_E_INVALID, "hificar_debug_force_tile: (%d, %d, %d, %d, %d) is not a tile shape of the engine", mi, wm, wn, ks, nb);
+    }
+    const int rc = evict_plans(e);
+    if (rc != HIFICAR_OK) return rc;
+    const int req[5] = {mi, mi ? wm : 0, mi ? wn : 0, mi ? ks : 0, mi ? nb : 0};
+    memcpy(e->force_tile, req, sizeof(req));
     return HIFICAR_OK;
 }
 

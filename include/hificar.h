@@ -368,6 +368,15 @@ int hificar_backward_cond(hificar_handle* h, const float* dout, const float* dph
  * tap, name = NULL removes all.  Taps add copies and (for convs1) extra launches: not for timed runs. */
 int hificar_debug_tap(hificar_handle* h, const char* name, float* dst, size_t capacity);
 
+/* Test aid, not for production runs: from now on every conv launch of this engine (any model's: hificar_engine_of, hificar_disc_engine,
+ * hificar_bigru_engine) runs tile shape (mi, wm, wn, ks, nb) instead of the one its planner would choose — mi x 32 rows per wave, wm x wn
+ * MFMA waves, ks = 4: the split-K form (wm = wn = 1), nb = 2: two channel blocks per wave — wherever that launch can run the shape at all
+ * (the instantiation exists for its arithmetic and K chunk, the LDS budget holds, the layers meet the register-blocked / split-K forms'
+ * conditions); a launch that cannot keeps the planner's choice.  mi = 0 ends it.  The tuple must be one of the engine's 15 shapes
+ * (HIFICAR_E_INVALID otherwise).  Synchronises the device and drops every cached launch plan.  Results stay correct under any shape; speed does not.
+ * No reference counterpart (the reference has no tiles). */
+int hificar_debug_force_tile(hificar_engine* e, int mi, int wm, int wn, int ks, int nb);
+
 void hificar_destroy(hificar_handle* h);
 
 const char* hificar_last_error(void);
