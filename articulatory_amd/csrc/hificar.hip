@@ -876,8 +876,6 @@ extern "C" double hificar_macs(const hificar_handle* h, int B, int T) {
 // ------------------------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------------------------
-// Ragged batch context of one forward: utterance b has seq_len[b] frames (device array, null = all equal); the forward
-// covers frames [f0, f0 + frames) of every utterance.
 // Training tape: every activated conv input of one forward gets its own buffer (the backward pass reads them: wgrad operands and
 // LeakyReLU' masks); nothing is overwritten.  Filled by plan_tape() from a caller-provided tape buffer.
 struct Tape {
@@ -899,8 +897,23 @@ struct Tape {
     size_t bytes = 0;
 };
 
-// Conditioning inputs / extra output of one forward (hificar_forward_cond)
-struct Cond {
+// One generator forward on B sequences of T frames, as its entry point describes it: every caller fills the fields it uses.
+//   c: element (b, ch, t) at c[b*c_bstride + ch*c_cstride + t];  prev: (b, i) at prev[b*prev_bstride + i] or null
+//   out: sample (b, n) at out[b*out_bstride + n]
+struct FwdCall {
+    const float* c = nullptr;
+    int64_t c_bstride = 0, c_cstride = 0;
+    const float* prev = nullptr;
+    int64_t prev_bstride = 0;
+    float* out = nullptr;
+    int64_t out_bstride = 0;
+    int B = 0;
+    int T = 0;         // frames the launches cover
+    int T_valid = -1;  // (<= T, default T): frames that exist in c / out (bucketed non-AR lengths)
+    int f0 = 0;        // the forward covers frames [f0, f0 + T) of every utterance
+    const int32_t* seq_len = nullptr;  // utterance b has seq_len[b] frames (device array, null = all equal)
+    const int2* slots = nullptr;       // packed AR loop / streaming step: sequence b is (utterance, first frame) slots[b]
+    // conditioning inputs / extra output (hificar_forward_cond)
     const int32_t* spk_id = nullptr;
     const int32_t* ph = nullptr;
     int ph_stride = 0;
@@ -912,15 +925,30 @@ struct Cond {
     const int4* seqs = nullptr;
     int2* seqs_slots = nullptr;
     int* seqs_valid = nullptr;
+    const Tape* tp = nullptr;  // training forward: where the activations are kept
+    Workspace ws = {};
+    hipStream_t stream = nullptr;
 };
 
+// Ragged batch context of the launches of one forward: utterance b has seq_len[b] frames (device array, null = all equal); the forward
+// covers frames [f0, f0 + frames) of every utterance.
 struct Ragged {
     const int32_t* seq_len = nullptr;
     int const_len = -1;  // >= 0 (and seq_len null): every utterance has this many frames, fewer than the launch covers (bucketed lengths)
     int f0 = 0;
     int frames = 0;
-    float* ctx = nullptr;  // streaming steps (Cond::ctx): the output conv writes out densely by sequence and refreshes the context rows
+    float* ctx = nullptr;  // streaming steps (FwdCall::ctx): the output conv writes out densely by sequence and refreshes the context rows
 };
+
+static Ragged ragged_of(const FwdCall& k) {  // (k.T_valid resolved: forward_impl)
+    Ragged rg;
+    rg.seq_len = k.seq_len;
+    rg.const_len = k.T_valid < k.T ? k.f0 + k.T_valid : -1;
+    rg.f0 = k.f0;
+    rg.frames = k.T;
+    rg.ctx = k.ctx;
+    return rg;
+}
 
 // Launch geometry of a non-AR forward is rounded up to a bucket of frames (the extra frames are masked exactly like the tail of a
 // ragged batch: bit-identical results), so that a dataset of many distinct utterance lengths shares launch shapes / schedules.
@@ -1520,33 +1548,83 @@ static int emit_tap(hificar_handle* h, const std::string& name, const void* src,
 
 static bool tap_wanted(const hificar_handle* h, const std::string& name) { return h->taps.count(name) != 0; }
 
+// The `x0..x3, nin` prefix of the parameter blocks whose kernels average up to four fp32 streams (MrfSplitParams, PhHeadParams, OutConvParams
+// and their backward blocks)
+template <class P>
+static void fill_inputs(P& p, const float* const* fin, int nin) {
+    p.x0 = fin[0];
+    p.x1 = nin > 1 ? fin[1] : nullptr;
+    p.x2 = nin > 2 ? fin[2] : nullptr;
+    p.x3 = nin > 3 ? fin[3] : nullptr;
+    p.nin = nin;
+}
+
+// n branches of `rows` rows as launch_conv launches of layers l1 (io) or, with iop, as launch_pair launches of (l1, l2).  A launch carries up
+// to three branches (MultiConvParams / PairParams): a fourth residual block rides in a second launch
+static int launch_n(hificar_engine* h, const ConvLayer* const* l1, const ConvLayer* const* l2, int n, int nseq, int rows, const ConvIO* io,
+                    const PairIOB* iop, float slope, const Ragged& rg, hipStream_t stream) {
+    for (int q0 = 0; q0 < n; q0 += 3) {
+        const int m = std::min(3, n - q0);
+        const int r = iop ? launch_pair(h, l1 + q0, l2 + q0, m, nseq, rows, iop + q0, slope, rg, stream)
+                          : launch_conv(h, l1 + q0, m, nseq, rows, io + q0, slope, rg, stream);
+        if (r != HIFICAR_OK) return r;
+    }
+    return HIFICAR_OK;
+}
+
+// residual blocks of a stage run side by side, heaviest kernel size first
+struct BlockOrder {
+    int order[kMaxBlk];
+    int max_d = 0;  // dilations of the deepest block
+};
+static BlockOrder block_order(const hificar_config& cfg) {
+    BlockOrder bo;
+    for (int j = 0; j < kMaxBlk; ++j) bo.order[j] = j;
+    std::sort(bo.order, bo.order + cfg.n_blocks, [&](int a, int b) { return cfg.resblock_kernel_sizes[a] > cfg.resblock_kernel_sizes[b]; });
+    for (int j = 0; j < cfg.n_blocks; ++j) bo.max_d = std::max(bo.max_d, cfg.n_dilations[j]);
+    return bo;
+}
+
+// The branches of the launches of dilation d in one stage, in launch order: the blocks that have a dilation d, as block j[q] and the
+// index ci[q] of its layer in convs1 / convs2
+struct Branches {
+    int n = 0;
+    int j[kMaxBlk], ci[kMaxBlk];
+};
+static Branches gather_branches(const hificar_handle* h, const BlockOrder& bo, int stage, int d) {
+    Branches br;
+    for (int oj = 0; oj < h->cfg.n_blocks; ++oj) {
+        const int j = bo.order[oj];
+        if (d >= h->cfg.n_dilations[j]) continue;
+        br.j[br.n] = j;
+        br.ci[br.n] = conv_index(h, stage, j, d);
+        ++br.n;
+    }
+    return br;
+}
+
 // LeakyReLU(0.01) + Conv1d(C -> 1, k) + tanh on the mean of `nin` fp32 inputs (hifigan.py:146-159, 231; gblock_gen.py:71-93, 131)
-static int launch_output_conv(hificar_handle* h, const float* const* fin, int nin, int Cpad, int rows, int B, int T, float* out,
-                              int64_t out_bstride, const int32_t* seq_len, const Ragged& rg, const int2* slots, hipStream_t stream) {
+static int launch_output_conv(hificar_handle* h, const FwdCall& k, const Ragged& rg, const float* const* fin, int nin, int Cpad, int rows) {
     const hificar_config& cfg = h->cfg;
     OutConvParams op;
     memset(&op, 0, sizeof(op));
-    op.x0 = fin[0];
-    op.x1 = nin > 1 ? fin[1] : nullptr;
-    op.x2 = nin > 2 ? fin[2] : nullptr;
-    op.x3 = nin > 3 ? fin[3] : nullptr;
-    op.nin = nin;
+    fill_inputs(op, fin, nin);
     op.w = h->d_out_w;
     op.bias = h->out_bias;
     op.bias_ptr = h->d_out_bias;
-    op.out = out;
-    op.out_bstride = out_bstride;
+    op.out = k.out;
+    op.out_bstride = k.out_bstride;
     op.L = rows;
     op.C = Cpad;
     op.K = cfg.kernel_size;
     op.slope = 0.01f;
     op.use_tanh = cfg.use_tanh;
-    op.seq_len = seq_len;
-    op.len_const = seq_len ? -1 : rg.const_len;
+    op.seq_len = rg.seq_len;
+    op.len_const = rg.seq_len ? -1 : rg.const_len;
     op.len_f0 = rg.f0;
-    op.len_max = T;
-    op.len_mul = rows / T;
-    op.slots = slots;
+    op.len_max = k.T;
+    op.len_mul = rows / k.T;
+    op.slots = k.slots;
     op.ctx = rg.ctx;
     op.ar_input = cfg.ar_input;
     op.hop = h->hop;
@@ -1556,71 +1634,77 @@ static int launch_output_conv(hificar_handle* h, const float* const* fin, int ni
     op.TR = (int)std::min<long long>(256, fit);
     const size_t lds = ((size_t)(op.TR + op.K - 1) * (op.C + 1) + (size_t)op.K * op.C) * sizeof(float);
     {
-        const double pos = (double)B * rows;
-        ProfScope prof(h, stream, "output_conv_kernel", 2.0 * pos * op.C * op.K, 4.0 * pos * (op.C * nin + 1));
-        hipLaunchKernelGGL(output_conv_kernel, dim3((rows + op.TR - 1) / op.TR, B), dim3(256), lds, stream, op);
+        const double pos = (double)k.B * rows;
+        ProfScope prof(h, k.stream, "output_conv_kernel", 2.0 * pos * op.C * op.K, 4.0 * pos * (op.C * nin + 1));
+        hipLaunchKernelGGL(output_conv_kernel, dim3((rows + op.TR - 1) / op.TR, k.B), dim3(256), lds, k.stream, op);
     }
     HIP_TRY(hipGetLastError());
     return HIFICAR_OK;
 }
 
-struct Tape;
-struct Cond;
-struct Workspace;
-// GBlockGenerator body of a forward: input conv -> GBlocks -> output conv (hificar_gblock.hip.inc)
-static int gblock_forward(hificar_handle* h, float* out, int64_t out_bstride, int B, int T, const Workspace& ws, hipStream_t stream,
-                          const int32_t* seq_len, const Ragged& rg, const int2* slots, const Tape* tp);
+// Scratch for the pre-activation copies a debug tap wants and the normal path never writes: grown to `elems` floats
+static int grow_tap_scratch(hificar_handle* h, size_t elems) {
+    if (elems <= h->tap_scratch_elems) return HIFICAR_OK;
+    if (h->tap_scratch) HIP_TRY(hipFree(h->tap_scratch));
+    h->tap_scratch = nullptr;
+    h->tap_scratch_elems = 0;
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, elems * sizeof(float)));
+    h->tap_scratch = static_cast<float*>(p);
+    h->tap_scratch_elems = elems;
+    return HIFICAR_OK;
+}
 
-// One generator forward on B sequences of T frames.
-//   c: element (b, ch, t) at c[b*c_bstride + ch*c_cstride + t];  prev: (b, i) at prev[b*prev_bstride + i] or null
-//   out: sample (b, n) at out[b*out_bstride + n]
-static int forward_impl(hificar_handle* h, const float* c, int64_t c_bstride, int64_t c_cstride, const float* prev,
-                        int64_t prev_bstride, float* out, int64_t out_bstride, int B, int T, const Workspace& ws,
-                        hipStream_t stream, const int32_t* seq_len = nullptr, int f0 = 0, const int2* slots = nullptr, int T_valid = -1,
-                        const Cond& cond = Cond(), const Tape* tp = nullptr) {
-    // T: frames the launches cover; T_valid (<= T, default T): frames that exist in c / out (bucketed non-AR lengths)
-    const hificar_config& cfg = h->cfg;
-    if (T_valid < 0) T_valid = T;
+// What the steps of one HiFi-GAN forward hand on to each other
+struct FwdState {
     Ragged rg;
-    rg.seq_len = seq_len;
-    rg.const_len = T_valid < T ? f0 + T_valid : -1;
-    rg.f0 = f0;
-    rg.frames = T;
-    // 1. front end
+    BlockOrder bo;
+    int rows = 0;               // rows per sequence at the current stage
+    const float* fin[kMaxBlk];  // where each branch's ResBlock output of the current stage lives
+    bool tapping = false;
+    bool tap_convs1 = false;    // a conv1 output is wanted: those pairs run layer by layer (the fused kernel keeps it in LDS)
+    size_t tap_se = 0;
+};
+
+// GBlockGenerator body of a forward: input conv -> GBlocks -> output conv (hificar_gblock.hip.inc)
+static int gblock_forward(hificar_handle* h, const FwdCall& k, const Ragged& rg);
+
+// 1. front end: the input rows of the input conv from the features, the PastFCEncoder of the AR context and the conditioning
+static int launch_front(hificar_handle* h, const FwdCall& k) {
+    const hificar_config& cfg = h->cfg;
     FrontParams fp;
     memset(&fp, 0, sizeof(fp));
-    fp.c = c;
-    fp.c_bstride = c_bstride;
-    fp.c_cstride = c_cstride;
-    fp.prev = prev;
-    fp.prev_bstride = prev_bstride;
-    fp.slots = slots;
-    fp.valid = seq_len;
-    if (cond.ctx) {
-        fp.prev = cond.ctx;
+    fp.c = k.c;
+    fp.c_bstride = k.c_bstride;
+    fp.c_cstride = k.c_cstride;
+    fp.prev = k.prev;
+    fp.prev_bstride = k.prev_bstride;
+    fp.slots = k.slots;
+    fp.valid = k.seq_len;
+    if (k.ctx) {
+        fp.prev = k.ctx;
         fp.prev_bstride = cfg.ar_input;
-        fp.seqs = cond.seqs;
-        fp.seqs_slots = cond.seqs_slots;
-        fp.seqs_valid = cond.seqs_valid;
-        rg.ctx = cond.ctx;
+        fp.seqs = k.seqs;
+        fp.seqs_slots = k.seqs_slots;
+        fp.seqs_valid = k.seqs_valid;
     }
     fp.hop = h->hop;
     const bool f32 = h->precision == HIFICAR_PREC_F32;
-    fp.xin = f32 ? (tp ? tp->xin : ws.xin) : nullptr;
-    fp.xin_s = f32 ? nullptr : reinterpret_cast<char*>(ws.xin);
-    fp.mlp_tape = tp ? tp->mlp : nullptr;
-    fp.T = T;
-    fp.t_valid = T_valid;
+    fp.xin = f32 ? (k.tp ? k.tp->xin : k.ws.xin) : nullptr;
+    fp.xin_s = f32 ? nullptr : reinterpret_cast<char*>(k.ws.xin);
+    fp.mlp_tape = k.tp ? k.tp->mlp : nullptr;
+    fp.T = k.T;
+    fp.t_valid = k.T_valid;
     if (cfg.use_spk_id) {
-        fp.spk_id = cond.spk_id;
+        fp.spk_id = k.spk_id;
         fp.spk_emb = h->d_spk_emb;
         fp.spk_w = h->d_spk_w;
         fp.spk_b = h->d_spk_b;
         fp.spk_e = cfg.spk_emb_size;
     }
     if (cfg.use_ph) {
-        fp.ph = cond.ph;
-        fp.ph_stride = cond.ph_stride;
+        fp.ph = k.ph;
+        fp.ph_stride = k.ph_stride;
         fp.ph_emb = h->d_ph_emb;
         fp.ph_e = cfg.ph_emb_size;
     }
@@ -1637,245 +1721,278 @@ static int forward_impl(hificar_handle* h, const float* c, int64_t c_bstride, in
     {
         const double mlp_macs = cfg.use_ar ? (double)cfg.ar_input * cfg.ar_hidden + 3.0 * cfg.ar_hidden * cfg.ar_hidden +
                                                  (double)cfg.ar_hidden * cfg.ar_output : 0.0;
-        ProfScope prof(h, stream, "front_kernel", 2.0 * B * mlp_macs, 4.0 * B * (mlp_macs + (double)T * (h->cf + h->cin_pad)));
-        hipLaunchKernelGGL(front_kernel, dim3(B), dim3(kFrontThreads), 0, stream, fp);
+        ProfScope prof(h, k.stream, "front_kernel", 2.0 * k.B * mlp_macs, 4.0 * k.B * (mlp_macs + (double)k.T * (h->cf + h->cin_pad)));
+        hipLaunchKernelGGL(front_kernel, dim3(k.B), dim3(kFrontThreads), 0, k.stream, fp);
     }
     HIP_TRY(hipGetLastError());
-    if (h->arch == 1) return gblock_forward(h, out, out_bstride, B, T, ws, stream, seq_len, rg, slots, tp);
+    return HIFICAR_OK;
+}
 
+// Activations travel between layers already activated — split rows (bf16x3) or plain fp32 rows (exact fp32), the
+// "_s" buffers — and are staged by LDS-DMA; the layer's own fp32 value only where a residual / the MRF mean needs it
+static char* act_h0(const FwdCall& k) { return k.tp ? k.tp->h0_s : reinterpret_cast<char*>(k.ws.h0); }
+static char* act_xt(const FwdCall& k, int j) { return reinterpret_cast<char*>(k.ws.xt[j]); }
+
+// 2. input conv (no activation in front of it: hifigan.py:221); its consumer applies LeakyReLU(slope)
+static int forward_input_conv(hificar_handle* h, const FwdCall& k, const FwdState& fs) {
+    const hificar_config& cfg = h->cfg;
     int rc;
-    int rows = T;
-    const bool tapping = !h->taps.empty();
-    bool tap_convs1 = false;  // a conv1 output is wanted: those pairs run layer by layer (the fused kernel keeps it in LDS)
-    if (tapping) {
-        for (auto& kv : h->taps) tap_convs1 = tap_convs1 || kv.first.find(".convs1.") != std::string::npos;
-        // pre-activation copies that the normal path never writes: 3 stage-sized scratch buffers
-        const size_t need = kMaxBlk * stage_elems(h, B, T) + (size_t)B * T * stage_pad(cfg, 0);
-        if (need > h->tap_scratch_elems) {
-            if (h->tap_scratch) HIP_TRY(hipFree(h->tap_scratch));
-            h->tap_scratch = nullptr;
-            h->tap_scratch_elems = 0;
-            void* p = nullptr;
-            HIP_TRY(hipMalloc(&p, need * sizeof(float)));
-            h->tap_scratch = static_cast<float*>(p);
-            h->tap_scratch_elems = need;
+    const ConvLayer* lay[1] = {&h->input_conv};
+    float* y_tap = tap_wanted(h, "input_conv") ? h->tap_scratch + kMaxBlk * fs.tap_se : nullptr;
+    const ConvIO io[1] = {{reinterpret_cast<char*>(k.tp ? k.tp->xin : k.ws.xin), nullptr, y_tap, act_h0(k)}};
+    if ((rc = launch_conv(h, lay, 1, k.B, k.T, io, cfg.lrelu_slope, fs.rg, k.stream)) != HIFICAR_OK) return rc;
+    if (y_tap && (rc = emit_tap(h, "input_conv", y_tap, stage_pad(cfg, 0), 0, cfg.channels, k.B, k.T, 0, k.stream)) != HIFICAR_OK) return rc;
+    return HIFICAR_OK;
+}
+
+// The activated MRF mean of the previous stage's ResBlock outputs as its own launch -> the rows the upsampler reads
+static int launch_mrf_split(hificar_handle* h, const FwdCall& k, const FwdState& fs, int i, const char** up_in) {
+    const hificar_config& cfg = h->cfg;
+    const int nbk = cfg.n_blocks;
+    MrfSplitParams mq;
+    memset(&mq, 0, sizeof(mq));
+    fill_inputs(mq, fs.fin, nbk);
+    mq.out = fs.fin[0] == k.ws.xt[0] ? k.ws.x_s[0] : act_xt(k, 0);  // a buffer none of the inputs lives in
+    if (k.tp) mq.out = k.tp->upin_s[i];
+    mq.C = stage_pad(cfg, i);
+    mq.rows = (long long)k.B * fs.rows;
+    mq.slope = cfg.lrelu_slope;
+    mq.f32 = h->precision == HIFICAR_PREC_F32 ? 1 : 0;
+    const long long units = mq.rows * (mq.C / 8);
+    const unsigned blocks = (unsigned)std::min<long long>((units + 255) / 256, 8LL * h->num_cus);
+    {
+        ProfScope prof(h, k.stream, "mrf_split_kernel", 0.0, 4.0 * mq.rows * mq.C * (nbk + 1));
+        hipLaunchKernelGGL(mrf_split_kernel, dim3(blocks), dim3(256), 0, k.stream, mq);
+    }
+    HIP_TRY(hipGetLastError());
+    *up_in = mq.out;
+    return HIFICAR_OK;
+}
+
+// debug taps of the residual stream of block j of stage i after dilation d
+static int tap_block(hificar_handle* h, const FwdCall& k, const FwdState& fs, int i, int j, int d, const float* xcur) {
+    if (!fs.tapping) return HIFICAR_OK;
+    const hificar_config& cfg = h->cfg;
+    const int Cs = stage_channels(cfg, i + 1), Cp = stage_pad(cfg, i + 1);
+    const std::string base = "blocks." + std::to_string(i * cfg.n_blocks + j);
+    int r = emit_tap(h, base + ".x." + std::to_string(d), xcur, Cp, 0, Cs, k.B, fs.rows, 0, k.stream);
+    if (r == HIFICAR_OK && d + 1 == cfg.n_dilations[j]) r = emit_tap(h, base, xcur, Cp, 0, Cs, k.B, fs.rows, 0, k.stream);
+    return r;
+}
+
+// ResBlock layers of a narrow stage whose every layer pair runs in the fused kernel: the residual stream stays fp32-only (the pair
+// kernel activates + splits its input while staging), ping-ponging between x[j] and xt[j]; no activated copies
+// are written at all.
+static int resblocks_all_pairs(hificar_handle* h, const FwdCall& k, FwdState& fs, int i) {
+    const hificar_config& cfg = h->cfg;
+    const Workspace& ws = k.ws;
+    const int nbk = cfg.n_blocks;
+    int rc;
+    const float* cur_f[kMaxBlk] = {ws.u, ws.u, ws.u, ws.u};
+    for (int d = 0; d < fs.bo.max_d; ++d) {  // residual_block.py:217-221
+        const ConvLayer* l1[kMaxBlk];
+        const ConvLayer* l2[kMaxBlk];
+        PairIOB iop[kMaxBlk];
+        const Branches br = gather_branches(h, fs.bo, i, d);
+        for (int n = 0; n < br.n; ++n) {
+            const int j = br.j[n];
+            l1[n] = &h->convs1[br.ci[n]];
+            l2[n] = &h->convs2[br.ci[n]];
+            // a tile's output pass must not overwrite rows a neighbouring tile still reads as halo: out != in
+            float* out_f = cur_f[j] == ws.x[j] ? ws.xt[j] : ws.x[j];
+            iop[n] = {cur_f[j], nullptr, cur_f[j], out_f, nullptr};
+            cur_f[j] = out_f;
         }
-        if (cfg.use_ar && (rc = emit_tap(h, "ar_feats", ws.xin, f32 ? h->cin_pad : -h->cin_pad, h->cf, cfg.ar_output, B, 1, f32 ? 0 : 1, stream, T)) != HIFICAR_OK)
+        if ((rc = launch_n(h, l1, l2, br.n, k.B, fs.rows, nullptr, iop, cfg.lrelu_slope, fs.rg, k.stream)) != HIFICAR_OK) return rc;
+        for (int j = 0; j < nbk; ++j)
+            if (d < cfg.n_dilations[j] && (rc = tap_block(h, k, fs, i, j, d, cur_f[j])) != HIFICAR_OK) return rc;
+    }
+    for (int j = 0; j < nbk; ++j) fs.fin[j] = cur_f[j];
+    return HIFICAR_OK;
+}
+
+// ResBlock layers of any other stage: activated copies ("_s") travel next to the fp32 stream; a dilation's pairs still fuse where they all can.
+// u_act: the upsampler's activated output
+static int resblocks_general(hificar_handle* h, const FwdCall& k, FwdState& fs, int i, const char* u_act) {
+    const hificar_config& cfg = h->cfg;
+    const Workspace& ws = k.ws;
+    const Tape* const tp = k.tp;
+    const int nbk = cfg.n_blocks, B = k.B, rows = fs.rows;
+    const int Cs = stage_channels(cfg, i + 1), Cp = stage_pad(cfg, i + 1);
+    const bool add_convs = cfg.use_additional_convs != 0;  // false: a ResBlock layer is x = x + conv1(LeakyReLU(x)) (residual_block.py:217-221)
+    int rc;
+    // fp32 residual streams; training keeps the LAST stage's (the output conv's backward needs the MRF mean) in the tape
+    float* xres[kMaxBlk] = {ws.x[0], ws.x[1], ws.x[2], ws.x[3]};
+    if (tp && i + 1 == cfg.n_stages)
+        for (int j = 0; j < nbk; ++j) xres[j] = tp->fin[j];
+    for (int j = 0; j < nbk; ++j) fs.fin[j] = xres[j];
+    // activated stream of each branch: where the next conv1 reads its input.  It alternates between x_s[j] and
+    // xt_s[j]: a launch never writes the buffer it (or a neighbouring tile, through the halo) reads.
+    const char* cur_s[kMaxBlk] = {u_act, u_act, u_act, u_act};
+    for (int d = 0; d < fs.bo.max_d; ++d) {  // residual_block.py:217-221
+        const ConvLayer* l1[kMaxBlk];
+        const ConvLayer* l2[kMaxBlk];
+        ConvIO io1[kMaxBlk], io2[kMaxBlk];
+        PairIOB iop[kMaxBlk];
+        char* pair_out[kMaxBlk];
+        char* lbl_out[kMaxBlk];
+        bool fuse = add_convs;
+        const Branches br = gather_branches(h, fs.bo, i, d);
+        for (int n = 0; n < br.n; ++n) {
+            const int j = br.j[n];
+            char* const xt_s = act_xt(k, j);
+            l1[n] = &h->convs1[br.ci[n]];
+            l2[n] = add_convs ? &h->convs2[br.ci[n]] : nullptr;
+            fuse = fuse && !fs.tap_convs1 && !tp && pair_eligible(h, *l1[n], *l2[n], B, rows);
+            const bool last = d + 1 == cfg.n_dilations[j];
+            // fused pair: cur -> the other buffer.  Layer by layer: cur -> mid -> the buffer that is not mid.
+            pair_out[n] = cur_s[j] == ws.x_s[j] ? xt_s : ws.x_s[j];
+            char* mid = cur_s[j] == xt_s ? ws.x_s[j] : xt_s;
+            lbl_out[n] = mid == xt_s ? ws.x_s[j] : xt_s;
+            if (tp) {  // training: unique buffers, kept for the backward pass
+                mid = tp->xt_s[i][j][d];
+                lbl_out[n] = tp->x_s[i][j][d];
+            }
+            io1[n] = {cur_s[j], nullptr, fs.tap_convs1 ? h->tap_scratch + (size_t)n * fs.tap_se : nullptr, mid};
+            io2[n] = {mid, d == 0 ? ws.u : xres[j], xres[j], last ? nullptr : lbl_out[n]};
+            if (!add_convs) {  // one conv per layer: conv1 carries the residual epilogue; its activated output is the next layer's input
+                char* nxt = tp ? tp->x_s[i][j][d] : pair_out[n];
+                io1[n] = {cur_s[j], d == 0 ? ws.u : xres[j], xres[j], last ? nullptr : nxt};
+                lbl_out[n] = nxt;
+            }
+            iop[n] = {nullptr, cur_s[j], d == 0 ? ws.u : xres[j], xres[j], last ? nullptr : pair_out[n]};
+        }
+        if (fuse) {
+            if ((rc = launch_n(h, l1, l2, br.n, B, rows, nullptr, iop, cfg.lrelu_slope, fs.rg, k.stream)) != HIFICAR_OK) return rc;
+        } else {
+            if ((rc = launch_n(h, l1, nullptr, br.n, B, rows, io1, nullptr, cfg.lrelu_slope, fs.rg, k.stream)) != HIFICAR_OK) return rc;
+            if (add_convs && fs.tap_convs1)
+                for (int q = 0; q < br.n; ++q)
+                    if ((rc = emit_tap(h, "blocks." + std::to_string(i * nbk + br.j[q]) + ".convs1." + std::to_string(d), io1[q].y, Cp, 0, Cs,
+                                       B, rows, 0, k.stream)) != HIFICAR_OK)
+                        return rc;
+            if (add_convs && (rc = launch_n(h, l2, nullptr, br.n, B, rows, io2, nullptr, cfg.lrelu_slope, fs.rg, k.stream)) != HIFICAR_OK) return rc;
+        }
+        for (int q = 0; q < br.n; ++q)
+            if ((rc = tap_block(h, k, fs, i, br.j[q], d, xres[br.j[q]])) != HIFICAR_OK) return rc;
+        for (int q = 0; q < br.n; ++q) cur_s[br.j[q]] = fuse ? pair_out[q] : lbl_out[q];
+    }
+    return HIFICAR_OK;
+}
+
+// 3. one HiFi-GAN stage: MRF mean of the stage before -> upsampler -> ResBlocks side by side.  fs.rows / fs.fin: this stage's on return
+static int forward_stage(hificar_handle* h, const FwdCall& k, FwdState& fs, int i) {
+    const hificar_config& cfg = h->cfg;
+    const Tape* const tp = k.tp;
+    const int nbk = cfg.n_blocks;
+    int rc;
+    const char* up_in = act_h0(k);
+    // MRF mean of the previous stage (hifigan.py:226-230).  Exact fp32 inference: folded into the upsampler's staging (ConvIO::x_more — its
+    // loader waves read the blocks' fp32 streams, sum, divide, activate), so no launch and no buffer for the mean exist.  Training (the tape keeps
+    // the activated mean for the upsampler's weight gradient) and bf16x3 (split rows): mrf_split_kernel.
+    const bool fold_mrf = i > 0 && h->precision == HIFICAR_PREC_F32 && !tp;
+    if (i > 0 && !fold_mrf && (rc = launch_mrf_split(h, k, fs, i, &up_in)) != HIFICAR_OK) return rc;
+    // Whether every layer pair of the stage runs in the fused kernel (resblocks_all_pairs) or not (resblocks_general)
+    bool all_pairs = !fs.tap_convs1 && !tp && cfg.use_additional_convs != 0;
+    for (int j = 0; j < nbk && all_pairs; ++j)
+        for (int d = 0; d < cfg.n_dilations[j]; ++d) {
+            const int ci = conv_index(h, i, j, d);
+            all_pairs = all_pairs && pair_eligible(h, h->convs1[ci], h->convs2[ci], k.B, fs.rows * cfg.upsample_scales[i]);
+        }
+    char* const u_act = tp ? tp->u_s[i] : k.ws.u_s;
+    {   // LeakyReLU + ConvTranspose1d (hifigan.py:224): fp32 u (first residual) (+ activated copy: first conv input)
+        const ConvLayer* lay[1] = {&h->ups[i]};
+        ConvIO io[1] = {{up_in, nullptr, k.ws.u, all_pairs ? nullptr : u_act}};
+        if (fold_mrf) {
+            io[0].xs = reinterpret_cast<const char*>(fs.fin[0]);
+            io[0].x_slope = cfg.lrelu_slope;
+            io[0].x_n = nbk;
+            for (int j = 1; j < nbk; ++j) io[0].x_more[j - 1] = fs.fin[j];
+        }
+        if ((rc = launch_conv(h, lay, 1, k.B, fs.rows, io, cfg.lrelu_slope, fs.rg, k.stream)) != HIFICAR_OK) return rc;
+    }
+    fs.rows *= cfg.upsample_scales[i];
+    if (fs.tapping && (rc = emit_tap(h, "upsamples." + std::to_string(i), k.ws.u, stage_pad(cfg, i + 1), 0, stage_channels(cfg, i + 1), k.B, fs.rows, 0,
+                                     k.stream)) != HIFICAR_OK)
+        return rc;
+    return all_pairs ? resblocks_all_pairs(h, k, fs, i) : resblocks_general(h, k, fs, i, u_act);
+}
+
+// phoneme-loss head on the last stage's MRF mean (hifigan.py:232-237)
+static int launch_ph_head(hificar_handle* h, const FwdCall& k, const FwdState& fs) {
+    const hificar_config& cfg = h->cfg;
+    const int nbk = cfg.n_blocks;
+    PhHeadParams pq;
+    memset(&pq, 0, sizeof(pq));
+    fill_inputs(pq, fs.fin, nbk);
+    pq.w = h->d_phfc_w;
+    pq.bias = h->d_phfc_b;
+    pq.out = k.ph_out;
+    pq.C = stage_channels(cfg, cfg.n_stages);
+    pq.Cp = stage_pad(cfg, cfg.n_stages);
+    pq.L = fs.rows;
+    pq.T = k.ph_out_T;
+    pq.hop = h->hop;
+    pq.num_ph = cfg.num_ph;
+    pq.seq_len = k.seq_len;
+    pq.len_const = k.seq_len ? -1 : (k.T_valid < k.T ? k.T_valid : -1);
+    ProfScope prof(h, k.stream, "ph_head_kernel", 2.0 * k.B * k.T_valid * (double)pq.C * cfg.num_ph, 4.0 * k.B * (double)fs.rows * pq.Cp * nbk);
+    hipLaunchKernelGGL(ph_head_kernel, dim3(k.T_valid, k.B), dim3(256), 0, k.stream, pq);
+    HIP_TRY(hipGetLastError());
+    return HIFICAR_OK;
+}
+
+// One generator forward: every generator path ends here.
+static int forward_impl(hificar_handle* h, FwdCall k) {
+    const hificar_config& cfg = h->cfg;
+    if (k.T_valid < 0) k.T_valid = k.T;
+    FwdState fs;
+    fs.rg = ragged_of(k);
+    int rc;
+    if ((rc = launch_front(h, k)) != HIFICAR_OK) return rc;
+    if (h->arch == 1) return gblock_forward(h, k, fs.rg);
+
+    fs.bo = block_order(cfg);
+    fs.rows = k.T;
+    for (int j = 0; j < kMaxBlk; ++j) fs.fin[j] = k.ws.x[j];
+    fs.tapping = !h->taps.empty();
+    if (fs.tapping) {
+        const bool f32 = h->precision == HIFICAR_PREC_F32;
+        for (auto& kv : h->taps) fs.tap_convs1 = fs.tap_convs1 || kv.first.find(".convs1.") != std::string::npos;
+        fs.tap_se = stage_elems(h, k.B, k.T);
+        // pre-activation copies that the normal path never writes: 3 stage-sized scratch buffers
+        if ((rc = grow_tap_scratch(h, kMaxBlk * fs.tap_se + (size_t)k.B * k.T * stage_pad(cfg, 0))) != HIFICAR_OK) return rc;
+        if (cfg.use_ar && (rc = emit_tap(h, "ar_feats", k.ws.xin, f32 ? h->cin_pad : -h->cin_pad, h->cf, cfg.ar_output, k.B, 1, f32 ? 0 : 1, k.stream, k.T)) != HIFICAR_OK)
             return rc;
     }
-    const size_t tap_se = tapping ? stage_elems(h, B, T) : 0;
-    const int nbk = cfg.n_blocks;
-    // residual blocks of a stage run side by side, heaviest kernel size first
-    int order[kMaxBlk];
-    for (int j = 0; j < kMaxBlk; ++j) order[j] = j;
-    std::sort(order, order + nbk, [&](int a, int b) { return cfg.resblock_kernel_sizes[a] > cfg.resblock_kernel_sizes[b]; });
-    int max_d = 0;
-    for (int j = 0; j < nbk; ++j) max_d = std::max(max_d, cfg.n_dilations[j]);
-    int rows_of_launch = 0;  // (conv_n: the stage's row count at the time of the call)
-    const bool add_convs = cfg.use_additional_convs != 0;  // false: a ResBlock layer is x = x + conv1(LeakyReLU(x)) (residual_block.py:217-221)
-    // a launch carries up to three branches (MultiConvParams / PairParams): a fourth residual block rides in a second launch
-    auto conv_n = [&](const ConvLayer* const* lay, int n, const ConvIO* io) -> int {
-        for (int q0 = 0; q0 < n; q0 += 3) {
-            const int r = launch_conv(h, lay + q0, std::min(3, n - q0), B, rows_of_launch, io + q0, cfg.lrelu_slope, rg, stream);
-            if (r != HIFICAR_OK) return r;
-        }
-        return HIFICAR_OK;
-    };
-
-    const float* fin[kMaxBlk] = {ws.x[0], ws.x[1], ws.x[2], ws.x[3]};  // where each branch's ResBlock output of the current stage lives
-    {
-        // Activations travel between layers already activated — split rows (bf16x3) or plain fp32 rows (exact fp32), the
-        // "_s" buffers — and are staged by LDS-DMA; the layer's own fp32 value only where a residual / the MRF mean needs it
-        char* xin_s = tp ? reinterpret_cast<char*>(tp->xin) : reinterpret_cast<char*>(ws.xin);
-        char* h0_s = tp ? tp->h0_s : reinterpret_cast<char*>(ws.h0);
-        char* xt_s[kMaxBlk] = {reinterpret_cast<char*>(ws.xt[0]), reinterpret_cast<char*>(ws.xt[1]), reinterpret_cast<char*>(ws.xt[2]),
-                               reinterpret_cast<char*>(ws.xt[3])};
-        {   // 2. input conv (no activation in front of it: hifigan.py:221); its consumer applies LeakyReLU(slope)
-            const ConvLayer* lay[1] = {&h->input_conv};
-            float* y_tap = tap_wanted(h, "input_conv") ? h->tap_scratch + kMaxBlk * tap_se : nullptr;
-            const ConvIO io[1] = {{xin_s, nullptr, y_tap, h0_s}};
-            if ((rc = launch_conv(h, lay, 1, B, T, io, cfg.lrelu_slope, rg, stream)) != HIFICAR_OK) return rc;
-            if (y_tap && (rc = emit_tap(h, "input_conv", y_tap, stage_pad(cfg, 0), 0, cfg.channels, B, T, 0, stream)) != HIFICAR_OK) return rc;
-        }
-        for (int i = 0; i < cfg.n_stages; ++i) {
-            const char* up_in = h0_s;
-            // MRF mean of the previous stage (hifigan.py:226-230).  Exact fp32 inference: folded into the upsampler's staging (ConvIO::x_more — its
-            // loader waves read the blocks' fp32 streams, sum, divide, activate), so no launch and no buffer for the mean exist.  Training (the tape keeps
-            // the activated mean for the upsampler's weight gradient) and bf16x3 (split rows): mrf_split_kernel.
-            const bool fold_mrf = i > 0 && f32 && !tp;
-            if (i > 0 && !fold_mrf) {
-                MrfSplitParams mq;
-                memset(&mq, 0, sizeof(mq));
-                mq.x0 = fin[0];
-                mq.x1 = nbk > 1 ? fin[1] : nullptr;
-                mq.x2 = nbk > 2 ? fin[2] : nullptr;
-                mq.x3 = nbk > 3 ? fin[3] : nullptr;
-                mq.out = fin[0] == ws.xt[0] ? ws.x_s[0] : xt_s[0];  // a buffer none of the inputs lives in
-                if (tp) mq.out = tp->upin_s[i];
-                mq.nin = nbk;
-                mq.C = stage_pad(cfg, i);
-                mq.rows = (long long)B * rows;
-                mq.slope = cfg.lrelu_slope;
-                mq.f32 = f32 ? 1 : 0;
-                const long long units = mq.rows * (mq.C / 8);
-                const unsigned blocks = (unsigned)std::min<long long>((units + 255) / 256, 8LL * h->num_cus);
-                {
-                    ProfScope prof(h, stream, "mrf_split_kernel", 0.0, 4.0 * mq.rows * mq.C * (nbk + 1));
-                    hipLaunchKernelGGL(mrf_split_kernel, dim3(blocks), dim3(256), 0, stream, mq);
-                }
-                HIP_TRY(hipGetLastError());
-                up_in = mq.out;
-            }
-            // Narrow stage whose every layer pair runs in the fused kernel: the residual stream stays fp32-only (the pair
-            // kernel activates + splits its input while staging), ping-ponging between x[j] and xt[j]; no activated copies
-            // are written at all.  Otherwise: activated copies ("_s") travel next to the fp32 stream.
-            bool all_pairs = !tap_convs1 && !tp && add_convs;
-            for (int j = 0; j < nbk && all_pairs; ++j)
-                for (int d = 0; d < cfg.n_dilations[j]; ++d) {
-                    const int ci = conv_index(h, i, j, d);
-                    all_pairs = all_pairs && pair_eligible(h, h->convs1[ci], h->convs2[ci], B, rows * cfg.upsample_scales[i]);
-                }
-            {   // LeakyReLU + ConvTranspose1d (hifigan.py:224): fp32 u (first residual) (+ activated copy: first conv input)
-                const ConvLayer* lay[1] = {&h->ups[i]};
-                ConvIO io[1] = {{up_in, nullptr, ws.u, all_pairs ? nullptr : (tp ? tp->u_s[i] : ws.u_s)}};
-                if (fold_mrf) {
-                    io[0].xs = reinterpret_cast<const char*>(fin[0]);
-                    io[0].x_slope = cfg.lrelu_slope;
-                    io[0].x_n = nbk;
-                    for (int j = 1; j < nbk; ++j) io[0].x_more[j - 1] = fin[j];
-                }
-                if ((rc = launch_conv(h, lay, 1, B, rows, io, cfg.lrelu_slope, rg, stream)) != HIFICAR_OK) return rc;
-            }
-            rows *= cfg.upsample_scales[i];
-            const int Cs = stage_channels(cfg, i + 1), Cp = stage_pad(cfg, i + 1);
-            if (tapping && (rc = emit_tap(h, "upsamples." + std::to_string(i), ws.u, Cp, 0, Cs, B, rows, 0, stream)) != HIFICAR_OK) return rc;
-            auto tap_block = [&](int j, int d, const float* xcur) -> int {  // residual stream of block j after dilation d
-                if (!tapping) return HIFICAR_OK;
-                const std::string base = "blocks." + std::to_string(i * nbk + j);
-                int r = emit_tap(h, base + ".x." + std::to_string(d), xcur, Cp, 0, Cs, B, rows, 0, stream);
-                if (r == HIFICAR_OK && d + 1 == cfg.n_dilations[j]) r = emit_tap(h, base, xcur, Cp, 0, Cs, B, rows, 0, stream);
-                return r;
-            };
-            if (all_pairs) {
-                const float* cur_f[kMaxBlk] = {ws.u, ws.u, ws.u, ws.u};
-                for (int d = 0; d < max_d; ++d) {  // residual_block.py:217-221
-                    const ConvLayer* l1[kMaxBlk];
-                    const ConvLayer* l2[kMaxBlk];
-                    PairIOB iop[kMaxBlk];
-                    int n = 0;
-                    for (int oj = 0; oj < nbk; ++oj) {
-                        const int j = order[oj];
-                        if (d >= cfg.n_dilations[j]) continue;
-                        const int ci = conv_index(h, i, j, d);
-                        l1[n] = &h->convs1[ci];
-                        l2[n] = &h->convs2[ci];
-                        // a tile's output pass must not overwrite rows a neighbouring tile still reads as halo: out != in
-                        float* out_f = cur_f[j] == ws.x[j] ? ws.xt[j] : ws.x[j];
-                        iop[n] = {cur_f[j], nullptr, cur_f[j], out_f, nullptr};
-                        cur_f[j] = out_f;
-                        ++n;
-                    }
-                    for (int q0 = 0; q0 < n; q0 += 3)
-                        if ((rc = launch_pair(h, l1 + q0, l2 + q0, std::min(3, n - q0), B, rows, iop + q0, cfg.lrelu_slope, rg, stream)) != HIFICAR_OK) return rc;
-                    for (int j = 0; j < nbk; ++j)
-                        if (d < cfg.n_dilations[j] && (rc = tap_block(j, d, cur_f[j])) != HIFICAR_OK) return rc;
-                }
-                for (int j = 0; j < nbk; ++j) fin[j] = cur_f[j];
-                continue;
-            }
-            // fp32 residual streams; training keeps the LAST stage's (the output conv's backward needs the MRF mean) in the tape
-            float* xres[kMaxBlk] = {ws.x[0], ws.x[1], ws.x[2], ws.x[3]};
-            if (tp && i + 1 == cfg.n_stages)
-                for (int j = 0; j < nbk; ++j) xres[j] = tp->fin[j];
-            for (int j = 0; j < nbk; ++j) fin[j] = xres[j];
-            // activated stream of each branch: where the next conv1 reads its input.  It alternates between x_s[j] and
-            // xt_s[j]: a launch never writes the buffer it (or a neighbouring tile, through the halo) reads.
-            const char* u_act = tp ? tp->u_s[i] : ws.u_s;
-            const char* cur_s[kMaxBlk] = {u_act, u_act, u_act, u_act};
-            for (int d = 0; d < max_d; ++d) {  // residual_block.py:217-221
-                const ConvLayer* l1[kMaxBlk];
-                const ConvLayer* l2[kMaxBlk];
-                ConvIO io1[kMaxBlk], io2[kMaxBlk];
-                PairIOB iop[kMaxBlk];
-                int jn[kMaxBlk];
-                char* pair_out[kMaxBlk];
-                char* lbl_out[kMaxBlk];
-                int n = 0;
-                bool fuse = add_convs;
-                for (int oj = 0; oj < nbk; ++oj) {
-                    const int j = order[oj];
-                    if (d >= cfg.n_dilations[j]) continue;
-                    const int ci = conv_index(h, i, j, d);
-                    l1[n] = &h->convs1[ci];
-                    l2[n] = add_convs ? &h->convs2[ci] : nullptr;
-                    fuse = fuse && !tap_convs1 && !tp && pair_eligible(h, *l1[n], *l2[n], B, rows);
-                    const bool last = d + 1 == cfg.n_dilations[j];
-                    // fused pair: cur -> the other buffer.  Layer by layer: cur -> mid -> the buffer that is not mid.
-                    pair_out[n] = cur_s[j] == ws.x_s[j] ? xt_s[j] : ws.x_s[j];
-                    char* mid = cur_s[j] == xt_s[j] ? ws.x_s[j] : xt_s[j];
-                    lbl_out[n] = mid == xt_s[j] ? ws.x_s[j] : xt_s[j];
-                    if (tp) {  // training: unique buffers, kept for the backward pass
-                        mid = tp->xt_s[i][j][d];
-                        lbl_out[n] = tp->x_s[i][j][d];
-                    }
-                    io1[n] = {cur_s[j], nullptr, tap_convs1 ? h->tap_scratch + (size_t)n * tap_se : nullptr, mid};
-                    io2[n] = {mid, d == 0 ? ws.u : xres[j], xres[j], last ? nullptr : lbl_out[n]};
-                    if (!add_convs) {  // one conv per layer: conv1 carries the residual epilogue; its activated output is the next layer's input
-                        char* nxt = tp ? tp->x_s[i][j][d] : pair_out[n];
-                        io1[n] = {cur_s[j], d == 0 ? ws.u : xres[j], xres[j], last ? nullptr : nxt};
-                        lbl_out[n] = nxt;
-                    }
-                    iop[n] = {nullptr, cur_s[j], d == 0 ? ws.u : xres[j], xres[j], last ? nullptr : pair_out[n]};
-                    jn[n] = j;
-                    ++n;
-                }
-                if (fuse) {
-                    for (int q0 = 0; q0 < n; q0 += 3)
-                        if ((rc = launch_pair(h, l1 + q0, l2 + q0, std::min(3, n - q0), B, rows, iop + q0, cfg.lrelu_slope, rg, stream)) != HIFICAR_OK) return rc;
-                } else if (!add_convs) {
-                    rows_of_launch = rows;
-                    if ((rc = conv_n(l1, n, io1)) != HIFICAR_OK) return rc;
-                } else {
-                    rows_of_launch = rows;
-                    if ((rc = conv_n(l1, n, io1)) != HIFICAR_OK) return rc;
-                    if (tap_convs1)
-                        for (int q = 0; q < n; ++q)
-                            if ((rc = emit_tap(h, "blocks." + std::to_string(i * nbk + jn[q]) + ".convs1." + std::to_string(d), io1[q].y, Cp, 0, Cs,
-                                               B, rows, 0, stream)) != HIFICAR_OK)
-                                return rc;
-                    if ((rc = conv_n(l2, n, io2)) != HIFICAR_OK) return rc;
-                }
-                for (int q = 0; q < n; ++q)
-                    if ((rc = tap_block(jn[q], d, xres[jn[q]])) != HIFICAR_OK) return rc;
-                for (int q = 0; q < n; ++q) cur_s[jn[q]] = fuse ? pair_out[q] : lbl_out[q];
-            }
-        }
-    }
-    if (cfg.use_ph_loss && cond.ph_out) {  // phoneme-loss head on the last stage's MRF mean (hifigan.py:232-237)
-        PhHeadParams pq;
-        memset(&pq, 0, sizeof(pq));
-        pq.x0 = fin[0];
-        pq.x1 = nbk > 1 ? fin[1] : nullptr;
-        pq.x2 = nbk > 2 ? fin[2] : nullptr;
-        pq.x3 = nbk > 3 ? fin[3] : nullptr;
-        pq.nin = nbk;
-        pq.w = h->d_phfc_w;
-        pq.bias = h->d_phfc_b;
-        pq.out = cond.ph_out;
-        pq.C = stage_channels(cfg, cfg.n_stages);
-        pq.Cp = stage_pad(cfg, cfg.n_stages);
-        pq.L = rows;
-        pq.T = cond.ph_out_T;
-        pq.hop = h->hop;
-        pq.num_ph = cfg.num_ph;
-        pq.seq_len = seq_len;
-        pq.len_const = seq_len ? -1 : (T_valid < T ? T_valid : -1);
-        ProfScope prof(h, stream, "ph_head_kernel", 2.0 * B * T_valid * (double)pq.C * cfg.num_ph, 4.0 * B * (double)rows * pq.Cp * nbk);
-        hipLaunchKernelGGL(ph_head_kernel, dim3(T_valid, B), dim3(256), 0, stream, pq);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = forward_input_conv(h, k, fs)) != HIFICAR_OK) return rc;
+    for (int i = 0; i < cfg.n_stages; ++i)
+        if ((rc = forward_stage(h, k, fs, i)) != HIFICAR_OK) return rc;
+    if (cfg.use_ph_loss && k.ph_out && (rc = launch_ph_head(h, k, fs)) != HIFICAR_OK) return rc;
     // 4. output conv: LeakyReLU(0.01) + Conv1d + tanh (hifigan.py:146-159)
-    return launch_output_conv(h, fin, nbk, stage_pad(cfg, cfg.n_stages), rows, B, T, out, out_bstride, seq_len, rg, slots, stream);
+    return launch_output_conv(h, k, fs.rg, fs.fin, cfg.n_blocks, stage_pad(cfg, cfg.n_stages), fs.rows);
+}
+
+// The record of a forward over whole utterances of T frames: (B, cf, T) features, (B, ar_input) AR context, (B, hop T) waveform; T and ws: the caller
+static FwdCall whole_call(const hificar_handle* h, const float* c, const float* ar, const int32_t* spk_id, const int32_t* ph, float* out, float* ph_out,
+                          int B, int T, hipStream_t stream) {
+    FwdCall k;
+    k.c = c;
+    k.c_bstride = (int64_t)h->cf * T;
+    k.c_cstride = T;
+    k.prev = h->cfg.use_ar ? ar : nullptr;
+    k.prev_bstride = h->cfg.ar_input;
+    k.out = out;
+    k.out_bstride = (int64_t)h->hop * T;
+    k.B = B;
+    k.T_valid = T;
+    k.spk_id = spk_id;
+    k.ph = ph;
+    k.ph_stride = T;
+    k.ph_out = ph_out;
+    k.ph_out_T = T;
+    k.stream = stream;
+    return k;
 }
 
 static int check_ready(hificar_handle* h, int B, int T, void* ws, size_t ws_bytes) {
@@ -1897,17 +2014,12 @@ extern "C" int hificar_forward_cond(hificar_handle* h, const float* c, const flo
     if (h->cfg.use_ar && !ar) return fail(HIFICAR_E_INVALID, "use_ar model needs the ar context (got NULL)");
     if (h->cfg.use_spk_id && !spk_id) return fail(HIFICAR_E_INVALID, "use_spk_id model needs spk_id (got NULL)");
     if (h->cfg.use_ph && !ph) return fail(HIFICAR_E_INVALID, "use_ph model needs ph (got NULL)");
-    Cond cond;
-    cond.spk_id = spk_id;
-    cond.ph = ph;
-    cond.ph_stride = T;
-    cond.ph_out = ph_out;
-    cond.ph_out_T = T;
     if ((rc = enter_stream(h, static_cast<hipStream_t>(stream))) != HIFICAR_OK) return rc;
-    const int Tb = bucket_frames(T);
-    const Workspace ws = plan_workspace(h, B, Tb, workspace);
-    return forward_impl(h, c, (int64_t)h->cf * T, T, h->cfg.use_ar ? ar : nullptr, h->cfg.ar_input, out,
-                        (int64_t)h->hop * T, B, Tb, ws, static_cast<hipStream_t>(stream), lengths, 0, nullptr, T, cond);
+    FwdCall k = whole_call(h, c, ar, spk_id, ph, out, ph_out, B, T, static_cast<hipStream_t>(stream));
+    k.T = bucket_frames(T);
+    k.seq_len = lengths;
+    k.ws = plan_workspace(h, B, k.T, workspace);
+    return forward_impl(h, k);
 }
 
 extern "C" int hificar_forward_ragged(hificar_handle* h, const float* c, const float* ar, const int32_t* lengths, float* out, int B,
@@ -1922,8 +2034,10 @@ extern "C" int hificar_forward(hificar_handle* h, const float* c, const float* a
     return hificar_forward_ragged(h, c, ar, nullptr, out, B, T, workspace, workspace_bytes, stream);
 }
 
-// The conditioning pointers of a *_cond AR entry point against the model: each is needed exactly when the model uses it.
-static int check_cond_args(const hificar_handle* h, const char* who, const void* spk, const void* ph) {
+// The first checks of every *_cond AR entry point: the model runs autoregressively (who_ar names the family in that refusal), and each
+// conditioning pointer is there exactly when the model uses it.
+static int check_ar_model(const hificar_handle* h, const char* who_ar, const char* who, const void* spk, const void* ph) {
+    if (!h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "%s on a model built with use_ar=false", who_ar);
     if (h->cfg.use_spk_id && !spk) return fail(HIFICAR_E_INVALID, "%s: use_spk_id model needs spk_id (got NULL)", who);
     if (h->cfg.use_ph && !ph) return fail(HIFICAR_E_INVALID, "%s: use_ph model needs ph (got NULL)", who);
     if (!h->cfg.use_spk_id && spk) return fail(HIFICAR_E_INVALID, "%s: spk_id given to a model built with use_spk_id=false", who);
@@ -1931,98 +2045,116 @@ static int check_cond_args(const hificar_handle* h, const char* who, const void*
     return HIFICAR_OK;
 }
 
+// A loop of more than one chunk feeds the last ar_input samples of a chunk's audio to the next chunk
+static int check_ar_chunk(const hificar_handle* h, int chunk_frames, bool more_chunks) {
+    if (h->cfg.ar_input > h->hop * chunk_frames && more_chunks)
+        return fail(HIFICAR_E_INVALID, "ar_input (%d) > chunk audio length (%d): the reference loop (decode.py:79-81) is ill-formed there",
+                    h->cfg.ar_input, h->hop * chunk_frames);
+    return HIFICAR_OK;
+}
+
+static int check_lengths(const int32_t* lengths_host, int n, int T_max) {
+    for (int b = 0; b < n; ++b)
+        if (lengths_host[b] < 0 || lengths_host[b] > T_max)
+            return fail(HIFICAR_E_INVALID, "lengths[%d]=%d outside [0, %d]", b, lengths_host[b], T_max);
+    return HIFICAR_OK;
+}
+
+// The record of chunk f0 of hificar_ar_loop for the Bn utterances from b0 on of a batch of (B, cf, T_total) features and (B, hop T_total) audio
+static FwdCall ar_chunk_call(const hificar_handle* h, const float* c, const int32_t* spk_id, const int32_t* ph, float* out, int T_total, int chunk_frames,
+                             int f0, int b0, int Bn, void* workspace, hipStream_t stream) {
+    FwdCall k;
+    k.c_bstride = (int64_t)h->cf * T_total;
+    k.c_cstride = T_total;
+    k.prev_bstride = k.out_bstride = (int64_t)h->hop * T_total;
+    const int64_t pos = b0 * k.out_bstride + (int64_t)h->hop * f0;
+    k.c = c + (size_t)b0 * h->cf * T_total + f0;
+    // prev = last ar_input samples already written for this utterance (zeros for the first chunk)
+    k.prev = f0 == 0 ? nullptr : out + pos - h->cfg.ar_input;
+    k.out = out + pos;
+    k.B = Bn;
+    k.T = std::min(chunk_frames, T_total - f0);
+    k.f0 = f0;
+    // chunk f0 of utterance b reads spk_id[b] and ph[b, f0 + t]
+    k.spk_id = spk_id ? spk_id + b0 : nullptr;
+    k.ph = ph ? ph + (size_t)b0 * T_total + f0 : nullptr;
+    k.ph_stride = T_total;
+    k.ws = plan_workspace(h, Bn, k.T, workspace);
+    k.stream = stream;
+    return k;
+}
+
+// The loop of a mid-size batch on TWO streams (round 4).  Utterances do not depend on each other, and a step is a chain of 34 dependent launches whose tile
+// lists quantise badly between batch 17 and 62 (a 25-frame chunk is ONE 128-row tile per utterance at the widest stage: 6 B tiles of weight
+// 11 : 7 : 3 for 256 workgroups — batch 44 to 64 all take the same 11 units): the two halves of the batch run their own chains on two streams
+// and each half's idle workgroups, launch latencies and tails are filled by the other half's kernels.  Measured (10-s clips, chunk 25, fp32,
+// single / dual ms per step): batch 18 108.2 / 103.4, 22 130.3 / 122.6, 28 146.3 / 135.3, 32 153.1 / 142.2, 36 184.6 / 171.3, 44 224.8 / 201.5,
+// 48 225.4 / 214.7, 56 263.7 / 239.2, 60 266.2 / 258.8; below the window the halves' launches are less efficient than the whole batch's
+// (batch 8: 58.1 / 68.1, 4: 44.2 / 48.4, 16: 90.7 / 91.6), at 64 the tile lists are full (269.3 / 276.5).  Same kernels, same per-utterance
+// arithmetic up to the launch-shape dependence HIFICAR_KSPLIT=0 removes.  Not while profiling or tapping (one stream's events / scratch), not for
+// ragged batches (their steps shrink the batch prefix).
+// ws0_bytes: the first half's workspace; the second half's follows it.
+static int ar_loop_two_streams(hificar_handle* h, const float* c, const int32_t* spk_id, const int32_t* ph, float* out, int B, int T_total,
+                               int chunk_frames, void* workspace, size_t ws0_bytes, hipStream_t s0) {
+    if (!h->ar_side) {
+        HIP_TRY(hipStreamCreateWithFlags(&h->ar_side, hipStreamNonBlocking));
+        for (hipEvent_t& e : h->ar_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    const hipStream_t s1 = h->ar_side;
+    HIP_TRY(hipEventRecord(h->ar_ev[0], s0));  // fork: the side stream starts behind the caller's work so far
+    HIP_TRY(hipStreamWaitEvent(s1, h->ar_ev[0], 0));
+    // The halves' launches share the chip, so a launch's own exact makespan is the wrong yardstick for its tile shape (measured: with the
+    // simulated makespan the halves pick shapes that fill the chip alone and batch 32 / 44 lose 5 / 4 %; choosing by workgroup-time as the
+    // discriminators' engine does loses 20-30 %): they keep the closed-form estimate.  (Reset below on every path: nothing in between returns.)
+    h->shared_chip = true;
+    unsigned long long seen = h->sched_up_seq;
+    // a tile schedule first needed by one half is uploaded on that half's stream: the other stream must not use it before it has landed
+    auto publish = [&](hipStream_t from, hipStream_t to, hipEvent_t ev) -> int {
+        if (h->sched_up_seq != seen) {
+            HIP_TRY(hipEventRecord(ev, from));
+            HIP_TRY(hipStreamWaitEvent(to, ev, 0));
+            seen = h->sched_up_seq;
+        }
+        return HIFICAR_OK;
+    };
+    const int B0 = (B + 1) / 2;  // the second half's rows start at B0, its workspace behind the first half's
+    char* const wsp1 = static_cast<char*>(workspace) + ws0_bytes;
+    int rc = HIFICAR_OK;
+    for (int f0 = 0; f0 < T_total && rc == HIFICAR_OK; f0 += chunk_frames) {
+        rc = forward_impl(h, ar_chunk_call(h, c, spk_id, ph, out, T_total, chunk_frames, f0, 0, B0, workspace, s0));
+        if (rc == HIFICAR_OK) rc = publish(s0, s1, h->ar_ev[0]);
+        if (rc == HIFICAR_OK) rc = forward_impl(h, ar_chunk_call(h, c, spk_id, ph, out, T_total, chunk_frames, f0, B0, B - B0, wsp1, s1));
+        if (rc == HIFICAR_OK) rc = publish(s1, s0, h->ar_ev[1]);
+    }
+    h->shared_chip = false;
+    // join (also on an error return: the caller's stream must stay ordered behind what the side stream was given)
+    if (hipEventRecord(h->ar_ev[1], s1) != hipSuccess || hipStreamWaitEvent(s0, h->ar_ev[1], 0) != hipSuccess)
+        return rc != HIFICAR_OK ? rc : fail(HIFICAR_E_HIP, "hificar_ar_loop: joining the side stream failed");
+    return rc;
+}
+
 extern "C" int hificar_ar_loop_cond(hificar_handle* h, const float* c, const int32_t* spk_id, const int32_t* ph, const int32_t* lengths,
                                     const int32_t* lengths_host, float* out, int B, int T_total, int chunk_frames, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    if (h && !h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_loop on a model built with use_ar=false");
-    if (h && check_cond_args(h, "hificar_ar_loop", spk_id, ph) != HIFICAR_OK) return HIFICAR_E_INVALID;
+    int rc;
+    if (h && (rc = check_ar_model(h, "hificar_ar_loop", "hificar_ar_loop", spk_id, ph)) != HIFICAR_OK) return rc;
     if (chunk_frames < 1) return fail(HIFICAR_E_INVALID, "chunk_frames=%d must be positive", chunk_frames);
-    int rc = check_ready(h, B, std::min(chunk_frames, std::max(T_total, 1)), workspace, workspace_bytes);
-    if (rc != HIFICAR_OK) return rc;
+    if ((rc = check_ready(h, B, std::min(chunk_frames, std::max(T_total, 1)), workspace, workspace_bytes)) != HIFICAR_OK) return rc;
     if (T_total < 1) return fail(HIFICAR_E_INVALID, "T_total=%d must be positive", T_total);
     if (!c || !out) return fail(HIFICAR_E_INVALID, "hificar_ar_loop: null tensor");
-    if (h->cfg.ar_input > h->hop * chunk_frames && T_total > chunk_frames)
-        return fail(HIFICAR_E_INVALID, "ar_input (%d) > chunk audio length (%d): the reference loop (decode.py:79-81) is ill-formed there",
-                    h->cfg.ar_input, h->hop * chunk_frames);
-    if ((rc = enter_stream(h, static_cast<hipStream_t>(stream))) != HIFICAR_OK) return rc;
-    const int64_t out_bstride = (int64_t)h->hop * T_total;
-    if (lengths_host && !lengths) return fail(HIFICAR_E_INVALID, "hificar_ar_loop_ragged: lengths_host without the device copy");
-    if (lengths_host)
-        for (int b = 0; b < B; ++b)
-            if (lengths_host[b] < 0 || lengths_host[b] > T_total)
-                return fail(HIFICAR_E_INVALID, "lengths[%d]=%d outside [0, %d]", b, lengths_host[b], T_total);
-    // Mid-size batches on TWO streams (round 4).  Utterances do not depend on each other, and a step is a chain of 34 dependent launches whose tile
-    // lists quantise badly between batch 17 and 62 (a 25-frame chunk is ONE 128-row tile per utterance at the widest stage: 6 B tiles of weight
-    // 11 : 7 : 3 for 256 workgroups — batch 44 to 64 all take the same 11 units): the two halves of the batch run their own chains on two streams
-    // and each half's idle workgroups, launch latencies and tails are filled by the other half's kernels.  Measured (10-s clips, chunk 25, fp32,
-    // single / dual ms per step): batch 18 108.2 / 103.4, 22 130.3 / 122.6, 28 146.3 / 135.3, 32 153.1 / 142.2, 36 184.6 / 171.3, 44 224.8 / 201.5,
-    // 48 225.4 / 214.7, 56 263.7 / 239.2, 60 266.2 / 258.8; below the window the halves' launches are less efficient than the whole batch's
-    // (batch 8: 58.1 / 68.1, 4: 44.2 / 48.4, 16: 90.7 / 91.6), at 64 the tile lists are full (269.3 / 276.5).  Same kernels, same per-utterance
-    // arithmetic up to the launch-shape dependence HIFICAR_KSPLIT=0 removes.  Not while profiling or tapping (one stream's events / scratch), not for
-    // ragged batches (their steps shrink the batch prefix).
+    if ((rc = check_ar_chunk(h, chunk_frames, T_total > chunk_frames)) != HIFICAR_OK) return rc;
     const hipStream_t s0 = static_cast<hipStream_t>(stream);
+    if ((rc = enter_stream(h, s0)) != HIFICAR_OK) return rc;
+    if (lengths_host && !lengths) return fail(HIFICAR_E_INVALID, "hificar_ar_loop_ragged: lengths_host without the device copy");
+    if (lengths_host && (rc = check_lengths(lengths_host, B, T_total)) != HIFICAR_OK) return rc;
     const int Tn_max = std::min(chunk_frames, T_total);
-    const int B0 = (B + 1) / 2, B1 = B - B0;
-    const size_t ws0_bytes = plan_workspace(h, B0, Tn_max, nullptr).bytes;
+    const size_t ws0_bytes = plan_workspace(h, (B + 1) / 2, Tn_max, nullptr).bytes;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s0, &cap);  // (a loop being captured into a hipGraph stays on the capturing stream)
     if (!lengths && B >= 2 && B >= h->ar_dual_min && B <= h->ar_dual_max && !h->profiling && h->taps.empty() && cap == hipStreamCaptureStatusNone &&
-        ws0_bytes + plan_workspace(h, B1, Tn_max, nullptr).bytes <= workspace_bytes) {
-        if (!h->ar_side) {
-            HIP_TRY(hipStreamCreateWithFlags(&h->ar_side, hipStreamNonBlocking));
-            for (hipEvent_t& e : h->ar_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        const hipStream_t s1 = h->ar_side;
-        HIP_TRY(hipEventRecord(h->ar_ev[0], s0));  // fork: the side stream starts behind the caller's work so far
-        HIP_TRY(hipStreamWaitEvent(s1, h->ar_ev[0], 0));
-        // The halves' launches share the chip, so a launch's own exact makespan is the wrong yardstick for its tile shape (measured: with the
-        // simulated makespan the halves pick shapes that fill the chip alone and batch 32 / 44 lose 5 / 4 %; choosing by workgroup-time as the
-        // discriminators' engine does loses 20-30 %): they keep the closed-form estimate.  (Reset below on every path: nothing in between returns.)
-        h->shared_chip = true;
-        unsigned long long seen = h->sched_up_seq;
-        // a tile schedule first needed by one half is uploaded on that half's stream: the other stream must not use it before it has landed
-        auto publish = [&](hipStream_t from, hipStream_t to, hipEvent_t ev) -> int {
-            if (h->sched_up_seq != seen) {
-                HIP_TRY(hipEventRecord(ev, from));
-                HIP_TRY(hipStreamWaitEvent(to, ev, 0));
-                seen = h->sched_up_seq;
-            }
-            return HIFICAR_OK;
-        };
-        const float* const c1 = c + (size_t)B0 * h->cf * T_total;
-        // chunk f0 of utterance b reads spk_id[b] and ph[b, f0 + t]: the second half's rows start at B0
-        Cond cond0, cond1;
-        cond0.spk_id = spk_id;
-        cond1.spk_id = spk_id ? spk_id + B0 : nullptr;
-        cond0.ph_stride = cond1.ph_stride = T_total;
-        float* const out1 = out + (size_t)B0 * out_bstride;
-        char* const wsp1 = static_cast<char*>(workspace) + ws0_bytes;
-        for (int f0 = 0; f0 < T_total && rc == HIFICAR_OK; f0 += chunk_frames) {
-            const int Tn = std::min(chunk_frames, T_total - f0);
-            const int64_t pos = (int64_t)h->hop * f0;
-            const int64_t back = f0 == 0 ? 0 : pos - h->cfg.ar_input;
-            cond0.ph = ph ? ph + f0 : nullptr;
-            cond1.ph = ph ? ph + (size_t)B0 * T_total + f0 : nullptr;
-            rc = forward_impl(h, c + f0, (int64_t)h->cf * T_total, T_total, f0 == 0 ? nullptr : out + back, out_bstride, out + pos, out_bstride, B0, Tn,
-                              plan_workspace(h, B0, Tn, workspace), s0, nullptr, f0, nullptr, -1, cond0);
-            if (rc == HIFICAR_OK) rc = publish(s0, s1, h->ar_ev[0]);
-            if (rc == HIFICAR_OK)
-                rc = forward_impl(h, c1 + f0, (int64_t)h->cf * T_total, T_total, f0 == 0 ? nullptr : out1 + back, out_bstride, out1 + pos, out_bstride, B1, Tn,
-                                  plan_workspace(h, B1, Tn, wsp1), s1, nullptr, f0, nullptr, -1, cond1);
-            if (rc == HIFICAR_OK) rc = publish(s1, s0, h->ar_ev[1]);
-        }
-        h->shared_chip = false;
-        // join (also on an error return: the caller's stream must stay ordered behind what the side stream was given)
-        if (hipEventRecord(h->ar_ev[1], s1) != hipSuccess || hipStreamWaitEvent(s0, h->ar_ev[1], 0) != hipSuccess)
-            return rc != HIFICAR_OK ? rc : fail(HIFICAR_E_HIP, "hificar_ar_loop: joining the side stream failed");
-        return rc;
-    }
-    Cond cond;
-    cond.spk_id = spk_id;
-    cond.ph_stride = T_total;
+        ws0_bytes + plan_workspace(h, B / 2, Tn_max, nullptr).bytes <= workspace_bytes)
+        return ar_loop_two_streams(h, c, spk_id, ph, out, B, T_total, chunk_frames, workspace, ws0_bytes, s0);
     for (int f0 = 0; f0 < T_total; f0 += chunk_frames) {
-        const int Tn = std::min(chunk_frames, T_total - f0);
-        cond.ph = ph ? ph + f0 : nullptr;
         // With the host copy of the lengths the step only covers the utterances still running: the batch prefix up to the
         // last one longer than f0 (all of them when the batch is sorted longest first).
         int Bn = B;
@@ -2032,12 +2164,9 @@ extern "C" int hificar_ar_loop_cond(hificar_handle* h, const float* c, const int
                 if (lengths_host[b] > f0) Bn = b + 1;
             if (Bn == 0) break;
         }
-        const int64_t pos = (int64_t)h->hop * f0;
-        // prev = last ar_input samples already written for this utterance (zeros for the first chunk)
-        const float* prev = f0 == 0 ? nullptr : out + pos - h->cfg.ar_input;
-        rc = forward_impl(h, c + f0, (int64_t)h->cf * T_total, T_total, prev, out_bstride, out + pos, out_bstride, Bn, Tn,
-                          plan_workspace(h, Bn, Tn, workspace), static_cast<hipStream_t>(stream), lengths, f0, nullptr, -1, cond);
-        if (rc != HIFICAR_OK) return rc;
+        FwdCall k = ar_chunk_call(h, c, spk_id, ph, out, T_total, chunk_frames, f0, 0, Bn, workspace, s0);
+        k.seq_len = lengths;
+        if ((rc = forward_impl(h, k)) != HIFICAR_OK) return rc;
     }
     return HIFICAR_OK;
 }
@@ -2045,10 +2174,49 @@ extern "C" int hificar_ar_loop_cond(hificar_handle* h, const float* c, const int
 extern "C" int hificar_ar_loop_ragged(hificar_handle* h, const float* c, const int32_t* lengths, const int32_t* lengths_host,
                                       float* out, int B, int T_total, int chunk_frames, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-    if (h && !h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_loop on a model built with use_ar=false");
-    if (h && (h->cfg.use_spk_id || h->cfg.use_ph))  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
+    // (a model built with use_ar=false is refused by hificar_ar_loop_cond, as its first check)
+    if (h && h->cfg.use_ar && (h->cfg.use_spk_id || h->cfg.use_ph))  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
         return fail(HIFICAR_E_INVALID, "hificar_ar_loop: speaker / phoneme conditioned models are driven through hificar_forward_cond");
     return hificar_ar_loop_cond(h, c, nullptr, nullptr, lengths, lengths_host, out, B, T_total, chunk_frames, workspace, workspace_bytes, stream);
+}
+
+// The step table of the packed loop: steps[s] = {sequences, frames} of step s, whose row of `slots` lists the utterances it advances as
+// (utterance, first frame) and whose row of `valid` their valid frames.  Rows start on an even index in both arrays.
+struct PackedSteps {
+    struct Step {
+        int n, frames;
+    };
+    std::vector<Step> steps;
+    std::vector<int2> slots;
+    std::vector<int> valid;
+};
+static PackedSteps packed_step_table(const int32_t* lengths_host, int N, int T_max, int chunk_frames, int batch) {
+    PackedSteps t;
+    std::vector<int> run, f0((size_t)N, 0);
+    int next = 0;
+    for (;;) {
+        while ((int)run.size() < batch && next < N) {
+            if (lengths_host[next] > 0) run.push_back(next);
+            ++next;
+        }
+        if (run.empty()) break;
+        // every step is launched over a full chunk (shorter last chunks are masked per sequence and their empty tiles
+        // skipped): launch shapes then differ by the number of running utterances only, and their schedules stay cached
+        t.steps.push_back({(int)run.size(), std::min(chunk_frames, T_max)});
+        for (int u : run) {
+            t.slots.push_back(int2{u, f0[u]});
+            t.valid.push_back(std::min(chunk_frames, lengths_host[u] - f0[u]));
+        }
+        t.slots.resize((t.slots.size() + 1) & ~(size_t)1);  // rows start on an even index in both arrays (int2 rows 16-byte aligned)
+        t.valid.resize(t.slots.size());
+        std::vector<int> keep;
+        for (int u : run) {
+            f0[u] += chunk_frames;
+            if (f0[u] < lengths_host[u]) keep.push_back(u);
+        }
+        run.swap(keep);
+    }
+    return t;
 }
 
 // Packed (continuously batched) AR synthesis: N utterances, at most `batch` of them in flight; as soon as one finishes the
@@ -2057,59 +2225,21 @@ extern "C" int hificar_ar_loop_ragged(hificar_handle* h, const float* c, const i
 extern "C" int hificar_ar_loop_packed_cond(hificar_handle* h, const float* c, const int32_t* spk_id, const int32_t* ph,
                                            const int32_t* lengths_host, float* out, int N, int T_max, int chunk_frames, int batch,
                                            void* workspace, size_t workspace_bytes, void* stream_) {
-    if (h && !h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_loop on a model built with use_ar=false");
-    if (h && check_cond_args(h, "hificar_ar_loop_packed", spk_id, ph) != HIFICAR_OK) return HIFICAR_E_INVALID;
+    int rc;
+    if (h && (rc = check_ar_model(h, "hificar_ar_loop", "hificar_ar_loop_packed", spk_id, ph)) != HIFICAR_OK) return rc;
     if (chunk_frames < 1 || batch < 1 || N < 1 || T_max < 1)
         return fail(HIFICAR_E_INVALID, "hificar_ar_loop_packed: N=%d, T_max=%d, chunk_frames=%d, batch=%d must be positive", N, T_max,
                     chunk_frames, batch);
     batch = std::min(batch, N);
-    int rc = check_ready(h, batch, std::min(chunk_frames, T_max), workspace, workspace_bytes);
-    if (rc != HIFICAR_OK) return rc;
+    if ((rc = check_ready(h, batch, std::min(chunk_frames, T_max), workspace, workspace_bytes)) != HIFICAR_OK) return rc;
     if (!c || !out || !lengths_host) return fail(HIFICAR_E_INVALID, "hificar_ar_loop_packed: null argument");
-    if (h->cfg.ar_input > h->hop * chunk_frames && T_max > chunk_frames)
-        return fail(HIFICAR_E_INVALID, "ar_input (%d) > chunk audio length (%d): the reference loop (decode.py:79-81) is ill-formed there",
-                    h->cfg.ar_input, h->hop * chunk_frames);
-    for (int u = 0; u < N; ++u)
-        if (lengths_host[u] < 0 || lengths_host[u] > T_max)
-            return fail(HIFICAR_E_INVALID, "lengths[%d]=%d outside [0, %d]", u, lengths_host[u], T_max);
+    if ((rc = check_ar_chunk(h, chunk_frames, T_max > chunk_frames)) != HIFICAR_OK) return rc;
+    if ((rc = check_lengths(lengths_host, N, T_max)) != HIFICAR_OK) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
-    // step table: row s lists the utterances advanced by step s as (utterance, first frame) + their valid frames
-    struct Step {
-        int n, frames;
-    };
-    std::vector<Step> steps;
-    std::vector<int2> slots;
-    std::vector<int> valid;
-    {
-        std::vector<int> run, f0((size_t)N, 0);
-        int next = 0;
-        for (;;) {
-            while ((int)run.size() < batch && next < N) {
-                if (lengths_host[next] > 0) run.push_back(next);
-                ++next;
-            }
-            if (run.empty()) break;
-            // every step is launched over a full chunk (shorter last chunks are masked per sequence and their empty tiles
-            // skipped): launch shapes then differ by the number of running utterances only, and their schedules stay cached
-            Step st{(int)run.size(), std::min(chunk_frames, T_max)};
-            for (int u : run) {
-                slots.push_back(int2{u, f0[u]});
-                valid.push_back(std::min(chunk_frames, lengths_host[u] - f0[u]));
-            }
-            slots.resize((slots.size() + 1) & ~(size_t)1);  // rows start on an even index in both arrays (int2 rows 16-byte aligned)
-            valid.resize(slots.size());
-            steps.push_back(st);
-            std::vector<int> keep;
-            for (int u : run) {
-                f0[u] += chunk_frames;
-                if (f0[u] < lengths_host[u]) keep.push_back(u);
-            }
-            run.swap(keep);
-        }
-    }
-    if (steps.empty()) return HIFICAR_OK;
-    const size_t tab_bytes = slots.size() * (sizeof(int2) + sizeof(int));
+    const PackedSteps tab = packed_step_table(lengths_host, N, T_max, chunk_frames, batch);
+    if (tab.steps.empty()) return HIFICAR_OK;
+    const size_t n_slots = tab.slots.size(), tab_bytes = n_slots * (sizeof(int2) + sizeof(int));
     if (!h->tab_copied) HIP_TRY(hipEventCreateWithFlags(&h->tab_copied, hipEventDisableTiming));
     else HIP_TRY(hipEventSynchronize(h->tab_copied));  // the previous upload has left the staging copy (long ago, normally)
     if (tab_bytes > h->tab_bytes) {
@@ -2122,22 +2252,30 @@ extern "C" int hificar_ar_loop_packed_cond(hificar_handle* h, const float* c, co
         h->tab_bytes = tab_bytes * 2;
     }
     int2* d_slots = static_cast<int2*>(h->d_tab);
-    int* d_valid = reinterpret_cast<int*>(d_slots + slots.size());
-    memcpy(h->h_tab, slots.data(), slots.size() * sizeof(int2));
-    memcpy(static_cast<char*>(h->h_tab) + slots.size() * sizeof(int2), valid.data(), valid.size() * sizeof(int));
+    int* d_valid = reinterpret_cast<int*>(d_slots + n_slots);
+    memcpy(h->h_tab, tab.slots.data(), n_slots * sizeof(int2));
+    memcpy(static_cast<char*>(h->h_tab) + n_slots * sizeof(int2), tab.valid.data(), tab.valid.size() * sizeof(int));
     // one asynchronous upload, ordered on the stream behind any earlier call that still reads the table
     HIP_TRY(hipMemcpyAsync(h->d_tab, h->h_tab, tab_bytes, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(h->tab_copied, stream));
-    const int64_t out_bstride = (int64_t)h->hop * T_max;
+    FwdCall k;  // the features and the conditioning are indexed by utterance / (utterance, frame) through the slots
+    k.c = c;
+    k.c_bstride = (int64_t)h->cf * T_max;
+    k.c_cstride = T_max;
+    k.prev = k.out = out;
+    k.prev_bstride = k.out_bstride = (int64_t)h->hop * T_max;
+    k.spk_id = spk_id;
+    k.ph = ph;
+    k.ph_stride = T_max;
+    k.stream = stream;
     size_t row = 0;
-    Cond cond;  // indexed by utterance / (utterance, frame) through the slots, like the features
-    cond.spk_id = spk_id;
-    cond.ph = ph;
-    cond.ph_stride = T_max;
-    for (const Step& st : steps) {
-        rc = forward_impl(h, c, (int64_t)h->cf * T_max, T_max, out, out_bstride, out, out_bstride, st.n, st.frames,
-                          plan_workspace(h, st.n, st.frames, workspace), stream, d_valid + row, 0, d_slots + row, -1, cond);
-        if (rc != HIFICAR_OK) return rc;
+    for (const PackedSteps::Step& st : tab.steps) {
+        k.B = st.n;
+        k.T = st.frames;
+        k.seq_len = d_valid + row;
+        k.slots = d_slots + row;
+        k.ws = plan_workspace(h, st.n, st.frames, workspace);
+        if ((rc = forward_impl(h, k)) != HIFICAR_OK) return rc;
         row += ((size_t)st.n + 1) & ~(size_t)1;
     }
     return HIFICAR_OK;
@@ -2145,8 +2283,8 @@ extern "C" int hificar_ar_loop_packed_cond(hificar_handle* h, const float* c, co
 
 extern "C" int hificar_ar_loop_packed(hificar_handle* h, const float* c, const int32_t* lengths_host, float* out, int N, int T_max,
                                       int chunk_frames, int batch, void* workspace, size_t workspace_bytes, void* stream) {
-    if (h && !h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_loop on a model built with use_ar=false");
-    if (h && (h->cfg.use_spk_id || h->cfg.use_ph))  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
+    // (a model built with use_ar=false is refused by hificar_ar_loop_packed_cond, as its first check)
+    if (h && h->cfg.use_ar && (h->cfg.use_spk_id || h->cfg.use_ph))  // the reference's ar_loop calls model(c, ar=prev) only (decode.py:72)
         return fail(HIFICAR_E_INVALID, "hificar_ar_loop: speaker / phoneme conditioned models are driven through hificar_forward_cond");
     return hificar_ar_loop_packed_cond(h, c, nullptr, nullptr, lengths_host, out, N, T_max, chunk_frames, batch, workspace, workspace_bytes, stream);
 }
@@ -2167,16 +2305,14 @@ extern "C" int hificar_ar_step_cond(hificar_handle* h, const float* c, int64_t c
                                     int ctx_rows, float* out, void* workspace, size_t workspace_bytes, void* stream_) {
     // every argument is checked before the handle's state (finalize, workspace): nothing is enqueued for a bad table
     if (!h) return fail(HIFICAR_E_INVALID, "null handle");
-    if (!h->cfg.use_ar) return fail(HIFICAR_E_INVALID, "hificar_ar_step on a model built with use_ar=false");
-    if (check_cond_args(h, "hificar_ar_step", spk_rows, ph) != HIFICAR_OK) return HIFICAR_E_INVALID;
+    int rc;
+    if ((rc = check_ar_model(h, "hificar_ar_step", "hificar_ar_step", spk_rows, ph)) != HIFICAR_OK) return rc;
     if (ph && (ph_bstride < 1 || ph_bstride > INT32_MAX))
         return fail(HIFICAR_E_INVALID, "hificar_ar_step: phoneme ring row pitch %lld outside [1, 2^31)", (long long)ph_bstride);
     if (n < 1 || chunk_frames < 1 || ctx_rows < 1)
         return fail(HIFICAR_E_INVALID, "hificar_ar_step: n=%d, chunk_frames=%d, ctx_rows=%d must be positive", n, chunk_frames, ctx_rows);
     if (!c || !seqs_host || !ctx || !out) return fail(HIFICAR_E_INVALID, "hificar_ar_step: null argument");
-    if (h->cfg.ar_input > h->hop * chunk_frames)
-        return fail(HIFICAR_E_INVALID, "ar_input (%d) > chunk audio length (%d): the reference loop (decode.py:79-81) is ill-formed there",
-                    h->cfg.ar_input, h->hop * chunk_frames);
+    if ((rc = check_ar_chunk(h, chunk_frames, true)) != HIFICAR_OK) return rc;
     if (c_bstride < 0 || c_cstride < 1) return fail(HIFICAR_E_INVALID, "hificar_ar_step: strides %lld / %lld", (long long)c_bstride, (long long)c_cstride);
     if (n > ctx_rows) return fail(HIFICAR_E_INVALID, "hificar_ar_step: %d sequences for %d context rows", n, ctx_rows);
     std::vector<char> seen((size_t)ctx_rows, 0);
@@ -2196,8 +2332,7 @@ extern "C" int hificar_ar_step_cond(hificar_handle* h, const float* c, int64_t c
             return fail(HIFICAR_E_INVALID, "hificar_ar_step: sequence %d: frames [%d, %d) outside the phoneme ring's rows (%lld)", b, e[1],
                         e[1] + e[2], (long long)ph_bstride);
     }
-    int rc = check_ready(h, n, chunk_frames, workspace, workspace_bytes);
-    if (rc != HIFICAR_OK) return rc;
+    if ((rc = check_ready(h, n, chunk_frames, workspace, workspace_bytes)) != HIFICAR_OK) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     const size_t cap = ((size_t)ctx_rows + 1) & ~(size_t)1;  // entries: any valid table of this arena fits (n <= ctx_rows)
@@ -2230,18 +2365,28 @@ extern "C" int hificar_ar_step_cond(hificar_handle* h, const float* c, int64_t c
     // serves every step: a step's launches are done with it before the next step's front_kernel runs (one stream, enter_stream)
     int2* d_slots = reinterpret_cast<int2*>(h->step_d);
     int* d_valid = reinterpret_cast<int*>(d_slots + h->step_cap);
-    Cond cond;
-    cond.ctx = ctx;
-    cond.seqs = reinterpret_cast<const int4*>(h->step_hd) + (size_t)k * h->step_cap;
-    cond.seqs_slots = d_slots;
-    cond.seqs_valid = d_valid;
-    cond.spk_id = spk_rows;  // one speaker per session row: front_kernel indexes both by the table's row
-    cond.ph = ph;
-    cond.ph_stride = (int)ph_bstride;
+    FwdCall fc;
+    fc.c = c;
+    fc.c_bstride = c_bstride;
+    fc.c_cstride = c_cstride;
+    fc.out = out;
+    fc.out_bstride = (int64_t)h->hop * chunk_frames;
+    fc.B = n;
+    fc.T = chunk_frames;
     // a step of full chunks only (every step but a session's last) runs the launches unmasked, as an ar_synthesis step does: the masked
     // form's per-tile length loads cost ~1 us per launch, and for full chunks both forms compute the same values
-    rc = forward_impl(h, c, c_bstride, c_cstride, nullptr, 0, out, (int64_t)h->hop * chunk_frames, n, chunk_frames,
-                      plan_workspace(h, n, chunk_frames, workspace), stream, all_full ? nullptr : d_valid, 0, d_slots, -1, cond);
+    fc.seq_len = all_full ? nullptr : d_valid;
+    fc.slots = d_slots;
+    fc.ctx = ctx;
+    fc.seqs = reinterpret_cast<const int4*>(h->step_hd) + (size_t)k * h->step_cap;
+    fc.seqs_slots = d_slots;
+    fc.seqs_valid = d_valid;
+    fc.spk_id = spk_rows;  // one speaker per session row: front_kernel indexes both by the table's row
+    fc.ph = ph;
+    fc.ph_stride = (int)ph_bstride;
+    fc.ws = plan_workspace(h, n, chunk_frames, workspace);
+    fc.stream = stream;
+    rc = forward_impl(h, fc);
     // (also behind a failed step: what it did enqueue may read the slot)
     if (hipEventRecord(slot.done, stream) == hipSuccess) slot.used = true;
     else if (rc == HIFICAR_OK) rc = fail(HIFICAR_E_HIP, "hificar_ar_step: recording the step's event failed");

@@ -159,22 +159,16 @@ __global__ __launch_bounds__(256) static void rows_upsample2_kernel(const float*
     }
 }
 
-static int gblock_forward(hificar_handle* h, float* out, int64_t out_bstride, int B, int T, const Workspace& ws, hipStream_t stream,
-                          const int32_t* seq_len, const Ragged& rg, const int2* slots, const Tape* tp) {
+static int gblock_forward(hificar_handle* h, const FwdCall& k, const Ragged& rg) {
     const hificar_config& cfg = h->cfg;
+    const Workspace& ws = k.ws;
+    const Tape* const tp = k.tp;
+    const hipStream_t stream = k.stream;
+    const int B = k.B, T = k.T;
     int rc;
     const bool tapping = !h->taps.empty();
-    const size_t se = stage_elems(h, B, T);
     if (tapping) {
-        if (se > h->tap_scratch_elems) {
-            if (h->tap_scratch) HIP_TRY(hipFree(h->tap_scratch));
-            h->tap_scratch = nullptr;
-            h->tap_scratch_elems = 0;
-            void* p = nullptr;
-            HIP_TRY(hipMalloc(&p, se * sizeof(float)));
-            h->tap_scratch = static_cast<float*>(p);
-            h->tap_scratch_elems = se;
-        }
+        if ((rc = grow_tap_scratch(h, stage_elems(h, B, T))) != HIFICAR_OK) return rc;
         if (cfg.use_ar && (rc = emit_tap(h, "ar_feats", tp ? tp->xin : ws.xin, h->cin_pad, h->cf, cfg.ar_output, B, 1, 0, stream, T)) != HIFICAR_OK) return rc;
     }
     const int nb = (int)h->gb.size();
@@ -248,7 +242,7 @@ static int gblock_forward(hificar_handle* h, float* out, int64_t out_bstride, in
         }
     }
     const float* fin[3] = {last, nullptr, nullptr};
-    return launch_output_conv(h, fin, 1, round_up(h->c_last, 32), rows, B, T, out, out_bstride, seq_len, rg, slots, stream);
+    return launch_output_conv(h, k, rg, fin, 1, round_up(h->c_last, 32), rows);
 }
 
 // ------------------------------------------------------------------------------------------------

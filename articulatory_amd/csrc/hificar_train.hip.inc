@@ -919,15 +919,11 @@ extern "C" int hificar_forward_train_cond(hificar_handle* h, const float* c, con
         return fail(HIFICAR_E_WORKSPACE, "tape too small or not 256-byte aligned: need %zu bytes", plan_tape(h, B, T, nullptr).bytes);
     if ((rc = enter_stream(h, static_cast<hipStream_t>(stream))) != HIFICAR_OK) return rc;
     const Tape tp = plan_tape(h, B, T, tape);
-    const Workspace ws = plan_workspace(h, B, T, workspace);
-    Cond cond;
-    cond.spk_id = spk_id;
-    cond.ph = ph;
-    cond.ph_stride = T;
-    cond.ph_out = ph_out;
-    cond.ph_out_T = T;
-    return forward_impl(h, c, (int64_t)h->cf * T, T, h->cfg.use_ar ? ar : nullptr, h->cfg.ar_input, out, (int64_t)h->hop * T, B, T, ws,
-                        static_cast<hipStream_t>(stream), nullptr, 0, nullptr, T, cond, &tp);
+    FwdCall k = whole_call(h, c, ar, spk_id, ph, out, ph_out, B, T, static_cast<hipStream_t>(stream));
+    k.T = T;
+    k.tp = &tp;
+    k.ws = plan_workspace(h, B, T, workspace);
+    return forward_impl(h, k);
 }
 
 extern "C" int hificar_forward_train(hificar_handle* h, const float* c, const float* ar, float* out, int B, int T, void* workspace,
@@ -1193,11 +1189,7 @@ static int bwd_output_conv(hificar_handle* h, TrainState* ts, const Tape& tp, co
     auto G = [&](const std::string& name) { return grads + ts->raw.offset(name); };
         OutBwdParams op;
         memset(&op, 0, sizeof(op));
-        op.x0 = tp.fin[0];
-        op.x1 = nin > 1 ? tp.fin[1] : nullptr;
-        op.x2 = nin > 2 ? tp.fin[2] : nullptr;
-        op.x3 = nin > 3 ? tp.fin[3] : nullptr;
-        op.nin = nin;
+        fill_inputs(op, tp.fin, nin);
         op.w = h->d_out_w;
         op.dout = dout;
         op.out = out;
@@ -1359,22 +1351,10 @@ extern "C" int hificar_backward_cond(hificar_handle* h, const float* dout, const
     auto G = [&](const std::string& name) { return grads + ts->raw.offset(name); };
     Ragged rg;  // dense
     rg.frames = T;
-    int order[kMaxBlk];
-    for (int j = 0; j < kMaxBlk; ++j) order[j] = j;
-    std::sort(order, order + nbk, [&](int a, int b) { return cfg.resblock_kernel_sizes[a] > cfg.resblock_kernel_sizes[b]; });
-    int max_d = 0;
-    for (int j = 0; j < nbk; ++j) max_d = std::max(max_d, cfg.n_dilations[j]);
+    const BlockOrder bo = block_order(cfg);
     const bool add_convs = cfg.use_additional_convs != 0;
 
     int rows = T * h->hop;
-    // a launch carries up to three branches: a fourth residual block rides in a second launch
-    auto conv_n = [&](const ConvLayer* const* lay, int n, const ConvIO* io) -> int {
-        for (int q0 = 0; q0 < n; q0 += 3) {
-            const int r = launch_conv(h, lay + q0, std::min(3, n - q0), B, rows, io + q0, slope, rg, stream);
-            if (r != HIFICAR_OK) return r;
-        }
-        return HIFICAR_OK;
-    };
     if ((rc = bwd_output_conv(h, ts, tp, bw, dout, out, B, T, rows, nbk, grads, stream)) != HIFICAR_OK) return rc;
     // ---- phoneme-loss head (hifigan.py:232-237): its gradient joins the output conv's on the last stage's ResBlock outputs ----
     if (cfg.use_ph_loss) {
@@ -1382,11 +1362,7 @@ extern "C" int hificar_backward_cond(hificar_handle* h, const float* dout, const
         if (dph_out) {
             PhHeadBwdParams pq;
             memset(&pq, 0, sizeof(pq));
-            pq.x0 = tp.fin[0];
-            pq.x1 = nbk > 1 ? tp.fin[1] : nullptr;
-            pq.x2 = nbk > 2 ? tp.fin[2] : nullptr;
-            pq.x3 = nbk > 3 ? tp.fin[3] : nullptr;
-            pq.nin = nbk;
+            fill_inputs(pq, tp.fin, nbk);
             pq.w = h->d_phfc_w;
             pq.dph_out = dph_out;
             pq.dwin = bw.dwin;
@@ -1428,19 +1404,16 @@ extern "C" int hificar_backward_cond(hificar_handle* h, const float* dout, const
     for (int i = cfg.n_stages - 1; i >= 0; --i) {
         const int Cp = stage_pad(cfg, i + 1);
         const float* dsrc[kMaxBlk] = {bw.dm[dmi], bw.dm[dmi], bw.dm[dmi], bw.dm[dmi]};
-        for (int d = max_d - 1; d >= 0; --d) {
+        for (int d = bo.max_d - 1; d >= 0; --d) {
             const ConvLayer* f1[kMaxBlk];
             const ConvLayer* f2[kMaxBlk];
             const ConvLayer* d1[kMaxBlk];
             const ConvLayer* d2[kMaxBlk];
             ConvIO io2[kMaxBlk], io1[kMaxBlk];
-            int jn[kMaxBlk];
             float* dst1[kMaxBlk];
-            int n = 0;
-            for (int oj = 0; oj < nbk; ++oj) {
-                const int j = order[oj];
-                if (d >= cfg.n_dilations[j]) continue;
-                const int ci = conv_index(h, i, j, d);
+            const Branches br = gather_branches(h, bo, i, d);
+            for (int n = 0; n < br.n; ++n) {
+                const int j = br.j[n], ci = br.ci[n];
                 f1[n] = &h->convs1[ci];
                 d1[n] = &ts->dg_c1[ci];
                 const float* a1 = reinterpret_cast<const float*>(d == 0 ? tp.u_s[i] : tp.x_s[i][j][d - 1]);
@@ -1458,15 +1431,13 @@ extern "C" int hificar_backward_cond(hificar_handle* h, const float* dout, const
                     dst1[n] = dsrc[j] == bw.dx[j] ? bw.g1[j] : bw.dx[j];
                     io1[n] = {reinterpret_cast<const char*>(dsrc[j]), dsrc[j], dst1[n], nullptr, a1, slope};
                 }
-                jn[n] = j;
-                ++n;
             }
-            if (n == 0) continue;
-            if (add_convs && (rc = conv_n(d2, n, io2)) != HIFICAR_OK) return rc;
-            for (int q = 0; q < n; ++q) {
+            if (br.n == 0) continue;
+            if (add_convs && (rc = launch_n(h, d2, nullptr, br.n, B, rows, io2, nullptr, slope, rg, stream)) != HIFICAR_OK) return rc;
+            for (int q = 0; q < br.n; ++q) {
                 // weight / bias gradients of the slot's two convs in one launch: conv2 from (its input a2, the gradient of its output =
                 // the running skip gradient), conv1 from (its input a1, g1)
-                const int j = jn[q];
+                const int j = br.j[q];
                 const float* a1 = reinterpret_cast<const float*>(d == 0 ? tp.u_s[i] : tp.x_s[i][j][d - 1]);
                 if (!add_convs) {  // one conv per layer: its weight gradient from (a1, the running gradient)
                     const WgradJob one[1] = {{f1[q], dsrc[j], Cp, a1, Cp, G(f1[q]->name + ".weight"), f1[q]->has_bias ? G(f1[q]->name + ".bias") : nullptr}};
@@ -1479,8 +1450,8 @@ extern "C" int hificar_backward_cond(hificar_handle* h, const float* dout, const
                     {f1[q], bw.g1[j], Cp, a1, Cp, G(f1[q]->name + ".weight"), f1[q]->has_bias ? G(f1[q]->name + ".bias") : nullptr}};
                 if ((rc = launch_wgrad_n(h, pairj, 2, B, rows, bw, stream)) != HIFICAR_OK) return rc;
             }
-            if ((rc = conv_n(d1, n, io1)) != HIFICAR_OK) return rc;
-            for (int q = 0; q < n; ++q) dsrc[jn[q]] = dst1[q];
+            if ((rc = launch_n(h, d1, nullptr, br.n, B, rows, io1, nullptr, slope, rg, stream)) != HIFICAR_OK) return rc;
+            for (int q = 0; q < br.n; ++q) dsrc[br.j[q]] = dst1[q];
         }
         // every ResBlock gradient of stage i (and, for the last stage, the output conv's and the phoneme head's) is enqueued: bucket done
         if (ts->raw.bucket_fn) {
