@@ -110,6 +110,14 @@ SYMBOLS = (
     "hificar_bigru_forward_train",
     "hificar_bigru_forward_train_ragged",
     "hificar_bigru_backward",
+    "hificar_xfmr_create",
+    "hificar_xfmr_set_weight",
+    "hificar_xfmr_finalize",
+    "hificar_xfmr_workspace_bytes",
+    "hificar_xfmr_forward",
+    "hificar_xfmr_debug_tap",
+    "hificar_xfmr_engine",
+    "hificar_xfmr_destroy",
     "hificar_destroy",
     "hificar_last_error",
     "hificar_version",
@@ -183,6 +191,18 @@ class HificarBigruConfig(ctypes.Structure):
         ("hidden_size", ctypes.c_int32),
         ("out_channels", ctypes.c_int32),
         ("use_tanh", ctypes.c_int32),
+    ]
+
+
+class HificarXfmrConfig(ctypes.Structure):
+    """hificar_xfmr_config (include/hificar.h): the keyword arguments of the reference's Transformer.__init__ (transformer.py:22-24) that
+    shape eval-mode inference."""
+
+    _fields_ = [
+        ("in_channels", ctypes.c_int32),
+        ("out_channels", ctypes.c_int32),
+        ("elayers", ctypes.c_int32),
+        ("hidden_dim", ctypes.c_int32),
     ]
 
 
@@ -470,6 +490,22 @@ def load_library():
     lib.hificar_bigru_forward_train_ragged.restype = ci
     lib.hificar_bigru_backward.argtypes = [vp, vp, ci, ci, vp, cs, vp, vp, vp, cs, vp]
     lib.hificar_bigru_backward.restype = ci
+    lib.hificar_xfmr_create.argtypes = [ctypes.POINTER(HificarXfmrConfig), ctypes.POINTER(vp)]
+    lib.hificar_xfmr_create.restype = ci
+    lib.hificar_xfmr_set_weight.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(c64), ci]
+    lib.hificar_xfmr_set_weight.restype = ci
+    lib.hificar_xfmr_finalize.argtypes = [vp]
+    lib.hificar_xfmr_finalize.restype = ci
+    lib.hificar_xfmr_workspace_bytes.argtypes = [vp, ci, ci]
+    lib.hificar_xfmr_workspace_bytes.restype = cs
+    lib.hificar_xfmr_forward.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]
+    lib.hificar_xfmr_forward.restype = ci
+    lib.hificar_xfmr_debug_tap.argtypes = [vp, ctypes.c_char_p, vp, cs]
+    lib.hificar_xfmr_debug_tap.restype = ci
+    lib.hificar_xfmr_engine.argtypes = [vp]
+    lib.hificar_xfmr_engine.restype = vp
+    lib.hificar_xfmr_destroy.argtypes = [vp]
+    lib.hificar_xfmr_destroy.restype = None
     lib.hificar_destroy.argtypes = [vp]
     lib.hificar_destroy.restype = None
     lib.hificar_last_error.argtypes = []
@@ -609,4 +645,38 @@ def make_bigru_config(params: dict) -> HificarBigruConfig:
     cfg.hidden_size = params["hidden_size"]
     cfg.out_channels = params["out_channels"]
     cfg.use_tanh = int(params["use_tanh"])
+    return cfg
+
+
+# what hificar_xfmr_create accepts (csrc/hificar_xfmr.hip.inc; HIFICAR_XFMR_MAX_* of include/hificar.h); Transformer.__init__ checks the same
+# numbers so that an unsupported configuration fails at construction, before any device work
+XFMR_MAX_IN = 4096
+XFMR_MAX_OUT = 1024      # w_out's rows share the feed-forward buffer
+XFMR_MAX_HIDDEN = 1024   # head size hidden_dim / 8 up to 128: the attention kernel's instantiations
+XFMR_MAX_LAYERS = 24
+XFMR_HEADS = 8           # nhead, dim_feedforward, relative_positional_distance: the reference constructor's constants (transformer.py:43)
+XFMR_FF = 3072
+XFMR_REL = 100
+
+
+def check_xfmr_params(params: dict):
+    """ValueError for a Transformer configuration libhificar's engine rejects."""
+    f = params["hidden_dim"]
+    if not 1 <= params["in_channels"] <= XFMR_MAX_IN:
+        raise ValueError(f"in_channels={params['in_channels']} out of range (1 .. {XFMR_MAX_IN})")
+    if not 1 <= params["out_channels"] <= XFMR_MAX_OUT:
+        raise ValueError(f"out_channels={params['out_channels']} out of range (1 .. {XFMR_MAX_OUT})")
+    if not 1 <= params["elayers"] <= XFMR_MAX_LAYERS:
+        raise ValueError(f"elayers={params['elayers']} out of range (1 .. {XFMR_MAX_LAYERS})")
+    if f < 128 or f > XFMR_MAX_HIDDEN or f % 128:
+        raise ValueError(f"hidden_dim={f} unsupported (multiples of 128 up to {XFMR_MAX_HIDDEN}: the attention kernel is built for head sizes 16 .. 128)")
+
+
+def make_xfmr_config(params: dict) -> HificarXfmrConfig:
+    """Transformer keyword arguments (reference names) -> hificar_xfmr_config."""
+    cfg = HificarXfmrConfig()
+    cfg.in_channels = params["in_channels"]
+    cfg.out_channels = params["out_channels"]
+    cfg.elayers = params["elayers"]
+    cfg.hidden_dim = params["hidden_dim"]
     return cfg

@@ -8,6 +8,7 @@
 #include "hificar_disc_kernels.hip.h"
 #include "hificar_bigru_kernels.hip.h"
 #include "hificar_bigru_train_kernels.hip.h"
+#include "hificar_xfmr_kernels.hip.h"
 
 #include "../../include/hificar.h"
 
@@ -245,6 +246,7 @@ struct hificar_handle : hificar_engine {
 // The generators add HIFICAR_AR_DUAL_MIN / _MAX: the batch sizes hificar_ar_loop runs as two halves on two streams (default 17..62; MAX=0: never).
 // hificar_disc.hip.inc adds HIFICAR_DISC_STREAMS=0 (sub-discriminators on the caller's stream: per-launch counters) and HIFICAR_COL2IM_VEC4=0.
 // hificar_bigru.hip.inc adds HIFICAR_BIGRU_NS=1|2 (sequences per workgroup of the recurrent kernel, A/B runs) and always runs with KSPLIT off.
+// hificar_xfmr.hip.inc (the Transformer) adds none and always runs with KSPLIT off and without the pair kernels.
 static FILE* g_launch_log = nullptr;
 static void read_env_switches(hificar_engine* h) {
     if (const char* e = getenv("HIFICAR_PROFILE_DETAIL")) h->profile_detail = atoi(e) != 0;
@@ -2464,3 +2466,4 @@ extern "C" int hificar_pcm16(const float* x, int16_t* y, size_t n, void* stream)
 #include "hificar_mel.hip.inc"
 #include "hificar_bigru.hip.inc"
 #include "hificar_bigru_train.hip.inc"
+#include "hificar_xfmr.hip.inc"

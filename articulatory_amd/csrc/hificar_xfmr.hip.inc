@@ -1,0 +1,435 @@
+// The Transformer feature model (articulatory/models/transformer.py:21-105): features (B, in_channels, T) -> features (B, out_channels, T), eval mode.
+//   rows        (B, C, T) -> channels-last rows, and back at the end                       xfmr_rows_kernel / xfmr_out_kernel
+//   conv_blocks three ResBlocks (pytorch_layers.py:94-125), the eval-mode BatchNorm1ds folded into their convs: conv1 writes its ReLU'd copy,
+//               conv2 takes the block input (block 0: the folded 1 x 1 residual_path) as its fp32 residual and writes the ReLU'd sum      conv engine
+//   w_raw_in    Linear(F, F)                                                                conv engine, one-tap launch
+//   per layer   q, k, v as ONE GEMM (N = 3 F, no bias)                                      conv engine
+//               banded relative-position attention -> rows [head][d]                        xfmr_attn_kernel
+//               w_o (no bias) + the layer input as residual, LayerNorm                      conv engine, xfmr_ln_kernel
+//               linear1 (ReLU'd copy), linear2 + residual, LayerNorm                        conv engine, xfmr_ln_kernel
+//   w_out       Linear(F, out)                                                              conv engine
+// Every launch is per sequence (nseq = B, rows = T) under the ragged context: rows at or past a sequence's length read as zero padding and
+// are never written, so the k = 3 convs see each utterance's own end.  Exact fp32, split-K off: one accumulation order whatever the batch.
+// Workspace: the input rows, three row buffers [B T][F] that rotate, and one wide buffer [B T][3072] (q | k | v, then the feed-forward's
+// hidden rows, then w_out's rows).
+
+struct XfmrEncLayer {
+    ConvLayer qkv, wo, l1, l2;
+    float* d_emb = nullptr;                 // [8][199][d]
+    float* d_ln[4] = {nullptr, nullptr, nullptr, nullptr};  // norm1.weight, norm1.bias, norm2.weight, norm2.bias
+};
+
+struct hificar_xfmr {
+    hificar_xfmr_config cfg;
+    hificar_engine eng;
+    std::map<std::string, std::vector<int64_t>> expected;
+    std::map<std::string, HostTensor> tensors;
+    ConvLayer c1[3], c2[3], rp, w_in, w_out;
+    std::vector<XfmrEncLayer> enc;  // sized once, in hificar_xfmr_create (launch plans are keyed by the layers' addresses)
+    int cin_pad = 0;
+    bool finalized = false;
+    struct Tap {
+        float* dst;
+        size_t cap;
+    };
+    std::map<std::string, Tap> taps;
+};
+
+static bool xfmr_head_dim_built(int d) { return d >= 16 && d <= 128 && d % 16 == 0; }
+
+static int xfmr_plan(ConvLayer& L, const std::string& name, int cin, int cin_pad, int cout, int K) {
+    L.name = name;
+    L.cin = cin;
+    L.cin_pad = cin_pad;
+    L.cout = cout;
+    L.K = K;
+    L.padding = K / 2;
+    return plan_layer(L);
+}
+
+extern "C" int hificar_xfmr_create(const hificar_xfmr_config* cfg, hificar_xfmr** out) {
+    if (!cfg || !out) return fail(HIFICAR_E_INVALID, "hificar_xfmr_create: null argument");
+    const hificar_xfmr_config& c = *cfg;
+    if (c.in_channels < 1 || c.in_channels > HIFICAR_XFMR_MAX_IN)
+        return fail(HIFICAR_E_INVALID, "Transformer: in_channels=%d out of range (1 .. %d)", c.in_channels, HIFICAR_XFMR_MAX_IN);
+    if (c.out_channels < 1 || c.out_channels > HIFICAR_XFMR_MAX_OUT)
+        return fail(HIFICAR_E_INVALID, "Transformer: out_channels=%d out of range (1 .. %d)", c.out_channels, HIFICAR_XFMR_MAX_OUT);
+    if (c.elayers < 1 || c.elayers > HIFICAR_XFMR_MAX_LAYERS)
+        return fail(HIFICAR_E_INVALID, "Transformer: elayers=%d out of range (1 .. %d)", c.elayers, HIFICAR_XFMR_MAX_LAYERS);
+    if (c.hidden_dim < 128 || c.hidden_dim > HIFICAR_XFMR_MAX_HIDDEN || c.hidden_dim % 128 != 0 || !xfmr_head_dim_built(c.hidden_dim / kXfmrHeads))
+        return fail(HIFICAR_E_INVALID, "Transformer: hidden_dim=%d unsupported (multiples of 128 up to %d: the attention kernel is built for head sizes 16 .. 128)",
+                    c.hidden_dim, HIFICAR_XFMR_MAX_HIDDEN);
+    static_assert(HIFICAR_XFMR_MAX_OUT <= kXfmrFF, "w_out's rows share the feed-forward buffer");
+    hificar_xfmr* g = new hificar_xfmr();
+    g->cfg = c;
+    const int64_t F = c.hidden_dim, C = c.in_channels, O = c.out_channels, d = F / kXfmrHeads;
+    g->cin_pad = round_up(c.in_channels, 32);
+    for (int i = 0; i < 3; ++i) {
+        const std::string b = "conv_blocks." + std::to_string(i) + ".";
+        g->expected[b + "conv1.weight"] = {F, i == 0 ? C : F, 3};
+        g->expected[b + "conv2.weight"] = {F, F, 3};
+        for (const char* m : {"conv1", "conv2", "bn1", "bn2"}) g->expected[b + m + ".bias"] = {F};
+        for (const char* m : {"bn1", "bn2"})
+            for (const char* t : {".weight", ".running_mean", ".running_var"}) g->expected[b + m + t] = {F};
+        if (i == 0 && C != F) {  // (pytorch_layers.py:108-112: the 1 x 1 path exists when the block changes the width)
+            g->expected[b + "residual_path.weight"] = {F, C, 1};
+            g->expected[b + "residual_path.bias"] = {F};
+            for (const char* t : {".weight", ".bias", ".running_mean", ".running_var"}) g->expected[b + "res_norm" + t] = {F};
+        }
+    }
+    g->expected["w_raw_in.weight"] = {F, F};
+    g->expected["w_raw_in.bias"] = {F};
+    for (int l = 0; l < c.elayers; ++l) {
+        const std::string b = "transformer.layers." + std::to_string(l) + ".";
+        for (const char* w : {"w_q", "w_k", "w_v"}) g->expected[b + "self_attn." + w] = {kXfmrHeads, F, d};
+        g->expected[b + "self_attn.w_o"] = {kXfmrHeads, d, F};
+        g->expected[b + "self_attn.relative_positional.embeddings"] = {kXfmrHeads, kXfmrTab, d, 1};
+        g->expected[b + "linear1.weight"] = {kXfmrFF, F};
+        g->expected[b + "linear1.bias"] = {kXfmrFF};
+        g->expected[b + "linear2.weight"] = {F, kXfmrFF};
+        g->expected[b + "linear2.bias"] = {F};
+        for (const char* n : {"norm1", "norm2"})
+            for (const char* t : {".weight", ".bias"}) g->expected[b + n + t] = {F};
+    }
+    g->expected["w_out.weight"] = {O, F};
+    g->expected["w_out.bias"] = {O};
+    g->enc.resize((size_t)c.elayers);
+    const int Fi = c.hidden_dim;
+    int rc = HIFICAR_OK;
+    for (int i = 0; i < 3 && rc == HIFICAR_OK; ++i) {
+        const std::string b = "conv_blocks." + std::to_string(i);
+        rc = xfmr_plan(g->c1[i], b + ".conv1#bn1", i == 0 ? c.in_channels : Fi, i == 0 ? g->cin_pad : Fi, Fi, 3);
+        if (rc == HIFICAR_OK) rc = xfmr_plan(g->c2[i], b + ".conv2#bn2", Fi, Fi, Fi, 3);
+    }
+    if (rc == HIFICAR_OK && c.in_channels != Fi) rc = xfmr_plan(g->rp, "conv_blocks.0.residual_path#res_norm", c.in_channels, g->cin_pad, Fi, 1);
+    if (rc == HIFICAR_OK) rc = xfmr_plan(g->w_in, "w_raw_in", Fi, Fi, Fi, 1);
+    for (int l = 0; l < c.elayers && rc == HIFICAR_OK; ++l) {
+        const std::string b = "transformer.layers." + std::to_string(l);
+        XfmrEncLayer& E = g->enc[(size_t)l];
+        rc = xfmr_plan(E.qkv, b + ".self_attn#qkv", Fi, Fi, 3 * Fi, 1);
+        if (rc == HIFICAR_OK) rc = xfmr_plan(E.wo, b + ".self_attn.w_o", Fi, Fi, Fi, 1);
+        if (rc == HIFICAR_OK) rc = xfmr_plan(E.l1, b + ".linear1", Fi, Fi, kXfmrFF, 1);
+        if (rc == HIFICAR_OK) rc = xfmr_plan(E.l2, b + ".linear2", kXfmrFF, kXfmrFF, Fi, 1);
+    }
+    if (rc == HIFICAR_OK) rc = xfmr_plan(g->w_out, "w_out", Fi, Fi, c.out_channels, 1);
+    if (rc != HIFICAR_OK) {
+        delete g;
+        return rc;
+    }
+    *out = g;
+    return HIFICAR_OK;
+}
+
+extern "C" void hificar_xfmr_destroy(hificar_xfmr* g) {
+    if (!g) return;
+    engine_close(&g->eng);
+    delete g;
+}
+
+extern "C" hificar_engine* hificar_xfmr_engine(hificar_xfmr* g) { return g ? &g->eng : nullptr; }
+
+extern "C" int hificar_xfmr_set_weight(hificar_xfmr* g, const char* name, const float* data, const int64_t* shape, int ndim) {
+    if (!g || !name || !data || !shape) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_weight: null argument");
+    if (g->finalized) return fail(HIFICAR_E_STATE, "hificar_xfmr_set_weight(%s) after hificar_xfmr_finalize", name);
+    auto it = g->expected.find(name);
+    if (it == g->expected.end()) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", name);
+    std::vector<int64_t> s(shape, shape + ndim);
+    if (s != it->second) {
+        std::string want, got;
+        for (auto v : it->second) want += std::to_string(v) + ",";
+        for (auto v : s) got += std::to_string(v) + ",";
+        return fail(HIFICAR_E_INVALID, "size mismatch for %s: expected (%s) got (%s)", name, want.c_str(), got.c_str());
+    }
+    size_t n = 1;
+    for (auto v : s) n *= (size_t)v;
+    HostTensor t;
+    t.shape = s;
+    t.data.assign(data, data + n);
+    g->tensors[name] = std::move(t);
+    return HIFICAR_OK;
+}
+
+// bias and exact-fp32 weight fragments of one layer (the bf16x3 fragments pack_conv would add are never used here)
+static int xfmr_pack(hificar_engine* h, ConvLayer& L, const HostTensor& W, const std::vector<float>* bias) {
+    std::vector<float> b((size_t)L.cout_total, 0.f);
+    if (bias) std::copy(bias->begin(), bias->begin() + L.cout, b.begin());
+    const int rc = upload(h, b, &L.d_bias);
+    if (rc != HIFICAR_OK) return rc;
+    return pack_w32(h, L, W, L.chunk16, &L.d_w32);
+}
+
+// Conv1d followed by an eval-mode BatchNorm1d as one conv: y = (W x + b - mean) * gamma / sqrt(var + 1e-5) + beta, folded in double
+static int xfmr_pack_folded(hificar_xfmr* g, ConvLayer& L, const std::string& conv, const std::string& bn) {
+    const HostTensor& W = g->tensors.at(conv + ".weight");
+    const std::vector<float>&b = g->tensors.at(conv + ".bias").data, &gm = g->tensors.at(bn + ".weight").data, &bt = g->tensors.at(bn + ".bias").data,
+                     &mu = g->tensors.at(bn + ".running_mean").data, &var = g->tensors.at(bn + ".running_var").data;
+    HostTensor Wf;
+    Wf.shape = W.shape;
+    Wf.data.resize(W.data.size());
+    std::vector<float> bf((size_t)L.cout);
+    const size_t per = (size_t)L.cin * L.K;
+    for (int o = 0; o < L.cout; ++o) {
+        const double s = (double)gm[o] / std::sqrt((double)var[o] + 1e-5);
+        for (size_t k = 0; k < per; ++k) Wf.data[o * per + k] = (float)((double)W.data[o * per + k] * s);
+        bf[o] = (float)(((double)b[o] - (double)mu[o]) * s + (double)bt[o]);
+    }
+    return xfmr_pack(&g->eng, L, Wf, &bf);
+}
+
+template <int D>
+static hipError_t xfmr_attn_attr() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_attn_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XfmrAttnLds<D>::bytes);
+}
+
+template <int D>
+static hipError_t xfmr_attn_launch_one(const XfmrAttnParams& p, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((xfmr_attn_kernel<D>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
+    return hipGetLastError();
+}
+
+static hipError_t xfmr_attn_launch(int d, const XfmrAttnParams& p, dim3 grid, hipStream_t stream) {
+    switch (d) {
+        case 16: return xfmr_attn_launch_one<16>(p, grid, stream);
+        case 32: return xfmr_attn_launch_one<32>(p, grid, stream);
+        case 48: return xfmr_attn_launch_one<48>(p, grid, stream);
+        case 64: return xfmr_attn_launch_one<64>(p, grid, stream);
+        case 80: return xfmr_attn_launch_one<80>(p, grid, stream);
+        case 96: return xfmr_attn_launch_one<96>(p, grid, stream);
+        case 112: return xfmr_attn_launch_one<112>(p, grid, stream);
+        case 128: return xfmr_attn_launch_one<128>(p, grid, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
+    if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_finalize: null handle");
+    if (g->finalized) return HIFICAR_OK;
+    for (auto& kv : g->expected)
+        if (!g->tensors.count(kv.first)) return fail(HIFICAR_E_STATE, "Missing key(s) in state_dict: \"%s\"", kv.first.c_str());
+    hificar_engine* h = &g->eng;
+    const int F = g->cfg.hidden_dim, d = F / kXfmrHeads;
+    int rc;
+    for (int i = 0; i < 3; ++i) {
+        const std::string b = "conv_blocks." + std::to_string(i) + ".";
+        if ((rc = xfmr_pack_folded(g, g->c1[i], b + "conv1", b + "bn1")) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_folded(g, g->c2[i], b + "conv2", b + "bn2")) != HIFICAR_OK) return rc;
+    }
+    if (g->rp.cout && (rc = xfmr_pack_folded(g, g->rp, "conv_blocks.0.residual_path", "conv_blocks.0.res_norm")) != HIFICAR_OK) return rc;
+    auto linear = [&](ConvLayer& L, const std::string& name) {
+        HostTensor W = g->tensors.at(name + ".weight");
+        W.shape.push_back(1);
+        return xfmr_pack(h, L, W, &g->tensors.at(name + ".bias").data);
+    };
+    if ((rc = linear(g->w_in, "w_raw_in")) != HIFICAR_OK) return rc;
+    if ((rc = linear(g->w_out, "w_out")) != HIFICAR_OK) return rc;
+    for (int l = 0; l < g->cfg.elayers; ++l) {
+        const std::string b = "transformer.layers." + std::to_string(l) + ".";
+        XfmrEncLayer& E = g->enc[(size_t)l];
+        {   // q = einsum('tbf,hfa->bhta', x, w_q) (pytorch_layers.py:213-215): row (s 8 + h) d + a of the GEMM's weight is w_s[h, :, a]
+            HostTensor W;
+            W.shape = {3 * F, F, 1};
+            W.data.resize((size_t)3 * F * F);
+            int s = 0;
+            for (const char* w : {"w_q", "w_k", "w_v"}) {
+                const std::vector<float>& src = g->tensors.at(b + "self_attn." + w).data;
+                for (int hh = 0; hh < kXfmrHeads; ++hh)
+                    for (int f = 0; f < F; ++f)
+                        for (int a = 0; a < d; ++a) W.data[((size_t)(s * kXfmrHeads + hh) * d + a) * F + f] = src[((size_t)hh * F + f) * d + a];
+                ++s;
+            }
+            if ((rc = xfmr_pack(h, E.qkv, W, nullptr)) != HIFICAR_OK) return rc;
+        }
+        {   // out = einsum('bhta,haf->tbf', o, w_o) (:228): row f of the GEMM's weight is w_o[:, :, f] over (h, a)
+            const std::vector<float>& src = g->tensors.at(b + "self_attn.w_o").data;
+            HostTensor W;
+            W.shape = {F, F, 1};
+            W.data.resize((size_t)F * F);
+            for (int k = 0; k < F; ++k)
+                for (int f = 0; f < F; ++f) W.data[(size_t)f * F + k] = src[(size_t)k * F + f];
+            if ((rc = xfmr_pack(h, E.wo, W, nullptr)) != HIFICAR_OK) return rc;
+        }
+        if ((rc = linear(E.l1, b + "linear1")) != HIFICAR_OK) return rc;
+        if ((rc = linear(E.l2, b + "linear2")) != HIFICAR_OK) return rc;
+        if ((rc = upload(h, g->tensors.at(b + "self_attn.relative_positional.embeddings").data, &E.d_emb)) != HIFICAR_OK) return rc;
+        int i = 0;
+        for (const char* n : {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"})
+            if ((rc = upload(h, g->tensors.at(b + n).data, &E.d_ln[i++])) != HIFICAR_OK) return rc;
+    }
+    HIP_TRY(xfmr_attn_attr<16>());
+    HIP_TRY(xfmr_attn_attr<32>());
+    HIP_TRY(xfmr_attn_attr<48>());
+    HIP_TRY(xfmr_attn_attr<64>());
+    HIP_TRY(xfmr_attn_attr<80>());
+    HIP_TRY(xfmr_attn_attr<96>());
+    HIP_TRY(xfmr_attn_attr<112>());
+    HIP_TRY(xfmr_attn_attr<128>());
+    // the engine opens here, not in hificar_xfmr_create: a handle can be created and described without a device
+    if ((rc = engine_open(h, true)) != HIFICAR_OK) return rc;
+    h->precision = HIFICAR_PREC_F32;
+    h->use_pair = false;
+    h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's result does not depend on what it is batched with
+    HIP_TRY(hipDeviceSynchronize());
+    g->tensors.clear();
+    g->finalized = true;
+    return HIFICAR_OK;
+}
+
+struct XfmrWorkspace {
+    float* xin;     // [rows][cin_pad]
+    float* r[3];    // [rows][F]
+    float* wide;    // [rows][3072]
+    size_t bytes;
+};
+
+static XfmrWorkspace xfmr_plan_workspace(const hificar_xfmr* g, int B, int T, void* base) {
+    const size_t rows = round_up_sz((size_t)std::max(B, 0) * (size_t)std::max(T, 0), 256);  // whole tiles of slack behind the last row
+    const size_t xb = round_up_sz(rows * g->cin_pad * sizeof(float), 256);
+    const size_t rb = round_up_sz(rows * g->cfg.hidden_dim * sizeof(float), 256);
+    const size_t wb = round_up_sz(rows * kXfmrFF * sizeof(float), 256);
+    XfmrWorkspace w;
+    char* p = static_cast<char*>(base);
+    w.xin = reinterpret_cast<float*>(p);
+    for (int i = 0; i < 3; ++i) w.r[i] = reinterpret_cast<float*>(p + xb + i * rb);
+    w.wide = reinterpret_cast<float*>(p + xb + 3 * rb);
+    w.bytes = xb + 3 * rb + wb;
+    return w;
+}
+
+extern "C" size_t hificar_xfmr_workspace_bytes(const hificar_xfmr* g, int B, int T) {
+    if (!g || B < 1 || T < 1) return 0;
+    return xfmr_plan_workspace(g, B, T, nullptr).bytes;
+}
+
+// Test aid: the next forwards copy the named intermediate, as rows (B, T, hidden_dim), into dst (capacity in floats).  Names: "conv_blocks",
+// "w_raw_in", "layers.<n>.norm1" (the attention sub-block's output), "layers.<n>" (the layer's output).  name = NULL: forget all; dst = NULL: forget one.
+extern "C" int hificar_xfmr_debug_tap(hificar_xfmr* g, const char* name, float* dst, size_t capacity) {
+    if (!g) return fail(HIFICAR_E_INVALID, "null handle");
+    if (!name) {
+        g->taps.clear();
+        return HIFICAR_OK;
+    }
+    if (!dst) {
+        g->taps.erase(name);
+        return HIFICAR_OK;
+    }
+    g->taps[name] = {dst, capacity};
+    return HIFICAR_OK;
+}
+
+static int xfmr_emit_tap(hificar_xfmr* g, const std::string& name, const float* rows, size_t floats, hipStream_t stream) {
+    auto it = g->taps.find(name);
+    if (it == g->taps.end()) return HIFICAR_OK;
+    if (it->second.cap < floats) return fail(HIFICAR_E_INVALID, "debug tap '%s' needs %zu floats, buffer has %zu", name.c_str(), floats, it->second.cap);
+    HIP_TRY(hipMemcpyAsync(it->second.dst, rows, floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    return HIFICAR_OK;
+}
+
+extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int T,
+                                    void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!g || !x || !out) return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: null argument");
+    if (!g->finalized) return fail(HIFICAR_E_STATE, "hificar_xfmr_forward before hificar_xfmr_finalize");
+    if (B < 1 || T < 1 || B > 65535 || (long long)B * T > (1LL << 30) / 8 || (long long)B * T * kXfmrFF >= (1LL << 31))
+        return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: B=%d, T=%d out of range (B T 3072 < 2^31)", B, T);
+    if (lengths_host && !lengths) return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: lengths_host without the device copy");
+    if (lengths_host)
+        for (int b = 0; b < B; ++b)
+            if (lengths_host[b] < 0 || lengths_host[b] > T)
+                return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: lengths[%d]=%d outside 0 .. T=%d", b, lengths_host[b], T);
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
+    const XfmrWorkspace ws = xfmr_plan_workspace(g, B, T, workspace);
+    if (workspace_bytes < ws.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
+    hificar_engine* h = &g->eng;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc;
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads;
+    const double M = (double)B * T;
+    const size_t MF = (size_t)B * T * F;
+    Ragged rg;
+    rg.seq_len = lengths;
+    rg.frames = T;
+    // one launch of one layer: xs -> y (fp32) and / or ys (the ReLU'd copy), + res
+    auto conv = [&](const ConvLayer& L, const float* xs, const float* res, float* y, float* ys) {
+        const ConvLayer* ls[1] = {&L};
+        ConvIO io[1];
+        io[0] = ConvIO();
+        io[0].xs = reinterpret_cast<const char*>(xs);
+        io[0].res = res;
+        io[0].y = y;
+        io[0].ys = reinterpret_cast<char*>(ys);
+        return launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream);
+    };
+    auto layer_norm = [&](const float* src, const float* gamma, const float* beta, float* dst) {
+        XfmrLnParams p;
+        p.x = src;
+        p.gamma = gamma;
+        p.beta = beta;
+        p.lengths = lengths;
+        p.y = dst;
+        p.B = B;
+        p.T = T;
+        p.F = F;
+        ProfScope prof(h, stream, "xfmr_ln_kernel", 8.0 * M * F, 8.0 * M * F);
+        hipLaunchKernelGGL(xfmr_ln_kernel, dim3((unsigned)(((long long)B * T + 3) / 4)), dim3(256), 0, stream, p);
+        return hipGetLastError();
+    };
+    {
+        ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
+        hipLaunchKernelGGL(xfmr_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, ws.xin,
+                           lengths, C, g->cin_pad, T);
+        HIP_TRY(hipGetLastError());
+    }
+    // conv_blocks: the block's input in `in`, its output in r[2] (blocks 0 and 2) or r[1] (block 1); r[0] holds conv1's ReLU'd output
+    const float* in = ws.xin;
+    for (int i = 0; i < 3; ++i) {
+        float* const dst = i == 1 ? ws.r[1] : ws.r[2];
+        float* const other = i == 1 ? ws.r[2] : ws.r[1];
+        if ((rc = conv(g->c1[i], in, nullptr, nullptr, ws.r[0])) != HIFICAR_OK) return rc;
+        const float* res = in;
+        if (i == 0 && g->rp.cout) {
+            if ((rc = conv(g->rp, in, nullptr, other, nullptr)) != HIFICAR_OK) return rc;
+            res = other;
+        }
+        if ((rc = conv(g->c2[i], ws.r[0], res, nullptr, dst)) != HIFICAR_OK) return rc;
+        in = dst;
+    }
+    if ((rc = xfmr_emit_tap(g, "conv_blocks", in, MF, stream)) != HIFICAR_OK) return rc;
+    float* X = ws.r[0];  // the layer input; r[1] and r[2] are free from here on
+    if ((rc = conv(g->w_in, in, nullptr, X, nullptr)) != HIFICAR_OK) return rc;
+    if ((rc = xfmr_emit_tap(g, "w_raw_in", X, MF, stream)) != HIFICAR_OK) return rc;
+    for (int l = 0; l < g->cfg.elayers; ++l) {
+        const XfmrEncLayer& E = g->enc[(size_t)l];
+        const std::string name = "layers." + std::to_string(l);
+        if ((rc = conv(E.qkv, X, nullptr, ws.wide, nullptr)) != HIFICAR_OK) return rc;
+        {
+            XfmrAttnParams p;
+            p.qkv = ws.wide;
+            p.emb = E.d_emb;
+            p.lengths = lengths;
+            p.out = ws.r[1];
+            p.T = T;
+            p.F = F;
+            p.scale = (float)(1.0 / std::sqrt((double)d));
+            // per query at most 199 keys: Q K^T, the positional product and P V
+            ProfScope prof(h, stream, "xfmr_attn_kernel", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
+            const hipError_t e = xfmr_attn_launch(d, p, dim3((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B), stream);
+            if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn_kernel launch failed: %s", hipGetErrorString(e));
+        }
+        if ((rc = conv(E.wo, ws.r[1], X, ws.r[2], nullptr)) != HIFICAR_OK) return rc;
+        HIP_TRY(layer_norm(ws.r[2], E.d_ln[0], E.d_ln[1], ws.r[1]));
+        if ((rc = xfmr_emit_tap(g, name + ".norm1", ws.r[1], MF, stream)) != HIFICAR_OK) return rc;
+        if ((rc = conv(E.l1, ws.r[1], nullptr, nullptr, ws.wide)) != HIFICAR_OK) return rc;
+        if ((rc = conv(E.l2, ws.wide, ws.r[1], ws.r[2], nullptr)) != HIFICAR_OK) return rc;
+        HIP_TRY(layer_norm(ws.r[2], E.d_ln[2], E.d_ln[3], X));
+        if ((rc = xfmr_emit_tap(g, name, X, MF, stream)) != HIFICAR_OK) return rc;
+    }
+    if ((rc = conv(g->w_out, X, nullptr, ws.wide, nullptr)) != HIFICAR_OK) return rc;
+    {
+        const int Op = g->w_out.cout_pad;
+        ProfScope prof(h, stream, "xfmr_out_kernel", 0.0, 4.0 * M * (O + Op));
+        hipLaunchKernelGGL(xfmr_out_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, ws.wide, out, lengths, O,
+                           Op, T);
+        HIP_TRY(hipGetLastError());
+    }
+    return HIFICAR_OK;
+}

@@ -13,6 +13,7 @@ from .discriminator import (  # noqa: F401
 from .bigru import BiGRU  # noqa: F401
 from .gblock import GBlockGenerator  # noqa: F401
 from .hifigan import HiFiGANGenerator  # noqa: F401
+from .transformer import Transformer  # noqa: F401
 
-__all__ = ["HiFiGANGenerator", "GBlockGenerator", "BiGRU", "HiFiGANMultiScaleMultiPeriodDiscriminator", "HiFiGANMultiScaleDiscriminator", "HiFiGANMultiPeriodDiscriminator",
+__all__ = ["HiFiGANGenerator", "GBlockGenerator", "BiGRU", "Transformer", "HiFiGANMultiScaleMultiPeriodDiscriminator", "HiFiGANMultiScaleDiscriminator", "HiFiGANMultiPeriodDiscriminator",
            "HiFiGANScaleDiscriminator", "HiFiGANPeriodDiscriminator"]

@@ -46,7 +46,7 @@ def load_model(checkpoint, config=None, stats=None):
     if stats is not None:
         model.register_stats(stats)
 
-    # (a BiGRU's out_channels are EMA dimensions, not PQMF sub-bands: nothing is attached to it)
-    if config["generator_params"]["out_channels"] > 1 and generator_type != "BiGRU":
+    # (a BiGRU's or a Transformer's out_channels are feature dimensions, not PQMF sub-bands: nothing is attached to them)
+    if config["generator_params"]["out_channels"] > 1 and generator_type not in ("BiGRU", "Transformer"):
         raise NotImplementedError("multi-band (PQMF) generators are out of scope for this package")
     return model

@@ -512,3 +512,86 @@ def bigru_dropout_mask(seed: int, offset: int, site, shape, p: float) -> np.ndar
     u = (bits >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
     scale = np.float32(1.0) / (np.float32(1.0) - p32)
     return np.where(u >= p32, scale, np.float32(0.0)).astype(np.float32).reshape(shape)
+
+
+# ------------------------------------------------------------------------------------------------
+# Transformer, the feature-to-feature encoder (reference articulatory/models/transformer.py:21-105)
+# ------------------------------------------------------------------------------------------------
+def transformer_param_spec(in_channels=8, out_channels=80, elayers=6, hidden_dim=768, **_ignored):
+    """Ordered {state_dict key: shape} of the reference's ``Transformer(**kwargs)`` without extra_art / num_ph: a ResBlock lists conv1, bn1
+    (parameters, then buffers), conv2, bn2 and, where it changes the width, residual_path and res_norm; an encoder layer its attention's
+    w_q, w_k, w_v, w_o and table, linear1, linear2, norm1, norm2.  Checked key-for-key against the real class by
+    tools/make_golden_transformer.py (tests/golden/gold_transformer_keys.txt)."""
+    spec = OrderedDict()
+    F, d = hidden_dim, hidden_dim // 8
+
+    def bn(base):
+        for t in ("weight", "bias", "running_mean", "running_var"):
+            spec[f"{base}.{t}"] = (F,)
+        spec[f"{base}.num_batches_tracked"] = ()
+
+    for i in range(3):
+        cin = in_channels if i == 0 else F
+        b = f"conv_blocks.{i}"
+        spec[b + ".conv1.weight"] = (F, cin, 3)
+        spec[b + ".conv1.bias"] = (F,)
+        bn(b + ".bn1")
+        spec[b + ".conv2.weight"] = (F, F, 3)
+        spec[b + ".conv2.bias"] = (F,)
+        bn(b + ".bn2")
+        if cin != F:
+            spec[b + ".residual_path.weight"] = (F, cin, 1)
+            spec[b + ".residual_path.bias"] = (F,)
+            bn(b + ".res_norm")
+    spec["w_raw_in.weight"] = (F, F)
+    spec["w_raw_in.bias"] = (F,)
+    for l in range(elayers):
+        b = f"transformer.layers.{l}"
+        for w in ("w_q", "w_k", "w_v"):
+            spec[f"{b}.self_attn.{w}"] = (8, F, d)
+        spec[b + ".self_attn.w_o"] = (8, d, F)
+        spec[b + ".self_attn.relative_positional.embeddings"] = (8, 199, d, 1)
+        spec[b + ".linear1.weight"] = (3072, F)
+        spec[b + ".linear1.bias"] = (3072,)
+        spec[b + ".linear2.weight"] = (F, 3072)
+        spec[b + ".linear2.bias"] = (F,)
+        for n in ("norm1", "norm2"):
+            spec[f"{b}.{n}.weight"] = (F,)
+            spec[f"{b}.{n}.bias"] = (F,)
+    spec["w_out.weight"] = (out_channels, F)
+    spec["w_out.bias"] = (out_channels,)
+    return spec
+
+
+def synth_transformer_state_dict(params: dict, seed: int = 1234, gain: float = 1.0) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic reference-layout state_dict of a Transformer from the same name-keyed generator as the other specs: matrices and conv
+    kernels U(+-gain * sqrt(3 / fan_in)) (w_q / w_k / w_v: fan_in = hidden_dim, w_o: 8 d; the positional table U(+-sqrt(3 / d)), the
+    reference's initial spread), biases U(+-0.05), batch norms that are not the identity (running_var in [0.5, 2], weight in [0.8, 1.2],
+    running_mean and bias in +-0.3), layer norms with weight in [0.8, 1.2], num_batches_tracked an int64 scalar."""
+    out = OrderedDict()
+    for name, shape in transformer_param_spec(**params).items():
+        leaf = name.rsplit(".", 1)[-1]
+        norm = any(t in name for t in (".bn1.", ".bn2.", ".res_norm.", ".norm1.", ".norm2."))
+        if leaf == "num_batches_tracked":
+            out[name] = np.array(1000, dtype=np.int64)
+        elif leaf == "running_var":
+            out[name] = uniform(seed, name, shape, 0.5, 2.0)
+        elif norm and leaf == "weight":
+            out[name] = uniform(seed, name, shape, 0.8, 1.2)
+        elif leaf == "running_mean" or (norm and leaf == "bias" and ".norm" not in name):
+            out[name] = uniform(seed, name, shape, -0.3, 0.3)
+        elif leaf == "embeddings":
+            b = np.sqrt(3.0 / shape[2])
+            out[name] = uniform(seed, name, shape, -b, b)
+        elif leaf in ("w_q", "w_k", "w_v"):
+            b = gain * np.sqrt(3.0 / shape[1])
+            out[name] = uniform(seed, name, shape, -b, b)
+        elif leaf == "w_o":
+            b = gain * np.sqrt(3.0 / (shape[0] * shape[1]))
+            out[name] = uniform(seed, name, shape, -b, b)
+        elif len(shape) >= 2:
+            b = gain * np.sqrt(3.0 / int(np.prod(shape[1:])))
+            out[name] = uniform(seed, name, shape, -b, b)
+        else:
+            out[name] = uniform(seed, name, shape, -0.05, 0.05)
+    return out

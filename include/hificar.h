@@ -26,6 +26,8 @@
  *                           forward(c, spk_id=, ar=prev, ph=)                    articulatory/bin/decode.py:54-83 + hifigan.py:212-220
  *   hificar_bigru_*         BiGRU (the speech-to-EMA inversion model): __init__, load_state_dict, eval().to(device), forward
  *                                                                articulatory/models/pytorch_models.py:22-72 (declared at the end of this file)
+ *   hificar_xfmr_*          Transformer (the feature-to-feature encoder): __init__, load_state_dict, eval().to(device), forward
+ *                                                                articulatory/models/transformer.py:21-77 (declared at the end of this file)
  *   hificar_pcm16           sf.write(..., "PCM_16") sample conversion articulatory/bin/decode.py:319-324
  *   hificar_workspace_bytes (torch's caching allocator does this implicitly in the reference)
  *   hificar_last_error      Python exceptions / assert           articulatory/models/hifigan.py:78-80
@@ -72,7 +74,7 @@ extern "C" {
 
 typedef struct hificar_handle hificar_handle;
 /* The conv engine every model of the library launches through (plans, schedules, stream ordering, profiling).  A generator handle
- * has one (hificar_engine_of), so do the discriminators (hificar_disc_engine) and the BiGRU (hificar_bigru_engine); it lives and
+ * has one (hificar_engine_of), so do the discriminators (hificar_disc_engine), the BiGRU (hificar_bigru_engine) and the Transformer (hificar_xfmr_engine); it lives and
  * dies with its model.  Only the profiling calls take it: the generator's entry points do not accept another model's engine. */
 typedef struct hificar_engine hificar_engine;
 
@@ -621,6 +623,70 @@ int hificar_bigru_forward_train_ragged(hificar_bigru* h, const float* x, const i
  * hificar_bigru_forward_train_ragged: see there. */
 int hificar_bigru_backward(hificar_bigru* h, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Feature-to-feature mapping: the Transformer encoder (articulatory/models/transformer.py:21-105; layers articulatory/layers/pytorch_layers.py:94-423)
+ * in eval mode — three ResBlocks (Conv1d k = 3 + BatchNorm1d on running statistics, ReLU), Linear, `elayers` post-LayerNorm encoder layers
+ * (8-head self-attention with learned relative positions up to distance 100, a 3072-wide ReLU feed-forward), Linear.  nhead = 8,
+ * dim_feedforward = 3072 and relative_positional_distance = 100 are the reference constructor's constants.  The attention is computed in its
+ * banded form: a sequence of more than 100 frames has every logit with |k - q| >= 100 lowered by 1e8 in the reference (weight exactly 0 in
+ * fp32), so only keys with |k - q| <= 99 are visited.  Not built: training, bf16x3, extra_art, num_ph (the binding refuses them).
+ * Exact fp32.  Errors as everywhere: a negative HIFICAR_E_* code and hificar_last_error().
+ * --------------------------------------------------------------------------------------------------------------------------- */
+#define HIFICAR_XFMR_MAX_IN 4096
+#define HIFICAR_XFMR_MAX_OUT 1024
+#define HIFICAR_XFMR_MAX_HIDDEN 1024
+#define HIFICAR_XFMR_MAX_LAYERS 24
+
+/* Mirrors the keyword arguments of Transformer.__init__ (transformer.py:22-24) that shape eval-mode inference. */
+typedef struct hificar_xfmr_config {
+    int32_t in_channels;  /* 1 .. HIFICAR_XFMR_MAX_IN */
+    int32_t out_channels; /* 1 .. HIFICAR_XFMR_MAX_OUT */
+    int32_t elayers;      /* 1 .. HIFICAR_XFMR_MAX_LAYERS */
+    int32_t hidden_dim;   /* a multiple of 128, at most HIFICAR_XFMR_MAX_HIDDEN: head size hidden_dim / 8 = 16 .. 128 in steps of 16 */
+} hificar_xfmr_config;
+
+typedef struct hificar_xfmr hificar_xfmr;
+
+/* Transformer.__init__: an empty model for these hyper-parameters.  Touches no device. */
+int hificar_xfmr_create(const hificar_xfmr_config* cfg, hificar_xfmr** out);
+
+/* load_state_dict, one tensor at a time by its reference state_dict name: "conv_blocks.<i>.conv1.weight" (F, C or F, 3), ".conv1.bias",
+ * ".bn1.weight" / ".bias" / ".running_mean" / ".running_var" (F), the same for conv2 / bn2, and for block 0 of a model with in_channels != F
+ * "conv_blocks.0.residual_path.weight" (F, C, 1), ".bias", "conv_blocks.0.res_norm.*"; "w_raw_in.weight" (F, F), ".bias";
+ * "transformer.layers.<l>.self_attn.w_q" / "w_k" / "w_v" (8, F, d), ".w_o" (8, d, F), ".relative_positional.embeddings" (8, 199, d, 1),
+ * ".linear1.weight" (3072, F), ".linear2.weight" (F, 3072), their biases, ".norm1" / ".norm2" ".weight" / ".bias" (F); "w_out.weight" (out, F),
+ * "w_out.bias".  F = hidden_dim, d = F / 8.  data: HOST pointer to contiguous fp32; the caller keeps ownership. */
+int hificar_xfmr_set_weight(hificar_xfmr* h, const char* name, const float* data, const int64_t* shape, int ndim);
+
+/* model.eval().to(device): checks that every tensor arrived, folds the batch norms into their convs (in double), repacks w_q / w_k / w_v into
+ * one GEMM and w_o into another, uploads.  Synchronises the device once. */
+int hificar_xfmr_finalize(hificar_xfmr* h);
+
+/* Bytes of device scratch hificar_xfmr_forward needs for B sequences of T frames: the input rows, three row buffers of hidden_dim floats and
+ * one of 3072 floats per frame (B T rounded up to 256 rows). */
+size_t hificar_xfmr_workspace_bytes(const hificar_xfmr* h, int B, int T);
+
+/* Transformer.forward in eval mode (transformer.py:55-77): x (B, in_channels, T) device fp32 -> out (B, out_channels, T) device fp32.
+ * lengths: DEVICE pointer to B int32 frame counts (0 <= lengths[b] <= T) or NULL (all T): sequence b is computed exactly as if it were alone
+ * with lengths[b] frames — the convs see zero padding at its own end, its keys stop at its length — bit for bit, and out[b, :, lengths[b]:]
+ * is written as zeros; what x holds past a length is never read.  The reference has no such batches: this is its per-utterance loop
+ * (articulatory/bin/decode.py:292-351) run B utterances at a time.  lengths_host: optional HOST copy of the same values, checked against T before
+ * anything is enqueued.  workspace: 256-byte aligned, hificar_xfmr_workspace_bytes(h, B, T) bytes; what it holds on entry does not matter.
+ * B T 3072 < 2^31.  Stream rules as in the conventions at the top. */
+int hificar_xfmr_forward(hificar_xfmr* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int T,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* Test aid: the following forwards also copy the named intermediate, as rows (B, T, hidden_dim), into dst (device, `capacity` floats).
+ * Names: "conv_blocks", "w_raw_in", "layers.<l>.norm1" (the attention sub-block's output), "layers.<l>" (the layer's output).
+ * name = NULL forgets every tap, dst = NULL that one. */
+int hificar_xfmr_debug_tap(hificar_xfmr* h, const char* name, float* dst, size_t capacity);
+
+/* The model's engine, for hificar_profile_begin / hificar_profile_end. */
+hificar_engine* hificar_xfmr_engine(hificar_xfmr* h);
+
+/* del model */
+void hificar_xfmr_destroy(hificar_xfmr* h);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""The Transformer feature model (articulatory_amd.models.Transformer, C ABI hificar_xfmr_*) at the reference's default size (12 -> 80,
+hidden 768, 6 layers), T = 2000.
+   python tools/transformer_bench.py [--batches 1 8 32] [--frames 2000] [--window 0.5] [--out profiles/transformer.txt]
+
+Per batch size B, device time from events, every shape warmed up first, windows of at least --window seconds:
+  native   Transformer.forward (libhificar.so)
+  stock    the same function from stock PyTorch-ROCm operators in fp32 on the same GPU: tests/transformer_oracle.py (conv1d, batch_norm,
+           linear, einsum, softmax, layer_norm; the attention in its banded form, query chunks of 128 against the keys they can see)
+alternated native / stock / native / stock in the same process: the two native windows run on unchanged code, and their difference is the
+spread a ratio has to exceed.  The ratio reported is the conservative one: fastest stock window over slowest native window.  Then, with
+hificar_profile_begin / hificar_profile_end on one native forward: time per kernel, the attention kernel's share of the forward and its
+achieved TFLOP/s — counted as 2 * 3 * 199 * hidden FLOP per frame and layer (Q K^T, the positional product, P V over a full band) — against
+the 157.3 TFLOP/s fp32 matrix peak.
+Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from articulatory_amd import _native  # noqa: E402
+from articulatory_amd.models import Transformer  # noqa: E402
+from articulatory_amd.utils.synth import synth_transformer_state_dict, uniform  # noqa: E402
+from transformer_oracle import TransformerOracle  # noqa: E402
+
+PARAMS = dict(in_channels=12, out_channels=80, elayers=6, hidden_dim=768)
+PEAK_TFLOPS = 157.3
+
+
+def window(fn, x, seconds):
+    """Mean device milliseconds per call over a window of at least `seconds` (events around blocks of calls)."""
+    total_ms, calls, n = 0.0, 0, 1
+    while total_ms < seconds * 1e3:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn(x)
+        e1.record()
+        e1.synchronize()
+        total_ms += e0.elapsed_time(e1)
+        calls += n
+        n = min(n * 2, 64)
+    return total_ms / calls
+
+
+def kernel_profile(m, x):
+    lib, eng = m._lib, m.engine()
+    _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
+    m(x)
+    stats = (_native.HificarKernelStat * 128)()
+    n = ctypes.c_int()
+    _native.check(lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
+    return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(n.value)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 32])
+    ap.add_argument("--frames", type=int, default=2000)
+    ap.add_argument("--window", type=float, default=0.5)
+    ap.add_argument("--no-stock", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    T = a.frames
+    sd = synth_transformer_state_dict(PARAMS, seed=6101)
+    native = Transformer(**PARAMS)
+    native.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    native = native.eval().cuda()
+    stock = None if a.no_stock else TransformerOracle(sd, dtype=torch.float32, device="cuda").forward
+    lines = []
+    with torch.no_grad():
+        for B in a.batches:
+            x = torch.from_numpy(uniform(1, f"bench.{B}", (B, PARAMS["in_channels"], T), -1.0, 1.0)).cuda()
+            res = {"B": B, "T": T}
+            y = native(x)
+            if stock is not None:
+                ys = stock(x)
+                res["native_vs_stock_max_rel"] = float((y - ys).abs().max() / ys.abs().max())
+                for _ in range(2):
+                    native(x), stock(x)
+            torch.cuda.synchronize()
+            n1 = window(native, x, a.window)
+            s1 = None if stock is None else window(stock, x, a.window)
+            n2 = window(native, x, a.window)
+            s2 = None if stock is None else window(stock, x, a.window)
+            res["native_ms"] = [round(n1, 4), round(n2, 4)]
+            res["native_frames_per_s"] = round(B * T / (min(n1, n2) * 1e-3))
+            res["native_spread"] = round(abs(n1 - n2) / min(n1, n2), 4)
+            if s1 is not None:
+                res["stock_ms"] = [round(s1, 4), round(s2, 4)]
+                res["stock_spread"] = round(abs(s1 - s2) / min(s1, s2), 4)
+                res["stock_over_native"] = round(min(s1, s2) / max(n1, n2), 3)
+            prof = kernel_profile(native, x)
+            total = sum(ms for _, ms in prof.values())
+            attn = prof.get("xfmr_attn_kernel", (0, 0.0))[1]
+            gemm = sum(ms for k, (_, ms) in prof.items() if k.startswith("conv_"))
+            res["kernels_ms"] = {k: round(ms, 4) for k, (_, ms) in sorted(prof.items())}
+            res["profiled_total_ms"] = round(total, 4)
+            res["attn_share"] = round(attn / total, 4) if total else None
+            res["gemm_share"] = round(gemm / total, 4) if total else None
+            flop = 2.0 * 3 * 199 * PARAMS["hidden_dim"] * B * T * PARAMS["elayers"]
+            res["attn_tflops"] = round(flop / (attn * 1e-3) / 1e12, 2) if attn else None
+            res["attn_of_peak"] = round(flop / (attn * 1e-3) / 1e12 / PEAK_TFLOPS, 4) if attn else None
+            lines.append(json.dumps(res))
+            print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
