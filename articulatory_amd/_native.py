@@ -118,6 +118,14 @@ SYMBOLS = (
     "hificar_xfmr_debug_tap",
     "hificar_xfmr_engine",
     "hificar_xfmr_destroy",
+    "hificar_xfmr_set_parameters_device",
+    "hificar_xfmr_grad_count",
+    "hificar_xfmr_grad_info",
+    "hificar_xfmr_grad_floats",
+    "hificar_xfmr_tape_bytes",
+    "hificar_xfmr_train_workspace_bytes",
+    "hificar_xfmr_forward_train",
+    "hificar_xfmr_backward",
     "hificar_destroy",
     "hificar_last_error",
     "hificar_version",
@@ -506,6 +514,22 @@ def load_library():
     lib.hificar_xfmr_engine.restype = vp
     lib.hificar_xfmr_destroy.argtypes = [vp]
     lib.hificar_xfmr_destroy.restype = None
+    lib.hificar_xfmr_set_parameters_device.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp), ci, vp]
+    lib.hificar_xfmr_set_parameters_device.restype = ci
+    lib.hificar_xfmr_grad_count.argtypes = [vp]
+    lib.hificar_xfmr_grad_count.restype = ci
+    lib.hificar_xfmr_grad_info.argtypes = [vp, ci, ctypes.c_char_p, ctypes.POINTER(c64), ctypes.POINTER(c64)]
+    lib.hificar_xfmr_grad_info.restype = ci
+    lib.hificar_xfmr_grad_floats.argtypes = [vp]
+    lib.hificar_xfmr_grad_floats.restype = c64
+    lib.hificar_xfmr_tape_bytes.argtypes = [vp, ci, ci]
+    lib.hificar_xfmr_tape_bytes.restype = cs
+    lib.hificar_xfmr_train_workspace_bytes.argtypes = [vp, ci, ci]
+    lib.hificar_xfmr_train_workspace_bytes.restype = cs
+    lib.hificar_xfmr_forward_train.argtypes = [vp, vp, vp, vp, ci, ci, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp, cs, vp, cs, vp]
+    lib.hificar_xfmr_forward_train.restype = ci
+    lib.hificar_xfmr_backward.argtypes = [vp, vp, ci, ci, vp, cs, vp, vp, vp, cs, vp]
+    lib.hificar_xfmr_backward.restype = ci
     lib.hificar_destroy.argtypes = [vp]
     lib.hificar_destroy.restype = None
     lib.hificar_last_error.argtypes = []

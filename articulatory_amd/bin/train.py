@@ -226,8 +226,8 @@ class Trainer:
     def __init__(self, config, device, distributed=False):
         self.config, self.device, self.distributed = config, device, distributed
         gtype_name = config.get("generator_type", "HiFiGANGenerator")
-        if gtype_name == "BiGRU":
-            raise NotImplementedError("generator_type BiGRU trains with InversionTrainer (dataset_mode art / a2m / m2a), not with the GAN Trainer")
+        if gtype_name in INVERSION_TYPES:
+            raise NotImplementedError(f"generator_type {gtype_name} trains with InversionTrainer (dataset_mode art / a2m / m2a), not with the GAN Trainer")
         if gtype_name not in ("HiFiGANGenerator", "GBlockGenerator"):
             raise NotImplementedError(f"generator_type {gtype_name} is not built")
         import articulatory_amd.models as models
@@ -633,24 +633,28 @@ class LengthBucketBatchSampler(torch.utils.data.Sampler):
 PACKAGE_MODES = ("random_window", "pad")
 
 
+INVERSION_TYPES = ("BiGRU", "Transformer")  # the feature-to-feature models InversionTrainer builds
+
+
 class InversionTrainer:
-    """The reference's training step for ``generator_type: BiGRU`` (dataset_mode art / a2m / m2a): the generator half of ``_train_step``
+    """The reference's training step for ``generator_type: BiGRU`` or ``Transformer`` (dataset_mode art / a2m / m2a): the generator half of ``_train_step``
     (train.py:268-383) with ``criterion["mel"] = F.l1_loss`` — forward in train() mode, L1 * lambda_aux, zero_grad, backward, gradient
     clipping, optimizer step, scheduler step.  No discriminator: the reference would start an adversarial phase on the trajectories at
     discriminator_train_start_steps, which is not built, so a config that reaches it is refused.
 
     ``package_mode: pad`` (batches of ``PadCollater``: whole utterances with their lengths): the step is ``forward_padded`` ->
     ``masked_l1_loss`` * lambda_aux, the rest as above; the padding takes no part in statistics, loss or gradients (the reference's pad mode
-    trains on it).  ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval mode, under ``masked_l1_loss``."""
+    trains on it); BiGRU only — ragged Transformer training is not built.  ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval
+    mode, under ``masked_l1_loss``."""
 
     def __init__(self, config, device):
         self.config, self.device = config, device
         gtype = config.get("generator_type", "HiFiGANGenerator")
-        if gtype != "BiGRU":
-            raise NotImplementedError(f"InversionTrainer trains generator_type BiGRU (got {gtype})")
+        if gtype not in INVERSION_TYPES:
+            raise NotImplementedError(f"InversionTrainer trains generator_type BiGRU or Transformer (got {gtype})")
         mode = config.get("dataset_mode", "default")
         if mode not in INVERSION_MODES:
-            raise NotImplementedError(f"generator_type BiGRU trains with dataset_mode in {' / '.join(INVERSION_MODES)} (got {mode!r})")
+            raise NotImplementedError(f"generator_type {gtype} trains with dataset_mode in {' / '.join(INVERSION_MODES)} (got {mode!r})")
         if "train_max_steps" not in config:
             raise ValueError("the config has no train_max_steps")
         if config.get("discriminator_train_start_steps", 0) < config["train_max_steps"]:
@@ -664,9 +668,12 @@ class InversionTrainer:
         self.package_mode = config.get("package_mode", "random_window")
         if self.package_mode not in PACKAGE_MODES:
             raise NotImplementedError(f"package_mode {self.package_mode!r} is not built for inversion models (one of {' / '.join(PACKAGE_MODES)})")
+        if self.package_mode == "pad" and gtype != "BiGRU":
+            raise NotImplementedError(f"package_mode pad is not built for generator_type {gtype} (ragged training exists for the BiGRU only; "
+                                      "use package_mode random_window)")
         import articulatory_amd.models as models
 
-        self.G = models.BiGRU(**config["generator_params"]).to(device).train()
+        self.G = getattr(models, gtype)(**config["generator_params"]).to(device).train()
         self.optimizer = {"generator": _optimizer(config.get("generator_optimizer_type", "Adam"), self.G.parameters(),
                                                   config["generator_optimizer_params"], config.get("fused_optimizers", True))}
         self.scheduler = {"generator": getattr(torch.optim.lr_scheduler, config.get("generator_scheduler_type", "StepLR"))(
@@ -761,7 +768,7 @@ class InversionTrainer:
 
 
 def _main_inversion(a, config, device, rank):
-    """``main`` for generator_type BiGRU: input / target ``.npy`` scp pairs (--feats-scp: the model's input side, --audio-scp: its target
+    """``main`` for generator_type BiGRU / Transformer: input / target ``.npy`` scp pairs (--feats-scp: the model's input side, --audio-scp: its target
     side; dataset_mode m2a swaps them) or --synthetic N, cut into equal windows of batch_max_frames + 2 aux_context_window frames
     (package_mode random_window, the default) or taken whole in length-bucketed, zero-padded batches (package_mode pad; config keys
     pad_max_frames, pad_bucket_batches; --synthetic then draws each utterance's length uniformly from one to four windows).
@@ -778,7 +785,7 @@ def _main_inversion(a, config, device, rank):
                            frames_range=(window, 4 * window) if pad else None)
     else:
         if not (a.audio_scp and a.feats_scp):
-            raise SystemExit("generator_type BiGRU: give --feats-scp (input frames) and --audio-scp (target frames) of .npy files, or --synthetic N")
+            raise SystemExit(f"generator_type {config.get('generator_type')}: give --feats-scp (input frames) and --audio-scp (target frames) of .npy files, or --synthetic N")
         data = WindowPairs(a.feats_scp, a.audio_scp, min_frames=0 if pad else window, swap=swap)
     sampler = None
     if pad:
@@ -854,8 +861,8 @@ def main(argv=None):
     ap.add_argument("--feats-scp")
     ap.add_argument("--train-dumpdir", help="dump directory of <utt>.h5 (wave + feats) or <utt>-wave.npy / <utt>-feats.npy files (config: format)")
     ap.add_argument("--dev-dumpdir", help="dev-set dump directory: evaluated every eval_interval_steps (rank 0)")
-    ap.add_argument("--dev-feats-scp", help="generator_type BiGRU: the dev set's input frames (.npy scp), evaluated whole every eval_interval_steps")
-    ap.add_argument("--dev-audio-scp", help="generator_type BiGRU: the dev set's target frames (.npy scp)")
+    ap.add_argument("--dev-feats-scp", help="generator_type BiGRU / Transformer: the dev set's input frames (.npy scp), evaluated whole every eval_interval_steps")
+    ap.add_argument("--dev-audio-scp", help="generator_type BiGRU / Transformer: the dev set's target frames (.npy scp)")
     ap.add_argument("--synthetic", type=int, default=0, help="train on this many random utterances instead of a dataset")
     ap.add_argument("--utt2spk", help="'utt spk' lines (use_spk_id: speaker ids are ranks in the sorted speaker list)")
     ap.add_argument("--ph-scp", help="'utt path.npy' lines: one phoneme index per feature frame (use_ph / use_ph_loss)")
@@ -885,9 +892,9 @@ def main(argv=None):
             raise SystemExit(f"WORLD_SIZE={world} but the process group has {torch.distributed.get_world_size()} ranks")
         logging.info(f"rank {rank}/{world}: {pinned or 'host affinity unchanged'}")
     config["distributed"] = world > 1
-    if config.get("generator_type", "HiFiGANGenerator") == "BiGRU":
+    if config.get("generator_type", "HiFiGANGenerator") in INVERSION_TYPES:
         if world > 1:
-            raise SystemExit("generator_type BiGRU trains on one GPU (multi-GPU training of the inversion model is not built)")
+            raise SystemExit(f"generator_type {config['generator_type']} trains on one GPU (multi-GPU training of the inversion models is not built)")
         return _main_inversion(a, config, device, rank)
     hop = hop_of(config)
     frames = config["batch_max_steps"] // hop

@@ -9,6 +9,7 @@
 #include "hificar_bigru_kernels.hip.h"
 #include "hificar_bigru_train_kernels.hip.h"
 #include "hificar_xfmr_kernels.hip.h"
+#include "hificar_xfmr_train_kernels.hip.h"
 
 #include "../../include/hificar.h"
 
@@ -2467,3 +2468,4 @@ extern "C" int hificar_pcm16(const float* x, int16_t* y, size_t n, void* stream)
 #include "hificar_bigru.hip.inc"
 #include "hificar_bigru_train.hip.inc"
 #include "hificar_xfmr.hip.inc"
+#include "hificar_xfmr_train.hip.inc"

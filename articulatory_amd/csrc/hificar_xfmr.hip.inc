@@ -19,6 +19,8 @@ struct XfmrEncLayer {
     float* d_ln[4] = {nullptr, nullptr, nullptr, nullptr};  // norm1.weight, norm1.bias, norm2.weight, norm2.bias
 };
 
+struct XfmrTrain;  // hificar_xfmr_train.hip.inc
+
 struct hificar_xfmr {
     hificar_xfmr_config cfg;
     hificar_engine eng;
@@ -33,7 +35,11 @@ struct hificar_xfmr {
         size_t cap;
     };
     std::map<std::string, Tap> taps;
+    XfmrTrain* train = nullptr;  // built by the first training entry point
+    int train_failed = HIFICAR_OK;
 };
+
+static void xfmr_train_free(hificar_xfmr* g);
 
 static bool xfmr_head_dim_built(int d) { return d >= 16 && d <= 128 && d % 16 == 0; }
 
@@ -122,6 +128,7 @@ extern "C" int hificar_xfmr_create(const hificar_xfmr_config* cfg, hificar_xfmr*
 
 extern "C" void hificar_xfmr_destroy(hificar_xfmr* g) {
     if (!g) return;
+    xfmr_train_free(g);
     engine_close(&g->eng);
     delete g;
 }
@@ -269,7 +276,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
     h->use_pair = false;
     h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's result does not depend on what it is batched with
     HIP_TRY(hipDeviceSynchronize());
-    g->tensors.clear();
+    g->tensors.clear();  // (g->expected stays: the training entry points go by it)
     g->finalized = true;
     return HIFICAR_OK;
 }

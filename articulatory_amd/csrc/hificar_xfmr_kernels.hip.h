@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "hificar_conv.hip.h"
+#include "hificar_bigru_train_kernels.hip.h"
 
 namespace hificar {
 
@@ -41,6 +42,29 @@ struct XfmrAttnParams {
     float* out;          // [B T][F]: [head][d]
     int T, F;
     float scale;         // 1 / sqrt(d)
+    // the training instantiation only (hificar_xfmr_train_kernels.hip.h)
+    float* lse = nullptr;                   // [B][8][T]: m + log l of every query's softmax
+    const BigruTapeHeader* hdr = nullptr;   // seed, offset and p of the dropout on the probabilities
+    int site = 0;
+};
+
+// Dropout of the Transformer's training step: the BiGRU's generator (BigruDrop: splitmix64 of key + element, top 24 bits against p) with a
+// key that has room for the encoder's sites, key = mix(seed ^ mix(128 offset + site)); site 4 l + {0: attention probabilities, 1: dropout1,
+// 2: the feed-forward's hidden rows, 3: dropout2}.  Element: the row-major index in (B, T, C); site 0: ((b 8 + h) T + q) 199 + (k - q + 99).
+// The numpy restatement is articulatory_amd.utils.synth.xfmr_dropout_mask.
+struct XfmrDrop {
+    unsigned long long key;
+    float p, scale;
+    __device__ __forceinline__ XfmrDrop(const BigruTapeHeader* hdr, int site) {
+        p = hdr->p;
+        scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
+        key = bigru_mix64(hdr->seed ^ bigru_mix64(hdr->offset * 128ull + (unsigned long long)site));
+    }
+    __device__ __forceinline__ float operator()(unsigned long long e) const {
+        if (!(p > 0.f)) return 1.f;
+        const float u = (float)(unsigned)(bigru_mix64(key + e) >> 40) * (1.f / 16777216.f);
+        return u >= p ? scale : 0.f;
+    }
 };
 
 template <int D>
@@ -61,7 +85,9 @@ __device__ __forceinline__ void xfmr_stage(float* dst, const float* src, size_t 
     }
 }
 
-template <int D>
+// TRAIN (the training forward): the kept probabilities are scaled by the dropout factor before P V (the denominator sums all of them, as
+// F.softmax followed by nn.Dropout does) and L = m + log l is kept per query.  The eval instantiation compiles none of it.
+template <int D, bool TRAIN = false>
 __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) {
     extern __shared__ float xfmr_lds[];
     constexpr int PT = D + 4, NS = D / 4, NM = D / 16, PP = kXfmrPosPitch;
@@ -165,6 +191,15 @@ __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) 
         ls += __shfl_xor(ls, 32);
         l = l * alpha + ls;
         m = m_new;
+        if constexpr (TRAIN) {
+            const XfmrDrop drop(p.hdr, p.site);
+            const unsigned long long e0 = ((unsigned long long)(b * kXfmrHeads + h) * p.T + (qok ? q : 0)) * kXfmrTab;
+#pragma unroll
+            for (int sb = 0; sb < 4; ++sb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if ((valid >> (4 * sb + i)) & 1u) s[sb][i] *= drop(e0 + (unsigned long long)(kb + 16 * sb + 4 * g + i - q + (kXfmrRel - 1)));
+        }
 #pragma unroll
         for (int j = 0; j < NM; ++j) o[j] *= alpha;
 #pragma unroll
@@ -180,6 +215,9 @@ __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) 
     }
     if (!qok) return;
     const float inv = 1.f / l;  // (l >= 1: the query's own key is in its band)
+    if constexpr (TRAIN) {
+        if (g == 0) p.lse[((size_t)b * kXfmrHeads + h) * p.T + q] = m + logf(l);
+    }
     float* orow = p.out + (row0 + q) * p.F + h * D + 4 * g;
 #pragma unroll
     for (int j = 0; j < NM; ++j)

@@ -1,0 +1,821 @@
+// Training of the Transformer feature model (the reference's step: articulatory/bin/train.py:241-383 through models/transformer.py:55-77 in
+// train() mode): device-resident parameters, the training-mode forward with its tape, and the backward pass.
+//   forward   rows -> 3 x [conv1 -> batch statistics -> normalise + ReLU -> conv2 -> batch statistics -> normalise + residual + ReLU]
+//             -> w_raw_in -> elayers x [q|k|v GEMM -> attention (keeps L, dropout on P) -> w_o -> x + dropout -> LayerNorm -> linear1 (ReLU)
+//             -> dropout -> linear2 -> x + dropout -> LayerNorm] -> w_out
+//   backward  the same walked from the end: LayerNorm / dropout / ReLU masks elementwise, the attention's three kernels, BatchNorm's sums
+//             and input gradient; every GEMM's data gradient is a conv-engine launch on its transposed pack, every weight and bias
+//             gradient a launch of the weight-gradient kernels of hificar_train.hip.inc.
+// Equal-length batches only.  Kernels: hificar_xfmr_train_kernels.hip.h.
+
+struct XfmrTrainLayer {
+    ConvLayer dg_qkv, dg_wo, dg_l1, dg_l2;
+    int64_t off_fused = 0, off_wot = 0;  // the q | k | v weight (3 F, F) and w_o's (F, F) transpose in the master copy
+};
+
+struct XfmrTrain {
+    struct Slot {
+        std::string name;
+        std::vector<int64_t> shape;
+        int64_t offset, numel;
+    };
+    std::vector<Slot> slots;                // the trainable parameters in gradient-buffer order (reference names and layouts)
+    std::map<std::string, int64_t> offset;  // name -> floats into the master copy (the trainable ones: = into the gradient buffer)
+    int64_t grad_total = 0, master_total = 0;
+    float* d_master = nullptr;
+    float* d_wscr = nullptr;  // (3 F, F): a fused layer's weight gradient before it is unpacked
+    // the batch norms in registration order: the conv in front of each, unfolded (training) and folded (eval), and where the fold lives
+    struct Bn {
+        std::string conv, bn;
+        ConvLayer raw, dg;
+        ConvLayer* folded;
+        int64_t off_fw = 0, off_fb = 0;
+    };
+    std::vector<Bn> bns;  // sized once (launch plans are keyed by the layers' addresses)
+    int bn_c1[3], bn_c2[3], bn_rp = -1;
+    ConvLayer dg_win, dg_wout;
+    std::vector<XfmrTrainLayer> enc;
+    bool have_params = false;
+};
+
+static void xfmr_train_free(hificar_xfmr* g) {
+    delete g->train;  // (device memory: the engine's allocation list)
+    g->train = nullptr;
+}
+
+#define HIFICAR_XFMR_BY_D(fn, d, ...)                                                                                                     \
+    ((d) == 16 ? fn<16>(__VA_ARGS__) : (d) == 32 ? fn<32>(__VA_ARGS__) : (d) == 48 ? fn<48>(__VA_ARGS__) : (d) == 64 ? fn<64>(__VA_ARGS__) \
+     : (d) == 80 ? fn<80>(__VA_ARGS__) : (d) == 96 ? fn<96>(__VA_ARGS__) : (d) == 112 ? fn<112>(__VA_ARGS__) : fn<128>(__VA_ARGS__))
+
+template <int D>
+static hipError_t xfmr_train_attr() {
+    static_assert(XfmrAttnLds<D>::bytes <= 160 * 1024 && XfmrEmbLds<D>::bytes <= 160 * 1024, "the attention kernels' LDS");
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_attn_kernel<D, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)XfmrAttnLds<D>::bytes);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_attn_bwd_q_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XfmrAttnLds<D>::bytes);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_attn_bwd_k_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)XfmrAttnBwdKLds<D>::bytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_demb_partial_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)XfmrEmbLds<D>::bytes);
+}
+
+template <int D>
+static hipError_t xfmr_attn_train_launch(const XfmrAttnParams& p, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((xfmr_attn_kernel<D, true>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
+    return hipGetLastError();
+}
+
+template <int D>
+static hipError_t xfmr_attn_bwd_launch(const XfmrAttnBwdParams& p, dim3 grid, float* emb_partial, int M, int chunks, hipStream_t stream) {
+    hipLaunchKernelGGL((xfmr_attn_bwd_q_kernel<D>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
+    hipLaunchKernelGGL((xfmr_attn_bwd_k_kernel<D>), grid, dim3(256), XfmrAttnBwdKLds<D>::bytes, stream, p);
+    hipLaunchKernelGGL((xfmr_demb_partial_kernel<D>), dim3((unsigned)chunks, kXfmrHeads), dim3(256), XfmrEmbLds<D>::bytes, stream, p.qkv, p.ds, emb_partial, M,
+                       p.T, p.F);
+    return hipGetLastError();
+}
+
+static int xfmr_alloc(hificar_engine* h, size_t bytes, void** out) {
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    h->allocs.push_back(p);
+    HIP_TRY(hipMemset(p, 0, bytes));
+    *out = p;
+    return HIFICAR_OK;
+}
+
+static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts);
+
+static int xfmr_train_init(hificar_xfmr* g) {
+    if (g->train) return HIFICAR_OK;
+    if (!g->finalized) return fail(HIFICAR_E_STATE, "Transformer training entry points need hificar_xfmr_finalize first");
+    // a failed set-up (out of device memory, in practice) is final for this handle, as for the BiGRU
+    if (g->train_failed != HIFICAR_OK)
+        return fail(g->train_failed, "the Transformer training state could not be set up on this handle earlier; destroy it and make a new one");
+    std::unique_ptr<XfmrTrain> ts(new XfmrTrain());
+    const int rc = xfmr_train_build(g, ts.get());
+    if (rc != HIFICAR_OK) {
+        g->train_failed = rc;
+        return rc;
+    }
+    g->train = ts.release();
+    return HIFICAR_OK;
+}
+
+static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts) {
+    hificar_engine* h = &g->eng;
+    const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, E = g->cfg.elayers;
+    const bool has_rp = g->rp.cout != 0;
+    int64_t total = 0;
+    auto add = [&](const std::string& name, bool trainable) {
+        const std::vector<int64_t>& shape = g->expected.at(name);
+        int64_t n = 1;
+        for (auto v : shape) n *= v;
+        ts->offset[name] = total;
+        if (trainable) ts->slots.push_back({name, shape, total, n});
+        total += (n + 3) & ~(int64_t)3;
+    };
+    // state_dict order: a module's weight and bias lie back to back (the (d gamma | d beta) pairs are reduced as one row of 2 F)
+    for (int i = 0; i < 3; ++i) {
+        const std::string b = "conv_blocks." + std::to_string(i) + ".";
+        for (const char* m : {"conv1", "bn1", "conv2", "bn2"})
+            for (const char* t : {".weight", ".bias"}) add(b + m + t, true);
+        if (i == 0 && has_rp)
+            for (const char* m : {"residual_path", "res_norm"})
+                for (const char* t : {".weight", ".bias"}) add(b + m + t, true);
+    }
+    add("w_raw_in.weight", true);
+    add("w_raw_in.bias", true);
+    for (int l = 0; l < E; ++l) {
+        const std::string b = "transformer.layers." + std::to_string(l) + ".";
+        for (const char* w : {"w_q", "w_k", "w_v", "w_o"}) add(b + "self_attn." + w, true);
+        add(b + "self_attn.relative_positional.embeddings", true);
+        for (const char* m : {"linear1", "linear2", "norm1", "norm2"})
+            for (const char* t : {".weight", ".bias"}) add(b + m + t, true);
+    }
+    add("w_out.weight", true);
+    add("w_out.bias", true);
+    ts->grad_total = total;
+    // the batch norms, in registration order
+    ts->bns.resize(has_rp ? 7 : 6);
+    {
+        int j = 0;
+        for (int i = 0; i < 3; ++i) {
+            const std::string b = "conv_blocks." + std::to_string(i) + ".";
+            ts->bn_c1[i] = j;
+            ts->bns[(size_t)j].conv = b + "conv1";
+            ts->bns[(size_t)j].bn = b + "bn1";
+            ts->bns[(size_t)j++].folded = &g->c1[i];
+            ts->bn_c2[i] = j;
+            ts->bns[(size_t)j].conv = b + "conv2";
+            ts->bns[(size_t)j].bn = b + "bn2";
+            ts->bns[(size_t)j++].folded = &g->c2[i];
+            if (i == 0 && has_rp) {
+                ts->bn_rp = j;
+                ts->bns[(size_t)j].conv = b + "residual_path";
+                ts->bns[(size_t)j].bn = b + "res_norm";
+                ts->bns[(size_t)j++].folded = &g->rp;
+            }
+        }
+    }
+    for (auto& bn : ts->bns) {
+        add(bn.bn + ".running_mean", false);
+        add(bn.bn + ".running_var", false);
+    }
+    for (auto& bn : ts->bns) {
+        const ConvLayer& L = *bn.folded;
+        bn.off_fw = total;
+        total += (int64_t)L.cout * L.cin * L.K;
+        bn.off_fb = total;
+        total += L.cout;
+    }
+    ts->enc.resize((size_t)E);
+    for (auto& e : ts->enc) {
+        e.off_fused = total;
+        total += (int64_t)3 * F * F;
+        e.off_wot = total;
+        total += (int64_t)F * F;
+    }
+    ts->master_total = total;
+    int rc;
+    void* p = nullptr;
+    if ((rc = xfmr_alloc(h, (size_t)total * sizeof(float), &p)) != HIFICAR_OK) return rc;
+    ts->d_master = static_cast<float*>(p);
+    if ((rc = xfmr_alloc(h, (size_t)3 * F * F * sizeof(float), &p)) != HIFICAR_OK) return rc;
+    ts->d_wscr = static_cast<float*>(p);
+    for (auto& bn : ts->bns) {
+        const ConvLayer& L = *bn.folded;
+        if ((rc = xfmr_plan(bn.raw, bn.conv + "#raw", L.cin, L.cin_pad, L.cout, L.K)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_alloc(h, pack_w32_elems(bn.raw, bn.raw.chunk16) * sizeof(float), &p)) != HIFICAR_OK) return rc;
+        bn.raw.d_w32 = static_cast<float*>(p);
+        if ((rc = xfmr_alloc(h, (size_t)bn.raw.cout_total * sizeof(float), &p)) != HIFICAR_OK) return rc;
+        bn.raw.d_bias = static_cast<float*>(p);
+        if ((rc = make_dgrad_layer(h, bn.raw, bn.dg, nullptr)) != HIFICAR_OK) return rc;
+        if (bn.dg.cout_pad != L.cin_pad) return fail(HIFICAR_E_INVALID, "internal: data-gradient rows of %s are %d wide, its input rows %d", bn.conv.c_str(), bn.dg.cout_pad, L.cin_pad);
+    }
+    (void)C;
+    if ((rc = make_dgrad_layer(h, g->w_in, ts->dg_win, nullptr)) != HIFICAR_OK) return rc;
+    if ((rc = make_dgrad_layer(h, g->w_out, ts->dg_wout, nullptr)) != HIFICAR_OK) return rc;
+    for (int l = 0; l < E; ++l) {
+        const XfmrEncLayer& L = g->enc[(size_t)l];
+        XfmrTrainLayer& D = ts->enc[(size_t)l];
+        if ((rc = make_dgrad_layer(h, L.qkv, D.dg_qkv, nullptr)) != HIFICAR_OK) return rc;
+        if ((rc = make_dgrad_layer(h, L.wo, D.dg_wo, nullptr)) != HIFICAR_OK) return rc;
+        if ((rc = make_dgrad_layer(h, L.l1, D.dg_l1, nullptr)) != HIFICAR_OK) return rc;
+        if ((rc = make_dgrad_layer(h, L.l2, D.dg_l2, nullptr)) != HIFICAR_OK) return rc;
+    }
+    if ((rc = wgrad_setup()) != HIFICAR_OK) return rc;
+    HIP_TRY(xfmr_train_attr<16>());
+    HIP_TRY(xfmr_train_attr<32>());
+    HIP_TRY(xfmr_train_attr<48>());
+    HIP_TRY(xfmr_train_attr<64>());
+    HIP_TRY(xfmr_train_attr<80>());
+    HIP_TRY(xfmr_train_attr<96>());
+    HIP_TRY(xfmr_train_attr<112>());
+    HIP_TRY(xfmr_train_attr<128>());
+    return HIFICAR_OK;
+}
+
+extern "C" int hificar_xfmr_grad_count(hificar_xfmr* g) {
+    if (!g || xfmr_train_init(g) != HIFICAR_OK) return -1;
+    return (int)g->train->slots.size();
+}
+
+extern "C" int hificar_xfmr_grad_info(hificar_xfmr* g, int i, char* name96, int64_t* offset, int64_t* numel) {
+    if (!g || !name96 || !offset || !numel) return fail(HIFICAR_E_INVALID, "hificar_xfmr_grad_info: null argument");
+    int rc = xfmr_train_init(g);
+    if (rc != HIFICAR_OK) return rc;
+    if (i < 0 || i >= (int)g->train->slots.size()) return fail(HIFICAR_E_INVALID, "gradient index %d out of range", i);
+    const XfmrTrain::Slot& s = g->train->slots[(size_t)i];
+    snprintf(name96, 96, "%s", s.name.c_str());
+    *offset = s.offset;
+    *numel = s.numel;
+    return HIFICAR_OK;
+}
+
+extern "C" int64_t hificar_xfmr_grad_floats(hificar_xfmr* g) {
+    if (!g || xfmr_train_init(g) != HIFICAR_OK) return -1;
+    return g->train->grad_total;
+}
+
+// forward pack (+ bias, when the layer has one) of a layer, and its data-gradient pack, from a (cout, cin, K) weight on the device
+static int xfmr_pack_dev(const ConvLayer& L, const ConvLayer* D, const float* w, const float* b, hipStream_t stream) {
+    int rc;
+    PackParams pp;
+    fill_pack(pp, L, L.chunk16);
+    pp.src = w;
+    pp.dst = L.d_w32;
+    pp.mode = 0;
+    pp.cin = L.cin;
+    pp.cout = L.cout;
+    pp.K = L.K;
+    pp.cin_pack = L.cin;
+    pp.cout_pack = L.cout;
+    if ((rc = launch_pack(pp, stream)) != HIFICAR_OK) return rc;
+    if (b) {
+        PackParams pb = simple_pack(6, b, L.d_bias, (long long)L.n_phase * L.cout);
+        pb.cout = L.cout;
+        pb.cout_pad = L.cout_pad;
+        if ((rc = launch_pack(pb, stream)) != HIFICAR_OK) return rc;
+    }
+    if (D) {
+        fill_pack(pp, *D, D->chunk16);
+        pp.src = w;
+        pp.dst = D->d_w32;
+        pp.mode = 2;
+        pp.cin = L.cin;
+        pp.cout = L.cout;
+        pp.K = L.K;
+        pp.cin_pack = L.cout;
+        pp.cout_pack = L.cin;
+        if ((rc = launch_pack(pp, stream)) != HIFICAR_OK) return rc;
+    }
+    return HIFICAR_OK;
+}
+
+extern "C" int hificar_xfmr_set_parameters_device(hificar_xfmr* g, const char* const* names, const float* const* data, int n, void* stream_) {
+    if (!g || !names || !data) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_parameters_device: null argument");
+    int rc = xfmr_train_init(g);
+    if (rc != HIFICAR_OK) return rc;
+    XfmrTrain* ts = g->train;
+    hificar_engine* h = &g->eng;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    if (n != (int)g->expected.size()) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_parameters_device: %d tensors, the model has %zu", n, g->expected.size());
+    std::set<std::string> seen;
+    for (int i = 0; i < n; ++i) {
+        if (!names[i] || !data[i]) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_parameters_device: null entry %d", i);
+        auto it = g->expected.find(names[i]);
+        if (it == g->expected.end()) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", names[i]);
+        if (!seen.insert(names[i]).second) return fail(HIFICAR_E_INVALID, "tensor '%s' given twice", names[i]);
+    }
+    for (int i = 0; i < n; ++i) {
+        size_t numel = 1;
+        for (auto v : g->expected.at(names[i])) numel *= (size_t)v;
+        HIP_TRY(hipMemcpyAsync(ts->d_master + ts->offset.at(names[i]), data[i], numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+    const int F = g->cfg.hidden_dim, d = F / kXfmrHeads;
+    float* const m = ts->d_master;
+    auto at = [&](const std::string& name) { return m + ts->offset.at(name); };
+    for (auto& bn : ts->bns) {
+        const ConvLayer& L = *bn.folded;
+        if ((rc = xfmr_pack_dev(bn.raw, &bn.dg, at(bn.conv + ".weight"), at(bn.conv + ".bias"), stream)) != HIFICAR_OK) return rc;
+        hipLaunchKernelGGL(xfmr_fold_kernel, dim3((unsigned)L.cout), dim3(256), 0, stream, at(bn.conv + ".weight"), at(bn.conv + ".bias"), at(bn.bn + ".weight"),
+                           at(bn.bn + ".bias"), at(bn.bn + ".running_mean"), at(bn.bn + ".running_var"), m + bn.off_fw, m + bn.off_fb, L.cin * L.K);
+        HIP_TRY(hipGetLastError());
+        if ((rc = xfmr_pack_dev(L, nullptr, m + bn.off_fw, m + bn.off_fb, stream)) != HIFICAR_OK) return rc;
+    }
+    if ((rc = xfmr_pack_dev(g->w_in, &ts->dg_win, at("w_raw_in.weight"), at("w_raw_in.bias"), stream)) != HIFICAR_OK) return rc;
+    if ((rc = xfmr_pack_dev(g->w_out, &ts->dg_wout, at("w_out.weight"), at("w_out.bias"), stream)) != HIFICAR_OK) return rc;
+    for (int l = 0; l < g->cfg.elayers; ++l) {
+        const std::string b = "transformer.layers." + std::to_string(l) + ".";
+        XfmrEncLayer& L = g->enc[(size_t)l];
+        XfmrTrainLayer& D = ts->enc[(size_t)l];
+        hipLaunchKernelGGL(xfmr_qkv_weight_kernel, dim3(1024), dim3(256), 0, stream, at(b + "self_attn.w_q"), at(b + "self_attn.w_k"), at(b + "self_attn.w_v"),
+                           m + D.off_fused, F, d, 0);
+        hipLaunchKernelGGL(transpose_kernel, dim3(1024), dim3(256), 0, stream, at(b + "self_attn.w_o"), m + D.off_wot, F, F);
+        HIP_TRY(hipGetLastError());
+        if ((rc = xfmr_pack_dev(L.qkv, &D.dg_qkv, m + D.off_fused, nullptr, stream)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_dev(L.wo, &D.dg_wo, m + D.off_wot, nullptr, stream)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_dev(L.l1, &D.dg_l1, at(b + "linear1.weight"), at(b + "linear1.bias"), stream)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_dev(L.l2, &D.dg_l2, at(b + "linear2.weight"), at(b + "linear2.bias"), stream)) != HIFICAR_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(L.d_emb, at(b + "self_attn.relative_positional.embeddings"), (size_t)kXfmrHeads * kXfmrTab * d * sizeof(float),
+                               hipMemcpyDeviceToDevice, stream));
+        int i = 0;
+        for (const char* nm : {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"})
+            HIP_TRY(hipMemcpyAsync(L.d_ln[i++], at(b + nm), (size_t)F * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+    ts->have_params = true;
+    return HIFICAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// tape and workspace
+// ------------------------------------------------------------------------------------------------
+static size_t xfmr_train_rows(int B, int T) { return round_up_sz((size_t)B * (size_t)T + 64, 256); }  // slack behind the last row for whole GEMM tiles
+
+struct XfmrTapeLayer {
+    float *qkv, *o, *lse, *p1, *n1, *hid, *p2;
+};
+
+struct XfmrTape {
+    BigruTapeHeader* hdr;
+    float* xin;       // [rows][cin_pad]
+    float* y[7];      // per batch norm: its conv's raw output rows [rows][F]
+    float* stats[7];  // ... and mean | biased variance | rstd, [3][F]
+    float* a1[3];     // per ResBlock: relu(bn1(conv1))
+    float* bo[3];     // ... and its output
+    std::vector<float*> X;  // [elayers + 1]: the encoder layers' inputs, and the last one's output
+    std::vector<XfmrTapeLayer> L;
+    size_t bytes;
+};
+
+static XfmrTape xfmr_plan_tape(const hificar_xfmr* g, int B, int T, void* base) {
+    const size_t rows = xfmr_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;
+    const int nbn = g->rp.cout ? 7 : 6;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base ? static_cast<char*>(base) + off : nullptr;
+        off += round_up_sz(bytes, 256);
+        return reinterpret_cast<float*>(p);
+    };
+    XfmrTape t;
+    t.hdr = reinterpret_cast<BigruTapeHeader*>(take(256));
+    t.xin = take(rows * g->cin_pad * 4);
+    for (int j = 0; j < 7; ++j) {
+        t.y[j] = j < nbn ? take(rows * F * 4) : nullptr;
+        t.stats[j] = j < nbn ? take(3 * F * 4) : nullptr;
+    }
+    for (int i = 0; i < 3; ++i) {
+        t.a1[i] = take(rows * F * 4);
+        t.bo[i] = take(rows * F * 4);
+    }
+    const int E = g->cfg.elayers;
+    t.X.resize((size_t)E + 1);
+    t.L.resize((size_t)E);
+    for (int l = 0; l <= E; ++l) t.X[(size_t)l] = take(rows * F * 4);
+    for (int l = 0; l < E; ++l) {
+        XfmrTapeLayer& L = t.L[(size_t)l];
+        L.qkv = take(rows * 3 * F * 4);
+        L.o = take(rows * F * 4);
+        L.lse = take(rows * kXfmrHeads * 4);
+        L.p1 = take(rows * F * 4);
+        L.n1 = take(rows * F * 4);
+        L.hid = take(rows * kXfmrFF * 4);
+        L.p2 = take(rows * F * 4);
+    }
+    t.bytes = off;
+    return t;
+}
+
+struct XfmrTrainWs {
+    float* t1;       // [rows][F]: a sub-block's output before its dropout
+    float* res;      // [rows][F]: res_norm's rows
+    float* d[3];     // [rows][F]: gradient rows
+    float* wide;     // [rows][3072]: dropout(hidden rows); w_out's rows; dout as rows
+    float* gw;       // [rows][3072]: gradient of the hidden rows; dq | dk | dv
+    float* dxr[2];   // [rows][cin_pad]
+    float* ds;       // [B][8][T][200] banded dS
+    float* pd;       // ... and the dropped probabilities
+    float* rowstats; // [rows][2]
+    float* colpart;  // [chunks][2][F]
+    float* embpart;  // [chunks][8][199][d]
+    float* partial;  // weight-gradient partials
+    float* colsum;   // bias-gradient partials
+    char* light;     // a forward without a tape keeps its rows here
+    size_t partial_elems, colsum_elems;
+    size_t bytes;
+};
+
+static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void* base) {
+    const size_t rows = xfmr_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;
+    const int M = B * T;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base ? static_cast<char*>(base) + off : nullptr;
+        off += round_up_sz(bytes, 256);
+        return reinterpret_cast<float*>(p);
+    };
+    XfmrTrainWs w;
+    w.t1 = take(rows * F * 4);
+    w.res = take(rows * F * 4);
+    for (int i = 0; i < 3; ++i) w.d[i] = take(rows * F * 4);
+    w.wide = take(rows * kXfmrFF * 4);
+    w.gw = take(rows * kXfmrFF * 4);
+    for (int i = 0; i < 2; ++i) w.dxr[i] = take(rows * g->cin_pad * 4);
+    w.ds = take(rows * kXfmrHeads * kXfmrBand * 4);
+    w.pd = take(rows * kXfmrHeads * kXfmrBand * 4);
+    w.rowstats = take(rows * 2 * 4);
+    w.colpart = take((size_t)((M + kXfmrColRows - 1) / kXfmrColRows) * 2 * F * 4);
+    w.embpart = take((size_t)((M + kXfmrEmbRows - 1) / kXfmrEmbRows) * kXfmrTab * F * 4);
+    w.partial_elems = w.colsum_elems = 0;
+    if (g->train) {
+        const hificar_engine* h = &g->eng;
+        auto one = [&](const ConvLayer& L, int nseq, int r) {
+            w.partial_elems = std::max(w.partial_elems, wgrad_partial_elems(h, L, nseq, r));
+            w.colsum_elems = std::max(w.colsum_elems, wgrad_colsum_elems(h, L, nseq, r));
+        };
+        for (const auto& bn : g->train->bns) one(bn.raw, bn.raw.K > 1 ? B : 1, bn.raw.K > 1 ? T : M);
+        one(g->w_in, 1, M);
+        one(g->w_out, 1, M);
+        for (const auto& L : g->enc) {
+            one(L.qkv, 1, M);
+            one(L.wo, 1, M);
+            one(L.l1, 1, M);
+            one(L.l2, 1, M);
+        }
+    }
+    w.partial = take(w.partial_elems * 4);
+    w.colsum = take(w.colsum_elems * 4);
+    w.light = reinterpret_cast<char*>(take(xfmr_plan_tape(g, B, T, nullptr).bytes));
+    w.bytes = off;
+    return w;
+}
+
+extern "C" size_t hificar_xfmr_tape_bytes(const hificar_xfmr* g, int B, int T) {
+    if (!g || !g->finalized || B < 1 || T < 1) return 0;
+    return xfmr_plan_tape(g, B, T, nullptr).bytes;
+}
+
+extern "C" size_t hificar_xfmr_train_workspace_bytes(hificar_xfmr* g, int B, int T) {
+    if (!g || B < 1 || T < 1 || xfmr_train_init(g) != HIFICAR_OK) return 0;
+    return xfmr_plan_train_ws(g, B, T, nullptr).bytes;
+}
+
+static int xfmr_train_check(hificar_xfmr* g, const char* what, int B, int T, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
+                            bool tape_optional = false) {
+    if (!g) return fail(HIFICAR_E_INVALID, "%s: null handle", what);
+    int rc = xfmr_train_init(g);
+    if (rc != HIFICAR_OK) return rc;
+    if (!g->train->have_params) return fail(HIFICAR_E_STATE, "%s before hificar_xfmr_set_parameters_device", what);
+    if (B < 1 || T < 1 || B > 65535 || (long long)B * T > (1LL << 30) / 8 || (long long)B * T * kXfmrFF >= (1LL << 31))
+        return fail(HIFICAR_E_INVALID, "%s: B=%d, T=%d out of range (B T 3072 < 2^31)", what, B, T);
+    if ((long long)B * T < 2) return fail(HIFICAR_E_INVALID, "%s: batch statistics need more than one frame (B * T = 1)", what);
+    if ((!tape && !tape_optional) || reinterpret_cast<uintptr_t>(tape) % 256 || !workspace || reinterpret_cast<uintptr_t>(workspace) % 256)
+        return fail(HIFICAR_E_INVALID, "%s: tape and workspace must be 256-byte aligned device pointers", what);
+    const size_t tb = xfmr_plan_tape(g, B, T, nullptr).bytes, wb = xfmr_plan_train_ws(g, B, T, nullptr).bytes;
+    if (tape && tape_bytes < tb) return fail(HIFICAR_E_WORKSPACE, "%s: tape too small: %zu < %zu", what, tape_bytes, tb);
+    if (workspace_bytes < wb) return fail(HIFICAR_E_WORKSPACE, "%s: workspace too small: %zu < %zu", what, workspace_bytes, wb);
+    return HIFICAR_OK;
+}
+
+// The launches both passes are made of
+struct XfmrTrainCtx {
+    hificar_xfmr* g;
+    hificar_engine* h;
+    hipStream_t stream;
+    int B, T, M, F;
+    const BigruTapeHeader* hdr;
+    const XfmrTrainWs* ws;
+    BwdWs bw;
+
+    unsigned ew_grid(long long n) const { return (unsigned)std::min<long long>((n / 4 + 255) / 256, 4096); }
+    // one launch of one layer over B sequences of T rows (K = 3: the sequences' own ends) or, seq = false, over the B T rows as one
+    int conv(const ConvLayer& L, const float* xs, const float* res, float* y, float* ys, bool seq = true) const {
+        const ConvLayer* ls[1] = {&L};
+        ConvIO io[1];
+        io[0] = ConvIO();
+        io[0].xs = reinterpret_cast<const char*>(xs);
+        io[0].res = res;
+        io[0].y = y;
+        io[0].ys = reinterpret_cast<char*>(ys);
+        const Ragged rg;
+        return seq ? launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream) : launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream);
+    }
+    int wgrad(const ConvLayer& L, const float* gr, int gpitch, const float* a, int apitch, float* dW, float* db) const {
+        return L.K > 1 ? launch_wgrad(h, L, gr, gpitch, a, apitch, B, T, dW, bw, stream, db) : launch_wgrad(h, L, gr, gpitch, a, apitch, 1, M, dW, bw, stream, db);
+    }
+    int colsum(int mode, const float* x, const float* dy, const float* stats) const {
+        XfmrColParams p;
+        p.x = x;
+        p.dy = dy;
+        p.stats = stats;
+        p.rowstats = ws->rowstats;
+        p.partial = ws->colpart;
+        p.M = M;
+        p.F = F;
+        p.mode = mode;
+        hipLaunchKernelGGL(xfmr_colsum_kernel, dim3((unsigned)(F / 64), (unsigned)chunks()), dim3(256), 0, stream, p);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+    int chunks() const { return (M + kXfmrColRows - 1) / kXfmrColRows; }
+    // partial (d gamma | d beta) -> the gradient buffer (the two tensors lie back to back)
+    int pair_reduce(float* dgamma) const {
+        hipLaunchKernelGGL(bigru_colreduce_kernel, dim3((unsigned)((2 * F + 255) / 256)), dim3(256), 0, stream, ws->colpart, chunks(), 2 * F, dgamma);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+    int bn_stats(const float* y, float* stats, float* batch_stats) const {
+        ProfScope prof(h, stream, "xfmr_bn_stats_kernels", 0.0, 8.0 * M * F);
+        int rc;
+        if ((rc = colsum(0, y, nullptr, nullptr)) != HIFICAR_OK) return rc;
+        hipLaunchKernelGGL(xfmr_bn_mean_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, stream, ws->colpart, chunks(), F, M, stats);
+        if ((rc = colsum(1, y, nullptr, stats)) != HIFICAR_OK) return rc;
+        hipLaunchKernelGGL(xfmr_bn_var_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, stream, ws->colpart, chunks(), F, M, stats, batch_stats);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+    int bn_apply(const float* y, const float* stats, const float* gamma, const float* res, float* out, bool relu) const {
+        const long long n4 = (long long)M * F / 4;
+        ProfScope prof(h, stream, "xfmr_bn_apply_kernel", 0.0, 4.0 * M * F * (res ? 3 : 2));
+        hipLaunchKernelGGL(xfmr_bn_apply_kernel, dim3(ew_grid(4 * n4)), dim3(256), 0, stream, y, stats, gamma, gamma + F, res, out, n4, F, relu ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+    // dy -> dx (may be the same rows), d gamma | d beta into the gradient buffer at dgamma
+    int bn_bwd(const float* y, const float* dy, const float* stats, const float* gamma, float* dgamma, float* dx) const {
+        ProfScope prof(h, stream, "xfmr_bn_bwd_kernels", 0.0, 20.0 * M * F);
+        int rc;
+        if ((rc = colsum(2, y, dy, stats)) != HIFICAR_OK) return rc;
+        if ((rc = pair_reduce(dgamma)) != HIFICAR_OK) return rc;
+        const long long n = (long long)M * F;
+        hipLaunchKernelGGL(xfmr_bn_bwd_dx_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, y, dy, stats, gamma, dgamma, dgamma + F, dx, n, F, M);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+    int layer_norm(const float* src, const float* gamma, const float* beta, float* dst) const {
+        XfmrLnParams p;
+        p.x = src;
+        p.gamma = gamma;
+        p.beta = beta;
+        p.lengths = nullptr;
+        p.y = dst;
+        p.B = B;
+        p.T = T;
+        p.F = F;
+        ProfScope prof(h, stream, "xfmr_ln_kernel", 8.0 * M * F, 8.0 * M * F);
+        hipLaunchKernelGGL(xfmr_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, p);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+    int ln_bwd(const float* x, const float* dy, const float* gamma, float* dgamma, float* dx) const {
+        ProfScope prof(h, stream, "xfmr_ln_bwd_kernels", 16.0 * M * F, 20.0 * M * F);
+        int rc;
+        // (dx is never dy here: the column sums below still read dy; the first pass leaves the row statistics for them)
+        hipLaunchKernelGGL(xfmr_ln_bwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, dy, gamma, dx, ws->rowstats, (long long)M, F);
+        HIP_TRY(hipGetLastError());
+        if ((rc = colsum(3, x, dy, nullptr)) != HIFICAR_OK) return rc;
+        return pair_reduce(dgamma);
+    }
+    int add_drop(const float* x, const float* t, float* out, int site) const {
+        const long long n = (long long)M * F;
+        ProfScope prof(h, stream, "xfmr_add_drop_kernel", 0.0, 12.0 * n);
+        hipLaunchKernelGGL(xfmr_add_drop_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, x, t, out, n, hdr, site);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+    // out = (a > 0 ? d : 0) * dropout factor of `site` (a = null: no ReLU mask; site < 0: no dropout)
+    int gate(const float* a, const float* dsrc, float* out, long long n, int site) const {
+        ProfScope prof(h, stream, "xfmr_gate_kernel", 0.0, 4.0 * n * (a ? 3 : 2));
+        hipLaunchKernelGGL(xfmr_gate_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, a, dsrc, out, n, hdr, site);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+};
+
+#define XT(call)                                  \
+    do {                                          \
+        if ((rc = (call)) != HIFICAR_OK) return rc; \
+    } while (0)
+
+// Transformer.forward in train() mode; see include/hificar.h.  tape = NULL: the rows a tape would keep live in the workspace.
+// Test aid (hificar_xfmr_debug_tap): the ReLU outputs, as rows — "conv_blocks.<n>.relu1", "conv_blocks.<n>.relu2" (B, T, hidden_dim) and
+// "layers.<n>.hidden" (B, T, 3072, before its dropout): which side of each ReLU the device took.
+extern "C" int hificar_xfmr_forward_train(hificar_xfmr* g, const float* x, float* out, float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed,
+                                          uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hificar_xfmr_forward_train";
+    int rc = xfmr_train_check(g, what, B, T, tape, tape_bytes, workspace, workspace_bytes, true);
+    if (rc != HIFICAR_OK) return rc;
+    if (!x || !out || !bn_batch_stats) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HIFICAR_E_INVALID, "%s: dropout_p=%g outside [0, 1)", what, (double)dropout_p);
+    hificar_engine* h = &g->eng;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    XfmrTrain* ts = g->train;
+    const XfmrTrainWs ws = xfmr_plan_train_ws(g, B, T, workspace);
+    const XfmrTape tp = xfmr_plan_tape(g, B, T, tape ? tape : ws.light);
+    const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = B * T;
+    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, &ws, {}};
+    auto P = [&](const std::string& name) { return ts->d_master + ts->offset.at(name); };
+    hipLaunchKernelGGL(bigru_header_kernel, dim3(1), dim3(1), 0, stream, tp.hdr, (unsigned long long)seed, (unsigned long long)offset, dropout_p, B, T, M, 0);
+    HIP_TRY(hipGetLastError());
+    {
+        ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
+        hipLaunchKernelGGL(xfmr_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, tp.xin,
+                           (const int*)nullptr, C, g->cin_pad, T);
+        HIP_TRY(hipGetLastError());
+    }
+    const float* in = tp.xin;
+    for (int i = 0; i < 3; ++i) {
+        const int j1 = ts->bn_c1[i], j2 = ts->bn_c2[i];
+        XfmrTrain::Bn &b1 = ts->bns[(size_t)j1], &b2 = ts->bns[(size_t)j2];
+        XT(cx.conv(b1.raw, in, nullptr, tp.y[j1], nullptr));
+        XT(cx.bn_stats(tp.y[j1], tp.stats[j1], bn_batch_stats + (size_t)j1 * 2 * F));
+        XT(cx.bn_apply(tp.y[j1], tp.stats[j1], P(b1.bn + ".weight"), nullptr, tp.a1[i], true));
+        XT(xfmr_emit_tap(g, "conv_blocks." + std::to_string(i) + ".relu1", tp.a1[i], (size_t)M * F, stream));
+        XT(cx.conv(b2.raw, tp.a1[i], nullptr, tp.y[j2], nullptr));
+        XT(cx.bn_stats(tp.y[j2], tp.stats[j2], bn_batch_stats + (size_t)j2 * 2 * F));
+        const float* res = in;
+        if (i == 0 && ts->bn_rp >= 0) {
+            const int j3 = ts->bn_rp;
+            XfmrTrain::Bn& b3 = ts->bns[(size_t)j3];
+            XT(cx.conv(b3.raw, in, nullptr, tp.y[j3], nullptr));
+            XT(cx.bn_stats(tp.y[j3], tp.stats[j3], bn_batch_stats + (size_t)j3 * 2 * F));
+            XT(cx.bn_apply(tp.y[j3], tp.stats[j3], P(b3.bn + ".weight"), nullptr, ws.res, false));
+            res = ws.res;
+        }
+        XT(cx.bn_apply(tp.y[j2], tp.stats[j2], P(b2.bn + ".weight"), res, tp.bo[i], true));
+        XT(xfmr_emit_tap(g, "conv_blocks." + std::to_string(i) + ".relu2", tp.bo[i], (size_t)M * F, stream));
+        in = tp.bo[i];
+    }
+    XT(cx.conv(g->w_in, in, nullptr, tp.X[0], nullptr));
+    for (int l = 0; l < g->cfg.elayers; ++l) {
+        const XfmrEncLayer& E = g->enc[(size_t)l];
+        const XfmrTapeLayer& L = tp.L[(size_t)l];
+        const float* X = tp.X[(size_t)l];
+        XT(cx.conv(E.qkv, X, nullptr, L.qkv, nullptr));
+        {
+            XfmrAttnParams p;
+            p.qkv = L.qkv;
+            p.emb = E.d_emb;
+            p.lengths = nullptr;
+            p.out = L.o;
+            p.T = T;
+            p.F = F;
+            p.scale = (float)(1.0 / std::sqrt((double)d));
+            p.lse = L.lse;
+            p.hdr = tp.hdr;
+            p.site = 4 * l;
+            ProfScope prof(h, stream, "xfmr_attn_kernel<train>", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
+            const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B);
+            const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_train_launch, d, p, grid, stream);
+            if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn_kernel launch failed: %s", hipGetErrorString(e));
+        }
+        XT(cx.conv(E.wo, L.o, nullptr, ws.t1, nullptr));
+        XT(cx.add_drop(X, ws.t1, L.p1, 4 * l + 1));
+        XT(cx.layer_norm(L.p1, E.d_ln[0], E.d_ln[1], L.n1));
+        XT(cx.conv(E.l1, L.n1, nullptr, nullptr, L.hid));
+        XT(xfmr_emit_tap(g, "layers." + std::to_string(l) + ".hidden", L.hid, (size_t)M * kXfmrFF, stream));
+        XT(cx.gate(nullptr, L.hid, ws.wide, (long long)M * kXfmrFF, 4 * l + 2));
+        XT(cx.conv(E.l2, ws.wide, nullptr, ws.t1, nullptr));
+        XT(cx.add_drop(L.n1, ws.t1, L.p2, 4 * l + 3));
+        XT(cx.layer_norm(L.p2, E.d_ln[2], E.d_ln[3], tp.X[(size_t)l + 1]));
+    }
+    XT(cx.conv(g->w_out, tp.X[(size_t)g->cfg.elayers], nullptr, ws.wide, nullptr));
+    {
+        const int Op = g->w_out.cout_pad;
+        ProfScope prof(h, stream, "xfmr_out_kernel", 0.0, 4.0 * M * (O + Op));
+        hipLaunchKernelGGL(xfmr_out_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, ws.wide, out,
+                           (const int*)nullptr, O, Op, T);
+        HIP_TRY(hipGetLastError());
+    }
+    return HIFICAR_OK;
+}
+
+extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
+                                     void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hificar_xfmr_backward";
+    int rc = xfmr_train_check(g, what, B, T, const_cast<void*>(tape), tape_bytes, workspace, workspace_bytes);
+    if (rc != HIFICAR_OK) return rc;
+    if (!dout || !grads) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
+    hificar_engine* h = &g->eng;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    XfmrTrain* ts = g->train;
+    const XfmrTape tp = xfmr_plan_tape(g, B, T, const_cast<void*>(tape));
+    const XfmrTrainWs ws = xfmr_plan_train_ws(g, B, T, workspace);
+    const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = B * T, FF = kXfmrFF;
+    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, &ws, {}};
+    cx.bw.partial = ws.partial;
+    cx.bw.colsum = ws.colsum;
+    cx.bw.partial_elems = ws.partial_elems;
+    cx.bw.colsum_elems = ws.colsum_elems;
+    cx.bw.accumulate = false;
+    cx.bw.defer = nullptr;
+    auto P = [&](const std::string& name) { return ts->d_master + ts->offset.at(name); };
+    auto G = [&](const std::string& name) { return grads + ts->offset.at(name); };
+    const long long MF = (long long)M * F;
+    float *d0 = ws.d[0], *d1 = ws.d[1], *d2 = ws.d[2];
+    const int E = g->cfg.elayers, Op = g->w_out.cout_pad;
+    {   // dout (B, O, T) -> rows [B T][Op]
+        ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (O + Op));
+        hipLaunchKernelGGL(xfmr_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, dout, ws.wide,
+                           (const int*)nullptr, O, Op, T);
+        HIP_TRY(hipGetLastError());
+    }
+    XT(cx.wgrad(g->w_out, ws.wide, Op, tp.X[(size_t)E], F, G("w_out.weight"), G("w_out.bias")));
+    XT(cx.conv(ts->dg_wout, ws.wide, nullptr, d0, nullptr, false));
+    for (int l = E - 1; l >= 0; --l) {
+        const std::string b = "transformer.layers." + std::to_string(l) + ".";
+        const XfmrEncLayer& L = g->enc[(size_t)l];
+        const XfmrTrainLayer& D = ts->enc[(size_t)l];
+        const XfmrTapeLayer& K = tp.L[(size_t)l];
+        // norm2, the join n1 + dropout2(linear2(...))
+        XT(cx.ln_bwd(K.p2, d0, L.d_ln[2], G(b + "norm2.weight"), d1));                 // d1 = d p2 (= the residual's share of d n1)
+        XT(cx.gate(nullptr, d1, d2, MF, 4 * l + 3));                                   // d2 = d linear2's output
+        XT(cx.gate(nullptr, K.hid, ws.wide, (long long)M * FF, 4 * l + 2));            // linear2's input, as the forward made it
+        XT(cx.wgrad(L.l2, d2, F, ws.wide, FF, G(b + "linear2.weight"), G(b + "linear2.bias")));
+        XT(cx.conv(D.dg_l2, d2, nullptr, ws.gw, nullptr, false));
+        XT(cx.gate(K.hid, ws.gw, ws.gw, (long long)M * FF, 4 * l + 2));                // through the dropout and the ReLU
+        XT(cx.wgrad(L.l1, ws.gw, FF, K.n1, F, G(b + "linear1.weight"), G(b + "linear1.bias")));
+        XT(cx.conv(D.dg_l1, ws.gw, d1, d2, nullptr, false));                           // d2 = d n1
+        // norm1, the join x + dropout1(w_o(attention))
+        XT(cx.ln_bwd(K.p1, d2, L.d_ln[0], G(b + "norm1.weight"), d1));                 // d1 = d p1 (= the residual's share of d x)
+        XT(cx.gate(nullptr, d1, d2, MF, 4 * l + 1));                                   // d2 = d w_o's output
+        XT(cx.wgrad(L.wo, d2, F, K.o, F, ts->d_wscr, nullptr));
+        hipLaunchKernelGGL(transpose_kernel, dim3(1024), dim3(256), 0, stream, ts->d_wscr, G(b + "self_attn.w_o"), F, F);
+        HIP_TRY(hipGetLastError());
+        XT(cx.conv(D.dg_wo, d2, nullptr, d0, nullptr, false));                         // d0 = d O
+        {
+            XfmrAttnBwdParams p;
+            p.qkv = K.qkv;
+            p.emb = L.d_emb;
+            p.o = K.o;
+            p.dout = d0;
+            p.lse = K.lse;
+            p.dqkv = ws.gw;
+            p.ds = ws.ds;
+            p.pd = ws.pd;
+            p.hdr = tp.hdr;
+            p.site = 4 * l;
+            p.T = T;
+            p.F = F;
+            p.scale = (float)(1.0 / std::sqrt((double)d));
+            const int chunks = (M + kXfmrEmbRows - 1) / kXfmrEmbRows;
+            // S, dP, dQ (K and E parts), dK, dV, dE: six banded products of 2 M F 199 flops each
+            ProfScope prof(h, stream, "xfmr_attn_bwd_kernels", 2.0 * M * F * 7 * kXfmrTab, 4.0 * M * (8.0 * F + 4.0 * kXfmrHeads * kXfmrBand));
+            const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B);
+            const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_bwd_launch, d, p, grid, ws.embpart, M, chunks, stream);
+            if (e != hipSuccess) return fail(HIFICAR_E_HIP, "attention backward launch failed: %s", hipGetErrorString(e));
+            const int width = kXfmrHeads * kXfmrTab * d;
+            hipLaunchKernelGGL(bigru_colreduce_kernel, dim3((unsigned)((width + 255) / 256)), dim3(256), 0, stream, ws.embpart, chunks, width,
+                               G(b + "self_attn.relative_positional.embeddings"));
+            HIP_TRY(hipGetLastError());
+        }
+        XT(cx.wgrad(L.qkv, ws.gw, 3 * F, tp.X[(size_t)l], F, ts->d_wscr, nullptr));
+        hipLaunchKernelGGL(xfmr_qkv_weight_kernel, dim3(1024), dim3(256), 0, stream, G(b + "self_attn.w_q"), G(b + "self_attn.w_k"), G(b + "self_attn.w_v"),
+                           ts->d_wscr, F, d, 1);
+        HIP_TRY(hipGetLastError());
+        XT(cx.conv(D.dg_qkv, ws.gw, d1, d0, nullptr, false));                          // d0 = d x: the layer below's output gradient
+    }
+    XT(cx.wgrad(g->w_in, d0, F, tp.bo[2], F, G("w_raw_in.weight"), G("w_raw_in.bias")));
+    XT(cx.conv(ts->dg_win, d0, nullptr, d1, nullptr, false));                          // d1 = d (the last ResBlock's output)
+    for (int i = 2; i >= 0; --i) {
+        const int j1 = ts->bn_c1[i], j2 = ts->bn_c2[i];
+        XfmrTrain::Bn &b1 = ts->bns[(size_t)j1], &b2 = ts->bns[(size_t)j2];
+        const float* in = i ? tp.bo[i - 1] : tp.xin;
+        const int in_pitch = i ? F : g->cin_pad;
+        XT(cx.gate(tp.bo[i], d1, d1, MF, -1));                                          // d1 = dz: through the block's last ReLU
+        XT(cx.bn_bwd(tp.y[j2], d1, tp.stats[j2], P(b2.bn + ".weight"), G(b2.bn + ".weight"), d2));
+        XT(cx.wgrad(b2.raw, d2, F, tp.a1[i], F, G(b2.conv + ".weight"), G(b2.conv + ".bias")));
+        XT(cx.conv(b2.dg, d2, nullptr, d0, nullptr));
+        XT(cx.gate(tp.a1[i], d0, d0, MF, -1));
+        XT(cx.bn_bwd(tp.y[j1], d0, tp.stats[j1], P(b1.bn + ".weight"), G(b1.bn + ".weight"), d0));
+        XT(cx.wgrad(b1.raw, d0, F, in, in_pitch, G(b1.conv + ".weight"), G(b1.conv + ".bias")));
+        if (i > 0) {
+            XT(cx.conv(b1.dg, d0, d1, d2, nullptr));                                    // + the identity residual's dz
+            std::swap(d1, d2);
+            continue;
+        }
+        const float* dres = d1;  // the residual path's share of d (input rows): dz itself without a residual_path (then cin_pad = F)
+        if (ts->bn_rp >= 0) {
+            XfmrTrain::Bn& b3 = ts->bns[(size_t)ts->bn_rp];
+            XT(cx.bn_bwd(tp.y[ts->bn_rp], d1, tp.stats[ts->bn_rp], P(b3.bn + ".weight"), G(b3.bn + ".weight"), d2));
+            XT(cx.wgrad(b3.raw, d2, F, tp.xin, g->cin_pad, G(b3.conv + ".weight"), G(b3.conv + ".bias")));
+            if (dx) XT(cx.conv(b3.dg, d2, nullptr, ws.dxr[0], nullptr));
+            dres = ws.dxr[0];
+        }
+        if (dx) {
+            XT(cx.conv(b1.dg, d0, dres, ws.dxr[1], nullptr));
+            ProfScope prof(h, stream, "bigru_unrows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
+            hipLaunchKernelGGL(bigru_unrows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, ws.dxr[1], dx,
+                               C, g->cin_pad, T);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return HIFICAR_OK;
+}
+#undef XT

@@ -1,15 +1,26 @@
 """``Transformer`` — the feature-to-feature encoder (EMA -> mel and the like) behind the reference's ``generator_type`` plugin surface.
 
-Drop-in for ``articulatory.models.Transformer`` (reference articulatory/models/transformer.py:21-105) in eval mode: same class name,
+Drop-in for ``articulatory.models.Transformer`` (reference articulatory/models/transformer.py:21-105): same class name,
 constructor keywords and defaults, the same state_dict keys, shapes and order — ``conv_blocks.N.{conv1,bn1,conv2,bn2,residual_path,res_norm}.*``
 (the batch norms' buffers included), ``w_raw_in.*``, ``transformer.layers.N.self_attn.{w_q,w_k,w_v,w_o}``,
 ``...self_attn.relative_positional.embeddings``, ``linear1/2``, ``norm1/2``, ``w_out.*`` — and the same ``forward`` / ``inference`` /
 ``register_stats`` / ``remove_weight_norm``.  The modules below only HOLD parameters; the arithmetic runs in ``libhificar.so``
 (``hificar_xfmr_*`` of include/hificar.h): no PyTorch-operator implementation, no CPU fallback.
 
-Not built, refused with ``NotImplementedError``: training (``forward`` in train() mode), ``extra_art=True`` and ``num_ph`` (phoneme input).
-``dropout`` and the ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size`` keywords are accepted and unused, as in the reference.
-``lengths=`` is this package's addition: a ragged batch in which every utterance's result is that of running it alone.
+In ``train()`` mode the forward is the reference's training-mode forward — the ResBlocks' ``BatchNorm1d`` on batch statistics with the
+running-statistics update, ``Dropout(p)`` on the attention probabilities, behind both sub-blocks of every encoder layer and on the
+feed-forward's hidden rows — under autograd: ``_TransformerFunction`` keeps a tape in ``hificar_xfmr_forward_train`` and routes
+``hificar_xfmr_backward``'s gradients to every parameter (and to the input when it requires grad).  Dropout masks come from the package's
+own counter-based generator (``set_dropout_seed``; numpy restatement: ``utils.synth.xfmr_dropout_mask``).
+
+One deliberate difference: the reference pads its relative-position tables under ``torch.no_grad()`` (pytorch_layers.py:331-344), which cuts
+them out of the graph — ``embeddings.grad`` stays None there and its optimizer never moves them from their initial values.  This package
+computes the table's gradient (``train_relative_positions = True``, the default); set the attribute to False to train exactly what the
+reference trains (the tables then get no gradient).
+
+Not built, refused with ``NotImplementedError``: ``extra_art=True``, ``num_ph`` (phoneme input) and ``lengths=`` in train() mode (ragged
+training).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size`` keywords are accepted and unused, as in the reference.
+``lengths=`` in eval mode is this package's addition: a ragged batch in which every utterance's result is that of running it alone.
 """
 
 import ctypes
@@ -89,9 +100,67 @@ class _EncoderParams(torch.nn.Module):
         self.layers = torch.nn.ModuleList(layers)
 
 
+def _grad_layout(module):
+    """[(state_dict key, offset, numel)] of the native gradient buffer (hificar_xfmr_grad_info), cached per handle."""
+    cached = module.__dict__.get("_grad_info")
+    if cached is not None and cached[0] == id(module._handle):
+        return cached[1]
+    lib, handle = module._lib, module._handle
+    out = []
+    name = ctypes.create_string_buffer(96)
+    off, num = ctypes.c_int64(), ctypes.c_int64()
+    for i in range(lib.hificar_xfmr_grad_count(handle)):
+        _native.check(lib.hificar_xfmr_grad_info(handle, i, name, ctypes.byref(off), ctypes.byref(num)), "hificar_xfmr_grad_info")
+        out.append((name.value.decode(), off.value, num.value))
+    module.__dict__["_grad_info"] = (id(module._handle), out)
+    return out
+
+
+class _TransformerFunction(torch.autograd.Function):
+    """Autograd node of the native Transformer in train() mode: forward = hificar_xfmr_forward_train (keeps a tape), backward =
+    hificar_xfmr_backward.  Inputs after (module, x, p, seed, offset, names) are the module's parameters in ``names`` order.  Returns
+    (out, batch statistics (number of batch norms, 2, hidden_dim): mean | biased variance); the statistics carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, module, x, p, seed, offset, names, *params):
+        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True)
+        B, _, T = x.shape
+        ctx.module, ctx.names, ctx.tape, ctx.toff, ctx.BT = module, names, tape, toff, (B, T)
+        ctx.save_for_backward(*params)  # torch's own version check covers an in-place edit that bumps Parameter._version ...
+        ctx.steps_seen = module._steps_seen  # ... and this one a fused optimizer step, which does not
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, dout, _dstats=None):
+        module = ctx.module
+        lib, handle = module._lib, module._handle
+        B, T = ctx.BT
+        params = ctx.saved_tensors
+        if handle is None or ctx.steps_seen != module._steps_seen:
+            raise RuntimeError("a Transformer parameter was modified between forward and backward (the backward pass reads the weights the "
+                               "forward used)")
+        dev = ctx.tape.device
+        dout = dout.to(torch.float32).contiguous()
+        dx = torch.empty((B, module._params["in_channels"], T), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            grads = torch.empty(int(lib.hificar_xfmr_grad_floats(handle)), dtype=torch.float32, device=dev)
+            ws_ptr, ws_bytes = module._train_workspace(B, T)
+            rc = lib.hificar_xfmr_backward(handle, dout.data_ptr(), B, T, ctx.tape.data_ptr() + ctx.toff, ctx.tape.numel() - ctx.toff,
+                                           grads.data_ptr(), dx.data_ptr() if dx is not None else None, ws_ptr, ws_bytes, stream)
+        _native.check(rc, "hificar_xfmr_backward")
+        views = {name: grads[off:off + num] for name, off, num in _grad_layout(module)}
+        skip = () if module.train_relative_positions else ("relative_positional.embeddings",)
+        gw = tuple(views[n].view(t.shape) if need and not n.endswith(skip or ("\0",)) else None
+                   for n, t, need in zip(ctx.names, params, ctx.needs_input_grad[6:]))
+        ctx.tape = None
+        return (None, dx, None, None, None, None, *gw)
+
+
 class Transformer(torch.nn.Module):
     """Three ResBlocks -> Linear -> ``elayers`` post-LayerNorm encoder layers (8 heads, learned relative positions, 3072-wide feed-forward)
-    -> Linear; MI355X-native, eval mode."""
+    -> Linear; MI355X-native, eval and train()."""
 
     def __init__(self, in_channels=8, out_channels=80, elayers=6, hidden_dim=768, dropout=.2, extra_art=False,
                  use_ar=False, ar_input=512, ar_hidden=256, ar_output=128, use_tanh=False,
@@ -116,6 +185,39 @@ class Transformer(torch.nn.Module):
         self._lib = None
         self._workspace_buf = None
         self._sig = None
+        self._train_ws_buf = None
+        self._on_device = False  # the handle's weights are refreshed from device tensors (set once a training forward ran on it)
+        self._dirty = False      # an optimizer stepped since the last hand-over (fused optimizers do not bump Parameter._version)
+        self._steps_seen = 0     # optimizer steps noticed so far
+        self._calls = 0          # training forwards so far: the dropout generator's offset
+        self._last_stats = None
+        self.train_relative_positions = True  # False: the tables get no gradient, as in the reference (see the module's docstring)
+        # drawn from torch's generator (after the parameters): torch.manual_seed makes a training run repeatable
+        self._dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        from ..utils.optim_hook import watch
+
+        watch(self)  # fused optimizers do not bump Parameter._version: every optimizer.step() over these parameters marks them stale
+
+    # ------------------------------------------------------------------ training surface
+    def set_dropout_seed(self, seed, offset=0):
+        """Seed of the dropout masks; the count of training forwards (the generator's offset) restarts at ``offset``."""
+        self._dropout_seed = int(seed) & (2 ** 64 - 1)
+        self._calls = int(offset)
+
+    def invalidate_parameters(self):
+        """The parameters changed in place without their version counters showing it (what ``utils.optim_hook`` calls after every
+        ``optimizer.step()``): the next forward hands them to the native handle again."""
+        self._dirty = True
+        self._steps_seen += 1
+
+    def _batch_norms(self):
+        """The BatchNorm1d holders in registration order: the order of hificar_xfmr_forward_train's bn_batch_stats."""
+        out = []
+        for blk in self.conv_blocks:
+            out += [blk.bn1, blk.bn2]
+            if hasattr(blk, "res_norm"):
+                out.append(blk.res_norm)
+        return out
 
     # ------------------------------------------------------------------ reference surface
     def remove_weight_norm(self):
@@ -174,7 +276,10 @@ class Transformer(torch.nn.Module):
             self._lib.hificar_xfmr_destroy(h)
         self._handle = None
         self._workspace_buf = None
+        self._train_ws_buf = None
         self._sig = None
+        self._on_device = False
+        self._dirty = False
 
     def __del__(self):
         try:
@@ -184,9 +289,17 @@ class Transformer(torch.nn.Module):
 
     def __getstate__(self):  # copies and pickles never share a native handle
         state = self.__dict__.copy()
-        for k in ("_handle", "_lib", "_workspace_buf", "_sig"):
+        for k in ("_handle", "_lib", "_workspace_buf", "_sig", "_train_ws_buf", "_last_stats"):
             state[k] = None
+        state["_on_device"] = state["_dirty"] = False
+        state.pop("_grad_info", None)
         return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        from ..utils.optim_hook import watch
+
+        watch(self)  # a copy trains with its own optimizer
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         out = super().load_state_dict(state_dict, strict=strict, **kw)
@@ -202,8 +315,35 @@ class Transformer(torch.nn.Module):
         """Re-upload the weights after an in-place parameter edit that the version counters do not show (``p.data.copy_``)."""
         self._invalidate()
 
-    def _native_handle(self):
-        if self._handle is not None and self._sig == self._signature():
+    def _send_parameters(self):
+        """Every float tensor of the state_dict from device memory into the handle (hificar_xfmr_set_parameters_device): nothing goes
+        through the host.  The tensors are read on the current stream, in stream order with the optimizer step that wrote them."""
+        names, held = [], []
+        for k, v in self.state_dict(keep_vars=True).items():
+            if k in ("mean", "scale") or k.endswith("num_batches_tracked"):
+                continue
+            names.append(k)
+            held.append(v if (v.dtype == torch.float32 and v.is_contiguous()) else v.detach().to(torch.float32).contiguous())
+        arr = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
+        ptrs = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
+        with torch.cuda.device(self._device()):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _native.check(self._lib.hificar_xfmr_set_parameters_device(self._handle, arr, ptrs, len(held), stream),
+                          "hificar_xfmr_set_parameters_device")
+        self._on_device = True
+        self._dirty = False
+        self._sig = self._signature()
+
+    def _native_handle(self, train=False):
+        if self._handle is not None and self._on_device:
+            # a handle that has trained: its weights follow the parameters on the device (eval after training sees the updated weights and
+            # running statistics without a trip through the host)
+            if self._dirty or self._sig != self._signature():
+                self._send_parameters()
+            return self._handle
+        if self._handle is not None and self._sig == self._signature() and not self._dirty:
+            if train:
+                self._send_parameters()
             return self._handle
         self._invalidate()
         dev = self._device()
@@ -227,7 +367,39 @@ class Transformer(torch.nn.Module):
                 raise
         self._handle = handle
         self._sig = self._signature()
+        if train:
+            self._send_parameters()
         return handle
+
+    def _train_workspace(self, B, T):
+        """One grow-only scratch buffer shared by the training forward and the backward pass (hificar_xfmr_train_workspace_bytes)."""
+        n = self._lib.hificar_xfmr_train_workspace_bytes(self._handle, B, T) + 256
+        ws = self._train_ws_buf
+        if ws is None or ws.numel() < n:
+            ws = torch.empty(int(n * 1.25) if ws is not None else n, dtype=torch.uint8, device=self._device())
+            self._train_ws_buf = ws
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
+    def _run_forward_train(self, x, p, seed, offset, keep_tape):
+        """hificar_xfmr_forward_train on the current stream: (out, batch statistics, tape or None, the tape's alignment offset)."""
+        lib, handle = self._lib, self._handle
+        B, _, T = x.shape
+        dev = x.device
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            tape, toff = None, 0
+            if keep_tape:
+                tape = torch.empty(lib.hificar_xfmr_tape_bytes(handle, B, T) + 256, dtype=torch.uint8, device=dev)
+                toff = (-tape.data_ptr()) % 256
+            out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=dev)
+            stats = torch.empty((len(self._batch_norms()), 2, self._params["hidden_dim"]), dtype=torch.float32, device=dev)
+            ws_ptr, ws_bytes = self._train_workspace(B, T)
+            rc = lib.hificar_xfmr_forward_train(handle, x.data_ptr(), out.data_ptr(), stats.data_ptr(), B, T, float(p), seed, offset,
+                                                tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
+                                                ws_ptr, ws_bytes, stream)
+        _native.check(rc, "hificar_xfmr_forward_train")
+        return out, stats, tape, toff
 
     def _workspace(self, B, T):
         """One grow-only scratch buffer per model (hificar_xfmr_workspace_bytes)."""
@@ -247,7 +419,8 @@ class Transformer(torch.nn.Module):
 
     def debug_tap(self, name, dst=None):
         """Test aid (hificar_xfmr_debug_tap): the following forwards copy intermediate ``name`` — "conv_blocks", "w_raw_in", "layers.N.norm1",
-        "layers.N" — as rows (B, T, hidden_dim) into the float32 CUDA tensor ``dst``; ``dst=None`` forgets it, ``name=None`` all of them."""
+        "layers.N" — as rows (B, T, hidden_dim) into the float32 CUDA tensor ``dst``; ``dst=None`` forgets it, ``name=None`` all of them.  A
+        train()-mode forward serves its ReLU outputs: "conv_blocks.N.relu1", "conv_blocks.N.relu2" and "layers.N.hidden" (B, T, 3072)."""
         handle = self._native_handle()
         _native.check(self._lib.hificar_xfmr_debug_tap(handle, name.encode() if name is not None else None, dst.data_ptr() if dst is not None else None,
                                                        dst.numel() if dst is not None else 0), "hificar_xfmr_debug_tap")
@@ -259,8 +432,7 @@ class Transformer(torch.nn.Module):
         lengths[b] frames (the convs see zero padding at its own end, its keys stop at its length), out[b, :, lengths[b]:] is zero, and
         what x holds past a length is never read."""
         if self.training:
-            raise NotImplementedError("Transformer.forward in train() mode is not built (no backward pass, dropout or batch statistics): "
-                                      "call .eval() for inference")
+            return self._forward_train(x, lengths)
         if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
             raise RuntimeError("Transformer.forward needs a CUDA/HIP tensor; there is no CPU fallback")
         if x.dim() != 3 or x.shape[1] != self._params["in_channels"]:
@@ -284,6 +456,46 @@ class Transformer(torch.nn.Module):
             rc = self._lib.hificar_xfmr_forward(handle, c.data_ptr(), lens[0], lens[1], out.data_ptr(), B, T, ws_ptr, ws_bytes,
                                                 ctypes.c_void_p(stream))
         _native.check(rc, "hificar_xfmr_forward")
+        return out
+
+    def _forward_train(self, x, lengths):
+        """train() mode (transformer.py:55-77 with every nn.Dropout active and the batch norms on batch statistics): with grad enabled the
+        output is part of the autograd graph; without, the same arithmetic runs and its tape is dropped.  Every call — either way —
+        advances the dropout generator's offset and updates every batch norm's running_mean / running_var / num_batches_tracked as
+        torch.nn.BatchNorm1d does."""
+        if lengths is not None:
+            raise NotImplementedError("Transformer.forward(lengths=...) in train() mode: ragged training is not built (equal-length "
+                                      "batches only, as the reference's collater makes them; call .eval() for ragged inference)")
+        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+            raise NotImplementedError("Transformer.forward in train() mode needs a CUDA/HIP tensor: the training path exists on the device "
+                                      "only, as HIP kernels (there is no CPU fallback)")
+        if x.dim() != 3 or x.shape[1] != self._params["in_channels"]:
+            raise RuntimeError(f"Transformer.forward: expected (B, {self._params['in_channels']}, T), got {tuple(x.shape)}")
+        B, _, T = x.shape
+        if B < 1 or T < 1:
+            raise RuntimeError(f"Transformer.forward: empty input {tuple(x.shape)}")
+        n = B * T
+        if n < 2:  # torch.nn.functional.batch_norm's own refusal
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, self._params['hidden_dim'], T]}")
+        self._native_handle(train=True)
+        if x.device != self._device():
+            raise RuntimeError(f"Transformer.forward: input on {x.device}, parameters on {self._device()}")
+        c = x.to(torch.float32).contiguous()
+        named = list(self.named_parameters())
+        names, params = tuple(k for k, _ in named), [p for _, p in named]
+        offset = self._calls
+        self._calls += 1
+        if torch.is_grad_enabled() and (c.requires_grad or any(p.requires_grad for p in params)):
+            out, stats = _TransformerFunction.apply(self, c, self._params["dropout"], self._dropout_seed, offset, names, *params)
+        else:  # no graph: the same arithmetic without a tape (tape = NULL)
+            out, stats, _, _ = self._run_forward_train(c.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False)
+        self._last_stats = stats.detach()  # (number of batch norms, 2, hidden_dim): this batch's mean | biased variance, for inspection
+        with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance
+            for j, bn in enumerate(self._batch_norms()):
+                bn.running_mean.mul_(0.9).add_(stats[j, 0], alpha=0.1)
+                bn.running_var.mul_(0.9).add_(stats[j, 1], alpha=0.1 * n / (n - 1))
+                bn.num_batches_tracked += 1
+        # (the running statistics only enter the eval path: its folds are refreshed when an eval forward next asks for the handle)
         return out
 
     @staticmethod

@@ -517,6 +517,49 @@ def bigru_dropout_mask(seed: int, offset: int, site, shape, p: float) -> np.ndar
 # ------------------------------------------------------------------------------------------------
 # Transformer, the feature-to-feature encoder (reference articulatory/models/transformer.py:21-105)
 # ------------------------------------------------------------------------------------------------
+XFMR_DROPOUT_SITES = {"attn": 0, "dropout1": 1, "dropout": 2, "dropout2": 3}  # per encoder layer l: site 4 l + these
+
+
+def xfmr_dropout_mask(seed: int, offset: int, site: int, shape_or_band, p: float) -> np.ndarray:
+    """The dropout factors (0, or 1 / (1 - p) in float32) of the Transformer's training forward number ``offset`` at ``site`` = 4 l + {0: the
+    attention probabilities, 1: dropout1, 2: the feed-forward's hidden rows, 3: dropout2} of encoder layer l (csrc/hificar_xfmr_kernels.hip.h:
+    XfmrDrop): the BiGRU generator's draw, u = the top 24 bits of splitmix64(key + e) / 2^24 kept when u >= p, with
+    key = splitmix64(seed ^ splitmix64(128 offset + site)).
+
+    Sites 1-3: ``shape_or_band`` is the (B, T, C) shape and e the row-major index.  Site 0: ``shape_or_band`` is (B, T) and the result is the
+    dense (B, 8, T, T) mask whose entry (b, h, q, k) with |k - q| <= 99 is element e = ((b 8 + h) T + q) 199 + (k - q + 99); entries outside the
+    band are 1 (no such probability exists).  ``p = 0`` gives all ones and draws nothing."""
+    site = int(site)
+    band = site % 4 == 0
+    if band:
+        B, T = (int(v) for v in shape_or_band)
+        shape = (B, 8, T, T)
+    else:
+        shape = tuple(int(v) for v in shape_or_band)
+    p32 = np.float32(p)
+    if not p32 > 0:
+        return np.ones(shape, dtype=np.float32)
+    inner = _splitmix64(np.array([(128 * int(offset) + site) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))
+    key = _splitmix64(np.array([int(seed) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64) ^ inner)
+    if band:
+        q = np.arange(T, dtype=np.int64)[:, None]
+        k = np.arange(T, dtype=np.int64)[None, :]
+        rel = k - q + 99
+        inband = (rel >= 0) & (rel < 199)
+        row = (np.arange(B * 8, dtype=np.int64).reshape(B, 8, 1, 1) * T + q[None, None]) * 199
+        e = (row + np.where(inband, rel, 0)[None, None]).astype(np.uint64)
+    else:
+        e = np.arange(int(np.prod(shape)), dtype=np.uint64).reshape(shape)
+    with np.errstate(over="ignore"):
+        bits = _splitmix64((e + key) & _MASK)
+    u = (bits >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    scale = np.float32(1.0) / (np.float32(1.0) - p32)
+    out = np.where(u >= p32, scale, np.float32(0.0)).astype(np.float32)
+    if band:
+        out = np.where(inband[None, None], out, np.float32(1.0)).astype(np.float32)
+    return out
+
+
 def transformer_param_spec(in_channels=8, out_channels=80, elayers=6, hidden_dim=768, **_ignored):
     """Ordered {state_dict key: shape} of the reference's ``Transformer(**kwargs)`` without extra_art / num_ph: a ResBlock lists conv1, bn1
     (parameters, then buffers), conv2, bn2 and, where it changes the width, residual_path and res_norm; an encoder layer its attention's

@@ -630,7 +630,8 @@ int hificar_bigru_backward(hificar_bigru* h, const float* dout, int B, int T, co
  * (8-head self-attention with learned relative positions up to distance 100, a 3072-wide ReLU feed-forward), Linear.  nhead = 8,
  * dim_feedforward = 3072 and relative_positional_distance = 100 are the reference constructor's constants.  The attention is computed in its
  * banded form: a sequence of more than 100 frames has every logit with |k - q| >= 100 lowered by 1e8 in the reference (weight exactly 0 in
- * fp32), so only keys with |k - q| <= 99 are visited.  Not built: training, bf16x3, extra_art, num_ph (the binding refuses them).
+ * fp32), so only keys with |k - q| <= 99 are visited.  Training: the block behind hificar_xfmr_destroy.  Not built: bf16x3, extra_art, num_ph
+ * (the binding refuses them).
  * Exact fp32.  Errors as everywhere: a negative HIFICAR_E_* code and hificar_last_error().
  * --------------------------------------------------------------------------------------------------------------------------- */
 #define HIFICAR_XFMR_MAX_IN 4096
@@ -679,6 +680,8 @@ int hificar_xfmr_forward(hificar_xfmr* h, const float* x, const int32_t* lengths
 
 /* Test aid: the following forwards also copy the named intermediate, as rows (B, T, hidden_dim), into dst (device, `capacity` floats).
  * Names: "conv_blocks", "w_raw_in", "layers.<l>.norm1" (the attention sub-block's output), "layers.<l>" (the layer's output).
+ * hificar_xfmr_forward_train serves three more, the outputs of its ReLUs (which side of each the device took): "conv_blocks.<n>.relu1",
+ * "conv_blocks.<n>.relu2" (rows of hidden_dim) and "layers.<l>.hidden" (rows of 3072, before the dropout).
  * name = NULL forgets every tap, dst = NULL that one. */
 int hificar_xfmr_debug_tap(hificar_xfmr* h, const char* name, float* dst, size_t capacity);
 
@@ -687,6 +690,53 @@ hificar_engine* hificar_xfmr_engine(hificar_xfmr* h);
 
 /* del model */
 void hificar_xfmr_destroy(hificar_xfmr* h);
+
+/* ---- Transformer training: the reference's step for dataset_mode art / a2m / m2a (articulatory/bin/train.py:241-383), the model in train()
+ * mode: BatchNorm1d on batch statistics in the three ResBlocks, Dropout(p) on the attention probabilities, behind the attention and feed-forward
+ * sub-blocks and on the feed-forward's hidden rows.  Exact fp32, deterministic: every reduction is summed in a fixed order, no floating-point
+ * atomics.  Equal-length batches only (the reference's CollaterMelArt cuts equal windows): there is no lengths argument.
+ * All of these may be called after hificar_xfmr_finalize; the first one builds the training state.
+ * Not built: ragged Transformer training, bf16x3, extra_art, num_ph, multi-GPU training of this model. ---- */
+
+/* Every float tensor of the state_dict (reference names and layouts, the batch norms' running_mean / running_var included; n = all of them,
+ * each once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs (the
+ * q | k | v weight of 3 hidden_dim rows and w_o's transpose among them), their data-gradient packs, and the eval-mode fold of every batch norm
+ * into its conv — hificar_xfmr_forward sees the new weights too.  Call it after every optimizer step (and before the first
+ * hificar_xfmr_forward_train). */
+int hificar_xfmr_set_parameters_device(hificar_xfmr* h, const char* const* names, const float* const* data, int n, void* stream);
+
+/* The gradient buffer: hificar_xfmr_grad_floats(h) floats; tensor i of hificar_xfmr_grad_count(h) has the reference's state_dict name
+ * (name96: at least 96 bytes) and layout — w_q / w_k / w_v (8, F, d), w_o (8, d, F), relative_positional.embeddings (8, 199, d, 1), conv
+ * weights (F, C, 3) — at `offset` floats, `numel` long.  Same contract as hificar_grad_info. */
+int hificar_xfmr_grad_count(hificar_xfmr* h);
+int hificar_xfmr_grad_info(hificar_xfmr* h, int i, char* name96, int64_t* offset, int64_t* numel);
+int64_t hificar_xfmr_grad_floats(hificar_xfmr* h);
+
+/* Bytes of the tape (what a training forward keeps for its backward pass: the input rows; per batch norm its conv's raw output rows and the
+ * statistics; per ResBlock its two ReLU outputs; per encoder layer its input rows, q | k | v, the attention's output rows and L = m + log l
+ * per (head, query), both pre-LayerNorm rows, norm1's output and the feed-forward's hidden rows; dropout masks are regenerated, not stored)
+ * and of the scratch shared by hificar_xfmr_forward_train and hificar_xfmr_backward. */
+size_t hificar_xfmr_tape_bytes(const hificar_xfmr* h, int B, int T);
+size_t hificar_xfmr_train_workspace_bytes(hificar_xfmr* h, int B, int T);
+
+/* Transformer.forward in train() mode: x (B, in_channels, T) -> out (B, out_channels, T), device fp32.
+ * Batch norms: per-channel mean and BIASED variance over the B T frames (two-pass variance); bn_batch_stats receives 2 hidden_dim device
+ * floats (mean | variance) per BatchNorm1d in registration order — conv_blocks.0.bn1, .bn2, (.res_norm when in_channels != hidden_dim),
+ * conv_blocks.1.bn1, ... : 7 of them, or 6 — and the caller updates the running statistics as torch.nn.BatchNorm1d does.
+ * Dropout: element e of site s is kept when u(seed, offset, s, e) >= dropout_p and scaled by 1 / (1 - dropout_p); u is the counter-based
+ * generator of hificar_bigru_forward_train with the key mix(seed ^ mix(128 offset + s)) (numpy restatement:
+ * articulatory_amd.utils.synth.xfmr_dropout_mask), `offset` the caller's count of training forwards.  Sites of encoder layer l: 4 l + 0 the
+ * attention probabilities, e = ((b 8 + h) T + q) 199 + (k - q + 99) (only in-band probabilities exist); 4 l + 1 dropout1, 4 l + 2 the
+ * feed-forward's hidden rows, 4 l + 3 dropout2, e = the element's index in the (B, T, C) tensor.  dropout_p = 0 is the identity.
+ * B * T >= 2.  tape / workspace: 256-byte aligned device memory of at least the sizes above; what they hold on entry does not matter; the
+ * tape is the caller's until hificar_xfmr_backward ran.  tape = NULL (tape_bytes ignored): the same arithmetic and outputs without a tape. */
+int hificar_xfmr_forward_train(hificar_xfmr* h, const float* x, float* out, float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed,
+                               uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dout (B, out_channels, T) -> grads (hificar_xfmr_grad_floats floats: written, not accumulated) and, with dx non-NULL, the input's
+ * gradient (B, in_channels, T).  The weights must be those of the forward that filled the tape.  Deterministic, as above. */
+int hificar_xfmr_backward(hificar_xfmr* h, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

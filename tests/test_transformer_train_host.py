@@ -1,0 +1,174 @@
+"""Host-side checks of Transformer training (``pytest -m "not gpu"``): the torch-autograd restatement tests/transformer_train_oracle.py against
+the golden vectors of the REAL reference class in train() mode (tools/make_golden_transformer_train.py), the numpy restatement of the
+dropout generator, the admission of every shape the device tests run, the new block of the C header, and the trainer's surface.
+"""
+
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import transformer_train_oracle as O
+from conftest import GOLDEN, REPO, rel_err
+from articulatory_amd import _native
+from articulatory_amd.bin import train as T
+from articulatory_amd.utils.synth import xfmr_dropout_mask
+
+NEW_SYMBOLS = ("hificar_xfmr_set_parameters_device", "hificar_xfmr_grad_count", "hificar_xfmr_grad_info", "hificar_xfmr_grad_floats",
+               "hificar_xfmr_tape_bytes", "hificar_xfmr_train_workspace_bytes", "hificar_xfmr_forward_train", "hificar_xfmr_backward")
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(os.path.join(GOLDEN, "gold_transformer_train.npz"))
+
+
+def golden_errors(gold, tag, got, skip=()):
+    """{quantity: (deviation from the golden case, bar)} for what tools/make_golden_transformer_train.py stores."""
+    out = {"out": (rel_err(got["out"].cpu().numpy(), gold[f"{tag}_out"]), O.BARS["out"]),
+           "loss": (abs(float(got["loss"]) - float(gold[f"{tag}_loss"][0])) / abs(float(gold[f"{tag}_loss"][0])), O.BARS["loss"]),
+           "stats": (rel_err(got["stats"].cpu().numpy(), gold[f"{tag}_stats"]), O.BARS["out"]),
+           "dx": (rel_err(got["dx"].cpu().numpy(), gold[f"{tag}_dx"]), O.BARS["grad"])}
+    for k, v in got["running"].items():
+        out["running." + k] = (rel_err(v.cpu().numpy(), gold[f"{tag}_running.{k}"]), O.BARS["out"])
+    nograd = set(gold[f"{tag}_nograd"].tolist())
+    for k, g in got["grads"].items():
+        if k in nograd or k in skip:
+            continue
+        g = g.detach().cpu().double().numpy()
+        scale = float(gold[f"{tag}_scale.{k}"])
+        if f"{tag}_grad.{k}" in gold.files:
+            e = float(np.abs(g - gold[f"{tag}_grad.{k}"]).max() / scale)
+        else:
+            e = float(np.abs(g.reshape(-1)[O.sample_index(k, g.size)] - gold[f"{tag}_gsample.{k}"]).max() / scale)
+            s, n2 = gold[f"{tag}_gsum.{k}"]
+            # the sum of N entries each within bar * scale, and the norm, which moves by at most the difference's norm
+            e = max(e, abs(g.sum() - s) / (g.size * scale), abs(np.sqrt((g ** 2).sum()) - n2) / (np.sqrt(g.size) * scale))
+        out["grad." + k] = (e, O.BARS["grad"])
+    return out
+
+
+def test_golden_file_lists_its_keys(gold):
+    keys = open(os.path.join(GOLDEN, "gold_transformer_train_keys.txt")).read().split()
+    assert sorted(gold.files) == keys
+    assert os.path.getsize(os.path.join(GOLDEN, "gold_transformer_train.npz")) < 1024 * 1024
+    assert float(gold[f"{O.GOLD_CASE}_f32_share"]) <= 0.5  # the tool's admission, as stored
+    # the reference's relative-position tables are cut out of its graph (padded under no_grad): exactly these get no gradient there
+    assert sorted(gold[f"{O.GOLD_CASE}_nograd"].tolist()) == [f"transformer.layers.{l}.self_attn.relative_positional.embeddings" for l in range(2)]
+
+
+def test_restatement_reproduces_the_golden_case(gold):
+    tag = O.GOLD_CASE
+    r = O.restatement(tag, torch.float32)
+    errs = golden_errors(gold, tag, r)
+    assert len([k for k in errs if k.startswith("grad.")]) == len(r["grads"]) - 2
+    for k, (e, bar) in errs.items():
+        assert e < 0.5 * bar, (k, e)
+
+
+def test_dropout_mask_generator():
+    shape = (2, 50, 128)
+    for p in (0.2, 0.5):
+        m = xfmr_dropout_mask(5, 3, 6, shape, p)
+        assert m.shape == shape and m.dtype == np.float32
+        assert set(np.unique(m).tolist()) == {0.0, float(np.float32(1) / (np.float32(1) - np.float32(p)))}
+        n = m.size
+        assert abs((m > 0).mean() - (1 - p)) < 3 * np.sqrt(p * (1 - p) / n)  # keep rate within 3 sigma
+        assert np.array_equal(m, xfmr_dropout_mask(5, 3, 6, shape, p))      # a pure function
+        # another seed, offset or site; and the pair (offset 4, site 2), which the BiGRU's key 4 offset + site would confuse with (3, 6)
+        for other in (xfmr_dropout_mask(6, 3, 6, shape, p), xfmr_dropout_mask(5, 4, 6, shape, p), xfmr_dropout_mask(5, 3, 7, shape, p),
+                      xfmr_dropout_mask(5, 4, 2, shape, p)):
+            agree = ((m > 0) == (other > 0)).mean()
+            assert abs(agree - (p * p + (1 - p) * (1 - p))) < 4 * np.sqrt(0.25 / n)
+    assert np.array_equal(xfmr_dropout_mask(5, 3, 6, shape, 0.0), np.ones(shape, dtype=np.float32))
+    # site 0 of a layer: the band.  Entry (b, h, q, k) is element ((b 8 + h) T + q) 199 + (k - q + 99) of the same draw
+    B, T_, p = 2, 130, 0.5
+    m = xfmr_dropout_mask(9, 1, 4, (B, T_), p)
+    assert m.shape == (B, 8, T_, T_)
+    flat = xfmr_dropout_mask(9, 1, 5, (B * 8 * T_ * 199,), p)  # sites 1-3 index row-major: the same generator under another key ...
+    assert not np.array_equal(flat[:T_], m[0, 0, 0])
+    from articulatory_amd.utils import synth as S
+    key = S._splitmix64(np.array([9], dtype=np.uint64) ^ S._splitmix64(np.array([128 * 1 + 4], dtype=np.uint64)))
+    for (b, h, q, k) in ((0, 0, 0, 0), (1, 7, 129, 30), (0, 3, 50, 129), (1, 2, 100, 1)):
+        e = np.uint64(((b * 8 + h) * T_ + q) * 199 + (k - q + 99))
+        with np.errstate(over="ignore"):
+            u = np.float32(int(S._splitmix64((e + key) & S._MASK)[0]) >> 40) * np.float32(1.0 / 16777216.0)
+        assert m[b, h, q, k] == (np.float32(2.0) if u >= np.float32(p) else np.float32(0.0))
+    assert (m[0, 0, 0, 100:] == 1).all() and (m[1, 5, 129, :30] == 1).all()  # outside the band: no probability, factor 1
+
+
+@pytest.mark.parametrize("name", list(O.SHAPES))
+def test_device_shape_is_admitted(name):
+    """The admission rule of the BiGRU edge tests: the restatement's own float32 run is within half of every bar against its float64 run,
+    and the case is off the L1 kink."""
+    ref = O.restatement(name, torch.float64)
+    assert ref["kink"] > O.KINK_MARGIN
+    worst = {k: e / bar for k, (e, bar) in O.errors(O.restatement(name, torch.float32), ref).items()}
+    k = max(worst, key=worst.get)
+    print(f"{name}: worst fp32 share of a bar: {k} {worst[k]:.3f}")
+    assert worst[k] <= 0.5, (k, worst[k])
+
+
+def test_new_symbols_in_header_and_library(tmp_path):
+    src = tmp_path / "t.c"
+    src.write_text('#include "hificar.h"\n'
+                   "int use(hificar_xfmr* h, const float* x, float* y, void* p, const char* const* n, const float* const* d) {\n"
+                   "    return hificar_xfmr_forward_train(h, x, y, y, 1, 2, 0.2f, 1u, 0u, p, hificar_xfmr_tape_bytes(h, 1, 2), p,\n"
+                   "                                      hificar_xfmr_train_workspace_bytes(h, 1, 2), 0)\n"
+                   "         + hificar_xfmr_backward(h, x, 1, 2, p, 0, y, 0, p, 0, 0) + hificar_xfmr_set_parameters_device(h, n, d, 0, 0)\n"
+                   "         + hificar_xfmr_grad_count(h) + (int)hificar_xfmr_grad_floats(h) + hificar_xfmr_grad_info(h, 0, 0, 0, 0);\n}\n")
+    r = subprocess.run(["cc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    lib = _native.load_library()
+    for name in NEW_SYMBOLS:
+        assert name in _native.SYMBOLS and hasattr(lib, name)
+    # before finalize: no sizes, no training state
+    h = ctypes.c_void_p()
+    cfg = _native.make_xfmr_config(dict(O.BASE))
+    _native.check(lib.hificar_xfmr_create(ctypes.byref(cfg), ctypes.byref(h)), "hificar_xfmr_create")
+    try:
+        assert lib.hificar_xfmr_tape_bytes(h, 2, 100) == 0
+        assert lib.hificar_xfmr_train_workspace_bytes(h, 2, 100) == 0
+        assert b"hificar_xfmr_finalize" in lib.hificar_last_error()
+        assert lib.hificar_xfmr_grad_count(h) == -1 and lib.hificar_xfmr_grad_floats(h) == -1
+        assert lib.hificar_xfmr_forward_train(h, None, None, None, 2, 100, 0.0, 0, 0, None, 0, None, 0, None) < 0
+    finally:
+        lib.hificar_xfmr_destroy(h)
+
+
+def config(**kw):
+    cfg = dict(generator_type="Transformer", dataset_mode="a2m", generator_params=dict(O.BASE, dropout=0.2), generator_optimizer_type="Adam",
+               generator_optimizer_params=dict(lr=1e-3), generator_scheduler_params=dict(step_size=10, gamma=0.5), train_max_steps=100,
+               discriminator_train_start_steps=100)
+    cfg.update(kw)
+    return cfg
+
+
+def test_inversion_trainer_builds_a_transformer_and_refuses_pad():
+    cpu = torch.device("cpu")
+    tr = T.InversionTrainer(config(), cpu)  # parameters on the CPU: nothing touches a device before the first step
+    from articulatory_amd.models import Transformer
+
+    assert isinstance(tr.G, Transformer) and tr.G.training and tr.steps == 0 and set(tr.optimizer) == {"generator"}
+    assert tr.G._calls == 0 and isinstance(tr.G._dropout_seed, int)
+    tr.G.set_dropout_seed(5, offset=3)
+    assert (tr.G._dropout_seed, tr.G._calls) == (5, 3)
+    steps = tr.G._steps_seen
+    tr.G.invalidate_parameters()
+    assert tr.G._dirty and tr.G._steps_seen == steps + 1
+    with pytest.raises(NotImplementedError, match="package_mode pad"):
+        T.InversionTrainer(config(package_mode="pad"), cpu)
+    with pytest.raises(NotImplementedError, match="ragged training"):
+        tr.G(torch.zeros(2, 12, 5), lengths=[5, 3])
+    with pytest.raises(NotImplementedError, match=r"train\(\) mode.*on the device only"):
+        tr.G(torch.zeros(2, 12, 5))
+    with pytest.raises(NotImplementedError, match="generator_type Transformer trains with InversionTrainer"):
+        T.Trainer(config(), cpu)
+    # a checkpoint is the reference's layout and loads strictly
+    sd = tr.G.state_dict()
+    assert "conv_blocks.0.bn1.num_batches_tracked" in sd and "transformer.layers.1.self_attn.relative_positional.embeddings" in sd
+    T.InversionTrainer(config(), cpu).G.load_state_dict(sd, strict=True)

@@ -1,0 +1,285 @@
+"""Restatement of the Transformer feature model's TRAINING step for the tests, under torch autograd, written from the formulas (not from
+the reference's text):
+
+    ResBlock   as tests/transformer_oracle.py, the norms on BATCH statistics (F.batch_norm(training=True): per-channel mean and biased variance
+               over the B T frames; the running buffers move by momentum 0.1 with the unbiased variance)
+    layer      a = x + drop1(attention(x));  x1 = LayerNorm(a);  x2 = LayerNorm(x1 + drop3(linear2(drop2(relu(linear1(x1))))))
+    attention  softmax over the band as in tests/transformer_oracle.py, the probabilities multiplied by drop0 before they meet V
+    dropout    the package's own masks (articulatory_amd.utils.synth.xfmr_dropout_mask): site 4 l + {0, 1, 2, 3} of layer l
+
+float64 or float32, CPU or (for tools/transformer_bench.py --train, as the stock-PyTorch side) a GPU.  Test infrastructure only.
+"""
+
+from collections import OrderedDict
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from articulatory_amd.utils.synth import synth_transformer_state_dict, uniform, xfmr_dropout_mask
+from transformer_oracle import REL, _pos_index
+
+BASE = dict(in_channels=12, out_channels=8, elayers=2, hidden_dim=128)  # head size 16
+# The shapes of tests/test_gpu_transformer_train.py: name -> (model params, B, T, dropout p).  T: the 64-query / 64-key tile edges, the band
+# edge at 99 / 100, 199 .. 201 (the first T at which a key tile's band spans more than three query tiles), a ragged last tile at 263; the
+# head sizes 96 and 128 (template parameters); no residual_path; one sequence.  Each is admitted on the CPU first
+# (tests/test_transformer_train_host.py): the restatement's own float32 run must be within half of every bar the device is held to.
+SHAPES = OrderedDict([
+    ("t2", (BASE, 2, 2, 0.5)),
+    ("t63", (BASE, 2, 63, 0.0)),
+    ("t64", (BASE, 2, 64, 0.2)),
+    ("t65", (BASE, 2, 65, 0.5)),
+    ("t100", (BASE, 2, 100, 0.2)),
+    ("t101", (BASE, 2, 101, 0.0)),   # the golden case (tools/make_golden_transformer_train.py)
+    ("t199", (BASE, 2, 199, 0.2)),
+    ("t200", (BASE, 2, 200, 0.5)),
+    ("t201", (BASE, 2, 201, 0.0)),
+    ("t263", (BASE, 2, 263, 0.2)),
+    ("d96", (dict(in_channels=12, out_channels=8, elayers=1, hidden_dim=768), 2, 130, 0.2)),
+    ("d128", (dict(in_channels=12, out_channels=8, elayers=1, hidden_dim=1024), 2, 70, 0.2)),
+    ("nores", (dict(in_channels=128, out_channels=8, elayers=1, hidden_dim=128), 2, 65, 0.2)),
+    ("b1", (BASE, 1, 100, 0.5)),
+])
+SEEDS = {name: 8100 + i for i, name in enumerate(SHAPES)}
+# Seeds changed by the admission rule, not the bars: at the first seed of these shapes one feed-forward hidden value lies so close to zero
+# that the restatement's own float32 run takes the other side of the ReLU than its float64 run (linear1.weight's gradient then differs by a
+# whole row: 243, 306 and 264 bars; d128 again at 8200: 45 bars).
+SEEDS.update(t200=8200, d96=8200, d128=8201)
+GOLD_CASE = "t101"
+DROPOUT_SEED = 777
+BARS = dict(out=2e-5, loss=1e-5, grad=2e-4)  # the BiGRU training suite's bars: relative to each tensor's max; the loss relative
+KINK_MARGIN = 1e-4  # the project's convention (tests/bigru_train_oracle.py): min |y - target| / max |y| above it keeps the L1 loss off its kink
+STEPS = dict(n=5, lr=1e-3, grad_norm=10.0, step_size=1, gamma=0.5, lambda_aux=1.0)  # the five-step run on the golden case's model
+FULL_LIMIT, SAMPLES = 16384, 4096  # golden gradients: whole up to FULL_LIMIT elements, else SAMPLES seeded entries + float64 sum and L2 norm
+
+
+def case(name, step=0):
+    """(model params with dropout, state_dict, x (B, in, T), target (B, out, T)) of a SHAPES entry; ``step`` draws another batch."""
+    params, B, T, p = SHAPES[name]
+    seed = SEEDS[name]
+    x = uniform(seed, f"x.{step}", (B, params["in_channels"], T), -1.0, 1.0)
+    # |y| is a few tenths: targets in +-[4, 5] keep every |y - target| off the L1 kink
+    t = uniform(seed, f"t.{step}", (B, params["out_channels"], T), 4.0, 5.0) * np.where(
+        uniform(seed, f"s.{step}", (B, params["out_channels"], T), -1.0, 1.0) >= 0, 1.0, -1.0).astype(np.float32)
+    return dict(params, dropout=p), synth_transformer_state_dict(params, seed=seed), x, t
+
+
+GATE_GAP = 2e-5  # a ReLU may be taken on the other side than the float64 run only where its input is within the output bar of zero
+
+
+def relu_names(params):
+    return [f"conv_blocks.{i}.relu{j}" for i in range(3) for j in (1, 2)] + [f"layers.{l}.hidden" for l in range(params["elayers"])]
+
+
+def restatement(name, dtype, device="cpu", gates=None):
+    """One step of the restatement on a SHAPES entry: step()'s dict + running buffers {name: tensor} + kink (+ gate_gap, gate_flips with
+    ``gates``: see TransformerTrainOracle)."""
+    params, sd, x, t = case(name)
+    o = TransformerTrainOracle(sd, dtype=dtype, device=device, dropout=params["dropout"], seed=DROPOUT_SEED, gates=gates)
+    r = o.step(x, t)
+    r["gate_gap"], r["gate_flips"] = o.gate_gap, o.gate_flips
+    r["running"] = dict(o.buffers)
+    r["kink"] = float((r["out"] - torch.from_numpy(t).to(r["out"])).abs().min() / r["out"].abs().max())
+    return r
+
+
+def grad_scale(ref_grads, k):
+    """What a gradient's deviation is relative to: its own max — except a conv bias in front of a batch norm on batch statistics, whose
+    gradient is mathematically zero (the norm subtracts the mean): its conv weight's."""
+    if k.startswith("conv_blocks.") and k.endswith((".conv1.bias", ".conv2.bias", ".residual_path.bias")):
+        k = k[:-len("bias")] + "weight"
+    return max(float(torch.as_tensor(ref_grads[k]).abs().max()), 1e-30)
+
+
+def errors(got, ref):
+    """{quantity: (deviation of ``got`` from the float64 results ``ref``, its bar)}: out, batch statistics and running buffers relative to
+    the tensor's max, the loss relative, dx and every gradient relative to grad_scale."""
+    def rel(a, b, scale=None):
+        b = torch.as_tensor(b).detach().cpu().double()
+        return float((torch.as_tensor(a).detach().cpu().double() - b).abs().max() / (scale or max(float(b.abs().max()), 1e-30)))
+
+    out = {"out": (rel(got["out"], ref["out"]), BARS["out"]),
+           "loss": (abs(float(got["loss"]) - float(ref["loss"])) / abs(float(ref["loss"])), BARS["loss"]),
+           "stats": (rel(got["stats"], ref["stats"]), BARS["out"])}
+    for k, v in ref["running"].items():
+        out["running." + k] = (rel(got["running"][k], v), BARS["out"])
+    if got.get("dx") is not None:
+        out["dx"] = (rel(got["dx"], ref["dx"]), BARS["grad"])
+    for k, r in ref["grads"].items():
+        out["grad." + k] = (rel(got["grads"][k], r, grad_scale(ref["grads"], k)), BARS["grad"])
+    return out
+
+
+def sample_index(name, numel):
+    """The SAMPLES seeded flat indices at which a golden gradient larger than FULL_LIMIT is stored."""
+    u = uniform(4242, "sample." + name, (SAMPLES,), 0.0, 1.0)
+    return np.minimum((u.astype(np.float64) * numel).astype(np.int64), numel - 1)
+
+
+def banded_attention_train(q, k, v, emb, mask=None, chunk=128):
+    """q, k, v: (B, H, T, d); emb: (H, 199, d); mask: None or the dense (B, H, T, T) dropout factors -> (B, H, T, d).  Autograd-friendly
+    (no in-place writes): the query chunks are concatenated."""
+    B, H, T, d = q.shape
+    outs = []
+    for q0 in range(0, T, chunk):
+        nq = min(chunk, T - q0)
+        k0, k1 = max(0, q0 - (REL - 1)), min(T, q0 + nq + (REL - 1))
+        qc = q[:, :, q0:q0 + nq]
+        s = torch.einsum("bhqa,bhka->bhqk", qc, k[:, :, k0:k1]) / (d ** 0.5)
+        rel, ok = _pos_index(q0, nq, k0, k1 - k0, q.device)
+        pos = torch.einsum("bhqa,hra->bhqr", qc, emb)
+        s = s + torch.gather(pos, 3, rel.clamp(0, 2 * REL - 2).expand(B, H, -1, -1))
+        s = s.masked_fill(~ok, float("-inf"))
+        pr = torch.softmax(s, dim=-1)
+        if mask is not None:
+            pr = pr * mask[:, :, q0:q0 + nq, k0:k1]
+        outs.append(torch.einsum("bhqk,bhka->bhqa", pr, v[:, :, k0:k1]))
+    return torch.cat(outs, dim=2)
+
+
+class TransformerTrainOracle:
+    """``params``: the trainable tensors (leaves with requires_grad), ``buffers``: running_mean / running_var (updated by every forward)."""
+
+    def __init__(self, state_dict, dtype=torch.float64, device="cpu", dropout=0.0, seed=0, gates=None):
+        """``gates``: None, or {ReLU name: bool tensor in the ReLU input's shape}: which side of every ReLU ANOTHER run of the same step took
+        ("conv_blocks.N.relu1" / ".relu2": (B, F, T); "layers.N.hidden": (B, T, 3072)).  Each ReLU is then x * gate.  Among the 3072 B T
+        hidden values of a layer a few lie within float32 rounding of zero, so two correct float32 runs (and a float64 one) take different
+        sides of those ReLUs; the outputs do not notice, a gradient does (one frame's share of a row: a hundred gradient bars).  With the
+        other run's gates the two compute the same piecewise-linear function and their gradients compare at the bar; how far from the kink a
+        disagreeing gate was is recorded (``gate_gap``: |x| / max |x|, and ``gate_flips``), for the caller to bound."""
+        self.dtype, self.device, self.p, self.seed = dtype, device, float(dropout), int(seed)
+        self.gates, self.gate_gap, self.gate_flips = gates, 0.0, 0
+        self.params, self.buffers = {}, {}
+        for k, v in state_dict.items():
+            if k.endswith("num_batches_tracked") or k in ("mean", "scale"):
+                continue
+            t = torch.as_tensor(np.asarray(v)).to(device=device, dtype=dtype).clone()
+            if k.endswith(("running_mean", "running_var")):
+                self.buffers[k] = t
+            else:
+                self.params[k] = t.requires_grad_(True)
+        self.elayers = 1 + max(int(k.split(".")[2]) for k in self.params if k.startswith("transformer.layers."))
+        self.calls = 0
+        self.min_relu_margin = float("inf")  # smallest |ReLU input| / max |ReLU input| met so far (the kink-free admission rule)
+
+    def bn_names(self):
+        out = []
+        for i in range(3):
+            out += [f"conv_blocks.{i}.bn1", f"conv_blocks.{i}.bn2"]
+            if f"conv_blocks.{i}.res_norm.weight" in self.params:
+                out.append(f"conv_blocks.{i}.res_norm")
+        return out
+
+    def _mask(self, site, shape):
+        if self.p <= 0:
+            return None
+        return torch.as_tensor(xfmr_dropout_mask(self.seed, self._offset, site, shape, self.p)).to(self.device, self.dtype)
+
+    def _relu(self, x, name):
+        with torch.no_grad():
+            self.min_relu_margin = min(self.min_relu_margin, float(x.abs().min() / x.abs().max()))
+        if self.gates is None:
+            return torch.relu(x)
+        g = self.gates[name].to(x.device)
+        with torch.no_grad():
+            differ = (x > 0) != g
+            if bool(differ.any()):
+                self.gate_gap = max(self.gate_gap, float(x.abs()[differ].max() / x.abs().max()))
+                self.gate_flips += int(differ.sum())
+        return x * g.to(x.dtype)
+
+    def _bn(self, x, base, stats):
+        p = self.params
+        with torch.no_grad():
+            stats[base] = (x.mean(dim=(0, 2)), x.var(dim=(0, 2), unbiased=False))
+        return F.batch_norm(x, self.buffers[base + ".running_mean"], self.buffers[base + ".running_var"], p[base + ".weight"], p[base + ".bias"],
+                            training=True, momentum=0.1, eps=1e-5)
+
+    def _resblock(self, x, base, stats):
+        p = self.params
+        y = self._relu(self._bn(F.conv1d(x, p[base + ".conv1.weight"], p[base + ".conv1.bias"], padding=1), base + ".bn1", stats), base + ".relu1")
+        y = self._bn(F.conv1d(y, p[base + ".conv2.weight"], p[base + ".conv2.bias"], padding=1), base + ".bn2", stats)
+        if base + ".residual_path.weight" in p:
+            x = self._bn(F.conv1d(x, p[base + ".residual_path.weight"], p[base + ".residual_path.bias"]), base + ".res_norm", stats)
+        return self._relu(y + x, base + ".relu2")
+
+    def forward(self, x):
+        """x: (B, C, T) tensor (may require grad) -> (out (B, O, T), {bn name: (mean, biased variance)})."""
+        p = self.params
+        self._offset = self.calls
+        self.calls += 1
+        stats = {}
+        for i in range(3):
+            x = self._resblock(x, f"conv_blocks.{i}", stats)
+        x = x.transpose(1, 2)
+        x = F.linear(x, p["w_raw_in.weight"], p["w_raw_in.bias"])
+        B, T, n = x.shape
+
+        def drop(t, site):
+            m = self._mask(site, t.shape)
+            return t if m is None else t * m
+
+        for l in range(self.elayers):
+            b = f"transformer.layers.{l}"
+            a = b + ".self_attn"
+            q, k, v = (torch.einsum("btf,hfa->bhta", x, p[f"{a}.{w}"]) for w in ("w_q", "w_k", "w_v"))
+            o = banded_attention_train(q, k, v, p[a + ".relative_positional.embeddings"][..., 0], self._mask(4 * l, (B, T)))
+            x = F.layer_norm(x + drop(torch.einsum("bhta,haf->btf", o, p[a + ".w_o"]), 4 * l + 1), (n,), p[b + ".norm1.weight"], p[b + ".norm1.bias"],
+                             eps=1e-5)
+            h = drop(self._relu(F.linear(x, p[b + ".linear1.weight"], p[b + ".linear1.bias"]), f"layers.{l}.hidden"), 4 * l + 2)
+            x = F.layer_norm(x + drop(F.linear(h, p[b + ".linear2.weight"], p[b + ".linear2.bias"]), 4 * l + 3), (n,), p[b + ".norm2.weight"],
+                             p[b + ".norm2.bias"], eps=1e-5)
+        return F.linear(x, p["w_out.weight"], p["w_out.bias"]).transpose(1, 2), stats
+
+    def step(self, x, y):
+        """One forward + L1 loss + backward: dict(out, loss, dx, grads {name: tensor}, stats (nbn, 2, F)); running buffers updated."""
+        x = torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).to(self.device, self.dtype).clone().requires_grad_(True)
+        y = torch.as_tensor(np.asarray(y) if not isinstance(y, torch.Tensor) else y).to(self.device, self.dtype)
+        for t in self.params.values():
+            t.grad = None
+        out, stats = self.forward(x)
+        loss = F.l1_loss(out, y)
+        loss.backward()
+        st = torch.stack([torch.stack(stats[n]) for n in self.bn_names()])
+        return dict(out=out.detach(), loss=loss.detach(), dx=x.grad.detach(), grads={k: v.grad.detach() for k, v in self.params.items()}, stats=st)
+
+
+STEPS_CASE, STEPS_FIRST = "t64", 0  # the five-step run: model and batches of this SHAPES entry (p = 0.2), from batch STEPS_FIRST on
+# parameters the five-step run cannot be compared on: their gradient is mathematically zero (grad_scale), so Adam's lr g / (|g| + eps) moves
+# them by a rounding-noise-dependent share of lr in any arithmetic; the batch norm behind them removes what they hold from every output
+STEPS_UNCOMPARED = (".conv1.bias", ".conv2.bias", ".residual_path.bias")
+
+
+def five_steps(dtype, device="cpu"):
+    """The trainer's step (L1 * lambda_aux, clip, Adam, StepLR) STEPS["n"] times on the restatement: (losses, final state {name: tensor})."""
+    params, sd, _, _ = case(STEPS_CASE)
+    o = TransformerTrainOracle(sd, dtype=dtype, device=device, dropout=params["dropout"], seed=DROPOUT_SEED)
+    plist = list(o.params.values())
+    opt = torch.optim.Adam(plist, lr=STEPS["lr"])
+    sched = torch.optim.lr_scheduler.StepLR(opt, step_size=STEPS["step_size"], gamma=STEPS["gamma"])
+    losses = []
+    for s in range(STEPS["n"]):
+        _, _, x, t = case(STEPS_CASE, STEPS_FIRST + s)
+        out, _ = o.forward(torch.from_numpy(x).to(device, dtype))
+        loss = F.l1_loss(out, torch.from_numpy(t).to(device, dtype)) * STEPS["lambda_aux"]
+        opt.zero_grad()
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(plist, STEPS["grad_norm"])
+        opt.step()
+        sched.step()
+        losses.append(float(loss.detach()))
+    final = {k: v.detach() for k, v in o.params.items()}
+    final.update(o.buffers)
+    return losses, final
+
+
+def five_step_errors(losses, final, ref_losses, ref_final):
+    """(worst relative loss deviation, {name: deviation of a final tensor relative to its max}) without STEPS_UNCOMPARED."""
+    e_loss = max(abs(a - b) / abs(b) for a, b in zip(losses, ref_losses))
+    worst = {}
+    for k, r in ref_final.items():
+        if k.endswith(STEPS_UNCOMPARED):
+            continue
+        r = r.detach().cpu().double()
+        worst[k] = float((final[k].detach().cpu().double() - r).abs().max() / max(float(r.abs().max()), 1e-30))
+    return e_loss, worst

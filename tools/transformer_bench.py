@@ -12,6 +12,14 @@ spread a ratio has to exceed.  The ratio reported is the conservative one: faste
 hificar_profile_begin / hificar_profile_end on one native forward: time per kernel, the attention kernel's share of the forward and its
 achieved TFLOP/s — counted as 2 * 3 * 199 * hidden FLOP per frame and layer (Q K^T, the positional product, P V over a full band) — against
 the 157.3 TFLOP/s fp32 matrix peak.
+
+   python tools/transformer_bench.py --train [--shapes 8x200 32x500] [--out profiles/transformer_train.txt]
+
+--train: one training step (forward in train() mode, dropout 0.2 + L1 loss + backward + fused Adam) at the same default size, per shape B x T,
+native against stock alternated the same way.  Stock is tests/transformer_train_oracle.py in fp32 on the same GPU (conv1d, batch_norm,
+linear, einsum, softmax, layer_norm under autograd, the attention banded too), its dropout masks drawn with torch.rand on the device (the
+package's counter-based masks would be generated on the host).  The per-kernel profile covers one native forward + backward; the
+attention backward's TFLOP/s counts 2 * 7 * 199 * hidden FLOP per frame and layer (S, dP, the K and E parts of dQ, dK, dV, dE).
 Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
 import argparse
 import ctypes
@@ -60,14 +68,93 @@ def kernel_profile(m, x):
     return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(n.value)}
 
 
+def train_main(a):
+    import torch.nn.functional as F
+
+    from transformer_train_oracle import TransformerTrainOracle
+
+    class Stock(TransformerTrainOracle):
+        def _mask(self, site, shape):
+            if site % 4 == 0:
+                shape = (shape[0], 8, shape[1], shape[1])
+            return (torch.rand(shape, device=self.device) >= self.p).to(self.dtype) / (1.0 - self.p)
+
+        def _relu(self, x, name):  # (without the restatement's bookkeeping, which synchronises)
+            return torch.relu(x)
+
+        def _bn(self, x, base, stats):
+            q = self.params
+            return F.batch_norm(x, self.buffers[base + ".running_mean"], self.buffers[base + ".running_var"], q[base + ".weight"], q[base + ".bias"],
+                                training=True, momentum=0.1, eps=1e-5)
+
+    p = 0.2
+    sd = synth_transformer_state_dict(PARAMS, seed=6101)
+    native = Transformer(dropout=p, **PARAMS)
+    native.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    native = native.cuda().train()
+    n_opt = torch.optim.Adam(native.parameters(), lr=1e-4, fused=True)
+    stock = Stock(sd, dtype=torch.float32, device="cuda", dropout=p)
+    s_opt = torch.optim.Adam(list(stock.params.values()), lr=1e-4, fused=True)
+    lines = []
+    for shape in a.shapes:
+        B, T = (int(v) for v in shape.split("x"))
+        x = torch.from_numpy(uniform(1, f"bench.{B}", (B, PARAMS["in_channels"], T), -1.0, 1.0)).cuda()
+        y = torch.from_numpy(uniform(2, f"bench.{B}", (B, PARAMS["out_channels"], T), -1.0, 1.0)).cuda()
+
+        def native_step(_):
+            n_opt.zero_grad(set_to_none=True)
+            F.l1_loss(native(x), y).backward()
+            n_opt.step()
+
+        def stock_step(_):
+            s_opt.zero_grad(set_to_none=True)
+            F.l1_loss(stock.forward(x)[0], y).backward()
+            s_opt.step()
+
+        for _ in range(2):
+            native_step(None), stock_step(None)
+        torch.cuda.synchronize()
+        n1 = window(native_step, None, a.window)
+        s1 = window(stock_step, None, a.window)
+        n2 = window(native_step, None, a.window)
+        s2 = window(stock_step, None, a.window)
+        res = {"train": True, "B": B, "T": T, "dropout": p, "native_ms": [round(n1, 3), round(n2, 3)], "stock_ms": [round(s1, 3), round(s2, 3)],
+               "native_spread": round(abs(n1 - n2) / min(n1, n2), 4), "stock_spread": round(abs(s1 - s2) / min(s1, s2), 4),
+               "stock_over_native": round(min(s1, s2) / max(n1, n2), 3), "native_frames_per_s": round(B * T / (min(n1, n2) * 1e-3))}
+        lib, eng = native._lib, native.engine()
+        _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
+        native.zero_grad(set_to_none=True)
+        F.l1_loss(native(x), y).backward()
+        stats = (_native.HificarKernelStat * 128)()
+        n = ctypes.c_int()
+        _native.check(lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
+        prof = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+        total = sum(prof.values())
+        res["kernels_share"] = {k: round(ms / total, 4) for k, ms in sorted(prof.items(), key=lambda kv: -kv[1])}
+        res["profiled_total_ms"] = round(total, 3)
+        bwd = prof.get("xfmr_attn_bwd_kernels", 0.0)
+        flop = 2.0 * 7 * 199 * PARAMS["hidden_dim"] * B * T * PARAMS["elayers"]
+        res["attn_bwd_ms"] = round(bwd, 3)
+        res["attn_bwd_tflops"] = round(flop / (bwd * 1e-3) / 1e12, 2) if bwd else None
+        lines.append(json.dumps(res))
+        print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true")
+    ap.add_argument("--shapes", nargs="+", default=["8x200", "32x500"])
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 32])
     ap.add_argument("--frames", type=int, default=2000)
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--no-stock", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.train:
+        return train_main(a)
     T = a.frames
     sd = synth_transformer_state_dict(PARAMS, seed=6101)
     native = Transformer(**PARAMS)
