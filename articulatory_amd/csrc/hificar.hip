@@ -93,7 +93,7 @@ struct GBlockLayers {
 struct PlanKey {
     const ConvLayer* layers[6];  // launch_conv: the branches' layers; launch_pair: conv1 of every branch, from [3] on conv2; null: no such branch
     int nseq, rows, zrep;
-    int flags;                   // 1: exact fp32, 2: training (device-resident weights), 4: shared_chip, 8: launch_pair
+    int flags;                   // 1: exact fp32, 2: training (device-resident weights), 4: shared_chip, 8: launch_pair, 16: launch_merged (up to four layers)
     bool operator<(const PlanKey& o) const { return memcmp(this, &o, sizeof(PlanKey)) < 0; }  // (six pointers, four ints: no padding)
 };
 
@@ -108,6 +108,8 @@ struct ConvPlan {
     // own tile schedule in the arenas (null: the kernel's round-robin walk) — and the rest zero: a launch copies it and adds the call's IO
     MultiConvParams conv = {};  // launch_conv
     PairParams pair = {};       // launch_pair
+    MergeConvParams merge = {}; // launch_merged
+    bool merge_wins = false;    // launch_merged: the estimate puts this launch + a one-stream upsampler ahead of the side-by-side launch + the folded mean
 };
 
 // The conv engine: everything a launch needs whatever network owns it.  Every model type holds one — the generators by inheritance
@@ -117,8 +119,9 @@ struct hificar_engine {
     int num_cus = 256;
     bool training = false;         // weights are device-resident (the generator sets it where it creates its TrainState): part of the plan key
     bool profile_detail = false;   // HIFICAR_PROFILE_DETAIL=1: profile rows carry the layer name
-    bool use_pair = true;          // HIFICAR_PAIR=0: run narrow stages layer by layer (A/B runs)
+    bool use_pair = true;          // HIFICAR_PAIR=0: layer by layer, no fused launch forms (neither the pair kernels nor the branch-summing launch)
     bool pair_small = true;        // HIFICAR_PAIR_SMALL: 128-row fused pair tiles at C = 32 for mid-size launches (pair_small_tiles)
+    int mrf_merge = 1;             // HIFICAR_MRF_MERGE: 0 = never sum the MRF branches in the last ResBlock launch, 1 = where estimated faster (default), 2 = wherever allowed
     int ksplit = 1;                // HIFICAR_KSPLIT: 0 = never use the split-K conv form, 1 = when it is estimated faster (default), 2 = always
     double mi1_penalty = 1.05;     // cost factor of 32-row tiles in the exact-fp32 tile choice (they re-stream the weights most often: L2-bound when
                                    // K is long).  The discriminator engine raises it: its launches overlap on several streams, so a nearly
@@ -242,8 +245,13 @@ struct hificar_handle : hificar_engine {
 //                              joined with rocprofv3's per-dispatch rows by tools/pmc_by_layer.py (implies PROFILE_DETAIL)
 //   HIFICAR_KSPLIT=0|1|2       split-K conv form: never / when estimated faster (default) / always.  0 makes every launch shape use one accumulation
 //                              order, so results are bit-identical across batch compositions (tests/test_gpu_parity.py)
-//   HIFICAR_PAIR=0             narrow stages layer by layer instead of the fused pair kernels;  HIFICAR_PAIR_SMALL=0: no 128-row pair tiles at C = 32
+//   HIFICAR_PAIR=0             layer by layer, no fused launch forms: neither the fused pair kernels of the narrow stages nor the branch-summing last
+//                              ResBlock launch (one "layer xN" row per layer in the profile);  HIFICAR_PAIR_SMALL=0: no 128-row pair tiles at C = 32
 //                              (the GBlock generator, the discriminators and the BiGRU have no such stages: they switch the pair kernels off)
+//   HIFICAR_MRF_MERGE=0|1|2    the last ResBlock launch of a stage sums all blocks in one accumulator and writes the activated MRF mean (conv_f32mrg_kernel,
+//                              exact fp32 inference only; mrf_merge_allowed): never / where the planner estimates it faster (default) / wherever allowed.
+//                              Always off with HIFICAR_KSPLIT=0 (whether it runs depends on the launch size, and it rounds differently), HIFICAR_KSPLIT=2
+//                              (the form is dense) and HIFICAR_PAIR=0.  A forced tile shape (hificar_debug_force_tile) does not enter the planner's estimate
 // The generators add HIFICAR_AR_DUAL_MIN / _MAX: the batch sizes hificar_ar_loop runs as two halves on two streams (default 17..62; MAX=0: never).
 // hificar_disc.hip.inc adds HIFICAR_DISC_STREAMS=0 (sub-discriminators on the caller's stream: per-launch counters) and HIFICAR_COL2IM_VEC4=0.
 // hificar_bigru.hip.inc adds HIFICAR_BIGRU_NS=1|2 (sequences per workgroup of the recurrent kernel, A/B runs) and always runs with KSPLIT off.
@@ -258,6 +266,7 @@ static void read_env_switches(hificar_engine* h) {
     if (const char* e = getenv("HIFICAR_KSPLIT")) h->ksplit = atoi(e);
     if (const char* e = getenv("HIFICAR_PAIR")) h->use_pair = atoi(e) != 0;
     if (const char* e = getenv("HIFICAR_PAIR_SMALL")) h->pair_small = atoi(e) != 0;
+    if (const char* e = getenv("HIFICAR_MRF_MERGE")) h->mrf_merge = atoi(e);
 }
 
 // RAII bracket around one kernel launch: the launch log, and an event before and after while profiling is on.
@@ -665,6 +674,7 @@ hipError_t hificar::conv_launch(const ConvShape& s, const void* params, dim3 gri
     if (handled) return e;
     HIFICAR_TRY_SET(0) HIFICAR_TRY_SET(1) HIFICAR_TRY_SET(2) HIFICAR_TRY_SET(3) HIFICAR_TRY_SET(4)
     HIFICAR_TRY_SET(5) HIFICAR_TRY_SET(6) HIFICAR_TRY_SET(7) HIFICAR_TRY_SET(8) HIFICAR_TRY_SET(9)
+    HIFICAR_TRY_SET(10) HIFICAR_TRY_SET(11) HIFICAR_TRY_SET(12)
 #undef HIFICAR_TRY_SET
     return hipErrorInvalidValue;  // a shape that is not built
 }
@@ -675,6 +685,7 @@ hipError_t hificar::conv_set_lds_attributes() {
     if (e == hipSuccess) e = conv_inst_attrs_##n();
     HIFICAR_ATTR_SET(0) HIFICAR_ATTR_SET(1) HIFICAR_ATTR_SET(2) HIFICAR_ATTR_SET(3) HIFICAR_ATTR_SET(4)
     HIFICAR_ATTR_SET(5) HIFICAR_ATTR_SET(6) HIFICAR_ATTR_SET(7) HIFICAR_ATTR_SET(8) HIFICAR_ATTR_SET(9)
+    HIFICAR_ATTR_SET(10) HIFICAR_ATTR_SET(11) HIFICAR_ATTR_SET(12)
 #undef HIFICAR_ATTR_SET
     return e;
 }
@@ -1166,7 +1177,11 @@ static bool tile_admissible(const hificar_engine* h, const ConvLayer* const* lay
 // Tile shape of a launch_conv launch: simulate the kernel's tile walk and take the shape with the smallest makespan.  A tile costs its
 // MFMA issue cycles (all four MFMA waves run in lock step: 3*MI MFMAs of 32 cycles per 16-channel K slab) plus a fixed per-tile and
 // per-item overhead.  Pure host arithmetic on the launch shape and the engine's fixed switches.
-static TileCfg pick_tile(const hificar_engine* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, int zrep) {
+// merged: the branch-summing launch (conv_f32mrg_kernel) — a tile is a POSITION, whose workgroup runs the K loops of all nbr branches one after the
+// other and one epilogue: dense one-block shapes only.  est: the chosen shape's estimated makespan in cycles (1e300: no shape can run).
+// use_force = false: the planner's own choice even while a test forces a shape (build_merge_plan's estimates: which FORM runs must not depend on the hook).
+static TileCfg pick_tile(const hificar_engine* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, int zrep, bool merged = false,
+                         double* est = nullptr, bool use_force = true) {
     const ConvLayer& L0 = *layers[0];
     const bool f32 = h->precision == HIFICAR_PREC_F32;  // rows are plain fp32 LeakyReLU(x) instead of split rows
     int halo_all = 0;
@@ -1178,18 +1193,20 @@ static TileCfg pick_tile(const hificar_engine* h, const ConvLayer* const* layers
     // may prefer them (+1.3 %; in exact fp32 they measured -1.0 %: profiles/r04_nb_register_blocking.txt).
     int nsteps_min = 1 << 30;
     for (int b = 0; b < nbr; ++b) nsteps_min = std::min(nsteps_min, layers[b]->ntaps * (L0.chunk16 / 16));
-    if (h->force_tile[0] != 0) {  // a test's forced shape (hificar_debug_force_tile), where this launch can run it; otherwise the normal choice below
+    if (h->force_tile[0] != 0 && use_force) {  // a test's forced shape (hificar_debug_force_tile), where this launch can run it; otherwise the normal choice below
         const TileCfg t = {h->force_tile[0], h->force_tile[1], h->force_tile[2], h->force_tile[3], h->force_tile[4]};
-        if (tile_admissible(h, layers, nbr, t, halo_all, nsteps_min)) return t;
+        if (tile_admissible(h, layers, nbr, t, halo_all, nsteps_min) && (!merged || (t.KS == 1 && t.NB == 1))) return t;
     }
     for (int ti = 0; ti < kNumTileCfgs; ++ti) {
         const TileCfg& t = kTileCfgs[ti];
         const int TM = t.WM * t.MI * 32;
         const int chunk = L0.chunk16;
         if (!tile_admissible(h, layers, nbr, t, halo_all, nsteps_min)) continue;
-        if (t.KS == 1 && h->ksplit == 2 && nsteps_min >= 2) continue;
+        if (merged && (t.KS != 1 || t.NB != 1)) continue;
+        if (!merged && t.KS == 1 && h->ksplit == 2 && nsteps_min >= 2) continue;
         const long long tiles_per_branch = (long long)nseq * ((rows + TM - 1) / TM) * ((L0.n_blocks32 + t.WN * t.NB - 1) / (t.WN * t.NB));
-        const long long total = tiles_per_branch * nbr * zrep;
+        const int ncls = merged ? 1 : nbr;  // cost classes of tiles: the branches, or (merged) the one kind of position
+        const long long total = tiles_per_branch * ncls * zrep;
         const int G = (int)std::min<long long>(total, h->num_cus);
         const int nchunks = L0.cin_pad / chunk;
         // LPT makespan estimate: max(heaviest tile, total / G), plus one light tile when the count does not divide
@@ -1204,10 +1221,18 @@ static TileCfg pick_tile(const hificar_engine* h, const ConvLayer* const* layers
                 const int steps = layers[b]->ntaps * (chunk / 16);
                 c = (double)((steps + 3) / 4) * nchunks * slab * t.MI + 4000.0 + 600.0 * nchunks;
             }
+            if (merged) {  // one position: every branch's K loop, one tile set-up and epilogue, every branch's items
+                cb[0] += c - (b ? 2500.0 : 0.0);
+                continue;
+            }
             total_cost += c * tiles_per_branch * zrep;
             heaviest = std::max(heaviest, c);
             lightest = std::min(lightest, c);
             cb[b] = c;
+        }
+        if (merged) {
+            total_cost = cb[0] * tiles_per_branch * zrep;
+            heaviest = lightest = cb[0];
         }
         double worst = std::max(heaviest, total_cost / G);
         if (!h->shared_chip && total > G && total <= 4096) {
@@ -1215,11 +1240,11 @@ static TileCfg pick_tile(const hificar_engine* h, const ConvLayer* const* layers
             // Round 4: the closed form below charged "+ half a light tile" whenever the tile count is not a multiple of the workgroups — 384
             // tiles of weight 12 : 8 : 4 on 256 workgroups balance exactly (12 | 8 + 4), and the 128-row tile it ruled out at C = 256 is 1.1 %
             // faster end to end than the 64-row one it picked.
-            std::sort(cb, cb + nbr, [](double x, double y) { return x > y; });
+            std::sort(cb, cb + ncls, [](double x, double y) { return x > y; });
             std::priority_queue<double, std::vector<double>, std::greater<double>> load;
             for (int w = 0; w < G; ++w) load.push(0.0);
             worst = 0.0;
-            for (int b = 0; b < nbr; ++b)
+            for (int b = 0; b < ncls; ++b)
                 for (long long i = 0; i < tiles_per_branch * zrep; ++i) {
                     const double v = load.top() + cb[b];
                     load.pop();
@@ -1244,17 +1269,19 @@ static TileCfg pick_tile(const hificar_engine* h, const ConvLayer* const* layers
             tc = t;
         }
     }
+    if (est) *est = best;
     return tc;
 }
 
-// Kernel name of a plan as ProfScope wants it: the instantiation (hificar_launch.h), + "|layer xN" for per-layer rows in the profile (tools/layer_profile.py)
+// Kernel name of a plan as ProfScope wants it: the instantiation (hificar_launch.h), + "|layer xN" for per-layer rows in the profile (tools/layer_profile.py);
+// "|layer +N": the N branches summed in one accumulator (launch_merged) instead of side by side
 static std::string plan_name(const hificar_engine* h, const ConvShape& s, const ConvLayer& L0, int nbr) {
     static const char* const family[] = {"conv_f32do_kernel", "conv_bf16x3_kernel", "conv_bf16x3nb_kernel", "conv_sk_f32_kernel", "conv_sk_bf16x3_kernel",
-                                         "conv_pair_f32_kernel", "conv_pair_bf16x3_kernel"};
+                                         "conv_pair_f32_kernel", "conv_pair_bf16x3_kernel", "conv_f32mrg_kernel"};
     char kname[96];
     int n = s.family == kConvSkF32 || s.family == kConvSkBf16x3 ? snprintf(kname, sizeof(kname), "%s<%d,%d>", family[s.family], s.mi, s.nc16)
                                                                 : snprintf(kname, sizeof(kname), "%s<%d,%d,%d,%d>", family[s.family], s.mi, s.wm, s.wn, s.nc16);
-    if (h->profile_detail) snprintf(kname + n, sizeof(kname) - n, "|%s x%d", L0.name.c_str(), nbr);
+    if (h->profile_detail) snprintf(kname + n, sizeof(kname) - n, s.family == kConvF32mrg ? "|%s +%d" : "|%s x%d", L0.name.c_str(), nbr);
     return kname;
 }
 
@@ -1301,6 +1328,54 @@ static int build_conv_plan(hificar_engine* h, const ConvLayer* const* layers, in
         lists = lpt_lists(costs, (int)pl.grid);
     }
     return lists.empty() ? HIFICAR_OK : upload_schedule(h, lists, mp.total_tiles, stream, &mp.sched_start, &mp.sched_tiles);
+}
+
+// The branch-summing launch (conv_f32mrg_kernel): the last ResBlock layers of ALL nbr blocks of a stage, whose workgroups run the K loops of the nbr
+// branches of a position — (sequence, row tile, channel group) — into the same accumulators and write the activated MRF mean once.  Tiles are
+// positions: ngroups x nseq_tiles of them, each costing the sum of its branches' taps + 1, all alike — position q goes to workgroup q mod G, and a
+// workgroup's list holds, per position, the nbr tile ids (branch-major, as conv_ws_body decodes them) in launch order: always an explicit list.
+// merge_wins: this launch is estimated to beat the side-by-side launches of the same layers (groups
+// of up to three, launch_n) by more than the folded mean costs the upsampler — its loader waves re-read (nbr - 1) further fp32 streams, at best
+// at the HBM's ~2 KB per cycle (the measured difference, profiles/r06a vs r06 by layer, is 1.5 x that) — so small launches stay side by side.
+static int build_merge_plan(hificar_engine* h, const ConvLayer* const* layers, int nbr, int nseq, int rows, hipStream_t stream, ConvPlan& pl) {
+    const ConvLayer& L0 = *layers[0];
+    MergeConvParams& mp = pl.merge;
+    double est_merged = 1e300, est_classic = 0.0;
+    const TileCfg tc_free = pick_tile(h, layers, nbr, nseq, rows, 1, true, &est_merged, false);
+    const TileCfg tc = pick_tile(h, layers, nbr, nseq, rows, 1, true);  // (a forced shape where the launch can run it)
+    if (est_merged >= 1e300) return fail(HIFICAR_E_INVALID, "internal: no tile shape for the merged launch of %s", L0.name.c_str());
+    for (int q0 = 0; q0 < nbr; q0 += 3) {
+        double e = 0.0;
+        (void)pick_tile(h, layers + q0, std::min(3, nbr - q0), nseq, rows, 1, false, &e, false);
+        est_classic += e;
+    }
+    const double up_extra = 4.0 * nseq * rows * L0.cout_total * (nbr - 1) / 2048.0;
+    // Two cases the estimate does not cover stay side by side (measured, profiles/r07_batch_sizes.txt): the halves of a batch on two streams (shared_chip:
+    // pick_tile does not simulate the walk there, and a third of the tiles leaves the other half's launches less to overlap with: batch 32 -2 %),
+    // and a merged launch that would need 32-row wave tiles to spread (MI = 1 re-streams the weights most often and a position's K loop is n times
+    // as long: batch 16 -0.15 %)
+    pl.merge_wins = !h->shared_chip && tc_free.MI > 1 && est_merged < est_classic + up_extra;
+    if (!pl.merge_wins && h->mrf_merge != 2) return HIFICAR_OK;  // (the plan only records the decision: no schedule for a launch that will not run)
+    int halo_all = 0;
+    for (int b = 0; b < nbr; ++b) halo_all = std::max(halo_all, layers[b]->off_max - layers[b]->off_min);
+    const int TM = tc.WM * tc.MI * 32, nc16 = L0.chunk16 / 16;
+    const size_t buf_bytes = round_up_sz((size_t)(TM + halo_all) * L0.chunk16 * 4, 1024);
+    pl.shape = {kConvF32mrg, tc.MI, tc.WM, tc.WN, nc16};
+    pl.lds = 2 * buf_bytes;
+    mp.buf_bytes = (int)buf_bytes;
+    mp.n_branches = nbr;
+    mp.nseq_tiles = nseq * ((rows + TM - 1) / TM);
+    mp.ngroups = (L0.n_blocks32 + tc.WN - 1) / tc.WN;
+    const int npos = mp.ngroups * mp.nseq_tiles;
+    mp.total_tiles = nbr * npos;
+    pl.grid = (unsigned)std::min(npos, h->num_cus);
+    mp.xcd_order = 0;
+    mp.stage_cached = mp.ngroups > 2 ? 1 : 0;
+    pl.name = plan_name(h, pl.shape, L0, nbr);
+    TileLists lists(pl.grid);
+    for (int q = 0; q < npos; ++q)
+        for (int b = 0; b < nbr; ++b) lists[(size_t)q % pl.grid].push_back(b * npos + q);
+    return upload_schedule(h, lists, mp.total_tiles, stream, &mp.sched_start, &mp.sched_tiles);
 }
 
 // Fused conv1 -> LeakyReLU -> conv2 (+ residual) for C = 32 / 64 (conv_pair_bf16x3_kernel / conv_pair_f32_kernel).
@@ -1386,9 +1461,9 @@ static int build_pair_plan(hificar_engine* h, const ConvLayer* const* l1, const 
 // touches vectors, strings or the arenas — on the launch's stream: a new schedule is uploaded on the stream that first needs it (publish()
 // in hificar_ar_loop).  Null: failed, *rc says how.
 static const ConvPlan* get_plan(hificar_engine* h, const ConvLayer* const* a, const ConvLayer* const* b, int nbr, int nseq, int rows, int zrep,
-                                hipStream_t stream, int* rc) {
+                                hipStream_t stream, int* rc, bool merged = false) {
     *rc = HIFICAR_OK;
-    PlanKey k = {{}, nseq, rows, zrep, (h->precision == HIFICAR_PREC_F32 ? 1 : 0) | (h->training ? 2 : 0) | (h->shared_chip ? 4 : 0) | (b ? 8 : 0)};
+    PlanKey k = {{}, nseq, rows, zrep, (h->precision == HIFICAR_PREC_F32 ? 1 : 0) | (h->training ? 2 : 0) | (h->shared_chip ? 4 : 0) | (b ? 8 : 0) | (merged ? 16 : 0)};
     for (int i = 0; i < nbr; ++i) k.layers[i] = a[i];
     for (int i = 0; b && i < nbr; ++i) k.layers[3 + i] = b[i];
     auto it = h->plans.find(k);
@@ -1396,7 +1471,9 @@ static const ConvPlan* get_plan(hificar_engine* h, const ConvLayer* const* a, co
         ConvPlan pl;
         if (h->plans.size() > 20000) *rc = evict_plans(h);  // (a very large number of distinct launch shapes: start over)
         if (*rc == HIFICAR_OK)
-            *rc = b ? build_pair_plan(h, a, b, nbr, nseq, rows, stream, pl) : build_conv_plan(h, a, nbr, nseq, rows, zrep, stream, pl);
+            *rc = merged ? build_merge_plan(h, a, nbr, nseq, rows, stream, pl)
+                  : b    ? build_pair_plan(h, a, b, nbr, nseq, rows, stream, pl)
+                         : build_conv_plan(h, a, nbr, nseq, rows, zrep, stream, pl);
         if (*rc != HIFICAR_OK) return nullptr;
         it = h->plans.emplace(k, std::move(pl)).first;
     }
@@ -1456,6 +1533,38 @@ static int launch_conv(hificar_engine* h, const ConvLayer* const* layers, int nb
     ProfScope prof(h, stream, pl->name, flops, bytes);
     const hipError_t e = conv_launch(pl->shape, &mp, dim3(pl->grid, 1, 1), pl->lds, stream);
     if (e != hipSuccess) return fail(HIFICAR_E_HIP, "conv launch (%s, %s) failed: %s", L0.name.c_str(), pl->name.c_str(), hipGetErrorString(e));
+    return HIFICAR_OK;
+}
+
+// The branch-summing launch of layers[0 .. nbr) (2 to 4 blocks): branch b reads the activated rows io[b].xs and adds the residual io[b].res; the one
+// output, LeakyReLU(mean of the blocks' outputs, slope_out), goes to ys_out — a buffer no branch reads.  No block's own output is written.
+static int launch_merged(hificar_engine* h, const ConvPlan* pl, const ConvLayer* const* layers, int nbr, int nseq, int rows, const ConvIO* io, char* ys_out,
+                         float slope_out, const Ragged& rg, hipStream_t stream) {
+    const int TM = pl->shape.wm * pl->shape.mi * 32;
+    const ConvLayer& L0 = *layers[0];
+    MergeConvParams mp = pl->merge;
+    double flops = 0.0, bytes = 0.0;
+    const double pos = (double)nseq * rows;
+    for (int b = 0; b < nbr; ++b) {
+        const ConvLayer& Lb = *layers[b];
+        if (Lb.n_blocks32 != L0.n_blocks32 || Lb.chunk16 != L0.chunk16 || Lb.cin_pad != L0.cin_pad || Lb.cout_total != L0.cout_total || Lb.n_phase != 1 ||
+            !io[b].res || !io[b].xs || io[b].xs == ys_out)
+            return fail(HIFICAR_E_INVALID, "internal: merged launch of %s: branch %d does not fit", L0.name.c_str(), b);
+        fill_params(mp.p[b], Lb, rows, TM, io[b].res, nullptr, rg);
+        mp.p[b].xs = io[b].xs;
+        mp.p[b].ys = ys_out;
+        mp.p[b].zeros = h->d_zeros;
+        mp.p[b].slope_out = slope_out;
+        mp.p[b].cout_real = Lb.cout_pad;
+        mp.p[b].w16 = reinterpret_cast<const bf16x8*>(Lb.d_w32);
+        flops += 2.0 * pos * Lb.cin * Lb.cout * Lb.K;
+        bytes += 4.0 * (pos * Lb.cin_pad + pos * Lb.cout_total + (double)Lb.cin * Lb.cout * Lb.K);  // input, residual, weights
+    }
+    bytes += 4.0 * pos * L0.cout_total;  // the one output
+    mp.zrep = 1;
+    ProfScope prof(h, stream, pl->name, flops, bytes);
+    const hipError_t e = conv_launch(pl->shape, &mp, dim3(pl->grid, 1, 1), pl->lds, stream);
+    if (e != hipSuccess) return fail(HIFICAR_E_HIP, "merged conv launch (%s, %s) failed: %s", L0.name.c_str(), pl->name.c_str(), hipGetErrorString(e));
     return HIFICAR_OK;
 }
 
@@ -1664,6 +1773,7 @@ struct FwdState {
     BlockOrder bo;
     int rows = 0;               // rows per sequence at the current stage
     const float* fin[kMaxBlk];  // where each branch's ResBlock output of the current stage lives
+    const char* mrf_act = nullptr;  // the current stage's last ResBlock launch summed the branches (launch_merged): the ACTIVATED MRF mean, and fin is not written
     bool tapping = false;
     bool tap_convs1 = false;    // a conv1 output is wanted: those pairs run layer by layer (the fused kernel keeps it in LDS)
     size_t tap_se = 0;
@@ -1814,6 +1924,20 @@ static int resblocks_all_pairs(hificar_handle* h, const FwdCall& k, FwdState& fs
     return HIFICAR_OK;
 }
 
+// Whether stage i's last ResBlock launch may sum the branches (launch_merged) as far as the call decides it: exact fp32 inference without tape or taps
+// (a tap wants the blocks' own outputs), not the last stage (the output conv and the phoneme head read the blocks' outputs), two blocks or more that
+// all end at the same dilation, conv2 layers.  Off with HIFICAR_PAIR=0 (layer by layer: no fused launch forms), with HIFICAR_KSPLIT=0 (the batch-invariant
+// mode: one accumulation order at every launch size — whether the merged form runs depends on the size, and it rounds differently), with
+// HIFICAR_KSPLIT=2 (every launch split-K: the merged form has no such variant) and with HIFICAR_MRF_MERGE=0.  The rest — the pair of that dilation does not fuse, the planner's estimate — is resblocks_general's, at the launch.
+static bool mrf_merge_allowed(const hificar_handle* h, const FwdCall& k, const FwdState& fs, int i) {
+    const hificar_config& cfg = h->cfg;
+    if (h->precision != HIFICAR_PREC_F32 || k.tp || fs.tapping || i + 1 >= cfg.n_stages || cfg.n_blocks < 2 || !cfg.use_additional_convs) return false;
+    if (h->mrf_merge == 0 || !h->use_pair || h->ksplit != 1) return false;  // (HIFICAR_KSPLIT=2, "always split-K": the merged form is dense)
+    for (int j = 0; j < cfg.n_blocks; ++j)
+        if (cfg.n_dilations[j] != fs.bo.max_d) return false;
+    return true;
+}
+
 // ResBlock layers of any other stage: activated copies ("_s") travel next to the fp32 stream; a dilation's pairs still fuse where they all can.
 // u_act: the upsampler's activated output
 static int resblocks_general(hificar_handle* h, const FwdCall& k, FwdState& fs, int i, const char* u_act) {
@@ -1832,6 +1956,7 @@ static int resblocks_general(hificar_handle* h, const FwdCall& k, FwdState& fs, 
     // activated stream of each branch: where the next conv1 reads its input.  It alternates between x_s[j] and
     // xt_s[j]: a launch never writes the buffer it (or a neighbouring tile, through the halo) reads.
     const char* cur_s[kMaxBlk] = {u_act, u_act, u_act, u_act};
+    const bool may_merge = mrf_merge_allowed(h, k, fs, i);
     for (int d = 0; d < fs.bo.max_d; ++d) {  // residual_block.py:217-221
         const ConvLayer* l1[kMaxBlk];
         const ConvLayer* l2[kMaxBlk];
@@ -1874,7 +1999,17 @@ static int resblocks_general(hificar_handle* h, const FwdCall& k, FwdState& fs, 
                     if ((rc = emit_tap(h, "blocks." + std::to_string(i * nbk + br.j[q]) + ".convs1." + std::to_string(d), io1[q].y, Cp, 0, Cs,
                                        B, rows, 0, k.stream)) != HIFICAR_OK)
                         return rc;
-            if (add_convs && (rc = launch_n(h, l2, nullptr, br.n, B, rows, io2, nullptr, cfg.lrelu_slope, fs.rg, k.stream)) != HIFICAR_OK) return rc;
+            // the stage's last launch: all blocks summed in one accumulator, the activated MRF mean as the only output (launch_merged) — into
+            // branch 0's free ping-pong buffer, which no launch reads any more — where the plan's estimate (or HIFICAR_MRF_MERGE=2) says so
+            const ConvPlan* mpl = nullptr;
+            if (may_merge && d + 1 == fs.bo.max_d && br.n == nbk) {
+                if (!(mpl = get_plan(h, l2, nullptr, br.n, B, rows, 1, k.stream, &rc, true))) return rc;
+                if (!mpl->merge_wins && h->mrf_merge != 2) mpl = nullptr;
+            }
+            if (mpl) {
+                if ((rc = launch_merged(h, mpl, l2, br.n, B, rows, io2, lbl_out[0], cfg.lrelu_slope, fs.rg, k.stream)) != HIFICAR_OK) return rc;
+                fs.mrf_act = lbl_out[0];
+            } else if (add_convs && (rc = launch_n(h, l2, nullptr, br.n, B, rows, io2, nullptr, cfg.lrelu_slope, fs.rg, k.stream)) != HIFICAR_OK) return rc;
         }
         for (int q = 0; q < br.n; ++q)
             if ((rc = tap_block(h, k, fs, i, br.j[q], d, xres[br.j[q]])) != HIFICAR_OK) return rc;
@@ -1893,8 +2028,12 @@ static int forward_stage(hificar_handle* h, const FwdCall& k, FwdState& fs, int 
     // MRF mean of the previous stage (hifigan.py:226-230).  Exact fp32 inference: folded into the upsampler's staging (ConvIO::x_more — its
     // loader waves read the blocks' fp32 streams, sum, divide, activate), so no launch and no buffer for the mean exist.  Training (the tape keeps
     // the activated mean for the upsampler's weight gradient) and bf16x3 (split rows): mrf_split_kernel.
-    const bool fold_mrf = i > 0 && h->precision == HIFICAR_PREC_F32 && !tp;
-    if (i > 0 && !fold_mrf && (rc = launch_mrf_split(h, k, fs, i, &up_in)) != HIFICAR_OK) return rc;
+    // Where the previous stage's last launch summed the blocks itself (launch_merged) the upsampler reads that one activated stream by LDS-DMA.
+    const char* const merged_in = fs.mrf_act;
+    fs.mrf_act = nullptr;
+    const bool fold_mrf = i > 0 && h->precision == HIFICAR_PREC_F32 && !tp && !merged_in;
+    if (merged_in) up_in = merged_in;
+    if (i > 0 && !fold_mrf && !merged_in && (rc = launch_mrf_split(h, k, fs, i, &up_in)) != HIFICAR_OK) return rc;
     // Whether every layer pair of the stage runs in the fused kernel (resblocks_all_pairs) or not (resblocks_general)
     bool all_pairs = !fs.tap_convs1 && !tp && cfg.use_additional_convs != 0;
     for (int j = 0; j < nbk && all_pairs; ++j)

@@ -15,6 +15,7 @@
 // Two arithmetics on one persistent, wave-specialised, LDS-DMA-staged kernel body:
 //   conv_f32do_kernel          exact fp32 products (v_mfma_f32_32x32x2_f32), plain fp32 rows, tiles stored straight from the accumulators
 //   conv_bf16x3(nb)_kernel     fp32 operands split hi+lo bf16, 3 x v_mfma_f32_32x32x16_bf16 per K slab; "split rows"
+//   conv_f32mrg_kernel         the branch-summing form of conv_f32do_kernel: a stage's last ResBlock layers of all blocks in one accumulator -> the activated MRF mean
 //   conv_sk_{f32,bf16x3}_kernel  split-K forms of both for launches with few tiles
 //   conv_pair_{f32,bf16x3}_kernel  fuse conv1 -> conv2 of a ResBlock layer pair at C <= 64
 // plus front_kernel (PastFCEncoder + input assembly), mrf_split_kernel (MRF mean + split), output_conv_kernel.
@@ -125,8 +126,9 @@ __device__ __forceinline__ int seq_rows(const ConvParams& p, int seq) {
     return min(max(n, 0), p.len_max) * p.len_mul;
 }
 
-struct MultiConvParams {
-    ConvParams p[3];
+template <int NBR>
+struct MultiConvParamsN {
+    ConvParams p[NBR];
     // persistent-tile bookkeeping (wave-specialised kernel): tiles are numbered branch-major (heaviest branch
     // first), then channel group, then (sequence, time tile); workgroup w takes tiles w, w + gridDim.x, ...
     int n_branches;
@@ -148,6 +150,9 @@ struct MultiConvParams {
                        // of a wide layer: the ten groups of upsampler 0, the eight of a 1024-wide discriminator GEMM), so the re-reads should hit
                        // the L2.  0: non-temporal (a row is staged by one or two CUs only: +2.3 % end to end on the ResBlock launches)
 };
+struct MultiConvParams : MultiConvParamsN<3> {};
+// the branch-summing launch (conv_f32mrg_kernel): all residual blocks of a stage, up to four, in ONE launch
+struct MergeConvParams : MultiConvParamsN<4> {};
 
 
 #ifdef HIFICAR_TRACE
@@ -255,9 +260,10 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // slots during the K loop (and the waits at the out-buffer hand-over barriers) for an epilogue the matrix pipe idles through: +1.5 % end to end (37.41 -> 37.96 M).
 // Round 5: in this form the operands are SWAPPED — D = X * W^T, activations as the A operand, same products in the same order — so that a lane owns ONE channel and
 // 16 rows per 32 x 32 block and a 4-byte wave-store writes two whole 128-byte rows (kRowMajorAcc / epilogue_rm below; 38.4 -> 39.6 M with the waits around it removed).
-template <int MI, int WM, int WN, int NC16, bool F32, int KS = 1, int NB = 1, bool DOUT = false>
-__device__ __forceinline__ void conv_ws_body(const MultiConvParams& mp) {
+template <int MI, int WM, int WN, int NC16, bool F32, int KS = 1, int NB = 1, bool DOUT = false, bool MRG = false, class MP = MultiConvParams>
+__device__ __forceinline__ void conv_ws_body(const MP& mp) {
     static_assert(!DOUT || (F32 && KS == 1 && NB == 1), "direct output: exact fp32, dense form, one channel block per wave");
+    static_assert(!MRG || DOUT, "branch-summing form: a direct-output kernel");
     static_assert(NB == 1 || (NB == 2 && KS == 1), "one or two channel blocks per MFMA wave");
     static_assert(KS == 1 || (KS == 4 && WM == 1 && WN == 1), "split-K: four waves share one 32-channel block");
     static_assert(KS == 4 || WM * WN == 4 || WM * WN == 8, "4 or 8 MFMA waves per workgroup");
@@ -326,7 +332,8 @@ __device__ __forceinline__ void conv_ws_body(const MultiConvParams& mp) {
                                          : (mp.total_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
     auto tile_of = [&](int it) {
         int i = it;
-        if ((blockIdx.x & 1) && my_rounds >= 3 && it >= my_rounds - 2) i = it == my_rounds - 1 ? my_rounds - 2 : my_rounds - 1;
+        // (MRG: the branches of a position are consecutive list entries and stay so)
+        if (!MRG && (blockIdx.x & 1) && my_rounds >= 3 && it >= my_rounds - 2) i = it == my_rounds - 1 ? my_rounds - 2 : my_rounds - 1;
         if (mp.sched_start) return scalar_load_i32(mp.sched_tiles + sched_lo + i);
         if (mp.xcd_order) {
             // one tile per workgroup, weights outweigh activations (small batches, the discriminators' few-row GEMMs): workgroups are
@@ -825,6 +832,67 @@ __device__ __forceinline__ void conv_ws_body(const MultiConvParams& mp) {
             }
         }
     };
+    // Branch-summing form (MRG): the epilogue of one POSITION, after the K loops of all its n branches have run into the same accumulators.  Per element
+    //     m = ((((acc + bias_sum) + res_0) + res_1) + ... + res_{n-1}) / (float)n,     bias_sum = ((bias_0 + bias_1) + ...) in launch order,
+    //     ys = LeakyReLU(m, slope_out)
+    // where acc holds the products of branch 0's taps, then branch 1's, ... in K-loop order and res_b is branch b's residual stream: the MRF mean
+    // (hifigan.py:226-230) of the blocks' outputs y_b = conv_b + bias_b + res_b, activated for the next upsampler.  The layer-by-layer path rounds every
+    // y_b to fp32 and computes ((y_0 + y_1) + y_2) / n: the two agree to fp32 rounding, not bit for bit.  The order does not depend on the tile shape.
+    // The only output is the activated stream p[0].ys; rows past a sequence's end fall outside the buffer ranges, as in epilogue_rm.
+    auto epilogue_mrg = [&](const Tile& T, int nb, int rows_valid, const float (&bias_b)[4]) {
+        if constexpr (MRG) {
+            const ConvParams& p = mp.p[0];  // (row pitch, rows and sequence length are the same in every branch)
+            const int rows_w = __builtin_amdgcn_readfirstlane(max(min(rows_valid - wave_row0, MI * 32), 0));
+            const unsigned pitch_b = __builtin_amdgcn_readfirstlane((unsigned)p.cout_total * 4u);
+            const size_t first = ((size_t)T.seq * p.L + T.t0 + wave_row0) * p.cout_total;
+            auto uni64 = [](unsigned long long v) {
+                const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+                return ((unsigned long long)hi << 32) | lo;
+            };
+            const unsigned long long b_ys = uni64((unsigned long long)(reinterpret_cast<float*>(p.ys) + first));
+            auto rsrc_of = [&](unsigned long long base, int mi) {  // row block mi of an operand
+                const unsigned rows = (unsigned)max(min(rows_w - mi * 32, 32), 0);
+                return __builtin_amdgcn_make_buffer_rsrc((void*)uni64(base + (unsigned long long)(mi * 32) * pitch_b), 0,
+                                                         __builtin_amdgcn_readfirstlane(rows * pitch_b), 0x00020000);
+            };
+            const int voff = (int)((4u * g * p.cout_total + nb * 32 + li) * 4u);  // (row 4 g, this lane's channel)
+            int off16[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) off16[r] = voff + (int)((8 * (r >> 2) + (r & 3)) * pitch_b);
+            const float slope_out = p.slope_out;
+            auto pass = [&](auto NBR) {
+                constexpr int N = decltype(NBR)::value;
+                float bias_sum = bias_b[0];
+#pragma unroll
+                for (int b = 1; b < N; ++b) bias_sum += bias_b[b];
+                unsigned long long b_res[N];
+#pragma unroll
+                for (int b = 0; b < N; ++b) b_res[b] = uni64((unsigned long long)(mp.p[b].res + first));
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi) {
+                    float rs[N][16];
+#pragma unroll
+                    for (int b = 0; b < N; ++b)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            rs[b][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc_of(b_res[b], mi), off16[r], 0, 0));
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float m = acc[0][mi][r] + bias_sum;
+#pragma unroll
+                        for (int b = 0; b < N; ++b) m += rs[b][r];
+                        m = m / (float)N;
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, __builtin_amdgcn_fmed3f(m, m * slope_out, __builtin_inff())),
+                                                              rsrc_of(b_ys, mi), off16[r], 0, 0);
+                    }
+                }
+            };
+            const int n = mp.n_branches;
+            if (n == 3) pass(std::integral_constant<int, 3>{});
+            else if (n == 2) pass(std::integral_constant<int, 2>{});
+            else pass(std::integral_constant<int, 4>{});
+        }
+    };
     auto bias_of = [&](const Tile& T) {
         const int nb = (T.ng * WN + wn) * NB;
         return (mp.p[T.b].bias + (size_t)T.z * mp.zs_b)[(nb < mp.p[T.b].n_blocks32 ? nb : 0) * 32 + li];
@@ -973,17 +1041,29 @@ __device__ __forceinline__ void conv_ws_body(const MultiConvParams& mp) {
         }
         // Direct output with transposed accumulators: a lane owns ONE channel, so the accumulators start at its bias (one value per lane for all MI x 16
         // registers) and the epilogue has no bias to add or wait for; the NEXT tile's value is requested now and arrives behind this tile's K loop.
+        // (MRG: the branches of a position accumulate into the same registers — zeroed at its first branch only, no epilogue in between)
+        if (!MRG || T.b == 0) {
 #pragma unroll
-        for (int q = 0; q < NB; ++q)
+            for (int q = 0; q < NB; ++q)
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
+                for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[q][mi][r] = 0.f;
+                    for (int r = 0; r < 16; ++r) acc[q][mi][r] = 0.f;
+        }
         // (kRowMajorAcc) this lane's bias, requested here and first used in the epilogue: the load has the whole K loop to arrive.  (Requested a tile
         // ahead and folded into the accumulators' start value it costs more than it saves: hipcc waits for the loop-carried load with a vmcnt that
         // also sits out every store of the previous tile's epilogue.)  A wave without a channel block of its own reads block 0's and never uses it.
         float bias_l = 0.f;
-        if constexpr (kRowMajorAcc) bias_l = bias_of(T);
+        float bias_b[4] = {0.f, 0.f, 0.f, 0.f};  // (MRG) every branch's bias of this lane's channel, requested in front of the position's last K loop
+        (void)bias_b;
+        const bool last_branch = !MRG || T.b == mp.n_branches - 1;
+        if constexpr (MRG) {
+            if (last_branch) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    if (b < mp.n_branches) bias_b[b] = mp.p[b].bias[(nb < p.n_blocks32 ? nb : 0) * 32 + li];
+            }
+        } else if constexpr (kRowMajorAcc) bias_l = bias_of(T);
 
         for (int c = 0; c < nchunks; ++c, ++j) {
             HIFICAR_STAMP(1 + 3 * j);
@@ -1061,7 +1141,9 @@ __device__ __forceinline__ void conv_ws_body(const MultiConvParams& mp) {
         }
         HIFICAR_STAMP(3 * j);
         primed = active;  // (!kPrimeOnce) an active tile ends with the ring holding the next tile's head
-        if constexpr (kRowMajorAcc) {
+        if constexpr (MRG) {
+            if (active && last_branch) epilogue_mrg(T, nb, rows_valid_t, bias_b);
+        } else if constexpr (kRowMajorAcc) {
             if (active) epilogue_rm(T, p, nb, rows_valid_t, bias_l);
         } else if (active) {
             // hand the raw accumulators to the loader waves through the LDS out-buffer O[time row][channel]:
@@ -1092,6 +1174,14 @@ __device__ __forceinline__ void conv_ws_body(const MultiConvParams& mp) {
 template <int MI, int WM, int WN, int NC16>
 __global__ __launch_bounds__((WM * WN + 4) * 64) void conv_f32do_kernel(const MultiConvParams mp) {
     conv_ws_body<MI, WM, WN, NC16, true, 1, 1, true>(mp);
+}
+
+// branch-summing form (MRG) of the direct-output kernel: the last ResBlock layers of all blocks of a stage in one launch, whose output is the activated
+// MRF mean (epilogue_mrg).  The host's tile list gives every workgroup whole positions: the n branches of a (sequence, row tile, channel group), in launch
+// order, as consecutive entries (build_merge_plan, hificar.hip).
+template <int MI, int WM, int WN, int NC16>
+__global__ __launch_bounds__((WM * WN + 4) * 64) void conv_f32mrg_kernel(const MergeConvParams mp) {
+    conv_ws_body<MI, WM, WN, NC16, true, 1, 1, true, true>(mp);
 }
 
 template <int MI, int WM, int WN, int NC16>

@@ -1,16 +1,17 @@
 // Instantiation sets of the conv engine's kernel templates (hificar_conv.hip.h).  This file is compiled once per set with
-// -DHIFICAR_INST_SET=n (the Makefile builds the ten objects in parallel; one translation unit with all of them took four minutes):
+// -DHIFICAR_INST_SET=n (the Makefile builds the thirteen objects in parallel; one translation unit with all of them took four minutes):
 //   0 / 1 / 2   conv_f32do_kernel, K chunks of 16 / 32 / 64 channels        (9 tile shapes each)
 //   3 / 4 / 5   conv_bf16x3_kernel, the same
 //   6           conv_bf16x3nb_kernel                                         (6 shapes)
 //   7 / 8       conv_sk_f32_kernel / conv_sk_bf16x3_kernel                   (9 shapes each)
 //   9           conv_pair_f32_kernel (3 shapes), conv_pair_bf16x3_kernel (2)
+//   10 / 11 / 12  conv_f32mrg_kernel (the branch-summing form of conv_f32do_kernel), K chunks of 16 / 32 / 64 channels  (9 tile shapes each)
 // Each set exports conv_inst_launch_<n> / conv_inst_attrs_<n> (hificar_launch.h); hificar.hip dispatches over them.
 #include "hificar_conv.hip.h"
 #include "hificar_launch.h"
 
 #ifndef HIFICAR_INST_SET
-#error "compile with -DHIFICAR_INST_SET=0..9"
+#error "compile with -DHIFICAR_INST_SET=0..12"
 #endif
 
 namespace hificar {
@@ -66,6 +67,17 @@ namespace hificar {
 #define THREADS(wm, wn) 512
 #define PARAMS MultiConvParams
 #define SHAPES(X) X(1, 1, 1, 1) X(2, 1, 1, 1) X(4, 1, 1, 1) X(1, 1, 1, 2) X(2, 1, 1, 2) X(4, 1, 1, 2) X(1, 1, 1, 4) X(2, 1, 1, 4) X(4, 1, 1, 4)
+#elif HIFICAR_INST_SET >= 10 && HIFICAR_INST_SET <= 12
+#define FAMILY kConvF32mrg
+#define KERNEL conv_f32mrg_kernel
+#define PARAMS MergeConvParams
+#if HIFICAR_INST_SET == 10
+#define SHAPES(X) HIFICAR_TILES9(X, 1)
+#elif HIFICAR_INST_SET == 11
+#define SHAPES(X) HIFICAR_TILES9(X, 2)
+#else
+#define SHAPES(X) HIFICAR_TILES9(X, 4)
+#endif
 #elif HIFICAR_INST_SET == 9
 #define PARAMS PairParams
 #define THREADS(wm, wn) 512
