@@ -125,6 +125,7 @@ SYMBOLS = (
     "hificar_xfmr_tape_bytes",
     "hificar_xfmr_train_workspace_bytes",
     "hificar_xfmr_forward_train",
+    "hificar_xfmr_forward_train_ragged",
     "hificar_xfmr_backward",
     "hificar_destroy",
     "hificar_last_error",
@@ -528,6 +529,9 @@ def load_library():
     lib.hificar_xfmr_train_workspace_bytes.restype = cs
     lib.hificar_xfmr_forward_train.argtypes = [vp, vp, vp, vp, ci, ci, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp, cs, vp, cs, vp]
     lib.hificar_xfmr_forward_train.restype = ci
+    lib.hificar_xfmr_forward_train_ragged.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp, cs, vp,
+                                                      cs, vp]
+    lib.hificar_xfmr_forward_train_ragged.restype = ci
     lib.hificar_xfmr_backward.argtypes = [vp, vp, ci, ci, vp, cs, vp, vp, vp, cs, vp]
     lib.hificar_xfmr_backward.restype = ci
     lib.hificar_destroy.argtypes = [vp]

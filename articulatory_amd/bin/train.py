@@ -558,9 +558,10 @@ class FrameWindowCollater:
 
 
 class PadCollater:
-    """``package_mode: pad`` (the reference's key, train.py:909-913, 1036-1063): whole utterances, zero-padded to the batch's longest ->
+    """``package_mode: pad`` (the reference's key, train.py:909-913, 1036-1063) and ``pad_masked``: whole utterances, zero-padded to the batch's longest ->
     {"x": (B, Cin, T), "y": (B, Cout, T), "lengths": (B,) int32}.  Unlike the reference, which trains on the padding as if it were speech,
-    the padded frames take no part in the batch statistics, the loss or the gradients (``BiGRU.forward_padded`` + ``masked_l1_loss``).
+    the padded frames take no part in the batch statistics, the loss or the gradients (``forward_padded`` of the BiGRU and the Transformer +
+    ``masked_l1_loss``).
     ``pad_max_frames`` (this package's key, optional): a longer utterance is cut to a random window of that many frames."""
 
     def __init__(self, pad_max_frames=None, seed=None):
@@ -630,7 +631,8 @@ class LengthBucketBatchSampler(torch.utils.data.Sampler):
         return sum(min(self.pool, n - p) // self.batch_size for p in range(0, n, self.pool))
 
 
-PACKAGE_MODES = ("random_window", "pad")
+PACKAGE_MODES = ("random_window", "pad", "pad_masked")
+PADDED_MODES = ("pad", "pad_masked")  # whole utterances with their lengths (PadCollater)
 
 
 INVERSION_TYPES = ("BiGRU", "Transformer")  # the feature-to-feature models InversionTrainer builds
@@ -644,7 +646,8 @@ class InversionTrainer:
 
     ``package_mode: pad`` (batches of ``PadCollater``: whole utterances with their lengths): the step is ``forward_padded`` ->
     ``masked_l1_loss`` * lambda_aux, the rest as above; the padding takes no part in statistics, loss or gradients (the reference's pad mode
-    trains on it); BiGRU only — ragged Transformer training is not built.  ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval
+    trains on it).  ``package_mode: pad_masked`` (this package's key) is the same step under a name that says what it does; it is the way
+    in for the Transformer, for which ``pad`` stays refused.  ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval
     mode, under ``masked_l1_loss``."""
 
     def __init__(self, config, device):
@@ -669,8 +672,10 @@ class InversionTrainer:
         if self.package_mode not in PACKAGE_MODES:
             raise NotImplementedError(f"package_mode {self.package_mode!r} is not built for inversion models (one of {' / '.join(PACKAGE_MODES)})")
         if self.package_mode == "pad" and gtype != "BiGRU":
-            raise NotImplementedError(f"package_mode pad is not built for generator_type {gtype} (ragged training exists for the BiGRU only; "
-                                      "use package_mode random_window)")
+            raise NotImplementedError(f"package_mode pad is not built for generator_type {gtype}: the reference's pad trains on its padding, "
+                                      "this package masks it; ask for that by name with package_mode pad_masked (ragged training on whole "
+                                      "utterances), or use package_mode random_window")
+        self.padded = self.package_mode in PADDED_MODES
         import articulatory_amd.models as models
 
         self.G = getattr(models, gtype)(**config["generator_params"]).to(device).train()
@@ -686,10 +691,10 @@ class InversionTrainer:
         x = batch["x"].to(self.device, non_blocking=True)
         y = batch["y"].to(self.device, non_blocking=True)
         log = {}
-        if self.package_mode == "pad" and "lengths" not in batch:
-            raise ValueError(f"package_mode pad: the batch has no lengths (batch keys {sorted(batch)}); build it with PadCollater")
+        if self.padded and "lengths" not in batch:
+            raise ValueError(f"package_mode {self.package_mode}: the batch has no lengths (batch keys {sorted(batch)}); build it with PadCollater")
         if self.steps > cfg.get("generator_train_start_steps", 0):  # train.py:268
-            if self.package_mode == "pad":
+            if self.padded:
                 y_ = self.G.forward_padded(x, batch["lengths"])
                 mel_loss = masked_l1_loss(y_, y, batch["lengths"])
             else:
@@ -770,7 +775,7 @@ class InversionTrainer:
 def _main_inversion(a, config, device, rank):
     """``main`` for generator_type BiGRU / Transformer: input / target ``.npy`` scp pairs (--feats-scp: the model's input side, --audio-scp: its target
     side; dataset_mode m2a swaps them) or --synthetic N, cut into equal windows of batch_max_frames + 2 aux_context_window frames
-    (package_mode random_window, the default) or taken whole in length-bucketed, zero-padded batches (package_mode pad; config keys
+    (package_mode random_window, the default) or taken whole in length-bucketed, zero-padded batches (package_mode pad or pad_masked; config keys
     pad_max_frames, pad_bucket_batches; --synthetic then draws each utterance's length uniformly from one to four windows).
     --dev-feats-scp / --dev-audio-scp: a dev set, evaluated whole every eval_interval_steps in either mode."""
     gp = config["generator_params"]
@@ -778,7 +783,7 @@ def _main_inversion(a, config, device, rank):
     ctx = int(config.get("aux_context_window", gp.get("aux_context_window", 0)))
     frames = config["batch_max_steps"] // hop  # CollaterMelArt: batch_max_frames
     window = frames + 2 * ctx
-    pad = config.get("package_mode", "random_window") == "pad"
+    pad = config.get("package_mode", "random_window") in PADDED_MODES
     swap = config.get("dataset_mode") == "m2a"
     if a.synthetic:
         data = WindowPairs(synthetic=a.synthetic, frames=4 * window, dims=(gp.get("in_channels", 80), gp.get("out_channels", 1)), seed=rank,

@@ -85,8 +85,18 @@ __device__ __forceinline__ void xfmr_stage(float* dst, const float* src, size_t 
     }
 }
 
+// lane (c, g)'s share of one head's D floats of a row, as the attention kernels write it (columns 16 j + 4 g .. + 3), as zeros: the rows of
+// padded frames (q < T at or past the sequence's length), which the GEMMs over all B T rows read
+template <int D>
+__device__ __forceinline__ void xfmr_zero_head_row(float* row4g, bool in_tensor) {
+    if (!in_tensor) return;
+#pragma unroll
+    for (int j = 0; j < D / 16; ++j) *reinterpret_cast<float4*>(row4g + 16 * j) = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
 // TRAIN (the training forward): the kept probabilities are scaled by the dropout factor before P V (the denominator sums all of them, as
-// F.softmax followed by nn.Dropout does) and L = m + log l is kept per query.  The eval instantiation compiles none of it.
+// F.softmax followed by nn.Dropout does), L = m + log l is kept per query, and the `out` rows of padded frames are written as zeros (a
+// workgroup whose 64 queries are all padded writes them and returns).  The eval instantiation compiles none of it.
 template <int D, bool TRAIN = false>
 __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) {
     extern __shared__ float xfmr_lds[];
@@ -98,11 +108,14 @@ __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) 
     const int c = lane & 15, g = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kXfmrTQ;
     const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
-    if (q0 >= len) return;  // (the whole workgroup: no barrier has been reached)
     const size_t row0 = (size_t)b * p.T;
     const size_t F3 = (size_t)3 * p.F;
     const int qw = q0 + wave * 16, q = qw + c;
     const bool qok = q < len;
+    if (q0 >= len) {  // (the whole workgroup: no barrier has been reached, nothing staged)
+        if constexpr (TRAIN) xfmr_zero_head_row<D>(p.out + (row0 + q) * p.F + h * D + 4 * g, q < p.T);
+        return;
+    }
 
     // this lane's B operands of every product: Q[q][4 s + g]
     float qf[NS];
@@ -213,7 +226,11 @@ __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) 
             }
         }
     }
-    if (!qok) return;
+    if (!qok) {
+        // (training: w_o's GEMM and its weight gradient read every row of `out`; a padded frame's is zeros)
+        if constexpr (TRAIN) xfmr_zero_head_row<D>(p.out + (row0 + q) * p.F + h * D + 4 * g, q < p.T);
+        return;
+    }
     const float inv = 1.f / l;  // (l >= 1: the query's own key is in its band)
     if constexpr (TRAIN) {
         if (g == 0) p.lse[((size_t)b * kXfmrHeads + h) * p.T + q] = m + logf(l);
@@ -227,7 +244,7 @@ __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) 
 // ---------------------------------------------------------------------------------------------------------------------------
 // LayerNorm(F) (eps 1e-5, biased variance; torch.nn.LayerNorm, pytorch_layers.py:155-156): one wave per row, one pass over memory — the row
 // lives in registers between the two reductions (mean, then squared deviations), whose lanes are joined in a fixed order.  F <= 1024, a
-// multiple of 4.  Rows at or past a sequence's length are left alone.  x and y may be the same buffer.
+// multiple of 4.  Rows at or past a sequence's length are left alone (zero_pad: written as zeros).  x and y may be the same buffer.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct XfmrLnParams {
     const float* x;
@@ -236,6 +253,7 @@ struct XfmrLnParams {
     const int* lengths;  // device, or null
     float* y;
     int B, T, F;
+    int zero_pad = 0;  // 1 (the ragged training step): rows at or past a length are written as zeros
 };
 
 __device__ __forceinline__ float xfmr_wave_sum(float v) {
@@ -250,8 +268,12 @@ __global__ __launch_bounds__(256) void xfmr_ln_kernel(const XfmrLnParams p) {
     if (row >= (long long)p.B * p.T) return;
     const int b = (int)(row / p.T), t = (int)(row - (long long)b * p.T);
     const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
-    if (t >= len) return;
     const int nv = p.F >> 2;
+    if (t >= len) {
+        if (p.zero_pad)
+            for (int i = lane; i < nv; i += 64) reinterpret_cast<float4*>(p.y + row * p.F)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
     const float4* x = reinterpret_cast<const float4*>(p.x + row * p.F);
     float4 v[4];
     float sum = 0.f;

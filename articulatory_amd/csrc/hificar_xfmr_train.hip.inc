@@ -6,7 +6,12 @@
 //   backward  the same walked from the end: LayerNorm / dropout / ReLU masks elementwise, the attention's three kernels, BatchNorm's sums
 //             and input gradient; every GEMM's data gradient is a conv-engine launch on its transposed pack, every weight and bias
 //             gradient a launch of the weight-gradient kernels of hificar_train.hip.inc.
-// Equal-length batches only.  Kernels: hificar_xfmr_train_kernels.hip.h.
+// Ragged batches (hificar_xfmr_forward_train_ragged): the tape keeps the frame counts and M, the number of valid frames.  Every GEMM, conv,
+// data gradient and weight gradient still runs over all B T rows; what makes that right is a rule about buffers: every buffer of rows that
+// such a launch reads is written by this call on every row, and on the rows of padded frames either as zeros (the outputs of the row-wise
+// kernels and of the attention kernels: a k = 3 conv then sees zero padding at a sequence's own end, and a weight gradient adds 0 * finite)
+// or as the finite output of a GEMM over such rows, which only a row-wise kernel or a predicate-guarded sum reads next.  DESIGN.md 3.10
+// lists the buffers.  Kernels: hificar_xfmr_train_kernels.hip.h.
 
 struct XfmrTrainLayer {
     ConvLayer dg_qkv, dg_wo, dg_l1, dg_l2;
@@ -73,7 +78,7 @@ static hipError_t xfmr_attn_bwd_launch(const XfmrAttnBwdParams& p, dim3 grid, fl
     hipLaunchKernelGGL((xfmr_attn_bwd_q_kernel<D>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
     hipLaunchKernelGGL((xfmr_attn_bwd_k_kernel<D>), grid, dim3(256), XfmrAttnBwdKLds<D>::bytes, stream, p);
     hipLaunchKernelGGL((xfmr_demb_partial_kernel<D>), dim3((unsigned)chunks, kXfmrHeads), dim3(256), XfmrEmbLds<D>::bytes, stream, p.qkv, p.ds, emb_partial, M,
-                       p.T, p.F);
+                       p.T, p.F, p.hdr, p.lens);
     return hipGetLastError();
 }
 
@@ -349,6 +354,7 @@ struct XfmrTape {
     float* bo[3];     // ... and its output
     std::vector<float*> X;  // [elayers + 1]: the encoder layers' inputs, and the last one's output
     std::vector<XfmrTapeLayer> L;
+    int* lens;  // [B] frame counts of a ragged forward (the header says whether they hold)
     size_t bytes;
 };
 
@@ -386,6 +392,7 @@ static XfmrTape xfmr_plan_tape(const hificar_xfmr* g, int B, int T, void* base) 
         L.hid = take(rows * kXfmrFF * 4);
         L.p2 = take(rows * F * 4);
     }
+    t.lens = reinterpret_cast<int*>(take((size_t)B * 4));
     t.bytes = off;
     return t;
 }
@@ -486,8 +493,10 @@ struct XfmrTrainCtx {
     hificar_xfmr* g;
     hificar_engine* h;
     hipStream_t stream;
-    int B, T, M, F;
+    int B, T, M, F;  // M = B T: the rows of the padded batch (the valid ones are counted by the tape's header)
     const BigruTapeHeader* hdr;
+    const int* lens;      // the tape's frame counts (the kernels honour them when the header says ragged)
+    const int* fwd_lens;  // the same for the kernels the eval path shares, which take no header: null in a dense forward
     const XfmrTrainWs* ws;
     BwdWs bw;
 
@@ -514,7 +523,10 @@ struct XfmrTrainCtx {
         p.stats = stats;
         p.rowstats = ws->rowstats;
         p.partial = ws->colpart;
+        p.hdr = hdr;
+        p.lens = lens;
         p.M = M;
+        p.T = T;
         p.F = F;
         p.mode = mode;
         hipLaunchKernelGGL(xfmr_colsum_kernel, dim3((unsigned)(F / 64), (unsigned)chunks()), dim3(256), 0, stream, p);
@@ -532,16 +544,17 @@ struct XfmrTrainCtx {
         ProfScope prof(h, stream, "xfmr_bn_stats_kernels", 0.0, 8.0 * M * F);
         int rc;
         if ((rc = colsum(0, y, nullptr, nullptr)) != HIFICAR_OK) return rc;
-        hipLaunchKernelGGL(xfmr_bn_mean_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, stream, ws->colpart, chunks(), F, M, stats);
+        hipLaunchKernelGGL(xfmr_bn_mean_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, stream, ws->colpart, chunks(), F, hdr, stats);
         if ((rc = colsum(1, y, nullptr, stats)) != HIFICAR_OK) return rc;
-        hipLaunchKernelGGL(xfmr_bn_var_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, stream, ws->colpart, chunks(), F, M, stats, batch_stats);
+        hipLaunchKernelGGL(xfmr_bn_var_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, stream, ws->colpart, chunks(), F, hdr, stats, batch_stats);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
     int bn_apply(const float* y, const float* stats, const float* gamma, const float* res, float* out, bool relu) const {
         const long long n4 = (long long)M * F / 4;
         ProfScope prof(h, stream, "xfmr_bn_apply_kernel", 0.0, 4.0 * M * F * (res ? 3 : 2));
-        hipLaunchKernelGGL(xfmr_bn_apply_kernel, dim3(ew_grid(4 * n4)), dim3(256), 0, stream, y, stats, gamma, gamma + F, res, out, n4, F, relu ? 1 : 0);
+        hipLaunchKernelGGL(xfmr_bn_apply_kernel, dim3(ew_grid(4 * n4)), dim3(256), 0, stream, y, stats, gamma, gamma + F, res, out, n4, F, relu ? 1 : 0,
+                           fwd_lens, T);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
@@ -552,7 +565,7 @@ struct XfmrTrainCtx {
         if ((rc = colsum(2, y, dy, stats)) != HIFICAR_OK) return rc;
         if ((rc = pair_reduce(dgamma)) != HIFICAR_OK) return rc;
         const long long n = (long long)M * F;
-        hipLaunchKernelGGL(xfmr_bn_bwd_dx_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, y, dy, stats, gamma, dgamma, dgamma + F, dx, n, F, M);
+        hipLaunchKernelGGL(xfmr_bn_bwd_dx_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, y, dy, stats, gamma, dgamma, dgamma + F, dx, n, F, hdr, lens, T);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
@@ -561,7 +574,8 @@ struct XfmrTrainCtx {
         p.x = src;
         p.gamma = gamma;
         p.beta = beta;
-        p.lengths = nullptr;
+        p.lengths = fwd_lens;
+        p.zero_pad = 1;  // the next GEMM and its weight gradient read every row
         p.y = dst;
         p.B = B;
         p.T = T;
@@ -575,7 +589,8 @@ struct XfmrTrainCtx {
         ProfScope prof(h, stream, "xfmr_ln_bwd_kernels", 16.0 * M * F, 20.0 * M * F);
         int rc;
         // (dx is never dy here: the column sums below still read dy; the first pass leaves the row statistics for them)
-        hipLaunchKernelGGL(xfmr_ln_bwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, dy, gamma, dx, ws->rowstats, (long long)M, F);
+        hipLaunchKernelGGL(xfmr_ln_bwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, dy, gamma, dx, ws->rowstats, (long long)M, F, hdr,
+                           lens, T);
         HIP_TRY(hipGetLastError());
         if ((rc = colsum(3, x, dy, nullptr)) != HIFICAR_OK) return rc;
         return pair_reduce(dgamma);
@@ -583,14 +598,14 @@ struct XfmrTrainCtx {
     int add_drop(const float* x, const float* t, float* out, int site) const {
         const long long n = (long long)M * F;
         ProfScope prof(h, stream, "xfmr_add_drop_kernel", 0.0, 12.0 * n);
-        hipLaunchKernelGGL(xfmr_add_drop_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, x, t, out, n, hdr, site);
+        hipLaunchKernelGGL(xfmr_add_drop_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, x, t, out, n, hdr, site, lens, F, T);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
     // out = (a > 0 ? d : 0) * dropout factor of `site` (a = null: no ReLU mask; site < 0: no dropout)
     int gate(const float* a, const float* dsrc, float* out, long long n, int site) const {
         ProfScope prof(h, stream, "xfmr_gate_kernel", 0.0, 4.0 * n * (a ? 3 : 2));
-        hipLaunchKernelGGL(xfmr_gate_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, a, dsrc, out, n, hdr, site);
+        hipLaunchKernelGGL(xfmr_gate_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, a, dsrc, out, n, hdr, site, lens, (int)(n / M), T);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
@@ -604,11 +619,10 @@ struct XfmrTrainCtx {
 // Transformer.forward in train() mode; see include/hificar.h.  tape = NULL: the rows a tape would keep live in the workspace.
 // Test aid (hificar_xfmr_debug_tap): the ReLU outputs, as rows — "conv_blocks.<n>.relu1", "conv_blocks.<n>.relu2" (B, T, hidden_dim) and
 // "layers.<n>.hidden" (B, T, 3072, before its dropout): which side of each ReLU the device took.
-extern "C" int hificar_xfmr_forward_train(hificar_xfmr* g, const float* x, float* out, float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed,
-                                          uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
-    const char* what = "hificar_xfmr_forward_train";
-    int rc = xfmr_train_check(g, what, B, T, tape, tape_bytes, workspace, workspace_bytes, true);
-    if (rc != HIFICAR_OK) return rc;
+// lengths = null: the dense form.  Otherwise B frame counts on the device and their sum (checked by the caller): the ragged form.
+static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const float* x, const int* lengths, int valid, float* out, float* bn_batch_stats, int B,
+                                   int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape, void* workspace, void* stream_) {
+    int rc;
     if (!x || !out || !bn_batch_stats) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HIFICAR_E_INVALID, "%s: dropout_p=%g outside [0, 1)", what, (double)dropout_p);
     hificar_engine* h = &g->eng;
@@ -618,14 +632,28 @@ extern "C" int hificar_xfmr_forward_train(hificar_xfmr* g, const float* x, float
     const XfmrTrainWs ws = xfmr_plan_train_ws(g, B, T, workspace);
     const XfmrTape tp = xfmr_plan_tape(g, B, T, tape ? tape : ws.light);
     const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = B * T;
-    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, &ws, {}};
+    const int* const lens = lengths ? tp.lens : nullptr;
+    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, tp.lens, lens, &ws, {}};
     auto P = [&](const std::string& name) { return ts->d_master + ts->offset.at(name); };
-    hipLaunchKernelGGL(bigru_header_kernel, dim3(1), dim3(1), 0, stream, tp.hdr, (unsigned long long)seed, (unsigned long long)offset, dropout_p, B, T, M, 0);
+    hipLaunchKernelGGL(bigru_header_kernel, dim3(1), dim3(1), 0, stream, tp.hdr, (unsigned long long)seed, (unsigned long long)offset, dropout_p, B, T,
+                       lengths ? valid : M, lengths ? 1 : 0);
     HIP_TRY(hipGetLastError());
+    if (lengths) HIP_TRY(hipMemcpyAsync(tp.lens, lengths, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    // a tap of a ragged forward: the rows of padded frames are zeros (a GEMM's output there is finite, not zero)
+    auto tap = [&](const std::string& name, const float* rows, int width) -> int {
+        auto it = g->taps.find(name);
+        if (it == g->taps.end()) return HIFICAR_OK;
+        int rc2 = xfmr_emit_tap(g, name, rows, (size_t)M * width, stream);
+        if (rc2 != HIFICAR_OK || !lengths) return rc2;
+        hipLaunchKernelGGL(bigru_zero_pad_kernel, dim3((unsigned)std::min<long long>(((long long)T * (width / 4) + 255) / 256, 8), (unsigned)B), dim3(256), 0,
+                           stream, it->second.dst, width, tp.lens, T);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    };
     {
         ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
         hipLaunchKernelGGL(xfmr_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, tp.xin,
-                           (const int*)nullptr, C, g->cin_pad, T);
+                           lens, C, g->cin_pad, T);
         HIP_TRY(hipGetLastError());
     }
     const float* in = tp.xin;
@@ -635,7 +663,7 @@ extern "C" int hificar_xfmr_forward_train(hificar_xfmr* g, const float* x, float
         XT(cx.conv(b1.raw, in, nullptr, tp.y[j1], nullptr));
         XT(cx.bn_stats(tp.y[j1], tp.stats[j1], bn_batch_stats + (size_t)j1 * 2 * F));
         XT(cx.bn_apply(tp.y[j1], tp.stats[j1], P(b1.bn + ".weight"), nullptr, tp.a1[i], true));
-        XT(xfmr_emit_tap(g, "conv_blocks." + std::to_string(i) + ".relu1", tp.a1[i], (size_t)M * F, stream));
+        XT(tap("conv_blocks." + std::to_string(i) + ".relu1", tp.a1[i], F));
         XT(cx.conv(b2.raw, tp.a1[i], nullptr, tp.y[j2], nullptr));
         XT(cx.bn_stats(tp.y[j2], tp.stats[j2], bn_batch_stats + (size_t)j2 * 2 * F));
         const float* res = in;
@@ -648,7 +676,7 @@ extern "C" int hificar_xfmr_forward_train(hificar_xfmr* g, const float* x, float
             res = ws.res;
         }
         XT(cx.bn_apply(tp.y[j2], tp.stats[j2], P(b2.bn + ".weight"), res, tp.bo[i], true));
-        XT(xfmr_emit_tap(g, "conv_blocks." + std::to_string(i) + ".relu2", tp.bo[i], (size_t)M * F, stream));
+        XT(tap("conv_blocks." + std::to_string(i) + ".relu2", tp.bo[i], F));
         in = tp.bo[i];
     }
     XT(cx.conv(g->w_in, in, nullptr, tp.X[0], nullptr));
@@ -661,7 +689,7 @@ extern "C" int hificar_xfmr_forward_train(hificar_xfmr* g, const float* x, float
             XfmrAttnParams p;
             p.qkv = L.qkv;
             p.emb = E.d_emb;
-            p.lengths = nullptr;
+            p.lengths = lens;
             p.out = L.o;
             p.T = T;
             p.F = F;
@@ -678,7 +706,7 @@ extern "C" int hificar_xfmr_forward_train(hificar_xfmr* g, const float* x, float
         XT(cx.add_drop(X, ws.t1, L.p1, 4 * l + 1));
         XT(cx.layer_norm(L.p1, E.d_ln[0], E.d_ln[1], L.n1));
         XT(cx.conv(E.l1, L.n1, nullptr, nullptr, L.hid));
-        XT(xfmr_emit_tap(g, "layers." + std::to_string(l) + ".hidden", L.hid, (size_t)M * kXfmrFF, stream));
+        XT(tap("layers." + std::to_string(l) + ".hidden", L.hid, kXfmrFF));
         XT(cx.gate(nullptr, L.hid, ws.wide, (long long)M * kXfmrFF, 4 * l + 2));
         XT(cx.conv(E.l2, ws.wide, nullptr, ws.t1, nullptr));
         XT(cx.add_drop(L.n1, ws.t1, L.p2, 4 * l + 3));
@@ -689,10 +717,39 @@ extern "C" int hificar_xfmr_forward_train(hificar_xfmr* g, const float* x, float
         const int Op = g->w_out.cout_pad;
         ProfScope prof(h, stream, "xfmr_out_kernel", 0.0, 4.0 * M * (O + Op));
         hipLaunchKernelGGL(xfmr_out_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, ws.wide, out,
-                           (const int*)nullptr, O, Op, T);
+                           lens, O, Op, T);
         HIP_TRY(hipGetLastError());
     }
     return HIFICAR_OK;
+}
+
+extern "C" int hificar_xfmr_forward_train(hificar_xfmr* g, const float* x, float* out, float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed,
+                                          uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hificar_xfmr_forward_train";
+    const int rc = xfmr_train_check(g, what, B, T, tape, tape_bytes, workspace, workspace_bytes, true);
+    if (rc != HIFICAR_OK) return rc;
+    return xfmr_forward_train_impl(g, what, x, nullptr, B * T, out, bn_batch_stats, B, T, dropout_p, seed, offset, tape, workspace, stream_);
+}
+
+// The same step on a ragged batch; see include/hificar.h.  lengths: device int32[B]; lengths_host: the same values on the host (required:
+// checked before anything is enqueued).  All lengths = T: every result is bitwise that of hificar_xfmr_forward_train.
+extern "C" int hificar_xfmr_forward_train_ragged(hificar_xfmr* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out,
+                                                 float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape,
+                                                 size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hificar_xfmr_forward_train_ragged";
+    // the arguments first (they need no device), then the handle's state
+    if (!g) return fail(HIFICAR_E_INVALID, "%s: null handle", what);
+    if (B < 1 || T < 1) return fail(HIFICAR_E_INVALID, "%s: B=%d, T=%d out of range", what, B, T);
+    if (!lengths || !lengths_host) return fail(HIFICAR_E_INVALID, "%s: lengths and lengths_host are both required", what);
+    long long valid = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths_host[b] < 0 || lengths_host[b] > T) return fail(HIFICAR_E_INVALID, "%s: lengths[%d]=%d outside [0, %d]", what, b, (int)lengths_host[b], T);
+        valid += lengths_host[b];
+    }
+    if (valid < 2) return fail(HIFICAR_E_INVALID, "%s: batch statistics need more than one valid frame (sum of lengths = %lld)", what, valid);
+    const int rc = xfmr_train_check(g, what, B, T, tape, tape_bytes, workspace, workspace_bytes, true);
+    if (rc != HIFICAR_OK) return rc;
+    return xfmr_forward_train_impl(g, what, x, lengths, (int)valid, out, bn_batch_stats, B, T, dropout_p, seed, offset, tape, workspace, stream_);
 }
 
 extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
@@ -708,7 +765,7 @@ extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, 
     const XfmrTape tp = xfmr_plan_tape(g, B, T, const_cast<void*>(tape));
     const XfmrTrainWs ws = xfmr_plan_train_ws(g, B, T, workspace);
     const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = B * T, FF = kXfmrFF;
-    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, &ws, {}};
+    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, tp.lens, nullptr, &ws, {}};
     cx.bw.partial = ws.partial;
     cx.bw.colsum = ws.colsum;
     cx.bw.partial_elems = ws.partial_elems;
@@ -720,10 +777,10 @@ extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, 
     const long long MF = (long long)M * F;
     float *d0 = ws.d[0], *d1 = ws.d[1], *d2 = ws.d[2];
     const int E = g->cfg.elayers, Op = g->w_out.cout_pad;
-    {   // dout (B, O, T) -> rows [B T][Op]
+    {   // dout (B, O, T) -> rows [B T][Op]; a ragged tape: dout past a length is not read, its rows are zeros
         ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (O + Op));
-        hipLaunchKernelGGL(xfmr_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, dout, ws.wide,
-                           (const int*)nullptr, O, Op, T);
+        hipLaunchKernelGGL(xfmr_drows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, dout, ws.wide, tp.hdr,
+                           tp.lens, O, Op, T);
         HIP_TRY(hipGetLastError());
     }
     XT(cx.wgrad(g->w_out, ws.wide, Op, tp.X[(size_t)E], F, G("w_out.weight"), G("w_out.bias")));
@@ -760,6 +817,7 @@ extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, 
             p.ds = ws.ds;
             p.pd = ws.pd;
             p.hdr = tp.hdr;
+            p.lens = tp.lens;
             p.site = 4 * l;
             p.T = T;
             p.F = F;
@@ -810,9 +868,9 @@ extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, 
         }
         if (dx) {
             XT(cx.conv(b1.dg, d0, dres, ws.dxr[1], nullptr));
-            ProfScope prof(h, stream, "bigru_unrows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
-            hipLaunchKernelGGL(bigru_unrows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, ws.dxr[1], dx,
-                               C, g->cin_pad, T);
+            ProfScope prof(h, stream, "xfmr_unrows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
+            hipLaunchKernelGGL(xfmr_unrows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, ws.dxr[1], dx,
+                               tp.hdr, tp.lens, C, g->cin_pad, T);
             HIP_TRY(hipGetLastError());
         }
     }

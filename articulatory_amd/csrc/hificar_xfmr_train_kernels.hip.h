@@ -2,6 +2,10 @@
 // layers pytorch_layers.py:94-229): the backward of the banded relative-position attention, LayerNorm backwards, BatchNorm1d on batch
 // statistics over conv rows, and the elementwise pieces (dropout, ReLU masks) between the GEMMs.  The GEMMs, their data gradients and their
 // weight gradients run on the conv engine (hificar_xfmr_train.hip.inc).  Exact fp32; every reduction is summed in a fixed order (no atomics).
+// Ragged batches (hificar_xfmr_forward_train_ragged): the tape keeps the frame counts (`lens`, honoured when its header says ragged).  The
+// GEMMs run over all B T rows, so every kernel below that writes rows writes those of padded frames (at or past a sequence's count) as
+// zeros without reading them, and every sum over rows skips them by a predicate — never by a multiplication (NaN * 0 is NaN).  A dense
+// tape takes the same statements with every count = T.
 #pragma once
 #include "hificar_xfmr_kernels.hip.h"
 
@@ -12,6 +16,11 @@ constexpr int kXfmrColRows = 256;   // rows per partial of the two-stage column 
 constexpr int kXfmrEmbRows = 256;   // rows per partial of the table gradient
 constexpr int kXfmrEmbPitch = 208;  // floats per row of the staged dS block: 13 tiles of 16 table rows; 208 = 16 (mod 64): no bank conflicts
 
+// element e of rows [B T][width] belongs to a frame of its sequence (lens null: always)
+__device__ __forceinline__ bool xfmr_elem_valid(const int* lens, long long e, int width, int T) {
+    return !lens || bigru_row_valid(lens, (int)(e / width), T);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Attention backward.  With L = m + log l kept by the forward (XfmrAttnParams::lse), per head
 //     P[q, k]  = exp(S[q, k] - L[q])                      recomputed exactly as the forward computed S
@@ -20,7 +29,9 @@ constexpr int kXfmrEmbPitch = 208;  // floats per row of the staged dS block: 13
 //     dS       = P o (dO V^T o mask / (1 - p) - Delta)
 //     dQ[q]    = sum_k dS[q, k] (K[k] / sqrt(d) + E[k - q + 99])
 //     dK[k]    = sum_q dS[q, k] Q[q] / sqrt(d),   dV[k] = sum_q Pd[q, k] dO[q],   dE[r] = sum_{b, q} dS[q, q + r - 99] Q[q]
-// Keys outside the band or the sequence stay a predicate everywhere.
+// Keys outside the band or the sequence stay a predicate everywhere.  A ragged tape: the sequence's length is its frame count; the
+// dq | dk | dv rows of padded frames are written as zeros (the fused q | k | v weight-gradient launch reads all rows), the banded dS and Pd
+// rows of padded queries are neither written nor read, and a workgroup whose 64 queries (keys) are all padded stages nothing.
 //
 // The query-tiled kernel has xfmr_attn_kernel's layout (a query is a lane column): S^T = K Q^T and dPd^T = V dO^T are 16 x 16 tiles whose
 // accumulator registers are the B operands of dQ^T += K^T dS^T.  dS of the wave's 16 queries replaces the positional logits in LDS entry by
@@ -37,6 +48,7 @@ struct XfmrAttnBwdParams {
     float* ds;          // [B][8][T][200]
     float* pd;          // [B][8][T][200]
     const BigruTapeHeader* hdr;
+    const int* lens;    // [B]: the tape's frame counts (hdr->ragged)
     int site;
     int T, F;
     float scale;
@@ -52,12 +64,16 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_q_kernel(const XfmrAttnBwdP
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kXfmrTQ;
-    const int len = p.T;
+    const int len = bigru_len(bigru_tape_lens(p.hdr, p.lens), b, p.T);
     const size_t row0 = (size_t)b * p.T;
     const size_t F3 = (size_t)3 * p.F;
     const size_t bh = (size_t)b * kXfmrHeads + h;
     const int qw = q0 + wave * 16, q = qw + c;
     const bool qok = q < len;
+    if (q0 >= len) {  // (the whole workgroup, before any barrier) 64 padded queries: their dq rows are zeros
+        xfmr_zero_head_row<D>(p.dqkv + (row0 + q) * F3 + h * D + 4 * g, q < p.T);
+        return;
+    }
     const XfmrDrop drop(p.hdr, p.site);
 
     float qf[NS], dof[NS];
@@ -176,8 +192,11 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_q_kernel(const XfmrAttnBwdP
             for (int j = 0; j < NM; ++j) o[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[16 * j], bv, o[j], 0, 0, 0);
         }
     }
-    if (!qok) return;
     float* orow = p.dqkv + (row0 + q) * F3 + h * D + 4 * g;
+    if (!qok) {
+        xfmr_zero_head_row<D>(orow, q < p.T);
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < NM; ++j) *reinterpret_cast<float4*>(orow + 16 * j) = make_float4(o[j][0], o[j][1], o[j][2], o[j][3]);
 }
@@ -199,12 +218,19 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_k_kernel(const XfmrAttnBwdP
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, k0 = blockIdx.x * kXfmrKB;
-    const int len = p.T;
+    const int len = bigru_len(bigru_tape_lens(p.hdr, p.lens), b, p.T);
     const size_t row0 = (size_t)b * p.T;
     const size_t F3 = (size_t)3 * p.F;
     const size_t bh = (size_t)b * kXfmrHeads + h;
     const int kw = k0 + wave * 16, k = kw + c;
     const bool kok = k < len;
+    float* const krow = p.dqkv + (row0 + k) * F3 + p.F + h * D + 4 * g;
+    float* const vrow = krow + p.F;
+    if (k0 >= len) {  // (the whole workgroup, before any barrier) 64 padded keys: their dk | dv rows are zeros
+        xfmr_zero_head_row<D>(krow, k < p.T);
+        xfmr_zero_head_row<D>(vrow, k < p.T);
+        return;
+    }
     f32x4 dv[NM], dk[NM];
 #pragma unroll
     for (int j = 0; j < NM; ++j) dv[j] = dk[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -238,9 +264,11 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_k_kernel(const XfmrAttnBwdP
             }
         }
     }
-    if (!kok) return;
-    float* krow = p.dqkv + (row0 + k) * F3 + p.F + h * D + 4 * g;
-    float* vrow = krow + p.F;
+    if (!kok) {
+        xfmr_zero_head_row<D>(krow, k < p.T);
+        xfmr_zero_head_row<D>(vrow, k < p.T);
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < NM; ++j) {
         *reinterpret_cast<float4*>(krow + 16 * j) = make_float4(dk[j][0] * p.scale, dk[j][1] * p.scale, dk[j][2] * p.scale, dk[j][3] * p.scale);
@@ -250,7 +278,8 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_k_kernel(const XfmrAttnBwdP
 
 // Table gradient, first stage: partial[chunk][h][r][d] = sum over the chunk's 256 rows (b, q) of dS[b, h, q, r] Q[b, h, q], the rows taken
 // in blocks of 64 in order.  grid (chunks, 8).  Wave w owns the table-row tiles w, w + 4, w + 8 (and 12: wave 0).  The second stage
-// (bigru_colreduce_kernel) adds the chunks in order.
+// (bigru_colreduce_kernel) adds the chunks in order.  The rows are those of the padded batch; a padded frame's row is staged as zeros
+// (both operands, neither read) and a block of 64 rows without a valid one is skipped.
 template <int D>
 struct XfmrEmbLds {
     static constexpr size_t bytes = (size_t)64 * (D + 4 + kXfmrEmbPitch) * sizeof(float);
@@ -258,7 +287,7 @@ struct XfmrEmbLds {
 
 template <int D>
 __global__ __launch_bounds__(256) void xfmr_demb_partial_kernel(const float* __restrict__ qkv, const float* __restrict__ ds, float* __restrict__ partial,
-                                                                int M, int T, int F) {
+                                                                int M, int T, int F, const BigruTapeHeader* hdr, const int* __restrict__ tape_lens) {
     extern __shared__ float xfmr_lds[];
     constexpr int PT = D + 4, NM = D / 16, DP = kXfmrEmbPitch;
     float* const qbuf = xfmr_lds;
@@ -267,6 +296,7 @@ __global__ __launch_bounds__(256) void xfmr_demb_partial_kernel(const float* __r
     const int c = lane & 15, g = lane >> 4;
     const int chunk = blockIdx.x, h = blockIdx.y;
     const size_t F3 = (size_t)3 * F;
+    const int* const lens = bigru_tape_lens(hdr, tape_lens);
     f32x4 acc[4][NM];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -276,12 +306,26 @@ __global__ __launch_bounds__(256) void xfmr_demb_partial_kernel(const float* __r
         const int r0 = chunk * kXfmrEmbRows + blk * 64;
         if (r0 >= M) break;  // (the whole workgroup)
         const int n = min(64, M - r0);
+        if (lens) {  // (the whole workgroup) no frame among these rows: nothing to add
+            bool any = false;
+            for (int bb = r0 / T; bb <= (r0 + n - 1) / T; ++bb) any = any || max(r0, bb * T) < min(r0 + n, bb * T + bigru_len(lens, bb, T));
+            if (!any) continue;
+        }
         __syncthreads();
-        xfmr_stage<D>(qbuf, qkv + (size_t)r0 * F3 + h * D, F3, n, tid);
+        if (!lens) {
+            xfmr_stage<D>(qbuf, qkv + (size_t)r0 * F3 + h * D, F3, n, tid);
+        } else {
+            for (int i = tid; i < 64 * (D / 4); i += 256) {
+                const int rr = i / (D / 4), v = i - rr * (D / 4);
+                float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (rr < n && bigru_row_valid(lens, r0 + rr, T)) x = *reinterpret_cast<const float4*>(qkv + (size_t)(r0 + rr) * F3 + h * D + 4 * v);
+                *reinterpret_cast<float4*>(qbuf + rr * PT + 4 * v) = x;
+            }
+        }
         for (int i = tid; i < 64 * (DP / 4); i += 256) {
             const int rr = i / (DP / 4), v = i - rr * (DP / 4);
             float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (rr < n && 4 * v < kXfmrBand) {  // (entry 199 of a row is a written zero)
+            if (rr < n && 4 * v < kXfmrBand && bigru_row_valid(lens, r0 + rr, T)) {  // (entry 199 of a row is a written zero)
                 const int row = r0 + rr, bb = row / T, t = row - bb * T;
                 x = *reinterpret_cast<const float4*>(ds + (((size_t)bb * kXfmrHeads + h) * T + t) * kXfmrBand + 4 * v);
             }
@@ -325,6 +369,8 @@ __global__ __launch_bounds__(256) void xfmr_demb_partial_kernel(const float* __r
 //   mode 1  s0 = (x - mean[c])^2                                 BatchNorm variance: the second pass, not E[x^2] - E[x]^2
 //   mode 2  s0 = dy xhat, s1 = dy, xhat = (x - mean[c]) rstd[c]  BatchNorm backward (stats: mean | var | rstd)
 //   mode 3  s0 = dy xhat, s1 = dy, xhat = (x - mean_r) rstd_r    LayerNorm backward (rowstats[r]: mean, rstd of row r)
+// A ragged tape: the chunks are those of the padded row index and a valid row keeps its lane and its turn; a padded row is skipped, not
+// read.  The BatchNorm means divide by the tape's M, the number of valid rows.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct XfmrColParams {
     const float* x;
@@ -332,7 +378,9 @@ struct XfmrColParams {
     const float* stats;     // [3][F]
     const float* rowstats;  // [M][2]
     float* partial;         // [chunks][2][F]
-    int M, F, mode;
+    const BigruTapeHeader* hdr;
+    const int* lens;        // [B]: the tape's frame counts (hdr->ragged)
+    int M, T, F, mode;      // M = B T: the rows of the padded batch
 };
 
 __global__ __launch_bounds__(256) void xfmr_colsum_kernel(const XfmrColParams p) {
@@ -342,8 +390,10 @@ __global__ __launch_bounds__(256) void xfmr_colsum_kernel(const XfmrColParams p)
     float mean = 0.f, rstd = 0.f;
     if (p.mode == 1 || p.mode == 2) mean = p.stats[c];
     if (p.mode == 2) rstd = p.stats[2 * p.F + c];
+    const int* const lens = bigru_tape_lens(p.hdr, p.lens);
     float s0 = 0.f, s1 = 0.f;
     for (int r = r0 + ty; r < r1; r += 4) {
+        if (!bigru_row_valid(lens, r, p.T)) continue;
         const size_t e = (size_t)r * p.F + c;
         const float x = p.x[e];
         if (p.mode == 0) {
@@ -370,19 +420,22 @@ __global__ __launch_bounds__(256) void xfmr_colsum_kernel(const XfmrColParams p)
 }
 
 // stats[c] = mean of column c (the chunks' sums added in order, in double)
-__global__ __launch_bounds__(256) void xfmr_bn_mean_kernel(const float* __restrict__ partial, int chunks, int F, int M, float* __restrict__ stats) {
+__global__ __launch_bounds__(256) void xfmr_bn_mean_kernel(const float* __restrict__ partial, int chunks, int F, const BigruTapeHeader* hdr,
+                                                           float* __restrict__ stats) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= F) return;
+    const int M = hdr->M;
     double s = 0.0;
     for (int i = 0; i < chunks; ++i) s += (double)partial[(size_t)i * 2 * F + c];
     stats[c] = (float)(s / M);
 }
 
 // stats: mean | biased variance | 1 / sqrt(var + 1e-5); batch_stats (mean | biased variance) goes back to the caller
-__global__ __launch_bounds__(256) void xfmr_bn_var_kernel(const float* __restrict__ partial, int chunks, int F, int M, float* __restrict__ stats,
-                                                          float* __restrict__ batch_stats) {
+__global__ __launch_bounds__(256) void xfmr_bn_var_kernel(const float* __restrict__ partial, int chunks, int F, const BigruTapeHeader* hdr,
+                                                          float* __restrict__ stats, float* __restrict__ batch_stats) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= F) return;
+    const int M = hdr->M;
     double s = 0.0;
     for (int i = 0; i < chunks; ++i) s += (double)partial[(size_t)i * 2 * F + c];
     const float var = (float)(s / M);
@@ -392,11 +445,16 @@ __global__ __launch_bounds__(256) void xfmr_bn_var_kernel(const float* __restric
     batch_stats[F + c] = var;
 }
 
-// out = (x - mean) rstd gamma + beta (+ res) (ReLU'd with relu != 0) over rows [M][F]; n4 = M F / 4
+// out = (x - mean) rstd gamma + beta (+ res) (ReLU'd with relu != 0) over rows [B T][F]; n4 = B T F / 4.  lens (null: dense): the rows of
+// padded frames are written as zeros
 __global__ __launch_bounds__(256) void xfmr_bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, const float* __restrict__ res, float* __restrict__ out,
-                                                            long long n4, int F, int relu) {
+                                                            long long n4, int F, int relu, const int* __restrict__ lens, int T) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        if (!xfmr_elem_valid(lens, i * 4, F, T)) {
+            reinterpret_cast<float4*>(out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
         const int c = (int)((i * 4) % F);
         const float4 v = reinterpret_cast<const float4*>(x)[i];
         const float4 mu = *reinterpret_cast<const float4*>(stats + c), rs = *reinterpret_cast<const float4*>(stats + 2 * F + c);
@@ -412,12 +470,19 @@ __global__ __launch_bounds__(256) void xfmr_bn_apply_kernel(const float* __restr
     }
 }
 
-// BatchNorm backward, the input gradient: dx = gamma rstd (dy - dbeta / M - xhat dgamma / M); dx == dy is allowed
+// BatchNorm backward, the input gradient: dx = gamma rstd (dy - dbeta / M - xhat dgamma / M), M the tape's valid rows; dx == dy is
+// allowed.  The rows of padded frames are written as zeros.
 __global__ __launch_bounds__(256) void xfmr_bn_bwd_dx_kernel(const float* __restrict__ x, const float* dy, const float* __restrict__ stats,
                                                              const float* __restrict__ gamma, const float* __restrict__ dgamma,
-                                                             const float* __restrict__ dbeta, float* dx, long long n, int F, int M) {
-    const float inv_m = 1.f / (float)M;
+                                                             const float* __restrict__ dbeta, float* dx, long long n, int F, const BigruTapeHeader* hdr,
+                                                             const int* __restrict__ tape_lens, int T) {
+    const float inv_m = 1.f / (float)hdr->M;
+    const int* const lens = bigru_tape_lens(hdr, tape_lens);
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        if (!xfmr_elem_valid(lens, e, F, T)) {
+            dx[e] = 0.f;
+            continue;
+        }
         const int c = (int)(e % F);
         const float rstd = stats[2 * F + c];
         const float xhat = (x[e] - stats[c]) * rstd;
@@ -429,20 +494,32 @@ __global__ __launch_bounds__(256) void xfmr_bn_bwd_dx_kernel(const float* __rest
 // Elementwise pieces over rows (n % 4 == 0; element index = the row-major index in (B, T, C)).  site < 0: no dropout.
 //   xfmr_add_drop_kernel   out = x + t factor(site, e)                 the residual joins of an encoder layer (dropout1, dropout2)
 //   xfmr_gate_kernel       out = a > 0 ? d factor(site, e) : 0         ReLU' (a: the ReLU's output) and the dropout behind it; a = null: dropout only
+// Rows are `width` floats (width % 4 == 0); on a ragged tape the rows of padded frames are written as zeros and their inputs not read.
 // ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void xfmr_add_drop_kernel(const float* __restrict__ x, const float* __restrict__ t, float* __restrict__ out, long long n,
-                                                            const BigruTapeHeader* hdr, int site) {
+                                                            const BigruTapeHeader* hdr, int site, const int* __restrict__ tape_lens, int width, int T) {
     const XfmrDrop drop(hdr, site);
+    const int* const lens = bigru_tape_lens(hdr, tape_lens);
     for (long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; e < n; e += (long long)gridDim.x * 1024) {
+        if (!xfmr_elem_valid(lens, e, width, T)) {
+            *reinterpret_cast<float4*>(out + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
         const float4 a = *reinterpret_cast<const float4*>(x + e), v = *reinterpret_cast<const float4*>(t + e);
         *reinterpret_cast<float4*>(out + e) = make_float4(a.x + v.x * drop((unsigned long long)e), a.y + v.y * drop((unsigned long long)e + 1),
                                                           a.z + v.z * drop((unsigned long long)e + 2), a.w + v.w * drop((unsigned long long)e + 3));
     }
 }
 
-__global__ __launch_bounds__(256) void xfmr_gate_kernel(const float* a, const float* d, float* out, long long n, const BigruTapeHeader* hdr, int site) {
+__global__ __launch_bounds__(256) void xfmr_gate_kernel(const float* a, const float* d, float* out, long long n, const BigruTapeHeader* hdr, int site,
+                                                        const int* __restrict__ tape_lens, int width, int T) {
     const XfmrDrop drop(hdr, site < 0 ? 0 : site);
+    const int* const lens = bigru_tape_lens(hdr, tape_lens);
     for (long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; e < n; e += (long long)gridDim.x * 1024) {
+        if (!xfmr_elem_valid(lens, e, width, T)) {
+            *reinterpret_cast<float4*>(out + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
         float4 v = *reinterpret_cast<const float4*>(d + e);
         if (site >= 0) {
             v.x *= drop((unsigned long long)e);
@@ -462,13 +539,19 @@ __global__ __launch_bounds__(256) void xfmr_gate_kernel(const float* a, const fl
 // LayerNorm backward: one wave per row, mean and rstd recomputed from the saved pre-norm row exactly as xfmr_ln_kernel computes them (and
 // left in rowstats for the column sums of d gamma / d beta): with g = dy gamma and xhat = (x - mean) rstd,
 //     dx = rstd (g - mean(g) - xhat mean(g xhat)).     F <= 1024, a multiple of 4.  dx == dy is allowed.
+// A padded frame's row (ragged tape): dx is written as zeros, nothing is read, and its rowstats stay unwritten (the column sums skip it).
 // ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void xfmr_ln_bwd_kernel(const float* __restrict__ x, const float* dy, const float* __restrict__ gamma, float* dx,
-                                                          float* __restrict__ rowstats, long long M, int F) {
+                                                          float* __restrict__ rowstats, long long M, int F, const BigruTapeHeader* hdr,
+                                                          const int* __restrict__ tape_lens, int T) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const int nv = F >> 2;
+    if (!bigru_row_valid(bigru_tape_lens(hdr, tape_lens), (int)row, T)) {
+        for (int i = lane; i < nv; i += 64) reinterpret_cast<float4*>(dx + row * F)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
     const float4* xr = reinterpret_cast<const float4*>(x + row * F);
     const float4* dr = reinterpret_cast<const float4*>(dy + row * F);
     const float4* gm = reinterpret_cast<const float4*>(gamma);
@@ -519,6 +602,43 @@ __global__ __launch_bounds__(256) void xfmr_ln_bwd_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------------------------------------
 // Between the reference's layouts and the fused GEMMs'.
 // ---------------------------------------------------------------------------------------------------------------------------
+// xfmr_rows_kernel by the tape's frame counts: dout (B, C, T) -> rows [b T + t][Cp]
+__global__ __launch_bounds__(256) void xfmr_drows_kernel(const float* __restrict__ x, float* __restrict__ rows, const BigruTapeHeader* hdr,
+                                                         const int* __restrict__ tape_lens, int C, int Cp, int T) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int len = bigru_len(bigru_tape_lens(hdr, tape_lens), b, T);
+    for (int r = ty; r < 32; r += 8) {
+        const int c = c0 + r, t = t0 + tx;
+        tile[r][tx] = (c < C && t < len) ? x[((size_t)b * C + c) * T + t] : 0.f;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+        const int t = t0 + r, c = c0 + tx;
+        if (t < T && c < Cp) rows[((size_t)b * T + t) * Cp + c] = tile[tx][r];
+    }
+}
+
+// rows [b T + t][Cp] -> dx (B, C, T): the input gradient in the reference's layout; a padded frame's (ragged tape) is zero and its row,
+// which holds what the k = 3 data gradient spilled over the sequence's end, is not read
+__global__ __launch_bounds__(256) void xfmr_unrows_kernel(const float* __restrict__ rows, float* __restrict__ dx, const BigruTapeHeader* hdr,
+                                                          const int* __restrict__ tape_lens, int C, int Cp, int T) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int len = bigru_len(bigru_tape_lens(hdr, tape_lens), b, T);
+    for (int r = ty; r < 32; r += 8) {
+        const int t = t0 + r, c = c0 + tx;
+        tile[r][tx] = (t < len && c < Cp) ? rows[((size_t)b * T + t) * Cp + c] : 0.f;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+        const int c = c0 + r, t = t0 + tx;
+        if (c < C && t < T) dx[((size_t)b * C + c) * T + t] = tile[tx][r];
+    }
+}
+
 // w_q | w_k | w_v, each (8, F, d), -> the q | k | v GEMM's (3 F, F) weight: row (s 8 + h) d + a, column f is w_s[h, f, a]; back == 1: the
 // weight gradient the other way
 __global__ __launch_bounds__(256) void xfmr_qkv_weight_kernel(float* __restrict__ wq, float* __restrict__ wk, float* __restrict__ wv,

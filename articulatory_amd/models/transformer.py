@@ -18,8 +18,13 @@ them out of the graph — ``embeddings.grad`` stays None there and its optimizer
 computes the table's gradient (``train_relative_positions = True``, the default); set the attribute to False to train exactly what the
 reference trains (the tables then get no gradient).
 
-Not built, refused with ``NotImplementedError``: ``extra_art=True``, ``num_ph`` (phoneme input) and ``lengths=`` in train() mode (ragged
-training).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size`` keywords are accepted and unused, as in the reference.
+``forward_padded(x, lengths)`` trains on whole utterances of unequal lengths (this package's definition, the reference never masks):
+``hificar_xfmr_forward_train_ragged`` through the same autograd node; the padded frames take no part in batch statistics, attention or
+gradients.
+
+Not built, refused with ``NotImplementedError``: ``extra_art=True`` and ``num_ph`` (phoneme input).  ``forward(lengths=...)`` in train() mode
+is refused too (ragged training is asked for by name: ``forward_padded``).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size``
+keywords are accepted and unused, as in the reference.
 ``lengths=`` in eval mode is this package's addition: a ragged batch in which every utterance's result is that of running it alone.
 """
 
@@ -117,13 +122,14 @@ def _grad_layout(module):
 
 
 class _TransformerFunction(torch.autograd.Function):
-    """Autograd node of the native Transformer in train() mode: forward = hificar_xfmr_forward_train (keeps a tape), backward =
+    """Autograd node of the native Transformer in train() mode: forward = hificar_xfmr_forward_train (or, with ``module._lens`` set by
+    ``forward_padded``, hificar_xfmr_forward_train_ragged: the lengths are read here, at forward time, and live on in the tape), backward =
     hificar_xfmr_backward.  Inputs after (module, x, p, seed, offset, names) are the module's parameters in ``names`` order.  Returns
     (out, batch statistics (number of batch norms, 2, hidden_dim): mean | biased variance); the statistics carry no gradient."""
 
     @staticmethod
     def forward(ctx, module, x, p, seed, offset, names, *params):
-        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True)
+        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True, lens=module._lens)
         B, _, T = x.shape
         ctx.module, ctx.names, ctx.tape, ctx.toff, ctx.BT = module, names, tape, toff, (B, T)
         ctx.save_for_backward(*params)  # torch's own version check covers an in-place edit that bumps Parameter._version ...
@@ -190,6 +196,7 @@ class Transformer(torch.nn.Module):
         self._dirty = False      # an optimizer stepped since the last hand-over (fused optimizers do not bump Parameter._version)
         self._steps_seen = 0     # optimizer steps noticed so far
         self._calls = 0          # training forwards so far: the dropout generator's offset
+        self._lens = None        # the lengths of the ragged training forward under way (forward_padded)
         self._last_stats = None
         self.train_relative_positions = True  # False: the tables get no gradient, as in the reference (see the module's docstring)
         # drawn from torch's generator (after the parameters): torch.manual_seed makes a training run repeatable
@@ -289,7 +296,7 @@ class Transformer(torch.nn.Module):
 
     def __getstate__(self):  # copies and pickles never share a native handle
         state = self.__dict__.copy()
-        for k in ("_handle", "_lib", "_workspace_buf", "_sig", "_train_ws_buf", "_last_stats"):
+        for k in ("_handle", "_lib", "_workspace_buf", "_sig", "_train_ws_buf", "_last_stats", "_lens"):
             state[k] = None
         state["_on_device"] = state["_dirty"] = False
         state.pop("_grad_info", None)
@@ -381,8 +388,9 @@ class Transformer(torch.nn.Module):
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
 
-    def _run_forward_train(self, x, p, seed, offset, keep_tape):
-        """hificar_xfmr_forward_train on the current stream: (out, batch statistics, tape or None, the tape's alignment offset)."""
+    def _run_forward_train(self, x, p, seed, offset, keep_tape, lens=None):
+        """hificar_xfmr_forward_train (lens = (host, device) int32 lengths: hificar_xfmr_forward_train_ragged) on the current stream: (out,
+        batch statistics, tape or None, the tape's alignment offset)."""
         lib, handle = self._lib, self._handle
         B, _, T = x.shape
         dev = x.device
@@ -395,10 +403,14 @@ class Transformer(torch.nn.Module):
             out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=dev)
             stats = torch.empty((len(self._batch_norms()), 2, self._params["hidden_dim"]), dtype=torch.float32, device=dev)
             ws_ptr, ws_bytes = self._train_workspace(B, T)
-            rc = lib.hificar_xfmr_forward_train(handle, x.data_ptr(), out.data_ptr(), stats.data_ptr(), B, T, float(p), seed, offset,
-                                                tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
-                                                ws_ptr, ws_bytes, stream)
-        _native.check(rc, "hificar_xfmr_forward_train")
+            tail = (B, T, float(p), seed, offset, tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
+                    ws_ptr, ws_bytes, stream)
+            if lens is None:
+                rc = lib.hificar_xfmr_forward_train(handle, x.data_ptr(), out.data_ptr(), stats.data_ptr(), *tail)
+            else:
+                rc = lib.hificar_xfmr_forward_train_ragged(handle, x.data_ptr(), lens[1].data_ptr(), lens[0].data_ptr(), out.data_ptr(),
+                                                           stats.data_ptr(), *tail)
+        _native.check(rc, "hificar_xfmr_forward_train" if lens is None else "hificar_xfmr_forward_train_ragged")
         return out, stats, tape, toff
 
     def _workspace(self, B, T):
@@ -458,14 +470,30 @@ class Transformer(torch.nn.Module):
         _native.check(rc, "hificar_xfmr_forward")
         return out
 
-    def _forward_train(self, x, lengths):
+    def forward_padded(self, x, lengths):
+        """A batch of whole utterances, zero-padded to (B, in_channels, T), with their frame counts ``lengths`` (B values in 0 .. T).
+        eval(): ``forward(x, lengths=lengths)``.  train(): the training step on the ragged batch, under autograd — this package's
+        definition, the reference never masks: the convs see zero padding at a sequence's own end, a query's keys lie below its sequence's
+        own length, dropout masks are those of the padded tensors (they depend on T), every batch norm takes mean and biased variance over
+        the M = sum(lengths) valid frames (running variance: M / (M - 1)), ``out[b, :, lengths[b]:]`` is exactly zero; backwards, the output
+        gradient on padded frames is ignored whatever it holds, the input gradient is zero there, and every parameter gradient sums valid
+        frames only.  With every length equal to T all results are bitwise those of ``forward``.  What ``x`` holds in padded frames is
+        never used."""
+        if not self.training:
+            return self.forward(x, lengths=lengths)
+        if lengths is None:
+            raise RuntimeError("Transformer.forward_padded needs lengths")
+        return self._forward_train(x, lengths, padded=True)
+
+    def _forward_train(self, x, lengths, padded=False):
         """train() mode (transformer.py:55-77 with every nn.Dropout active and the batch norms on batch statistics): with grad enabled the
         output is part of the autograd graph; without, the same arithmetic runs and its tape is dropped.  Every call — either way —
         advances the dropout generator's offset and updates every batch norm's running_mean / running_var / num_batches_tracked as
         torch.nn.BatchNorm1d does."""
-        if lengths is not None:
-            raise NotImplementedError("Transformer.forward(lengths=...) in train() mode: ragged training is not built (equal-length "
-                                      "batches only, as the reference's collater makes them; call .eval() for ragged inference)")
+        if lengths is not None and not padded:
+            raise NotImplementedError("Transformer.forward(lengths=...) in train() mode is refused: ragged training uses masked batch "
+                                      "statistics, this package's definition and not the reference's, so asking for it is explicit: call "
+                                      "forward_padded(x, lengths) (or .eval() for ragged inference)")
         if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
             raise NotImplementedError("Transformer.forward in train() mode needs a CUDA/HIP tensor: the training path exists on the device "
                                       "only, as HIP kernels (there is no CPU fallback)")
@@ -475,8 +503,13 @@ class Transformer(torch.nn.Module):
         if B < 1 or T < 1:
             raise RuntimeError(f"Transformer.forward: empty input {tuple(x.shape)}")
         n = B * T
+        lens = None
+        if padded:
+            lens = self._check_lengths(lengths, B, T, x.device)
+            n = int(lens[0].sum())
         if n < 2:  # torch.nn.functional.batch_norm's own refusal
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, self._params['hidden_dim'], T]}")
+            raise ValueError("Expected more than 1 value per channel when training, got input size "
+                             f"{[B, self._params['hidden_dim'], T] if lens is None else [n, self._params['hidden_dim']]}")
         self._native_handle(train=True)
         if x.device != self._device():
             raise RuntimeError(f"Transformer.forward: input on {x.device}, parameters on {self._device()}")
@@ -485,12 +518,16 @@ class Transformer(torch.nn.Module):
         names, params = tuple(k for k, _ in named), [p for _, p in named]
         offset = self._calls
         self._calls += 1
-        if torch.is_grad_enabled() and (c.requires_grad or any(p.requires_grad for p in params)):
-            out, stats = _TransformerFunction.apply(self, c, self._params["dropout"], self._dropout_seed, offset, names, *params)
-        else:  # no graph: the same arithmetic without a tape (tape = NULL)
-            out, stats, _, _ = self._run_forward_train(c.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False)
+        self._lens = lens
+        try:
+            if torch.is_grad_enabled() and (c.requires_grad or any(p.requires_grad for p in params)):
+                out, stats = _TransformerFunction.apply(self, c, self._params["dropout"], self._dropout_seed, offset, names, *params)
+            else:  # no graph: the same arithmetic without a tape (tape = NULL)
+                out, stats, _, _ = self._run_forward_train(c.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False, lens=lens)
+        finally:
+            self._lens = None
         self._last_stats = stats.detach()  # (number of batch norms, 2, hidden_dim): this batch's mean | biased variance, for inspection
-        with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance
+        with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance (n: the valid frames)
             for j, bn in enumerate(self._batch_norms()):
                 bn.running_mean.mul_(0.9).add_(stats[j, 0], alpha=0.1)
                 bn.running_var.mul_(0.9).add_(stats[j, 1], alpha=0.1 * n / (n - 1))

@@ -681,7 +681,8 @@ int hificar_xfmr_forward(hificar_xfmr* h, const float* x, const int32_t* lengths
 /* Test aid: the following forwards also copy the named intermediate, as rows (B, T, hidden_dim), into dst (device, `capacity` floats).
  * Names: "conv_blocks", "w_raw_in", "layers.<l>.norm1" (the attention sub-block's output), "layers.<l>" (the layer's output).
  * hificar_xfmr_forward_train serves three more, the outputs of its ReLUs (which side of each the device took): "conv_blocks.<n>.relu1",
- * "conv_blocks.<n>.relu2" (rows of hidden_dim) and "layers.<l>.hidden" (rows of 3072, before the dropout).
+ * "conv_blocks.<n>.relu2" (rows of hidden_dim) and "layers.<l>.hidden" (rows of 3072, before the dropout); hificar_xfmr_forward_train_ragged
+ * serves the same names, the rows of padded frames as zeros.
  * name = NULL forgets every tap, dst = NULL that one. */
 int hificar_xfmr_debug_tap(hificar_xfmr* h, const char* name, float* dst, size_t capacity);
 
@@ -694,9 +695,10 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
 /* ---- Transformer training: the reference's step for dataset_mode art / a2m / m2a (articulatory/bin/train.py:241-383), the model in train()
  * mode: BatchNorm1d on batch statistics in the three ResBlocks, Dropout(p) on the attention probabilities, behind the attention and feed-forward
  * sub-blocks and on the feed-forward's hidden rows.  Exact fp32, deterministic: every reduction is summed in a fixed order, no floating-point
- * atomics.  Equal-length batches only (the reference's CollaterMelArt cuts equal windows): there is no lengths argument.
+ * atomics.  hificar_xfmr_forward_train takes equal-length batches (the reference's CollaterMelArt cuts equal windows);
+ * hificar_xfmr_forward_train_ragged takes whole utterances of unequal lengths (this library's definition: the reference never masks).
  * All of these may be called after hificar_xfmr_finalize; the first one builds the training state.
- * Not built: ragged Transformer training, bf16x3, extra_art, num_ph, multi-GPU training of this model. ---- */
+ * Not built: packed (padding-free) GEMMs for ragged batches, a smaller tape, bf16x3, extra_art, num_ph, multi-GPU training of this model. ---- */
 
 /* Every float tensor of the state_dict (reference names and layouts, the batch norms' running_mean / running_var included; n = all of them,
  * each once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs (the
@@ -715,7 +717,7 @@ int64_t hificar_xfmr_grad_floats(hificar_xfmr* h);
 /* Bytes of the tape (what a training forward keeps for its backward pass: the input rows; per batch norm its conv's raw output rows and the
  * statistics; per ResBlock its two ReLU outputs; per encoder layer its input rows, q | k | v, the attention's output rows and L = m + log l
  * per (head, query), both pre-LayerNorm rows, norm1's output and the feed-forward's hidden rows; dropout masks are regenerated, not stored)
- * and of the scratch shared by hificar_xfmr_forward_train and hificar_xfmr_backward. */
+ * and of the scratch shared by hificar_xfmr_forward_train and hificar_xfmr_backward; the B frame counts of a ragged forward). */
 size_t hificar_xfmr_tape_bytes(const hificar_xfmr* h, int B, int T);
 size_t hificar_xfmr_train_workspace_bytes(hificar_xfmr* h, int B, int T);
 
@@ -733,8 +735,31 @@ size_t hificar_xfmr_train_workspace_bytes(hificar_xfmr* h, int B, int T);
 int hificar_xfmr_forward_train(hificar_xfmr* h, const float* x, float* out, float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed,
                                uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same step on a ragged batch of whole utterances: sequence b has lengths[b] frames (0 .. T; M = their sum >= 2) of x (B, in_channels, T);
+ * what x holds past them is never used (NaN included), and neither is what the tape and the workspace hold on entry.
+ *   convs (k = 3)  a sequence sees zero padding at its own end (as hificar_xfmr_forward does with lengths)
+ *   batch norms    mean and biased variance over the M valid rows (two-pass); bn_batch_stats as above (the caller's running variance takes
+ *                  M / (M - 1))
+ *   attention      a query's keys lie within +-99 and below its sequence's own length; queries at or past the length do not exist
+ *   LayerNorm, Linear, feed-forward   per row: valid rows exactly as above
+ *   dropout        element e is the index in the PADDED (B, T, C) tensor, and ((b 8 + h) T + q) 199 + (k - q + 99) for the probabilities,
+ *                  as above: the masks depend on T, not only on the lengths
+ *   out            out[b, :, lengths[b]:] is exactly zero
+ * lengths: device int32[B].  lengths_host: the same values on the host, required: each is checked against 0 .. T and their sum against >= 2
+ * before anything is enqueued (HIFICAR_E_INVALID otherwise).  The tape records the lengths and M, so hificar_xfmr_backward takes no new
+ * argument and cannot be run with other lengths than its forward: on such a tape it ignores dout on padded frames, whatever it holds, writes
+ * dx = 0 there, and every weight, bias, d gamma / d beta and relative-position table gradient sums valid frames only (the batch norms'
+ * backward divides by the same M).  With all lengths = T every result is bitwise that of hificar_xfmr_forward_train.  Deterministic (no
+ * atomics).  tape = NULL: the forward-only form, as above.
+ * The GEMMs still run over all B T rows (zeros in the padded rows mask them); the attention kernels skip the 64-frame tiles that hold
+ * padding only.  Padding costs GEMM time, not correctness. */
+int hificar_xfmr_forward_train_ragged(hificar_xfmr* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out,
+                                      float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape,
+                                      size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* dout (B, out_channels, T) -> grads (hificar_xfmr_grad_floats floats: written, not accumulated) and, with dx non-NULL, the input's
- * gradient (B, in_channels, T).  The weights must be those of the forward that filled the tape.  Deterministic, as above. */
+ * gradient (B, in_channels, T).  The weights must be those of the forward that filled the tape.  Deterministic, as above.  A tape of
+ * hificar_xfmr_forward_train_ragged: see there. */
 int hificar_xfmr_backward(hificar_xfmr* h, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
                           void* workspace, size_t workspace_bytes, void* stream);
 

@@ -20,6 +20,13 @@ native against stock alternated the same way.  Stock is tests/transformer_train_
 linear, einsum, softmax, layer_norm under autograd, the attention banded too), its dropout masks drawn with torch.rand on the device (the
 package's counter-based masks would be generated on the host).  The per-kernel profile covers one native forward + backward; the
 attention backward's TFLOP/s counts 2 * 7 * 199 * hidden FLOP per frame and layer (S, dP, the K and E parts of dQ, dK, dV, dE).
+
+   python tools/transformer_bench.py --train --ragged [--seed 0] [--out profiles/transformer_train_ragged.txt]
+
+--train --ragged: one batch of whole utterances instead — the default size, B 32, padded to T 500, lengths uniform in 100 .. 500 from --seed
+(as tools/bigru_train_bench.py --ragged draws them) — and two legs of the same model in alternated windows: the native ragged step
+(Transformer.forward_padded + masked_l1_loss) and the native dense step on the same padded batch (every frame counted, as the reference's
+pad mode trains).  Then one profiled step of each: time per kernel, and what the skipped attention tiles recover.
 Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
 import argparse
 import ctypes
@@ -143,6 +150,70 @@ def train_main(a):
             f.write("\n".join(lines) + "\n")
 
 
+def ragged_train_main(a):
+    """--train --ragged: see the module docstring."""
+    import torch.nn.functional as F
+
+    from articulatory_amd.losses import masked_l1_loss
+
+    p, B, T = 0.2, 32, 500
+    lengths = torch.from_numpy(np.random.default_rng(a.seed).integers(100, T + 1, size=B)).to(torch.int64)
+    M = int(lengths.sum())
+    valid = torch.arange(T)[None, :] < lengths[:, None]
+    sd = synth_transformer_state_dict(PARAMS, seed=6101)
+    m = Transformer(dropout=p, **PARAMS)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    m = m.cuda().train()
+    opt = torch.optim.Adam(m.parameters(), lr=1e-4, fused=True)
+    x = (torch.from_numpy(uniform(1, f"bench.{B}", (B, PARAMS["in_channels"], T), -1.0, 1.0)) * valid[:, None, :]).cuda().contiguous()
+    y = (torch.from_numpy(uniform(2, f"bench.{B}", (B, PARAMS["out_channels"], T), -1.0, 1.0)) * valid[:, None, :]).cuda().contiguous()
+    lens32 = lengths.to(torch.int32)
+
+    def make(loss_fn):
+        def step(_=None):
+            opt.zero_grad(set_to_none=True)
+            loss_fn().backward()
+            opt.step()
+
+        return step
+
+    legs = {"native_ragged": make(lambda: masked_l1_loss(m.forward_padded(x, lens32), y, lens32)), "native_dense": make(lambda: F.l1_loss(m(x), y))}
+    for _ in range(2):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(2):
+        for k, fn in legs.items():
+            ms[k].append(window(fn, None, a.window))
+    tiles = sum((T + 63) // 64 - (int(n) + 63) // 64 for n in lengths)
+    res = {"train": True, "case": "ragged", "B": B, "T": T, "dropout": p, "seed": a.seed, "valid_frames": M, "padded_share": round(1.0 - M / (B * T), 4),
+           "skipped_attention_tiles": tiles, "attention_tiles": B * ((T + 63) // 64)}
+    for k, v in ms.items():
+        res[k + "_step_ms"] = [round(u, 3) for u in v]
+        res[k + "_spread"] = round(abs(v[0] - v[1]) / min(v), 4)
+    res["dense_over_ragged"] = round(min(ms["native_dense"]) / max(ms["native_ragged"]), 3)  # slowest ragged, fastest dense
+    lib, eng = m._lib, m.engine()
+    profs = {}
+    for tag in ("ragged", "dense"):
+        _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
+        legs["native_" + tag]()
+        stats = (_native.HificarKernelStat * 128)()
+        n = ctypes.c_int()
+        _native.check(lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
+        profs[tag] = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+        res[tag + "_kernels_ms"] = {k: round(v, 4) for k, v in sorted(profs[tag].items(), key=lambda kv: -kv[1])}
+        res[tag + "_kernels_total_ms"] = round(sum(profs[tag].values()), 3)
+    res["attention_recovered_ms"] = {k: round(profs["dense"].get(k, 0.0) - profs["ragged"].get(k, 0.0), 4)
+                                     for k in ("xfmr_attn_kernel<train>", "xfmr_attn_bwd_kernels")}
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--train", action="store_true")
@@ -152,7 +223,13 @@ def main():
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--no-stock", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ragged", action="store_true", help="--train: the ragged batch's two legs instead of the dense shapes")
+    ap.add_argument("--seed", type=int, default=0, help="--train --ragged: seed of the lengths")
     a = ap.parse_args()
+    if a.ragged and not a.train:
+        ap.error("--ragged goes with --train")
+    if a.train and a.ragged:
+        return ragged_train_main(a)
     if a.train:
         return train_main(a)
     T = a.frames
