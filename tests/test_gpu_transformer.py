@@ -101,14 +101,38 @@ def test_batch_of_three_T263(gold):
     assert err < TOL
 
 
-@pytest.mark.parametrize("hidden", [256, 512])
+@pytest.mark.parametrize("hidden", [256, 384, 512, 640, 896])
 def test_other_head_sizes(hidden):
+    """Head sizes 32 to 112: with the golden cases' 16 and 96 every xfmr_attn_kernel<D, false> instantiation but 128."""
     params = dict(in_channels=24, out_channels=40, elayers=1, hidden_dim=hidden)
     m, sd = build(params, 6200 + hidden)
     x = uniform(6200 + hidden, "x.201", (1, 24, 201), -1.0, 1.0)
     err = rel_err(m(dev(x)).cpu().numpy(), TransformerOracle(sd).forward(x).numpy())
     print(f"hidden {hidden}: {err:.3g}")
     assert err < TOL
+
+
+def test_ragged_batch_at_another_head_size():
+    """test_ragged_batch_equals_alone_bitwise at head size 80, whose lengths branch no other test takes: a ragged batch is bitwise its
+    sequences alone, each of which meets the float64 restatement."""
+    hidden, lens = 640, [201, 100]
+    params = dict(in_channels=24, out_channels=40, elayers=1, hidden_dim=hidden)
+    m, sd = build(params, 6200 + hidden)
+    o = TransformerOracle(sd)
+    x = uniform(6200 + hidden, "ragged.x", (2, 24, 201), -1.0, 1.0)
+    xd = dev(x)
+    y = m(xd, lengths=lens)
+    assert y.shape == (2, 40, 201)
+    for b, n in enumerate(lens):
+        alone = m(xd[b:b + 1, :, :n].contiguous())
+        assert torch.equal(alone[0], y[b, :, :n]), (b, n)
+        assert not y[b, :, n:].any(), b
+        err = rel_err(alone.cpu().numpy(), o.forward(x[b:b + 1, :, :n]).numpy())
+        print(f"hidden {hidden} ragged, sequence {b} ({n} frames): {err:.3g}")
+        assert err < TOL
+    xn = xd.clone()
+    xn[1, :, 100:] = float("nan")  # what the input holds past a length is never used
+    assert torch.equal(m(xn, lengths=lens), y)
 
 
 def test_default_size_batch(gold):

@@ -31,8 +31,10 @@ def dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to("cuda:0")
 
 
-def build(name, seed=O.DROPOUT_SEED):
-    params, sd, x, t = O.case(name)
+def build(name, seed=O.DROPOUT_SEED, shapes=None):
+    """The model of an entry of ``shapes`` (transformer_train_oracle.SHAPES, or its EDGE_SHAPES) on the device in train() mode, and the
+    entry's batch."""
+    params, sd, x, t = O.case(name, shapes=shapes)
     m = Transformer(**params)
     m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
     m = m.to("cuda:0").train()
@@ -64,10 +66,11 @@ def step(m, x, t, need_dx=True, gates=None):
                 stats=m._last_stats.clone(), running={k: v.detach().clone() for k, v in m.named_buffers() if k.endswith(("running_mean", "running_var"))})
 
 
-def reference(name, gates):
+def reference(name, gates, shapes=None, device="cpu"):
     """The float64 restatement's step on a shape, every ReLU taken on the side the device took it (TransformerTrainOracle explains why);
-    a gate may differ from the float64 run's own only where the ReLU's input is within GATE_GAP (the output bar) of zero."""
-    ref = O.restatement(name, torch.float64, gates=gates)
+    a gate may differ from the float64 run's own only where the ReLU's input is within GATE_GAP (the output bar) of zero.  ``device``: where
+    the restatement (stock PyTorch in float64) runs."""
+    ref = O.restatement(name, torch.float64, device=device, gates=gates, shapes=shapes)
     print(f"  {name}: {ref['gate_flips']} ReLU(s) on the other side than float64's own, the farthest {ref['gate_gap']:.3g} of max |x| from zero")
     assert ref["gate_gap"] < O.GATE_GAP
     return ref
@@ -213,9 +216,13 @@ def test_deterministic_new_masks_streams_dirty_scratch_and_dx_on_request():
 
 
 def test_refusals_on_the_device():
+    """forward(lengths=...) in train() mode stays refused now that ragged training exists: it is asked for by name, and the refusal names
+    the way in (forward_padded; tests/test_gpu_transformer_ragged.py holds that call's own refusals)."""
     m, x, t = build("t2")
-    with pytest.raises(NotImplementedError, match="ragged training"):
+    before = (m._calls, int(m.conv_blocks[0].bn1.num_batches_tracked))
+    with pytest.raises(NotImplementedError, match=r"forward\(lengths=\.\.\.\) in train\(\) mode is refused: ragged training.*forward_padded\(x, lengths\)"):
         m(dev(x), lengths=[2, 1])
+    assert (m._calls, int(m.conv_blocks[0].bn1.num_batches_tracked)) == before  # a refused call draws no mask and tracks no batch
     with pytest.raises(ValueError, match="more than 1 value per channel"):
         m(dev(x[:1, :, :1]))
 

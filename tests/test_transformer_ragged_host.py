@@ -32,14 +32,15 @@ def test_ragged_shape_is_admitted(name):
 
 def test_shapes_are_the_issues_table():
     S = R.RAGGED_SHAPES
-    assert list(S) == ["mixed", "tiles", "band", "band2", "zero", "chunks", "d96", "d128", "nores", "b1"]
+    assert list(S) == ["mixed", "tiles", "band", "band2", "zero", "chunks", "d96", "d128", "nores", "b1", "d32", "d64"]
     assert [(v[1], v[2], v[3], v[4]) for v in S.values()] == [
         (3, 70, (70, 33, 1), 0.2), (4, 130, (64, 65, 128, 130), 0.5), (2, 263, (263, 100), 0.2), (2, 201, (201, 99), 0.0),
         (3, 65, (65, 0, 2), 0.0), (3, 200, (200, 57, 143), 0.2), (2, 130, (130, 71), 0.2), (2, 70, (70, 17), 0.2), (2, 65, (65, 40), 0.2),
-        (1, 100, (37,), 0.5)]
+        (1, 100, (37,), 0.5), (2, 130, (130, 71), 0.2), (2, 130, (130, 71), 0.2)]
     assert S["d96"][0]["hidden_dim"] == 768 and S["d128"][0]["hidden_dim"] == 1024 and S["d96"][0]["elayers"] == S["d128"][0]["elayers"] == 1
+    assert S["d32"][0] == dict(S["d96"][0], hidden_dim=256) and S["d64"][0] == dict(S["d96"][0], hidden_dim=512)  # the head sizes people train at
     assert S["nores"][0]["in_channels"] == S["nores"][0]["hidden_dim"] == 128
-    assert all(v[0] == O.BASE for k, v in S.items() if k not in ("d96", "d128", "nores"))
+    assert all(v[0] == O.BASE for k, v in S.items() if k not in ("d96", "d128", "nores", "d32", "d64"))
 
 
 def test_all_lengths_full_is_the_dense_restatement():

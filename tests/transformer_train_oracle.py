@@ -45,6 +45,31 @@ SEEDS = {name: 8100 + i for i, name in enumerate(SHAPES)}
 # that the restatement's own float32 run takes the other side of the ReLU than its float64 run (linear1.weight's gradient then differs by a
 # whole row: 243, 306 and 264 bars; d128 again at 8200: 45 bars).
 SEEDS.update(t200=8200, d96=8200, d128=8201)
+# The shapes of tests/test_gpu_transformer_train_edges.py, in SHAPES' layout: what SHAPES leaves out in every direction but T.  One trip of an
+# element-wise grid-stride loop (hificar_xfmr_train.hip.inc: ew_grid caps the grid at 4096 workgroups of 256 threads of 4 floats) covers
+# 4096 * 256 * 4 = 4 194 304 floats; the column sums and the table gradient work in chunks of 256 rows (kXfmrColRows, kXfmrEmbRows).
+_ONE = dict(in_channels=12, out_channels=8, elayers=1)
+EDGE_SHAPES = OrderedDict([
+    ("d32", (dict(_ONE, hidden_dim=256), 2, 130, 0.2)),    # the <32> attention / table-gradient instantiations: band edge, a third query tile
+    ("d48", (dict(_ONE, hidden_dim=384), 2, 130, 0.2)),    # <48>
+    ("d64", (dict(_ONE, hidden_dim=512), 2, 130, 0.2)),    # <64>
+    ("d80", (dict(_ONE, hidden_dim=640), 2, 130, 0.2)),    # <80>
+    ("d112", (dict(_ONE, hidden_dim=896), 2, 70, 0.2)),    # <112>
+    ("t330", (BASE, 1, 330, 0.2)),                         # a query tile and a key tile whose band no end of the sequence clips (bwd_q / bwd_k)
+    ("rows1380", (BASE, 6, 230, 0.2)),                     # 1380 * 3072 > 4 194 304: second trip of the 3072-wide gate launches; six 256-row chunks, the last partial
+    ("rows4112", (dict(_ONE, hidden_dim=1024), 16, 257, 0.2)),  # 4112 * 1024 > 4 194 304: second trip of bn_apply, the conv ReLU gates and add-drop; 17 chunks; gridDim.z = 16
+    ("io", (dict(in_channels=40, out_channels=80, elayers=1, hidden_dim=128), 2, 65, 0.2)),  # cin_pad 64; three channel tiles in xfmr_out_kernel / xfmr_drows_kernel, the last half full
+])
+assert not set(EDGE_SHAPES) & set(SHAPES)
+SEEDS.update({name: 8500 + i for i, name in enumerate(EDGE_SHAPES)})
+# Seeds changed by the admission rule, as above, never by a device result.  d48 at 8501: one feed-forward hidden value within float32 rounding
+# of zero (conv_blocks.1.conv2.weight's gradient differs by 140 bars between the restatement's float32 and float64 runs).  d32 at 8500 and io
+# at 8508 pass with the float32 sums split over four or eight threads and miss on one (89 bars on layers.0.linear1.weight, 899 bars on
+# conv_blocks.2.conv1.weight): the rule is to hold whatever the host; 8600, 8601 and 8608 hold on 1, 2, 4 and 8 threads.
+SEEDS.update(d32=8600, d48=8601, io=8608)
+# Admitted in the gated form (tests/test_transformer_train_host.py: test_edge_shape_is_admitted says why): no seed keeps the 8.5 M and
+# 12.6 M feed-forward ReLU inputs of these two off the kink in every float32 arithmetic.
+GATED_ADMISSION = ("rows1380", "rows4112")
 GOLD_CASE = "t101"
 DROPOUT_SEED = 777
 BARS = dict(out=2e-5, loss=1e-5, grad=2e-4)  # the BiGRU training suite's bars: relative to each tensor's max; the loss relative
@@ -53,9 +78,10 @@ STEPS = dict(n=5, lr=1e-3, grad_norm=10.0, step_size=1, gamma=0.5, lambda_aux=1.
 FULL_LIMIT, SAMPLES = 16384, 4096  # golden gradients: whole up to FULL_LIMIT elements, else SAMPLES seeded entries + float64 sum and L2 norm
 
 
-def case(name, step=0):
-    """(model params with dropout, state_dict, x (B, in, T), target (B, out, T)) of a SHAPES entry; ``step`` draws another batch."""
-    params, B, T, p = SHAPES[name]
+def case(name, step=0, shapes=None):
+    """(model params with dropout, state_dict, x (B, in, T), target (B, out, T)) of an entry of ``shapes`` (SHAPES, or EDGE_SHAPES); ``step``
+    draws another batch."""
+    params, B, T, p = (SHAPES if shapes is None else shapes)[name]
     seed = SEEDS[name]
     x = uniform(seed, f"x.{step}", (B, params["in_channels"], T), -1.0, 1.0)
     # |y| is a few tenths: targets in +-[4, 5] keep every |y - target| off the L1 kink
@@ -71,13 +97,14 @@ def relu_names(params):
     return [f"conv_blocks.{i}.relu{j}" for i in range(3) for j in (1, 2)] + [f"layers.{l}.hidden" for l in range(params["elayers"])]
 
 
-def restatement(name, dtype, device="cpu", gates=None):
-    """One step of the restatement on a SHAPES entry: step()'s dict + running buffers {name: tensor} + kink (+ gate_gap, gate_flips with
-    ``gates``: see TransformerTrainOracle)."""
-    params, sd, x, t = case(name)
+def restatement(name, dtype, device="cpu", gates=None, shapes=None):
+    """One step of the restatement on an entry of ``shapes`` (SHAPES, or EDGE_SHAPES): step()'s dict + running buffers {name: tensor} + kink
+    + sides (which side of every ReLU this run took: another run's ``gates``) (+ gate_gap, gate_flips with ``gates``: see
+    TransformerTrainOracle)."""
+    params, sd, x, t = case(name, shapes=shapes)
     o = TransformerTrainOracle(sd, dtype=dtype, device=device, dropout=params["dropout"], seed=DROPOUT_SEED, gates=gates)
     r = o.step(x, t)
-    r["gate_gap"], r["gate_flips"] = o.gate_gap, o.gate_flips
+    r["gate_gap"], r["gate_flips"], r["sides"] = o.gate_gap, o.gate_flips, o.sides
     r["running"] = dict(o.buffers)
     r["kink"] = float((r["out"] - torch.from_numpy(t).to(r["out"])).abs().min() / r["out"].abs().max())
     return r
@@ -149,6 +176,7 @@ class TransformerTrainOracle:
         disagreeing gate was is recorded (``gate_gap``: |x| / max |x|, and ``gate_flips``), for the caller to bound."""
         self.dtype, self.device, self.p, self.seed = dtype, device, float(dropout), int(seed)
         self.gates, self.gate_gap, self.gate_flips = gates, 0.0, 0
+        self.sides = {}  # {ReLU name: bool tensor}: which side of zero every ReLU input of the last forward lay on, in the layout of ``gates``
         self.params, self.buffers = {}, {}
         for k, v in state_dict.items():
             if k.endswith("num_batches_tracked") or k in ("mean", "scale"):
@@ -178,11 +206,12 @@ class TransformerTrainOracle:
     def _relu(self, x, name):
         with torch.no_grad():
             self.min_relu_margin = min(self.min_relu_margin, float(x.abs().min() / x.abs().max()))
+            self.sides[name] = x > 0
         if self.gates is None:
             return torch.relu(x)
         g = self.gates[name].to(x.device)
         with torch.no_grad():
-            differ = (x > 0) != g
+            differ = self.sides[name] != g
             if bool(differ.any()):
                 self.gate_gap = max(self.gate_gap, float(x.abs()[differ].max() / x.abs().max()))
                 self.gate_flips += int(differ.sum())
