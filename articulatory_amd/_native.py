@@ -127,6 +127,11 @@ SYMBOLS = (
     "hificar_xfmr_forward_train",
     "hificar_xfmr_forward_train_ragged",
     "hificar_xfmr_backward",
+    "hificar_xfmr_packed_rows",
+    "hificar_xfmr_tape_bytes_packed",
+    "hificar_xfmr_train_workspace_bytes_packed",
+    "hificar_xfmr_forward_train_packed",
+    "hificar_xfmr_backward_packed",
     "hificar_destroy",
     "hificar_last_error",
     "hificar_version",
@@ -534,6 +539,16 @@ def load_library():
     lib.hificar_xfmr_forward_train_ragged.restype = ci
     lib.hificar_xfmr_backward.argtypes = [vp, vp, ci, ci, vp, cs, vp, vp, vp, cs, vp]
     lib.hificar_xfmr_backward.restype = ci
+    lib.hificar_xfmr_packed_rows.argtypes = [ci, ci, vp]
+    lib.hificar_xfmr_packed_rows.restype = ci
+    lib.hificar_xfmr_tape_bytes_packed.argtypes = [vp, ci, ci]
+    lib.hificar_xfmr_tape_bytes_packed.restype = cs
+    lib.hificar_xfmr_train_workspace_bytes_packed.argtypes = [vp, ci, ci]
+    lib.hificar_xfmr_train_workspace_bytes_packed.restype = cs
+    lib.hificar_xfmr_forward_train_packed.argtypes = list(lib.hificar_xfmr_forward_train_ragged.argtypes)
+    lib.hificar_xfmr_forward_train_packed.restype = ci
+    lib.hificar_xfmr_backward_packed.argtypes = [vp, vp, vp, ci, ci, vp, cs, vp, vp, vp, cs, vp]
+    lib.hificar_xfmr_backward_packed.restype = ci
     lib.hificar_destroy.argtypes = [vp]
     lib.hificar_destroy.restype = None
     lib.hificar_last_error.argtypes = []

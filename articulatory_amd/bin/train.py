@@ -647,8 +647,9 @@ class InversionTrainer:
     ``package_mode: pad`` (batches of ``PadCollater``: whole utterances with their lengths): the step is ``forward_padded`` ->
     ``masked_l1_loss`` * lambda_aux, the rest as above; the padding takes no part in statistics, loss or gradients (the reference's pad mode
     trains on it).  ``package_mode: pad_masked`` (this package's key) is the same step under a name that says what it does; it is the way
-    in for the Transformer, for which ``pad`` stays refused.  ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval
-    mode, under ``masked_l1_loss``."""
+    in for the Transformer, for which ``pad`` stays refused.  ``pad_packed: true`` (this package's key, default false; the Transformer under
+    ``pad_masked`` only): the same step through ``forward_padded(..., packed=True)``, which spends no GEMM rows on the padding.
+    ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval mode, under ``masked_l1_loss`` (``pad_packed`` plays no part there)."""
 
     def __init__(self, config, device):
         self.config, self.device = config, device
@@ -676,6 +677,11 @@ class InversionTrainer:
                                       "this package masks it; ask for that by name with package_mode pad_masked (ragged training on whole "
                                       "utterances), or use package_mode random_window")
         self.padded = self.package_mode in PADDED_MODES
+        self.packed = bool(config.get("pad_packed", False))
+        if self.packed and (gtype != "Transformer" or self.package_mode != "pad_masked"):
+            raise NotImplementedError(f"pad_packed is built for generator_type Transformer with package_mode pad_masked (got {gtype} with "
+                                      f"package_mode {self.package_mode}): the BiGRU has no packed form; drop the key, or set package_mode: "
+                                      "pad_masked for the Transformer")
         import articulatory_amd.models as models
 
         self.G = getattr(models, gtype)(**config["generator_params"]).to(device).train()
@@ -695,7 +701,7 @@ class InversionTrainer:
             raise ValueError(f"package_mode {self.package_mode}: the batch has no lengths (batch keys {sorted(batch)}); build it with PadCollater")
         if self.steps > cfg.get("generator_train_start_steps", 0):  # train.py:268
             if self.padded:
-                y_ = self.G.forward_padded(x, batch["lengths"])
+                y_ = self.G.forward_padded(x, batch["lengths"], packed=True) if self.packed else self.G.forward_padded(x, batch["lengths"])
                 mel_loss = masked_l1_loss(y_, y, batch["lengths"])
             else:
                 y_ = self.G(x)

@@ -383,7 +383,7 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
     {
         ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
         hipLaunchKernelGGL(xfmr_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, ws.xin,
-                           lengths, C, g->cin_pad, T);
+                           lengths, C, g->cin_pad, T, nullptr);
         HIP_TRY(hipGetLastError());
     }
     // conv_blocks: the block's input in `in`, its output in r[2] (blocks 0 and 2) or r[1] (block 1); r[0] holds conv1's ReLU'd output
@@ -435,7 +435,7 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
         const int Op = g->w_out.cout_pad;
         ProfScope prof(h, stream, "xfmr_out_kernel", 0.0, 4.0 * M * (O + Op));
         hipLaunchKernelGGL(xfmr_out_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, ws.wide, out, lengths, O,
-                           Op, T);
+                           Op, T, nullptr);
         HIP_TRY(hipGetLastError());
     }
     return HIFICAR_OK;

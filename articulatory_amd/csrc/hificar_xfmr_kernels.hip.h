@@ -46,6 +46,7 @@ struct XfmrAttnParams {
     float* lse = nullptr;                   // [B][8][T]: m + log l of every query's softmax
     const BigruTapeHeader* hdr = nullptr;   // seed, offset and p of the dropout on the probabilities
     int site = 0;
+    const int* row0 = nullptr;              // [B + 1]: the packed layout (sequence b's rows start at row0[b]; lse is [rows][8]); null: b T
 };
 
 // Dropout of the Transformer's training step: the BiGRU's generator (BigruDrop: splitmix64 of key + element, top 24 bits against p) with a
@@ -97,6 +98,15 @@ __device__ __forceinline__ void xfmr_zero_head_row(float* row4g, bool in_tensor)
 // TRAIN (the training forward): the kept probabilities are scaled by the dropout factor before P V (the denominator sums all of them, as
 // F.softmax followed by nn.Dropout does), L = m + log l is kept per query, and the `out` rows of padded frames are written as zeros (a
 // workgroup whose 64 queries are all padded writes them and returns).  The eval instantiation compiles none of it.
+// first row of sequence b: b T, or the packed layout's table (training only)
+template <bool TRAIN>
+__device__ __forceinline__ size_t xfmr_attn_row0(const XfmrAttnParams& p, int b) {
+    if constexpr (TRAIN) {
+        if (p.row0) return (size_t)p.row0[b];
+    }
+    return (size_t)b * p.T;
+}
+
 template <int D, bool TRAIN = false>
 __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) {
     extern __shared__ float xfmr_lds[];
@@ -108,12 +118,13 @@ __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) 
     const int c = lane & 15, g = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kXfmrTQ;
     const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
-    const size_t row0 = (size_t)b * p.T;
+    const size_t row0 = xfmr_attn_row0<TRAIN>(p, b);
     const size_t F3 = (size_t)3 * p.F;
     const int qw = q0 + wave * 16, q = qw + c;
     const bool qok = q < len;
     if (q0 >= len) {  // (the whole workgroup: no barrier has been reached, nothing staged)
-        if constexpr (TRAIN) xfmr_zero_head_row<D>(p.out + (row0 + q) * p.F + h * D + 4 * g, q < p.T);
+        // (packed: the rows past a length are another sequence's; the gap rows are xfmr_zero_gaps_kernel's)
+        if constexpr (TRAIN) xfmr_zero_head_row<D>(p.out + (row0 + q) * p.F + h * D + 4 * g, q < p.T && !p.row0);
         return;
     }
 
@@ -228,12 +239,12 @@ __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) 
     }
     if (!qok) {
         // (training: w_o's GEMM and its weight gradient read every row of `out`; a padded frame's is zeros)
-        if constexpr (TRAIN) xfmr_zero_head_row<D>(p.out + (row0 + q) * p.F + h * D + 4 * g, q < p.T);
+        if constexpr (TRAIN) xfmr_zero_head_row<D>(p.out + (row0 + q) * p.F + h * D + 4 * g, q < p.T && !p.row0);
         return;
     }
     const float inv = 1.f / l;  // (l >= 1: the query's own key is in its band)
     if constexpr (TRAIN) {
-        if (g == 0) p.lse[((size_t)b * kXfmrHeads + h) * p.T + q] = m + logf(l);
+        if (g == 0) p.lse[p.row0 ? (row0 + q) * kXfmrHeads + h : ((size_t)b * kXfmrHeads + h) * p.T + q] = m + logf(l);
     }
     float* orow = p.out + (row0 + q) * p.F + h * D + 4 * g;
 #pragma unroll
@@ -254,6 +265,7 @@ struct XfmrLnParams {
     float* y;
     int B, T, F;
     int zero_pad = 0;  // 1 (the ragged training step): rows at or past a length are written as zeros
+    const int* pad_row = nullptr;  // the packed training step (B = 1, T = the packed rows, lengths null): a row r with pad_row[r] < 0 is a gap row
 };
 
 __device__ __forceinline__ float xfmr_wave_sum(float v) {
@@ -269,7 +281,7 @@ __global__ __launch_bounds__(256) void xfmr_ln_kernel(const XfmrLnParams p) {
     const int b = (int)(row / p.T), t = (int)(row - (long long)b * p.T);
     const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
     const int nv = p.F >> 2;
-    if (t >= len) {
+    if (p.pad_row ? p.pad_row[row] < 0 : t >= len) {
         if (p.zero_pad)
             for (int i = lane; i < nv; i += 64) reinterpret_cast<float4*>(p.y + row * p.F)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
@@ -306,9 +318,9 @@ __global__ __launch_bounds__(256) void xfmr_ln_kernel(const XfmrLnParams p) {
 }
 
 // x (B, C, T) fp32 -> rows [b T + t][Cp] (channels last; columns C .. Cp - 1 and frames at or past the sequence's length are zeros, the
-// latter without being read)
+// latter without being read).  row0 (the packed training step, null otherwise): rows [row0[b] + t], a sequence's own frames only
 __global__ __launch_bounds__(256) void xfmr_rows_kernel(const float* __restrict__ x, float* __restrict__ rows, const int* __restrict__ lengths, int C,
-                                                        int Cp, int T) {
+                                                        int Cp, int T, const int* __restrict__ row0) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -318,22 +330,26 @@ __global__ __launch_bounds__(256) void xfmr_rows_kernel(const float* __restrict_
         tile[r][tx] = (c < C && t < len) ? x[((size_t)b * C + c) * T + t] : 0.f;
     }
     __syncthreads();
+    const size_t base = row0 ? (size_t)row0[b] : (size_t)b * T;
+    const int tw = row0 ? len : T;
     for (int r = ty; r < 32; r += 8) {
         const int t = t0 + r, c = c0 + tx;
-        if (t < T && c < Cp) rows[((size_t)b * T + t) * Cp + c] = tile[tx][r];
+        if (t < tw && c < Cp) rows[(base + t) * Cp + c] = tile[tx][r];
     }
 }
 
 // rows [b T + t][Cp] -> out (B, C, T); frames at or past the sequence's length are written as zeros (their rows are not read)
+// row0 (the packed training step, null otherwise): rows [row0[b] + t]
 __global__ __launch_bounds__(256) void xfmr_out_kernel(const float* __restrict__ rows, float* __restrict__ out, const int* __restrict__ lengths, int C,
-                                                       int Cp, int T) {
+                                                       int Cp, int T, const int* __restrict__ row0) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int len = lengths ? min(max(lengths[b], 0), T) : T;
+    const size_t base = row0 ? (size_t)row0[b] : (size_t)b * T;
     for (int r = ty; r < 32; r += 8) {
         const int t = t0 + r, c = c0 + tx;
-        tile[r][tx] = (t < len && c < Cp) ? rows[((size_t)b * T + t) * Cp + c] : 0.f;
+        tile[r][tx] = (t < len && c < Cp) ? rows[(base + t) * Cp + c] : 0.f;
     }
     __syncthreads();
     for (int r = ty; r < 32; r += 8) {

@@ -12,6 +12,9 @@
 // kernels and of the attention kernels: a k = 3 conv then sees zero padding at a sequence's own end, and a weight gradient adds 0 * finite)
 // or as the finite output of a GEMM over such rows, which only a row-wise kernel or a predicate-guarded sum reads next.  DESIGN.md 3.10
 // lists the buffers.  Kernels: hificar_xfmr_train_kernels.hip.h.
+// Packed batches (hificar_xfmr_forward_train_packed / hificar_xfmr_backward_packed): the ragged step on Mp = sum (length + 1) rows, rounded up to
+// 256, instead of B T: every sequence's frames back to back with one zero gap row behind each, so that every launch — k = 3 included — is one run
+// of Mp rows; the same code path with XfmrTrainCtx::lay set.  The same buffer rule with "gap row" for "padded row".
 
 struct XfmrTrainLayer {
     ConvLayer dg_qkv, dg_wo, dg_l1, dg_l2;
@@ -41,6 +44,14 @@ struct XfmrTrain {
     ConvLayer dg_win, dg_wout;
     std::vector<XfmrTrainLayer> enc;
     bool have_params = false;
+    // The packed tapes this handle filled, by address, with the frame counts their forward ran on: what lets a backward refuse, before it
+    // enqueues anything, a tape of the other kind or other counts than the forward's (the tape's own header lives on the device).  A dense
+    // or ragged forward into the same memory takes the entry out.
+    struct PackedTape {
+        int B, T;
+        std::vector<int32_t> lengths;
+    };
+    std::map<const void*, PackedTape> packed_tapes;
 };
 
 static void xfmr_train_free(hificar_xfmr* g) {
@@ -78,7 +89,7 @@ static hipError_t xfmr_attn_bwd_launch(const XfmrAttnBwdParams& p, dim3 grid, fl
     hipLaunchKernelGGL((xfmr_attn_bwd_q_kernel<D>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
     hipLaunchKernelGGL((xfmr_attn_bwd_k_kernel<D>), grid, dim3(256), XfmrAttnBwdKLds<D>::bytes, stream, p);
     hipLaunchKernelGGL((xfmr_demb_partial_kernel<D>), dim3((unsigned)chunks, kXfmrHeads), dim3(256), XfmrEmbLds<D>::bytes, stream, p.qkv, p.ds, emb_partial, M,
-                       p.T, p.F, p.hdr, p.lens);
+                       p.T, p.F, p.hdr, p.lens, p.lay);
     return hipGetLastError();
 }
 
@@ -341,6 +352,22 @@ extern "C" int hificar_xfmr_set_parameters_device(hificar_xfmr* g, const char* c
 // ------------------------------------------------------------------------------------------------
 static size_t xfmr_train_rows(int B, int T) { return round_up_sz((size_t)B * (size_t)T + 64, 256); }  // slack behind the last row for whole GEMM tiles
 
+// Mp of a packed batch: every sequence's frames and one gap row behind each, rounded up to kXfmrPackGranule rows (the tail: gap rows).
+// 256 = kXfmrColRows = kXfmrEmbRows: whole chunks for the column sums and the table gradient, and few distinct row counts per length
+// bucket for the conv engine's plan cache, which is keyed by the row count.  0: a length outside 0 .. T, or fewer than two frames.
+constexpr int kXfmrPackGranule = 256;
+static long long xfmr_packed_rows(int B, int T, const int32_t* lengths_host, long long* valid = nullptr) {
+    if (B < 1 || T < 1 || !lengths_host) return 0;
+    long long m = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths_host[b] < 0 || lengths_host[b] > T) return 0;
+        m += lengths_host[b];
+    }
+    if (valid) *valid = m;
+    if (m < 2) return 0;
+    return (m + B + kXfmrPackGranule - 1) / kXfmrPackGranule * kXfmrPackGranule;
+}
+
 struct XfmrTapeLayer {
     float *qkv, *o, *lse, *p1, *n1, *hid, *p2;
 };
@@ -355,11 +382,13 @@ struct XfmrTape {
     std::vector<float*> X;  // [elayers + 1]: the encoder layers' inputs, and the last one's output
     std::vector<XfmrTapeLayer> L;
     int* lens;  // [B] frame counts of a ragged forward (the header says whether they hold)
+    int *row0, *pad_row;  // a packed forward's tables, [B + 1] and [Mp] (XfmrLayout); null otherwise
     size_t bytes;
 };
 
-static XfmrTape xfmr_plan_tape(const hificar_xfmr* g, int B, int T, void* base) {
-    const size_t rows = xfmr_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;
+// Mp = 0: the rows of the padded batch (dense, ragged); Mp > 0: a packed batch of Mp rows (T plays no part)
+static XfmrTape xfmr_plan_tape(const hificar_xfmr* g, int B, int T, void* base, int Mp = 0) {
+    const size_t rows = Mp ? (size_t)Mp : xfmr_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;  // (Mp: a multiple of 256 already, as the eval path's rows)
     const int nbn = g->rp.cout ? 7 : 6;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -393,6 +422,8 @@ static XfmrTape xfmr_plan_tape(const hificar_xfmr* g, int B, int T, void* base) 
         L.p2 = take(rows * F * 4);
     }
     t.lens = reinterpret_cast<int*>(take((size_t)B * 4));
+    t.row0 = Mp ? reinterpret_cast<int*>(take(((size_t)B + 1) * 4)) : nullptr;
+    t.pad_row = Mp ? reinterpret_cast<int*>(take((size_t)Mp * 4)) : nullptr;
     t.bytes = off;
     return t;
 }
@@ -404,7 +435,7 @@ struct XfmrTrainWs {
     float* wide;     // [rows][3072]: dropout(hidden rows); w_out's rows; dout as rows
     float* gw;       // [rows][3072]: gradient of the hidden rows; dq | dk | dv
     float* dxr[2];   // [rows][cin_pad]
-    float* ds;       // [B][8][T][200] banded dS
+    float* ds;       // [B][8][T][200] banded dS (packed: [Mp][8][200])
     float* pd;       // ... and the dropped probabilities
     float* rowstats; // [rows][2]
     float* colpart;  // [chunks][2][F]
@@ -416,9 +447,9 @@ struct XfmrTrainWs {
     size_t bytes;
 };
 
-static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void* base) {
-    const size_t rows = xfmr_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;
-    const int M = B * T;
+static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void* base, int Mp = 0) {
+    const int M = Mp ? Mp : B * T;
+    const size_t rows = Mp ? (size_t)Mp : xfmr_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;
     size_t off = 0;
     auto take = [&](size_t bytes) {
         char* p = base ? static_cast<char*>(base) + off : nullptr;
@@ -444,7 +475,7 @@ static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void*
             w.partial_elems = std::max(w.partial_elems, wgrad_partial_elems(h, L, nseq, r));
             w.colsum_elems = std::max(w.colsum_elems, wgrad_colsum_elems(h, L, nseq, r));
         };
-        for (const auto& bn : g->train->bns) one(bn.raw, bn.raw.K > 1 ? B : 1, bn.raw.K > 1 ? T : M);
+        for (const auto& bn : g->train->bns) one(bn.raw, bn.raw.K > 1 && !Mp ? B : 1, bn.raw.K > 1 && !Mp ? T : M);
         one(g->w_in, 1, M);
         one(g->w_out, 1, M);
         for (const auto& L : g->enc) {
@@ -456,7 +487,7 @@ static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void*
     }
     w.partial = take(w.partial_elems * 4);
     w.colsum = take(w.colsum_elems * 4);
-    w.light = reinterpret_cast<char*>(take(xfmr_plan_tape(g, B, T, nullptr).bytes));
+    w.light = reinterpret_cast<char*>(take(xfmr_plan_tape(g, B, T, nullptr, Mp).bytes));
     w.bytes = off;
     return w;
 }
@@ -471,18 +502,40 @@ extern "C" size_t hificar_xfmr_train_workspace_bytes(hificar_xfmr* g, int B, int
     return xfmr_plan_train_ws(g, B, T, nullptr).bytes;
 }
 
+static bool xfmr_packed_size_ok(int B, int Mp) {
+    return B >= 1 && B <= 65535 && Mp >= kXfmrPackGranule && Mp % kXfmrPackGranule == 0 && (long long)Mp * kXfmrFF < (1LL << 31);
+}
+
+extern "C" int hificar_xfmr_packed_rows(int B, int T, const int32_t* lengths_host) {
+    const long long mp = xfmr_packed_rows(B, T, lengths_host);
+    return mp * kXfmrFF < (1LL << 31) ? (int)mp : 0;
+}
+
+extern "C" size_t hificar_xfmr_tape_bytes_packed(const hificar_xfmr* g, int B, int Mp) {
+    if (!g || !g->finalized || !xfmr_packed_size_ok(B, Mp)) return 0;
+    return xfmr_plan_tape(g, B, 0, nullptr, Mp).bytes;
+}
+
+extern "C" size_t hificar_xfmr_train_workspace_bytes_packed(hificar_xfmr* g, int B, int Mp) {
+    if (!g || !xfmr_packed_size_ok(B, Mp) || xfmr_train_init(g) != HIFICAR_OK) return 0;
+    return xfmr_plan_train_ws(g, B, 0, nullptr, Mp).bytes;
+}
+
 static int xfmr_train_check(hificar_xfmr* g, const char* what, int B, int T, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
-                            bool tape_optional = false) {
+                            bool tape_optional = false, int Mp = 0) {
     if (!g) return fail(HIFICAR_E_INVALID, "%s: null handle", what);
     int rc = xfmr_train_init(g);
     if (rc != HIFICAR_OK) return rc;
     if (!g->train->have_params) return fail(HIFICAR_E_STATE, "%s before hificar_xfmr_set_parameters_device", what);
-    if (B < 1 || T < 1 || B > 65535 || (long long)B * T > (1LL << 30) / 8 || (long long)B * T * kXfmrFF >= (1LL << 31))
+    if (Mp) {  // packed: the row-major indices are those of Mp rows; the padded index b T + t only has to fit an int
+        if (B < 1 || T < 1 || (long long)B * T > (1LL << 30) / 8 || !xfmr_packed_size_ok(B, Mp))
+            return fail(HIFICAR_E_INVALID, "%s: B=%d, T=%d, %d packed rows out of range (packed rows * 3072 < 2^31)", what, B, T, Mp);
+    } else if (B < 1 || T < 1 || B > 65535 || (long long)B * T > (1LL << 30) / 8 || (long long)B * T * kXfmrFF >= (1LL << 31))
         return fail(HIFICAR_E_INVALID, "%s: B=%d, T=%d out of range (B T 3072 < 2^31)", what, B, T);
     if ((long long)B * T < 2) return fail(HIFICAR_E_INVALID, "%s: batch statistics need more than one frame (B * T = 1)", what);
     if ((!tape && !tape_optional) || reinterpret_cast<uintptr_t>(tape) % 256 || !workspace || reinterpret_cast<uintptr_t>(workspace) % 256)
         return fail(HIFICAR_E_INVALID, "%s: tape and workspace must be 256-byte aligned device pointers", what);
-    const size_t tb = xfmr_plan_tape(g, B, T, nullptr).bytes, wb = xfmr_plan_train_ws(g, B, T, nullptr).bytes;
+    const size_t tb = xfmr_plan_tape(g, B, T, nullptr, Mp).bytes, wb = xfmr_plan_train_ws(g, B, T, nullptr, Mp).bytes;
     if (tape && tape_bytes < tb) return fail(HIFICAR_E_WORKSPACE, "%s: tape too small: %zu < %zu", what, tape_bytes, tb);
     if (workspace_bytes < wb) return fail(HIFICAR_E_WORKSPACE, "%s: workspace too small: %zu < %zu", what, workspace_bytes, wb);
     return HIFICAR_OK;
@@ -493,12 +546,14 @@ struct XfmrTrainCtx {
     hificar_xfmr* g;
     hificar_engine* h;
     hipStream_t stream;
-    int B, T, M, F;  // M = B T: the rows of the padded batch (the valid ones are counted by the tape's header)
+    int B, T, M, F;  // M = B T: the rows of the padded batch (the valid ones are counted by the tape's header); packed: Mp
     const BigruTapeHeader* hdr;
     const int* lens;      // the tape's frame counts (the kernels honour them when the header says ragged)
     const int* fwd_lens;  // the same for the kernels the eval path shares, which take no header: null in a dense forward
     const XfmrTrainWs* ws;
     BwdWs bw;
+    XfmrLayout lay;  // the packed form's tables: every GEMM is then one run of M rows, K = 3 included (the gap rows are the sequences' ends)
+    bool packed() const { return lay.pad_row != nullptr; }
 
     unsigned ew_grid(long long n) const { return (unsigned)std::min<long long>((n / 4 + 255) / 256, 4096); }
     // one launch of one layer over B sequences of T rows (K = 3: the sequences' own ends) or, seq = false, over the B T rows as one
@@ -511,10 +566,11 @@ struct XfmrTrainCtx {
         io[0].y = y;
         io[0].ys = reinterpret_cast<char*>(ys);
         const Ragged rg;
-        return seq ? launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream) : launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream);
+        return seq && !packed() ? launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream) : launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream);
     }
     int wgrad(const ConvLayer& L, const float* gr, int gpitch, const float* a, int apitch, float* dW, float* db) const {
-        return L.K > 1 ? launch_wgrad(h, L, gr, gpitch, a, apitch, B, T, dW, bw, stream, db) : launch_wgrad(h, L, gr, gpitch, a, apitch, 1, M, dW, bw, stream, db);
+        return L.K > 1 && !packed() ? launch_wgrad(h, L, gr, gpitch, a, apitch, B, T, dW, bw, stream, db)
+                                    : launch_wgrad(h, L, gr, gpitch, a, apitch, 1, M, dW, bw, stream, db);
     }
     int colsum(int mode, const float* x, const float* dy, const float* stats) const {
         XfmrColParams p;
@@ -529,6 +585,7 @@ struct XfmrTrainCtx {
         p.T = T;
         p.F = F;
         p.mode = mode;
+        p.lay = lay;
         hipLaunchKernelGGL(xfmr_colsum_kernel, dim3((unsigned)(F / 64), (unsigned)chunks()), dim3(256), 0, stream, p);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
@@ -554,7 +611,7 @@ struct XfmrTrainCtx {
         const long long n4 = (long long)M * F / 4;
         ProfScope prof(h, stream, "xfmr_bn_apply_kernel", 0.0, 4.0 * M * F * (res ? 3 : 2));
         hipLaunchKernelGGL(xfmr_bn_apply_kernel, dim3(ew_grid(4 * n4)), dim3(256), 0, stream, y, stats, gamma, gamma + F, res, out, n4, F, relu ? 1 : 0,
-                           fwd_lens, T);
+                           fwd_lens, T, lay);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
@@ -565,7 +622,7 @@ struct XfmrTrainCtx {
         if ((rc = colsum(2, y, dy, stats)) != HIFICAR_OK) return rc;
         if ((rc = pair_reduce(dgamma)) != HIFICAR_OK) return rc;
         const long long n = (long long)M * F;
-        hipLaunchKernelGGL(xfmr_bn_bwd_dx_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, y, dy, stats, gamma, dgamma, dgamma + F, dx, n, F, hdr, lens, T);
+        hipLaunchKernelGGL(xfmr_bn_bwd_dx_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, y, dy, stats, gamma, dgamma, dgamma + F, dx, n, F, hdr, lens, T, lay);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
@@ -577,9 +634,10 @@ struct XfmrTrainCtx {
         p.lengths = fwd_lens;
         p.zero_pad = 1;  // the next GEMM and its weight gradient read every row
         p.y = dst;
-        p.B = B;
-        p.T = T;
+        p.B = packed() ? 1 : B;
+        p.T = packed() ? M : T;
         p.F = F;
+        p.pad_row = lay.pad_row;
         ProfScope prof(h, stream, "xfmr_ln_kernel", 8.0 * M * F, 8.0 * M * F);
         hipLaunchKernelGGL(xfmr_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, p);
         HIP_TRY(hipGetLastError());
@@ -590,7 +648,7 @@ struct XfmrTrainCtx {
         int rc;
         // (dx is never dy here: the column sums below still read dy; the first pass leaves the row statistics for them)
         hipLaunchKernelGGL(xfmr_ln_bwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, dy, gamma, dx, ws->rowstats, (long long)M, F, hdr,
-                           lens, T);
+                           lens, T, lay);
         HIP_TRY(hipGetLastError());
         if ((rc = colsum(3, x, dy, nullptr)) != HIFICAR_OK) return rc;
         return pair_reduce(dgamma);
@@ -598,14 +656,21 @@ struct XfmrTrainCtx {
     int add_drop(const float* x, const float* t, float* out, int site) const {
         const long long n = (long long)M * F;
         ProfScope prof(h, stream, "xfmr_add_drop_kernel", 0.0, 12.0 * n);
-        hipLaunchKernelGGL(xfmr_add_drop_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, x, t, out, n, hdr, site, lens, F, T);
+        hipLaunchKernelGGL(xfmr_add_drop_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, x, t, out, n, hdr, site, lens, F, T, lay);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
     // out = (a > 0 ? d : 0) * dropout factor of `site` (a = null: no ReLU mask; site < 0: no dropout)
     int gate(const float* a, const float* dsrc, float* out, long long n, int site) const {
         ProfScope prof(h, stream, "xfmr_gate_kernel", 0.0, 4.0 * n * (a ? 3 : 2));
-        hipLaunchKernelGGL(xfmr_gate_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, a, dsrc, out, n, hdr, site, lens, (int)(n / M), T);
+        hipLaunchKernelGGL(xfmr_gate_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, a, dsrc, out, n, hdr, site, lens, (int)(n / M), T, lay);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+    // packed: zeros in the gap rows of rows written by a kernel that writes a sequence's own rows only
+    int zero_gaps(float* rows, int width) const {
+        if (!packed()) return HIFICAR_OK;
+        hipLaunchKernelGGL(xfmr_zero_gaps_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, rows, width, lay.pad_row, M);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
@@ -619,9 +684,10 @@ struct XfmrTrainCtx {
 // Transformer.forward in train() mode; see include/hificar.h.  tape = NULL: the rows a tape would keep live in the workspace.
 // Test aid (hificar_xfmr_debug_tap): the ReLU outputs, as rows — "conv_blocks.<n>.relu1", "conv_blocks.<n>.relu2" (B, T, hidden_dim) and
 // "layers.<n>.hidden" (B, T, 3072, before its dropout): which side of each ReLU the device took.
-// lengths = null: the dense form.  Otherwise B frame counts on the device and their sum (checked by the caller): the ragged form.
+// lengths = null: the dense form.  Otherwise B frame counts on the device and their sum (checked by the caller): the ragged form, or, with
+// Mp > 0 (xfmr_packed_rows of the same counts), the packed form.
 static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const float* x, const int* lengths, int valid, float* out, float* bn_batch_stats, int B,
-                                   int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape, void* workspace, void* stream_) {
+                                   int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape, void* workspace, void* stream_, int Mp = 0) {
     int rc;
     if (!x || !out || !bn_batch_stats) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HIFICAR_E_INVALID, "%s: dropout_p=%g outside [0, 1)", what, (double)dropout_p);
@@ -629,20 +695,34 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     XfmrTrain* ts = g->train;
-    const XfmrTrainWs ws = xfmr_plan_train_ws(g, B, T, workspace);
-    const XfmrTape tp = xfmr_plan_tape(g, B, T, tape ? tape : ws.light);
-    const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = B * T;
+    if (tape) ts->packed_tapes.erase(tape);  // (the packed entry point records it again once everything is enqueued)
+    const XfmrTrainWs ws = xfmr_plan_train_ws(g, B, T, workspace, Mp);
+    const XfmrTape tp = xfmr_plan_tape(g, B, T, tape ? tape : ws.light, Mp);
+    const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = Mp ? Mp : B * T;
     const int* const lens = lengths ? tp.lens : nullptr;
-    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, tp.lens, lens, &ws, {}};
+    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, tp.lens, lens, &ws, {}, {tp.row0, tp.pad_row}};
     auto P = [&](const std::string& name) { return ts->d_master + ts->offset.at(name); };
     hipLaunchKernelGGL(bigru_header_kernel, dim3(1), dim3(1), 0, stream, tp.hdr, (unsigned long long)seed, (unsigned long long)offset, dropout_p, B, T,
                        lengths ? valid : M, lengths ? 1 : 0);
     HIP_TRY(hipGetLastError());
     if (lengths) HIP_TRY(hipMemcpyAsync(tp.lens, lengths, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, stream));
-    // a tap of a ragged forward: the rows of padded frames are zeros (a GEMM's output there is finite, not zero)
+    if (Mp) {
+        hipLaunchKernelGGL(xfmr_pack_table_kernel, dim3((unsigned)B + 1), dim3(256), 0, stream, tp.lens, B, T, Mp, tp.row0, tp.pad_row);
+        HIP_TRY(hipGetLastError());
+    }
+    // a tap of a ragged forward: the rows of padded frames are zeros (a GEMM's output there is finite, not zero); of a packed forward: the
+    // rows go back to the padded (B, T, width) layout, zeros on padded frames
     auto tap = [&](const std::string& name, const float* rows, int width) -> int {
         auto it = g->taps.find(name);
         if (it == g->taps.end()) return HIFICAR_OK;
+        if (Mp) {
+            const size_t floats = (size_t)B * T * width;
+            if (it->second.cap < floats) return fail(HIFICAR_E_INVALID, "debug tap '%s' needs %zu floats, buffer has %zu", name.c_str(), floats, it->second.cap);
+            hipLaunchKernelGGL(xfmr_unpack_rows_kernel, dim3((unsigned)std::min<long long>(((long long)T * (width / 4) + 255) / 256, 64), (unsigned)B), dim3(256),
+                               0, stream, rows, it->second.dst, width, tp.lens, tp.row0, T);
+            HIP_TRY(hipGetLastError());
+            return HIFICAR_OK;
+        }
         int rc2 = xfmr_emit_tap(g, name, rows, (size_t)M * width, stream);
         if (rc2 != HIFICAR_OK || !lengths) return rc2;
         hipLaunchKernelGGL(bigru_zero_pad_kernel, dim3((unsigned)std::min<long long>(((long long)T * (width / 4) + 255) / 256, 8), (unsigned)B), dim3(256), 0,
@@ -653,8 +733,9 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
     {
         ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
         hipLaunchKernelGGL(xfmr_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, tp.xin,
-                           lens, C, g->cin_pad, T);
+                           lens, C, g->cin_pad, T, tp.row0);
         HIP_TRY(hipGetLastError());
+        XT(cx.zero_gaps(tp.xin, g->cin_pad));
     }
     const float* in = tp.xin;
     for (int i = 0; i < 3; ++i) {
@@ -697,6 +778,8 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
             p.lse = L.lse;
             p.hdr = tp.hdr;
             p.site = 4 * l;
+            p.row0 = tp.row0;
+            XT(cx.zero_gaps(L.o, F));
             ProfScope prof(h, stream, "xfmr_attn_kernel<train>", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
             const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B);
             const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_train_launch, d, p, grid, stream);
@@ -717,7 +800,7 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
         const int Op = g->w_out.cout_pad;
         ProfScope prof(h, stream, "xfmr_out_kernel", 0.0, 4.0 * M * (O + Op));
         hipLaunchKernelGGL(xfmr_out_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, ws.wide, out,
-                           lens, O, Op, T);
+                           lens, O, Op, T, tp.row0);
         HIP_TRY(hipGetLastError());
     }
     return HIFICAR_OK;
@@ -752,20 +835,77 @@ extern "C" int hificar_xfmr_forward_train_ragged(hificar_xfmr* g, const float* x
     return xfmr_forward_train_impl(g, what, x, lengths, (int)valid, out, bn_batch_stats, B, T, dropout_p, seed, offset, tape, workspace, stream_);
 }
 
+// The same step on a packed batch; see include/hificar.h.  The rows of every buffer are the Mp packed rows (XfmrLayout); the user-facing
+// tensors keep the padded layout.
+extern "C" int hificar_xfmr_forward_train_packed(hificar_xfmr* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out,
+                                                 float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape,
+                                                 size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hificar_xfmr_forward_train_packed";
+    if (!g) return fail(HIFICAR_E_INVALID, "%s: null handle", what);
+    if (B < 1 || T < 1) return fail(HIFICAR_E_INVALID, "%s: B=%d, T=%d out of range", what, B, T);
+    if (!lengths || !lengths_host) return fail(HIFICAR_E_INVALID, "%s: lengths and lengths_host are both required", what);
+    for (int b = 0; b < B; ++b)
+        if (lengths_host[b] < 0 || lengths_host[b] > T) return fail(HIFICAR_E_INVALID, "%s: lengths[%d]=%d outside [0, %d]", what, b, (int)lengths_host[b], T);
+    long long valid = 0;
+    const long long mp = xfmr_packed_rows(B, T, lengths_host, &valid);
+    if (valid < 2) return fail(HIFICAR_E_INVALID, "%s: batch statistics need more than one valid frame (sum of lengths = %lld)", what, valid);
+    if (mp * kXfmrFF >= (1LL << 31)) return fail(HIFICAR_E_INVALID, "%s: %lld packed rows out of range (packed rows * 3072 < 2^31)", what, mp);
+    int rc = xfmr_train_check(g, what, B, T, tape, tape_bytes, workspace, workspace_bytes, true, (int)mp);
+    if (rc != HIFICAR_OK) return rc;
+    rc = xfmr_forward_train_impl(g, what, x, lengths, (int)valid, out, bn_batch_stats, B, T, dropout_p, seed, offset, tape, workspace, stream_, (int)mp);
+    if (rc == HIFICAR_OK && tape) g->train->packed_tapes[tape] = {B, T, std::vector<int32_t>(lengths_host, lengths_host + B)};
+    return rc;
+}
+
+static int xfmr_backward_impl(hificar_xfmr* g, const float* dout, int B, int T, int Mp, const void* tape, float* grads, float* dx, void* workspace,
+                              void* stream_);
+
 extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
                                      void* workspace, size_t workspace_bytes, void* stream_) {
     const char* what = "hificar_xfmr_backward";
+    if (g && g->train && g->train->packed_tapes.count(tape))  // (first: a packed tape is sized by other rows)
+        return fail(HIFICAR_E_STATE, "%s: this tape was filled by hificar_xfmr_forward_train_packed; its backward is hificar_xfmr_backward_packed", what);
     int rc = xfmr_train_check(g, what, B, T, const_cast<void*>(tape), tape_bytes, workspace, workspace_bytes);
     if (rc != HIFICAR_OK) return rc;
     if (!dout || !grads) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
+    return xfmr_backward_impl(g, dout, B, T, 0, tape, grads, dx, workspace, stream_);
+}
+
+// The backward of a packed tape; see include/hificar.h.  lengths_host: the forward's frame counts, which give Mp on the host; they are
+// checked against what the handle recorded when it filled the tape.
+extern "C" int hificar_xfmr_backward_packed(hificar_xfmr* g, const float* dout, const int32_t* lengths_host, int B, int T, const void* tape,
+                                            size_t tape_bytes, float* grads, float* dx, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hificar_xfmr_backward_packed";
+    if (!g) return fail(HIFICAR_E_INVALID, "%s: null handle", what);
+    if (!lengths_host) return fail(HIFICAR_E_INVALID, "%s: lengths_host is required", what);
+    const int mp = hificar_xfmr_packed_rows(B, T, lengths_host);
+    if (!mp) return fail(HIFICAR_E_INVALID, "%s: B=%d, T=%d and these lengths are no packed batch (each length in 0 .. T, their sum >= 2)", what, B, T);
+    int rc = xfmr_train_init(g);
+    if (rc != HIFICAR_OK) return rc;
+    const auto it = g->train->packed_tapes.find(tape);
+    if (it == g->train->packed_tapes.end())
+        return fail(HIFICAR_E_STATE, "%s: this tape was not filled by hificar_xfmr_forward_train_packed on this handle (a dense or ragged tape's backward "
+                                     "is hificar_xfmr_backward)", what);
+    if (it->second.B != B || it->second.T != T || !std::equal(it->second.lengths.begin(), it->second.lengths.end(), lengths_host))
+        return fail(HIFICAR_E_INVALID, "%s: B, T or the lengths differ from those of the forward that filled this tape", what);
+    rc = xfmr_train_check(g, what, B, T, const_cast<void*>(tape), tape_bytes, workspace, workspace_bytes, false, mp);
+    if (rc != HIFICAR_OK) return rc;
+    if (!dout || !grads) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
+    return xfmr_backward_impl(g, dout, B, T, mp, tape, grads, dx, workspace, stream_);
+}
+
+// Both backwards, checked by their entry points.  Mp = 0: a dense or ragged tape; otherwise a packed one of Mp rows.
+static int xfmr_backward_impl(hificar_xfmr* g, const float* dout, int B, int T, int Mp, const void* tape, float* grads, float* dx, void* workspace,
+                              void* stream_) {
+    int rc;
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     XfmrTrain* ts = g->train;
-    const XfmrTape tp = xfmr_plan_tape(g, B, T, const_cast<void*>(tape));
-    const XfmrTrainWs ws = xfmr_plan_train_ws(g, B, T, workspace);
-    const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = B * T, FF = kXfmrFF;
-    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, tp.lens, nullptr, &ws, {}};
+    const XfmrTape tp = xfmr_plan_tape(g, B, T, const_cast<void*>(tape), Mp);
+    const XfmrTrainWs ws = xfmr_plan_train_ws(g, B, T, workspace, Mp);
+    const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = Mp ? Mp : B * T, FF = kXfmrFF;
+    XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, tp.lens, nullptr, &ws, {}, {tp.row0, tp.pad_row}};
     cx.bw.partial = ws.partial;
     cx.bw.colsum = ws.colsum;
     cx.bw.partial_elems = ws.partial_elems;
@@ -780,8 +920,9 @@ extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, 
     {   // dout (B, O, T) -> rows [B T][Op]; a ragged tape: dout past a length is not read, its rows are zeros
         ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (O + Op));
         hipLaunchKernelGGL(xfmr_drows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, dout, ws.wide, tp.hdr,
-                           tp.lens, O, Op, T);
+                           tp.lens, O, Op, T, cx.lay);
         HIP_TRY(hipGetLastError());
+        XT(cx.zero_gaps(ws.wide, Op));
     }
     XT(cx.wgrad(g->w_out, ws.wide, Op, tp.X[(size_t)E], F, G("w_out.weight"), G("w_out.bias")));
     XT(cx.conv(ts->dg_wout, ws.wide, nullptr, d0, nullptr, false));
@@ -822,6 +963,8 @@ extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, 
             p.T = T;
             p.F = F;
             p.scale = (float)(1.0 / std::sqrt((double)d));
+            p.lay = cx.lay;
+            XT(cx.zero_gaps(ws.gw, 3 * F));
             const int chunks = (M + kXfmrEmbRows - 1) / kXfmrEmbRows;
             // S, dP, dQ (K and E parts), dK, dV, dE: six banded products of 2 M F 199 flops each
             ProfScope prof(h, stream, "xfmr_attn_bwd_kernels", 2.0 * M * F * 7 * kXfmrTab, 4.0 * M * (8.0 * F + 4.0 * kXfmrHeads * kXfmrBand));
@@ -870,7 +1013,7 @@ extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, 
             XT(cx.conv(b1.dg, d0, dres, ws.dxr[1], nullptr));
             ProfScope prof(h, stream, "xfmr_unrows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
             hipLaunchKernelGGL(xfmr_unrows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, ws.dxr[1], dx,
-                               tp.hdr, tp.lens, C, g->cin_pad, T);
+                               tp.hdr, tp.lens, C, g->cin_pad, T, cx.lay);
             HIP_TRY(hipGetLastError());
         }
     }

@@ -6,6 +6,8 @@
 // GEMMs run over all B T rows, so every kernel below that writes rows writes those of padded frames (at or past a sequence's count) as
 // zeros without reading them, and every sum over rows skips them by a predicate — never by a multiplication (NaN * 0 is NaN).  A dense
 // tape takes the same statements with every count = T.
+// Packed batches (hificar_xfmr_forward_train_packed): the same rule over the rows of XfmrLayout, with a gap row where the ragged step has a
+// padded frame's row; the kernels take the layout as an argument and execute the statements above when its tables are null.
 #pragma once
 #include "hificar_xfmr_kernels.hip.h"
 
@@ -16,9 +18,80 @@ constexpr int kXfmrColRows = 256;   // rows per partial of the two-stage column 
 constexpr int kXfmrEmbRows = 256;   // rows per partial of the table gradient
 constexpr int kXfmrEmbPitch = 208;  // floats per row of the staged dS block: 13 tiles of 16 table rows; 208 = 16 (mod 64): no bank conflicts
 
-// element e of rows [B T][width] belongs to a frame of its sequence (lens null: always)
-__device__ __forceinline__ bool xfmr_elem_valid(const int* lens, long long e, int width, int T) {
+// The layout of a training step's rows.  Dense and ragged (both tables null): row b T + t is frame t of sequence b, and `lens` (null: dense)
+// says which rows are padding.  Packed (hificar_xfmr_forward_train_packed): sequence b's frames are rows row0[b] .. row0[b] + lens[b] - 1,
+// one gap row follows every sequence and the tail up to the row count is gap rows too; pad_row[r] is the padded index b T + t of packed
+// row r, or -1 for a gap row.  A gap row is what a padded frame's row is to the ragged step: written as zeros, never read into a sum.
+// The banded buffers and lse are [B][8][T] (dense, ragged) or [rows][8] (packed).
+struct XfmrLayout {
+    const int* row0 = nullptr;     // [B + 1]
+    const int* pad_row = nullptr;  // [rows]
+};
+
+__device__ __forceinline__ bool xfmr_row_valid(const XfmrLayout& lay, const int* lens, long long r, int T) {
+    if (lay.pad_row) return lay.pad_row[r] >= 0;
+    return bigru_row_valid(lens, (int)r, T);
+}
+// element e of rows [rows][width] belongs to a frame of its sequence (dense: always)
+__device__ __forceinline__ bool xfmr_elem_valid(const XfmrLayout& lay, const int* lens, long long e, int width, int T) {
+    if (lay.pad_row) return lay.pad_row[e / width] >= 0;
     return !lens || bigru_row_valid(lens, (int)(e / width), T);
+}
+// the dropout element of element e of a valid row: its index in the PADDED (B, T, width) tensor (packed: through pad_row, in 64 bits)
+__device__ __forceinline__ unsigned long long xfmr_drop_elem(const XfmrLayout& lay, long long e, int width) {
+    if (!lay.pad_row) return (unsigned long long)e;
+    const long long r = e / width;
+    return (unsigned long long)((long long)lay.pad_row[r] * width + (e - r * width));
+}
+// first row of sequence b, and the index of (b, h, q) in lse and in the banded buffers' rows
+__device__ __forceinline__ size_t xfmr_seq_row0(const XfmrLayout& lay, int b, int T) { return lay.row0 ? (size_t)lay.row0[b] : (size_t)b * T; }
+__device__ __forceinline__ size_t xfmr_band_row(const XfmrLayout& lay, size_t row0, int b, int h, int q, int T) {
+    return lay.row0 ? (row0 + q) * kXfmrHeads + h : ((size_t)b * kXfmrHeads + h) * T + q;
+}
+
+// pad_row and row0 of a packed forward from the frame counts.  grid (B + 1), block b: sequence b's rows and its gap row; block B: the tail.
+// Writes stay below `rows` whatever the device counts hold (the host sized the tables from its own copy).
+__global__ __launch_bounds__(256) void xfmr_pack_table_kernel(const int* __restrict__ lens, int B, int T, int rows, int* __restrict__ row0,
+                                                              int* __restrict__ pad_row) {
+    __shared__ int part[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int s = 0;
+    for (int i = tid; i < b; i += 256) s += min(max(lens[i], 0), T) + 1;
+    part[tid] = s;
+    __syncthreads();
+    for (int d = 128; d >= 1; d >>= 1) {
+        if (tid < d) part[tid] += part[tid + d];
+        __syncthreads();
+    }
+    const int r0 = min(part[0], rows);
+    if (tid == 0) row0[b] = r0;
+    if (b == B) {
+        for (int r = r0 + tid; r < rows; r += 256) pad_row[r] = -1;
+        return;
+    }
+    const int len = min(max(lens[b], 0), T);
+    for (int t = tid; t <= len; t += 256)
+        if (r0 + t < rows) pad_row[r0 + t] = t < len ? b * T + t : -1;
+}
+
+// rows[r][0 .. width) = 0 for every gap row r (width % 4 == 0): the rows the layout kernels and the attention kernels of a packed step,
+// which write a sequence's own rows only, leave to this one.  One wave per row.
+__global__ __launch_bounds__(256) void xfmr_zero_gaps_kernel(float* __restrict__ rows, int width, const int* __restrict__ pad_row, int n) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n || pad_row[r] >= 0) return;
+    for (int i = lane; i < width / 4; i += 64) reinterpret_cast<float4*>(rows + r * width)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// packed rows [row0[b] + t][width] -> dst (B, T, width), zeros on padded frames: the debug taps of a packed forward.  grid (blocks, B)
+__global__ __launch_bounds__(256) void xfmr_unpack_rows_kernel(const float* __restrict__ rows, float* __restrict__ dst, int width,
+                                                               const int* __restrict__ lens, const int* __restrict__ row0, int T) {
+    const int b = blockIdx.y, w4 = width / 4;
+    const long long n4 = (long long)T * w4, have = (long long)bigru_len(lens, b, T) * w4;
+    const float4* const src = reinterpret_cast<const float4*>(rows + (size_t)row0[b] * width);
+    float4* const out = reinterpret_cast<float4*>(dst + (size_t)b * T * width);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256)
+        out[i] = i < have ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -52,6 +125,7 @@ struct XfmrAttnBwdParams {
     int site;
     int T, F;
     float scale;
+    XfmrLayout lay;     // packed: rows [row0[b] + t], lse [rows][8], ds / pd [rows][8][200]
 };
 
 template <int D>
@@ -65,13 +139,14 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_q_kernel(const XfmrAttnBwdP
     const int c = lane & 15, g = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kXfmrTQ;
     const int len = bigru_len(bigru_tape_lens(p.hdr, p.lens), b, p.T);
-    const size_t row0 = (size_t)b * p.T;
+    const size_t row0 = xfmr_seq_row0(p.lay, b, p.T);
     const size_t F3 = (size_t)3 * p.F;
     const size_t bh = (size_t)b * kXfmrHeads + h;
     const int qw = q0 + wave * 16, q = qw + c;
     const bool qok = q < len;
+    const bool zero_pad = !p.lay.row0;  // (packed: the rows past a length are another sequence's; the gap rows are xfmr_zero_gaps_kernel's)
     if (q0 >= len) {  // (the whole workgroup, before any barrier) 64 padded queries: their dq rows are zeros
-        xfmr_zero_head_row<D>(p.dqkv + (row0 + q) * F3 + h * D + 4 * g, q < p.T);
+        xfmr_zero_head_row<D>(p.dqkv + (row0 + q) * F3 + h * D + 4 * g, q < p.T && zero_pad);
         return;
     }
     const XfmrDrop drop(p.hdr, p.site);
@@ -91,7 +166,7 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_q_kernel(const XfmrAttnBwdP
         }
         delta += __shfl_xor(delta, 16);
         delta += __shfl_xor(delta, 32);
-        if (qok) lq = p.lse[bh * p.T + q];
+        if (qok) lq = p.lse[xfmr_band_row(p.lay, row0, b, h, q, p.T)];
     }
 
     // positional logits of the wave's 16 queries, as the forward: pos[16 wave + c][r] = Q[q] . E[r]
@@ -150,7 +225,7 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_q_kernel(const XfmrAttnBwdP
                     const float f = drop((bh * p.T + q) * kXfmrTab + rel);
                     dsv = pr * (dp[i] * f - delta);
                     mypos[rel] = dsv;
-                    p.pd[(bh * p.T + q) * kXfmrBand + rel] = pr * f;
+                    p.pd[xfmr_band_row(p.lay, row0, b, h, q, p.T) * kXfmrBand + rel] = pr * f;
                 }
                 s[i] = dsv;
             }
@@ -174,7 +249,7 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_q_kernel(const XfmrAttnBwdP
         float v = 0.f;
         if (qa < len && r < kXfmrTab && k >= 0 && k < len) v = *e;
         *e = v;
-        if (qa < len) p.ds[(bh * p.T + qa) * kXfmrBand + r] = v;
+        if (qa < len) p.ds[xfmr_band_row(p.lay, row0, b, h, qa, p.T) * kXfmrBand + r] = v;
     }
 
     // dQ^T += E^T dS^T over the table rows (A: E[r][16 j + c], B: dS[q = c][r], r = 4 g-th of each step)
@@ -194,7 +269,7 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_q_kernel(const XfmrAttnBwdP
     }
     float* orow = p.dqkv + (row0 + q) * F3 + h * D + 4 * g;
     if (!qok) {
-        xfmr_zero_head_row<D>(orow, q < p.T);
+        xfmr_zero_head_row<D>(orow, q < p.T && zero_pad);
         return;
     }
 #pragma unroll
@@ -219,16 +294,16 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_k_kernel(const XfmrAttnBwdP
     const int c = lane & 15, g = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, k0 = blockIdx.x * kXfmrKB;
     const int len = bigru_len(bigru_tape_lens(p.hdr, p.lens), b, p.T);
-    const size_t row0 = (size_t)b * p.T;
+    const size_t row0 = xfmr_seq_row0(p.lay, b, p.T);
     const size_t F3 = (size_t)3 * p.F;
-    const size_t bh = (size_t)b * kXfmrHeads + h;
     const int kw = k0 + wave * 16, k = kw + c;
     const bool kok = k < len;
     float* const krow = p.dqkv + (row0 + k) * F3 + p.F + h * D + 4 * g;
     float* const vrow = krow + p.F;
+    const bool zero_pad = !p.lay.row0;  // (as in the query-tiled kernel)
     if (k0 >= len) {  // (the whole workgroup, before any barrier) 64 padded keys: their dk | dv rows are zeros
-        xfmr_zero_head_row<D>(krow, k < p.T);
-        xfmr_zero_head_row<D>(vrow, k < p.T);
+        xfmr_zero_head_row<D>(krow, k < p.T && zero_pad);
+        xfmr_zero_head_row<D>(vrow, k < p.T && zero_pad);
         return;
     }
     f32x4 dv[NM], dk[NM];
@@ -251,7 +326,7 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_k_kernel(const XfmrAttnBwdP
             const int rel = k - q + (kXfmrRel - 1);
             float pv = 0.f, sv = 0.f;
             if (kok && q < qb + n && rel >= 0 && rel < kXfmrTab) {
-                const size_t e = (bh * p.T + q) * kXfmrBand + rel;
+                const size_t e = xfmr_band_row(p.lay, row0, b, h, q, p.T) * kXfmrBand + rel;
                 pv = p.pd[e];
                 sv = p.ds[e];
             }
@@ -265,8 +340,8 @@ __global__ __launch_bounds__(256) void xfmr_attn_bwd_k_kernel(const XfmrAttnBwdP
         }
     }
     if (!kok) {
-        xfmr_zero_head_row<D>(krow, k < p.T);
-        xfmr_zero_head_row<D>(vrow, k < p.T);
+        xfmr_zero_head_row<D>(krow, k < p.T && zero_pad);
+        xfmr_zero_head_row<D>(vrow, k < p.T && zero_pad);
         return;
     }
 #pragma unroll
@@ -287,7 +362,8 @@ struct XfmrEmbLds {
 
 template <int D>
 __global__ __launch_bounds__(256) void xfmr_demb_partial_kernel(const float* __restrict__ qkv, const float* __restrict__ ds, float* __restrict__ partial,
-                                                                int M, int T, int F, const BigruTapeHeader* hdr, const int* __restrict__ tape_lens) {
+                                                                int M, int T, int F, const BigruTapeHeader* hdr, const int* __restrict__ tape_lens,
+                                                                const XfmrLayout lay) {
     extern __shared__ float xfmr_lds[];
     constexpr int PT = D + 4, NM = D / 16, DP = kXfmrEmbPitch;
     float* const qbuf = xfmr_lds;
@@ -306,7 +382,11 @@ __global__ __launch_bounds__(256) void xfmr_demb_partial_kernel(const float* __r
         const int r0 = chunk * kXfmrEmbRows + blk * 64;
         if (r0 >= M) break;  // (the whole workgroup)
         const int n = min(64, M - r0);
-        if (lens) {  // (the whole workgroup) no frame among these rows: nothing to add
+        if (lay.pad_row) {  // (the whole workgroup) packed rows: the same question asked of the table
+            bool any = false;
+            for (int i = 0; i < n; ++i) any = any || lay.pad_row[r0 + i] >= 0;
+            if (!any) continue;
+        } else if (lens) {  // (the whole workgroup) no frame among these rows: nothing to add
             bool any = false;
             for (int bb = r0 / T; bb <= (r0 + n - 1) / T; ++bb) any = any || max(r0, bb * T) < min(r0 + n, bb * T + bigru_len(lens, bb, T));
             if (!any) continue;
@@ -318,16 +398,17 @@ __global__ __launch_bounds__(256) void xfmr_demb_partial_kernel(const float* __r
             for (int i = tid; i < 64 * (D / 4); i += 256) {
                 const int rr = i / (D / 4), v = i - rr * (D / 4);
                 float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (rr < n && bigru_row_valid(lens, r0 + rr, T)) x = *reinterpret_cast<const float4*>(qkv + (size_t)(r0 + rr) * F3 + h * D + 4 * v);
+                if (rr < n && xfmr_row_valid(lay, lens, r0 + rr, T)) x = *reinterpret_cast<const float4*>(qkv + (size_t)(r0 + rr) * F3 + h * D + 4 * v);
                 *reinterpret_cast<float4*>(qbuf + rr * PT + 4 * v) = x;
             }
         }
         for (int i = tid; i < 64 * (DP / 4); i += 256) {
             const int rr = i / (DP / 4), v = i - rr * (DP / 4);
             float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (rr < n && 4 * v < kXfmrBand && bigru_row_valid(lens, r0 + rr, T)) {  // (entry 199 of a row is a written zero)
+            if (rr < n && 4 * v < kXfmrBand && xfmr_row_valid(lay, lens, r0 + rr, T)) {  // (entry 199 of a row is a written zero)
                 const int row = r0 + rr, bb = row / T, t = row - bb * T;
-                x = *reinterpret_cast<const float4*>(ds + (((size_t)bb * kXfmrHeads + h) * T + t) * kXfmrBand + 4 * v);
+                const size_t band = lay.pad_row ? (size_t)row * kXfmrHeads + h : ((size_t)bb * kXfmrHeads + h) * T + t;
+                x = *reinterpret_cast<const float4*>(ds + band * kXfmrBand + 4 * v);
             }
             *reinterpret_cast<float4*>(dbuf + rr * DP + 4 * v) = x;
         }
@@ -380,7 +461,8 @@ struct XfmrColParams {
     float* partial;         // [chunks][2][F]
     const BigruTapeHeader* hdr;
     const int* lens;        // [B]: the tape's frame counts (hdr->ragged)
-    int M, T, F, mode;      // M = B T: the rows of the padded batch
+    int M, T, F, mode;      // M = B T: the rows of the padded batch (packed: the packed rows)
+    XfmrLayout lay;
 };
 
 __global__ __launch_bounds__(256) void xfmr_colsum_kernel(const XfmrColParams p) {
@@ -393,7 +475,7 @@ __global__ __launch_bounds__(256) void xfmr_colsum_kernel(const XfmrColParams p)
     const int* const lens = bigru_tape_lens(p.hdr, p.lens);
     float s0 = 0.f, s1 = 0.f;
     for (int r = r0 + ty; r < r1; r += 4) {
-        if (!bigru_row_valid(lens, r, p.T)) continue;
+        if (!xfmr_row_valid(p.lay, lens, r, p.T)) continue;
         const size_t e = (size_t)r * p.F + c;
         const float x = p.x[e];
         if (p.mode == 0) {
@@ -449,9 +531,9 @@ __global__ __launch_bounds__(256) void xfmr_bn_var_kernel(const float* __restric
 // padded frames are written as zeros
 __global__ __launch_bounds__(256) void xfmr_bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, const float* __restrict__ res, float* __restrict__ out,
-                                                            long long n4, int F, int relu, const int* __restrict__ lens, int T) {
+                                                            long long n4, int F, int relu, const int* __restrict__ lens, int T, const XfmrLayout lay) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        if (!xfmr_elem_valid(lens, i * 4, F, T)) {
+        if (!xfmr_elem_valid(lay, lens, i * 4, F, T)) {
             reinterpret_cast<float4*>(out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             continue;
         }
@@ -475,11 +557,11 @@ __global__ __launch_bounds__(256) void xfmr_bn_apply_kernel(const float* __restr
 __global__ __launch_bounds__(256) void xfmr_bn_bwd_dx_kernel(const float* __restrict__ x, const float* dy, const float* __restrict__ stats,
                                                              const float* __restrict__ gamma, const float* __restrict__ dgamma,
                                                              const float* __restrict__ dbeta, float* dx, long long n, int F, const BigruTapeHeader* hdr,
-                                                             const int* __restrict__ tape_lens, int T) {
+                                                             const int* __restrict__ tape_lens, int T, const XfmrLayout lay) {
     const float inv_m = 1.f / (float)hdr->M;
     const int* const lens = bigru_tape_lens(hdr, tape_lens);
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-        if (!xfmr_elem_valid(lens, e, F, T)) {
+        if (!xfmr_elem_valid(lay, lens, e, F, T)) {
             dx[e] = 0.f;
             continue;
         }
@@ -497,35 +579,37 @@ __global__ __launch_bounds__(256) void xfmr_bn_bwd_dx_kernel(const float* __rest
 // Rows are `width` floats (width % 4 == 0); on a ragged tape the rows of padded frames are written as zeros and their inputs not read.
 // ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void xfmr_add_drop_kernel(const float* __restrict__ x, const float* __restrict__ t, float* __restrict__ out, long long n,
-                                                            const BigruTapeHeader* hdr, int site, const int* __restrict__ tape_lens, int width, int T) {
+                                                            const BigruTapeHeader* hdr, int site, const int* __restrict__ tape_lens, int width, int T,
+                                                            const XfmrLayout lay) {
     const XfmrDrop drop(hdr, site);
     const int* const lens = bigru_tape_lens(hdr, tape_lens);
     for (long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; e < n; e += (long long)gridDim.x * 1024) {
-        if (!xfmr_elem_valid(lens, e, width, T)) {
+        if (!xfmr_elem_valid(lay, lens, e, width, T)) {
             *reinterpret_cast<float4*>(out + e) = make_float4(0.f, 0.f, 0.f, 0.f);
             continue;
         }
+        const unsigned long long de = xfmr_drop_elem(lay, e, width);
         const float4 a = *reinterpret_cast<const float4*>(x + e), v = *reinterpret_cast<const float4*>(t + e);
-        *reinterpret_cast<float4*>(out + e) = make_float4(a.x + v.x * drop((unsigned long long)e), a.y + v.y * drop((unsigned long long)e + 1),
-                                                          a.z + v.z * drop((unsigned long long)e + 2), a.w + v.w * drop((unsigned long long)e + 3));
+        *reinterpret_cast<float4*>(out + e) = make_float4(a.x + v.x * drop(de), a.y + v.y * drop(de + 1), a.z + v.z * drop(de + 2), a.w + v.w * drop(de + 3));
     }
 }
 
 __global__ __launch_bounds__(256) void xfmr_gate_kernel(const float* a, const float* d, float* out, long long n, const BigruTapeHeader* hdr, int site,
-                                                        const int* __restrict__ tape_lens, int width, int T) {
+                                                        const int* __restrict__ tape_lens, int width, int T, const XfmrLayout lay) {
     const XfmrDrop drop(hdr, site < 0 ? 0 : site);
     const int* const lens = bigru_tape_lens(hdr, tape_lens);
     for (long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; e < n; e += (long long)gridDim.x * 1024) {
-        if (!xfmr_elem_valid(lens, e, width, T)) {
+        if (!xfmr_elem_valid(lay, lens, e, width, T)) {
             *reinterpret_cast<float4*>(out + e) = make_float4(0.f, 0.f, 0.f, 0.f);
             continue;
         }
         float4 v = *reinterpret_cast<const float4*>(d + e);
         if (site >= 0) {
-            v.x *= drop((unsigned long long)e);
-            v.y *= drop((unsigned long long)e + 1);
-            v.z *= drop((unsigned long long)e + 2);
-            v.w *= drop((unsigned long long)e + 3);
+            const unsigned long long de = xfmr_drop_elem(lay, e, width);
+            v.x *= drop(de);
+            v.y *= drop(de + 1);
+            v.z *= drop(de + 2);
+            v.w *= drop(de + 3);
         }
         if (a) {
             const float4 m = *reinterpret_cast<const float4*>(a + e);
@@ -543,12 +627,12 @@ __global__ __launch_bounds__(256) void xfmr_gate_kernel(const float* a, const fl
 // ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void xfmr_ln_bwd_kernel(const float* __restrict__ x, const float* dy, const float* __restrict__ gamma, float* dx,
                                                           float* __restrict__ rowstats, long long M, int F, const BigruTapeHeader* hdr,
-                                                          const int* __restrict__ tape_lens, int T) {
+                                                          const int* __restrict__ tape_lens, int T, const XfmrLayout lay) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const int nv = F >> 2;
-    if (!bigru_row_valid(bigru_tape_lens(hdr, tape_lens), (int)row, T)) {
+    if (!xfmr_row_valid(lay, bigru_tape_lens(hdr, tape_lens), row, T)) {
         for (int i = lane; i < nv; i += 64) reinterpret_cast<float4*>(dx + row * F)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
     }
@@ -604,7 +688,7 @@ __global__ __launch_bounds__(256) void xfmr_ln_bwd_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------------------------------------
 // xfmr_rows_kernel by the tape's frame counts: dout (B, C, T) -> rows [b T + t][Cp]
 __global__ __launch_bounds__(256) void xfmr_drows_kernel(const float* __restrict__ x, float* __restrict__ rows, const BigruTapeHeader* hdr,
-                                                         const int* __restrict__ tape_lens, int C, int Cp, int T) {
+                                                         const int* __restrict__ tape_lens, int C, int Cp, int T, const XfmrLayout lay) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -614,23 +698,26 @@ __global__ __launch_bounds__(256) void xfmr_drows_kernel(const float* __restrict
         tile[r][tx] = (c < C && t < len) ? x[((size_t)b * C + c) * T + t] : 0.f;
     }
     __syncthreads();
+    const size_t base = xfmr_seq_row0(lay, b, T);
+    const int tw = lay.row0 ? len : T;  // (packed: a sequence's own rows; the gap rows are xfmr_zero_gaps_kernel's)
     for (int r = ty; r < 32; r += 8) {
         const int t = t0 + r, c = c0 + tx;
-        if (t < T && c < Cp) rows[((size_t)b * T + t) * Cp + c] = tile[tx][r];
+        if (t < tw && c < Cp) rows[(base + t) * Cp + c] = tile[tx][r];
     }
 }
 
 // rows [b T + t][Cp] -> dx (B, C, T): the input gradient in the reference's layout; a padded frame's (ragged tape) is zero and its row,
 // which holds what the k = 3 data gradient spilled over the sequence's end, is not read
 __global__ __launch_bounds__(256) void xfmr_unrows_kernel(const float* __restrict__ rows, float* __restrict__ dx, const BigruTapeHeader* hdr,
-                                                          const int* __restrict__ tape_lens, int C, int Cp, int T) {
+                                                          const int* __restrict__ tape_lens, int C, int Cp, int T, const XfmrLayout lay) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int len = bigru_len(bigru_tape_lens(hdr, tape_lens), b, T);
+    const size_t base = xfmr_seq_row0(lay, b, T);
     for (int r = ty; r < 32; r += 8) {
         const int t = t0 + r, c = c0 + tx;
-        tile[r][tx] = (t < len && c < Cp) ? rows[((size_t)b * T + t) * Cp + c] : 0.f;
+        tile[r][tx] = (t < len && c < Cp) ? rows[(base + t) * Cp + c] : 0.f;
     }
     __syncthreads();
     for (int r = ty; r < 32; r += 8) {

@@ -20,7 +20,8 @@ reference trains (the tables then get no gradient).
 
 ``forward_padded(x, lengths)`` trains on whole utterances of unequal lengths (this package's definition, the reference never masks):
 ``hificar_xfmr_forward_train_ragged`` through the same autograd node; the padded frames take no part in batch statistics, attention or
-gradients.
+gradients.  ``forward_padded(x, lengths, packed=True)`` is the same step with no GEMM rows for the padding
+(``hificar_xfmr_forward_train_packed`` / ``hificar_xfmr_backward_packed``): the same masks and definitions, results equal to rounding.
 
 Not built, refused with ``NotImplementedError``: ``extra_art=True`` and ``num_ph`` (phoneme input).  ``forward(lengths=...)`` in train() mode
 is refused too (ragged training is asked for by name: ``forward_padded``).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size``
@@ -124,14 +125,15 @@ def _grad_layout(module):
 class _TransformerFunction(torch.autograd.Function):
     """Autograd node of the native Transformer in train() mode: forward = hificar_xfmr_forward_train (or, with ``module._lens`` set by
     ``forward_padded``, hificar_xfmr_forward_train_ragged: the lengths are read here, at forward time, and live on in the tape), backward =
-    hificar_xfmr_backward.  Inputs after (module, x, p, seed, offset, names) are the module's parameters in ``names`` order.  Returns
-    (out, batch statistics (number of batch norms, 2, hidden_dim): mean | biased variance); the statistics carry no gradient."""
+    hificar_xfmr_backward (``module._packed``: the packed pair of entry points).  Inputs after (module, x, p, seed, offset, names) are the
+    module's parameters in ``names`` order.  Returns (out, batch statistics (number of batch norms, 2, hidden_dim): mean | biased variance); the statistics carry no gradient."""
 
     @staticmethod
     def forward(ctx, module, x, p, seed, offset, names, *params):
-        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True, lens=module._lens)
+        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True, lens=module._lens, packed=module._packed)
         B, _, T = x.shape
         ctx.module, ctx.names, ctx.tape, ctx.toff, ctx.BT = module, names, tape, toff, (B, T)
+        ctx.packed_lens = module._lens[0] if module._packed else None  # the host lengths: hificar_xfmr_backward_packed checks them
         ctx.save_for_backward(*params)  # torch's own version check covers an in-place edit that bumps Parameter._version ...
         ctx.steps_seen = module._steps_seen  # ... and this one a fused optimizer step, which does not
         ctx.mark_non_differentiable(stats)
@@ -152,10 +154,14 @@ class _TransformerFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             grads = torch.empty(int(lib.hificar_xfmr_grad_floats(handle)), dtype=torch.float32, device=dev)
-            ws_ptr, ws_bytes = module._train_workspace(B, T)
-            rc = lib.hificar_xfmr_backward(handle, dout.data_ptr(), B, T, ctx.tape.data_ptr() + ctx.toff, ctx.tape.numel() - ctx.toff,
-                                           grads.data_ptr(), dx.data_ptr() if dx is not None else None, ws_ptr, ws_bytes, stream)
-        _native.check(rc, "hificar_xfmr_backward")
+            tail = (ctx.tape.data_ptr() + ctx.toff, ctx.tape.numel() - ctx.toff, grads.data_ptr(), dx.data_ptr() if dx is not None else None)
+            if ctx.packed_lens is None:
+                ws_ptr, ws_bytes = module._train_workspace(B, T)
+                rc = lib.hificar_xfmr_backward(handle, dout.data_ptr(), B, T, *tail, ws_ptr, ws_bytes, stream)
+            else:
+                ws_ptr, ws_bytes = module._train_workspace(B, T, module._packed_rows(ctx.packed_lens, B, T))
+                rc = lib.hificar_xfmr_backward_packed(handle, dout.data_ptr(), ctx.packed_lens.data_ptr(), B, T, *tail, ws_ptr, ws_bytes, stream)
+        _native.check(rc, "hificar_xfmr_backward" if ctx.packed_lens is None else "hificar_xfmr_backward_packed")
         views = {name: grads[off:off + num] for name, off, num in _grad_layout(module)}
         skip = () if module.train_relative_positions else ("relative_positional.embeddings",)
         gw = tuple(views[n].view(t.shape) if need and not n.endswith(skip or ("\0",)) else None
@@ -197,6 +203,7 @@ class Transformer(torch.nn.Module):
         self._steps_seen = 0     # optimizer steps noticed so far
         self._calls = 0          # training forwards so far: the dropout generator's offset
         self._lens = None        # the lengths of the ragged training forward under way (forward_padded)
+        self._packed = False     # ... and whether it is the packed form
         self._last_stats = None
         self.train_relative_positions = True  # False: the tables get no gradient, as in the reference (see the module's docstring)
         # drawn from torch's generator (after the parameters): torch.manual_seed makes a training run repeatable
@@ -378,9 +385,21 @@ class Transformer(torch.nn.Module):
             self._send_parameters()
         return handle
 
-    def _train_workspace(self, B, T):
-        """One grow-only scratch buffer shared by the training forward and the backward pass (hificar_xfmr_train_workspace_bytes)."""
-        n = self._lib.hificar_xfmr_train_workspace_bytes(self._handle, B, T) + 256
+    def _packed_rows(self, host_lens, B, T):
+        """Mp of a packed batch (hificar_xfmr_packed_rows), from the host lengths."""
+        mp = int(self._lib.hificar_xfmr_packed_rows(B, T, host_lens.data_ptr()))
+        if mp <= 0:
+            raise RuntimeError(f"Transformer.forward_padded(packed=True): a batch of {B} x {T} with {int(host_lens.sum())} frames cannot be packed "
+                               "(at least two frames; packed rows * 3072 < 2^31)")
+        return mp
+
+    def _train_workspace(self, B, T, packed_rows=None):
+        """One grow-only scratch buffer shared by the training forward and the backward pass (hificar_xfmr_train_workspace_bytes, or, for a
+        packed step of ``packed_rows`` rows, hificar_xfmr_train_workspace_bytes_packed)."""
+        if packed_rows is None:
+            n = self._lib.hificar_xfmr_train_workspace_bytes(self._handle, B, T) + 256
+        else:
+            n = self._lib.hificar_xfmr_train_workspace_bytes_packed(self._handle, B, packed_rows) + 256
         ws = self._train_ws_buf
         if ws is None or ws.numel() < n:
             ws = torch.empty(int(n * 1.25) if ws is not None else n, dtype=torch.uint8, device=self._device())
@@ -388,29 +407,31 @@ class Transformer(torch.nn.Module):
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
 
-    def _run_forward_train(self, x, p, seed, offset, keep_tape, lens=None):
-        """hificar_xfmr_forward_train (lens = (host, device) int32 lengths: hificar_xfmr_forward_train_ragged) on the current stream: (out,
-        batch statistics, tape or None, the tape's alignment offset)."""
+    def _run_forward_train(self, x, p, seed, offset, keep_tape, lens=None, packed=False):
+        """hificar_xfmr_forward_train (lens = (host, device) int32 lengths: hificar_xfmr_forward_train_ragged, or, packed,
+        hificar_xfmr_forward_train_packed) on the current stream: (out, batch statistics, tape or None, the tape's alignment offset)."""
         lib, handle = self._lib, self._handle
         B, _, T = x.shape
         dev = x.device
+        mp = self._packed_rows(lens[0], B, T) if packed else None
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             tape, toff = None, 0
             if keep_tape:
-                tape = torch.empty(lib.hificar_xfmr_tape_bytes(handle, B, T) + 256, dtype=torch.uint8, device=dev)
+                nbytes = lib.hificar_xfmr_tape_bytes_packed(handle, B, mp) if packed else lib.hificar_xfmr_tape_bytes(handle, B, T)
+                tape = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
                 toff = (-tape.data_ptr()) % 256
             out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=dev)
             stats = torch.empty((len(self._batch_norms()), 2, self._params["hidden_dim"]), dtype=torch.float32, device=dev)
-            ws_ptr, ws_bytes = self._train_workspace(B, T)
+            ws_ptr, ws_bytes = self._train_workspace(B, T, mp)
             tail = (B, T, float(p), seed, offset, tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
                     ws_ptr, ws_bytes, stream)
+            what = "hificar_xfmr_forward_train" if lens is None else "hificar_xfmr_forward_train_packed" if packed else "hificar_xfmr_forward_train_ragged"
             if lens is None:
                 rc = lib.hificar_xfmr_forward_train(handle, x.data_ptr(), out.data_ptr(), stats.data_ptr(), *tail)
             else:
-                rc = lib.hificar_xfmr_forward_train_ragged(handle, x.data_ptr(), lens[1].data_ptr(), lens[0].data_ptr(), out.data_ptr(),
-                                                           stats.data_ptr(), *tail)
-        _native.check(rc, "hificar_xfmr_forward_train" if lens is None else "hificar_xfmr_forward_train_ragged")
+                rc = getattr(lib, what)(handle, x.data_ptr(), lens[1].data_ptr(), lens[0].data_ptr(), out.data_ptr(), stats.data_ptr(), *tail)
+        _native.check(rc, what)
         return out, stats, tape, toff
 
     def _workspace(self, B, T):
@@ -470,7 +491,7 @@ class Transformer(torch.nn.Module):
         _native.check(rc, "hificar_xfmr_forward")
         return out
 
-    def forward_padded(self, x, lengths):
+    def forward_padded(self, x, lengths, packed=False):
         """A batch of whole utterances, zero-padded to (B, in_channels, T), with their frame counts ``lengths`` (B values in 0 .. T).
         eval(): ``forward(x, lengths=lengths)``.  train(): the training step on the ragged batch, under autograd — this package's
         definition, the reference never masks: the convs see zero padding at a sequence's own end, a query's keys lie below its sequence's
@@ -478,14 +499,17 @@ class Transformer(torch.nn.Module):
         the M = sum(lengths) valid frames (running variance: M / (M - 1)), ``out[b, :, lengths[b]:]`` is exactly zero; backwards, the output
         gradient on padded frames is ignored whatever it holds, the input gradient is zero there, and every parameter gradient sums valid
         frames only.  With every length equal to T all results are bitwise those of ``forward``.  What ``x`` holds in padded frames is
-        never used."""
+        never used.
+        ``packed=True`` (train() only; eval() ignores it): the same step, the same masks at the same seed, computed without GEMM rows for the
+        padding (hificar_xfmr_forward_train_packed): the sums over rows run in another order, so results equal the unpacked step's to
+        rounding, not bitwise."""
         if not self.training:
             return self.forward(x, lengths=lengths)
         if lengths is None:
             raise RuntimeError("Transformer.forward_padded needs lengths")
-        return self._forward_train(x, lengths, padded=True)
+        return self._forward_train(x, lengths, padded=True, packed=bool(packed))
 
-    def _forward_train(self, x, lengths, padded=False):
+    def _forward_train(self, x, lengths, padded=False, packed=False):
         """train() mode (transformer.py:55-77 with every nn.Dropout active and the batch norms on batch statistics): with grad enabled the
         output is part of the autograd graph; without, the same arithmetic runs and its tape is dropped.  Every call — either way —
         advances the dropout generator's offset and updates every batch norm's running_mean / running_var / num_batches_tracked as
@@ -494,6 +518,8 @@ class Transformer(torch.nn.Module):
             raise NotImplementedError("Transformer.forward(lengths=...) in train() mode is refused: ragged training uses masked batch "
                                       "statistics, this package's definition and not the reference's, so asking for it is explicit: call "
                                       "forward_padded(x, lengths) (or .eval() for ragged inference)")
+        if padded and packed and isinstance(x, torch.Tensor) and x.dim() == 3:  # the lengths first: checking them needs no device
+            self._check_lengths(lengths, x.shape[0], x.shape[2], torch.device("cpu"))
         if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
             raise NotImplementedError("Transformer.forward in train() mode needs a CUDA/HIP tensor: the training path exists on the device "
                                       "only, as HIP kernels (there is no CPU fallback)")
@@ -513,19 +539,22 @@ class Transformer(torch.nn.Module):
         self._native_handle(train=True)
         if x.device != self._device():
             raise RuntimeError(f"Transformer.forward: input on {x.device}, parameters on {self._device()}")
+        if padded and packed:
+            self._packed_rows(lens[0], B, T)  # (a batch too large to pack is refused here, before a mask is drawn)
         c = x.to(torch.float32).contiguous()
         named = list(self.named_parameters())
         names, params = tuple(k for k, _ in named), [p for _, p in named]
         offset = self._calls
         self._calls += 1
-        self._lens = lens
+        self._lens, self._packed = lens, packed and padded
         try:
             if torch.is_grad_enabled() and (c.requires_grad or any(p.requires_grad for p in params)):
                 out, stats = _TransformerFunction.apply(self, c, self._params["dropout"], self._dropout_seed, offset, names, *params)
             else:  # no graph: the same arithmetic without a tape (tape = NULL)
-                out, stats, _, _ = self._run_forward_train(c.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False, lens=lens)
+                out, stats, _, _ = self._run_forward_train(c.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False, lens=lens,
+                                                            packed=self._packed)
         finally:
-            self._lens = None
+            self._lens, self._packed = None, False
         self._last_stats = stats.detach()  # (number of batch norms, 2, hidden_dim): this batch's mean | biased variance, for inspection
         with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance (n: the valid frames)
             for j, bn in enumerate(self._batch_norms()):

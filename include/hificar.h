@@ -570,7 +570,8 @@ void hificar_bigru_destroy(hificar_bigru* h);
  * hificar_bigru_forward_train takes equal-length batches (the reference's CollaterMelArt cuts equal windows);
  * hificar_bigru_forward_train_ragged takes whole utterances of unequal lengths (this library's definition: the reference never masks).
  * All of these may be called after hificar_bigru_finalize; the first one builds the training state.
- * Not built: multi-GPU BiGRU training, packed (padding-free) GEMMs for ragged batches, use_ar, use_spk_emb. ---- */
+ * Not built: multi-GPU BiGRU training, packed (padding-free) GEMMs for ragged batches (the Transformer has them:
+ * hificar_xfmr_forward_train_packed), use_ar, use_spk_emb. ---- */
 
 /* Every float tensor of the state_dict (reference names and layouts, bn.running_mean / bn.running_var included; n = all of them, each
  * once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs, W_hh and
@@ -696,9 +697,10 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * mode: BatchNorm1d on batch statistics in the three ResBlocks, Dropout(p) on the attention probabilities, behind the attention and feed-forward
  * sub-blocks and on the feed-forward's hidden rows.  Exact fp32, deterministic: every reduction is summed in a fixed order, no floating-point
  * atomics.  hificar_xfmr_forward_train takes equal-length batches (the reference's CollaterMelArt cuts equal windows);
- * hificar_xfmr_forward_train_ragged takes whole utterances of unequal lengths (this library's definition: the reference never masks).
+ * hificar_xfmr_forward_train_ragged takes whole utterances of unequal lengths (this library's definition: the reference never masks), and
+ * hificar_xfmr_forward_train_packed computes the same step without GEMM rows for the padding.
  * All of these may be called after hificar_xfmr_finalize; the first one builds the training state.
- * Not built: packed (padding-free) GEMMs for ragged batches, a smaller tape, bf16x3, extra_art, num_ph, multi-GPU training of this model. ---- */
+ * Not built: a smaller tape per frame, bf16x3, extra_art, num_ph, multi-GPU training of this model. ---- */
 
 /* Every float tensor of the state_dict (reference names and layouts, the batch norms' running_mean / running_var included; n = all of them,
  * each once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs (the
@@ -762,6 +764,42 @@ int hificar_xfmr_forward_train_ragged(hificar_xfmr* h, const float* x, const int
  * hificar_xfmr_forward_train_ragged: see there. */
 int hificar_xfmr_backward(hificar_xfmr* h, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- The ragged step, packed: the same function as hificar_xfmr_forward_train_ragged + hificar_xfmr_backward — the same masks (dropout
+ * elements are those of the PADDED tensors, so they depend on T), the same batch statistics over the M valid rows, the same attention — with
+ * every GEMM, data gradient and weight gradient over Mp rows instead of B T; only the order of the sums over rows differs (results agree
+ * to rounding, not bitwise).  Inside, sequence b's frames are rows row0[b] .. row0[b] + lengths[b] - 1, one zero gap row follows every
+ * sequence (what a k = 3 conv over one run of rows needs to see each sequence's own end), and
+ *     Mp = sum over b of (lengths[b] + 1), rounded up to a multiple of 256        (hificar_xfmr_packed_rows; the tail rows are gap rows)
+ * x, out, dout and dx keep the padded (B, C, T) layout: out and dx are exactly zero on padded frames, x and dout are never read there (NaN
+ * included).  The tape and the workspace are sized by Mp (below), not by B T.  Deterministic, no atomics; what tape, workspace and outputs
+ * hold on entry does not matter.  Debug taps are delivered in the padded (B, T, width) layout, zeros on padded frames. ---- */
+
+/* Mp of a batch, on the host; 0 for invalid input: a null pointer, B or T < 1, a length outside 0 .. T, fewer than two frames in all, or
+ * Mp * 3072 >= 2^31. */
+int hificar_xfmr_packed_rows(int B, int T, const int32_t* lengths_host);
+
+/* Bytes of a packed tape and of the scratch shared by the packed forward and backward, for B sequences in Mp rows (T plays no part; 0 for
+ * an Mp that hificar_xfmr_packed_rows cannot return). */
+size_t hificar_xfmr_tape_bytes_packed(const hificar_xfmr* h, int B, int Mp);
+size_t hificar_xfmr_train_workspace_bytes_packed(hificar_xfmr* h, int B, int Mp);
+
+/* hificar_xfmr_forward_train_ragged's arguments and checks (lengths_host required: each length in 0 .. T, their sum >= 2, and
+ * Mp * 3072 < 2^31, all before anything is enqueued).  tape = NULL: the forward-only form. */
+int hificar_xfmr_forward_train_packed(hificar_xfmr* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out,
+                                      float* bn_batch_stats, int B, int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape,
+                                      size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The backward of a packed tape: hificar_xfmr_backward's arguments plus the forward's lengths on the host, which give Mp.  A separate entry
+ * point rather than a tape that hificar_xfmr_backward recognises: the tape's header lives on the device, and reading it back would cost
+ * every backward a synchronisation.  Instead the handle remembers, by address, the packed tapes it filled and their lengths (a dense or
+ * ragged forward into the same memory forgets the entry), so before anything is enqueued
+ *   hificar_xfmr_backward_packed on a tape that is not a packed tape of this handle      HIFICAR_E_STATE
+ *   hificar_xfmr_backward on a packed tape                                               HIFICAR_E_STATE
+ *   hificar_xfmr_backward_packed with another B, T or other lengths than the forward's   HIFICAR_E_INVALID
+ * and the tape stays usable for the right call.  A tape is known by its address: one copied elsewhere is not recognised. */
+int hificar_xfmr_backward_packed(hificar_xfmr* h, const float* dout, const int32_t* lengths_host, int B, int T, const void* tape, size_t tape_bytes,
+                                 float* grads, float* dx, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,12 +21,14 @@ linear, einsum, softmax, layer_norm under autograd, the attention banded too), i
 package's counter-based masks would be generated on the host).  The per-kernel profile covers one native forward + backward; the
 attention backward's TFLOP/s counts 2 * 7 * 199 * hidden FLOP per frame and layer (S, dP, the K and E parts of dQ, dK, dV, dE).
 
-   python tools/transformer_bench.py --train --ragged [--seed 0] [--out profiles/transformer_train_ragged.txt]
+   python tools/transformer_bench.py --train --ragged [--seed 0] [--full] [--out profiles/transformer_train_packed.txt]
 
 --train --ragged: one batch of whole utterances instead — the default size, B 32, padded to T 500, lengths uniform in 100 .. 500 from --seed
-(as tools/bigru_train_bench.py --ragged draws them) — and two legs of the same model in alternated windows: the native ragged step
-(Transformer.forward_padded + masked_l1_loss) and the native dense step on the same padded batch (every frame counted, as the reference's
-pad mode trains).  Then one profiled step of each: time per kernel, and what the skipped attention tiles recover.
+(as tools/bigru_train_bench.py --ragged draws them; --full: every length = T) — and three legs of the same model in alternated windows: the
+native packed step (Transformer.forward_padded(packed=True) + masked_l1_loss: no GEMM rows for the padding), the native ragged step
+(forward_padded + masked_l1_loss) and the native dense step on the same padded batch (every frame counted, as the reference's pad mode
+trains).  Then one profiled step of each: time per kernel, what the skipped attention tiles recover, the packed step's time over the
+ragged step's per kernel family beside Mp / (B T), and the tape bytes of the three forms.
 Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
 import argparse
 import ctypes
@@ -158,6 +160,8 @@ def ragged_train_main(a):
 
     p, B, T = 0.2, 32, 500
     lengths = torch.from_numpy(np.random.default_rng(a.seed).integers(100, T + 1, size=B)).to(torch.int64)
+    if a.full:
+        lengths = torch.full((B,), T, dtype=torch.int64)
     M = int(lengths.sum())
     valid = torch.arange(T)[None, :] < lengths[:, None]
     sd = synth_transformer_state_dict(PARAMS, seed=6101)
@@ -177,7 +181,8 @@ def ragged_train_main(a):
 
         return step
 
-    legs = {"native_ragged": make(lambda: masked_l1_loss(m.forward_padded(x, lens32), y, lens32)), "native_dense": make(lambda: F.l1_loss(m(x), y))}
+    legs = {"native_packed": make(lambda: masked_l1_loss(m.forward_padded(x, lens32, packed=True), y, lens32)),
+            "native_ragged": make(lambda: masked_l1_loss(m.forward_padded(x, lens32), y, lens32)), "native_dense": make(lambda: F.l1_loss(m(x), y))}
     for _ in range(2):
         for fn in legs.values():
             fn()
@@ -187,15 +192,22 @@ def ragged_train_main(a):
         for k, fn in legs.items():
             ms[k].append(window(fn, None, a.window))
     tiles = sum((T + 63) // 64 - (int(n) + 63) // 64 for n in lengths)
-    res = {"train": True, "case": "ragged", "B": B, "T": T, "dropout": p, "seed": a.seed, "valid_frames": M, "padded_share": round(1.0 - M / (B * T), 4),
-           "skipped_attention_tiles": tiles, "attention_tiles": B * ((T + 63) // 64)}
+    lib = m._lib
+    Mp = int(lib.hificar_xfmr_packed_rows(B, T, lens32.data_ptr()))
+    res = {"train": True, "case": "ragged", "B": B, "T": T, "dropout": p, "seed": a.seed, "full": bool(a.full), "valid_frames": M,
+           "padded_share": round(1.0 - M / (B * T), 4), "skipped_attention_tiles": tiles, "attention_tiles": B * ((T + 63) // 64), "packed_rows": Mp,
+           "packed_rows_over_padded_rows": round(Mp / (B * T), 4),
+           "tape_bytes": {"packed": int(lib.hificar_xfmr_tape_bytes_packed(m._handle, B, Mp)), "ragged": int(lib.hificar_xfmr_tape_bytes(m._handle, B, T)),
+                          "dense": int(lib.hificar_xfmr_tape_bytes(m._handle, B, T))}}
     for k, v in ms.items():
         res[k + "_step_ms"] = [round(u, 3) for u in v]
         res[k + "_spread"] = round(abs(v[0] - v[1]) / min(v), 4)
     res["dense_over_ragged"] = round(min(ms["native_dense"]) / max(ms["native_ragged"]), 3)  # slowest ragged, fastest dense
-    lib, eng = m._lib, m.engine()
+    res["ragged_over_packed"] = round(min(ms["native_ragged"]) / max(ms["native_packed"]), 3)  # slowest packed, fastest ragged
+    res["packed_windows_below_ragged"] = max(ms["native_packed"]) < min(ms["native_ragged"])
+    eng = m.engine()
     profs = {}
-    for tag in ("ragged", "dense"):
+    for tag in ("packed", "ragged", "dense"):
         _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
         legs["native_" + tag]()
         stats = (_native.HificarKernelStat * 128)()
@@ -206,6 +218,11 @@ def ragged_train_main(a):
         res[tag + "_kernels_total_ms"] = round(sum(profs[tag].values()), 3)
     res["attention_recovered_ms"] = {k: round(profs["dense"].get(k, 0.0) - profs["ragged"].get(k, 0.0), 4)
                                      for k in ("xfmr_attn_kernel<train>", "xfmr_attn_bwd_kernels")}
+    # packed over ragged per kernel family, to read beside packed_rows_over_padded_rows: conv_* are the forward GEMMs and the data gradients
+    fam = lambda prof, pre: sum(v for k, v in prof.items() if k.startswith(pre))  # noqa: E731
+    res["packed_over_ragged_ms"] = {k: round(profs["packed"].get(k, 0.0) / v, 4) for k, v in profs["ragged"].items() if v > 0}
+    res["packed_over_ragged_families"] = {pre: round(fam(profs["packed"], pre) / fam(profs["ragged"], pre), 4) for pre in ("conv", "wgrad", "xfmr_attn", "xfmr_")
+                                          if fam(profs["ragged"], pre) > 0}
     line = json.dumps(res)
     print(line, flush=True)
     if a.out:
@@ -225,6 +242,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--ragged", action="store_true", help="--train: the ragged batch's two legs instead of the dense shapes")
     ap.add_argument("--seed", type=int, default=0, help="--train --ragged: seed of the lengths")
+    ap.add_argument("--full", action="store_true", help="--train --ragged: every length = T (what the gap and rounding rows cost)")
     a = ap.parse_args()
     if a.ragged and not a.train:
         ap.error("--ragged goes with --train")
