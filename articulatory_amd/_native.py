@@ -112,6 +112,7 @@ SYMBOLS = (
     "hificar_bigru_backward",
     "hificar_xfmr_create",
     "hificar_xfmr_set_weight",
+    "hificar_xfmr_set_precision",
     "hificar_xfmr_finalize",
     "hificar_xfmr_workspace_bytes",
     "hificar_xfmr_forward",
@@ -508,6 +509,8 @@ def load_library():
     lib.hificar_xfmr_create.restype = ci
     lib.hificar_xfmr_set_weight.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(c64), ci]
     lib.hificar_xfmr_set_weight.restype = ci
+    lib.hificar_xfmr_set_precision.argtypes = [vp, ci]
+    lib.hificar_xfmr_set_precision.restype = ci
     lib.hificar_xfmr_finalize.argtypes = [vp]
     lib.hificar_xfmr_finalize.restype = ci
     lib.hificar_xfmr_workspace_bytes.argtypes = [vp, ci, ci]

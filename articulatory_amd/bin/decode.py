@@ -286,6 +286,9 @@ def get_parser():
     parser.add_argument("--verbose", type=int, default=1, help="logging level. higher is more logging. (default=1)")
     parser.add_argument("--batch-size", type=int, default=1,
                         help="utterances synthesised per device call (any lengths; not in the reference, which is batch-1)")
+    parser.add_argument("--precision", default=None, choices=("f32", "bf16x3"),
+                        help="arithmetic of the model's GEMMs, for models with set_precision (the Transformer): f32, the reference's IEEE fp32 "
+                             "products, or the opt-in fast mode bf16x3.  Not given: the model's own default, f32 (not in the reference)")
     parser.add_argument("--dry-run", default=False, action="store_true",
                         help="print this rank's share of the utterance list as one JSON line and exit (no GPU needed; not in the reference)")
     add_conditioning_arguments(parser)
@@ -457,6 +460,11 @@ def main(argv=None):
         assert hasattr(model, "mean"), "Feature stats are not registered."
         assert hasattr(model, "scale"), "Feature stats are not registered."
     model.remove_weight_norm()
+    if args.precision is not None:
+        if hasattr(model, "set_precision"):
+            model.set_precision(args.precision)  # (a class with one arithmetic refuses the other with its own message)
+        elif args.precision != "f32":
+            raise NotImplementedError(f"--precision {args.precision}: {type(model).__name__} runs in the exact-fp32 arithmetic only")
     model = model.eval().to(device)
     print(sum(p.numel() for p in model.parameters() if p.requires_grad))
     if dataset_mode in _FEAT_MODES:

@@ -1147,6 +1147,7 @@ struct ConvIO {
     float x_slope = -1.f;             // >= 0: xs holds PRE-activation fp32 rows, LeakyReLU(x_slope) is applied while staging (ConvParams::act_in; exact fp32 only)
     const float* x_more[3] = {nullptr, nullptr, nullptr};  // ... and the input is the mean of xs and these further streams (x_n in all), summed in this order
     int x_n = 1;
+    bool res_relu = false;            // res holds the rows before their ReLU (ConvParams::res_relu; bf16x3 dense launches only)
 };
 
 // Replicas of every branch at regular strides (the groups of a grouped conv): see MultiConvParams::zrep
@@ -1503,6 +1504,11 @@ static int launch_conv(hificar_engine* h, const ConvLayer* const* layers, int nb
             mp.p[b].act_in = io[b].x_n;
             for (int q = 0; q + 1 < io[b].x_n; ++q) mp.p[b].xs_more[q] = reinterpret_cast<const char*>(io[b].x_more[q]);
             mp.p[b].slope_in = io[b].x_slope;
+        }
+        if (io[b].res_relu) {
+            if (f32 || pl->shape.family == kConvSkBf16x3)
+                return fail(HIFICAR_E_INVALID, "internal: pre-activation residual rows of %s outside the dense bf16x3 launches", Lb.name.c_str());
+            mp.p[b].res_relu = 1;
         }
         mp.p[b].mask_src = io[b].mask_src;
         mp.p[b].mask_slope = io[b].mask_slope;

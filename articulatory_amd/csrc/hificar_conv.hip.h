@@ -98,6 +98,9 @@ struct ConvParams {
     // t / x_up == umulhi(t, x_up_rcp) for 0 <= t < 2^32 / x_up — two instructions in the staging loop instead of a division.
     int x_up;
     unsigned x_up_rcp;
+    // out-buffer output pass (write_out) only: 1 = the residual is max(res, 0) — its producer kept the fp32 rows BEFORE its ReLU (a bf16x3
+    // launch writes y pre-activation and the activated copy as split rows only), and the block's input is the activated value.  0 everywhere else.
+    int res_relu;
 };
 
 // A wave-uniform int the HOST wrote before the launch (tile schedules, sequence lengths), read through the scalar cache.  A plain load of it compiles to
@@ -413,6 +416,13 @@ __device__ __forceinline__ void conv_ws_body(const MP& mp) {
                         const float* rp = p.res + (seq_base + T.t0 + row_l) * p.cout_total + vc;
                         q0[q] = *reinterpret_cast<const f32x4*>(rp);
                         q1[q] = *reinterpret_cast<const f32x4*>(rp + 4);
+                        if (p.res_relu) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                q0[q][e] = fmaxf(q0[q][e], 0.f);
+                                q1[q][e] = fmaxf(q1[q][e], 0.f);
+                            }
+                        }
                     }
                 }
             }

@@ -12,6 +12,11 @@
 // are never written, so the k = 3 convs see each utterance's own end.  Exact fp32, split-K off: one accumulation order whatever the batch.
 // Workspace: the input rows, three row buffers [B T][F] that rotate, and one wide buffer [B T][3072] (q | k | v, then the feed-forward's
 // hidden rows, then w_out's rows).
+//
+// bf16x3 (hificar_xfmr_set_precision, eval only): every GEMM above runs in the engine's bf16x3 kernels, whose input is "split rows"
+// [hi: C bf16 | lo: C bf16] (4 C bytes per row, as fp32 rows) written by the producer: the engine's own output pass (ys), xfmr_rows_split_kernel,
+// xfmr_ln_kernel<true>, xfmr_attn_kernel<D, false, true>.  Everything else — attention, LayerNorm, bias and residual additions, the residual
+// stream — is fp32 as above.  Five row buffers instead of three: a GEMM's fp32 residual and the next GEMM's split input exist side by side.
 
 struct XfmrEncLayer {
     ConvLayer qkv, wo, l1, l2;
@@ -29,6 +34,7 @@ struct hificar_xfmr {
     ConvLayer c1[3], c2[3], rp, w_in, w_out;
     std::vector<XfmrEncLayer> enc;  // sized once, in hificar_xfmr_create (launch plans are keyed by the layers' addresses)
     int cin_pad = 0;
+    int precision = HIFICAR_PREC_F32;  // hificar_xfmr_set_precision: which fragments finalize packs and which kernels the forward launches
     bool finalized = false;
     struct Tap {
         float* dst;
@@ -156,13 +162,26 @@ extern "C" int hificar_xfmr_set_weight(hificar_xfmr* g, const char* name, const 
     return HIFICAR_OK;
 }
 
-// bias and exact-fp32 weight fragments of one layer (the bf16x3 fragments pack_conv would add are never used here)
+// bias and weight fragments of one layer, in the engine's arithmetic only (h->precision is set before the first pack): one resident copy
 static int xfmr_pack(hificar_engine* h, ConvLayer& L, const HostTensor& W, const std::vector<float>* bias) {
     std::vector<float> b((size_t)L.cout_total, 0.f);
     if (bias) std::copy(bias->begin(), bias->begin() + L.cout, b.begin());
     const int rc = upload(h, b, &L.d_bias);
     if (rc != HIFICAR_OK) return rc;
+    if (h->precision == HIFICAR_PREC_BF16X3) return pack_w16(h, L, W, L.chunk16, &L.d_w16);
     return pack_w32(h, L, W, L.chunk16, &L.d_w32);
+}
+
+static const char* xfmr_precision_name(int p) { return p == HIFICAR_PREC_BF16X3 ? "bf16x3" : "f32"; }
+
+extern "C" int hificar_xfmr_set_precision(hificar_xfmr* g, int precision) {
+    if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_precision: null handle");
+    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3) return fail(HIFICAR_E_INVALID, "unknown precision %d", precision);
+    if (g->finalized)
+        return fail(HIFICAR_E_STATE, "hificar_xfmr_set_precision after hificar_xfmr_finalize: the weights are packed for %s only; make a new handle",
+                    xfmr_precision_name(g->precision));
+    g->precision = precision;
+    return HIFICAR_OK;
 }
 
 // Conv1d followed by an eval-mode BatchNorm1d as one conv: y = (W x + b - mean) * gamma / sqrt(var + 1e-5) + beta, folded in double
@@ -185,25 +204,30 @@ static int xfmr_pack_folded(hificar_xfmr* g, ConvLayer& L, const std::string& co
 
 template <int D>
 static hipError_t xfmr_attn_attr() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_attn_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XfmrAttnLds<D>::bytes);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_attn_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XfmrAttnLds<D>::bytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_attn_kernel<D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)XfmrAttnLds<D>::bytes);
 }
 
+// split: the bf16x3 forward's instantiation, which stores split rows
 template <int D>
-static hipError_t xfmr_attn_launch_one(const XfmrAttnParams& p, dim3 grid, hipStream_t stream) {
-    hipLaunchKernelGGL((xfmr_attn_kernel<D>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
+static hipError_t xfmr_attn_launch_one(const XfmrAttnParams& p, dim3 grid, hipStream_t stream, bool split) {
+    if (split) hipLaunchKernelGGL((xfmr_attn_kernel<D, false, true>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
+    else hipLaunchKernelGGL((xfmr_attn_kernel<D>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
     return hipGetLastError();
 }
 
-static hipError_t xfmr_attn_launch(int d, const XfmrAttnParams& p, dim3 grid, hipStream_t stream) {
+static hipError_t xfmr_attn_launch(int d, const XfmrAttnParams& p, dim3 grid, hipStream_t stream, bool split = false) {
     switch (d) {
-        case 16: return xfmr_attn_launch_one<16>(p, grid, stream);
-        case 32: return xfmr_attn_launch_one<32>(p, grid, stream);
-        case 48: return xfmr_attn_launch_one<48>(p, grid, stream);
-        case 64: return xfmr_attn_launch_one<64>(p, grid, stream);
-        case 80: return xfmr_attn_launch_one<80>(p, grid, stream);
-        case 96: return xfmr_attn_launch_one<96>(p, grid, stream);
-        case 112: return xfmr_attn_launch_one<112>(p, grid, stream);
-        case 128: return xfmr_attn_launch_one<128>(p, grid, stream);
+        case 16: return xfmr_attn_launch_one<16>(p, grid, stream, split);
+        case 32: return xfmr_attn_launch_one<32>(p, grid, stream, split);
+        case 48: return xfmr_attn_launch_one<48>(p, grid, stream, split);
+        case 64: return xfmr_attn_launch_one<64>(p, grid, stream, split);
+        case 80: return xfmr_attn_launch_one<80>(p, grid, stream, split);
+        case 96: return xfmr_attn_launch_one<96>(p, grid, stream, split);
+        case 112: return xfmr_attn_launch_one<112>(p, grid, stream, split);
+        case 128: return xfmr_attn_launch_one<128>(p, grid, stream, split);
     }
     return hipErrorInvalidValue;
 }
@@ -216,6 +240,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
     hificar_engine* h = &g->eng;
     const int F = g->cfg.hidden_dim, d = F / kXfmrHeads;
     int rc;
+    h->precision = g->precision;  // (xfmr_pack goes by it)
     for (int i = 0; i < 3; ++i) {
         const std::string b = "conv_blocks." + std::to_string(i) + ".";
         if ((rc = xfmr_pack_folded(g, g->c1[i], b + "conv1", b + "bn1")) != HIFICAR_OK) return rc;
@@ -272,7 +297,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
     HIP_TRY(xfmr_attn_attr<128>());
     // the engine opens here, not in hificar_xfmr_create: a handle can be created and described without a device
     if ((rc = engine_open(h, true)) != HIFICAR_OK) return rc;
-    h->precision = HIFICAR_PREC_F32;
+    h->precision = g->precision;
     h->use_pair = false;
     h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's result does not depend on what it is batched with
     HIP_TRY(hipDeviceSynchronize());
@@ -283,7 +308,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
 
 struct XfmrWorkspace {
     float* xin;     // [rows][cin_pad]
-    float* r[3];    // [rows][F]
+    float* r[5];    // [rows][F]; r[3] and r[4] in bf16x3 only (null otherwise)
     float* wide;    // [rows][3072]
     size_t bytes;
 };
@@ -296,9 +321,11 @@ static XfmrWorkspace xfmr_plan_workspace(const hificar_xfmr* g, int B, int T, vo
     XfmrWorkspace w;
     char* p = static_cast<char*>(base);
     w.xin = reinterpret_cast<float*>(p);
-    for (int i = 0; i < 3; ++i) w.r[i] = reinterpret_cast<float*>(p + xb + i * rb);
-    w.wide = reinterpret_cast<float*>(p + xb + 3 * rb);
-    w.bytes = xb + 3 * rb + wb;
+    // bf16x3: split rows take a fp32 row's bytes, and the layer input and norm1's output exist in both formats at once: two more row buffers
+    const int nr = g->precision == HIFICAR_PREC_BF16X3 ? 5 : 3;
+    for (int i = 0; i < 5; ++i) w.r[i] = i < nr ? reinterpret_cast<float*>(p + xb + i * rb) : nullptr;
+    w.wide = reinterpret_cast<float*>(p + xb + nr * rb);
+    w.bytes = xb + nr * rb + wb;
     return w;
 }
 
@@ -319,6 +346,8 @@ extern "C" int hificar_xfmr_debug_tap(hificar_xfmr* g, const char* name, float* 
         g->taps.erase(name);
         return HIFICAR_OK;
     }
+    if (g->precision == HIFICAR_PREC_BF16X3 && std::string(name) == "conv_blocks")
+        return fail(HIFICAR_E_INVALID, "debug tap 'conv_blocks': a bf16x3 handle holds the conv blocks' output as split bf16 rows only, not as fp32 rows");
     g->taps[name] = {dst, capacity};
     return HIFICAR_OK;
 }
@@ -355,8 +384,11 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
     Ragged rg;
     rg.seq_len = lengths;
     rg.frames = T;
-    // one launch of one layer: xs -> y (fp32) and / or ys (the ReLU'd copy), + res
-    auto conv = [&](const ConvLayer& L, const float* xs, const float* res, float* y, float* ys) {
+    const bool x3 = g->precision == HIFICAR_PREC_BF16X3;
+    if (x3 && g->taps.count("conv_blocks")) return fail(HIFICAR_E_INVALID, "debug tap 'conv_blocks': a bf16x3 handle holds these rows as split bf16 rows only");
+    // one launch of one layer: xs -> y (fp32) and / or ys (the activated copy: ReLU, or with slope 1 the identity), + res.  xs and ys are fp32
+    // rows in exact fp32 and split rows in bf16x3; res_relu (bf16x3): res holds the rows before their ReLU
+    auto conv = [&](const ConvLayer& L, const float* xs, const float* res, float* y, float* ys, float slope = 0.f, bool res_relu = false) {
         const ConvLayer* ls[1] = {&L};
         ConvIO io[1];
         io[0] = ConvIO();
@@ -364,50 +396,69 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
         io[0].res = res;
         io[0].y = y;
         io[0].ys = reinterpret_cast<char*>(ys);
-        return launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream);
+        io[0].res_relu = res_relu;
+        return launch_conv(h, ls, 1, B, T, io, slope, rg, stream);
     };
-    auto layer_norm = [&](const float* src, const float* gamma, const float* beta, float* dst) {
+    // dst: the fp32 rows; dst_s (bf16x3): the same rows as split rows, the next GEMM's input
+    auto layer_norm = [&](const float* src, const float* gamma, const float* beta, float* dst, float* dst_s) {
         XfmrLnParams p;
         p.x = src;
         p.gamma = gamma;
         p.beta = beta;
         p.lengths = lengths;
         p.y = dst;
+        p.ys = reinterpret_cast<char*>(dst_s);
         p.B = B;
         p.T = T;
         p.F = F;
-        ProfScope prof(h, stream, "xfmr_ln_kernel", 8.0 * M * F, 8.0 * M * F);
-        hipLaunchKernelGGL(xfmr_ln_kernel, dim3((unsigned)(((long long)B * T + 3) / 4)), dim3(256), 0, stream, p);
+        ProfScope prof(h, stream, dst_s ? "xfmr_ln_kernel<split>" : "xfmr_ln_kernel", 8.0 * M * F, (dst_s ? 12.0 : 8.0) * M * F);
+        const dim3 grid((unsigned)(((long long)B * T + 3) / 4));
+        if (dst_s) hipLaunchKernelGGL(xfmr_ln_kernel<true>, grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL(xfmr_ln_kernel<false>, grid, dim3(256), 0, stream, p);
         return hipGetLastError();
     };
+    const bool has_rp = g->rp.cout != 0;
     {
-        ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
-        hipLaunchKernelGGL(xfmr_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, ws.xin,
-                           lengths, C, g->cin_pad, T, nullptr);
+        const dim3 grid((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B);
+        if (x3) {  // (no residual_path: block 0's conv2 takes the input as its fp32 residual, kept in r[1])
+            ProfScope prof(h, stream, "xfmr_rows_split_kernel", 0.0, 4.0 * M * (C + g->cin_pad * (has_rp ? 1 : 2)));
+            hipLaunchKernelGGL(xfmr_rows_split_kernel, grid, dim3(256), 0, stream, x, reinterpret_cast<char*>(ws.xin), has_rp ? nullptr : ws.r[1], lengths, C,
+                               g->cin_pad, T);
+        } else {
+            ProfScope prof(h, stream, "xfmr_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
+            hipLaunchKernelGGL(xfmr_rows_kernel, grid, dim3(256), 0, stream, x, ws.xin, lengths, C, g->cin_pad, T, nullptr);
+        }
         HIP_TRY(hipGetLastError());
     }
-    // conv_blocks: the block's input in `in`, its output in r[2] (blocks 0 and 2) or r[1] (block 1); r[0] holds conv1's ReLU'd output
+    // conv_blocks.  `in`: the block's input as conv1's operand; `res`: the same values as conv2's fp32 residual (block 0: residual_path's output).
+    // Exact fp32: one buffer is both — a conv2 writes only the ReLU'd sum (ys), into r[2] (blocks 0 and 2) or r[1] (block 1).
+    // bf16x3: the operand is split rows, so a conv2 writes the ReLU'd sum as split rows (ys: r[3], block 1: r[4]) and the sum BEFORE the ReLU as
+    // fp32 rows (y: r[1] / r[2]), which the next conv2 ReLUs as it reads its residual.  r[0] holds conv1's ReLU'd output.
     const float* in = ws.xin;
+    const float* res = x3 ? ws.r[1] : ws.xin;
     for (int i = 0; i < 3; ++i) {
-        float* const dst = i == 1 ? ws.r[1] : ws.r[2];
-        float* const other = i == 1 ? ws.r[2] : ws.r[1];
         if ((rc = conv(g->c1[i], in, nullptr, nullptr, ws.r[0])) != HIFICAR_OK) return rc;
-        const float* res = in;
-        if (i == 0 && g->rp.cout) {
-            if ((rc = conv(g->rp, in, nullptr, other, nullptr)) != HIFICAR_OK) return rc;
-            res = other;
+        if (i == 0 && has_rp) {
+            if ((rc = conv(g->rp, in, nullptr, ws.r[1], nullptr)) != HIFICAR_OK) return rc;
+            res = ws.r[1];
         }
-        if ((rc = conv(g->c2[i], ws.r[0], res, nullptr, dst)) != HIFICAR_OK) return rc;
-        in = dst;
+        float* const ys = x3 ? (i == 1 ? ws.r[4] : ws.r[3]) : (i == 1 ? ws.r[1] : ws.r[2]);
+        float* const y = x3 && i < 2 ? (res == ws.r[1] ? ws.r[2] : ws.r[1]) : nullptr;
+        if ((rc = conv(g->c2[i], ws.r[0], res, y, ys, 0.f, x3 && i > 0)) != HIFICAR_OK) return rc;
+        in = ys;
+        res = x3 ? y : ys;
     }
-    if ((rc = xfmr_emit_tap(g, "conv_blocks", in, MF, stream)) != HIFICAR_OK) return rc;
-    float* X = ws.r[0];  // the layer input; r[1] and r[2] are free from here on
-    if ((rc = conv(g->w_in, in, nullptr, X, nullptr)) != HIFICAR_OK) return rc;
+    if (!x3 && (rc = xfmr_emit_tap(g, "conv_blocks", in, MF, stream)) != HIFICAR_OK) return rc;
+    float* const X = ws.r[0];                     // the layer input, fp32 rows; r[1] and r[2] are free from here on
+    float* const Xs = x3 ? ws.r[4] : nullptr;     // bf16x3: ... and its split copy (r[3], w_raw_in's operand, is free after this launch)
+    // (bf16x3: slope 1 makes the activated copy the identity — w_raw_in's output is q | k | v's operand un-activated)
+    if ((rc = conv(g->w_in, in, nullptr, X, Xs, x3 ? 1.f : 0.f)) != HIFICAR_OK) return rc;
     if ((rc = xfmr_emit_tap(g, "w_raw_in", X, MF, stream)) != HIFICAR_OK) return rc;
+    float* const Ns = x3 ? ws.r[3] : nullptr;  // norm1's output as split rows
     for (int l = 0; l < g->cfg.elayers; ++l) {
         const XfmrEncLayer& E = g->enc[(size_t)l];
         const std::string name = "layers." + std::to_string(l);
-        if ((rc = conv(E.qkv, X, nullptr, ws.wide, nullptr)) != HIFICAR_OK) return rc;
+        if ((rc = conv(E.qkv, x3 ? Xs : X, nullptr, ws.wide, nullptr)) != HIFICAR_OK) return rc;
         {
             XfmrAttnParams p;
             p.qkv = ws.wide;
@@ -418,19 +469,19 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
             p.F = F;
             p.scale = (float)(1.0 / std::sqrt((double)d));
             // per query at most 199 keys: Q K^T, the positional product and P V
-            ProfScope prof(h, stream, "xfmr_attn_kernel", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
-            const hipError_t e = xfmr_attn_launch(d, p, dim3((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B), stream);
+            ProfScope prof(h, stream, x3 ? "xfmr_attn_kernel<split>" : "xfmr_attn_kernel", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
+            const hipError_t e = xfmr_attn_launch(d, p, dim3((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B), stream, x3);
             if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn_kernel launch failed: %s", hipGetErrorString(e));
         }
         if ((rc = conv(E.wo, ws.r[1], X, ws.r[2], nullptr)) != HIFICAR_OK) return rc;
-        HIP_TRY(layer_norm(ws.r[2], E.d_ln[0], E.d_ln[1], ws.r[1]));
+        HIP_TRY(layer_norm(ws.r[2], E.d_ln[0], E.d_ln[1], ws.r[1], Ns));
         if ((rc = xfmr_emit_tap(g, name + ".norm1", ws.r[1], MF, stream)) != HIFICAR_OK) return rc;
-        if ((rc = conv(E.l1, ws.r[1], nullptr, nullptr, ws.wide)) != HIFICAR_OK) return rc;
+        if ((rc = conv(E.l1, x3 ? Ns : ws.r[1], nullptr, nullptr, ws.wide)) != HIFICAR_OK) return rc;
         if ((rc = conv(E.l2, ws.wide, ws.r[1], ws.r[2], nullptr)) != HIFICAR_OK) return rc;
-        HIP_TRY(layer_norm(ws.r[2], E.d_ln[2], E.d_ln[3], X));
+        HIP_TRY(layer_norm(ws.r[2], E.d_ln[2], E.d_ln[3], X, Xs));
         if ((rc = xfmr_emit_tap(g, name, X, MF, stream)) != HIFICAR_OK) return rc;
     }
-    if ((rc = conv(g->w_out, X, nullptr, ws.wide, nullptr)) != HIFICAR_OK) return rc;
+    if ((rc = conv(g->w_out, x3 ? Xs : X, nullptr, ws.wide, nullptr)) != HIFICAR_OK) return rc;
     {
         const int Op = g->w_out.cout_pad;
         ProfScope prof(h, stream, "xfmr_out_kernel", 0.0, 4.0 * M * (O + Op));

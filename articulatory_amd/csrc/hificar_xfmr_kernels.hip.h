@@ -1,5 +1,7 @@
 // Kernels of the Transformer feature model (articulatory/models/transformer.py:21-105, layers articulatory/layers/pytorch_layers.py:94-423)
-// that are not GEMMs: the banded relative-position attention, the post-LayerNorm, and the layout changes at both ends.  Exact fp32.
+// that are not GEMMs: the banded relative-position attention, the post-LayerNorm, and the layout changes at both ends.  Exact fp32
+// arithmetic throughout; the bf16x3 forward's variants (xfmr_rows_split_kernel, xfmr_ln_kernel<true>, xfmr_attn_kernel<D, false, true>) differ
+// in the FORMAT they store — split rows for the bf16x3 GEMM that reads them (xfmr_store_split) — not in how they compute.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -95,6 +97,25 @@ __device__ __forceinline__ void xfmr_zero_head_row(float* row4g, bool in_tensor)
     for (int j = 0; j < D / 16; ++j) *reinterpret_cast<float4*>(row4g + 16 * j) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// The bf16x3 GEMMs' input format ("split rows", hificar_conv.hip.h): per row [hi: F bf16 | lo: F bf16], hi = bf16(x), lo = bf16(x - hi) — the
+// expression of the conv engine's own output pass, so a consumer cannot tell its producers apart.  This lane holds channels ch4 .. ch4 + 3 of
+// a row and lane ^ xm the neighbouring four (`odd`: this lane's are the upper four of the eight); the pair trades halves, so that the even
+// lane stores 16 bytes of the hi half and the odd lane 16 bytes of the lo half.  Both lanes of a pair must be active; `store` is the same for both.
+__device__ __forceinline__ void xfmr_store_split(char* row, int F, int ch4, bool odd, int xm, float a0, float a1, float a2, float a3, bool store) {
+    const float a[4] = {a0, a1, a2, a3};
+    bf16x4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        hi[e] = (__bf16)a[e];
+        lo[e] = (__bf16)(a[e] - (float)hi[e]);
+    }
+    const uint2 H = __builtin_bit_cast(uint2, hi), L = __builtin_bit_cast(uint2, lo);
+    const uint2 send = odd ? H : L;
+    const unsigned g0 = (unsigned)__shfl_xor((int)send.x, xm), g1 = (unsigned)__shfl_xor((int)send.y, xm);
+    const uint4 pk = odd ? make_uint4(g0, g1, L.x, L.y) : make_uint4(H.x, H.y, g0, g1);
+    if (store) *reinterpret_cast<uint4*>(row + (odd ? 2 * F : 0) + 2 * (odd ? ch4 - 4 : ch4)) = pk;
+}
+
 // TRAIN (the training forward): the kept probabilities are scaled by the dropout factor before P V (the denominator sums all of them, as
 // F.softmax followed by nn.Dropout does), L = m + log l is kept per query, and the `out` rows of padded frames are written as zeros (a
 // workgroup whose 64 queries are all padded writes them and returns).  The eval instantiation compiles none of it.
@@ -107,7 +128,9 @@ __device__ __forceinline__ size_t xfmr_attn_row0(const XfmrAttnParams& p, int b)
     return (size_t)b * p.T;
 }
 
-template <int D, bool TRAIN = false>
+// SPLIT (the bf16x3 forward; eval only): `out` is w_o's input and nothing else, so the rows are stored as split rows only (p.out: [B T][4 F
+// bytes]).  Lanes g and g ^ 1 of a query column hold eight adjacent channels of every 16-channel block: xfmr_store_split, no pass through LDS.
+template <int D, bool TRAIN = false, bool SPLIT = false>
 __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) {
     extern __shared__ float xfmr_lds[];
     constexpr int PT = D + 4, NS = D / 4, NM = D / 16, PP = kXfmrPosPitch;
@@ -237,6 +260,15 @@ __global__ __launch_bounds__(256) void xfmr_attn_kernel(const XfmrAttnParams p) 
             }
         }
     }
+    if constexpr (SPLIT) {
+        static_assert(!TRAIN, "split rows are an inference format");
+        const float inv = qok ? 1.f / l : 0.f;
+        char* const orow = reinterpret_cast<char*>(p.out) + (row0 + (qok ? q : q0)) * (size_t)p.F * 4;  // (qok is shared by the lanes of a column)
+#pragma unroll
+        for (int j = 0; j < NM; ++j)
+            xfmr_store_split(orow, p.F, h * D + 16 * j + 4 * g, g & 1, 16, o[j][0] * inv, o[j][1] * inv, o[j][2] * inv, o[j][3] * inv, qok);
+        return;
+    }
     if (!qok) {
         // (training: w_o's GEMM and its weight gradient read every row of `out`; a padded frame's is zeros)
         if constexpr (TRAIN) xfmr_zero_head_row<D>(p.out + (row0 + q) * p.F + h * D + 4 * g, q < p.T && !p.row0);
@@ -266,6 +298,7 @@ struct XfmrLnParams {
     int B, T, F;
     int zero_pad = 0;  // 1 (the ragged training step): rows at or past a length are written as zeros
     const int* pad_row = nullptr;  // the packed training step (B = 1, T = the packed rows, lengths null): a row r with pad_row[r] < 0 is a gap row
+    char* ys = nullptr;  // xfmr_ln_kernel<true>: the same rows once more as split rows [B T][4 F bytes], the next GEMM's bf16x3 input
 };
 
 __device__ __forceinline__ float xfmr_wave_sum(float v) {
@@ -274,6 +307,8 @@ __device__ __forceinline__ float xfmr_wave_sum(float v) {
     return v;
 }
 
+// SPLIT (the bf16x3 forward): the fp32 row (the next sub-block's residual) and its split copy p.ys (the next GEMM's input) in the same pass; F % 128 == 0
+template <bool SPLIT = false>
 __global__ __launch_bounds__(256) void xfmr_ln_kernel(const XfmrLnParams p) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -312,8 +347,11 @@ __global__ __launch_bounds__(256) void xfmr_ln_kernel(const XfmrLnParams p) {
         const int i = lane + 64 * j;
         if (i >= nv) continue;
         const float4 gv = gm[i], bv = bt[i];
-        y[i] = make_float4((v[j].x - mean) * rstd * gv.x + bv.x, (v[j].y - mean) * rstd * gv.y + bv.y, (v[j].z - mean) * rstd * gv.z + bv.z,
-                           (v[j].w - mean) * rstd * gv.w + bv.w);
+        const float4 r = make_float4((v[j].x - mean) * rstd * gv.x + bv.x, (v[j].y - mean) * rstd * gv.y + bv.y, (v[j].z - mean) * rstd * gv.z + bv.z,
+                                     (v[j].w - mean) * rstd * gv.w + bv.w);
+        y[i] = r;
+        // (F % 128 == 0, so nv is even: lanes i and i ^ 1 pass the test above together)
+        if constexpr (SPLIT) xfmr_store_split(p.ys + row * p.F * 4, p.F, 4 * i, i & 1, 1, r.x, r.y, r.z, r.w, true);
     }
 }
 
@@ -336,6 +374,39 @@ __global__ __launch_bounds__(256) void xfmr_rows_kernel(const float* __restrict_
         const int t = t0 + r, c = c0 + tx;
         if (t < tw && c < Cp) rows[(base + t) * Cp + c] = tile[tx][r];
     }
+}
+
+// The bf16x3 forward's input: the same rows as split rows [b T + t][hi: Cp bf16 | lo: Cp bf16] (raw: no activation; the padded channels are
+// zero bits), one 16-byte store per thread: thread u writes eight channels of one half of row u / 8.  rows32 (non-null when in_channels ==
+// hidden_dim: the input is block 0's fp32 residual as well as its operand): the fp32 rows too, as xfmr_rows_kernel writes them.
+__global__ __launch_bounds__(256) void xfmr_rows_split_kernel(const float* __restrict__ x, char* __restrict__ rows, float* __restrict__ rows32,
+                                                              const int* __restrict__ lengths, int C, int Cp, int T) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int len = lengths ? min(max(lengths[b], 0), T) : T;
+    for (int r = ty; r < 32; r += 8) {
+        const int c = c0 + r, t = t0 + tx;
+        tile[r][tx] = (c < C && t < len) ? x[((size_t)b * C + c) * T + t] : 0.f;
+    }
+    __syncthreads();
+    const size_t base = (size_t)b * T;
+    if (rows32)
+        for (int r = ty; r < 32; r += 8) {
+            const int t = t0 + r, c = c0 + tx;
+            if (t < T && c < Cp) rows32[(base + t) * Cp + c] = tile[tx][r];
+        }
+    const int r = threadIdx.x >> 3, half = (threadIdx.x >> 2) & 1, c8 = (threadIdx.x & 3) * 8;
+    const int t = t0 + r;
+    if (t >= T || c0 + c8 >= Cp) return;  // (32 | Cp)
+    bf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float a = tile[c8 + e][r];
+        const __bf16 hi = (__bf16)a;
+        v[e] = half ? (__bf16)(a - (float)hi) : hi;
+    }
+    *reinterpret_cast<bf16x8*>(rows + (base + t) * (size_t)Cp * 4 + (half ? 2 * Cp : 0) + 2 * (c0 + c8)) = v;
 }
 
 // rows [b T + t][Cp] -> out (B, C, T); frames at or past the sequence's length are written as zeros (their rows are not read)

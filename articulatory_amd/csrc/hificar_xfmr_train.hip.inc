@@ -107,6 +107,9 @@ static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts);
 static int xfmr_train_init(hificar_xfmr* g) {
     if (g->train) return HIFICAR_OK;
     if (!g->finalized) return fail(HIFICAR_E_STATE, "Transformer training entry points need hificar_xfmr_finalize first");
+    if (g->precision != HIFICAR_PREC_F32)
+        return fail(HIFICAR_E_STATE, "this Transformer handle is packed for the %s arithmetic: training and hificar_xfmr_set_parameters_device run in exact fp32 only",
+                    xfmr_precision_name(g->precision));
     // a failed set-up (out of device memory, in practice) is final for this handle, as for the BiGRU
     if (g->train_failed != HIFICAR_OK)
         return fail(g->train_failed, "the Transformer training state could not be set up on this handle earlier; destroy it and make a new one");
@@ -639,7 +642,7 @@ struct XfmrTrainCtx {
         p.F = F;
         p.pad_row = lay.pad_row;
         ProfScope prof(h, stream, "xfmr_ln_kernel", 8.0 * M * F, 8.0 * M * F);
-        hipLaunchKernelGGL(xfmr_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL(xfmr_ln_kernel<false>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, p);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }

@@ -23,6 +23,11 @@ reference trains (the tables then get no gradient).
 gradients.  ``forward_padded(x, lengths, packed=True)`` is the same step with no GEMM rows for the padding
 (``hificar_xfmr_forward_train_packed`` / ``hificar_xfmr_backward_packed``): the same masks and definitions, results equal to rounding.
 
+``precision="bf16x3"`` (opt-in; ``"f32"``, the reference's IEEE fp32 products, is the default) runs every GEMM of the eval-mode forward
+in the conv engine's bf16x3 kernels (x w ~ hi hi + hi lo + lo hi on bf16 MFMAs, fp32 accumulation); attention, LayerNorm, bias and residual
+additions and the residual stream stay fp32.  Inference only: a train()-mode forward of a bf16x3 model is refused.  Unlike
+``HiFiGANGenerator`` the constructor does not read ``$HIFICAR_PRECISION``: the arithmetic of this model is chosen by keyword only.
+
 Not built, refused with ``NotImplementedError``: ``extra_art=True`` and ``num_ph`` (phoneme input).  ``forward(lengths=...)`` in train() mode
 is refused too (ragged training is asked for by name: ``forward_padded``).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size``
 keywords are accepted and unused, as in the reference.
@@ -170,14 +175,30 @@ class _TransformerFunction(torch.autograd.Function):
         return (None, dx, None, None, None, None, *gw)
 
 
-class Transformer(torch.nn.Module):
+class _PrecisionKeyword(type):
+    """``Transformer(..., precision=None)``: this package's one constructor keyword beyond the reference's, taken by the class call so that
+    ``Transformer.__init__`` keeps the reference's signature, keyword for keyword (drop-in code inspects it).  None: "f32" —
+    ``$HIFICAR_PRECISION`` is deliberately not consulted (see the module's docstring); anything but "f32" / "bf16x3": ValueError."""
+
+    def __call__(cls, *args, precision=None, **kwargs):
+        if precision is None:
+            precision = "f32"
+        if precision not in _native.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_native.PRECISIONS)}")
+        self = super().__call__(*args, **kwargs)
+        self.precision = precision
+        return self
+
+
+class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
     """Three ResBlocks -> Linear -> ``elayers`` post-LayerNorm encoder layers (8 heads, learned relative positions, 3072-wide feed-forward)
-    -> Linear; MI355X-native, eval and train()."""
+    -> Linear; MI355X-native, eval and train().  ``precision="bf16x3"`` (keyword only): see the module's docstring and ``set_precision``."""
 
     def __init__(self, in_channels=8, out_channels=80, elayers=6, hidden_dim=768, dropout=.2, extra_art=False,
                  use_ar=False, ar_input=512, ar_hidden=256, ar_output=128, use_tanh=False,
                  num_ph=None, ph_emb_size=8, layer_type='default'):
         super().__init__()
+        self.precision = "f32"  # (Transformer(..., precision=...): _PrecisionKeyword)
         if extra_art:
             raise NotImplementedError("Transformer(extra_art=True) is not built (its kernel-size-2 input conv shortens the sequence by a frame)")
         if num_ph is not None:
@@ -211,6 +232,22 @@ class Transformer(torch.nn.Module):
         from ..utils.optim_hook import watch
 
         watch(self)  # fused optimizers do not bump Parameter._version: every optimizer.step() over these parameters marks them stale
+
+    def set_precision(self, precision):
+        """Arithmetic of the following eval-mode forwards: "f32" or "bf16x3".  The native handle holds the weight fragments of one
+        arithmetic only, so a change drops it: the next forward builds a new handle from the parameters' host copies
+        (hificar_xfmr_set_precision between create and finalize).  A model that has just trained in fp32 can therefore be switched to
+        bf16x3 for evaluation, at the cost of one trip of its weights through the host (and one more to switch back)."""
+        if precision not in _native.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_native.PRECISIONS)}")
+        if precision != self.precision:
+            self.precision = precision
+            self._invalidate()
+
+    def _refuse_bf16x3_training(self):
+        if self.precision != "f32":
+            raise RuntimeError(f"training runs in the exact-fp32 arithmetic: this Transformer has precision='{self.precision}' "
+                               "(set_precision('f32') before train()-mode forwards)")
 
     # ------------------------------------------------------------------ training surface
     def set_dropout_seed(self, seed, offset=0):
@@ -375,6 +412,7 @@ class Transformer(torch.nn.Module):
                     shape = (ctypes.c_int64 * t.dim())(*t.shape)
                     _native.check(lib.hificar_xfmr_set_weight(handle, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim()),
                                   "hificar_xfmr_set_weight")
+                _native.check(lib.hificar_xfmr_set_precision(handle, _native.PRECISIONS[self.precision]), "hificar_xfmr_set_precision")
                 _native.check(lib.hificar_xfmr_finalize(handle), "hificar_xfmr_finalize")
             except Exception:
                 lib.hificar_xfmr_destroy(handle)
@@ -453,7 +491,7 @@ class Transformer(torch.nn.Module):
     def debug_tap(self, name, dst=None):
         """Test aid (hificar_xfmr_debug_tap): the following forwards copy intermediate ``name`` — "conv_blocks", "w_raw_in", "layers.N.norm1",
         "layers.N" — as rows (B, T, hidden_dim) into the float32 CUDA tensor ``dst``; ``dst=None`` forgets it, ``name=None`` all of them.  A
-        train()-mode forward serves its ReLU outputs: "conv_blocks.N.relu1", "conv_blocks.N.relu2" and "layers.N.hidden" (B, T, 3072)."""
+        bf16x3 model refuses "conv_blocks" (those rows exist as split bf16 rows only).  A train()-mode forward serves its ReLU outputs: "conv_blocks.N.relu1", "conv_blocks.N.relu2" and "layers.N.hidden" (B, T, 3072)."""
         handle = self._native_handle()
         _native.check(self._lib.hificar_xfmr_debug_tap(handle, name.encode() if name is not None else None, dst.data_ptr() if dst is not None else None,
                                                        dst.numel() if dst is not None else 0), "hificar_xfmr_debug_tap")
@@ -465,6 +503,7 @@ class Transformer(torch.nn.Module):
         lengths[b] frames (the convs see zero padding at its own end, its keys stop at its length), out[b, :, lengths[b]:] is zero, and
         what x holds past a length is never read."""
         if self.training:
+            self._refuse_bf16x3_training()  # (before any device check)
             return self._forward_train(x, lengths)
         if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
             raise RuntimeError("Transformer.forward needs a CUDA/HIP tensor; there is no CPU fallback")
@@ -505,6 +544,7 @@ class Transformer(torch.nn.Module):
         rounding, not bitwise."""
         if not self.training:
             return self.forward(x, lengths=lengths)
+        self._refuse_bf16x3_training()
         if lengths is None:
             raise RuntimeError("Transformer.forward_padded needs lengths")
         return self._forward_train(x, lengths, padded=True, packed=bool(packed))

@@ -631,9 +631,13 @@ int hificar_bigru_backward(hificar_bigru* h, const float* dout, int B, int T, co
  * (8-head self-attention with learned relative positions up to distance 100, a 3072-wide ReLU feed-forward), Linear.  nhead = 8,
  * dim_feedforward = 3072 and relative_positional_distance = 100 are the reference constructor's constants.  The attention is computed in its
  * banded form: a sequence of more than 100 frames has every logit with |k - q| >= 100 lowered by 1e8 in the reference (weight exactly 0 in
- * fp32), so only keys with |k - q| <= 99 are visited.  Training: the block behind hificar_xfmr_destroy.  Not built: bf16x3, extra_art, num_ph
+ * fp32), so only keys with |k - q| <= 99 are visited.  Training: the block behind hificar_xfmr_destroy.  Not built: extra_art, num_ph
  * (the binding refuses them).
- * Exact fp32.  Errors as everywhere: a negative HIFICAR_E_* code and hificar_last_error().
+ * Exact fp32 by default.  Opt-in bf16x3 (hificar_xfmr_set_precision, inference only): every GEMM — the ResBlock convs and residual_path,
+ * w_raw_in, q | k | v, w_o, linear1, linear2, w_out — runs in the conv engine's bf16x3 kernels (x w ~ hi hi + hi lo + lo hi on bf16 MFMAs, fp32
+ * accumulation); the attention, LayerNorm, bias and residual additions and the residual stream stay fp32.  Not built: the attention's products
+ * on bf16 MFMAs, bf16x3 training, a device-side bf16 fragment pack.
+ * Errors as everywhere: a negative HIFICAR_E_* code and hificar_last_error().
  * --------------------------------------------------------------------------------------------------------------------------- */
 #define HIFICAR_XFMR_MAX_IN 4096
 #define HIFICAR_XFMR_MAX_OUT 1024
@@ -661,12 +665,21 @@ int hificar_xfmr_create(const hificar_xfmr_config* cfg, hificar_xfmr** out);
  * "w_out.bias".  F = hidden_dim, d = F / 8.  data: HOST pointer to contiguous fp32; the caller keeps ownership. */
 int hificar_xfmr_set_weight(hificar_xfmr* h, const char* name, const float* data, const int64_t* shape, int ndim);
 
+/* The arithmetic of the handle's GEMMs: HIFICAR_PREC_F32 (the default) or HIFICAR_PREC_BF16X3.  Legal between hificar_xfmr_create and
+ * hificar_xfmr_finalize only (HIFICAR_E_STATE afterwards): finalize packs the weight fragments of the chosen arithmetic alone and drops the host
+ * tensors.  An unknown value: HIFICAR_E_INVALID.  Touches no device.  A bf16x3 handle serves hificar_xfmr_forward; every training entry point
+ * and hificar_xfmr_set_parameters_device refuse it with HIFICAR_E_STATE (there is no device-side bf16 fragment pack), and so does the debug
+ * tap "conv_blocks" with HIFICAR_E_INVALID (those rows exist as split bf16 rows only).  As in exact fp32, split-K is off: a sequence's result
+ * does not depend on what it is batched with. */
+int hificar_xfmr_set_precision(hificar_xfmr* h, int precision);
+
 /* model.eval().to(device): checks that every tensor arrived, folds the batch norms into their convs (in double), repacks w_q / w_k / w_v into
  * one GEMM and w_o into another, uploads.  Synchronises the device once. */
 int hificar_xfmr_finalize(hificar_xfmr* h);
 
-/* Bytes of device scratch hificar_xfmr_forward needs for B sequences of T frames: the input rows, three row buffers of hidden_dim floats and
- * one of 3072 floats per frame (B T rounded up to 256 rows). */
+/* Bytes of device scratch hificar_xfmr_forward needs for B sequences of T frames: the input rows, three row buffers of hidden_dim floats (five
+ * on a bf16x3 handle: the layer input and norm1's output exist as fp32 rows and as split rows at once) and one of 3072 floats per frame (B T
+ * rounded up to 256 rows).  Answers for the handle's arithmetic as it stands: ask after hificar_xfmr_set_precision. */
 size_t hificar_xfmr_workspace_bytes(const hificar_xfmr* h, int B, int T);
 
 /* Transformer.forward in eval mode (transformer.py:55-77): x (B, in_channels, T) device fp32 -> out (B, out_channels, T) device fp32.

@@ -13,6 +13,14 @@ hificar_profile_begin / hificar_profile_end on one native forward: time per kern
 achieved TFLOP/s — counted as 2 * 3 * 199 * hidden FLOP per frame and layer (Q K^T, the positional product, P V over a full band) — against
 the 157.3 TFLOP/s fp32 matrix peak.
 
+   python tools/transformer_bench.py --precision bf16x3 [--out profiles/transformer_bf16x3.txt]
+
+--precision bf16x3: a third leg, the same model with precision="bf16x3" (every GEMM in the conv engine's bf16x3 kernels), alternated
+native-f32 / native-bf16x3 / stock, two windows each, in the same process.  Per B the line then also carries bf16x3_ms, the factor
+f32_over_bf16x3 (fastest f32 window over slowest bf16x3 window: the conservative one), bf16x3_faster — the slowest bf16x3 window is
+below the fastest f32 window by more than the two legs' window spreads added — the bf16x3 forward's error against the stock result,
+and its own per-kernel table (bf16x3_kernels_ms) with the attention's and the GEMMs' shares.
+
    python tools/transformer_bench.py --train [--shapes 8x200 32x500] [--out profiles/transformer_train.txt]
 
 --train: one training step (forward in train() mode, dropout 0.2 + L1 loss + backward + fused Adam) at the same default size, per shape B x T,
@@ -239,6 +247,7 @@ def main():
     ap.add_argument("--frames", type=int, default=2000)
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--no-stock", action="store_true")
+    ap.add_argument("--precision", choices=("f32", "bf16x3"), default="f32", help="bf16x3: add the bf16x3 leg to the native / stock alternation")
     ap.add_argument("--out", default=None)
     ap.add_argument("--ragged", action="store_true", help="--train: the ragged batch's two legs instead of the dense shapes")
     ap.add_argument("--seed", type=int, default=0, help="--train --ragged: seed of the lengths")
@@ -255,6 +264,11 @@ def main():
     native = Transformer(**PARAMS)
     native.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
     native = native.eval().cuda()
+    fast = None
+    if a.precision == "bf16x3":
+        fast = Transformer(**PARAMS, precision="bf16x3")
+        fast.load_state_dict(native.state_dict(), strict=True)
+        fast = fast.eval().cuda()
     stock = None if a.no_stock else TransformerOracle(sd, dtype=torch.float32, device="cuda").forward
     lines = []
     with torch.no_grad():
@@ -267,10 +281,19 @@ def main():
                 res["native_vs_stock_max_rel"] = float((y - ys).abs().max() / ys.abs().max())
                 for _ in range(2):
                     native(x), stock(x)
+            if fast is not None:
+                yf = fast(x)
+                res["bf16x3_vs_f32_max_rel"] = float((yf - y).abs().max() / y.abs().max())
+                if stock is not None:
+                    res["bf16x3_vs_stock_max_rel"] = float((yf - ys).abs().max() / ys.abs().max())
+                for _ in range(2):
+                    fast(x)
             torch.cuda.synchronize()
             n1 = window(native, x, a.window)
+            f1 = None if fast is None else window(fast, x, a.window)
             s1 = None if stock is None else window(stock, x, a.window)
             n2 = window(native, x, a.window)
+            f2 = None if fast is None else window(fast, x, a.window)
             s2 = None if stock is None else window(stock, x, a.window)
             res["native_ms"] = [round(n1, 4), round(n2, 4)]
             res["native_frames_per_s"] = round(B * T / (min(n1, n2) * 1e-3))
@@ -290,6 +313,21 @@ def main():
             flop = 2.0 * 3 * 199 * PARAMS["hidden_dim"] * B * T * PARAMS["elayers"]
             res["attn_tflops"] = round(flop / (attn * 1e-3) / 1e12, 2) if attn else None
             res["attn_of_peak"] = round(flop / (attn * 1e-3) / 1e12 / PEAK_TFLOPS, 4) if attn else None
+            if fast is not None:
+                res["bf16x3_ms"] = [round(f1, 4), round(f2, 4)]
+                res["bf16x3_frames_per_s"] = round(B * T / (min(f1, f2) * 1e-3))
+                res["bf16x3_spread"] = round(abs(f1 - f2) / min(f1, f2), 4)
+                res["f32_over_bf16x3"] = round(min(n1, n2) / max(f1, f2), 3)
+                res["bf16x3_faster"] = bool(min(n1, n2) - max(f1, f2) > abs(n1 - n2) + abs(f1 - f2))
+                if s1 is not None:
+                    res["stock_over_bf16x3"] = round(min(s1, s2) / max(f1, f2), 3)
+                fprof = kernel_profile(fast, x)
+                ftotal = sum(ms for _, ms in fprof.values())
+                fattn = fprof.get("xfmr_attn_kernel<split>", (0, 0.0))[1]
+                res["bf16x3_kernels_ms"] = {k: round(ms, 4) for k, (_, ms) in sorted(fprof.items())}
+                res["bf16x3_profiled_total_ms"] = round(ftotal, 4)
+                res["bf16x3_attn_share"] = round(fattn / ftotal, 4) if ftotal else None
+                res["bf16x3_gemm_share"] = round(sum(ms for k, (_, ms) in fprof.items() if k.startswith("conv_")) / ftotal, 4) if ftotal else None
             lines.append(json.dumps(res))
             print(lines[-1], flush=True)
     if a.out:
