@@ -119,6 +119,8 @@ SYMBOLS = (
     "hificar_xfmr_debug_tap",
     "hificar_xfmr_engine",
     "hificar_xfmr_destroy",
+    "hificar_xfmr_set_train_precision",
+    "hificar_debug_pack16",
     "hificar_xfmr_set_parameters_device",
     "hificar_xfmr_grad_count",
     "hificar_xfmr_grad_info",
@@ -513,6 +515,10 @@ def load_library():
     lib.hificar_xfmr_set_precision.restype = ci
     lib.hificar_xfmr_finalize.argtypes = [vp]
     lib.hificar_xfmr_finalize.restype = ci
+    lib.hificar_xfmr_set_train_precision.argtypes = [vp, ci]
+    lib.hificar_xfmr_set_train_precision.restype = ci
+    lib.hificar_debug_pack16.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, cs, ctypes.POINTER(cs)]
+    lib.hificar_debug_pack16.restype = ci
     lib.hificar_xfmr_workspace_bytes.argtypes = [vp, ci, ci]
     lib.hificar_xfmr_workspace_bytes.restype = cs
     lib.hificar_xfmr_forward.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]

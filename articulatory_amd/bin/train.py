@@ -649,7 +649,10 @@ class InversionTrainer:
     trains on it).  ``package_mode: pad_masked`` (this package's key) is the same step under a name that says what it does; it is the way
     in for the Transformer, for which ``pad`` stays refused.  ``pad_packed: true`` (this package's key, default false; the Transformer under
     ``pad_masked`` only): the same step through ``forward_padded(..., packed=True)``, which spends no GEMM rows on the padding.
-    ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval mode, under ``masked_l1_loss`` (``pad_packed`` plays no part there)."""
+    ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval mode, under ``masked_l1_loss`` (``pad_packed`` plays no part there).
+    ``train_precision: bf16x3`` (this package's key, default ``f32``; the Transformer only, the BiGRU is refused): the training step's forward
+    GEMMs and data gradients in the bf16x3 kernels (``Transformer.set_train_precision``), in every package mode; the first log line names the
+    arithmetic.  Checkpoints do not change: the weights are fp32 either way."""
 
     def __init__(self, config, device):
         self.config, self.device = config, device
@@ -682,9 +685,20 @@ class InversionTrainer:
             raise NotImplementedError(f"pad_packed is built for generator_type Transformer with package_mode pad_masked (got {gtype} with "
                                       f"package_mode {self.package_mode}): the BiGRU has no packed form; drop the key, or set package_mode: "
                                       "pad_masked for the Transformer")
+        # train_precision (this package's key, default f32): the arithmetic of the Transformer's forward GEMMs and data gradients in training
+        # (Transformer.set_train_precision); the weights, and so the checkpoints, are fp32 either way
+        self.train_precision = config.get("train_precision", "f32")
+        if self.train_precision not in ("f32", "bf16x3"):
+            raise ValueError(f"train_precision must be f32 or bf16x3 (got {self.train_precision!r})")
+        if self.train_precision != "f32" and gtype != "Transformer":
+            raise NotImplementedError(f"train_precision {self.train_precision} is built for generator_type Transformer (got {gtype}): the BiGRU "
+                                      "trains in exact fp32; drop the key")
+        logging.info(f"InversionTrainer: generator_type {gtype}, training arithmetic {self.train_precision}")
         import articulatory_amd.models as models
 
         self.G = getattr(models, gtype)(**config["generator_params"]).to(device).train()
+        if self.train_precision != "f32":
+            self.G.set_train_precision(self.train_precision)
         self.optimizer = {"generator": _optimizer(config.get("generator_optimizer_type", "Adam"), self.G.parameters(),
                                                   config["generator_optimizer_params"], config.get("fused_optimizers", True))}
         self.scheduler = {"generator": getattr(torch.optim.lr_scheduler, config.get("generator_scheduler_type", "StepLR"))(

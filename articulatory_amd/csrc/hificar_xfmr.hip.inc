@@ -35,6 +35,9 @@ struct hificar_xfmr {
     std::vector<XfmrEncLayer> enc;  // sized once, in hificar_xfmr_create (launch plans are keyed by the layers' addresses)
     int cin_pad = 0;
     int precision = HIFICAR_PREC_F32;  // hificar_xfmr_set_precision: which fragments finalize packs and which kernels the forward launches
+    // hificar_xfmr_set_train_precision: the arithmetic of the training step's forward and data-gradient GEMMs (an f32 handle only; the eval
+    // forward goes by `precision` alone)
+    int train_precision = HIFICAR_PREC_F32;
     bool finalized = false;
     struct Tap {
         float* dst;

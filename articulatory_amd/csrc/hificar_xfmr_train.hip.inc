@@ -15,6 +15,11 @@
 // Packed batches (hificar_xfmr_forward_train_packed / hificar_xfmr_backward_packed): the ragged step on Mp = sum (length + 1) rows, rounded up to
 // 256, instead of B T: every sequence's frames back to back with one zero gap row behind each, so that every launch — k = 3 included — is one run
 // of Mp rows; the same code path with XfmrTrainCtx::lay set.  The same buffer rule with "gap row" for "padded row".
+// bf16x3 training (hificar_xfmr_set_train_precision): every forward GEMM and every data gradient — all of them XfmrTrainCtx::conv — runs the
+// layer's bf16 twin (the same ConvLayer with d_w16 filled by pack16_kernel) in the engine's bf16x3 kernels, on split rows that
+// xfmr_split_rows_kernel writes from the fp32 operand into one scratch buffer.  The engine is told by its precision field, set around
+// the launch alone: the precision is part of the plan key, so these launches have plans of their own and every fp32 launch plans and
+// runs as before.  Weight and bias gradients (XfmrTrainCtx::wgrad), the attention, the norms, the dropout and the tape are the fp32 step's.
 
 struct XfmrTrainLayer {
     ConvLayer dg_qkv, dg_wo, dg_l1, dg_l2;
@@ -44,6 +49,8 @@ struct XfmrTrain {
     ConvLayer dg_win, dg_wout;
     std::vector<XfmrTrainLayer> enc;
     bool have_params = false;
+    bool have16 = false;      // the bf16 fragments of every forward and data-gradient layer are allocated (the first bf16x3 training arithmetic)
+    int fwd_precision = HIFICAR_PREC_F32;  // the arithmetic of the last training forward: a backward in the other one is refused
     // The packed tapes this handle filled, by address, with the frame counts their forward ran on: what lets a backward refuse, before it
     // enqueues anything, a tape of the other kind or other counts than the forward's (the tape's own header lives on the device).  A dense
     // or ragged forward into the same memory takes the entry out.
@@ -103,6 +110,37 @@ static int xfmr_alloc(hificar_engine* h, size_t bytes, void** out) {
 }
 
 static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts);
+static int xfmr_repack(hificar_xfmr* g, hipStream_t stream);
+static size_t xfmr_pack16_bytes(const ConvLayer& L);
+
+// bf16 fragment buffers of every layer XfmrTrainCtx::conv launches (the layers' fp32 twins stay as they are), once
+static int xfmr_train_alloc16(hificar_xfmr* g, XfmrTrain* ts) {
+    if (ts->have16) return HIFICAR_OK;
+    hificar_engine* h = &g->eng;
+    std::vector<ConvLayer*> ls;
+    for (auto& bn : ts->bns) {
+        ls.push_back(&bn.raw);
+        ls.push_back(&bn.dg);
+    }
+    ls.push_back(&g->w_in);
+    ls.push_back(&g->w_out);
+    ls.push_back(&ts->dg_win);
+    ls.push_back(&ts->dg_wout);
+    for (size_t l = 0; l < g->enc.size(); ++l) {
+        XfmrEncLayer& L = g->enc[l];
+        XfmrTrainLayer& D = ts->enc[l];
+        for (ConvLayer* p : {&L.qkv, &L.wo, &L.l1, &L.l2, &D.dg_qkv, &D.dg_wo, &D.dg_l1, &D.dg_l2}) ls.push_back(p);
+    }
+    for (ConvLayer* L : ls) {
+        if (L->d_w16) continue;
+        void* p = nullptr;
+        const int rc = xfmr_alloc(h, xfmr_pack16_bytes(*L), &p);
+        if (rc != HIFICAR_OK) return rc;
+        L->d_w16 = static_cast<uint16_t*>(p);
+    }
+    ts->have16 = true;
+    return HIFICAR_OK;
+}
 
 static int xfmr_train_init(hificar_xfmr* g) {
     if (g->train) return HIFICAR_OK;
@@ -259,8 +297,44 @@ extern "C" int64_t hificar_xfmr_grad_floats(hificar_xfmr* g) {
     return g->train->grad_total;
 }
 
-// forward pack (+ bias, when the layer has one) of a layer, and its data-gradient pack, from a (cout, cin, K) weight on the device
-static int xfmr_pack_dev(const ConvLayer& L, const ConvLayer* D, const float* w, const float* b, hipStream_t stream) {
+static size_t xfmr_pack16_bytes(const ConvLayer& L) {
+    return ((size_t)L.n_blocks32 * (L.cin_pad / L.chunk16) * L.ntaps * (L.chunk16 / 16) * 2 + 4 * (L.chunk16 / 16)) * 512 * sizeof(uint16_t);
+}
+
+// mode 0: P's own weight `w` (P.cout, P.cin, K);  mode 2: P is the data-gradient layer of the (cout, cin, K) weight `w`
+static Pack16Params xfmr_pack16_params(const ConvLayer& P, const float* w, uint16_t* dst, int mode, int cin, int cout) {
+    Pack16Params p;
+    memset(&p, 0, sizeof(p));
+    p.src = w;
+    p.dst = dst;
+    p.mode = mode;
+    p.n_blocks32 = P.n_blocks32;
+    p.nchunk = P.cin_pad / P.chunk16;
+    p.ntaps = P.ntaps;
+    p.nc16 = P.chunk16 / 16;
+    p.chunk = P.chunk16;
+    p.cin = cin;
+    p.cout = cout;
+    p.K = P.K;
+    p.cin_pack = P.cin;
+    p.cout_pack = P.cout;
+    for (int t = 0; t < kPack16MaxTaps; ++t) p.tap_k[t] = t < P.ntaps ? P.tap_k[0][t] : -1;
+    return p;
+}
+
+static int launch_pack16(hificar_engine* h, const Pack16Params& p, hipStream_t stream) {
+    const long long n = pack16_items(p);
+    ProfScope prof(h, stream, "pack16_kernel", 0.0, 4.0 * p.cin * p.cout * p.K + 2.0 * (double)pack16_frags(p) * 512);
+    hipLaunchKernelGGL(pack16_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 2048)), dim3(256), 0, stream, p);
+    HIP_TRY(hipGetLastError());
+    return HIFICAR_OK;
+}
+
+// forward pack (+ bias, when the layer has one) of a layer, and its data-gradient pack, from a (cout, cin, K) weight on the device.
+// x3 (the bf16x3 training arithmetic): the bf16 fragments of both, and of the fp32 packs only what the eval forward reads — the forward
+// pack of a layer it runs (train_only = false)
+static int xfmr_pack_dev(hificar_engine* h, const ConvLayer& L, const ConvLayer* D, const float* w, const float* b, hipStream_t stream, bool x3 = false,
+                         bool train_only = false) {
     int rc;
     PackParams pp;
     fill_pack(pp, L, L.chunk16);
@@ -272,14 +346,19 @@ static int xfmr_pack_dev(const ConvLayer& L, const ConvLayer* D, const float* w,
     pp.K = L.K;
     pp.cin_pack = L.cin;
     pp.cout_pack = L.cout;
-    if ((rc = launch_pack(pp, stream)) != HIFICAR_OK) return rc;
+    if (!(x3 && train_only) && (rc = launch_pack(pp, stream)) != HIFICAR_OK) return rc;
+    if (x3) {
+        if (L.n_phase != 1 || !L.d_w16 || (D && (D->n_phase != 1 || !D->d_w16))) return fail(HIFICAR_E_INVALID, "internal: no bf16 fragments for %s", L.name.c_str());
+        if ((rc = launch_pack16(h, xfmr_pack16_params(L, w, L.d_w16, 0, L.cin, L.cout), stream)) != HIFICAR_OK) return rc;
+        if (D && (rc = launch_pack16(h, xfmr_pack16_params(*D, w, D->d_w16, 2, L.cin, L.cout), stream)) != HIFICAR_OK) return rc;
+    }
     if (b) {
         PackParams pb = simple_pack(6, b, L.d_bias, (long long)L.n_phase * L.cout);
         pb.cout = L.cout;
         pb.cout_pad = L.cout_pad;
         if ((rc = launch_pack(pb, stream)) != HIFICAR_OK) return rc;
     }
-    if (D) {
+    if (D && !x3) {
         fill_pack(pp, *D, D->chunk16);
         pp.src = w;
         pp.dst = D->d_w32;
@@ -315,19 +394,31 @@ extern "C" int hificar_xfmr_set_parameters_device(hificar_xfmr* g, const char* c
         for (auto v : g->expected.at(names[i])) numel *= (size_t)v;
         HIP_TRY(hipMemcpyAsync(ts->d_master + ts->offset.at(names[i]), data[i], numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
+    if ((rc = xfmr_repack(g, stream)) != HIFICAR_OK) return rc;
+    ts->have_params = true;
+    return HIFICAR_OK;
+}
+
+// every pack the handle's arithmetics read, from the master copy, on `stream`
+static int xfmr_repack(hificar_xfmr* g, hipStream_t stream) {
+    XfmrTrain* ts = g->train;
+    hificar_engine* h = &g->eng;
+    int rc;
+    const bool x3 = g->train_precision == HIFICAR_PREC_BF16X3;
+    if (x3 && (rc = xfmr_train_alloc16(g, ts)) != HIFICAR_OK) return rc;
     const int F = g->cfg.hidden_dim, d = F / kXfmrHeads;
     float* const m = ts->d_master;
     auto at = [&](const std::string& name) { return m + ts->offset.at(name); };
     for (auto& bn : ts->bns) {
         const ConvLayer& L = *bn.folded;
-        if ((rc = xfmr_pack_dev(bn.raw, &bn.dg, at(bn.conv + ".weight"), at(bn.conv + ".bias"), stream)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_dev(h, bn.raw, &bn.dg, at(bn.conv + ".weight"), at(bn.conv + ".bias"), stream, x3, true)) != HIFICAR_OK) return rc;
         hipLaunchKernelGGL(xfmr_fold_kernel, dim3((unsigned)L.cout), dim3(256), 0, stream, at(bn.conv + ".weight"), at(bn.conv + ".bias"), at(bn.bn + ".weight"),
                            at(bn.bn + ".bias"), at(bn.bn + ".running_mean"), at(bn.bn + ".running_var"), m + bn.off_fw, m + bn.off_fb, L.cin * L.K);
         HIP_TRY(hipGetLastError());
-        if ((rc = xfmr_pack_dev(L, nullptr, m + bn.off_fw, m + bn.off_fb, stream)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_dev(h, L, nullptr, m + bn.off_fw, m + bn.off_fb, stream)) != HIFICAR_OK) return rc;
     }
-    if ((rc = xfmr_pack_dev(g->w_in, &ts->dg_win, at("w_raw_in.weight"), at("w_raw_in.bias"), stream)) != HIFICAR_OK) return rc;
-    if ((rc = xfmr_pack_dev(g->w_out, &ts->dg_wout, at("w_out.weight"), at("w_out.bias"), stream)) != HIFICAR_OK) return rc;
+    if ((rc = xfmr_pack_dev(h, g->w_in, &ts->dg_win, at("w_raw_in.weight"), at("w_raw_in.bias"), stream, x3)) != HIFICAR_OK) return rc;
+    if ((rc = xfmr_pack_dev(h, g->w_out, &ts->dg_wout, at("w_out.weight"), at("w_out.bias"), stream, x3)) != HIFICAR_OK) return rc;
     for (int l = 0; l < g->cfg.elayers; ++l) {
         const std::string b = "transformer.layers." + std::to_string(l) + ".";
         XfmrEncLayer& L = g->enc[(size_t)l];
@@ -336,18 +427,40 @@ extern "C" int hificar_xfmr_set_parameters_device(hificar_xfmr* g, const char* c
                            m + D.off_fused, F, d, 0);
         hipLaunchKernelGGL(transpose_kernel, dim3(1024), dim3(256), 0, stream, at(b + "self_attn.w_o"), m + D.off_wot, F, F);
         HIP_TRY(hipGetLastError());
-        if ((rc = xfmr_pack_dev(L.qkv, &D.dg_qkv, m + D.off_fused, nullptr, stream)) != HIFICAR_OK) return rc;
-        if ((rc = xfmr_pack_dev(L.wo, &D.dg_wo, m + D.off_wot, nullptr, stream)) != HIFICAR_OK) return rc;
-        if ((rc = xfmr_pack_dev(L.l1, &D.dg_l1, at(b + "linear1.weight"), at(b + "linear1.bias"), stream)) != HIFICAR_OK) return rc;
-        if ((rc = xfmr_pack_dev(L.l2, &D.dg_l2, at(b + "linear2.weight"), at(b + "linear2.bias"), stream)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_dev(h, L.qkv, &D.dg_qkv, m + D.off_fused, nullptr, stream, x3)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_dev(h, L.wo, &D.dg_wo, m + D.off_wot, nullptr, stream, x3)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_dev(h, L.l1, &D.dg_l1, at(b + "linear1.weight"), at(b + "linear1.bias"), stream, x3)) != HIFICAR_OK) return rc;
+        if ((rc = xfmr_pack_dev(h, L.l2, &D.dg_l2, at(b + "linear2.weight"), at(b + "linear2.bias"), stream, x3)) != HIFICAR_OK) return rc;
         HIP_TRY(hipMemcpyAsync(L.d_emb, at(b + "self_attn.relative_positional.embeddings"), (size_t)kXfmrHeads * kXfmrTab * d * sizeof(float),
                                hipMemcpyDeviceToDevice, stream));
         int i = 0;
         for (const char* nm : {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"})
             HIP_TRY(hipMemcpyAsync(L.d_ln[i++], at(b + nm), (size_t)F * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
-    ts->have_params = true;
     return HIFICAR_OK;
+}
+
+// The arithmetic of the training step's forward and data-gradient GEMMs; see include/hificar.h.  Before the training state exists it only
+// records the choice.  Afterwards the packs of the new arithmetic are rebuilt from the master copy, behind the handle's last call.
+extern "C" int hificar_xfmr_set_train_precision(hificar_xfmr* g, int precision) {
+    if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_train_precision: null handle");
+    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3) return fail(HIFICAR_E_INVALID, "unknown training precision %d", precision);
+    if (g->precision != HIFICAR_PREC_F32)
+        return fail(HIFICAR_E_STATE, "this Transformer handle is packed for the %s inference arithmetic: it has no training step, in either arithmetic",
+                    xfmr_precision_name(g->precision));
+    if (precision == g->train_precision) return HIFICAR_OK;
+    if (!g->train || !g->train->have_params) {
+        g->train_precision = precision;
+        return HIFICAR_OK;
+    }
+    hificar_engine* h = &g->eng;
+    hipStream_t stream = h->have_last_stream ? h->last_stream : nullptr;
+    int rc = enter_stream(h, stream);
+    if (rc != HIFICAR_OK) return rc;
+    const int before = g->train_precision;
+    g->train_precision = precision;
+    if ((rc = xfmr_repack(g, stream)) != HIFICAR_OK) g->train_precision = before;
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -446,6 +559,7 @@ struct XfmrTrainWs {
     float* partial;  // weight-gradient partials
     float* colsum;   // bias-gradient partials
     char* light;     // a forward without a tape keeps its rows here
+    char* split;     // [rows][3072] split rows (4 bytes per channel): the operand of the next bf16x3 GEMM; null in the fp32 arithmetic
     size_t partial_elems, colsum_elems;
     size_t bytes;
 };
@@ -491,6 +605,8 @@ static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void*
     w.partial = take(w.partial_elems * 4);
     w.colsum = take(w.colsum_elems * 4);
     w.light = reinterpret_cast<char*>(take(xfmr_plan_tape(g, B, T, nullptr, Mp).bytes));
+    // (last: everything in front of it lies where the fp32 arithmetic has it)
+    w.split = g->train_precision == HIFICAR_PREC_BF16X3 ? reinterpret_cast<char*>(take(rows * kXfmrFF * 4)) : nullptr;
     w.bytes = off;
     return w;
 }
@@ -569,7 +685,30 @@ struct XfmrTrainCtx {
         io[0].y = y;
         io[0].ys = reinterpret_cast<char*>(ys);
         const Ragged rg;
-        return seq && !packed() ? launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream) : launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream);
+        if (!x3()) return seq && !packed() ? launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream) : launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream);
+        // bf16x3: the operand as split rows, the layer's bf16 twin in the engine's bf16x3 kernels.  Their activated copy is split rows, so a
+        // ReLU'd fp32 copy (linear1's hidden rows) is the fp32 output ReLU'd in place.
+        if (!L.d_w16 || !ws->split || (y && ys)) return fail(HIFICAR_E_INVALID, "internal: bf16x3 training launch of %s", L.name.c_str());
+        int rc;
+        if ((rc = split_rows(xs, L.cin_pad)) != HIFICAR_OK) return rc;
+        io[0].xs = ws->split;
+        io[0].ys = nullptr;
+        if (ys) io[0].y = ys;
+        h->precision = HIFICAR_PREC_BF16X3;  // (part of the plan key: these launches' plans are their own)
+        rc = seq && !packed() ? launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream) : launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream);
+        h->precision = HIFICAR_PREC_F32;
+        if (rc != HIFICAR_OK || !ys) return rc;
+        return gate(ys, ys, ys, (long long)M * L.cout_pad, -1);
+    }
+    bool x3() const { return g->train_precision == HIFICAR_PREC_BF16X3; }
+    // fp32 rows [M][C] -> the split scratch (rows of padded frames and gap rows: zero bits, not read)
+    int split_rows(const float* x, int C) const {
+        const long long n8 = (long long)M * C / 8;
+        ProfScope prof(h, stream, "xfmr_split_rows_kernel", 0.0, 8.0 * M * C);
+        hipLaunchKernelGGL(xfmr_split_rows_kernel, dim3((unsigned)std::min<long long>((n8 + 255) / 256, 8192)), dim3(256), 0, stream, x, ws->split, n8, C, hdr, lens,
+                           T, lay);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
     }
     int wgrad(const ConvLayer& L, const float* gr, int gpitch, const float* a, int apitch, float* dW, float* db) const {
         return L.K > 1 && !packed() ? launch_wgrad(h, L, gr, gpitch, a, apitch, B, T, dW, bw, stream, db)
@@ -699,6 +838,7 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     XfmrTrain* ts = g->train;
     if (tape) ts->packed_tapes.erase(tape);  // (the packed entry point records it again once everything is enqueued)
+    ts->fwd_precision = g->train_precision;
     const XfmrTrainWs ws = xfmr_plan_train_ws(g, B, T, workspace, Mp);
     const XfmrTape tp = xfmr_plan_tape(g, B, T, tape ? tape : ws.light, Mp);
     const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = Mp ? Mp : B * T;
@@ -863,6 +1003,13 @@ extern "C" int hificar_xfmr_forward_train_packed(hificar_xfmr* g, const float* x
 static int xfmr_backward_impl(hificar_xfmr* g, const float* dout, int B, int T, int Mp, const void* tape, float* grads, float* dx, void* workspace,
                               void* stream_);
 
+// A tape goes back through the arithmetic that filled it: the handle remembers its last training forward's (no device read-back)
+static int xfmr_backward_arith(const hificar_xfmr* g, const char* what) {
+    if (g->train->fwd_precision == g->train_precision) return HIFICAR_OK;
+    return fail(HIFICAR_E_STATE, "%s: the handle's training arithmetic is %s, its last training forward ran in %s (hificar_xfmr_set_train_precision between "
+                                 "a forward and its backward)", what, xfmr_precision_name(g->train_precision), xfmr_precision_name(g->train->fwd_precision));
+}
+
 extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
                                      void* workspace, size_t workspace_bytes, void* stream_) {
     const char* what = "hificar_xfmr_backward";
@@ -871,6 +1018,7 @@ extern "C" int hificar_xfmr_backward(hificar_xfmr* g, const float* dout, int B, 
     int rc = xfmr_train_check(g, what, B, T, const_cast<void*>(tape), tape_bytes, workspace, workspace_bytes);
     if (rc != HIFICAR_OK) return rc;
     if (!dout || !grads) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
+    if ((rc = xfmr_backward_arith(g, what)) != HIFICAR_OK) return rc;
     return xfmr_backward_impl(g, dout, B, T, 0, tape, grads, dx, workspace, stream_);
 }
 
@@ -894,6 +1042,7 @@ extern "C" int hificar_xfmr_backward_packed(hificar_xfmr* g, const float* dout, 
     rc = xfmr_train_check(g, what, B, T, const_cast<void*>(tape), tape_bytes, workspace, workspace_bytes, false, mp);
     if (rc != HIFICAR_OK) return rc;
     if (!dout || !grads) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
+    if ((rc = xfmr_backward_arith(g, what)) != HIFICAR_OK) return rc;
     return xfmr_backward_impl(g, dout, B, T, mp, tape, grads, dx, workspace, stream_);
 }
 
@@ -1023,3 +1172,57 @@ static int xfmr_backward_impl(hificar_xfmr* g, const float* dout, int B, int T, 
     return HIFICAR_OK;
 }
 #undef XT
+
+// Test aid: the bf16 fragments of a Conv1d weight w (cout, cin, K; host floats; input rows cin_pad wide) as the bf16x3 training arithmetic
+// builds them.  mode 0: the layer's own pack; 2: its data gradient's.  how 0: pack16_kernel's index functions run on the host (no device);
+// 1: pack16_kernel itself, over a buffer of 0xFF bytes; 2: pack_w16, the host pack of the inference handles, read back from the device.
+// out: `capacity` bf16 elements; *elems: how many the pack has (the zero tail included).
+extern "C" int hificar_debug_pack16(int cout, int cin, int cin_pad, int K, int mode, int how, const float* w, uint16_t* out, size_t capacity, size_t* elems) {
+    if (!w || !out || !elems || (mode != 0 && mode != 2) || how < 0 || how > 2 || K < 1 || K % 2 != 1) return fail(HIFICAR_E_INVALID, "hificar_debug_pack16: bad argument");
+    ConvLayer P;
+    int rc = mode == 0 ? xfmr_plan(P, "debug", cin, cin_pad, cout, K) : xfmr_plan(P, "debug#dgrad", cout, round_up(cout, 32), cin, K);
+    if (rc != HIFICAR_OK) return rc;
+    const size_t n = xfmr_pack16_bytes(P) / sizeof(uint16_t);
+    *elems = n;
+    if (capacity < n) return fail(HIFICAR_E_INVALID, "hificar_debug_pack16: %zu elements, the buffer has %zu", n, capacity);
+    const size_t wn = (size_t)cout * cin * K;
+    if (how == 0) {
+        memset(out, 0xFF, n * sizeof(uint16_t));
+        const Pack16Params p = xfmr_pack16_params(P, w, out, mode, cin, cout);
+        for (long long i = 0; i < pack16_items(p); ++i) pack16_item(p, i);
+        memset(out + pack16_frags(p) * 512, 0, (size_t)4 * p.nc16 * 512 * sizeof(uint16_t));
+        return HIFICAR_OK;
+    }
+    if (how == 1) {
+        void *dw = nullptr, *dp = nullptr;
+        HIP_TRY(hipMalloc(&dw, wn * sizeof(float)));
+        hipError_t e = hipMalloc(&dp, n * sizeof(uint16_t));
+        if (e == hipSuccess) e = hipMemcpy(dw, w, wn * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(dp, 0xFF, n * sizeof(uint16_t));
+        if (e == hipSuccess) {
+            const Pack16Params p = xfmr_pack16_params(P, static_cast<const float*>(dw), static_cast<uint16_t*>(dp), mode, cin, cout);
+            hipLaunchKernelGGL(pack16_kernel, dim3((unsigned)std::min<long long>((pack16_items(p) + 255) / 256, 2048)), dim3(256), 0, nullptr, p);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpy(out, dp, n * sizeof(uint16_t), hipMemcpyDeviceToHost);
+        (void)hipFree(dw);
+        (void)hipFree(dp);
+        HIP_TRY(e);
+        return HIFICAR_OK;
+    }
+    HostTensor W;
+    W.shape = {P.cout, P.cin, K};
+    W.data.resize(wn);
+    for (int co = 0; co < P.cout; ++co)
+        for (int ci = 0; ci < P.cin; ++ci)
+            for (int t = 0; t < K; ++t)
+                W.data[((size_t)co * P.cin + ci) * K + t] = mode == 0 ? w[((size_t)co * cin + ci) * K + t] : w[((size_t)ci * cin + co) * K + (K - 1 - t)];
+    hificar_engine tmp;
+    uint16_t* d = nullptr;
+    rc = pack_w16(&tmp, P, W, P.chunk16, &d);
+    hipError_t e = rc == HIFICAR_OK ? hipMemcpy(out, d, n * sizeof(uint16_t), hipMemcpyDeviceToHost) : hipSuccess;
+    for (void* p : tmp.allocs) (void)hipFree(p);
+    if (rc != HIFICAR_OK) return rc;
+    HIP_TRY(e);
+    return HIFICAR_OK;
+}

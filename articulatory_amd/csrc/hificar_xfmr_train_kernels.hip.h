@@ -752,3 +752,5 @@ __global__ __launch_bounds__(256) void xfmr_fold_kernel(const float* __restrict_
 }
 
 }  // namespace hificar
+
+#include "hificar_xfmr_pack16.hip.h"  // the bf16x3 training arithmetic's two passes

@@ -28,6 +28,12 @@ in the conv engine's bf16x3 kernels (x w ~ hi hi + hi lo + lo hi on bf16 MFMAs, 
 additions and the residual stream stay fp32.  Inference only: a train()-mode forward of a bf16x3 model is refused.  Unlike
 ``HiFiGANGenerator`` the constructor does not read ``$HIFICAR_PRECISION``: the arithmetic of this model is chosen by keyword only.
 
+``train_precision="bf16x3"`` (opt-in, keyword or ``set_train_precision``; ``"f32"`` is the default and unchanged) is the training step's
+own switch, on a ``precision="f32"`` model: every forward GEMM of ``forward`` / ``forward_padded`` (packed or not) in train() mode and every
+data gradient runs in the bf16x3 kernels, on weight fragments packed on the device after every optimizer step; weight and bias gradients,
+the attention, the norms, dropout (the same masks) and the tape stay fp32, and so does the eval-mode forward.  Not built: bf16x3
+weight-gradient kernels, bf16 MFMAs in the attention.
+
 Not built, refused with ``NotImplementedError``: ``extra_art=True`` and ``num_ph`` (phoneme input).  ``forward(lengths=...)`` in train() mode
 is refused too (ragged training is asked for by name: ``forward_padded``).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size``
 keywords are accepted and unused, as in the reference.
@@ -180,13 +186,20 @@ class _PrecisionKeyword(type):
     ``Transformer.__init__`` keeps the reference's signature, keyword for keyword (drop-in code inspects it).  None: "f32" —
     ``$HIFICAR_PRECISION`` is deliberately not consulted (see the module's docstring); anything but "f32" / "bf16x3": ValueError."""
 
-    def __call__(cls, *args, precision=None, **kwargs):
+    def __call__(cls, *args, precision=None, train_precision=None, **kwargs):
         if precision is None:
             precision = "f32"
         if precision not in _native.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_native.PRECISIONS)}")
+        if train_precision is None:
+            train_precision = "f32"
+        if train_precision not in _native.PRECISIONS:
+            raise ValueError(f"train_precision must be one of {sorted(_native.PRECISIONS)}")
+        if precision != "f32" and train_precision != "f32":
+            raise ValueError("train_precision='bf16x3' needs precision='f32': a precision='bf16x3' model is inference-only")
         self = super().__call__(*args, **kwargs)
         self.precision = precision
+        self.train_precision = train_precision
         return self
 
 
@@ -199,6 +212,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                  num_ph=None, ph_emb_size=8, layer_type='default'):
         super().__init__()
         self.precision = "f32"  # (Transformer(..., precision=...): _PrecisionKeyword)
+        self.train_precision = "f32"  # (Transformer(..., train_precision=...): the same)
         if extra_art:
             raise NotImplementedError("Transformer(extra_art=True) is not built (its kernel-size-2 input conv shortens the sequence by a frame)")
         if num_ph is not None:
@@ -240,9 +254,29 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         bf16x3 for evaluation, at the cost of one trip of its weights through the host (and one more to switch back)."""
         if precision not in _native.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_native.PRECISIONS)}")
+        if precision != "f32" and self.train_precision != "f32":
+            raise ValueError("precision='bf16x3' is inference-only: set_train_precision('f32') first")
         if precision != self.precision:
             self.precision = precision
             self._invalidate()
+
+    def set_train_precision(self, train_precision):
+        """Arithmetic of the following train()-mode forwards and their backward passes: "f32" (the default) or "bf16x3" — every forward GEMM
+        and every data gradient as x w ~ hi hi + hi lo + lo hi on bf16 MFMAs with fp32 accumulation; weight and bias gradients, attention,
+        norms, dropout and the tape stay fp32 (hificar_xfmr_set_train_precision).  The eval-mode forward is exact fp32 either way.  The
+        native handle is kept: its packs are rebuilt on the device.  A backward whose forward ran in the other arithmetic is refused
+        (RuntimeError).  Not with ``precision="bf16x3"`` (ValueError)."""
+        if train_precision not in _native.PRECISIONS:
+            raise ValueError(f"train_precision must be one of {sorted(_native.PRECISIONS)}")
+        if train_precision != "f32" and self.precision != "f32":
+            raise ValueError("train_precision='bf16x3' needs precision='f32': a precision='bf16x3' model is inference-only")
+        if train_precision == self.train_precision:
+            return
+        self.train_precision = train_precision
+        if self.__dict__.get("_handle") is not None:
+            with torch.cuda.device(self._device()):
+                _native.check(self._lib.hificar_xfmr_set_train_precision(self._handle, _native.PRECISIONS[train_precision]),
+                              "hificar_xfmr_set_train_precision")
 
     def _refuse_bf16x3_training(self):
         if self.precision != "f32":
@@ -347,6 +381,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         return state
 
     def __setstate__(self, state):
+        state.setdefault("train_precision", "f32")  # (a pickle from before the keyword)
         super().__setstate__(state)
         from ..utils.optim_hook import watch
 
@@ -414,6 +449,9 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                                   "hificar_xfmr_set_weight")
                 _native.check(lib.hificar_xfmr_set_precision(handle, _native.PRECISIONS[self.precision]), "hificar_xfmr_set_precision")
                 _native.check(lib.hificar_xfmr_finalize(handle), "hificar_xfmr_finalize")
+                if self.precision == "f32":  # (a bf16x3 inference handle has no training arithmetic to choose)
+                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.PRECISIONS[self.train_precision]),
+                                  "hificar_xfmr_set_train_precision")
             except Exception:
                 lib.hificar_xfmr_destroy(handle)
                 raise

@@ -635,8 +635,9 @@ int hificar_bigru_backward(hificar_bigru* h, const float* dout, int B, int T, co
  * (the binding refuses them).
  * Exact fp32 by default.  Opt-in bf16x3 (hificar_xfmr_set_precision, inference only): every GEMM — the ResBlock convs and residual_path,
  * w_raw_in, q | k | v, w_o, linear1, linear2, w_out — runs in the conv engine's bf16x3 kernels (x w ~ hi hi + hi lo + lo hi on bf16 MFMAs, fp32
- * accumulation); the attention, LayerNorm, bias and residual additions and the residual stream stay fp32.  Not built: the attention's products
- * on bf16 MFMAs, bf16x3 training, a device-side bf16 fragment pack.
+ * accumulation); the attention, LayerNorm, bias and residual additions and the residual stream stay fp32.  The training step has the same
+ * opt-in for its forward GEMMs and data gradients (hificar_xfmr_set_train_precision, below).  Not built: the attention's products on bf16
+ * MFMAs, bf16x3 weight-gradient kernels.
  * Errors as everywhere: a negative HIFICAR_E_* code and hificar_last_error().
  * --------------------------------------------------------------------------------------------------------------------------- */
 #define HIFICAR_XFMR_MAX_IN 4096
@@ -668,7 +669,8 @@ int hificar_xfmr_set_weight(hificar_xfmr* h, const char* name, const float* data
 /* The arithmetic of the handle's GEMMs: HIFICAR_PREC_F32 (the default) or HIFICAR_PREC_BF16X3.  Legal between hificar_xfmr_create and
  * hificar_xfmr_finalize only (HIFICAR_E_STATE afterwards): finalize packs the weight fragments of the chosen arithmetic alone and drops the host
  * tensors.  An unknown value: HIFICAR_E_INVALID.  Touches no device.  A bf16x3 handle serves hificar_xfmr_forward; every training entry point
- * and hificar_xfmr_set_parameters_device refuse it with HIFICAR_E_STATE (there is no device-side bf16 fragment pack), and so does the debug
+ * and hificar_xfmr_set_parameters_device refuse it with HIFICAR_E_STATE (bf16x3 training is an f32 handle's
+ * hificar_xfmr_set_train_precision), and so does the debug
  * tap "conv_blocks" with HIFICAR_E_INVALID (those rows exist as split bf16 rows only).  As in exact fp32, split-K is off: a sequence's result
  * does not depend on what it is batched with. */
 int hificar_xfmr_set_precision(hificar_xfmr* h, int precision);
@@ -713,7 +715,31 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * hificar_xfmr_forward_train_ragged takes whole utterances of unequal lengths (this library's definition: the reference never masks), and
  * hificar_xfmr_forward_train_packed computes the same step without GEMM rows for the padding.
  * All of these may be called after hificar_xfmr_finalize; the first one builds the training state.
- * Not built: a smaller tape per frame, bf16x3, extra_art, num_ph, multi-GPU training of this model. ---- */
+ * The forward GEMMs and data gradients have an opt-in bf16x3 arithmetic (hificar_xfmr_set_train_precision, below).
+ * Not built: a smaller tape per frame, bf16x3 weight-gradient kernels, bf16 MFMAs in the attention, extra_art, num_ph, multi-GPU training of this model. ---- */
+
+/* The arithmetic of the training step's GEMMs: HIFICAR_PREC_F32 (the default: the step above, bit for bit) or HIFICAR_PREC_BF16X3.
+ * bf16x3: every forward GEMM of hificar_xfmr_forward_train / _ragged / _packed (the six ResBlock convs and residual_path, w_raw_in,
+ * q | k | v, w_o, linear1, linear2, w_out) and every data gradient of the same layers runs as x w ~ hi hi + hi lo + lo hi on bf16 MFMAs with
+ * fp32 accumulation, in the conv engine's bf16x3 kernels (hi = bf16(x), lo = bf16(x - hi), round to nearest even; split-K off: one
+ * accumulation order whatever the batch).  Weight and bias gradients stay exact fp32 on the tape's fp32 rows; so do the attention forward
+ * and backward, softmax, LayerNorm and BatchNorm, dropout (the same masks), bias and residual additions, and the tape's contents and layout
+ * (hificar_xfmr_tape_bytes* do not change).  hificar_xfmr_forward stays exact fp32.  hificar_xfmr_set_parameters_device then also builds the
+ * bf16 fragments of every forward and data-gradient layer on the device, and the training workspace grows by one buffer of split rows
+ * (3072 columns): ask hificar_xfmr_train_workspace_bytes* after this call.
+ * Legal at any time on an f32 handle, also after hificar_xfmr_finalize and between steps: once parameters have been handed over, the packs of
+ * the new arithmetic are rebuilt from the handle's device copy, in stream order behind the handle's last call.  A handle whose
+ * hificar_xfmr_set_precision is bf16x3 (inference only): HIFICAR_E_STATE.  An unknown value: HIFICAR_E_INVALID.
+ * A tape goes back through the arithmetic that filled it: hificar_xfmr_backward / _packed on a handle whose training arithmetic is not that
+ * of its last training forward return HIFICAR_E_STATE before anything is enqueued (switch back and the tape is as good as before). */
+int hificar_xfmr_set_train_precision(hificar_xfmr* h, int precision);
+
+/* Test aid: the bf16 hi | lo weight fragments ([n_block32][chunk][tap][c16][hi | lo][lane][8] and a zero tail) of a Conv1d weight w (cout,
+ * cin, K odd; HOST floats; input rows cin_pad channels wide) as bf16x3 training builds them.  mode 0: the layer's own pack; 2: its data
+ * gradient's (transposed, taps flipped).  how 0: the device pack's index functions run on the host (no device needed); 1: the device pack
+ * kernel, over a buffer of 0xFF bytes; 2: the host pack of the inference handles, read back from the device.  out: HOST, `capacity` 16-bit
+ * elements; *elems: the pack's size in elements (set even when the buffer is too small: HIFICAR_E_INVALID then). */
+int hificar_debug_pack16(int cout, int cin, int cin_pad, int K, int mode, int how, const float* w, uint16_t* out, size_t capacity, size_t* elems);
 
 /* Every float tensor of the state_dict (reference names and layouts, the batch norms' running_mean / running_var included; n = all of them,
  * each once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs (the

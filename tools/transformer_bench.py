@@ -37,6 +37,15 @@ native packed step (Transformer.forward_padded(packed=True) + masked_l1_loss: no
 (forward_padded + masked_l1_loss) and the native dense step on the same padded batch (every frame counted, as the reference's pad mode
 trains).  Then one profiled step of each: time per kernel, what the skipped attention tiles recover, the packed step's time over the
 ragged step's per kernel family beside Mp / (B T), and the tape bytes of the three forms.
+
+   python tools/transformer_bench.py --train --train-precision bf16x3 [--ragged] [--out profiles/transformer_train_bf16x3.txt]
+
+--train-precision bf16x3 (with --train): one more leg, the same model with train_precision="bf16x3" (forward GEMMs and data gradients in the
+bf16x3 kernels, fragments packed on the device after every optimizer step), alternated native-f32 / native-bf16x3 / stock, two windows
+each, in the same process.  The line then carries bf16x3_ms, f32_over_bf16x3 (fastest f32 window over slowest bf16x3 window),
+bf16x3_faster — the slowest bf16x3 window is below the fastest f32 window by more than the two legs' window spreads added — and the
+bf16x3 step's per-kernel table (one forward + backward + the packs of one parameter hand-over).  With --ragged: the bf16x3 ragged and
+packed legs beside the fp32 ones.
 Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
 import argparse
 import ctypes
@@ -112,6 +121,25 @@ def train_main(a):
     n_opt = torch.optim.Adam(native.parameters(), lr=1e-4, fused=True)
     stock = Stock(sd, dtype=torch.float32, device="cuda", dropout=p)
     s_opt = torch.optim.Adam(list(stock.params.values()), lr=1e-4, fused=True)
+    fast = f_opt = None
+    if a.train_precision == "bf16x3":
+        fast = Transformer(dropout=p, train_precision="bf16x3", **PARAMS)
+        fast.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+        fast = fast.cuda().train()
+        f_opt = torch.optim.Adam(fast.parameters(), lr=1e-4, fused=True)
+
+    def profile_step(m, opt):
+        """{kernel: ms} of one step: the parameter hand-over behind the optimizer step before it, forward and backward."""
+        eng = m.engine()
+        opt.step()
+        _native.check(m._lib.hificar_profile_begin(eng), "hificar_profile_begin")
+        m.zero_grad(set_to_none=True)
+        F.l1_loss(m(x), y).backward()
+        stats = (_native.HificarKernelStat * 128)()
+        n = ctypes.c_int()
+        _native.check(m._lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
+        return {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+
     lines = []
     for shape in a.shapes:
         B, T = (int(v) for v in shape.split("x"))
@@ -128,12 +156,21 @@ def train_main(a):
             F.l1_loss(stock.forward(x)[0], y).backward()
             s_opt.step()
 
+        def fast_step(_):
+            f_opt.zero_grad(set_to_none=True)
+            F.l1_loss(fast(x), y).backward()
+            f_opt.step()
+
         for _ in range(2):
             native_step(None), stock_step(None)
+            if fast is not None:
+                fast_step(None)
         torch.cuda.synchronize()
         n1 = window(native_step, None, a.window)
+        f1 = None if fast is None else window(fast_step, None, a.window)
         s1 = window(stock_step, None, a.window)
         n2 = window(native_step, None, a.window)
+        f2 = None if fast is None else window(fast_step, None, a.window)
         s2 = window(stock_step, None, a.window)
         res = {"train": True, "B": B, "T": T, "dropout": p, "native_ms": [round(n1, 3), round(n2, 3)], "stock_ms": [round(s1, 3), round(s2, 3)],
                "native_spread": round(abs(n1 - n2) / min(n1, n2), 4), "stock_spread": round(abs(s1 - s2) / min(s1, s2), 4),
@@ -153,9 +190,21 @@ def train_main(a):
         flop = 2.0 * 7 * 199 * PARAMS["hidden_dim"] * B * T * PARAMS["elayers"]
         res["attn_bwd_ms"] = round(bwd, 3)
         res["attn_bwd_tflops"] = round(flop / (bwd * 1e-3) / 1e12, 2) if bwd else None
+        if fast is not None:
+            res["bf16x3_ms"] = [round(f1, 3), round(f2, 3)]
+            res["bf16x3_spread"] = round(abs(f1 - f2) / min(f1, f2), 4)
+            res["f32_over_bf16x3"] = round(min(n1, n2) / max(f1, f2), 3)
+            res["stock_over_bf16x3"] = round(min(s1, s2) / max(f1, f2), 3)
+            res["bf16x3_faster"] = bool(min(n1, n2) - max(f1, f2) > abs(n1 - n2) + abs(f1 - f2))
+            pf, pn = profile_step(fast, f_opt), profile_step(native, n_opt)
+            res["bf16x3_kernels_ms"] = {k: round(v, 4) for k, v in sorted(pf.items(), key=lambda kv: -kv[1])}
+            res["f32_kernels_ms"] = {k: round(v, 4) for k, v in sorted(pn.items(), key=lambda kv: -kv[1])}
+            fam = lambda prof, pre: round(sum(v for k, v in prof.items() if k.startswith(pre)), 4)  # noqa: E731
+            res["families_ms"] = {pre: {"f32": fam(pn, pre), "bf16x3": fam(pf, pre)} for pre in ("conv", "wgrad", "wreduce", "xfmr_attn", "xfmr_split_rows", "pack16", "xfmr_")}
         lines.append(json.dumps(res))
         print(lines[-1], flush=True)
     if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
         with open(a.out, "a") as f:
             f.write("\n".join(lines) + "\n")
 
@@ -191,6 +240,22 @@ def ragged_train_main(a):
 
     legs = {"native_packed": make(lambda: masked_l1_loss(m.forward_padded(x, lens32, packed=True), y, lens32)),
             "native_ragged": make(lambda: masked_l1_loss(m.forward_padded(x, lens32), y, lens32)), "native_dense": make(lambda: F.l1_loss(m(x), y))}
+    if a.train_precision == "bf16x3":  # the same batch through a second model in the bf16x3 training arithmetic, padded and packed
+        m3 = Transformer(dropout=p, train_precision="bf16x3", **PARAMS)
+        m3.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+        m3 = m3.cuda().train()
+        opt3 = torch.optim.Adam(m3.parameters(), lr=1e-4, fused=True)
+
+        def make3(loss_fn):
+            def step(_=None):
+                opt3.zero_grad(set_to_none=True)
+                loss_fn().backward()
+                opt3.step()
+
+            return step
+
+        legs["bf16x3_packed"] = make3(lambda: masked_l1_loss(m3.forward_padded(x, lens32, packed=True), y, lens32))
+        legs["bf16x3_ragged"] = make3(lambda: masked_l1_loss(m3.forward_padded(x, lens32), y, lens32))
     for _ in range(2):
         for fn in legs.values():
             fn()
@@ -213,6 +278,11 @@ def ragged_train_main(a):
     res["dense_over_ragged"] = round(min(ms["native_dense"]) / max(ms["native_ragged"]), 3)  # slowest ragged, fastest dense
     res["ragged_over_packed"] = round(min(ms["native_ragged"]) / max(ms["native_packed"]), 3)  # slowest packed, fastest ragged
     res["packed_windows_below_ragged"] = max(ms["native_packed"]) < min(ms["native_ragged"])
+    for form in ("packed", "ragged"):
+        if "bf16x3_" + form in ms:
+            n_, f_ = ms["native_" + form], ms["bf16x3_" + form]
+            res[f"f32_over_bf16x3_{form}"] = round(min(n_) / max(f_), 3)
+            res[f"bf16x3_faster_{form}"] = bool(min(n_) - max(f_) > abs(n_[0] - n_[1]) + abs(f_[0] - f_[1]))
     eng = m.engine()
     profs = {}
     for tag in ("packed", "ragged", "dense"):
@@ -224,6 +294,17 @@ def ragged_train_main(a):
         profs[tag] = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
         res[tag + "_kernels_ms"] = {k: round(v, 4) for k, v in sorted(profs[tag].items(), key=lambda kv: -kv[1])}
         res[tag + "_kernels_total_ms"] = round(sum(profs[tag].values()), 3)
+    if a.train_precision == "bf16x3":
+        eng3 = m3.engine()
+        for tag in ("packed", "ragged"):
+            _native.check(lib.hificar_profile_begin(eng3), "hificar_profile_begin")
+            legs["bf16x3_" + tag]()
+            stats = (_native.HificarKernelStat * 128)()
+            n = ctypes.c_int()
+            _native.check(lib.hificar_profile_end(eng3, stats, 128, ctypes.byref(n)), "hificar_profile_end")
+            prof3 = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+            res[f"bf16x3_{tag}_kernels_ms"] = {k: round(v, 4) for k, v in sorted(prof3.items(), key=lambda kv: -kv[1])}
+            res[f"bf16x3_{tag}_kernels_total_ms"] = round(sum(prof3.values()), 3)
     res["attention_recovered_ms"] = {k: round(profs["dense"].get(k, 0.0) - profs["ragged"].get(k, 0.0), 4)
                                      for k in ("xfmr_attn_kernel<train>", "xfmr_attn_bwd_kernels")}
     # packed over ragged per kernel family, to read beside packed_rows_over_padded_rows: conv_* are the forward GEMMs and the data gradients
@@ -248,6 +329,7 @@ def main():
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--no-stock", action="store_true")
     ap.add_argument("--precision", choices=("f32", "bf16x3"), default="f32", help="bf16x3: add the bf16x3 leg to the native / stock alternation")
+    ap.add_argument("--train-precision", choices=("f32", "bf16x3"), default="f32", help="--train: bf16x3 adds the bf16x3 training leg(s)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--ragged", action="store_true", help="--train: the ragged batch's two legs instead of the dense shapes")
     ap.add_argument("--seed", type=int, default=0, help="--train --ragged: seed of the lengths")
