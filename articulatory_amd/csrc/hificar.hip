@@ -240,7 +240,9 @@ struct hificar_handle : hificar_engine {
 
 // The library's environment switches — all of them.  engine_open reads the engine's own, once per engine: the generators' (in hificar_finalize),
 // the discriminators' and the BiGRU's; the mel / STFT loss engine runs with the defaults.
-//   HIFICAR_PROFILE_DETAIL=1   rows of hificar_profile_end carry the layer name ("kernel|layer xN")
+//   HIFICAR_PROFILE_DETAIL=1   rows of hificar_profile_end carry the layer name ("kernel|layer xN"); weight-gradient rows the instantiation launched,
+//                              the layer's shape, split count, row split and layers per launch ("wgrad_taps_kernel<7,0,128> 48x48k5p1 s3 r1 n2"),
+//                              reduction rows which reduction ran ("wreduce_kernel ..", "wreduce_gemm_kernel<5> ..", "reduce_multi_kernel w9 b8")
 //   HIFICAR_LAUNCH_LOG=<path>  every kernel launch of the library is appended to <path> in enqueue order as "kernel|layer<TAB>flops<TAB>algorithmic bytes":
 //                              joined with rocprofv3's per-dispatch rows by tools/pmc_by_layer.py (implies PROFILE_DETAIL)
 //   HIFICAR_KSPLIT=0|1|2       split-K conv form: never / when estimated faster (default) / always.  0 makes every launch shape use one accumulation

@@ -138,7 +138,6 @@ static int wgrad_setup() {
     HIFICAR_WGT_LDS(3, true);
     HIFICAR_WGT_LDS(7, true);
     HIFICAR_WGT_LDS(11, true);
-    HIFICAR_WGT_LDS(3, false);
     HIFICAR_WGT_LDS(7, false);
     HIFICAR_WGT_LDS(11, false);
 #undef HIFICAR_WGT_LDS
@@ -735,7 +734,9 @@ static int flush_reduce(hificar_engine* h, DeferredReduce& dr, hipStream_t strea
     t.nw = (int)nw;
     t.nb = (int)nb;
     {
-        ProfScope prof(h, stream, "reduce_multi_kernel", 0.0, dr.rbytes);
+        std::string rname = "reduce_multi_kernel";  // with profile_detail: how many weight (w) and bias (b) reductions the launch runs
+        if (h->profile_detail) rname += " w" + std::to_string(t.nw) + " b" + std::to_string(t.nb);
+        ProfScope prof(h, stream, rname, 0.0, dr.rbytes);
         hipLaunchKernelGGL(reduce_multi_kernel, dim3((unsigned)(wgs + bwgs)), dim3(256), 0, stream, t);
     }
     HIP_TRY(hipGetLastError());
@@ -957,7 +958,10 @@ struct WgradJob {
 // Weight (and bias) gradients of n = 1 or 2 layers over the same rows.  Two layers share one launch of each kernel when both take the
 // all-taps kernel with the same tap count (conv2 + conv1 of a ResBlock slot): half the row splits each.
 static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int nseq, int rows, const BwdWs& bw, hipStream_t stream) {
-    if (n == 2 && !(wgrad_all_taps(*jobs[0].L) && wgrad_all_taps(*jobs[1].L) && jobs[0].L->ntaps == jobs[1].L->ntaps)) {
+    // (... and the same chunk rows: a dilated conv1 whose halo exceeds 32 rows takes 64-row chunks where its conv2 takes 128, kernel 7 at
+    // dilation 6 for one; one launch has one chunk size, so such a slot runs as two launches)
+    if (n == 2 && !(wgrad_all_taps(*jobs[0].L) && wgrad_all_taps(*jobs[1].L) && jobs[0].L->ntaps == jobs[1].L->ntaps &&
+                    wgrad_chunk_rows(*jobs[0].L, rows) == wgrad_chunk_rows(*jobs[1].L, rows))) {
         int rc = launch_wgrad_n(h, jobs, 1, nseq, rows, bw, stream);
         return rc != HIFICAR_OK ? rc : launch_wgrad_n(h, jobs + 1, 1, nseq, rows, bw, stream);
     }
@@ -1092,23 +1096,43 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
     }
     {
         const ConvLayer& L = *jobs[0].L;
-        std::string kname = gemm ? "wgrad_gemm_kernel" : taps ? "wgrad_taps_kernel" : "wgrad_kernel";
-        if (h->profile_detail)
-            kname += " " + std::to_string(L.cout) + "x" + std::to_string(L.cin) + "k" + std::to_string(L.K) + "p" + std::to_string(L.n_phase) +
-                     " s" + std::to_string(nsplit) + " r" + std::to_string(tp.q[0].w.row_split) + " n" + std::to_string(n);
-        ProfScope prof(h, stream, kname, flops, bytes);
+        // the profile row: the kernel's name; with profile_detail the template arguments of the instantiation launched (written by the
+        // macro that launches it, from the same arguments), the layer's shape and the launch's split / row split / layer count
+        auto kname = [&](const char* kernel, std::initializer_list<int> targs) {
+            std::string s = kernel;
+            if (!h->profile_detail) return s;
+            const char* sep = "<";
+            for (int v : targs) {
+                s += sep + std::to_string(v);
+                sep = ",";
+            }
+            if (targs.size()) s += ">";
+            return s + " " + std::to_string(L.cout) + "x" + std::to_string(L.cin) + "k" + std::to_string(L.K) + "p" + std::to_string(L.n_phase) +
+                   " s" + std::to_string(nsplit) + " r" + std::to_string(tp.q[0].w.row_split) + " n" + std::to_string(n);
+        };
         if (gemm) {
-            if (wgrad_gemm_wide(L)) hipLaunchKernelGGL((wgrad_gemm_kernel<4, 32>), dim3(tiles, nsplit, zg), dim3(256), 2 * 32 * 384 * sizeof(float) + 2048, stream, tp);
-            else hipLaunchKernelGGL((wgrad_gemm_kernel<2, 64>), dim3(tiles, nsplit, zg), dim3(256), 4 * kWggR * 128 * sizeof(float) + 1024, stream, tp);
+#define HIFICAR_WGG(MI, R, LDS)                                                                                            \
+    do {                                                                                                                   \
+        ProfScope prof(h, stream, kname("wgrad_gemm_kernel", {MI, R}), flops, bytes);                                      \
+        hipLaunchKernelGGL((wgrad_gemm_kernel<MI, R>), dim3(tiles, nsplit, zg), dim3(256), LDS, stream, tp);               \
+    } while (0)
+            if (wgrad_gemm_wide(L)) HIFICAR_WGG(4, 32, 2 * 32 * 384 * sizeof(float) + 2048);
+            else HIFICAR_WGG(2, 64, 4 * kWggR * 128 * sizeof(float) + 1024);
+#undef HIFICAR_WGG
         } else if (taps) {
             const dim3 grid(tiles, nsplit, n * zg);
             const int cr = wgrad_chunk_rows(L, rows);
             if (n == 2 && wgrad_chunk_rows(*jobs[1].L, rows) != cr) return fail(HIFICAR_E_INVALID, "internal: paired weight gradients with unlike chunks");
+#define HIFICAR_WGT1(NT, EX, R)                                                                                    \
+    do {                                                                                                           \
+        ProfScope prof(h, stream, kname("wgrad_taps_kernel", {NT, EX, R}), flops, bytes);                          \
+        hipLaunchKernelGGL((wgrad_taps_kernel<NT, EX, R>), grid, dim3(256), lds, stream, tp);                      \
+    } while (0)
 #define HIFICAR_WGT(NT, EX)                                                                                        \
     do {                                                                                                           \
-        if (cr == 32) hipLaunchKernelGGL((wgrad_taps_kernel<NT, EX, 32>), grid, dim3(256), lds, stream, tp);       \
-        else if (cr == 128) hipLaunchKernelGGL((wgrad_taps_kernel<(NT <= 7 ? NT : 7), EX, 128>), grid, dim3(256), lds, stream, tp); \
-        else hipLaunchKernelGGL((wgrad_taps_kernel<NT, EX, 64>), grid, dim3(256), lds, stream, tp);                \
+        if (cr == 32) HIFICAR_WGT1(NT, EX, 32);                                                                    \
+        else if (cr == 128) HIFICAR_WGT1((NT <= 7 ? NT : 7), EX, 128);                                             \
+        else HIFICAR_WGT1(NT, EX, 64);                                                                             \
     } while (0)
             switch (L.ntaps) {
                 case 1: HIFICAR_WGT(1, true); break;
@@ -1117,13 +1141,14 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
                 case 7: HIFICAR_WGT(7, true); break;
                 case 11: HIFICAR_WGT(11, true); break;
                 default:
-                    if (L.ntaps < 3) HIFICAR_WGT(3, false);
-                    else if (L.ntaps < 7) HIFICAR_WGT(7, false);
+                    if (L.ntaps < 7) HIFICAR_WGT(7, false);
                     else HIFICAR_WGT(11, false);
             }
 #undef HIFICAR_WGT
+#undef HIFICAR_WGT1
         } else {
             if (zg != 1) return fail(HIFICAR_E_INVALID, "internal: grouped weight gradients need the all-taps kernel");
+            ProfScope prof(h, stream, kname("wgrad_kernel", {}), flops, bytes);
             hipLaunchKernelGGL(wgrad_kernel, dim3(tiles, nsplit), dim3(256), 0, stream, tp.q[0].w);
         }
     }
@@ -1153,15 +1178,17 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
         return HIFICAR_OK;
     }
     {
+        const int gemm_k = r0.K == 5 ? 5 : 3;  // the contiguous kernel's instantiation
         std::string rname = "wreduce_kernel";
         if (h->profile_detail) {
             const ConvLayer& L = *jobs[0].L;
+            if (contiguous) rname = "wreduce_gemm_kernel<" + std::to_string(gemm_k) + ">";
             rname += " " + std::to_string(L.cout) + "x" + std::to_string(L.cin) + "k" + std::to_string(L.K) + " s" + std::to_string(nsplit) + " n" + std::to_string(n) + " z" + std::to_string(zg);
         }
         ProfScope prof(h, stream, rname, 0.0, rbytes);
         if (contiguous) {
             const dim3 grid((unsigned)std::min<long long>((gemm_units + 255) / 256, 4096), zg);
-            if (r0.K == 5) hipLaunchKernelGGL(wreduce_gemm_kernel<5>, grid, dim3(256), 0, stream, rp);
+            if (gemm_k == 5) hipLaunchKernelGGL(wreduce_gemm_kernel<5>, grid, dim3(256), 0, stream, rp);
             else hipLaunchKernelGGL(wreduce_gemm_kernel<3>, grid, dim3(256), 0, stream, rp);
         } else {
             hipLaunchKernelGGL(wreduce_kernel, dim3((unsigned)red_wgs, n * zg), dim3(256), 0, stream, rp);

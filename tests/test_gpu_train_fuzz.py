@@ -1,7 +1,8 @@
 """Seeded random-configuration fuzz of the generator's BACKWARD pass (``pytest -m gpu``): widths 24 .. 256,
 strides 2 .. 8, kernel sizes 3 .. 11, dilations up to 5, 1 .. 3 ResBlocks of unequal depth, with / without weight norm, ResBlock bias,
 AR branch — every element of every parameter / input gradient against the CPU oracle's autograd.  The backward has its own kernels per
-tap count (wgrad_taps_kernel<1,2,3,7,11>, wgrad_gemm_kernel) and split-K forms; this walks them.  HIFICAR_FUZZ_CASES raises the count.
+tap count (wgrad_taps_kernel<1,2,3,7,11>, wgrad_gemm_kernel) and split-K forms; the drawn configurations run whichever of them their
+shapes select (tests/test_gpu_wgrad_forms.py reaches every one of them by name).  HIFICAR_FUZZ_CASES raises the count.
 
 LeakyReLU makes gradients discontinuous where a pre-activation is within rounding distance of zero, and ONE activation
 that falls on the other side moves a whole output channel's weight gradient of a short sequence by percents (tests/dev/grad_fuzz_probe.py:

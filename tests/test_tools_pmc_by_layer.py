@@ -56,3 +56,30 @@ def test_join_by_dispatch_order_and_groups(tmp_path):
     assert g["period discriminators (convs, im2col / col2im)"]["launches"] == 2
     assert g["conv_f32do_kernel @ period discriminators (convs, im2col / col2im)"]["traffic_over_algorithmic"] == 9.0
     assert g["other (reductions, packs, losses, element-wise)"]["launches"] == 3  # front_kernel + the two packs
+
+
+def test_weight_gradient_detail_labels_join_by_family(tmp_path):
+    """With HIFICAR_PROFILE_DETAIL the weight-gradient label carries the instantiation ("wgrad_taps_kernel<7,0,128> shape sS rR nN") and the
+    deferred reduction its counts ("reduce_multi_kernel wN bM"): both still join with rocprofv3's names by family, the rest of the label is the layer."""
+    disp = [("void hificar::front_kernel(hificar::FrontParams)", 10.0, 100),
+            ("void hificar::wgrad_taps_kernel<7, false, 128>(hificar::WgradTapsPair)", 200.0, 400),
+            ("void hificar::wgrad_gemm_kernel<4, 32>(hificar::WgradTapsPair)", 400.0, 800),
+            ("void hificar::wgrad_kernel(hificar::WgradParams)", 100.0, 200),
+            ("void hificar::reduce_multi_kernel(hificar::ReduceTable)", 20.0, 50)]
+    log = ["front_kernel\t0\t1000", "wgrad_taps_kernel<7,0,128> 48x48k5p1 s3 r1 n2\t1e9\t204800", "wgrad_gemm_kernel<4,32> 256x256k1p1 s6 r1 n1\t2e9\t409600",
+           "wgrad_kernel 48x48k13p1 s6 r1 n1\t1e9\t102400", "reduce_multi_kernel w3 b3\t0\t20480"]
+    for name, ctr in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
+        _write_pass(str(tmp_path / name), ctr, disp)
+        (tmp_path / f"{name}.log").write_text("\n".join(log) + "\n")
+    out, gj = tmp_path / "t.csv", tmp_path / "g.json"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "pmc_by_layer.py"), "--fetch", str(tmp_path / "fetch"), "--fetch-log", str(tmp_path / "fetch.log"),
+                        "--write", str(tmp_path / "write"), "--write-log", str(tmp_path / "write.log"), "--out", str(out), "--groups-json", str(gj)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert "5 launches joined, 0 unlogged dispatches {}, 0 log entries without a dispatch" in r.stderr
+    rows = {(x["Kernel"], x["Layer"]): x for x in csv.DictReader(ln for ln in open(out) if not ln.startswith("#"))}
+    assert ("wgrad_taps_kernel<7,false,128>", "48x48k5p1 s3 r1 n2") in rows and ("wgrad_gemm_kernel<4,32>", "256x256k1p1 s6 r1 n1") in rows
+    assert ("wgrad_kernel", "48x48k13p1 s6 r1 n1") in rows and ("reduce_multi_kernel", "w3 b3") in rows
+    g = json.load(open(gj))
+    assert g["weight gradients"]["launches"] == 3 and g["wgrad_taps_kernel @ weight gradients"]["launches"] == 1
+    assert g["other (reductions, packs, losses, element-wise)"]["launches"] == 2  # front_kernel and the reduction
