@@ -86,7 +86,8 @@ static int disc_join(hificar_disc* d, hipStream_t main) {
     return HIFICAR_OK;
 }
 
-static int disc_out_len(int L, int k, int stride, int pad) { return (L + 2 * pad - k) / stride + 1; }
+// (an input shorter than the kernel has no output position: 0, not the 1 that C's division towards zero would make of it)
+static int disc_out_len(int L, int k, int stride, int pad) { return L + 2 * pad < k ? 0 : (L + 2 * pad - k) / stride + 1; }
 
 struct DiscGeom {
     int nseq = 0;
@@ -582,6 +583,10 @@ extern "C" int hificar_disc_forward(hificar_disc* d, const float* x, int B, int 
         if (s.period > 0 && (s.period - T % s.period) % s.period >= T)
             return fail(HIFICAR_E_INVALID, "reflect padding needs T > the pad (period %d, T %d)", s.period, T);
     const DiscPlan p = disc_plan(d, B, T);
+    // (checked before anything is enqueued, the pool chain included, and before the fork: an error return must not leave the side streams forked)
+    for (size_t si = 0; si < d->subs.size(); ++si)
+        for (size_t l = 0; l < d->subs[si].layers.size(); ++l)
+            if (p.tape[si][l].M < 1) return fail(HIFICAR_E_INVALID, "discriminator: T=%d is too short for %s", T, d->subs[si].layers[l].base.c_str());
     if (tape_bytes < p.tape_floats * sizeof(float)) return fail(HIFICAR_E_WORKSPACE, "discriminator tape too small: %zu < %zu", tape_bytes, p.tape_floats * sizeof(float));
     if (reinterpret_cast<uintptr_t>(tape_) % 256) return fail(HIFICAR_E_INVALID, "discriminator tape must be 256-byte aligned");
     hificar_engine* h = &d->eng;
@@ -613,9 +618,6 @@ extern "C" int hificar_disc_forward(hificar_disc* d, const float* x, int B, int 
         hipLaunchKernelGGL(avgpool_kernel, dim3(ew_blocks(h, pp.total)), dim3(256), 0, stream, pp);
         HIP_TRY(hipGetLastError());
     }
-    for (size_t si = 0; si < d->subs.size(); ++si)  // (checked before the fork: an error return must not leave the side streams forked)
-        for (size_t l = 0; l < d->subs[si].layers.size(); ++l)
-            if (p.tape[si][l].M < 1) return fail(HIFICAR_E_INVALID, "discriminator: T=%d is too short for %s", T, d->subs[si].layers[l].base.c_str());
     if ((rc = disc_fork(d, main_stream)) != HIFICAR_OK) return rc;
     // (the forked region runs inside a lambda so that EVERY error return below still joins the side streams: the caller's stream must never be
     // left waiting on — or racing with — work that was enqueued on them before the failure)
@@ -665,10 +667,12 @@ extern "C" int hificar_disc_forward(hificar_disc* d, const float* x, int B, int 
                     ip.prev_np = P.Np;
                     ip.prev_gstride = (long long)p.tape[si][l - 1].y_stride;
                 }
-                ProfScope prof(h, stream, h->profile_detail ? "im2col_kernel|" + L.base : std::string("im2col_kernel"), 0.0, 8.0 * tb.M * L.Kg_pad * L.groups);
                 const bool vec4 = d->col2im_vec4 && ip.src_mode == 2 && ip.cin_g % 4 == 0 && ip.prev_cout_g % 4 == 0 && ip.prev_np % 4 == 0 &&
                                   ip.prev_gstride % 4 == 0 && ip.dst_gstride % 4 == 0 && ip.per_group4 < (1LL << 31) && L.groups <= 65535 &&
                                   (reinterpret_cast<uintptr_t>(ip.src) | reinterpret_cast<uintptr_t>(ip.dst)) % 16 == 0;
+                // (with profile_detail the row says which gather ran: " v4" the 4-wide kernel, " v1" the scalar one — the conv rows' " xN" convention)
+                ProfScope prof(h, stream, h->profile_detail ? "im2col_kernel|" + L.base + (vec4 ? " v4" : " v1") : std::string("im2col_kernel"), 0.0,
+                               8.0 * tb.M * L.Kg_pad * L.groups);
                 if (vec4) hipLaunchKernelGGL(im2col4_kernel, dim3(ew_blocks(h, ip.per_group4), (unsigned)L.groups), dim3(256), 0, stream, ip);
                 else hipLaunchKernelGGL(im2col_kernel, dim3(ew_blocks(h, ip.total4)), dim3(256), 0, stream, ip);
                 HIP_TRY(hipGetLastError());
@@ -798,11 +802,12 @@ extern "C" int hificar_disc_backward(hificar_disc* d, const float* const* douts,
                     cp.win_pitch = N.cin_g;
                     cp.win_off = N.pad;
                 }
-                ProfScope prof(h, stream, h->profile_detail ? "col2im_mask_kernel|" + L.base : std::string("col2im_mask_kernel"), 0.0, 12.0 * cp.total);
                 bool vec4 = d->col2im_vec4 && cp.np % 4 == 0 && cp.cout_g_prev % 4 == 0 && cp.cin_g % 4 == 0 && cp.Kg_pad % 4 == 0 && cp.y_gstride % 4 == 0 &&
                             cp.da_gstride % 4 == 0 && (!cp.win || cp.win_pitch % 4 == 0) && cp.per_group < (1LL << 31) &&
                             (reinterpret_cast<uintptr_t>(cp.dA) | reinterpret_cast<uintptr_t>(cp.y) | reinterpret_cast<uintptr_t>(cp.dz)) % 16 == 0;
                 for (int gi = 0; gi < L.groups; ++gi) vec4 = vec4 && reinterpret_cast<uintptr_t>(cp.dy[gi]) % 16 == 0;
+                ProfScope prof(h, stream, h->profile_detail ? "col2im_mask_kernel|" + L.base + (vec4 ? " v4" : " v1") : std::string("col2im_mask_kernel"), 0.0,
+                               12.0 * cp.total);
                 if (vec4) hipLaunchKernelGGL(col2im_mask4_kernel, dim3(ew_blocks(h, cp.per_group / 4), (unsigned)L.groups), dim3(256), 0, stream, cp);
                 else hipLaunchKernelGGL(col2im_mask_kernel, dim3(ew_blocks(h, cp.total)), dim3(256), 0, stream, cp);
                 HIP_TRY(hipGetLastError());

@@ -83,3 +83,31 @@ def test_weight_gradient_detail_labels_join_by_family(tmp_path):
     g = json.load(open(gj))
     assert g["weight gradients"]["launches"] == 3 and g["wgrad_taps_kernel @ weight gradients"]["launches"] == 1
     assert g["other (reductions, packs, losses, element-wise)"]["launches"] == 2  # front_kernel and the reduction
+
+
+def test_gather_width_suffix_joins_by_family(tmp_path):
+    """With HIFICAR_PROFILE_DETAIL the discriminators' gather labels say which kernel ran ("im2col_kernel|layer v4", "col2im_mask_kernel|layer v1"):
+    they still join with rocprofv3's names by family (the 4-wide kernels under their scalar siblings'), and the layer keeps its engine."""
+    disp = [("void hificar::front_kernel(hificar::FrontParams)", 10.0, 100),
+            ("void hificar::im2col4_kernel(hificar::Im2colParams)", 50.0, 100),
+            ("void hificar::im2col_kernel(hificar::Im2colParams)", 60.0, 120),
+            ("void hificar::col2im_mask4_kernel(hificar::Col2imParams)", 70.0, 140),
+            ("void hificar::col2im_mask_kernel(hificar::Col2imParams)", 80.0, 160)]
+    log = ["front_kernel\t0\t1000", "im2col_kernel|msd.discriminators.0.layers.1.0 v4\t0\t51200", "im2col_kernel|mpd.discriminators.1.convs.1.0 v1\t0\t51200",
+           "col2im_mask_kernel|msd.discriminators.0.layers.0.0 v4\t0\t51200", "col2im_mask_kernel|mpd.discriminators.1.convs.0.0 v1\t0\t51200"]
+    for name, ctr in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
+        _write_pass(str(tmp_path / name), ctr, disp)
+        (tmp_path / f"{name}.log").write_text("\n".join(log) + "\n")
+    out, gj = tmp_path / "t.csv", tmp_path / "g.json"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "pmc_by_layer.py"), "--fetch", str(tmp_path / "fetch"), "--fetch-log", str(tmp_path / "fetch.log"),
+                        "--write", str(tmp_path / "write"), "--write-log", str(tmp_path / "write.log"), "--out", str(out), "--groups-json", str(gj)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert "5 launches joined, 0 unlogged dispatches {}, 0 log entries without a dispatch" in r.stderr
+    rows = {(x["Kernel"], x["Layer"]): x for x in csv.DictReader(ln for ln in open(out) if not ln.startswith("#"))}
+    assert ("im2col4_kernel", "msd.discriminators.0.layers.1.0 v4") in rows and ("im2col_kernel", "mpd.discriminators.1.convs.1.0 v1") in rows
+    assert ("col2im_mask4_kernel", "msd.discriminators.0.layers.0.0 v4") in rows and ("col2im_mask_kernel", "mpd.discriminators.1.convs.0.0 v1") in rows
+    g = json.load(open(gj))
+    assert g["scale discriminators (convs, im2col / col2im)"]["launches"] == 2 and g["period discriminators (convs, im2col / col2im)"]["launches"] == 2
+    assert g["im2col_kernel @ scale discriminators (convs, im2col / col2im)"]["launches"] == 1
+    assert g["col2im_mask_kernel @ period discriminators (convs, im2col / col2im)"]["launches"] == 1
