@@ -18,7 +18,10 @@ MAX_DILATIONS = 4
 
 PREC_F32 = 0
 PREC_BF16X3 = 1
-PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}
+PREC_BF16X3W = 2
+PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}  # the inference arithmetics (``precision=``)
+# ... and the Transformer's training arithmetics (``train_precision=``): bf16x3w = bf16x3 with the one-tap weight gradients in it too
+TRAIN_PRECISIONS = dict(PRECISIONS, bf16x3w=PREC_BF16X3W)
 
 # every symbol include/hificar.h declares (tests/test_cabi.py checks the .so exports each one)
 SYMBOLS = (
@@ -121,6 +124,7 @@ SYMBOLS = (
     "hificar_xfmr_destroy",
     "hificar_xfmr_set_train_precision",
     "hificar_debug_pack16",
+    "hificar_debug_split_rows_t",
     "hificar_xfmr_set_parameters_device",
     "hificar_xfmr_grad_count",
     "hificar_xfmr_grad_info",
@@ -519,6 +523,8 @@ def load_library():
     lib.hificar_xfmr_set_train_precision.restype = ci
     lib.hificar_debug_pack16.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, cs, ctypes.POINTER(cs)]
     lib.hificar_debug_pack16.restype = ci
+    lib.hificar_debug_split_rows_t.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, cs, ctypes.POINTER(cs)]
+    lib.hificar_debug_split_rows_t.restype = ci
     lib.hificar_xfmr_workspace_bytes.argtypes = [vp, ci, ci]
     lib.hificar_xfmr_workspace_bytes.restype = cs
     lib.hificar_xfmr_forward.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]

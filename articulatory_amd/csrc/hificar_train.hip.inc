@@ -133,6 +133,8 @@ static int wgrad_setup() {
     HIFICAR_WGT_LDS1((NT <= 7 ? NT : 7), EX, 128)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_gemm_kernel<2, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_gemm_kernel<4, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16x3_kernel<2, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_bf16x3_lds<2, 64>()));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16x3_kernel<4, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_bf16x3_lds<4, 32>()));
     HIFICAR_WGT_LDS(1, true);
     HIFICAR_WGT_LDS(2, true);
     HIFICAR_WGT_LDS(3, true);
@@ -953,6 +955,9 @@ struct WgradJob {
     int acols = 0;
     int a_rows = 0;             // A rows per sequence when they differ from `rows` (WgradTapsParams::a_rows)
     int poly_s = 0, poly_cin = 0, poly_k = 0;  // polyphase-input form of a strided conv: dW in the conv's (cout, poly_cin, poly_k) layout
+    // both non-null (a wgrad_gemm_form layer, one sequence, one group): g and a as xfmr_split_rows_t_kernel wrote them, gpitch and apitch
+    // channels wide; the launch is wgrad_bf16x3_kernel (the Transformer's bf16x3w training arithmetic) and g / a are not read
+    const char *g16 = nullptr, *a16 = nullptr;
 };
 
 // Weight (and bias) gradients of n = 1 or 2 layers over the same rows.  Two layers share one launch of each kernel when both take the
@@ -1110,7 +1115,19 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
             return s + " " + std::to_string(L.cout) + "x" + std::to_string(L.cin) + "k" + std::to_string(L.K) + "p" + std::to_string(L.n_phase) +
                    " s" + std::to_string(nsplit) + " r" + std::to_string(tp.q[0].w.row_split) + " n" + std::to_string(n);
         };
-        if (gemm) {
+        if (gemm && jobs[0].g16) {
+            if (!jobs[0].a16 || nseq != 1 || zg != 1) return fail(HIFICAR_E_INVALID, "internal: bf16x3 weight gradient of %s", L.name.c_str());
+            const WgradParams& w = tp.q[0].w;
+            const WgradX3Params xp = {jobs[0].g16, jobs[0].a16, (rows + 7) / 8, w.gpitch, w.apitch, w.n_gblk, w.n_ablk, w.nsplit, w.partial, w.bias_partial, h->d_zeros};
+#define HIFICAR_WGX(MI, R)                                                                                                              \
+    do {                                                                                                                                \
+        ProfScope prof(h, stream, kname("wgrad_bf16x3_kernel", {MI, R}), flops, bytes);                                                 \
+        hipLaunchKernelGGL((wgrad_bf16x3_kernel<MI, R>), dim3(tiles, nsplit), dim3(256), (wgrad_bf16x3_lds<MI, R>()), stream, xp);      \
+    } while (0)
+            if (wgrad_gemm_wide(L)) HIFICAR_WGX(4, 32);
+            else HIFICAR_WGX(2, 64);
+#undef HIFICAR_WGX
+        } else if (gemm) {
 #define HIFICAR_WGG(MI, R, LDS)                                                                                            \
     do {                                                                                                                   \
         ProfScope prof(h, stream, kname("wgrad_gemm_kernel", {MI, R}), flops, bytes);                                      \

@@ -175,7 +175,7 @@ static int xfmr_pack(hificar_engine* h, ConvLayer& L, const HostTensor& W, const
     return pack_w32(h, L, W, L.chunk16, &L.d_w32);
 }
 
-static const char* xfmr_precision_name(int p) { return p == HIFICAR_PREC_BF16X3 ? "bf16x3" : "f32"; }
+static const char* xfmr_precision_name(int p) { return p == HIFICAR_PREC_BF16X3W ? "bf16x3w" : p == HIFICAR_PREC_BF16X3 ? "bf16x3" : "f32"; }
 
 extern "C" int hificar_xfmr_set_precision(hificar_xfmr* g, int precision) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_precision: null handle");

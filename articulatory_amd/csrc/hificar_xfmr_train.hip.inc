@@ -20,6 +20,10 @@
 // xfmr_split_rows_kernel writes from the fp32 operand into one scratch buffer.  The engine is told by its precision field, set around
 // the launch alone: the precision is part of the plan key, so these launches have plans of their own and every fp32 launch plans and
 // runs as before.  Weight and bias gradients (XfmrTrainCtx::wgrad), the attention, the norms, the dropout and the tape are the fp32 step's.
+// bf16x3w training (HIFICAR_PREC_BF16X3W): the bf16x3 step, and the weight (and bias) gradient of every layer wgrad_gemm_form selects — one tap,
+// at least 128 x 128: w_raw_in, q | k | v, w_o, linear1, linear2 — in wgrad_bf16x3_kernel on rows xfmr_split_rows_t_kernel splits into two
+// scratch buffers of their own (hificar_xfmr_wgrad16.hip.h); the partials and their reductions are the fp32 form's.  Every other weight
+// gradient (the k = 3 convs, residual_path, w_out) is the fp32 step's.
 
 struct XfmrTrainLayer {
     ConvLayer dg_qkv, dg_wo, dg_l1, dg_l2;
@@ -109,6 +113,7 @@ static int xfmr_alloc(hificar_engine* h, size_t bytes, void** out) {
     return HIFICAR_OK;
 }
 
+static bool xfmr_train_x3(const hificar_xfmr* g) { return g->train_precision != HIFICAR_PREC_F32; }  // bf16x3 or bf16x3w: the same forward and packs
 static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts);
 static int xfmr_repack(hificar_xfmr* g, hipStream_t stream);
 static size_t xfmr_pack16_bytes(const ConvLayer& L);
@@ -404,7 +409,7 @@ static int xfmr_repack(hificar_xfmr* g, hipStream_t stream) {
     XfmrTrain* ts = g->train;
     hificar_engine* h = &g->eng;
     int rc;
-    const bool x3 = g->train_precision == HIFICAR_PREC_BF16X3;
+    const bool x3 = xfmr_train_x3(g);
     if (x3 && (rc = xfmr_train_alloc16(g, ts)) != HIFICAR_OK) return rc;
     const int F = g->cfg.hidden_dim, d = F / kXfmrHeads;
     float* const m = ts->d_master;
@@ -444,12 +449,14 @@ static int xfmr_repack(hificar_xfmr* g, hipStream_t stream) {
 // records the choice.  Afterwards the packs of the new arithmetic are rebuilt from the master copy, behind the handle's last call.
 extern "C" int hificar_xfmr_set_train_precision(hificar_xfmr* g, int precision) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_train_precision: null handle");
-    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3) return fail(HIFICAR_E_INVALID, "unknown training precision %d", precision);
+    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3W)
+        return fail(HIFICAR_E_INVALID, "unknown training precision %d", precision);
     if (g->precision != HIFICAR_PREC_F32)
         return fail(HIFICAR_E_STATE, "this Transformer handle is packed for the %s inference arithmetic: it has no training step, in either arithmetic",
                     xfmr_precision_name(g->precision));
     if (precision == g->train_precision) return HIFICAR_OK;
-    if (!g->train || !g->train->have_params) {
+    // (bf16x3 <-> bf16x3w: the same packs, another weight-gradient kernel)
+    if (!g->train || !g->train->have_params || (precision != HIFICAR_PREC_F32 && xfmr_train_x3(g))) {
         g->train_precision = precision;
         return HIFICAR_OK;
     }
@@ -560,6 +567,7 @@ struct XfmrTrainWs {
     float* colsum;   // bias-gradient partials
     char* light;     // a forward without a tape keeps its rows here
     char* split;     // [rows][3072] split rows (4 bytes per channel): the operand of the next bf16x3 GEMM; null in the fp32 arithmetic
+    char* split_t[2];  // [rows / 8][3072][32 bytes]: G and A of the next bf16x3w weight gradient (xfmr_split_rows_t_kernel); null otherwise
     size_t partial_elems, colsum_elems;
     size_t bytes;
 };
@@ -606,7 +614,9 @@ static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void*
     w.colsum = take(w.colsum_elems * 4);
     w.light = reinterpret_cast<char*>(take(xfmr_plan_tape(g, B, T, nullptr, Mp).bytes));
     // (last: everything in front of it lies where the fp32 arithmetic has it)
-    w.split = g->train_precision == HIFICAR_PREC_BF16X3 ? reinterpret_cast<char*>(take(rows * kXfmrFF * 4)) : nullptr;
+    w.split = xfmr_train_x3(g) ? reinterpret_cast<char*>(take(rows * kXfmrFF * 4)) : nullptr;
+    for (char*& s : w.split_t)  // (behind it: a bf16x3 workspace is a prefix of the bf16x3w one)
+        s = g->train_precision == HIFICAR_PREC_BF16X3W ? reinterpret_cast<char*>(take((size_t)split_t_bytes((long long)rows, kXfmrFF))) : nullptr;
     w.bytes = off;
     return w;
 }
@@ -700,7 +710,7 @@ struct XfmrTrainCtx {
         if (rc != HIFICAR_OK || !ys) return rc;
         return gate(ys, ys, ys, (long long)M * L.cout_pad, -1);
     }
-    bool x3() const { return g->train_precision == HIFICAR_PREC_BF16X3; }
+    bool x3() const { return xfmr_train_x3(g); }
     // fp32 rows [M][C] -> the split scratch (rows of padded frames and gap rows: zero bits, not read)
     int split_rows(const float* x, int C) const {
         const long long n8 = (long long)M * C / 8;
@@ -710,7 +720,25 @@ struct XfmrTrainCtx {
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
+    // fp32 rows [M][C] -> 8-row groups of split columns (rows of padded frames and gap rows: zero bits, not read)
+    int split_rows_t(const float* x, int C, char* dst) const {
+        const long long n = split_t_items(M, C);
+        ProfScope prof(h, stream, "xfmr_split_rows_t_kernel", 0.0, 8.0 * M * C);
+        hipLaunchKernelGGL(xfmr_split_rows_t_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 8192)), dim3(256), 0, stream, x, dst, (long long)M, C, hdr,
+                           lens, T, lay);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
     int wgrad(const ConvLayer& L, const float* gr, int gpitch, const float* a, int apitch, float* dW, float* db) const {
+        if (g->train_precision == HIFICAR_PREC_BF16X3W && wgrad_gemm_form(L)) {  // bf16x3w: the one-tap GEMM form on bf16 MFMAs
+            if (!ws->split_t[0] || !ws->split_t[1] || gpitch > kXfmrFF || apitch > kXfmrFF) return fail(HIFICAR_E_INVALID, "internal: bf16x3w weight gradient of %s", L.name.c_str());
+            int rc;
+            if ((rc = split_rows_t(gr, gpitch, ws->split_t[0])) != HIFICAR_OK || (rc = split_rows_t(a, apitch, ws->split_t[1])) != HIFICAR_OK) return rc;
+            WgradJob job = {&L, gr, gpitch, a, apitch, dW, db};
+            job.g16 = ws->split_t[0];
+            job.a16 = ws->split_t[1];
+            return launch_wgrad_n(h, &job, 1, 1, M, bw, stream);
+        }
         return L.K > 1 && !packed() ? launch_wgrad(h, L, gr, gpitch, a, apitch, B, T, dW, bw, stream, db)
                                     : launch_wgrad(h, L, gr, gpitch, a, apitch, 1, M, dW, bw, stream, db);
     }
@@ -1223,6 +1251,48 @@ extern "C" int hificar_debug_pack16(int cout, int cin, int cin_pad, int K, int m
     hipError_t e = rc == HIFICAR_OK ? hipMemcpy(out, d, n * sizeof(uint16_t), hipMemcpyDeviceToHost) : hipSuccess;
     for (void* p : tmp.allocs) (void)hipFree(p);
     if (rc != HIFICAR_OK) return rc;
+    HIP_TRY(e);
+    return HIFICAR_OK;
+}
+
+// Test aid: the split of fp32 rows x [M][C] (host floats) into 8-row groups, as the bf16x3w training arithmetic's weight gradients read them
+// (xfmr_split_rows_t_kernel).  lengths / T (B = M / T sequences; null: dense) mark a ragged batch's padded frames, pad_row (M entries, < 0: a
+// gap row; null: none) a packed batch's gap rows; both kinds of row are written as zero bits.  how 0: the kernel's index functions run on the
+// host (no device); 1: the kernel itself, over a buffer of 0xFF bytes.  out: `capacity` bytes; *bytes: how many the split has.
+extern "C" int hificar_debug_split_rows_t(int M, int C, int T, const int32_t* lengths, const int32_t* pad_row, int how, const float* x, void* out,
+                                          size_t capacity, size_t* bytes) {
+    if (!x || !out || !bytes || M < 1 || C < 1 || how < 0 || how > 1 || (long long)M * C >= (1LL << 31) || (lengths && (T < 1 || M % T)) || (lengths && pad_row))
+        return fail(HIFICAR_E_INVALID, "hificar_debug_split_rows_t: bad argument");
+    const size_t n = (size_t)split_t_bytes(M, C);
+    *bytes = n;
+    if (capacity < n) return fail(HIFICAR_E_INVALID, "hificar_debug_split_rows_t: %zu bytes, the buffer has %zu", n, capacity);
+    if (how == 0) {
+        memset(out, 0xFF, n);
+        auto valid = [&](long long r) { return pad_row ? pad_row[r] >= 0 : !lengths || r % T < std::min(std::max(lengths[r / T], 0), T); };
+        for (long long i = 0; i < split_t_items(M, C); ++i) split_t_item(x, static_cast<char*>(out), M, C, i, valid);
+        return HIFICAR_OK;
+    }
+    void *dx = nullptr, *dd = nullptr, *dl = nullptr;
+    const int32_t* table = pad_row ? pad_row : lengths;
+    const size_t tn = pad_row ? (size_t)M : lengths ? (size_t)(M / T) : 0;
+    hipError_t e = hipMalloc(&dx, (size_t)M * C * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&dd, n);
+    if (e == hipSuccess && tn) e = hipMalloc(&dl, tn * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(dx, x, (size_t)M * C * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && tn) e = hipMemcpy(dl, table, tn * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dd, 0xFF, n);
+    if (e == hipSuccess) {
+        XfmrLayout lay;
+        if (pad_row) lay.pad_row = static_cast<const int*>(dl);
+        hipLaunchKernelGGL(xfmr_split_rows_t_kernel, dim3((unsigned)std::min<long long>((split_t_items(M, C) + 255) / 256, 8192)), dim3(256), 0, nullptr,
+                           static_cast<const float*>(dx), static_cast<char*>(dd), (long long)M, C, nullptr, pad_row ? nullptr : static_cast<const int*>(dl),
+                           T > 0 ? T : 1, lay);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, dd, n, hipMemcpyDeviceToHost);
+    (void)hipFree(dx);
+    (void)hipFree(dd);
+    (void)hipFree(dl);
     HIP_TRY(e);
     return HIFICAR_OK;
 }

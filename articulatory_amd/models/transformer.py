@@ -31,8 +31,11 @@ additions and the residual stream stay fp32.  Inference only: a train()-mode for
 ``train_precision="bf16x3"`` (opt-in, keyword or ``set_train_precision``; ``"f32"`` is the default and unchanged) is the training step's
 own switch, on a ``precision="f32"`` model: every forward GEMM of ``forward`` / ``forward_padded`` (packed or not) in train() mode and every
 data gradient runs in the bf16x3 kernels, on weight fragments packed on the device after every optimizer step; weight and bias gradients,
-the attention, the norms, dropout (the same masks) and the tape stay fp32, and so does the eval-mode forward.  Not built: bf16x3
-weight-gradient kernels, bf16 MFMAs in the attention.
+the attention, the norms, dropout (the same masks) and the tape stay fp32, and so does the eval-mode forward.
+``train_precision="bf16x3w"`` is that step with, in addition, the weight gradients of the one-tap layers at least 128 x 128 wide (``w_raw_in``,
+q | k | v, ``w_o``, ``linear1``, ``linear2``) as G^T A ~ hi^T hi + hi^T lo + lo^T hi on bf16 MFMAs, and their bias gradients as the fp32 sum of
+hi + lo; the k = 3 ResBlock convs, ``residual_path`` and ``w_out`` keep exact fp32 weight gradients.  ``precision="bf16x3w"`` is a ValueError.
+Not built: bf16x3 weight gradients of the k = 3 convs, bf16 MFMAs in the attention.
 
 Not built, refused with ``NotImplementedError``: ``extra_art=True`` and ``num_ph`` (phoneme input).  ``forward(lengths=...)`` in train() mode
 is refused too (ragged training is asked for by name: ``forward_padded``).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size``
@@ -193,10 +196,10 @@ class _PrecisionKeyword(type):
             raise ValueError(f"precision must be one of {sorted(_native.PRECISIONS)}")
         if train_precision is None:
             train_precision = "f32"
-        if train_precision not in _native.PRECISIONS:
-            raise ValueError(f"train_precision must be one of {sorted(_native.PRECISIONS)}")
+        if train_precision not in _native.TRAIN_PRECISIONS:
+            raise ValueError(f"train_precision must be one of {sorted(_native.TRAIN_PRECISIONS)}")
         if precision != "f32" and train_precision != "f32":
-            raise ValueError("train_precision='bf16x3' needs precision='f32': a precision='bf16x3' model is inference-only")
+            raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='bf16x3' model is inference-only")
         self = super().__call__(*args, **kwargs)
         self.precision = precision
         self.train_precision = train_precision
@@ -265,17 +268,18 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         and every data gradient as x w ~ hi hi + hi lo + lo hi on bf16 MFMAs with fp32 accumulation; weight and bias gradients, attention,
         norms, dropout and the tape stay fp32 (hificar_xfmr_set_train_precision).  The eval-mode forward is exact fp32 either way.  The
         native handle is kept: its packs are rebuilt on the device.  A backward whose forward ran in the other arithmetic is refused
-        (RuntimeError).  Not with ``precision="bf16x3"`` (ValueError)."""
-        if train_precision not in _native.PRECISIONS:
-            raise ValueError(f"train_precision must be one of {sorted(_native.PRECISIONS)}")
+        (RuntimeError).  "bf16x3w": "bf16x3", and the weight and bias gradients of the one-tap layers at least 128 x 128 wide in the same
+        arithmetic (see the module's docstring).  Not with ``precision="bf16x3"`` (ValueError)."""
+        if train_precision not in _native.TRAIN_PRECISIONS:
+            raise ValueError(f"train_precision must be one of {sorted(_native.TRAIN_PRECISIONS)}")
         if train_precision != "f32" and self.precision != "f32":
-            raise ValueError("train_precision='bf16x3' needs precision='f32': a precision='bf16x3' model is inference-only")
+            raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='bf16x3' model is inference-only")
         if train_precision == self.train_precision:
             return
         self.train_precision = train_precision
         if self.__dict__.get("_handle") is not None:
             with torch.cuda.device(self._device()):
-                _native.check(self._lib.hificar_xfmr_set_train_precision(self._handle, _native.PRECISIONS[train_precision]),
+                _native.check(self._lib.hificar_xfmr_set_train_precision(self._handle, _native.TRAIN_PRECISIONS[train_precision]),
                               "hificar_xfmr_set_train_precision")
 
     def _refuse_bf16x3_training(self):
@@ -450,7 +454,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                 _native.check(lib.hificar_xfmr_set_precision(handle, _native.PRECISIONS[self.precision]), "hificar_xfmr_set_precision")
                 _native.check(lib.hificar_xfmr_finalize(handle), "hificar_xfmr_finalize")
                 if self.precision == "f32":  # (a bf16x3 inference handle has no training arithmetic to choose)
-                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.PRECISIONS[self.train_precision]),
+                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.TRAIN_PRECISIONS[self.train_precision]),
                                   "hificar_xfmr_set_train_precision")
             except Exception:
                 lib.hificar_xfmr_destroy(handle)

@@ -71,6 +71,8 @@ extern "C" {
 /* arithmetic used by the convolution kernels */
 #define HIFICAR_PREC_F32 0         /* v_mfma_f32_32x32x2_f32: exact fp32 multiply, fp32 accumulate */
 #define HIFICAR_PREC_BF16X3 1      /* fp32 operands split hi+lo bf16, 3 bf16 MFMAs, fp32 accumulate */
+#define HIFICAR_PREC_BF16X3W 2     /* hificar_xfmr_set_train_precision ONLY: bf16x3, and the one-tap GEMM-form weight gradients in it too;
+                                      every other entry point that takes a precision refuses it (HIFICAR_E_INVALID) */
 
 typedef struct hificar_handle hificar_handle;
 /* The conv engine every model of the library launches through (plans, schedules, stream ordering, profiling).  A generator handle
@@ -716,9 +718,11 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * hificar_xfmr_forward_train_packed computes the same step without GEMM rows for the padding.
  * All of these may be called after hificar_xfmr_finalize; the first one builds the training state.
  * The forward GEMMs and data gradients have an opt-in bf16x3 arithmetic (hificar_xfmr_set_train_precision, below).
- * Not built: a smaller tape per frame, bf16x3 weight-gradient kernels, bf16 MFMAs in the attention, extra_art, num_ph, multi-GPU training of this model. ---- */
+ * The one-tap weight gradients have one too (HIFICAR_PREC_BF16X3W).
+ * Not built: a smaller tape per frame, bf16x3 weight gradients of the k = 3 convs, bf16 MFMAs in the attention, extra_art, num_ph, multi-GPU training of this model. ---- */
 
-/* The arithmetic of the training step's GEMMs: HIFICAR_PREC_F32 (the default: the step above, bit for bit) or HIFICAR_PREC_BF16X3.
+/* The arithmetic of the training step's GEMMs: HIFICAR_PREC_F32 (the default: the step above, bit for bit), HIFICAR_PREC_BF16X3 or
+ * HIFICAR_PREC_BF16X3W.
  * bf16x3: every forward GEMM of hificar_xfmr_forward_train / _ragged / _packed (the six ResBlock convs and residual_path, w_raw_in,
  * q | k | v, w_o, linear1, linear2, w_out) and every data gradient of the same layers runs as x w ~ hi hi + hi lo + lo hi on bf16 MFMAs with
  * fp32 accumulation, in the conv engine's bf16x3 kernels (hi = bf16(x), lo = bf16(x - hi), round to nearest even; split-K off: one
@@ -727,6 +731,13 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * (hificar_xfmr_tape_bytes* do not change).  hificar_xfmr_forward stays exact fp32.  hificar_xfmr_set_parameters_device then also builds the
  * bf16 fragments of every forward and data-gradient layer on the device, and the training workspace grows by one buffer of split rows
  * (3072 columns): ask hificar_xfmr_train_workspace_bytes* after this call.
+ * bf16x3w: the bf16x3 step, bit for bit in its forward, data gradients, attention, norms, dropout masks, tape and eval forward, and in
+ * addition the weight gradient of every one-tap layer at least 128 output channels and 128 input columns wide (w_raw_in, q | k | v, w_o,
+ * linear1, linear2 at the default size) as dW = G^T A ~ hi^T hi + hi^T lo + lo^T hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, on
+ * operands split the same way (hi = bf16(x), lo = bf16(x - hi)) into groups of 8 rows per column; the bias gradient of such a layer is the
+ * fp32 sum of hi + lo over the rows.  Deterministic (fixed summation order, no atomics).  Every other weight and bias gradient — the k = 3
+ * ResBlock convs, residual_path, w_out, anything narrower than 128 — stays on the exact fp32 kernels.  The workspace grows by two more
+ * buffers (the split G and A rows, 3072 columns each) behind the bf16x3 one.  bf16x3 <-> bf16x3w rebuilds nothing.
  * Legal at any time on an f32 handle, also after hificar_xfmr_finalize and between steps: once parameters have been handed over, the packs of
  * the new arithmetic are rebuilt from the handle's device copy, in stream order behind the handle's last call.  A handle whose
  * hificar_xfmr_set_precision is bf16x3 (inference only): HIFICAR_E_STATE.  An unknown value: HIFICAR_E_INVALID.
@@ -740,6 +751,14 @@ int hificar_xfmr_set_train_precision(hificar_xfmr* h, int precision);
  * kernel, over a buffer of 0xFF bytes; 2: the host pack of the inference handles, read back from the device.  out: HOST, `capacity` 16-bit
  * elements; *elems: the pack's size in elements (set even when the buffer is too small: HIFICAR_E_INVALID then). */
 int hificar_debug_pack16(int cout, int cin, int cin_pad, int K, int mode, int how, const float* w, uint16_t* out, size_t capacity, size_t* elems);
+
+/* Test aid: fp32 rows x [M][C] (HOST floats) split for the bf16x3w weight gradients: [ceil(M / 8)][C][hi 8 | lo 8] bf16, 32 bytes per (group of 8
+ * rows, column); rows past M are zero bits.  lengths (M / T frame counts of sequences of T rows; NULL: dense) marks a ragged batch's padded
+ * frames, pad_row (M entries, < 0: a gap row; NULL: none; not both) a packed batch's gap rows: both are written as zero bits.  how 0: the
+ * device pass's index functions run on the host (no device needed); 1: the device pass, over a buffer of 0xFF bytes.  out: HOST, `capacity`
+ * bytes; *bytes: the split's size (set even when the buffer is too small: HIFICAR_E_INVALID then). */
+int hificar_debug_split_rows_t(int M, int C, int T, const int32_t* lengths, const int32_t* pad_row, int how, const float* x, void* out, size_t capacity,
+                               size_t* bytes);
 
 /* Every float tensor of the state_dict (reference names and layouts, the batch norms' running_mean / running_var included; n = all of them,
  * each once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs (the

@@ -46,6 +46,14 @@ each, in the same process.  The line then carries bf16x3_ms, f32_over_bf16x3 (fa
 bf16x3_faster — the slowest bf16x3 window is below the fastest f32 window by more than the two legs' window spreads added — and the
 bf16x3 step's per-kernel table (one forward + backward + the packs of one parameter hand-over).  With --ragged: the bf16x3 ragged and
 packed legs beside the fp32 ones.
+
+   python tools/transformer_bench.py --train --train-precision bf16x3w [--ragged] [--out profiles/transformer_train_bf16x3w.txt]
+
+--train-precision bf16x3w: the bf16x3 leg(s) above AND one more, train_precision="bf16x3w" (the one-tap weight gradients on bf16 MFMAs too),
+all in the same alternation: its yardsticks are the f32 and bf16x3 legs of the same run.  The line carries bf16x3w_ms,
+bf16x3_over_bf16x3w (fastest bf16x3 window over slowest bf16x3w window), bf16x3w_faster (the slowest bf16x3w window is below the fastest
+bf16x3 window by more than the two spreads added), the bf16x3w step's per-kernel table and wgrad_bf16x3_mfma_share: the bf16 MFMA issue
+time of the new kernel's launches at the peak rate over their measured time.
 Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
 import argparse
 import ctypes
@@ -66,6 +74,7 @@ from transformer_oracle import TransformerOracle  # noqa: E402
 
 PARAMS = dict(in_channels=12, out_channels=80, elayers=6, hidden_dim=768)
 PEAK_TFLOPS = 157.3
+BF16_PEAK_TFLOPS = 16 * PEAK_TFLOPS  # v_mfma_f32_32x32x16_bf16: 8 x the flops of 32x32x2_f32 in half its passes; wgrad_bf16x3_mfma_share divides by it
 
 
 def window(fn, x, seconds):
@@ -122,11 +131,18 @@ def train_main(a):
     stock = Stock(sd, dtype=torch.float32, device="cuda", dropout=p)
     s_opt = torch.optim.Adam(list(stock.params.values()), lr=1e-4, fused=True)
     fast = f_opt = None
-    if a.train_precision == "bf16x3":
-        fast = Transformer(dropout=p, train_precision="bf16x3", **PARAMS)
-        fast.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-        fast = fast.cuda().train()
-        f_opt = torch.optim.Adam(fast.parameters(), lr=1e-4, fused=True)
+    fastw = w_opt = None
+
+    def leg(arith):
+        m = Transformer(dropout=p, train_precision=arith, **PARAMS)
+        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+        m = m.cuda().train()
+        return m, torch.optim.Adam(m.parameters(), lr=1e-4, fused=True)
+
+    if a.train_precision in ("bf16x3", "bf16x3w"):
+        fast, f_opt = leg("bf16x3")
+    if a.train_precision == "bf16x3w":
+        fastw, w_opt = leg("bf16x3w")
 
     def profile_step(m, opt):
         """{kernel: ms} of one step: the parameter hand-over behind the optimizer step before it, forward and backward."""
@@ -138,6 +154,7 @@ def train_main(a):
         stats = (_native.HificarKernelStat * 128)()
         n = ctypes.c_int()
         _native.check(m._lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
+        profile_step.flops = {stats[i].name.decode(): float(stats[i].flops) for i in range(n.value)}
         return {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
 
     lines = []
@@ -161,16 +178,25 @@ def train_main(a):
             F.l1_loss(fast(x), y).backward()
             f_opt.step()
 
+        def fastw_step(_):
+            w_opt.zero_grad(set_to_none=True)
+            F.l1_loss(fastw(x), y).backward()
+            w_opt.step()
+
         for _ in range(2):
             native_step(None), stock_step(None)
             if fast is not None:
                 fast_step(None)
+            if fastw is not None:
+                fastw_step(None)
         torch.cuda.synchronize()
         n1 = window(native_step, None, a.window)
         f1 = None if fast is None else window(fast_step, None, a.window)
+        w1 = None if fastw is None else window(fastw_step, None, a.window)
         s1 = window(stock_step, None, a.window)
         n2 = window(native_step, None, a.window)
         f2 = None if fast is None else window(fast_step, None, a.window)
+        w2 = None if fastw is None else window(fastw_step, None, a.window)
         s2 = window(stock_step, None, a.window)
         res = {"train": True, "B": B, "T": T, "dropout": p, "native_ms": [round(n1, 3), round(n2, 3)], "stock_ms": [round(s1, 3), round(s2, 3)],
                "native_spread": round(abs(n1 - n2) / min(n1, n2), 4), "stock_spread": round(abs(s1 - s2) / min(s1, s2), 4),
@@ -201,6 +227,21 @@ def train_main(a):
             res["f32_kernels_ms"] = {k: round(v, 4) for k, v in sorted(pn.items(), key=lambda kv: -kv[1])}
             fam = lambda prof, pre: round(sum(v for k, v in prof.items() if k.startswith(pre)), 4)  # noqa: E731
             res["families_ms"] = {pre: {"f32": fam(pn, pre), "bf16x3": fam(pf, pre)} for pre in ("conv", "wgrad", "wreduce", "xfmr_attn", "xfmr_split_rows", "pack16", "xfmr_")}
+        if fastw is not None:
+            res["bf16x3w_ms"] = [round(w1, 3), round(w2, 3)]
+            res["bf16x3w_spread"] = round(abs(w1 - w2) / min(w1, w2), 4)
+            res["f32_over_bf16x3w"] = round(min(n1, n2) / max(w1, w2), 3)
+            res["bf16x3_over_bf16x3w"] = round(min(f1, f2) / max(w1, w2), 3)
+            res["bf16x3w_faster"] = bool(min(f1, f2) - max(w1, w2) > abs(f1 - f2) + abs(w1 - w2))
+            pw = profile_step(fastw, w_opt)
+            res["bf16x3w_kernels_ms"] = {k: round(v, 4) for k, v in sorted(pw.items(), key=lambda kv: -kv[1])}
+            for pre in res["families_ms"]:
+                res["families_ms"][pre]["bf16x3w"] = fam(pw, pre)
+            res["families_ms"]["xfmr_split_rows_t"] = {"f32": 0.0, "bf16x3": 0.0, "bf16x3w": fam(pw, "xfmr_split_rows_t")}
+            # three bf16 MFMAs per fp32 product: the new kernel's bf16 MFMA issue time at the peak rate over its measured time
+            wflops = sum(v for k, v in profile_step.flops.items() if k.startswith("wgrad_bf16x3"))
+            wms = fam(pw, "wgrad_bf16x3")
+            res["wgrad_bf16x3_mfma_share"] = round(3.0 * wflops / (BF16_PEAK_TFLOPS * 1e12) / (wms * 1e-3), 4) if wms else None
         lines.append(json.dumps(res))
         print(lines[-1], flush=True)
     if a.out:
@@ -240,13 +281,16 @@ def ragged_train_main(a):
 
     legs = {"native_packed": make(lambda: masked_l1_loss(m.forward_padded(x, lens32, packed=True), y, lens32)),
             "native_ragged": make(lambda: masked_l1_loss(m.forward_padded(x, lens32), y, lens32)), "native_dense": make(lambda: F.l1_loss(m(x), y))}
-    if a.train_precision == "bf16x3":  # the same batch through a second model in the bf16x3 training arithmetic, padded and packed
-        m3 = Transformer(dropout=p, train_precision="bf16x3", **PARAMS)
+    ariths = {"bf16x3": ("bf16x3",), "bf16x3w": ("bf16x3", "bf16x3w")}.get(a.train_precision, ())
+    fast = {}
+    for arith in ariths:  # the same batch through further models in the bf16x3 (and bf16x3w) training arithmetic, padded and packed
+        m3 = Transformer(dropout=p, train_precision=arith, **PARAMS)
         m3.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
         m3 = m3.cuda().train()
         opt3 = torch.optim.Adam(m3.parameters(), lr=1e-4, fused=True)
+        fast[arith] = m3
 
-        def make3(loss_fn):
+        def make3(loss_fn, opt3=opt3):
             def step(_=None):
                 opt3.zero_grad(set_to_none=True)
                 loss_fn().backward()
@@ -254,8 +298,8 @@ def ragged_train_main(a):
 
             return step
 
-        legs["bf16x3_packed"] = make3(lambda: masked_l1_loss(m3.forward_padded(x, lens32, packed=True), y, lens32))
-        legs["bf16x3_ragged"] = make3(lambda: masked_l1_loss(m3.forward_padded(x, lens32), y, lens32))
+        legs[arith + "_packed"] = make3(lambda m3=m3: masked_l1_loss(m3.forward_padded(x, lens32, packed=True), y, lens32))
+        legs[arith + "_ragged"] = make3(lambda m3=m3: masked_l1_loss(m3.forward_padded(x, lens32), y, lens32))
     for _ in range(2):
         for fn in legs.values():
             fn()
@@ -283,6 +327,10 @@ def ragged_train_main(a):
             n_, f_ = ms["native_" + form], ms["bf16x3_" + form]
             res[f"f32_over_bf16x3_{form}"] = round(min(n_) / max(f_), 3)
             res[f"bf16x3_faster_{form}"] = bool(min(n_) - max(f_) > abs(n_[0] - n_[1]) + abs(f_[0] - f_[1]))
+        if "bf16x3w_" + form in ms:
+            f_, w_ = ms["bf16x3_" + form], ms["bf16x3w_" + form]
+            res[f"bf16x3_over_bf16x3w_{form}"] = round(min(f_) / max(w_), 3)
+            res[f"bf16x3w_faster_{form}"] = bool(min(f_) - max(w_) > abs(f_[0] - f_[1]) + abs(w_[0] - w_[1]))
     eng = m.engine()
     profs = {}
     for tag in ("packed", "ragged", "dense"):
@@ -294,17 +342,17 @@ def ragged_train_main(a):
         profs[tag] = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
         res[tag + "_kernels_ms"] = {k: round(v, 4) for k, v in sorted(profs[tag].items(), key=lambda kv: -kv[1])}
         res[tag + "_kernels_total_ms"] = round(sum(profs[tag].values()), 3)
-    if a.train_precision == "bf16x3":
+    for arith, m3 in fast.items():
         eng3 = m3.engine()
         for tag in ("packed", "ragged"):
             _native.check(lib.hificar_profile_begin(eng3), "hificar_profile_begin")
-            legs["bf16x3_" + tag]()
+            legs[f"{arith}_{tag}"]()
             stats = (_native.HificarKernelStat * 128)()
             n = ctypes.c_int()
             _native.check(lib.hificar_profile_end(eng3, stats, 128, ctypes.byref(n)), "hificar_profile_end")
             prof3 = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
-            res[f"bf16x3_{tag}_kernels_ms"] = {k: round(v, 4) for k, v in sorted(prof3.items(), key=lambda kv: -kv[1])}
-            res[f"bf16x3_{tag}_kernels_total_ms"] = round(sum(prof3.values()), 3)
+            res[f"{arith}_{tag}_kernels_ms"] = {k: round(v, 4) for k, v in sorted(prof3.items(), key=lambda kv: -kv[1])}
+            res[f"{arith}_{tag}_kernels_total_ms"] = round(sum(prof3.values()), 3)
     res["attention_recovered_ms"] = {k: round(profs["dense"].get(k, 0.0) - profs["ragged"].get(k, 0.0), 4)
                                      for k in ("xfmr_attn_kernel<train>", "xfmr_attn_bwd_kernels")}
     # packed over ragged per kernel family, to read beside packed_rows_over_padded_rows: conv_* are the forward GEMMs and the data gradients
@@ -329,7 +377,8 @@ def main():
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--no-stock", action="store_true")
     ap.add_argument("--precision", choices=("f32", "bf16x3"), default="f32", help="bf16x3: add the bf16x3 leg to the native / stock alternation")
-    ap.add_argument("--train-precision", choices=("f32", "bf16x3"), default="f32", help="--train: bf16x3 adds the bf16x3 training leg(s)")
+    ap.add_argument("--train-precision", choices=("f32", "bf16x3", "bf16x3w"), default="f32",
+                    help="--train: bf16x3 adds the bf16x3 training leg(s); bf16x3w adds those and the bf16x3w leg(s)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--ragged", action="store_true", help="--train: the ragged batch's two legs instead of the dense shapes")
     ap.add_argument("--seed", type=int, default=0, help="--train --ragged: seed of the lengths")
