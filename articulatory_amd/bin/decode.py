@@ -286,9 +286,9 @@ def get_parser():
     parser.add_argument("--verbose", type=int, default=1, help="logging level. higher is more logging. (default=1)")
     parser.add_argument("--batch-size", type=int, default=1,
                         help="utterances synthesised per device call (any lengths; not in the reference, which is batch-1)")
-    parser.add_argument("--precision", default=None, choices=("f32", "bf16x3"),
+    parser.add_argument("--precision", default=None, choices=("f32", "bf16x3", "bf16x3a"),
                         help="arithmetic of the model's GEMMs, for models with set_precision (the Transformer): f32, the reference's IEEE fp32 "
-                             "products, or the opt-in fast mode bf16x3.  Not given: the model's own default, f32 (not in the reference)")
+                             "products, or the opt-in fast modes bf16x3 and (the Transformer only) bf16x3a, which runs the attention on bf16 MFMAs too.  Not given: the model's own default, f32 (not in the reference)")
     parser.add_argument("--dry-run", default=False, action="store_true",
                         help="print this rank's share of the utterance list as one JSON line and exit (no GPU needed; not in the reference)")
     add_conditioning_arguments(parser)

@@ -17,10 +17,15 @@
 // [hi: C bf16 | lo: C bf16] (4 C bytes per row, as fp32 rows) written by the producer: the engine's own output pass (ys), xfmr_rows_split_kernel,
 // xfmr_ln_kernel<true>, xfmr_attn_kernel<D, false, true>.  Everything else — attention, LayerNorm, bias and residual additions, the residual
 // stream — is fp32 as above.  Five row buffers instead of three: a GEMM's fp32 residual and the next GEMM's split input exist side by side.
+//
+// bf16x3a (HIFICAR_PREC_BF16X3A, eval only): the bf16x3 forward with the attention's three products on bf16 MFMAs too
+// (hificar_xfmr_attn16.hip.h).  The q | k | v GEMM writes split rows only ([hi: 3 F bf16 | lo: 3 F bf16], the bytes of the fp32 row), and
+// finalize splits each layer's position tables once.  The conv engine sees a bf16x3 handle.
 
 struct XfmrEncLayer {
     ConvLayer qkv, wo, l1, l2;
     float* d_emb = nullptr;                 // [8][199][d]
+    uint16_t* d_emb16 = nullptr;            // bf16x3a: [hi, lo][8][208][d] bf16, rows 199 .. 207 zeros
     float* d_ln[4] = {nullptr, nullptr, nullptr, nullptr};  // norm1.weight, norm1.bias, norm2.weight, norm2.bias
 };
 
@@ -49,6 +54,9 @@ struct hificar_xfmr {
 };
 
 static void xfmr_train_free(hificar_xfmr* g);
+
+// the handle's GEMMs run in the engine's bf16x3 kernels (bf16x3 and bf16x3a differ in the attention alone)
+static bool xfmr_x3(const hificar_xfmr* g) { return g->precision == HIFICAR_PREC_BF16X3 || g->precision == HIFICAR_PREC_BF16X3A; }
 
 static bool xfmr_head_dim_built(int d) { return d >= 16 && d <= 128 && d % 16 == 0; }
 
@@ -175,11 +183,14 @@ static int xfmr_pack(hificar_engine* h, ConvLayer& L, const HostTensor& W, const
     return pack_w32(h, L, W, L.chunk16, &L.d_w32);
 }
 
-static const char* xfmr_precision_name(int p) { return p == HIFICAR_PREC_BF16X3W ? "bf16x3w" : p == HIFICAR_PREC_BF16X3 ? "bf16x3" : "f32"; }
+static const char* xfmr_precision_name(int p) {
+    return p == HIFICAR_PREC_BF16X3A ? "bf16x3a" : p == HIFICAR_PREC_BF16X3W ? "bf16x3w" : p == HIFICAR_PREC_BF16X3 ? "bf16x3" : "f32";
+}
 
 extern "C" int hificar_xfmr_set_precision(hificar_xfmr* g, int precision) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_precision: null handle");
-    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3) return fail(HIFICAR_E_INVALID, "unknown precision %d", precision);
+    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3A)
+        return fail(HIFICAR_E_INVALID, "unknown precision %d", precision);
     if (g->finalized)
         return fail(HIFICAR_E_STATE, "hificar_xfmr_set_precision after hificar_xfmr_finalize: the weights are packed for %s only; make a new handle",
                     xfmr_precision_name(g->precision));
@@ -243,7 +254,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
     hificar_engine* h = &g->eng;
     const int F = g->cfg.hidden_dim, d = F / kXfmrHeads;
     int rc;
-    h->precision = g->precision;  // (xfmr_pack goes by it)
+    h->precision = xfmr_x3(g) ? HIFICAR_PREC_BF16X3 : HIFICAR_PREC_F32;  // (xfmr_pack goes by it)
     for (int i = 0; i < 3; ++i) {
         const std::string b = "conv_blocks." + std::to_string(i) + ".";
         if ((rc = xfmr_pack_folded(g, g->c1[i], b + "conv1", b + "bn1")) != HIFICAR_OK) return rc;
@@ -286,6 +297,24 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
         if ((rc = linear(E.l1, b + "linear1")) != HIFICAR_OK) return rc;
         if ((rc = linear(E.l2, b + "linear2")) != HIFICAR_OK) return rc;
         if ((rc = upload(h, g->tensors.at(b + "self_attn.relative_positional.embeddings").data, &E.d_emb)) != HIFICAR_OK) return rc;
+        if (g->precision == HIFICAR_PREC_BF16X3A) {  // the tables as the attention's MFMA operand: split once, padded to whole 16-row tiles
+            const std::vector<float>& src = g->tensors.at(b + "self_attn.relative_positional.embeddings").data;
+            const size_t half = (size_t)kXfmrHeads * kXfmrTabPad * d;
+            std::vector<uint16_t> t16(2 * half, 0);
+            for (int hh = 0; hh < kXfmrHeads; ++hh)
+                for (int r = 0; r < kXfmrTab; ++r)
+                    for (int a = 0; a < d; ++a) {
+                        const float v = src[((size_t)hh * kXfmrTab + r) * d + a];
+                        const uint16_t vh = f32_to_bf16(v);
+                        t16[((size_t)hh * kXfmrTabPad + r) * d + a] = vh;
+                        t16[half + ((size_t)hh * kXfmrTabPad + r) * d + a] = f32_to_bf16(v - bf16_to_f32(vh));
+                    }
+            void* dp = nullptr;
+            HIP_TRY(hipMalloc(&dp, t16.size() * sizeof(uint16_t)));
+            h->allocs.push_back(dp);
+            HIP_TRY(hipMemcpy(dp, t16.data(), t16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            E.d_emb16 = static_cast<uint16_t*>(dp);
+        }
         int i = 0;
         for (const char* n : {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"})
             if ((rc = upload(h, g->tensors.at(b + n).data, &E.d_ln[i++])) != HIFICAR_OK) return rc;
@@ -298,9 +327,10 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
     HIP_TRY(xfmr_attn_attr<96>());
     HIP_TRY(xfmr_attn_attr<112>());
     HIP_TRY(xfmr_attn_attr<128>());
+    if (g->precision == HIFICAR_PREC_BF16X3A) HIP_TRY(xfmr_attn16_attr_all());
     // the engine opens here, not in hificar_xfmr_create: a handle can be created and described without a device
     if ((rc = engine_open(h, true)) != HIFICAR_OK) return rc;
-    h->precision = g->precision;
+    h->precision = xfmr_x3(g) ? HIFICAR_PREC_BF16X3 : HIFICAR_PREC_F32;
     h->use_pair = false;
     h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's result does not depend on what it is batched with
     HIP_TRY(hipDeviceSynchronize());
@@ -325,7 +355,7 @@ static XfmrWorkspace xfmr_plan_workspace(const hificar_xfmr* g, int B, int T, vo
     char* p = static_cast<char*>(base);
     w.xin = reinterpret_cast<float*>(p);
     // bf16x3: split rows take a fp32 row's bytes, and the layer input and norm1's output exist in both formats at once: two more row buffers
-    const int nr = g->precision == HIFICAR_PREC_BF16X3 ? 5 : 3;
+    const int nr = xfmr_x3(g) ? 5 : 3;
     for (int i = 0; i < 5; ++i) w.r[i] = i < nr ? reinterpret_cast<float*>(p + xb + i * rb) : nullptr;
     w.wide = reinterpret_cast<float*>(p + xb + nr * rb);
     w.bytes = xb + nr * rb + wb;
@@ -349,7 +379,7 @@ extern "C" int hificar_xfmr_debug_tap(hificar_xfmr* g, const char* name, float* 
         g->taps.erase(name);
         return HIFICAR_OK;
     }
-    if (g->precision == HIFICAR_PREC_BF16X3 && std::string(name) == "conv_blocks")
+    if (xfmr_x3(g) && std::string(name) == "conv_blocks")
         return fail(HIFICAR_E_INVALID, "debug tap 'conv_blocks': a bf16x3 handle holds the conv blocks' output as split bf16 rows only, not as fp32 rows");
     g->taps[name] = {dst, capacity};
     return HIFICAR_OK;
@@ -387,7 +417,7 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
     Ragged rg;
     rg.seq_len = lengths;
     rg.frames = T;
-    const bool x3 = g->precision == HIFICAR_PREC_BF16X3;
+    const bool x3 = xfmr_x3(g), a16 = g->precision == HIFICAR_PREC_BF16X3A;
     if (x3 && g->taps.count("conv_blocks")) return fail(HIFICAR_E_INVALID, "debug tap 'conv_blocks': a bf16x3 handle holds these rows as split bf16 rows only");
     // one launch of one layer: xs -> y (fp32) and / or ys (the activated copy: ReLU, or with slope 1 the identity), + res.  xs and ys are fp32
     // rows in exact fp32 and split rows in bf16x3; res_relu (bf16x3): res holds the rows before their ReLU
@@ -461,8 +491,22 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
     for (int l = 0; l < g->cfg.elayers; ++l) {
         const XfmrEncLayer& E = g->enc[(size_t)l];
         const std::string name = "layers." + std::to_string(l);
-        if ((rc = conv(E.qkv, x3 ? Xs : X, nullptr, ws.wide, nullptr)) != HIFICAR_OK) return rc;
-        {
+        // (bf16x3a: q | k | v as split rows only — slope 1 is the identity copy — for the attention's MFMAs)
+        if ((rc = a16 ? conv(E.qkv, Xs, nullptr, nullptr, ws.wide, 1.f) : conv(E.qkv, x3 ? Xs : X, nullptr, ws.wide, nullptr)) != HIFICAR_OK) return rc;
+        if (a16) {
+            XfmrAttn16Params p;
+            p.qkv = reinterpret_cast<const char*>(ws.wide);
+            p.emb_hi = E.d_emb16;
+            p.emb_lo = E.d_emb16 + (size_t)kXfmrHeads * kXfmrTabPad * d;
+            p.lengths = lengths;
+            p.out = reinterpret_cast<char*>(ws.r[1]);
+            p.T = T;
+            p.F = F;
+            p.scale = (float)(1.0 / std::sqrt((double)d));
+            ProfScope prof(h, stream, "xfmr_attn16_kernel", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
+            const hipError_t e = xfmr_attn16_launch(d, p, dim3((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B), stream);
+            if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn16_kernel launch failed: %s", hipGetErrorString(e));
+        } else {
             XfmrAttnParams p;
             p.qkv = ws.wide;
             p.emb = E.d_emb;

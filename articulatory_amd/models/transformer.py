@@ -28,6 +28,12 @@ in the conv engine's bf16x3 kernels (x w ~ hi hi + hi lo + lo hi on bf16 MFMAs, 
 additions and the residual stream stay fp32.  Inference only: a train()-mode forward of a bf16x3 model is refused.  Unlike
 ``HiFiGANGenerator`` the constructor does not read ``$HIFICAR_PRECISION``: the arithmetic of this model is chosen by keyword only.
 
+``precision="bf16x3a"`` (opt-in, this model only) is ``"bf16x3"`` with the attention's three products — Q K^T, the relative-position product
+Q E^T and P V — as hi hi + hi lo + lo hi on bf16 MFMAs as well, in a kernel of its own (``xfmr_attn16_kernel``) that reads q | k | v as split
+rows and position tables split when the handle is built; the softmax itself, LayerNorm and the additions stay fp32.  Every bf16x3 rule holds:
+inference only, keyword or ``set_precision`` only, kept by copies and ``load_state_dict``, not part of the ``state_dict``.  The generators
+refuse the value.
+
 ``train_precision="bf16x3"`` (opt-in, keyword or ``set_train_precision``; ``"f32"`` is the default and unchanged) is the training step's
 own switch, on a ``precision="f32"`` model: every forward GEMM of ``forward`` / ``forward_padded`` (packed or not) in train() mode and every
 data gradient runs in the bf16x3 kernels, on weight fragments packed on the device after every optimizer step; weight and bias gradients,
@@ -35,7 +41,7 @@ the attention, the norms, dropout (the same masks) and the tape stay fp32, and s
 ``train_precision="bf16x3w"`` is that step with, in addition, the weight gradients of the one-tap layers at least 128 x 128 wide (``w_raw_in``,
 q | k | v, ``w_o``, ``linear1``, ``linear2``) as G^T A ~ hi^T hi + hi^T lo + lo^T hi on bf16 MFMAs, and their bias gradients as the fp32 sum of
 hi + lo; the k = 3 ResBlock convs, ``residual_path`` and ``w_out`` keep exact fp32 weight gradients.  ``precision="bf16x3w"`` is a ValueError.
-Not built: bf16x3 weight gradients of the k = 3 convs, bf16 MFMAs in the attention.
+Not built: bf16x3 weight gradients of the k = 3 convs, bf16 MFMAs in the training step's attention.
 
 Not built, refused with ``NotImplementedError``: ``extra_art=True`` and ``num_ph`` (phoneme input).  ``forward(lengths=...)`` in train() mode
 is refused too (ragged training is asked for by name: ``forward_padded``).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size``
@@ -187,19 +193,19 @@ class _TransformerFunction(torch.autograd.Function):
 class _PrecisionKeyword(type):
     """``Transformer(..., precision=None)``: this package's one constructor keyword beyond the reference's, taken by the class call so that
     ``Transformer.__init__`` keeps the reference's signature, keyword for keyword (drop-in code inspects it).  None: "f32" —
-    ``$HIFICAR_PRECISION`` is deliberately not consulted (see the module's docstring); anything but "f32" / "bf16x3": ValueError."""
+    ``$HIFICAR_PRECISION`` is deliberately not consulted (see the module's docstring); anything but "f32" / "bf16x3" / "bf16x3a": ValueError."""
 
     def __call__(cls, *args, precision=None, train_precision=None, **kwargs):
         if precision is None:
             precision = "f32"
-        if precision not in _native.PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(_native.PRECISIONS)}")
+        if precision not in _native.XFMR_PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_native.XFMR_PRECISIONS)}")
         if train_precision is None:
             train_precision = "f32"
         if train_precision not in _native.TRAIN_PRECISIONS:
             raise ValueError(f"train_precision must be one of {sorted(_native.TRAIN_PRECISIONS)}")
         if precision != "f32" and train_precision != "f32":
-            raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='bf16x3' model is inference-only")
+            raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='{precision}' model is inference-only")
         self = super().__call__(*args, **kwargs)
         self.precision = precision
         self.train_precision = train_precision
@@ -251,14 +257,14 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         watch(self)  # fused optimizers do not bump Parameter._version: every optimizer.step() over these parameters marks them stale
 
     def set_precision(self, precision):
-        """Arithmetic of the following eval-mode forwards: "f32" or "bf16x3".  The native handle holds the weight fragments of one
+        """Arithmetic of the following eval-mode forwards: "f32", "bf16x3" or "bf16x3a".  The native handle holds the weight fragments of one
         arithmetic only, so a change drops it: the next forward builds a new handle from the parameters' host copies
         (hificar_xfmr_set_precision between create and finalize).  A model that has just trained in fp32 can therefore be switched to
         bf16x3 for evaluation, at the cost of one trip of its weights through the host (and one more to switch back)."""
-        if precision not in _native.PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(_native.PRECISIONS)}")
+        if precision not in _native.XFMR_PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_native.XFMR_PRECISIONS)}")
         if precision != "f32" and self.train_precision != "f32":
-            raise ValueError("precision='bf16x3' is inference-only: set_train_precision('f32') first")
+            raise ValueError(f"precision='{precision}' is inference-only: set_train_precision('f32') first")
         if precision != self.precision:
             self.precision = precision
             self._invalidate()
@@ -273,7 +279,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         if train_precision not in _native.TRAIN_PRECISIONS:
             raise ValueError(f"train_precision must be one of {sorted(_native.TRAIN_PRECISIONS)}")
         if train_precision != "f32" and self.precision != "f32":
-            raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='bf16x3' model is inference-only")
+            raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='{self.precision}' model is inference-only")
         if train_precision == self.train_precision:
             return
         self.train_precision = train_precision
@@ -451,7 +457,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                     shape = (ctypes.c_int64 * t.dim())(*t.shape)
                     _native.check(lib.hificar_xfmr_set_weight(handle, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim()),
                                   "hificar_xfmr_set_weight")
-                _native.check(lib.hificar_xfmr_set_precision(handle, _native.PRECISIONS[self.precision]), "hificar_xfmr_set_precision")
+                _native.check(lib.hificar_xfmr_set_precision(handle, _native.XFMR_PRECISIONS[self.precision]), "hificar_xfmr_set_precision")
                 _native.check(lib.hificar_xfmr_finalize(handle), "hificar_xfmr_finalize")
                 if self.precision == "f32":  # (a bf16x3 inference handle has no training arithmetic to choose)
                     _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.TRAIN_PRECISIONS[self.train_precision]),

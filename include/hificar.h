@@ -73,6 +73,9 @@ extern "C" {
 #define HIFICAR_PREC_BF16X3 1      /* fp32 operands split hi+lo bf16, 3 bf16 MFMAs, fp32 accumulate */
 #define HIFICAR_PREC_BF16X3W 2     /* hificar_xfmr_set_train_precision ONLY: bf16x3, and the one-tap GEMM-form weight gradients in it too;
                                       every other entry point that takes a precision refuses it (HIFICAR_E_INVALID) */
+#define HIFICAR_PREC_BF16X3A 3     /* hificar_xfmr_set_precision ONLY: bf16x3, and the attention's three products on bf16 MFMAs too
+                                      (v_mfma_f32_16x16x32_bf16, hi hi + hi lo + lo hi, fp32 accumulate; inference only); every other entry
+                                      point that takes a precision refuses it (HIFICAR_E_INVALID) */
 
 typedef struct hificar_handle hificar_handle;
 /* The conv engine every model of the library launches through (plans, schedules, stream ordering, profiling).  A generator handle
@@ -638,8 +641,12 @@ int hificar_bigru_backward(hificar_bigru* h, const float* dout, int B, int T, co
  * Exact fp32 by default.  Opt-in bf16x3 (hificar_xfmr_set_precision, inference only): every GEMM — the ResBlock convs and residual_path,
  * w_raw_in, q | k | v, w_o, linear1, linear2, w_out — runs in the conv engine's bf16x3 kernels (x w ~ hi hi + hi lo + lo hi on bf16 MFMAs, fp32
  * accumulation); the attention, LayerNorm, bias and residual additions and the residual stream stay fp32.  The training step has the same
- * opt-in for its forward GEMMs and data gradients (hificar_xfmr_set_train_precision, below).  Not built: the attention's products on bf16
- * MFMAs, bf16x3 weight-gradient kernels.
+ * opt-in for its forward GEMMs and data gradients (hificar_xfmr_set_train_precision, below).
+ * Opt-in bf16x3a (HIFICAR_PREC_BF16X3A, inference only): bf16x3, and the attention's three products (Q K^T, Q E^T, P V) as hi hi + hi lo + lo hi
+ * on v_mfma_f32_16x16x32_bf16 as well, in a kernel of its own (xfmr_attn16_kernel) that reads q | k | v as split rows — the q | k | v GEMM
+ * writes nothing else — and position tables split once at finalize; softmax, LayerNorm, additions and the residual stream stay fp32.  Such a
+ * handle is a bf16x3 handle everywhere else: the same workspace, the same refusals.
+ * Not built: bf16 MFMAs in the training step's attention (forward and backward), bf16x3 weight-gradient kernels of the k = 3 convs.
  * Errors as everywhere: a negative HIFICAR_E_* code and hificar_last_error().
  * --------------------------------------------------------------------------------------------------------------------------- */
 #define HIFICAR_XFMR_MAX_IN 4096
@@ -668,7 +675,8 @@ int hificar_xfmr_create(const hificar_xfmr_config* cfg, hificar_xfmr** out);
  * "w_out.bias".  F = hidden_dim, d = F / 8.  data: HOST pointer to contiguous fp32; the caller keeps ownership. */
 int hificar_xfmr_set_weight(hificar_xfmr* h, const char* name, const float* data, const int64_t* shape, int ndim);
 
-/* The arithmetic of the handle's GEMMs: HIFICAR_PREC_F32 (the default) or HIFICAR_PREC_BF16X3.  Legal between hificar_xfmr_create and
+/* The arithmetic of the handle's GEMMs: HIFICAR_PREC_F32 (the default), HIFICAR_PREC_BF16X3, or HIFICAR_PREC_BF16X3A (bf16x3 with the
+ * attention on bf16 MFMAs too; whatever is said of a bf16x3 handle below holds for it).  Legal between hificar_xfmr_create and
  * hificar_xfmr_finalize only (HIFICAR_E_STATE afterwards): finalize packs the weight fragments of the chosen arithmetic alone and drops the host
  * tensors.  An unknown value: HIFICAR_E_INVALID.  Touches no device.  A bf16x3 handle serves hificar_xfmr_forward; every training entry point
  * and hificar_xfmr_set_parameters_device refuse it with HIFICAR_E_STATE (bf16x3 training is an f32 handle's

@@ -21,6 +21,14 @@ f32_over_bf16x3 (fastest f32 window over slowest bf16x3 window: the conservative
 below the fastest f32 window by more than the two legs' window spreads added — the bf16x3 forward's error against the stock result,
 and its own per-kernel table (bf16x3_kernels_ms) with the attention's and the GEMMs' shares.
 
+   python tools/transformer_bench.py --precision bf16x3a [--out profiles/transformer_bf16x3a.txt]
+
+--precision bf16x3a: the bf16x3 leg above AND one more, precision="bf16x3a" (the attention's products on bf16 MFMAs too, xfmr_attn16_kernel),
+alternated native-f32 / native-bf16x3 / native-bf16x3a / stock, two windows each, in the same process: its yardstick is the bf16x3 leg of
+the same run.  The line carries bf16x3a_ms, bf16x3_over_bf16x3a (fastest bf16x3 window over slowest bf16x3a window), bf16x3a_faster (the
+slowest bf16x3a window is below the fastest bf16x3 window by more than the two legs' window spreads added), the error against the stock
+result, the bf16x3a forward's per-kernel table, and per leg the profiled attention time and its share of the forward (attn_ms).
+
    python tools/transformer_bench.py --train [--shapes 8x200 32x500] [--out profiles/transformer_train.txt]
 
 --train: one training step (forward in train() mode, dropout 0.2 + L1 loss + backward + fused Adam) at the same default size, per shape B x T,
@@ -376,7 +384,8 @@ def main():
     ap.add_argument("--frames", type=int, default=2000)
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--no-stock", action="store_true")
-    ap.add_argument("--precision", choices=("f32", "bf16x3"), default="f32", help="bf16x3: add the bf16x3 leg to the native / stock alternation")
+    ap.add_argument("--precision", choices=("f32", "bf16x3", "bf16x3a"), default="f32",
+                    help="bf16x3: add the bf16x3 leg to the native / stock alternation; bf16x3a: that leg and the bf16x3a leg")
     ap.add_argument("--train-precision", choices=("f32", "bf16x3", "bf16x3w"), default="f32",
                     help="--train: bf16x3 adds the bf16x3 training leg(s); bf16x3w adds those and the bf16x3w leg(s)")
     ap.add_argument("--out", default=None)
@@ -396,10 +405,15 @@ def main():
     native.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
     native = native.eval().cuda()
     fast = None
-    if a.precision == "bf16x3":
+    fasta = None
+    if a.precision in ("bf16x3", "bf16x3a"):
         fast = Transformer(**PARAMS, precision="bf16x3")
         fast.load_state_dict(native.state_dict(), strict=True)
         fast = fast.eval().cuda()
+    if a.precision == "bf16x3a":
+        fasta = Transformer(**PARAMS, precision="bf16x3a")
+        fasta.load_state_dict(native.state_dict(), strict=True)
+        fasta = fasta.eval().cuda()
     stock = None if a.no_stock else TransformerOracle(sd, dtype=torch.float32, device="cuda").forward
     lines = []
     with torch.no_grad():
@@ -419,12 +433,22 @@ def main():
                     res["bf16x3_vs_stock_max_rel"] = float((yf - ys).abs().max() / ys.abs().max())
                 for _ in range(2):
                     fast(x)
+            if fasta is not None:
+                ya = fasta(x)
+                res["bf16x3a_vs_f32_max_rel"] = float((ya - y).abs().max() / y.abs().max())
+                res["bf16x3a_vs_bf16x3_max_rel"] = float((ya - yf).abs().max() / y.abs().max())
+                if stock is not None:
+                    res["bf16x3a_vs_stock_max_rel"] = float((ya - ys).abs().max() / ys.abs().max())
+                for _ in range(2):
+                    fasta(x)
             torch.cuda.synchronize()
             n1 = window(native, x, a.window)
             f1 = None if fast is None else window(fast, x, a.window)
+            a1 = None if fasta is None else window(fasta, x, a.window)
             s1 = None if stock is None else window(stock, x, a.window)
             n2 = window(native, x, a.window)
             f2 = None if fast is None else window(fast, x, a.window)
+            a2 = None if fasta is None else window(fasta, x, a.window)
             s2 = None if stock is None else window(stock, x, a.window)
             res["native_ms"] = [round(n1, 4), round(n2, 4)]
             res["native_frames_per_s"] = round(B * T / (min(n1, n2) * 1e-3))
@@ -459,6 +483,25 @@ def main():
                 res["bf16x3_profiled_total_ms"] = round(ftotal, 4)
                 res["bf16x3_attn_share"] = round(fattn / ftotal, 4) if ftotal else None
                 res["bf16x3_gemm_share"] = round(sum(ms for k, (_, ms) in fprof.items() if k.startswith("conv_")) / ftotal, 4) if ftotal else None
+            if fasta is not None:
+                res["bf16x3a_ms"] = [round(a1, 4), round(a2, 4)]
+                res["bf16x3a_frames_per_s"] = round(B * T / (min(a1, a2) * 1e-3))
+                res["bf16x3a_spread"] = round(abs(a1 - a2) / min(a1, a2), 4)
+                res["bf16x3_over_bf16x3a"] = round(min(f1, f2) / max(a1, a2), 3)
+                res["bf16x3a_faster"] = bool(min(f1, f2) - max(a1, a2) > abs(f1 - f2) + abs(a1 - a2))
+                if s1 is not None:
+                    res["stock_over_bf16x3a"] = round(min(s1, s2) / max(a1, a2), 3)
+                aprof = kernel_profile(fasta, x)
+                atotal = sum(ms for _, ms in aprof.values())
+                aattn = aprof.get("xfmr_attn16_kernel", (0, 0.0))[1]
+                res["bf16x3a_kernels_ms"] = {k: round(ms, 4) for k, (_, ms) in sorted(aprof.items())}
+                res["bf16x3a_profiled_total_ms"] = round(atotal, 4)
+                res["bf16x3a_attn_share"] = round(aattn / atotal, 4) if atotal else None
+                res["bf16x3a_gemm_share"] = round(sum(ms for k, (_, ms) in aprof.items() if k.startswith("conv_")) / atotal, 4) if atotal else None
+                # the attention kernel's own profiled time and its share of the forward, per leg
+                res["attn_ms"] = {"f32": [round(attn, 4), res["attn_share"]], "bf16x3": [round(fattn, 4), res["bf16x3_attn_share"]],
+                                  "bf16x3a": [round(aattn, 4), res["bf16x3a_attn_share"]]}
+                res["attn_bf16x3_over_bf16x3a"] = round(fattn / aattn, 3) if aattn else None
             lines.append(json.dumps(res))
             print(lines[-1], flush=True)
     if a.out:
