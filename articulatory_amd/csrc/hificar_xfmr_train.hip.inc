@@ -24,6 +24,9 @@
 // at least 128 x 128: w_raw_in, q | k | v, w_o, linear1, linear2 — in wgrad_bf16x3_kernel on rows xfmr_split_rows_t_kernel splits into two
 // scratch buffers of their own (hificar_xfmr_wgrad16.hip.h); the partials and their reductions are the fp32 form's.  Every other weight
 // gradient (the k = 3 convs, residual_path, w_out) is the fp32 step's.
+// bf16x3wa training (HIFICAR_PREC_BF16X3WA): the bf16x3w step, and the attention's two query-tiled kernels — the forward and the backward's
+// S, dPd and dQ — on bf16 MFMAs (hificar_xfmr_attn16_train.hip.h), on position tables xfmr_split_tab_kernel splits behind every parameter
+// hand-over (xfmr_split_tables); the key-tiled kernels (dK, dV, the table gradient) are the fp32 step's, under a profile row of their own.
 
 struct XfmrTrainLayer {
     ConvLayer dg_qkv, dg_wo, dg_l1, dg_l2;
@@ -85,8 +88,9 @@ static hipError_t xfmr_train_attr() {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_attn_bwd_k_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)XfmrAttnBwdKLds<D>::bytes);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_demb_partial_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)XfmrEmbLds<D>::bytes);
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_demb_partial_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XfmrEmbLds<D>::bytes);
+    if (e != hipSuccess) return e;
+    return xfmr_attn16_train_attr<D>();
 }
 
 template <int D>
@@ -95,13 +99,19 @@ static hipError_t xfmr_attn_train_launch(const XfmrAttnParams& p, dim3 grid, hip
     return hipGetLastError();
 }
 
+// the key-tiled side of the attention backward: dK, dV and the table gradient's partials, from the banded dS and Pd a query-tiled kernel wrote
 template <int D>
-static hipError_t xfmr_attn_bwd_launch(const XfmrAttnBwdParams& p, dim3 grid, float* emb_partial, int M, int chunks, hipStream_t stream) {
-    hipLaunchKernelGGL((xfmr_attn_bwd_q_kernel<D>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
+static hipError_t xfmr_attn_bwd_k_launch(const XfmrAttnBwdParams& p, dim3 grid, float* emb_partial, int M, int chunks, hipStream_t stream) {
     hipLaunchKernelGGL((xfmr_attn_bwd_k_kernel<D>), grid, dim3(256), XfmrAttnBwdKLds<D>::bytes, stream, p);
     hipLaunchKernelGGL((xfmr_demb_partial_kernel<D>), dim3((unsigned)chunks, kXfmrHeads), dim3(256), XfmrEmbLds<D>::bytes, stream, p.qkv, p.ds, emb_partial, M,
                        p.T, p.F, p.hdr, p.lens, p.lay);
     return hipGetLastError();
+}
+
+template <int D>
+static hipError_t xfmr_attn_bwd_launch(const XfmrAttnBwdParams& p, dim3 grid, float* emb_partial, int M, int chunks, hipStream_t stream) {
+    hipLaunchKernelGGL((xfmr_attn_bwd_q_kernel<D>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
+    return xfmr_attn_bwd_k_launch<D>(p, grid, emb_partial, M, chunks, stream);
 }
 
 static int xfmr_alloc(hificar_engine* h, size_t bytes, void** out) {
@@ -113,9 +123,12 @@ static int xfmr_alloc(hificar_engine* h, size_t bytes, void** out) {
     return HIFICAR_OK;
 }
 
-static bool xfmr_train_x3(const hificar_xfmr* g) { return g->train_precision != HIFICAR_PREC_F32; }  // bf16x3 or bf16x3w: the same forward and packs
+static bool xfmr_train_x3(const hificar_xfmr* g) { return g->train_precision != HIFICAR_PREC_F32; }  // bf16x3, bf16x3w or bf16x3wa: the same GEMMs and packs
+static bool xfmr_train_w(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3W || g->train_precision == HIFICAR_PREC_BF16X3WA; }
+static bool xfmr_train_a(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WA; }  // the attention's query-tiled kernels on bf16 MFMAs
 static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts);
 static int xfmr_repack(hificar_xfmr* g, hipStream_t stream);
+static int xfmr_split_tables(hificar_xfmr* g, hipStream_t stream);
 static size_t xfmr_pack16_bytes(const ConvLayer& L);
 
 // bf16 fragment buffers of every layer XfmrTrainCtx::conv launches (the layers' fp32 twins stay as they are), once
@@ -442,6 +455,27 @@ static int xfmr_repack(hificar_xfmr* g, hipStream_t stream) {
         for (const char* nm : {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"})
             HIP_TRY(hipMemcpyAsync(L.d_ln[i++], at(b + nm), (size_t)F * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
+    if (xfmr_train_a(g)) return xfmr_split_tables(g, stream);
+    return HIFICAR_OK;
+}
+
+// bf16x3wa: every layer's position table as the attention's MFMA operand ([hi, lo][8][208][d] bf16, rows 199 .. 207 zeros), from the
+// handle's fp32 copy, on `stream` — behind every parameter hand-over (xfmr_repack) and behind a switch to this arithmetic
+static int xfmr_split_tables(hificar_xfmr* g, hipStream_t stream) {
+    hificar_engine* h = &g->eng;
+    const int d = g->cfg.hidden_dim / kXfmrHeads;
+    const size_t n = (size_t)kXfmrHeads * kXfmrTabPad * d;
+    for (XfmrEncLayer& L : g->enc) {
+        if (!L.d_emb16) {
+            void* p = nullptr;
+            const int rc = xfmr_alloc(h, 2 * n * sizeof(uint16_t), &p);
+            if (rc != HIFICAR_OK) return rc;
+            L.d_emb16 = static_cast<uint16_t*>(p);
+        }
+        ProfScope prof(h, stream, "xfmr_split_tab_kernel", 0.0, 8.0 * n);
+        hipLaunchKernelGGL(xfmr_split_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, L.d_emb, L.d_emb16, L.d_emb16 + n, d);
+        HIP_TRY(hipGetLastError());
+    }
     return HIFICAR_OK;
 }
 
@@ -449,14 +483,15 @@ static int xfmr_repack(hificar_xfmr* g, hipStream_t stream) {
 // records the choice.  Afterwards the packs of the new arithmetic are rebuilt from the master copy, behind the handle's last call.
 extern "C" int hificar_xfmr_set_train_precision(hificar_xfmr* g, int precision) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_train_precision: null handle");
-    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3W)
+    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3W && precision != HIFICAR_PREC_BF16X3WA)
         return fail(HIFICAR_E_INVALID, "unknown training precision %d", precision);
     if (g->precision != HIFICAR_PREC_F32)
         return fail(HIFICAR_E_STATE, "this Transformer handle is packed for the %s inference arithmetic: it has no training step, in either arithmetic",
                     xfmr_precision_name(g->precision));
     if (precision == g->train_precision) return HIFICAR_OK;
-    // (bf16x3 <-> bf16x3w: the same packs, another weight-gradient kernel)
-    if (!g->train || !g->train->have_params || (precision != HIFICAR_PREC_F32 && xfmr_train_x3(g))) {
+    // (among bf16x3, bf16x3w and bf16x3wa: the same packs, other weight-gradient or attention kernels; towards bf16x3wa the tables are split)
+    const bool same_packs = precision != HIFICAR_PREC_F32 && xfmr_train_x3(g);
+    if (!g->train || !g->train->have_params || (same_packs && precision != HIFICAR_PREC_BF16X3WA)) {
         g->train_precision = precision;
         return HIFICAR_OK;
     }
@@ -466,7 +501,7 @@ extern "C" int hificar_xfmr_set_train_precision(hificar_xfmr* g, int precision) 
     if (rc != HIFICAR_OK) return rc;
     const int before = g->train_precision;
     g->train_precision = precision;
-    if ((rc = xfmr_repack(g, stream)) != HIFICAR_OK) g->train_precision = before;
+    if ((rc = same_packs ? xfmr_split_tables(g, stream) : xfmr_repack(g, stream)) != HIFICAR_OK) g->train_precision = before;
     return rc;
 }
 
@@ -615,8 +650,8 @@ static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void*
     w.light = reinterpret_cast<char*>(take(xfmr_plan_tape(g, B, T, nullptr, Mp).bytes));
     // (last: everything in front of it lies where the fp32 arithmetic has it)
     w.split = xfmr_train_x3(g) ? reinterpret_cast<char*>(take(rows * kXfmrFF * 4)) : nullptr;
-    for (char*& s : w.split_t)  // (behind it: a bf16x3 workspace is a prefix of the bf16x3w one)
-        s = g->train_precision == HIFICAR_PREC_BF16X3W ? reinterpret_cast<char*>(take((size_t)split_t_bytes((long long)rows, kXfmrFF))) : nullptr;
+    for (char*& s : w.split_t)  // (behind it: a bf16x3 workspace is a prefix of the bf16x3w one; bf16x3wa's is bf16x3w's)
+        s = xfmr_train_w(g) ? reinterpret_cast<char*>(take((size_t)split_t_bytes((long long)rows, kXfmrFF))) : nullptr;
     w.bytes = off;
     return w;
 }
@@ -730,7 +765,7 @@ struct XfmrTrainCtx {
         return HIFICAR_OK;
     }
     int wgrad(const ConvLayer& L, const float* gr, int gpitch, const float* a, int apitch, float* dW, float* db) const {
-        if (g->train_precision == HIFICAR_PREC_BF16X3W && wgrad_gemm_form(L)) {  // bf16x3w: the one-tap GEMM form on bf16 MFMAs
+        if (xfmr_train_w(g) && wgrad_gemm_form(L)) {  // bf16x3w, bf16x3wa: the one-tap GEMM form on bf16 MFMAs
             if (!ws->split_t[0] || !ws->split_t[1] || gpitch > kXfmrFF || apitch > kXfmrFF) return fail(HIFICAR_E_INVALID, "internal: bf16x3w weight gradient of %s", L.name.c_str());
             int rc;
             if ((rc = split_rows_t(gr, gpitch, ws->split_t[0])) != HIFICAR_OK || (rc = split_rows_t(a, apitch, ws->split_t[1])) != HIFICAR_OK) return rc;
@@ -951,10 +986,21 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
             p.site = 4 * l;
             p.row0 = tp.row0;
             XT(cx.zero_gaps(L.o, F));
-            ProfScope prof(h, stream, "xfmr_attn_kernel<train>", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
             const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B);
-            const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_train_launch, d, p, grid, stream);
-            if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn_kernel launch failed: %s", hipGetErrorString(e));
+            if (xfmr_train_a(g)) {  // bf16x3wa: the same statements on bf16 MFMAs, the tables as xfmr_split_tables left them
+                if (!E.d_emb16) return fail(HIFICAR_E_INVALID, "internal: bf16x3wa forward without split position tables");
+                XfmrAttn16TrainParams p16;
+                p16.f = p;
+                p16.emb_hi = E.d_emb16;
+                p16.emb_lo = E.d_emb16 + (size_t)kXfmrHeads * kXfmrTabPad * d;
+                ProfScope prof(h, stream, "xfmr_attn16_kernel<train>", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
+                const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn16_train_launch, d, p16, grid, stream);
+                if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn16_train_kernel launch failed: %s", hipGetErrorString(e));
+            } else {
+                ProfScope prof(h, stream, "xfmr_attn_kernel<train>", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
+                const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_train_launch, d, p, grid, stream);
+                if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn_kernel launch failed: %s", hipGetErrorString(e));
+            }
         }
         XT(cx.conv(E.wo, L.o, nullptr, ws.t1, nullptr));
         XT(cx.add_drop(X, ws.t1, L.p1, 4 * l + 1));
@@ -1146,11 +1192,27 @@ static int xfmr_backward_impl(hificar_xfmr* g, const float* dout, int B, int T, 
             p.lay = cx.lay;
             XT(cx.zero_gaps(ws.gw, 3 * F));
             const int chunks = (M + kXfmrEmbRows - 1) / kXfmrEmbRows;
-            // S, dP, dQ (K and E parts), dK, dV, dE: six banded products of 2 M F 199 flops each
-            ProfScope prof(h, stream, "xfmr_attn_bwd_kernels", 2.0 * M * F * 7 * kXfmrTab, 4.0 * M * (8.0 * F + 4.0 * kXfmrHeads * kXfmrBand));
             const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B);
-            const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_bwd_launch, d, p, grid, ws.embpart, M, chunks, stream);
-            if (e != hipSuccess) return fail(HIFICAR_E_HIP, "attention backward launch failed: %s", hipGetErrorString(e));
+            if (xfmr_train_a(g)) {  // bf16x3wa: S, dPd and both parts of dQ on bf16 MFMAs; dK, dV, dE in the fp32 kernels, on the same banded buffers
+                if (!L.d_emb16) return fail(HIFICAR_E_INVALID, "internal: bf16x3wa backward without split position tables");
+                XfmrAttn16BwdParams p16;
+                p16.b = p;
+                p16.emb_hi = L.d_emb16;
+                p16.emb_lo = L.d_emb16 + (size_t)kXfmrHeads * kXfmrTabPad * d;
+                {
+                    ProfScope prof(h, stream, "xfmr_attn16_bwd_q_kernel", 2.0 * M * F * 4 * kXfmrTab, 4.0 * M * (6.0 * F + 2.0 * kXfmrHeads * kXfmrBand));
+                    const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn16_bwd_q_launch, d, p16, grid, stream);
+                    if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn16_bwd_q_kernel launch failed: %s", hipGetErrorString(e));
+                }
+                ProfScope prof(h, stream, "xfmr_attn_bwd_k_kernels", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * (5.0 * F + 3.0 * kXfmrHeads * kXfmrBand));
+                const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_bwd_k_launch, d, p, grid, ws.embpart, M, chunks, stream);
+                if (e != hipSuccess) return fail(HIFICAR_E_HIP, "attention backward launch failed: %s", hipGetErrorString(e));
+            } else {
+                // S, dP, dQ (K and E parts), dK, dV, dE: six banded products of 2 M F 199 flops each
+                ProfScope prof(h, stream, "xfmr_attn_bwd_kernels", 2.0 * M * F * 7 * kXfmrTab, 4.0 * M * (8.0 * F + 4.0 * kXfmrHeads * kXfmrBand));
+                const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_bwd_launch, d, p, grid, ws.embpart, M, chunks, stream);
+                if (e != hipSuccess) return fail(HIFICAR_E_HIP, "attention backward launch failed: %s", hipGetErrorString(e));
+            }
             const int width = kXfmrHeads * kXfmrTab * d;
             hipLaunchKernelGGL(bigru_colreduce_kernel, dim3((unsigned)((width + 255) / 256)), dim3(256), 0, stream, ws.embpart, chunks, width,
                                G(b + "self_attn.relative_positional.embeddings"));

@@ -41,7 +41,11 @@ the attention, the norms, dropout (the same masks) and the tape stay fp32, and s
 ``train_precision="bf16x3w"`` is that step with, in addition, the weight gradients of the one-tap layers at least 128 x 128 wide (``w_raw_in``,
 q | k | v, ``w_o``, ``linear1``, ``linear2``) as G^T A ~ hi^T hi + hi^T lo + lo^T hi on bf16 MFMAs, and their bias gradients as the fp32 sum of
 hi + lo; the k = 3 ResBlock convs, ``residual_path`` and ``w_out`` keep exact fp32 weight gradients.  ``precision="bf16x3w"`` is a ValueError.
-Not built: bf16x3 weight gradients of the k = 3 convs, bf16 MFMAs in the training step's attention.
+``train_precision="bf16x3wa"`` is the bf16x3w step with, in addition, the training attention's query-tiled kernels on bf16 MFMAs: the forward
+(Q K^T, the relative-position product, P V) and the backward's recomputed S, dO V^T and both parts of dQ, as hi hi + hi lo + lo hi with fp32
+accumulation; the softmax statistics, dropout (the same masks), dS itself, dK, dV and the tables' gradient stay fp32, and so does the tape.
+``precision="bf16x3wa"`` is a ValueError.
+Not built: bf16x3 weight gradients of the k = 3 convs, bf16 MFMAs for dK, dV and the tables' gradient.
 
 Not built, refused with ``NotImplementedError``: ``extra_art=True`` and ``num_ph`` (phoneme input).  ``forward(lengths=...)`` in train() mode
 is refused too (ragged training is asked for by name: ``forward_padded``).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size``
@@ -202,8 +206,8 @@ class _PrecisionKeyword(type):
             raise ValueError(f"precision must be one of {sorted(_native.XFMR_PRECISIONS)}")
         if train_precision is None:
             train_precision = "f32"
-        if train_precision not in _native.TRAIN_PRECISIONS:
-            raise ValueError(f"train_precision must be one of {sorted(_native.TRAIN_PRECISIONS)}")
+        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS:
+            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS)}")
         if precision != "f32" and train_precision != "f32":
             raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='{precision}' model is inference-only")
         self = super().__call__(*args, **kwargs)
@@ -275,9 +279,10 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         norms, dropout and the tape stay fp32 (hificar_xfmr_set_train_precision).  The eval-mode forward is exact fp32 either way.  The
         native handle is kept: its packs are rebuilt on the device.  A backward whose forward ran in the other arithmetic is refused
         (RuntimeError).  "bf16x3w": "bf16x3", and the weight and bias gradients of the one-tap layers at least 128 x 128 wide in the same
-        arithmetic (see the module's docstring).  Not with ``precision="bf16x3"`` (ValueError)."""
-        if train_precision not in _native.TRAIN_PRECISIONS:
-            raise ValueError(f"train_precision must be one of {sorted(_native.TRAIN_PRECISIONS)}")
+        arithmetic; "bf16x3wa": "bf16x3w", and the attention's query-tiled kernels on bf16 MFMAs (see the module's docstring).  Not with
+        ``precision="bf16x3"`` (ValueError)."""
+        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS:
+            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS)}")
         if train_precision != "f32" and self.precision != "f32":
             raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='{self.precision}' model is inference-only")
         if train_precision == self.train_precision:
@@ -285,7 +290,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         self.train_precision = train_precision
         if self.__dict__.get("_handle") is not None:
             with torch.cuda.device(self._device()):
-                _native.check(self._lib.hificar_xfmr_set_train_precision(self._handle, _native.TRAIN_PRECISIONS[train_precision]),
+                _native.check(self._lib.hificar_xfmr_set_train_precision(self._handle, _native.XFMR_TRAIN_PRECISIONS[train_precision]),
                               "hificar_xfmr_set_train_precision")
 
     def _refuse_bf16x3_training(self):
@@ -460,7 +465,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                 _native.check(lib.hificar_xfmr_set_precision(handle, _native.XFMR_PRECISIONS[self.precision]), "hificar_xfmr_set_precision")
                 _native.check(lib.hificar_xfmr_finalize(handle), "hificar_xfmr_finalize")
                 if self.precision == "f32":  # (a bf16x3 inference handle has no training arithmetic to choose)
-                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.TRAIN_PRECISIONS[self.train_precision]),
+                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.XFMR_TRAIN_PRECISIONS[self.train_precision]),
                                   "hificar_xfmr_set_train_precision")
             except Exception:
                 lib.hificar_xfmr_destroy(handle)

@@ -76,6 +76,9 @@ extern "C" {
 #define HIFICAR_PREC_BF16X3A 3     /* hificar_xfmr_set_precision ONLY: bf16x3, and the attention's three products on bf16 MFMAs too
                                       (v_mfma_f32_16x16x32_bf16, hi hi + hi lo + lo hi, fp32 accumulate; inference only); every other entry
                                       point that takes a precision refuses it (HIFICAR_E_INVALID) */
+#define HIFICAR_PREC_BF16X3WA 4    /* hificar_xfmr_set_train_precision ONLY: bf16x3w, and the training attention's query-tiled kernels (forward
+                                      and backward-q: seven of its ten banded products) on v_mfma_f32_16x16x32_bf16 too; every other entry
+                                      point that takes a precision refuses it (HIFICAR_E_INVALID) */
 
 typedef struct hificar_handle hificar_handle;
 /* The conv engine every model of the library launches through (plans, schedules, stream ordering, profiling).  A generator handle
@@ -646,7 +649,8 @@ int hificar_bigru_backward(hificar_bigru* h, const float* dout, int B, int T, co
  * on v_mfma_f32_16x16x32_bf16 as well, in a kernel of its own (xfmr_attn16_kernel) that reads q | k | v as split rows — the q | k | v GEMM
  * writes nothing else — and position tables split once at finalize; softmax, LayerNorm, additions and the residual stream stay fp32.  Such a
  * handle is a bf16x3 handle everywhere else: the same workspace, the same refusals.
- * Not built: bf16 MFMAs in the training step's attention (forward and backward), bf16x3 weight-gradient kernels of the k = 3 convs.
+ * Not built: bf16 MFMAs in the training attention's key-tiled backward (dK, dV, the table gradient), bf16x3 weight-gradient kernels of the
+ * k = 3 convs.
  * Errors as everywhere: a negative HIFICAR_E_* code and hificar_last_error().
  * --------------------------------------------------------------------------------------------------------------------------- */
 #define HIFICAR_XFMR_MAX_IN 4096
@@ -726,11 +730,11 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * hificar_xfmr_forward_train_packed computes the same step without GEMM rows for the padding.
  * All of these may be called after hificar_xfmr_finalize; the first one builds the training state.
  * The forward GEMMs and data gradients have an opt-in bf16x3 arithmetic (hificar_xfmr_set_train_precision, below).
- * The one-tap weight gradients have one too (HIFICAR_PREC_BF16X3W).
- * Not built: a smaller tape per frame, bf16x3 weight gradients of the k = 3 convs, bf16 MFMAs in the attention, extra_art, num_ph, multi-GPU training of this model. ---- */
+ * The one-tap weight gradients have one too (HIFICAR_PREC_BF16X3W), and so have the attention's query-tiled kernels (HIFICAR_PREC_BF16X3WA).
+ * Not built: a smaller tape per frame, bf16x3 weight gradients of the k = 3 convs, dK / dV / the table gradient on bf16 MFMAs, extra_art, num_ph, multi-GPU training of this model. ---- */
 
-/* The arithmetic of the training step's GEMMs: HIFICAR_PREC_F32 (the default: the step above, bit for bit), HIFICAR_PREC_BF16X3 or
- * HIFICAR_PREC_BF16X3W.
+/* The arithmetic of the training step's GEMMs: HIFICAR_PREC_F32 (the default: the step above, bit for bit), HIFICAR_PREC_BF16X3,
+ * HIFICAR_PREC_BF16X3W or HIFICAR_PREC_BF16X3WA.
  * bf16x3: every forward GEMM of hificar_xfmr_forward_train / _ragged / _packed (the six ResBlock convs and residual_path, w_raw_in,
  * q | k | v, w_o, linear1, linear2, w_out) and every data gradient of the same layers runs as x w ~ hi hi + hi lo + lo hi on bf16 MFMAs with
  * fp32 accumulation, in the conv engine's bf16x3 kernels (hi = bf16(x), lo = bf16(x - hi), round to nearest even; split-K off: one
@@ -746,6 +750,15 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * fp32 sum of hi + lo over the rows.  Deterministic (fixed summation order, no atomics).  Every other weight and bias gradient — the k = 3
  * ResBlock convs, residual_path, w_out, anything narrower than 128 — stays on the exact fp32 kernels.  The workspace grows by two more
  * buffers (the split G and A rows, 3072 columns each) behind the bf16x3 one.  bf16x3 <-> bf16x3w rebuilds nothing.
+ * bf16x3wa: the bf16x3w step, bit for bit in every launch outside the attention, with the attention's two query-tiled kernels on
+ * v_mfma_f32_16x16x32_bf16 (hi hi + hi lo + lo hi, fp32 accumulation, operands split as above).  Forward (dense, ragged, packed): S^T = K Q^T,
+ * the positional product E Q^T and O^T += V^T Pd^T; softmax statistics, the online rescale, L = m + log l and the division by l stay fp32, the
+ * dropout factor (the same element index, so the same masks) is applied to the kept probabilities before P V.  Backward: S recomputed with the
+ * forward's own MFMA sequence, dPd^T = V dO^T and both parts of dQ (K^T dS^T, E^T dS^T) in the same form; Delta, the exponential and dS stay
+ * fp32, and dS and Pd go to the same banded fp32 buffers, which the key-tiled kernels (dK, dV, the table gradient: exact fp32, unchanged)
+ * read.  The tape keeps fp32 q | k | v, O and lse rows (its size does not change): a fetched key block is split on its way into LDS.  The
+ * position tables are split on the device behind every parameter hand-over (8 x 208 x d bf16, twice, per layer; handle state, no workspace).
+ * bf16x3w <-> bf16x3wa rebuilds no weight pack (towards bf16x3wa the tables are split).
  * Legal at any time on an f32 handle, also after hificar_xfmr_finalize and between steps: once parameters have been handed over, the packs of
  * the new arithmetic are rebuilt from the handle's device copy, in stream order behind the handle's last call.  A handle whose
  * hificar_xfmr_set_precision is bf16x3 (inference only): HIFICAR_E_STATE.  An unknown value: HIFICAR_E_INVALID.

@@ -62,6 +62,15 @@ all in the same alternation: its yardsticks are the f32 and bf16x3 legs of the s
 bf16x3_over_bf16x3w (fastest bf16x3 window over slowest bf16x3w window), bf16x3w_faster (the slowest bf16x3w window is below the fastest
 bf16x3 window by more than the two spreads added), the bf16x3w step's per-kernel table and wgrad_bf16x3_mfma_share: the bf16 MFMA issue
 time of the new kernel's launches at the peak rate over their measured time.
+
+   python tools/transformer_bench.py --train --train-precision bf16x3wa [--ragged] [--out profiles/transformer_train_bf16x3wa.txt]
+
+--train-precision bf16x3wa: the bf16x3 and bf16x3w leg(s) above AND one more, train_precision="bf16x3wa" (the training attention's
+query-tiled kernels on bf16 MFMAs too), in the same alternation: its yardstick is the bf16x3w leg of the same run.  The line carries
+bf16x3wa_ms, bf16x3w_over_bf16x3wa (fastest bf16x3w window over slowest bf16x3wa window), bf16x3wa_faster (the slowest bf16x3wa window is
+below the fastest bf16x3w window by more than the two spreads added), the bf16x3wa step's per-kernel table and attention_ms: the forward
+(xfmr_attn16_kernel<train> against xfmr_attn_kernel<train>), the backward (xfmr_attn16_bwd_q_kernel + xfmr_attn_bwd_k_kernels against
+xfmr_attn_bwd_kernels) and the tables' split (xfmr_split_tab_kernel, a cost) of the two legs' profiled steps.
 Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
 import argparse
 import ctypes
@@ -111,6 +120,15 @@ def kernel_profile(m, x):
     return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(n.value)}
 
 
+def attention_rows(pw, pa):
+    """The attention's rows of a bf16x3w step's profile (pw) beside a bf16x3wa step's (pa): forward, backward, and the tables' split as a cost."""
+    g = lambda prof, k: round(prof.get(k, 0.0), 4)  # noqa: E731
+    return {"forward": {"bf16x3w xfmr_attn_kernel<train>": g(pw, "xfmr_attn_kernel<train>"), "bf16x3wa xfmr_attn16_kernel<train>": g(pa, "xfmr_attn16_kernel<train>")},
+            "backward": {"bf16x3w xfmr_attn_bwd_kernels": g(pw, "xfmr_attn_bwd_kernels"), "bf16x3wa xfmr_attn16_bwd_q_kernel": g(pa, "xfmr_attn16_bwd_q_kernel"),
+                         "bf16x3wa xfmr_attn_bwd_k_kernels": g(pa, "xfmr_attn_bwd_k_kernels")},
+            "cost": {"bf16x3wa xfmr_split_tab_kernel": g(pa, "xfmr_split_tab_kernel")}}
+
+
 def train_main(a):
     import torch.nn.functional as F
 
@@ -140,6 +158,7 @@ def train_main(a):
     s_opt = torch.optim.Adam(list(stock.params.values()), lr=1e-4, fused=True)
     fast = f_opt = None
     fastw = w_opt = None
+    fastwa = wa_opt = None
 
     def leg(arith):
         m = Transformer(dropout=p, train_precision=arith, **PARAMS)
@@ -147,10 +166,12 @@ def train_main(a):
         m = m.cuda().train()
         return m, torch.optim.Adam(m.parameters(), lr=1e-4, fused=True)
 
-    if a.train_precision in ("bf16x3", "bf16x3w"):
+    if a.train_precision in ("bf16x3", "bf16x3w", "bf16x3wa"):
         fast, f_opt = leg("bf16x3")
-    if a.train_precision == "bf16x3w":
+    if a.train_precision in ("bf16x3w", "bf16x3wa"):
         fastw, w_opt = leg("bf16x3w")
+    if a.train_precision == "bf16x3wa":
+        fastwa, wa_opt = leg("bf16x3wa")
 
     def profile_step(m, opt):
         """{kernel: ms} of one step: the parameter hand-over behind the optimizer step before it, forward and backward."""
@@ -191,20 +212,29 @@ def train_main(a):
             F.l1_loss(fastw(x), y).backward()
             w_opt.step()
 
+        def fastwa_step(_):
+            wa_opt.zero_grad(set_to_none=True)
+            F.l1_loss(fastwa(x), y).backward()
+            wa_opt.step()
+
         for _ in range(2):
             native_step(None), stock_step(None)
             if fast is not None:
                 fast_step(None)
             if fastw is not None:
                 fastw_step(None)
+            if fastwa is not None:
+                fastwa_step(None)
         torch.cuda.synchronize()
         n1 = window(native_step, None, a.window)
         f1 = None if fast is None else window(fast_step, None, a.window)
         w1 = None if fastw is None else window(fastw_step, None, a.window)
+        a1 = None if fastwa is None else window(fastwa_step, None, a.window)
         s1 = window(stock_step, None, a.window)
         n2 = window(native_step, None, a.window)
         f2 = None if fast is None else window(fast_step, None, a.window)
         w2 = None if fastw is None else window(fastw_step, None, a.window)
+        a2 = None if fastwa is None else window(fastwa_step, None, a.window)
         s2 = window(stock_step, None, a.window)
         res = {"train": True, "B": B, "T": T, "dropout": p, "native_ms": [round(n1, 3), round(n2, 3)], "stock_ms": [round(s1, 3), round(s2, 3)],
                "native_spread": round(abs(n1 - n2) / min(n1, n2), 4), "stock_spread": round(abs(s1 - s2) / min(s1, s2), 4),
@@ -250,6 +280,16 @@ def train_main(a):
             wflops = sum(v for k, v in profile_step.flops.items() if k.startswith("wgrad_bf16x3"))
             wms = fam(pw, "wgrad_bf16x3")
             res["wgrad_bf16x3_mfma_share"] = round(3.0 * wflops / (BF16_PEAK_TFLOPS * 1e12) / (wms * 1e-3), 4) if wms else None
+        if fastwa is not None:
+            res["bf16x3wa_ms"] = [round(a1, 3), round(a2, 3)]
+            res["bf16x3wa_spread"] = round(abs(a1 - a2) / min(a1, a2), 4)
+            res["bf16x3w_over_bf16x3wa"] = round(min(w1, w2) / max(a1, a2), 3)
+            res["bf16x3wa_faster"] = bool(min(w1, w2) - max(a1, a2) > abs(w1 - w2) + abs(a1 - a2))
+            pa = profile_step(fastwa, wa_opt)
+            res["bf16x3wa_kernels_ms"] = {k: round(v, 4) for k, v in sorted(pa.items(), key=lambda kv: -kv[1])}
+            for pre in ("conv", "wgrad", "wreduce", "xfmr_attn", "xfmr_split_rows", "pack16", "xfmr_", "xfmr_split_rows_t"):
+                res["families_ms"][pre]["bf16x3wa"] = fam(pa, pre)
+            res["attention_ms"] = attention_rows(pw, pa)
         lines.append(json.dumps(res))
         print(lines[-1], flush=True)
     if a.out:
@@ -289,7 +329,7 @@ def ragged_train_main(a):
 
     legs = {"native_packed": make(lambda: masked_l1_loss(m.forward_padded(x, lens32, packed=True), y, lens32)),
             "native_ragged": make(lambda: masked_l1_loss(m.forward_padded(x, lens32), y, lens32)), "native_dense": make(lambda: F.l1_loss(m(x), y))}
-    ariths = {"bf16x3": ("bf16x3",), "bf16x3w": ("bf16x3", "bf16x3w")}.get(a.train_precision, ())
+    ariths = {"bf16x3": ("bf16x3",), "bf16x3w": ("bf16x3", "bf16x3w"), "bf16x3wa": ("bf16x3", "bf16x3w", "bf16x3wa")}.get(a.train_precision, ())
     fast = {}
     for arith in ariths:  # the same batch through further models in the bf16x3 (and bf16x3w) training arithmetic, padded and packed
         m3 = Transformer(dropout=p, train_precision=arith, **PARAMS)
@@ -339,6 +379,10 @@ def ragged_train_main(a):
             f_, w_ = ms["bf16x3_" + form], ms["bf16x3w_" + form]
             res[f"bf16x3_over_bf16x3w_{form}"] = round(min(f_) / max(w_), 3)
             res[f"bf16x3w_faster_{form}"] = bool(min(f_) - max(w_) > abs(f_[0] - f_[1]) + abs(w_[0] - w_[1]))
+        if "bf16x3wa_" + form in ms:
+            w_, a_ = ms["bf16x3w_" + form], ms["bf16x3wa_" + form]
+            res[f"bf16x3w_over_bf16x3wa_{form}"] = round(min(w_) / max(a_), 3)
+            res[f"bf16x3wa_faster_{form}"] = bool(min(w_) - max(a_) > abs(w_[0] - w_[1]) + abs(a_[0] - a_[1]))
     eng = m.engine()
     profs = {}
     for tag in ("packed", "ragged", "dense"):
@@ -361,6 +405,8 @@ def ragged_train_main(a):
             prof3 = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
             res[f"{arith}_{tag}_kernels_ms"] = {k: round(v, 4) for k, v in sorted(prof3.items(), key=lambda kv: -kv[1])}
             res[f"{arith}_{tag}_kernels_total_ms"] = round(sum(prof3.values()), 3)
+    if "bf16x3wa" in fast:
+        res["attention_ms"] = {tag: attention_rows(res[f"bf16x3w_{tag}_kernels_ms"], res[f"bf16x3wa_{tag}_kernels_ms"]) for tag in ("packed", "ragged")}
     res["attention_recovered_ms"] = {k: round(profs["dense"].get(k, 0.0) - profs["ragged"].get(k, 0.0), 4)
                                      for k in ("xfmr_attn_kernel<train>", "xfmr_attn_bwd_kernels")}
     # packed over ragged per kernel family, to read beside packed_rows_over_padded_rows: conv_* are the forward GEMMs and the data gradients
@@ -386,8 +432,8 @@ def main():
     ap.add_argument("--no-stock", action="store_true")
     ap.add_argument("--precision", choices=("f32", "bf16x3", "bf16x3a"), default="f32",
                     help="bf16x3: add the bf16x3 leg to the native / stock alternation; bf16x3a: that leg and the bf16x3a leg")
-    ap.add_argument("--train-precision", choices=("f32", "bf16x3", "bf16x3w"), default="f32",
-                    help="--train: bf16x3 adds the bf16x3 training leg(s); bf16x3w adds those and the bf16x3w leg(s)")
+    ap.add_argument("--train-precision", choices=("f32", "bf16x3", "bf16x3w", "bf16x3wa"), default="f32",
+                    help="--train: bf16x3 adds the bf16x3 training leg(s); bf16x3w adds those and the bf16x3w leg(s); bf16x3wa those and the bf16x3wa leg(s)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--ragged", action="store_true", help="--train: the ragged batch's two legs instead of the dense shapes")
     ap.add_argument("--seed", type=int, default=0, help="--train --ragged: seed of the lengths")
