@@ -21,6 +21,7 @@ PREC_BF16X3 = 1
 PREC_BF16X3W = 2
 PREC_BF16X3A = 3
 PREC_BF16X3WA = 4
+PREC_BF16X3WAC = 6
 PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}  # the inference arithmetics (``precision=``)
 # ... and the Transformer's training arithmetics (``train_precision=``): bf16x3w = bf16x3 with the one-tap weight gradients in it too
 TRAIN_PRECISIONS = dict(PRECISIONS, bf16x3w=PREC_BF16X3W)
@@ -28,6 +29,8 @@ TRAIN_PRECISIONS = dict(PRECISIONS, bf16x3w=PREC_BF16X3W)
 XFMR_PRECISIONS = dict(PRECISIONS, bf16x3a=PREC_BF16X3A)
 # the Transformer's training arithmetics with bf16x3wa: bf16x3w with the attention's query-tiled kernels (forward, backward-q) on bf16 MFMAs too
 XFMR_TRAIN_PRECISIONS = dict(TRAIN_PRECISIONS, bf16x3wa=PREC_BF16X3WA)
+# ... and with bf16x3wac: bf16x3wa with the weight gradients of the wide k = 3 ResBlock convs on bf16 MFMAs too (what ``train_precision=`` accepts)
+XFMR_TRAIN_PRECISIONS_ALL = dict(XFMR_TRAIN_PRECISIONS, bf16x3wac=PREC_BF16X3WAC)
 
 # every symbol include/hificar.h declares (tests/test_cabi.py checks the .so exports each one)
 SYMBOLS = (
@@ -131,6 +134,7 @@ SYMBOLS = (
     "hificar_xfmr_set_train_precision",
     "hificar_debug_pack16",
     "hificar_debug_split_rows_t",
+    "hificar_debug_split_taps_t",
     "hificar_xfmr_set_parameters_device",
     "hificar_xfmr_grad_count",
     "hificar_xfmr_grad_info",
@@ -531,6 +535,8 @@ def load_library():
     lib.hificar_debug_pack16.restype = ci
     lib.hificar_debug_split_rows_t.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, cs, ctypes.POINTER(cs)]
     lib.hificar_debug_split_rows_t.restype = ci
+    lib.hificar_debug_split_taps_t.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, cs, ctypes.POINTER(cs)]
+    lib.hificar_debug_split_taps_t.restype = ci
     lib.hificar_xfmr_workspace_bytes.argtypes = [vp, ci, ci]
     lib.hificar_xfmr_workspace_bytes.restype = cs
     lib.hificar_xfmr_forward.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]

@@ -487,6 +487,7 @@ struct WreduceParams {
     int accumulate;  // 1: dst += the reduced gradient (a second backward pass into the same buffer) instead of dst = it
     int poly_s, poly_cin;  // poly_s > 0: polyphase-input form of a strided conv (cout, poly_cin, K): (tap q, a = r * poly_cin + c) -> kernel index
                            // poly_s * q + r, dst[(co * poly_cin + c) * K + poly_s * q + r] (indices >= K carry zero weights: skipped)
+    int gemm_pitch;  // > 0 (with gemm_cin, generic kernel only): the taps lie gemm_pitch >= gemm_cin columns apart, a = tap * gemm_pitch + c
 };
 
 struct WreducePair {
@@ -519,7 +520,7 @@ __device__ __forceinline__ void wreduce_body(const WreducePair& pair, int bx, in
             if (k < 0) continue;
         }
         if (co >= p.cout) continue;
-        if (p.gemm_cin > 0 && a >= p.gemm_cin * p.K) continue;
+        if (p.gemm_cin > 0 && a >= (p.gemm_pitch > 0 ? p.gemm_pitch : p.gemm_cin) * p.K) continue;
         const float4* src = reinterpret_cast<const float4*>(partial_p) + i;
         const size_t stride = total / 4;
         float4 s[4];
@@ -544,8 +545,10 @@ __device__ __forceinline__ void wreduce_body(const WreducePair& pair, int bx, in
             if (a + j >= p.cin) break;
             size_t d = p.transposed ? ((size_t)(a + j) * p.cout + co) * p.K + k : ((size_t)co * p.cin + a + j) * p.K + k;
             if (p.gemm_cin > 0) {
-                const int tap = (a + j) / p.gemm_cin, c = (a + j) - tap * p.gemm_cin;
+                const int pitch = p.gemm_pitch > 0 ? p.gemm_pitch : p.gemm_cin;
+                const int tap = (a + j) / pitch, c = (a + j) - tap * pitch;
                 if (tap >= p.K) break;
+                if (c >= p.gemm_cin) continue;
                 d = ((size_t)co * p.gemm_cin + c) * p.K + tap;
             }
             if (p.poly_s > 0) {

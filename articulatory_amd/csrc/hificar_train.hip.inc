@@ -958,6 +958,10 @@ struct WgradJob {
     // both non-null (a wgrad_gemm_form layer, one sequence, one group): g and a as xfmr_split_rows_t_kernel wrote them, gpitch and apitch
     // channels wide; the launch is wgrad_bf16x3_kernel (the Transformer's bf16x3w training arithmetic) and g / a are not read
     const char *g16 = nullptr, *a16 = nullptr;
+    // a k = 3 conv run as its one-tap GEMM twin L (the Transformer's bf16x3wac training arithmetic; with gemm_cin / gemm_kt): the conv itself,
+    // whose shape the profile rows and the FLOP count carry, and the columns from one tap to the next where they are more than gemm_cin
+    const ConvLayer* shape = nullptr;
+    int gemm_pitch = 0;
 };
 
 // Weight (and bias) gradients of n = 1 or 2 layers over the same rows.  Two layers share one launch of each kernel when both take the
@@ -1050,7 +1054,8 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
             return fail(HIFICAR_E_INVALID, "weight gradient of %s: %d taps reaching over %d rows need %zu KB of LDS staging (160 KB per CU); "
                         "kernels this long at this dilation run in inference only", L.name.c_str(), L.ntaps, tp.q[i].halo, lds / 1024);
         const double pos = (double)nseq * rows;
-        flops += 2.0 * pos * L.cin * L.cout * L.K * zg;
+        const ConvLayer& S = jobs[i].shape ? *jobs[i].shape : L;
+        flops += 2.0 * pos * S.cin * S.cout * S.K * zg;
         bytes += 4.0 * pos * (jobs[i].gpitch + jobs[i].apitch) * zg;
 
         WreduceParams& r = rp.r[i];
@@ -1067,7 +1072,8 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
         if (jobs[i].gemm_cin > 0) {
             r.gemm_cin = jobs[i].gemm_cin;
             r.K = jobs[i].gemm_kt;
-            r.cin = jobs[i].gemm_cin * jobs[i].gemm_kt;
+            r.gemm_pitch = jobs[i].gemm_pitch;
+            r.cin = (jobs[i].gemm_pitch > 0 ? jobs[i].gemm_pitch : jobs[i].gemm_cin) * jobs[i].gemm_kt;
         }
         if (jobs[i].poly_s > 0) {
             r.poly_s = jobs[i].poly_s;
@@ -1101,6 +1107,7 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
     }
     {
         const ConvLayer& L = *jobs[0].L;
+        const ConvLayer& S = jobs[0].shape ? *jobs[0].shape : L;
         // the profile row: the kernel's name; with profile_detail the template arguments of the instantiation launched (written by the
         // macro that launches it, from the same arguments), the layer's shape and the launch's split / row split / layer count
         auto kname = [&](const char* kernel, std::initializer_list<int> targs) {
@@ -1112,7 +1119,7 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
                 sep = ",";
             }
             if (targs.size()) s += ">";
-            return s + " " + std::to_string(L.cout) + "x" + std::to_string(L.cin) + "k" + std::to_string(L.K) + "p" + std::to_string(L.n_phase) +
+            return s + " " + std::to_string(S.cout) + "x" + std::to_string(S.cin) + "k" + std::to_string(S.K) + "p" + std::to_string(S.n_phase) +
                    " s" + std::to_string(nsplit) + " r" + std::to_string(tp.q[0].w.row_split) + " n" + std::to_string(n);
         };
         if (gemm && jobs[0].g16) {
@@ -1174,7 +1181,7 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
     // walks all the splits of all its taps one after the other: the small layers with hundreds of splits stay on the generic kernel,
     // measured 3 x slower here): the contiguous-store kernel
     const WreduceParams& r0 = rp.r[0];
-    const bool contiguous = n == 1 && r0.gemm_cin > 0 && r0.gemm_cin % 4 == 0 && (r0.K == 3 || r0.K == 5) && r0.ntaps == 1 &&
+    const bool contiguous = n == 1 && r0.gemm_cin > 0 && r0.gemm_pitch == 0 && r0.gemm_cin % 4 == 0 && (r0.K == 3 || r0.K == 5) && r0.ntaps == 1 &&
                             (long long)r0.cout * (r0.gemm_cin / 4) * zg >= 64LL * 1024 &&
                             (reinterpret_cast<uintptr_t>(r0.dst) & 15) == 0 && (rp.zs_dst[0] & 3) == 0 && (rp.zs_partial[0] & 3) == 0;
     const long long gemm_units = (long long)r0.cout * (r0.gemm_cin / 4);
@@ -1198,7 +1205,7 @@ static int launch_wgrad_n(hificar_engine* h, const WgradJob* jobs, int n, int ns
         const int gemm_k = r0.K == 5 ? 5 : 3;  // the contiguous kernel's instantiation
         std::string rname = "wreduce_kernel";
         if (h->profile_detail) {
-            const ConvLayer& L = *jobs[0].L;
+            const ConvLayer& L = jobs[0].shape ? *jobs[0].shape : *jobs[0].L;
             if (contiguous) rname = "wreduce_gemm_kernel<" + std::to_string(gemm_k) + ">";
             rname += " " + std::to_string(L.cout) + "x" + std::to_string(L.cin) + "k" + std::to_string(L.K) + " s" + std::to_string(nsplit) + " n" + std::to_string(n) + " z" + std::to_string(zg);
         }

@@ -27,6 +27,11 @@
 // bf16x3wa training (HIFICAR_PREC_BF16X3WA): the bf16x3w step, and the attention's two query-tiled kernels — the forward and the backward's
 // S, dPd and dQ — on bf16 MFMAs (hificar_xfmr_attn16_train.hip.h), on position tables xfmr_split_tab_kernel splits behind every parameter
 // hand-over (xfmr_split_tables); the key-tiled kernels (dK, dV, the table gradient) are the fp32 step's, under a profile row of their own.
+// bf16x3wac training (HIFICAR_PREC_BF16X3WAC): the bf16x3wa step, and the weight (and bias) gradient of every k = 3 conv wgrad_gemm3_form selects
+// — conv_blocks.{1,2}.conv1, conv_blocks.{0,1,2}.conv2, and conv_blocks.0.conv1 where the input rows are 128 .. 1024 wide — as the one-tap GEMM
+// G^T A3 in wgrad_bf16x3_kernel: A3's column k cin_pad + c of row r is row r + k - 1 of channel c within the row's own sequence
+// (xfmr_split_taps_t_kernel writes it into the second of bf16x3w's two scratch buffers), the layer's one-tap twin (XfmrTrain::Bn::wg3) gives the
+// launch its tiles and split count, and wreduce's gemm_cin form lays the partial out as (cout, cin, 3).
 
 struct XfmrTrainLayer {
     ConvLayer dg_qkv, dg_wo, dg_l1, dg_l2;
@@ -48,6 +53,7 @@ struct XfmrTrain {
     struct Bn {
         std::string conv, bn;
         ConvLayer raw, dg;
+        ConvLayer wg3;  // wgrad_gemm3_form(raw): the one-tap layer (cout, 3 cin_pad) whose weight gradient is raw's in bf16x3wac; else unplanned (cout 0)
         ConvLayer* folded;
         int64_t off_fw = 0, off_fb = 0;
     };
@@ -124,8 +130,13 @@ static int xfmr_alloc(hificar_engine* h, size_t bytes, void** out) {
 }
 
 static bool xfmr_train_x3(const hificar_xfmr* g) { return g->train_precision != HIFICAR_PREC_F32; }  // bf16x3, bf16x3w or bf16x3wa: the same GEMMs and packs
-static bool xfmr_train_w(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3W || g->train_precision == HIFICAR_PREC_BF16X3WA; }
-static bool xfmr_train_a(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WA; }  // the attention's query-tiled kernels on bf16 MFMAs
+static bool xfmr_train_c(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WAC; }  // the wide k = 3 convs' weight gradients on bf16 MFMAs
+static bool xfmr_train_a(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WA || xfmr_train_c(g); }  // the attention's query-tiled kernels on bf16 MFMAs
+static bool xfmr_train_w(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3W || xfmr_train_a(g); }
+// three taps, one phase, at least 128 x 128, and the three taps' columns side by side fit a split buffer: the one-tap GEMM form on tap-shifted columns
+static bool wgrad_gemm3_form(const ConvLayer& L) {
+    return L.K == 3 && L.ntaps == 3 && L.n_phase == 1 && L.n_blocks32 >= 4 && (L.cin_pad + 31) / 32 >= 4 && 3 * L.cin_pad <= kXfmrFF;
+}
 static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts);
 static int xfmr_repack(hificar_xfmr* g, hipStream_t stream);
 static int xfmr_split_tables(hificar_xfmr* g, hipStream_t stream);
@@ -269,6 +280,11 @@ static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts) {
         bn.raw.d_bias = static_cast<float*>(p);
         if ((rc = make_dgrad_layer(h, bn.raw, bn.dg, nullptr)) != HIFICAR_OK) return rc;
         if (bn.dg.cout_pad != L.cin_pad) return fail(HIFICAR_E_INVALID, "internal: data-gradient rows of %s are %d wide, its input rows %d", bn.conv.c_str(), bn.dg.cout_pad, L.cin_pad);
+        if (wgrad_gemm3_form(bn.raw)) {
+            if ((rc = xfmr_plan(bn.wg3, bn.conv + "#wg3", 3 * L.cin_pad, 3 * L.cin_pad, L.cout, 1)) != HIFICAR_OK) return rc;
+            if (!wgrad_gemm_form(bn.wg3) || !wgrad_gemm_wide(bn.wg3) || bn.wg3.n_blocks32 != bn.raw.n_blocks32)
+                return fail(HIFICAR_E_INVALID, "internal: the one-tap twin of %s", bn.conv.c_str());
+        }
     }
     (void)C;
     if ((rc = make_dgrad_layer(h, g->w_in, ts->dg_win, nullptr)) != HIFICAR_OK) return rc;
@@ -483,15 +499,18 @@ static int xfmr_split_tables(hificar_xfmr* g, hipStream_t stream) {
 // records the choice.  Afterwards the packs of the new arithmetic are rebuilt from the master copy, behind the handle's last call.
 extern "C" int hificar_xfmr_set_train_precision(hificar_xfmr* g, int precision) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_train_precision: null handle");
-    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3W && precision != HIFICAR_PREC_BF16X3WA)
+    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3W && precision != HIFICAR_PREC_BF16X3WA &&
+        precision != HIFICAR_PREC_BF16X3WAC)
         return fail(HIFICAR_E_INVALID, "unknown training precision %d", precision);
     if (g->precision != HIFICAR_PREC_F32)
         return fail(HIFICAR_E_STATE, "this Transformer handle is packed for the %s inference arithmetic: it has no training step, in either arithmetic",
                     xfmr_precision_name(g->precision));
     if (precision == g->train_precision) return HIFICAR_OK;
-    // (among bf16x3, bf16x3w and bf16x3wa: the same packs, other weight-gradient or attention kernels; towards bf16x3wa the tables are split)
+    // (among bf16x3, bf16x3w, bf16x3wa and bf16x3wac: the same packs, other weight-gradient or attention kernels; towards bf16x3wa or bf16x3wac
+    // from one of the first two the tables are split)
     const bool same_packs = precision != HIFICAR_PREC_F32 && xfmr_train_x3(g);
-    if (!g->train || !g->train->have_params || (same_packs && precision != HIFICAR_PREC_BF16X3WA)) {
+    const bool to_a = precision == HIFICAR_PREC_BF16X3WA || precision == HIFICAR_PREC_BF16X3WAC;
+    if (!g->train || !g->train->have_params || (same_packs && (!to_a || xfmr_train_a(g)))) {
         g->train_precision = precision;
         return HIFICAR_OK;
     }
@@ -602,7 +621,8 @@ struct XfmrTrainWs {
     float* colsum;   // bias-gradient partials
     char* light;     // a forward without a tape keeps its rows here
     char* split;     // [rows][3072] split rows (4 bytes per channel): the operand of the next bf16x3 GEMM; null in the fp32 arithmetic
-    char* split_t[2];  // [rows / 8][3072][32 bytes]: G and A of the next bf16x3w weight gradient (xfmr_split_rows_t_kernel); null otherwise
+    char* split_t[2];  // [rows / 8][3072][32 bytes]: G and A of the next bf16x3w weight gradient (xfmr_split_rows_t_kernel), or G and the
+                       // tap-shifted A3 of a k = 3 conv's in bf16x3wac (xfmr_split_taps_t_kernel: 3 cin_pad <= 3072 columns); null otherwise
     size_t partial_elems, colsum_elems;
     size_t bytes;
 };
@@ -635,7 +655,10 @@ static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void*
             w.partial_elems = std::max(w.partial_elems, wgrad_partial_elems(h, L, nseq, r));
             w.colsum_elems = std::max(w.colsum_elems, wgrad_colsum_elems(h, L, nseq, r));
         };
-        for (const auto& bn : g->train->bns) one(bn.raw, bn.raw.K > 1 && !Mp ? B : 1, bn.raw.K > 1 && !Mp ? T : M);
+        for (const auto& bn : g->train->bns) {
+            one(bn.raw, bn.raw.K > 1 && !Mp ? B : 1, bn.raw.K > 1 && !Mp ? T : M);
+            if (xfmr_train_c(g) && bn.wg3.cout) one(bn.wg3, 1, M);  // (the GEMM form's split count, not the taps form's)
+        }
         one(g->w_in, 1, M);
         one(g->w_out, 1, M);
         for (const auto& L : g->enc) {
@@ -650,7 +673,7 @@ static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void*
     w.light = reinterpret_cast<char*>(take(xfmr_plan_tape(g, B, T, nullptr, Mp).bytes));
     // (last: everything in front of it lies where the fp32 arithmetic has it)
     w.split = xfmr_train_x3(g) ? reinterpret_cast<char*>(take(rows * kXfmrFF * 4)) : nullptr;
-    for (char*& s : w.split_t)  // (behind it: a bf16x3 workspace is a prefix of the bf16x3w one; bf16x3wa's is bf16x3w's)
+    for (char*& s : w.split_t)  // (behind it: a bf16x3 workspace is a prefix of the bf16x3w one; bf16x3wa's and bf16x3wac's are bf16x3w's)
         s = xfmr_train_w(g) ? reinterpret_cast<char*>(take((size_t)split_t_bytes((long long)rows, kXfmrFF))) : nullptr;
     w.bytes = off;
     return w;
@@ -764,7 +787,31 @@ struct XfmrTrainCtx {
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     }
-    int wgrad(const ConvLayer& L, const float* gr, int gpitch, const float* a, int apitch, float* dW, float* db) const {
+    // fp32 rows [M][C] -> 8-row groups of 3 C split columns, tap k's at k C: row r + k - 1 of the row's own sequence, zero bits outside it
+    int split_taps_t(const float* x, int C, char* dst) const {
+        const long long n = split_t3_items(M, C);
+        ProfScope prof(h, stream, "xfmr_split_taps_t_kernel", 0.0, 16.0 * M * C);
+        hipLaunchKernelGGL(xfmr_split_taps_t_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 8192)), dim3(256), 0, stream, x, dst, (long long)M, C, hdr,
+                           lens, T, lay);
+        HIP_TRY(hipGetLastError());
+        return HIFICAR_OK;
+    }
+    // g3: the layer's one-tap twin (XfmrTrain::Bn::wg3), where it has one
+    int wgrad(const ConvLayer& L, const float* gr, int gpitch, const float* a, int apitch, float* dW, float* db, const ConvLayer* g3 = nullptr) const {
+        if (xfmr_train_c(g) && g3 && g3->cout) {  // bf16x3wac: a wide k = 3 conv as the one-tap GEMM G^T A3 on bf16 MFMAs
+            if (!ws->split_t[0] || !ws->split_t[1] || gpitch > kXfmrFF || apitch != L.cin_pad || g3->cin_pad != 3 * apitch || 3 * apitch > kXfmrFF)
+                return fail(HIFICAR_E_INVALID, "internal: bf16x3wac weight gradient of %s", L.name.c_str());
+            int rc;
+            if ((rc = split_rows_t(gr, gpitch, ws->split_t[0])) != HIFICAR_OK || (rc = split_taps_t(a, apitch, ws->split_t[1])) != HIFICAR_OK) return rc;
+            WgradJob job = {g3, gr, gpitch, a, 3 * apitch, dW, db};
+            job.gemm_cin = L.cin;
+            job.gemm_kt = 3;
+            job.gemm_pitch = L.cin_pad != L.cin ? L.cin_pad : 0;
+            job.shape = &L;
+            job.g16 = ws->split_t[0];
+            job.a16 = ws->split_t[1];
+            return launch_wgrad_n(h, &job, 1, 1, M, bw, stream);
+        }
         if (xfmr_train_w(g) && wgrad_gemm_form(L)) {  // bf16x3w, bf16x3wa: the one-tap GEMM form on bf16 MFMAs
             if (!ws->split_t[0] || !ws->split_t[1] || gpitch > kXfmrFF || apitch > kXfmrFF) return fail(HIFICAR_E_INVALID, "internal: bf16x3w weight gradient of %s", L.name.c_str());
             int rc;
@@ -1233,11 +1280,11 @@ static int xfmr_backward_impl(hificar_xfmr* g, const float* dout, int B, int T, 
         const int in_pitch = i ? F : g->cin_pad;
         XT(cx.gate(tp.bo[i], d1, d1, MF, -1));                                          // d1 = dz: through the block's last ReLU
         XT(cx.bn_bwd(tp.y[j2], d1, tp.stats[j2], P(b2.bn + ".weight"), G(b2.bn + ".weight"), d2));
-        XT(cx.wgrad(b2.raw, d2, F, tp.a1[i], F, G(b2.conv + ".weight"), G(b2.conv + ".bias")));
+        XT(cx.wgrad(b2.raw, d2, F, tp.a1[i], F, G(b2.conv + ".weight"), G(b2.conv + ".bias"), &b2.wg3));
         XT(cx.conv(b2.dg, d2, nullptr, d0, nullptr));
         XT(cx.gate(tp.a1[i], d0, d0, MF, -1));
         XT(cx.bn_bwd(tp.y[j1], d0, tp.stats[j1], P(b1.bn + ".weight"), G(b1.bn + ".weight"), d0));
-        XT(cx.wgrad(b1.raw, d0, F, in, in_pitch, G(b1.conv + ".weight"), G(b1.conv + ".bias")));
+        XT(cx.wgrad(b1.raw, d0, F, in, in_pitch, G(b1.conv + ".weight"), G(b1.conv + ".bias"), &b1.wg3));
         if (i > 0) {
             XT(cx.conv(b1.dg, d0, d1, d2, nullptr));                                    // + the identity residual's dz
             std::swap(d1, d2);
@@ -1349,6 +1396,51 @@ extern "C" int hificar_debug_split_rows_t(int M, int C, int T, const int32_t* le
         hipLaunchKernelGGL(xfmr_split_rows_t_kernel, dim3((unsigned)std::min<long long>((split_t_items(M, C) + 255) / 256, 8192)), dim3(256), 0, nullptr,
                            static_cast<const float*>(dx), static_cast<char*>(dd), (long long)M, C, nullptr, pad_row ? nullptr : static_cast<const int*>(dl),
                            T > 0 ? T : 1, lay);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, dd, n, hipMemcpyDeviceToHost);
+    (void)hipFree(dx);
+    (void)hipFree(dd);
+    (void)hipFree(dl);
+    HIP_TRY(e);
+    return HIFICAR_OK;
+}
+
+// Test aid: the tap-column split of fp32 rows x [M][C] (host floats) into 8-row groups of 3 C columns, as the bf16x3wac training arithmetic's
+// k = 3 weight gradients read their A operand (xfmr_split_taps_t_kernel): column k C + c of row r is row r + k - 1 of channel c, zero bits
+// where that row is outside [0, M), a padded frame, a gap row or another sequence's.  T > 0: M / T sequences of T rows (lengths: their frame
+// counts; null: dense); T = 0 (lengths null): one sequence of M rows.  pad_row (M entries, < 0: a gap row): a packed batch, T is not used.
+// how 0: the kernel's index functions run on the host (no device); 1: the kernel itself, over a buffer of 0xFF bytes.  out: `capacity`
+// bytes; *bytes: how many the split has.
+extern "C" int hificar_debug_split_taps_t(int M, int C, int T, const int32_t* lengths, const int32_t* pad_row, int how, const float* x, void* out,
+                                          size_t capacity, size_t* bytes) {
+    if (!x || !out || !bytes || M < 1 || C < 1 || T < 0 || how < 0 || how > 1 || (long long)M * C * 3 >= (1LL << 31) || (T > 0 && M % T) || (lengths && T < 1) ||
+        (lengths && pad_row))
+        return fail(HIFICAR_E_INVALID, "hificar_debug_split_taps_t: bad argument");
+    const size_t n = (size_t)split_t3_bytes(M, C);
+    *bytes = n;
+    if (capacity < n) return fail(HIFICAR_E_INVALID, "hificar_debug_split_taps_t: %zu bytes, the buffer has %zu", n, capacity);
+    const int Ts = T > 0 ? T : M;
+    if (how == 0) {
+        memset(out, 0xFF, n);
+        auto valid = [&](long long r) { return pad_row ? pad_row[r] >= 0 : !lengths || r % Ts < std::min(std::max(lengths[r / Ts], 0), Ts); };
+        for (long long i = 0; i < split_t3_items(M, C); ++i) split_t3_item(x, static_cast<char*>(out), M, C, pad_row ? (long long)M + 8 : (long long)Ts, i, valid);
+        return HIFICAR_OK;
+    }
+    void *dx = nullptr, *dd = nullptr, *dl = nullptr;
+    const int32_t* table = pad_row ? pad_row : lengths;
+    const size_t tn = pad_row ? (size_t)M : lengths ? (size_t)(M / Ts) : 0;
+    hipError_t e = hipMalloc(&dx, (size_t)M * C * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&dd, n);
+    if (e == hipSuccess && tn) e = hipMalloc(&dl, tn * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(dx, x, (size_t)M * C * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && tn) e = hipMemcpy(dl, table, tn * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dd, 0xFF, n);
+    if (e == hipSuccess) {
+        XfmrLayout lay;
+        if (pad_row) lay.pad_row = static_cast<const int*>(dl);
+        hipLaunchKernelGGL(xfmr_split_taps_t_kernel, dim3((unsigned)std::min<long long>((split_t3_items(M, C) + 255) / 256, 8192)), dim3(256), 0, nullptr,
+                           static_cast<const float*>(dx), static_cast<char*>(dd), (long long)M, C, nullptr, pad_row ? nullptr : static_cast<const int*>(dl), Ts, lay);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, dd, n, hipMemcpyDeviceToHost);

@@ -8,7 +8,12 @@
 //   wgrad_bf16x3_kernel        the GEMM on those rows, wgrad_gemm_kernel's tiling (128 x 128 on 64-row chunks, 128 x 256 on 32-row chunks, chunks
 //                              double-buffered through LDS-DMA, the row chunks split over blockIdx.y) and its partial / bias-partial layouts: the
 //                              reductions behind it are the fp32 form's.  Fixed summation order, no atomics.
-// The split's index arithmetic is plain C++ (HIFICAR_HD): hificar_debug_split_rows_t runs the same functions on the host.
+//   xfmr_split_taps_t_kernel   bf16x3wac (HIFICAR_PREC_BF16X3WAC): the A operand of a wide k = 3 conv's weight gradient, run as the one-tap GEMM
+//                              dW[co][k C + c] = G^T A3.  fp32 rows [M][C] -> [ceil(M / 8)][3 C][hi 8 | lo 8]: column k C + c of row r holds row
+//                              r + k - 1 of channel c, and zero bits where that row lies outside [0, M), is a padded frame or a gap row, or
+//                              belongs to another sequence than row r.  Such rows are not read.
+// The splits' index arithmetic is plain C++ (HIFICAR_HD): hificar_debug_split_rows_t and hificar_debug_split_taps_t run the same functions on
+// the host.
 #pragma once
 #include "hificar_xfmr_pack16.hip.h"
 
@@ -48,6 +53,47 @@ HIFICAR_HD void split_t_item(const float* x, char* dst, long long M, int C, long
     memcpy(dst + split_t_offset(C, gi * 8, c), v, 32);
 }
 
+// The tap-column split.  One item: one (group of 8 rows, channel) for all three taps: reads the channel's rows 8 gi - 1 .. 8 gi + 8 once (the
+// valid ones among them), writes three runs of 32 bytes, C columns apart.  Tseq: rows per sequence (dense, ragged: T; packed: anything above
+// M — the gap rows are the sequences' ends).  valid(s): row s < M is a frame of its sequence.
+HIFICAR_HD long long split_t3_items(long long M, int C) { return split_t_groups(M) * C; }
+HIFICAR_HD long long split_t3_bytes(long long M, int C) { return split_t_bytes(M, 3 * C); }
+
+template <typename V>
+HIFICAR_HD void split_t3_item(const float* x, char* dst, long long M, int C, long long Tseq, long long i, V valid) {
+    const long long gi = i / C;
+    const int c = (int)(i - gi * C);
+    const long long r0 = gi * 8;
+    uint16_t hi[10], lo[10];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 10; ++j) {
+        const long long s = r0 - 1 + j;
+        hi[j] = lo[j] = 0;
+        if (s >= 0 && s < M && valid(s)) split_t_pair(x[s * C + c], &hi[j], &lo[j]);
+    }
+    const long long t0 = r0 % Tseq;  // the frame row r0 is in its sequence
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 3; ++k) {
+        alignas(16) uint16_t v[16];
+        long long t = t0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int j = 0; j < 8; ++j) {
+            // the frame in front of a sequence's first and the one behind its last are another sequence's (or nobody's)
+            const bool in = !(k == 0 && t == 0) && !(k == 2 && t == Tseq - 1);
+            v[j] = in ? hi[j + k] : (uint16_t)0;
+            v[8 + j] = in ? lo[j + k] : (uint16_t)0;
+            if (++t == Tseq) t = 0;
+        }
+        memcpy(dst + split_t_offset(3 * C, r0, k * C + c), v, 32);
+    }
+}
+
 #if defined(__HIPCC__)
 // hdr = null: `tape_lens` holds as it stands (null: dense) — the debug entry
 __global__ __launch_bounds__(256) void xfmr_split_rows_t_kernel(const float* __restrict__ x, char* __restrict__ dst, long long M, int C,
@@ -56,6 +102,15 @@ __global__ __launch_bounds__(256) void xfmr_split_rows_t_kernel(const float* __r
     const long long n = split_t_items(M, C);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
         split_t_item(x, dst, M, C, i, [&](long long r) { return xfmr_row_valid(lay, lens, r, T); });
+}
+
+// hdr = null: as above.  T: the rows of a sequence (packed: not used)
+__global__ __launch_bounds__(256) void xfmr_split_taps_t_kernel(const float* __restrict__ x, char* __restrict__ dst, long long M, int C,
+                                                                const BigruTapeHeader* hdr, const int* __restrict__ tape_lens, int T, const XfmrLayout lay) {
+    const int* const lens = hdr ? bigru_tape_lens(hdr, tape_lens) : tape_lens;
+    const long long n = split_t3_items(M, C), Tseq = lay.pad_row ? M + 8 : T;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        split_t3_item(x, dst, M, C, Tseq, i, [&](long long s) { return xfmr_row_valid(lay, lens, s, T); });
 }
 
 struct WgradX3Params {

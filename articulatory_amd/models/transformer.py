@@ -45,7 +45,12 @@ hi + lo; the k = 3 ResBlock convs, ``residual_path`` and ``w_out`` keep exact fp
 (Q K^T, the relative-position product, P V) and the backward's recomputed S, dO V^T and both parts of dQ, as hi hi + hi lo + lo hi with fp32
 accumulation; the softmax statistics, dropout (the same masks), dS itself, dK, dV and the tables' gradient stay fp32, and so does the tape.
 ``precision="bf16x3wa"`` is a ValueError.
-Not built: bf16x3 weight gradients of the k = 3 convs, bf16 MFMAs for dK, dV and the tables' gradient.
+``train_precision="bf16x3wac"`` is the bf16x3wa step with, in addition, the weight and bias gradients of the wide k = 3 ResBlock convs
+(``conv_blocks.{1,2}.conv1``, ``conv_blocks.{0,1,2}.conv2``, and ``conv_blocks.0.conv1`` where ``in_channels`` pads to 128 .. 1024 columns) on
+bf16 MFMAs: each as a one-tap G^T A3 whose columns k cin + c hold frame t + k - 1 of channel c, zero outside the frame's own sequence.
+``conv_blocks.0.conv1`` at other widths, ``residual_path`` and ``w_out`` keep exact fp32 weight gradients.  ``precision="bf16x3wac"`` is a
+ValueError.
+Not built: a k = 3 weight-gradient kernel that forms the three taps from one staged chunk, bf16 MFMAs for dK, dV and the tables' gradient.
 
 Not built, refused with ``NotImplementedError``: ``extra_art=True`` and ``num_ph`` (phoneme input).  ``forward(lengths=...)`` in train() mode
 is refused too (ragged training is asked for by name: ``forward_padded``).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size``
@@ -206,8 +211,8 @@ class _PrecisionKeyword(type):
             raise ValueError(f"precision must be one of {sorted(_native.XFMR_PRECISIONS)}")
         if train_precision is None:
             train_precision = "f32"
-        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS:
-            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS)}")
+        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS_ALL:
+            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS_ALL)}")
         if precision != "f32" and train_precision != "f32":
             raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='{precision}' model is inference-only")
         self = super().__call__(*args, **kwargs)
@@ -279,10 +284,11 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         norms, dropout and the tape stay fp32 (hificar_xfmr_set_train_precision).  The eval-mode forward is exact fp32 either way.  The
         native handle is kept: its packs are rebuilt on the device.  A backward whose forward ran in the other arithmetic is refused
         (RuntimeError).  "bf16x3w": "bf16x3", and the weight and bias gradients of the one-tap layers at least 128 x 128 wide in the same
-        arithmetic; "bf16x3wa": "bf16x3w", and the attention's query-tiled kernels on bf16 MFMAs (see the module's docstring).  Not with
+        arithmetic; "bf16x3wa": "bf16x3w", and the attention's query-tiled kernels on bf16 MFMAs; "bf16x3wac": "bf16x3wa", and the weight
+        gradients of the wide k = 3 convs on bf16 MFMAs (see the module's docstring).  Not with
         ``precision="bf16x3"`` (ValueError)."""
-        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS:
-            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS)}")
+        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS_ALL:
+            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS_ALL)}")
         if train_precision != "f32" and self.precision != "f32":
             raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='{self.precision}' model is inference-only")
         if train_precision == self.train_precision:
@@ -290,7 +296,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         self.train_precision = train_precision
         if self.__dict__.get("_handle") is not None:
             with torch.cuda.device(self._device()):
-                _native.check(self._lib.hificar_xfmr_set_train_precision(self._handle, _native.XFMR_TRAIN_PRECISIONS[train_precision]),
+                _native.check(self._lib.hificar_xfmr_set_train_precision(self._handle, _native.XFMR_TRAIN_PRECISIONS_ALL[train_precision]),
                               "hificar_xfmr_set_train_precision")
 
     def _refuse_bf16x3_training(self):
@@ -465,7 +471,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                 _native.check(lib.hificar_xfmr_set_precision(handle, _native.XFMR_PRECISIONS[self.precision]), "hificar_xfmr_set_precision")
                 _native.check(lib.hificar_xfmr_finalize(handle), "hificar_xfmr_finalize")
                 if self.precision == "f32":  # (a bf16x3 inference handle has no training arithmetic to choose)
-                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.XFMR_TRAIN_PRECISIONS[self.train_precision]),
+                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.XFMR_TRAIN_PRECISIONS_ALL[self.train_precision]),
                                   "hificar_xfmr_set_train_precision")
             except Exception:
                 lib.hificar_xfmr_destroy(handle)

@@ -79,6 +79,9 @@ extern "C" {
 #define HIFICAR_PREC_BF16X3WA 4    /* hificar_xfmr_set_train_precision ONLY: bf16x3w, and the training attention's query-tiled kernels (forward
                                       and backward-q: seven of its ten banded products) on v_mfma_f32_16x16x32_bf16 too; every other entry
                                       point that takes a precision refuses it (HIFICAR_E_INVALID) */
+#define HIFICAR_PREC_BF16X3WAC 6   /* hificar_xfmr_set_train_precision ONLY: bf16x3wa, and the weight gradients of the wide k = 3 ResBlock convs
+                                      as one-tap GEMMs on tap-shifted split columns (v_mfma_f32_32x32x16_bf16) too; every other entry point
+                                      that takes a precision refuses it (HIFICAR_E_INVALID) */
 
 typedef struct hificar_handle hificar_handle;
 /* The conv engine every model of the library launches through (plans, schedules, stream ordering, profiling).  A generator handle
@@ -730,11 +733,12 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * hificar_xfmr_forward_train_packed computes the same step without GEMM rows for the padding.
  * All of these may be called after hificar_xfmr_finalize; the first one builds the training state.
  * The forward GEMMs and data gradients have an opt-in bf16x3 arithmetic (hificar_xfmr_set_train_precision, below).
- * The one-tap weight gradients have one too (HIFICAR_PREC_BF16X3W), and so have the attention's query-tiled kernels (HIFICAR_PREC_BF16X3WA).
- * Not built: a smaller tape per frame, bf16x3 weight gradients of the k = 3 convs, dK / dV / the table gradient on bf16 MFMAs, extra_art, num_ph, multi-GPU training of this model. ---- */
+ * The one-tap weight gradients have one too (HIFICAR_PREC_BF16X3W), and so have the attention's query-tiled kernels (HIFICAR_PREC_BF16X3WA)
+ * and the weight gradients of the wide k = 3 convs (HIFICAR_PREC_BF16X3WAC).
+ * Not built: a smaller tape per frame, a k = 3 weight-gradient kernel that forms the three taps from one staged chunk, dK / dV / the table gradient on bf16 MFMAs, extra_art, num_ph, multi-GPU training of this model. ---- */
 
 /* The arithmetic of the training step's GEMMs: HIFICAR_PREC_F32 (the default: the step above, bit for bit), HIFICAR_PREC_BF16X3,
- * HIFICAR_PREC_BF16X3W or HIFICAR_PREC_BF16X3WA.
+ * HIFICAR_PREC_BF16X3W, HIFICAR_PREC_BF16X3WA or HIFICAR_PREC_BF16X3WAC.
  * bf16x3: every forward GEMM of hificar_xfmr_forward_train / _ragged / _packed (the six ResBlock convs and residual_path, w_raw_in,
  * q | k | v, w_o, linear1, linear2, w_out) and every data gradient of the same layers runs as x w ~ hi hi + hi lo + lo hi on bf16 MFMAs with
  * fp32 accumulation, in the conv engine's bf16x3 kernels (hi = bf16(x), lo = bf16(x - hi), round to nearest even; split-K off: one
@@ -759,6 +763,14 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * read.  The tape keeps fp32 q | k | v, O and lse rows (its size does not change): a fetched key block is split on its way into LDS.  The
  * position tables are split on the device behind every parameter hand-over (8 x 208 x d bf16, twice, per layer; handle state, no workspace).
  * bf16x3w <-> bf16x3wa rebuilds no weight pack (towards bf16x3wa the tables are split).
+ * bf16x3wac: the bf16x3wa step, bit for bit in every launch but the weight (and bias) gradients of the k = 3 convs that have at least 128 output
+ * channels, input rows of 128 .. 1024 columns (cin_pad) and one phase: conv_blocks.{1,2}.conv1 and conv_blocks.{0,1,2}.conv2 at any hidden size,
+ * conv_blocks.0.conv1 where in_channels pads to 128 .. 1024.  Such a gradient is the one-tap GEMM dW[co][k cin_pad + ci] = G^T A3 in the bf16x3w
+ * kernel (hi^T hi + hi^T lo + lo^T hi, fp32 accumulation, fixed summation order): column k cin_pad + ci of row r of A3 is row r + k - 1 of
+ * channel ci where that row is a frame of row r's own sequence, and zero where it is not (the batch's ends, padded frames, gap rows, the
+ * neighbouring sequence).  A3 is written in the split layout into the second of bf16x3w's two scratch buffers (3 cin_pad <= 3072): the
+ * workspace is bf16x3wa's.  The bias gradient is the fp32 sum of hi + lo over the rows of G.  conv_blocks.0.conv1 at other widths,
+ * residual_path and w_out stay on the exact fp32 kernels.  bf16x3w / bf16x3wa <-> bf16x3wac rebuilds no weight pack.
  * Legal at any time on an f32 handle, also after hificar_xfmr_finalize and between steps: once parameters have been handed over, the packs of
  * the new arithmetic are rebuilt from the handle's device copy, in stream order behind the handle's last call.  A handle whose
  * hificar_xfmr_set_precision is bf16x3 (inference only): HIFICAR_E_STATE.  An unknown value: HIFICAR_E_INVALID.
@@ -779,6 +791,14 @@ int hificar_debug_pack16(int cout, int cin, int cin_pad, int K, int mode, int ho
  * device pass's index functions run on the host (no device needed); 1: the device pass, over a buffer of 0xFF bytes.  out: HOST, `capacity`
  * bytes; *bytes: the split's size (set even when the buffer is too small: HIFICAR_E_INVALID then). */
 int hificar_debug_split_rows_t(int M, int C, int T, const int32_t* lengths, const int32_t* pad_row, int how, const float* x, void* out, size_t capacity,
+                               size_t* bytes);
+
+/* Test aid: fp32 rows x [M][C] (HOST floats) split for the bf16x3wac k = 3 weight gradients: [ceil(M / 8)][3 C][hi 8 | lo 8] bf16; column
+ * k C + c of row r holds row r + k - 1 of channel c, and zero bits where that row is outside [0, M), a padded frame, a gap row or a row of
+ * another sequence than row r (such rows are not read).  T > 0: M / T sequences of T rows, lengths their frame counts (NULL: dense); T = 0
+ * (lengths NULL): one sequence of M rows.  pad_row (M entries, < 0: a gap row; not with lengths): a packed batch, T is not used.  how, out,
+ * capacity, *bytes: as hificar_debug_split_rows_t. */
+int hificar_debug_split_taps_t(int M, int C, int T, const int32_t* lengths, const int32_t* pad_row, int how, const float* x, void* out, size_t capacity,
                                size_t* bytes);
 
 /* Every float tensor of the state_dict (reference names and layouts, the batch norms' running_mean / running_var included; n = all of them,

@@ -71,6 +71,16 @@ bf16x3wa_ms, bf16x3w_over_bf16x3wa (fastest bf16x3w window over slowest bf16x3wa
 below the fastest bf16x3w window by more than the two spreads added), the bf16x3wa step's per-kernel table and attention_ms: the forward
 (xfmr_attn16_kernel<train> against xfmr_attn_kernel<train>), the backward (xfmr_attn16_bwd_q_kernel + xfmr_attn_bwd_k_kernels against
 xfmr_attn_bwd_kernels) and the tables' split (xfmr_split_tab_kernel, a cost) of the two legs' profiled steps.
+
+   python tools/transformer_bench.py --train --train-precision bf16x3wac [--ragged] [--out profiles/transformer_train_bf16x3wac.txt]
+
+--train-precision bf16x3wac: the bf16x3, bf16x3w and bf16x3wa leg(s) above AND one more, train_precision="bf16x3wac" (the wide k = 3 convs'
+weight gradients on bf16 MFMAs too), in the same alternation: its yardstick is the bf16x3wa leg of the same run.  The line carries
+bf16x3wac_ms, bf16x3wa_over_bf16x3wac (fastest bf16x3wa window over slowest bf16x3wac window), bf16x3wac_faster (the slowest bf16x3wac window
+is below the fastest bf16x3wa window by more than the two spreads added), the bf16x3wac step's per-kernel table and conv_wgrad_ms: the moved
+convs' rows of one bf16x3wa step (wgrad_taps_kernel and its reductions, by layer shape) beside those of one bf16x3wac step (the k3 rows of
+wgrad_bf16x3_kernel, their reductions, xfmr_split_taps_t_kernel and what xfmr_split_rows_t_kernel takes above the bf16x3wa step's: the
+moved layers' G splits), from two further models built under HIFICAR_PROFILE_DETAIL=1, which take no part in the timed windows.
 Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
 import argparse
 import ctypes
@@ -129,6 +139,47 @@ def attention_rows(pw, pa):
             "cost": {"bf16x3wa xfmr_split_tab_kernel": g(pa, "xfmr_split_tab_kernel")}}
 
 
+def detail_profile(arith, sd, p, run):
+    """{row: ms} of one step of a further model in `arith`, built under HIFICAR_PROFILE_DETAIL=1 (weight-gradient and reduction rows carry the
+    layer's shape); run(m): one forward and backward.  The parameter hand-over behind an optimizer step lies inside the profile."""
+    before = os.environ.get("HIFICAR_PROFILE_DETAIL")
+    os.environ["HIFICAR_PROFILE_DETAIL"] = "1"
+    try:
+        m = Transformer(dropout=p, train_precision=arith, **PARAMS)
+        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+        m = m.cuda().train()
+        opt = torch.optim.Adam(m.parameters(), lr=1e-4, fused=True)
+        for _ in range(2):
+            opt.zero_grad(set_to_none=True)
+            run(m)
+            opt.step()
+    finally:
+        if before is None:
+            del os.environ["HIFICAR_PROFILE_DETAIL"]
+        else:
+            os.environ["HIFICAR_PROFILE_DETAIL"] = before
+    eng = m.engine()
+    _native.check(m._lib.hificar_profile_begin(eng), "hificar_profile_begin")
+    opt.zero_grad(set_to_none=True)
+    run(m)
+    stats = (_native.HificarKernelStat * 512)()
+    n = ctypes.c_int()
+    _native.check(m._lib.hificar_profile_end(eng, stats, 512, ctypes.byref(n)), "hificar_profile_end")
+    return {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+
+
+def conv_wgrad_rows(pa, pc):
+    """The moved k = 3 convs' rows of a bf16x3wa step's detailed profile (pa) beside a bf16x3wac step's (pc), and both sums."""
+    shape = lambda r: r.split(" ")[1].split("p")[0]  # noqa: E731  ('kernel CxIkK[pP] ...')
+    moved = {shape(r) for r in pc if r.startswith("wgrad_bf16x3_kernel") and "k3" in shape(r)}
+    rows = lambda prof, pre: {r: round(v, 4) for r, v in sorted(prof.items()) if r.startswith(pre) and shape(r) in moved}  # noqa: E731
+    old = rows(pa, ("wgrad_taps_kernel", "wreduce_"))
+    new = rows(pc, ("wgrad_bf16x3_kernel", "wreduce_"))
+    new["xfmr_split_taps_t_kernel"] = round(pc.get("xfmr_split_taps_t_kernel", 0.0), 4)
+    new["xfmr_split_rows_t_kernel over bf16x3wa's"] = round(pc.get("xfmr_split_rows_t_kernel", 0.0) - pa.get("xfmr_split_rows_t_kernel", 0.0), 4)
+    return {"bf16x3wa": old, "bf16x3wac": new, "bf16x3wa_sum": round(sum(old.values()), 4), "bf16x3wac_sum": round(sum(new.values()), 4)}
+
+
 def train_main(a):
     import torch.nn.functional as F
 
@@ -159,6 +210,7 @@ def train_main(a):
     fast = f_opt = None
     fastw = w_opt = None
     fastwa = wa_opt = None
+    fastwac = wac_opt = None
 
     def leg(arith):
         m = Transformer(dropout=p, train_precision=arith, **PARAMS)
@@ -166,12 +218,14 @@ def train_main(a):
         m = m.cuda().train()
         return m, torch.optim.Adam(m.parameters(), lr=1e-4, fused=True)
 
-    if a.train_precision in ("bf16x3", "bf16x3w", "bf16x3wa"):
+    if a.train_precision in ("bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac"):
         fast, f_opt = leg("bf16x3")
-    if a.train_precision in ("bf16x3w", "bf16x3wa"):
+    if a.train_precision in ("bf16x3w", "bf16x3wa", "bf16x3wac"):
         fastw, w_opt = leg("bf16x3w")
-    if a.train_precision == "bf16x3wa":
+    if a.train_precision in ("bf16x3wa", "bf16x3wac"):
         fastwa, wa_opt = leg("bf16x3wa")
+    if a.train_precision == "bf16x3wac":
+        fastwac, wac_opt = leg("bf16x3wac")
 
     def profile_step(m, opt):
         """{kernel: ms} of one step: the parameter hand-over behind the optimizer step before it, forward and backward."""
@@ -217,6 +271,11 @@ def train_main(a):
             F.l1_loss(fastwa(x), y).backward()
             wa_opt.step()
 
+        def fastwac_step(_):
+            wac_opt.zero_grad(set_to_none=True)
+            F.l1_loss(fastwac(x), y).backward()
+            wac_opt.step()
+
         for _ in range(2):
             native_step(None), stock_step(None)
             if fast is not None:
@@ -225,16 +284,20 @@ def train_main(a):
                 fastw_step(None)
             if fastwa is not None:
                 fastwa_step(None)
+            if fastwac is not None:
+                fastwac_step(None)
         torch.cuda.synchronize()
         n1 = window(native_step, None, a.window)
         f1 = None if fast is None else window(fast_step, None, a.window)
         w1 = None if fastw is None else window(fastw_step, None, a.window)
         a1 = None if fastwa is None else window(fastwa_step, None, a.window)
+        c1 = None if fastwac is None else window(fastwac_step, None, a.window)
         s1 = window(stock_step, None, a.window)
         n2 = window(native_step, None, a.window)
         f2 = None if fast is None else window(fast_step, None, a.window)
         w2 = None if fastw is None else window(fastw_step, None, a.window)
         a2 = None if fastwa is None else window(fastwa_step, None, a.window)
+        c2 = None if fastwac is None else window(fastwac_step, None, a.window)
         s2 = window(stock_step, None, a.window)
         res = {"train": True, "B": B, "T": T, "dropout": p, "native_ms": [round(n1, 3), round(n2, 3)], "stock_ms": [round(s1, 3), round(s2, 3)],
                "native_spread": round(abs(n1 - n2) / min(n1, n2), 4), "stock_spread": round(abs(s1 - s2) / min(s1, s2), 4),
@@ -290,6 +353,18 @@ def train_main(a):
             for pre in ("conv", "wgrad", "wreduce", "xfmr_attn", "xfmr_split_rows", "pack16", "xfmr_", "xfmr_split_rows_t"):
                 res["families_ms"][pre]["bf16x3wa"] = fam(pa, pre)
             res["attention_ms"] = attention_rows(pw, pa)
+        if fastwac is not None:
+            res["bf16x3wac_ms"] = [round(c1, 3), round(c2, 3)]
+            res["bf16x3wac_spread"] = round(abs(c1 - c2) / min(c1, c2), 4)
+            res["bf16x3wa_over_bf16x3wac"] = round(min(a1, a2) / max(c1, c2), 3)
+            res["bf16x3wac_faster"] = bool(min(a1, a2) - max(c1, c2) > abs(a1 - a2) + abs(c1 - c2))
+            pc = profile_step(fastwac, wac_opt)
+            res["bf16x3wac_kernels_ms"] = {k: round(v, 4) for k, v in sorted(pc.items(), key=lambda kv: -kv[1])}
+            for pre in ("conv", "wgrad", "wreduce", "xfmr_attn", "xfmr_split_rows", "pack16", "xfmr_", "xfmr_split_rows_t"):
+                res["families_ms"][pre]["bf16x3wac"] = fam(pc, pre)
+            res["families_ms"]["xfmr_split_taps_t"] = {"bf16x3wa": 0.0, "bf16x3wac": fam(pc, "xfmr_split_taps_t")}
+            run = lambda m: F.l1_loss(m(x), y).backward()  # noqa: E731
+            res["conv_wgrad_ms"] = conv_wgrad_rows(detail_profile("bf16x3wa", sd, p, run), detail_profile("bf16x3wac", sd, p, run))
         lines.append(json.dumps(res))
         print(lines[-1], flush=True)
     if a.out:
@@ -329,7 +404,8 @@ def ragged_train_main(a):
 
     legs = {"native_packed": make(lambda: masked_l1_loss(m.forward_padded(x, lens32, packed=True), y, lens32)),
             "native_ragged": make(lambda: masked_l1_loss(m.forward_padded(x, lens32), y, lens32)), "native_dense": make(lambda: F.l1_loss(m(x), y))}
-    ariths = {"bf16x3": ("bf16x3",), "bf16x3w": ("bf16x3", "bf16x3w"), "bf16x3wa": ("bf16x3", "bf16x3w", "bf16x3wa")}.get(a.train_precision, ())
+    ariths = {"bf16x3": ("bf16x3",), "bf16x3w": ("bf16x3", "bf16x3w"), "bf16x3wa": ("bf16x3", "bf16x3w", "bf16x3wa"),
+              "bf16x3wac": ("bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac")}.get(a.train_precision, ())
     fast = {}
     for arith in ariths:  # the same batch through further models in the bf16x3 (and bf16x3w) training arithmetic, padded and packed
         m3 = Transformer(dropout=p, train_precision=arith, **PARAMS)
@@ -383,6 +459,10 @@ def ragged_train_main(a):
             w_, a_ = ms["bf16x3w_" + form], ms["bf16x3wa_" + form]
             res[f"bf16x3w_over_bf16x3wa_{form}"] = round(min(w_) / max(a_), 3)
             res[f"bf16x3wa_faster_{form}"] = bool(min(w_) - max(a_) > abs(w_[0] - w_[1]) + abs(a_[0] - a_[1]))
+        if "bf16x3wac_" + form in ms:
+            a_, c_ = ms["bf16x3wa_" + form], ms["bf16x3wac_" + form]
+            res[f"bf16x3wa_over_bf16x3wac_{form}"] = round(min(a_) / max(c_), 3)
+            res[f"bf16x3wac_faster_{form}"] = bool(min(a_) - max(c_) > abs(a_[0] - a_[1]) + abs(c_[0] - c_[1]))
     eng = m.engine()
     profs = {}
     for tag in ("packed", "ragged", "dense"):
@@ -407,6 +487,10 @@ def ragged_train_main(a):
             res[f"{arith}_{tag}_kernels_total_ms"] = round(sum(prof3.values()), 3)
     if "bf16x3wa" in fast:
         res["attention_ms"] = {tag: attention_rows(res[f"bf16x3w_{tag}_kernels_ms"], res[f"bf16x3wa_{tag}_kernels_ms"]) for tag in ("packed", "ragged")}
+    if "bf16x3wac" in fast:
+        runs = {"packed": lambda m3: masked_l1_loss(m3.forward_padded(x, lens32, packed=True), y, lens32).backward(),
+                "ragged": lambda m3: masked_l1_loss(m3.forward_padded(x, lens32), y, lens32).backward()}
+        res["conv_wgrad_ms"] = {tag: conv_wgrad_rows(detail_profile("bf16x3wa", sd, p, run), detail_profile("bf16x3wac", sd, p, run)) for tag, run in runs.items()}
     res["attention_recovered_ms"] = {k: round(profs["dense"].get(k, 0.0) - profs["ragged"].get(k, 0.0), 4)
                                      for k in ("xfmr_attn_kernel<train>", "xfmr_attn_bwd_kernels")}
     # packed over ragged per kernel family, to read beside packed_rows_over_padded_rows: conv_* are the forward GEMMs and the data gradients
@@ -432,8 +516,9 @@ def main():
     ap.add_argument("--no-stock", action="store_true")
     ap.add_argument("--precision", choices=("f32", "bf16x3", "bf16x3a"), default="f32",
                     help="bf16x3: add the bf16x3 leg to the native / stock alternation; bf16x3a: that leg and the bf16x3a leg")
-    ap.add_argument("--train-precision", choices=("f32", "bf16x3", "bf16x3w", "bf16x3wa"), default="f32",
-                    help="--train: bf16x3 adds the bf16x3 training leg(s); bf16x3w adds those and the bf16x3w leg(s); bf16x3wa those and the bf16x3wa leg(s)")
+    ap.add_argument("--train-precision", choices=("f32", "bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac"), default="f32",
+                    help="--train: bf16x3 adds the bf16x3 training leg(s); bf16x3w adds those and the bf16x3w leg(s); bf16x3wa those and the bf16x3wa leg(s); "
+                         "bf16x3wac those and the bf16x3wac leg(s)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--ragged", action="store_true", help="--train: the ragged batch's two legs instead of the dense shapes")
     ap.add_argument("--seed", type=int, default=0, help="--train --ragged: seed of the lengths")
