@@ -22,6 +22,7 @@ PREC_BF16X3W = 2
 PREC_BF16X3A = 3
 PREC_BF16X3WA = 4
 PREC_BF16X3WAC = 6
+PREC_BF16X3WACK = 8
 PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}  # the inference arithmetics (``precision=``)
 # ... and the Transformer's training arithmetics (``train_precision=``): bf16x3w = bf16x3 with the one-tap weight gradients in it too
 TRAIN_PRECISIONS = dict(PRECISIONS, bf16x3w=PREC_BF16X3W)
@@ -29,8 +30,11 @@ TRAIN_PRECISIONS = dict(PRECISIONS, bf16x3w=PREC_BF16X3W)
 XFMR_PRECISIONS = dict(PRECISIONS, bf16x3a=PREC_BF16X3A)
 # the Transformer's training arithmetics with bf16x3wa: bf16x3w with the attention's query-tiled kernels (forward, backward-q) on bf16 MFMAs too
 XFMR_TRAIN_PRECISIONS = dict(TRAIN_PRECISIONS, bf16x3wa=PREC_BF16X3WA)
-# ... and with bf16x3wac: bf16x3wa with the weight gradients of the wide k = 3 ResBlock convs on bf16 MFMAs too (what ``train_precision=`` accepts)
+# ... and with bf16x3wac: bf16x3wa with the weight gradients of the wide k = 3 ResBlock convs on bf16 MFMAs too (what ``train_precision=`` accepted before bf16x3wack)
 XFMR_TRAIN_PRECISIONS_ALL = dict(XFMR_TRAIN_PRECISIONS, bf16x3wac=PREC_BF16X3WAC)
+# ... and with bf16x3wack: bf16x3wac with the attention's key-tiled backward (dK, dV, the tables' gradient) on bf16 MFMAs too: every value
+# ``train_precision=`` accepts (the three mappings above stay as they are: they are what their arithmetics' tests pin)
+XFMR_TRAIN_PRECISIONS_K = dict(XFMR_TRAIN_PRECISIONS_ALL, bf16x3wack=PREC_BF16X3WACK)
 
 # every symbol include/hificar.h declares (tests/test_cabi.py checks the .so exports each one)
 SYMBOLS = (

@@ -652,7 +652,8 @@ class InversionTrainer:
     ``eval_step`` / ``eval_epoch``: dev utterances whole, in eval mode, under ``masked_l1_loss`` (``pad_packed`` plays no part there).
     ``train_precision: bf16x3`` (this package's key, default ``f32``; the Transformer only, the BiGRU is refused): the training step's forward
     GEMMs and data gradients in the bf16x3 kernels (``Transformer.set_train_precision``; ``bf16x3w``: the one-tap weight gradients too; ``bf16x3wa``: and the
-    attention's query-tiled kernels; ``bf16x3wac``: and the wide k = 3 convs' weight gradients), in every
+    attention's query-tiled kernels; ``bf16x3wac``: and the wide k = 3 convs' weight gradients;
+    ``bf16x3wack``: and the attention's dK, dV and table gradients), in every
     package mode; the first log line names the
     arithmetic.  Checkpoints do not change: the weights are fp32 either way."""
 
@@ -690,8 +691,8 @@ class InversionTrainer:
         # train_precision (this package's key, default f32): the arithmetic of the Transformer's forward GEMMs and data gradients in training
         # (Transformer.set_train_precision); the weights, and so the checkpoints, are fp32 either way
         self.train_precision = config.get("train_precision", "f32")
-        if self.train_precision not in ("f32", "bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac"):
-            raise ValueError(f"train_precision must be f32, bf16x3, bf16x3w, bf16x3wa or bf16x3wac (got {self.train_precision!r})")
+        if self.train_precision not in ("f32", "bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac", "bf16x3wack"):
+            raise ValueError(f"train_precision must be f32, bf16x3, bf16x3w, bf16x3wa, bf16x3wac or bf16x3wack (got {self.train_precision!r})")
         if self.train_precision != "f32" and gtype != "Transformer":
             raise NotImplementedError(f"train_precision {self.train_precision} is built for generator_type Transformer (got {gtype}): the BiGRU "
                                       "trains in exact fp32; drop the key")

@@ -12,6 +12,7 @@
 #include "hificar_xfmr_attn16.hip.h"
 #include "hificar_xfmr_train_kernels.hip.h"
 #include "hificar_xfmr_attn16_train.hip.h"
+#include "hificar_xfmr_attn16_train_k.hip.h"
 #include "hificar_xfmr_wgrad16.hip.h"
 
 #include "../../include/hificar.h"

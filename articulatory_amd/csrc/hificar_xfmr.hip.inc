@@ -184,7 +184,7 @@ static int xfmr_pack(hificar_engine* h, ConvLayer& L, const HostTensor& W, const
 }
 
 static const char* xfmr_precision_name(int p) {
-    return p == HIFICAR_PREC_BF16X3WAC ? "bf16x3wac" : p == HIFICAR_PREC_BF16X3WA ? "bf16x3wa" : p == HIFICAR_PREC_BF16X3A ? "bf16x3a" : p == HIFICAR_PREC_BF16X3W ? "bf16x3w" : p == HIFICAR_PREC_BF16X3 ? "bf16x3" : "f32";
+    return p == HIFICAR_PREC_BF16X3WACK ? "bf16x3wack" : p == HIFICAR_PREC_BF16X3WAC ? "bf16x3wac" : p == HIFICAR_PREC_BF16X3WA ? "bf16x3wa" : p == HIFICAR_PREC_BF16X3A ? "bf16x3a" : p == HIFICAR_PREC_BF16X3W ? "bf16x3w" : p == HIFICAR_PREC_BF16X3 ? "bf16x3" : "f32";
 }
 
 extern "C" int hificar_xfmr_set_precision(hificar_xfmr* g, int precision) {

@@ -32,6 +32,9 @@
 // G^T A3 in wgrad_bf16x3_kernel: A3's column k cin_pad + c of row r is row r + k - 1 of channel c within the row's own sequence
 // (xfmr_split_taps_t_kernel writes it into the second of bf16x3w's two scratch buffers), the layer's one-tap twin (XfmrTrain::Bn::wg3) gives the
 // launch its tiles and split count, and wreduce's gemm_cin form lays the partial out as (cout, cin, 3).
+// bf16x3wack training (HIFICAR_PREC_BF16X3WACK): the bf16x3wac step, and the attention's key-tiled backward — dK, dV and the first stage of the
+// table gradient — on bf16 MFMAs (hificar_xfmr_attn16_train_k.hip.h), on the banded fp32 dS / Pd xfmr_attn16_bwd_q_kernel writes: the same
+// workspace and tape, profile rows xfmr_attn16_bwd_k_kernel and xfmr_demb16_partial_kernel in place of xfmr_attn_bwd_k_kernels.
 
 struct XfmrTrainLayer {
     ConvLayer dg_qkv, dg_wo, dg_l1, dg_l2;
@@ -96,7 +99,8 @@ static hipError_t xfmr_train_attr() {
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_demb_partial_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XfmrEmbLds<D>::bytes);
     if (e != hipSuccess) return e;
-    return xfmr_attn16_train_attr<D>();
+    if ((e = xfmr_attn16_train_attr<D>()) != hipSuccess) return e;
+    return xfmr_attn16_train_k_attr<D>();
 }
 
 template <int D>
@@ -130,7 +134,8 @@ static int xfmr_alloc(hificar_engine* h, size_t bytes, void** out) {
 }
 
 static bool xfmr_train_x3(const hificar_xfmr* g) { return g->train_precision != HIFICAR_PREC_F32; }  // bf16x3, bf16x3w or bf16x3wa: the same GEMMs and packs
-static bool xfmr_train_c(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WAC; }  // the wide k = 3 convs' weight gradients on bf16 MFMAs
+static bool xfmr_train_k(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WACK; }  // the attention's key-tiled backward on bf16 MFMAs
+static bool xfmr_train_c(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WAC || xfmr_train_k(g); }  // the wide k = 3 convs' weight gradients on bf16 MFMAs
 static bool xfmr_train_a(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WA || xfmr_train_c(g); }  // the attention's query-tiled kernels on bf16 MFMAs
 static bool xfmr_train_w(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3W || xfmr_train_a(g); }
 // three taps, one phase, at least 128 x 128, and the three taps' columns side by side fit a split buffer: the one-tap GEMM form on tap-shifted columns
@@ -500,16 +505,16 @@ static int xfmr_split_tables(hificar_xfmr* g, hipStream_t stream) {
 extern "C" int hificar_xfmr_set_train_precision(hificar_xfmr* g, int precision) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_train_precision: null handle");
     if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3W && precision != HIFICAR_PREC_BF16X3WA &&
-        precision != HIFICAR_PREC_BF16X3WAC)
+        precision != HIFICAR_PREC_BF16X3WAC && precision != HIFICAR_PREC_BF16X3WACK)
         return fail(HIFICAR_E_INVALID, "unknown training precision %d", precision);
     if (g->precision != HIFICAR_PREC_F32)
         return fail(HIFICAR_E_STATE, "this Transformer handle is packed for the %s inference arithmetic: it has no training step, in either arithmetic",
                     xfmr_precision_name(g->precision));
     if (precision == g->train_precision) return HIFICAR_OK;
-    // (among bf16x3, bf16x3w, bf16x3wa and bf16x3wac: the same packs, other weight-gradient or attention kernels; towards bf16x3wa or bf16x3wac
-    // from one of the first two the tables are split)
+    // (among bf16x3, bf16x3w, bf16x3wa, bf16x3wac and bf16x3wack: the same packs, other weight-gradient or attention kernels; towards one of the
+    // last three from one of the first two the tables are split)
     const bool same_packs = precision != HIFICAR_PREC_F32 && xfmr_train_x3(g);
-    const bool to_a = precision == HIFICAR_PREC_BF16X3WA || precision == HIFICAR_PREC_BF16X3WAC;
+    const bool to_a = precision == HIFICAR_PREC_BF16X3WA || precision == HIFICAR_PREC_BF16X3WAC || precision == HIFICAR_PREC_BF16X3WACK;
     if (!g->train || !g->train->have_params || (same_packs && (!to_a || xfmr_train_a(g)))) {
         g->train_precision = precision;
         return HIFICAR_OK;
@@ -1251,9 +1256,20 @@ static int xfmr_backward_impl(hificar_xfmr* g, const float* dout, int B, int T, 
                     const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn16_bwd_q_launch, d, p16, grid, stream);
                     if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn16_bwd_q_kernel launch failed: %s", hipGetErrorString(e));
                 }
-                ProfScope prof(h, stream, "xfmr_attn_bwd_k_kernels", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * (5.0 * F + 3.0 * kXfmrHeads * kXfmrBand));
-                const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_bwd_k_launch, d, p, grid, ws.embpart, M, chunks, stream);
-                if (e != hipSuccess) return fail(HIFICAR_E_HIP, "attention backward launch failed: %s", hipGetErrorString(e));
+                if (xfmr_train_k(g)) {  // bf16x3wack: dK, dV and dE's first stage on bf16 MFMAs too, from the same banded buffers
+                    {
+                        ProfScope prof(h, stream, "xfmr_attn16_bwd_k_kernel", 2.0 * M * F * 2 * kXfmrTab, 4.0 * M * (4.0 * F + 2.0 * kXfmrHeads * kXfmrBand));
+                        const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn16_bwd_k_launch, d, p, grid, stream);
+                        if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn16_bwd_k_kernel launch failed: %s", hipGetErrorString(e));
+                    }
+                    ProfScope prof(h, stream, "xfmr_demb16_partial_kernel", 2.0 * M * F * kXfmrTab, 4.0 * M * (1.0 * F + 1.0 * kXfmrHeads * kXfmrBand));
+                    const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_demb16_partial_launch, d, p, ws.embpart, M, chunks, stream);
+                    if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_demb16_partial_kernel launch failed: %s", hipGetErrorString(e));
+                } else {
+                    ProfScope prof(h, stream, "xfmr_attn_bwd_k_kernels", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * (5.0 * F + 3.0 * kXfmrHeads * kXfmrBand));
+                    const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_bwd_k_launch, d, p, grid, ws.embpart, M, chunks, stream);
+                    if (e != hipSuccess) return fail(HIFICAR_E_HIP, "attention backward launch failed: %s", hipGetErrorString(e));
+                }
             } else {
                 // S, dP, dQ (K and E parts), dK, dV, dE: six banded products of 2 M F 199 flops each
                 ProfScope prof(h, stream, "xfmr_attn_bwd_kernels", 2.0 * M * F * 7 * kXfmrTab, 4.0 * M * (8.0 * F + 4.0 * kXfmrHeads * kXfmrBand));

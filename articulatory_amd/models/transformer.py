@@ -50,7 +50,11 @@ accumulation; the softmax statistics, dropout (the same masks), dS itself, dK, d
 bf16 MFMAs: each as a one-tap G^T A3 whose columns k cin + c hold frame t + k - 1 of channel c, zero outside the frame's own sequence.
 ``conv_blocks.0.conv1`` at other widths, ``residual_path`` and ``w_out`` keep exact fp32 weight gradients.  ``precision="bf16x3wac"`` is a
 ValueError.
-Not built: a k = 3 weight-gradient kernel that forms the three taps from one staged chunk, bf16 MFMAs for dK, dV and the tables' gradient.
+``train_precision="bf16x3wack"`` is the bf16x3wac step with, in addition, the attention's key-tiled backward on bf16 MFMAs: dK = dS^T Q / sqrt(d),
+dV = Pd^T dO and the first stage of the tables' gradient dE[h][r] = sum dS[., r] Q as hi hi + hi lo + lo hi with fp32 accumulation, from the
+same banded fp32 dS and Pd (dS, Pd and dQ themselves, the forward, the masks and the tape are bf16x3wac's bit for bit; no workspace of its
+own).  ``precision="bf16x3wack"`` is a ValueError.
+Not built: a k = 3 weight-gradient kernel that forms the three taps from one staged chunk, a key-major or pre-split copy of the dS / Pd bands.
 
 Not built, refused with ``NotImplementedError``: ``extra_art=True`` and ``num_ph`` (phoneme input).  ``forward(lengths=...)`` in train() mode
 is refused too (ragged training is asked for by name: ``forward_padded``).  The ``use_ar`` / ``ar_*`` / ``use_tanh`` / ``ph_emb_size``
@@ -211,8 +215,8 @@ class _PrecisionKeyword(type):
             raise ValueError(f"precision must be one of {sorted(_native.XFMR_PRECISIONS)}")
         if train_precision is None:
             train_precision = "f32"
-        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS_ALL:
-            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS_ALL)}")
+        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS_K:
+            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS_K)}")
         if precision != "f32" and train_precision != "f32":
             raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='{precision}' model is inference-only")
         self = super().__call__(*args, **kwargs)
@@ -285,10 +289,11 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         native handle is kept: its packs are rebuilt on the device.  A backward whose forward ran in the other arithmetic is refused
         (RuntimeError).  "bf16x3w": "bf16x3", and the weight and bias gradients of the one-tap layers at least 128 x 128 wide in the same
         arithmetic; "bf16x3wa": "bf16x3w", and the attention's query-tiled kernels on bf16 MFMAs; "bf16x3wac": "bf16x3wa", and the weight
-        gradients of the wide k = 3 convs on bf16 MFMAs (see the module's docstring).  Not with
+        gradients of the wide k = 3 convs on bf16 MFMAs; "bf16x3wack": "bf16x3wac", and the attention's dK, dV and table gradients on bf16
+        MFMAs (see the module's docstring).  Not with
         ``precision="bf16x3"`` (ValueError)."""
-        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS_ALL:
-            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS_ALL)}")
+        if not isinstance(train_precision, str) or train_precision not in _native.XFMR_TRAIN_PRECISIONS_K:
+            raise ValueError(f"train_precision must be one of {sorted(_native.XFMR_TRAIN_PRECISIONS_K)}")
         if train_precision != "f32" and self.precision != "f32":
             raise ValueError(f"train_precision='{train_precision}' needs precision='f32': a precision='{self.precision}' model is inference-only")
         if train_precision == self.train_precision:
@@ -296,7 +301,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         self.train_precision = train_precision
         if self.__dict__.get("_handle") is not None:
             with torch.cuda.device(self._device()):
-                _native.check(self._lib.hificar_xfmr_set_train_precision(self._handle, _native.XFMR_TRAIN_PRECISIONS_ALL[train_precision]),
+                _native.check(self._lib.hificar_xfmr_set_train_precision(self._handle, _native.XFMR_TRAIN_PRECISIONS_K[train_precision]),
                               "hificar_xfmr_set_train_precision")
 
     def _refuse_bf16x3_training(self):
@@ -471,7 +476,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                 _native.check(lib.hificar_xfmr_set_precision(handle, _native.XFMR_PRECISIONS[self.precision]), "hificar_xfmr_set_precision")
                 _native.check(lib.hificar_xfmr_finalize(handle), "hificar_xfmr_finalize")
                 if self.precision == "f32":  # (a bf16x3 inference handle has no training arithmetic to choose)
-                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.XFMR_TRAIN_PRECISIONS_ALL[self.train_precision]),
+                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.XFMR_TRAIN_PRECISIONS_K[self.train_precision]),
                                   "hificar_xfmr_set_train_precision")
             except Exception:
                 lib.hificar_xfmr_destroy(handle)

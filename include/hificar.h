@@ -82,6 +82,9 @@ extern "C" {
 #define HIFICAR_PREC_BF16X3WAC 6   /* hificar_xfmr_set_train_precision ONLY: bf16x3wa, and the weight gradients of the wide k = 3 ResBlock convs
                                       as one-tap GEMMs on tap-shifted split columns (v_mfma_f32_32x32x16_bf16) too; every other entry point
                                       that takes a precision refuses it (HIFICAR_E_INVALID) */
+#define HIFICAR_PREC_BF16X3WACK 8  /* hificar_xfmr_set_train_precision ONLY: bf16x3wac, and the attention's key-tiled backward (dK, dV and the
+                                      first stage of the position tables' gradient) on v_mfma_f32_16x16x32_bf16 too; every other entry point
+                                      that takes a precision refuses it (HIFICAR_E_INVALID).  5 and 7 are no arithmetic. */
 
 typedef struct hificar_handle hificar_handle;
 /* The conv engine every model of the library launches through (plans, schedules, stream ordering, profiling).  A generator handle
@@ -734,11 +737,11 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * All of these may be called after hificar_xfmr_finalize; the first one builds the training state.
  * The forward GEMMs and data gradients have an opt-in bf16x3 arithmetic (hificar_xfmr_set_train_precision, below).
  * The one-tap weight gradients have one too (HIFICAR_PREC_BF16X3W), and so have the attention's query-tiled kernels (HIFICAR_PREC_BF16X3WA)
- * and the weight gradients of the wide k = 3 convs (HIFICAR_PREC_BF16X3WAC).
- * Not built: a smaller tape per frame, a k = 3 weight-gradient kernel that forms the three taps from one staged chunk, dK / dV / the table gradient on bf16 MFMAs, extra_art, num_ph, multi-GPU training of this model. ---- */
+ * the weight gradients of the wide k = 3 convs (HIFICAR_PREC_BF16X3WAC) and the attention's key-tiled backward (HIFICAR_PREC_BF16X3WACK).
+ * Not built: a smaller tape per frame, a k = 3 weight-gradient kernel that forms the three taps from one staged chunk, a key-major or pre-split copy of the dS / Pd bands, extra_art, num_ph, multi-GPU training of this model. ---- */
 
 /* The arithmetic of the training step's GEMMs: HIFICAR_PREC_F32 (the default: the step above, bit for bit), HIFICAR_PREC_BF16X3,
- * HIFICAR_PREC_BF16X3W, HIFICAR_PREC_BF16X3WA or HIFICAR_PREC_BF16X3WAC.
+ * HIFICAR_PREC_BF16X3W, HIFICAR_PREC_BF16X3WA, HIFICAR_PREC_BF16X3WAC or HIFICAR_PREC_BF16X3WACK.
  * bf16x3: every forward GEMM of hificar_xfmr_forward_train / _ragged / _packed (the six ResBlock convs and residual_path, w_raw_in,
  * q | k | v, w_o, linear1, linear2, w_out) and every data gradient of the same layers runs as x w ~ hi hi + hi lo + lo hi on bf16 MFMAs with
  * fp32 accumulation, in the conv engine's bf16x3 kernels (hi = bf16(x), lo = bf16(x - hi), round to nearest even; split-K off: one
@@ -771,6 +774,13 @@ void hificar_xfmr_destroy(hificar_xfmr* h);
  * neighbouring sequence).  A3 is written in the split layout into the second of bf16x3w's two scratch buffers (3 cin_pad <= 3072): the
  * workspace is bf16x3wa's.  The bias gradient is the fp32 sum of hi + lo over the rows of G.  conv_blocks.0.conv1 at other widths,
  * residual_path and w_out stay on the exact fp32 kernels.  bf16x3w / bf16x3wa <-> bf16x3wac rebuilds no weight pack.
+ * bf16x3wack: the bf16x3wac step, bit for bit in every launch but the attention's key-tiled backward: dK^T += Q^T dS (the 1 / sqrt(d) scale in the
+ * epilogue), dV^T += dO^T Pd and the first stage of the position tables' gradient dE[h][r] = sum dS[., r] Q run as hi hi + hi lo + lo hi on
+ * v_mfma_f32_16x16x32_bf16 with fp32 accumulation, 32 queries (rows) per MFMA.  dO and Q rows are split on their way into LDS and read as the
+ * transposed operand; dS and Pd are read from the same banded fp32 buffers the query-tiled backward writes (dQ and those buffers are
+ * bf16x3wac's bit for bit) and split in registers (dK, dV) or on their way into LDS (the table gradient).  The second stage of the table
+ * gradient stays the ordered fp32 column sum.  Deterministic; padded keys and gap rows get the same zero dk | dv rows.  Workspace and tape are
+ * bf16x3wac's: no byte more.  Switching to or from any of bf16x3w / bf16x3wa / bf16x3wac rebuilds no weight pack.
  * Legal at any time on an f32 handle, also after hificar_xfmr_finalize and between steps: once parameters have been handed over, the packs of
  * the new arithmetic are rebuilt from the handle's device copy, in stream order behind the handle's last call.  A handle whose
  * hificar_xfmr_set_precision is bf16x3 (inference only): HIFICAR_E_STATE.  An unknown value: HIFICAR_E_INVALID.

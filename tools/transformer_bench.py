@@ -81,6 +81,15 @@ is below the fastest bf16x3wa window by more than the two spreads added), the bf
 convs' rows of one bf16x3wa step (wgrad_taps_kernel and its reductions, by layer shape) beside those of one bf16x3wac step (the k3 rows of
 wgrad_bf16x3_kernel, their reductions, xfmr_split_taps_t_kernel and what xfmr_split_rows_t_kernel takes above the bf16x3wa step's: the
 moved layers' G splits), from two further models built under HIFICAR_PROFILE_DETAIL=1, which take no part in the timed windows.
+
+   python tools/transformer_bench.py --train --train-precision bf16x3wack [--ragged] [--out profiles/transformer_train_bf16x3wack.txt]
+
+--train-precision bf16x3wack: the bf16x3, bf16x3w, bf16x3wa and bf16x3wac leg(s) above AND one more, train_precision="bf16x3wack" (the
+attention's key-tiled backward on bf16 MFMAs too), in the same alternation: its yardstick is the bf16x3wac leg of the same run.  The line
+carries bf16x3wack_ms, bf16x3wac_over_bf16x3wack (fastest bf16x3wac window over slowest bf16x3wack window), bf16x3wack_faster (the slowest
+bf16x3wack window is below the fastest bf16x3wac window by more than the two spreads added), the bf16x3wack step's per-kernel table and
+key_tiled_ms: xfmr_attn_bwd_k_kernels of the bf16x3wac leg's profiled step beside xfmr_attn16_bwd_k_kernel and xfmr_demb16_partial_kernel of
+the bf16x3wack leg's, and the ratio of the old row to the new pair's sum (below 1: the new pair is slower).
 Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
 import argparse
 import ctypes
@@ -137,6 +146,15 @@ def attention_rows(pw, pa):
             "backward": {"bf16x3w xfmr_attn_bwd_kernels": g(pw, "xfmr_attn_bwd_kernels"), "bf16x3wa xfmr_attn16_bwd_q_kernel": g(pa, "xfmr_attn16_bwd_q_kernel"),
                          "bf16x3wa xfmr_attn_bwd_k_kernels": g(pa, "xfmr_attn_bwd_k_kernels")},
             "cost": {"bf16x3wa xfmr_split_tab_kernel": g(pa, "xfmr_split_tab_kernel")}}
+
+
+def key_tiled_rows(pc, pk):
+    """The key-tiled attention backward's rows of a bf16x3wac step's profile (pc) beside a bf16x3wack step's (pk)."""
+    old = pc.get("xfmr_attn_bwd_k_kernels", 0.0)
+    new = {k: round(pk.get(k, 0.0), 4) for k in ("xfmr_attn16_bwd_k_kernel", "xfmr_demb16_partial_kernel")}
+    total = sum(new.values())
+    return {"bf16x3wac xfmr_attn_bwd_k_kernels": round(old, 4), **{"bf16x3wack " + k: v for k, v in new.items()}, "bf16x3wack_sum": round(total, 4),
+            "old_over_new": round(old / total, 3) if total else None}
 
 
 def detail_profile(arith, sd, p, run):
@@ -211,6 +229,7 @@ def train_main(a):
     fastw = w_opt = None
     fastwa = wa_opt = None
     fastwac = wac_opt = None
+    fastwack = wack_opt = None
 
     def leg(arith):
         m = Transformer(dropout=p, train_precision=arith, **PARAMS)
@@ -218,14 +237,16 @@ def train_main(a):
         m = m.cuda().train()
         return m, torch.optim.Adam(m.parameters(), lr=1e-4, fused=True)
 
-    if a.train_precision in ("bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac"):
+    if a.train_precision in ("bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac", "bf16x3wack"):
         fast, f_opt = leg("bf16x3")
-    if a.train_precision in ("bf16x3w", "bf16x3wa", "bf16x3wac"):
+    if a.train_precision in ("bf16x3w", "bf16x3wa", "bf16x3wac", "bf16x3wack"):
         fastw, w_opt = leg("bf16x3w")
-    if a.train_precision in ("bf16x3wa", "bf16x3wac"):
+    if a.train_precision in ("bf16x3wa", "bf16x3wac", "bf16x3wack"):
         fastwa, wa_opt = leg("bf16x3wa")
-    if a.train_precision == "bf16x3wac":
+    if a.train_precision in ("bf16x3wac", "bf16x3wack"):
         fastwac, wac_opt = leg("bf16x3wac")
+    if a.train_precision == "bf16x3wack":
+        fastwack, wack_opt = leg("bf16x3wack")
 
     def profile_step(m, opt):
         """{kernel: ms} of one step: the parameter hand-over behind the optimizer step before it, forward and backward."""
@@ -276,6 +297,11 @@ def train_main(a):
             F.l1_loss(fastwac(x), y).backward()
             wac_opt.step()
 
+        def fastwack_step(_):
+            wack_opt.zero_grad(set_to_none=True)
+            F.l1_loss(fastwack(x), y).backward()
+            wack_opt.step()
+
         for _ in range(2):
             native_step(None), stock_step(None)
             if fast is not None:
@@ -286,18 +312,22 @@ def train_main(a):
                 fastwa_step(None)
             if fastwac is not None:
                 fastwac_step(None)
+            if fastwack is not None:
+                fastwack_step(None)
         torch.cuda.synchronize()
         n1 = window(native_step, None, a.window)
         f1 = None if fast is None else window(fast_step, None, a.window)
         w1 = None if fastw is None else window(fastw_step, None, a.window)
         a1 = None if fastwa is None else window(fastwa_step, None, a.window)
         c1 = None if fastwac is None else window(fastwac_step, None, a.window)
+        k1 = None if fastwack is None else window(fastwack_step, None, a.window)
         s1 = window(stock_step, None, a.window)
         n2 = window(native_step, None, a.window)
         f2 = None if fast is None else window(fast_step, None, a.window)
         w2 = None if fastw is None else window(fastw_step, None, a.window)
         a2 = None if fastwa is None else window(fastwa_step, None, a.window)
         c2 = None if fastwac is None else window(fastwac_step, None, a.window)
+        k2 = None if fastwack is None else window(fastwack_step, None, a.window)
         s2 = window(stock_step, None, a.window)
         res = {"train": True, "B": B, "T": T, "dropout": p, "native_ms": [round(n1, 3), round(n2, 3)], "stock_ms": [round(s1, 3), round(s2, 3)],
                "native_spread": round(abs(n1 - n2) / min(n1, n2), 4), "stock_spread": round(abs(s1 - s2) / min(s1, s2), 4),
@@ -365,6 +395,16 @@ def train_main(a):
             res["families_ms"]["xfmr_split_taps_t"] = {"bf16x3wa": 0.0, "bf16x3wac": fam(pc, "xfmr_split_taps_t")}
             run = lambda m: F.l1_loss(m(x), y).backward()  # noqa: E731
             res["conv_wgrad_ms"] = conv_wgrad_rows(detail_profile("bf16x3wa", sd, p, run), detail_profile("bf16x3wac", sd, p, run))
+        if fastwack is not None:
+            res["bf16x3wack_ms"] = [round(k1, 3), round(k2, 3)]
+            res["bf16x3wack_spread"] = round(abs(k1 - k2) / min(k1, k2), 4)
+            res["bf16x3wac_over_bf16x3wack"] = round(min(c1, c2) / max(k1, k2), 3)
+            res["bf16x3wack_faster"] = bool(min(c1, c2) - max(k1, k2) > abs(c1 - c2) + abs(k1 - k2))
+            pk = profile_step(fastwack, wack_opt)
+            res["bf16x3wack_kernels_ms"] = {k: round(v, 4) for k, v in sorted(pk.items(), key=lambda kv: -kv[1])}
+            for pre in ("conv", "wgrad", "wreduce", "xfmr_attn", "xfmr_split_rows", "pack16", "xfmr_", "xfmr_split_rows_t", "xfmr_split_taps_t"):
+                res["families_ms"][pre]["bf16x3wack"] = fam(pk, pre)
+            res["key_tiled_ms"] = key_tiled_rows(pc, pk)
         lines.append(json.dumps(res))
         print(lines[-1], flush=True)
     if a.out:
@@ -405,7 +445,8 @@ def ragged_train_main(a):
     legs = {"native_packed": make(lambda: masked_l1_loss(m.forward_padded(x, lens32, packed=True), y, lens32)),
             "native_ragged": make(lambda: masked_l1_loss(m.forward_padded(x, lens32), y, lens32)), "native_dense": make(lambda: F.l1_loss(m(x), y))}
     ariths = {"bf16x3": ("bf16x3",), "bf16x3w": ("bf16x3", "bf16x3w"), "bf16x3wa": ("bf16x3", "bf16x3w", "bf16x3wa"),
-              "bf16x3wac": ("bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac")}.get(a.train_precision, ())
+              "bf16x3wac": ("bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac"),
+              "bf16x3wack": ("bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac", "bf16x3wack")}.get(a.train_precision, ())
     fast = {}
     for arith in ariths:  # the same batch through further models in the bf16x3 (and bf16x3w) training arithmetic, padded and packed
         m3 = Transformer(dropout=p, train_precision=arith, **PARAMS)
@@ -463,6 +504,10 @@ def ragged_train_main(a):
             a_, c_ = ms["bf16x3wa_" + form], ms["bf16x3wac_" + form]
             res[f"bf16x3wa_over_bf16x3wac_{form}"] = round(min(a_) / max(c_), 3)
             res[f"bf16x3wac_faster_{form}"] = bool(min(a_) - max(c_) > abs(a_[0] - a_[1]) + abs(c_[0] - c_[1]))
+        if "bf16x3wack_" + form in ms:
+            c_, k_ = ms["bf16x3wac_" + form], ms["bf16x3wack_" + form]
+            res[f"bf16x3wac_over_bf16x3wack_{form}"] = round(min(c_) / max(k_), 3)
+            res[f"bf16x3wack_faster_{form}"] = bool(min(c_) - max(k_) > abs(c_[0] - c_[1]) + abs(k_[0] - k_[1]))
     eng = m.engine()
     profs = {}
     for tag in ("packed", "ragged", "dense"):
@@ -491,6 +536,8 @@ def ragged_train_main(a):
         runs = {"packed": lambda m3: masked_l1_loss(m3.forward_padded(x, lens32, packed=True), y, lens32).backward(),
                 "ragged": lambda m3: masked_l1_loss(m3.forward_padded(x, lens32), y, lens32).backward()}
         res["conv_wgrad_ms"] = {tag: conv_wgrad_rows(detail_profile("bf16x3wa", sd, p, run), detail_profile("bf16x3wac", sd, p, run)) for tag, run in runs.items()}
+    if "bf16x3wack" in fast:
+        res["key_tiled_ms"] = {tag: key_tiled_rows(res[f"bf16x3wac_{tag}_kernels_ms"], res[f"bf16x3wack_{tag}_kernels_ms"]) for tag in ("packed", "ragged")}
     res["attention_recovered_ms"] = {k: round(profs["dense"].get(k, 0.0) - profs["ragged"].get(k, 0.0), 4)
                                      for k in ("xfmr_attn_kernel<train>", "xfmr_attn_bwd_kernels")}
     # packed over ragged per kernel family, to read beside packed_rows_over_padded_rows: conv_* are the forward GEMMs and the data gradients
@@ -516,9 +563,9 @@ def main():
     ap.add_argument("--no-stock", action="store_true")
     ap.add_argument("--precision", choices=("f32", "bf16x3", "bf16x3a"), default="f32",
                     help="bf16x3: add the bf16x3 leg to the native / stock alternation; bf16x3a: that leg and the bf16x3a leg")
-    ap.add_argument("--train-precision", choices=("f32", "bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac"), default="f32",
+    ap.add_argument("--train-precision", choices=("f32", "bf16x3", "bf16x3w", "bf16x3wa", "bf16x3wac", "bf16x3wack"), default="f32",
                     help="--train: bf16x3 adds the bf16x3 training leg(s); bf16x3w adds those and the bf16x3w leg(s); bf16x3wa those and the bf16x3wa leg(s); "
-                         "bf16x3wac those and the bf16x3wac leg(s)")
+                         "bf16x3wac those and the bf16x3wac leg(s); bf16x3wack those and the bf16x3wack leg(s)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--ragged", action="store_true", help="--train: the ragged batch's two legs instead of the dense shapes")
     ap.add_argument("--seed", type=int, default=0, help="--train --ragged: seed of the lengths")
