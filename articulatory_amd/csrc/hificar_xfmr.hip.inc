@@ -55,10 +55,76 @@ struct hificar_xfmr {
 
 static void xfmr_train_free(hificar_xfmr* g);
 
+// The arithmetics, one row per HIFICAR_PREC_* value: which setter takes it and what it switches on.
+//   x3  the GEMMs run in the engine's bf16x3 kernels        w  training: the one-tap GEMM-form weight gradients on bf16 MFMAs
+//   a   the attention's query-tiled kernels on bf16 MFMAs    c  training: the wide k = 3 convs' weight gradients on bf16 MFMAs
+//   k   training: the attention's key-tiled backward on bf16 MFMAs
+struct XfmrArith {
+    int value;
+    const char* name;
+    bool eval, train;  // hificar_xfmr_set_precision, hificar_xfmr_set_train_precision
+    bool x3, w, a, c, k;
+};
+static const XfmrArith kXfmrArith[] = {
+    {HIFICAR_PREC_F32, "f32", true, true, false, false, false, false, false},
+    {HIFICAR_PREC_BF16X3, "bf16x3", true, true, true, false, false, false, false},
+    {HIFICAR_PREC_BF16X3W, "bf16x3w", false, true, true, true, false, false, false},
+    {HIFICAR_PREC_BF16X3A, "bf16x3a", true, false, true, false, true, false, false},
+    {HIFICAR_PREC_BF16X3WA, "bf16x3wa", false, true, true, true, true, false, false},
+    {HIFICAR_PREC_BF16X3WAC, "bf16x3wac", false, true, true, true, true, true, false},
+    {HIFICAR_PREC_BF16X3WACK, "bf16x3wack", false, true, true, true, true, true, true},
+};
+// null: no such arithmetic
+static const XfmrArith* xfmr_arith_find(int p) {
+    for (const XfmrArith& a : kXfmrArith)
+        if (a.value == p) return &a;
+    return nullptr;
+}
+// (of a handle's own field: the setters let nothing else in)
+static const XfmrArith& xfmr_arith(int p) {
+    const XfmrArith* a = xfmr_arith_find(p);
+    return a ? *a : kXfmrArith[0];
+}
+static const char* xfmr_precision_name(int p) { return xfmr_arith(p).name; }
+
 // the handle's GEMMs run in the engine's bf16x3 kernels (bf16x3 and bf16x3a differ in the attention alone)
-static bool xfmr_x3(const hificar_xfmr* g) { return g->precision == HIFICAR_PREC_BF16X3 || g->precision == HIFICAR_PREC_BF16X3A; }
+static bool xfmr_x3(const hificar_xfmr* g) { return xfmr_arith(g->precision).x3; }
 
 static bool xfmr_head_dim_built(int d) { return d >= 16 && d <= 128 && d % 16 == 0; }
+
+// The one head-size dispatch: fn(std::integral_constant<int, D>) for the instantiation D = d.
+template <class Fn>
+static hipError_t xfmr_by_d(int d, Fn&& fn) {
+    switch (d) {
+        case 16: return fn(std::integral_constant<int, 16>());
+        case 32: return fn(std::integral_constant<int, 32>());
+        case 48: return fn(std::integral_constant<int, 48>());
+        case 64: return fn(std::integral_constant<int, 64>());
+        case 80: return fn(std::integral_constant<int, 80>());
+        case 96: return fn(std::integral_constant<int, 96>());
+        case 112: return fn(std::integral_constant<int, 112>());
+        case 128: return fn(std::integral_constant<int, 128>());
+    }
+    return hipErrorInvalidValue;
+}
+// ... and for every head size in turn, until one fails
+template <class Fn>
+static hipError_t xfmr_for_every_d(Fn&& fn) {
+    for (int d = 16; xfmr_head_dim_built(d); d += 16) {
+        const hipError_t e = xfmr_by_d(d, fn);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// one 256-thread launch of an attention kernel
+template <class... P, class... A>
+static hipError_t xfmr_launch(void (*kernel)(P...), dim3 grid, size_t lds_bytes, hipStream_t stream, const A&... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds_bytes, stream, args...);
+    return hipGetLastError();
+}
+
+static XfmrTab16 xfmr_tab16(const uint16_t* d_emb16, int d) { return {d_emb16, d_emb16 + (size_t)kXfmrHeads * kXfmrTabPad * d}; }
 
 static int xfmr_plan(ConvLayer& L, const std::string& name, int cin, int cin_pad, int cout, int K) {
     L.name = name;
@@ -183,14 +249,10 @@ static int xfmr_pack(hificar_engine* h, ConvLayer& L, const HostTensor& W, const
     return pack_w32(h, L, W, L.chunk16, &L.d_w32);
 }
 
-static const char* xfmr_precision_name(int p) {
-    return p == HIFICAR_PREC_BF16X3WACK ? "bf16x3wack" : p == HIFICAR_PREC_BF16X3WAC ? "bf16x3wac" : p == HIFICAR_PREC_BF16X3WA ? "bf16x3wa" : p == HIFICAR_PREC_BF16X3A ? "bf16x3a" : p == HIFICAR_PREC_BF16X3W ? "bf16x3w" : p == HIFICAR_PREC_BF16X3 ? "bf16x3" : "f32";
-}
-
 extern "C" int hificar_xfmr_set_precision(hificar_xfmr* g, int precision) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_precision: null handle");
-    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3A)
-        return fail(HIFICAR_E_INVALID, "unknown precision %d", precision);
+    const XfmrArith* a = xfmr_arith_find(precision);
+    if (!a || !a->eval) return fail(HIFICAR_E_INVALID, "unknown precision %d", precision);
     if (g->finalized)
         return fail(HIFICAR_E_STATE, "hificar_xfmr_set_precision after hificar_xfmr_finalize: the weights are packed for %s only; make a new handle",
                     xfmr_precision_name(g->precision));
@@ -222,28 +284,6 @@ static hipError_t xfmr_attn_attr() {
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_attn_kernel<D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)XfmrAttnLds<D>::bytes);
-}
-
-// split: the bf16x3 forward's instantiation, which stores split rows
-template <int D>
-static hipError_t xfmr_attn_launch_one(const XfmrAttnParams& p, dim3 grid, hipStream_t stream, bool split) {
-    if (split) hipLaunchKernelGGL((xfmr_attn_kernel<D, false, true>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
-    else hipLaunchKernelGGL((xfmr_attn_kernel<D>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
-    return hipGetLastError();
-}
-
-static hipError_t xfmr_attn_launch(int d, const XfmrAttnParams& p, dim3 grid, hipStream_t stream, bool split = false) {
-    switch (d) {
-        case 16: return xfmr_attn_launch_one<16>(p, grid, stream, split);
-        case 32: return xfmr_attn_launch_one<32>(p, grid, stream, split);
-        case 48: return xfmr_attn_launch_one<48>(p, grid, stream, split);
-        case 64: return xfmr_attn_launch_one<64>(p, grid, stream, split);
-        case 80: return xfmr_attn_launch_one<80>(p, grid, stream, split);
-        case 96: return xfmr_attn_launch_one<96>(p, grid, stream, split);
-        case 112: return xfmr_attn_launch_one<112>(p, grid, stream, split);
-        case 128: return xfmr_attn_launch_one<128>(p, grid, stream, split);
-    }
-    return hipErrorInvalidValue;
 }
 
 extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
@@ -297,7 +337,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
         if ((rc = linear(E.l1, b + "linear1")) != HIFICAR_OK) return rc;
         if ((rc = linear(E.l2, b + "linear2")) != HIFICAR_OK) return rc;
         if ((rc = upload(h, g->tensors.at(b + "self_attn.relative_positional.embeddings").data, &E.d_emb)) != HIFICAR_OK) return rc;
-        if (g->precision == HIFICAR_PREC_BF16X3A) {  // the tables as the attention's MFMA operand: split once, padded to whole 16-row tiles
+        if (xfmr_arith(g->precision).a) {  // the tables as the attention's MFMA operand: split once, padded to whole 16-row tiles
             const std::vector<float>& src = g->tensors.at(b + "self_attn.relative_positional.embeddings").data;
             const size_t half = (size_t)kXfmrHeads * kXfmrTabPad * d;
             std::vector<uint16_t> t16(2 * half, 0);
@@ -319,15 +359,8 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
         for (const char* n : {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"})
             if ((rc = upload(h, g->tensors.at(b + n).data, &E.d_ln[i++])) != HIFICAR_OK) return rc;
     }
-    HIP_TRY(xfmr_attn_attr<16>());
-    HIP_TRY(xfmr_attn_attr<32>());
-    HIP_TRY(xfmr_attn_attr<48>());
-    HIP_TRY(xfmr_attn_attr<64>());
-    HIP_TRY(xfmr_attn_attr<80>());
-    HIP_TRY(xfmr_attn_attr<96>());
-    HIP_TRY(xfmr_attn_attr<112>());
-    HIP_TRY(xfmr_attn_attr<128>());
-    if (g->precision == HIFICAR_PREC_BF16X3A) HIP_TRY(xfmr_attn16_attr_all());
+    HIP_TRY(xfmr_for_every_d([](auto D) { return xfmr_attn_attr<D()>(); }));
+    if (xfmr_arith(g->precision).a) HIP_TRY(xfmr_for_every_d([](auto D) { return xfmr_attn16_attr<D()>(); }));
     // the engine opens here, not in hificar_xfmr_create: a handle can be created and described without a device
     if ((rc = engine_open(h, true)) != HIFICAR_OK) return rc;
     h->precision = xfmr_x3(g) ? HIFICAR_PREC_BF16X3 : HIFICAR_PREC_F32;
@@ -417,7 +450,7 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
     Ragged rg;
     rg.seq_len = lengths;
     rg.frames = T;
-    const bool x3 = xfmr_x3(g), a16 = g->precision == HIFICAR_PREC_BF16X3A;
+    const bool x3 = xfmr_x3(g), a16 = xfmr_arith(g->precision).a;
     if (x3 && g->taps.count("conv_blocks")) return fail(HIFICAR_E_INVALID, "debug tap 'conv_blocks': a bf16x3 handle holds these rows as split bf16 rows only");
     // one launch of one layer: xs -> y (fp32) and / or ys (the activated copy: ReLU, or with slope 1 the identity), + res.  xs and ys are fp32
     // rows in exact fp32 and split rows in bf16x3; res_relu (bf16x3): res holds the rows before their ReLU
@@ -496,15 +529,15 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
         if (a16) {
             XfmrAttn16Params p;
             p.qkv = reinterpret_cast<const char*>(ws.wide);
-            p.emb_hi = E.d_emb16;
-            p.emb_lo = E.d_emb16 + (size_t)kXfmrHeads * kXfmrTabPad * d;
+            p.tab = xfmr_tab16(E.d_emb16, d);
             p.lengths = lengths;
             p.out = reinterpret_cast<char*>(ws.r[1]);
             p.T = T;
             p.F = F;
             p.scale = (float)(1.0 / std::sqrt((double)d));
             ProfScope prof(h, stream, "xfmr_attn16_kernel", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
-            const hipError_t e = xfmr_attn16_launch(d, p, dim3((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B), stream);
+            const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B);
+            const hipError_t e = xfmr_by_d(d, [&](auto D) { return xfmr_launch(xfmr_attn16_kernel<D()>, grid, XfmrAttn16Lds<D()>::bytes, stream, p); });
             if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn16_kernel launch failed: %s", hipGetErrorString(e));
         } else {
             XfmrAttnParams p;
@@ -517,7 +550,11 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
             p.scale = (float)(1.0 / std::sqrt((double)d));
             // per query at most 199 keys: Q K^T, the positional product and P V
             ProfScope prof(h, stream, x3 ? "xfmr_attn_kernel<split>" : "xfmr_attn_kernel", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
-            const hipError_t e = xfmr_attn_launch(d, p, dim3((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B), stream, x3);
+            const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B);
+            // (bf16x3: the instantiation that stores split rows)
+            const hipError_t e = xfmr_by_d(d, [&](auto D) {
+                return xfmr_launch(x3 ? xfmr_attn_kernel<D(), false, true> : xfmr_attn_kernel<D()>, grid, XfmrAttnLds<D()>::bytes, stream, p);
+            });
             if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn_kernel launch failed: %s", hipGetErrorString(e));
         }
         if ((rc = conv(E.wo, ws.r[1], X, ws.r[2], nullptr)) != HIFICAR_OK) return rc;

@@ -14,12 +14,9 @@
 // contraction runs over rows, so BOTH operands are read transposed: the dS block is staged split as [64][hi: 208 | lo: 208] bf16, the Q rows
 // as in the other kernel.  Wave w owns the table-row tiles w, w + 4, w + 8 (and 12: wave 0), as in the fp32 kernel.
 //
-// LDS images (bytes).  dO, Q rows: [64][hi: DP bf16 | lo: DP bf16 | 32], DP = D rounded up to 32 (XfmrAttn16TrainLds's row; the padded
-// channels are zeros, written once, never staged over).  dS rows: [64][hi: 416 | lo: 416 | 96].  Both pitches are 32 or 160 (mod 256), so the
-// 8 rows x 32 bytes a 32-lane half reads transposed start at 8 different multiples of 32 in the 256-byte bank row (r 32 or r 160 mod 256,
-// r = 0 .. 7: all distinct): conflict-free by the bank rule at every head size.  The largest images (D = 128): 69 632 bytes (dK, dV) and
-// 94 208 bytes (dE).  Every transposed read is 8-byte aligned and runs with EXEC all ones: no lane leaves before the end, and the only
-// branches around a read are wave-uniform.
+// LDS images (bytes).  dO, Q rows: the common row image.  dS rows: [64][hi: 416 | lo: 416 | 96].  Both pitches are 32 or 160 (mod 256):
+// conflict-free transposed reads by the bank rule at every head size.  The largest images (D = 128): 69 632 bytes (dK, dV) and 94 208
+// bytes (dE).
 //
 // The order of every sum depends on the key's (table row's) position and the sequence's length only.  Rows past a block's count, padded
 // frames and padded channels are zero operands on the staged side, never read from memory; a band entry is read only where the query-tiled
@@ -33,67 +30,23 @@ constexpr int kXfmrEmb16Pitch = 4 * kXfmrEmbPitch + 96;  // bytes per staged dS 
 
 template <int D>
 struct XfmrAttn16BwdKLds {
-    using R = XfmrAttn16TrainLds<D>;
-    static constexpr size_t bytes = (size_t)2 * R::img_bytes;  // dO rows, Q rows
+    static constexpr size_t bytes = (size_t)2 * XfmrAttn16Row<D>::img_bytes;  // dO rows, Q rows
 };
 
 template <int D>
 struct XfmrEmb16Lds {
-    using R = XfmrAttn16TrainLds<D>;
     static constexpr int ds_bytes = 64 * kXfmrEmb16Pitch;
-    static constexpr size_t bytes = (size_t)ds_bytes + R::img_bytes;  // dS block, Q rows
-};
-
-// This thread's share of a 64-query block: D / 16 pieces of 8 channels.  Piece u = tid + 256 i is piece (u mod 2 CPR) of query row
-// u / (2 CPR); a row's pieces are dO, then Q, CPR = D / 8 each.  Source and destination offsets are the same for every block.
-template <int D>
-struct XfmrAttn16StageQ {
-    using L = XfmrAttn16TrainLds<D>;
-    static constexpr int NP = D / 16, CPR = D / 8;
-    int row[NP], src[NP], dst[NP];
-    bool isq[NP];
-    float4 a[NP], b[NP];
-    __device__ __forceinline__ void init(int tid, int F, int h) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int u = tid + 256 * i, r = u / (2 * CPR), w = u - r * (2 * CPR), part = w / CPR, ch = w - part * CPR;
-            row[i] = r;
-            isq[i] = part != 0;
-            src[i] = r * (part ? 3 * F : F) + h * D + 8 * ch;
-            dst[i] = part * L::img_bytes + r * L::PK + 16 * ch;
-        }
-    }
-    // rows at or past n are zeros, never read
-    __device__ __forceinline__ void fetch(const float* dout, const float* qkv, int n) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            a[i] = b[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row[i] < n) {
-                const float* s = (isq[i] ? qkv : dout) + src[i];
-                a[i] = *reinterpret_cast<const float4*>(s);
-                b[i] = *reinterpret_cast<const float4*>(s + 4);
-            }
-        }
-    }
-    __device__ __forceinline__ void commit(char* lds) const {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            bf16x8 hi, lo;
-            xfmr_split8(a[i], b[i], hi, lo);
-            *reinterpret_cast<bf16x8*>(lds + dst[i]) = hi;
-            *reinterpret_cast<bf16x8*>(lds + dst[i] + 2 * L::DP) = lo;
-        }
-    }
+    static constexpr size_t bytes = (size_t)ds_bytes + XfmrAttn16Row<D>::img_bytes;  // dS block, Q rows
 };
 
 template <int D>
 __global__ __launch_bounds__(256) void xfmr_attn16_bwd_k_kernel(const XfmrAttnBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char xfmr16_lds[];
-    using L = XfmrAttn16TrainLds<D>;
-    constexpr int DP = L::DP, PK = L::PK, NM = D / 16;
+    using R = XfmrAttn16Row<D>;
+    constexpr int DP = R::DP, PK = R::PK, NM = R::NM;
     static_assert(kXfmrKB == 64, "the staging shares are for 64-query blocks and 256 threads");
     char* const doimg = xfmr16_lds;
-    char* const qimg = xfmr16_lds + L::img_bytes;
+    char* const qimg = xfmr16_lds + R::img_bytes;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 15, g = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, k0 = blockIdx.x * kXfmrKB;
@@ -112,9 +65,9 @@ __global__ __launch_bounds__(256) void xfmr_attn16_bwd_k_kernel(const XfmrAttnBw
     }
 
     // the padded channels of both images are zeros from here on: the staging never writes them
-    for (int i = tid; i < 2 * L::img_bytes / 16; i += 256) *reinterpret_cast<uint4*>(xfmr16_lds + 16 * i) = make_uint4(0u, 0u, 0u, 0u);
+    xfmr_attn16_zero(xfmr16_lds, 2 * R::img_bytes, tid);
 
-    XfmrAttn16StageQ<D> st;
+    XfmrAttn16Stage<D, XfmrAttn16SrcDoQ> st;
     st.init(tid, p.F, h);
     const int q_lo = max(0, k0 - (kXfmrRel - 1));
     const int q_hi = min(len, k0 + kXfmrKB + (kXfmrRel - 1));
@@ -126,8 +79,8 @@ __global__ __launch_bounds__(256) void xfmr_attn16_bwd_k_kernel(const XfmrAttnBw
     f32x4 dv[NM], dk[NM];
 #pragma unroll
     for (int j = 0; j < NM; ++j) dv[j] = dk[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // this lane's address for the transposed read of queries 4 g .. 4 g + 3, channels 0 .. 15: row 4 g + (c >> 2), channels 4 (c & 3) ..
-    const int troff = (4 * g + (c >> 2)) * PK + 8 * (c & 3);
+    const char* const dotr = xfmr_attn16_tr_ptr<PK>(doimg, c, g);
+    const char* const qtr = xfmr_attn16_tr_ptr<PK>(qimg, c, g);
 
     for (int qb = q_lo; qb < q_hi; qb += kXfmrKB) {
         const int n = min(kXfmrKB, q_hi - qb);
@@ -140,7 +93,7 @@ __global__ __launch_bounds__(256) void xfmr_attn16_bwd_k_kernel(const XfmrAttnBw
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int q32 = qb + 32 * t;
-            act[t] = 32 * t < n && q32 + 31 >= kw - (kXfmrRel - 1) && q32 <= kw + 15 + (kXfmrRel - 1);
+            act[t] = xfmr_attn16_step_meets(t, n, q32, kw);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 pv[t][u] = sv[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -149,7 +102,7 @@ __global__ __launch_bounds__(256) void xfmr_attn16_bwd_k_kernel(const XfmrAttnBw
                 for (int i = 0; i < 4; ++i) {
                     const int q = q32 + 16 * u + 4 * g + i;
                     const int rel = k - q + (kXfmrRel - 1);
-                    if (kok && q < qb + n && rel >= 0 && rel < kXfmrTab) {
+                    if (xfmr_attn16_in_band(kok, q, qb + n, rel)) {
                         const size_t e = xfmr_band_row(p.lay, row0, b, h, q, p.T) * kXfmrBand + rel;
                         pv[t][u][i] = p.pd[e];
                         sv[t][u][i] = p.ds[e];
@@ -163,13 +116,8 @@ __global__ __launch_bounds__(256) void xfmr_attn16_bwd_k_kernel(const XfmrAttnBw
             bf16x8 ph, pl, sh, sl;
             xfmr_split_b(pv[t][0], pv[t][1], ph, pl);
             xfmr_split_b(sv[t][0], sv[t][1], sh, sl);
-            const char* ad = doimg + troff + 32 * t * PK;
-            const char* aq = qimg + troff + 32 * t * PK;
-#pragma unroll
-            for (int j = 0; j < NM; ++j) {
-                dv[j] = xfmr_attn16_mfma3(xfmr_attn16_vfrag<PK>(ad + 32 * j), xfmr_attn16_vfrag<PK>(ad + 2 * DP + 32 * j), ph, pl, dv[j]);
-                dk[j] = xfmr_attn16_mfma3(xfmr_attn16_vfrag<PK>(aq + 32 * j), xfmr_attn16_vfrag<PK>(aq + 2 * DP + 32 * j), sh, sl, dk[j]);
-            }
+            xfmr_attn16_tr_dot<NM, PK, 2 * DP>(dotr + 32 * t * PK, ph, pl, dv);
+            xfmr_attn16_tr_dot<NM, PK, 2 * DP>(qtr + 32 * t * PK, sh, sl, dk);
         }
         if (!more) break;
         __syncthreads();  // every wave has read this block
@@ -188,28 +136,16 @@ __global__ __launch_bounds__(256) void xfmr_attn16_bwd_k_kernel(const XfmrAttnBw
     }
 }
 
-// four fp32 values -> 4 hi and 4 lo bf16, 8 bytes each
-__device__ __forceinline__ void xfmr_split4(const float4& x, uint2& hi, uint2& lo) {
-    const float v[4] = {x.x, x.y, x.z, x.w};
-    uint16_t hb[4], lb[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const __bf16 a = (__bf16)v[e], b = (__bf16)(v[e] - (float)a);
-        hb[e] = __builtin_bit_cast(uint16_t, a);
-        lb[e] = __builtin_bit_cast(uint16_t, b);
-    }
-    hi = make_uint2((unsigned)hb[0] | ((unsigned)hb[1] << 16), (unsigned)hb[2] | ((unsigned)hb[3] << 16));
-    lo = make_uint2((unsigned)lb[0] | ((unsigned)lb[1] << 16), (unsigned)lb[2] | ((unsigned)lb[3] << 16));
-}
+typedef __bf16 xfmr_bf16x4 __attribute__((ext_vector_type(4)));
 
 template <int D>
 __global__ __launch_bounds__(256) void xfmr_demb16_partial_kernel(const float* __restrict__ qkv, const float* __restrict__ ds, float* __restrict__ partial,
                                                                   int M, int T, int F, const BigruTapeHeader* hdr, const int* __restrict__ tape_lens,
                                                                   const XfmrLayout lay) {
     extern __shared__ __attribute__((aligned(16))) char xfmr16_lds[];
-    using L = XfmrAttn16TrainLds<D>;
+    using R = XfmrAttn16Row<D>;
     using E = XfmrEmb16Lds<D>;
-    constexpr int DP = L::DP, PK = L::PK, NM = D / 16, PS = kXfmrEmb16Pitch, NT = kXfmrEmbPitch / 16;
+    constexpr int DP = R::DP, PK = R::PK, NM = R::NM, PS = kXfmrEmb16Pitch, NT = kXfmrEmbPitch / 16;
     static_assert(kXfmrBand % 4 == 0 && kXfmrBand <= kXfmrEmbPitch && kXfmrEmbRows % 64 == 0, "the staging of a dS block");
     char* const dimg = xfmr16_lds;
     char* const qimg = xfmr16_lds + E::ds_bytes;
@@ -220,16 +156,15 @@ __global__ __launch_bounds__(256) void xfmr_demb16_partial_kernel(const float* _
     const int* const lens = bigru_tape_lens(hdr, tape_lens);
 
     // columns 200 .. 207 of the dS rows and the padded channels of the Q rows are zeros from here on: the staging never writes them
-    for (int i = tid; i < (int)(E::bytes / 16); i += 256) *reinterpret_cast<uint4*>(xfmr16_lds + 16 * i) = make_uint4(0u, 0u, 0u, 0u);
+    xfmr_attn16_zero(xfmr16_lds, (int)E::bytes, tid);
 
     f32x4 acc[4][NM];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int j = 0; j < NM; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // this lane's offsets for the transposed reads of rows 4 g .. 4 g + 3: row 4 g + (c >> 2), columns 4 (c & 3) .. of a 16-column tile
-    const char* const atr = dimg + (4 * g + (c >> 2)) * PS + 8 * (c & 3);
-    const char* const btr = qimg + (4 * g + (c >> 2)) * PK + 8 * (c & 3);
+    const char* const atr = xfmr_attn16_tr_ptr<PS>(dimg, c, g);
+    const char* const btr = xfmr_attn16_tr_ptr<PK>(qimg, c, g);
 
     for (int blk = 0; blk < kXfmrEmbRows / 64; ++blk) {
         const int r0 = chunk * kXfmrEmbRows + blk * 64;
@@ -266,12 +201,15 @@ __global__ __launch_bounds__(256) void xfmr_demb16_partial_kernel(const float* _
                 const size_t band = lay.pad_row ? (size_t)row * kXfmrHeads + h : ((size_t)bb * kXfmrHeads + h) * T + t;
                 x = *reinterpret_cast<const float4*>(ds + band * kXfmrBand + 4 * v);
             }
-            uint2 hi, lo;
-            xfmr_split4(x, hi, lo);
-            *reinterpret_cast<uint2*>(dimg + rr * PS + 8 * v) = hi;
-            *reinterpret_cast<uint2*>(dimg + rr * PS + 2 * kXfmrEmbPitch + 8 * v) = lo;
+            const float v4[4] = {x.x, x.y, x.z, x.w};
+            xfmr_bf16x4 hi, lo;
+            xfmr_split_n(v4, hi, lo);
+            *reinterpret_cast<xfmr_bf16x4*>(dimg + rr * PS + 8 * v) = hi;
+            *reinterpret_cast<xfmr_bf16x4*>(dimg + rr * PS + 2 * kXfmrEmbPitch + 8 * v) = lo;
         }
         __syncthreads();
+        // (the transposed product with its B fragments hoisted out of the table-row tiles: xfmr_attn16_tr_dot's statement, the A operand
+        // on the dS pitch)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             if (32 * s >= n) continue;  // (the whole workgroup)
@@ -314,19 +252,6 @@ static hipError_t xfmr_attn16_train_k_attr() {
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&xfmr_demb16_partial_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)XfmrEmb16Lds<D>::bytes);
-}
-
-template <int D>
-static hipError_t xfmr_attn16_bwd_k_launch(const XfmrAttnBwdParams& p, dim3 grid, hipStream_t stream) {
-    hipLaunchKernelGGL((xfmr_attn16_bwd_k_kernel<D>), grid, dim3(256), XfmrAttn16BwdKLds<D>::bytes, stream, p);
-    return hipGetLastError();
-}
-
-template <int D>
-static hipError_t xfmr_demb16_partial_launch(const XfmrAttnBwdParams& p, float* emb_partial, int M, int chunks, hipStream_t stream) {
-    hipLaunchKernelGGL((xfmr_demb16_partial_kernel<D>), dim3((unsigned)chunks, kXfmrHeads), dim3(256), XfmrEmb16Lds<D>::bytes, stream, p.qkv, p.ds, emb_partial,
-                       M, p.T, p.F, p.hdr, p.lens, p.lay);
-    return hipGetLastError();
 }
 
 }  // namespace hificar

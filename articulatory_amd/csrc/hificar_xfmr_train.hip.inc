@@ -82,10 +82,6 @@ static void xfmr_train_free(hificar_xfmr* g) {
     g->train = nullptr;
 }
 
-#define HIFICAR_XFMR_BY_D(fn, d, ...)                                                                                                     \
-    ((d) == 16 ? fn<16>(__VA_ARGS__) : (d) == 32 ? fn<32>(__VA_ARGS__) : (d) == 48 ? fn<48>(__VA_ARGS__) : (d) == 64 ? fn<64>(__VA_ARGS__) \
-     : (d) == 80 ? fn<80>(__VA_ARGS__) : (d) == 96 ? fn<96>(__VA_ARGS__) : (d) == 112 ? fn<112>(__VA_ARGS__) : fn<128>(__VA_ARGS__))
-
 template <int D>
 static hipError_t xfmr_train_attr() {
     static_assert(XfmrAttnLds<D>::bytes <= 160 * 1024 && XfmrEmbLds<D>::bytes <= 160 * 1024, "the attention kernels' LDS");
@@ -101,12 +97,6 @@ static hipError_t xfmr_train_attr() {
     if (e != hipSuccess) return e;
     if ((e = xfmr_attn16_train_attr<D>()) != hipSuccess) return e;
     return xfmr_attn16_train_k_attr<D>();
-}
-
-template <int D>
-static hipError_t xfmr_attn_train_launch(const XfmrAttnParams& p, dim3 grid, hipStream_t stream) {
-    hipLaunchKernelGGL((xfmr_attn_kernel<D, true>), grid, dim3(256), XfmrAttnLds<D>::bytes, stream, p);
-    return hipGetLastError();
 }
 
 // the key-tiled side of the attention backward: dK, dV and the table gradient's partials, from the banded dS and Pd a query-tiled kernel wrote
@@ -133,11 +123,12 @@ static int xfmr_alloc(hificar_engine* h, size_t bytes, void** out) {
     return HIFICAR_OK;
 }
 
-static bool xfmr_train_x3(const hificar_xfmr* g) { return g->train_precision != HIFICAR_PREC_F32; }  // bf16x3, bf16x3w or bf16x3wa: the same GEMMs and packs
-static bool xfmr_train_k(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WACK; }  // the attention's key-tiled backward on bf16 MFMAs
-static bool xfmr_train_c(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WAC || xfmr_train_k(g); }  // the wide k = 3 convs' weight gradients on bf16 MFMAs
-static bool xfmr_train_a(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3WA || xfmr_train_c(g); }  // the attention's query-tiled kernels on bf16 MFMAs
-static bool xfmr_train_w(const hificar_xfmr* g) { return g->train_precision == HIFICAR_PREC_BF16X3W || xfmr_train_a(g); }
+// what the training arithmetic switches on (kXfmrArith); x3: every bf16x3 training arithmetic has the same GEMMs and packs
+static bool xfmr_train_x3(const hificar_xfmr* g) { return xfmr_arith(g->train_precision).x3; }
+static bool xfmr_train_w(const hificar_xfmr* g) { return xfmr_arith(g->train_precision).w; }
+static bool xfmr_train_a(const hificar_xfmr* g) { return xfmr_arith(g->train_precision).a; }
+static bool xfmr_train_c(const hificar_xfmr* g) { return xfmr_arith(g->train_precision).c; }
+static bool xfmr_train_k(const hificar_xfmr* g) { return xfmr_arith(g->train_precision).k; }
 // three taps, one phase, at least 128 x 128, and the three taps' columns side by side fit a split buffer: the one-tap GEMM form on tap-shifted columns
 static bool wgrad_gemm3_form(const ConvLayer& L) {
     return L.K == 3 && L.ntaps == 3 && L.n_phase == 1 && L.n_blocks32 >= 4 && (L.cin_pad + 31) / 32 >= 4 && 3 * L.cin_pad <= kXfmrFF;
@@ -303,14 +294,7 @@ static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts) {
         if ((rc = make_dgrad_layer(h, L.l2, D.dg_l2, nullptr)) != HIFICAR_OK) return rc;
     }
     if ((rc = wgrad_setup()) != HIFICAR_OK) return rc;
-    HIP_TRY(xfmr_train_attr<16>());
-    HIP_TRY(xfmr_train_attr<32>());
-    HIP_TRY(xfmr_train_attr<48>());
-    HIP_TRY(xfmr_train_attr<64>());
-    HIP_TRY(xfmr_train_attr<80>());
-    HIP_TRY(xfmr_train_attr<96>());
-    HIP_TRY(xfmr_train_attr<112>());
-    HIP_TRY(xfmr_train_attr<128>());
+    HIP_TRY(xfmr_for_every_d([](auto D) { return xfmr_train_attr<D()>(); }));
     return HIFICAR_OK;
 }
 
@@ -504,18 +488,16 @@ static int xfmr_split_tables(hificar_xfmr* g, hipStream_t stream) {
 // records the choice.  Afterwards the packs of the new arithmetic are rebuilt from the master copy, behind the handle's last call.
 extern "C" int hificar_xfmr_set_train_precision(hificar_xfmr* g, int precision) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_train_precision: null handle");
-    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3W && precision != HIFICAR_PREC_BF16X3WA &&
-        precision != HIFICAR_PREC_BF16X3WAC && precision != HIFICAR_PREC_BF16X3WACK)
-        return fail(HIFICAR_E_INVALID, "unknown training precision %d", precision);
+    const XfmrArith* to = xfmr_arith_find(precision);
+    if (!to || !to->train) return fail(HIFICAR_E_INVALID, "unknown training precision %d", precision);
     if (g->precision != HIFICAR_PREC_F32)
         return fail(HIFICAR_E_STATE, "this Transformer handle is packed for the %s inference arithmetic: it has no training step, in either arithmetic",
                     xfmr_precision_name(g->precision));
     if (precision == g->train_precision) return HIFICAR_OK;
     // (among bf16x3, bf16x3w, bf16x3wa, bf16x3wac and bf16x3wack: the same packs, other weight-gradient or attention kernels; towards one of the
     // last three from one of the first two the tables are split)
-    const bool same_packs = precision != HIFICAR_PREC_F32 && xfmr_train_x3(g);
-    const bool to_a = precision == HIFICAR_PREC_BF16X3WA || precision == HIFICAR_PREC_BF16X3WAC || precision == HIFICAR_PREC_BF16X3WACK;
-    if (!g->train || !g->train->have_params || (same_packs && (!to_a || xfmr_train_a(g)))) {
+    const bool same_packs = to->x3 && xfmr_train_x3(g);
+    if (!g->train || !g->train->have_params || (same_packs && (!to->a || xfmr_train_a(g)))) {
         g->train_precision = precision;
         return HIFICAR_OK;
     }
@@ -774,6 +756,14 @@ struct XfmrTrainCtx {
         return gate(ys, ys, ys, (long long)M * L.cout_pad, -1);
     }
     bool x3() const { return xfmr_train_x3(g); }
+    // one profile row of attention launches at head size d: launch(std::integral_constant<int, D>) enqueues them
+    template <class Launch>
+    int attn(const char* row, double flops, double bytes, const char* what, int d, Launch&& launch) const {
+        ProfScope prof(h, stream, row, flops, bytes);
+        const hipError_t e = xfmr_by_d(d, launch);
+        if (e != hipSuccess) return fail(HIFICAR_E_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+        return HIFICAR_OK;
+    }
     // fp32 rows [M][C] -> the split scratch (rows of padded frames and gap rows: zero bits, not read)
     int split_rows(const float* x, int C) const {
         const long long n8 = (long long)M * C / 8;
@@ -1041,17 +1031,14 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
             const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B);
             if (xfmr_train_a(g)) {  // bf16x3wa: the same statements on bf16 MFMAs, the tables as xfmr_split_tables left them
                 if (!E.d_emb16) return fail(HIFICAR_E_INVALID, "internal: bf16x3wa forward without split position tables");
-                XfmrAttn16TrainParams p16;
-                p16.f = p;
-                p16.emb_hi = E.d_emb16;
-                p16.emb_lo = E.d_emb16 + (size_t)kXfmrHeads * kXfmrTabPad * d;
-                ProfScope prof(h, stream, "xfmr_attn16_kernel<train>", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
-                const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn16_train_launch, d, p16, grid, stream);
-                if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn16_train_kernel launch failed: %s", hipGetErrorString(e));
+                const XfmrAttn16TrainParams p16 = {p, xfmr_tab16(E.d_emb16, d)};
+                XT(cx.attn("xfmr_attn16_kernel<train>", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F, "xfmr_attn16_train_kernel", d, [&](auto D) {
+                    return xfmr_launch(xfmr_attn16_train_kernel<D()>, grid, XfmrAttn16TrainLds<D()>::bytes, stream, p16);
+                }));
             } else {
-                ProfScope prof(h, stream, "xfmr_attn_kernel<train>", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F);
-                const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_train_launch, d, p, grid, stream);
-                if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn_kernel launch failed: %s", hipGetErrorString(e));
+                XT(cx.attn("xfmr_attn_kernel<train>", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * 4 * F, "xfmr_attn_kernel", d, [&](auto D) {
+                    return xfmr_launch(xfmr_attn_kernel<D(), true>, grid, XfmrAttnLds<D()>::bytes, stream, p);
+                }));
             }
         }
         XT(cx.conv(E.wo, L.o, nullptr, ws.t1, nullptr));
@@ -1247,34 +1234,25 @@ static int xfmr_backward_impl(hificar_xfmr* g, const float* dout, int B, int T, 
             const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), kXfmrHeads, (unsigned)B);
             if (xfmr_train_a(g)) {  // bf16x3wa: S, dPd and both parts of dQ on bf16 MFMAs; dK, dV, dE in the fp32 kernels, on the same banded buffers
                 if (!L.d_emb16) return fail(HIFICAR_E_INVALID, "internal: bf16x3wa backward without split position tables");
-                XfmrAttn16BwdParams p16;
-                p16.b = p;
-                p16.emb_hi = L.d_emb16;
-                p16.emb_lo = L.d_emb16 + (size_t)kXfmrHeads * kXfmrTabPad * d;
-                {
-                    ProfScope prof(h, stream, "xfmr_attn16_bwd_q_kernel", 2.0 * M * F * 4 * kXfmrTab, 4.0 * M * (6.0 * F + 2.0 * kXfmrHeads * kXfmrBand));
-                    const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn16_bwd_q_launch, d, p16, grid, stream);
-                    if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn16_bwd_q_kernel launch failed: %s", hipGetErrorString(e));
-                }
+                const XfmrAttn16BwdParams p16 = {p, xfmr_tab16(L.d_emb16, d)};
+                XT(cx.attn("xfmr_attn16_bwd_q_kernel", 2.0 * M * F * 4 * kXfmrTab, 4.0 * M * (6.0 * F + 2.0 * kXfmrHeads * kXfmrBand), "xfmr_attn16_bwd_q_kernel", d,
+                           [&](auto D) { return xfmr_launch(xfmr_attn16_bwd_q_kernel<D()>, grid, XfmrAttn16TrainLds<D()>::bytes, stream, p16); }));
                 if (xfmr_train_k(g)) {  // bf16x3wack: dK, dV and dE's first stage on bf16 MFMAs too, from the same banded buffers
-                    {
-                        ProfScope prof(h, stream, "xfmr_attn16_bwd_k_kernel", 2.0 * M * F * 2 * kXfmrTab, 4.0 * M * (4.0 * F + 2.0 * kXfmrHeads * kXfmrBand));
-                        const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn16_bwd_k_launch, d, p, grid, stream);
-                        if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_attn16_bwd_k_kernel launch failed: %s", hipGetErrorString(e));
-                    }
-                    ProfScope prof(h, stream, "xfmr_demb16_partial_kernel", 2.0 * M * F * kXfmrTab, 4.0 * M * (1.0 * F + 1.0 * kXfmrHeads * kXfmrBand));
-                    const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_demb16_partial_launch, d, p, ws.embpart, M, chunks, stream);
-                    if (e != hipSuccess) return fail(HIFICAR_E_HIP, "xfmr_demb16_partial_kernel launch failed: %s", hipGetErrorString(e));
+                    XT(cx.attn("xfmr_attn16_bwd_k_kernel", 2.0 * M * F * 2 * kXfmrTab, 4.0 * M * (4.0 * F + 2.0 * kXfmrHeads * kXfmrBand), "xfmr_attn16_bwd_k_kernel",
+                               d, [&](auto D) { return xfmr_launch(xfmr_attn16_bwd_k_kernel<D()>, grid, XfmrAttn16BwdKLds<D()>::bytes, stream, p); }));
+                    XT(cx.attn("xfmr_demb16_partial_kernel", 2.0 * M * F * kXfmrTab, 4.0 * M * (1.0 * F + 1.0 * kXfmrHeads * kXfmrBand), "xfmr_demb16_partial_kernel",
+                               d, [&](auto D) {
+                                   return xfmr_launch(xfmr_demb16_partial_kernel<D()>, dim3((unsigned)chunks, kXfmrHeads), XfmrEmb16Lds<D()>::bytes, stream, p.qkv, p.ds,
+                                                      ws.embpart, M, p.T, p.F, p.hdr, p.lens, p.lay);
+                               }));
                 } else {
-                    ProfScope prof(h, stream, "xfmr_attn_bwd_k_kernels", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * (5.0 * F + 3.0 * kXfmrHeads * kXfmrBand));
-                    const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_bwd_k_launch, d, p, grid, ws.embpart, M, chunks, stream);
-                    if (e != hipSuccess) return fail(HIFICAR_E_HIP, "attention backward launch failed: %s", hipGetErrorString(e));
+                    XT(cx.attn("xfmr_attn_bwd_k_kernels", 2.0 * M * F * 3 * kXfmrTab, 4.0 * M * (5.0 * F + 3.0 * kXfmrHeads * kXfmrBand), "attention backward", d,
+                               [&](auto D) { return xfmr_attn_bwd_k_launch<D()>(p, grid, ws.embpart, M, chunks, stream); }));
                 }
             } else {
                 // S, dP, dQ (K and E parts), dK, dV, dE: six banded products of 2 M F 199 flops each
-                ProfScope prof(h, stream, "xfmr_attn_bwd_kernels", 2.0 * M * F * 7 * kXfmrTab, 4.0 * M * (8.0 * F + 4.0 * kXfmrHeads * kXfmrBand));
-                const hipError_t e = HIFICAR_XFMR_BY_D(xfmr_attn_bwd_launch, d, p, grid, ws.embpart, M, chunks, stream);
-                if (e != hipSuccess) return fail(HIFICAR_E_HIP, "attention backward launch failed: %s", hipGetErrorString(e));
+                XT(cx.attn("xfmr_attn_bwd_kernels", 2.0 * M * F * 7 * kXfmrTab, 4.0 * M * (8.0 * F + 4.0 * kXfmrHeads * kXfmrBand), "attention backward", d,
+                           [&](auto D) { return xfmr_attn_bwd_launch<D()>(p, grid, ws.embpart, M, chunks, stream); }));
             }
             const int width = kXfmrHeads * kXfmrTab * d;
             hipLaunchKernelGGL(bigru_colreduce_kernel, dim3((unsigned)((width + 255) / 256)), dim3(256), 0, stream, ws.embpart, chunks, width,
