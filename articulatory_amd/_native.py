@@ -115,6 +115,8 @@ SYMBOLS = (
     "hificar_bigru_finalize",
     "hificar_bigru_workspace_bytes",
     "hificar_bigru_forward",
+    "hificar_bigru_workspace_bytes_lowrate",
+    "hificar_bigru_forward_lowrate",
     "hificar_bigru_engine",
     "hificar_bigru_destroy",
     "hificar_bigru_set_parameters_device",
@@ -132,6 +134,8 @@ SYMBOLS = (
     "hificar_xfmr_finalize",
     "hificar_xfmr_workspace_bytes",
     "hificar_xfmr_forward",
+    "hificar_xfmr_workspace_bytes_lowrate",
+    "hificar_xfmr_forward_lowrate",
     "hificar_xfmr_debug_tap",
     "hificar_xfmr_engine",
     "hificar_xfmr_destroy",
@@ -502,6 +506,10 @@ def load_library():
     lib.hificar_bigru_workspace_bytes.restype = cs
     lib.hificar_bigru_forward.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]
     lib.hificar_bigru_forward.restype = ci
+    lib.hificar_bigru_workspace_bytes_lowrate.argtypes = [vp, ci, ci, ci]
+    lib.hificar_bigru_workspace_bytes_lowrate.restype = cs
+    lib.hificar_bigru_forward_lowrate.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, cs, vp]
+    lib.hificar_bigru_forward_lowrate.restype = ci
     lib.hificar_bigru_engine.argtypes = [vp]
     lib.hificar_bigru_engine.restype = vp
     lib.hificar_bigru_destroy.argtypes = [vp]
@@ -545,6 +553,10 @@ def load_library():
     lib.hificar_xfmr_workspace_bytes.restype = cs
     lib.hificar_xfmr_forward.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]
     lib.hificar_xfmr_forward.restype = ci
+    lib.hificar_xfmr_workspace_bytes_lowrate.argtypes = [vp, ci, ci, ci]
+    lib.hificar_xfmr_workspace_bytes_lowrate.restype = cs
+    lib.hificar_xfmr_forward_lowrate.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, cs, vp]
+    lib.hificar_xfmr_forward_lowrate.restype = ci
     lib.hificar_xfmr_debug_tap.argtypes = [vp, ctypes.c_char_p, vp, cs]
     lib.hificar_xfmr_debug_tap.restype = ci
     lib.hificar_xfmr_engine.argtypes = [vp]
@@ -588,6 +600,21 @@ def load_library():
     lib.hificar_version.restype = ctypes.c_char_p
     _lib = lib
     return lib
+
+
+LOWRATE_MAX_FACTOR = 16  # HIFICAR_LOWRATE_MAX_FACTOR (include/hificar.h)
+
+
+def check_interp_factor(interp_factor) -> int:
+    """``interp_factor`` of ``forward_lowrate`` as hificar_*_forward_lowrate takes it: an integer in 1 .. 16 (ValueError otherwise, before any
+    device work)."""
+    import numbers
+
+    if isinstance(interp_factor, bool) or not isinstance(interp_factor, numbers.Integral):
+        raise ValueError(f"interp_factor must be an integer in 1 .. {LOWRATE_MAX_FACTOR}, got {interp_factor!r}")
+    if not 1 <= int(interp_factor) <= LOWRATE_MAX_FACTOR:
+        raise ValueError(f"interp_factor must lie in 1 .. {LOWRATE_MAX_FACTOR}, got {interp_factor}")
+    return int(interp_factor)
 
 
 def check(rc, what):

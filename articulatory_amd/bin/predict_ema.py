@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Speech-to-EMA: the counterpart of the reference's ``egs/ema/voc1/local/predict_ema.py`` behind the features.
+
+    python -m articulatory_amd.bin.predict_ema MODEL_DIR FEATS OUTDIR [--interp-factor N] [--zscore | --no-zscore] [--batch-size N]
+                                               [--precision P] [--dry-run]
+
+``MODEL_DIR`` holds ``best_mel_ckpt.pkl`` and ``config.yml`` (predict_ema.py:54-55; what ``InversionTrainer`` writes).  ``FEATS`` is a directory
+of ``<utt>.npy`` files, each (frames, channels) — the speech model's last hidden states, or the MFCC matrix transposed — or a kaldi-style scp
+file; the SSL / MFCC extraction itself is the caller's (s3prl and librosa are not dependencies of this package).  ``OUTDIR/<utt>.npy`` is
+(factor * frames, out_channels) float32, as ``np.save(pred)`` at predict_ema.py:102.
+
+The defaults follow the reference's own rules (predict_ema.py:37-47), read off the directory's name: ``_h2`` in it means SSL features, which
+are interpolated and not z-scored — by 2 when the name starts with ``hprc``, else by 4 —; any other name means MFCCs, which are z-scored per
+utterance and not interpolated.  ``--interp-factor`` / ``--zscore`` / ``--no-zscore`` override them.  Both steps run on the device inside
+``model.forward_lowrate`` (no stretched or normalised copy of the features exists); ``--batch-size N`` runs ragged batches of N utterances,
+every one computed as if alone: any batch size writes the same files.
+"""
+
+import argparse
+import glob
+import json
+import logging
+import os
+
+import numpy as np
+import torch
+import yaml
+
+from articulatory_amd.bin.decode import _load, length_batches, npy_frames, pad_utterances
+from articulatory_amd.utils.scp import is_supported
+
+CHECKPOINT = "best_mel_ckpt.pkl"  # predict_ema.py:54
+
+
+def derive_defaults(model_dir):
+    """(interp_factor, zscore) by the reference's rules for an experiment id (predict_ema.py:37-47)."""
+    exp_id = os.path.basename(os.path.normpath(model_dir))
+    if "_h2" in exp_id:  # input_modality 'hubert': interpolated (:86-89), not normalised
+        return (2 if exp_id.startswith("hprc") else 4), False
+    return 1, True  # input_modality 'mfcc': stats.zscore(feat, axis=None) (:34), no interpolation
+
+
+def list_features(feats):
+    """(utt_id, path) pairs of a directory of ``<utt_id>.npy`` files or of a kaldi-style ``utt_id path`` scp file.  Nothing is loaded."""
+    pairs = []
+    if os.path.isdir(feats):
+        for path in sorted(glob.glob(os.path.join(feats, "*.npy"))):
+            pairs.append((os.path.basename(path)[: -len(".npy")], path))
+        return pairs
+    with open(feats) as f:
+        for line in f:
+            parts = line.strip().split()
+            if len(parts) < 2:
+                continue
+            if not is_supported(parts[1]):
+                raise ValueError("Not supported feats.scp type.")
+            pairs.append((parts[0], parts[1]))
+    return pairs
+
+
+def get_parser():
+    parser = argparse.ArgumentParser(description="Predict EMA from dumped speech features with a trained inversion model.")
+    parser.add_argument("model_dir", type=str, help=f"directory holding {CHECKPOINT} and config.yml")
+    parser.add_argument("feats", type=str, help="directory of <utt>.npy files, each (frames, channels), or a kaldi-style scp file")
+    parser.add_argument("outdir", type=str, help="directory to save <utt>.npy, each (factor * frames, out_channels)")
+    parser.add_argument("--interp-factor", type=int, default=None,
+                        help="stretch every utterance by this integer factor (1 .. 16) with linear interpolation; default: by the "
+                             "directory name, as the reference decides (4, or 2 for hprc*, with _h2 in the name; else 1)")
+    z = parser.add_mutually_exclusive_group()
+    z.add_argument("--zscore", dest="zscore", action="store_true", default=None,
+                   help="normalise every utterance by the mean and standard deviation of all its elements (default without _h2 in the name)")
+    z.add_argument("--no-zscore", dest="zscore", action="store_false")
+    parser.add_argument("--batch-size", type=int, default=1, help="utterances per device call (any lengths; the reference is batch-1)")
+    parser.add_argument("--precision", default=None, choices=("f32", "bf16x3", "bf16x3a"),
+                        help="arithmetic of the model's GEMMs, for models with set_precision (the Transformer); default: f32")
+    parser.add_argument("--verbose", type=int, default=1, help="logging level. higher is more logging. (default=1)")
+    parser.add_argument("--dry-run", default=False, action="store_true", help="print the plan as one JSON line and exit (no GPU needed)")
+    return parser
+
+
+def predict_features(model, items, outdir, device, interp_factor=1, zscore=False, batch_size=1):
+    """predict_ema.py:77-102 behind the feature extraction: (utt_id, (frames, channels) ndarray) items ->
+    ``outdir/<utt_id>.npy`` (factor * frames, out_channels).  Batches of similar lengths through ``model.forward_lowrate``; every
+    utterance is computed as if alone, so the files do not depend on ``batch_size``.  Returns the number of utterances."""
+    n = 0
+    with torch.no_grad():
+        feats = ((u, torch.tensor(np.asarray(c), dtype=torch.float).to(device)) for u, c in items)
+        for batch in length_batches(feats, max(1, batch_size)):
+            padded, lens = pad_utterances([c for _, c in batch])
+            yb = model.forward_lowrate(padded.permute(0, 2, 1), lengths=lens, interp_factor=interp_factor, zscore=zscore)
+            for i, (utt_id, _) in enumerate(batch):
+                np.save(os.path.join(outdir, f"{utt_id}.npy"), yb[i, :, :interp_factor * lens[i]].transpose(0, 1).cpu().numpy())
+                n += 1
+    return n
+
+
+def main(argv=None):
+    from articulatory_amd._native import check_interp_factor
+    from articulatory_amd.utils import load_model
+
+    args = get_parser().parse_args(argv)
+    level = logging.DEBUG if args.verbose > 1 else logging.INFO if args.verbose > 0 else logging.WARN
+    logging.basicConfig(level=level, format="%(asctime)s (%(module)s:%(lineno)d) %(levelname)s: %(message)s")
+    factor, zscore = derive_defaults(args.model_dir)
+    if args.interp_factor is not None:
+        factor = args.interp_factor
+    if args.zscore is not None:
+        zscore = args.zscore
+    factor = check_interp_factor(factor)
+    checkpoint = os.path.join(args.model_dir, CHECKPOINT)
+    with open(os.path.join(args.model_dir, "config.yml")) as f:
+        config = yaml.load(f, Loader=yaml.Loader)
+    config.setdefault("format", "npy")
+    if config.get("generator_params", {}).get("use_ar", False):
+        raise NotImplementedError("predict_ema with use_ar: ar_loop's feature branches are not built")
+    pairs = list_features(args.feats)
+    logging.info(f"The number of features to be decoded = {len(pairs)}.")
+    if args.dry_run:
+        print(json.dumps({"model_dir": args.model_dir, "checkpoint": checkpoint, "generator_type": config.get("generator_type"),
+                          "interp_factor": factor, "zscore": bool(zscore), "batch_size": args.batch_size, "precision": args.precision or "f32",
+                          "utterances": [u for u, _ in pairs], "frames": int(sum(npy_frames(p) for _, p in pairs))}), flush=True)
+        return
+    if not torch.cuda.is_available():
+        raise RuntimeError("predict_ema: no GPU visible; this package has no CPU inference path")
+    if not os.path.exists(args.outdir):
+        os.makedirs(args.outdir)
+    device = torch.device("cuda")
+    model = load_model(checkpoint, config)
+    logging.info(f"Loaded model parameters from {checkpoint}.")
+    if not hasattr(model, "forward_lowrate"):
+        raise NotImplementedError(f"{type(model).__name__} is not an inversion model (BiGRU, Transformer): it has no low-rate front end")
+    model.remove_weight_norm()
+    if args.precision is not None:
+        if hasattr(model, "set_precision"):
+            model.set_precision(args.precision)
+        elif args.precision != "f32":
+            raise NotImplementedError(f"--precision {args.precision}: {type(model).__name__} runs in the exact-fp32 arithmetic only")
+    model = model.eval().to(device)
+    n = predict_features(model, ((u, _load(p)) for u, p in pairs), args.outdir, device, interp_factor=factor, zscore=zscore,
+                         batch_size=args.batch_size)
+    logging.info(f"Finished prediction of {n} utterances.")
+
+
+if __name__ == "__main__":
+    main()

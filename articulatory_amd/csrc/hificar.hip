@@ -9,6 +9,7 @@
 #include "hificar_bigru_kernels.hip.h"
 #include "hificar_bigru_train_kernels.hip.h"
 #include "hificar_xfmr_kernels.hip.h"
+#include "hificar_frontend_kernels.hip.h"
 #include "hificar_xfmr_attn16.hip.h"
 #include "hificar_xfmr_train_kernels.hip.h"
 #include "hificar_xfmr_attn16_train.hip.h"

@@ -326,3 +326,140 @@ extern "C" int hificar_bigru_forward(hificar_bigru* g, const float* x, const int
     }
     return HIFICAR_OK;
 }
+
+// ---- The low-rate front end (egs/ema/voc1/local/predict_ema.py:83-101): features at 1 / factor of the model's rate, and / or to be z-scored
+// per utterance.  Linear interpolation is an affine combination whose weights sum to one, so interp(X) W_ih^T + b_ih = interp(X W_ih^T + b_ih):
+// layer 1's projection runs over the B Tl low-rate rows and its 6H-wide pre-gates are interpolated (hificar_frontend_kernels.hip.h).  From
+// the first sweep on the launches are hificar_bigru_forward's.
+struct BigruLowWorkspace {
+    float* gates;   // [B T rows][6H], as BigruWorkspace
+    float* gates_l; // [B Tl rows][6H]: layer 1's pre-gates at the low rate (factor 1: none, the GEMM writes `gates`)
+    float* rows;    // the low-rate input rows [B Tl rows][cin_pad], then the layers' hidden states [B T rows][2H]
+    double* stats;  // [B][mean, 1 / std]
+    int* lens;      // [B]: factor * lengths[b], what the sweeps and the head go by
+    size_t bytes;
+};
+
+static BigruLowWorkspace bigru_plan_workspace_lowrate(const hificar_bigru* g, int B, int Tl, int factor, void* base) {
+    const size_t rows_l = round_up_sz((size_t)std::max(B, 0) * (size_t)std::max(Tl, 0), 256);
+    const size_t rows_h = round_up_sz((size_t)std::max(B, 0) * (size_t)std::max(Tl, 0) * (size_t)std::max(factor, 1), 256);
+    const size_t H = (size_t)g->cfg.hidden_size;
+    const size_t gb = round_up_sz(rows_h * 6 * H * sizeof(float), 256);
+    const size_t lb = factor > 1 ? round_up_sz(rows_l * 6 * H * sizeof(float), 256) : 0;
+    const size_t rb = round_up_sz(std::max(rows_l * (size_t)g->cin_pad, rows_h * 2 * H) * sizeof(float), 256);
+    const size_t sb = round_up_sz((size_t)std::max(B, 0) * 2 * sizeof(double), 256);
+    BigruLowWorkspace w;
+    char* p = static_cast<char*>(base);
+    w.gates = reinterpret_cast<float*>(p);
+    w.gates_l = reinterpret_cast<float*>(p + gb);
+    w.rows = reinterpret_cast<float*>(p + gb + lb);
+    w.stats = reinterpret_cast<double*>(p + gb + lb + rb);
+    w.lens = reinterpret_cast<int*>(p + gb + lb + rb + sb);
+    w.bytes = gb + lb + rb + sb + round_up_sz((size_t)std::max(B, 0) * sizeof(int), 256);
+    return w;
+}
+
+static bool lowrate_shape_ok(int B, int Tl, int factor) {
+    return B >= 1 && Tl >= 1 && B <= 65535 && factor >= 1 && factor <= HIFICAR_LOWRATE_MAX_FACTOR && (long long)B * Tl * factor <= (1LL << 30) / 8;
+}
+
+extern "C" size_t hificar_bigru_workspace_bytes_lowrate(const hificar_bigru* g, int B, int Tl, int factor) {
+    if (!g || !lowrate_shape_ok(B, Tl, factor)) return 0;
+    // (factor 1 without zscore is hificar_bigru_forward on the same memory)
+    return std::max(bigru_plan_workspace_lowrate(g, B, Tl, factor, nullptr).bytes, bigru_plan_workspace(g, B, Tl * factor, nullptr).bytes);
+}
+
+extern "C" int hificar_bigru_forward_lowrate(hificar_bigru* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int Tl,
+                                             int factor, int zscore, void* workspace, size_t workspace_bytes, void* stream_) {
+    static_assert(HIFICAR_LOWRATE_MAX_FACTOR == kFrontMaxFactor, "the front end's tile");
+    if (!g || !x || !out) return fail(HIFICAR_E_INVALID, "hificar_bigru_forward_lowrate: null argument");
+    if (factor < 1 || factor > HIFICAR_LOWRATE_MAX_FACTOR)
+        return fail(HIFICAR_E_INVALID, "hificar_bigru_forward_lowrate: factor=%d out of range (1 .. %d)", factor, HIFICAR_LOWRATE_MAX_FACTOR);
+    if (!lowrate_shape_ok(B, Tl, factor)) return fail(HIFICAR_E_INVALID, "hificar_bigru_forward_lowrate: B=%d, Tl=%d, factor=%d out of range", B, Tl, factor);
+    if (lengths_host && !lengths) return fail(HIFICAR_E_INVALID, "hificar_bigru_forward_lowrate: lengths_host without the device copy");
+    if (lengths_host)
+        for (int b = 0; b < B; ++b)
+            if (lengths_host[b] < 0 || lengths_host[b] > Tl)
+                return fail(HIFICAR_E_INVALID, "hificar_bigru_forward_lowrate: lengths[%d]=%d outside 0 .. Tl=%d", b, lengths_host[b], Tl);
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
+    const size_t need = hificar_bigru_workspace_bytes_lowrate(g, B, Tl, factor);
+    if (workspace_bytes < need) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+    // (every argument above is checked without the device: a handle that was never finalized is told so last)
+    if (!g->finalized) return fail(HIFICAR_E_STATE, "hificar_bigru_forward_lowrate before hificar_bigru_finalize");
+    if (factor == 1 && !zscore) return hificar_bigru_forward(g, x, lengths, lengths_host, out, B, Tl, workspace, workspace_bytes, stream_);
+    const BigruLowWorkspace ws = bigru_plan_workspace_lowrate(g, B, Tl, factor, workspace);
+    hificar_engine* h = &g->eng;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc;
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    const int H = g->cfg.hidden_size, C = g->cfg.in_channels, O = g->cfg.out_channels, T = Tl * factor, Ml = B * Tl, M = B * T;
+    const Ragged rg;
+    const int* lens_h = nullptr;  // the frame counts at the model's rate
+    if (lengths) {
+        hipLaunchKernelGGL(frontend_lengths_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, lengths, ws.lens, B, Tl, factor);
+        HIP_TRY(hipGetLastError());
+        lens_h = ws.lens;
+    }
+    if (zscore) {
+        ProfScope prof(h, stream, "frontend_stats_kernel", 0.0, 8.0 * Ml * C);
+        hipLaunchKernelGGL(frontend_stats_kernel, dim3((unsigned)B), dim3(256), 0, stream, x, lengths, ws.stats, C, Tl);
+        HIP_TRY(hipGetLastError());
+    }
+    {   // the input rows at the LOW rate: the interpolation commutes with the projection behind them
+        ProfScope prof(h, stream, "frontend_rows_kernel", 0.0, 4.0 * Ml * (C + g->cin_pad));
+        hipLaunchKernelGGL(frontend_rows_kernel<false>, dim3((unsigned)((Tl + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, ws.rows,
+                           static_cast<char*>(nullptr), lengths, zscore ? ws.stats : static_cast<const double*>(nullptr), C, g->cin_pad, Tl, 1);
+        HIP_TRY(hipGetLastError());
+    }
+    const int NS = bigru_tile_height(g, B);
+    for (int l = 0; l < 2; ++l) {
+        const ConvLayer* ls[1] = {&g->proj[l]};
+        ConvIO io[1];
+        io[0] = ConvIO();
+        io[0].xs = reinterpret_cast<const char*>(ws.rows);
+        io[0].y = l == 0 && factor > 1 ? ws.gates_l : ws.gates;
+        if ((rc = launch_conv(h, ls, 1, 1, l == 0 ? Ml : M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+        if (l == 0 && factor > 1) {
+            const int N4 = 6 * H / 4;
+            ProfScope prof(h, stream, "bigru_interp_gates_kernel", 3.0 * M * 6 * H, 4.0 * M * 6 * H * 3);
+            hipLaunchKernelGGL(bigru_interp_gates_kernel, dim3((unsigned)(((long long)T * N4 + 255) / 256), 1, (unsigned)B), dim3(256), 0, stream, ws.gates_l,
+                               ws.gates, lengths, N4, Tl, factor);
+            HIP_TRY(hipGetLastError());
+        }
+        BigruRecParams p;
+        p.g = ws.gates;
+        p.w = g->d_whh[l];
+        p.bhh = g->d_bhh[l];
+        p.lengths = lens_h;
+        p.y = ws.rows;  // (the projection that read the rows is complete: same stream)
+        p.B = B;
+        p.T = T;
+        ProfScope prof(h, stream, "bigru_rec_kernel", 2.0 * M * 2 * 3 * H * H, 4.0 * M * 8 * H);
+        const hipError_t e = NS == 1 ? bigru_rec_launch_h<1>(H, p, stream) : bigru_rec_launch_h<2>(H, p, stream);
+        if (e != hipSuccess) return fail(HIFICAR_E_HIP, "bigru_rec_kernel launch failed: %s", hipGetErrorString(e));
+    }
+    {
+        const ConvLayer* ls[1] = {&g->fc1};
+        ConvIO io[1];
+        io[0] = ConvIO();
+        io[0].xs = reinterpret_cast<const char*>(ws.rows);
+        io[0].y = ws.gates;
+        if ((rc = launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+    }
+    {
+        BigruHeadParams p;
+        p.f = ws.gates;
+        p.w2 = g->d_w2;
+        p.b2 = g->d_b2;
+        p.lengths = lens_h;
+        p.out = out;
+        p.B = B;
+        p.T = T;
+        p.O = O;
+        p.use_tanh = g->cfg.use_tanh;
+        ProfScope prof(h, stream, "bigru_head_kernel", 2.0 * M * kBigruFc1 * O, 4.0 * M * (kBigruFc1 + O));
+        hipLaunchKernelGGL(bigru_head_kernel, dim3((unsigned)((T + 63) / 64), (unsigned)B), dim3(256), 0, stream, p);
+        HIP_TRY(hipGetLastError());
+    }
+    return HIFICAR_OK;
+}

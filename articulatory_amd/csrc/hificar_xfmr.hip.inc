@@ -426,24 +426,19 @@ static int xfmr_emit_tap(hificar_xfmr* g, const std::string& name, const float* 
     return HIFICAR_OK;
 }
 
-extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int T,
-                                    void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!g || !x || !out) return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: null argument");
-    if (!g->finalized) return fail(HIFICAR_E_STATE, "hificar_xfmr_forward before hificar_xfmr_finalize");
-    if (B < 1 || T < 1 || B > 65535 || (long long)B * T > (1LL << 30) / 8 || (long long)B * T * kXfmrFF >= (1LL << 31))
-        return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: B=%d, T=%d out of range (B T 3072 < 2^31)", B, T);
-    if (lengths_host && !lengths) return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: lengths_host without the device copy");
-    if (lengths_host)
-        for (int b = 0; b < B; ++b)
-            if (lengths_host[b] < 0 || lengths_host[b] > T)
-                return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: lengths[%d]=%d outside 0 .. T=%d", b, lengths_host[b], T);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
-    const XfmrWorkspace ws = xfmr_plan_workspace(g, B, T, workspace);
-    if (workspace_bytes < ws.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
+// The low-rate front end in place of xfmr_rows_kernel (hificar_xfmr_forward_lowrate): x is (B, in_channels, Tl) with `lengths` low-rate frame
+// counts; everything behind the input rows goes by the frame counts at the model's rate.
+struct XfmrFront {
+    int Tl, factor;
+    const int32_t* lengths;  // low-rate, device (or null)
+    const double* stats;     // [B][mean, 1 / std], or null
+};
+
+// Every launch of the eval forward, after the arguments were checked and the stream entered.  lengths: at the model's rate.
+static int xfmr_forward_run(hificar_xfmr* g, const float* x, const int32_t* lengths, float* out, int B, int T, const XfmrWorkspace& ws, hipStream_t stream,
+                            const XfmrFront* fe) {
     hificar_engine* h = &g->eng;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc;
-    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads;
     const double M = (double)B * T;
     const size_t MF = (size_t)B * T * F;
@@ -486,7 +481,17 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
     const bool has_rp = g->rp.cout != 0;
     {
         const dim3 grid((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B);
-        if (x3) {  // (no residual_path: block 0's conv2 takes the input as its fp32 residual, kept in r[1])
+        if (fe) {  // (the same rows, formed from the low-rate input: hificar_frontend_kernels.hip.h)
+            const double Ml = (double)B * fe->Tl;
+            ProfScope prof(h, stream, x3 ? "frontend_rows_kernel<split>" : "frontend_rows_kernel", 0.0,
+                           4.0 * (Ml * C + M * g->cin_pad * (x3 && !has_rp ? 2 : 1)));
+            if (x3)
+                hipLaunchKernelGGL(frontend_rows_kernel<true>, grid, dim3(256), 0, stream, x, has_rp ? nullptr : ws.r[1], reinterpret_cast<char*>(ws.xin),
+                                   fe->lengths, fe->stats, C, g->cin_pad, fe->Tl, fe->factor);
+            else
+                hipLaunchKernelGGL(frontend_rows_kernel<false>, grid, dim3(256), 0, stream, x, ws.xin, static_cast<char*>(nullptr), fe->lengths, fe->stats, C,
+                                   g->cin_pad, fe->Tl, fe->factor);
+        } else if (x3) {  // (no residual_path: block 0's conv2 takes the input as its fp32 residual, kept in r[1])
             ProfScope prof(h, stream, "xfmr_rows_split_kernel", 0.0, 4.0 * M * (C + g->cin_pad * (has_rp ? 1 : 2)));
             hipLaunchKernelGGL(xfmr_rows_split_kernel, grid, dim3(256), 0, stream, x, reinterpret_cast<char*>(ws.xin), has_rp ? nullptr : ws.r[1], lengths, C,
                                g->cin_pad, T);
@@ -574,4 +579,98 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
         HIP_TRY(hipGetLastError());
     }
     return HIFICAR_OK;
+}
+
+extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int T,
+                                    void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!g || !x || !out) return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: null argument");
+    if (!g->finalized) return fail(HIFICAR_E_STATE, "hificar_xfmr_forward before hificar_xfmr_finalize");
+    if (B < 1 || T < 1 || B > 65535 || (long long)B * T > (1LL << 30) / 8 || (long long)B * T * kXfmrFF >= (1LL << 31))
+        return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: B=%d, T=%d out of range (B T 3072 < 2^31)", B, T);
+    if (lengths_host && !lengths) return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: lengths_host without the device copy");
+    if (lengths_host)
+        for (int b = 0; b < B; ++b)
+            if (lengths_host[b] < 0 || lengths_host[b] > T)
+                return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: lengths[%d]=%d outside 0 .. T=%d", b, lengths_host[b], T);
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
+    const XfmrWorkspace ws = xfmr_plan_workspace(g, B, T, workspace);
+    if (workspace_bytes < ws.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
+    hificar_engine* h = &g->eng;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc;
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    return xfmr_forward_run(g, x, lengths, out, B, T, ws, stream, nullptr);
+}
+
+// ---- The low-rate front end (egs/ema/voc1/local/predict_ema.py:83-101): the input rows are formed from features at 1 / factor of the model's
+// rate, z-scored per utterance if asked; every launch behind them is hificar_xfmr_forward's.
+struct XfmrLowWorkspace {
+    double* stats;  // [B][mean, 1 / std]
+    int* lens;      // [B]: factor * lengths[b]
+    size_t bytes;   // behind xfmr_plan_workspace(B, factor Tl)
+};
+
+static XfmrLowWorkspace xfmr_plan_workspace_lowrate(const hificar_xfmr* g, int B, int Tl, int factor, void* base) {
+    const size_t main = xfmr_plan_workspace(g, B, Tl * factor, nullptr).bytes;
+    const size_t sb = round_up_sz((size_t)std::max(B, 0) * 2 * sizeof(double), 256), lb = round_up_sz((size_t)std::max(B, 0) * sizeof(int), 256);
+    XfmrLowWorkspace w;
+    char* p = static_cast<char*>(base);
+    w.stats = reinterpret_cast<double*>(p + main);
+    w.lens = reinterpret_cast<int*>(p + main + sb);
+    w.bytes = main + sb + lb;
+    return w;
+}
+
+static bool xfmr_lowrate_shape_ok(int B, int Tl, int factor) {
+    const long long M = (long long)B * Tl * factor;
+    return B >= 1 && Tl >= 1 && B <= 65535 && factor >= 1 && factor <= HIFICAR_LOWRATE_MAX_FACTOR && M <= (1LL << 30) / 8 && M * kXfmrFF < (1LL << 31);
+}
+
+extern "C" size_t hificar_xfmr_workspace_bytes_lowrate(const hificar_xfmr* g, int B, int Tl, int factor) {
+    if (!g || !xfmr_lowrate_shape_ok(B, Tl, factor)) return 0;
+    return xfmr_plan_workspace_lowrate(g, B, Tl, factor, nullptr).bytes;
+}
+
+extern "C" int hificar_xfmr_forward_lowrate(hificar_xfmr* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int Tl,
+                                            int factor, int zscore, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!g || !x || !out) return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward_lowrate: null argument");
+    if (factor < 1 || factor > HIFICAR_LOWRATE_MAX_FACTOR)
+        return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward_lowrate: factor=%d out of range (1 .. %d)", factor, HIFICAR_LOWRATE_MAX_FACTOR);
+    if (!xfmr_lowrate_shape_ok(B, Tl, factor))
+        return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward_lowrate: B=%d, Tl=%d, factor=%d out of range (B factor Tl 3072 < 2^31)", B, Tl, factor);
+    if (lengths_host && !lengths) return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward_lowrate: lengths_host without the device copy");
+    if (lengths_host)
+        for (int b = 0; b < B; ++b)
+            if (lengths_host[b] < 0 || lengths_host[b] > Tl)
+                return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward_lowrate: lengths[%d]=%d outside 0 .. Tl=%d", b, lengths_host[b], Tl);
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
+    const XfmrLowWorkspace lw = xfmr_plan_workspace_lowrate(g, B, Tl, factor, workspace);
+    if (workspace_bytes < lw.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, lw.bytes);
+    // (every argument above is checked without the device: a handle that was never finalized is told so last)
+    if (!g->finalized) return fail(HIFICAR_E_STATE, "hificar_xfmr_forward_lowrate before hificar_xfmr_finalize");
+    if (factor == 1 && !zscore) return hificar_xfmr_forward(g, x, lengths, lengths_host, out, B, Tl, workspace, workspace_bytes, stream_);
+    const int T = Tl * factor;
+    const XfmrWorkspace ws = xfmr_plan_workspace(g, B, T, workspace);
+    hificar_engine* h = &g->eng;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc;
+    if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
+    XfmrFront fe;
+    fe.Tl = Tl;
+    fe.factor = factor;
+    fe.lengths = lengths;
+    fe.stats = nullptr;
+    const int32_t* lens_h = nullptr;
+    if (lengths) {
+        hipLaunchKernelGGL(frontend_lengths_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, lengths, lw.lens, B, Tl, factor);
+        HIP_TRY(hipGetLastError());
+        lens_h = lw.lens;
+    }
+    if (zscore) {
+        ProfScope prof(h, stream, "frontend_stats_kernel", 0.0, 8.0 * B * Tl * g->cfg.in_channels);
+        hipLaunchKernelGGL(frontend_stats_kernel, dim3((unsigned)B), dim3(256), 0, stream, x, lengths, lw.stats, g->cfg.in_channels, Tl);
+        HIP_TRY(hipGetLastError());
+        fe.stats = lw.stats;
+    }
+    return xfmr_forward_run(g, x, lens_h, out, B, T, ws, stream, &fe);
 }

@@ -536,9 +536,16 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         _native.check(rc, what)
         return out, stats, tape, toff
 
-    def _workspace(self, B, T):
-        """One grow-only scratch buffer per model (hificar_xfmr_workspace_bytes)."""
-        n = self._lib.hificar_xfmr_workspace_bytes(self._handle, B, T) + 256
+    def _workspace(self, B, T, factor=None):
+        """One grow-only scratch buffer per model (hificar_xfmr_workspace_bytes; ``factor``: T low-rate frames,
+        hificar_xfmr_workspace_bytes_lowrate)."""
+        if factor is None:
+            n = self._lib.hificar_xfmr_workspace_bytes(self._handle, B, T) + 256
+        else:
+            n = self._lib.hificar_xfmr_workspace_bytes_lowrate(self._handle, B, T, factor)
+            if n == 0:
+                raise RuntimeError(f"Transformer.forward_lowrate: B={B}, Tl={T}, interp_factor={factor} out of range (B factor Tl 3072 < 2^31)")
+            n += 256
         ws = self._workspace_buf
         if ws is None or ws.numel() < n:
             # work already enqueued on the old buffer keeps it alive through the caching allocator's stream ordering
@@ -592,6 +599,45 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
             rc = self._lib.hificar_xfmr_forward(handle, c.data_ptr(), lens[0], lens[1], out.data_ptr(), B, T, ws_ptr, ws_bytes,
                                                 ctypes.c_void_p(stream))
         _native.check(rc, "hificar_xfmr_forward")
+        return out
+
+    def forward_lowrate(self, x, lengths=None, interp_factor=1, zscore=False):
+        """The reference's speech-to-EMA front end and the forward behind it in one call (egs/ema/voc1/local/predict_ema.py:83-101), eval mode:
+        x (B, in_channels, Tl) features as the speech model or the MFCC extraction delivers them -> (B, out_channels, interp_factor * Tl).
+        ``interp_factor`` (an integer in 1 .. 16; the reference uses 4, or 2 for its hprc models): every utterance is stretched as
+        ``F.interpolate(x_b[..., :l_b], size=interp_factor * l_b, mode='linear', align_corners=False)`` does, clamped at its own first and last
+        frame.  ``zscore``: every utterance is first normalised by the mean and the population standard deviation of all its in_channels x l_b
+        elements (``scipy.stats.zscore(feat, axis=None)``, predict_ema.py:32-35; a constant utterance gives NaN, as scipy does).  ``lengths``
+        (B LOW-RATE frame counts): a ragged batch — an utterance's result is bitwise that of running it alone, the output is zero past
+        interp_factor * lengths[b], and padded input frames are never read.  Neither the stretched nor the normalised input is ever
+        materialised: the input rows are formed at the model's rate from the low-rate input, at any ``precision``.  ``interp_factor=1, zscore=False`` is ``forward(x, lengths=lengths)``."""
+        f = _native.check_interp_factor(interp_factor)
+        if self.training:
+            raise NotImplementedError("Transformer.forward_lowrate: the low-rate front end is an inference path (call .eval(); training on "
+                                      "low-rate inputs is not built)")
+        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+            raise RuntimeError("Transformer.forward_lowrate needs a CUDA/HIP tensor; there is no CPU fallback")
+        if x.dim() != 3 or x.shape[1] != self._params["in_channels"]:
+            raise RuntimeError(f"Transformer.forward_lowrate: expected (B, {self._params['in_channels']}, Tl), got {tuple(x.shape)}")
+        handle = self._native_handle()
+        if x.device != self._device():
+            raise RuntimeError(f"Transformer.forward_lowrate: input on {x.device}, parameters on {self._device()}")
+        c = x.detach().to(torch.float32).contiguous()
+        B, _, Tl = c.shape
+        if B < 1 or Tl < 1:
+            raise RuntimeError(f"Transformer.forward_lowrate: empty input {tuple(c.shape)}")
+        lens = (None, None)
+        keep = None
+        if lengths is not None:
+            keep = self._check_lengths(lengths, B, Tl, c.device)
+            lens = (keep[1].data_ptr(), keep[0].data_ptr())
+        out = torch.empty((B, self._params["out_channels"], f * Tl), dtype=torch.float32, device=c.device)
+        with torch.cuda.device(c.device):
+            ws_ptr, ws_bytes = self._workspace(B, Tl, factor=f)
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = self._lib.hificar_xfmr_forward_lowrate(handle, c.data_ptr(), lens[0], lens[1], out.data_ptr(), B, Tl, f, 1 if zscore else 0, ws_ptr,
+                                           ws_bytes, ctypes.c_void_p(stream))
+        _native.check(rc, "hificar_xfmr_forward_lowrate")
         return out
 
     def forward_padded(self, x, lengths, packed=False):

@@ -573,6 +573,34 @@ size_t hificar_bigru_workspace_bytes(const hificar_bigru* h, int B, int T);
 int hificar_bigru_forward(hificar_bigru* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int T,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- The low-rate front end: the step between "features from the speech model" and the model's forward in the reference's speech-to-EMA
+ * driver (egs/ema/voc1/local/predict_ema.py:83-101), on the device and without a stretched or normalised copy of the input.
+ *   factor   1 .. HIFICAR_LOWRATE_MAX_FACTOR.  A sequence of l low-rate frames becomes factor * l frames by the rule of
+ *            F.interpolate(size=factor * l, mode='linear', align_corners=False) (predict_ema.py:86-90; the reference uses 4, or 2 for its hprc
+ *            models): src = max(0, (t + 0.5) / factor - 0.5), i0 = floor(src), i1 = min(i0 + 1, l - 1), lam = src - i0,
+ *            y[t] = (1 - lam) x[i0] + lam x[i1].  Every sequence of a batch clamps at its OWN first and last frame.  l = 0: no frames; l = 1: the
+ *            frame factor times; factor = 1: the identity.
+ *   zscore   != 0: per utterance (x - mean) / std, mean and std (population) over all in_channels * l elements of its valid frames, as
+ *            scipy.stats.zscore(feat, axis=None) (predict_ema.py:32-35): two passes in double, a fixed summation order.  std = 0 gives what
+ *            IEEE division gives (NaN), as scipy does.  With both options the normalisation comes first (either order is the same function).
+ * An utterance's result does not depend on what it is batched with, bit for bit; padded input frames are never read, and what the workspace
+ * holds on entry does not matter. ---- */
+#define HIFICAR_LOWRATE_MAX_FACTOR 16
+
+/* Bytes of device scratch hificar_bigru_forward_lowrate needs for B sequences of Tl low-rate frames: the pre-gate buffer at the model's rate
+ * (B factor Tl 6H floats), layer 1's pre-gates at the low rate (B Tl 6H floats; none at factor 1), one row buffer of
+ * max(Tl in_channels, factor Tl 2H) floats per sequence, and the per-utterance statistics and frame counts.  0: arguments out of range. */
+size_t hificar_bigru_workspace_bytes_lowrate(const hificar_bigru* h, int B, int Tl, int factor);
+
+/* predict_ema.py:83-101 for the BiGRU: x (B, in_channels, Tl) device fp32, lengths LOW-RATE frame counts (device; NULL: all Tl; lengths_host as
+ * in hificar_bigru_forward, checked against Tl) -> out (B, out_channels, factor * Tl), zero past factor * lengths[b].  Layer 1's input projection
+ * runs over the B Tl low-rate rows and its pre-gates are interpolated (interp(X) W + b = interp(X W + b): the two weights sum to one); from
+ * the first sweep on the launches are hificar_bigru_forward's.  factor = 1 and zscore = 0 IS hificar_bigru_forward: the same launches, the same
+ * bits.  Every argument is checked on the host before anything is enqueued; HIFICAR_E_STATE before hificar_bigru_finalize.  workspace: 256-byte
+ * aligned, hificar_bigru_workspace_bytes_lowrate(h, B, Tl, factor) bytes. */
+int hificar_bigru_forward_lowrate(hificar_bigru* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int Tl,
+                                  int factor, int zscore, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The model's engine, for hificar_profile_begin / hificar_profile_end (the reference times whole utterances, decode.py:302-318). */
 hificar_engine* hificar_bigru_engine(hificar_bigru* h);
 
@@ -713,6 +741,17 @@ size_t hificar_xfmr_workspace_bytes(const hificar_xfmr* h, int B, int T);
  * B T 3072 < 2^31.  Stream rules as in the conventions at the top. */
 int hificar_xfmr_forward(hificar_xfmr* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int T,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of device scratch hificar_xfmr_forward_lowrate needs: hificar_xfmr_workspace_bytes(h, B, factor * Tl) and the per-utterance statistics and
+ * frame counts.  0: arguments out of range. */
+size_t hificar_xfmr_workspace_bytes_lowrate(const hificar_xfmr* h, int B, int Tl, int factor);
+
+/* predict_ema.py:83-101 for the Transformer (the low-rate front end described at hificar_bigru_forward_lowrate: the same factor, zscore, lengths
+ * and guarantees): x (B, in_channels, Tl) -> out (B, out_channels, factor * Tl), zero past factor * lengths[b].  The input rows are formed at the
+ * model's rate from the low-rate input in one kernel (on a bf16x3 / bf16x3a handle as split rows, with the fp32 residual copy when in_channels ==
+ * hidden_dim); every launch behind them is hificar_xfmr_forward's.  factor = 1 and zscore = 0 IS hificar_xfmr_forward.  B factor Tl 3072 < 2^31. */
+int hificar_xfmr_forward_lowrate(hificar_xfmr* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int Tl,
+                                 int factor, int zscore, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Test aid: the following forwards also copy the named intermediate, as rows (B, T, hidden_dim), into dst (device, `capacity` floats).
  * Names: "conv_blocks", "w_raw_in", "layers.<l>.norm1" (the attention sub-block's output), "layers.<l>" (the layer's output).

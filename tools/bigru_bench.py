@@ -10,6 +10,13 @@ alternated native / stock / native / stock in the same process: the two native w
 spread a ratio has to exceed.  Then, with hificar_profile_begin / hificar_profile_end on one native forward: time per kernel, the recurrent
 kernel's time / (2 layers * T) = microseconds per step, and the projection GEMMs' share of the total.
 --cpu adds the CPU restatement (the same torch modules on the host) at B = 1 with 1 and 16 threads.
+--interp-factor N (with --frames as the LOW-RATE frame count, e.g. --frames 500 --interp-factor 4): the low-rate front end instead.  Two legs in
+alternated windows a / b / a / b of one process, by device events:
+  materialised  stock F.interpolate(size=N frames, mode='linear', align_corners=False) on the device, then BiGRU.forward: what a user does
+                without the front end
+  lowrate       BiGRU.forward_lowrate(x, interp_factor=N): layer 1's projection at the low rate, its pre-gates interpolated
+Per leg: ms per forward, the per-kernel times of one forward from the library's event profile with the GEMMs' sum (the legs differ in layer
+1's projection only), and the bytes of workspace (the materialised leg's stretched input counted with it).
 HIFICAR_BIGRU_NS=1|2 overrides the number of sequences a workgroup sweeps (A/B runs of the tile height).
 For per-kernel figures from the profiler instead:  rocprofv3 --kernel-trace --stats -- python tools/bigru_bench.py --batches 1 --window 0.05
 Prints one JSON line per B; --out also appends them to a file."""
@@ -67,14 +74,54 @@ def window(fn, x, seconds):
     return total_ms / calls
 
 
-def kernel_profile(m, x):
+def kernel_profile(m, x, fn=None):
     lib, eng = m._lib, m.engine()
     _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
-    m(x)
+    (fn or m)(x)
     stats = (_native.HificarKernelStat * 32)()
     n = ctypes.c_int()
     _native.check(lib.hificar_profile_end(eng, stats, 32, ctypes.byref(n)), "hificar_profile_end")
     return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(n.value)}
+
+
+def lowrate_legs(native, B, Tl, f, seconds):
+    """One JSON-able record of the two legs at batch size B (see the module docstring)."""
+    import torch.nn.functional as F
+
+    C = PARAMS["in_channels"]
+    x = torch.from_numpy(uniform(1, f"bench.low.{B}", (B, C, Tl), -1.0, 1.0)).cuda()
+
+    def materialised(x):
+        return native(F.interpolate(x, size=f * Tl, mode="linear", align_corners=False))
+
+    def lowrate(x):
+        return native.forward_lowrate(x, interp_factor=f)
+
+    ya, yb = materialised(x), lowrate(x)
+    res = {"B": B, "Tl": Tl, "interp_factor": f, "T": f * Tl, "lowrate_vs_materialised_max_rel": float((ya - yb).abs().max() / ya.abs().max())}
+    for _ in range(2):
+        materialised(x), lowrate(x)
+    torch.cuda.synchronize()
+    a1 = window(materialised, x, seconds)
+    b1 = window(lowrate, x, seconds)
+    a2 = window(materialised, x, seconds)
+    b2 = window(lowrate, x, seconds)
+    res["materialised_ms"] = [round(a1, 4), round(a2, 4)]
+    res["lowrate_ms"] = [round(b1, 4), round(b2, 4)]
+    spread = abs(a1 - a2) + abs(b1 - b2)  # the two legs' window spreads, added: what a difference has to exceed
+    diff = (b1 + b2) / 2 - (a1 + a2) / 2
+    res["added_spread_ms"] = round(spread, 4)
+    res["lowrate_minus_materialised_ms"] = round(diff, 4)
+    res["verdict"] = "not separated" if abs(diff) <= spread else ("lowrate faster" if diff < 0 else "lowrate slower")
+    res["materialised_over_lowrate"] = round(((a1 + a2) / 2) / ((b1 + b2) / 2), 3)
+    lib, h = native._lib, native._native_handle()
+    res["workspace_bytes"] = {"materialised": int(lib.hificar_bigru_workspace_bytes(h, B, f * Tl)) + 4 * B * C * f * Tl,
+                              "lowrate": int(lib.hificar_bigru_workspace_bytes_lowrate(h, B, Tl, f))}
+    for leg, fn in (("materialised", materialised), ("lowrate", lowrate)):
+        prof = kernel_profile(native, x, fn)
+        res[leg + "_kernels_ms"] = {k: round(ms, 4) for k, (_, ms) in sorted(prof.items())}
+        res[leg + "_gemm_ms"] = round(sum(ms for k, (_, ms) in prof.items() if k.startswith("conv_")), 4)
+    return res
 
 
 def main():
@@ -84,6 +131,8 @@ def main():
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--no-stock", action="store_true")
+    ap.add_argument("--interp-factor", type=int, default=None,
+                    help="measure the low-rate front end: --frames low-rate frames stretched by this factor, materialised against forward_lowrate")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     T = a.frames
@@ -96,6 +145,15 @@ def main():
     stock.load_state_dict(tsd, strict=True)
     stock_cpu = stock.eval()
     lines = []
+    if a.interp_factor is not None:
+        with torch.no_grad():
+            for B in a.batches:
+                lines.append(json.dumps(lowrate_legs(native, B, T, a.interp_factor, a.window)))
+                print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     with torch.no_grad():
         if not a.no_stock:
             import copy
