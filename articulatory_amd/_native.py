@@ -128,6 +128,10 @@ SYMBOLS = (
     "hificar_bigru_forward_train",
     "hificar_bigru_forward_train_ragged",
     "hificar_bigru_backward",
+    "hificar_bigru_tape_bytes_lowrate",
+    "hificar_bigru_train_workspace_bytes_lowrate",
+    "hificar_bigru_forward_train_lowrate",
+    "hificar_bigru_backward_lowrate",
     "hificar_xfmr_create",
     "hificar_xfmr_set_weight",
     "hificar_xfmr_set_precision",
@@ -533,6 +537,15 @@ def load_library():
     lib.hificar_bigru_forward_train_ragged.restype = ci
     lib.hificar_bigru_backward.argtypes = [vp, vp, ci, ci, vp, cs, vp, vp, vp, cs, vp]
     lib.hificar_bigru_backward.restype = ci
+    lib.hificar_bigru_tape_bytes_lowrate.argtypes = [vp, ci, ci, ci]
+    lib.hificar_bigru_tape_bytes_lowrate.restype = cs
+    lib.hificar_bigru_train_workspace_bytes_lowrate.argtypes = [vp, ci, ci, ci]
+    lib.hificar_bigru_train_workspace_bytes_lowrate.restype = cs
+    lib.hificar_bigru_forward_train_lowrate.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp, cs,
+                                                        vp, cs, vp]
+    lib.hificar_bigru_forward_train_lowrate.restype = ci
+    lib.hificar_bigru_backward_lowrate.argtypes = [vp, vp, ci, ci, ci, ci, vp, cs, vp, vp, vp, cs, vp]
+    lib.hificar_bigru_backward_lowrate.restype = ci
     lib.hificar_xfmr_create.argtypes = [ctypes.POINTER(HificarXfmrConfig), ctypes.POINTER(vp)]
     lib.hificar_xfmr_create.restype = ci
     lib.hificar_xfmr_set_weight.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(c64), ci]

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 import yaml
 
+from articulatory_amd import _native
 from articulatory_amd.losses import MelSpectrogramLoss, MultiResolutionSTFTLoss, masked_l1_loss
 from articulatory_amd.models import HiFiGANGenerator
 
@@ -507,17 +508,20 @@ INVERSION_MODES = ("art", "a2m", "m2a")  # the reference's dataset modes whose c
 
 class WindowPairs(torch.utils.data.Dataset):
     """(input frames (T, Cin), target frames (T, Cout)) pairs for an inversion model: two aligned ``.npy`` scp files, or ``n`` synthetic
-    utterances.  ``swap`` (dataset_mode m2a) exchanges the two sides, as CollaterMelArt does (train.py:855-859)."""
+    utterances.  ``swap`` (dataset_mode m2a) exchanges the two sides, as CollaterMelArt does (train.py:855-859).  ``x_factor`` N > 1
+    (lowrate_interp_factor): the input side holds LOW-RATE frames, one per N target frames — l = min(len(x), len(y) // N) of them, the
+    target cut to N l; synthetic inputs are drawn at the low rate."""
 
-    def __init__(self, x_scp=None, y_scp=None, min_frames=1, swap=False, synthetic=0, frames=0, dims=(1, 1), seed=0, frames_range=None):
+    def __init__(self, x_scp=None, y_scp=None, min_frames=1, swap=False, synthetic=0, frames=0, dims=(1, 1), seed=0, frames_range=None, x_factor=1):
+        N = int(x_factor)
         if synthetic:
             rng = np.random.default_rng(seed)
             if frames_range is not None:  # utterances of unequal lengths (package_mode pad): uniform in [lo, hi], drawn before the data
                 counts = [int(n) for n in rng.integers(frames_range[0], frames_range[1] + 1, size=synthetic)]
             else:
                 counts = [frames] * synthetic
-            self.items = [(rng.standard_normal((n, dims[0])).astype(np.float32), np.tanh(rng.standard_normal((n, dims[1]))).astype(np.float32))
-                          for n in counts]
+            self.items = [(rng.standard_normal((n // N, dims[0])).astype(np.float32),
+                           np.tanh(rng.standard_normal((n // N * N, dims[1]))).astype(np.float32)) for n in counts]
             return
 
         def read(p):
@@ -528,6 +532,12 @@ class WindowPairs(torch.utils.data.Dataset):
         self.items = []
         for utt in sorted(set(xs) & set(ys)):
             a, b = np.load(xs[utt].strip()).astype(np.float32), np.load(ys[utt].strip()).astype(np.float32)
+            if N > 1:
+                x, y = (b, a) if swap else (a, b)
+                l = min(len(x), len(y) // N)
+                if N * l > min_frames:
+                    self.items.append((x[:l], y[:N * l]))
+                continue
             n = min(len(a), len(b))
             if n > min_frames:
                 self.items.append((b[:n], a[:n]) if swap else (a[:n], b[:n]))
@@ -555,6 +565,67 @@ class FrameWindowCollater:
             xs.append(a[start:start + n])
             ys.append(b[start:start + n])
         return {"x": torch.from_numpy(np.stack(xs)).transpose(2, 1).contiguous(), "y": torch.from_numpy(np.stack(ys)).transpose(2, 1).contiguous()}
+
+
+class LowRateWindowCollater:
+    """``FrameWindowCollater`` for ``lowrate_interp_factor: N`` > 1: the input side holds low-rate frames, one per N target frames.  The window
+    of n = batch_max_frames + 2 aux_context_window model-rate frames must be a multiple of N (ValueError otherwise); one random LOW-RATE
+    start s per utterance, x = a[s : s + n / N], y = b[N s : N s + n] -> {"x": (B, Cin, n / N), "y": (B, Cout, n)}.
+    A window's edges clamp at the WINDOW, not at the utterance: the model stretches the n / N frames it is given, so the first N / 2 and
+    the last N / 2 target frames of a window face its own first and last low-rate frame repeated, whatever the utterance holds beyond
+    them.  That is this package's definition of a low-rate training window (the reference stretches before it cuts)."""
+
+    def __init__(self, batch_max_frames, aux_context_window=0, factor=1, seed=None):
+        self.n, self.N = batch_max_frames + 2 * aux_context_window, int(factor)
+        if self.N < 1 or self.n % self.N:
+            raise ValueError(f"lowrate_interp_factor {factor}: the window of batch_max_frames + 2 aux_context_window = {self.n} frames is no "
+                             f"multiple of it")
+        self.rng = np.random.default_rng(seed)
+
+    def __call__(self, items):
+        nl = self.n // self.N
+        xs, ys = [], []
+        for a, b in items:
+            s = int(self.rng.integers(0, min(len(a), len(b) // self.N) - nl + 1))
+            xs.append(a[s:s + nl])
+            ys.append(b[self.N * s:self.N * s + self.n])
+        return {"x": torch.from_numpy(np.stack(xs)).transpose(2, 1).contiguous(), "y": torch.from_numpy(np.stack(ys)).transpose(2, 1).contiguous()}
+
+
+class LowRatePadCollater:
+    """``PadCollater`` for ``lowrate_interp_factor: N`` > 1: utterance i has l = min(len(a), len(b) // N) low-rate frames and its target is cut
+    to N l -> {"x": (B, Cin, Tl), "y": (B, Cout, N Tl), "lengths": (B,) int32 LOW-RATE frame counts}.  ``pad_max_frames`` counts model-rate
+    frames and must be a multiple of N (ValueError otherwise): a longer utterance is cut to a random window of pad_max_frames / N low-rate
+    frames from a low-rate start (the window's edges clamp at the window, as ``LowRateWindowCollater`` says)."""
+
+    def __init__(self, factor, pad_max_frames=None, seed=None):
+        self.N = int(factor)
+        if pad_max_frames and int(pad_max_frames) % self.N:
+            raise ValueError(f"pad_max_frames = {pad_max_frames} counts model-rate frames and must be a multiple of lowrate_interp_factor {factor}")
+        self.max_low = int(pad_max_frames) // self.N if pad_max_frames else None
+        self.rng = np.random.default_rng(seed)
+
+    def __call__(self, items):
+        N = self.N
+        xs, ys = [], []
+        for a, b in items:
+            l = min(len(a), len(b) // N)
+            s = 0
+            if self.max_low is not None and l > self.max_low:
+                s = int(self.rng.integers(0, l - self.max_low + 1))
+                l = self.max_low
+            xs.append(np.asarray(a[s:s + l], np.float32))
+            ys.append(np.asarray(b[N * s:N * (s + l)], np.float32))
+        lengths = [len(a) for a in xs]
+        Tl = max(lengths)
+        if Tl < 1:
+            raise ValueError("a batch of empty utterances")
+        x = np.zeros((len(xs), xs[0].shape[1], Tl), np.float32)
+        y = np.zeros((len(ys), ys[0].shape[1], N * Tl), np.float32)
+        for i, (a, b) in enumerate(zip(xs, ys)):
+            x[i, :, :len(a)] = a.T
+            y[i, :, :len(b)] = b.T
+        return {"x": torch.from_numpy(x), "y": torch.from_numpy(y), "lengths": torch.tensor(lengths, dtype=torch.int32)}
 
 
 class PadCollater:
@@ -655,7 +726,11 @@ class InversionTrainer:
     attention's query-tiled kernels; ``bf16x3wac``: and the wide k = 3 convs' weight gradients;
     ``bf16x3wack``: and the attention's dK, dV and table gradients), in every
     package mode; the first log line names the
-    arithmetic.  Checkpoints do not change: the weights are fp32 either way."""
+    arithmetic.  Checkpoints do not change: the weights are fp32 either way.
+    ``lowrate_interp_factor: N`` / ``lowrate_zscore: bool`` (this package's keys, defaults 1 and false; the BiGRU only, the Transformer is
+    refused): the input side of a batch holds low-rate frames, one per N target frames (``LowRateWindowCollater`` / ``LowRatePadCollater``;
+    ``lengths`` are low-rate counts); the step is ``forward_lowrate_train`` -> L1 (``masked_l1_loss`` over N * lengths), ``eval_step`` is
+    ``forward_lowrate`` with the same factor; the first log line names the factor.  Checkpoints do not change."""
 
     def __init__(self, config, device):
         self.config, self.device = config, device
@@ -696,7 +771,15 @@ class InversionTrainer:
         if self.train_precision != "f32" and gtype != "Transformer":
             raise NotImplementedError(f"train_precision {self.train_precision} is built for generator_type Transformer (got {gtype}): the BiGRU "
                                       "trains in exact fp32; drop the key")
-        logging.info(f"InversionTrainer: generator_type {gtype}, training arithmetic {self.train_precision}")
+        # lowrate_interp_factor / lowrate_zscore (this package's keys): batches carry low-rate inputs (BiGRU.forward_lowrate_train)
+        self.low_factor = _native.check_interp_factor(config.get("lowrate_interp_factor", 1))
+        self.low_zscore = bool(config.get("lowrate_zscore", False))
+        self.lowrate = self.low_factor > 1 or self.low_zscore
+        if self.lowrate and gtype != "BiGRU":
+            raise NotImplementedError(f"lowrate_interp_factor / lowrate_zscore are built for generator_type BiGRU (got {gtype}): the "
+                                      "Transformer's forward_lowrate is an inference path (nothing commutes through its k = 3 conv); drop the keys")
+        logging.info(f"InversionTrainer: generator_type {gtype}, training arithmetic {self.train_precision}"
+                     + (f", low-rate inputs: lowrate_interp_factor {self.low_factor}, lowrate_zscore {self.low_zscore}" if self.lowrate else ""))
         import articulatory_amd.models as models
 
         self.G = getattr(models, gtype)(**config["generator_params"]).to(device).train()
@@ -717,7 +800,11 @@ class InversionTrainer:
         if self.padded and "lengths" not in batch:
             raise ValueError(f"package_mode {self.package_mode}: the batch has no lengths (batch keys {sorted(batch)}); build it with PadCollater")
         if self.steps > cfg.get("generator_train_start_steps", 0):  # train.py:268
-            if self.padded:
+            if self.lowrate:
+                lengths = batch["lengths"] if self.padded else None
+                y_ = self.G.forward_lowrate_train(x, lengths, interp_factor=self.low_factor, zscore=self.low_zscore)
+                mel_loss = masked_l1_loss(y_, y, self.low_factor * lengths) if self.padded else torch.nn.functional.l1_loss(y_, y)
+            elif self.padded:
                 y_ = self.G.forward_padded(x, batch["lengths"], packed=True) if self.packed else self.G.forward_padded(x, batch["lengths"])
                 mel_loss = masked_l1_loss(y_, y, batch["lengths"])
             else:
@@ -745,7 +832,11 @@ class InversionTrainer:
         x = batch["x"].to(self.device, non_blocking=True)
         y = batch["y"].to(self.device, non_blocking=True)
         assert not self.G.training, "eval_step runs in eval mode (eval_epoch switches)"
-        mel_loss = masked_l1_loss(self.G(x, lengths=batch["lengths"]), y, batch["lengths"])
+        if self.lowrate:  # (lengths: low-rate frame counts, LowRatePadCollater)
+            y_ = self.G.forward_lowrate(x, lengths=batch["lengths"], interp_factor=self.low_factor, zscore=self.low_zscore)
+            mel_loss = masked_l1_loss(y_, y, self.low_factor * batch["lengths"])
+        else:
+            mel_loss = masked_l1_loss(self.G(x, lengths=batch["lengths"]), y, batch["lengths"])
         return {"eval/mel_loss": mel_loss, "eval/generator_loss": mel_loss * self.config.get("lambda_aux", 1.0)}
 
     def eval_epoch(self, loader, outdir=None):
@@ -800,7 +891,9 @@ def _main_inversion(a, config, device, rank):
     side; dataset_mode m2a swaps them) or --synthetic N, cut into equal windows of batch_max_frames + 2 aux_context_window frames
     (package_mode random_window, the default) or taken whole in length-bucketed, zero-padded batches (package_mode pad or pad_masked; config keys
     pad_max_frames, pad_bucket_batches; --synthetic then draws each utterance's length uniformly from one to four windows).
-    --dev-feats-scp / --dev-audio-scp: a dev set, evaluated whole every eval_interval_steps in either mode."""
+    --dev-feats-scp / --dev-audio-scp: a dev set, evaluated whole every eval_interval_steps in either mode.
+    lowrate_interp_factor: N > 1 (generator_type BiGRU): the input side holds low-rate frames, one per N target frames (LowRateWindowCollater /
+    LowRatePadCollater; --synthetic draws the inputs at the low rate)."""
     gp = config["generator_params"]
     hop = int(config.get("hop_size", 1))
     ctx = int(config.get("aux_context_window", gp.get("aux_context_window", 0)))
@@ -808,30 +901,33 @@ def _main_inversion(a, config, device, rank):
     window = frames + 2 * ctx
     pad = config.get("package_mode", "random_window") in PADDED_MODES
     swap = config.get("dataset_mode") == "m2a"
+    N = _native.check_interp_factor(config.get("lowrate_interp_factor", 1))  # > 1: the input side holds low-rate frames (LowRate*Collater)
     if a.synthetic:
         data = WindowPairs(synthetic=a.synthetic, frames=4 * window, dims=(gp.get("in_channels", 80), gp.get("out_channels", 1)), seed=rank,
-                           frames_range=(window, 4 * window) if pad else None)
+                           frames_range=(window, 4 * window) if pad else None, x_factor=N)
     else:
         if not (a.audio_scp and a.feats_scp):
             raise SystemExit(f"generator_type {config.get('generator_type')}: give --feats-scp (input frames) and --audio-scp (target frames) of .npy files, or --synthetic N")
-        data = WindowPairs(a.feats_scp, a.audio_scp, min_frames=0 if pad else window, swap=swap)
+        data = WindowPairs(a.feats_scp, a.audio_scp, min_frames=0 if pad else window, swap=swap, x_factor=N)
     sampler = None
     if pad:
+        collate = PadCollater(config.get("pad_max_frames"), seed=1234 + rank) if N == 1 else LowRatePadCollater(N, config.get("pad_max_frames"), seed=1234 + rank)
         sampler = LengthBucketBatchSampler([len(it[0]) for it in data.items], config["batch_size"], config.get("pad_bucket_batches", 16), seed=1234 + rank,
-                                           max_frames=config.get("pad_max_frames"))
-        loader = torch.utils.data.DataLoader(data, batch_sampler=sampler, collate_fn=PadCollater(config.get("pad_max_frames"), seed=1234 + rank),
-                                             num_workers=config.get("num_workers", 0))
+                                           max_frames=config.get("pad_max_frames") if N == 1 else collate.max_low)
+        loader = torch.utils.data.DataLoader(data, batch_sampler=sampler, collate_fn=collate, num_workers=config.get("num_workers", 0))
     else:
-        loader = torch.utils.data.DataLoader(data, batch_size=config["batch_size"], shuffle=True, drop_last=True,
-                                             collate_fn=FrameWindowCollater(frames, ctx, seed=1234 + rank), num_workers=config.get("num_workers", 0))
+        collate = FrameWindowCollater(frames, ctx, seed=1234 + rank) if N == 1 else LowRateWindowCollater(frames, ctx, N, seed=1234 + rank)
+        loader = torch.utils.data.DataLoader(data, batch_size=config["batch_size"], shuffle=True, drop_last=True, collate_fn=collate,
+                                             num_workers=config.get("num_workers", 0))
     if len(loader) == 0:
         raise SystemExit(f"fewer utterances ({len(data)}) than one batch ({config['batch_size']})")
     dev_loader = None
     if bool(a.dev_feats_scp) != bool(a.dev_audio_scp):
         raise SystemExit("give both --dev-feats-scp and --dev-audio-scp, or neither")
     if a.dev_feats_scp and rank == 0:  # whole utterances in file order, in either package mode
-        dev = WindowPairs(a.dev_feats_scp, a.dev_audio_scp, min_frames=0, swap=swap)
-        dev_loader = torch.utils.data.DataLoader(dev, batch_size=config["batch_size"], shuffle=False, drop_last=False, collate_fn=PadCollater())
+        dev = WindowPairs(a.dev_feats_scp, a.dev_audio_scp, min_frames=0, swap=swap, x_factor=N)
+        dev_loader = torch.utils.data.DataLoader(dev, batch_size=config["batch_size"], shuffle=False, drop_last=False,
+                                                 collate_fn=PadCollater() if N == 1 else LowRatePadCollater(N))
     if a.max_steps is not None:  # the refusal of a reachable adversarial phase looks at the steps this run will take
         config = dict(config, train_max_steps=a.max_steps)
     trainer = InversionTrainer(config, device)

@@ -7,7 +7,9 @@
 // The GEMMs are the conv engine's one-tap launches (forward and data gradients) and the weight-gradient kernels of hificar_train.hip.inc.
 // Ragged batches (hificar_bigru_forward_train_ragged): every sequence is swept over its own frame count, the batch statistics and every
 // gradient take the valid frames only; the GEMMs still run over all B T rows, and zeros in the padded rows of their operands mask them.
-// Kernels: hificar_bigru_train_kernels.hip.h.
+// Low-rate inputs (hificar_bigru_forward_train_lowrate / hificar_bigru_backward_lowrate): the same step on x at 1 / factor of the model's rate;
+// layer 1's projection and its gradients run over the B Tl low-rate rows, the interpolation and its adjoint stand between them and the sweeps.
+// Kernels: hificar_bigru_train_kernels.hip.h, hificar_frontend_kernels.hip.h.
 
 struct BigruTrain {
     struct Slot {
@@ -273,11 +275,23 @@ struct BigruTape {
     float* out;      // (B, O, T)
     int* lens;       // [B] frame counts of a ragged forward (the header says whether they hold): in the slack rows behind the first layer's
                      // gate values, which no kernel reads or writes (the tape's size is that of a dense one); a tape-less forward: a piece of its own
+    double* zstats;  // [B][mean, 1 / std] of a low-rate forward with zscore: in the slack rows behind the second layer's gate values, as lens
+                     // (a tape-less forward keeps them in the workspace's gh, which only a backward pass uses: null here)
     size_t bytes;
 };
 
-// with_gates = false: what a forward alone needs (no per-step gate values): the tape-less form, laid out inside the workspace
-static BigruTape bigru_plan_tape(const hificar_bigru* g, int B, int T, void* base, bool with_gates = true) {
+// the slack rows behind a layer's gate values (64 rows of 8H >= 512 floats) hold this many utterances' statistics
+constexpr int kBigruZscoreMaxB = 8192;
+
+// The input of a low-rate step (hificar_bigru_forward_train_lowrate): Tl low-rate frames per sequence, T = factor Tl.  Tl = 0: the input is at
+// the model's rate (hificar_bigru_forward_train[_ragged]).
+struct BigruLow {
+    int Tl = 0, factor = 1, zscore = 0;
+};
+
+// with_gates = false: what a forward alone needs (no per-step gate values): the tape-less form, laid out inside the workspace.
+// Tl > 0: the input block holds the B Tl low-rate rows; everything behind it is the tape of B x T frames.
+static BigruTape bigru_plan_tape(const hificar_bigru* g, int B, int T, void* base, bool with_gates = true, int Tl = 0) {
     const size_t rows = bigru_train_rows(B, T), H = (size_t)g->cfg.hidden_size;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -287,13 +301,15 @@ static BigruTape bigru_plan_tape(const hificar_bigru* g, int B, int T, void* bas
     };
     BigruTape t;
     t.hdr = reinterpret_cast<BigruTapeHeader*>(take(256));
-    t.x0 = reinterpret_cast<float*>(take(rows * g->cin_pad * 4));
+    t.x0 = reinterpret_cast<float*>(take((Tl > 0 ? bigru_train_rows(B, Tl) : rows) * g->cin_pad * 4));
     for (int l = 0; l < 2; ++l) t.y[l] = reinterpret_cast<float*>(take(rows * 2 * H * 4));
     for (int l = 0; l < 2; ++l) t.gates[l] = with_gates ? reinterpret_cast<float*>(take(rows * 8 * H * 4)) : nullptr;
     t.f1 = reinterpret_cast<float*>(take(rows * kBigruFc1 * 4));
     t.stats = reinterpret_cast<float*>(take(3 * kBigruFc1 * 4));
     t.out = reinterpret_cast<float*>(take((size_t)B * T * g->cfg.out_channels * 4));
     t.lens = with_gates ? reinterpret_cast<int*>(t.gates[0] + (base ? (size_t)B * T * 8 * H : 0)) : reinterpret_cast<int*>(take((size_t)B * 4));
+    t.zstats = nullptr;
+    if (Tl > 0 && with_gates) t.zstats = reinterpret_cast<double*>(t.gates[1] + (base ? (size_t)B * T * 8 * H : 0));
     t.bytes = off;
     return t;
 }
@@ -309,11 +325,13 @@ struct BigruTrainWs {
     float* colsum;  // bias-gradient partials
     float* head;    // fc2 partials [tiles][O * 128 + O]
     char* light;    // a forward without a tape keeps its rows here (bigru_plan_tape without the gate values)
+    float* gxl;     // [low-rate rows][6H], a low-rate step at factor > 1 only: layer 1's pre-gates at the low rate / the adjoint interpolation of dgx
     size_t partial_elems, colsum_elems;
     size_t bytes;
 };
 
-static BigruTrainWs bigru_plan_train_ws(const hificar_bigru* g, int B, int T, void* base) {
+// low.Tl > 0: the workspace of a low-rate step: that of B x T frames and, behind it, the [B Tl][6H] buffer (factor > 1)
+static BigruTrainWs bigru_plan_train_ws(const hificar_bigru* g, int B, int T, void* base, const BigruLow& low = BigruLow()) {
     const size_t rows = bigru_train_rows(B, T), H = (size_t)g->cfg.hidden_size;
     const int M = B * T;
     size_t off = 0;
@@ -336,12 +354,17 @@ static BigruTrainWs bigru_plan_train_ws(const hificar_bigru* g, int B, int T, vo
             w.partial_elems = std::max(w.partial_elems, wgrad_partial_elems(h, *L, 1, M));
             w.colsum_elems = std::max(w.colsum_elems, wgrad_colsum_elems(h, *L, 1, M));
         }
+        if (low.Tl > 0) {  // layer 1's weight gradient runs over the B Tl low-rate rows (its row split is chosen by the row count)
+            w.partial_elems = std::max(w.partial_elems, wgrad_partial_elems(h, g->proj[0], 1, B * low.Tl));
+            w.colsum_elems = std::max(w.colsum_elems, wgrad_colsum_elems(h, g->proj[0], 1, B * low.Tl));
+        }
     }
     w.partial = take(w.partial_elems * 4);
     w.colsum = take(w.colsum_elems * 4);
     const size_t tiles = (size_t)B * ((T + 63) / 64);
     w.head = take(tiles * (g->cfg.out_channels * (kBigruFc1 + 1)) * 4);
-    w.light = reinterpret_cast<char*>(take(bigru_plan_tape(g, B, T, nullptr, false).bytes));
+    w.light = reinterpret_cast<char*>(take(bigru_plan_tape(g, B, T, nullptr, false, low.Tl).bytes));
+    w.gxl = low.Tl > 0 && low.factor > 1 ? take(bigru_train_rows(B, low.Tl) * 6 * H * 4) : nullptr;
     w.bytes = off;
     return w;
 }
@@ -413,7 +436,8 @@ static void bigru_head_params(const hificar_bigru* g, const BigruTape& tp, int B
 // tape = NULL: the same arithmetic without a tape (no gate values are written; the rows live in the workspace): no backward pass can follow.
 // lengths = null: the dense form.  Otherwise B frame counts on the device and their sum (checked by the caller): the ragged form.
 static int bigru_forward_train_impl(hificar_bigru* g, const char* what, const float* x, const int* lengths, int valid, float* out, float* bn_batch_stats, int B,
-                                    int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape, void* workspace, void* stream_) {
+                                    int T, float dropout_p, uint64_t seed, uint64_t offset, void* tape, void* workspace, void* stream_,
+                                    const BigruLow& low = BigruLow()) {
     if (!x || !out || !bn_batch_stats) return fail(HIFICAR_E_INVALID, "%s: null tensor", what);
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HIFICAR_E_INVALID, "%s: dropout_p=%g outside [0, 1)", what, (double)dropout_p);
     int rc;
@@ -421,13 +445,18 @@ static int bigru_forward_train_impl(hificar_bigru* g, const char* what, const fl
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     BigruTrain* ts = g->train;
-    const BigruTrainWs ws = bigru_plan_train_ws(g, B, T, workspace);
-    const BigruTape tp = tape ? bigru_plan_tape(g, B, T, tape) : bigru_plan_tape(g, B, T, ws.light, false);
+    const BigruTrainWs ws = bigru_plan_train_ws(g, B, T, workspace, low);
+    const BigruTape tp = tape ? bigru_plan_tape(g, B, T, tape, true, low.Tl) : bigru_plan_tape(g, B, T, ws.light, false, low.Tl);
     const int H = g->cfg.hidden_size, C = g->cfg.in_channels, O = g->cfg.out_channels, M = B * T;
+    const int Tl = low.Tl, Ml = B * Tl;  // (a low-rate step: `lengths` are LOW-RATE frame counts, `valid` and the tape's counts are at the model's rate)
     hipLaunchKernelGGL(bigru_header_kernel, dim3(1), dim3(1), 0, stream, tp.hdr, (unsigned long long)seed, (unsigned long long)offset, dropout_p, B, T,
-                       lengths ? valid : M, lengths ? 1 : 0);
+                       lengths ? valid : M, lengths ? 1 : 0, low.factor, Tl ? Tl : T, low.zscore);
     HIP_TRY(hipGetLastError());
-    if (lengths) HIP_TRY(hipMemcpyAsync(tp.lens, lengths, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    if (lengths && !Tl) HIP_TRY(hipMemcpyAsync(tp.lens, lengths, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    if (lengths && Tl) {
+        hipLaunchKernelGGL(frontend_lengths_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, lengths, tp.lens, B, Tl, low.factor);
+        HIP_TRY(hipGetLastError());
+    }
     // the frames a ragged sweep does not write are operands of the GEMMs behind it (0 * NaN is NaN): zeros, written by this call
     auto zero_pad = [&](float* rows, int width) -> int {
         if (!lengths) return HIFICAR_OK;
@@ -437,16 +466,40 @@ static int bigru_forward_train_impl(hificar_bigru* g, const char* what, const fl
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     };
-    {
-        ProfScope prof(h, stream, "bigru_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
-        hipLaunchKernelGGL(bigru_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, tp.x0, C,
-                           g->cin_pad, T);
+    if (Tl) {
+        // the tape's input rows at the LOW rate (z-scored on the way): the interpolation commutes with the projection behind them, forwards
+        // and backwards.  Padded low-rate rows — an operand of layer 1's dW_ih — are zeros written without reading x.
+        double* const zstats = tape ? tp.zstats : reinterpret_cast<double*>(ws.gh);
+        if (low.zscore) {
+            ProfScope prof(h, stream, "frontend_stats_kernel", 0.0, 8.0 * Ml * C);
+            hipLaunchKernelGGL(frontend_stats_kernel, dim3((unsigned)B), dim3(256), 0, stream, x, lengths, zstats, C, Tl);
+            HIP_TRY(hipGetLastError());
+        }
+        ProfScope prof(h, stream, "frontend_rows_kernel", 0.0, 4.0 * Ml * (C + g->cin_pad));
+        hipLaunchKernelGGL(frontend_rows_kernel<false>, dim3((unsigned)((Tl + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, tp.x0,
+                           static_cast<char*>(nullptr), lengths, low.zscore ? zstats : static_cast<const double*>(nullptr), C, g->cin_pad, Tl, 1);
         HIP_TRY(hipGetLastError());
+    } else {
+        {
+            ProfScope prof(h, stream, "bigru_rows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
+            hipLaunchKernelGGL(bigru_rows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, x, tp.x0, C,
+                               g->cin_pad, T);
+            HIP_TRY(hipGetLastError());
+        }
+        if ((rc = zero_pad(tp.x0, g->cin_pad)) != HIFICAR_OK) return rc;
     }
-    if ((rc = zero_pad(tp.x0, g->cin_pad)) != HIFICAR_OK) return rc;
     const int NS = bigru_tile_height(g, B);
     for (int l = 0; l < 2; ++l) {
-        if ((rc = bigru_gemm(h, g->proj[l], l == 0 ? tp.x0 : ws.a, ws.gx, M, stream)) != HIFICAR_OK) return rc;
+        if (l == 0 && Tl) {  // layer 1's projection over the B Tl low-rate rows, its 6H-wide pre-gates interpolated
+            if ((rc = bigru_gemm(h, g->proj[0], tp.x0, low.factor > 1 ? ws.gxl : ws.gx, Ml, stream)) != HIFICAR_OK) return rc;
+            if (low.factor > 1) {
+                const int N4 = 6 * H / 4;
+                ProfScope prof(h, stream, "bigru_interp_gates_kernel", 3.0 * M * 6 * H, 4.0 * M * 6 * H * 3);
+                hipLaunchKernelGGL(bigru_interp_gates_kernel, dim3((unsigned)(((long long)T * N4 + 255) / 256), 1, (unsigned)B), dim3(256), 0, stream, ws.gxl, ws.gx,
+                                   lengths, N4, Tl, low.factor);
+                HIP_TRY(hipGetLastError());
+            }
+        } else if ((rc = bigru_gemm(h, g->proj[l], l == 0 ? tp.x0 : ws.a, ws.gx, M, stream)) != HIFICAR_OK) return rc;
         if ((rc = zero_pad(tp.y[l], 2 * H)) != HIFICAR_OK) return rc;  // (the sweep writes the other rows: no order between the two)
         BigruRecParams p;
         p.g = ws.gx;
@@ -513,6 +566,109 @@ extern "C" int hificar_bigru_forward_train_ragged(hificar_bigru* g, const float*
     return bigru_forward_train_impl(g, what, x, lengths, (int)valid, out, bn_batch_stats, B, T, dropout_p, seed, offset, tape, workspace, stream_);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Training on low-rate inputs: x (B, in_channels, Tl) at 1 / factor of the model's rate (and / or to be z-scored per utterance), the step that
+// hificar_bigru_forward_train[_ragged] runs on the stretched input, T = factor Tl.  interp(X) W + b = interp(X W + b) holds under the chain
+// rule too: with A the interpolation matrix, dW_ih = (A^T dGX)^T X_low, db_ih = column sums of A^T dGX (A's rows sum to one: those of dGX, to
+// rounding), dX_low = (A^T dGX) W_ih.  So the tape keeps the B Tl low-rate rows, layer 1's projection, weight gradient and data gradient run
+// over B Tl rows, and bigru_interp_gates_kernel / bigru_interp_gates_adj_kernel stand between them and the sweeps.
+// ------------------------------------------------------------------------------------------------
+extern "C" size_t hificar_bigru_tape_bytes_lowrate(const hificar_bigru* g, int B, int Tl, int factor) {
+    if (!g || !lowrate_shape_ok(B, Tl, factor)) return 0;
+    return bigru_plan_tape(g, B, Tl * factor, nullptr, true, Tl).bytes;  // (factor 1: the input block is that of B x Tl frames, the same bytes)
+}
+
+static BigruLow bigru_low(int Tl, int factor, int zscore) {
+    BigruLow low;
+    low.Tl = Tl;
+    low.factor = factor;
+    low.zscore = zscore ? 1 : 0;
+    return low;
+}
+
+extern "C" size_t hificar_bigru_train_workspace_bytes_lowrate(hificar_bigru* g, int B, int Tl, int factor) {
+    if (!g || !lowrate_shape_ok(B, Tl, factor) || bigru_train_init(g) != HIFICAR_OK) return 0;
+    return bigru_plan_train_ws(g, B, Tl * factor, nullptr, bigru_low(Tl, factor, 0)).bytes;
+}
+
+// What both low-rate entry points check, in this order: the shape, the pointers' alignment and the sizes (on a handle without its training state:
+// against the sizes known without the device, a lower bound) — everything that needs no device, so that a handle that was never finalized is
+// told so last — then the state, then the sizes again with the weight-gradient partials the device's CU count decides.
+static int bigru_lowrate_check(hificar_bigru* g, const char* what, int B, int Tl, int factor, int zscore, void* tape, size_t tape_bytes, void* workspace,
+                               size_t workspace_bytes, bool tape_optional) {
+    if (!g) return fail(HIFICAR_E_INVALID, "%s: null handle", what);
+    if (factor < 1 || factor > HIFICAR_LOWRATE_MAX_FACTOR)
+        return fail(HIFICAR_E_INVALID, "%s: factor=%d out of range (1 .. %d)", what, factor, HIFICAR_LOWRATE_MAX_FACTOR);
+    if (!lowrate_shape_ok(B, Tl, factor)) return fail(HIFICAR_E_INVALID, "%s: B=%d, Tl=%d, factor=%d out of range", what, B, Tl, factor);
+    if (zscore && B > kBigruZscoreMaxB)
+        return fail(HIFICAR_E_INVALID, "%s: B=%d above %d with zscore (what the tape's slack rows hold of statistics)", what, B, kBigruZscoreMaxB);
+    if ((!tape && !tape_optional) || reinterpret_cast<uintptr_t>(tape) % 256 || !workspace || reinterpret_cast<uintptr_t>(workspace) % 256)
+        return fail(HIFICAR_E_INVALID, "%s: tape and workspace must be 256-byte aligned device pointers", what);
+    const BigruLow low = bigru_low(Tl, factor, zscore);
+    const size_t tb = bigru_plan_tape(g, B, Tl * factor, nullptr, true, Tl).bytes;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (tape && tape_bytes < tb) return fail(HIFICAR_E_WORKSPACE, "%s: tape too small: %zu < %zu", what, tape_bytes, tb);
+        const size_t wb = bigru_plan_train_ws(g, B, Tl * factor, nullptr, low).bytes;
+        if (workspace_bytes < wb) return fail(HIFICAR_E_WORKSPACE, "%s: workspace too small: %zu < %zu", what, workspace_bytes, wb);
+        if (pass == 1) break;
+        if (!g->finalized) return fail(HIFICAR_E_STATE, "%s before hificar_bigru_finalize", what);
+        const int rc = bigru_train_init(g);
+        if (rc != HIFICAR_OK) return rc;
+        if (!g->train->have_params) return fail(HIFICAR_E_STATE, "%s before hificar_bigru_set_parameters_device", what);
+    }
+    return HIFICAR_OK;
+}
+
+// lengths = NULL: the dense form (every sequence Tl low-rate frames).  Otherwise LOW-RATE frame counts: sequence b has factor * lengths[b]
+// frames at the model's rate, and the step is hificar_bigru_forward_train_ragged's on the stretched batch: masks of the (B, T, C) tensors,
+// batch statistics over M = factor * sum(lengths) >= 2 rows, out zero past factor * lengths[b].  Every sequence is interpolated by its own
+// length (front_source / front_mix, clamped at its own last frame); padded low-rate frames of x are never read.  zscore: frontend_stats_kernel's
+// utterance statistics, applied as constants.  tape = NULL: the forward-only form.  factor = 1 without zscore IS
+// hificar_bigru_forward_train[_ragged]: the same launches, the same tape.
+extern "C" int hificar_bigru_forward_train_lowrate(hificar_bigru* g, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out,
+                                                   float* bn_batch_stats, int B, int Tl, int factor, int zscore, float dropout_p, uint64_t seed,
+                                                   uint64_t offset, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hificar_bigru_forward_train_lowrate";
+    if (!g || !x || !out || !bn_batch_stats) return fail(HIFICAR_E_INVALID, "%s: null argument", what);
+    if (factor < 1 || factor > HIFICAR_LOWRATE_MAX_FACTOR)
+        return fail(HIFICAR_E_INVALID, "%s: factor=%d out of range (1 .. %d)", what, factor, HIFICAR_LOWRATE_MAX_FACTOR);
+    if (!lowrate_shape_ok(B, Tl, factor)) return fail(HIFICAR_E_INVALID, "%s: B=%d, Tl=%d, factor=%d out of range", what, B, Tl, factor);
+    if (!lengths != !lengths_host) return fail(HIFICAR_E_INVALID, "%s: lengths and lengths_host come together (both NULL: the dense form)", what);
+    if (lengths && B > kBigruRaggedMaxB) return fail(HIFICAR_E_INVALID, "%s: B=%d above %d (what the tape's slack rows hold of lengths)", what, B, kBigruRaggedMaxB);
+    long long valid = (long long)B * Tl;
+    if (lengths_host) {
+        valid = 0;
+        for (int b = 0; b < B; ++b) {
+            if (lengths_host[b] < 0 || lengths_host[b] > Tl)
+                return fail(HIFICAR_E_INVALID, "%s: lengths[%d]=%d outside 0 .. Tl=%d", what, b, (int)lengths_host[b], Tl);
+            valid += lengths_host[b];
+        }
+    }
+    valid *= factor;
+    if (valid < 2) return fail(HIFICAR_E_INVALID, "%s: batch statistics need more than one valid frame (factor * sum of lengths = %lld)", what, valid);
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HIFICAR_E_INVALID, "%s: dropout_p=%g outside [0, 1)", what, (double)dropout_p);
+    if (factor == 1 && !zscore) {
+        // (the existing entry points on the same memory; their own checks repeat the ones above and come to the same verdicts)
+        const size_t tb = hificar_bigru_tape_bytes(g, B, Tl);
+        if ((tape && reinterpret_cast<uintptr_t>(tape) % 256) || !workspace || reinterpret_cast<uintptr_t>(workspace) % 256)
+            return fail(HIFICAR_E_INVALID, "%s: tape and workspace must be 256-byte aligned device pointers", what);
+        if (tape && tape_bytes < tb) return fail(HIFICAR_E_WORKSPACE, "%s: tape too small: %zu < %zu", what, tape_bytes, tb);
+        if (workspace_bytes < bigru_plan_train_ws(g, B, Tl, nullptr).bytes) return fail(HIFICAR_E_WORKSPACE, "%s: workspace too small", what);
+        if (!g->finalized) return fail(HIFICAR_E_STATE, "%s before hificar_bigru_finalize", what);
+        return lengths ? hificar_bigru_forward_train_ragged(g, x, lengths, lengths_host, out, bn_batch_stats, B, Tl, dropout_p, seed, offset, tape, tape_bytes,
+                                                            workspace, workspace_bytes, stream_)
+                       : hificar_bigru_forward_train(g, x, out, bn_batch_stats, B, Tl, dropout_p, seed, offset, tape, tape_bytes, workspace, workspace_bytes,
+                                                     stream_);
+    }
+    const int rc = bigru_lowrate_check(g, what, B, Tl, factor, zscore, tape, tape_bytes, workspace, workspace_bytes, true);
+    if (rc != HIFICAR_OK) return rc;
+    return bigru_forward_train_impl(g, what, x, lengths, (int)valid, out, bn_batch_stats, B, Tl * factor, dropout_p, seed, offset, tape, workspace, stream_,
+                                    bigru_low(Tl, factor, zscore));
+}
+
+static int bigru_backward_impl(hificar_bigru* g, const float* dout, int B, int T, const void* tape, float* grads, float* dx, void* workspace, void* stream_,
+                               const BigruLow& low);
+
 // dout (B, O, T) -> the gradient of every parameter in `grads` (hificar_bigru_grad_floats floats, laid out as hificar_bigru_grad_info says;
 // written, not accumulated) and, with dx non-null, of the input (B, in_channels, T).  The tape says whether its forward was ragged and with
 // which lengths: then dout past a length is not read, dx is zero there and every gradient sums valid frames only.
@@ -521,12 +677,35 @@ extern "C" int hificar_bigru_backward(hificar_bigru* g, const float* dout, int B
     int rc = bigru_train_check(g, "hificar_bigru_backward", B, T, const_cast<void*>(tape), tape_bytes, workspace, workspace_bytes);
     if (rc != HIFICAR_OK) return rc;
     if (!dout || !grads) return fail(HIFICAR_E_INVALID, "hificar_bigru_backward: null tensor");
+    return bigru_backward_impl(g, dout, B, T, tape, grads, dx, workspace, stream_, BigruLow());
+}
+
+// The backward pass of hificar_bigru_forward_train_lowrate: dout (B, O, factor Tl) -> grads as above and, with dx non-null, the input's
+// gradient AT THE LOW RATE (B, in_channels, Tl), exactly zero on padded low-rate frames.  A separate entry point, not a tape that
+// hificar_bigru_backward recognises: the tape's header lives on the device, so the host cannot read the layout out of it without a
+// synchronising copy; B, Tl, factor and zscore are the forward's, as B and T are hificar_bigru_backward's.  A z-scored forward's dx is
+// refused (the statistics' own derivative is not built).  factor = 1 without zscore IS hificar_bigru_backward.
+extern "C" int hificar_bigru_backward_lowrate(hificar_bigru* g, const float* dout, int B, int Tl, int factor, int zscore, const void* tape, size_t tape_bytes,
+                                              float* grads, float* dx, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hificar_bigru_backward_lowrate";
+    if (!g || !dout || !grads) return fail(HIFICAR_E_INVALID, "%s: null argument", what);
+    if (zscore && dx) return fail(HIFICAR_E_INVALID, "%s: dx of a z-scored forward is not built (the statistics are taken as constants)", what);
+    if (factor == 1 && !zscore && lowrate_shape_ok(B, Tl, factor))
+        return hificar_bigru_backward(g, dout, B, Tl, tape, tape_bytes, grads, dx, workspace, workspace_bytes, stream_);
+    const int rc = bigru_lowrate_check(g, what, B, Tl, factor, zscore, const_cast<void*>(tape), tape_bytes, workspace, workspace_bytes, false);
+    if (rc != HIFICAR_OK) return rc;
+    return bigru_backward_impl(g, dout, B, Tl * factor, tape, grads, dx, workspace, stream_, bigru_low(Tl, factor, zscore));
+}
+
+static int bigru_backward_impl(hificar_bigru* g, const float* dout, int B, int T, const void* tape, float* grads, float* dx, void* workspace, void* stream_,
+                               const BigruLow& low) {
+    int rc;
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     BigruTrain* ts = g->train;
-    const BigruTape tp = bigru_plan_tape(g, B, T, const_cast<void*>(tape));
-    const BigruTrainWs ws = bigru_plan_train_ws(g, B, T, workspace);
+    const BigruTape tp = bigru_plan_tape(g, B, T, const_cast<void*>(tape), true, low.Tl);
+    const BigruTrainWs ws = bigru_plan_train_ws(g, B, T, workspace, low);
     const int H = g->cfg.hidden_size, C = g->cfg.in_channels, O = g->cfg.out_channels, M = B * T;
     auto G = [&](const std::string& name) { return grads + ts->offset.at(name); };
     BwdWs bw = {};
@@ -604,16 +783,31 @@ extern "C" int hificar_bigru_backward(hificar_bigru* g, const float* dout, int B
             if ((rc = bigru_dropout(h, tp.y[0], ws.b, (size_t)M * 2 * H, tp.hdr, kBigruSiteGru1, stream)) != HIFICAR_OK) return rc;
             xin = ws.b;
         }
-        if ((rc = launch_wgrad(h, g->proj[l], ws.gx, 6 * H, xin, g->proj[l].cin_pad, 1, M, G(b + "weight_ih_l0"), bw, stream, G(b + "bias_ih_l0"))) != HIFICAR_OK)
+        // a low-rate step's layer 1: the tape's rows are the B Tl low-rate ones, and dgx goes back to them through the interpolation's adjoint
+        const float* dg = ws.gx;
+        int Mx = M, Tx = T;
+        if (l == 0 && low.Tl) {
+            Tx = low.Tl;
+            Mx = B * Tx;
+            if (low.factor > 1) {
+                const int N4 = 6 * H / 4;
+                ProfScope prof(h, stream, "bigru_interp_gates_adj_kernel", 2.0 * M * 6 * H * 2, 4.0 * (2.0 * M + Mx) * 6 * H);
+                hipLaunchKernelGGL(bigru_interp_gates_adj_kernel, dim3((unsigned)(((long long)Tx * N4 + 255) / 256), 1, (unsigned)B), dim3(256), 0, stream, ws.gx,
+                                   ws.gxl, tp.hdr, tp.lens, N4, Tx, low.factor);
+                HIP_TRY(hipGetLastError());
+                dg = ws.gxl;
+            }
+        }
+        if ((rc = launch_wgrad(h, g->proj[l], dg, 6 * H, xin, g->proj[l].cin_pad, 1, Mx, G(b + "weight_ih_l0"), bw, stream, G(b + "bias_ih_l0"))) != HIFICAR_OK)
             return rc;
         if (l == 1) {
             if ((rc = bigru_gemm(h, ts->dg_proj[1], ws.gx, ws.a, M, stream)) != HIFICAR_OK) return rc;  // d(dropout(y1))
         } else if (dx) {
             // (ragged: the padded rows of dgx are zeros, so those of dxr are sums of 0 * w: zeros, and bigru_unrows_kernel needs no mask)
-            if ((rc = bigru_gemm(h, ts->dg_proj[0], ws.gx, ws.dxr, M, stream)) != HIFICAR_OK) return rc;
-            ProfScope prof(h, stream, "bigru_unrows_kernel", 0.0, 4.0 * M * (C + g->cin_pad));
-            hipLaunchKernelGGL(bigru_unrows_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, ws.dxr, dx, C,
-                               g->cin_pad, T);
+            if ((rc = bigru_gemm(h, ts->dg_proj[0], dg, ws.dxr, Mx, stream)) != HIFICAR_OK) return rc;
+            ProfScope prof(h, stream, "bigru_unrows_kernel", 0.0, 4.0 * Mx * (C + g->cin_pad));
+            hipLaunchKernelGGL(bigru_unrows_kernel, dim3((unsigned)((Tx + 31) / 32), (unsigned)(g->cin_pad / 32), (unsigned)B), dim3(256), 0, stream, ws.dxr, dx, C,
+                               g->cin_pad, Tx);
             HIP_TRY(hipGetLastError());
         }
     }

@@ -20,6 +20,7 @@ struct BigruTapeHeader {  // the first 256 bytes of a tape: what the backward pa
     int B, T;
     int M;       // valid frames: the sum of the frame counts (dense: B T), what the batch statistics divide by
     int ragged;  // the tape's frame counts hold (hificar_bigru_forward_train_ragged); 0: every sequence is T frames long
+    int factor, Tl, zscore;  // hificar_bigru_forward_train_lowrate: T = factor Tl, the tape's input rows are the Tl low-rate ones (z-scored); else 1, T, 0
 };
 
 // the frame counts a kernel goes by: `lens` is the tape's copy, honoured only by a ragged tape
@@ -80,7 +81,7 @@ struct BigruDrop {
 };
 
 __global__ __launch_bounds__(1) void bigru_header_kernel(BigruTapeHeader* hdr, unsigned long long seed, unsigned long long offset, float p, int B, int T,
-                                                         int M, int ragged) {
+                                                         int M, int ragged, int factor, int Tl, int zscore) {
     hdr->seed = seed;
     hdr->offset = offset;
     hdr->p = p;
@@ -88,6 +89,9 @@ __global__ __launch_bounds__(1) void bigru_header_kernel(BigruTapeHeader* hdr, u
     hdr->T = T;
     hdr->M = M;
     hdr->ragged = ragged;
+    hdr->factor = factor;
+    hdr->Tl = Tl;
+    hdr->zscore = zscore;
 }
 
 // rows[b T + t][0 .. width) = 0 for lens[b] <= t < T (width % 4 == 0): the frames a ragged sweep leaves unwritten, which later GEMMs read.

@@ -9,9 +9,13 @@
 //   frontend_lengths_kernel  the low-rate frame counts times f, for every kernel behind the front end
 //   bigru_interp_gates_kernel  the same rule on rows [b Tl + i][N] -> [b f Tl + t][N]: the BiGRU's layer-1 pre-gates, projected at the low
 //                            rate (interp(X) W + b = interp(X W + b): the two weights of a frame sum to one)
+//   bigru_interp_gates_adj_kernel  its adjoint, rows [b f Tl + t][N] -> [b Tl + i][N]: the gradient of the pre-gates back at the low rate, in
+//                            front of layer 1's dW_ih, db_ih and dX when the BiGRU trains on low-rate inputs (hificar_bigru_backward_lowrate)
 // Fixed summation order, no atomics: an utterance's result does not depend on what it is batched with.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "hificar_bigru_train_kernels.hip.h"  // (the tape header and frame counts the adjoint kernel goes by)
 
 namespace hificar {
 
@@ -166,6 +170,44 @@ __global__ __launch_bounds__(256) void bigru_interp_gates_kernel(const float* __
     const float4 v = reinterpret_cast<const float4*>(g)[((size_t)b * Tl + i1) * N4 + k];
     reinterpret_cast<float4*>(y)[((size_t)b * f * Tl + t) * N4 + k] =
         make_float4(front_mix(u.x, v.x, lam), front_mix(u.y, v.y, lam), front_mix(u.z, v.z, lam), front_mix(u.w, v.w, lam));
+}
+
+// The first output frame whose i0 (before the clamp at l - 1) is j: front_source's num = 2 t + 1 - f reaches 2 f j at
+// t = f j + ceil((f - 1) / 2) = f j + f / 2; frame 0 also takes every t with 2 t + 1 <= f.
+__host__ __device__ __forceinline__ int front_first_frame(int j, int f) { return j <= 0 ? 0 : f * j + f / 2; }
+
+// The adjoint of bigru_interp_gates_kernel, for training (hificar_bigru_backward_lowrate): d [b f Tl + t][N] -> dl [b Tl + i][N],
+// dl[i] = sum over t of A[t][i] d[t] with A the interpolation matrix of front_source.  A gather: low-rate frame i receives (1 - lam_t) d[t]
+// from the frames whose i0 is i and lam_t d[t] from those whose i1 is i (i1 != i0: lam_t != 0), and by front_source these are ONE
+// contiguous run of t: from the first frame whose i0 is i - 1 (i = 0: from 0) up to the first frame whose i0 is i + 1 (i = l - 1: up to f l,
+// every frame clamped at the last one).  One thread per float4 of a low-rate row sums its run in ascending t: no atomics, one order, so an
+// utterance's gradient has the same bits in any batch.  l = the sequence's own low-rate frame count, (the tape's model-rate count) / f; rows
+// i >= l are written as zeros, and d is not read at or past f l.  16-byte loads and stores; grid (ceil(Tl N / 4 / 256), 1, B).
+__global__ __launch_bounds__(256) void bigru_interp_gates_adj_kernel(const float* __restrict__ d, float* __restrict__ dl, const BigruTapeHeader* hdr,
+                                                                     const int* __restrict__ tape_lens, int N4, int Tl, int f) {
+    const int b = blockIdx.z;
+    const int l = bigru_len(bigru_tape_lens(hdr, tape_lens), b, f * Tl) / f;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int i = (int)(e / N4), k = (int)(e - (long long)i * N4);
+    if (i >= Tl) return;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < l) {
+        const int t_end = i == l - 1 ? f * l : front_first_frame(i + 1, f);
+        const float4* const src = reinterpret_cast<const float4*>(d) + (size_t)b * f * Tl * N4 + k;
+        for (int t = front_first_frame(i - 1, f); t < t_end; ++t) {
+            int i0, i1;
+            float lam;
+            front_source(t, f, l, i0, i1, lam);
+            const float w = i0 == i ? 1.f - lam : lam;  // (i0 = i - 1 and i1 = i otherwise; lam = 0 there: the frame gives nothing)
+            if (w == 0.f) continue;
+            const float4 v = src[(size_t)t * N4];
+            acc.x += w * v.x;
+            acc.y += w * v.y;
+            acc.z += w * v.z;
+            acc.w += w * v.w;
+        }
+    }
+    reinterpret_cast<float4*>(dl)[((size_t)b * Tl + i) * N4 + k] = acc;
 }
 
 }  // namespace hificar

@@ -951,7 +951,7 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
     XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, tp.lens, lens, &ws, {}, {tp.row0, tp.pad_row}};
     auto P = [&](const std::string& name) { return ts->d_master + ts->offset.at(name); };
     hipLaunchKernelGGL(bigru_header_kernel, dim3(1), dim3(1), 0, stream, tp.hdr, (unsigned long long)seed, (unsigned long long)offset, dropout_p, B, T,
-                       lengths ? valid : M, lengths ? 1 : 0);
+                       lengths ? valid : M, lengths ? 1 : 0, 1, T, 0);
     HIP_TRY(hipGetLastError());
     if (lengths) HIP_TRY(hipMemcpyAsync(tp.lens, lengths, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, stream));
     if (Mp) {

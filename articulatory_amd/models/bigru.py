@@ -13,6 +13,8 @@ package's own counter-based generator (``set_dropout_seed``; numpy restatement: 
 
 ``forward_lowrate(x, lengths, interp_factor, zscore)`` is the reference's speech-to-EMA front end (egs/ema/voc1/local/predict_ema.py:83-101:
 linear interpolation of low-rate features, per-utterance z-score) and the eval forward in one device call (``hificar_bigru_forward_lowrate``).
+``forward_lowrate_train`` is the same front end in front of the training step, under autograd (``hificar_bigru_forward_train_lowrate`` /
+``hificar_bigru_backward_lowrate``): the model trains on the low-rate inputs themselves, and their gradient comes back at the low rate.
 
 Not built, refused with ``NotImplementedError``: ``use_ar`` (the reference's own driver for it is broken: predict_ema.py:92 passes a
 keyword ``ar_loop`` does not take) and ``use_spk_emb``.  ``lengths=`` is this package's addition for eval mode: a ragged batch in which
@@ -85,13 +87,15 @@ class _BiGRUFunction(torch.autograd.Function):
     """Autograd node of the native BiGRU in train() mode: forward = hificar_bigru_forward_train (keeps a tape), backward =
     hificar_bigru_backward.  Inputs after (module, x, p, seed, offset, names) are the module's parameters in ``names`` order.  Returns
     (out, batch statistics (2, 128): mean | biased variance of the batch norm's input); the statistics carry no gradient.  ``module._lens``
-    (None, or the (host, device) int32 lengths of a ragged batch) is read at forward time; the tape keeps the lengths for the backward."""
+    (None, or the (host, device) int32 lengths of a ragged batch) is read at forward time; the tape keeps the lengths for the backward.
+    ``module._low`` (None, or (interp_factor, zscore) of ``forward_lowrate_train``): x is (B, in_channels, Tl) at the low rate, and so is its
+    gradient (hificar_bigru_forward_train_lowrate / hificar_bigru_backward_lowrate)."""
 
     @staticmethod
     def forward(ctx, module, x, p, seed, offset, names, *params):
-        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True, lens=module._lens)
+        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True, lens=module._lens, low=module._low)
         B, _, T = x.shape
-        ctx.module, ctx.names, ctx.tape, ctx.toff, ctx.BT = module, names, tape, toff, (B, T)
+        ctx.module, ctx.names, ctx.tape, ctx.toff, ctx.BT, ctx.low = module, names, tape, toff, (B, T), module._low
         ctx.save_for_backward(*params)  # torch's own version check covers an in-place edit that bumps Parameter._version ...
         ctx.steps_seen = module._steps_seen  # ... and this one a fused optimizer step, which does not
         ctx.mark_non_differentiable(stats)
@@ -113,10 +117,14 @@ class _BiGRUFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             grads = torch.empty(int(lib.hificar_bigru_grad_floats(handle)), dtype=torch.float32, device=dev)
-            ws_ptr, ws_bytes = module._train_workspace(B, T)
-            rc = lib.hificar_bigru_backward(handle, dout.data_ptr(), B, T, ctx.tape.data_ptr() + ctx.toff, ctx.tape.numel() - ctx.toff,
-                                            grads.data_ptr(), dx.data_ptr() if dx is not None else None, ws_ptr, ws_bytes, stream)
-        _native.check(rc, "hificar_bigru_backward")
+            tail = (ctx.tape.data_ptr() + ctx.toff, ctx.tape.numel() - ctx.toff, grads.data_ptr(), dx.data_ptr() if dx is not None else None)
+            if ctx.low is None:
+                ws_ptr, ws_bytes = module._train_workspace(B, T)
+                rc = lib.hificar_bigru_backward(handle, dout.data_ptr(), B, T, *tail, ws_ptr, ws_bytes, stream)
+            else:  # (T: low-rate frames, as x has them; dx likewise)
+                ws_ptr, ws_bytes = module._train_workspace(B, T, factor=ctx.low[0])
+                rc = lib.hificar_bigru_backward_lowrate(handle, dout.data_ptr(), B, T, ctx.low[0], 1 if ctx.low[1] else 0, *tail, ws_ptr, ws_bytes, stream)
+        _native.check(rc, "hificar_bigru_backward" if ctx.low is None else "hificar_bigru_backward_lowrate")
         views = {name: grads[off:off + num] for name, off, num in _grad_layout(module)}
         gw = tuple(views[n].view(t.shape) if need else None for n, t, need in zip(ctx.names, params, ctx.needs_input_grad[6:]))
         ctx.tape = None
@@ -154,6 +162,7 @@ class BiGRU(torch.nn.Module):
         self._steps_seen = 0     # optimizer steps noticed so far
         self._calls = 0          # training forwards so far: the dropout generator's offset
         self._lens = None        # the lengths of the ragged training forward under way (forward_padded)
+        self._low = None         # (interp_factor, zscore) of the low-rate training forward under way (forward_lowrate_train)
         # drawn from torch's generator (after the parameters): torch.manual_seed makes a training run repeatable
         self._dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         from ..utils.optim_hook import watch
@@ -323,9 +332,16 @@ class BiGRU(torch.nn.Module):
             self._send_parameters()
         return handle
 
-    def _train_workspace(self, B, T):
-        """One grow-only scratch buffer shared by the training forward and the backward pass (hificar_bigru_train_workspace_bytes)."""
-        n = self._lib.hificar_bigru_train_workspace_bytes(self._handle, B, T) + 256
+    def _train_workspace(self, B, T, factor=None):
+        """One grow-only scratch buffer shared by the training forward and the backward pass (hificar_bigru_train_workspace_bytes; ``factor``:
+        T low-rate frames, hificar_bigru_train_workspace_bytes_lowrate)."""
+        if factor is None:
+            n = self._lib.hificar_bigru_train_workspace_bytes(self._handle, B, T) + 256
+        else:
+            n = self._lib.hificar_bigru_train_workspace_bytes_lowrate(self._handle, B, T, factor)
+            if n == 0:
+                raise RuntimeError(f"BiGRU.forward_lowrate_train: B={B}, Tl={T}, interp_factor={factor} out of range")
+            n += 256
         ws = self._train_ws_buf
         if ws is None or ws.numel() < n:
             ws = torch.empty(int(n * 1.25) if ws is not None else n, dtype=torch.uint8, device=self._device())
@@ -333,29 +349,39 @@ class BiGRU(torch.nn.Module):
         off = (-ws.data_ptr()) % 256
         return ws.data_ptr() + off, ws.numel() - off
 
-    def _run_forward_train(self, x, p, seed, offset, keep_tape, lens=None):
-        """hificar_bigru_forward_train (lens = (host, device) int32 lengths: hificar_bigru_forward_train_ragged) on the current stream: (out,
-        batch statistics, tape or None, the tape's alignment offset)."""
+    def _run_forward_train(self, x, p, seed, offset, keep_tape, lens=None, low=None):
+        """hificar_bigru_forward_train (lens = (host, device) int32 lengths: hificar_bigru_forward_train_ragged; low = (interp_factor, zscore):
+        hificar_bigru_forward_train_lowrate, x and lens at the low rate) on the current stream: (out, batch statistics, tape or None, the
+        tape's alignment offset)."""
         lib, handle = self._lib, self._handle
         B, _, T = x.shape
+        f = 1 if low is None else low[0]
         dev = x.device
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             tape, toff = None, 0
             if keep_tape:
-                tape = torch.empty(lib.hificar_bigru_tape_bytes(handle, B, T) + 256, dtype=torch.uint8, device=dev)
+                n = lib.hificar_bigru_tape_bytes(handle, B, T) if low is None else lib.hificar_bigru_tape_bytes_lowrate(handle, B, T, f)
+                tape = torch.empty(n + 256, dtype=torch.uint8, device=dev)
                 toff = (-tape.data_ptr()) % 256
-            out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=dev)
+            out = torch.empty((B, self._params["out_channels"], f * T), dtype=torch.float32, device=dev)
             stats = torch.empty((2, FC1_DIM), dtype=torch.float32, device=dev)
-            ws_ptr, ws_bytes = self._train_workspace(B, T)
-            tail = (B, T, float(p), seed, offset, tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
+            ws_ptr, ws_bytes = self._train_workspace(B, T, factor=None if low is None else f)
+            tail = (float(p), seed, offset, tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
                     ws_ptr, ws_bytes, stream)
-            if lens is None:
-                rc = lib.hificar_bigru_forward_train(handle, x.data_ptr(), out.data_ptr(), stats.data_ptr(), *tail)
+            if low is not None:
+                what = "hificar_bigru_forward_train_lowrate"
+                rc = lib.hificar_bigru_forward_train_lowrate(handle, x.data_ptr(), None if lens is None else lens[1].data_ptr(),
+                                                             None if lens is None else lens[0].data_ptr(), out.data_ptr(), stats.data_ptr(), B, T, f,
+                                                             1 if low[1] else 0, *tail)
+            elif lens is None:
+                what = "hificar_bigru_forward_train"
+                rc = lib.hificar_bigru_forward_train(handle, x.data_ptr(), out.data_ptr(), stats.data_ptr(), B, T, *tail)
             else:
+                what = "hificar_bigru_forward_train_ragged"
                 rc = lib.hificar_bigru_forward_train_ragged(handle, x.data_ptr(), lens[1].data_ptr(), lens[0].data_ptr(), out.data_ptr(),
-                                                            stats.data_ptr(), *tail)
-        _native.check(rc, "hificar_bigru_forward_train" if lens is None else "hificar_bigru_forward_train_ragged")
+                                                            stats.data_ptr(), B, T, *tail)
+        _native.check(rc, what)
         return out, stats, tape, toff
 
     def _workspace(self, B, T, factor=None):
@@ -427,8 +453,8 @@ class BiGRU(torch.nn.Module):
         materialised: layer 1's input projection runs at the low rate and its pre-gates are interpolated.  ``interp_factor=1, zscore=False`` is ``forward(x, lengths=lengths)``."""
         f = _native.check_interp_factor(interp_factor)
         if self.training:
-            raise NotImplementedError("BiGRU.forward_lowrate: the low-rate front end is an inference path (call .eval(); training on "
-                                      "low-rate inputs is not built)")
+            raise NotImplementedError("BiGRU.forward_lowrate: the low-rate front end is an inference path (call .eval(); to train on "
+                                      "low-rate inputs call forward_lowrate_train)")
         if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
             raise RuntimeError("BiGRU.forward_lowrate needs a CUDA/HIP tensor; there is no CPU fallback")
         if x.dim() != 3 or x.shape[1] != self._params["in_channels"]:
@@ -453,6 +479,29 @@ class BiGRU(torch.nn.Module):
                                             ws_bytes, ctypes.c_void_p(stream))
         _native.check(rc, "hificar_bigru_forward_lowrate")
         return out
+
+    def forward_lowrate_train(self, x, lengths=None, interp_factor=1, zscore=False):
+        """Training on low-rate inputs.  eval(): ``forward_lowrate(x, lengths, interp_factor, zscore)``.  train(): x (B, in_channels, Tl) ->
+        (B, out_channels, interp_factor * Tl) under autograd, with T = interp_factor * Tl exactly ``forward`` (``lengths=None``) or
+        ``forward_padded`` (``lengths``: B LOW-RATE frame counts; sequence b has interp_factor * lengths[b] frames at the model's rate) applied
+        to the input stretched as ``forward_lowrate`` describes, every sequence clamped at its own last frame: the dropout masks are those of
+        the (B, T, C) tensors, the batch statistics run over M = interp_factor * sum(lengths) rows (M >= 2), the output is zero past
+        interp_factor * lengths[b], ``bn.running_*`` and the dropout offset advance as they do there, and with grad disabled the tape-less
+        form runs.  The stretched input is never materialised, forwards or backwards: layer 1's projection and its weight and data gradients
+        run over the B Tl low-rate rows (the interpolation commutes with them) and the tape keeps low-rate rows.  When ``x`` requires grad its
+        gradient is (B, in_channels, Tl), exactly zero on padded low-rate frames; what ``x`` holds there is never read.  ``zscore``: every
+        utterance is normalised by its own mean and population standard deviation first, taken as constants: the parameter gradients are
+        exact, an ``x`` that requires grad is refused (the statistics' own derivative is not built).  ``interp_factor=1, zscore=False`` is
+        ``forward`` / ``forward_padded`` (the same launches)."""
+        f = _native.check_interp_factor(interp_factor)
+        if not self.training:
+            return self.forward_lowrate(x, lengths=lengths, interp_factor=interp_factor, zscore=zscore)
+        if zscore and isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("BiGRU.forward_lowrate_train(zscore=True): the gradient of the input is not built (the utterance "
+                                      "statistics are taken as constants); detach x")
+        if f == 1 and not zscore:
+            return self._forward_train(x, lengths, padded=lengths is not None)
+        return self._forward_train(x, lengths, padded=lengths is not None, low=(f, bool(zscore)))
 
     @staticmethod
     def _check_lengths(lengths, B, T, device):
@@ -480,7 +529,7 @@ class BiGRU(torch.nn.Module):
             raise RuntimeError("BiGRU.forward_padded needs lengths")
         return self._forward_train(mels, lengths, padded=True)
 
-    def _forward_train(self, mels, lengths, padded=False):
+    def _forward_train(self, mels, lengths, padded=False, low=None):
         """train() mode (pytorch_models.py:45-72 with its three nn.Dropout active and the batch norm on batch statistics): with grad enabled
         the output is part of the autograd graph; without, the same arithmetic runs and its tape is dropped.  Every call — either way —
         advances the dropout generator's offset and updates bn.running_mean / running_var / num_batches_tracked as torch.nn.BatchNorm1d does."""
@@ -496,13 +545,14 @@ class BiGRU(torch.nn.Module):
         B, _, T = mels.shape
         if B < 1 or T < 1:
             raise RuntimeError(f"BiGRU.forward: empty input {tuple(mels.shape)}")
-        n = B * T
+        f = 1 if low is None else low[0]  # (low: mels and lengths are at the low rate, T low-rate frames; the model sees f T)
+        n = B * T * f
         lens = None
         if padded:
             lens = self._check_lengths(lengths, B, T, mels.device)
-            n = int(lens[0].sum())
+            n = int(lens[0].sum()) * f
         if n < 2:  # torch.nn.functional.batch_norm's own refusal
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, FC1_DIM, T] if lens is None else [n, FC1_DIM]}")
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, FC1_DIM, f * T] if lens is None else [n, FC1_DIM]}")
         self._native_handle(train=True)
         if mels.device != self._device():
             raise RuntimeError(f"BiGRU.forward: input on {mels.device}, parameters on {self._device()}")
@@ -511,14 +561,15 @@ class BiGRU(torch.nn.Module):
         names, params = tuple(n for n, _ in named), [p for _, p in named]
         offset = self._calls
         self._calls += 1
-        self._lens = lens
+        self._lens, self._low = lens, low
         try:
             if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
                 out, stats = _BiGRUFunction.apply(self, x, self._params["dropout"], self._dropout_seed, offset, names, *params)
             else:  # no graph: the same arithmetic without a tape (tape = NULL)
-                out, stats, _, _ = self._run_forward_train(x.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False, lens=lens)
+                out, stats, _, _ = self._run_forward_train(x.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False, lens=lens,
+                                                           low=low)
         finally:
-            self._lens = None
+            self._lens = self._low = None
         with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance (n: the valid frames)
             self.bn.running_mean.mul_(0.9).add_(stats[0], alpha=0.1)
             self.bn.running_var.mul_(0.9).add_(stats[1], alpha=0.1 * n / (n - 1))

@@ -612,8 +612,9 @@ void hificar_bigru_destroy(hificar_bigru* h);
  * hificar_bigru_forward_train takes equal-length batches (the reference's CollaterMelArt cuts equal windows);
  * hificar_bigru_forward_train_ragged takes whole utterances of unequal lengths (this library's definition: the reference never masks).
  * All of these may be called after hificar_bigru_finalize; the first one builds the training state.
+ * Training on low-rate inputs: hificar_bigru_forward_train_lowrate / hificar_bigru_backward_lowrate, behind hificar_bigru_backward.
  * Not built: multi-GPU BiGRU training, packed (padding-free) GEMMs for ragged batches (the Transformer has them:
- * hificar_xfmr_forward_train_packed), use_ar, use_spk_emb. ---- */
+ * hificar_xfmr_forward_train_packed), the gradient through the z-score's statistics, use_ar, use_spk_emb. ---- */
 
 /* Every float tensor of the state_dict (reference names and layouts, bn.running_mean / bn.running_var included; n = all of them, each
  * once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs, W_hh and
@@ -666,6 +667,40 @@ int hificar_bigru_forward_train_ragged(hificar_bigru* h, const float* x, const i
  * hificar_bigru_forward_train_ragged: see there. */
 int hificar_bigru_backward(hificar_bigru* h, const float* dout, int B, int T, const void* tape, size_t tape_bytes, float* grads, float* dx,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Training on low-rate inputs: the step above on x (B, in_channels, Tl) at 1 / factor of the model's rate (and / or z-scored per utterance),
+ * as the low-rate front end defines them (factor, zscore: see HIFICAR_LOWRATE_MAX_FACTOR), T = factor * Tl.  The results are those of
+ * hificar_bigru_forward_train[_ragged] on the stretched input, to rounding: interp(X) W + b = interp(X W + b) also holds under the chain rule
+ * (A: the interpolation matrix; dW_ih = (A^T dGX)^T X_low, db_ih = column sums of A^T dGX, dX_low = (A^T dGX) W_ih), so layer 1's projection, weight
+ * gradient and data gradient run over the B Tl low-rate rows and no stretched copy of the input exists, on the tape or anywhere else.
+ * Tape: the header (it records factor, Tl and zscore), the input block [B Tl (+ slack)][in_channels rounded up to 32] of LOW-RATE rows, and behind
+ * it the tape of hificar_bigru_tape_bytes(h, B, factor * Tl) unchanged; the 16 bytes of statistics per utterance of a z-scored forward lie in
+ * slack rows of that tape, as the lengths do (so B <= 8192 with zscore).  Workspace: that of hificar_bigru_train_workspace_bytes(h, B, factor * Tl)
+ * (the block a tape-less forward keeps its rows in holds the low-rate input block too) and a [B Tl][6H] buffer (the low-rate pre-gates; backwards
+ * the adjoint interpolation's output).  At factor 1 both sizes are those of the existing functions.  0: arguments out of range. ---- */
+size_t hificar_bigru_tape_bytes_lowrate(const hificar_bigru* h, int B, int Tl, int factor);
+size_t hificar_bigru_train_workspace_bytes_lowrate(hificar_bigru* h, int B, int Tl, int factor);
+
+/* lengths = NULL (with lengths_host = NULL): the dense form.  Otherwise both are required, LOW-RATE frame counts in 0 .. Tl: sequence b has
+ * factor * lengths[b] frames at the model's rate and is interpolated by its own length (clamped at its own last frame); the step is
+ * hificar_bigru_forward_train_ragged's on the stretched batch: the dropout masks are those of the (B, T, C) tensors, the batch statistics run over
+ * M = factor * sum(lengths) >= 2 rows, out (B, out_channels, factor * Tl) is zero past factor * lengths[b]; padded low-rate frames of x are never
+ * read.  zscore != 0: every utterance is normalised by its own statistics first, which the backward pass takes as constants.
+ * tape = NULL: the forward-only form.  Every argument is checked on the host before anything is enqueued, the handle's state last.
+ * factor = 1 and zscore = 0 IS hificar_bigru_forward_train[_ragged]: the same launches, the same bits, the same tape. */
+int hificar_bigru_forward_train_lowrate(hificar_bigru* h, const float* x, const int32_t* lengths, const int32_t* lengths_host, float* out,
+                                        float* bn_batch_stats, int B, int Tl, int factor, int zscore, float dropout_p, uint64_t seed, uint64_t offset,
+                                        void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The backward pass on a tape of hificar_bigru_forward_train_lowrate: dout (B, out_channels, factor * Tl) -> grads as hificar_bigru_backward
+ * writes them and, with dx non-NULL, the input's gradient at the LOW rate (B, in_channels, Tl), exactly zero on padded low-rate frames.
+ * A separate entry point: the tape's header lives in device memory, so hificar_bigru_backward could learn the layout of the tape it is handed
+ * only through a synchronising copy.  B, Tl, factor and zscore must be the forward's (as B and T must be for hificar_bigru_backward; a tape is
+ * not portable between factors).  dx with zscore != 0 is HIFICAR_E_INVALID: the statistics' own derivative is not built.
+ * factor = 1 and zscore = 0 IS hificar_bigru_backward.  The adjoint interpolation (bigru_interp_gates_adj_kernel) is a gather with a fixed
+ * summation order: deterministic, and a sequence's dx does not depend on what it is batched with. */
+int hificar_bigru_backward_lowrate(hificar_bigru* h, const float* dout, int B, int Tl, int factor, int zscore, const void* tape, size_t tape_bytes,
+                                   float* grads, float* dx, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Feature-to-feature mapping: the Transformer encoder (articulatory/models/transformer.py:21-105; layers articulatory/layers/pytorch_layers.py:94-423)

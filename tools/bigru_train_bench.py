@@ -17,7 +17,17 @@ from --seed — and three legs in alternated windows: the native ragged step (Bi
 the same padded batch (every frame counted, as the reference's pad mode trains), and a stock PyTorch-ROCm ragged step (pack_padded_sequence
 through nn.GRU, batch norm and L1 on the valid rows, the same optimizer).  Reports the padded-frame share and both native steps' kernel
 and per-step sweep times.
-   python tools/bigru_train_bench.py --ragged --out profiles/bigru_train_ragged.txt"""
+   python tools/bigru_train_bench.py --ragged --out profiles/bigru_train_ragged.txt
+
+--interp-factor N (> 1): training on low-rate inputs — the published shape (1024, 256, 18), x (B, 1024, T / N) for every B of --batches and
+T of --frames (defaults: Tl 50 / 125 -> T 200 / 500 at N = 4), and two legs in windows alternated in one process: the low-rate step
+(BiGRU.forward_lowrate_train: no stretched input, low-rate rows on the tape) against the materialised step (stock F.interpolate on the
+device, then BiGRU.forward: what a user did before), the same loss and optimizer.  With --ragged: B 32, Tl 125, low-rate lengths uniform in
+25 .. 125, forward_padded / masked_l1_loss on the materialised side (F.interpolate over the padded batch: timed, not compared — it clamps
+at the padding, not at each utterance).  Reports both legs' windows, a verdict (a leg is called faster only when the gap exceeds the two
+legs' window spreads added together, "not separated" otherwise), per-kernel times from the library's event profile and the tape and
+workspace bytes of both legs.
+   python tools/bigru_train_bench.py --interp-factor 4 --out profiles/bigru_train_lowrate.txt"""
 import argparse
 import ctypes
 import json
@@ -150,6 +160,86 @@ def ragged_main(a):
             f.write(line + "\n")
 
 
+def lowrate_main(a):
+    """--interp-factor N: see the module docstring."""
+    params, N = SHAPES["full"], a.interp_factor
+    tsd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth_bigru_state_dict(params, seed=5101).items()}
+    cases = [(32, 500 // N * N)] if a.ragged else [(B, T) for B in a.batches for T in a.frames]
+    lines = []
+    for B, T in cases:
+        if T % N:
+            raise SystemExit(f"--frames {T} is no multiple of --interp-factor {N}")
+        Tl = T // N
+        xl = torch.from_numpy(uniform(1, f"xl.{B}.{Tl}", (B, params["in_channels"], Tl), -1.0, 1.0)).cuda()
+        t = torch.from_numpy(uniform(1, f"t.{B}.{T}", (B, params["out_channels"], T), -1.0, 1.0)).cuda()
+        lens = hi = None
+        if a.ragged:
+            lens = torch.from_numpy(np.random.default_rng(a.seed).integers(Tl // 5, Tl + 1, size=B)).to(torch.int32)
+            hi = N * lens
+            valid = (torch.arange(T)[None, :] < hi[:, None]).cuda()
+            t = (t * valid[:, None, :]).contiguous()
+
+        def native_model():
+            m = BiGRU(**params, dropout=DROPOUT)
+            m.load_state_dict(tsd, strict=True)
+            return m.cuda().train()
+
+        def make(model, fwd):
+            opt = torch.optim.Adam(model.parameters(), lr=1e-4, fused=True)
+
+            def step():
+                opt.zero_grad(set_to_none=True)
+                y = fwd(model)
+                (F.l1_loss(y, t) if lens is None else masked_l1_loss(y, t, hi)).backward()
+                opt.step()
+
+            return step
+
+        def stretched():
+            return F.interpolate(xl, size=T, mode="linear", align_corners=False)
+
+        ml, mm = native_model(), native_model()
+        legs = {"lowrate": make(ml, lambda m: m.forward_lowrate_train(xl, lens, interp_factor=N)),
+                "materialised": make(mm, (lambda m: m(stretched())) if lens is None else (lambda m: m.forward_padded(stretched(), hi)))}
+        for _ in range(3):
+            for fn in legs.values():
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in legs}
+        for _ in range(2):
+            for k, fn in legs.items():
+                ms[k].append(window(fn, a.window, a.limit))
+        res = {"case": "lowrate_ragged" if a.ragged else "lowrate", "shape": "full", "B": B, "Tl": Tl, "T": T, "interp_factor": N}
+        if a.ragged:
+            res.update(seed=a.seed, valid_low_frames=int(lens.sum()), padded_share=round(1.0 - int(lens.sum()) / (B * Tl), 4))
+        for k, v in ms.items():
+            res[k + "_step_ms"] = [round(u, 3) for u in v]
+            res[k + "_spread_ms"] = round(abs(v[0] - v[1]), 3)
+        gap = sum(ms["materialised"]) / 2 - sum(ms["lowrate"]) / 2
+        spreads = abs(ms["lowrate"][0] - ms["lowrate"][1]) + abs(ms["materialised"][0] - ms["materialised"][1])
+        res["materialised_minus_lowrate_ms"] = round(gap, 3)
+        res["added_spreads_ms"] = round(spreads, 3)
+        res["verdict"] = "not separated" if abs(gap) <= spreads else ("lowrate faster" if gap > 0 else "materialised faster")
+        for tag, m in (("lowrate", ml), ("materialised", mm)):
+            prof = kernel_profile(m, legs[tag])
+            res[tag + "_kernels_ms"] = {k: round(v, 4) for k, (_, v) in sorted(prof.items())}
+            res[tag + "_kernels_total_ms"] = round(sum(v for _, v in prof.values()), 3)
+        lib, h = ml._lib, ml._handle
+        res["lowrate_tape_bytes"] = int(lib.hificar_bigru_tape_bytes_lowrate(h, B, Tl, N))
+        res["lowrate_workspace_bytes"] = int(lib.hificar_bigru_train_workspace_bytes_lowrate(h, B, Tl, N))
+        res["materialised_tape_bytes"] = int(lib.hificar_bigru_tape_bytes(h, B, T))
+        res["materialised_workspace_bytes"] = int(lib.hificar_bigru_train_workspace_bytes(h, B, T))
+        res["materialised_stretched_input_bytes"] = B * params["in_channels"] * T * 4
+        lines.append(json.dumps(res))
+        print(lines[-1], flush=True)
+        del ml, mm, legs
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def window(fn, seconds, limit):
     """Mean device milliseconds per call over a window of at least `seconds` (events around blocks of calls)."""
     total_ms, calls, n = 0.0, 0, 1
@@ -190,7 +280,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--ragged", action="store_true", help="the ragged batch's three legs instead of the dense grid")
     ap.add_argument("--seed", type=int, default=0, help="--ragged: seed of the lengths")
+    ap.add_argument("--interp-factor", type=int, default=1, help="> 1: the low-rate step against the materialised step (with --ragged: on a ragged batch)")
     a = ap.parse_args()
+    if a.interp_factor != 1:
+        _native.check_interp_factor(a.interp_factor)
+        return lowrate_main(a)
     if a.ragged:
         return ragged_main(a)
     lines = []
