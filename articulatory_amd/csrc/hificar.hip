@@ -2617,6 +2617,99 @@ extern "C" int hificar_pcm16(const float* x, int16_t* y, size_t n, void* stream)
 #include "hificar_gblock.hip.inc"
 #include "hificar_disc.hip.inc"
 #include "hificar_mel.hip.inc"
+
+// ------------------------------------------------------------------------------------------------
+// What the training states of the two feature models (BiGRU, Transformer) share: the table of their device-resident parameters — every
+// float tensor of the state_dict in one master copy, the trainable ones in front, in gradient-buffer order — and its hand-over.
+// ------------------------------------------------------------------------------------------------
+using FeatureShapes = std::map<std::string, std::vector<int64_t>>;  // a handle's `expected`: state_dict name -> shape
+
+struct FeatureParamTable {
+    struct Slot {
+        std::string name;
+        std::vector<int64_t> shape;
+        int64_t offset, numel;
+    };
+    std::vector<Slot> slots;                // the trainable parameters in gradient-buffer order (reference names and layouts)
+    std::map<std::string, int64_t> offset;  // name -> floats into the master copy (the trainable ones: = into the gradient buffer)
+    int64_t grad_total = 0;                 // floats of the gradient buffer
+    int64_t master_total = 0;               // ... of the master copy: the tensors and, behind them, the model's derived forms (its folds)
+    float* d_master = nullptr;
+
+    // the next tensor of the master copy, at a multiple of four floats
+    void add(const FeatureShapes& expected, const std::string& name, bool trainable) {
+        const std::vector<int64_t>& shape = expected.at(name);
+        int64_t n = 1;
+        for (auto v : shape) n *= v;
+        offset[name] = master_total;
+        if (trainable) slots.push_back({name, shape, master_total, n});
+        master_total += (n + 3) & ~(int64_t)3;
+    }
+    // `floats` of the master copy behind what it holds so far, for a derived form
+    int64_t reserve(int64_t floats) {
+        const int64_t at = master_total;
+        master_total += floats;
+        return at;
+    }
+    float* at(const std::string& name) const { return d_master + offset.at(name); }
+};
+
+// hificar_{bigru,xfmr}_grad_info
+static int feature_grad_info(const FeatureParamTable& tab, int i, char* name96, int64_t* offset, int64_t* numel) {
+    if (i < 0 || i >= (int)tab.slots.size()) return fail(HIFICAR_E_INVALID, "gradient index %d out of range", i);
+    const FeatureParamTable::Slot& s = tab.slots[(size_t)i];
+    snprintf(name96, 96, "%s", s.name.c_str());
+    *offset = s.offset;
+    *numel = s.numel;
+    return HIFICAR_OK;
+}
+
+// hificar_{bigru,xfmr}_set_parameters_device (`what`) up to the master copy: n device tensors, every name of `expected` exactly once.  Every
+// name is checked before any byte is copied: a refused list leaves the master copy, and with it the handle, exactly as it was.
+static int feature_upload(const FeatureShapes& expected, const FeatureParamTable& tab, const char* const* names, const float* const* data, int n,
+                          const char* what, hipStream_t stream) {
+    if (n != (int)expected.size()) return fail(HIFICAR_E_INVALID, "%s: %d tensors, the model has %zu", what, n, expected.size());
+    std::set<std::string> seen;
+    for (int i = 0; i < n; ++i) {
+        if (!names[i] || !data[i]) return fail(HIFICAR_E_INVALID, "%s: null entry %d", what, i);
+        if (!expected.count(names[i])) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", names[i]);
+        if (!seen.insert(names[i]).second) return fail(HIFICAR_E_INVALID, "tensor '%s' given twice", names[i]);
+    }
+    for (int i = 0; i < n; ++i) {
+        size_t numel = 1;
+        for (auto v : expected.at(names[i])) numel *= (size_t)v;
+        HIP_TRY(hipMemcpyAsync(tab.at(names[i]), data[i], numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+    return HIFICAR_OK;
+}
+
+// zeroed device memory on the engine's allocation list (freed with the handle)
+static int feature_alloc(hificar_engine* h, size_t bytes, void** out) {
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    h->allocs.push_back(p);
+    HIP_TRY(hipMemset(p, 0, bytes));
+    *out = p;
+    return HIFICAR_OK;
+}
+
+// rows of a training step's buffers for B x T frames: slack behind the last row for whole GEMM tiles
+static size_t feature_train_rows(int B, int T) { return round_up_sz((size_t)B * (size_t)T + 64, 256); }
+
+// The first training entry point on a handle builds its training state.  A failed set-up (out of device memory, in practice) is final for
+// the handle: what it allocated stays on the engine's allocation list until destroy, so another attempt per entry point would only grow
+// that list.  Nothing half-built stays behind.
+template <class G, class TS>
+static int feature_train_make(G* g, int (*build)(G*, TS*), const char* model) {
+    if (g->train_failed != HIFICAR_OK)
+        return fail(g->train_failed, "the %s training state could not be set up on this handle earlier; destroy it and make a new one", model);
+    std::unique_ptr<TS> ts(new TS());
+    const int rc = build(g, ts.get());
+    if (rc != HIFICAR_OK) return g->train_failed = rc;
+    g->train = ts.release();
+    return HIFICAR_OK;
+}
+
 #include "hificar_bigru.hip.inc"
 #include "hificar_bigru_train.hip.inc"
 #include "hificar_xfmr.hip.inc"

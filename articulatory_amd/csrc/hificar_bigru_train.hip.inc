@@ -12,17 +12,8 @@
 // Kernels: hificar_bigru_train_kernels.hip.h, hificar_frontend_kernels.hip.h.
 
 struct BigruTrain {
-    struct Slot {
-        std::string name;
-        std::vector<int64_t> shape;
-        int64_t offset, numel;
-    };
-    std::vector<Slot> slots;  // the trainable parameters in gradient-buffer order (reference names and layouts)
-    std::map<std::string, int64_t> offset;  // name -> floats into the master copy (the trainable ones: = into the gradient buffer)
-    int64_t grad_total = 0;    // floats of the gradient buffer
-    int64_t master_total = 0;  // ... of the master copy: the parameters, bn.running_mean / running_var, the folded fc1 (eval form)
+    FeatureParamTable tab;  // the master copy: the parameters, bn.running_mean / running_var, the folded fc1 (eval form)
     int64_t off_fold_w = 0, off_fold_b = 0;
-    float* d_master = nullptr;
     ConvLayer fc1_raw, hh;     // fc1 without the batch norm; the shape of one direction's W_hh for the weight-gradient kernels
     ConvLayer dg_proj[2], dg_fc1;
     float4* d_whht[2] = {nullptr, nullptr};  // W_hh transposed and packed for the backward sweep
@@ -62,45 +53,19 @@ static hipError_t bigru_rec_bwd_launch_one(const BigruRecBwdParams& p, hipStream
     ((NS) == 1 ? ((H) == 64 ? fn<64, 1>(__VA_ARGS__) : (H) == 128 ? fn<128, 1>(__VA_ARGS__) : (H) == 192 ? fn<192, 1>(__VA_ARGS__) : fn<256, 1>(__VA_ARGS__)) \
                : ((H) == 64 ? fn<64, 2>(__VA_ARGS__) : (H) == 128 ? fn<128, 2>(__VA_ARGS__) : (H) == 192 ? fn<192, 2>(__VA_ARGS__) : fn<256, 2>(__VA_ARGS__)))
 
-static int bigru_alloc(hificar_engine* h, size_t bytes, void** out) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    h->allocs.push_back(p);
-    HIP_TRY(hipMemset(p, 0, bytes));
-    *out = p;
-    return HIFICAR_OK;
-}
-
 static int bigru_train_build(hificar_bigru* g, BigruTrain* ts);
 
 static int bigru_train_init(hificar_bigru* g) {
     if (g->train) return HIFICAR_OK;
     if (!g->finalized) return fail(HIFICAR_E_STATE, "BiGRU training entry points need hificar_bigru_finalize first");
-    // a failed set-up (out of device memory, in practice) is final for this handle: what it allocated stays on the engine's allocation list until
-    // destroy, so another attempt per entry point would only grow that list
-    if (g->train_failed != HIFICAR_OK) return fail(g->train_failed, "the BiGRU training state could not be set up on this handle earlier; destroy it and make a new one");
-    std::unique_ptr<BigruTrain> ts(new BigruTrain());
-    const int rc = bigru_train_build(g, ts.get());
-    if (rc != HIFICAR_OK) {
-        g->train_failed = rc;
-        return rc;  // nothing half-built stays behind
-    }
-    g->train = ts.release();
-    return HIFICAR_OK;
+    return feature_train_make(g, bigru_train_build, "BiGRU");
 }
 
 static int bigru_train_build(hificar_bigru* g, BigruTrain* ts) {
     hificar_engine* h = &g->eng;
     const int H = g->cfg.hidden_size;
-    int64_t total = 0;
-    auto add = [&](const std::string& name, bool trainable) {
-        const std::vector<int64_t>& shape = g->expected.at(name);
-        int64_t n = 1;
-        for (auto v : shape) n *= v;
-        ts->offset[name] = total;
-        if (trainable) ts->slots.push_back({name, shape, total, n});
-        total += (n + 3) & ~(int64_t)3;
-    };
+    FeatureParamTable& tab = ts->tab;
+    auto add = [&](const std::string& name, bool trainable) { tab.add(g->expected, name, trainable); };
     // a layer's forward and reverse tensors of one kind lie back to back: (6H, Cin) / (6H) / 2 x (3H, H) blocks, as the GEMMs see them
     for (int l = 1; l <= 2; ++l) {
         const std::string b = "gru" + std::to_string(l) + ".";
@@ -110,18 +75,15 @@ static int bigru_train_build(hificar_bigru* g, BigruTrain* ts) {
     for (const char* n : {"fc1.0.weight", "fc1.0.bias", "bn.weight", "bn.bias"}) add(n, true);
     add(bigru_fc2_name(g) + ".weight", true);
     add(bigru_fc2_name(g) + ".bias", true);
-    ts->grad_total = total;
+    tab.grad_total = tab.master_total;
     add("bn.running_mean", false);
     add("bn.running_var", false);
-    ts->off_fold_w = total;
-    total += (int64_t)kBigruFc1 * 2 * H;
-    ts->off_fold_b = total;
-    total += kBigruFc1;
-    ts->master_total = total;
+    ts->off_fold_w = tab.reserve((int64_t)kBigruFc1 * 2 * H);
+    ts->off_fold_b = tab.reserve(kBigruFc1);
     int rc;
     void* p = nullptr;
-    if ((rc = bigru_alloc(h, (size_t)total * sizeof(float), &p)) != HIFICAR_OK) return rc;
-    ts->d_master = static_cast<float*>(p);
+    if ((rc = feature_alloc(h, (size_t)tab.master_total * sizeof(float), &p)) != HIFICAR_OK) return rc;
+    tab.d_master = static_cast<float*>(p);
 
     ConvLayer& F = ts->fc1_raw;
     F.name = "fc1#raw";
@@ -129,9 +91,9 @@ static int bigru_train_build(hificar_bigru* g, BigruTrain* ts) {
     F.cout = kBigruFc1;
     F.K = 1;
     if ((rc = plan_layer(F)) != HIFICAR_OK) return rc;
-    if ((rc = bigru_alloc(h, pack_w32_elems(F, F.chunk16) * sizeof(float), &p)) != HIFICAR_OK) return rc;
+    if ((rc = feature_alloc(h, pack_w32_elems(F, F.chunk16) * sizeof(float), &p)) != HIFICAR_OK) return rc;
     F.d_w32 = static_cast<float*>(p);
-    if ((rc = bigru_alloc(h, (size_t)F.cout_total * sizeof(float), &p)) != HIFICAR_OK) return rc;
+    if ((rc = feature_alloc(h, (size_t)F.cout_total * sizeof(float), &p)) != HIFICAR_OK) return rc;
     F.d_bias = static_cast<float*>(p);
     ConvLayer& Hh = ts->hh;
     Hh.name = "gru#hh";
@@ -143,7 +105,7 @@ static int bigru_train_build(hificar_bigru* g, BigruTrain* ts) {
         if ((rc = make_dgrad_layer(h, g->proj[l], ts->dg_proj[l], nullptr)) != HIFICAR_OK) return rc;
     if ((rc = make_dgrad_layer(h, F, ts->dg_fc1, nullptr)) != HIFICAR_OK) return rc;
     for (int l = 0; l < 2; ++l) {
-        if ((rc = bigru_alloc(h, (size_t)2 * 3 * (H / 8) * 2 * H * sizeof(float4), &p)) != HIFICAR_OK) return rc;
+        if ((rc = feature_alloc(h, (size_t)2 * 3 * (H / 8) * 2 * H * sizeof(float4), &p)) != HIFICAR_OK) return rc;
         ts->d_whht[l] = static_cast<float4*>(p);
     }
     if ((rc = wgrad_setup()) != HIFICAR_OK) return rc;
@@ -159,25 +121,17 @@ static int bigru_train_build(hificar_bigru* g, BigruTrain* ts) {
 }
 
 extern "C" int hificar_bigru_grad_count(hificar_bigru* g) {
-    if (!g || bigru_train_init(g) != HIFICAR_OK) return -1;
-    return (int)g->train->slots.size();
+    return g && bigru_train_init(g) == HIFICAR_OK ? (int)g->train->tab.slots.size() : -1;
 }
 
 extern "C" int hificar_bigru_grad_info(hificar_bigru* g, int i, char* name96, int64_t* offset, int64_t* numel) {
     if (!g || !name96 || !offset || !numel) return fail(HIFICAR_E_INVALID, "hificar_bigru_grad_info: null argument");
-    int rc = bigru_train_init(g);
-    if (rc != HIFICAR_OK) return rc;
-    if (i < 0 || i >= (int)g->train->slots.size()) return fail(HIFICAR_E_INVALID, "gradient index %d out of range", i);
-    const BigruTrain::Slot& s = g->train->slots[(size_t)i];
-    snprintf(name96, 96, "%s", s.name.c_str());
-    *offset = s.offset;
-    *numel = s.numel;
-    return HIFICAR_OK;
+    const int rc = bigru_train_init(g);
+    return rc != HIFICAR_OK ? rc : feature_grad_info(g->train->tab, i, name96, offset, numel);
 }
 
 extern "C" int64_t hificar_bigru_grad_floats(hificar_bigru* g) {
-    if (!g || bigru_train_init(g) != HIFICAR_OK) return -1;
-    return g->train->grad_total;
+    return g && bigru_train_init(g) == HIFICAR_OK ? g->train->tab.grad_total : -1;
 }
 
 // forward pack + bias of a one-tap layer, and its data-gradient pack, from a (cout, cin) weight in the master copy (as pack_jobs_for)
@@ -215,7 +169,7 @@ static int bigru_pack_layer(const ConvLayer& L, const ConvLayer* D, const float*
 
 // Every float tensor of the state_dict (reference names and layouts; n of them, each exactly once) from DEVICE memory: copied into the
 // handle's master copy and every derived form — the GEMM packs, W_hh and its transpose in the sweeps' orders, the eval path's folded fc1 —
-// rebuilt on the device, on `stream`.
+// rebuilt on the device, on `stream`.  A list that is refused (feature_upload) leaves the handle exactly as it was.
 extern "C" int hificar_bigru_set_parameters_device(hificar_bigru* g, const char* const* names, const float* const* data, int n, void* stream_) {
     if (!g || !names || !data) return fail(HIFICAR_E_INVALID, "hificar_bigru_set_parameters_device: null argument");
     int rc = bigru_train_init(g);
@@ -224,20 +178,10 @@ extern "C" int hificar_bigru_set_parameters_device(hificar_bigru* g, const char*
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
-    if (n != (int)g->expected.size()) return fail(HIFICAR_E_INVALID, "hificar_bigru_set_parameters_device: %d tensors, the model has %zu", n, g->expected.size());
-    std::set<std::string> seen;
-    for (int i = 0; i < n; ++i) {
-        if (!names[i] || !data[i]) return fail(HIFICAR_E_INVALID, "hificar_bigru_set_parameters_device: null entry %d", i);
-        auto it = g->expected.find(names[i]);
-        if (it == g->expected.end()) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", names[i]);
-        if (!seen.insert(names[i]).second) return fail(HIFICAR_E_INVALID, "tensor '%s' given twice", names[i]);
-        size_t numel = 1;
-        for (auto v : it->second) numel *= (size_t)v;
-        HIP_TRY(hipMemcpyAsync(ts->d_master + ts->offset.at(names[i]), data[i], numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    }
+    if ((rc = feature_upload(g->expected, ts->tab, names, data, n, "hificar_bigru_set_parameters_device", stream)) != HIFICAR_OK) return rc;
     const int H = g->cfg.hidden_size, O = g->cfg.out_channels;
-    float* const m = ts->d_master;
-    auto at = [&](const std::string& name) { return m + ts->offset.at(name); };
+    float* const m = ts->tab.d_master;
+    auto at = [&](const std::string& name) { return ts->tab.at(name); };
     for (int l = 0; l < 2; ++l) {
         const std::string b = "gru" + std::to_string(l + 1) + ".";
         if ((rc = bigru_pack_layer(g->proj[l], &ts->dg_proj[l], at(b + "weight_ih_l0"), at(b + "bias_ih_l0"), stream)) != HIFICAR_OK) return rc;
@@ -260,9 +204,7 @@ extern "C" int hificar_bigru_set_parameters_device(hificar_bigru* g, const char*
 // ------------------------------------------------------------------------------------------------
 // tape and workspaces
 // ------------------------------------------------------------------------------------------------
-static size_t bigru_train_rows(int B, int T) { return round_up_sz((size_t)B * (size_t)T + 64, 256); }  // slack behind the last row for whole GEMM tiles
-
-// bigru_train_rows leaves at least 64 slack rows of 8H >= 512 floats behind a layer's gate values: room for this many frame counts
+// feature_train_rows leaves at least 64 slack rows of 8H >= 512 floats behind a layer's gate values: room for this many frame counts
 constexpr int kBigruRaggedMaxB = 32768;
 
 struct BigruTape {
@@ -292,7 +234,7 @@ struct BigruLow {
 // with_gates = false: what a forward alone needs (no per-step gate values): the tape-less form, laid out inside the workspace.
 // Tl > 0: the input block holds the B Tl low-rate rows; everything behind it is the tape of B x T frames.
 static BigruTape bigru_plan_tape(const hificar_bigru* g, int B, int T, void* base, bool with_gates = true, int Tl = 0) {
-    const size_t rows = bigru_train_rows(B, T), H = (size_t)g->cfg.hidden_size;
+    const size_t rows = feature_train_rows(B, T), H = (size_t)g->cfg.hidden_size;
     size_t off = 0;
     auto take = [&](size_t bytes) {
         char* p = base ? static_cast<char*>(base) + off : nullptr;
@@ -301,7 +243,7 @@ static BigruTape bigru_plan_tape(const hificar_bigru* g, int B, int T, void* bas
     };
     BigruTape t;
     t.hdr = reinterpret_cast<BigruTapeHeader*>(take(256));
-    t.x0 = reinterpret_cast<float*>(take((Tl > 0 ? bigru_train_rows(B, Tl) : rows) * g->cin_pad * 4));
+    t.x0 = reinterpret_cast<float*>(take((Tl > 0 ? feature_train_rows(B, Tl) : rows) * g->cin_pad * 4));
     for (int l = 0; l < 2; ++l) t.y[l] = reinterpret_cast<float*>(take(rows * 2 * H * 4));
     for (int l = 0; l < 2; ++l) t.gates[l] = with_gates ? reinterpret_cast<float*>(take(rows * 8 * H * 4)) : nullptr;
     t.f1 = reinterpret_cast<float*>(take(rows * kBigruFc1 * 4));
@@ -332,7 +274,7 @@ struct BigruTrainWs {
 
 // low.Tl > 0: the workspace of a low-rate step: that of B x T frames and, behind it, the [B Tl][6H] buffer (factor > 1)
 static BigruTrainWs bigru_plan_train_ws(const hificar_bigru* g, int B, int T, void* base, const BigruLow& low = BigruLow()) {
-    const size_t rows = bigru_train_rows(B, T), H = (size_t)g->cfg.hidden_size;
+    const size_t rows = feature_train_rows(B, T), H = (size_t)g->cfg.hidden_size;
     const int M = B * T;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -364,7 +306,7 @@ static BigruTrainWs bigru_plan_train_ws(const hificar_bigru* g, int B, int T, vo
     const size_t tiles = (size_t)B * ((T + 63) / 64);
     w.head = take(tiles * (g->cfg.out_channels * (kBigruFc1 + 1)) * 4);
     w.light = reinterpret_cast<char*>(take(bigru_plan_tape(g, B, T, nullptr, false, low.Tl).bytes));
-    w.gxl = low.Tl > 0 && low.factor > 1 ? take(bigru_train_rows(B, low.Tl) * 6 * H * 4) : nullptr;
+    w.gxl = low.Tl > 0 && low.factor > 1 ? take(feature_train_rows(B, low.Tl) * 6 * H * 4) : nullptr;
     w.bytes = off;
     return w;
 }
@@ -417,10 +359,10 @@ static void bigru_head_params(const hificar_bigru* g, const BigruTape& tp, int B
     memset(&p, 0, sizeof(p));
     p.f1 = tp.f1;
     p.stats = tp.stats;
-    p.gamma = ts->d_master + ts->offset.at("bn.weight");
-    p.beta = ts->d_master + ts->offset.at("bn.bias");
-    p.w2 = ts->d_master + ts->offset.at(bigru_fc2_name(g) + ".weight");
-    p.b2 = ts->d_master + ts->offset.at(bigru_fc2_name(g) + ".bias");
+    p.gamma = ts->tab.at("bn.weight");
+    p.beta = ts->tab.at("bn.bias");
+    p.w2 = ts->tab.at(bigru_fc2_name(g) + ".weight");
+    p.b2 = ts->tab.at(bigru_fc2_name(g) + ".bias");
     p.hdr = tp.hdr;
     p.lens = tp.lens;
     p.out_keep = tp.out;
@@ -707,7 +649,7 @@ static int bigru_backward_impl(hificar_bigru* g, const float* dout, int B, int T
     const BigruTape tp = bigru_plan_tape(g, B, T, const_cast<void*>(tape), true, low.Tl);
     const BigruTrainWs ws = bigru_plan_train_ws(g, B, T, workspace, low);
     const int H = g->cfg.hidden_size, C = g->cfg.in_channels, O = g->cfg.out_channels, M = B * T;
-    auto G = [&](const std::string& name) { return grads + ts->offset.at(name); };
+    auto G = [&](const std::string& name) { return grads + ts->tab.offset.at(name); };
     BwdWs bw = {};
     bw.partial = ws.partial;
     bw.colsum = ws.colsum;
@@ -735,7 +677,7 @@ static int bigru_backward_impl(hificar_bigru* g, const float* dout, int B, int T
         HIP_TRY(hipGetLastError());
     }
     {   // batch norm (batch statistics) and the dropout in front of it
-        const float* gamma = ts->d_master + ts->offset.at("bn.weight");
+        const float* gamma = ts->tab.at("bn.weight");
         ProfScope prof(h, stream, "bigru_bn_bwd_kernels", 0.0, 20.0 * M * kBigruFc1);
         hipLaunchKernelGGL(bigru_bn_bwd_sums_kernel, dim3(kBigruFc1 / 32), dim3(1024), 0, stream, tp.f1, ws.dbn, M, tp.hdr, tp.lens, tp.stats, G("bn.weight"),
                            G("bn.bias"));

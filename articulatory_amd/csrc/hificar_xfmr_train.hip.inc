@@ -42,15 +42,7 @@ struct XfmrTrainLayer {
 };
 
 struct XfmrTrain {
-    struct Slot {
-        std::string name;
-        std::vector<int64_t> shape;
-        int64_t offset, numel;
-    };
-    std::vector<Slot> slots;                // the trainable parameters in gradient-buffer order (reference names and layouts)
-    std::map<std::string, int64_t> offset;  // name -> floats into the master copy (the trainable ones: = into the gradient buffer)
-    int64_t grad_total = 0, master_total = 0;
-    float* d_master = nullptr;
+    FeatureParamTable tab;  // the master copy: the parameters, the batch norms' running statistics, the folds, the fused q | k | v and w_o^T
     float* d_wscr = nullptr;  // (3 F, F): a fused layer's weight gradient before it is unpacked
     // the batch norms in registration order: the conv in front of each, unfolded (training) and folded (eval), and where the fold lives
     struct Bn {
@@ -114,15 +106,6 @@ static hipError_t xfmr_attn_bwd_launch(const XfmrAttnBwdParams& p, dim3 grid, fl
     return xfmr_attn_bwd_k_launch<D>(p, grid, emb_partial, M, chunks, stream);
 }
 
-static int xfmr_alloc(hificar_engine* h, size_t bytes, void** out) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    h->allocs.push_back(p);
-    HIP_TRY(hipMemset(p, 0, bytes));
-    *out = p;
-    return HIFICAR_OK;
-}
-
 // what the training arithmetic switches on (kXfmrArith); x3: every bf16x3 training arithmetic has the same GEMMs and packs
 static bool xfmr_train_x3(const hificar_xfmr* g) { return xfmr_arith(g->train_precision).x3; }
 static bool xfmr_train_w(const hificar_xfmr* g) { return xfmr_arith(g->train_precision).w; }
@@ -159,7 +142,7 @@ static int xfmr_train_alloc16(hificar_xfmr* g, XfmrTrain* ts) {
     for (ConvLayer* L : ls) {
         if (L->d_w16) continue;
         void* p = nullptr;
-        const int rc = xfmr_alloc(h, xfmr_pack16_bytes(*L), &p);
+        const int rc = feature_alloc(h, xfmr_pack16_bytes(*L), &p);
         if (rc != HIFICAR_OK) return rc;
         L->d_w16 = static_cast<uint16_t*>(p);
     }
@@ -173,32 +156,15 @@ static int xfmr_train_init(hificar_xfmr* g) {
     if (g->precision != HIFICAR_PREC_F32)
         return fail(HIFICAR_E_STATE, "this Transformer handle is packed for the %s arithmetic: training and hificar_xfmr_set_parameters_device run in exact fp32 only",
                     xfmr_precision_name(g->precision));
-    // a failed set-up (out of device memory, in practice) is final for this handle, as for the BiGRU
-    if (g->train_failed != HIFICAR_OK)
-        return fail(g->train_failed, "the Transformer training state could not be set up on this handle earlier; destroy it and make a new one");
-    std::unique_ptr<XfmrTrain> ts(new XfmrTrain());
-    const int rc = xfmr_train_build(g, ts.get());
-    if (rc != HIFICAR_OK) {
-        g->train_failed = rc;
-        return rc;
-    }
-    g->train = ts.release();
-    return HIFICAR_OK;
+    return feature_train_make(g, xfmr_train_build, "Transformer");
 }
 
 static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts) {
     hificar_engine* h = &g->eng;
     const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, E = g->cfg.elayers;
     const bool has_rp = g->rp.cout != 0;
-    int64_t total = 0;
-    auto add = [&](const std::string& name, bool trainable) {
-        const std::vector<int64_t>& shape = g->expected.at(name);
-        int64_t n = 1;
-        for (auto v : shape) n *= v;
-        ts->offset[name] = total;
-        if (trainable) ts->slots.push_back({name, shape, total, n});
-        total += (n + 3) & ~(int64_t)3;
-    };
+    FeatureParamTable& tab = ts->tab;
+    auto add = [&](const std::string& name, bool trainable) { tab.add(g->expected, name, trainable); };
     // state_dict order: a module's weight and bias lie back to back (the (d gamma | d beta) pairs are reduced as one row of 2 F)
     for (int i = 0; i < 3; ++i) {
         const std::string b = "conv_blocks." + std::to_string(i) + ".";
@@ -219,7 +185,7 @@ static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts) {
     }
     add("w_out.weight", true);
     add("w_out.bias", true);
-    ts->grad_total = total;
+    tab.grad_total = tab.master_total;
     // the batch norms, in registration order
     ts->bns.resize(has_rp ? 7 : 6);
     {
@@ -248,31 +214,26 @@ static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts) {
     }
     for (auto& bn : ts->bns) {
         const ConvLayer& L = *bn.folded;
-        bn.off_fw = total;
-        total += (int64_t)L.cout * L.cin * L.K;
-        bn.off_fb = total;
-        total += L.cout;
+        bn.off_fw = tab.reserve((int64_t)L.cout * L.cin * L.K);
+        bn.off_fb = tab.reserve(L.cout);
     }
     ts->enc.resize((size_t)E);
     for (auto& e : ts->enc) {
-        e.off_fused = total;
-        total += (int64_t)3 * F * F;
-        e.off_wot = total;
-        total += (int64_t)F * F;
+        e.off_fused = tab.reserve((int64_t)3 * F * F);
+        e.off_wot = tab.reserve((int64_t)F * F);
     }
-    ts->master_total = total;
     int rc;
     void* p = nullptr;
-    if ((rc = xfmr_alloc(h, (size_t)total * sizeof(float), &p)) != HIFICAR_OK) return rc;
-    ts->d_master = static_cast<float*>(p);
-    if ((rc = xfmr_alloc(h, (size_t)3 * F * F * sizeof(float), &p)) != HIFICAR_OK) return rc;
+    if ((rc = feature_alloc(h, (size_t)tab.master_total * sizeof(float), &p)) != HIFICAR_OK) return rc;
+    tab.d_master = static_cast<float*>(p);
+    if ((rc = feature_alloc(h, (size_t)3 * F * F * sizeof(float), &p)) != HIFICAR_OK) return rc;
     ts->d_wscr = static_cast<float*>(p);
     for (auto& bn : ts->bns) {
         const ConvLayer& L = *bn.folded;
         if ((rc = xfmr_plan(bn.raw, bn.conv + "#raw", L.cin, L.cin_pad, L.cout, L.K)) != HIFICAR_OK) return rc;
-        if ((rc = xfmr_alloc(h, pack_w32_elems(bn.raw, bn.raw.chunk16) * sizeof(float), &p)) != HIFICAR_OK) return rc;
+        if ((rc = feature_alloc(h, pack_w32_elems(bn.raw, bn.raw.chunk16) * sizeof(float), &p)) != HIFICAR_OK) return rc;
         bn.raw.d_w32 = static_cast<float*>(p);
-        if ((rc = xfmr_alloc(h, (size_t)bn.raw.cout_total * sizeof(float), &p)) != HIFICAR_OK) return rc;
+        if ((rc = feature_alloc(h, (size_t)bn.raw.cout_total * sizeof(float), &p)) != HIFICAR_OK) return rc;
         bn.raw.d_bias = static_cast<float*>(p);
         if ((rc = make_dgrad_layer(h, bn.raw, bn.dg, nullptr)) != HIFICAR_OK) return rc;
         if (bn.dg.cout_pad != L.cin_pad) return fail(HIFICAR_E_INVALID, "internal: data-gradient rows of %s are %d wide, its input rows %d", bn.conv.c_str(), bn.dg.cout_pad, L.cin_pad);
@@ -299,25 +260,17 @@ static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts) {
 }
 
 extern "C" int hificar_xfmr_grad_count(hificar_xfmr* g) {
-    if (!g || xfmr_train_init(g) != HIFICAR_OK) return -1;
-    return (int)g->train->slots.size();
+    return g && xfmr_train_init(g) == HIFICAR_OK ? (int)g->train->tab.slots.size() : -1;
 }
 
 extern "C" int hificar_xfmr_grad_info(hificar_xfmr* g, int i, char* name96, int64_t* offset, int64_t* numel) {
     if (!g || !name96 || !offset || !numel) return fail(HIFICAR_E_INVALID, "hificar_xfmr_grad_info: null argument");
-    int rc = xfmr_train_init(g);
-    if (rc != HIFICAR_OK) return rc;
-    if (i < 0 || i >= (int)g->train->slots.size()) return fail(HIFICAR_E_INVALID, "gradient index %d out of range", i);
-    const XfmrTrain::Slot& s = g->train->slots[(size_t)i];
-    snprintf(name96, 96, "%s", s.name.c_str());
-    *offset = s.offset;
-    *numel = s.numel;
-    return HIFICAR_OK;
+    const int rc = xfmr_train_init(g);
+    return rc != HIFICAR_OK ? rc : feature_grad_info(g->train->tab, i, name96, offset, numel);
 }
 
 extern "C" int64_t hificar_xfmr_grad_floats(hificar_xfmr* g) {
-    if (!g || xfmr_train_init(g) != HIFICAR_OK) return -1;
-    return g->train->grad_total;
+    return g && xfmr_train_init(g) == HIFICAR_OK ? g->train->tab.grad_total : -1;
 }
 
 static size_t xfmr_pack16_bytes(const ConvLayer& L) {
@@ -404,19 +357,7 @@ extern "C" int hificar_xfmr_set_parameters_device(hificar_xfmr* g, const char* c
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
-    if (n != (int)g->expected.size()) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_parameters_device: %d tensors, the model has %zu", n, g->expected.size());
-    std::set<std::string> seen;
-    for (int i = 0; i < n; ++i) {
-        if (!names[i] || !data[i]) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_parameters_device: null entry %d", i);
-        auto it = g->expected.find(names[i]);
-        if (it == g->expected.end()) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", names[i]);
-        if (!seen.insert(names[i]).second) return fail(HIFICAR_E_INVALID, "tensor '%s' given twice", names[i]);
-    }
-    for (int i = 0; i < n; ++i) {
-        size_t numel = 1;
-        for (auto v : g->expected.at(names[i])) numel *= (size_t)v;
-        HIP_TRY(hipMemcpyAsync(ts->d_master + ts->offset.at(names[i]), data[i], numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    }
+    if ((rc = feature_upload(g->expected, ts->tab, names, data, n, "hificar_xfmr_set_parameters_device", stream)) != HIFICAR_OK) return rc;
     if ((rc = xfmr_repack(g, stream)) != HIFICAR_OK) return rc;
     ts->have_params = true;
     return HIFICAR_OK;
@@ -430,8 +371,8 @@ static int xfmr_repack(hificar_xfmr* g, hipStream_t stream) {
     const bool x3 = xfmr_train_x3(g);
     if (x3 && (rc = xfmr_train_alloc16(g, ts)) != HIFICAR_OK) return rc;
     const int F = g->cfg.hidden_dim, d = F / kXfmrHeads;
-    float* const m = ts->d_master;
-    auto at = [&](const std::string& name) { return m + ts->offset.at(name); };
+    float* const m = ts->tab.d_master;
+    auto at = [&](const std::string& name) { return ts->tab.at(name); };
     for (auto& bn : ts->bns) {
         const ConvLayer& L = *bn.folded;
         if ((rc = xfmr_pack_dev(h, bn.raw, &bn.dg, at(bn.conv + ".weight"), at(bn.conv + ".bias"), stream, x3, true)) != HIFICAR_OK) return rc;
@@ -473,7 +414,7 @@ static int xfmr_split_tables(hificar_xfmr* g, hipStream_t stream) {
     for (XfmrEncLayer& L : g->enc) {
         if (!L.d_emb16) {
             void* p = nullptr;
-            const int rc = xfmr_alloc(h, 2 * n * sizeof(uint16_t), &p);
+            const int rc = feature_alloc(h, 2 * n * sizeof(uint16_t), &p);
             if (rc != HIFICAR_OK) return rc;
             L.d_emb16 = static_cast<uint16_t*>(p);
         }
@@ -514,8 +455,6 @@ extern "C" int hificar_xfmr_set_train_precision(hificar_xfmr* g, int precision) 
 // ------------------------------------------------------------------------------------------------
 // tape and workspace
 // ------------------------------------------------------------------------------------------------
-static size_t xfmr_train_rows(int B, int T) { return round_up_sz((size_t)B * (size_t)T + 64, 256); }  // slack behind the last row for whole GEMM tiles
-
 // Mp of a packed batch: every sequence's frames and one gap row behind each, rounded up to kXfmrPackGranule rows (the tail: gap rows).
 // 256 = kXfmrColRows = kXfmrEmbRows: whole chunks for the column sums and the table gradient, and few distinct row counts per length
 // bucket for the conv engine's plan cache, which is keyed by the row count.  0: a length outside 0 .. T, or fewer than two frames.
@@ -552,7 +491,7 @@ struct XfmrTape {
 
 // Mp = 0: the rows of the padded batch (dense, ragged); Mp > 0: a packed batch of Mp rows (T plays no part)
 static XfmrTape xfmr_plan_tape(const hificar_xfmr* g, int B, int T, void* base, int Mp = 0) {
-    const size_t rows = Mp ? (size_t)Mp : xfmr_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;  // (Mp: a multiple of 256 already, as the eval path's rows)
+    const size_t rows = Mp ? (size_t)Mp : feature_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;  // (Mp: a multiple of 256 already, as the eval path's rows)
     const int nbn = g->rp.cout ? 7 : 6;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -616,7 +555,7 @@ struct XfmrTrainWs {
 
 static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void* base, int Mp = 0) {
     const int M = Mp ? Mp : B * T;
-    const size_t rows = Mp ? (size_t)Mp : xfmr_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;
+    const size_t rows = Mp ? (size_t)Mp : feature_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;
     size_t off = 0;
     auto take = [&](size_t bytes) {
         char* p = base ? static_cast<char*>(base) + off : nullptr;
@@ -949,7 +888,7 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
     const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, O = g->cfg.out_channels, d = F / kXfmrHeads, M = Mp ? Mp : B * T;
     const int* const lens = lengths ? tp.lens : nullptr;
     XfmrTrainCtx cx = {g, h, stream, B, T, M, F, tp.hdr, tp.lens, lens, &ws, {}, {tp.row0, tp.pad_row}};
-    auto P = [&](const std::string& name) { return ts->d_master + ts->offset.at(name); };
+    auto P = [&](const std::string& name) { return ts->tab.at(name); };
     hipLaunchKernelGGL(bigru_header_kernel, dim3(1), dim3(1), 0, stream, tp.hdr, (unsigned long long)seed, (unsigned long long)offset, dropout_p, B, T,
                        lengths ? valid : M, lengths ? 1 : 0, 1, T, 0);
     HIP_TRY(hipGetLastError());
@@ -1177,8 +1116,8 @@ static int xfmr_backward_impl(hificar_xfmr* g, const float* dout, int B, int T, 
     cx.bw.colsum_elems = ws.colsum_elems;
     cx.bw.accumulate = false;
     cx.bw.defer = nullptr;
-    auto P = [&](const std::string& name) { return ts->d_master + ts->offset.at(name); };
-    auto G = [&](const std::string& name) { return grads + ts->offset.at(name); };
+    auto P = [&](const std::string& name) { return ts->tab.at(name); };
+    auto G = [&](const std::string& name) { return grads + ts->tab.offset.at(name); };
     const long long MF = (long long)M * F;
     float *d0 = ws.d[0], *d1 = ws.d[1], *d2 = ws.d[2];
     const int E = g->cfg.elayers, Op = g->w_out.cout_pad;

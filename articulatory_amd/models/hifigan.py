@@ -26,6 +26,7 @@ import torch
 
 from .. import _native
 from ..utils.buckets import raw_grad_views
+from ._feature_model import register_stats
 
 
 def _fold(v: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
@@ -300,19 +301,7 @@ class _NativeGenerator(torch.nn.Module):
 
     def register_stats(self, stats):
         """Register mean/scale buffers for input normalisation (hifigan.py:280-296)."""
-        assert stats.endswith(".h5") or stats.endswith(".npy")
-        if stats.endswith(".h5"):
-            from ..utils.hdf5 import read_hdf5  # h5py when importable, else the built-in reader of plain HDF5 files
-
-            mean = read_hdf5(stats, "mean").reshape(-1)
-            scale = read_hdf5(stats, "scale").reshape(-1)
-        else:
-            arr = np.load(stats)
-            mean = arr[0].reshape(-1)
-            scale = arr[1].reshape(-1)
-        self.register_buffer("mean", torch.from_numpy(np.asarray(mean)).float())
-        self.register_buffer("scale", torch.from_numpy(np.asarray(scale)).float())
-        logging.info("Successfully registered stats as buffer.")
+        register_stats(self, stats)
 
     def folded_state(self):
         """{reference post-remove_weight_norm key: fp32 CPU tensor} — what the C ABI consumes."""

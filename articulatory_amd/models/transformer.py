@@ -63,13 +63,12 @@ keywords are accepted and unused, as in the reference.
 """
 
 import ctypes
-import logging
 import math
 
-import numpy as np
 import torch
 
 from .. import _native
+from ._feature_model import NativeFeatureModel, _grad_layout, _tape_backward, _tape_forward  # noqa: F401  (_grad_layout: imported from here too)
 from .bigru import _BatchNormParams, _LinearParams
 
 
@@ -139,22 +138,6 @@ class _EncoderParams(torch.nn.Module):
         self.layers = torch.nn.ModuleList(layers)
 
 
-def _grad_layout(module):
-    """[(state_dict key, offset, numel)] of the native gradient buffer (hificar_xfmr_grad_info), cached per handle."""
-    cached = module.__dict__.get("_grad_info")
-    if cached is not None and cached[0] == id(module._handle):
-        return cached[1]
-    lib, handle = module._lib, module._handle
-    out = []
-    name = ctypes.create_string_buffer(96)
-    off, num = ctypes.c_int64(), ctypes.c_int64()
-    for i in range(lib.hificar_xfmr_grad_count(handle)):
-        _native.check(lib.hificar_xfmr_grad_info(handle, i, name, ctypes.byref(off), ctypes.byref(num)), "hificar_xfmr_grad_info")
-        out.append((name.value.decode(), off.value, num.value))
-    module.__dict__["_grad_info"] = (id(module._handle), out)
-    return out
-
-
 class _TransformerFunction(torch.autograd.Function):
     """Autograd node of the native Transformer in train() mode: forward = hificar_xfmr_forward_train (or, with ``module._lens`` set by
     ``forward_padded``, hificar_xfmr_forward_train_ragged: the lengths are read here, at forward time, and live on in the tape), backward =
@@ -163,44 +146,21 @@ class _TransformerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, x, p, seed, offset, names, *params):
-        out, stats, tape, toff = module._run_forward_train(x, p, seed, offset, keep_tape=True, lens=module._lens, packed=module._packed)
-        B, _, T = x.shape
-        ctx.module, ctx.names, ctx.tape, ctx.toff, ctx.BT = module, names, tape, toff, (B, T)
         ctx.packed_lens = module._lens[0] if module._packed else None  # the host lengths: hificar_xfmr_backward_packed checks them
-        ctx.save_for_backward(*params)  # torch's own version check covers an in-place edit that bumps Parameter._version ...
-        ctx.steps_seen = module._steps_seen  # ... and this one a fused optimizer step, which does not
-        ctx.mark_non_differentiable(stats)
-        return out, stats
+        return _tape_forward(ctx, module, x, p, seed, offset, names, params, packed=module._packed)
 
     @staticmethod
     def backward(ctx, dout, _dstats=None):
-        module = ctx.module
-        lib, handle = module._lib, module._handle
-        B, T = ctx.BT
-        params = ctx.saved_tensors
-        if handle is None or ctx.steps_seen != module._steps_seen:
-            raise RuntimeError("a Transformer parameter was modified between forward and backward (the backward pass reads the weights the "
-                               "forward used)")
-        dev = ctx.tape.device
-        dout = dout.to(torch.float32).contiguous()
-        dx = torch.empty((B, module._params["in_channels"], T), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            grads = torch.empty(int(lib.hificar_xfmr_grad_floats(handle)), dtype=torch.float32, device=dev)
-            tail = (ctx.tape.data_ptr() + ctx.toff, ctx.tape.numel() - ctx.toff, grads.data_ptr(), dx.data_ptr() if dx is not None else None)
-            if ctx.packed_lens is None:
-                ws_ptr, ws_bytes = module._train_workspace(B, T)
-                rc = lib.hificar_xfmr_backward(handle, dout.data_ptr(), B, T, *tail, ws_ptr, ws_bytes, stream)
+        module, packed_lens = ctx.module, ctx.packed_lens
+
+        def launch(handle, dout_ptr, B, T, tail, stream):
+            if packed_lens is None:
+                module._call("_backward", handle, dout_ptr, B, T, *tail, *module._train_workspace(B, T), stream)
             else:
-                ws_ptr, ws_bytes = module._train_workspace(B, T, module._packed_rows(ctx.packed_lens, B, T))
-                rc = lib.hificar_xfmr_backward_packed(handle, dout.data_ptr(), ctx.packed_lens.data_ptr(), B, T, *tail, ws_ptr, ws_bytes, stream)
-        _native.check(rc, "hificar_xfmr_backward" if ctx.packed_lens is None else "hificar_xfmr_backward_packed")
-        views = {name: grads[off:off + num] for name, off, num in _grad_layout(module)}
-        skip = () if module.train_relative_positions else ("relative_positional.embeddings",)
-        gw = tuple(views[n].view(t.shape) if need and not n.endswith(skip or ("\0",)) else None
-                   for n, t, need in zip(ctx.names, params, ctx.needs_input_grad[6:]))
-        ctx.tape = None
-        return (None, dx, None, None, None, None, *gw)
+                module._call("_backward_packed", handle, dout_ptr, packed_lens.data_ptr(), B, T, *tail,
+                             *module._train_workspace(B, T, module._packed_rows(packed_lens, B, T)), stream)
+
+        return _tape_backward(ctx, dout, launch, skip=() if module.train_relative_positions else ("relative_positional.embeddings",))
 
 
 class _PrecisionKeyword(type):
@@ -225,9 +185,16 @@ class _PrecisionKeyword(type):
         return self
 
 
-class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
+class Transformer(NativeFeatureModel, metaclass=_PrecisionKeyword):
     """Three ResBlocks -> Linear -> ``elayers`` post-LayerNorm encoder layers (8 heads, learned relative positions, 3072-wide feed-forward)
     -> Linear; MI355X-native, eval and train().  ``precision="bf16x3"`` (keyword only): see the module's docstring and ``set_precision``."""
+
+    _PREFIX = "hificar_xfmr"
+    _NAME = "Transformer"
+    # whether the ragged training forward under way is the packed form; this batch's statistics, for inspection
+    _TRANSIENT = {"_packed": False, "_last_stats": None}
+    _LOWRATE_TRAINING = "training on low-rate inputs is not built"
+    _LOWRATE_RANGE = " (B factor Tl 3072 < 2^31)"
 
     def __init__(self, in_channels=8, out_channels=80, elayers=6, hidden_dim=768, dropout=.2, extra_art=False,
                  use_ar=False, ar_input=512, ar_hidden=256, ar_output=128, use_tanh=False,
@@ -250,24 +217,8 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                                            for _ in range(elayers)])
         self.w_out = _LinearParams(hidden_dim, out_channels)
         self.in_emb_mat = None
-        self._handle = None
-        self._lib = None
-        self._workspace_buf = None
-        self._sig = None
-        self._train_ws_buf = None
-        self._on_device = False  # the handle's weights are refreshed from device tensors (set once a training forward ran on it)
-        self._dirty = False      # an optimizer stepped since the last hand-over (fused optimizers do not bump Parameter._version)
-        self._steps_seen = 0     # optimizer steps noticed so far
-        self._calls = 0          # training forwards so far: the dropout generator's offset
-        self._lens = None        # the lengths of the ragged training forward under way (forward_padded)
-        self._packed = False     # ... and whether it is the packed form
-        self._last_stats = None
         self.train_relative_positions = True  # False: the tables get no gradient, as in the reference (see the module's docstring)
-        # drawn from torch's generator (after the parameters): torch.manual_seed makes a training run repeatable
-        self._dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        from ..utils.optim_hook import watch
-
-        watch(self)  # fused optimizers do not bump Parameter._version: every optimizer.step() over these parameters marks them stale
+        self._init_native()
 
     def set_precision(self, precision):
         """Arithmetic of the following eval-mode forwards: "f32", "bf16x3" or "bf16x3a".  The native handle holds the weight fragments of one
@@ -309,18 +260,6 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
             raise RuntimeError(f"training runs in the exact-fp32 arithmetic: this Transformer has precision='{self.precision}' "
                                "(set_precision('f32') before train()-mode forwards)")
 
-    # ------------------------------------------------------------------ training surface
-    def set_dropout_seed(self, seed, offset=0):
-        """Seed of the dropout masks; the count of training forwards (the generator's offset) restarts at ``offset``."""
-        self._dropout_seed = int(seed) & (2 ** 64 - 1)
-        self._calls = int(offset)
-
-    def invalidate_parameters(self):
-        """The parameters changed in place without their version counters showing it (what ``utils.optim_hook`` calls after every
-        ``optimizer.step()``): the next forward hands them to the native handle again."""
-        self._dirty = True
-        self._steps_seen += 1
-
     def _batch_norms(self):
         """The BatchNorm1d holders in registration order: the order of hificar_xfmr_forward_train's bn_batch_stats."""
         out = []
@@ -329,26 +268,6 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
             if hasattr(blk, "res_norm"):
                 out.append(blk.res_norm)
         return out
-
-    # ------------------------------------------------------------------ reference surface
-    def remove_weight_norm(self):
-        """Nothing carries weight norm (transformer.py:97-98); articulatory_amd.bin.decode calls it on every model."""
-
-    def register_stats(self, stats):
-        """Register mean/scale buffers (transformer.py:79-95)."""
-        assert stats.endswith(".h5") or stats.endswith(".npy")
-        if stats.endswith(".h5"):
-            from ..utils.hdf5 import read_hdf5
-
-            mean = read_hdf5(stats, "mean").reshape(-1)
-            scale = read_hdf5(stats, "scale").reshape(-1)
-        else:
-            arr = np.load(stats)
-            mean = arr[0].reshape(-1)
-            scale = arr[1].reshape(-1)
-        self.register_buffer("mean", torch.from_numpy(np.asarray(mean)).float())
-        self.register_buffer("scale", torch.from_numpy(np.asarray(scale)).float())
-        logging.info("Successfully registered stats as buffer.")
 
     def inference(self, x, normalize_before=False):
         """(T, in_channels) -> (T, out_channels), transformer.py:100-105 statement for statement.  The reference takes ``normalize_before`` and
@@ -368,124 +287,21 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
     def _device(self):
         return self.w_out.weight.device
 
-    def native_state(self):
-        """{reference state_dict key: fp32 CPU tensor} of what the C ABI consumes (every float tensor but the input statistics)."""
-        out = {}
-        for k, v in self.state_dict().items():
-            if k in ("mean", "scale") or k.endswith("num_batches_tracked"):
-                continue
-            out[k] = v.detach().float().cpu().contiguous()
-        return out
+    def _make_config(self):
+        return _native.make_xfmr_config(self._params)
 
-    def _signature(self):
-        ts = list(self.parameters()) + [b for n, b in self.named_buffers() if n.endswith(("running_mean", "running_var"))]
-        return tuple((t.data_ptr(), t._version) for t in ts)
-
-    def _invalidate(self):
-        h = self.__dict__.get("_handle")
-        if h is not None and self._lib is not None:
-            self._lib.hificar_xfmr_destroy(h)
-        self._handle = None
-        self._workspace_buf = None
-        self._train_ws_buf = None
-        self._sig = None
-        self._on_device = False
-        self._dirty = False
-
-    def __del__(self):
-        try:
-            self._invalidate()
-        except Exception:
-            pass
-
-    def __getstate__(self):  # copies and pickles never share a native handle
-        state = self.__dict__.copy()
-        for k in ("_handle", "_lib", "_workspace_buf", "_sig", "_train_ws_buf", "_last_stats", "_lens"):
-            state[k] = None
-        state["_on_device"] = state["_dirty"] = False
-        state.pop("_grad_info", None)
-        return state
+    def _stats_shape(self):
+        return (len(self._batch_norms()), 2, self._params["hidden_dim"])
 
     def __setstate__(self, state):
         state.setdefault("train_precision", "f32")  # (a pickle from before the keyword)
         super().__setstate__(state)
-        from ..utils.optim_hook import watch
 
-        watch(self)  # a copy trains with its own optimizer
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        out = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._invalidate()
-        return out
-
-    def _apply(self, fn, *a, **kw):
-        out = super()._apply(fn, *a, **kw)
-        self._invalidate()
-        return out
-
-    def refresh_native(self):
-        """Re-upload the weights after an in-place parameter edit that the version counters do not show (``p.data.copy_``)."""
-        self._invalidate()
-
-    def _send_parameters(self):
-        """Every float tensor of the state_dict from device memory into the handle (hificar_xfmr_set_parameters_device): nothing goes
-        through the host.  The tensors are read on the current stream, in stream order with the optimizer step that wrote them."""
-        names, held = [], []
-        for k, v in self.state_dict(keep_vars=True).items():
-            if k in ("mean", "scale") or k.endswith("num_batches_tracked"):
-                continue
-            names.append(k)
-            held.append(v if (v.dtype == torch.float32 and v.is_contiguous()) else v.detach().to(torch.float32).contiguous())
-        arr = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
-        ptrs = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
-        with torch.cuda.device(self._device()):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _native.check(self._lib.hificar_xfmr_set_parameters_device(self._handle, arr, ptrs, len(held), stream),
-                          "hificar_xfmr_set_parameters_device")
-        self._on_device = True
-        self._dirty = False
-        self._sig = self._signature()
-
-    def _native_handle(self, train=False):
-        if self._handle is not None and self._on_device:
-            # a handle that has trained: its weights follow the parameters on the device (eval after training sees the updated weights and
-            # running statistics without a trip through the host)
-            if self._dirty or self._sig != self._signature():
-                self._send_parameters()
-            return self._handle
-        if self._handle is not None and self._sig == self._signature() and not self._dirty:
-            if train:
-                self._send_parameters()
-            return self._handle
-        self._invalidate()
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("Transformer: parameters are on %s; the forward only exists as HIP kernels (move the model to a MI355X with "
-                               ".to('cuda')). There is no CPU fallback." % (dev,))
-        lib = _native.load_library()
-        self._lib = lib
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(dev):
-            cfg = _native.make_xfmr_config(self._params)
-            _native.check(lib.hificar_xfmr_create(ctypes.byref(cfg), ctypes.byref(handle)), "hificar_xfmr_create")
-            try:
-                for name, t in self.native_state().items():
-                    shape = (ctypes.c_int64 * t.dim())(*t.shape)
-                    _native.check(lib.hificar_xfmr_set_weight(handle, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim()),
-                                  "hificar_xfmr_set_weight")
-                _native.check(lib.hificar_xfmr_set_precision(handle, _native.XFMR_PRECISIONS[self.precision]), "hificar_xfmr_set_precision")
-                _native.check(lib.hificar_xfmr_finalize(handle), "hificar_xfmr_finalize")
-                if self.precision == "f32":  # (a bf16x3 inference handle has no training arithmetic to choose)
-                    _native.check(lib.hificar_xfmr_set_train_precision(handle, _native.XFMR_TRAIN_PRECISIONS_K[self.train_precision]),
-                                  "hificar_xfmr_set_train_precision")
-            except Exception:
-                lib.hificar_xfmr_destroy(handle)
-                raise
-        self._handle = handle
-        self._sig = self._signature()
-        if train:
-            self._send_parameters()
-        return handle
+    def _finalize_handle(self, handle):
+        self._call("_set_precision", handle, _native.XFMR_PRECISIONS[self.precision])
+        super()._finalize_handle(handle)
+        if self.precision == "f32":  # (a bf16x3 inference handle has no training arithmetic to choose)
+            self._call("_set_train_precision", handle, _native.XFMR_TRAIN_PRECISIONS_K[self.train_precision])
 
     def _packed_rows(self, host_lens, B, T):
         """Mp of a packed batch (hificar_xfmr_packed_rows), from the host lengths."""
@@ -499,15 +315,10 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         """One grow-only scratch buffer shared by the training forward and the backward pass (hificar_xfmr_train_workspace_bytes, or, for a
         packed step of ``packed_rows`` rows, hificar_xfmr_train_workspace_bytes_packed)."""
         if packed_rows is None:
-            n = self._lib.hificar_xfmr_train_workspace_bytes(self._handle, B, T) + 256
+            n = self._lib.hificar_xfmr_train_workspace_bytes(self._handle, B, T)
         else:
-            n = self._lib.hificar_xfmr_train_workspace_bytes_packed(self._handle, B, packed_rows) + 256
-        ws = self._train_ws_buf
-        if ws is None or ws.numel() < n:
-            ws = torch.empty(int(n * 1.25) if ws is not None else n, dtype=torch.uint8, device=self._device())
-            self._train_ws_buf = ws
-        off = (-ws.data_ptr()) % 256
-        return ws.data_ptr() + off, ws.numel() - off
+            n = self._lib.hificar_xfmr_train_workspace_bytes_packed(self._handle, B, packed_rows)
+        return self._scratch("_train_ws_buf", n)
 
     def _run_forward_train(self, x, p, seed, offset, keep_tape, lens=None, packed=False):
         """hificar_xfmr_forward_train (lens = (host, device) int32 lengths: hificar_xfmr_forward_train_ragged, or, packed,
@@ -524,7 +335,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                 tape = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
                 toff = (-tape.data_ptr()) % 256
             out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=dev)
-            stats = torch.empty((len(self._batch_norms()), 2, self._params["hidden_dim"]), dtype=torch.float32, device=dev)
+            stats = torch.empty(self._stats_shape(), dtype=torch.float32, device=dev)
             ws_ptr, ws_bytes = self._train_workspace(B, T, mp)
             tail = (B, T, float(p), seed, offset, tape.data_ptr() + toff if keep_tape else None, tape.numel() - toff if keep_tape else 0,
                     ws_ptr, ws_bytes, stream)
@@ -535,29 +346,6 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
                 rc = getattr(lib, what)(handle, x.data_ptr(), lens[1].data_ptr(), lens[0].data_ptr(), out.data_ptr(), stats.data_ptr(), *tail)
         _native.check(rc, what)
         return out, stats, tape, toff
-
-    def _workspace(self, B, T, factor=None):
-        """One grow-only scratch buffer per model (hificar_xfmr_workspace_bytes; ``factor``: T low-rate frames,
-        hificar_xfmr_workspace_bytes_lowrate)."""
-        if factor is None:
-            n = self._lib.hificar_xfmr_workspace_bytes(self._handle, B, T) + 256
-        else:
-            n = self._lib.hificar_xfmr_workspace_bytes_lowrate(self._handle, B, T, factor)
-            if n == 0:
-                raise RuntimeError(f"Transformer.forward_lowrate: B={B}, Tl={T}, interp_factor={factor} out of range (B factor Tl 3072 < 2^31)")
-            n += 256
-        ws = self._workspace_buf
-        if ws is None or ws.numel() < n:
-            # work already enqueued on the old buffer keeps it alive through the caching allocator's stream ordering
-            ws = torch.empty(int(n * 1.25) if ws is not None else n, dtype=torch.uint8, device=self._device())
-            self._workspace_buf = ws
-        off = (-ws.data_ptr()) % 256
-        return ws.data_ptr() + off, ws.numel() - off
-
-    def engine(self):
-        """The engine handle for ``hificar_profile_begin`` / ``hificar_profile_end`` (per-kernel device times; tools/transformer_bench.py)."""
-        handle = self._native_handle()  # first: it is what loads self._lib
-        return ctypes.c_void_p(self._lib.hificar_xfmr_engine(handle))
 
     def debug_tap(self, name, dst=None):
         """Test aid (hificar_xfmr_debug_tap): the following forwards copy intermediate ``name`` — "conv_blocks", "w_raw_in", "layers.N.norm1",
@@ -576,69 +364,7 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         if self.training:
             self._refuse_bf16x3_training()  # (before any device check)
             return self._forward_train(x, lengths)
-        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-            raise RuntimeError("Transformer.forward needs a CUDA/HIP tensor; there is no CPU fallback")
-        if x.dim() != 3 or x.shape[1] != self._params["in_channels"]:
-            raise RuntimeError(f"Transformer.forward: expected (B, {self._params['in_channels']}, T), got {tuple(x.shape)}")
-        handle = self._native_handle()
-        if x.device != self._device():
-            raise RuntimeError(f"Transformer.forward: input on {x.device}, parameters on {self._device()}")
-        c = x.detach().to(torch.float32).contiguous()
-        B, _, T = c.shape
-        if B < 1 or T < 1:
-            raise RuntimeError(f"Transformer.forward: empty input {tuple(c.shape)}")
-        lens = (None, None)
-        keep = None
-        if lengths is not None:
-            keep = self._check_lengths(lengths, B, T, c.device)
-            lens = (keep[1].data_ptr(), keep[0].data_ptr())
-        out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=c.device)
-        with torch.cuda.device(c.device):
-            ws_ptr, ws_bytes = self._workspace(B, T)
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = self._lib.hificar_xfmr_forward(handle, c.data_ptr(), lens[0], lens[1], out.data_ptr(), B, T, ws_ptr, ws_bytes,
-                                                ctypes.c_void_p(stream))
-        _native.check(rc, "hificar_xfmr_forward")
-        return out
-
-    def forward_lowrate(self, x, lengths=None, interp_factor=1, zscore=False):
-        """The reference's speech-to-EMA front end and the forward behind it in one call (egs/ema/voc1/local/predict_ema.py:83-101), eval mode:
-        x (B, in_channels, Tl) features as the speech model or the MFCC extraction delivers them -> (B, out_channels, interp_factor * Tl).
-        ``interp_factor`` (an integer in 1 .. 16; the reference uses 4, or 2 for its hprc models): every utterance is stretched as
-        ``F.interpolate(x_b[..., :l_b], size=interp_factor * l_b, mode='linear', align_corners=False)`` does, clamped at its own first and last
-        frame.  ``zscore``: every utterance is first normalised by the mean and the population standard deviation of all its in_channels x l_b
-        elements (``scipy.stats.zscore(feat, axis=None)``, predict_ema.py:32-35; a constant utterance gives NaN, as scipy does).  ``lengths``
-        (B LOW-RATE frame counts): a ragged batch — an utterance's result is bitwise that of running it alone, the output is zero past
-        interp_factor * lengths[b], and padded input frames are never read.  Neither the stretched nor the normalised input is ever
-        materialised: the input rows are formed at the model's rate from the low-rate input, at any ``precision``.  ``interp_factor=1, zscore=False`` is ``forward(x, lengths=lengths)``."""
-        f = _native.check_interp_factor(interp_factor)
-        if self.training:
-            raise NotImplementedError("Transformer.forward_lowrate: the low-rate front end is an inference path (call .eval(); training on "
-                                      "low-rate inputs is not built)")
-        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-            raise RuntimeError("Transformer.forward_lowrate needs a CUDA/HIP tensor; there is no CPU fallback")
-        if x.dim() != 3 or x.shape[1] != self._params["in_channels"]:
-            raise RuntimeError(f"Transformer.forward_lowrate: expected (B, {self._params['in_channels']}, Tl), got {tuple(x.shape)}")
-        handle = self._native_handle()
-        if x.device != self._device():
-            raise RuntimeError(f"Transformer.forward_lowrate: input on {x.device}, parameters on {self._device()}")
-        c = x.detach().to(torch.float32).contiguous()
-        B, _, Tl = c.shape
-        if B < 1 or Tl < 1:
-            raise RuntimeError(f"Transformer.forward_lowrate: empty input {tuple(c.shape)}")
-        lens = (None, None)
-        keep = None
-        if lengths is not None:
-            keep = self._check_lengths(lengths, B, Tl, c.device)
-            lens = (keep[1].data_ptr(), keep[0].data_ptr())
-        out = torch.empty((B, self._params["out_channels"], f * Tl), dtype=torch.float32, device=c.device)
-        with torch.cuda.device(c.device):
-            ws_ptr, ws_bytes = self._workspace(B, Tl, factor=f)
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = self._lib.hificar_xfmr_forward_lowrate(handle, c.data_ptr(), lens[0], lens[1], out.data_ptr(), B, Tl, f, 1 if zscore else 0, ws_ptr,
-                                           ws_bytes, ctypes.c_void_p(stream))
-        _native.check(rc, "hificar_xfmr_forward_lowrate")
-        return out
+        return self._forward_eval("forward", x, lengths)
 
     def forward_padded(self, x, lengths, packed=False):
         """A batch of whole utterances, zero-padded to (B, in_channels, T), with their frame counts ``lengths`` (B values in 0 .. T).
@@ -673,54 +399,9 @@ class Transformer(torch.nn.Module, metaclass=_PrecisionKeyword):
         if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
             raise NotImplementedError("Transformer.forward in train() mode needs a CUDA/HIP tensor: the training path exists on the device "
                                       "only, as HIP kernels (there is no CPU fallback)")
-        if x.dim() != 3 or x.shape[1] != self._params["in_channels"]:
-            raise RuntimeError(f"Transformer.forward: expected (B, {self._params['in_channels']}, T), got {tuple(x.shape)}")
-        B, _, T = x.shape
-        if B < 1 or T < 1:
-            raise RuntimeError(f"Transformer.forward: empty input {tuple(x.shape)}")
-        n = B * T
-        lens = None
-        if padded:
-            lens = self._check_lengths(lengths, B, T, x.device)
-            n = int(lens[0].sum())
-        if n < 2:  # torch.nn.functional.batch_norm's own refusal
-            raise ValueError("Expected more than 1 value per channel when training, got input size "
-                             f"{[B, self._params['hidden_dim'], T] if lens is None else [n, self._params['hidden_dim']]}")
-        self._native_handle(train=True)
-        if x.device != self._device():
-            raise RuntimeError(f"Transformer.forward: input on {x.device}, parameters on {self._device()}")
+        lens, n = self._train_head(x, lengths, padded)
         if padded and packed:
-            self._packed_rows(lens[0], B, T)  # (a batch too large to pack is refused here, before a mask is drawn)
-        c = x.to(torch.float32).contiguous()
-        named = list(self.named_parameters())
-        names, params = tuple(k for k, _ in named), [p for _, p in named]
-        offset = self._calls
-        self._calls += 1
-        self._lens, self._packed = lens, packed and padded
-        try:
-            if torch.is_grad_enabled() and (c.requires_grad or any(p.requires_grad for p in params)):
-                out, stats = _TransformerFunction.apply(self, c, self._params["dropout"], self._dropout_seed, offset, names, *params)
-            else:  # no graph: the same arithmetic without a tape (tape = NULL)
-                out, stats, _, _ = self._run_forward_train(c.detach(), self._params["dropout"], self._dropout_seed, offset, keep_tape=False, lens=lens,
-                                                            packed=self._packed)
-        finally:
-            self._lens, self._packed = None, False
+            self._packed_rows(lens[0], x.shape[0], x.shape[2])  # (a batch too large to pack is refused here, before a mask is drawn)
+        out, stats = self._train_tail(_TransformerFunction, x, lens, n, packed=packed and padded)
         self._last_stats = stats.detach()  # (number of batch norms, 2, hidden_dim): this batch's mean | biased variance, for inspection
-        with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance (n: the valid frames)
-            for j, bn in enumerate(self._batch_norms()):
-                bn.running_mean.mul_(0.9).add_(stats[j, 0], alpha=0.1)
-                bn.running_var.mul_(0.9).add_(stats[j, 1], alpha=0.1 * n / (n - 1))
-                bn.num_batches_tracked += 1
-        # (the running statistics only enter the eval path: its folds are refreshed when an eval forward next asks for the handle)
         return out
-
-    @staticmethod
-    def _check_lengths(lengths, B, T, device):
-        """(host int32 tensor, its copy on ``device``) of B frame counts in 0 .. T."""
-        host = (lengths.detach().to("cpu", torch.int32) if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths, dtype=torch.int32))
-        host = host.reshape(-1).contiguous()
-        if host.numel() != B:
-            raise RuntimeError(f"lengths has {host.numel()} entries for a batch of {B}")
-        if int(host.min()) < 0 or int(host.max()) > T:
-            raise RuntimeError(f"lengths must lie in [0, {T}]")
-        return host, host.to(device).contiguous()

@@ -619,7 +619,9 @@ void hificar_bigru_destroy(hificar_bigru* h);
 /* Every float tensor of the state_dict (reference names and layouts, bn.running_mean / bn.running_var included; n = all of them, each
  * once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs, W_hh and
  * its transpose in the recurrent kernels' orders, and the eval-mode fold of the batch norm into fc1 — hificar_bigru_forward sees the
- * new weights too.  Call it after every optimizer step (and before the first hificar_bigru_forward_train). */
+ * new weights too.  Call it after every optimizer step (and before the first hificar_bigru_forward_train).  Every name is checked before any
+ * byte is copied: a list that is refused (HIFICAR_E_INVALID: another count, a null entry, an unknown or a repeated name) leaves the handle
+ * exactly as it was. */
 int hificar_bigru_set_parameters_device(hificar_bigru* h, const char* const* names, const float* const* data, int n, void* stream);
 
 /* The gradient buffer: hificar_bigru_grad_floats(h) floats; tensor i of hificar_bigru_grad_count(h) has the reference's state_dict name
@@ -889,7 +891,7 @@ int hificar_debug_split_taps_t(int M, int C, int T, const int32_t* lengths, cons
  * each once) from DEVICE memory.  The handle copies them and rebuilds every derived form on the device, on `stream`: the GEMM packs (the
  * q | k | v weight of 3 hidden_dim rows and w_o's transpose among them), their data-gradient packs, and the eval-mode fold of every batch norm
  * into its conv — hificar_xfmr_forward sees the new weights too.  Call it after every optimizer step (and before the first
- * hificar_xfmr_forward_train). */
+ * hificar_xfmr_forward_train).  A list that is refused leaves the handle exactly as it was, as hificar_bigru_set_parameters_device. */
 int hificar_xfmr_set_parameters_device(hificar_xfmr* h, const char* const* names, const float* const* data, int n, void* stream);
 
 /* The gradient buffer: hificar_xfmr_grad_floats(h) floats; tensor i of hificar_xfmr_grad_count(h) has the reference's state_dict name

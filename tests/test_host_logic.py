@@ -347,29 +347,73 @@ def test_reassigned_parameter_objects_refresh_the_cached_lists():
     assert names1 == names0 and any(t is new for t in tensors1)
 
 
-def test_copies_and_pickles_of_native_modules_register_themselves_and_share_no_native_state():
-    """copy.deepcopy / pickle skip __init__ (round-4 advisor finding): the copy carries no native handle, no cached parameter list of the original,
-    and is watched by the optimizer post-step hook — a fused optimizer's step over ITS parameters invalidates ITS hand-over."""
+def _check_copies_and_pickles(m, also=lambda clone: None):
+    """Every copy.deepcopy / pickle round trip of ``m``: watched by the optimizer post-step hook, no native handle, its own tensors, and a
+    step of an optimizer over ITS parameters invalidates ITS hand-over; ``also``: what else holds of each clone."""
     import copy
     import pickle
 
-    from articulatory_amd.models import GBlockGenerator, HiFiGANGenerator, HiFiGANMultiScaleMultiPeriodDiscriminator
     from articulatory_amd.utils import optim_hook
+
+    list(m.parameters())
+    for clone in (copy.deepcopy(m), pickle.loads(pickle.dumps(m))):
+        assert clone in optim_hook._watched
+        assert clone._handle is None and clone._lib is None
+        assert all(torch.equal(a, b) and a is not b for a, b in zip(m.state_dict().values(), clone.state_dict().values()))
+        if hasattr(clone, "_plist"):
+            assert all(p is q for p, q in zip(clone._plist(), clone.parameters()))  # its own tensors, not the original's
+        also(clone)
+        flag = []
+        clone.invalidate_parameters = lambda flag=flag: flag.append(1)
+        opt = torch.optim.SGD(list(clone.parameters())[:1], lr=0.1)
+        next(iter(clone.parameters())).grad = torch.zeros_like(next(iter(clone.parameters())))
+        opt.step()
+        assert flag == [1]
+
+
+def test_copies_and_pickles_of_native_modules_register_themselves_and_share_no_native_state():
+    """copy.deepcopy / pickle skip __init__ (round-4 advisor finding): the copy carries no native handle, no cached parameter list of the original,
+    and is watched by the optimizer post-step hook — a fused optimizer's step over ITS parameters invalidates ITS hand-over."""
+    from articulatory_amd.models import GBlockGenerator, HiFiGANGenerator, HiFiGANMultiScaleMultiPeriodDiscriminator
 
     g = HiFiGANGenerator(in_channels=13, channels=64, use_ar=False)
     gb = GBlockGenerator(in_channels=13, channels=64, g_scales=[5, 1, 4, 1, 1, 2, 1, 2, 1, 1], g_kernel_sizes=[3] * 10, use_ar=False)
     d = HiFiGANMultiScaleMultiPeriodDiscriminator()
     for m in (g, gb, d):
-        list(m.parameters())
-        for clone in (copy.deepcopy(m), pickle.loads(pickle.dumps(m))):
-            assert clone in optim_hook._watched
-            assert clone._handle is None and clone._lib is None
-            assert all(torch.equal(a, b) and a is not b for a, b in zip(m.state_dict().values(), clone.state_dict().values()))
-            if hasattr(clone, "_plist"):
-                assert all(p is q for p, q in zip(clone._plist(), clone.parameters()))  # its own tensors, not the original's
-            flag = []
-            clone.invalidate_parameters = lambda flag=flag: flag.append(1)
-            opt = torch.optim.SGD(list(clone.parameters())[:1], lr=0.1)
-            next(iter(clone.parameters())).grad = torch.zeros_like(next(iter(clone.parameters())))
-            opt.step()
-            assert flag == [1]
+        _check_copies_and_pickles(m)
+
+
+@pytest.mark.parametrize("which", ["BiGRU", "Transformer"])
+def test_copies_and_pickles_of_feature_models_carry_no_handle_state_and_no_forward_under_way(which):
+    """The same of the two feature models (NativeFeatureModel.__getstate__), copied in the middle of everything: with a handle, buffers, a
+    cached gradient layout and a training forward's transient fields set by hand, a clone comes back idle in all of them."""
+    import ctypes
+
+    from articulatory_amd import models
+
+    if which == "BiGRU":
+        m = models.BiGRU(in_channels=8, hidden_size=64, out_channels=12)
+        own = dict(_low=None)
+        m._low = (4, True)
+    else:
+        m = models.Transformer(in_channels=12, out_channels=8, elayers=1, hidden_dim=128)
+        own = dict(_packed=False, _last_stats=None)
+        m._packed, m._last_stats = True, torch.zeros(7, 2, 128)
+    lens = (torch.tensor([3, 2], dtype=torch.int32),) * 2
+    m._handle, m._lib = ctypes.c_void_p(1), object()  # (neither can be pickled: a clone that came back did not carry them)
+    m._sig, m._lens, m._on_device, m._dirty = ((0, 0),), lens, True, True
+    m._workspace_buf, m._train_ws_buf = torch.zeros(8, dtype=torch.uint8), torch.zeros(8, dtype=torch.uint8)
+    m.__dict__["_grad_info"] = (0, [("w", 0, 1)])
+
+    def idle(clone):
+        for k in ("_handle", "_lib", "_workspace_buf", "_train_ws_buf", "_sig", "_lens"):
+            assert getattr(clone, k) is None, k
+        for k, v in own.items():
+            assert getattr(clone, k) is v, k
+        assert clone._on_device is False and clone._dirty is False
+        assert "_grad_info" not in clone.__dict__
+        assert (clone._calls, clone._dropout_seed, clone._steps_seen) == (m._calls, m._dropout_seed, m._steps_seen)
+
+    _check_copies_and_pickles(m, idle)
+    assert m._lens is lens and m._on_device and "_grad_info" in m.__dict__  # the original keeps what it held
+    m._handle = None  # (made up: nothing to destroy)
