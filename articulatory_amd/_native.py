@@ -90,6 +90,12 @@ SYMBOLS = (
     "hificar_mel_loss",
     "hificar_stft_loss_forward",
     "hificar_stft_loss_backward",
+    "hificar_feat_create",
+    "hificar_feat_destroy",
+    "hificar_feat_engine",
+    "hificar_feat_frames",
+    "hificar_feat_workspace_bytes",
+    "hificar_feat_forward",
     "hificar_tape_bytes",
     "hificar_forward_train",
     "hificar_backward_workspace_bytes",
@@ -307,6 +313,27 @@ class HificarMelConfig(ctypes.Structure):
     ]
 
 
+FEAT_LOGMEL = 0
+FEAT_MFCC = 1
+FEAT_MAX_MELS = 128
+
+
+class HificarFeatConfig(ctypes.Structure):
+    """hificar_feat_config (include/hificar.h)."""
+
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("fft_size", ctypes.c_int32),
+        ("hop_size", ctypes.c_int32),
+        ("win_length", ctypes.c_int32),
+        ("num_mels", ctypes.c_int32),
+        ("n_mfcc", ctypes.c_int32),
+        ("amin", ctypes.c_float),
+        ("top_db", ctypes.c_float),
+        ("log_base", ctypes.c_int32),
+    ]
+
+
 class HificarDiscOutput(ctypes.Structure):
     _fields_ = [
         ("sub", ctypes.c_int32),
@@ -460,6 +487,18 @@ def load_library():
     lib.hificar_stft_loss_forward.restype = ci
     lib.hificar_stft_loss_backward.argtypes = [vp, ci, ci, vp, vp, vp, cs, vp]
     lib.hificar_stft_loss_backward.restype = ci
+    lib.hificar_feat_create.argtypes = [ctypes.POINTER(HificarFeatConfig), vp, ctypes.POINTER(vp)]
+    lib.hificar_feat_create.restype = ci
+    lib.hificar_feat_destroy.argtypes = [vp]
+    lib.hificar_feat_destroy.restype = None
+    lib.hificar_feat_engine.argtypes = [vp]
+    lib.hificar_feat_engine.restype = vp
+    lib.hificar_feat_frames.argtypes = [vp, ci]
+    lib.hificar_feat_frames.restype = ci
+    lib.hificar_feat_workspace_bytes.argtypes = [vp, ci, ci]
+    lib.hificar_feat_workspace_bytes.restype = cs
+    lib.hificar_feat_forward.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]
+    lib.hificar_feat_forward.restype = ci
     lib.hificar_tape_bytes.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     lib.hificar_tape_bytes.restype = ctypes.c_size_t
     lib.hificar_forward_train.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]

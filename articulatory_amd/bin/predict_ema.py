@@ -3,10 +3,11 @@
 
     python -m articulatory_amd.bin.predict_ema MODEL_DIR FEATS OUTDIR [--interp-factor N] [--zscore | --no-zscore] [--batch-size N]
                                                [--precision P] [--dry-run]
+    python -m articulatory_amd.bin.predict_ema MODEL_DIR WAVS OUTDIR --from-wav [--hop-length N] [...]
 
 ``MODEL_DIR`` holds ``best_mel_ckpt.pkl`` and ``config.yml`` (predict_ema.py:54-55; what ``InversionTrainer`` writes).  ``FEATS`` is a directory
 of ``<utt>.npy`` files, each (frames, channels) — the speech model's last hidden states, or the MFCC matrix transposed — or a kaldi-style scp
-file; the SSL / MFCC extraction itself is the caller's (s3prl and librosa are not dependencies of this package).  ``OUTDIR/<utt>.npy`` is
+file; the SSL extraction is the caller's (s3prl is not a dependency of this package; MFCCs: ``--from-wav`` below).  ``OUTDIR/<utt>.npy`` is
 (factor * frames, out_channels) float32, as ``np.save(pred)`` at predict_ema.py:102.
 
 The defaults follow the reference's own rules (predict_ema.py:37-47), read off the directory's name: ``_h2`` in it means SSL features, which
@@ -14,6 +15,12 @@ are interpolated and not z-scored — by 2 when the name starts with ``hprc``, e
 utterance and not interpolated.  ``--interp-factor`` / ``--zscore`` / ``--no-zscore`` override them.  Both steps run on the device inside
 ``model.forward_lowrate`` (no stretched or normalised copy of the features exists); ``--batch-size N`` runs ragged batches of N utterances,
 every one computed as if alone: any batch size writes the same files.
+
+``--from-wav`` is the reference's own command line for its MFCC models: ``WAVS`` is a directory of ``<utt>.wav`` files (or a ``utt path``
+scp file) of mono 16-bit PCM, read as ``int16 / 32768`` — what soundfile's float read gives —, and ``wav2mfcc`` (predict_ema.py:32-33) runs
+on the device (``articulatory_amd.features.MFCC``) in front of ``forward_lowrate``: hop 160 when the directory's name starts with ``hprc``,
+else 80 (predict_ema.py:42-47; ``--hop-length`` overrides), the filterbank of every file's own sampling rate, nothing resampled.  A
+directory with ``_h2`` in its name is refused: SSL extraction is not built.
 """
 
 import argparse
@@ -21,6 +28,7 @@ import glob
 import json
 import logging
 import os
+import wave
 
 import numpy as np
 import torch
@@ -58,14 +66,67 @@ def list_features(feats):
     return pairs
 
 
+def derive_hop_length(model_dir):
+    """``hop_length`` of ``wav2mfcc`` by the reference's rule for an experiment id (predict_ema.py:42-47)."""
+    return 160 if os.path.basename(os.path.normpath(model_dir)).startswith("hprc") else 80
+
+
+def list_wavs(wavs):
+    """(utt_id, path) pairs of a directory of ``<utt_id>.wav`` files or of a kaldi-style ``utt_id path`` wav.scp.  Nothing is loaded."""
+    if os.path.isdir(wavs):
+        return [(os.path.basename(path)[: -len(".wav")], path) for path in sorted(glob.glob(os.path.join(wavs, "*.wav")))]
+    pairs = []
+    with open(wavs) as f:
+        for line in f:
+            parts = line.strip().split()
+            if len(parts) >= 2:
+                pairs.append((parts[0], parts[1]))
+    return pairs
+
+
+def _open_wav(path):
+    try:
+        w = wave.open(path, "rb")
+    except (wave.Error, EOFError) as e:
+        raise ValueError(f"{path}: not a PCM wav file ({e})") from None
+    if w.getnchannels() != 1 or w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+        what = f"{w.getnchannels()} channel(s), {8 * w.getsampwidth()} bit, compression {w.getcomptype()}"
+        w.close()
+        raise ValueError(f"{path}: only mono PCM_16 wav files are read, this one has {what}")
+    return w
+
+
+def wav_info(path):
+    """(sampling rate, samples) from the header of a mono PCM_16 wav file; anything else is refused by name."""
+    with _open_wav(path) as w:
+        return w.getframerate(), w.getnframes()
+
+
+def read_wav(path):
+    """(float32 samples ``int16 / 32768`` — exactly what soundfile's float read gives —, sampling rate) of a mono PCM_16 wav file.  Another
+    format and a file shorter than its header says are refused by name."""
+    with _open_wav(path) as w:
+        n, sr = w.getnframes(), w.getframerate()
+        data = w.readframes(n)
+    if len(data) != 2 * n:
+        raise ValueError(f"{path}: truncated, the header promises {n} samples and the file holds {len(data) // 2}")
+    return np.frombuffer(data, dtype="<i2").astype(np.float32) / np.float32(32768.0), sr
+
+
 def get_parser():
     parser = argparse.ArgumentParser(description="Predict EMA from dumped speech features with a trained inversion model.")
     parser.add_argument("model_dir", type=str, help=f"directory holding {CHECKPOINT} and config.yml")
-    parser.add_argument("feats", type=str, help="directory of <utt>.npy files, each (frames, channels), or a kaldi-style scp file")
+    parser.add_argument("feats", type=str, help="directory of <utt>.npy files, each (frames, channels), or a kaldi-style scp file; with "
+                                                "--from-wav: directory of <utt>.wav files (mono PCM_16) or a wav.scp")
     parser.add_argument("outdir", type=str, help="directory to save <utt>.npy, each (factor * frames, out_channels)")
     parser.add_argument("--interp-factor", type=int, default=None,
                         help="stretch every utterance by this integer factor (1 .. 16) with linear interpolation; default: by the "
                              "directory name, as the reference decides (4, or 2 for hprc*, with _h2 in the name; else 1)")
+    parser.add_argument("--from-wav", default=False, action="store_true",
+                        help="the second argument holds wav files: extract MFCCs on the device (wav2mfcc of the reference), for model "
+                             "directories without _h2 in their name")
+    parser.add_argument("--hop-length", type=int, default=None,
+                        help="hop of the MFCC extraction in samples (--from-wav); default: 160 when the directory name starts with hprc, else 80")
     z = parser.add_mutually_exclusive_group()
     z.add_argument("--zscore", dest="zscore", action="store_true", default=None,
                    help="normalise every utterance by the mean and standard deviation of all its elements (default without _h2 in the name)")
@@ -94,6 +155,36 @@ def predict_features(model, items, outdir, device, interp_factor=1, zscore=False
     return n
 
 
+def predict_wavs(model, pairs, outdir, device, hop_length=80, interp_factor=1, zscore=True, batch_size=1, rates=None):
+    """predict_ema.py:77-102 for its MFCC models: (utt_id, wav path) pairs -> ``outdir/<utt_id>.npy``.  One ``MFCC`` module per sampling
+    rate (the filterbank is the rate's own), utterances batched with others of their rate; per batch the padded waveforms go to the device
+    in one copy and stay there up to the prediction.  Every utterance is computed as if alone.  Returns the number of utterances."""
+    from articulatory_amd.features import MFCC
+
+    if rates is None:
+        rates = {path: wav_info(path)[0] for _, path in pairs}
+    n = 0
+    with torch.no_grad():
+        for sr in sorted(set(rates.values())):
+            mfcc = MFCC(sampling_rate=sr, hop_length=hop_length)
+            wavs = ((u, read_wav(p)[0]) for u, p in pairs if rates[p] == sr)
+            for batch in length_batches(wavs, max(1, batch_size)):
+                lens = [len(y) for _, y in batch]
+                for (u, _), l in zip(batch, lens):
+                    if l <= mfcc.fft_size // 2:
+                        raise ValueError(f"{u}: {l} samples, the MFCC's reflect padding needs more than {mfcc.fft_size // 2}")
+                padded = np.zeros((len(batch), max(lens)), dtype=np.float32)
+                for i, (_, y) in enumerate(batch):
+                    padded[i, :lens[i]] = y
+                feats, _ = mfcc(torch.from_numpy(padded).to(device), lens)
+                frames = [mfcc.frames(l) for l in lens]
+                yb = model.forward_lowrate(feats, lengths=frames, interp_factor=interp_factor, zscore=zscore)
+                for i, (utt_id, _) in enumerate(batch):
+                    np.save(os.path.join(outdir, f"{utt_id}.npy"), yb[i, :, :interp_factor * frames[i]].transpose(0, 1).cpu().numpy())
+                    n += 1
+    return n
+
+
 def main(argv=None):
     from articulatory_amd._native import check_interp_factor
     from articulatory_amd.utils import load_model
@@ -113,8 +204,28 @@ def main(argv=None):
     config.setdefault("format", "npy")
     if config.get("generator_params", {}).get("use_ar", False):
         raise NotImplementedError("predict_ema with use_ar: ar_loop's feature branches are not built")
-    pairs = list_features(args.feats)
+    if args.from_wav and "_h2" in os.path.basename(os.path.normpath(args.model_dir)):
+        raise NotImplementedError("predict_ema --from-wav for a model directory with _h2 in its name: SSL extraction is not built "
+                                  "(extract the speech model's hidden states and pass them as .npy files)")
+    if args.hop_length is not None and not args.from_wav:
+        raise ValueError("--hop-length belongs to --from-wav")
+    if args.hop_length is not None and args.hop_length < 1:
+        raise ValueError(f"--hop-length must be positive, got {args.hop_length}")
+    pairs = list_wavs(args.feats) if args.from_wav else list_features(args.feats)
     logging.info(f"The number of features to be decoded = {len(pairs)}.")
+    hop = rates = None
+    if args.from_wav:
+        hop = derive_hop_length(args.model_dir) if args.hop_length is None else args.hop_length
+        info = {p: wav_info(p) for _, p in pairs}
+        rates = {p: sr for p, (sr, _) in info.items()}
+    if args.dry_run and args.from_wav:
+        print(json.dumps({"model_dir": args.model_dir, "checkpoint": checkpoint, "generator_type": config.get("generator_type"),
+                          "interp_factor": factor, "zscore": bool(zscore), "batch_size": args.batch_size, "precision": args.precision or "f32",
+                          "front_end": "mfcc", "n_mfcc": 13, "n_mels": 40, "n_fft": 320, "hop_length": hop,
+                          "rates": sorted(set(rates.values())), "utterances": [u for u, _ in pairs],
+                          "samples": int(sum(info[p][1] for _, p in pairs)),
+                          "frames": int(sum(1 + info[p][1] // hop for _, p in pairs))}), flush=True)
+        return
     if args.dry_run:
         print(json.dumps({"model_dir": args.model_dir, "checkpoint": checkpoint, "generator_type": config.get("generator_type"),
                           "interp_factor": factor, "zscore": bool(zscore), "batch_size": args.batch_size, "precision": args.precision or "f32",
@@ -136,8 +247,12 @@ def main(argv=None):
         elif args.precision != "f32":
             raise NotImplementedError(f"--precision {args.precision}: {type(model).__name__} runs in the exact-fp32 arithmetic only")
     model = model.eval().to(device)
-    n = predict_features(model, ((u, _load(p)) for u, p in pairs), args.outdir, device, interp_factor=factor, zscore=zscore,
-                         batch_size=args.batch_size)
+    if args.from_wav:
+        n = predict_wavs(model, pairs, args.outdir, device, hop_length=hop, interp_factor=factor, zscore=zscore, batch_size=args.batch_size,
+                         rates=rates)
+    else:
+        n = predict_features(model, ((u, _load(p)) for u, p in pairs), args.outdir, device, interp_factor=factor, zscore=zscore,
+                             batch_size=args.batch_size)
     logging.info(f"Finished prediction of {n} utterances.")
 
 

@@ -10,6 +10,7 @@
 #include "hificar_bigru_train_kernels.hip.h"
 #include "hificar_xfmr_kernels.hip.h"
 #include "hificar_frontend_kernels.hip.h"
+#include "hificar_feat_kernels.hip.h"
 #include "hificar_xfmr_attn16.hip.h"
 #include "hificar_xfmr_train_kernels.hip.h"
 #include "hificar_xfmr_attn16_train.hip.h"
@@ -2617,6 +2618,7 @@ extern "C" int hificar_pcm16(const float* x, int16_t* y, size_t n, void* stream)
 #include "hificar_gblock.hip.inc"
 #include "hificar_disc.hip.inc"
 #include "hificar_mel.hip.inc"
+#include "hificar_feat.hip.inc"
 
 // ------------------------------------------------------------------------------------------------
 // What the training states of the two feature models (BiGRU, Transformer) share: the table of their device-resident parameters — every

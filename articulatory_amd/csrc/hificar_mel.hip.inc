@@ -47,6 +47,25 @@ static int mel_make_layer(hificar_engine* h, ConvLayer& L, const char* name, int
     return launch_pack(pp, nullptr);
 }
 
+// windowed DFT matrix (2 nfp, N): rows [0, nf) = w[n] cos(2 pi f n / N), rows [nfp, nfp + nf) = -w[n] sin(...); torch.hann_window is
+// periodic, a shorter window sits centred in the frame (torch.stft, librosa.stft)
+static std::vector<float> mel_dft_matrix(int N, int win_length, int nfp) {
+    const int nf = N / 2 + 1;
+    std::vector<float> dft((size_t)2 * nfp * N, 0.f);
+    const int w0 = (N - win_length) / 2;
+    const double pi = 3.14159265358979323846;
+    for (int n = 0; n < N; ++n) {
+        const int wn = n - w0;
+        const double w = (wn >= 0 && wn < win_length) ? 0.5 - 0.5 * cos(2.0 * pi * wn / win_length) : 0.0;
+        for (int f = 0; f < nf; ++f) {
+            const double ang = 2.0 * pi * (double)(((long long)f * n) % N) / N;
+            dft[(size_t)f * N + n] = (float)(w * cos(ang));
+            dft[(size_t)(nfp + f) * N + n] = (float)(-w * sin(ang));
+        }
+    }
+    return dft;
+}
+
 extern "C" int hificar_mel_create(const hificar_mel_config* cfg, const float* melmat, hificar_mel** out) {
     if (!cfg || !out || (!melmat && cfg->mode == 0)) return fail(HIFICAR_E_INVALID, "hificar_mel_create: null argument");
     const hificar_mel_config& c = *cfg;
@@ -71,20 +90,7 @@ extern "C" int hificar_mel_create(const hificar_mel_config* cfg, const float* me
     m->nf = nf;
     m->nfp = nfp;
     m->mp = mp;
-    // windowed DFT matrix (2 nfp, N): rows [0, nf) = w[n] cos(2 pi f n / N), rows [nfp, nfp + nf) = -w[n] sin(...); torch.hann_window is
-    // periodic, a shorter window sits centred in the frame (torch.stft)
-    std::vector<float> dft((size_t)2 * nfp * N, 0.f);
-    const int w0 = (N - c.win_length) / 2;
-    const double pi = 3.14159265358979323846;
-    for (int n = 0; n < N; ++n) {
-        const int wn = n - w0;
-        const double w = (wn >= 0 && wn < c.win_length) ? 0.5 - 0.5 * cos(2.0 * pi * wn / c.win_length) : 0.0;
-        for (int f = 0; f < nf; ++f) {
-            const double ang = 2.0 * pi * (double)(((long long)f * n) % N) / N;
-            dft[(size_t)f * N + n] = (float)(w * cos(ang));
-            dft[(size_t)(nfp + f) * N + n] = (float)(-w * sin(ang));
-        }
-    }
+    const std::vector<float> dft = mel_dft_matrix(N, c.win_length, nfp);
     if ((rc = mel_make_layer(h, m->Fdft, "mel#dft", N, N, 2 * nfp, dft, false, N, 2 * nfp)) != HIFICAR_OK) return bail(rc);
     if ((rc = mel_make_layer(h, m->Ddft, "mel#dft^T", 2 * nfp, 2 * nfp, N, dft, true, N, 2 * nfp)) != HIFICAR_OK) return bail(rc);
     if (c.mode == 0) {

@@ -88,7 +88,7 @@ extern "C" {
 
 typedef struct hificar_handle hificar_handle;
 /* The conv engine every model of the library launches through (plans, schedules, stream ordering, profiling).  A generator handle
- * has one (hificar_engine_of), so do the discriminators (hificar_disc_engine), the BiGRU (hificar_bigru_engine) and the Transformer (hificar_xfmr_engine); it lives and
+ * has one (hificar_engine_of), so do the discriminators (hificar_disc_engine), the BiGRU (hificar_bigru_engine), the Transformer (hificar_xfmr_engine) and the speech features (hificar_feat_engine); it lives and
  * dies with its model.  Only the profiling calls take it: the generator's entry points do not accept another model's engine. */
 typedef struct hificar_engine hificar_engine;
 
@@ -525,6 +525,45 @@ int hificar_stft_loss_backward(hificar_mel* m, int B, int T, const float* gweigh
                                void* stream);
 int hificar_mel_loss(hificar_mel* m, const float* y_hat, const float* y, int B, int T, float* value, float* dy_hat, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* Speech features of a ragged batch of waveforms, on the device (forward only; exact fp32).
+ *   HIFICAR_FEAT_MFCC    librosa 0.8.1's feature.mfcc as egs/ema/voc1/local/predict_ema.py:32-33 calls it: P = |STFT|^2, mel = fb P,
+ *                        dB = 10 log10(max(amin, mel)), dB = max(dB, max over the utterance's own frames and bands - top_db) (top_db < 0: no
+ *                        clamp), orthonormal DCT-II over the bands, the first n_mfcc coefficients.  No z-score: hificar_*_forward_lowrate's.
+ *   HIFICAR_FEAT_LOGMEL  articulatory/bin/preprocess.py:58-82: log_b(max(amin, fb |STFT|)), log_base 0 (natural), 2 or 10; amin is its eps.
+ * STFT: center = True with reflect padding of fft_size / 2 at the utterance's own two ends, periodic Hann of win_length centred in the frame,
+ * 1 + L / hop_size frames for L samples.  melmat: (num_mels, fft_size / 2 + 1) filterbank, host memory (librosa.filters.mel in the
+ * reference).  hificar_feat_create touches no device (it checks the configuration and builds host tables); the first hificar_feat_forward
+ * whose arguments pass every check sets the device state up.
+ *
+ * hificar_feat_forward: wav (B, Lmax) device floats; lengths: device int32[B] sample counts, or NULL (every utterance has Lmax); lengths_host:
+ * the same numbers in host memory, or NULL — given, every entry is checked (fft_size / 2 < l <= Lmax) before anything is enqueued; not
+ * given, the kernels clamp a length into 0 .. Lmax and give an utterance of fft_size / 2 samples or fewer no frames.  out: (B, C, Tmax), C =
+ * n_mfcc | num_mels, Tmax = hificar_feat_frames(h, Lmax), exactly zero from an utterance's own frame count on; frames_out: device int32[B]
+ * (those counts) or NULL.  Samples at or past a length are never read, and an utterance's result is bit for bit that of running it alone
+ * (split-K off, fixed-order reductions, no atomics).  workspace: 256-byte aligned, hificar_feat_workspace_bytes(h, B, Lmax) bytes (0: the
+ * shape is refused).  Lmax <= fft_size / 2: HIFICAR_E_INVALID. */
+#define HIFICAR_FEAT_LOGMEL 0
+#define HIFICAR_FEAT_MFCC 1
+#define HIFICAR_FEAT_MAX_MELS 128
+typedef struct hificar_feat_config {
+    int kind;       /* HIFICAR_FEAT_LOGMEL | HIFICAR_FEAT_MFCC */
+    int fft_size;   /* a multiple of 32, 32 .. 8192 */
+    int hop_size, win_length;
+    int num_mels;   /* 1 .. HIFICAR_FEAT_MAX_MELS */
+    int n_mfcc;     /* MFCC: 1 .. num_mels */
+    float amin;     /* MFCC: power_to_db's amin (1e-10); log-mel: eps */
+    float top_db;   /* MFCC: power_to_db's top_db (80); negative: none */
+    int log_base;   /* log-mel: 0 natural, 2 or 10 */
+} hificar_feat_config;
+typedef struct hificar_feat hificar_feat;
+int hificar_feat_create(const hificar_feat_config* cfg, const float* melmat, hificar_feat** out);
+void hificar_feat_destroy(hificar_feat* h);
+hificar_engine* hificar_feat_engine(hificar_feat* h);     /* for hificar_profile_begin / hificar_profile_end */
+int hificar_feat_frames(const hificar_feat* h, int L);   /* 1 + L / hop_size; 0 for L <= fft_size / 2 */
+size_t hificar_feat_workspace_bytes(const hificar_feat* h, int B, int Lmax);
+int hificar_feat_forward(hificar_feat* h, const float* wav, const int32_t* lengths, const int32_t* lengths_host, float* out, int32_t* frames_out,
+                         int B, int Lmax, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Articulatory inversion: the BiGRU speech-to-EMA model (articulatory/models/pytorch_models.py:22-123) in eval mode — two bidirectional
