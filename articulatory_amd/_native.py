@@ -1,4 +1,9 @@
-"""ctypes binding of libhificar.so (C ABI: include/hificar.h).
+"""ctypes binding of libhificar.so, derived at import from its C ABI, include/hificar.h.
+
+The header is the one place where an entry point, a struct or a constant is written down.  parse_header() reads its ``#define``s, its
+``typedef struct``s and its prototypes; the constants (``HIFICAR_X`` -> ``X``), the ctypes.Structure classes (``hificar_x_config`` ->
+``HificarXConfig``), SYMBOLS and every argtypes / restype of load_library() come from what it returns.  What the parser has no rule for it
+refuses with the header line (HeaderError): it never guesses a type.
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, a
 RuntimeError is raised.  The CPU oracle under ``oracle/`` is test infrastructure and is never
@@ -7,22 +12,165 @@ imported from here.
 
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HIFICAR_LIB: developer override (A/B runs of two builds of the same ABI inside one gpurun call)
 LIB_PATH = os.environ.get("HIFICAR_LIB") or os.path.join(_HERE, "libhificar.so")
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "hificar.h"))  # in-tree only: there is no packaged copy
 
-MAX_STAGES = 8
-MAX_BLOCKS = 4
-MAX_DILATIONS = 4
+# hificar_bucket_fn (include/hificar.h): void (*)(int bucket, void* stream, void* user)
+BUCKET_FN = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 
-PREC_F32 = 0
-PREC_BF16X3 = 1
-PREC_BF16X3W = 2
-PREC_BF16X3A = 3
-PREC_BF16X3WA = 4
-PREC_BF16X3WAC = 6
-PREC_BF16X3WACK = 8
+
+class HeaderError(RuntimeError):
+    """The header holds a declaration the binding has no rule for."""
+
+
+# by value, as a struct field, or (the first row of the pointer rules) behind a typed pointer
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "double": ctypes.c_double, "char": ctypes.c_char}
+_TYPED_POINTEES = ("int", "int64_t", "size_t")  # small host arrays and results (shapes, counts, offsets): POINTER(T), ctypes checks the argument
+_VOID_POINTEES = ("void", "float", "int32_t", "int16_t", "uint16_t")  # tensors, device or host: c_void_p, callers pass data_ptr() integers
+_CLASS_NAMES = {"hificar_gblock_config": "HificarGBlockConfig"}  # where CamelCase of the C name is not the class's name
+
+
+def parse_header(text, path="hificar.h", callbacks=None):
+    """Plain-C99 header text -> (constants, structs, prototypes), each in the header's order:
+
+    constants   macro name -> int, for every ``#define NAME <decimal integer>`` (parentheses allowed)
+    structs     C name -> ctypes.Structure subclass, for every ``typedef struct name { ... } name;``
+    prototypes  function name -> (restype, [argtypes])
+
+    callbacks: function-pointer typedef name -> its CFUNCTYPE (default: hificar_bucket_fn).  Anything else — a type, a declarator, an array
+    extent, a preprocessor line or a statement outside these shapes — raises HeaderError naming the line."""
+    callbacks = {"hificar_bucket_fn": BUCKET_FN} if callbacks is None else callbacks
+
+    def blank(m):  # keeps the line numbers
+        return " " + "\n" * m.group().count("\n")
+
+    def fail(pos, why):
+        line = text.count("\n", 0, pos) + 1
+        raise HeaderError(f"{path}:{line}: {why}")
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", blank, text, flags=re.S)
+    text = re.sub(r"^#ifdef __cplusplus$.*?^#endif$", blank, text, flags=re.S | re.M)  # extern "C" { and its }
+
+    constants = {}
+    for m in re.finditer(r"^[ \t]*#[^\n]*$", text, flags=re.M):
+        d = re.fullmatch(r"\s*#\s*define\s+(\w+)\s+\(?\s*(-?\d+)\s*\)?\s*", m.group())
+        if d:
+            constants[d.group(1)] = int(d.group(2))
+        elif not re.fullmatch(r"\s*#\s*(ifndef\s+\w+|define\s+\w+|include\s*<\w+\.h>|endif)\s*", m.group()):
+            fail(m.start(), f"preprocessor line outside '#define NAME <integer>': {m.group().strip()!r}")
+    text = re.sub(r"^[ \t]*#[^\n]*$", blank, text, flags=re.M)
+
+    structs, opaque, prototypes = {}, set(), {}
+
+    def ctype(decl, pos, what, ret=False):
+        """'const float* const*' and the like -> its ctypes type; a type outside these rules is refused."""
+        m = re.fullmatch(r"(?:const )?(\w+) ?((?:\* ?(?:const ?)?)*)", decl.strip())
+        base, stars = (m.group(1), m.group(2).count("*")) if m else (None, 0)
+        if stars == 0:
+            if base == "void" and ret:
+                return None
+            if base in _SCALARS:
+                return _SCALARS[base]
+            if base in callbacks:
+                return callbacks[base]
+        elif stars == 1:
+            if base == "char":
+                return ctypes.c_char_p
+            if base in structs:
+                return ctypes.POINTER(structs[base])
+            if base in _TYPED_POINTEES:
+                return ctypes.POINTER(_SCALARS[base])
+            if base in _VOID_POINTEES or base in opaque:
+                return ctypes.c_void_p
+        elif stars == 2:
+            if base == "char":
+                return ctypes.POINTER(ctypes.c_char_p)
+            if base in _VOID_POINTEES or base in opaque:
+                return ctypes.POINTER(ctypes.c_void_p)
+        fail(pos, f"no rule for the type {decl.strip()!r} of {what}")
+
+    def struct_fields(name, body, pos):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            m = re.fullmatch(r"(\w+) (.+)", decl)
+            if not m or m.group(1) not in _SCALARS:
+                fail(pos, f"struct {name}: no rule for the field declaration {decl!r}")
+            for declarator in m.group(2).split(","):
+                f = re.fullmatch(r"(\w+)((?:\[\w+\])*)", declarator.strip())  # a pointer, a bit-field, an expression as extent: refused
+                if not f:
+                    fail(pos, f"struct {name}: no rule for the declarator {declarator.strip()!r} in {decl!r}")
+                t = _SCALARS[m.group(1)]
+                for extent in reversed(re.findall(r"\[(\w+)\]", f.group(2))):
+                    if not extent.isdigit() and extent not in constants:
+                        fail(pos, f"struct {name}: array extent {extent!r} of {f.group(1)!r} is no integer and no macro defined above it")
+                    t = t * (int(extent) if extent.isdigit() else constants[extent])
+                fields.append((f.group(1), t))
+        return fields
+
+    def parameters(name, params, pos):
+        argtypes = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            a = re.fullmatch(r"(.+?[ *])(\w+)", p.strip())
+            if not a or a.group(2) in _SCALARS or a.group(2) in ("void", "const"):
+                fail(pos, f"{name}: parameter {p.strip()!r} has no name (or is no plain 'type name')")
+            argtypes.append(ctype(a.group(1), pos, f"{name}'s parameter {a.group(2)!r}"))
+        return argtypes
+
+    end = 0
+    for m in re.finditer(r"\s*([^;{}]*(?:\{[^{}]*\}[^;{}]*)*);", text):  # one statement: up to the first ';' outside braces
+        if m.start() != end:
+            fail(end, "unbalanced braces")
+        end, pos = m.end(), m.start(1)
+        s = " ".join(m.group(1).split())
+        fwd = re.fullmatch(r"typedef struct (\w+) (\w+)", s)
+        full = re.fullmatch(r"typedef struct (\w+) ?\{(.*)\} ?(\w+)", s)
+        fnptr = re.fullmatch(r"typedef void ?\( ?\* ?(\w+) ?\) ?\(([^()]*)\)", s)
+        proto = re.fullmatch(r"(.+?[ *])(\w+) ?\(([^()]*)\)", s)
+        if fwd and fwd.group(1) == fwd.group(2):
+            opaque.add(fwd.group(1))
+        elif full and full.group(1) == full.group(3) and full.group(1) not in structs:
+            name = full.group(1)
+            cls_name = _CLASS_NAMES.get(name) or "".join(p.capitalize() for p in name.split("_"))
+            structs[name] = type(cls_name, (ctypes.Structure,), {"_fields_": struct_fields(name, full.group(2), pos),
+                                                                 "__doc__": f"{name} ({os.path.basename(path)})."})
+        elif fnptr:
+            fn = callbacks.get(fnptr.group(1))
+            if fn is None or fn._restype_ is not None or list(fn._argtypes_) != parameters(fnptr.group(1), fnptr.group(2), pos):
+                fail(pos, f"function-pointer typedef {fnptr.group(1)!r} has no CFUNCTYPE of these parameters in the binding")
+        elif proto and not s.startswith("typedef") and proto.group(2) not in prototypes:
+            name = proto.group(2)
+            prototypes[name] = (ctype(proto.group(1), pos, f"{name}'s return value", ret=True), parameters(name, proto.group(3), pos))
+        else:
+            fail(pos, f"no rule for the declaration {s[:100]!r}")
+    if text[end:].strip():
+        fail(end, f"text outside any declaration: {text[end:].strip()[:60]!r}")
+    return constants, structs, prototypes
+
+
+def _parse_own_header():
+    try:
+        with open(HEADER_PATH, encoding="utf-8") as f:
+            text = f.read()
+    except OSError as e:
+        raise RuntimeError(f"{HEADER_PATH} not found ({e.strerror}): the binding is derived from the C ABI header, which is looked for at "
+                           "../include/hificar.h from the articulatory_amd package (run from the repository tree)") from e
+    return parse_header(text, HEADER_PATH)
+
+
+_CONSTANTS, STRUCTS, PROTOTYPES = _parse_own_header()
+# HIFICAR_PREC_F32 -> PREC_F32, HIFICAR_MAX_STAGES -> MAX_STAGES, HIFICAR_E_INVALID -> E_INVALID, ...: every integer macro of the header
+CONSTANTS = {k[len("HIFICAR_"):]: v for k, v in _CONSTANTS.items() if k.startswith("HIFICAR_")}
+globals().update(CONSTANTS)
+# hificar_config -> HificarConfig, hificar_kernel_stat -> HificarKernelStat, ...: every struct of the header
+globals().update({cls.__name__: cls for cls in STRUCTS.values()})
+# every function the header declares, known without loading the library (tests/test_cabi.py checks the .so exports each one)
+SYMBOLS = tuple(PROTOTYPES)
+
 PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}  # the inference arithmetics (``precision=``)
 # ... and the Transformer's training arithmetics (``train_precision=``): bf16x3w = bf16x3 with the one-tap weight gradients in it too
 TRAIN_PRECISIONS = dict(PRECISIONS, bf16x3w=PREC_BF16X3W)
@@ -36,338 +184,11 @@ XFMR_TRAIN_PRECISIONS_ALL = dict(XFMR_TRAIN_PRECISIONS, bf16x3wac=PREC_BF16X3WAC
 # ``train_precision=`` accepts (the three mappings above stay as they are: they are what their arithmetics' tests pin)
 XFMR_TRAIN_PRECISIONS_K = dict(XFMR_TRAIN_PRECISIONS_ALL, bf16x3wack=PREC_BF16X3WACK)
 
-# every symbol include/hificar.h declares (tests/test_cabi.py checks the .so exports each one)
-SYMBOLS = (
-    "hificar_create",
-    "hificar_gblock_create",
-    "hificar_set_weight",
-    "hificar_finalize",
-    "hificar_set_precision",
-    "hificar_workspace_bytes",
-    "hificar_forward",
-    "hificar_ar_loop",
-    "hificar_forward_ragged",
-    "hificar_forward_cond",
-    "hificar_ar_loop_ragged",
-    "hificar_ar_loop_packed",
-    "hificar_ar_step",
-    "hificar_ar_loop_cond",
-    "hificar_ar_loop_packed_cond",
-    "hificar_ar_step_cond",
-    "hificar_macs",
-    "hificar_pcm16",
-    "hificar_engine_of",
-    "hificar_profile_begin",
-    "hificar_profile_end",
-    "hificar_debug_tap",
-    "hificar_debug_force_tile",
-    "hificar_set_weight_device",
-    "hificar_set_parameters_device",
-    "hificar_raw_grad_floats",
-    "hificar_weight_norm_backward",
-    "hificar_disc_create",
-    "hificar_disc_destroy",
-    "hificar_disc_engine",
-    "hificar_disc_param_count",
-    "hificar_disc_param_info",
-    "hificar_disc_grad_floats",
-    "hificar_disc_raw_grad_floats",
-    "hificar_disc_set_parameters_device",
-    "hificar_disc_weight_norm_backward",
-    "hificar_disc_tape_bytes",
-    "hificar_disc_macs",
-    "hificar_disc_backward_workspace_bytes",
-    "hificar_disc_output_count",
-    "hificar_disc_output_info",
-    "hificar_disc_forward",
-    "hificar_disc_backward",
-    "hificar_disc_dout_floats",
-    "hificar_disc_loss",
-    "hificar_disc_backward_flat",
-    "hificar_mel_create",
-    "hificar_mel_destroy",
-    "hificar_mel_workspace_bytes",
-    "hificar_mel_loss",
-    "hificar_stft_loss_forward",
-    "hificar_stft_loss_backward",
-    "hificar_feat_create",
-    "hificar_feat_destroy",
-    "hificar_feat_engine",
-    "hificar_feat_frames",
-    "hificar_feat_workspace_bytes",
-    "hificar_feat_forward",
-    "hificar_tape_bytes",
-    "hificar_forward_train",
-    "hificar_backward_workspace_bytes",
-    "hificar_grad_count",
-    "hificar_grad_info",
-    "hificar_grad_floats",
-    "hificar_backward",
-    "hificar_forward_train_cond",
-    "hificar_backward_cond",
-    "hificar_grad_bucket_count",
-    "hificar_raw_param_bucket",
-    "hificar_set_bucket_callback",
-    "hificar_weight_norm_backward_bucket",
-    "hificar_disc_grad_bucket_count",
-    "hificar_disc_raw_param_bucket",
-    "hificar_disc_bucket_folded_range",
-    "hificar_disc_set_bucket_callback",
-    "hificar_disc_weight_norm_backward_bucket",
-    "hificar_disc_set_grad_accumulate",
-    "hificar_disc_set_grad_scale",
-    "hificar_bigru_create",
-    "hificar_bigru_set_weight",
-    "hificar_bigru_finalize",
-    "hificar_bigru_workspace_bytes",
-    "hificar_bigru_forward",
-    "hificar_bigru_workspace_bytes_lowrate",
-    "hificar_bigru_forward_lowrate",
-    "hificar_bigru_engine",
-    "hificar_bigru_destroy",
-    "hificar_bigru_set_parameters_device",
-    "hificar_bigru_grad_count",
-    "hificar_bigru_grad_info",
-    "hificar_bigru_grad_floats",
-    "hificar_bigru_tape_bytes",
-    "hificar_bigru_train_workspace_bytes",
-    "hificar_bigru_forward_train",
-    "hificar_bigru_forward_train_ragged",
-    "hificar_bigru_backward",
-    "hificar_bigru_tape_bytes_lowrate",
-    "hificar_bigru_train_workspace_bytes_lowrate",
-    "hificar_bigru_forward_train_lowrate",
-    "hificar_bigru_backward_lowrate",
-    "hificar_xfmr_create",
-    "hificar_xfmr_set_weight",
-    "hificar_xfmr_set_precision",
-    "hificar_xfmr_finalize",
-    "hificar_xfmr_workspace_bytes",
-    "hificar_xfmr_forward",
-    "hificar_xfmr_workspace_bytes_lowrate",
-    "hificar_xfmr_forward_lowrate",
-    "hificar_xfmr_debug_tap",
-    "hificar_xfmr_engine",
-    "hificar_xfmr_destroy",
-    "hificar_xfmr_set_train_precision",
-    "hificar_debug_pack16",
-    "hificar_debug_split_rows_t",
-    "hificar_debug_split_taps_t",
-    "hificar_xfmr_set_parameters_device",
-    "hificar_xfmr_grad_count",
-    "hificar_xfmr_grad_info",
-    "hificar_xfmr_grad_floats",
-    "hificar_xfmr_tape_bytes",
-    "hificar_xfmr_train_workspace_bytes",
-    "hificar_xfmr_forward_train",
-    "hificar_xfmr_forward_train_ragged",
-    "hificar_xfmr_backward",
-    "hificar_xfmr_packed_rows",
-    "hificar_xfmr_tape_bytes_packed",
-    "hificar_xfmr_train_workspace_bytes_packed",
-    "hificar_xfmr_forward_train_packed",
-    "hificar_xfmr_backward_packed",
-    "hificar_destroy",
-    "hificar_last_error",
-    "hificar_version",
-)
-
-
-class HificarConfig(ctypes.Structure):
-    _fields_ = [
-        ("in_channels", ctypes.c_int32),
-        ("out_channels", ctypes.c_int32),
-        ("channels", ctypes.c_int32),
-        ("kernel_size", ctypes.c_int32),
-        ("n_stages", ctypes.c_int32),
-        ("upsample_scales", ctypes.c_int32 * MAX_STAGES),
-        ("upsample_kernel_sizes", ctypes.c_int32 * MAX_STAGES),
-        ("n_blocks", ctypes.c_int32),
-        ("resblock_kernel_sizes", ctypes.c_int32 * MAX_BLOCKS),
-        ("n_dilations", ctypes.c_int32 * MAX_BLOCKS),
-        ("resblock_dilations", (ctypes.c_int32 * MAX_DILATIONS) * MAX_BLOCKS),
-        ("use_additional_convs", ctypes.c_int32),
-        ("bias", ctypes.c_int32),
-        ("lrelu_slope", ctypes.c_float),
-        ("use_tanh", ctypes.c_int32),
-        ("use_ar", ctypes.c_int32),
-        ("ar_input", ctypes.c_int32),
-        ("ar_hidden", ctypes.c_int32),
-        ("ar_output", ctypes.c_int32),
-        ("precision", ctypes.c_int32),
-        ("use_spk_id", ctypes.c_int32),
-        ("num_spk", ctypes.c_int32),
-        ("spk_emb_size", ctypes.c_int32),
-        ("use_ph", ctypes.c_int32),
-        ("num_ph", ctypes.c_int32),
-        ("ph_emb_size", ctypes.c_int32),
-        ("use_ph_loss", ctypes.c_int32),
-    ]
-
-
-MAX_GBLOCKS = 10
-
-
-class HificarGBlockConfig(ctypes.Structure):
-    """hificar_gblock_config (include/hificar.h): the keyword arguments of the reference's GBlockGenerator.__init__ (gblock_gen.py:17-31)."""
-
-    _fields_ = [
-        ("in_channels", ctypes.c_int32),
-        ("out_channels", ctypes.c_int32),
-        ("channels", ctypes.c_int32),
-        ("kernel_size", ctypes.c_int32),
-        ("n_blocks", ctypes.c_int32),
-        ("g_scales", ctypes.c_int32 * MAX_GBLOCKS),
-        ("g_kernel_sizes", ctypes.c_int32 * MAX_GBLOCKS),
-        ("use_tanh", ctypes.c_int32),
-        ("use_ar", ctypes.c_int32),
-        ("ar_input", ctypes.c_int32),
-        ("ar_hidden", ctypes.c_int32),
-        ("ar_output", ctypes.c_int32),
-        ("use_spk_id", ctypes.c_int32),
-        ("num_spk", ctypes.c_int32),
-        ("spk_emb_size", ctypes.c_int32),
-        ("precision", ctypes.c_int32),
-    ]
-
-
-class HificarBigruConfig(ctypes.Structure):
-    """hificar_bigru_config (include/hificar.h): the keyword arguments of the reference's BiGRU.__init__ (pytorch_models.py:23-25) that
-    affect eval-mode inference."""
-
-    _fields_ = [
-        ("in_channels", ctypes.c_int32),
-        ("hidden_size", ctypes.c_int32),
-        ("out_channels", ctypes.c_int32),
-        ("use_tanh", ctypes.c_int32),
-    ]
-
-
-class HificarXfmrConfig(ctypes.Structure):
-    """hificar_xfmr_config (include/hificar.h): the keyword arguments of the reference's Transformer.__init__ (transformer.py:22-24) that
-    shape eval-mode inference."""
-
-    _fields_ = [
-        ("in_channels", ctypes.c_int32),
-        ("out_channels", ctypes.c_int32),
-        ("elayers", ctypes.c_int32),
-        ("hidden_dim", ctypes.c_int32),
-    ]
-
-
-DISC_MAX_SUBS = 8
-DISC_MAX_LAYERS = 12
-_LAY = ctypes.c_int32 * DISC_MAX_LAYERS
-
-
-class HificarDiscConfig(ctypes.Structure):
-    """hificar_disc_config (include/hificar.h)."""
-
-    _fields_ = [
-        ("n_scales", ctypes.c_int32),
-        ("pool_kernel", ctypes.c_int32),
-        ("pool_stride", ctypes.c_int32),
-        ("pool_pad", ctypes.c_int32),
-        ("s_n_layers", ctypes.c_int32),
-        ("s_cin", _LAY),
-        ("s_cout", _LAY),
-        ("s_k", _LAY),
-        ("s_stride", _LAY),
-        ("s_pad", _LAY),
-        ("s_groups", _LAY),
-        ("s_bias", ctypes.c_int32),
-        ("s_slope", ctypes.c_float),
-        ("n_periods", ctypes.c_int32),
-        ("periods", ctypes.c_int32 * DISC_MAX_SUBS),
-        ("p_n_layers", ctypes.c_int32),
-        ("p_cin", _LAY),
-        ("p_cout", _LAY),
-        ("p_k", _LAY),
-        ("p_stride", _LAY),
-        ("p_pad", _LAY),
-        ("p_slope", ctypes.c_float),
-    ]
-
-
-class HificarGanLossConfig(ctypes.Structure):
-    _fields_ = [
-        ("loss_type", ctypes.c_int32),
-        ("average_by_discriminators", ctypes.c_int32),
-        ("fm_average_by_layers", ctypes.c_int32),
-        ("fm_average_by_discriminators", ctypes.c_int32),
-        ("fm_include_final_outputs", ctypes.c_int32),
-        ("lambda_adv", ctypes.c_float),
-        ("lambda_feat_match", ctypes.c_float),
-    ]
-
-
-class HificarMelConfig(ctypes.Structure):
-    _fields_ = [
-        ("fft_size", ctypes.c_int32),
-        ("hop_size", ctypes.c_int32),
-        ("win_length", ctypes.c_int32),
-        ("num_mels", ctypes.c_int32),
-        ("eps", ctypes.c_float),
-        ("log_base", ctypes.c_int32),
-        ("mode", ctypes.c_int32),
-    ]
-
-
-FEAT_LOGMEL = 0
-FEAT_MFCC = 1
-FEAT_MAX_MELS = 128
-
-
-class HificarFeatConfig(ctypes.Structure):
-    """hificar_feat_config (include/hificar.h)."""
-
-    _fields_ = [
-        ("kind", ctypes.c_int32),
-        ("fft_size", ctypes.c_int32),
-        ("hop_size", ctypes.c_int32),
-        ("win_length", ctypes.c_int32),
-        ("num_mels", ctypes.c_int32),
-        ("n_mfcc", ctypes.c_int32),
-        ("amin", ctypes.c_float),
-        ("top_db", ctypes.c_float),
-        ("log_base", ctypes.c_int32),
-    ]
-
-
-class HificarDiscOutput(ctypes.Structure):
-    _fields_ = [
-        ("sub", ctypes.c_int32),
-        ("layer", ctypes.c_int32),
-        ("group", ctypes.c_int32),
-        ("n_groups", ctypes.c_int32),
-        ("period", ctypes.c_int32),
-        ("offset_bytes", ctypes.c_int64),
-        ("nseq", ctypes.c_int32),
-        ("rows", ctypes.c_int32),
-        ("pitch", ctypes.c_int32),
-        ("channels", ctypes.c_int32),
-    ]
-
-
-# hificar_bucket_fn (include/hificar.h): void (*)(int bucket, void* stream, void* user)
-BUCKET_FN = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
-
-
-class HificarKernelStat(ctypes.Structure):
-    _fields_ = [
-        ("name", ctypes.c_char * 96),
-        ("launches", ctypes.c_int64),
-        ("total_ms", ctypes.c_double),
-        ("flops", ctypes.c_double),
-        ("bytes", ctypes.c_double),
-    ]
-
-
 _lib = None
 
 
 def load_library():
-    """Load libhificar.so (once) and declare the prototypes.  Raises RuntimeError if it is absent."""
+    """Load libhificar.so (once) and declare every prototype of the header.  Raises RuntimeError if it is absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -378,283 +199,23 @@ def load_library():
             "There is no CPU fallback for the generator forward pass."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    vp = ctypes.c_void_p
-    lib.hificar_create.argtypes = [ctypes.POINTER(HificarConfig), ctypes.POINTER(vp)]
-    lib.hificar_create.restype = ctypes.c_int
-    lib.hificar_gblock_create.argtypes = [ctypes.POINTER(HificarGBlockConfig), ctypes.POINTER(vp)]
-    lib.hificar_gblock_create.restype = ctypes.c_int
-    lib.hificar_set_weight.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
-    lib.hificar_set_weight.restype = ctypes.c_int
-    lib.hificar_finalize.argtypes = [vp]
-    lib.hificar_finalize.restype = ctypes.c_int
-    lib.hificar_set_precision.argtypes = [vp, ctypes.c_int]
-    lib.hificar_set_precision.restype = ctypes.c_int
-    lib.hificar_workspace_bytes.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-    lib.hificar_workspace_bytes.restype = ctypes.c_size_t
-    lib.hificar_forward.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.hificar_forward.restype = ctypes.c_int
-    lib.hificar_ar_loop.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.hificar_ar_loop.restype = ctypes.c_int
-    lib.hificar_forward_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.hificar_forward_ragged.restype = ctypes.c_int
-    lib.hificar_forward_cond.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.hificar_forward_cond.restype = ctypes.c_int
-    lib.hificar_ar_loop_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.hificar_ar_loop_ragged.restype = ctypes.c_int
-    lib.hificar_ar_loop_packed.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.hificar_ar_loop_packed.restype = ctypes.c_int
-    lib.hificar_ar_step.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp,
-                                    ctypes.c_size_t, vp]
-    lib.hificar_ar_step.restype = ctypes.c_int
-    lib.hificar_ar_loop_cond.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.hificar_ar_loop_cond.restype = ctypes.c_int
-    lib.hificar_ar_loop_packed_cond.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp,
-                                                ctypes.c_size_t, vp]
-    lib.hificar_ar_loop_packed_cond.restype = ctypes.c_int
-    lib.hificar_ar_step_cond.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int, vp,
-                                         ctypes.c_int, vp, vp, ctypes.c_size_t, vp]
-    lib.hificar_ar_step_cond.restype = ctypes.c_int
-    lib.hificar_macs.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-    lib.hificar_macs.restype = ctypes.c_double
-    lib.hificar_pcm16.argtypes = [vp, vp, ctypes.c_size_t, vp]
-    lib.hificar_pcm16.restype = ctypes.c_int
-    lib.hificar_engine_of.argtypes = [vp]
-    lib.hificar_engine_of.restype = vp
-    lib.hificar_profile_begin.argtypes = [vp]
-    lib.hificar_profile_begin.restype = ctypes.c_int
-    lib.hificar_profile_end.argtypes = [vp, ctypes.POINTER(HificarKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    lib.hificar_profile_end.restype = ctypes.c_int
-    lib.hificar_debug_tap.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_size_t]
-    lib.hificar_debug_tap.restype = ctypes.c_int
-    lib.hificar_debug_force_tile.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.hificar_debug_force_tile.restype = ctypes.c_int
-    lib.hificar_set_weight_device.argtypes = [vp, ctypes.c_char_p, vp, vp]
-    lib.hificar_set_weight_device.restype = ctypes.c_int
-    lib.hificar_set_parameters_device.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, vp]
-    lib.hificar_set_parameters_device.restype = ctypes.c_int
-    lib.hificar_raw_grad_floats.argtypes = [vp]
-    lib.hificar_raw_grad_floats.restype = ctypes.c_int64
-    lib.hificar_weight_norm_backward.argtypes = [vp, vp, vp, vp]
-    lib.hificar_weight_norm_backward.restype = ctypes.c_int
-    ci, cs, c64 = ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
-    lib.hificar_disc_create.argtypes = [ctypes.POINTER(HificarDiscConfig), ctypes.POINTER(vp)]
-    lib.hificar_disc_create.restype = ci
-    lib.hificar_disc_destroy.argtypes = [vp]
-    lib.hificar_disc_destroy.restype = None
-    lib.hificar_disc_engine.argtypes = [vp]
-    lib.hificar_disc_engine.restype = vp
-    lib.hificar_disc_param_count.argtypes = [vp]
-    lib.hificar_disc_param_count.restype = ci
-    lib.hificar_disc_param_info.argtypes = [vp, ci, ctypes.c_char_p, ctypes.POINTER(c64), ctypes.POINTER(ci), ctypes.POINTER(c64)]
-    lib.hificar_disc_param_info.restype = ci
-    lib.hificar_disc_grad_floats.argtypes = [vp]
-    lib.hificar_disc_grad_floats.restype = c64
-    lib.hificar_disc_raw_grad_floats.argtypes = [vp]
-    lib.hificar_disc_raw_grad_floats.restype = c64
-    lib.hificar_disc_set_parameters_device.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp), ci, vp]
-    lib.hificar_disc_set_parameters_device.restype = ci
-    lib.hificar_disc_weight_norm_backward.argtypes = [vp, vp, vp, vp]
-    lib.hificar_disc_weight_norm_backward.restype = ci
-    lib.hificar_disc_tape_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_disc_tape_bytes.restype = cs
-    lib.hificar_disc_macs.argtypes = [vp, ci, ci]
-    lib.hificar_disc_macs.restype = ctypes.c_double
-    lib.hificar_disc_backward_workspace_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_disc_backward_workspace_bytes.restype = cs
-    lib.hificar_disc_output_count.argtypes = [vp]
-    lib.hificar_disc_output_count.restype = ci
-    lib.hificar_disc_output_info.argtypes = [vp, ci, ci, ci, ctypes.POINTER(HificarDiscOutput)]
-    lib.hificar_disc_output_info.restype = ci
-    lib.hificar_disc_forward.argtypes = [vp, vp, ci, ci, vp, cs, vp]
-    lib.hificar_disc_forward.restype = ci
-    lib.hificar_disc_backward.argtypes = [vp, ctypes.POINTER(vp), ci, ci, vp, cs, vp, vp, vp, cs, vp]
-    lib.hificar_disc_backward.restype = ci
-    lib.hificar_disc_dout_floats.argtypes = [vp, ci, ci]
-    lib.hificar_disc_dout_floats.restype = cs
-    lib.hificar_disc_loss.argtypes = [vp, ctypes.POINTER(HificarGanLossConfig), ci, vp, vp, ci, ci, vp, vp, vp]
-    lib.hificar_disc_loss.restype = ci
-    lib.hificar_disc_backward_flat.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, cs, vp, vp, vp, cs, vp]
-    lib.hificar_disc_backward_flat.restype = ci
-    lib.hificar_mel_create.argtypes = [ctypes.POINTER(HificarMelConfig), vp, ctypes.POINTER(vp)]
-    lib.hificar_mel_create.restype = ci
-    lib.hificar_mel_destroy.argtypes = [vp]
-    lib.hificar_mel_destroy.restype = None
-    lib.hificar_mel_workspace_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_mel_workspace_bytes.restype = cs
-    lib.hificar_mel_loss.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, cs, vp]
-    lib.hificar_mel_loss.restype = ci
-    lib.hificar_stft_loss_forward.argtypes = [vp, vp, vp, ci, ci, vp, vp, cs, vp]
-    lib.hificar_stft_loss_forward.restype = ci
-    lib.hificar_stft_loss_backward.argtypes = [vp, ci, ci, vp, vp, vp, cs, vp]
-    lib.hificar_stft_loss_backward.restype = ci
-    lib.hificar_feat_create.argtypes = [ctypes.POINTER(HificarFeatConfig), vp, ctypes.POINTER(vp)]
-    lib.hificar_feat_create.restype = ci
-    lib.hificar_feat_destroy.argtypes = [vp]
-    lib.hificar_feat_destroy.restype = None
-    lib.hificar_feat_engine.argtypes = [vp]
-    lib.hificar_feat_engine.restype = vp
-    lib.hificar_feat_frames.argtypes = [vp, ci]
-    lib.hificar_feat_frames.restype = ci
-    lib.hificar_feat_workspace_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_feat_workspace_bytes.restype = cs
-    lib.hificar_feat_forward.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]
-    lib.hificar_feat_forward.restype = ci
-    lib.hificar_tape_bytes.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-    lib.hificar_tape_bytes.restype = ctypes.c_size_t
-    lib.hificar_forward_train.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
-    lib.hificar_forward_train.restype = ctypes.c_int
-    lib.hificar_backward_workspace_bytes.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-    lib.hificar_backward_workspace_bytes.restype = ctypes.c_size_t
-    lib.hificar_grad_count.argtypes = [vp]
-    lib.hificar_grad_count.restype = ctypes.c_int
-    lib.hificar_grad_info.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
-    lib.hificar_grad_info.restype = ctypes.c_int
-    lib.hificar_grad_floats.argtypes = [vp]
-    lib.hificar_grad_floats.restype = ctypes.c_int64
-    lib.hificar_backward.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.hificar_backward.restype = ctypes.c_int
-    lib.hificar_forward_train_cond.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
-    lib.hificar_forward_train_cond.restype = ctypes.c_int
-    lib.hificar_backward_cond.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.hificar_backward_cond.restype = ctypes.c_int
-    lib.hificar_grad_bucket_count.argtypes = [vp]
-    lib.hificar_grad_bucket_count.restype = ctypes.c_int
-    lib.hificar_raw_param_bucket.argtypes = [vp, ctypes.c_int]
-    lib.hificar_raw_param_bucket.restype = ctypes.c_int
-    lib.hificar_set_bucket_callback.argtypes = [vp, BUCKET_FN, vp]
-    lib.hificar_set_bucket_callback.restype = ctypes.c_int
-    lib.hificar_weight_norm_backward_bucket.argtypes = [vp, vp, vp, ctypes.c_int, vp]
-    lib.hificar_weight_norm_backward_bucket.restype = ctypes.c_int
-    lib.hificar_disc_grad_bucket_count.argtypes = [vp]
-    lib.hificar_disc_grad_bucket_count.restype = ctypes.c_int
-    lib.hificar_disc_raw_param_bucket.argtypes = [vp, ctypes.c_int]
-    lib.hificar_disc_raw_param_bucket.restype = ctypes.c_int
-    lib.hificar_disc_bucket_folded_range.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
-    lib.hificar_disc_bucket_folded_range.restype = ctypes.c_int
-    lib.hificar_disc_set_bucket_callback.argtypes = [vp, BUCKET_FN, vp]
-    lib.hificar_disc_set_bucket_callback.restype = ctypes.c_int
-    lib.hificar_disc_weight_norm_backward_bucket.argtypes = [vp, vp, vp, ctypes.c_int, vp]
-    lib.hificar_disc_weight_norm_backward_bucket.restype = ctypes.c_int
-    lib.hificar_disc_set_grad_accumulate.argtypes = [vp, ctypes.c_int]
-    lib.hificar_disc_set_grad_accumulate.restype = ctypes.c_int
-    lib.hificar_disc_set_grad_scale.argtypes = [vp, vp]
-    lib.hificar_disc_set_grad_scale.restype = ctypes.c_int
-    lib.hificar_bigru_create.argtypes = [ctypes.POINTER(HificarBigruConfig), ctypes.POINTER(vp)]
-    lib.hificar_bigru_create.restype = ci
-    lib.hificar_bigru_set_weight.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(c64), ci]
-    lib.hificar_bigru_set_weight.restype = ci
-    lib.hificar_bigru_finalize.argtypes = [vp]
-    lib.hificar_bigru_finalize.restype = ci
-    lib.hificar_bigru_workspace_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_bigru_workspace_bytes.restype = cs
-    lib.hificar_bigru_forward.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]
-    lib.hificar_bigru_forward.restype = ci
-    lib.hificar_bigru_workspace_bytes_lowrate.argtypes = [vp, ci, ci, ci]
-    lib.hificar_bigru_workspace_bytes_lowrate.restype = cs
-    lib.hificar_bigru_forward_lowrate.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, cs, vp]
-    lib.hificar_bigru_forward_lowrate.restype = ci
-    lib.hificar_bigru_engine.argtypes = [vp]
-    lib.hificar_bigru_engine.restype = vp
-    lib.hificar_bigru_destroy.argtypes = [vp]
-    lib.hificar_bigru_destroy.restype = None
-    lib.hificar_bigru_set_parameters_device.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp), ci, vp]
-    lib.hificar_bigru_set_parameters_device.restype = ci
-    lib.hificar_bigru_grad_count.argtypes = [vp]
-    lib.hificar_bigru_grad_count.restype = ci
-    lib.hificar_bigru_grad_info.argtypes = [vp, ci, ctypes.c_char_p, ctypes.POINTER(c64), ctypes.POINTER(c64)]
-    lib.hificar_bigru_grad_info.restype = ci
-    lib.hificar_bigru_grad_floats.argtypes = [vp]
-    lib.hificar_bigru_grad_floats.restype = c64
-    lib.hificar_bigru_tape_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_bigru_tape_bytes.restype = cs
-    lib.hificar_bigru_train_workspace_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_bigru_train_workspace_bytes.restype = cs
-    lib.hificar_bigru_forward_train.argtypes = [vp, vp, vp, vp, ci, ci, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp, cs, vp, cs, vp]
-    lib.hificar_bigru_forward_train.restype = ci
-    lib.hificar_bigru_forward_train_ragged.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp, cs, vp,
-                                                       cs, vp]
-    lib.hificar_bigru_forward_train_ragged.restype = ci
-    lib.hificar_bigru_backward.argtypes = [vp, vp, ci, ci, vp, cs, vp, vp, vp, cs, vp]
-    lib.hificar_bigru_backward.restype = ci
-    lib.hificar_bigru_tape_bytes_lowrate.argtypes = [vp, ci, ci, ci]
-    lib.hificar_bigru_tape_bytes_lowrate.restype = cs
-    lib.hificar_bigru_train_workspace_bytes_lowrate.argtypes = [vp, ci, ci, ci]
-    lib.hificar_bigru_train_workspace_bytes_lowrate.restype = cs
-    lib.hificar_bigru_forward_train_lowrate.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp, cs,
-                                                        vp, cs, vp]
-    lib.hificar_bigru_forward_train_lowrate.restype = ci
-    lib.hificar_bigru_backward_lowrate.argtypes = [vp, vp, ci, ci, ci, ci, vp, cs, vp, vp, vp, cs, vp]
-    lib.hificar_bigru_backward_lowrate.restype = ci
-    lib.hificar_xfmr_create.argtypes = [ctypes.POINTER(HificarXfmrConfig), ctypes.POINTER(vp)]
-    lib.hificar_xfmr_create.restype = ci
-    lib.hificar_xfmr_set_weight.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(c64), ci]
-    lib.hificar_xfmr_set_weight.restype = ci
-    lib.hificar_xfmr_set_precision.argtypes = [vp, ci]
-    lib.hificar_xfmr_set_precision.restype = ci
-    lib.hificar_xfmr_finalize.argtypes = [vp]
-    lib.hificar_xfmr_finalize.restype = ci
-    lib.hificar_xfmr_set_train_precision.argtypes = [vp, ci]
-    lib.hificar_xfmr_set_train_precision.restype = ci
-    lib.hificar_debug_pack16.argtypes = [ci, ci, ci, ci, ci, ci, vp, vp, cs, ctypes.POINTER(cs)]
-    lib.hificar_debug_pack16.restype = ci
-    lib.hificar_debug_split_rows_t.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, cs, ctypes.POINTER(cs)]
-    lib.hificar_debug_split_rows_t.restype = ci
-    lib.hificar_debug_split_taps_t.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, cs, ctypes.POINTER(cs)]
-    lib.hificar_debug_split_taps_t.restype = ci
-    lib.hificar_xfmr_workspace_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_xfmr_workspace_bytes.restype = cs
-    lib.hificar_xfmr_forward.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, cs, vp]
-    lib.hificar_xfmr_forward.restype = ci
-    lib.hificar_xfmr_workspace_bytes_lowrate.argtypes = [vp, ci, ci, ci]
-    lib.hificar_xfmr_workspace_bytes_lowrate.restype = cs
-    lib.hificar_xfmr_forward_lowrate.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, cs, vp]
-    lib.hificar_xfmr_forward_lowrate.restype = ci
-    lib.hificar_xfmr_debug_tap.argtypes = [vp, ctypes.c_char_p, vp, cs]
-    lib.hificar_xfmr_debug_tap.restype = ci
-    lib.hificar_xfmr_engine.argtypes = [vp]
-    lib.hificar_xfmr_engine.restype = vp
-    lib.hificar_xfmr_destroy.argtypes = [vp]
-    lib.hificar_xfmr_destroy.restype = None
-    lib.hificar_xfmr_set_parameters_device.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp), ci, vp]
-    lib.hificar_xfmr_set_parameters_device.restype = ci
-    lib.hificar_xfmr_grad_count.argtypes = [vp]
-    lib.hificar_xfmr_grad_count.restype = ci
-    lib.hificar_xfmr_grad_info.argtypes = [vp, ci, ctypes.c_char_p, ctypes.POINTER(c64), ctypes.POINTER(c64)]
-    lib.hificar_xfmr_grad_info.restype = ci
-    lib.hificar_xfmr_grad_floats.argtypes = [vp]
-    lib.hificar_xfmr_grad_floats.restype = c64
-    lib.hificar_xfmr_tape_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_xfmr_tape_bytes.restype = cs
-    lib.hificar_xfmr_train_workspace_bytes.argtypes = [vp, ci, ci]
-    lib.hificar_xfmr_train_workspace_bytes.restype = cs
-    lib.hificar_xfmr_forward_train.argtypes = [vp, vp, vp, vp, ci, ci, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp, cs, vp, cs, vp]
-    lib.hificar_xfmr_forward_train.restype = ci
-    lib.hificar_xfmr_forward_train_ragged.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp, cs, vp,
-                                                      cs, vp]
-    lib.hificar_xfmr_forward_train_ragged.restype = ci
-    lib.hificar_xfmr_backward.argtypes = [vp, vp, ci, ci, vp, cs, vp, vp, vp, cs, vp]
-    lib.hificar_xfmr_backward.restype = ci
-    lib.hificar_xfmr_packed_rows.argtypes = [ci, ci, vp]
-    lib.hificar_xfmr_packed_rows.restype = ci
-    lib.hificar_xfmr_tape_bytes_packed.argtypes = [vp, ci, ci]
-    lib.hificar_xfmr_tape_bytes_packed.restype = cs
-    lib.hificar_xfmr_train_workspace_bytes_packed.argtypes = [vp, ci, ci]
-    lib.hificar_xfmr_train_workspace_bytes_packed.restype = cs
-    lib.hificar_xfmr_forward_train_packed.argtypes = list(lib.hificar_xfmr_forward_train_ragged.argtypes)
-    lib.hificar_xfmr_forward_train_packed.restype = ci
-    lib.hificar_xfmr_backward_packed.argtypes = [vp, vp, vp, ci, ci, vp, cs, vp, vp, vp, cs, vp]
-    lib.hificar_xfmr_backward_packed.restype = ci
-    lib.hificar_destroy.argtypes = [vp]
-    lib.hificar_destroy.restype = None
-    lib.hificar_last_error.argtypes = []
-    lib.hificar_last_error.restype = ctypes.c_char_p
-    lib.hificar_version.argtypes = []
-    lib.hificar_version.restype = ctypes.c_char_p
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
 
-LOWRATE_MAX_FACTOR = 16  # HIFICAR_LOWRATE_MAX_FACTOR (include/hificar.h)
+def profile_rows(lib, engine, capacity):
+    """hificar_profile_end on ``engine`` into ``capacity`` rows -> (rows, n): the rows the library filled, as dicts with the fields of
+    hificar_kernel_stat (name, launches, total_ms, flops, bytes), and the number n of distinct kernels it reported (n > capacity: rows
+    were dropped)."""
+    stats = (HificarKernelStat * capacity)()
+    n = ctypes.c_int(0)
+    check(lib.hificar_profile_end(engine, stats, capacity, ctypes.byref(n)), "hificar_profile_end")
+    rows = [dict(name=s.name.decode(), launches=int(s.launches), total_ms=float(s.total_ms), flops=float(s.flops), bytes=float(s.bytes))
+            for s in stats[:min(n.value, capacity)]]
+    return rows, n.value
 
 
 def check_interp_factor(interp_factor) -> int:
@@ -672,7 +233,7 @@ def check_interp_factor(interp_factor) -> int:
 def check(rc, what):
     if rc != 0:
         msg = load_library().hificar_last_error().decode("utf-8", "replace")
-        exc = ValueError if rc == -1 else RuntimeError
+        exc = ValueError if rc == E_INVALID else RuntimeError
         raise exc(f"{what}: {msg} (hificar error {rc})")
 
 
@@ -775,9 +336,8 @@ def make_gblock_config(params: dict, precision: int) -> HificarGBlockConfig:
 
 # what hificar_bigru_create accepts (csrc/hificar_bigru.hip.inc; HIFICAR_BIGRU_MAX_* of include/hificar.h); BiGRU.__init__ checks the same
 # numbers so that an unsupported configuration fails at construction, not at the first forward on the device
-BIGRU_MAX_IN = 4096
-BIGRU_MAX_HIDDEN = 256   # one workgroup holds one direction's W_hh in registers + LDS + a streamed remainder
-BIGRU_MAX_OUT = 32       # fc2's rows in the head kernel's LDS
+# (BIGRU_MAX_HIDDEN: one workgroup holds one direction's W_hh in registers + LDS + a streamed remainder; BIGRU_MAX_OUT: fc2's rows in the head
+# kernel's LDS)
 
 
 def check_bigru_params(params: dict):
@@ -803,10 +363,8 @@ def make_bigru_config(params: dict) -> HificarBigruConfig:
 
 # what hificar_xfmr_create accepts (csrc/hificar_xfmr.hip.inc; HIFICAR_XFMR_MAX_* of include/hificar.h); Transformer.__init__ checks the same
 # numbers so that an unsupported configuration fails at construction, before any device work
-XFMR_MAX_IN = 4096
-XFMR_MAX_OUT = 1024      # w_out's rows share the feed-forward buffer
-XFMR_MAX_HIDDEN = 1024   # head size hidden_dim / 8 up to 128: the attention kernel's instantiations
-XFMR_MAX_LAYERS = 24
+# (XFMR_MAX_OUT: w_out's rows share the feed-forward buffer; XFMR_MAX_HIDDEN: head size hidden_dim / 8 up to 128, the attention kernel's
+# instantiations)
 XFMR_HEADS = 8           # nhead, dim_feedforward, relative_positional_distance: the reference constructor's constants (transformer.py:43)
 XFMR_FF = 3072
 XFMR_REL = 100

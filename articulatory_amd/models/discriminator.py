@@ -563,11 +563,7 @@ class HiFiGANMultiScaleMultiPeriodDiscriminator(torch.nn.Module):
         _native.check(self._lib.hificar_profile_begin(self._lib.hificar_disc_engine(self._handle)), "hificar_profile_begin")
 
     def profile_end(self):
-        stats = (_native.HificarKernelStat * 96)()
-        n = ctypes.c_int(0)
-        _native.check(self._lib.hificar_profile_end(self._lib.hificar_disc_engine(self._handle), stats, 96, ctypes.byref(n)), "hificar_profile_end")
-        return [dict(name=stats[i].name.decode(), launches=int(stats[i].launches), total_ms=float(stats[i].total_ms),
-                     flops=float(stats[i].flops), bytes=float(stats[i].bytes)) for i in range(min(n.value, 96))]
+        return _native.profile_rows(self._lib, self._lib.hificar_disc_engine(self._handle), 96)[0]
 
     # ------------------------------------------------------------------ fused GAN criterion
     def generator_loss(self, y_fake, y_real=None, loss_type="mse", average_by_discriminators=True, lambda_adv=1.0, lambda_feat_match=0.0,

@@ -458,11 +458,7 @@ class _NativeGenerator(torch.nn.Module):
 
     def profile_end(self):
         """Stop profiling; returns [{name, launches, total_ms, flops, bytes}], slowest kernel first."""
-        stats = (_native.HificarKernelStat * 96)()
-        n = ctypes.c_int(0)
-        _native.check(self._lib.hificar_profile_end(self._lib.hificar_engine_of(self._handle), stats, 96, ctypes.byref(n)), "hificar_profile_end")
-        return [dict(name=stats[i].name.decode(), launches=int(stats[i].launches), total_ms=float(stats[i].total_ms),
-                     flops=float(stats[i].flops), bytes=float(stats[i].bytes)) for i in range(min(n.value, 96))]
+        return _native.profile_rows(self._lib, self._lib.hificar_engine_of(self._handle), 96)[0]
 
     def debug_taps(self, names, c, ar=None, spk_id=None):
         """Parity aid (C ABI: hificar_debug_tap): one forward that also returns the named per-layer intermediates in the

@@ -4,7 +4,6 @@ restatement the GPU tests measure against, refusals, the C struct, and the ``art
 import ctypes
 import json
 import os
-import shutil
 import subprocess
 import sys
 
@@ -155,7 +154,7 @@ def test_refusals():
         Trainer(dict(generator_type="BiGRU"), "cpu")
 
 
-def test_config_struct_matches_header_and_create_checks(tmp_path):
+def test_config_struct_matches_header_and_create_checks():
     assert ctypes.sizeof(_native.HificarBigruConfig) == 16
     hdr = open(os.path.join(REPO, "include", "hificar.h")).read()
     for name, v in (("IN", _native.BIGRU_MAX_IN), ("HIDDEN", _native.BIGRU_MAX_HIDDEN), ("OUT", _native.BIGRU_MAX_OUT)):
@@ -180,17 +179,6 @@ def test_config_struct_matches_header_and_create_checks(tmp_path):
         lib.hificar_bigru_destroy(h)
     bad = _native.make_bigru_config(dict(in_channels=80, hidden_size=96, out_channels=12, use_tanh=False))
     assert lib.hificar_bigru_create(ctypes.byref(bad), ctypes.byref(h)) == -1 and b"hidden_size" in lib.hificar_last_error()
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not available")
-    fields = [f[0] for f in _native.HificarBigruConfig._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hificar.h"\nint main(void) {\n'
-                   '  printf("%zu\\n", sizeof(hificar_bigru_config));\n' +
-                   "".join(f'  printf("%zu\\n", offsetof(hificar_bigru_config, {f}));\n' for f in fields) + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(_native.HificarBigruConfig)] + [getattr(_native.HificarBigruConfig, f).offset for f in fields]
 
 
 class _StubInversion:

@@ -18,8 +18,6 @@ is what HIFICAR_KSPLIT=0 promises ("every launch shape uses one accumulation ord
 with HIFICAR_KSPLIT=0 — a launch the rule keeps from the forced shape then takes another DENSE shape — and must reproduce one dense shape's
 taps, waveforms and gradients bit for bit; the split-K shapes run on a model with the default switch and agree to XSHAPE_TOL."""
 
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -144,12 +142,10 @@ def force(lib, eng, shape):
 
 def profile_rows(lib, eng):
     """{"layer xN": kernel} of the conv launches since hificar_profile_begin (HIFICAR_PROFILE_DETAIL=1 rows: "kernel|layer xN")."""
-    stats, n = (_native.HificarKernelStat * 512)(), ctypes.c_int(0)
-    _native.check(lib.hificar_profile_end(eng, stats, 512, ctypes.byref(n)), "hificar_profile_end")
-    assert n.value <= 512
+    stats, n = _native.profile_rows(lib, eng, 512)
+    assert n <= 512
     rows = {}
-    for i in range(n.value):
-        name = stats[i].name.decode()
+    for name in (s["name"] for s in stats):
         if name.startswith("conv_") and "|" in name:
             kernel, layer = name.split("|")
             assert layer not in rows, (layer, kernel, rows[layer])  # one launch shape per layer in the profiled window

@@ -440,7 +440,6 @@ def test_profiling_through_an_engine_of_every_kind(kind):
     """hificar_profile_begin / hificar_profile_end take the conv engine of any model: the generator's own (hificar_engine_of), the
     discriminators' and the BiGRU's.  One forward at B = 1 and the shortest length each model's tests use: every launch is a row with a
     count and a device time, and the shared conv kernels are among them."""
-    import ctypes
 
     from conftest import E2W_PARAMS
     from articulatory_amd import _native
@@ -473,9 +472,7 @@ def test_profiling_through_an_engine_of_every_kind(kind):
             lib, eng = _native.load_library(), m.engine()
             _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
             m(x)
-            stats, n = (_native.HificarKernelStat * 32)(), ctypes.c_int()
-            _native.check(lib.hificar_profile_end(eng, stats, 32, ctypes.byref(n)), "hificar_profile_end")
-            rows = [dict(name=stats[i].name.decode(), launches=int(stats[i].launches), total_ms=float(stats[i].total_ms)) for i in range(n.value)]
+            rows, _ = _native.profile_rows(lib, eng, 32)
     print(kind, [(r["name"], r["launches"], round(r["total_ms"], 4)) for r in rows])
     assert len(rows) >= 1
     assert all(r["launches"] >= 1 and r["total_ms"] > 0 for r in rows), rows

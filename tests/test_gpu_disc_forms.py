@@ -38,7 +38,6 @@ the tensor's max (worst case named):
 All but one are below a hundredth of their bar.  The period output conv's weight_g is one number, sum(dW * v) / |v|, a sum that cancels: the
 oracle's own float32 run moves it by a quarter of the bar, so that tensor alone is held to the bar plus three times the measured gap,
 2e-4 + 3 * 4.8e-5 = 3.44e-4 (ONE_ELEMENT_G_TOL)."""
-import ctypes
 from collections import Counter
 
 import numpy as np
@@ -141,10 +140,9 @@ def build(params, sd):
 
 def profile_rows(lib, eng):
     """{row: launches} since hificar_profile_begin."""
-    stats, n = (_native.HificarKernelStat * 512)(), ctypes.c_int(0)
-    _native.check(lib.hificar_profile_end(eng, stats, 512, ctypes.byref(n)), "hificar_profile_end")
-    assert n.value <= 512
-    return {stats[i].name.decode(): int(stats[i].launches) for i in range(n.value)}
+    rows, n = _native.profile_rows(lib, eng, 512)
+    assert n <= 512
+    return {r["name"]: r["launches"] for r in rows}
 
 
 def step(d, x_np, cots, profile=False):

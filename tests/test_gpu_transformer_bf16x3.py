@@ -107,10 +107,7 @@ def kernel_names(m, x):
     eng = m.engine()
     _native.check(m._lib.hificar_profile_begin(eng), "hificar_profile_begin")
     y = m(x)
-    stats = (_native.HificarKernelStat * 128)()
-    n = ctypes.c_int()
-    _native.check(m._lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
-    return y, [stats[i].name.decode() for i in range(n.value)]
+    return y, [r["name"] for r in _native.profile_rows(m._lib, eng, 128)[0]]
 
 
 def test_the_arithmetic_really_ran(gold):

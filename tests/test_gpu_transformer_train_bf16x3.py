@@ -7,7 +7,6 @@ the emulation to a quarter of them).  A ReLU may be taken on another side than f
 bf16x3 output bar (2e-4, relative) of zero.
 """
 
-import ctypes
 import os
 
 import numpy as np
@@ -52,10 +51,7 @@ def profiled(m, fn):
     lib = m._lib
     _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
     out = fn()
-    stats = (_native.HificarKernelStat * 128)()
-    n = ctypes.c_int()
-    _native.check(lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
-    return out, {stats[i].name.decode(): int(stats[i].launches) for i in range(n.value)}
+    return out, {r["name"]: r["launches"] for r in _native.profile_rows(lib, eng, 128)[0]}
 
 
 # ------------------------------------------------------------------------------------------------ 1

@@ -10,8 +10,6 @@ another side than float64 takes it only where float64's input lies within 2e-4, 
 bitwise a bf16x3w step's.  On a subset: repeats on dirty scratch around a step of another shape, NaN on padded frames, the switches.
 """
 
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -60,10 +58,9 @@ def profiled(m, fn):
     lib = m._lib
     _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
     out = fn()
-    stats, n = (_native.HificarKernelStat * 512)(), ctypes.c_int()
-    _native.check(lib.hificar_profile_end(eng, stats, 512, ctypes.byref(n)), "hificar_profile_end")
-    assert n.value < 512
-    return out, {stats[i].name.decode(): int(stats[i].launches) for i in range(n.value)}
+    rows, n = _native.profile_rows(lib, eng, 512)
+    assert n < 512
+    return out, {r["name"]: r["launches"] for r in rows}
 
 
 def check_rows(what, rows_a, rows_w, elayers):

@@ -10,7 +10,6 @@ holds the emulation to a quarter of them; a ReLU may be taken on another side th
 """
 
 import collections
-import ctypes
 
 import numpy as np
 import pytest
@@ -71,10 +70,9 @@ def profiled(m, fn):
     lib = m._lib
     _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
     out = fn()
-    stats, n = (_native.HificarKernelStat * 512)(), ctypes.c_int()
-    _native.check(lib.hificar_profile_end(eng, stats, 512, ctypes.byref(n)), "hificar_profile_end")
-    assert n.value < 512
-    return out, {stats[i].name.decode(): int(stats[i].launches) for i in range(n.value)}
+    rows, n = _native.profile_rows(lib, eng, 512)
+    assert n < 512
+    return out, {r["name"]: r["launches"] for r in rows}
 
 
 def row_shape(row):

@@ -19,7 +19,6 @@ every condition of its table.  Here each case, in train() mode, exact fp32, Leak
 With slope 1 the generator has no kinks but the output conv's LeakyReLU(0.01) and the PastFCEncoder's (0.1); as in test_gpu_train_fuzz.py the
 input seed of a case is the first whose float64 forward keeps every such pre-activation further than 2e-6 of its tensor's scale from zero
 (``case_inputs``; no case needs more than its first few seeds, and a case without such a seed fails)."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -71,10 +70,9 @@ def detail_env():
 
 def profile_rows(lib, eng):
     """{row: launches} since hificar_profile_begin."""
-    stats, n = (_native.HificarKernelStat * 512)(), ctypes.c_int(0)
-    _native.check(lib.hificar_profile_end(eng, stats, 512, ctypes.byref(n)), "hificar_profile_end")
-    assert n.value <= 512
-    return {stats[i].name.decode(): int(stats[i].launches) for i in range(n.value)}
+    rows, n = _native.profile_rows(lib, eng, 512)
+    assert n <= 512
+    return {r["name"]: r["launches"] for r in rows}
 
 
 def step(g, c_np, ar_np, cot, profile=False):

@@ -4,8 +4,6 @@ restatement the GPU tests measure against, refusals, the C struct, and the ``a2m
 import ctypes
 import inspect
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -196,7 +194,7 @@ def test_refusals():
         Trainer(dict(generator_type="Transformer"), "cpu")
 
 
-def test_config_struct_matches_header_and_create_checks(tmp_path):
+def test_config_struct_matches_header_and_create_checks():
     assert ctypes.sizeof(_native.HificarXfmrConfig) == 16
     hdr = open(os.path.join(REPO, "include", "hificar.h")).read()
     for name, v in (("IN", _native.XFMR_MAX_IN), ("OUT", _native.XFMR_MAX_OUT), ("HIDDEN", _native.XFMR_MAX_HIDDEN), ("LAYERS", _native.XFMR_MAX_LAYERS)):
@@ -227,17 +225,6 @@ def test_config_struct_matches_header_and_create_checks(tmp_path):
     for hidden in (192, 1152):
         bad = _native.make_xfmr_config(dict(SMALL, hidden_dim=hidden))
         assert lib.hificar_xfmr_create(ctypes.byref(bad), ctypes.byref(h)) == -1 and b"hidden_dim" in lib.hificar_last_error()
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not available")
-    fields = [f[0] for f in _native.HificarXfmrConfig._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hificar.h"\nint main(void) {\n'
-                   '  printf("%zu\\n", sizeof(hificar_xfmr_config));\n' +
-                   "".join(f'  printf("%zu\\n", offsetof(hificar_xfmr_config, {f}));\n' for f in fields) + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(_native.HificarXfmrConfig)] + [getattr(_native.HificarXfmrConfig, f).offset for f in fields]
 
 
 class _StubModel:

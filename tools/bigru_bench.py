@@ -21,7 +21,6 @@ HIFICAR_BIGRU_NS=1|2 overrides the number of sequences a workgroup sweeps (A/B r
 For per-kernel figures from the profiler instead:  rocprofv3 --kernel-trace --stats -- python tools/bigru_bench.py --batches 1 --window 0.05
 Prints one JSON line per B; --out also appends them to a file."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -78,10 +77,7 @@ def kernel_profile(m, x, fn=None):
     lib, eng = m._lib, m.engine()
     _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
     (fn or m)(x)
-    stats = (_native.HificarKernelStat * 32)()
-    n = ctypes.c_int()
-    _native.check(lib.hificar_profile_end(eng, stats, 32, ctypes.byref(n)), "hificar_profile_end")
-    return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(n.value)}
+    return {r["name"]: (r["launches"], r["total_ms"]) for r in _native.profile_rows(lib, eng, 32)[0]}
 
 
 def lowrate_legs(native, B, Tl, f, seconds):

@@ -29,7 +29,6 @@ legs' window spreads added together, "not separated" otherwise), per-kernel time
 workspace bytes of both legs.
    python tools/bigru_train_bench.py --interp-factor 4 --out profiles/bigru_train_lowrate.txt"""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -263,10 +262,7 @@ def kernel_profile(m, fn):
     lib, eng = m._lib, m.engine()
     _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
     fn()
-    stats = (_native.HificarKernelStat * 64)()
-    n = ctypes.c_int()
-    _native.check(lib.hificar_profile_end(eng, stats, 64, ctypes.byref(n)), "hificar_profile_end")
-    return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(n.value)}
+    return {r["name"]: (r["launches"], r["total_ms"]) for r in _native.profile_rows(lib, eng, 64)[0]}
 
 
 def main():

@@ -17,7 +17,6 @@ writes), not measured.
 """
 
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -74,10 +73,7 @@ def kernel_profile(f, fn):
     lib, eng = f._lib, f.engine()
     _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
     fn()
-    stats = (_native.HificarKernelStat * 64)()
-    n = ctypes.c_int()
-    _native.check(lib.hificar_profile_end(eng, stats, 64, ctypes.byref(n)), "hificar_profile_end")
-    return {stats[i].name.decode(): round(float(stats[i].total_ms), 4) for i in range(n.value)}
+    return {r["name"]: round(r["total_ms"], 4) for r in _native.profile_rows(lib, eng, 64)[0]}
 
 
 def counted(f, B, L):

@@ -92,7 +92,6 @@ key_tiled_ms: xfmr_attn_bwd_k_kernels of the bf16x3wac leg's profiled step besid
 the bf16x3wack leg's, and the ratio of the old row to the new pair's sum (below 1: the new pair is slower).
 Reads nothing outside the repository.  Prints one JSON line per B; --out also appends them to a file."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -133,10 +132,7 @@ def kernel_profile(m, x):
     lib, eng = m._lib, m.engine()
     _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
     m(x)
-    stats = (_native.HificarKernelStat * 128)()
-    n = ctypes.c_int()
-    _native.check(lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
-    return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(n.value)}
+    return {r["name"]: (r["launches"], r["total_ms"]) for r in _native.profile_rows(lib, eng, 128)[0]}
 
 
 def attention_rows(pw, pa):
@@ -180,10 +176,7 @@ def detail_profile(arith, sd, p, run):
     _native.check(m._lib.hificar_profile_begin(eng), "hificar_profile_begin")
     opt.zero_grad(set_to_none=True)
     run(m)
-    stats = (_native.HificarKernelStat * 512)()
-    n = ctypes.c_int()
-    _native.check(m._lib.hificar_profile_end(eng, stats, 512, ctypes.byref(n)), "hificar_profile_end")
-    return {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+    return {r["name"]: r["total_ms"] for r in _native.profile_rows(m._lib, eng, 512)[0]}
 
 
 def conv_wgrad_rows(pa, pc):
@@ -255,11 +248,9 @@ def train_main(a):
         _native.check(m._lib.hificar_profile_begin(eng), "hificar_profile_begin")
         m.zero_grad(set_to_none=True)
         F.l1_loss(m(x), y).backward()
-        stats = (_native.HificarKernelStat * 128)()
-        n = ctypes.c_int()
-        _native.check(m._lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
-        profile_step.flops = {stats[i].name.decode(): float(stats[i].flops) for i in range(n.value)}
-        return {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+        rows, _ = _native.profile_rows(m._lib, eng, 128)
+        profile_step.flops = {r["name"]: r["flops"] for r in rows}
+        return {r["name"]: r["total_ms"] for r in rows}
 
     lines = []
     for shape in a.shapes:
@@ -336,10 +327,7 @@ def train_main(a):
         _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
         native.zero_grad(set_to_none=True)
         F.l1_loss(native(x), y).backward()
-        stats = (_native.HificarKernelStat * 128)()
-        n = ctypes.c_int()
-        _native.check(lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
-        prof = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+        prof = {r["name"]: r["total_ms"] for r in _native.profile_rows(lib, eng, 128)[0]}
         total = sum(prof.values())
         res["kernels_share"] = {k: round(ms / total, 4) for k, ms in sorted(prof.items(), key=lambda kv: -kv[1])}
         res["profiled_total_ms"] = round(total, 3)
@@ -513,10 +501,7 @@ def ragged_train_main(a):
     for tag in ("packed", "ragged", "dense"):
         _native.check(lib.hificar_profile_begin(eng), "hificar_profile_begin")
         legs["native_" + tag]()
-        stats = (_native.HificarKernelStat * 128)()
-        n = ctypes.c_int()
-        _native.check(lib.hificar_profile_end(eng, stats, 128, ctypes.byref(n)), "hificar_profile_end")
-        profs[tag] = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+        profs[tag] = {r["name"]: r["total_ms"] for r in _native.profile_rows(lib, eng, 128)[0]}
         res[tag + "_kernels_ms"] = {k: round(v, 4) for k, v in sorted(profs[tag].items(), key=lambda kv: -kv[1])}
         res[tag + "_kernels_total_ms"] = round(sum(profs[tag].values()), 3)
     for arith, m3 in fast.items():
@@ -524,10 +509,7 @@ def ragged_train_main(a):
         for tag in ("packed", "ragged"):
             _native.check(lib.hificar_profile_begin(eng3), "hificar_profile_begin")
             legs[f"{arith}_{tag}"]()
-            stats = (_native.HificarKernelStat * 128)()
-            n = ctypes.c_int()
-            _native.check(lib.hificar_profile_end(eng3, stats, 128, ctypes.byref(n)), "hificar_profile_end")
-            prof3 = {stats[i].name.decode(): float(stats[i].total_ms) for i in range(n.value)}
+            prof3 = {r["name"]: r["total_ms"] for r in _native.profile_rows(lib, eng3, 128)[0]}
             res[f"{arith}_{tag}_kernels_ms"] = {k: round(v, 4) for k, v in sorted(prof3.items(), key=lambda kv: -kv[1])}
             res[f"{arith}_{tag}_kernels_total_ms"] = round(sum(prof3.values()), 3)
     if "bf16x3wa" in fast:
