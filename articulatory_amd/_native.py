@@ -391,3 +391,81 @@ def make_xfmr_config(params: dict) -> HificarXfmrConfig:
     cfg.elayers = params["elayers"]
     cfg.hidden_dim = params["hidden_dim"]
     return cfg
+
+
+# what hificar_hubert_create accepts (csrc/hificar_hubert.hip.inc; HIFICAR_HUBERT_* of include/hificar.h); features.HuBERT checks the same
+# numbers, and everything about the architecture that is not built, at construction: from a configuration alone, before any device work
+HUBERT_CONV_KERNEL = (10, 3, 3, 3, 3, 2, 2)
+HUBERT_CONV_STRIDE = (5, 2, 2, 2, 2, 2, 2)
+HUBERT_POS_TAPS = 128
+HUBERT_POS_GROUPS = 16
+HUBERT_HIDDEN_SIZES = (128, 256, 512, 768, 1024)  # 16 positional groups of 8, 16, 32, 48 or 64 channels: hubert_posconv_kernel's instantiations
+# the library's defaults for the keys a "large" config.json may leave out (transformers' HubertConfig), with the large family's switches on
+HUBERT_DEFAULTS = dict(conv_dim=(512,) * 7, conv_kernel=HUBERT_CONV_KERNEL, conv_stride=HUBERT_CONV_STRIDE, hidden_size=1024, num_hidden_layers=24,
+                       num_attention_heads=16, intermediate_size=4096, conv_bias=True, feat_extract_norm="layer", do_stable_layer_norm=True,
+                       feat_proj_layer_norm=True, layer_norm_eps=1e-5, num_conv_pos_embeddings=HUBERT_POS_TAPS,
+                       num_conv_pos_embedding_groups=HUBERT_POS_GROUPS, hidden_act="gelu", feat_extract_activation="gelu", mask_time_prob=0.05,
+                       mask_feature_prob=0.0)
+
+
+def check_hubert_config(config: dict) -> dict:
+    """A ``config.json`` mapping of a HuBERT model -> the same with the defaults filled in.  NotImplementedError for an architecture that is
+    not built (group-norm extractors, post-LN encoders, WavLM's gated relative position bias, adapters, other activations or conv plans),
+    ValueError for widths outside hificar_hubert_create's limits."""
+    c = dict(HUBERT_DEFAULTS)
+    c.update(config)
+    if str(c.get("model_type", "hubert")).lower() != "hubert" or any(k in c for k in ("num_buckets", "max_bucket_distance")):
+        raise NotImplementedError(f"HuBERT: model_type {c.get('model_type')!r}: WavLM's gated relative position bias is not built (HuBERT only)")
+    if c["feat_extract_norm"] != "layer":
+        raise NotImplementedError(f"HuBERT: feat_extract_norm={c['feat_extract_norm']!r}: group-norm extractors (HuBERT-base) are not built; "
+                                  "only the large family's layer-norm extractor is")
+    if not c["do_stable_layer_norm"]:
+        raise NotImplementedError("HuBERT: do_stable_layer_norm=False: post-LN encoders (HuBERT-base) are not built")
+    if not c["feat_proj_layer_norm"]:
+        raise NotImplementedError("HuBERT: feat_proj_layer_norm=False is not built")
+    if tuple(c["conv_kernel"]) != HUBERT_CONV_KERNEL or tuple(c["conv_stride"]) != HUBERT_CONV_STRIDE:
+        raise NotImplementedError(f"HuBERT: conv_kernel / conv_stride {tuple(c['conv_kernel'])} / {tuple(c['conv_stride'])}: only "
+                                  f"{HUBERT_CONV_KERNEL} / {HUBERT_CONV_STRIDE} is built")
+    if c["hidden_act"] != "gelu" or c["feat_extract_activation"] != "gelu":
+        raise NotImplementedError(f"HuBERT: activations {c['hidden_act']!r} / {c['feat_extract_activation']!r}: only 'gelu' (erf form) is built")
+    if c["num_conv_pos_embeddings"] != HUBERT_POS_TAPS or c["num_conv_pos_embedding_groups"] != HUBERT_POS_GROUPS or c.get("conv_pos_batch_norm"):
+        raise NotImplementedError(f"HuBERT: only the weight-normed positional conv of {HUBERT_POS_TAPS} taps in {HUBERT_POS_GROUPS} groups is built")
+    if c.get("adapter_attn_dim") is not None:
+        raise NotImplementedError("HuBERT: attention adapters are not built")
+    dims = tuple(c["conv_dim"])
+    if len(dims) != len(HUBERT_CONV_KERNEL) or len(set(dims)) != 1:
+        raise NotImplementedError(f"HuBERT: conv_dim={dims}: seven extractor layers of one width are built")
+    if dims[0] < 32 or dims[0] > HUBERT_MAX_CONV or dims[0] % 32:
+        raise ValueError(f"HuBERT: conv_dim={dims[0]} unsupported (multiples of 32 up to {HUBERT_MAX_CONV})")
+    if c["hidden_size"] not in HUBERT_HIDDEN_SIZES:
+        raise ValueError(f"HuBERT: hidden_size={c['hidden_size']} unsupported ({HUBERT_HIDDEN_SIZES}: 16 positional groups of 8 .. 64 channels)")
+    if c["num_attention_heads"] * HUBERT_HEAD_DIM != c["hidden_size"]:
+        raise ValueError(f"HuBERT: {c['num_attention_heads']} heads of hidden_size={c['hidden_size']}: head size {HUBERT_HEAD_DIM} is required "
+                         "(the attention kernel's one instantiation)")
+    if c["intermediate_size"] < 32 or c["intermediate_size"] > HUBERT_MAX_FFN or c["intermediate_size"] % 32:
+        raise ValueError(f"HuBERT: intermediate_size={c['intermediate_size']} unsupported (multiples of 32 up to {HUBERT_MAX_FFN})")
+    if not 1 <= c["num_hidden_layers"] <= HUBERT_MAX_LAYERS:
+        raise ValueError(f"HuBERT: num_hidden_layers={c['num_hidden_layers']} out of range (1 .. {HUBERT_MAX_LAYERS})")
+    return c
+
+
+def make_hubert_config(config: dict, normalize: bool, norm_eps: float) -> HificarHubertConfig:
+    """A checked HuBERT configuration (check_hubert_config) -> hificar_hubert_config."""
+    cfg = HificarHubertConfig()
+    cfg.conv_dim = config["conv_dim"][0]
+    cfg.hidden_size = config["hidden_size"]
+    cfg.num_hidden_layers = config["num_hidden_layers"]
+    cfg.num_attention_heads = config["num_attention_heads"]
+    cfg.intermediate_size = config["intermediate_size"]
+    cfg.conv_bias = int(bool(config["conv_bias"]))
+    cfg.normalize = int(bool(normalize))
+    cfg.layer_norm_eps = float(config["layer_norm_eps"])
+    cfg.norm_eps = float(norm_eps)
+    return cfg
+
+
+def hubert_frames(length) -> int:
+    """50-Hz frames of an utterance of ``length`` samples (hificar_hubert_frames): (length - 400) // 320 + 1; ValueError under 400 samples."""
+    if int(length) < HUBERT_MIN_SAMPLES:
+        raise ValueError(f"HuBERT: {int(length)} samples: an utterance under {HUBERT_MIN_SAMPLES} samples has no frame")
+    return (int(length) - 400) // 320 + 1

@@ -4,10 +4,11 @@
     python -m articulatory_amd.bin.predict_ema MODEL_DIR FEATS OUTDIR [--interp-factor N] [--zscore | --no-zscore] [--batch-size N]
                                                [--precision P] [--dry-run]
     python -m articulatory_amd.bin.predict_ema MODEL_DIR WAVS OUTDIR --from-wav [--hop-length N] [...]
+    python -m articulatory_amd.bin.predict_ema MODEL_h2_DIR WAVS OUTDIR --from-wav --ssl-model HUBERT_DIR [--ssl-layer N] [...]
 
 ``MODEL_DIR`` holds ``best_mel_ckpt.pkl`` and ``config.yml`` (predict_ema.py:54-55; what ``InversionTrainer`` writes).  ``FEATS`` is a directory
 of ``<utt>.npy`` files, each (frames, channels) — the speech model's last hidden states, or the MFCC matrix transposed — or a kaldi-style scp
-file; the SSL extraction is the caller's (s3prl is not a dependency of this package; MFCCs: ``--from-wav`` below).  ``OUTDIR/<utt>.npy`` is
+file (from wavs: ``--from-wav`` below, with MFCCs or, for the SSL models, ``--ssl-model``).  ``OUTDIR/<utt>.npy`` is
 (factor * frames, out_channels) float32, as ``np.save(pred)`` at predict_ema.py:102.
 
 The defaults follow the reference's own rules (predict_ema.py:37-47), read off the directory's name: ``_h2`` in it means SSL features, which
@@ -19,8 +20,16 @@ every one computed as if alone: any batch size writes the same files.
 ``--from-wav`` is the reference's own command line for its MFCC models: ``WAVS`` is a directory of ``<utt>.wav`` files (or a ``utt path``
 scp file) of mono 16-bit PCM, read as ``int16 / 32768`` — what soundfile's float read gives —, and ``wav2mfcc`` (predict_ema.py:32-33) runs
 on the device (``articulatory_amd.features.MFCC``) in front of ``forward_lowrate``: hop 160 when the directory's name starts with ``hprc``,
-else 80 (predict_ema.py:42-47; ``--hop-length`` overrides), the filterbank of every file's own sampling rate, nothing resampled.  A
-directory with ``_h2`` in its name is refused: SSL extraction is not built.
+else 80 (predict_ema.py:42-47; ``--hop-length`` overrides), the filterbank of every file's own sampling rate, nothing resampled.
+
+For a directory with ``_h2`` in its name — the SSL models, in front of which the reference puts ``hubert_large_ll60k`` (its last hidden state at
+50 Hz, stretched by 4) — ``--from-wav`` needs ``--ssl-model DIR``: a HuBERT model of the large family in the ``transformers`` layout
+(``config.json`` + ``model.safetensors`` | ``pytorch_model.bin``), run on the device by ``articulatory_amd.features.HuBERT`` in front of
+``forward_lowrate`` with the directory's factor and no z-score.  ``--ssl-layer N`` takes ``hidden_states[N]`` instead of the last hidden state.
+Every wav must be 16 kHz (the reference's ``linear_inference.py`` asserts the same; nothing is resampled) and at least 400 samples long; a
+file that is not is a ValueError naming it.  Utterances are batched by length, each computed as if alone: any ``--batch-size`` writes the same
+bytes.  ``--dry-run`` reads ``config.json`` alone.  Without ``--ssl-model`` such a directory is refused: SSL extraction is not built into the
+call then.
 """
 
 import argparse
@@ -127,6 +136,11 @@ def get_parser():
                              "directories without _h2 in their name")
     parser.add_argument("--hop-length", type=int, default=None,
                         help="hop of the MFCC extraction in samples (--from-wav); default: 160 when the directory name starts with hprc, else 80")
+    parser.add_argument("--ssl-model", type=str, default=None,
+                        help="directory of a HuBERT model (large family; transformers layout: config.json + model.safetensors | "
+                             "pytorch_model.bin): with --from-wav and a model directory with _h2 in its name, its hidden states are the features")
+    parser.add_argument("--ssl-layer", type=int, default=None,
+                        help="with --ssl-model: take hidden_states[N] (0 .. layers - 1) instead of the last hidden state")
     z = parser.add_mutually_exclusive_group()
     z.add_argument("--zscore", dest="zscore", action="store_true", default=None,
                    help="normalise every utterance by the mean and standard deviation of all its elements (default without _h2 in the name)")
@@ -185,6 +199,42 @@ def predict_wavs(model, pairs, outdir, device, hop_length=80, interp_factor=1, z
     return n
 
 
+SSL_RATE = 16000  # what the speech model was trained on (linear_inference.py asserts it); nothing is resampled
+
+
+def check_ssl_wavs(pairs, info):
+    """ValueError naming the first file that is not 16 kHz or is under 400 samples (``info``: path -> (rate, samples), from the headers)."""
+    from articulatory_amd._native import HUBERT_MIN_SAMPLES
+
+    for _, p in pairs:
+        sr, n = info[p]
+        if sr != SSL_RATE:
+            raise ValueError(f"{p}: sampling rate {sr}, the speech model takes {SSL_RATE} Hz only (no resampling is built)")
+        if n < HUBERT_MIN_SAMPLES:
+            raise ValueError(f"{p}: {n} samples, the speech model needs at least {HUBERT_MIN_SAMPLES} for one frame")
+
+
+def predict_ssl(model, hubert, pairs, outdir, device, interp_factor=4, zscore=False, batch_size=1, layer=-1):
+    """predict_ema.py:77-102 for its SSL models: (utt_id, wav path) pairs -> ``outdir/<utt_id>.npy``.  Batches of similar lengths; per batch
+    the padded waveforms go to the device in one copy and stay there through ``hubert`` and ``model.forward_lowrate`` up to the prediction.
+    Every utterance is computed as if alone.  Returns the number of utterances."""
+    n = 0
+    with torch.no_grad():
+        wavs = ((u, read_wav(p)[0]) for u, p in pairs)
+        for batch in length_batches(wavs, max(1, batch_size)):
+            lens = [len(y) for _, y in batch]
+            padded = np.zeros((len(batch), max(lens)), dtype=np.float32)
+            for i, (_, y) in enumerate(batch):
+                padded[i, :lens[i]] = y
+            feats, _ = hubert(torch.from_numpy(padded).to(device), lens, layer=layer)
+            frames = [hubert.frames(l) for l in lens]
+            yb = model.forward_lowrate(feats, lengths=frames, interp_factor=interp_factor, zscore=zscore)
+            for i, (utt_id, _) in enumerate(batch):
+                np.save(os.path.join(outdir, f"{utt_id}.npy"), yb[i, :, :interp_factor * frames[i]].transpose(0, 1).cpu().numpy())
+                n += 1
+    return n
+
+
 def main(argv=None):
     from articulatory_amd._native import check_interp_factor
     from articulatory_amd.utils import load_model
@@ -204,9 +254,17 @@ def main(argv=None):
     config.setdefault("format", "npy")
     if config.get("generator_params", {}).get("use_ar", False):
         raise NotImplementedError("predict_ema with use_ar: ar_loop's feature branches are not built")
-    if args.from_wav and "_h2" in os.path.basename(os.path.normpath(args.model_dir)):
-        raise NotImplementedError("predict_ema --from-wav for a model directory with _h2 in its name: SSL extraction is not built "
-                                  "(extract the speech model's hidden states and pass them as .npy files)")
+    ssl = "_h2" in os.path.basename(os.path.normpath(args.model_dir))
+    if args.from_wav and ssl and args.ssl_model is None:
+        raise NotImplementedError("predict_ema --from-wav for a model directory with _h2 in its name: SSL extraction is not built into this "
+                                  "call without a speech model (pass --ssl-model DIR, a HuBERT model of the large family, or extract the "
+                                  "hidden states yourself and pass them as .npy files)")
+    if args.ssl_model is not None and not (args.from_wav and ssl):
+        raise ValueError("--ssl-model belongs to --from-wav with a model directory with _h2 in its name")
+    if args.ssl_layer is not None and args.ssl_model is None:
+        raise ValueError("--ssl-layer belongs to --ssl-model")
+    if args.hop_length is not None and args.ssl_model is not None:
+        raise ValueError("--hop-length belongs to the MFCC extraction, not to --ssl-model")
     if args.hop_length is not None and not args.from_wav:
         raise ValueError("--hop-length belongs to --from-wav")
     if args.hop_length is not None and args.hop_length < 1:
@@ -218,6 +276,24 @@ def main(argv=None):
         hop = derive_hop_length(args.model_dir) if args.hop_length is None else args.hop_length
         info = {p: wav_info(p) for _, p in pairs}
         rates = {p: sr for p, (sr, _) in info.items()}
+    ssl_config = None
+    if args.ssl_model is not None:
+        from articulatory_amd._native import check_hubert_config, hubert_frames
+
+        with open(os.path.join(args.ssl_model, "config.json")) as f:
+            ssl_config = check_hubert_config(json.load(f))
+        if args.ssl_layer is not None and not 0 <= args.ssl_layer < ssl_config["num_hidden_layers"]:
+            raise ValueError(f"--ssl-layer {args.ssl_layer} outside 0 .. {ssl_config['num_hidden_layers'] - 1}")
+        check_ssl_wavs(pairs, info)
+    if args.dry_run and ssl_config is not None:
+        print(json.dumps({"model_dir": args.model_dir, "checkpoint": checkpoint, "generator_type": config.get("generator_type"),
+                          "interp_factor": factor, "zscore": bool(zscore), "batch_size": args.batch_size, "precision": args.precision or "f32",
+                          "front_end": "hubert", "ssl_model": args.ssl_model, "ssl_layer": -1 if args.ssl_layer is None else args.ssl_layer,
+                          "hidden_size": ssl_config["hidden_size"], "num_hidden_layers": ssl_config["num_hidden_layers"],
+                          "rates": [SSL_RATE], "utterances": [u for u, _ in pairs],
+                          "samples": int(sum(info[p][1] for _, p in pairs)),
+                          "frames": int(sum(hubert_frames(info[p][1]) for _, p in pairs))}), flush=True)
+        return
     if args.dry_run and args.from_wav:
         print(json.dumps({"model_dir": args.model_dir, "checkpoint": checkpoint, "generator_type": config.get("generator_type"),
                           "interp_factor": factor, "zscore": bool(zscore), "batch_size": args.batch_size, "precision": args.precision or "f32",
@@ -247,7 +323,17 @@ def main(argv=None):
         elif args.precision != "f32":
             raise NotImplementedError(f"--precision {args.precision}: {type(model).__name__} runs in the exact-fp32 arithmetic only")
     model = model.eval().to(device)
-    if args.from_wav:
+    if ssl_config is not None:
+        from articulatory_amd.features import HuBERT
+
+        width = config.get("generator_params", {}).get("in_channels")
+        if width is not None and width != ssl_config["hidden_size"]:
+            raise ValueError(f"--ssl-model: hidden_size {ssl_config['hidden_size']} does not match the model's in_channels {width}")
+        hubert = HuBERT.from_pretrained(args.ssl_model).to(device)
+        logging.info(f"Loaded the speech model from {args.ssl_model}.")
+        n = predict_ssl(model, hubert, pairs, args.outdir, device, interp_factor=factor, zscore=zscore, batch_size=args.batch_size,
+                        layer=-1 if args.ssl_layer is None else args.ssl_layer)
+    elif args.from_wav:
         n = predict_wavs(model, pairs, args.outdir, device, hop_length=hop, interp_factor=factor, zscore=zscore, batch_size=args.batch_size,
                          rates=rates)
     else:

@@ -16,6 +16,7 @@
 #include "hificar_xfmr_attn16_train.hip.h"
 #include "hificar_xfmr_attn16_train_k.hip.h"
 #include "hificar_xfmr_wgrad16.hip.h"
+#include "hificar_hubert_kernels.hip.h"
 
 #include "../../include/hificar.h"
 
@@ -263,7 +264,7 @@ struct hificar_handle : hificar_engine {
 // The generators add HIFICAR_AR_DUAL_MIN / _MAX: the batch sizes hificar_ar_loop runs as two halves on two streams (default 17..62; MAX=0: never).
 // hificar_disc.hip.inc adds HIFICAR_DISC_STREAMS=0 (sub-discriminators on the caller's stream: per-launch counters) and HIFICAR_COL2IM_VEC4=0.
 // hificar_bigru.hip.inc adds HIFICAR_BIGRU_NS=1|2 (sequences per workgroup of the recurrent kernel, A/B runs) and always runs with KSPLIT off.
-// hificar_xfmr.hip.inc (the Transformer) adds none and always runs with KSPLIT off and without the pair kernels.
+// hificar_xfmr.hip.inc (the Transformer) adds none and always runs with KSPLIT off and without the pair kernels; so does hificar_hubert.hip.inc.
 static FILE* g_launch_log = nullptr;
 static void read_env_switches(hificar_engine* h) {
     if (const char* e = getenv("HIFICAR_PROFILE_DETAIL")) h->profile_detail = atoi(e) != 0;
@@ -2716,3 +2717,4 @@ static int feature_train_make(G* g, int (*build)(G*, TS*), const char* model) {
 #include "hificar_bigru_train.hip.inc"
 #include "hificar_xfmr.hip.inc"
 #include "hificar_xfmr_train.hip.inc"
+#include "hificar_hubert.hip.inc"

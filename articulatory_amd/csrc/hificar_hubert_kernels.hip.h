@@ -1,0 +1,401 @@
+// Kernels of the HuBERT encoder ("large" family: layer-norm extractor, stable layer norm) that are not GEMMs on the conv engine.
+//   hubert_stats_kernel    per utterance, mean and 1 / sqrt(var + eps) of its own samples (population variance), two passes in double
+//   hubert_frames_kernel   the 50-Hz frame count of every utterance, (l - 400) / 320 + 1, for every kernel behind the extractor
+//   hubert_conv0_kernel    extractor layer 0: normalised samples -> Conv1d(1 -> C, k 10, s 5) + LayerNorm(C) + GELU, one wave per output row
+//   hubert_ln_kernel       LayerNorm(F) with the config's eps, optionally followed by GELU (extractor layers 1 - 6); source and destination
+//                          may have different rows per sequence
+//   hubert_gelu_kernel     GELU in place on the feed-forward's hidden rows
+//   hubert_posconv_kernel  the grouped 128-tap positional conv on v_mfma_f32_16x16x4_f32: x + GELU(conv(x) + b)
+//   hubert_attn_kernel     full softmax attention over the utterance's own keys: xfmr_attn_kernel's transposed-MFMA plan without band,
+//                          table or positional LDS region
+// Exact fp32 throughout (GELU in its erf form).  Every sum's order depends on the utterance alone: no atomics, no split reductions whose
+// shape depends on the batch.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "hificar_xfmr_kernels.hip.h"
+
+namespace hificar {
+
+constexpr int kHubK0 = 10, kHubS0 = 5;      // extractor layer 0: kernel and stride
+constexpr int kHubPosTaps = 128;            // num_conv_pos_embeddings
+constexpr int kHubPosGroups = 16;           // num_conv_pos_embedding_groups
+constexpr int kHubPosTR = 128;              // output rows per workgroup of the positional conv: four waves of 32
+constexpr int kHubHeadDim = 64;
+
+__device__ __forceinline__ float hubert_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+
+// One workgroup per utterance: stats[b] = (mean, 1 / sqrt(var + eps)) as doubles over wav[b, :l].  The summation plan of frontend_stats_kernel:
+// a thread sums its samples in index order, a wave's lanes by a butterfly, the four waves in wave order.
+__global__ __launch_bounds__(256) void hubert_stats_kernel(const float* __restrict__ wav, const int* __restrict__ lengths, double* __restrict__ stats, int L,
+                                                           double eps) {
+    __shared__ double part[4];
+    __shared__ double total;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int l = lengths ? min(max(lengths[b], 0), L) : L;
+    const float* const xb = wav + (size_t)b * L;
+    double mean = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {
+        double acc = 0.0;
+        for (int e = tid; e < l; e += 256) {
+            const double v = (double)xb[e];
+            acc += pass == 0 ? v : (v - mean) * (v - mean);
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+        if ((tid & 63) == 0) part[tid >> 6] = acc;
+        __syncthreads();
+        if (tid == 0) total = ((part[0] + part[1]) + part[2]) + part[3];
+        __syncthreads();
+        const double s = total;
+        __syncthreads();
+        if (pass == 0) mean = l > 0 ? s / (double)l : 0.0;
+        else if (tid == 0) {
+            stats[2 * b] = mean;
+            stats[2 * b + 1] = l > 0 ? 1.0 / sqrt(s / (double)l + eps) : 0.0;
+        }
+    }
+}
+
+// frames[b] = (l - 400) / 320 + 1 for l >= 400 samples (the seven convs' lengths composed), 0 below; l clamped into 0 .. L
+__global__ __launch_bounds__(256) void hubert_frames_kernel(const int* __restrict__ lengths, int* __restrict__ frames, int B, int L) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int l = lengths ? min(max(lengths[b], 0), L) : L;
+    frames[b] = l >= 400 ? (l - 400) / 320 + 1 : 0;
+}
+
+__device__ __forceinline__ void hubert_ln_row(float4 (&v)[4], int lane, int nv, int F, float eps, const float* gamma, const float* beta, bool gelu,
+                                              float* yrow) {
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (lane + 64 * j < nv) sum += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+    const float mean = xfmr_wave_sum(sum) / (float)F;
+    float sq = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (lane + 64 * j >= nv) continue;
+        const float a = v[j].x - mean, bb = v[j].y - mean, cc = v[j].z - mean, d = v[j].w - mean;
+        sq += (a * a + bb * bb) + (cc * cc + d * d);
+    }
+    const float rstd = 1.f / sqrtf(xfmr_wave_sum(sq) / (float)F + eps);
+    const float4* gm = reinterpret_cast<const float4*>(gamma);
+    const float4* bt = reinterpret_cast<const float4*>(beta);
+    float4* y = reinterpret_cast<float4*>(yrow);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = lane + 64 * j;
+        if (i >= nv) continue;
+        const float4 gv = gm[i], bv = bt[i];
+        float4 r = make_float4((v[j].x - mean) * rstd * gv.x + bv.x, (v[j].y - mean) * rstd * gv.y + bv.y, (v[j].z - mean) * rstd * gv.z + bv.z,
+                               (v[j].w - mean) * rstd * gv.w + bv.w);
+        if (gelu) r = make_float4(hubert_gelu(r.x), hubert_gelu(r.y), hubert_gelu(r.z), hubert_gelu(r.w));
+        y[i] = r;
+    }
+}
+
+// Extractor layer 0.  One wave per output row (position t of sequence b of this sub-batch): the row's ten samples are normalised in double
+// with the utterance's statistics (stats null: taken as they are) and rounded once; samples at or past the utterance's length are zeros, as
+// the library's padding after normalisation.  The C outputs are formed (taps in order), normalised over C (eps 1e-5, torch.nn.LayerNorm's
+// default), activated and stored once.  Rows T0 .. P - 1 of a sequence (the slack that makes its rows a whole number of stride-2 windows)
+// are zeros.  w: [10][C]; C a multiple of 4, at most 1024.
+struct HubertConv0Params {
+    const float* wav;      // [B][L], this sub-batch's first utterance
+    const int* lengths;    // this sub-batch's, or null
+    const double* stats;   // this sub-batch's [mean, rstd], or null
+    const float* w;        // [10][C]
+    const float* bias;     // [C] (zeros without conv_bias)
+    const float* gamma;
+    const float* beta;
+    float* y;              // [nseq][P][C]
+    int nseq, L, T0, P, C;
+};
+
+__global__ __launch_bounds__(256) void hubert_conv0_kernel(const HubertConv0Params p) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (long long)p.nseq * p.P) return;
+    const int b = (int)(row / p.P), t = (int)(row - (long long)b * p.P);
+    const int nv = p.C >> 2;
+    float* const yrow = p.y + (size_t)row * p.C;
+    if (t >= p.T0) {
+        for (int i = lane; i < nv; i += 64) reinterpret_cast<float4*>(yrow)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const int l = p.lengths ? min(max(p.lengths[b], 0), p.L) : p.L;
+    const double mean = p.stats ? p.stats[2 * b] : 0.0, rstd = p.stats ? p.stats[2 * b + 1] : 1.0;
+    float xs[kHubK0];
+#pragma unroll
+    for (int k = 0; k < kHubK0; ++k) {
+        const int s = kHubS0 * t + k;  // (< L: t < T0)
+        xs[k] = s < l ? (float)(((double)p.wav[(size_t)b * p.L + s] - mean) * rstd) : 0.f;
+    }
+    float4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = lane + 64 * j;
+        v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i >= nv) continue;
+        float4 a = reinterpret_cast<const float4*>(p.bias)[i];
+#pragma unroll
+        for (int k = 0; k < kHubK0; ++k) {
+            const float4 w = reinterpret_cast<const float4*>(p.w + (size_t)k * p.C)[i];
+            a.x = fmaf(w.x, xs[k], a.x);
+            a.y = fmaf(w.y, xs[k], a.y);
+            a.z = fmaf(w.z, xs[k], a.z);
+            a.w = fmaf(w.w, xs[k], a.w);
+        }
+        v[j] = a;
+    }
+    hubert_ln_row(v, lane, nv, p.C, 1e-5f, p.gamma, p.beta, true, yrow);
+}
+
+// LayerNorm(F) + optional GELU, one wave per row: row t of sequence b is read at x[(b Tin + t) F] and written at y[(b Tout + t) F], t < T.
+// Rows at or past a sequence's length (lengths non-null) are left alone.  x and y may be the same buffer when Tin == Tout.  F <= 1024, F % 4 == 0.
+struct HubertLnParams {
+    const float* x;
+    const float* gamma;
+    const float* beta;
+    const int* lengths;
+    float* y;
+    int B, T, Tin, Tout, F;
+    float eps;
+};
+
+template <bool GELU>
+__global__ __launch_bounds__(256) void hubert_ln_kernel(const HubertLnParams p) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (long long)p.B * p.T) return;
+    const int b = (int)(row / p.T), t = (int)(row - (long long)b * p.T);
+    const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
+    if (t >= len) return;
+    const int nv = p.F >> 2;
+    const float4* x = reinterpret_cast<const float4*>(p.x + ((size_t)b * p.Tin + t) * p.F);
+    float4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = lane + 64 * j;
+        v[j] = i < nv ? x[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    hubert_ln_row(v, lane, nv, p.F, p.eps, p.gamma, p.beta, GELU, p.y + ((size_t)b * p.Tout + t) * p.F);
+}
+
+// GELU in place on rows [B T][F] (F % 4 == 0); rows at or past a sequence's length are left alone.  grid (B T, ceil(F / 1024))
+__global__ __launch_bounds__(256) void hubert_gelu_kernel(float* __restrict__ x, const int* __restrict__ lengths, int T, int F) {
+    const long long row = blockIdx.x;
+    const int b = (int)(row / T), t = (int)(row - (long long)b * T);
+    const int len = lengths ? min(max(lengths[b], 0), T) : T;
+    const int i = blockIdx.y * 256 + threadIdx.x;
+    if (t >= len || 4 * i >= F) return;
+    float4* const px = reinterpret_cast<float4*>(x + (size_t)row * F) + i;
+    const float4 v = *px;
+    *px = make_float4(hubert_gelu(v.x), hubert_gelu(v.y), hubert_gelu(v.z), hubert_gelu(v.w));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The positional conv: Conv1d(H, H, 128, padding 64, groups 16) with its last output frame dropped, + bias, GELU, added to the stream:
+//     y[t, o] = x[t, o] + GELU(b[o] + sum_{k < 128} sum_{c < G} W[o, c, k] x[t + k - 64, grp G + c]),   frames outside 0 .. len - 1 are zeros.
+// One workgroup per (sequence, group, tile of 128 frames).  The tile's rows and its halo (64 before, 63 behind) of the group's G channels are
+// staged in LDS once; the taps are walked in order, each a G x G product per 16-frame block on v_mfma_f32_16x16x4_f32, computed transposed:
+// the A operand is the weight block (16 output channels x 4 input channels), the B operand 4 input channels x 16 frames read from LDS at the
+// tap's row offset, so a lane's four accumulator registers are four adjacent output channels of one frame: one float4 store.  Wave w owns
+// frames 32 w .. 32 w + 31 of the tile and all the group's output channels.  The weights are read from global memory in MFMA lane order
+// (wp: [group][tap][NOB][G / 4][64 lanes], output channels past G zeros; folded from weight_g / weight_v at hand-over): every wave of
+// every tile of a group streams the same 128 G G floats, which stay in L2.  An output's sum runs over (tap, input channel) in one fixed order.
+// pos_out (debug tap, or null): GELU(conv + b) alone.  y must not be x.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct HubertPosParams {
+    const float* x;        // [B T][H]
+    const float* wp;
+    const float* bias;     // [H]
+    const int* lengths;    // frames, device, or null
+    float* y;              // [B T][H]
+    float* pos_out;        // [B T][H] or null
+    int T, H;
+};
+
+template <int G>
+struct HubertPosLds {
+    static constexpr int pitch = G + 4;
+    static constexpr int rows = kHubPosTR + kHubPosTaps - 1;
+    static constexpr size_t bytes = (size_t)rows * pitch * sizeof(float);
+};
+
+template <int G>
+__global__ __launch_bounds__(256) void hubert_posconv_kernel(const HubertPosParams p) {
+    extern __shared__ float hubert_lds[];
+    constexpr int PT = HubertPosLds<G>::pitch, NR = HubertPosLds<G>::rows, V = G / 4, NOB = (G + 15) / 16, NS = G / 4, NT = 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    const int b = blockIdx.z, grp = blockIdx.y, t0 = blockIdx.x * kHubPosTR;
+    const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
+    if (t0 >= len) return;  // (the whole workgroup, before any barrier)
+    const size_t row0 = (size_t)b * p.T;
+    for (int i = tid; i < NR * V; i += 256) {
+        const int r = i / V, v = i - r * V;
+        const int t = t0 - kHubPosTaps / 2 + r;
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t >= 0 && t < len) x = *reinterpret_cast<const float4*>(p.x + (row0 + t) * p.H + grp * G + 4 * v);
+        *reinterpret_cast<float4*>(hubert_lds + r * PT + 4 * v) = x;
+    }
+    __syncthreads();
+    if (t0 + wave * 32 >= len) return;  // (no barrier behind this point)
+
+    f32x4 acc[NT][NOB];
+#pragma unroll
+    for (int tb = 0; tb < NT; ++tb)
+#pragma unroll
+        for (int ob = 0; ob < NOB; ++ob) acc[tb][ob] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* const wg = p.wp + (size_t)grp * kHubPosTaps * NOB * NS * 64 + lane;
+    const float* const xw = hubert_lds + (wave * 32 + c) * PT + g;
+    for (int k = 0; k < kHubPosTaps; ++k) {
+        const float* const wk = wg + (size_t)k * NOB * NS * 64;
+        const float* const xk = xw + k * PT;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            float bx[NT];
+#pragma unroll
+            for (int tb = 0; tb < NT; ++tb) bx[tb] = xk[tb * 16 * PT + 4 * s];
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob) {
+                const float a = wk[(ob * NS + s) * 64];
+#pragma unroll
+                for (int tb = 0; tb < NT; ++tb) acc[tb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bx[tb], acc[tb][ob], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int tb = 0; tb < NT; ++tb) {
+        const int tl = wave * 32 + tb * 16 + c, t = t0 + tl;
+        if (t >= len) continue;
+#pragma unroll
+        for (int ob = 0; ob < NOB; ++ob) {
+            const int o = ob * 16 + 4 * g;  // this lane's four output channels of the group
+            if (o >= G) continue;
+            const float4 bv = *reinterpret_cast<const float4*>(p.bias + grp * G + o);
+            const float4 xr = *reinterpret_cast<const float4*>(hubert_lds + (tl + kHubPosTaps / 2) * PT + o);
+            const float4 e = make_float4(hubert_gelu(acc[tb][ob][0] + bv.x), hubert_gelu(acc[tb][ob][1] + bv.y), hubert_gelu(acc[tb][ob][2] + bv.z),
+                                         hubert_gelu(acc[tb][ob][3] + bv.w));
+            const size_t at = (row0 + t) * p.H + grp * G + o;
+            *reinterpret_cast<float4*>(p.y + at) = make_float4(xr.x + e.x, xr.y + e.y, xr.z + e.z, xr.w + e.w);
+            if (p.pos_out) *reinterpret_cast<float4*>(p.pos_out + at) = e;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Full softmax attention of one head over the utterance's own keys: S[q, k] = (Q[q] . K[k]) / sqrt(d), k < len.  xfmr_attn_kernel's plan — one
+// workgroup per (sequence, head, tile of 64 queries), wave w owns queries 16 w .. 16 w + 15, everything computed transposed on
+// v_mfma_f32_16x16x4_f32 so that a query is a lane column, online softmax per 64-key block, P never in LDS — without band, table or positional
+// LDS region.  Keys past the length are skipped by predicate (weight 0, no part in the maximum); queries past it are not computed, their rows
+// of `out` not written.  The head count is the grid's y extent.  The order of every sum depends on the sequence's length only.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct HubertAttnParams {
+    const float* qkv;    // [B T][3 F]: q | k | v, each [head][d]
+    const int* lengths;  // device, or null
+    float* out;          // [B T][F]: [head][d]
+    int T, F;
+    float scale;         // 1 / sqrt(d)
+};
+
+template <int D>
+struct HubertAttnLds {
+    static constexpr size_t bytes = (size_t)2 * kXfmrKB * (D + 4) * sizeof(float);
+};
+
+template <int D>
+__global__ __launch_bounds__(256) void hubert_attn_kernel(const HubertAttnParams p) {
+    extern __shared__ float hubert_lds[];
+    constexpr int PT = D + 4, NS = D / 4, NM = D / 16;
+    float* const kbuf = hubert_lds;
+    float* const vbuf = hubert_lds + kXfmrKB * PT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kXfmrTQ;
+    const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
+    if (q0 >= len) return;  // (the whole workgroup: no barrier has been reached)
+    const size_t row0 = (size_t)b * p.T;
+    const size_t F3 = (size_t)3 * p.F;
+    const int q = q0 + wave * 16 + c;
+    const bool qok = q < len;
+
+    float qf[NS];  // this lane's B operands: Q[q][4 s + g]
+    {
+        const float* qrow = p.qkv + (row0 + (qok ? q : q0)) * F3 + h * D;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) qf[s] = qok ? qrow[4 * s + g] : 0.f;
+    }
+    float m = -INFINITY, l = 0.f;
+    f32x4 o[NM];
+#pragma unroll
+    for (int j = 0; j < NM; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int kb = 0; kb < len; kb += kXfmrKB) {
+        const int n = min(kXfmrKB, len - kb);
+        __syncthreads();
+        xfmr_stage<D>(kbuf, p.qkv + (row0 + kb) * F3 + p.F + h * D, F3, n, tid);
+        xfmr_stage<D>(vbuf, p.qkv + (row0 + kb) * F3 + 2 * p.F + h * D, F3, n, tid);
+        __syncthreads();
+
+        f32x4 s[4];
+        unsigned valid = 0;  // bit 4 sb + i: key kb + 16 sb + 4 g + i exists
+        float mb = -INFINITY;
+#pragma unroll
+        for (int sb = 0; sb < 4; ++sb) {
+            s[sb] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (16 * sb >= n) continue;  // (workgroup-uniform)
+            const float* a = kbuf + (16 * sb + c) * PT + g;
+#pragma unroll
+            for (int st = 0; st < NS; ++st) s[sb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * st], qf[st], s[sb], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (qok && 16 * sb + 4 * g + i < n) {
+                    const float v = s[sb][i] * p.scale;
+                    s[sb][i] = v;
+                    mb = fmaxf(mb, v);
+                    valid |= 1u << (4 * sb + i);
+                }
+            }
+        }
+        mb = fmaxf(mb, __shfl_xor(mb, 16));
+        mb = fmaxf(mb, __shfl_xor(mb, 32));
+        const float m_new = fmaxf(m, mb);
+        const float alpha = m_new == -INFINITY ? 1.f : expf(m - m_new);
+        float ls = 0.f;
+#pragma unroll
+        for (int sb = 0; sb < 4; ++sb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float e = (valid >> (4 * sb + i)) & 1u ? expf(s[sb][i] - m_new) : 0.f;
+                s[sb][i] = e;
+                ls += e;
+            }
+        ls += __shfl_xor(ls, 16);
+        ls += __shfl_xor(ls, 32);
+        l = l * alpha + ls;
+        m = m_new;
+#pragma unroll
+        for (int j = 0; j < NM; ++j) o[j] *= alpha;
+#pragma unroll
+        for (int sb = 0; sb < 4; ++sb) {
+            if (16 * sb >= n) continue;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float* a = vbuf + (16 * sb + 4 * g + i) * PT + c;
+#pragma unroll
+                for (int j = 0; j < NM; ++j) o[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[16 * j], s[sb][i], o[j], 0, 0, 0);
+            }
+        }
+    }
+    if (!qok) return;
+    const float inv = 1.f / l;  // (l >= 1: the query's own key exists)
+    float* orow = p.out + (row0 + q) * p.F + h * D + 4 * g;
+#pragma unroll
+    for (int j = 0; j < NM; ++j)
+        *reinterpret_cast<float4*>(orow + 16 * j) = make_float4(o[j][0] * inv, o[j][1] * inv, o[j][2] * inv, o[j][3] * inv);
+}
+
+}  // namespace hificar

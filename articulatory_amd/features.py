@@ -7,6 +7,9 @@ every utterance computed as if alone.  MI355X-native; there is no CPU fallback a
 The arithmetic restates librosa 0.8.1's published algorithm (``stft(center=True, pad_mode="reflect")``, the Slaney filterbank of
 ``utils.mel``, ``power_to_db``, ``scipy.fftpack.dct(type=2, norm="ortho")``); librosa is not a dependency and parity with it is not pinned.
 The z-score of ``wav2mfcc`` is not part of ``MFCC``: ``model.forward_lowrate(feats, lengths=frames, interp_factor=1, zscore=True)`` does it.
+
+``HuBERT`` — the speech model in front of the reference's SSL inversion models (``*_h2``) — has the same call shape but owns parameters: a
+``torch.nn.Module`` with the ``transformers`` library's ``HubertModel`` state_dict over a ``hificar_hubert_*`` handle (below).
 """
 
 import ctypes
@@ -15,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _native
+from .models import _feature_model
 from .utils.mel import mel_filterbank
 
 
@@ -178,3 +182,203 @@ class LogMel(_SpeechFeature):
         cfg = _native.HificarFeatConfig(_native.FEAT_LOGMEL, fft_size, hop_size, fft_size if win_length is None else win_length, num_mels, 0,
                                         eps, -1.0, 0 if log_base is None else int(log_base))
         self._init_native(cfg, melmat, num_mels)
+
+
+class _Holder(torch.nn.Module):
+    """A module that only holds sub-modules by name (the ``HubertModel`` hierarchy's inner nodes)."""
+
+    def __init__(self, **children):
+        super().__init__()
+        for k, v in children.items():
+            setattr(self, k, v)
+
+
+_WEIGHT_NORM_OLD = {"weight_g": "parametrizations.weight.original0", "weight_v": "parametrizations.weight.original1"}
+
+
+class HuBERT(_feature_model.NativeFeatureModel):
+    """The HuBERT encoder of the "large" family (layer-norm extractor, stable layer norm: ``hubert-large-ll60k``'s architecture), the speech
+    model the reference's ``egs/ema/voc1/local/predict_ema.py`` puts in front of its SSL inversion models.  The module owns the parameters —
+    ``state_dict()`` has the keys and shapes of the ``transformers`` library's ``HubertModel`` and loads with ``strict=True``; the positional
+    conv's weight norm is also accepted in its old form, ``weight_g`` / ``weight_v`` — while the arithmetic runs in ``libhificar.so`` behind one
+    native handle (``hificar_hubert_*`` of include/hificar.h): copies and pickles never share a handle, there is no CPU fallback and no
+    backward.  Inference only (``eval()`` mode, which the constructor sets); exact fp32.
+
+        feats, frames = hubert(wav, lengths=samples, layer=-1)          # (B, hidden_size, Tmax) at 50 Hz, (B,) int32
+        ema = model.forward_lowrate(feats, lengths=frames, interp_factor=4)
+
+    ``wav`` is (B, L) or (L,) at 16 kHz on the device, zero-padded; every utterance is computed as if alone, bit for bit, and ``feats`` is
+    exactly zero from an utterance's own ``frames(l) = (l - 400) // 320 + 1`` on.  ``layer=-1`` is the last hidden state (behind the encoder's
+    ``layer_norm``), ``layer=k`` in 0 .. N - 1 the library's ``hidden_states[k]``; layers k and above are then not run.
+
+    ``normalize`` (default on): every utterance is first brought to zero mean and unit variance over its own samples,
+    ``(x - mean) / sqrt(var + norm_eps)`` with the population variance, inside the first kernel's reads.  ``norm_eps`` defaults to 1e-7, the
+    constant of the library's ``Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm``.  The reference's s3prl pipeline normalises with
+    ``F.layer_norm`` over the waveform, whose eps is 1e-5 as far as is known here — s3prl is not on hand to check — so it is a field.
+
+    ``config``: a mapping with the keys of the model's ``config.json`` (missing keys: the large model's).  Not built, refused at
+    construction: group-norm extractors and post-LN encoders (HuBERT-base), WavLM's gated relative position bias, adapters, head sizes other
+    than 64; ``masked_spec_embed`` is held for ``strict=True`` and never used (spec-augment is a training device)."""
+
+    _PREFIX = "hificar_hubert"
+    _NAME = "HuBERT"
+    sampling_rate = 16000
+
+    def __init__(self, config=None, normalize=True, norm_eps=1e-7):
+        super().__init__()
+        c = _native.check_hubert_config(dict(config or {}))
+        self.config = c
+        self.normalize, self.norm_eps = bool(normalize), float(norm_eps)
+        C, H, I = c["conv_dim"][0], c["hidden_size"], c["intermediate_size"]
+        LN, Lin = torch.nn.LayerNorm, torch.nn.Linear
+        if c["mask_time_prob"] > 0.0 or c["mask_feature_prob"] > 0.0:  # (as the library decides; never read)
+            self.masked_spec_embed = torch.nn.Parameter(torch.rand(H))
+        self.feature_extractor = _Holder(conv_layers=torch.nn.ModuleList(
+            _Holder(conv=torch.nn.Conv1d(1 if i == 0 else C, C, k, stride=s, bias=bool(c["conv_bias"])), layer_norm=LN(C))
+            for i, (k, s) in enumerate(zip(_native.HUBERT_CONV_KERNEL, _native.HUBERT_CONV_STRIDE))))
+        self.feature_projection = _Holder(layer_norm=LN(C, eps=c["layer_norm_eps"]), projection=Lin(C, H))
+        # the positional conv under the names torch.nn.utils.parametrizations.weight_norm(conv, dim=2) gives it (original0: g, original1: v),
+        # as plain holders: a parametrized module cannot be pickled
+        K, G = _native.HUBERT_POS_TAPS, H // _native.HUBERT_POS_GROUPS
+        wn = _Holder()
+        bound = (G * K) ** -0.5
+        wn.original1 = torch.nn.Parameter(torch.empty(H, G, K).uniform_(-bound, bound))
+        wn.original0 = torch.nn.Parameter(wn.original1.detach().pow(2).sum((0, 1), keepdim=True).sqrt())
+        wn._parameters = {k: wn._parameters[k] for k in ("original0", "original1")}  # (the library's order)
+        pos = _Holder()
+        pos.bias = torch.nn.Parameter(torch.empty(H).uniform_(-bound, bound))
+        pos.parametrizations = _Holder(weight=wn)
+        self.encoder = _Holder(pos_conv_embed=_Holder(conv=pos), layer_norm=LN(H, eps=c["layer_norm_eps"]), layers=torch.nn.ModuleList(
+            _Holder(attention=_Holder(k_proj=Lin(H, H), v_proj=Lin(H, H), q_proj=Lin(H, H), out_proj=Lin(H, H)), layer_norm=LN(H, eps=c["layer_norm_eps"]),
+                    feed_forward=_Holder(intermediate_dense=Lin(H, I), output_dense=Lin(I, H)), final_layer_norm=LN(H, eps=c["layer_norm_eps"]))
+            for _ in range(c["num_hidden_layers"])))
+        self._params = {"in_channels": 1, "out_channels": H}
+        self._init_native()
+        self.eval()
+
+    # ------------------------------------------------------------------ what NativeFeatureModel asks of a model
+    def _device(self):
+        return self.encoder.layer_norm.weight.device
+
+    def _make_config(self):
+        return _native.make_hubert_config(self.config, self.normalize, self.norm_eps)
+
+    def _batch_norms(self):
+        return []
+
+    def native_state(self):
+        """{name as hificar_hubert_set_weight takes it: fp32 CPU tensor}: the state_dict without masked_spec_embed, the positional conv's
+        weight norm under its old names."""
+        out = {}
+        for k, v in self.state_dict().items():
+            if k == "masked_spec_embed":
+                continue
+            k = k.replace("parametrizations.weight.original0", "weight_g").replace("parametrizations.weight.original1", "weight_v")
+            out[k] = v.detach().float().cpu().contiguous()
+        return out
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """``HubertModel``'s keys; ``encoder.pos_conv_embed.conv.weight_g`` / ``weight_v`` are taken for the parametrized names."""
+        p = "encoder.pos_conv_embed.conv."
+        sd = {(p + _WEIGHT_NORM_OLD[k[len(p):]] if k.startswith(p) and k[len(p):] in _WEIGHT_NORM_OLD else k): v for k, v in state_dict.items()}
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("HuBERT: training (dropout, spec-augment, layerdrop, a backward pass) is not built; the module is inference-only")
+        return super().train(False)
+
+    @classmethod
+    def from_pretrained(cls, directory, normalize=True, norm_eps=1e-7):
+        """A model from a directory in the ``transformers`` layout: ``config.json`` and ``model.safetensors`` (when ``safetensors`` imports) or
+        ``pytorch_model.bin``.  fairseq and s3prl checkpoints are refused: neither layout could be checked against its package here."""
+        import json
+        import os
+
+        with open(os.path.join(directory, "config.json")) as f:
+            config = json.load(f)
+        model = cls(config, normalize=normalize, norm_eps=norm_eps)
+        st_path, bin_path = os.path.join(directory, "model.safetensors"), os.path.join(directory, "pytorch_model.bin")
+        sd = None
+        if os.path.exists(st_path):
+            try:
+                from safetensors.torch import load_file
+            except ImportError:
+                load_file = None
+            if load_file is not None:
+                sd = load_file(st_path)
+        if sd is None:
+            if not os.path.exists(bin_path):
+                raise FileNotFoundError(f"{directory}: neither pytorch_model.bin nor a readable model.safetensors")
+            sd = torch.load(bin_path, map_location="cpu", weights_only=True)
+        if not isinstance(sd, dict) or any(k in sd for k in ("model", "cfg", "args", "Upstream", "Config")) or \
+                any(isinstance(k, str) and (".self_attn." in k or k.startswith("w2v_encoder.")) for k in sd):
+            raise NotImplementedError(f"{directory}: a fairseq / s3prl checkpoint layout; only the transformers layout (HubertModel's keys) is read")
+        model.load_state_dict(sd, strict=True)
+        return model
+
+    @staticmethod
+    def frames(length):
+        """Frames of an utterance of ``length`` samples: ``(length - 400) // 320 + 1``; ValueError under 400 samples."""
+        return _native.hubert_frames(length)
+
+    def debug_tap(self, name, dst):
+        """Test aid (hificar_hubert_debug_tap): the following forwards copy the named intermediate into ``dst`` (a float32 device tensor)."""
+        handle = self._native_handle()
+        self._call("_debug_tap", handle, name.encode() if name is not None else None, None if dst is None else dst.data_ptr(),
+                   0 if dst is None else dst.numel())
+
+    def workspace_bytes(self, B, L):
+        """Bytes of device scratch a forward of B utterances of at most L samples takes (hificar_hubert_workspace_bytes; needs the handle)."""
+        return int(self._fn("_workspace_bytes")(self._native_handle(), B, L))
+
+    def forward(self, wav, lengths=None, layer=-1):
+        """wav: (B, L) or (L,) float tensor on the device; lengths: B sample counts in 400 .. L, or None (every utterance has L); layer: -1 or
+        0 .. N - 1.  Returns (feats (B, hidden_size, Tmax) float32, frames (B,) int32 on the device)."""
+        name = self._NAME
+        if not isinstance(wav, torch.Tensor) or wav.device.type != "cuda":
+            raise RuntimeError(f"{name} needs a CUDA/HIP tensor; there is no CPU fallback")
+        if wav.requires_grad:
+            raise RuntimeError(f"{name}: wav requires grad, and no backward through the encoder is built (detach it)")
+        if wav.dim() not in (1, 2) or not wav.is_floating_point():
+            raise RuntimeError(f"{name}: expected a (B, L) or (L,) float tensor, got {tuple(wav.shape)} {wav.dtype}")
+        n_layers = self.config["num_hidden_layers"]
+        if isinstance(layer, bool) or not isinstance(layer, int) or not -1 <= layer < n_layers:
+            raise ValueError(f"{name}: layer must be -1 or in 0 .. {n_layers - 1}, got {layer!r}")
+        y = wav.reshape(1, -1) if wav.dim() == 1 else wav
+        y = y.detach().to(torch.float32).contiguous()
+        B, L = y.shape
+        if B < 1:
+            raise RuntimeError(f"{name}: empty batch {tuple(wav.shape)}")
+        T = self.frames(L)
+        lens = (None, None)
+        keep = None
+        if lengths is not None:
+            host = lengths.detach().to("cpu", torch.int32) if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths, dtype=torch.int32)
+            host = host.reshape(-1).contiguous()
+            if host.numel() != B:
+                raise RuntimeError(f"{name}: lengths has {host.numel()} entries for a batch of {B}")
+            if int(host.max()) > L:
+                raise RuntimeError(f"{name}: lengths must lie in [{_native.HUBERT_MIN_SAMPLES}, {L}]")
+            self.frames(int(host.min()))
+            keep = (host, host.to(y.device))
+            lens = (keep[1].data_ptr(), keep[0].data_ptr())
+            frames = torch.div(keep[1] - 400, 320, rounding_mode="floor").to(torch.int32) + 1
+        else:
+            frames = torch.full((B,), T, dtype=torch.int32, device=y.device)
+        handle = self._native_handle()
+        if y.device != self._device():
+            raise RuntimeError(f"{name}: input on {y.device}, parameters on {self._device()}")
+        with torch.cuda.device(y.device):
+            n = int(self._fn("_workspace_bytes")(handle, B, L))
+            if n == 0:
+                raise RuntimeError(f"{name}: B={B}, L={L} out of range (B <= 65535, B frames max(3 hidden, intermediate) < 2^31)")
+            ws_ptr, ws_bytes = self._scratch("_workspace_buf", n)
+            out = torch.empty((B, self.config["hidden_size"], T), dtype=torch.float32, device=y.device)
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            self._call("_forward", handle, y.data_ptr(), lens[0], lens[1], out.data_ptr(), B, L, layer, ws_ptr, ws_bytes, stream)
+        del keep
+        return out, frames
+
+    def forward_lowrate(self, *a, **kw):
+        raise NotImplementedError("HuBERT has no low-rate front end: it IS the front end (its output goes into a model's forward_lowrate)")

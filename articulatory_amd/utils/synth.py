@@ -638,3 +638,76 @@ def synth_transformer_state_dict(params: dict, seed: int = 1234, gain: float = 1
         else:
             out[name] = uniform(seed, name, shape, -0.05, 0.05)
     return out
+
+
+# ---- HuBERT ("large" family) ----------------------------------------------------------------------------------------------------------
+HUBERT_CONV_KERNEL = (10, 3, 3, 3, 3, 2, 2)
+HUBERT_CONV_STRIDE = (5, 2, 2, 2, 2, 2, 2)
+
+
+def hubert_param_spec(config):
+    """Ordered {state_dict key: shape} of the ``transformers`` library's ``HubertModel`` for a "large"-family configuration (layer-norm
+    extractor, stable layer norm, weight-normed positional conv in its parametrized form); ``config``: a mapping with the keys of its
+    ``config.json``.  ``masked_spec_embed`` exists when the configuration's mask probabilities say so, as in the library.  Checked
+    key-for-key against the real class by tools/make_golden_hubert.py (tests/golden/gold_hubert_keys.txt)."""
+    spec = OrderedDict()
+    dims = list(config.get("conv_dim", (512,) * 7))
+    kernels = list(config.get("conv_kernel", HUBERT_CONV_KERNEL))
+    H, I = config.get("hidden_size", 1024), config.get("intermediate_size", 4096)
+    taps, groups = config.get("num_conv_pos_embeddings", 128), config.get("num_conv_pos_embedding_groups", 16)
+    if config.get("mask_time_prob", 0.05) > 0.0 or config.get("mask_feature_prob", 0.0) > 0.0:
+        spec["masked_spec_embed"] = (H,)
+    for i, (c, k) in enumerate(zip(dims, kernels)):
+        b = f"feature_extractor.conv_layers.{i}"
+        spec[b + ".conv.weight"] = (c, 1 if i == 0 else dims[i - 1], k)
+        if config.get("conv_bias", True):
+            spec[b + ".conv.bias"] = (c,)
+        spec[b + ".layer_norm.weight"] = (c,)
+        spec[b + ".layer_norm.bias"] = (c,)
+    spec["feature_projection.layer_norm.weight"] = (dims[-1],)
+    spec["feature_projection.layer_norm.bias"] = (dims[-1],)
+    spec["feature_projection.projection.weight"] = (H, dims[-1])
+    spec["feature_projection.projection.bias"] = (H,)
+    spec["encoder.pos_conv_embed.conv.bias"] = (H,)
+    spec["encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = (1, 1, taps)
+    spec["encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = (H, H // groups, taps)
+    spec["encoder.layer_norm.weight"] = (H,)
+    spec["encoder.layer_norm.bias"] = (H,)
+    for l in range(config.get("num_hidden_layers", 24)):
+        b = f"encoder.layers.{l}"
+        for w in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            spec[f"{b}.attention.{w}.weight"] = (H, H)
+            spec[f"{b}.attention.{w}.bias"] = (H,)
+        spec[b + ".layer_norm.weight"] = (H,)
+        spec[b + ".layer_norm.bias"] = (H,)
+        spec[b + ".feed_forward.intermediate_dense.weight"] = (I, H)
+        spec[b + ".feed_forward.intermediate_dense.bias"] = (I,)
+        spec[b + ".feed_forward.output_dense.weight"] = (H, I)
+        spec[b + ".feed_forward.output_dense.bias"] = (H,)
+        spec[b + ".final_layer_norm.weight"] = (H,)
+        spec[b + ".final_layer_norm.bias"] = (H,)
+    return spec
+
+
+def synth_hubert_state_dict(config, seed: int = 1234, gain: float = 1.0) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic ``HubertModel``-layout state_dict from the name-keyed generator of the other specs: matrices and conv kernels
+    U(+-gain * sqrt(3 / fan_in)), biases U(+-0.05), layer norms away from the identity (weight in [0.8, 1.2], bias in +-0.3), the
+    positional conv's weight_g (original0) in [0.5, 1.5] * sqrt(hidden_size / 128) — each tap's kernel is g v / ||v|| over ALL its
+    hidden x group elements — and masked_spec_embed in [0, 1) as the library draws it."""
+    out = OrderedDict()
+    H = config.get("hidden_size", 1024)
+    for name, shape in hubert_param_spec(config).items():
+        leaf = name.rsplit(".", 1)[-1]
+        if name == "masked_spec_embed":
+            out[name] = uniform(seed, name, shape, 0.0, 1.0)
+        elif "layer_norm" in name:
+            out[name] = uniform(seed, name, shape, 0.8, 1.2) if leaf == "weight" else uniform(seed, name, shape, -0.3, 0.3)
+        elif leaf == "original0":
+            s = float(np.sqrt(H / 128.0))
+            out[name] = uniform(seed, name, shape, 0.5 * s, 1.5 * s)
+        elif len(shape) >= 2:
+            b = gain * np.sqrt(3.0 / int(np.prod(shape[1:])))
+            out[name] = uniform(seed, name, shape, -b, b)
+        else:
+            out[name] = uniform(seed, name, shape, -0.05, 0.05)
+    return out

@@ -88,7 +88,7 @@ extern "C" {
 
 typedef struct hificar_handle hificar_handle;
 /* The conv engine every model of the library launches through (plans, schedules, stream ordering, profiling).  A generator handle
- * has one (hificar_engine_of), so do the discriminators (hificar_disc_engine), the BiGRU (hificar_bigru_engine), the Transformer (hificar_xfmr_engine) and the speech features (hificar_feat_engine); it lives and
+ * has one (hificar_engine_of), so do the discriminators (hificar_disc_engine), the BiGRU (hificar_bigru_engine), the Transformer (hificar_xfmr_engine), the speech features (hificar_feat_engine) and the HuBERT encoder (hificar_hubert_engine); it lives and
  * dies with its model.  Only the profiling calls take it: the generator's entry points do not accept another model's engine. */
 typedef struct hificar_engine hificar_engine;
 
@@ -1024,6 +1024,93 @@ int hificar_xfmr_forward_train_packed(hificar_xfmr* h, const float* x, const int
  * and the tape stays usable for the right call.  A tape is known by its address: one copied elsewhere is not recognised. */
 int hificar_xfmr_backward_packed(hificar_xfmr* h, const float* dout, const int32_t* lengths_host, int B, int T, const void* tape, size_t tape_bytes,
                                  float* grads, float* dx, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Speech representation: the HuBERT encoder of the "large" family (the published architecture as the `transformers` library's
+ * HubertModel states it with feat_extract_norm = "layer", do_stable_layer_norm = True, feat_proj_layer_norm = True), waveforms at 16 kHz ->
+ * hidden states at 50 Hz, the front end of the reference's SSL inversion models (egs/ema/voc1/local/predict_ema.py puts hubert_large_ll60k's
+ * last hidden state, stretched by 4, in front of the BiGRU).  Inference only, exact fp32.
+ *   normalisation  per utterance (x - mean) / sqrt(var + norm_eps) over its own samples, population variance, applied as layer 0 reads
+ *   extractor      seven Conv1d (kernels 10, 3, 3, 3, 3, 2, 2; strides 5, 2, 2, 2, 2, 2, 2; conv_dim channels), each + LayerNorm over channels
+ *                  (eps 1e-5) + GELU (erf): layer 0 in a kernel of its own, layers 1 - 6 on the conv engine as stride-1 convs over rows of two
+ *                  positions, in sub-batches of utterances (the workspace holds a sub-batch's layer-0 rows, never the batch's)
+ *   projection     LayerNorm(conv_dim) + Linear(conv_dim, hidden_size)
+ *   positional     Conv1d(hidden, hidden, 128, padding 64, groups 16) without its last frame, + bias, GELU, added to the stream
+ *   layers         x += W_o attn(LN(x)); x += W_2 GELU(W_1 LN(x)); heads of 64 channels, full softmax attention over the utterance's own frames
+ *   output         layer = -1: LayerNorm of the last layer's stream (last_hidden_state); layer = k in 0 .. N - 1: the stream in front of
+ *                  layer k (hidden_states[k] of output_hidden_states = True); layers k and above are then not run
+ * Limits: conv_dim a multiple of 32 in 32 .. HIFICAR_HUBERT_MAX_CONV; hidden_size one of 128, 256, 512, 768, 1024 (16 positional groups of 8 ..
+ * 64 channels, LayerNorm rows of at most 1024); num_attention_heads = hidden_size / 64; intermediate_size a multiple of 32 in 32 ..
+ * HIFICAR_HUBERT_MAX_FFN; 1 .. HIFICAR_HUBERT_MAX_LAYERS layers.  Not built (the binding refuses them): group-norm extractors, post-LN encoders,
+ * gated relative position bias, training, dropout, spec-augment.
+ * Every utterance of a batch is computed as if alone, bit for bit: the conv engine runs with split-K off, every other sum has one order.
+ * --------------------------------------------------------------------------------------------------------------------------- */
+#define HIFICAR_HUBERT_MAX_CONV 1024
+#define HIFICAR_HUBERT_MAX_HIDDEN 1024
+#define HIFICAR_HUBERT_MAX_FFN 8192
+#define HIFICAR_HUBERT_MAX_LAYERS 48
+#define HIFICAR_HUBERT_HEAD_DIM 64
+#define HIFICAR_HUBERT_MIN_SAMPLES 400
+
+typedef struct hificar_hubert_config {
+    int32_t conv_dim;            /* every extractor layer's channels */
+    int32_t hidden_size;
+    int32_t num_hidden_layers;
+    int32_t num_attention_heads; /* hidden_size / 64 */
+    int32_t intermediate_size;
+    int32_t conv_bias;           /* the extractor convs have biases */
+    int32_t normalize;           /* per-utterance waveform normalisation in front of layer 0 */
+    float layer_norm_eps;        /* every LayerNorm but the extractor's (1e-5 there, torch.nn.LayerNorm's default) */
+    float norm_eps;              /* the waveform normalisation's eps */
+} hificar_hubert_config;
+
+typedef struct hificar_hubert hificar_hubert;
+
+/* An empty model for this configuration.  Touches no device. */
+int hificar_hubert_create(const hificar_hubert_config* cfg, hificar_hubert** out);
+
+/* One tensor by its HubertModel state_dict name: "feature_extractor.conv_layers.<i>.conv.weight" (C, 1 | C, k), ".conv.bias" (conv_bias),
+ * ".layer_norm.weight" / ".bias"; "feature_projection.layer_norm.*" (C), "feature_projection.projection.weight" (H, C), ".bias";
+ * "encoder.pos_conv_embed.conv.weight_g" (1, 1, 128), ".weight_v" (H, H / 16, 128) — the weight norm over dim 2, folded in double by
+ * hificar_hubert_finalize — and ".bias"; "encoder.layer_norm.*"; per layer "encoder.layers.<l>.attention.{q,k,v,out}_proj.weight" (H, H) / ".bias",
+ * ".layer_norm.*", ".feed_forward.intermediate_dense.weight" (I, H) / ".bias", ".feed_forward.output_dense.weight" (H, I) / ".bias",
+ * ".final_layer_norm.*".  data: HOST pointer to contiguous fp32; the caller keeps ownership. */
+int hificar_hubert_set_weight(hificar_hubert* h, const char* name, const float* data, const int64_t* shape, int ndim);
+
+/* Checks that every tensor arrived, folds the weight norm, re-lays the strided convs' weights as windows of two positions, packs q | k | v
+ * as one GEMM, uploads.  Synchronises the device once. */
+int hificar_hubert_finalize(hificar_hubert* h);
+
+/* Frames of an utterance of L samples: (L - 400) / 320 + 1 (integer division); 0 for L < 400. */
+int hificar_hubert_frames(const hificar_hubert* h, int L);
+
+/* Bytes of device scratch hificar_hubert_forward needs for B utterances of at most L samples; 0: the shape is refused.  The extractor runs
+ * over sub-batches of utterances whose layer-0 rows take at most 512 MiB (one utterance's, if those are more), so the figure grows with B
+ * by the 50-Hz rows only: conv_dim + 4 hidden_size + max(3 hidden_size, intermediate_size) floats per frame. */
+size_t hificar_hubert_workspace_bytes(const hificar_hubert* h, int B, int L);
+
+/* wav (B, L) device fp32, zero-padded; lengths: DEVICE int32[B] sample counts or NULL (every utterance has L); lengths_host: the same on the
+ * host or NULL — given, every entry is checked (400 <= l <= L) before anything is enqueued; not given, a length is clamped into 0 .. L and an
+ * utterance under 400 samples has no frames.  out: (B, hidden_size, Tmax), Tmax = hificar_hubert_frames(h, L), exactly zero from an
+ * utterance's own frame count on.  layer: -1 or 0 .. num_hidden_layers - 1 (above).  workspace: 256-byte aligned,
+ * hificar_hubert_workspace_bytes(h, B, L) bytes; what it holds on entry does not matter.  L < 400: HIFICAR_E_INVALID. */
+int hificar_hubert_forward(hificar_hubert* h, const float* wav, const int32_t* lengths, const int32_t* lengths_host, float* out, int B, int L,
+                           int layer, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Test aid: the following forwards also copy the named intermediate into dst (device, `capacity` floats).  Names: "extractor.0" (B, T0,
+ * conv_dim) with T0 = (L - 10) / 5 + 1, "extract_features" (B, Tmax, conv_dim: extractor layer 6's output), "feature_projection", "pos_conv"
+ * (GELU(conv + bias) alone) and "layers.<l>" (the stream behind layer l), each (B, Tmax, hidden_size).  Rows past an utterance's frames hold
+ * whatever the workspace held.  name = NULL forgets every tap, dst = NULL that one. */
+int hificar_hubert_debug_tap(hificar_hubert* h, const char* name, float* dst, size_t capacity);
+
+/* Test aid: the extractor's sub-batches hold `utterances` utterances (0: as many as the 512-MiB budget allows, the default) from the next
+ * hificar_hubert_workspace_bytes / hificar_hubert_forward on.  Results do not depend on it. */
+int hificar_hubert_debug_sub_batch(hificar_hubert* h, int utterances);
+
+/* The model's engine, for hificar_profile_begin / hificar_profile_end. */
+hificar_engine* hificar_hubert_engine(hificar_hubert* h);
+
+void hificar_hubert_destroy(hificar_hubert* h);
 
 #ifdef __cplusplus
 }
