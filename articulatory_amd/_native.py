@@ -174,8 +174,10 @@ SYMBOLS = tuple(PROTOTYPES)
 PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}  # the inference arithmetics (``precision=``)
 # ... and the Transformer's training arithmetics (``train_precision=``): bf16x3w = bf16x3 with the one-tap weight gradients in it too
 TRAIN_PRECISIONS = dict(PRECISIONS, bf16x3w=PREC_BF16X3W)
-# the Transformer's inference arithmetics: bf16x3a is bf16x3 with the attention's products on bf16 MFMAs too (no other model takes it)
+# the Transformer's inference arithmetics: bf16x3a is bf16x3 with the attention's products on bf16 MFMAs too
 XFMR_PRECISIONS = dict(PRECISIONS, bf16x3a=PREC_BF16X3A)
+# the HuBERT encoder's (features.HuBERT): the same three names, defined as for the Transformer
+HUBERT_PRECISIONS = dict(PRECISIONS, bf16x3a=PREC_BF16X3A)
 # the Transformer's training arithmetics with bf16x3wa: bf16x3w with the attention's query-tiled kernels (forward, backward-q) on bf16 MFMAs too
 XFMR_TRAIN_PRECISIONS = dict(TRAIN_PRECISIONS, bf16x3wa=PREC_BF16X3WA)
 # ... and with bf16x3wac: bf16x3wa with the weight gradients of the wide k = 3 ResBlock convs on bf16 MFMAs too (what ``train_precision=`` accepted before bf16x3wack)

@@ -4,7 +4,8 @@
     python -m articulatory_amd.bin.predict_ema MODEL_DIR FEATS OUTDIR [--interp-factor N] [--zscore | --no-zscore] [--batch-size N]
                                                [--precision P] [--dry-run]
     python -m articulatory_amd.bin.predict_ema MODEL_DIR WAVS OUTDIR --from-wav [--hop-length N] [...]
-    python -m articulatory_amd.bin.predict_ema MODEL_h2_DIR WAVS OUTDIR --from-wav --ssl-model HUBERT_DIR [--ssl-layer N] [...]
+    python -m articulatory_amd.bin.predict_ema MODEL_h2_DIR WAVS OUTDIR --from-wav --ssl-model HUBERT_DIR [--ssl-layer N]
+                                               [--ssl-precision P] [...]
 
 ``MODEL_DIR`` holds ``best_mel_ckpt.pkl`` and ``config.yml`` (predict_ema.py:54-55; what ``InversionTrainer`` writes).  ``FEATS`` is a directory
 of ``<utt>.npy`` files, each (frames, channels) — the speech model's last hidden states, or the MFCC matrix transposed — or a kaldi-style scp
@@ -26,6 +27,8 @@ For a directory with ``_h2`` in its name — the SSL models, in front of which t
 50 Hz, stretched by 4) — ``--from-wav`` needs ``--ssl-model DIR``: a HuBERT model of the large family in the ``transformers`` layout
 (``config.json`` + ``model.safetensors`` | ``pytorch_model.bin``), run on the device by ``articulatory_amd.features.HuBERT`` in front of
 ``forward_lowrate`` with the directory's factor and no z-score.  ``--ssl-layer N`` takes ``hidden_states[N]`` instead of the last hidden state.
+``--ssl-precision {f32,bf16x3,bf16x3a}`` sets the encoder's arithmetic (``HuBERT(precision=)``; default f32); ``--precision`` stays the
+inversion model's.
 Every wav must be 16 kHz (the reference's ``linear_inference.py`` asserts the same; nothing is resampled) and at least 400 samples long; a
 file that is not is a ValueError naming it.  Utterances are batched by length, each computed as if alone: any ``--batch-size`` writes the same
 bytes.  ``--dry-run`` reads ``config.json`` alone.  Without ``--ssl-model`` such a directory is refused: SSL extraction is not built into the
@@ -141,6 +144,8 @@ def get_parser():
                              "pytorch_model.bin): with --from-wav and a model directory with _h2 in its name, its hidden states are the features")
     parser.add_argument("--ssl-layer", type=int, default=None,
                         help="with --ssl-model: take hidden_states[N] (0 .. layers - 1) instead of the last hidden state")
+    parser.add_argument("--ssl-precision", default=None, choices=("f32", "bf16x3", "bf16x3a"),
+                        help="with --ssl-model: arithmetic of the HuBERT encoder's GEMMs (bf16x3a: and of its attention); default: f32")
     z = parser.add_mutually_exclusive_group()
     z.add_argument("--zscore", dest="zscore", action="store_true", default=None,
                    help="normalise every utterance by the mean and standard deviation of all its elements (default without _h2 in the name)")
@@ -263,6 +268,8 @@ def main(argv=None):
         raise ValueError("--ssl-model belongs to --from-wav with a model directory with _h2 in its name")
     if args.ssl_layer is not None and args.ssl_model is None:
         raise ValueError("--ssl-layer belongs to --ssl-model")
+    if args.ssl_precision is not None and args.ssl_model is None:
+        raise ValueError("--ssl-precision belongs to --ssl-model")
     if args.hop_length is not None and args.ssl_model is not None:
         raise ValueError("--hop-length belongs to the MFCC extraction, not to --ssl-model")
     if args.hop_length is not None and not args.from_wav:
@@ -289,6 +296,7 @@ def main(argv=None):
         print(json.dumps({"model_dir": args.model_dir, "checkpoint": checkpoint, "generator_type": config.get("generator_type"),
                           "interp_factor": factor, "zscore": bool(zscore), "batch_size": args.batch_size, "precision": args.precision or "f32",
                           "front_end": "hubert", "ssl_model": args.ssl_model, "ssl_layer": -1 if args.ssl_layer is None else args.ssl_layer,
+                          "ssl_precision": args.ssl_precision or "f32",
                           "hidden_size": ssl_config["hidden_size"], "num_hidden_layers": ssl_config["num_hidden_layers"],
                           "rates": [SSL_RATE], "utterances": [u for u, _ in pairs],
                           "samples": int(sum(info[p][1] for _, p in pairs)),
@@ -329,7 +337,7 @@ def main(argv=None):
         width = config.get("generator_params", {}).get("in_channels")
         if width is not None and width != ssl_config["hidden_size"]:
             raise ValueError(f"--ssl-model: hidden_size {ssl_config['hidden_size']} does not match the model's in_channels {width}")
-        hubert = HuBERT.from_pretrained(args.ssl_model).to(device)
+        hubert = HuBERT.from_pretrained(args.ssl_model, precision=args.ssl_precision or "f32").to(device)
         logging.info(f"Loaded the speech model from {args.ssl_model}.")
         n = predict_ssl(model, hubert, pairs, args.outdir, device, interp_factor=factor, zscore=zscore, batch_size=args.batch_size,
                         layer=-1 if args.ssl_layer is None else args.ssl_layer)

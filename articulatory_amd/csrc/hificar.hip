@@ -17,6 +17,7 @@
 #include "hificar_xfmr_attn16_train_k.hip.h"
 #include "hificar_xfmr_wgrad16.hip.h"
 #include "hificar_hubert_kernels.hip.h"
+#include "hificar_hubert_attn16.hip.h"
 
 #include "../../include/hificar.h"
 

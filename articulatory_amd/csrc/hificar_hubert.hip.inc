@@ -14,6 +14,23 @@
 // garbage formed from the zero padding — are never read by a valid row (a zero-weight slot reads at most the finite slack row).  It runs over
 // sub-batches of utterances, so the workspace never holds a whole batch's layer-0 rows.  Everything behind it runs under the ragged context
 // (frames per utterance): rows at or past a sequence's frames read as zeros in the GEMMs and are never written.  Exact fp32, split-K off.
+//
+// bf16x3 (hificar_hubert_set_precision, inference only): every GEMM on the conv engine — extractor layers 1 - 6, the projection, q | k | v,
+// out_proj, intermediate_dense, output_dense — runs in the engine's bf16x3 kernels, whose input is "split rows" [hi: C bf16 | lo: C bf16]
+// (4 C bytes per row, as fp32 rows) written by whatever produces it; there is no split pass of its own:
+//   hubert_conv0_kernel<true>          split WINDOW rows [hi: 2 C | lo: 2 C] of two positions, layer 1's operand, in ws.ea
+//   hubert_ln_kernel<true, true>       behind layers 1 - 5: conv i reads ws.ea and writes fp32 rows to ws.eb; the LayerNorm + GELU reads ws.eb and
+//                                      writes layer i + 1's split window rows back into ws.ea (P[i] <= P[i - 1]: it fits; a position's bytes
+//                                      interleave with its neighbour's, so the pass cannot be in place).  Behind layer 6: fp32, as ever
+//   hubert_ln_kernel<false, true>      the projection's LayerNorm (in place over ws.feat) and the two per layer: split rows only — no later
+//                                      kernel reads those rows as fp32
+//   hubert_attn_kernel<64, true>       split rows for out_proj
+//   hubert_gelu_split_kernel           split rows of GELU(W_1 n + b), in place over the wide buffer: one workgroup holds a row
+// The waveform statistics, layer 0, every LayerNorm and GELU, the positional conv, the attention, biases, residual adds and the residual
+// stream stay fp32.  No buffer grows: a split row takes its fp32 row's bytes.  The tap "extractor.0" exists as split rows only.
+//
+// bf16x3a (HIFICAR_PREC_BF16X3A): bf16x3 with the attention's two products on bf16 MFMAs too (hificar_hubert_attn16.hip.h).  The q | k | v
+// GEMM writes split rows only ([hi: 3 H bf16 | lo: 3 H bf16], the bytes of the fp32 row).  The conv engine sees a bf16x3 handle.
 
 constexpr int kHubExtLayers = 7;
 static const int kHubExtK[kHubExtLayers] = {10, 3, 3, 3, 3, 2, 2};
@@ -39,6 +56,7 @@ struct hificar_hubert {
     float* d_enc_ln[2] = {nullptr, nullptr};
     float* d_pos_w = nullptr;  // hubert_posconv_kernel's lane-ordered weights
     float* d_pos_b = nullptr;
+    int precision = HIFICAR_PREC_F32;  // hificar_hubert_set_precision: which fragments finalize packs and which kernels the forward launches
     bool finalized = false;
     int sub_batch = 0;  // hificar_hubert_debug_sub_batch: utterances per extractor sub-batch (0: by kHubExtBudget)
     struct Tap {
@@ -59,6 +77,9 @@ static bool hubert_dims(int L, HubertDims* d) {
     for (int i = 0; i < kHubExtLayers; ++i) d->P[i] = i + 1 < kHubExtLayers ? round_up(d->T[i], 2) : d->T[i];
     return true;
 }
+
+// the handle's GEMMs run in the engine's bf16x3 kernels (bf16x3 and bf16x3a differ in the attention alone)
+static bool hubert_x3(const hificar_hubert* g) { return g->precision != HIFICAR_PREC_F32; }
 
 static bool hubert_pos_group_built(int G) { return G == 8 || G == 16 || G == 32 || G == 48 || G == 64; }
 
@@ -186,6 +207,17 @@ extern "C" int hificar_hubert_set_weight(hificar_hubert* g, const char* name, co
     return HIFICAR_OK;
 }
 
+extern "C" int hificar_hubert_set_precision(hificar_hubert* g, int precision) {
+    if (!g) return fail(HIFICAR_E_INVALID, "hificar_hubert_set_precision: null handle");
+    if (precision != HIFICAR_PREC_F32 && precision != HIFICAR_PREC_BF16X3 && precision != HIFICAR_PREC_BF16X3A)
+        return fail(HIFICAR_E_INVALID, "unknown precision %d", precision);
+    if (g->finalized)
+        return fail(HIFICAR_E_STATE, "hificar_hubert_set_precision after hificar_hubert_finalize: the weights are packed for %s only; make a new handle",
+                    xfmr_precision_name(g->precision));
+    g->precision = precision;
+    return HIFICAR_OK;
+}
+
 extern "C" int hificar_hubert_finalize(hificar_hubert* g) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_hubert_finalize: null handle");
     if (g->finalized) return HIFICAR_OK;
@@ -194,7 +226,8 @@ extern "C" int hificar_hubert_finalize(hificar_hubert* g) {
     hificar_engine* h = &g->eng;
     const int C = g->cfg.conv_dim, H = g->cfg.hidden_size, G = H / kHubPosGroups;
     int rc;
-    h->precision = HIFICAR_PREC_F32;  // (xfmr_pack goes by it)
+    const bool x3 = hubert_x3(g);
+    h->precision = x3 ? HIFICAR_PREC_BF16X3 : HIFICAR_PREC_F32;  // (xfmr_pack goes by it)
     auto vec = [&](const std::string& name) -> const std::vector<float>& { return g->tensors.at(name).data; };
     const std::vector<float> zeros_c((size_t)C, 0.f);
     for (int i = 0; i < kHubExtLayers; ++i) {
@@ -273,15 +306,18 @@ extern "C" int hificar_hubert_finalize(hificar_hubert* g) {
         for (const char* n : {"layer_norm.weight", "layer_norm.bias", "final_layer_norm.weight", "final_layer_norm.bias"})
             if ((rc = upload(h, vec(b + n), &E.d_ln[i++])) != HIFICAR_OK) return rc;
     }
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&hubert_attn_kernel<kHubHeadDim>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)HubertAttnLds<kHubHeadDim>::bytes));
+    if (g->precision == HIFICAR_PREC_BF16X3A) HIP_TRY(hubert_attn16_attr<kHubHeadDim>());
+    else
+        HIP_TRY(hipFuncSetAttribute(x3 ? reinterpret_cast<const void*>(&hubert_attn_kernel<kHubHeadDim, true>)
+                                       : reinterpret_cast<const void*>(&hubert_attn_kernel<kHubHeadDim>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)HubertAttnLds<kHubHeadDim>::bytes));
     HIP_TRY(hubert_by_group(G, [](auto Gc) {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(&hubert_posconv_kernel<Gc()>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)HubertPosLds<Gc()>::bytes);
     }));
     // the engine opens here, not in hificar_hubert_create: a handle can be created and described without a device
     if ((rc = engine_open(h, true)) != HIFICAR_OK) return rc;
-    h->precision = HIFICAR_PREC_F32;
+    h->precision = x3 ? HIFICAR_PREC_BF16X3 : HIFICAR_PREC_F32;
     h->use_pair = false;
     h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's states do not depend on what it is batched with
     HIP_TRY(hipDeviceSynchronize());
@@ -290,12 +326,13 @@ extern "C" int hificar_hubert_finalize(hificar_hubert* g) {
     return HIFICAR_OK;
 }
 
+// (bf16x3: the same buffers and bytes — a split row takes its fp32 row's bytes)
 struct HubertWorkspace {
     double* stats;  // [B][mean, rstd]
     int* frames;    // [B]
-    float* ea;      // extractor sub-batch: [Bs][P0][C] (layers 0, 2, 4, 6)
-    float* eb;      // [Bs][P1][C] (layers 1, 3, 5)
-    float* feat;    // [M][C]: layer 6's rows of the whole batch, then their LayerNorm
+    float* ea;      // extractor sub-batch: [Bs][P0][C] (layers 0, 2, 4, 6; bf16x3: every layer's split window rows)
+    float* eb;      // [Bs][P1][C] (layers 1, 3, 5; bf16x3: every conv's fp32 rows)
+    float* feat;    // [M][C]: layer 6's rows of the whole batch, then their LayerNorm (bf16x3: as split rows)
     float* r[4];    // [M][H]
     float* wide;    // [M][max(3 H, I)]
     int Bs;         // utterances per extractor sub-batch
@@ -353,6 +390,9 @@ extern "C" int hificar_hubert_debug_tap(hificar_hubert* g, const char* name, flo
         g->taps.erase(name);
         return HIFICAR_OK;
     }
+    if (hubert_x3(g) && std::string(name) == "extractor.0")
+        return fail(HIFICAR_E_STATE, "debug tap 'extractor.0': a %s handle holds layer 0's rows as split bf16 window rows only, not as fp32 rows",
+                    xfmr_precision_name(g->precision));
     g->taps[name] = {dst, capacity};
     return HIFICAR_OK;
 }
@@ -395,6 +435,10 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
     const hificar_hubert_config& c = g->cfg;
     const int C = c.conv_dim, H = c.hidden_size, I = c.intermediate_size, T = d.T[6];
     const double M = (double)B * T;
+    const bool x3 = hubert_x3(g), a16 = g->precision == HIFICAR_PREC_BF16X3A;
+    // (a tap set before hificar_hubert_set_precision)
+    if (x3 && g->taps.count("extractor.0"))
+        return fail(HIFICAR_E_STATE, "debug tap 'extractor.0': a %s handle holds layer 0's rows as split bf16 window rows only", xfmr_precision_name(g->precision));
 
     if (c.normalize) {
         ProfScope prof(h, stream, "hubert_stats_kernel", 0.0, 8.0 * B * L);
@@ -404,8 +448,9 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
     hipLaunchKernelGGL(hubert_frames_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, lengths, ws.frames, B, L);
     HIP_TRY(hipGetLastError());
 
+    // split (bf16x3): dst takes split rows instead of fp32 rows — 1: rows of their own, 2: window rows of two positions (dst must not be src)
     auto layer_norm = [&](const float* src, const float* gamma, const float* beta, float* dst, int nseq, int rows, int rows_in, int rows_out, int F, float eps,
-                          const int* lens, bool gelu) {
+                          const int* lens, bool gelu, int split = 0) {
         HubertLnParams p;
         p.x = src;
         p.gamma = gamma;
@@ -418,10 +463,14 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
         p.Tout = rows_out;
         p.F = F;
         p.eps = eps;
+        p.window = split == 2;
         const double n = (double)nseq * rows;
-        ProfScope prof(h, stream, gelu ? "hubert_ln_kernel<gelu>" : "hubert_ln_kernel", 8.0 * n * F, 8.0 * n * F);
+        ProfScope prof(h, stream, split ? (gelu ? "hubert_ln_kernel<gelu,split>" : "hubert_ln_kernel<split>") : gelu ? "hubert_ln_kernel<gelu>" : "hubert_ln_kernel",
+                       8.0 * n * F, 8.0 * n * F);
         const dim3 grid((unsigned)(((long long)nseq * rows + 3) / 4));
-        if (gelu) hipLaunchKernelGGL(hubert_ln_kernel<true>, grid, dim3(256), 0, stream, p);
+        if (split && gelu) hipLaunchKernelGGL((hubert_ln_kernel<true, true>), grid, dim3(256), 0, stream, p);
+        else if (split) hipLaunchKernelGGL((hubert_ln_kernel<false, true>), grid, dim3(256), 0, stream, p);
+        else if (gelu) hipLaunchKernelGGL(hubert_ln_kernel<true>, grid, dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(hubert_ln_kernel<false>, grid, dim3(256), 0, stream, p);
         return hipGetLastError();
     };
@@ -445,14 +494,17 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
             p.P = d.P[0];
             p.C = C;
             const double n = (double)nseq * d.P[0];
-            ProfScope prof(h, stream, "hubert_conv0_kernel", 2.0 * n * C * kHubK0, 4.0 * (n * C + (double)nseq * L));
-            hipLaunchKernelGGL(hubert_conv0_kernel, dim3((unsigned)(((long long)nseq * d.P[0] + 3) / 4)), dim3(256), 0, stream, p);
+            ProfScope prof(h, stream, x3 ? "hubert_conv0_kernel<split>" : "hubert_conv0_kernel", 2.0 * n * C * kHubK0, 4.0 * (n * C + (double)nseq * L));
+            const dim3 grid((unsigned)(((long long)nseq * d.P[0] + 3) / 4));
+            if (x3) hipLaunchKernelGGL(hubert_conv0_kernel<true>, grid, dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL(hubert_conv0_kernel<false>, grid, dim3(256), 0, stream, p);
             HIP_TRY(hipGetLastError());
         }
-        if ((rc = hubert_emit_tap(g, "extractor.0", ws.ea, b0, nseq, B, (size_t)d.T[0], (size_t)d.P[0], (size_t)C, stream)) != HIFICAR_OK) return rc;
+        if (!x3 && (rc = hubert_emit_tap(g, "extractor.0", ws.ea, b0, nseq, B, (size_t)d.T[0], (size_t)d.P[0], (size_t)C, stream)) != HIFICAR_OK) return rc;
         for (int i = 1; i < kHubExtLayers; ++i) {
-            const float* const in = i & 1 ? ws.ea : ws.eb;
-            float* const y = i & 1 ? ws.eb : ws.ea;
+            // (bf16x3: ws.ea holds every layer's split window rows, ws.eb every conv's fp32 rows)
+            const float* const in = x3 || (i & 1) ? ws.ea : ws.eb;
+            float* const y = x3 || (i & 1) ? ws.eb : ws.ea;
             const ConvLayer* ls[1] = {&g->ext[i]};
             ConvIO io[1];
             io[0] = ConvIO();
@@ -466,8 +518,8 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
             full.frames = d.P[i];
             if ((rc = launch_conv(h, ls, 1, nseq, d.P[i], io, 0.f, full, stream)) != HIFICAR_OK) return rc;
             const bool last = i + 1 == kHubExtLayers;
-            HIP_TRY(layer_norm(y, g->d_ext_ln[i][0], g->d_ext_ln[i][1], last ? ws.feat + (size_t)b0 * T * C : y, nseq, last ? T : d.P[i], d.P[i], last ? T : d.P[i],
-                               C, 1e-5f, nullptr, true));
+            HIP_TRY(layer_norm(y, g->d_ext_ln[i][0], g->d_ext_ln[i][1], last ? ws.feat + (size_t)b0 * T * C : x3 ? ws.ea : y, nseq, last ? T : d.P[i], d.P[i],
+                               last ? T : d.P[i], C, 1e-5f, nullptr, true, x3 && !last ? 2 : 0));
         }
     }
     if ((rc = hubert_emit_tap(g, "extract_features", ws.feat, 0, B, B, (size_t)T, (size_t)T, (size_t)C, stream)) != HIFICAR_OK) return rc;
@@ -476,18 +528,21 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
     Ragged rg;
     rg.seq_len = ws.frames;
     rg.frames = T;
-    auto conv = [&](const ConvLayer& Lr, const float* xs, const float* res, float* y) {
+    // xs: fp32 rows in exact fp32, split rows in bf16x3.  ys (bf16x3a's q | k | v): the output as split rows only — slope 1 makes the engine's
+    // activated copy the identity
+    auto conv = [&](const ConvLayer& Lr, const float* xs, const float* res, float* y, float* ys = nullptr) {
         const ConvLayer* ls[1] = {&Lr};
         ConvIO io[1];
         io[0] = ConvIO();
         io[0].xs = reinterpret_cast<const char*>(xs);
         io[0].res = res;
         io[0].y = y;
-        io[0].ys = nullptr;
-        return launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream);
+        io[0].ys = reinterpret_cast<char*>(ys);
+        return launch_conv(h, ls, 1, B, T, io, ys ? 1.f : 0.f, rg, stream);
     };
+    const int sp = x3 ? 1 : 0;  // a LayerNorm in front of a GEMM writes that GEMM's operand
     auto tap = [&](const std::string& name, const float* rows) { return hubert_emit_tap(g, name, rows, 0, B, B, (size_t)T, (size_t)T, (size_t)H, stream); };
-    HIP_TRY(layer_norm(ws.feat, g->d_fp_ln[0], g->d_fp_ln[1], ws.feat, B, T, T, T, C, c.layer_norm_eps, ws.frames, false));
+    HIP_TRY(layer_norm(ws.feat, g->d_fp_ln[0], g->d_fp_ln[1], ws.feat, B, T, T, T, C, c.layer_norm_eps, ws.frames, false, sp));
     if ((rc = conv(g->proj, ws.feat, nullptr, ws.r[0])) != HIFICAR_OK) return rc;
     if ((rc = tap("feature_projection", ws.r[0])) != HIFICAR_OK) return rc;
     float* cur = ws.r[1];    // the stream
@@ -517,9 +572,21 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
     const int nrun = layer < 0 ? c.num_hidden_layers : layer;  // hidden_states[k] is the stream in front of layer k
     for (int l = 0; l < nrun; ++l) {
         const HubertEncLayer& E = g->enc[(size_t)l];
-        HIP_TRY(layer_norm(cur, E.d_ln[0], E.d_ln[1], N, B, T, T, T, H, c.layer_norm_eps, ws.frames, false));
-        if ((rc = conv(E.qkv, N, nullptr, ws.wide)) != HIFICAR_OK) return rc;
-        {
+        HIP_TRY(layer_norm(cur, E.d_ln[0], E.d_ln[1], N, B, T, T, T, H, c.layer_norm_eps, ws.frames, false, sp));
+        if ((rc = a16 ? conv(E.qkv, N, nullptr, nullptr, ws.wide) : conv(E.qkv, N, nullptr, ws.wide)) != HIFICAR_OK) return rc;
+        if (a16) {
+            HubertAttn16Params p;
+            p.qkv = reinterpret_cast<const char*>(ws.wide);
+            p.lengths = ws.frames;
+            p.out = reinterpret_cast<char*>(R);
+            p.T = T;
+            p.F = H;
+            p.scale = (float)(1.0 / std::sqrt((double)kHubHeadDim));
+            ProfScope prof(h, stream, "hubert_attn16_kernel", 4.0 * M * T * H, 4.0 * M * 4 * H);
+            const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), (unsigned)c.num_attention_heads, (unsigned)B);
+            hipLaunchKernelGGL(hubert_attn16_kernel<kHubHeadDim>, grid, dim3(256), HubertAttn16Lds<kHubHeadDim>::bytes, stream, p);
+            HIP_TRY(hipGetLastError());
+        } else {
             HubertAttnParams p;
             p.qkv = ws.wide;
             p.lengths = ws.frames;
@@ -527,15 +594,21 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
             p.T = T;
             p.F = H;
             p.scale = (float)(1.0 / std::sqrt((double)kHubHeadDim));
-            ProfScope prof(h, stream, "hubert_attn_kernel", 4.0 * M * T * H, 4.0 * M * 4 * H);  // (every key of a full-length batch)
+            ProfScope prof(h, stream, x3 ? "hubert_attn_kernel<split>" : "hubert_attn_kernel", 4.0 * M * T * H, 4.0 * M * 4 * H);  // (every key of a full-length batch)
             const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), (unsigned)c.num_attention_heads, (unsigned)B);
-            hipLaunchKernelGGL(hubert_attn_kernel<kHubHeadDim>, grid, dim3(256), HubertAttnLds<kHubHeadDim>::bytes, stream, p);
+            // (bf16x3: the instantiation that stores split rows)
+            if (x3) hipLaunchKernelGGL((hubert_attn_kernel<kHubHeadDim, true>), grid, dim3(256), HubertAttnLds<kHubHeadDim>::bytes, stream, p);
+            else hipLaunchKernelGGL(hubert_attn_kernel<kHubHeadDim>, grid, dim3(256), HubertAttnLds<kHubHeadDim>::bytes, stream, p);
             HIP_TRY(hipGetLastError());
         }
         if ((rc = conv(E.wo, R, cur, other)) != HIFICAR_OK) return rc;
-        HIP_TRY(layer_norm(other, E.d_ln[2], E.d_ln[3], N, B, T, T, T, H, c.layer_norm_eps, ws.frames, false));
+        HIP_TRY(layer_norm(other, E.d_ln[2], E.d_ln[3], N, B, T, T, T, H, c.layer_norm_eps, ws.frames, false, sp));
         if ((rc = conv(E.l1, N, nullptr, ws.wide)) != HIFICAR_OK) return rc;
-        {
+        if (x3) {
+            ProfScope prof(h, stream, "hubert_gelu_split_kernel", 0.0, 8.0 * M * I);
+            hipLaunchKernelGGL(hubert_gelu_split_kernel, dim3((unsigned)(B * T)), dim3(256), 0, stream, ws.wide, ws.frames, T, I);
+            HIP_TRY(hipGetLastError());
+        } else {
             ProfScope prof(h, stream, "hubert_gelu_kernel", 0.0, 8.0 * M * I);
             hipLaunchKernelGGL(hubert_gelu_kernel, dim3((unsigned)(B * T), (unsigned)((I / 4 + 255) / 256)), dim3(256), 0, stream, ws.wide, ws.frames, T, I);
             HIP_TRY(hipGetLastError());

@@ -8,8 +8,10 @@
 //   hubert_posconv_kernel  the grouped 128-tap positional conv on v_mfma_f32_16x16x4_f32: x + GELU(conv(x) + b)
 //   hubert_attn_kernel     full softmax attention over the utterance's own keys: xfmr_attn_kernel's transposed-MFMA plan without band,
 //                          table or positional LDS region
-// Exact fp32 throughout (GELU in its erf form).  Every sum's order depends on the utterance alone: no atomics, no split reductions whose
-// shape depends on the batch.
+// Exact fp32 arithmetic throughout (GELU in its erf form).  Every sum's order depends on the utterance alone: no atomics, no split reductions
+// whose shape depends on the batch.  The bf16x3 forward's instantiations (hubert_conv0_kernel<true>, hubert_ln_kernel<GELU, true>,
+// hubert_gelu_split_kernel, hubert_attn_kernel<D, true>) differ in the FORMAT they store — split rows for the bf16x3 GEMM that reads them
+// (xfmr_store_split) — not in how they compute.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,8 +68,12 @@ __global__ __launch_bounds__(256) void hubert_frames_kernel(const int* __restric
     frames[b] = l >= 400 ? (l - 400) / 320 + 1 : 0;
 }
 
+// SPLIT: the row goes out as split rows instead of fp32: hi at ys, lo 2 FS bytes behind it (FS = F: a row of its own [hi: F | lo: F];
+// FS = 2 F: one position's half of a window row [hi: 2 F | lo: 2 F], hificar_hubert.hip.inc).  F % 8 == 0 there: lanes i and i ^ 1 hold
+// eight adjacent channels and are active together.
+template <bool SPLIT = false>
 __device__ __forceinline__ void hubert_ln_row(float4 (&v)[4], int lane, int nv, int F, float eps, const float* gamma, const float* beta, bool gelu,
-                                              float* yrow) {
+                                              float* yrow, char* ys = nullptr, int FS = 0) {
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -92,15 +98,21 @@ __device__ __forceinline__ void hubert_ln_row(float4 (&v)[4], int lane, int nv, 
         float4 r = make_float4((v[j].x - mean) * rstd * gv.x + bv.x, (v[j].y - mean) * rstd * gv.y + bv.y, (v[j].z - mean) * rstd * gv.z + bv.z,
                                (v[j].w - mean) * rstd * gv.w + bv.w);
         if (gelu) r = make_float4(hubert_gelu(r.x), hubert_gelu(r.y), hubert_gelu(r.z), hubert_gelu(r.w));
-        y[i] = r;
+        if constexpr (SPLIT) xfmr_store_split(ys, FS, 4 * i, i & 1, 1, r.x, r.y, r.z, r.w, true);
+        else y[i] = r;
     }
 }
+
+// where position t of a sequence whose rows start at `base` (pitch: P positions of C channels, 4 C bytes each in either format) keeps its hi
+// half in the window layout: window t / 2 is [hi: 2 C bf16 | lo: 2 C bf16], position t's C channels at (t & 1) C of each half
+__device__ __forceinline__ char* hubert_window_ptr(char* base, int t, int C) { return base + (size_t)(t >> 1) * 8 * C + (t & 1) * 2 * C; }
 
 // Extractor layer 0.  One wave per output row (position t of sequence b of this sub-batch): the row's ten samples are normalised in double
 // with the utterance's statistics (stats null: taken as they are) and rounded once; samples at or past the utterance's length are zeros, as
 // the library's padding after normalisation.  The C outputs are formed (taps in order), normalised over C (eps 1e-5, torch.nn.LayerNorm's
 // default), activated and stored once.  Rows T0 .. P - 1 of a sequence (the slack that makes its rows a whole number of stride-2 windows)
-// are zeros.  w: [10][C]; C a multiple of 4, at most 1024.
+// are zeros.  w: [10][C]; C a multiple of 4, at most 1024.  SPLIT (the bf16x3 forward): y holds the same rows as split window rows, layer
+// 1's operand (hubert_window_ptr; C a multiple of 8; zero rows are zero bits in either format).
 struct HubertConv0Params {
     const float* wav;      // [B][L], this sub-batch's first utterance
     const int* lengths;    // this sub-batch's, or null
@@ -113,6 +125,7 @@ struct HubertConv0Params {
     int nseq, L, T0, P, C;
 };
 
+template <bool SPLIT = false>
 __global__ __launch_bounds__(256) void hubert_conv0_kernel(const HubertConv0Params p) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -120,8 +133,14 @@ __global__ __launch_bounds__(256) void hubert_conv0_kernel(const HubertConv0Para
     const int b = (int)(row / p.P), t = (int)(row - (long long)b * p.P);
     const int nv = p.C >> 2;
     float* const yrow = p.y + (size_t)row * p.C;
+    char* const ys = SPLIT ? hubert_window_ptr(reinterpret_cast<char*>(p.y + (size_t)b * p.P * p.C), t, p.C) : nullptr;
     if (t >= p.T0) {
-        for (int i = lane; i < nv; i += 64) reinterpret_cast<float4*>(yrow)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (SPLIT) {  // nv / 2 pieces of 16 bytes in each half (2 C bytes), the lo half 4 C bytes behind the hi half
+            for (int i = lane; i < nv; i += 64)
+                *reinterpret_cast<uint4*>(ys + (i < nv / 2 ? 16 * i : 4 * p.C + 16 * (i - nv / 2))) = make_uint4(0u, 0u, 0u, 0u);
+        } else {
+            for (int i = lane; i < nv; i += 64) reinterpret_cast<float4*>(yrow)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         return;
     }
     const int l = p.lengths ? min(max(p.lengths[b], 0), p.L) : p.L;
@@ -149,11 +168,15 @@ __global__ __launch_bounds__(256) void hubert_conv0_kernel(const HubertConv0Para
         }
         v[j] = a;
     }
-    hubert_ln_row(v, lane, nv, p.C, 1e-5f, p.gamma, p.beta, true, yrow);
+    hubert_ln_row<SPLIT>(v, lane, nv, p.C, 1e-5f, p.gamma, p.beta, true, yrow, ys, 2 * p.C);
 }
 
 // LayerNorm(F) + optional GELU, one wave per row: row t of sequence b is read at x[(b Tin + t) F] and written at y[(b Tout + t) F], t < T.
 // Rows at or past a sequence's length (lengths non-null) are left alone.  x and y may be the same buffer when Tin == Tout.  F <= 1024, F % 4 == 0.
+// SPLIT (the bf16x3 forward; F % 8 == 0): y takes the rows as split rows only, 4 F bytes each like the fp32 row, so x and y may still be the
+// same buffer when Tin == Tout (a wave holds its whole row before it stores).  window: as split window rows of two positions
+// (hubert_window_ptr, Tout positions per sequence), the next extractor layer's operand — a position's bytes interleave with its
+// neighbour's there, so y must NOT be x.
 struct HubertLnParams {
     const float* x;
     const float* gamma;
@@ -162,9 +185,10 @@ struct HubertLnParams {
     float* y;
     int B, T, Tin, Tout, F;
     float eps;
+    int window = 0;
 };
 
-template <bool GELU>
+template <bool GELU, bool SPLIT = false>
 __global__ __launch_bounds__(256) void hubert_ln_kernel(const HubertLnParams p) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -180,7 +204,13 @@ __global__ __launch_bounds__(256) void hubert_ln_kernel(const HubertLnParams p) 
         const int i = lane + 64 * j;
         v[j] = i < nv ? x[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    hubert_ln_row(v, lane, nv, p.F, p.eps, p.gamma, p.beta, GELU, p.y + ((size_t)b * p.Tout + t) * p.F);
+    if constexpr (SPLIT) {
+        char* const seq = reinterpret_cast<char*>(p.y + (size_t)b * p.Tout * p.F);
+        hubert_ln_row<true>(v, lane, nv, p.F, p.eps, p.gamma, p.beta, GELU, nullptr, p.window ? hubert_window_ptr(seq, t, p.F) : seq + (size_t)t * p.F * 4,
+                            p.window ? 2 * p.F : p.F);
+    } else {
+        hubert_ln_row(v, lane, nv, p.F, p.eps, p.gamma, p.beta, GELU, p.y + ((size_t)b * p.Tout + t) * p.F);
+    }
 }
 
 // GELU in place on rows [B T][F] (F % 4 == 0); rows at or past a sequence's length are left alone.  grid (B T, ceil(F / 1024))
@@ -193,6 +223,33 @@ __global__ __launch_bounds__(256) void hubert_gelu_kernel(float* __restrict__ x,
     float4* const px = reinterpret_cast<float4*>(x + (size_t)row * F) + i;
     const float4 v = *px;
     *px = make_float4(hubert_gelu(v.x), hubert_gelu(v.y), hubert_gelu(v.z), hubert_gelu(v.w));
+}
+
+// The bf16x3 forward's GELU pass: rows [B T][F] fp32 -> the same rows, in place, as split rows [hi: F bf16 | lo: F bf16] of GELU(x), the
+// operand of output_dense.  A split row's lo half lands where the row's second half of inputs lies, so ONE workgroup owns a row: it holds
+// the row in registers (F <= 8192: eight float4 per thread) and stores behind a barrier.  F % 8 == 0 (threads i and i ^ 1 hold eight adjacent
+// channels).  Rows at or past a sequence's length are left alone (the whole workgroup returns before the barrier).  grid (B T)
+__global__ __launch_bounds__(256) void hubert_gelu_split_kernel(float* x, const int* __restrict__ lengths, int T, int F) {
+    const long long row = blockIdx.x;
+    const int b = (int)(row / T), t = (int)(row - (long long)b * T);
+    const int len = lengths ? min(max(lengths[b], 0), T) : T;
+    if (t >= len) return;
+    const int nv = F >> 2;
+    const float4* const px = reinterpret_cast<const float4*>(x + (size_t)row * F);
+    float4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int i = threadIdx.x + 256 * j;
+        v[j] = i < nv ? px[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    char* const ys = reinterpret_cast<char*>(x) + (size_t)row * F * 4;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int i = threadIdx.x + 256 * j;
+        if (i >= nv) continue;  // (nv is even: threads i and i ^ 1 pass together)
+        xfmr_store_split(ys, F, 4 * i, i & 1, 1, hubert_gelu(v[j].x), hubert_gelu(v[j].y), hubert_gelu(v[j].z), hubert_gelu(v[j].w), true);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -292,6 +349,8 @@ __global__ __launch_bounds__(256) void hubert_posconv_kernel(const HubertPosPara
 // v_mfma_f32_16x16x4_f32 so that a query is a lane column, online softmax per 64-key block, P never in LDS — without band, table or positional
 // LDS region.  Keys past the length are skipped by predicate (weight 0, no part in the maximum); queries past it are not computed, their rows
 // of `out` not written.  The head count is the grid's y extent.  The order of every sum depends on the sequence's length only.
+// SPLIT (the bf16x3 forward): `out` is out_proj's input and nothing else, so the rows are stored as split rows only (out: [B T][4 F bytes]),
+// as xfmr_attn_kernel<D, false, true> stores them.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct HubertAttnParams {
     const float* qkv;    // [B T][3 F]: q | k | v, each [head][d]
@@ -306,7 +365,7 @@ struct HubertAttnLds {
     static constexpr size_t bytes = (size_t)2 * kXfmrKB * (D + 4) * sizeof(float);
 };
 
-template <int D>
+template <int D, bool SPLIT = false>
 __global__ __launch_bounds__(256) void hubert_attn_kernel(const HubertAttnParams p) {
     extern __shared__ float hubert_lds[];
     constexpr int PT = D + 4, NS = D / 4, NM = D / 16;
@@ -389,6 +448,14 @@ __global__ __launch_bounds__(256) void hubert_attn_kernel(const HubertAttnParams
                 for (int j = 0; j < NM; ++j) o[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[16 * j], s[sb][i], o[j], 0, 0, 0);
             }
         }
+    }
+    if constexpr (SPLIT) {
+        const float inv = qok ? 1.f / l : 0.f;
+        char* const orow = reinterpret_cast<char*>(p.out) + (row0 + (qok ? q : q0)) * (size_t)p.F * 4;  // (qok is shared by the lanes of a column)
+#pragma unroll
+        for (int j = 0; j < NM; ++j)
+            xfmr_store_split(orow, p.F, h * D + 16 * j + 4 * g, g & 1, 16, o[j][0] * inv, o[j][1] * inv, o[j][2] * inv, o[j][3] * inv, qok);
+        return;
     }
     if (!qok) return;
     const float inv = 1.f / l;  // (l >= 1: the query's own key exists)

@@ -1,5 +1,5 @@
-// The building blocks the five bf16 attention kernels share (xfmr_attn16_kernel, xfmr_attn16_train_kernel, xfmr_attn16_bwd_q_kernel,
-// xfmr_attn16_bwd_k_kernel, xfmr_demb16_partial_kernel).  Their common plan: a query (or a key) is a lane column, blocks are 64 rows, the
+// The building blocks the bf16 attention kernels share (xfmr_attn16_kernel, xfmr_attn16_train_kernel, xfmr_attn16_bwd_q_kernel,
+// xfmr_attn16_bwd_k_kernel, xfmr_demb16_partial_kernel; hubert_attn16_kernel, without the band).  Their common plan: a query (or a key) is a lane column, blocks are 64 rows, the
 // next block is in flight global -> registers while the current one is multiplied, every product is hi.hi + hi.lo + lo.hi on
 // v_mfma_f32_16x16x32_bf16 with fp32 accumulation, hi = bf16(x), lo = bf16(x - hi).
 //
@@ -172,13 +172,15 @@ __device__ __forceinline__ void xfmr_attn16_pos(char* kimg, float* mypos, const 
 // exponentials in s (zeros where `valid` has no bit) and returns alpha, the factor the caller's accumulators of earlier blocks take.
 //   valid  bit 4 sb + i: the key is in this query's band and inside the sequence
 //   act    (wave-uniform) the 32-key step meets the band of the wave's queries qw .. qw + 15
-template <int D>
+// BAND = false (hubert_attn16_kernel: full attention, no position table): every key of the block's n counts, a step is active while it holds
+// one of them, and the logit is the scaled product alone; mypos, q and qw are not read.
+template <int D, bool BAND = true>
 __device__ __forceinline__ float xfmr_attn16_scores(const char* arow, const bf16x8* qh, const bf16x8* ql, const float* mypos, float scale, int kb, int n,
                                                     int q, int qw, bool qok, int g, f32x4 (&s)[4], unsigned& valid, bool (&act)[2], float& m, float& l) {
     valid = 0;
     float mb = -INFINITY;
 #pragma unroll
-    for (int t = 0; t < 2; ++t) act[t] = xfmr_attn16_step_meets(t, n, kb + 32 * t, qw);
+    for (int t = 0; t < 2; ++t) act[t] = BAND ? xfmr_attn16_step_meets(t, n, kb + 32 * t, qw) : 32 * t < n;
 #pragma unroll
     for (int sb = 0; sb < 4; ++sb) {
         s[sb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -188,8 +190,8 @@ __device__ __forceinline__ float xfmr_attn16_scores(const char* arow, const bf16
         for (int i = 0; i < 4; ++i) {
             const int k = kb + 16 * sb + 4 * g + i;
             const int rel = k - q + (kXfmrRel - 1);
-            if (xfmr_attn16_in_band(qok, k, kb + n, rel)) {
-                const float v = s[sb][i] * scale + mypos[rel];
+            if (BAND ? xfmr_attn16_in_band(qok, k, kb + n, rel) : qok && k < kb + n) {
+                const float v = BAND ? s[sb][i] * scale + mypos[rel] : s[sb][i] * scale;
                 s[sb][i] = v;
                 mb = fmaxf(mb, v);
                 valid |= 1u << (4 * sb + i);

@@ -202,7 +202,7 @@ class HuBERT(_feature_model.NativeFeatureModel):
     ``state_dict()`` has the keys and shapes of the ``transformers`` library's ``HubertModel`` and loads with ``strict=True``; the positional
     conv's weight norm is also accepted in its old form, ``weight_g`` / ``weight_v`` — while the arithmetic runs in ``libhificar.so`` behind one
     native handle (``hificar_hubert_*`` of include/hificar.h): copies and pickles never share a handle, there is no CPU fallback and no
-    backward.  Inference only (``eval()`` mode, which the constructor sets); exact fp32.
+    backward.  Inference only (``eval()`` mode, which the constructor sets); exact fp32 by default.
 
         feats, frames = hubert(wav, lengths=samples, layer=-1)          # (B, hidden_size, Tmax) at 50 Hz, (B,) int32
         ema = model.forward_lowrate(feats, lengths=frames, interp_factor=4)
@@ -216,6 +216,12 @@ class HuBERT(_feature_model.NativeFeatureModel):
     constant of the library's ``Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm``.  The reference's s3prl pipeline normalises with
     ``F.layer_norm`` over the waveform, whose eps is 1e-5 as far as is known here — s3prl is not on hand to check — so it is a field.
 
+    ``precision`` (opt-in; ``"f32"`` is the default and unchanged): ``"bf16x3"`` runs every GEMM — extractor layers 1 - 6, the projection,
+    q | k | v, ``out_proj`` and the feed-forward's two — as x w ~ hi hi + hi lo + lo hi on bf16 MFMAs with fp32 accumulation (hi = bf16(x),
+    lo = bf16(x - hi)); ``"bf16x3a"`` is that with the attention's two products in the same form too.  Everything else — statistics, layer 0,
+    LayerNorms, GELUs, the positional conv, softmax, biases, the residual stream — stays fp32; outputs stay within 2e-4 of max|y| of the
+    float64 restatement.  Keyword or ``set_precision``; kept by copies, pickles and ``load_state_dict``, not part of the ``state_dict``.
+
     ``config``: a mapping with the keys of the model's ``config.json`` (missing keys: the large model's).  Not built, refused at
     construction: group-norm extractors and post-LN encoders (HuBERT-base), WavLM's gated relative position bias, adapters, head sizes other
     than 64; ``masked_spec_embed`` is held for ``strict=True`` and never used (spec-augment is a training device)."""
@@ -224,8 +230,9 @@ class HuBERT(_feature_model.NativeFeatureModel):
     _NAME = "HuBERT"
     sampling_rate = 16000
 
-    def __init__(self, config=None, normalize=True, norm_eps=1e-7):
+    def __init__(self, config=None, normalize=True, norm_eps=1e-7, precision="f32"):
         super().__init__()
+        self.precision = self._check_precision(precision)
         c = _native.check_hubert_config(dict(config or {}))
         self.config = c
         self.normalize, self.norm_eps = bool(normalize), float(norm_eps)
@@ -255,6 +262,29 @@ class HuBERT(_feature_model.NativeFeatureModel):
         self._params = {"in_channels": 1, "out_channels": H}
         self._init_native()
         self.eval()
+
+    @staticmethod
+    def _check_precision(precision):
+        if not isinstance(precision, str) or precision not in _native.HUBERT_PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_native.HUBERT_PRECISIONS)}")
+        return precision
+
+    def set_precision(self, precision):
+        """Switch the encoder's arithmetic: ``"f32"``, ``"bf16x3"`` or ``"bf16x3a"`` (the class docstring).  The native handle is dropped, so
+        the next forward rebuilds it from the module's parameters and packs the weights for that arithmetic (hificar_hubert_set_precision
+        between create and finalize); back on ``"f32"`` the model gives the bytes it gave before."""
+        precision = self._check_precision(precision)
+        if precision != self.precision:
+            self.precision = precision
+            self._invalidate()
+
+    def __setstate__(self, state):
+        state.setdefault("precision", "f32")  # (a pickle from before the keyword)
+        super().__setstate__(state)
+
+    def _finalize_handle(self, handle):
+        self._call("_set_precision", handle, _native.HUBERT_PRECISIONS[self.precision])
+        self._call("_finalize", handle)
 
     # ------------------------------------------------------------------ what NativeFeatureModel asks of a model
     def _device(self):
@@ -289,7 +319,7 @@ class HuBERT(_feature_model.NativeFeatureModel):
         return super().train(False)
 
     @classmethod
-    def from_pretrained(cls, directory, normalize=True, norm_eps=1e-7):
+    def from_pretrained(cls, directory, normalize=True, norm_eps=1e-7, precision="f32"):
         """A model from a directory in the ``transformers`` layout: ``config.json`` and ``model.safetensors`` (when ``safetensors`` imports) or
         ``pytorch_model.bin``.  fairseq and s3prl checkpoints are refused: neither layout could be checked against its package here."""
         import json
@@ -297,7 +327,7 @@ class HuBERT(_feature_model.NativeFeatureModel):
 
         with open(os.path.join(directory, "config.json")) as f:
             config = json.load(f)
-        model = cls(config, normalize=normalize, norm_eps=norm_eps)
+        model = cls(config, normalize=normalize, norm_eps=norm_eps, precision=precision)
         st_path, bin_path = os.path.join(directory, "model.safetensors"), os.path.join(directory, "pytorch_model.bin")
         sd = None
         if os.path.exists(st_path):
@@ -323,7 +353,8 @@ class HuBERT(_feature_model.NativeFeatureModel):
         return _native.hubert_frames(length)
 
     def debug_tap(self, name, dst):
-        """Test aid (hificar_hubert_debug_tap): the following forwards copy the named intermediate into ``dst`` (a float32 device tensor)."""
+        """Test aid (hificar_hubert_debug_tap): the following forwards copy the named intermediate into ``dst`` (a float32 device tensor).
+        ``"extractor.0"`` exists on an ``"f32"`` model only (the other arithmetics hold layer 0's rows as split bf16 rows): refused by name."""
         handle = self._native_handle()
         self._call("_debug_tap", handle, name.encode() if name is not None else None, None if dst is None else dst.data_ptr(),
                    0 if dst is None else dst.numel())

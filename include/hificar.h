@@ -73,9 +73,9 @@ extern "C" {
 #define HIFICAR_PREC_BF16X3 1      /* fp32 operands split hi+lo bf16, 3 bf16 MFMAs, fp32 accumulate */
 #define HIFICAR_PREC_BF16X3W 2     /* hificar_xfmr_set_train_precision ONLY: bf16x3, and the one-tap GEMM-form weight gradients in it too;
                                       every other entry point that takes a precision refuses it (HIFICAR_E_INVALID) */
-#define HIFICAR_PREC_BF16X3A 3     /* hificar_xfmr_set_precision ONLY: bf16x3, and the attention's three products on bf16 MFMAs too
-                                      (v_mfma_f32_16x16x32_bf16, hi hi + hi lo + lo hi, fp32 accumulate; inference only); every other entry
-                                      point that takes a precision refuses it (HIFICAR_E_INVALID) */
+#define HIFICAR_PREC_BF16X3A 3     /* hificar_xfmr_set_precision and hificar_hubert_set_precision ONLY: bf16x3, and the attention's products on
+                                      bf16 MFMAs too (v_mfma_f32_16x16x32_bf16, hi hi + hi lo + lo hi, fp32 accumulate; inference only); every
+                                      other entry point that takes a precision refuses it (HIFICAR_E_INVALID) */
 #define HIFICAR_PREC_BF16X3WA 4    /* hificar_xfmr_set_train_precision ONLY: bf16x3w, and the training attention's query-tiled kernels (forward
                                       and backward-q: seven of its ten banded products) on v_mfma_f32_16x16x32_bf16 too; every other entry
                                       point that takes a precision refuses it (HIFICAR_E_INVALID) */
@@ -1029,7 +1029,7 @@ int hificar_xfmr_backward_packed(hificar_xfmr* h, const float* dout, const int32
  * Speech representation: the HuBERT encoder of the "large" family (the published architecture as the `transformers` library's
  * HubertModel states it with feat_extract_norm = "layer", do_stable_layer_norm = True, feat_proj_layer_norm = True), waveforms at 16 kHz ->
  * hidden states at 50 Hz, the front end of the reference's SSL inversion models (egs/ema/voc1/local/predict_ema.py puts hubert_large_ll60k's
- * last hidden state, stretched by 4, in front of the BiGRU).  Inference only, exact fp32.
+ * last hidden state, stretched by 4, in front of the BiGRU).  Inference only; exact fp32 unless hificar_hubert_set_precision says otherwise.
  *   normalisation  per utterance (x - mean) / sqrt(var + norm_eps) over its own samples, population variance, applied as layer 0 reads
  *   extractor      seven Conv1d (kernels 10, 3, 3, 3, 3, 2, 2; strides 5, 2, 2, 2, 2, 2, 2; conv_dim channels), each + LayerNorm over channels
  *                  (eps 1e-5) + GELU (erf): layer 0 in a kernel of its own, layers 1 - 6 on the conv engine as stride-1 convs over rows of two
@@ -1044,6 +1044,13 @@ int hificar_xfmr_backward_packed(hificar_xfmr* h, const float* dout, const int32
  * HIFICAR_HUBERT_MAX_FFN; 1 .. HIFICAR_HUBERT_MAX_LAYERS layers.  Not built (the binding refuses them): group-norm extractors, post-LN encoders,
  * gated relative position bias, training, dropout, spec-augment.
  * Every utterance of a batch is computed as if alone, bit for bit: the conv engine runs with split-K off, every other sum has one order.
+ *
+ * Opt-in bf16x3 (HIFICAR_PREC_BF16X3): every GEMM on the conv engine — extractor layers 1 - 6, the projection, q | k | v, out_proj,
+ * intermediate_dense, output_dense — as x w ~ hi hi + hi lo + lo hi on bf16 MFMAs with fp32 accumulation, hi = bf16(x), lo = bf16(x - hi).
+ * The producers of those GEMMs' inputs (layer 0, the LayerNorms, the attention, the GELU pass) write split rows directly; the waveform
+ * statistics, layer 0, every LayerNorm and GELU, the positional conv, the attention, biases, residual adds and the residual stream stay fp32.
+ * Opt-in bf16x3a (HIFICAR_PREC_BF16X3A): bf16x3, and the attention's two products (Q K^T, P V) in the same three-term form on
+ * v_mfma_f32_16x16x32_bf16; the softmax statistics stay fp32.  Both keep "every utterance as if alone, bit for bit" and the workspace's size.
  * --------------------------------------------------------------------------------------------------------------------------- */
 #define HIFICAR_HUBERT_MAX_CONV 1024
 #define HIFICAR_HUBERT_MAX_HIDDEN 1024
@@ -1076,6 +1083,13 @@ int hificar_hubert_create(const hificar_hubert_config* cfg, hificar_hubert** out
  * ".layer_norm.*", ".feed_forward.intermediate_dense.weight" (I, H) / ".bias", ".feed_forward.output_dense.weight" (H, I) / ".bias",
  * ".final_layer_norm.*".  data: HOST pointer to contiguous fp32; the caller keeps ownership. */
 int hificar_hubert_set_weight(hificar_hubert* h, const char* name, const float* data, const int64_t* shape, int ndim);
+
+/* The arithmetic of the handle's GEMMs: HIFICAR_PREC_F32 (the default), HIFICAR_PREC_BF16X3 or HIFICAR_PREC_BF16X3A (above).  Between
+ * hificar_hubert_create and hificar_hubert_finalize only (finalize packs the weights for one arithmetic): HIFICAR_E_STATE afterwards; any
+ * other value, the training-only ones included, HIFICAR_E_INVALID.  Touches no device.  hificar_hubert_workspace_bytes answers for the
+ * arithmetic set when it is called.  A handle that is not f32 refuses the debug tap "extractor.0" with HIFICAR_E_STATE (those rows exist as
+ * split bf16 rows only). */
+int hificar_hubert_set_precision(hificar_hubert* h, int precision);
 
 /* Checks that every tensor arrived, folds the weight norm, re-lays the strided convs' weights as windows of two positions, packs q | k | v
  * as one GEMM, uploads.  Synchronises the device once. */

@@ -15,10 +15,17 @@ One JSON line per batch size (appended to --out):
   ema                    HuBERT -> BiGRU.forward_lowrate(interp_factor=4) against the forward_lowrate alone on states already there: the
                          encoder's share of speech -> EMA
 
+--precision bf16x3 | bf16x3a adds that arithmetic's leg to the alternation: native f32 / native P / stock (bf16x3a: native f32 / native
+bf16x3 / native bf16x3a / stock — its yardstick is the bf16x3 leg of the same run), two windows per leg, on a copy of the same model.  The
+line gains "precision" and "legs": per leg its windows, spread, per-kernel groups, workspace and error against stock, and per pair
+(leg against its yardstick) "faster": true only where the leg's slowest window lies below the yardstick's fastest by more than the two
+window spreads added.  Without the flag the tool does what it did.
+
 Weights are the constructors' random ones (the time does not depend on the values).
 """
 
 import argparse
+import copy
 import json
 import os
 import sys
@@ -33,7 +40,7 @@ from articulatory_amd import _native  # noqa: E402
 from articulatory_amd.features import HuBERT  # noqa: E402
 from articulatory_amd.models import BiGRU  # noqa: E402
 from articulatory_amd.utils.synth import synth_bigru_state_dict  # noqa: E402
-from tools.features_bench import alternated  # noqa: E402
+from tools.features_bench import alternated, window  # noqa: E402
 
 SR = 16000
 PEAK_TFLOPS = 157.3
@@ -84,7 +91,7 @@ def flop_count(c, B, L):
 
 
 def group(name):
-    for key, label in (("hubert_conv0", "extractor layer 0"), ("#window", "extractor convs 1-6"), ("hubert_ln_kernel<gelu>", "extractor LayerNorm + GELU"),
+    for key, label in (("hubert_conv0", "extractor layer 0"), ("#window", "extractor convs 1-6"), ("hubert_ln_kernel<gelu", "extractor LayerNorm + GELU"),
                        ("hubert_posconv", "positional conv"), ("hubert_attn", "attention"), ("hubert_gelu", "GELU pass"), ("hubert_ln", "LayerNorm"),
                        ("conv_", "GEMMs")):
         if key in name:
@@ -102,6 +109,53 @@ def kernel_groups(m, fn):
     return {k: round(v, 3) for k, v in sorted(out.items(), key=lambda kv: -kv[1])}
 
 
+def alternated_legs(fns, seconds, limit):
+    """features_bench.alternated for any number of legs: leg 0, 1, .., 0, 1, ..; two windows each."""
+    for _ in range(3):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    first = [window(fn, seconds, limit) for fn in fns]
+    second = [window(fn, seconds, limit) for fn in fns]
+    return [[round(a, 4), round(b, 4)] for a, b in zip(first, second)]
+
+
+def faster(leg, yard):
+    """The leg's slowest window lies below the yardstick's fastest by more than the two window spreads added."""
+    return bool(min(yard) - max(leg) > abs(leg[0] - leg[1]) + abs(yard[0] - yard[1]))
+
+
+def precision_legs(m, bigru, wav, ref, frames, precision, a):
+    """The "legs" entry of a line: native f32, (bf16x3,) `precision` and stock alternated in one process."""
+    names = ["f32"] + (["bf16x3"] if precision == "bf16x3a" else []) + [precision]
+    models = {"f32": m}
+    for n in names[1:]:
+        models[n] = copy.deepcopy(m)
+        models[n].set_precision(n)
+    B, L = wav.shape
+    legs = {}
+    for n in names:
+        got = models[n](wav)[0]
+        legs[n] = {"rel_err_vs_stock": float((got - ref).abs().max() / ref.abs().max()), "workspace_mb": round(models[n].workspace_bytes(B, L) / 1e6, 1)}
+        del got
+    ms = alternated_legs([(lambda mm=models[n]: mm(wav)) for n in names] + [lambda: stock_forward(m, wav)], a.window, a.limit)
+    for n, w in zip(names + ["stock"], ms):
+        legs.setdefault(n, {})["ms"] = w
+        legs[n]["spread"] = round(abs(w[0] - w[1]) / min(w), 4)
+    for n in names:
+        legs[n]["kernels_ms"] = kernel_groups(models[n], lambda mm=models[n]: mm(wav))
+    pairs = [(names[i], names[i - 1]) for i in range(1, len(names))] + [(n, "stock") for n in names]
+    out = {"legs": legs, "faster": {f"{x} < {y}": faster(legs[x]["ms"], legs[y]["ms"]) for x, y in pairs},
+           "ratio": {f"{y} / {x}": round(min(legs[y]["ms"]) / max(legs[x]["ms"]), 3) for x, y in pairs}}
+    mp = models[precision]
+    e_ms, b_ms = alternated(lambda: bigru.forward_lowrate(mp(wav)[0], lengths=frames, interp_factor=4),
+                            lambda: bigru.forward_lowrate(ref, lengths=frames, interp_factor=4), a.window, a.limit)
+    out["ema"] = {"speech_to_ema_ms": e_ms, "forward_lowrate_ms": b_ms, "encoder_share": round((min(e_ms) - max(b_ms)) / min(e_ms), 4)}
+    for n in names[1:]:
+        models[n]._invalidate()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 64])
@@ -110,6 +164,7 @@ def main():
     ap.add_argument("--limit", type=float, default=30.0, help="seconds a single call may take")
     ap.add_argument("--layers", type=int, default=24)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--precision", default=None, choices=("bf16x3", "bf16x3a"), help="add this arithmetic's leg(s) to the alternation")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("hubert_bench: no GPU visible; a device time is measured on the device or not at all")
@@ -141,6 +196,9 @@ def main():
                    "peak_tflops": PEAK_TFLOPS, "workspace_mb": round(m.workspace_bytes(B, L) / 1e6, 1), "kernels_ms": kern,
                    "posconv_share": round(kern.get("positional conv", 0.0) / total, 4), "gelu_share": round(kern.get("GELU pass", 0.0) / total, 4),
                    "ema": {"speech_to_ema_ms": e_ms, "forward_lowrate_ms": b_ms, "encoder_share": round((min(e_ms) - max(b_ms)) / min(e_ms), 4)}}
+            if a.precision:
+                res["precision"] = a.precision
+                res["opt_in"] = precision_legs(m, bigru, wav, ref, frames, a.precision, a)
             lines.append(json.dumps(res))
             print(lines[-1], flush=True)
             del wav, ref, got
