@@ -451,6 +451,62 @@ def check_hubert_config(config: dict) -> dict:
     return c
 
 
+# WavLM (features.WavLM): HuBERT-large's encoder with the gated relative position bias; the published wavlm-large's table
+WAVLM_DEFAULTS = dict(num_buckets=320, max_bucket_distance=800)
+# the encoder's arithmetics under the bias: the bf16 attention kernel (bf16x3a) has no bias term
+WAVLM_PRECISIONS = dict(PRECISIONS)
+
+
+def check_wavlm_config(config: dict) -> dict:
+    """A ``config.json`` mapping of a WavLM model -> the same with the defaults filled in (the large model's; ``num_buckets`` 320,
+    ``max_bucket_distance`` 800).  Everything check_hubert_config refuses stays refused, under WavLM's name: group-norm extractors and post-LN
+    encoders (wavlm-base, wavlm-base-plus), adapters, head sizes other than 64."""
+    c = dict(config)
+    model_type = str(c.pop("model_type", "wavlm")).lower()
+    if model_type != "wavlm":
+        raise NotImplementedError(f"WavLM: model_type {model_type!r} (features.HuBERT reads HuBERT configurations)")
+    rel = {k: c.pop(k, v) for k, v in WAVLM_DEFAULTS.items()}
+    try:
+        c = check_hubert_config(c)
+    except (NotImplementedError, ValueError) as e:
+        raise type(e)(str(e).replace("HuBERT", "WavLM")) from None
+    nb, md = rel["num_buckets"], rel["max_bucket_distance"]
+    for k, v in rel.items():
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"WavLM: {k} must be an integer, got {v!r}")
+    if nb < 4 or nb % 2 or nb > HUBERT_MAX_BUCKETS:
+        raise ValueError(f"WavLM: num_buckets={nb} unsupported (even, 4 .. {HUBERT_MAX_BUCKETS})")
+    if not nb // 4 < md <= HUBERT_MAX_DISTANCE:
+        raise ValueError(f"WavLM: max_bucket_distance={md} unsupported (above num_buckets // 4 = {nb // 4}, the last exact bucket, up to "
+                         f"{HUBERT_MAX_DISTANCE})")
+    c.update(rel, model_type="wavlm")
+    return c
+
+
+def wavlm_bucket_of_distance(num_buckets: int, max_distance: int):
+    """int32 tensor of 2 max_distance + 1 entries: entry d + max_distance is the bucket of the relative position d = key - query, for d in
+    -max_distance .. max_distance, by the very float32 operations of the ``transformers`` library's ``WavLMAttention._relative_positions_bucket``
+    (a one-ulp difference of the logarithm at a bucket's edge would pick the neighbouring embedding row).  From |d| = max_distance on the
+    bucket is the side's last, so hificar_hubert_set_rel_bias's clamp of d into this range is exact.  The one place the map is computed."""
+    import math
+
+    import torch
+
+    relative_positions = torch.arange(-max_distance, max_distance + 1, dtype=torch.long)
+    nb = num_buckets // 2
+    relative_buckets = (relative_positions > 0).to(torch.long) * nb
+    relative_positions = torch.abs(relative_positions)
+    max_exact = nb // 2
+    is_small = relative_positions < max_exact
+    if_large = torch.log(relative_positions.float() / max_exact)
+    if_large = if_large / math.log(max_distance / max_exact)
+    if_large = if_large * (nb - max_exact)
+    if_large = (max_exact + if_large).to(torch.long)
+    if_large = torch.min(if_large, torch.full_like(if_large, nb - 1))
+    relative_buckets += torch.where(is_small, relative_positions, if_large)
+    return relative_buckets.to(torch.int32).contiguous()
+
+
 def make_hubert_config(config: dict, normalize: bool, norm_eps: float) -> HificarHubertConfig:
     """A checked HuBERT configuration (check_hubert_config) -> hificar_hubert_config."""
     cfg = HificarHubertConfig()

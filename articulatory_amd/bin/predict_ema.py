@@ -25,7 +25,8 @@ else 80 (predict_ema.py:42-47; ``--hop-length`` overrides), the filterbank of ev
 
 For a directory with ``_h2`` in its name — the SSL models, in front of which the reference puts ``hubert_large_ll60k`` (its last hidden state at
 50 Hz, stretched by 4) — ``--from-wav`` needs ``--ssl-model DIR``: a HuBERT model of the large family in the ``transformers`` layout
-(``config.json`` + ``model.safetensors`` | ``pytorch_model.bin``), run on the device by ``articulatory_amd.features.HuBERT`` in front of
+(``config.json`` + ``model.safetensors`` | ``pytorch_model.bin``), or a WavLM model of the large family (``model_type: wavlm``; a BiGRU
+trained on WavLM states), run on the device by ``articulatory_amd.features.HuBERT`` / ``WavLM`` (``features.ssl_encoder_from_pretrained``) in front of
 ``forward_lowrate`` with the directory's factor and no z-score.  ``--ssl-layer N`` takes ``hidden_states[N]`` instead of the last hidden state.
 ``--ssl-precision {f32,bf16x3,bf16x3a}`` sets the encoder's arithmetic (``HuBERT(precision=)``; default f32); ``--precision`` stays the
 inversion model's.
@@ -140,7 +141,7 @@ def get_parser():
     parser.add_argument("--hop-length", type=int, default=None,
                         help="hop of the MFCC extraction in samples (--from-wav); default: 160 when the directory name starts with hprc, else 80")
     parser.add_argument("--ssl-model", type=str, default=None,
-                        help="directory of a HuBERT model (large family; transformers layout: config.json + model.safetensors | "
+                        help="directory of a HuBERT or WavLM model (large family; transformers layout: config.json + model.safetensors | "
                              "pytorch_model.bin): with --from-wav and a model directory with _h2 in its name, its hidden states are the features")
     parser.add_argument("--ssl-layer", type=int, default=None,
                         help="with --ssl-model: take hidden_states[N] (0 .. layers - 1) instead of the last hidden state")
@@ -285,17 +286,20 @@ def main(argv=None):
         rates = {p: sr for p, (sr, _) in info.items()}
     ssl_config = None
     if args.ssl_model is not None:
-        from articulatory_amd._native import check_hubert_config, hubert_frames
+        from articulatory_amd._native import hubert_frames
+        from articulatory_amd.features import ssl_encoder_class
 
+        ssl_class = ssl_encoder_class(args.ssl_model)  # HuBERT or WavLM, by config.json's model_type
         with open(os.path.join(args.ssl_model, "config.json")) as f:
-            ssl_config = check_hubert_config(json.load(f))
+            ssl_config = ssl_class._check_config(json.load(f))
+        ssl_class._check_precision(args.ssl_precision or "f32")  # (WavLM refuses bf16x3a: before anything loads)
         if args.ssl_layer is not None and not 0 <= args.ssl_layer < ssl_config["num_hidden_layers"]:
             raise ValueError(f"--ssl-layer {args.ssl_layer} outside 0 .. {ssl_config['num_hidden_layers'] - 1}")
         check_ssl_wavs(pairs, info)
     if args.dry_run and ssl_config is not None:
         print(json.dumps({"model_dir": args.model_dir, "checkpoint": checkpoint, "generator_type": config.get("generator_type"),
                           "interp_factor": factor, "zscore": bool(zscore), "batch_size": args.batch_size, "precision": args.precision or "f32",
-                          "front_end": "hubert", "ssl_model": args.ssl_model, "ssl_layer": -1 if args.ssl_layer is None else args.ssl_layer,
+                          "front_end": ssl_class._NAME.lower(), "ssl_model": args.ssl_model, "ssl_layer": -1 if args.ssl_layer is None else args.ssl_layer,
                           "ssl_precision": args.ssl_precision or "f32",
                           "hidden_size": ssl_config["hidden_size"], "num_hidden_layers": ssl_config["num_hidden_layers"],
                           "rates": [SSL_RATE], "utterances": [u for u, _ in pairs],
@@ -332,12 +336,10 @@ def main(argv=None):
             raise NotImplementedError(f"--precision {args.precision}: {type(model).__name__} runs in the exact-fp32 arithmetic only")
     model = model.eval().to(device)
     if ssl_config is not None:
-        from articulatory_amd.features import HuBERT
-
         width = config.get("generator_params", {}).get("in_channels")
         if width is not None and width != ssl_config["hidden_size"]:
             raise ValueError(f"--ssl-model: hidden_size {ssl_config['hidden_size']} does not match the model's in_channels {width}")
-        hubert = HuBERT.from_pretrained(args.ssl_model, precision=args.ssl_precision or "f32").to(device)
+        hubert = ssl_class.from_pretrained(args.ssl_model, precision=args.ssl_precision or "f32").to(device)
         logging.info(f"Loaded the speech model from {args.ssl_model}.")
         n = predict_ssl(model, hubert, pairs, args.outdir, device, interp_factor=factor, zscore=zscore, batch_size=args.batch_size,
                         layer=-1 if args.ssl_layer is None else args.ssl_layer)

@@ -2719,3 +2719,4 @@ static int feature_train_make(G* g, int (*build)(G*, TS*), const char* model) {
 #include "hificar_xfmr.hip.inc"
 #include "hificar_xfmr_train.hip.inc"
 #include "hificar_hubert.hip.inc"
+#include "hificar_linear.hip.inc"

@@ -31,6 +31,11 @@
 //
 // bf16x3a (HIFICAR_PREC_BF16X3A): bf16x3 with the attention's two products on bf16 MFMAs too (hificar_hubert_attn16.hip.h).  The q | k | v
 // GEMM writes split rows only ([hi: 3 H bf16 | lo: 3 H bf16], the bytes of the fp32 row).  The conv engine sees a bf16x3 handle.
+//
+// WavLM (hificar_hubert_set_rel_bias; f32 and bf16x3): each layer's first LayerNorm also forms the attention's gates from the row it holds
+// (hubert_ln_kernel<false, SPLIT, true>, into ws.gates: (B, heads, T), one layer's, reused), and the attention adds
+// gate[b, h, q] bias_d[h][clamp(k - q)] to its scores (hubert_attn_kernel<64, SPLIT, true>); bias_d is folded at finalize from layer 0's
+// rel_attn_embed and the caller's bucket map.  Without the call nothing here differs from the above.
 
 constexpr int kHubExtLayers = 7;
 static const int kHubExtK[kHubExtLayers] = {10, 3, 3, 3, 3, 2, 2};
@@ -39,6 +44,7 @@ constexpr size_t kHubExtBudget = (size_t)512 << 20;  // bytes of layer-0 rows pe
 struct HubertEncLayer {
     ConvLayer qkv, wo, l1, l2;
     float* d_ln[4] = {nullptr, nullptr, nullptr, nullptr};  // layer_norm.weight, .bias, final_layer_norm.weight, .bias
+    float* d_gate[3] = {nullptr, nullptr, nullptr};         // rel_bias: gru_rel_pos_linear.weight (8, 64), .bias (8), gru_rel_pos_const (heads)
 };
 
 struct hificar_hubert {
@@ -56,6 +62,11 @@ struct hificar_hubert {
     float* d_enc_ln[2] = {nullptr, nullptr};
     float* d_pos_w = nullptr;  // hubert_posconv_kernel's lane-ordered weights
     float* d_pos_b = nullptr;
+    // hificar_hubert_set_rel_bias (WavLM): the attention adds gate[b, h, q] bias_d[h][clamp(k - q)] to its scores
+    bool rel_bias = false;
+    int num_buckets = 0, max_distance = 0;
+    std::vector<int32_t> bucket_of;  // [2 max_distance + 1], host
+    float* d_bias = nullptr;         // [heads][2 max_distance + 1]: rel_attn_embed folded with bucket_of at finalize
     int precision = HIFICAR_PREC_F32;  // hificar_hubert_set_precision: which fragments finalize packs and which kernels the forward launches
     bool finalized = false;
     int sub_batch = 0;  // hificar_hubert_debug_sub_batch: utterances per extractor sub-batch (0: by kHubExtBudget)
@@ -77,6 +88,9 @@ static bool hubert_dims(int L, HubertDims* d) {
     for (int i = 0; i < kHubExtLayers; ++i) d->P[i] = i + 1 < kHubExtLayers ? round_up(d->T[i], 2) : d->T[i];
     return true;
 }
+
+static const char* const kHubRelBiasA16 =
+    "HuBERT: the gated relative position bias (WavLM) is not built for bf16x3a: hubert_attn16_kernel has no bias term (f32 and bf16x3 are built)";
 
 // the handle's GEMMs run in the engine's bf16x3 kernels (bf16x3 and bf16x3a differ in the attention alone)
 static bool hubert_x3(const hificar_hubert* g) { return g->precision != HIFICAR_PREC_F32; }
@@ -214,7 +228,36 @@ extern "C" int hificar_hubert_set_precision(hificar_hubert* g, int precision) {
     if (g->finalized)
         return fail(HIFICAR_E_STATE, "hificar_hubert_set_precision after hificar_hubert_finalize: the weights are packed for %s only; make a new handle",
                     xfmr_precision_name(g->precision));
+    if (precision == HIFICAR_PREC_BF16X3A && g->rel_bias) return fail(HIFICAR_E_INVALID, "%s", kHubRelBiasA16);
     g->precision = precision;
+    return HIFICAR_OK;
+}
+
+extern "C" int hificar_hubert_set_rel_bias(hificar_hubert* g, int num_buckets, int max_distance, const int32_t* bucket_of_distance) {
+    if (!g || !bucket_of_distance) return fail(HIFICAR_E_INVALID, "hificar_hubert_set_rel_bias: null argument");
+    if (g->finalized) return fail(HIFICAR_E_STATE, "hificar_hubert_set_rel_bias after hificar_hubert_finalize");
+    if (num_buckets < 2 || num_buckets % 2 != 0 || num_buckets > HIFICAR_HUBERT_MAX_BUCKETS)
+        return fail(HIFICAR_E_INVALID, "hificar_hubert_set_rel_bias: num_buckets=%d must be even and in 2 .. %d", num_buckets, HIFICAR_HUBERT_MAX_BUCKETS);
+    if (max_distance < 1 || max_distance > HIFICAR_HUBERT_MAX_DISTANCE)
+        return fail(HIFICAR_E_INVALID, "hificar_hubert_set_rel_bias: max_distance=%d outside 1 .. %d", max_distance, HIFICAR_HUBERT_MAX_DISTANCE);
+    if (g->precision == HIFICAR_PREC_BF16X3A) return fail(HIFICAR_E_INVALID, "%s", kHubRelBiasA16);
+    for (int i = 0; i < 2 * max_distance + 1; ++i)
+        if (bucket_of_distance[i] < 0 || bucket_of_distance[i] >= num_buckets)
+            return fail(HIFICAR_E_INVALID, "hificar_hubert_set_rel_bias: bucket_of_distance[%d]=%d outside 0 .. %d", i, (int)bucket_of_distance[i], num_buckets - 1);
+    if (g->rel_bias) g->expected.erase("encoder.layers.0.attention.rel_attn_embed.weight");  // (a second call: the table's shape may differ)
+    g->tensors.erase("encoder.layers.0.attention.rel_attn_embed.weight");
+    g->rel_bias = true;
+    g->num_buckets = num_buckets;
+    g->max_distance = max_distance;
+    g->bucket_of.assign(bucket_of_distance, bucket_of_distance + 2 * max_distance + 1);
+    const int64_t heads = g->cfg.num_attention_heads;
+    g->expected["encoder.layers.0.attention.rel_attn_embed.weight"] = {num_buckets, heads};
+    for (int l = 0; l < g->cfg.num_hidden_layers; ++l) {
+        const std::string b = "encoder.layers." + std::to_string(l) + ".attention.";
+        g->expected[b + "gru_rel_pos_linear.weight"] = {8, kHubHeadDim};
+        g->expected[b + "gru_rel_pos_linear.bias"] = {8};
+        g->expected[b + "gru_rel_pos_const"] = {1, heads, 1, 1};
+    }
     return HIFICAR_OK;
 }
 
@@ -305,8 +348,23 @@ extern "C" int hificar_hubert_finalize(hificar_hubert* g) {
         int i = 0;
         for (const char* n : {"layer_norm.weight", "layer_norm.bias", "final_layer_norm.weight", "final_layer_norm.bias"})
             if ((rc = upload(h, vec(b + n), &E.d_ln[i++])) != HIFICAR_OK) return rc;
+        if (g->rel_bias) {
+            i = 0;
+            for (const char* n : {"attention.gru_rel_pos_linear.weight", "attention.gru_rel_pos_linear.bias", "attention.gru_rel_pos_const"})
+                if ((rc = upload(h, vec(b + n), &E.d_gate[i++])) != HIFICAR_OK) return rc;
+        }
     }
-    if (g->precision == HIFICAR_PREC_BF16X3A) HIP_TRY(hubert_attn16_attr<kHubHeadDim>());
+    if (g->rel_bias) {  // bias_d[h][d + D] = rel_attn_embed[bucket(d)][h]: the one table the attention reads
+        const std::vector<float>& emb = vec("encoder.layers.0.attention.rel_attn_embed.weight");
+        const int heads = g->cfg.num_attention_heads, W = 2 * g->max_distance + 1;
+        std::vector<float> table((size_t)heads * W);
+        for (int hd = 0; hd < heads; ++hd)
+            for (int i = 0; i < W; ++i) table[(size_t)hd * W + i] = emb[(size_t)g->bucket_of[(size_t)i] * heads + hd];
+        if ((rc = upload(h, table, &g->d_bias)) != HIFICAR_OK) return rc;
+        HIP_TRY(hipFuncSetAttribute(x3 ? reinterpret_cast<const void*>(&hubert_attn_kernel<kHubHeadDim, true, true>)
+                                       : reinterpret_cast<const void*>(&hubert_attn_kernel<kHubHeadDim, false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)HubertAttnLds<kHubHeadDim, true>::bytes));
+    } else if (g->precision == HIFICAR_PREC_BF16X3A) HIP_TRY(hubert_attn16_attr<kHubHeadDim>());
     else
         HIP_TRY(hipFuncSetAttribute(x3 ? reinterpret_cast<const void*>(&hubert_attn_kernel<kHubHeadDim, true>)
                                        : reinterpret_cast<const void*>(&hubert_attn_kernel<kHubHeadDim>),
@@ -335,6 +393,7 @@ struct HubertWorkspace {
     float* feat;    // [M][C]: layer 6's rows of the whole batch, then their LayerNorm (bf16x3: as split rows)
     float* r[4];    // [M][H]
     float* wide;    // [M][max(3 H, I)]
+    float* gates;   // rel_bias: [B][heads][T], one layer's, reused by the next (null without)
     int Bs;         // utterances per extractor sub-batch
     size_t bytes;
 };
@@ -364,7 +423,10 @@ static HubertWorkspace hubert_plan_workspace(const hificar_hubert* g, int B, con
     w.feat = reinterpret_cast<float*>(p + sb + fb + ab + bb);
     for (int i = 0; i < 4; ++i) w.r[i] = reinterpret_cast<float*>(p + sb + fb + ab + bb + cb + i * rb);
     w.wide = reinterpret_cast<float*>(p + sb + fb + ab + bb + cb + 4 * rb);
-    w.bytes = sb + fb + ab + bb + cb + 4 * rb + wb;
+    // (the gates only: the (heads, T, T) bias never exists)
+    const size_t gb = g->rel_bias ? round_up_sz((size_t)B * (size_t)g->cfg.num_attention_heads * (size_t)d.T[6] * sizeof(float), 256) : 0;
+    w.gates = g->rel_bias ? reinterpret_cast<float*>(p + sb + fb + ab + bb + cb + 4 * rb + wb) : nullptr;
+    w.bytes = sb + fb + ab + bb + cb + 4 * rb + wb + gb;
     return w;
 }
 
@@ -450,7 +512,7 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
 
     // split (bf16x3): dst takes split rows instead of fp32 rows — 1: rows of their own, 2: window rows of two positions (dst must not be src)
     auto layer_norm = [&](const float* src, const float* gamma, const float* beta, float* dst, int nseq, int rows, int rows_in, int rows_out, int F, float eps,
-                          const int* lens, bool gelu, int split = 0) {
+                          const int* lens, bool gelu, int split = 0, const HubertEncLayer* gate = nullptr) {
         HubertLnParams p;
         p.x = src;
         p.gamma = gamma;
@@ -465,6 +527,17 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
         p.eps = eps;
         p.window = split == 2;
         const double n = (double)nseq * rows;
+        if (gate) {  // (a layer's first LayerNorm under rel_bias: no GELU, no window)
+            p.gate_w = gate->d_gate[0];
+            p.gate_b = gate->d_gate[1];
+            p.gate_c = gate->d_gate[2];
+            p.gates = ws.gates;
+            ProfScope prof(h, stream, split ? "hubert_ln_kernel<gate,split>" : "hubert_ln_kernel<gate>", 8.0 * n * F + 2.0 * n * 8 * F, 8.0 * n * F);
+            const dim3 grid((unsigned)(((long long)nseq * rows + 3) / 4));
+            if (split) hipLaunchKernelGGL((hubert_ln_kernel<false, true, true>), grid, dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((hubert_ln_kernel<false, false, true>), grid, dim3(256), 0, stream, p);
+            return hipGetLastError();
+        }
         ProfScope prof(h, stream, split ? (gelu ? "hubert_ln_kernel<gelu,split>" : "hubert_ln_kernel<split>") : gelu ? "hubert_ln_kernel<gelu>" : "hubert_ln_kernel",
                        8.0 * n * F, 8.0 * n * F);
         const dim3 grid((unsigned)(((long long)nseq * rows + 3) / 4));
@@ -572,7 +645,10 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
     const int nrun = layer < 0 ? c.num_hidden_layers : layer;  // hidden_states[k] is the stream in front of layer k
     for (int l = 0; l < nrun; ++l) {
         const HubertEncLayer& E = g->enc[(size_t)l];
-        HIP_TRY(layer_norm(cur, E.d_ln[0], E.d_ln[1], N, B, T, T, T, H, c.layer_norm_eps, ws.frames, false, sp));
+        HIP_TRY(layer_norm(cur, E.d_ln[0], E.d_ln[1], N, B, T, T, T, H, c.layer_norm_eps, ws.frames, false, sp, g->rel_bias ? &E : nullptr));
+        if (g->rel_bias && (rc = hubert_emit_tap(g, "gate." + std::to_string(l), ws.gates, 0, B, B, (size_t)c.num_attention_heads,
+                                                 (size_t)c.num_attention_heads, (size_t)T, stream)) != HIFICAR_OK)
+            return rc;
         if ((rc = a16 ? conv(E.qkv, N, nullptr, nullptr, ws.wide) : conv(E.qkv, N, nullptr, ws.wide)) != HIFICAR_OK) return rc;
         if (a16) {
             HubertAttn16Params p;
@@ -594,10 +670,19 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
             p.T = T;
             p.F = H;
             p.scale = (float)(1.0 / std::sqrt((double)kHubHeadDim));
-            ProfScope prof(h, stream, x3 ? "hubert_attn_kernel<split>" : "hubert_attn_kernel", 4.0 * M * T * H, 4.0 * M * 4 * H);  // (every key of a full-length batch)
+            p.gates = ws.gates;
+            p.bias = g->d_bias;
+            p.maxd = g->max_distance;
+            ProfScope prof(h, stream, g->rel_bias ? (x3 ? "hubert_attn_kernel<relbias,split>" : "hubert_attn_kernel<relbias>")
+                                      : x3        ? "hubert_attn_kernel<split>"
+                                                  : "hubert_attn_kernel",
+                           4.0 * M * T * H, 4.0 * M * 4 * H);  // (every key of a full-length batch)
             const dim3 grid((unsigned)((T + kXfmrTQ - 1) / kXfmrTQ), (unsigned)c.num_attention_heads, (unsigned)B);
             // (bf16x3: the instantiation that stores split rows)
-            if (x3) hipLaunchKernelGGL((hubert_attn_kernel<kHubHeadDim, true>), grid, dim3(256), HubertAttnLds<kHubHeadDim>::bytes, stream, p);
+            constexpr size_t rel_lds = HubertAttnLds<kHubHeadDim, true>::bytes;
+            if (g->rel_bias && x3) hipLaunchKernelGGL((hubert_attn_kernel<kHubHeadDim, true, true>), grid, dim3(256), rel_lds, stream, p);
+            else if (g->rel_bias) hipLaunchKernelGGL((hubert_attn_kernel<kHubHeadDim, false, true>), grid, dim3(256), rel_lds, stream, p);
+            else if (x3) hipLaunchKernelGGL((hubert_attn_kernel<kHubHeadDim, true>), grid, dim3(256), HubertAttnLds<kHubHeadDim>::bytes, stream, p);
             else hipLaunchKernelGGL(hubert_attn_kernel<kHubHeadDim>, grid, dim3(256), HubertAttnLds<kHubHeadDim>::bytes, stream, p);
             HIP_TRY(hipGetLastError());
         }

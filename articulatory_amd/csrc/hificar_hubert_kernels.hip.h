@@ -12,6 +12,8 @@
 // whose shape depends on the batch.  The bf16x3 forward's instantiations (hubert_conv0_kernel<true>, hubert_ln_kernel<GELU, true>,
 // hubert_gelu_split_kernel, hubert_attn_kernel<D, true>) differ in the FORMAT they store — split rows for the bf16x3 GEMM that reads them
 // (xfmr_store_split) — not in how they compute.
+// WavLM's gated relative position bias (hificar_hubert_set_rel_bias): hubert_ln_kernel<false, SPLIT, true> also forms the attention's gates
+// from the normalised row it holds in registers, and hubert_attn_kernel<D, SPLIT, true> adds gate[q] bias_d[h][k - q] to every score.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -71,9 +73,24 @@ __global__ __launch_bounds__(256) void hubert_frames_kernel(const int* __restric
 // SPLIT: the row goes out as split rows instead of fp32: hi at ys, lo 2 FS bytes behind it (FS = F: a row of its own [hi: F | lo: F];
 // FS = 2 F: one position's half of a window row [hi: 2 F | lo: 2 F], hificar_hubert.hip.inc).  F % 8 == 0 there: lanes i and i ^ 1 hold
 // eight adjacent channels and are active together.
-template <bool SPLIT = false>
+// What the gate of WavLM's relative position bias reads (hubert_ln_row<SPLIT, true>): gru_rel_pos_linear (8, 64) and its bias (8),
+// gru_rel_pos_const (heads), and where the row's gates go: out[head * stride], one float per head.
+struct HubertGateArgs {
+    const float* w;
+    const float* b;
+    const float* c;
+    float* out;
+    size_t stride;
+};
+
+// GATE: the gates of the row, from the normalised values before they are stored — the same registers in either format, so an f32 and a bf16x3
+// model form the same bits.  F is a multiple of 64 there (heads of 64 channels): the float4 of index i = lane + 64 j belongs to head i / 16 =
+// lane / 16 + 4 j, so a head's 64 channels lie in one 16-lane group of one j.  A lane forms its four channels' part of the eight projections
+// (channels in order), sums them as (p0 + p1) + (p2 + p3) and (p4 + p5) + (p6 + p7), and the group adds its 16 lanes by a butterfly (xor 1,
+// 2, 4, 8); the biases go on last.  gate = a (b const - 1) + 2 with a, b the sigmoids of the two sums.
+template <bool SPLIT = false, bool GATE = false>
 __device__ __forceinline__ void hubert_ln_row(float4 (&v)[4], int lane, int nv, int F, float eps, const float* gamma, const float* beta, bool gelu,
-                                              float* yrow, char* ys = nullptr, int FS = 0) {
+                                              float* yrow, char* ys = nullptr, int FS = 0, const HubertGateArgs* gate = nullptr) {
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -100,6 +117,34 @@ __device__ __forceinline__ void hubert_ln_row(float4 (&v)[4], int lane, int nv, 
         if (gelu) r = make_float4(hubert_gelu(r.x), hubert_gelu(r.y), hubert_gelu(r.z), hubert_gelu(r.w));
         if constexpr (SPLIT) xfmr_store_split(ys, FS, 4 * i, i & 1, 1, r.x, r.y, r.z, r.w, true);
         else y[i] = r;
+        if constexpr (GATE) v[j] = r;  // (kept for the gates below: the wave leaves the loop before it shuffles)
+    }
+    if constexpr (GATE) {
+        const int c = lane & 15;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (64 * j >= nv) break;  // (wave-uniform)
+            const bool in = lane + 64 * j < nv;  // (nv is a multiple of 16: a 16-lane group is in or out together)
+            float pk[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float4 w = reinterpret_cast<const float4*>(gate->w + k * kHubHeadDim)[c];
+                pk[k] = in ? fmaf(w.w, v[j].w, fmaf(w.z, v[j].z, fmaf(w.y, v[j].y, w.x * v[j].x))) : 0.f;
+            }
+            float sa = (pk[0] + pk[1]) + (pk[2] + pk[3]), sb = (pk[4] + pk[5]) + (pk[6] + pk[7]);
+#pragma unroll
+            for (int m = 1; m <= 8; m <<= 1) {
+                sa += __shfl_xor(sa, m);
+                sb += __shfl_xor(sb, m);
+            }
+            if (in && c == 0) {
+                const int head = (lane >> 4) + 4 * j;
+                sa += (gate->b[0] + gate->b[1]) + (gate->b[2] + gate->b[3]);
+                sb += (gate->b[4] + gate->b[5]) + (gate->b[6] + gate->b[7]);
+                const float ga = 1.f / (1.f + expf(-sa)), gb = 1.f / (1.f + expf(-sb));
+                gate->out[(size_t)head * gate->stride] = ga * (gb * gate->c[head] - 1.f) + 2.f;
+            }
+        }
     }
 }
 
@@ -186,9 +231,15 @@ struct HubertLnParams {
     int B, T, Tin, Tout, F;
     float eps;
     int window = 0;
+    // GATE: gru_rel_pos_linear's weight (8, 64) and bias (8), gru_rel_pos_const (heads), and gates (B, heads, T): row t of sequence b writes
+    // gates[(b heads + head) T + t]
+    const float* gate_w = nullptr;
+    const float* gate_b = nullptr;
+    const float* gate_c = nullptr;
+    float* gates = nullptr;
 };
 
-template <bool GELU, bool SPLIT = false>
+template <bool GELU, bool SPLIT = false, bool GATE = false>
 __global__ __launch_bounds__(256) void hubert_ln_kernel(const HubertLnParams p) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -204,12 +255,14 @@ __global__ __launch_bounds__(256) void hubert_ln_kernel(const HubertLnParams p) 
         const int i = lane + 64 * j;
         v[j] = i < nv ? x[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    HubertGateArgs ga;
+    if constexpr (GATE) ga = HubertGateArgs{p.gate_w, p.gate_b, p.gate_c, p.gates + (size_t)b * (p.F / kHubHeadDim) * p.T + t, (size_t)p.T};
     if constexpr (SPLIT) {
         char* const seq = reinterpret_cast<char*>(p.y + (size_t)b * p.Tout * p.F);
-        hubert_ln_row<true>(v, lane, nv, p.F, p.eps, p.gamma, p.beta, GELU, nullptr, p.window ? hubert_window_ptr(seq, t, p.F) : seq + (size_t)t * p.F * 4,
-                            p.window ? 2 * p.F : p.F);
+        hubert_ln_row<true, GATE>(v, lane, nv, p.F, p.eps, p.gamma, p.beta, GELU, nullptr,
+                                  p.window ? hubert_window_ptr(seq, t, p.F) : seq + (size_t)t * p.F * 4, p.window ? 2 * p.F : p.F, &ga);
     } else {
-        hubert_ln_row(v, lane, nv, p.F, p.eps, p.gamma, p.beta, GELU, p.y + ((size_t)b * p.Tout + t) * p.F);
+        hubert_ln_row<false, GATE>(v, lane, nv, p.F, p.eps, p.gamma, p.beta, GELU, p.y + ((size_t)b * p.Tout + t) * p.F, nullptr, 0, &ga);
     }
 }
 
@@ -351,6 +404,12 @@ __global__ __launch_bounds__(256) void hubert_posconv_kernel(const HubertPosPara
 // of `out` not written.  The head count is the grid's y extent.  The order of every sum depends on the sequence's length only.
 // SPLIT (the bf16x3 forward): `out` is out_proj's input and nothing else, so the rows are stored as split rows only (out: [B T][4 F bytes]),
 // as xfmr_attn_kernel<D, false, true> stores them.
+// RELBIAS (WavLM): S[q, k] += gate[b, h, q] bias[h][clamp(k - q, -maxd, maxd) + maxd] in fp32, behind the scaling and in front of the running
+// maximum.  A lane loads its query's gate once.  Per key block the workgroup stages, between the barriers that fence the K and V tiles, the
+// 127 entries of the head's table that the block's 64 x 64 (key, query) pairs can meet: rel[j] = bias[h][clamp(kb - q0 - 63 + j)], so key
+// kb + kk against query q0 + ql reads rel[kk - ql + 63].  512 bytes of LDS behind the V tile.  Banks: a wave's ds_read_b32 for register i of
+// key block sb reads index 16 sb + 4 g + i - 16 w - c + 63 — within a 32-lane half (two values of g, sixteen of c) 20 consecutive dwords, equal
+// indices the same address (broadcast): conflict-free in both directions.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct HubertAttnParams {
     const float* qkv;    // [B T][3 F]: q | k | v, each [head][d]
@@ -358,19 +417,26 @@ struct HubertAttnParams {
     float* out;          // [B T][F]: [head][d]
     int T, F;
     float scale;         // 1 / sqrt(d)
+    const float* gates = nullptr;  // RELBIAS: (B, heads, T)
+    const float* bias = nullptr;   //          [heads][2 maxd + 1]
+    int maxd = 0;
 };
 
-template <int D>
+constexpr int kHubRelSlice = 2 * kXfmrKB;  // 127 entries used
+
+template <int D, bool RELBIAS = false>
 struct HubertAttnLds {
-    static constexpr size_t bytes = (size_t)2 * kXfmrKB * (D + 4) * sizeof(float);
+    static constexpr size_t bytes = ((size_t)2 * kXfmrKB * (D + 4) + (RELBIAS ? kHubRelSlice : 0)) * sizeof(float);
 };
 
-template <int D, bool SPLIT = false>
+template <int D, bool SPLIT = false, bool RELBIAS = false>
 __global__ __launch_bounds__(256) void hubert_attn_kernel(const HubertAttnParams p) {
+    static_assert(kXfmrKB == 64 && kXfmrTQ == 64, "the relative-bias slice is laid out for 64 keys x 64 queries");
     extern __shared__ float hubert_lds[];
     constexpr int PT = D + 4, NS = D / 4, NM = D / 16;
     float* const kbuf = hubert_lds;
     float* const vbuf = hubert_lds + kXfmrKB * PT;
+    float* const rel = hubert_lds + 2 * kXfmrKB * PT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kXfmrTQ;
@@ -387,6 +453,12 @@ __global__ __launch_bounds__(256) void hubert_attn_kernel(const HubertAttnParams
 #pragma unroll
         for (int s = 0; s < NS; ++s) qf[s] = qok ? qrow[4 * s + g] : 0.f;
     }
+    float gq = 0.f;  // this lane's query's gate
+    const float* relq = rel;
+    if constexpr (RELBIAS) {
+        if (qok) gq = p.gates[((size_t)b * gridDim.y + h) * p.T + q];
+        relq = rel + 63 - (wave * 16 + c) + 4 * g;  // + 16 sb + i: 0 .. 126
+    }
     float m = -INFINITY, l = 0.f;
     f32x4 o[NM];
 #pragma unroll
@@ -397,6 +469,10 @@ __global__ __launch_bounds__(256) void hubert_attn_kernel(const HubertAttnParams
         __syncthreads();
         xfmr_stage<D>(kbuf, p.qkv + (row0 + kb) * F3 + p.F + h * D, F3, n, tid);
         xfmr_stage<D>(vbuf, p.qkv + (row0 + kb) * F3 + 2 * p.F + h * D, F3, n, tid);
+        if constexpr (RELBIAS) {
+            if (tid < kHubRelSlice - 1)
+                rel[tid] = p.bias[(size_t)h * (2 * p.maxd + 1) + (min(max(kb - q0 - 63 + tid, -p.maxd), p.maxd) + p.maxd)];
+        }
         __syncthreads();
 
         f32x4 s[4];
@@ -412,7 +488,8 @@ __global__ __launch_bounds__(256) void hubert_attn_kernel(const HubertAttnParams
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (qok && 16 * sb + 4 * g + i < n) {
-                    const float v = s[sb][i] * p.scale;
+                    float v = s[sb][i] * p.scale;
+                    if constexpr (RELBIAS) v += gq * relq[16 * sb + i];
                     s[sb][i] = v;
                     mb = fmaxf(mb, v);
                     valid |= 1u << (4 * sb + i);

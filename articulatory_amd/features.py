@@ -9,7 +9,10 @@ The arithmetic restates librosa 0.8.1's published algorithm (``stft(center=True,
 The z-score of ``wav2mfcc`` is not part of ``MFCC``: ``model.forward_lowrate(feats, lengths=frames, interp_factor=1, zscore=True)`` does it.
 
 ``HuBERT`` — the speech model in front of the reference's SSL inversion models (``*_h2``) — has the same call shape but owns parameters: a
-``torch.nn.Module`` with the ``transformers`` library's ``HubertModel`` state_dict over a ``hificar_hubert_*`` handle (below).
+``torch.nn.Module`` with the ``transformers`` library's ``HubertModel`` state_dict over a ``hificar_hubert_*`` handle (below).  ``WavLM`` is the
+same encoder with WavLM-large's gated relative position bias (``WavLMModel``'s state_dict), the speech model of the reference's
+``egs/ema/voc1/local/linear_inference.py``; ``ssl_encoder_from_pretrained`` picks the class by a directory's ``config.json``, and ``LinearHead``
+is that script's fitted linear regression on the device.
 """
 
 import ctypes
@@ -223,17 +226,20 @@ class HuBERT(_feature_model.NativeFeatureModel):
     float64 restatement.  Keyword or ``set_precision``; kept by copies, pickles and ``load_state_dict``, not part of the ``state_dict``.
 
     ``config``: a mapping with the keys of the model's ``config.json`` (missing keys: the large model's).  Not built, refused at
-    construction: group-norm extractors and post-LN encoders (HuBERT-base), WavLM's gated relative position bias, adapters, head sizes other
-    than 64; ``masked_spec_embed`` is held for ``strict=True`` and never used (spec-augment is a training device)."""
+    construction: group-norm extractors and post-LN encoders (HuBERT-base), WavLM's gated relative position bias (``features.WavLM`` reads
+    those configurations), adapters, head sizes other than 64; ``masked_spec_embed`` is held for ``strict=True`` and never used (spec-augment
+    is a training device)."""
 
     _PREFIX = "hificar_hubert"
     _NAME = "HuBERT"
+    _PRECISIONS = _native.HUBERT_PRECISIONS
+    _check_config = staticmethod(_native.check_hubert_config)
     sampling_rate = 16000
 
     def __init__(self, config=None, normalize=True, norm_eps=1e-7, precision="f32"):
         super().__init__()
         self.precision = self._check_precision(precision)
-        c = _native.check_hubert_config(dict(config or {}))
+        c = self._check_config(dict(config or {}))
         self.config = c
         self.normalize, self.norm_eps = bool(normalize), float(norm_eps)
         C, H, I = c["conv_dim"][0], c["hidden_size"], c["intermediate_size"]
@@ -259,14 +265,18 @@ class HuBERT(_feature_model.NativeFeatureModel):
             _Holder(attention=_Holder(k_proj=Lin(H, H), v_proj=Lin(H, H), q_proj=Lin(H, H), out_proj=Lin(H, H)), layer_norm=LN(H, eps=c["layer_norm_eps"]),
                     feed_forward=_Holder(intermediate_dense=Lin(H, I), output_dense=Lin(I, H)), final_layer_norm=LN(H, eps=c["layer_norm_eps"]))
             for _ in range(c["num_hidden_layers"])))
+        self._extend(c)
         self._params = {"in_channels": 1, "out_channels": H}
         self._init_native()
         self.eval()
 
-    @staticmethod
-    def _check_precision(precision):
-        if not isinstance(precision, str) or precision not in _native.HUBERT_PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(_native.HUBERT_PRECISIONS)}")
+    def _extend(self, c):
+        """Parameter holders a subclass adds to the hierarchy, before the native state is set up."""
+
+    @classmethod
+    def _check_precision(cls, precision):
+        if not isinstance(precision, str) or precision not in cls._PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(cls._PRECISIONS)}")
         return precision
 
     def set_precision(self, precision):
@@ -315,7 +325,7 @@ class HuBERT(_feature_model.NativeFeatureModel):
 
     def train(self, mode=True):
         if mode:
-            raise NotImplementedError("HuBERT: training (dropout, spec-augment, layerdrop, a backward pass) is not built; the module is inference-only")
+            raise NotImplementedError(f"{self._NAME}: training (dropout, spec-augment, layerdrop, a backward pass) is not built; the module is inference-only")
         return super().train(False)
 
     @classmethod
@@ -412,4 +422,220 @@ class HuBERT(_feature_model.NativeFeatureModel):
         return out, frames
 
     def forward_lowrate(self, *a, **kw):
-        raise NotImplementedError("HuBERT has no low-rate front end: it IS the front end (its output goes into a model's forward_lowrate)")
+        raise NotImplementedError(f"{self._NAME} has no low-rate front end: it IS the front end (its output goes into a model's forward_lowrate)")
+
+
+class WavLM(HuBERT):
+    """The WavLM encoder of the "large" family (``wavlm-large``'s architecture: HuBERT-large's extractor, projection, positional conv,
+    stable-layer-norm layers and final LayerNorm, plus the gated relative position bias in every layer's attention), the speech model whose
+    ``hidden_states[9]`` the reference's ``egs/ema/voc1/local/linear_inference.py`` feeds to a fitted linear regression.  ``state_dict()`` has
+    the keys and shapes of the ``transformers`` library's ``WavLMModel`` in its order and loads with ``strict=True``.  Same call shape,
+    ``from_pretrained``, pickling, ``debug_tap`` and ``workspace_bytes`` as ``HuBERT``:
+
+        feats, frames = wavlm(wav, lengths=samples, layer=9)            # (B, 1024, Tmax) at 50 Hz; layers 9 .. 23 are not run
+        ema = head(feats, frames)                                       # features.LinearHead
+
+    The attention's scores are ``Q K / sqrt(d) + gate[b, h, q] * rel_attn_embed[bucket(k - q), h]``: layer 0 owns the embedding
+    (``num_buckets`` rows), every layer its own gate (``gru_rel_pos_linear``, ``gru_rel_pos_const``) computed from the layer's attention input.
+    The bucket of every distance is computed here, once, with torch's float32 operations (``_native.wavlm_bucket_of_distance``) and handed to
+    ``hificar_hubert_set_rel_bias``; the (heads, T, T) bias the library materialises never exists on the device.  The debug tap ``"gate.<l>"``
+    is (B, heads, Tmax): the gates layer l used.
+
+    ``precision``: ``"f32"`` (default) or ``"bf16x3"`` (``HuBERT``'s; the gates are the same bits in both).  ``"bf16x3a"`` is refused: the
+    bf16 attention kernel has no bias term.  ``config``: missing keys take the large model's values, ``num_buckets`` 320 and
+    ``max_bucket_distance`` 800.  Not built, refused at construction: group-norm extractors and post-LN encoders (``wavlm-base``,
+    ``wavlm-base-plus``), adapters, head sizes other than 64.  s3prl's ``hidden_states[k]`` is, by reading its code, the stream in front of
+    layer k, the same as the library's and as ``layer=k`` here; s3prl is not on hand, so this is unverified."""
+
+    _NAME = "WavLM"
+    _PRECISIONS = _native.WAVLM_PRECISIONS
+    _check_config = staticmethod(_native.check_wavlm_config)
+
+    @classmethod
+    def _check_precision(cls, precision):
+        if precision == "bf16x3a":
+            raise ValueError("WavLM: precision='bf16x3a' is not built: the bf16 attention kernel has no relative position bias "
+                             f"(choose from {sorted(cls._PRECISIONS)})")
+        return super()._check_precision(precision)
+
+    def _extend(self, c):
+        heads = c["num_attention_heads"]
+        for l, layer in enumerate(self.encoder.layers):
+            att = layer.attention
+            att.gru_rel_pos_linear = torch.nn.Linear(_native.HUBERT_HEAD_DIM, 8)
+            if l == 0:
+                att.rel_attn_embed = torch.nn.Embedding(c["num_buckets"], heads)
+            att.gru_rel_pos_const = torch.nn.Parameter(torch.ones(1, heads, 1, 1))
+
+    @staticmethod
+    def _is_rel_bias(key):
+        return "gru_rel_pos" in key or key.endswith("rel_attn_embed.weight")
+
+    def native_state(self):
+        """``HuBERT.native_state`` without the relative bias's tensors: hificar_hubert_set_weight takes those only once
+        hificar_hubert_set_rel_bias was called (``rel_bias_state``, ``_finalize_handle``)."""
+        return {k: v for k, v in super().native_state().items() if not self._is_rel_bias(k)}
+
+    def rel_bias_state(self):
+        """{name: fp32 CPU tensor} of ``rel_attn_embed`` and every layer's ``gru_rel_pos_linear`` / ``gru_rel_pos_const``."""
+        return {k: v for k, v in super().native_state().items() if self._is_rel_bias(k)}
+
+    def _finalize_handle(self, handle):
+        c = self.config
+        self._call("_set_precision", handle, _native.WAVLM_PRECISIONS[self.precision])
+        table = _native.wavlm_bucket_of_distance(c["num_buckets"], c["max_bucket_distance"])
+        self._call("_set_rel_bias", handle, c["num_buckets"], c["max_bucket_distance"], table.data_ptr())
+        for name, t in self.rel_bias_state().items():
+            shape = (ctypes.c_int64 * t.dim())(*t.shape)
+            self._call("_set_weight", handle, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim())
+        self._call("_finalize", handle)
+
+
+def ssl_encoder_from_pretrained(directory, **kw):
+    """``HuBERT.from_pretrained`` or ``WavLM.from_pretrained`` by the ``model_type`` of ``directory``'s ``config.json`` (absent: HuBERT, unless
+    the configuration has WavLM's ``num_buckets``).  Keywords as theirs."""
+    return ssl_encoder_class(directory).from_pretrained(directory, **kw)
+
+
+def ssl_encoder_class(directory):
+    """The class ``ssl_encoder_from_pretrained`` loads ``directory`` with, from its ``config.json`` alone."""
+    import json
+    import os
+
+    with open(os.path.join(directory, "config.json")) as f:
+        config = json.load(f)
+    model_type = str(config.get("model_type", "wavlm" if "num_buckets" in config else "hubert")).lower()
+    if model_type not in ("hubert", "wavlm"):
+        raise NotImplementedError(f"{directory}: model_type {model_type!r}: only 'hubert' (features.HuBERT) and 'wavlm' (features.WavLM) are built")
+    return WavLM if model_type == "wavlm" else HuBERT
+
+
+class LinearHead(torch.nn.Module):
+    """``y = coef x + intercept`` over device features: (B, H, T) -> (B, out, T), the fitted linear regression the reference's
+    ``egs/ema/voc1/local/linear_inference.py`` applies to ``hidden_states[9]`` of ``wavlm_large``.  It runs in ``libhificar.so`` as the one-tap
+    GEMM every ``Linear`` of this package is (``hificar_linear_*`` of include/hificar.h; exact fp32 only — the regression is tiny): every
+    utterance is computed as if alone, bit for bit, and rows from an utterance's own frame count on are exact zeros.  No CPU fallback, no
+    backward.
+
+        head = LinearHead.load("linear.joblib").to("cuda")
+        feats, frames = wavlm(wav, lengths=samples, layer=9)
+        ema = head(feats, frames)                                       # (B, out, Tmax)
+
+    ``coef``: (out, H), ``intercept``: (out,) — sklearn's ``coef_`` / ``intercept_`` (a 1-D ``coef_`` is one output)."""
+
+    def __init__(self, coef, intercept):
+        super().__init__()
+        coef = torch.from_numpy(np.array(coef, dtype=np.float32))  # (copies: a fitted model's arrays may be read-only)
+        coef = coef.reshape(1, -1) if coef.dim() == 1 else coef
+        intercept = torch.from_numpy(np.array(intercept, dtype=np.float32)).reshape(-1)
+        if coef.dim() != 2 or intercept.numel() != coef.shape[0]:
+            raise ValueError(f"LinearHead: coef {tuple(coef.shape)} and intercept {tuple(intercept.shape)} do not make out x in and out")
+        if not 1 <= coef.shape[1] <= _native.LINEAR_MAX_IN or not 1 <= coef.shape[0] <= _native.LINEAR_MAX_OUT:
+            raise ValueError(f"LinearHead: {coef.shape[1]} -> {coef.shape[0]} features out of range (1 .. {_native.LINEAR_MAX_IN} in, "
+                             f"1 .. {_native.LINEAR_MAX_OUT} out)")
+        self.register_buffer("coef", coef.contiguous().clone())
+        self.register_buffer("intercept", intercept.contiguous().clone())
+        self._lib = self._handle = self._handle_key = self._workspace_buf = None
+
+    in_features = property(lambda self: self.coef.shape[1])
+    out_features = property(lambda self: self.coef.shape[0])
+
+    @classmethod
+    def load(cls, path):
+        """A head from a ``.joblib`` file — a fitted sklearn ``LinearRegression`` or ``Ridge``, anything with ``coef_`` and ``intercept_``
+        (``joblib`` is imported only here) — or from an ``.npz`` with ``coef`` and ``intercept``."""
+        if str(path).endswith(".npz"):
+            with np.load(path) as z:
+                if "coef" not in z.files or "intercept" not in z.files:
+                    raise ValueError(f"{path}: an .npz head holds 'coef' and 'intercept', this one has {sorted(z.files)}")
+                return cls(z["coef"], z["intercept"])
+        if not str(path).endswith(".joblib"):
+            raise ValueError(f"{path}: a linear head is a .joblib (a fitted sklearn LinearRegression / Ridge) or an .npz with coef / intercept")
+        try:
+            import joblib
+        except ImportError:
+            raise RuntimeError(f"{path}: reading a .joblib head needs the joblib package, which does not import here; save coef_ / intercept_ "
+                               "as an .npz with 'coef' and 'intercept' instead") from None
+        reg = joblib.load(path)
+        if not hasattr(reg, "coef_") or not hasattr(reg, "intercept_"):
+            raise ValueError(f"{path}: {type(reg).__name__} has no coef_ / intercept_ (a fitted LinearRegression or Ridge is read)")
+        coef = np.asarray(reg.coef_)
+        coef = coef.reshape(1, -1) if coef.ndim == 1 else coef
+        return cls(coef, np.broadcast_to(np.asarray(reg.intercept_, dtype=np.float64).reshape(-1), (coef.shape[0],)))
+
+    def _invalidate(self):
+        handle, lib = self.__dict__.get("_handle"), self.__dict__.get("_lib")
+        self.__dict__["_handle"] = self.__dict__["_handle_key"] = self.__dict__["_workspace_buf"] = None
+        if handle is not None and lib is not None:
+            lib.hificar_linear_destroy(handle)
+
+    def __del__(self):
+        try:
+            self._invalidate()
+        except Exception:
+            pass
+
+    def __getstate__(self):  # copies and pickles never share a native handle
+        state = self.__dict__.copy()
+        state["_handle"] = state["_lib"] = state["_handle_key"] = state["_workspace_buf"] = None
+        return state
+
+    def _native_handle(self):
+        key = (self.coef.device, self.coef.data_ptr(), self.coef._version, self.intercept.data_ptr(), self.intercept._version)
+        if self._handle is not None and self._handle_key != key:
+            self._invalidate()
+        if self._handle is None:
+            self._lib = _native.load_library()
+            coef, intercept = self.coef.detach().cpu().contiguous(), self.intercept.detach().cpu().contiguous()
+            handle = ctypes.c_void_p()
+            with torch.cuda.device(self.coef.device):
+                _native.check(self._lib.hificar_linear_create(coef.shape[1], coef.shape[0], coef.data_ptr(), intercept.data_ptr(), ctypes.byref(handle)),
+                              "hificar_linear_create")
+            self._handle, self._handle_key = handle, key
+        return self._handle
+
+    def engine(self):
+        """The engine handle for ``hificar_profile_begin`` / ``hificar_profile_end``."""
+        handle = self._native_handle()
+        return ctypes.c_void_p(self._lib.hificar_linear_engine(handle))
+
+    def forward(self, feats, lengths=None):
+        """feats: (B, H, T) float tensor on the device; lengths: B frame counts in 0 .. T (a device int32 tensor — ``frames`` as ``WavLM``
+        returns it — is used as it is; anything else is copied), or None (every sequence has T).  Returns (B, out, T) float32."""
+        if not isinstance(feats, torch.Tensor) or feats.device.type != "cuda":
+            raise RuntimeError("LinearHead needs a CUDA/HIP tensor; there is no CPU fallback")
+        if feats.requires_grad:
+            raise RuntimeError("LinearHead: feats requires grad, and no backward is built (detach it)")
+        if feats.dim() != 3 or feats.shape[1] != self.in_features or not feats.is_floating_point():
+            raise RuntimeError(f"LinearHead: expected a (B, {self.in_features}, T) float tensor, got {tuple(feats.shape)} {feats.dtype}")
+        if feats.device != self.coef.device:
+            raise RuntimeError(f"LinearHead: input on {feats.device}, coefficients on {self.coef.device}")
+        x = feats.detach().to(torch.float32).contiguous()
+        B, _, T = x.shape
+        if B < 1 or T < 1:
+            raise RuntimeError(f"LinearHead: empty batch {tuple(feats.shape)}")
+        lens = None
+        if lengths is not None:
+            lens = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(lengths)
+            lens = lens.detach().reshape(-1).to(x.device, torch.int32).contiguous()
+            if lens.numel() != B:
+                raise RuntimeError(f"LinearHead: lengths has {lens.numel()} entries for a batch of {B}")
+        handle = self._native_handle()
+        lib = self._lib
+        with torch.cuda.device(x.device):
+            n = int(lib.hificar_linear_workspace_bytes(handle, B, T))
+            if n == 0:
+                raise RuntimeError(f"LinearHead: B={B}, T={T} out of range (B <= 65535, B T max(in, out) < 2^31)")
+            ws = self._workspace_buf
+            if ws is None or ws.device != x.device or ws.numel() < n + 256:
+                # work already enqueued on the old buffer keeps it alive through the caching allocator's stream ordering
+                ws = torch.empty(int((n + 256) * 1.25) if ws is not None else n + 256, dtype=torch.uint8, device=x.device)
+                self._workspace_buf = ws
+            off = (-ws.data_ptr()) % 256
+            out = torch.empty((B, self.out_features, T), dtype=torch.float32, device=x.device)
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            rc = lib.hificar_linear_forward(handle, x.data_ptr(), None if lens is None else lens.data_ptr(), out.data_ptr(), B, T, ws.data_ptr() + off,
+                                            ws.numel() - off, stream)
+        _native.check(rc, "hificar_linear_forward")
+        del lens
+        return out

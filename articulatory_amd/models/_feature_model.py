@@ -114,7 +114,7 @@ class NativeFeatureModel(torch.nn.Module):
         for k, v in self._TRANSIENT.items():
             setattr(self, k, v)
         # drawn from torch's generator (after the parameters): torch.manual_seed makes a training run repeatable
-        self._dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        self._dropout_seed = int(torch.randint(0, 2 ** 62, (1,), device="cpu").item())  # (the CPU generator, also under torch.device("meta"))
         from ..utils.optim_hook import watch
 
         watch(self)  # fused optimizers do not bump Parameter._version: every optimizer.step() over these parameters marks them stale

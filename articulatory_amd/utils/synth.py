@@ -711,3 +711,51 @@ def synth_hubert_state_dict(config, seed: int = 1234, gain: float = 1.0) -> "Ord
         else:
             out[name] = uniform(seed, name, shape, -0.05, 0.05)
     return out
+
+
+# ---- WavLM ("large" family): HuBERT-large with the gated relative position bias -----------------------------------------------------------
+def wavlm_param_spec(config):
+    """Ordered {state_dict key: shape} of the ``transformers`` library's ``WavLMModel`` for a "large"-family configuration: ``hubert_param_spec``
+    with, in every layer's attention, ``gru_rel_pos_const`` (1, heads, 1, 1) in front of the projections and ``gru_rel_pos_linear`` (8, 64)
+    behind them, and layer 0's ``rel_attn_embed`` (num_buckets, heads) last.  Checked key-for-key against the real class by
+    tools/make_golden_wavlm.py (tests/golden/gold_wavlm_keys.txt)."""
+    heads, nb = config.get("num_attention_heads", 16), config.get("num_buckets", 320)
+    H = config.get("hidden_size", 1024)
+    spec = OrderedDict()
+    for k, shape in hubert_param_spec(config).items():
+        if k.endswith(".attention.k_proj.weight"):
+            spec[k[:-len("k_proj.weight")] + "gru_rel_pos_const"] = (1, heads, 1, 1)
+        spec[k] = shape
+        if k.endswith(".attention.out_proj.bias"):
+            b = k[:-len("out_proj.bias")]
+            spec[b + "gru_rel_pos_linear.weight"] = (8, H // heads)
+            spec[b + "gru_rel_pos_linear.bias"] = (8,)
+            if b == "encoder.layers.0.attention.":
+                spec[b + "rel_attn_embed.weight"] = (nb, heads)
+    return spec
+
+
+def synth_wavlm_state_dict(config, seed: int = 1234, gain: float = 1.0) -> "OrderedDict[str, np.ndarray]":
+    """``synth_hubert_state_dict`` in ``WavLMModel``'s layout.  ``rel_attn_embed`` is N(0, 1) (Box-Muller over the name-keyed generator), as
+    large as the scaled dot products, ``gru_rel_pos_const`` U(0.5, 1.5), and the gate's ``Linear`` U(+-0.5 sqrt(3 / 64)) with biases
+    U(+-0.05): over a LayerNorm's output the two four-sums have a deviation near one, so the sigmoids stay off their rails and the gates spread
+    over most of their range — a wrong bucket, sign or gate moves the output by orders of magnitude more than any tolerance."""
+    base = synth_hubert_state_dict(config, seed=seed, gain=gain)
+    out = OrderedDict()
+    for name, shape in wavlm_param_spec(config).items():
+        if name in base:
+            out[name] = base[name]
+        elif name.endswith("rel_attn_embed.weight"):
+            n = int(np.prod(shape))
+            u1 = uniform01(seed, name + "#r", n).astype(np.float64)
+            u2 = uniform01(seed, name + "#a", n).astype(np.float64)
+            z = np.sqrt(-2.0 * np.log(np.maximum(u1, 2.0 ** -40))) * np.cos(2.0 * np.pi * u2)
+            out[name] = z.reshape(shape).astype(np.float32)
+        elif name.endswith("gru_rel_pos_const"):
+            out[name] = uniform(seed, name, shape, 0.5, 1.5)
+        elif name.endswith("gru_rel_pos_linear.weight"):
+            b = 0.5 * np.sqrt(3.0 / shape[1])
+            out[name] = uniform(seed, name, shape, -b, b)
+        else:
+            out[name] = uniform(seed, name, shape, -0.05, 0.05)
+    return out

@@ -1041,8 +1041,8 @@ int hificar_xfmr_backward_packed(hificar_xfmr* h, const float* dout, const int32
  *                  layer k (hidden_states[k] of output_hidden_states = True); layers k and above are then not run
  * Limits: conv_dim a multiple of 32 in 32 .. HIFICAR_HUBERT_MAX_CONV; hidden_size one of 128, 256, 512, 768, 1024 (16 positional groups of 8 ..
  * 64 channels, LayerNorm rows of at most 1024); num_attention_heads = hidden_size / 64; intermediate_size a multiple of 32 in 32 ..
- * HIFICAR_HUBERT_MAX_FFN; 1 .. HIFICAR_HUBERT_MAX_LAYERS layers.  Not built (the binding refuses them): group-norm extractors, post-LN encoders,
- * gated relative position bias, training, dropout, spec-augment.
+ * HIFICAR_HUBERT_MAX_FFN; 1 .. HIFICAR_HUBERT_MAX_LAYERS layers.  Not built (the binding refuses them): group-norm extractors, post-LN encoders
+ * (HuBERT-base, WavLM-base), the gated relative position bias under bf16x3a, training, dropout, spec-augment.
  * Every utterance of a batch is computed as if alone, bit for bit: the conv engine runs with split-K off, every other sum has one order.
  *
  * Opt-in bf16x3 (HIFICAR_PREC_BF16X3): every GEMM on the conv engine — extractor layers 1 - 6, the projection, q | k | v, out_proj,
@@ -1051,8 +1051,16 @@ int hificar_xfmr_backward_packed(hificar_xfmr* h, const float* dout, const int32
  * statistics, layer 0, every LayerNorm and GELU, the positional conv, the attention, biases, residual adds and the residual stream stay fp32.
  * Opt-in bf16x3a (HIFICAR_PREC_BF16X3A): bf16x3, and the attention's two products (Q K^T, P V) in the same three-term form on
  * v_mfma_f32_16x16x32_bf16; the softmax statistics stay fp32.  Both keep "every utterance as if alone, bit for bit" and the workspace's size.
+ *
+ * WavLM (hificar_hubert_set_rel_bias): the same encoder with the gated relative position bias of the library's WavLMAttention,
+ *     S[q, k] = Q[q] . K[k] / sqrt(d) + gate[b, h, q] bias[h][bucket(k - q)],
+ * gate = a (b const[h] - 1) + 2 with a, b the sigmoids of the two four-sums of gru_rel_pos_linear over the head's 64 channels of the layer's
+ * attention input (the LayerNorm's fp32 output, taken from the LayerNorm kernel's registers in either arithmetic: an f32 and a bf16x3 handle
+ * form the same gates, bit for bit).  The (heads, T, T) bias is never formed: the attention reads one table per head.
  * --------------------------------------------------------------------------------------------------------------------------- */
 #define HIFICAR_HUBERT_MAX_CONV 1024
+#define HIFICAR_HUBERT_MAX_BUCKETS 4096
+#define HIFICAR_HUBERT_MAX_DISTANCE 65536
 #define HIFICAR_HUBERT_MAX_HIDDEN 1024
 #define HIFICAR_HUBERT_MAX_FFN 8192
 #define HIFICAR_HUBERT_MAX_LAYERS 48
@@ -1091,6 +1099,20 @@ int hificar_hubert_set_weight(hificar_hubert* h, const char* name, const float* 
  * split bf16 rows only). */
 int hificar_hubert_set_precision(hificar_hubert* h, int precision);
 
+/* Switches the gated relative position bias on (WavLM), between hificar_hubert_create and hificar_hubert_finalize (HIFICAR_E_STATE
+ * afterwards).  bucket_of_distance: HOST, 2 max_distance + 1 entries, bucket_of_distance[d + max_distance] = bucket(d) in 0 .. num_buckets - 1
+ * for d in -max_distance .. max_distance; distances beyond are clamped, which is exact for the library's bucket function (its last bucket
+ * starts at max_distance).  The caller computes the map — the library takes a float32 logarithm there, and this side never evaluates one.
+ * HIFICAR_E_INVALID: num_buckets odd, under 2 or over HIFICAR_HUBERT_MAX_BUCKETS; max_distance outside 1 .. HIFICAR_HUBERT_MAX_DISTANCE; an
+ * entry out of range; a handle set to HIFICAR_PREC_BF16X3A (and hificar_hubert_set_precision(BF16X3A) after this call: the bf16 attention
+ * kernel has no bias term).  Afterwards hificar_hubert_set_weight also takes — and hificar_hubert_finalize asks for —
+ * "encoder.layers.0.attention.rel_attn_embed.weight" (num_buckets, heads) and, per layer, "encoder.layers.<l>.attention.gru_rel_pos_linear.weight"
+ * (8, 64), ".bias" (8) and "encoder.layers.<l>.attention.gru_rel_pos_const" (1, heads, 1, 1); finalize folds embedding and map into one fp32
+ * table per head, [heads][2 max_distance + 1].  hificar_hubert_workspace_bytes grows by one layer's gates, B heads Tmax floats; the debug tap
+ * "gate.<l>" (B, heads, Tmax) holds the gates layer l used.  Touches no device.  Without this call a handle computes, launches and
+ * reports exactly what it did before the call existed. */
+int hificar_hubert_set_rel_bias(hificar_hubert* h, int num_buckets, int max_distance, const int32_t* bucket_of_distance);
+
 /* Checks that every tensor arrived, folds the weight norm, re-lays the strided convs' weights as windows of two positions, packs q | k | v
  * as one GEMM, uploads.  Synchronises the device once. */
 int hificar_hubert_finalize(hificar_hubert* h);
@@ -1125,6 +1147,33 @@ int hificar_hubert_debug_sub_batch(hificar_hubert* h, int utterances);
 hificar_engine* hificar_hubert_engine(hificar_hubert* h);
 
 void hificar_hubert_destroy(hificar_hubert* h);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * A linear head on device features: y[b, :, t] = coef x[b, :, t] + intercept over (B, in, T) -> (B, out, T) — the fitted linear regression
+ * the reference's egs/ema/voc1/local/linear_inference.py applies to hidden_states[9] of wavlm_large.  The one-tap GEMM every Linear of this
+ * library is, on the conv engine, exact fp32, split-K off: every utterance is computed as if alone, bit for bit.
+ * --------------------------------------------------------------------------------------------------------------------------- */
+#define HIFICAR_LINEAR_MAX_IN 8192
+#define HIFICAR_LINEAR_MAX_OUT 1024
+
+typedef struct hificar_linear hificar_linear;
+
+/* coef: HOST (out_features, in_features) fp32, row-major (sklearn's coef_); intercept: HOST (out_features).  Packs and uploads the weights:
+ * runs on the current device and synchronises it once. */
+int hificar_linear_create(int in_features, int out_features, const float* coef, const float* intercept, hificar_linear** out);
+
+/* Bytes of device scratch hificar_linear_forward needs for B sequences of at most T frames; 0: the shape is refused. */
+size_t hificar_linear_workspace_bytes(const hificar_linear* h, int B, int T);
+
+/* x (B, in_features, T) device fp32; lengths: DEVICE int32[B] frame counts (clamped into 0 .. T) or NULL (every sequence has T);
+ * out (B, out_features, T), exactly zero from a sequence's own length on.  workspace: 256-byte aligned. */
+int hificar_linear_forward(hificar_linear* h, const float* x, const int32_t* lengths, float* out, int B, int T, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
+/* The head's engine, for hificar_profile_begin / hificar_profile_end. */
+hificar_engine* hificar_linear_engine(hificar_linear* h);
+
+void hificar_linear_destroy(hificar_linear* h);
 
 #ifdef __cplusplus
 }
