@@ -59,10 +59,7 @@ static int fail(int code, const char* fmt, ...) {
 // ------------------------------------------------------------------------------------------------
 // model description
 // ------------------------------------------------------------------------------------------------
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
+#include "hificar_host_util.h"  // HostTensor, Carver, WeightIntake, TapTable, check_workspace, launch_conv1, pack_linear
 
 struct ConvLayer {
     std::string name;     // reference module path, e.g. "blocks.3.convs1.2.1"
@@ -193,8 +190,7 @@ struct hificar_handle : hificar_engine {
     int cf = 0;       // feature channels = in_channels - ar_output*use_ar
     int cin_pad = 0;  // padded input-conv channels
     int hop = 1;
-    std::map<std::string, std::vector<int64_t>> expected;  // name -> shape
-    std::map<std::string, HostTensor> tensors;
+    WeightIntake weights;
     ConvLayer input_conv;
     std::vector<ConvLayer> ups;
     std::vector<ConvLayer> convs1;  // [stage][block][dil] flattened
@@ -236,12 +232,8 @@ struct hificar_handle : hificar_engine {
     int ar_dual_min = 17, ar_dual_max = 62;  // HIFICAR_AR_DUAL_MIN / _MAX: the batch sizes the loop splits (max 0: never)
     hipStream_t ar_side = nullptr;
     hipEvent_t ar_ev[2] = {nullptr, nullptr};
-    // debug taps (hificar_debug_tap): name -> (destination, capacity in floats); scratch for pre-activation copies
-    struct Tap {
-        float* dst;
-        size_t cap;
-    };
-    std::map<std::string, Tap> taps;
+    // debug taps (hificar_debug_tap); scratch for pre-activation copies
+    TapTable taps;
     float* tap_scratch = nullptr;
     size_t tap_scratch_elems = 0;
 };
@@ -422,7 +414,7 @@ extern "C" int hificar_create(const hificar_config* cfg, hificar_handle** out) {
     for (int i = 0; i < c.n_stages; ++i) h->hop *= c.upsample_scales[i];
 
     int rc = HIFICAR_OK;
-    auto expect = [&](const std::string& n, std::vector<int64_t> s) { h->expected[n] = s; };
+    auto expect = [&](const std::string& n, std::vector<int64_t> s) { h->weights.expected[n] = s; };
 
     ConvLayer& ic = h->input_conv;
     ic.name = "input_conv";
@@ -544,22 +536,7 @@ extern "C" void hificar_destroy(hificar_handle* h) {
 extern "C" int hificar_set_weight(hificar_handle* h, const char* name, const float* data, const int64_t* shape, int ndim) {
     if (!h || !name || !data || !shape) return fail(HIFICAR_E_INVALID, "hificar_set_weight: null argument");
     if (h->finalized) return fail(HIFICAR_E_STATE, "hificar_set_weight(%s) after hificar_finalize", name);
-    auto it = h->expected.find(name);
-    if (it == h->expected.end()) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", name);
-    std::vector<int64_t> s(shape, shape + ndim);
-    if (s != it->second) {
-        std::string want, got;
-        for (auto v : it->second) want += std::to_string(v) + ",";
-        for (auto v : s) got += std::to_string(v) + ",";
-        return fail(HIFICAR_E_INVALID, "size mismatch for %s: expected (%s) got (%s)", name, want.c_str(), got.c_str());
-    }
-    size_t n = 1;
-    for (auto v : s) n *= (size_t)v;
-    HostTensor t;
-    t.shape = s;
-    t.data.assign(data, data + n);
-    h->tensors[name] = std::move(t);
-    return HIFICAR_OK;
+    return h->weights.set(name, data, shape, ndim);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -741,10 +718,9 @@ static void engine_close(hificar_engine* h) {
 extern "C" int hificar_finalize(hificar_handle* h) {
     if (!h) return fail(HIFICAR_E_INVALID, "hificar_finalize: null handle");
     if (h->finalized) return HIFICAR_OK;
-    for (auto& kv : h->expected)
-        if (!h->tensors.count(kv.first)) return fail(HIFICAR_E_STATE, "Missing key(s) in state_dict: \"%s\"", kv.first.c_str());
+    if (const int missing = h->weights.check_complete()) return missing;
     int rc;
-    auto pack = [&](ConvLayer& L) { return pack_conv(h, L, h->tensors.at(L.name + ".weight"), L.has_bias ? &h->tensors.at(L.name + ".bias") : nullptr); };
+    auto pack = [&](ConvLayer& L) { return pack_conv(h, L, h->weights.at(L.name + ".weight"), L.has_bias ? &h->weights.at(L.name + ".bias") : nullptr); };
     if ((rc = pack(h->input_conv)) != HIFICAR_OK) return rc;
     for (auto& l : h->ups)
         if ((rc = pack(l)) != HIFICAR_OK) return rc;
@@ -756,34 +732,34 @@ extern "C" int hificar_finalize(hificar_handle* h) {
         for (ConvLayer* l : {&g.c1a, &g.c1b, &g.res, &g.c2a, &g.c2b})
             if ((rc = pack(*l)) != HIFICAR_OK) return rc;
     {   // output conv weight (1, C, K) -> [k][C]
-        const HostTensor& W = h->tensors.at("output_conv.1.weight");
+        const HostTensor& W = h->weights.at("output_conv.1.weight");
         const int C = (int)W.shape[1], K = (int)W.shape[2], Cp = round_up(C, 32);  // [k][padded channels]
         std::vector<float> w((size_t)Cp * K, 0.f);
         for (int ch = 0; ch < C; ++ch)
             for (int k = 0; k < K; ++k) w[(size_t)k * Cp + ch] = W.data[(size_t)ch * K + k];
         if ((rc = upload(h, w, &h->d_out_w)) != HIFICAR_OK) return rc;
-        h->out_bias = h->tensors.at("output_conv.1.bias").data[0];
+        h->out_bias = h->weights.data("output_conv.1.bias")[0];
     }
     if (h->cfg.use_ar) {
         for (int l = 0; l < 5; ++l) {
-            const HostTensor& W = h->tensors.at("ar_model.model." + std::to_string(2 * l) + ".weight");
+            const HostTensor& W = h->weights.at("ar_model.model." + std::to_string(2 * l) + ".weight");
             const int dout = (int)W.shape[0], din = (int)W.shape[1];
             std::vector<float> wt((size_t)din * dout);
             for (int o = 0; o < dout; ++o)
                 for (int i = 0; i < din; ++i) wt[(size_t)i * dout + o] = W.data[(size_t)o * din + i];
             if ((rc = upload(h, wt, &h->d_mlp_w[l])) != HIFICAR_OK) return rc;
-            if ((rc = upload(h, h->tensors.at("ar_model.model." + std::to_string(2 * l) + ".bias").data, &h->d_mlp_b[l])) != HIFICAR_OK) return rc;
+            if ((rc = upload(h, h->weights.data("ar_model.model." + std::to_string(2 * l) + ".bias"), &h->d_mlp_b[l])) != HIFICAR_OK) return rc;
         }
     }
     if (h->cfg.use_spk_id) {
-        if ((rc = upload(h, h->tensors.at("spk_emb_mat.weight").data, &h->d_spk_emb)) != HIFICAR_OK) return rc;
-        if ((rc = upload(h, h->tensors.at("spk_fc.weight").data, &h->d_spk_w)) != HIFICAR_OK) return rc;
-        if ((rc = upload(h, h->tensors.at("spk_fc.bias").data, &h->d_spk_b)) != HIFICAR_OK) return rc;
+        if ((rc = upload(h, h->weights.data("spk_emb_mat.weight"), &h->d_spk_emb)) != HIFICAR_OK) return rc;
+        if ((rc = upload(h, h->weights.data("spk_fc.weight"), &h->d_spk_w)) != HIFICAR_OK) return rc;
+        if ((rc = upload(h, h->weights.data("spk_fc.bias"), &h->d_spk_b)) != HIFICAR_OK) return rc;
     }
-    if (h->cfg.use_ph && (rc = upload(h, h->tensors.at("ph_emb_mat.weight").data, &h->d_ph_emb)) != HIFICAR_OK) return rc;
+    if (h->cfg.use_ph && (rc = upload(h, h->weights.data("ph_emb_mat.weight"), &h->d_ph_emb)) != HIFICAR_OK) return rc;
     if (h->cfg.use_ph_loss) {
-        if ((rc = upload(h, h->tensors.at("ph_fc.weight").data, &h->d_phfc_w)) != HIFICAR_OK) return rc;
-        if ((rc = upload(h, h->tensors.at("ph_fc.bias").data, &h->d_phfc_b)) != HIFICAR_OK) return rc;
+        if ((rc = upload(h, h->weights.data("ph_fc.weight"), &h->d_phfc_w)) != HIFICAR_OK) return rc;
+        if ((rc = upload(h, h->weights.data("ph_fc.bias"), &h->d_phfc_b)) != HIFICAR_OK) return rc;
     }
     // the engine opens here, not in hificar_create / hificar_gblock_create: a handle can be created and described without a device
     if ((rc = engine_open(h, true)) != HIFICAR_OK) return rc;
@@ -791,7 +767,7 @@ extern "C" int hificar_finalize(hificar_handle* h) {
     if (const char* e = getenv("HIFICAR_AR_DUAL_MIN")) h->ar_dual_min = atoi(e);
     if (const char* e = getenv("HIFICAR_AR_DUAL_MAX")) h->ar_dual_max = atoi(e);
     HIP_TRY(hipDeviceSynchronize());
-    h->tensors.clear();  // host copies no longer needed
+    h->weights.clear_staged();  // host copies no longer needed
     h->finalized = true;
     return HIFICAR_OK;
 }
@@ -844,22 +820,17 @@ static size_t stage_elems(const hificar_handle* h, int B, int T) {
 // One layout for both arithmetics (set_precision may switch a live handle).
 static Workspace plan_workspace(const hificar_handle* h, int B, int T, void* base) {
     Workspace w;
-    size_t off = 0;
-    auto take = [&](size_t elems) {
-        float* p = base ? reinterpret_cast<float*>(static_cast<char*>(base) + off) : nullptr;
-        off += round_up_sz(elems * sizeof(float), 1024);
-        return p;
-    };
-    w.xin = take((size_t)B * T * h->cin_pad);
-    w.h0 = take((size_t)B * T * stage_pad(h->cfg, 0));
+    Carver cv(base, 1024);
+    w.xin = cv.floats((size_t)B * T * h->cin_pad);
+    w.h0 = cv.floats((size_t)B * T * stage_pad(h->cfg, 0));
     const size_t se = stage_elems(h, B, T);
-    w.u = take(se);
+    w.u = cv.floats(se);
     const int nbw = std::max(3, h->cfg.n_blocks);  // (three sets at least: the GBlock engine and the MRF-mean ping-pong use them by index)
-    for (int j = 0; j < kMaxBlk; ++j) w.x[j] = j < nbw ? take(se) : nullptr;
-    for (int j = 0; j < kMaxBlk; ++j) w.xt[j] = j < nbw ? take(se) : nullptr;
-    w.u_s = reinterpret_cast<char*>(take(se));
-    for (int j = 0; j < kMaxBlk; ++j) w.x_s[j] = j < nbw ? reinterpret_cast<char*>(take(se)) : nullptr;
-    w.bytes = off;
+    for (int j = 0; j < kMaxBlk; ++j) w.x[j] = j < nbw ? cv.floats(se) : nullptr;
+    for (int j = 0; j < kMaxBlk; ++j) w.xt[j] = j < nbw ? cv.floats(se) : nullptr;
+    w.u_s = cv.floats<char>(se);
+    for (int j = 0; j < kMaxBlk; ++j) w.x_s[j] = j < nbw ? cv.floats<char>(se) : nullptr;
+    w.bytes = cv.bytes();
     return w;
 }
 
@@ -1624,15 +1595,7 @@ static int launch_pair(hificar_engine* h, const ConvLayer* const* l1, const Conv
 // ------------------------------------------------------------------------------------------------
 extern "C" int hificar_debug_tap(hificar_handle* h, const char* name, float* dst, size_t capacity) {
     if (!h) return fail(HIFICAR_E_INVALID, "null handle");
-    if (!name) {
-        h->taps.clear();
-        return HIFICAR_OK;
-    }
-    if (!dst) {
-        h->taps.erase(name);
-        return HIFICAR_OK;
-    }
-    h->taps[name] = {dst, capacity};
+    h->taps.set(name, dst, capacity);
     return HIFICAR_OK;
 }
 
@@ -1654,13 +1617,13 @@ extern "C" int hificar_debug_force_tile(hificar_engine* e, int mi, int wm, int w
 
 static int emit_tap(hificar_handle* h, const std::string& name, const void* src, int pitch, int c0, int C, int nseq, int rows, int split,
                     hipStream_t stream, int src_rows = 0) {
-    auto it = h->taps.find(name);
-    if (it == h->taps.end()) return HIFICAR_OK;
     const size_t need = (size_t)nseq * C * rows;
-    if (it->second.cap < need) return fail(HIFICAR_E_INVALID, "debug tap '%s' needs %zu floats, buffer has %zu", name.c_str(), need, it->second.cap);
+    float* dst;
+    const int rc = h->taps.find(name, need, &dst);
+    if (rc != HIFICAR_OK || !dst) return rc;
     TapParams tp;
     tp.src = src;
-    tp.dst = it->second.dst;
+    tp.dst = dst;
     tp.pitch = pitch;
     tp.c0 = c0;
     tp.C = C;
@@ -1674,7 +1637,7 @@ static int emit_tap(hificar_handle* h, const std::string& name, const void* src,
     return HIFICAR_OK;
 }
 
-static bool tap_wanted(const hificar_handle* h, const std::string& name) { return h->taps.count(name) != 0; }
+static bool tap_wanted(const hificar_handle* h, const std::string& name) { return h->taps.wanted(name); }
 
 // The `x0..x3, nin` prefix of the parameter blocks whose kernels average up to four fp32 streams (MrfSplitParams, PhHeadParams, OutConvParams
 // and their backward blocks)
@@ -2116,7 +2079,7 @@ static int forward_impl(hificar_handle* h, FwdCall k) {
     fs.tapping = !h->taps.empty();
     if (fs.tapping) {
         const bool f32 = h->precision == HIFICAR_PREC_F32;
-        for (auto& kv : h->taps) fs.tap_convs1 = fs.tap_convs1 || kv.first.find(".convs1.") != std::string::npos;
+        fs.tap_convs1 = h->taps.any_contains(".convs1.");
         fs.tap_se = stage_elems(h, k.B, k.T);
         // pre-activation copies that the normal path never writes: 3 stage-sized scratch buffers
         if ((rc = grow_tap_scratch(h, kMaxBlk * fs.tap_se + (size_t)k.B * k.T * stage_pad(cfg, 0))) != HIFICAR_OK) return rc;
@@ -2626,7 +2589,6 @@ extern "C" int hificar_pcm16(const float* x, int16_t* y, size_t n, void* stream)
 // What the training states of the two feature models (BiGRU, Transformer) share: the table of their device-resident parameters — every
 // float tensor of the state_dict in one master copy, the trainable ones in front, in gradient-buffer order — and its hand-over.
 // ------------------------------------------------------------------------------------------------
-using FeatureShapes = std::map<std::string, std::vector<int64_t>>;  // a handle's `expected`: state_dict name -> shape
 
 struct FeatureParamTable {
     struct Slot {

@@ -12,8 +12,7 @@ struct BigruTrain;  // training state (hificar_bigru_train.hip.inc): made by the
 struct hificar_bigru {
     hificar_bigru_config cfg;
     hificar_engine eng;
-    std::map<std::string, std::vector<int64_t>> expected;
-    std::map<std::string, HostTensor> tensors;
+    WeightIntake weights;
     ConvLayer proj[2], fc1;
     float4* d_whh[2] = {nullptr, nullptr};  // [dir][3 * H/8][2H] float4 per layer (BigruSplit)
     float* d_bhh[2] = {nullptr, nullptr};   // [dir][3H] per layer
@@ -47,16 +46,16 @@ extern "C" int hificar_bigru_create(const hificar_bigru_config* cfg, hificar_big
     for (int l = 1; l <= 2; ++l)
         for (const char* sfx : {"", "_reverse"}) {
             const std::string b = "gru" + std::to_string(l) + ".";
-            g->expected[b + "weight_ih_l0" + sfx] = {3 * H, l == 1 ? C : 2 * H};
-            g->expected[b + "weight_hh_l0" + sfx] = {3 * H, H};
-            g->expected[b + "bias_ih_l0" + sfx] = {3 * H};
-            g->expected[b + "bias_hh_l0" + sfx] = {3 * H};
+            g->weights.expected[b + "weight_ih_l0" + sfx] = {3 * H, l == 1 ? C : 2 * H};
+            g->weights.expected[b + "weight_hh_l0" + sfx] = {3 * H, H};
+            g->weights.expected[b + "bias_ih_l0" + sfx] = {3 * H};
+            g->weights.expected[b + "bias_hh_l0" + sfx] = {3 * H};
         }
-    g->expected["fc1.0.weight"] = {kBigruFc1, 2 * H};
-    g->expected["fc1.0.bias"] = {kBigruFc1};
-    for (const char* n : {"bn.weight", "bn.bias", "bn.running_mean", "bn.running_var"}) g->expected[n] = {kBigruFc1};
-    g->expected[bigru_fc2_name(g) + ".weight"] = {O, kBigruFc1};
-    g->expected[bigru_fc2_name(g) + ".bias"] = {O};
+    g->weights.expected["fc1.0.weight"] = {kBigruFc1, 2 * H};
+    g->weights.expected["fc1.0.bias"] = {kBigruFc1};
+    for (const char* n : {"bn.weight", "bn.bias", "bn.running_mean", "bn.running_var"}) g->weights.expected[n] = {kBigruFc1};
+    g->weights.expected[bigru_fc2_name(g) + ".weight"] = {O, kBigruFc1};
+    g->weights.expected[bigru_fc2_name(g) + ".bias"] = {O};
     int rc = HIFICAR_OK;
     for (int l = 0; l < 2 && rc == HIFICAR_OK; ++l) {
         ConvLayer& P = g->proj[l];
@@ -95,22 +94,7 @@ extern "C" hificar_engine* hificar_bigru_engine(hificar_bigru* g) { return g ? &
 extern "C" int hificar_bigru_set_weight(hificar_bigru* g, const char* name, const float* data, const int64_t* shape, int ndim) {
     if (!g || !name || !data || !shape) return fail(HIFICAR_E_INVALID, "hificar_bigru_set_weight: null argument");
     if (g->finalized) return fail(HIFICAR_E_STATE, "hificar_bigru_set_weight(%s) after hificar_bigru_finalize", name);
-    auto it = g->expected.find(name);
-    if (it == g->expected.end()) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", name);
-    std::vector<int64_t> s(shape, shape + ndim);
-    if (s != it->second) {
-        std::string want, got;
-        for (auto v : it->second) want += std::to_string(v) + ",";
-        for (auto v : s) got += std::to_string(v) + ",";
-        return fail(HIFICAR_E_INVALID, "size mismatch for %s: expected (%s) got (%s)", name, want.c_str(), got.c_str());
-    }
-    size_t n = 1;
-    for (auto v : s) n *= (size_t)v;
-    HostTensor t;
-    t.shape = s;
-    t.data.assign(data, data + n);
-    g->tensors[name] = std::move(t);
-    return HIFICAR_OK;
+    return g->weights.set(name, data, shape, ndim);
 }
 
 // W_hh of both directions in the recurrent kernel's order: [dir][gate * H/8 + column][thread 2 i + q] float4 = W_hh[gate H + i][q H/2 + 4 column ..]
@@ -167,8 +151,7 @@ static int bigru_tile_height(const hificar_bigru* g, int B) {
 extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_bigru_finalize: null handle");
     if (g->finalized) return HIFICAR_OK;
-    for (auto& kv : g->expected)
-        if (!g->tensors.count(kv.first)) return fail(HIFICAR_E_STATE, "Missing key(s) in state_dict: \"%s\"", kv.first.c_str());
+    if (const int missing = g->weights.check_complete()) return missing;
     hificar_engine* h = &g->eng;
     const int H = g->cfg.hidden_size, O = g->cfg.out_channels;
     int rc;
@@ -178,25 +161,25 @@ extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
         HostTensor W, Bv;  // (6H, Cin, 1): forward rows, then reverse rows
         W.shape = {6 * H, P.cin, 1};
         for (const char* sfx : {"", "_reverse"}) {
-            const HostTensor& wi = g->tensors.at(b + "weight_ih_l0" + sfx);
-            const HostTensor& bi = g->tensors.at(b + "bias_ih_l0" + sfx);
+            const HostTensor& wi = g->weights.at(b + "weight_ih_l0" + sfx);
+            const HostTensor& bi = g->weights.at(b + "bias_ih_l0" + sfx);
             W.data.insert(W.data.end(), wi.data.begin(), wi.data.end());
             Bv.data.insert(Bv.data.end(), bi.data.begin(), bi.data.end());
         }
         Bv.shape = {6 * H};
         if ((rc = pack_conv(h, P, W, &Bv)) != HIFICAR_OK) return rc;
         float* whh = nullptr;
-        if ((rc = upload(h, bigru_pack_whh(g->tensors.at(b + "weight_hh_l0"), g->tensors.at(b + "weight_hh_l0_reverse"), H), &whh)) != HIFICAR_OK) return rc;
+        if ((rc = upload(h, bigru_pack_whh(g->weights.at(b + "weight_hh_l0"), g->weights.at(b + "weight_hh_l0_reverse"), H), &whh)) != HIFICAR_OK) return rc;
         g->d_whh[l] = reinterpret_cast<float4*>(whh);
-        std::vector<float> bhh = g->tensors.at(b + "bias_hh_l0").data;
-        const std::vector<float>& br = g->tensors.at(b + "bias_hh_l0_reverse").data;
+        std::vector<float> bhh = g->weights.data(b + "bias_hh_l0");
+        const std::vector<float>& br = g->weights.data(b + "bias_hh_l0_reverse");
         bhh.insert(bhh.end(), br.begin(), br.end());
         if ((rc = upload(h, bhh, &g->d_bhh[l])) != HIFICAR_OK) return rc;
     }
     {   // fc1 with the eval-mode batch norm folded in: y = (W x + b - mean) * gamma / sqrt(var + 1e-5) + beta  (pytorch_models.py:68-70)
-        const HostTensor& W = g->tensors.at("fc1.0.weight");
-        const std::vector<float>&b1 = g->tensors.at("fc1.0.bias").data, &gm = g->tensors.at("bn.weight").data, &bt = g->tensors.at("bn.bias").data,
-                         &mu = g->tensors.at("bn.running_mean").data, &var = g->tensors.at("bn.running_var").data;
+        const HostTensor& W = g->weights.at("fc1.0.weight");
+        const std::vector<float>&b1 = g->weights.data("fc1.0.bias"), &gm = g->weights.data("bn.weight"), &bt = g->weights.data("bn.bias"),
+                         &mu = g->weights.data("bn.running_mean"), &var = g->weights.data("bn.running_var");
         HostTensor Wf, Bf;
         Wf.shape = {kBigruFc1, 2 * H, 1};
         Wf.data.resize(W.data.size());
@@ -209,8 +192,8 @@ extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
         }
         if ((rc = pack_conv(h, g->fc1, Wf, &Bf)) != HIFICAR_OK) return rc;
     }
-    if ((rc = upload(h, g->tensors.at(bigru_fc2_name(g) + ".weight").data, &g->d_w2)) != HIFICAR_OK) return rc;
-    if ((rc = upload(h, g->tensors.at(bigru_fc2_name(g) + ".bias").data, &g->d_b2)) != HIFICAR_OK) return rc;
+    if ((rc = upload(h, g->weights.data(bigru_fc2_name(g) + ".weight"), &g->d_w2)) != HIFICAR_OK) return rc;
+    if ((rc = upload(h, g->weights.data(bigru_fc2_name(g) + ".bias"), &g->d_b2)) != HIFICAR_OK) return rc;
     (void)O;
     HIP_TRY((bigru_rec_attr<64, 1>()));
     HIP_TRY((bigru_rec_attr<64, 2>()));
@@ -227,7 +210,7 @@ extern "C" int hificar_bigru_finalize(hificar_bigru* g) {
     h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's result does not depend on what it is batched with, bit
                     // for bit (the GEMMs are a few percent of a forward next to the sweeps, so the split-K form has nothing to win here)
     HIP_TRY(hipDeviceSynchronize());
-    g->tensors.clear();
+    g->weights.clear_staged();
     g->finalized = true;
     return HIFICAR_OK;
 }
@@ -240,13 +223,11 @@ struct BigruWorkspace {
 
 static BigruWorkspace bigru_plan_workspace(const hificar_bigru* g, int B, int T, void* base) {
     const size_t rows = round_up_sz((size_t)std::max(B, 0) * (size_t)std::max(T, 0), 256);  // whole tiles of slack behind the last row
-    const size_t gb = round_up_sz(rows * 6 * g->cfg.hidden_size * sizeof(float), 256);
-    const size_t rb = round_up_sz(rows * std::max(g->cin_pad, 2 * g->cfg.hidden_size) * sizeof(float), 256);
     BigruWorkspace w;
-    char* p = static_cast<char*>(base);
-    w.gates = reinterpret_cast<float*>(p);
-    w.rows = reinterpret_cast<float*>(p + gb);
-    w.bytes = gb + rb;
+    Carver cv(base, 256);
+    w.gates = cv.floats(rows * 6 * g->cfg.hidden_size);
+    w.rows = cv.floats(rows * std::max(g->cin_pad, 2 * g->cfg.hidden_size));
+    w.bytes = cv.bytes();
     return w;
 }
 
@@ -266,12 +247,11 @@ extern "C" int hificar_bigru_forward(hificar_bigru* g, const float* x, const int
         for (int b = 0; b < B; ++b)
             if (lengths_host[b] < 0 || lengths_host[b] > T)
                 return fail(HIFICAR_E_INVALID, "hificar_bigru_forward: lengths[%d]=%d outside 0 .. T=%d", b, lengths_host[b], T);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
     const BigruWorkspace ws = bigru_plan_workspace(g, B, T, workspace);
-    if (workspace_bytes < ws.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
+    int rc;
+    if ((rc = check_workspace(nullptr, workspace, workspace_bytes, ws.bytes)) != HIFICAR_OK) return rc;
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     const int H = g->cfg.hidden_size, C = g->cfg.in_channels, O = g->cfg.out_channels, M = B * T;
     const Ragged rg;
@@ -283,12 +263,10 @@ extern "C" int hificar_bigru_forward(hificar_bigru* g, const float* x, const int
     }
     const int NS = bigru_tile_height(g, B);
     for (int l = 0; l < 2; ++l) {
-        const ConvLayer* ls[1] = {&g->proj[l]};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(ws.rows);
-        io[0].y = ws.gates;
-        if ((rc = launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(ws.rows);
+        io.y = ws.gates;
+        if ((rc = launch_conv1(h, g->proj[l], 1, M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
         BigruRecParams p;
         p.g = ws.gates;
         p.w = g->d_whh[l];
@@ -302,12 +280,10 @@ extern "C" int hificar_bigru_forward(hificar_bigru* g, const float* x, const int
         if (e != hipSuccess) return fail(HIFICAR_E_HIP, "bigru_rec_kernel launch failed: %s", hipGetErrorString(e));
     }
     {
-        const ConvLayer* ls[1] = {&g->fc1};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(ws.rows);
-        io[0].y = ws.gates;
-        if ((rc = launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(ws.rows);
+        io.y = ws.gates;
+        if ((rc = launch_conv1(h, g->fc1, 1, M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
     }
     {
         BigruHeadParams p;
@@ -333,7 +309,7 @@ extern "C" int hificar_bigru_forward(hificar_bigru* g, const float* x, const int
 // the first sweep on the launches are hificar_bigru_forward's.
 struct BigruLowWorkspace {
     float* gates;   // [B T rows][6H], as BigruWorkspace
-    float* gates_l; // [B Tl rows][6H]: layer 1's pre-gates at the low rate (factor 1: none, the GEMM writes `gates`)
+    float* gates_l; // [B Tl rows][6H]: layer 1's pre-gates at the low rate (factor 1: null, the GEMM writes `gates`)
     float* rows;    // the low-rate input rows [B Tl rows][cin_pad], then the layers' hidden states [B T rows][2H]
     double* stats;  // [B][mean, 1 / std]
     int* lens;      // [B]: factor * lengths[b], what the sweeps and the head go by
@@ -344,18 +320,14 @@ static BigruLowWorkspace bigru_plan_workspace_lowrate(const hificar_bigru* g, in
     const size_t rows_l = round_up_sz((size_t)std::max(B, 0) * (size_t)std::max(Tl, 0), 256);
     const size_t rows_h = round_up_sz((size_t)std::max(B, 0) * (size_t)std::max(Tl, 0) * (size_t)std::max(factor, 1), 256);
     const size_t H = (size_t)g->cfg.hidden_size;
-    const size_t gb = round_up_sz(rows_h * 6 * H * sizeof(float), 256);
-    const size_t lb = factor > 1 ? round_up_sz(rows_l * 6 * H * sizeof(float), 256) : 0;
-    const size_t rb = round_up_sz(std::max(rows_l * (size_t)g->cin_pad, rows_h * 2 * H) * sizeof(float), 256);
-    const size_t sb = round_up_sz((size_t)std::max(B, 0) * 2 * sizeof(double), 256);
     BigruLowWorkspace w;
-    char* p = static_cast<char*>(base);
-    w.gates = reinterpret_cast<float*>(p);
-    w.gates_l = reinterpret_cast<float*>(p + gb);
-    w.rows = reinterpret_cast<float*>(p + gb + lb);
-    w.stats = reinterpret_cast<double*>(p + gb + lb + rb);
-    w.lens = reinterpret_cast<int*>(p + gb + lb + rb + sb);
-    w.bytes = gb + lb + rb + sb + round_up_sz((size_t)std::max(B, 0) * sizeof(int), 256);
+    Carver cv(base, 256);
+    w.gates = cv.floats(rows_h * 6 * H);
+    w.gates_l = factor > 1 ? cv.floats(rows_l * 6 * H) : nullptr;
+    w.rows = cv.floats(std::max(rows_l * (size_t)g->cin_pad, rows_h * 2 * H));
+    w.stats = cv.take<double>((size_t)std::max(B, 0) * 2 * sizeof(double));
+    w.lens = cv.take<int>((size_t)std::max(B, 0) * sizeof(int));
+    w.bytes = cv.bytes();
     return w;
 }
 
@@ -381,16 +353,14 @@ extern "C" int hificar_bigru_forward_lowrate(hificar_bigru* g, const float* x, c
         for (int b = 0; b < B; ++b)
             if (lengths_host[b] < 0 || lengths_host[b] > Tl)
                 return fail(HIFICAR_E_INVALID, "hificar_bigru_forward_lowrate: lengths[%d]=%d outside 0 .. Tl=%d", b, lengths_host[b], Tl);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
-    const size_t need = hificar_bigru_workspace_bytes_lowrate(g, B, Tl, factor);
-    if (workspace_bytes < need) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+    int rc;
+    if ((rc = check_workspace(nullptr, workspace, workspace_bytes, hificar_bigru_workspace_bytes_lowrate(g, B, Tl, factor))) != HIFICAR_OK) return rc;
     // (every argument above is checked without the device: a handle that was never finalized is told so last)
     if (!g->finalized) return fail(HIFICAR_E_STATE, "hificar_bigru_forward_lowrate before hificar_bigru_finalize");
     if (factor == 1 && !zscore) return hificar_bigru_forward(g, x, lengths, lengths_host, out, B, Tl, workspace, workspace_bytes, stream_);
     const BigruLowWorkspace ws = bigru_plan_workspace_lowrate(g, B, Tl, factor, workspace);
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     const int H = g->cfg.hidden_size, C = g->cfg.in_channels, O = g->cfg.out_channels, T = Tl * factor, Ml = B * Tl, M = B * T;
     const Ragged rg;
@@ -413,12 +383,10 @@ extern "C" int hificar_bigru_forward_lowrate(hificar_bigru* g, const float* x, c
     }
     const int NS = bigru_tile_height(g, B);
     for (int l = 0; l < 2; ++l) {
-        const ConvLayer* ls[1] = {&g->proj[l]};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(ws.rows);
-        io[0].y = l == 0 && factor > 1 ? ws.gates_l : ws.gates;
-        if ((rc = launch_conv(h, ls, 1, 1, l == 0 ? Ml : M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(ws.rows);
+        io.y = l == 0 && factor > 1 ? ws.gates_l : ws.gates;
+        if ((rc = launch_conv1(h, g->proj[l], 1, l == 0 ? Ml : M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
         if (l == 0 && factor > 1) {
             const int N4 = 6 * H / 4;
             ProfScope prof(h, stream, "bigru_interp_gates_kernel", 3.0 * M * 6 * H, 4.0 * M * 6 * H * 3);
@@ -439,12 +407,10 @@ extern "C" int hificar_bigru_forward_lowrate(hificar_bigru* g, const float* x, c
         if (e != hipSuccess) return fail(HIFICAR_E_HIP, "bigru_rec_kernel launch failed: %s", hipGetErrorString(e));
     }
     {
-        const ConvLayer* ls[1] = {&g->fc1};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(ws.rows);
-        io[0].y = ws.gates;
-        if ((rc = launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(ws.rows);
+        io.y = ws.gates;
+        if ((rc = launch_conv1(h, g->fc1, 1, M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
     }
     {
         BigruHeadParams p;

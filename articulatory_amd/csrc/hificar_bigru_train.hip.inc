@@ -65,7 +65,7 @@ static int bigru_train_build(hificar_bigru* g, BigruTrain* ts) {
     hificar_engine* h = &g->eng;
     const int H = g->cfg.hidden_size;
     FeatureParamTable& tab = ts->tab;
-    auto add = [&](const std::string& name, bool trainable) { tab.add(g->expected, name, trainable); };
+    auto add = [&](const std::string& name, bool trainable) { tab.add(g->weights.expected, name, trainable); };
     // a layer's forward and reverse tensors of one kind lie back to back: (6H, Cin) / (6H) / 2 x (3H, H) blocks, as the GEMMs see them
     for (int l = 1; l <= 2; ++l) {
         const std::string b = "gru" + std::to_string(l) + ".";
@@ -178,7 +178,7 @@ extern "C" int hificar_bigru_set_parameters_device(hificar_bigru* g, const char*
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
-    if ((rc = feature_upload(g->expected, ts->tab, names, data, n, "hificar_bigru_set_parameters_device", stream)) != HIFICAR_OK) return rc;
+    if ((rc = feature_upload(g->weights.expected, ts->tab, names, data, n, "hificar_bigru_set_parameters_device", stream)) != HIFICAR_OK) return rc;
     const int H = g->cfg.hidden_size, O = g->cfg.out_channels;
     float* const m = ts->tab.d_master;
     auto at = [&](const std::string& name) { return ts->tab.at(name); };
@@ -235,24 +235,19 @@ struct BigruLow {
 // Tl > 0: the input block holds the B Tl low-rate rows; everything behind it is the tape of B x T frames.
 static BigruTape bigru_plan_tape(const hificar_bigru* g, int B, int T, void* base, bool with_gates = true, int Tl = 0) {
     const size_t rows = feature_train_rows(B, T), H = (size_t)g->cfg.hidden_size;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? static_cast<char*>(base) + off : nullptr;
-        off += round_up_sz(bytes, 256);
-        return p;
-    };
+    Carver cv(base, 256);
     BigruTape t;
-    t.hdr = reinterpret_cast<BigruTapeHeader*>(take(256));
-    t.x0 = reinterpret_cast<float*>(take((Tl > 0 ? feature_train_rows(B, Tl) : rows) * g->cin_pad * 4));
-    for (int l = 0; l < 2; ++l) t.y[l] = reinterpret_cast<float*>(take(rows * 2 * H * 4));
-    for (int l = 0; l < 2; ++l) t.gates[l] = with_gates ? reinterpret_cast<float*>(take(rows * 8 * H * 4)) : nullptr;
-    t.f1 = reinterpret_cast<float*>(take(rows * kBigruFc1 * 4));
-    t.stats = reinterpret_cast<float*>(take(3 * kBigruFc1 * 4));
-    t.out = reinterpret_cast<float*>(take((size_t)B * T * g->cfg.out_channels * 4));
-    t.lens = with_gates ? reinterpret_cast<int*>(t.gates[0] + (base ? (size_t)B * T * 8 * H : 0)) : reinterpret_cast<int*>(take((size_t)B * 4));
+    t.hdr = cv.take<BigruTapeHeader>(256);
+    t.x0 = cv.floats((Tl > 0 ? feature_train_rows(B, Tl) : rows) * g->cin_pad);
+    for (int l = 0; l < 2; ++l) t.y[l] = cv.floats(rows * 2 * H);
+    for (int l = 0; l < 2; ++l) t.gates[l] = with_gates ? cv.floats(rows * 8 * H) : nullptr;
+    t.f1 = cv.floats(rows * kBigruFc1);
+    t.stats = cv.floats(3 * kBigruFc1);
+    t.out = cv.floats((size_t)B * T * g->cfg.out_channels);
+    t.lens = with_gates ? reinterpret_cast<int*>(t.gates[0] + (base ? (size_t)B * T * 8 * H : 0)) : cv.take<int>((size_t)B * 4);
     t.zstats = nullptr;
     if (Tl > 0 && with_gates) t.zstats = reinterpret_cast<double*>(t.gates[1] + (base ? (size_t)B * T * 8 * H : 0));
-    t.bytes = off;
+    t.bytes = cv.bytes();
     return t;
 }
 
@@ -276,19 +271,14 @@ struct BigruTrainWs {
 static BigruTrainWs bigru_plan_train_ws(const hificar_bigru* g, int B, int T, void* base, const BigruLow& low = BigruLow()) {
     const size_t rows = feature_train_rows(B, T), H = (size_t)g->cfg.hidden_size;
     const int M = B * T;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? static_cast<char*>(base) + off : nullptr;
-        off += round_up_sz(bytes, 256);
-        return reinterpret_cast<float*>(p);
-    };
+    Carver cv(base, 256);
     BigruTrainWs w;
-    w.gx = take(rows * 6 * H * 4);
-    w.gh = take(rows * 6 * H * 4);
-    w.a = take(rows * 2 * H * 4);
-    w.b = take(rows * 2 * H * 4);
-    w.dbn = take(rows * kBigruFc1 * 4);
-    w.dxr = take(rows * g->cin_pad * 4);
+    w.gx = cv.floats(rows * 6 * H);
+    w.gh = cv.floats(rows * 6 * H);
+    w.a = cv.floats(rows * 2 * H);
+    w.b = cv.floats(rows * 2 * H);
+    w.dbn = cv.floats(rows * kBigruFc1);
+    w.dxr = cv.floats(rows * g->cin_pad);
     w.partial_elems = w.colsum_elems = 0;
     if (g->train) {
         const hificar_engine* h = &g->eng;
@@ -301,13 +291,13 @@ static BigruTrainWs bigru_plan_train_ws(const hificar_bigru* g, int B, int T, vo
             w.colsum_elems = std::max(w.colsum_elems, wgrad_colsum_elems(h, g->proj[0], 1, B * low.Tl));
         }
     }
-    w.partial = take(w.partial_elems * 4);
-    w.colsum = take(w.colsum_elems * 4);
+    w.partial = cv.floats(w.partial_elems);
+    w.colsum = cv.floats(w.colsum_elems);
     const size_t tiles = (size_t)B * ((T + 63) / 64);
-    w.head = take(tiles * (g->cfg.out_channels * (kBigruFc1 + 1)) * 4);
-    w.light = reinterpret_cast<char*>(take(bigru_plan_tape(g, B, T, nullptr, false, low.Tl).bytes));
-    w.gxl = low.Tl > 0 && low.factor > 1 ? take(feature_train_rows(B, low.Tl) * 6 * H * 4) : nullptr;
-    w.bytes = off;
+    w.head = cv.floats(tiles * (g->cfg.out_channels * (kBigruFc1 + 1)));
+    w.light = cv.take<char>(bigru_plan_tape(g, B, T, nullptr, false, low.Tl).bytes);
+    w.gxl = low.Tl > 0 && low.factor > 1 ? cv.floats(feature_train_rows(B, low.Tl) * 6 * H) : nullptr;
+    w.bytes = cv.bytes();
     return w;
 }
 
@@ -333,18 +323,15 @@ static int bigru_train_check(hificar_bigru* g, const char* what, int B, int T, v
         return fail(HIFICAR_E_INVALID, "%s: tape and workspace must be 256-byte aligned device pointers", what);
     const size_t tb = bigru_plan_tape(g, B, T, nullptr).bytes, wb = bigru_plan_train_ws(g, B, T, nullptr).bytes;
     if (tape && tape_bytes < tb) return fail(HIFICAR_E_WORKSPACE, "%s: tape too small: %zu < %zu", what, tape_bytes, tb);
-    if (workspace_bytes < wb) return fail(HIFICAR_E_WORKSPACE, "%s: workspace too small: %zu < %zu", what, workspace_bytes, wb);
-    return HIFICAR_OK;
+    return check_workspace_size(what, workspace_bytes, wb);
 }
 
 static int bigru_gemm(hificar_engine* h, const ConvLayer& L, const float* x, float* y, int M, hipStream_t stream) {
-    const ConvLayer* ls[1] = {&L};
-    ConvIO io[1];
-    io[0] = ConvIO();
-    io[0].xs = reinterpret_cast<const char*>(x);
-    io[0].y = y;
+    ConvIO io{};
+    io.xs = reinterpret_cast<const char*>(x);
+    io.y = y;
     const Ragged rg;
-    return launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream);
+    return launch_conv1(h, L, 1, M, io, 0.f, rg, stream);
 }
 
 static int bigru_dropout(hificar_engine* h, const float* in, float* out, size_t n, const BigruTapeHeader* hdr, int site, hipStream_t stream) {
@@ -551,7 +538,7 @@ static int bigru_lowrate_check(hificar_bigru* g, const char* what, int B, int Tl
     for (int pass = 0; pass < 2; ++pass) {
         if (tape && tape_bytes < tb) return fail(HIFICAR_E_WORKSPACE, "%s: tape too small: %zu < %zu", what, tape_bytes, tb);
         const size_t wb = bigru_plan_train_ws(g, B, Tl * factor, nullptr, low).bytes;
-        if (workspace_bytes < wb) return fail(HIFICAR_E_WORKSPACE, "%s: workspace too small: %zu < %zu", what, workspace_bytes, wb);
+        if (const int small = check_workspace_size(what, workspace_bytes, wb)) return small;
         if (pass == 1) break;
         if (!g->finalized) return fail(HIFICAR_E_STATE, "%s before hificar_bigru_finalize", what);
         const int rc = bigru_train_init(g);

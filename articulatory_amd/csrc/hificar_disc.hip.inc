@@ -137,11 +137,7 @@ struct DiscPlan {
 
 static DiscPlan disc_plan(const hificar_disc* d, int B, int T) {
     DiscPlan p;
-    auto take = [](size_t& off, size_t elems) {
-        const size_t at = off;
-        off += round_up_sz(elems * sizeof(float), 1024) / sizeof(float);
-        return at;
-    };
+    Carver tape(nullptr, 1024), ws(nullptr, 1024);  // (offsets in floats into the caller's tape and backward workspace)
     int n_scales = 0;
     for (const DiscSub& s : d->subs)
         if (s.period == 0) n_scales = std::max(n_scales, s.scale + 1);
@@ -152,8 +148,8 @@ static DiscPlan disc_plan(const hificar_disc* d, int B, int T) {
         const DiscGeom g = disc_geom(d, s, B, T);
         p.geom.push_back(g);
         if (s.period == 0 && s.scale > 0) {
-            p.pooled[(size_t)s.scale] = take(p.tape_floats, (size_t)B * g.T_sub);
-            p.dpooled[(size_t)s.scale] = take(p.ws_floats, (size_t)B * g.T_sub);
+            p.pooled[(size_t)s.scale] = tape.floats_at((size_t)B * g.T_sub);
+            p.dpooled[(size_t)s.scale] = ws.floats_at((size_t)B * g.T_sub);
         }
         std::vector<DiscPlan::LayerBuf> tl, bl;
         for (size_t l = 0; l < s.layers.size(); ++l) {
@@ -169,10 +165,10 @@ static DiscPlan disc_plan(const hificar_disc* d, int B, int T) {
                 b.a_stride = t.a_stride;  // backward: dX at the same padded positions
             }
             t.y_stride = b.y_stride = round_up_sz((size_t)t.M * L.Np * sizeof(float), 1024) / sizeof(float);
-            t.A = take(p.tape_floats, t.a_stride * L.groups);
-            t.Y = take(p.tape_floats, t.y_stride * L.groups);
-            b.A = take(p.ws_floats, b.a_stride * L.groups);
-            b.Y = take(p.ws_floats, b.y_stride * L.groups);
+            t.A = tape.floats_at(t.a_stride * L.groups);
+            t.Y = tape.floats_at(t.y_stride * L.groups);
+            b.A = ws.floats_at(b.a_stride * L.groups);
+            b.Y = ws.floats_at(b.y_stride * L.groups);
             tl.push_back(t);
             bl.push_back(b);
             // (every layer its own piece of the scratch: the sub-discriminator's reductions run as one launch at the end of its pass)
@@ -181,12 +177,14 @@ static DiscPlan disc_plan(const hificar_disc* d, int B, int T) {
         }
         p.tape.push_back(tl);
         p.bwd.push_back(bl);
-        p.dsig.push_back(take(p.ws_floats, (size_t)B * g.T_sub));
+        p.dsig.push_back(ws.floats_at((size_t)B * g.T_sub));
         p.partial_elems.push_back(pe);
-        p.partial.push_back(take(p.ws_floats, pe));
+        p.partial.push_back(ws.floats_at(pe));
         p.colsum_elems.push_back(ce);
-        p.colsum.push_back(take(p.ws_floats, ce));
+        p.colsum.push_back(ws.floats_at(ce));
     }
+    p.tape_floats = tape.bytes() / sizeof(float);
+    p.ws_floats = ws.bytes() / sizeof(float);
     return p;
 }
 
@@ -679,16 +677,14 @@ extern "C" int hificar_disc_forward(hificar_disc* d, const float* x, int B, int 
             }
             {
                 const ConvLayer& FL = tb.Lp ? L.g[0].P : L.g[0].F;
-                const ConvLayer* ls[1] = {&FL};
-                ConvIO io[1];
-                io[0] = ConvIO();
+                ConvIO io{};
                 float* y = tape + tb.Y;
-                io[0].xs = reinterpret_cast<const char*>(tape + tb.A);
-                io[0].y = L.act ? nullptr : y;
-                io[0].ys = L.act ? reinterpret_cast<char*>(y) : nullptr;
+                io.xs = reinterpret_cast<const char*>(tape + tb.A);
+                io.y = L.act ? nullptr : y;
+                io.ys = L.act ? reinterpret_cast<char*>(y) : nullptr;
                 if (tb.Lp) {  // rows of `stride` padded positions; every row of X exists (the gather zero-filled the padding)
-                    io[0].x_seq_bytes = (long long)tb.Lp * L.cin_g * 4;
-                    io[0].x_rows = tb.Lp / L.stride;
+                    io.x_seq_bytes = (long long)tb.Lp * L.cin_g * 4;
+                    io.x_rows = tb.Lp / L.stride;
                 }
                 ConvRep zr;
                 zr.n = L.groups;
@@ -696,8 +692,8 @@ extern "C" int hificar_disc_forward(hificar_disc* d, const float* x, int B, int 
                 zr.zs_y = (long long)tb.y_stride;
                 zr.zs_w = (long long)pack_w32_elems(FL, FL.chunk16) * 4;
                 zr.zs_b = FL.cout_total;
-                if ((rc = tb.Lp ? launch_conv(h, ls, 1, g.nseq, g.L[l + 1], io, s.slope, rg, stream, zr)
-                                : launch_conv(h, ls, 1, 1, (int)tb.M, io, s.slope, rg, stream, zr)) != HIFICAR_OK)
+                if ((rc = tb.Lp ? launch_conv1(h, FL, g.nseq, g.L[l + 1], io, s.slope, rg, stream, zr)
+                                : launch_conv1(h, FL, 1, (int)tb.M, io, s.slope, rg, stream, zr)) != HIFICAR_OK)
                     return rc;
             }
         }
@@ -848,33 +844,29 @@ extern "C" int hificar_disc_backward(hificar_disc* d, const float* const* douts,
             }
             // ---- data gradient with respect to the im2col matrix (needed below layer 0 only when dx is wanted)
             if (bb.Lp) {  // dX4 rows = L_out + ntaps - 1 (more than the dZ rows they are computed from: x_rows)
-                const ConvLayer* ls[1] = {&L.g[0].Q};
-                ConvIO io[1];
-                io[0] = ConvIO();
-                io[0].xs = reinterpret_cast<const char*>(ws + bb.Y);
-                io[0].y = ws + bb.A;
-                io[0].x_rows = g.L[(size_t)l + 1];
-                io[0].x_seq_bytes = (long long)g.L[(size_t)l + 1] * L.Np * 4;
+                ConvIO io{};
+                io.xs = reinterpret_cast<const char*>(ws + bb.Y);
+                io.y = ws + bb.A;
+                io.x_rows = g.L[(size_t)l + 1];
+                io.x_seq_bytes = (long long)g.L[(size_t)l + 1] * L.Np * 4;
                 ConvRep zr;
                 zr.n = L.groups;
                 zr.zs_x = (long long)bb.y_stride * 4;
                 zr.zs_y = (long long)bb.a_stride;
                 zr.zs_w = (long long)pack_w32_elems(L.g[0].Q, L.g[0].Q.chunk16) * 4;
                 zr.zs_b = L.g[0].Q.cout_total;
-                if ((rc = launch_conv(h, ls, 1, g.nseq, bb.Lp / L.stride, io, 0.f, rg, stream, zr)) != HIFICAR_OK) return rc;
+                if ((rc = launch_conv1(h, L.g[0].Q, g.nseq, bb.Lp / L.stride, io, 0.f, rg, stream, zr)) != HIFICAR_OK) return rc;
             } else if (l > 0 || dx) {
-                const ConvLayer* ls[1] = {&L.g[0].D};
-                ConvIO io[1];
-                io[0] = ConvIO();
-                io[0].xs = reinterpret_cast<const char*>(ws + bb.Y);
-                io[0].y = ws + bb.A;
+                ConvIO io{};
+                io.xs = reinterpret_cast<const char*>(ws + bb.Y);
+                io.y = ws + bb.A;
                 ConvRep zr;
                 zr.n = L.groups;
                 zr.zs_x = (long long)bb.y_stride * 4;
                 zr.zs_y = (long long)bb.a_stride;
                 zr.zs_w = (long long)pack_w32_elems(L.g[0].D, L.g[0].D.chunk16) * 4;
                 zr.zs_b = L.g[0].D.cout_total;
-                if ((rc = launch_conv(h, ls, 1, 1, (int)tb.M, io, 0.f, rg, stream, zr)) != HIFICAR_OK) return rc;
+                if ((rc = launch_conv1(h, L.g[0].D, 1, (int)tb.M, io, 0.f, rg, stream, zr)) != HIFICAR_OK) return rc;
             }
         }
         if ((rc = flush_reduce(h, pending, stream)) != HIFICAR_OK) return rc;  // every weight / bias gradient reduction of this sub-discriminator

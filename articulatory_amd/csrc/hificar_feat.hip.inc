@@ -96,16 +96,13 @@ static FeatPlan feat_plan(const hificar_feat* g, int B, int Lmax) {
     FeatPlan p;
     p.Tmax = 1 + Lmax / g->cfg.hop_size;
     p.M = (long long)B * p.Tmax;
-    auto take = [&](size_t elems) {
-        const size_t at = p.floats;
-        p.floats += round_up_sz(elems * sizeof(float), 1024) / sizeof(float);
-        return at;
-    };
+    Carver cv(nullptr, 1024);  // (offsets in floats into the caller's workspace)
     const size_t rows = round_up_sz((size_t)p.M, 256);  // whole GEMM tiles of slack behind the last row
-    p.A = take(rows * g->cfg.fft_size);
-    p.S = take(rows * 2 * g->nfp);
-    p.V = take((size_t)p.M * g->cfg.num_mels);
-    p.maxv = take((size_t)B);
+    p.A = cv.floats_at(rows * g->cfg.fft_size);
+    p.S = cv.floats_at(rows * 2 * g->nfp);
+    p.V = cv.floats_at((size_t)p.M * g->cfg.num_mels);
+    p.maxv = cv.floats_at((size_t)B);
+    p.floats = cv.bytes() / sizeof(float);
     return p;
 }
 
@@ -156,12 +153,10 @@ extern "C" int hificar_feat_forward(hificar_feat* g, const float* wav, const int
             if (lengths_host[b] <= c.fft_size / 2 || lengths_host[b] > Lmax)
                 return fail(HIFICAR_E_INVALID, "hificar_feat_forward: lengths[%d]=%d outside fft_size / 2 + 1 = %d .. Lmax=%d", b, lengths_host[b],
                             c.fft_size / 2 + 1, Lmax);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
     const FeatPlan p = feat_plan(g, B, Lmax);
-    if (workspace_bytes < p.floats * sizeof(float))
-        return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.floats * sizeof(float));
-    // (every argument above is checked without the device)
     int rc;
+    if ((rc = check_workspace(nullptr, workspace, workspace_bytes, p.floats * sizeof(float))) != HIFICAR_OK) return rc;
+    // (every argument above is checked without the device)
     if (!g->ready && (rc = feat_device_init(g)) != HIFICAR_OK) return rc;
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -185,12 +180,10 @@ extern "C" int hificar_feat_forward(hificar_feat* g, const float* wav, const int
     }
     {
         const Ragged rg;
-        const ConvLayer* ls[1] = {&g->Fdft};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(ws + p.A);
-        io[0].y = ws + p.S;
-        if ((rc = launch_conv(h, ls, 1, 1, (int)p.M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(ws + p.A);
+        io.y = ws + p.S;
+        if ((rc = launch_conv1(h, g->Fdft, 1, (int)p.M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
     }
     {
         FeatMelParams mp;

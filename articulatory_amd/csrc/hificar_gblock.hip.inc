@@ -80,7 +80,7 @@ extern "C" int hificar_gblock_create(const hificar_gblock_config* gc, hificar_ha
     h->c_last = c.channels / 8;
 
     int rc = HIFICAR_OK;
-    auto expect = [&](const std::string& n, std::vector<int64_t> s) { h->expected[n] = s; };
+    auto expect = [&](const std::string& n, std::vector<int64_t> s) { h->weights.expected[n] = s; };
     ConvLayer& ic = h->input_conv;
     ic.name = "input_conv";
     ic.cin = c.in_channels;

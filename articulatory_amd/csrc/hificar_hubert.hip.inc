@@ -50,8 +50,7 @@ struct HubertEncLayer {
 struct hificar_hubert {
     hificar_hubert_config cfg;
     hificar_engine eng;
-    std::map<std::string, std::vector<int64_t>> expected;
-    std::map<std::string, HostTensor> tensors;
+    WeightIntake weights;
     ConvLayer ext[kHubExtLayers];  // [1 .. 6]: the strided convs in window form ([0] unused: layer 0 has its own kernel)
     ConvLayer proj;
     std::vector<HubertEncLayer> enc;  // sized once, in hificar_hubert_create (launch plans are keyed by the layers' addresses)
@@ -70,11 +69,7 @@ struct hificar_hubert {
     int precision = HIFICAR_PREC_F32;  // hificar_hubert_set_precision: which fragments finalize packs and which kernels the forward launches
     bool finalized = false;
     int sub_batch = 0;  // hificar_hubert_debug_sub_batch: utterances per extractor sub-batch (0: by kHubExtBudget)
-    struct Tap {
-        float* dst;
-        size_t cap;
-    };
-    std::map<std::string, Tap> taps;
+    TapTable taps;
 };
 
 // positions per sequence behind every extractor layer for L samples (T), and the rows its buffer holds (P: T rounded up to whole windows of two)
@@ -139,32 +134,32 @@ extern "C" int hificar_hubert_create(const hificar_hubert_config* cfg, hificar_h
     const int64_t C = c.conv_dim, H = c.hidden_size, I = c.intermediate_size;
     for (int i = 0; i < kHubExtLayers; ++i) {
         const std::string b = "feature_extractor.conv_layers." + std::to_string(i) + ".";
-        g->expected[b + "conv.weight"] = {C, i == 0 ? 1 : C, kHubExtK[i]};
-        if (c.conv_bias) g->expected[b + "conv.bias"] = {C};
-        g->expected[b + "layer_norm.weight"] = {C};
-        g->expected[b + "layer_norm.bias"] = {C};
+        g->weights.expected[b + "conv.weight"] = {C, i == 0 ? 1 : C, kHubExtK[i]};
+        if (c.conv_bias) g->weights.expected[b + "conv.bias"] = {C};
+        g->weights.expected[b + "layer_norm.weight"] = {C};
+        g->weights.expected[b + "layer_norm.bias"] = {C};
     }
-    g->expected["feature_projection.layer_norm.weight"] = {C};
-    g->expected["feature_projection.layer_norm.bias"] = {C};
-    g->expected["feature_projection.projection.weight"] = {H, C};
-    g->expected["feature_projection.projection.bias"] = {H};
-    g->expected["encoder.pos_conv_embed.conv.weight_g"] = {1, 1, kHubPosTaps};
-    g->expected["encoder.pos_conv_embed.conv.weight_v"] = {H, H / kHubPosGroups, kHubPosTaps};
-    g->expected["encoder.pos_conv_embed.conv.bias"] = {H};
-    g->expected["encoder.layer_norm.weight"] = {H};
-    g->expected["encoder.layer_norm.bias"] = {H};
+    g->weights.expected["feature_projection.layer_norm.weight"] = {C};
+    g->weights.expected["feature_projection.layer_norm.bias"] = {C};
+    g->weights.expected["feature_projection.projection.weight"] = {H, C};
+    g->weights.expected["feature_projection.projection.bias"] = {H};
+    g->weights.expected["encoder.pos_conv_embed.conv.weight_g"] = {1, 1, kHubPosTaps};
+    g->weights.expected["encoder.pos_conv_embed.conv.weight_v"] = {H, H / kHubPosGroups, kHubPosTaps};
+    g->weights.expected["encoder.pos_conv_embed.conv.bias"] = {H};
+    g->weights.expected["encoder.layer_norm.weight"] = {H};
+    g->weights.expected["encoder.layer_norm.bias"] = {H};
     for (int l = 0; l < c.num_hidden_layers; ++l) {
         const std::string b = "encoder.layers." + std::to_string(l) + ".";
         for (const char* w : {"q_proj", "k_proj", "v_proj", "out_proj"}) {
-            g->expected[b + "attention." + w + ".weight"] = {H, H};
-            g->expected[b + "attention." + w + ".bias"] = {H};
+            g->weights.expected[b + "attention." + w + ".weight"] = {H, H};
+            g->weights.expected[b + "attention." + w + ".bias"] = {H};
         }
         for (const char* n : {"layer_norm", "final_layer_norm"})
-            for (const char* t : {".weight", ".bias"}) g->expected[b + n + t] = {H};
-        g->expected[b + "feed_forward.intermediate_dense.weight"] = {I, H};
-        g->expected[b + "feed_forward.intermediate_dense.bias"] = {I};
-        g->expected[b + "feed_forward.output_dense.weight"] = {H, I};
-        g->expected[b + "feed_forward.output_dense.bias"] = {H};
+            for (const char* t : {".weight", ".bias"}) g->weights.expected[b + n + t] = {H};
+        g->weights.expected[b + "feed_forward.intermediate_dense.weight"] = {I, H};
+        g->weights.expected[b + "feed_forward.intermediate_dense.bias"] = {I};
+        g->weights.expected[b + "feed_forward.output_dense.weight"] = {H, I};
+        g->weights.expected[b + "feed_forward.output_dense.bias"] = {H};
     }
     g->enc.resize((size_t)c.num_hidden_layers);
     int rc = HIFICAR_OK;
@@ -203,22 +198,7 @@ extern "C" int hificar_hubert_frames(const hificar_hubert* g, int L) {
 extern "C" int hificar_hubert_set_weight(hificar_hubert* g, const char* name, const float* data, const int64_t* shape, int ndim) {
     if (!g || !name || !data || !shape) return fail(HIFICAR_E_INVALID, "hificar_hubert_set_weight: null argument");
     if (g->finalized) return fail(HIFICAR_E_STATE, "hificar_hubert_set_weight(%s) after hificar_hubert_finalize", name);
-    auto it = g->expected.find(name);
-    if (it == g->expected.end()) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", name);
-    std::vector<int64_t> s(shape, shape + ndim);
-    if (s != it->second) {
-        std::string want, got;
-        for (auto v : it->second) want += std::to_string(v) + ",";
-        for (auto v : s) got += std::to_string(v) + ",";
-        return fail(HIFICAR_E_INVALID, "size mismatch for %s: expected (%s) got (%s)", name, want.c_str(), got.c_str());
-    }
-    size_t n = 1;
-    for (auto v : s) n *= (size_t)v;
-    HostTensor t;
-    t.shape = s;
-    t.data.assign(data, data + n);
-    g->tensors[name] = std::move(t);
-    return HIFICAR_OK;
+    return g->weights.set(name, data, shape, ndim);
 }
 
 extern "C" int hificar_hubert_set_precision(hificar_hubert* g, int precision) {
@@ -244,19 +224,19 @@ extern "C" int hificar_hubert_set_rel_bias(hificar_hubert* g, int num_buckets, i
     for (int i = 0; i < 2 * max_distance + 1; ++i)
         if (bucket_of_distance[i] < 0 || bucket_of_distance[i] >= num_buckets)
             return fail(HIFICAR_E_INVALID, "hificar_hubert_set_rel_bias: bucket_of_distance[%d]=%d outside 0 .. %d", i, (int)bucket_of_distance[i], num_buckets - 1);
-    if (g->rel_bias) g->expected.erase("encoder.layers.0.attention.rel_attn_embed.weight");  // (a second call: the table's shape may differ)
-    g->tensors.erase("encoder.layers.0.attention.rel_attn_embed.weight");
+    if (g->rel_bias) g->weights.expected.erase("encoder.layers.0.attention.rel_attn_embed.weight");  // (a second call: the table's shape may differ)
+    g->weights.tensors.erase("encoder.layers.0.attention.rel_attn_embed.weight");
     g->rel_bias = true;
     g->num_buckets = num_buckets;
     g->max_distance = max_distance;
     g->bucket_of.assign(bucket_of_distance, bucket_of_distance + 2 * max_distance + 1);
     const int64_t heads = g->cfg.num_attention_heads;
-    g->expected["encoder.layers.0.attention.rel_attn_embed.weight"] = {num_buckets, heads};
+    g->weights.expected["encoder.layers.0.attention.rel_attn_embed.weight"] = {num_buckets, heads};
     for (int l = 0; l < g->cfg.num_hidden_layers; ++l) {
         const std::string b = "encoder.layers." + std::to_string(l) + ".attention.";
-        g->expected[b + "gru_rel_pos_linear.weight"] = {8, kHubHeadDim};
-        g->expected[b + "gru_rel_pos_linear.bias"] = {8};
-        g->expected[b + "gru_rel_pos_const"] = {1, heads, 1, 1};
+        g->weights.expected[b + "gru_rel_pos_linear.weight"] = {8, kHubHeadDim};
+        g->weights.expected[b + "gru_rel_pos_linear.bias"] = {8};
+        g->weights.expected[b + "gru_rel_pos_const"] = {1, heads, 1, 1};
     }
     return HIFICAR_OK;
 }
@@ -264,14 +244,13 @@ extern "C" int hificar_hubert_set_rel_bias(hificar_hubert* g, int num_buckets, i
 extern "C" int hificar_hubert_finalize(hificar_hubert* g) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_hubert_finalize: null handle");
     if (g->finalized) return HIFICAR_OK;
-    for (auto& kv : g->expected)
-        if (!g->tensors.count(kv.first)) return fail(HIFICAR_E_STATE, "Missing key(s) in state_dict: \"%s\"", kv.first.c_str());
+    if (const int missing = g->weights.check_complete()) return missing;
     hificar_engine* h = &g->eng;
     const int C = g->cfg.conv_dim, H = g->cfg.hidden_size, G = H / kHubPosGroups;
     int rc;
     const bool x3 = hubert_x3(g);
     h->precision = x3 ? HIFICAR_PREC_BF16X3 : HIFICAR_PREC_F32;  // (xfmr_pack goes by it)
-    auto vec = [&](const std::string& name) -> const std::vector<float>& { return g->tensors.at(name).data; };
+    auto vec = [&](const std::string& name) -> const std::vector<float>& { return g->weights.data(name); };
     const std::vector<float> zeros_c((size_t)C, 0.f);
     for (int i = 0; i < kHubExtLayers; ++i) {
         const std::string b = "feature_extractor.conv_layers." + std::to_string(i) + ".";
@@ -297,14 +276,9 @@ extern "C" int hificar_hubert_finalize(hificar_hubert* g) {
                 for (int j = 0; j < k; ++j) Ww.data[((size_t)o * 2 * C + (size_t)(j & 1) * C + c) * nt + (j >> 1)] = W[((size_t)o * C + c) * k + j];
         if ((rc = xfmr_pack(h, g->ext[i], Ww, bias)) != HIFICAR_OK) return rc;
     }
-    auto linear = [&](ConvLayer& L, const std::string& name) {
-        HostTensor W = g->tensors.at(name + ".weight");
-        W.shape.push_back(1);
-        return xfmr_pack(h, L, W, &vec(name + ".bias"));
-    };
     if ((rc = upload(h, vec("feature_projection.layer_norm.weight"), &g->d_fp_ln[0])) != HIFICAR_OK) return rc;
     if ((rc = upload(h, vec("feature_projection.layer_norm.bias"), &g->d_fp_ln[1])) != HIFICAR_OK) return rc;
-    if ((rc = linear(g->proj, "feature_projection.projection")) != HIFICAR_OK) return rc;
+    if ((rc = pack_linear(h, g->proj, g->weights, "feature_projection.projection")) != HIFICAR_OK) return rc;
     if ((rc = upload(h, vec("encoder.layer_norm.weight"), &g->d_enc_ln[0])) != HIFICAR_OK) return rc;
     if ((rc = upload(h, vec("encoder.layer_norm.bias"), &g->d_enc_ln[1])) != HIFICAR_OK) return rc;
     {   // weight norm over dim 2 (w[:, :, k] = g[k] v[:, :, k] / ||v[:, :, k]||), folded in double, in the kernel's lane order:
@@ -342,9 +316,9 @@ extern "C" int hificar_hubert_finalize(hificar_hubert* g) {
             }
             if ((rc = xfmr_pack(h, E.qkv, W, &bias)) != HIFICAR_OK) return rc;
         }
-        if ((rc = linear(E.wo, b + "attention.out_proj")) != HIFICAR_OK) return rc;
-        if ((rc = linear(E.l1, b + "feed_forward.intermediate_dense")) != HIFICAR_OK) return rc;
-        if ((rc = linear(E.l2, b + "feed_forward.output_dense")) != HIFICAR_OK) return rc;
+        if ((rc = pack_linear(h, E.wo, g->weights, b + "attention.out_proj")) != HIFICAR_OK) return rc;
+        if ((rc = pack_linear(h, E.l1, g->weights, b + "feed_forward.intermediate_dense")) != HIFICAR_OK) return rc;
+        if ((rc = pack_linear(h, E.l2, g->weights, b + "feed_forward.output_dense")) != HIFICAR_OK) return rc;
         int i = 0;
         for (const char* n : {"layer_norm.weight", "layer_norm.bias", "final_layer_norm.weight", "final_layer_norm.bias"})
             if ((rc = upload(h, vec(b + n), &E.d_ln[i++])) != HIFICAR_OK) return rc;
@@ -379,7 +353,7 @@ extern "C" int hificar_hubert_finalize(hificar_hubert* g) {
     h->use_pair = false;
     h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's states do not depend on what it is batched with
     HIP_TRY(hipDeviceSynchronize());
-    g->tensors.clear();
+    g->weights.clear_staged();
     g->finalized = true;
     return HIFICAR_OK;
 }
@@ -412,21 +386,17 @@ static HubertWorkspace hubert_plan_workspace(const hificar_hubert* g, int B, con
     const size_t per = (size_t)d.P[0] * C * sizeof(float);
     w.Bs = (int)std::min<size_t>((size_t)B, g->sub_batch > 0 ? (size_t)g->sub_batch : std::max<size_t>(1, kHubExtBudget / per));
     const size_t M = round_up_sz((size_t)B * (size_t)d.T[6] + 64, 256);  // whole tiles of slack behind the last row
-    const size_t sb = round_up_sz((size_t)B * 2 * sizeof(double), 256), fb = round_up_sz((size_t)B * sizeof(int), 256);
-    const size_t ab = round_up_sz(((size_t)w.Bs * d.P[0] + 256) * C * sizeof(float), 256), bb = round_up_sz(((size_t)w.Bs * d.P[1] + 256) * C * sizeof(float), 256);
-    const size_t cb = M * C * sizeof(float), rb = M * H * sizeof(float), wb = M * W * sizeof(float);
-    char* p = static_cast<char*>(base);
-    w.stats = reinterpret_cast<double*>(p);
-    w.frames = reinterpret_cast<int*>(p + sb);
-    w.ea = reinterpret_cast<float*>(p + sb + fb);
-    w.eb = reinterpret_cast<float*>(p + sb + fb + ab);
-    w.feat = reinterpret_cast<float*>(p + sb + fb + ab + bb);
-    for (int i = 0; i < 4; ++i) w.r[i] = reinterpret_cast<float*>(p + sb + fb + ab + bb + cb + i * rb);
-    w.wide = reinterpret_cast<float*>(p + sb + fb + ab + bb + cb + 4 * rb);
+    Carver cv(base, 256);
+    w.stats = cv.take<double>((size_t)B * 2 * sizeof(double));
+    w.frames = cv.take<int>((size_t)B * sizeof(int));
+    w.ea = cv.floats(((size_t)w.Bs * d.P[0] + 256) * C);
+    w.eb = cv.floats(((size_t)w.Bs * d.P[1] + 256) * C);
+    w.feat = cv.floats(M * C);
+    for (int i = 0; i < 4; ++i) w.r[i] = cv.floats(M * H);
+    w.wide = cv.floats(M * W);
     // (the gates only: the (heads, T, T) bias never exists)
-    const size_t gb = g->rel_bias ? round_up_sz((size_t)B * (size_t)g->cfg.num_attention_heads * (size_t)d.T[6] * sizeof(float), 256) : 0;
-    w.gates = g->rel_bias ? reinterpret_cast<float*>(p + sb + fb + ab + bb + cb + 4 * rb + wb) : nullptr;
-    w.bytes = sb + fb + ab + bb + cb + 4 * rb + wb + gb;
+    w.gates = g->rel_bias ? cv.floats((size_t)B * (size_t)g->cfg.num_attention_heads * (size_t)d.T[6]) : nullptr;
+    w.bytes = cv.bytes();
     return w;
 }
 
@@ -444,29 +414,20 @@ extern "C" int hificar_hubert_debug_sub_batch(hificar_hubert* g, int utterances)
 
 extern "C" int hificar_hubert_debug_tap(hificar_hubert* g, const char* name, float* dst, size_t capacity) {
     if (!g) return fail(HIFICAR_E_INVALID, "null handle");
-    if (!name) {
-        g->taps.clear();
-        return HIFICAR_OK;
-    }
-    if (!dst) {
-        g->taps.erase(name);
-        return HIFICAR_OK;
-    }
-    if (hubert_x3(g) && std::string(name) == "extractor.0")
+    if (name && dst && hubert_x3(g) && std::string(name) == "extractor.0")
         return fail(HIFICAR_E_STATE, "debug tap 'extractor.0': a %s handle holds layer 0's rows as split bf16 window rows only, not as fp32 rows",
                     xfmr_precision_name(g->precision));
-    g->taps[name] = {dst, capacity};
+    g->taps.set(name, dst, capacity);
     return HIFICAR_OK;
 }
 
 // rows [nseq][rows][width] of a buffer with `pitch` rows per sequence -> the tap's dense (.., rows, width) at sequence `seq0`
 static int hubert_emit_tap(hificar_hubert* g, const std::string& name, const float* src, int seq0, int nseq, int total_seq, size_t rows, size_t pitch,
                            size_t width, hipStream_t stream) {
-    auto it = g->taps.find(name);
-    if (it == g->taps.end()) return HIFICAR_OK;
-    const size_t need = (size_t)total_seq * rows * width;
-    if (it->second.cap < need) return fail(HIFICAR_E_INVALID, "debug tap '%s' needs %zu floats, buffer has %zu", name.c_str(), need, it->second.cap);
-    HIP_TRY(hipMemcpy2DAsync(it->second.dst + (size_t)seq0 * rows * width, rows * width * sizeof(float), src, pitch * width * sizeof(float),
+    float* dst;
+    const int rc = g->taps.find(name, (size_t)total_seq * rows * width, &dst);
+    if (rc != HIFICAR_OK || !dst) return rc;
+    HIP_TRY(hipMemcpy2DAsync(dst + (size_t)seq0 * rows * width, rows * width * sizeof(float), src, pitch * width * sizeof(float),
                              rows * width * sizeof(float), (size_t)nseq, hipMemcpyDeviceToDevice, stream));
     return HIFICAR_OK;
 }
@@ -486,20 +447,19 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
         for (int b = 0; b < B; ++b)
             if (lengths_host[b] < HIFICAR_HUBERT_MIN_SAMPLES || lengths_host[b] > L)
                 return fail(HIFICAR_E_INVALID, "hificar_hubert_forward: lengths[%d]=%d outside %d .. L=%d", b, lengths_host[b], HIFICAR_HUBERT_MIN_SAMPLES, L);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
     const HubertWorkspace ws = hubert_plan_workspace(g, B, d, workspace);
-    if (workspace_bytes < ws.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
+    int rc;
+    if ((rc = check_workspace(nullptr, workspace, workspace_bytes, ws.bytes)) != HIFICAR_OK) return rc;
     if (!g->finalized) return fail(HIFICAR_E_STATE, "hificar_hubert_forward before hificar_hubert_finalize");
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     const hificar_hubert_config& c = g->cfg;
     const int C = c.conv_dim, H = c.hidden_size, I = c.intermediate_size, T = d.T[6];
     const double M = (double)B * T;
     const bool x3 = hubert_x3(g), a16 = g->precision == HIFICAR_PREC_BF16X3A;
     // (a tap set before hificar_hubert_set_precision)
-    if (x3 && g->taps.count("extractor.0"))
+    if (x3 && g->taps.wanted("extractor.0"))
         return fail(HIFICAR_E_STATE, "debug tap 'extractor.0': a %s handle holds layer 0's rows as split bf16 window rows only", xfmr_precision_name(g->precision));
 
     if (c.normalize) {
@@ -578,18 +538,16 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
             // (bf16x3: ws.ea holds every layer's split window rows, ws.eb every conv's fp32 rows)
             const float* const in = x3 || (i & 1) ? ws.ea : ws.eb;
             float* const y = x3 || (i & 1) ? ws.eb : ws.ea;
-            const ConvLayer* ls[1] = {&g->ext[i]};
-            ConvIO io[1];
-            io[0] = ConvIO();
-            io[0].xs = reinterpret_cast<const char*>(in);
-            io[0].y = y;
-            io[0].res = nullptr;
-            io[0].ys = nullptr;
-            io[0].x_seq_bytes = (long long)d.P[i - 1] * C * 4;  // rows of two positions: P / 2 windows of 2 C floats per sequence
-            io[0].x_rows = d.P[i - 1] / 2;
+            ConvIO io{};
+            io.xs = reinterpret_cast<const char*>(in);
+            io.y = y;
+            io.res = nullptr;
+            io.ys = nullptr;
+            io.x_seq_bytes = (long long)d.P[i - 1] * C * 4;  // rows of two positions: P / 2 windows of 2 C floats per sequence
+            io.x_rows = d.P[i - 1] / 2;
             Ragged full;
             full.frames = d.P[i];
-            if ((rc = launch_conv(h, ls, 1, nseq, d.P[i], io, 0.f, full, stream)) != HIFICAR_OK) return rc;
+            if ((rc = launch_conv1(h, g->ext[i], nseq, d.P[i], io, 0.f, full, stream)) != HIFICAR_OK) return rc;
             const bool last = i + 1 == kHubExtLayers;
             HIP_TRY(layer_norm(y, g->d_ext_ln[i][0], g->d_ext_ln[i][1], last ? ws.feat + (size_t)b0 * T * C : x3 ? ws.ea : y, nseq, last ? T : d.P[i], d.P[i],
                                last ? T : d.P[i], C, 1e-5f, nullptr, true, x3 && !last ? 2 : 0));
@@ -604,14 +562,12 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
     // xs: fp32 rows in exact fp32, split rows in bf16x3.  ys (bf16x3a's q | k | v): the output as split rows only — slope 1 makes the engine's
     // activated copy the identity
     auto conv = [&](const ConvLayer& Lr, const float* xs, const float* res, float* y, float* ys = nullptr) {
-        const ConvLayer* ls[1] = {&Lr};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(xs);
-        io[0].res = res;
-        io[0].y = y;
-        io[0].ys = reinterpret_cast<char*>(ys);
-        return launch_conv(h, ls, 1, B, T, io, ys ? 1.f : 0.f, rg, stream);
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(xs);
+        io.res = res;
+        io.y = y;
+        io.ys = reinterpret_cast<char*>(ys);
+        return launch_conv1(h, Lr, B, T, io, ys ? 1.f : 0.f, rg, stream);
     };
     const int sp = x3 ? 1 : 0;  // a LayerNorm in front of a GEMM writes that GEMM's operand
     auto tap = [&](const std::string& name, const float* rows) { return hubert_emit_tap(g, name, rows, 0, B, B, (size_t)T, (size_t)T, (size_t)H, stream); };
@@ -629,7 +585,7 @@ extern "C" int hificar_hubert_forward(hificar_hubert* g, const float* wav, const
         p.bias = g->d_pos_b;
         p.lengths = ws.frames;
         p.y = cur;
-        p.pos_out = g->taps.count("pos_conv") ? N : nullptr;
+        p.pos_out = g->taps.wanted("pos_conv") ? N : nullptr;
         p.T = T;
         p.H = H;
         const int G = H / kHubPosGroups;

@@ -61,26 +61,39 @@ static bool linear_shape_ok(const hificar_linear* g, int B, int T) {
     return g && B >= 1 && B <= 65535 && T >= 1 && (long long)B * T * std::max(g->in_pad, g->w.cout_pad) < (1LL << 31);
 }
 
+struct LinearWorkspace {
+    float* xin;  // [rows][in_pad]
+    float* y;    // [rows][cout_pad]
+    size_t bytes;
+};
+
+static LinearWorkspace linear_plan_workspace(const hificar_linear* g, int B, int T, void* base) {
+    const size_t rows = round_up_sz((size_t)B * (size_t)T, 256);  // whole tiles of slack behind the last row
+    LinearWorkspace w;
+    Carver cv(base, 256);
+    w.xin = cv.floats(rows * g->in_pad);
+    w.y = cv.floats(rows * g->w.cout_pad);
+    w.bytes = cv.bytes();
+    return w;
+}
+
 extern "C" size_t hificar_linear_workspace_bytes(const hificar_linear* g, int B, int T) {
     if (!linear_shape_ok(g, B, T)) return 0;
-    const size_t rows = round_up_sz((size_t)B * (size_t)T, 256);  // whole tiles of slack behind the last row
-    return round_up_sz(rows * g->in_pad * sizeof(float), 256) + round_up_sz(rows * g->w.cout_pad * sizeof(float), 256);
+    return linear_plan_workspace(g, B, T, nullptr).bytes;
 }
 
 extern "C" int hificar_linear_forward(hificar_linear* g, const float* x, const int32_t* lengths, float* out, int B, int T, void* workspace,
                                       size_t workspace_bytes, void* stream_) {
     if (!g || !x || !out) return fail(HIFICAR_E_INVALID, "hificar_linear_forward: null argument");
     if (!linear_shape_ok(g, B, T)) return fail(HIFICAR_E_INVALID, "hificar_linear_forward: B=%d, T=%d out of range (B <= 65535, B T max(in, out) < 2^31)", B, T);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
-    const size_t need = hificar_linear_workspace_bytes(g, B, T);
-    if (workspace_bytes < need) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+    const LinearWorkspace ws = linear_plan_workspace(g, B, T, workspace);
+    int rc;
+    if ((rc = check_workspace(nullptr, workspace, workspace_bytes, ws.bytes)) != HIFICAR_OK) return rc;
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
-    const size_t rows = round_up_sz((size_t)B * (size_t)T, 256);
-    float* const xin = static_cast<float*>(workspace);
-    float* const y = reinterpret_cast<float*>(static_cast<char*>(workspace) + round_up_sz(rows * g->in_pad * sizeof(float), 256));
+    float* const xin = ws.xin;
+    float* const y = ws.y;
     const double M = (double)B * T;
     const int Op = g->w.cout_pad;
     {
@@ -92,14 +105,12 @@ extern "C" int hificar_linear_forward(hificar_linear* g, const float* x, const i
     Ragged rg;
     rg.seq_len = lengths;
     rg.frames = T;
-    const ConvLayer* ls[1] = {&g->w};
-    ConvIO io[1];
-    io[0] = ConvIO();
-    io[0].xs = reinterpret_cast<const char*>(xin);
-    io[0].res = nullptr;
-    io[0].y = y;
-    io[0].ys = nullptr;
-    if ((rc = launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+    ConvIO io{};
+    io.xs = reinterpret_cast<const char*>(xin);
+    io.res = nullptr;
+    io.y = y;
+    io.ys = nullptr;
+    if ((rc = launch_conv1(h, g->w, B, T, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
     {
         ProfScope prof(h, stream, "xfmr_out_kernel", 0.0, 4.0 * M * (g->out + Op));
         hipLaunchKernelGGL(xfmr_out_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)(Op / 32), (unsigned)B), dim3(256), 0, stream, static_cast<const float*>(y),

@@ -125,23 +125,20 @@ static MelPlan mel_plan(const hificar_mel* m, int B, int T) {
     MelPlan p;
     p.frames = 1 + T / m->cfg.hop_size;
     p.M = (long long)B * p.frames;
-    auto take = [&](size_t elems) {
-        const size_t at = p.floats;
-        p.floats += round_up_sz(elems * sizeof(float), 1024) / sizeof(float);
-        return at;
-    };
+    Carver cv(nullptr, 1024);  // (offsets in floats into the caller's workspace)
     const size_t M = (size_t)p.M, N = (size_t)m->cfg.fft_size;
     for (int i = 0; i < 2; ++i) {
-        p.A[i] = take(M * N);
-        p.S[i] = take(M * 2 * m->nfp);
-        p.amp[i] = take(M * m->nfp);
-        p.mel[i] = take(M * m->mp);
+        p.A[i] = cv.floats_at(M * N);
+        p.S[i] = cv.floats_at(M * 2 * m->nfp);
+        p.amp[i] = cv.floats_at(M * m->nfp);
+        p.mel[i] = cv.floats_at(M * m->mp);
     }
-    p.dmel = take(M * m->mp);
-    p.damp = take(M * m->nfp);
-    p.dS = take(M * 2 * m->nfp);
-    p.dA = take(M * N);
-    p.partial = take(kMelLossBlocks * 3 + 8);  // (STFT mode: [blocks][3] partials, then the 4 totals)
+    p.dmel = cv.floats_at(M * m->mp);
+    p.damp = cv.floats_at(M * m->nfp);
+    p.dS = cv.floats_at(M * 2 * m->nfp);
+    p.dA = cv.floats_at(M * N);
+    p.partial = cv.floats_at(kMelLossBlocks * 3 + 8);  // (STFT mode: [blocks][3] partials, then the 4 totals)
+    p.floats = cv.bytes() / sizeof(float);
     return p;
 }
 
@@ -168,12 +165,10 @@ extern "C" int hificar_mel_loss(hificar_mel* m, const float* y_hat, const float*
     const Ragged rg;
     const int N = c.fft_size;
     auto gemm = [&](const ConvLayer& L, const float* x, float* y_out) {
-        const ConvLayer* ls[1] = {&L};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(x);
-        io[0].y = y_out;
-        return launch_conv(h, ls, 1, 1, (int)p.M, io, 0.f, rg, stream);
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(x);
+        io.y = y_out;
+        return launch_conv1(h, L, 1, (int)p.M, io, 0.f, rg, stream);
     };
     for (int i = 0; i < 2; ++i) {
         FrameParams fp;
@@ -292,12 +287,10 @@ extern "C" int hificar_stft_loss_forward(hificar_mel* m, const float* y_hat, con
         fp.frames = p.frames;
         hipLaunchKernelGGL(mel_frame_kernel, dim3(ew_blocks(h, fp.total4)), dim3(256), 0, stream, fp);
         HIP_TRY(hipGetLastError());
-        const ConvLayer* ls[1] = {&m->Fdft};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(ws + p.A[i]);
-        io[0].y = ws + p.S[i];
-        if ((rc = launch_conv(h, ls, 1, 1, (int)p.M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(ws + p.A[i]);
+        io.y = ws + p.S[i];
+        if ((rc = launch_conv1(h, m->Fdft, 1, (int)p.M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
         AmpParams ap;
         memset(&ap, 0, sizeof(ap));
         ap.S = ws + p.S[i];
@@ -348,12 +341,10 @@ extern "C" int hificar_stft_loss_backward(hificar_mel* m, int B, int T, const fl
     ap.eps = c.eps;
     hipLaunchKernelGGL(mel_amp_bwd_kernel, dim3(ew_blocks(h, ap.total)), dim3(256), 0, stream, ap);
     HIP_TRY(hipGetLastError());
-    const ConvLayer* ls[1] = {&m->Ddft};
-    ConvIO io[1];
-    io[0] = ConvIO();
-    io[0].xs = reinterpret_cast<const char*>(ws + p.dS);
-    io[0].y = ws + p.dA;
-    if ((rc = launch_conv(h, ls, 1, 1, (int)p.M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
+    ConvIO io{};
+    io.xs = reinterpret_cast<const char*>(ws + p.dS);
+    io.y = ws + p.dA;
+    if ((rc = launch_conv1(h, m->Ddft, 1, (int)p.M, io, 0.f, rg, stream)) != HIFICAR_OK) return rc;
     OlaParams op;
     op.dA = ws + p.dA;
     op.dy = dy_hat;

@@ -187,7 +187,7 @@ static int train_init(hificar_handle* h) {
             ts->by_name[fw[q]->name] = {fw[q], &ts->dg_gb[i * 5 + q]};
         }
     }
-    for (auto& kv : h->expected) ts->raw.add(kv.first, kv.second, gen_bucket_of(h, kv.first));
+    for (auto& kv : h->weights.expected) ts->raw.add(kv.first, kv.second, gen_bucket_of(h, kv.first));
     ts->raw.n_buckets = gen_bucket_count(h);
     if (!h->d_out_bias) {
         void* p = nullptr;
@@ -252,7 +252,7 @@ static PackParams simple_pack(int mode, const float* src, float* dst, long long 
 // the bias replicated over a transposed conv's phases, the output conv's [k][Cp] layout, the PastFCEncoder's transposed matrices.
 static int pack_jobs_for(hificar_handle* h, const std::string& n, const float* data, std::vector<PackParams>& jobs) {
     TrainState* ts = train_state(h);
-    if (!h->expected.count(n)) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", n.c_str());
+    if (!h->weights.expected.count(n)) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", n.c_str());
     const hificar_config& cfg = h->cfg;
     if (n == "output_conv.1.weight") {
         const int C = h->c_last, Cp = round_up(h->c_last, 32);
@@ -285,7 +285,7 @@ static int pack_jobs_for(hificar_handle* h, const std::string& n, const float* d
                    : n == "ph_emb_mat.weight" ? h->d_ph_emb : n == "ph_fc.weight" ? h->d_phfc_w : n == "ph_fc.bias" ? h->d_phfc_b : nullptr;
         if (dst) {
             long long total = 1;
-            for (auto v : h->expected.at(n)) total *= v;
+            for (auto v : h->weights.expected.at(n)) total *= v;
             jobs.push_back(simple_pack(7, data, dst, total));
             return HIFICAR_OK;
         }
@@ -574,46 +574,41 @@ extern "C" int hificar_weight_norm_backward_bucket(hificar_handle* h, const floa
 // ------------------------------------------------------------------------------------------------
 static Tape plan_tape(const hificar_handle* h, int B, int T, void* base) {
     Tape t;
-    size_t off = 0;
-    auto take = [&](size_t elems) {
-        char* p = base ? static_cast<char*>(base) + off : nullptr;
-        off += round_up_sz(elems * sizeof(float), 1024);
-        return p;
-    };
+    Carver cv(base, 1024);
     const hificar_config& c = h->cfg;
-    t.xin = reinterpret_cast<float*>(take((size_t)B * T * h->cin_pad));
+    t.xin = cv.floats((size_t)B * T * h->cin_pad);
     if (h->arch == 1) {  // GBlockGenerator (hificar_gblock.hip.inc): per GBlock the two input copies at the output rate and three ReLU'd conv inputs
-        t.mlp = reinterpret_cast<float*>(take((size_t)B * 5 * 1024));
+        t.mlp = cv.floats((size_t)B * 5 * 1024);
         size_t r = (size_t)T;
         for (size_t i = 0; i < h->gb.size(); ++i) {
             r *= (size_t)h->gb[i].scale;
-            t.g_xu[i] = take((size_t)B * r * h->gb[i].c1a.cin_pad);
-            t.g_a1u[i] = take((size_t)B * r * h->gb[i].c1a.cin_pad);
-            t.g_a2[i] = take((size_t)B * r * h->gb[i].c1a.cout_pad);
-            t.g_a3[i] = take((size_t)B * r * h->gb[i].c1a.cout_pad);
-            t.g_a4[i] = take((size_t)B * r * h->gb[i].c1a.cout_pad);
+            t.g_xu[i] = cv.floats<char>((size_t)B * r * h->gb[i].c1a.cin_pad);
+            t.g_a1u[i] = cv.floats<char>((size_t)B * r * h->gb[i].c1a.cin_pad);
+            t.g_a2[i] = cv.floats<char>((size_t)B * r * h->gb[i].c1a.cout_pad);
+            t.g_a3[i] = cv.floats<char>((size_t)B * r * h->gb[i].c1a.cout_pad);
+            t.g_a4[i] = cv.floats<char>((size_t)B * r * h->gb[i].c1a.cout_pad);
         }
-        t.fin[0] = reinterpret_cast<float*>(take((size_t)B * r * round_up(h->c_last, 32)));
-        t.bytes = off;
+        t.fin[0] = cv.floats((size_t)B * r * round_up(h->c_last, 32));
+        t.bytes = cv.bytes();
         return t;
     }
-    t.h0_s = take((size_t)B * T * stage_pad(c, 0));
-    t.mlp = reinterpret_cast<float*>(take((size_t)B * 5 * 1024));
+    t.h0_s = cv.floats<char>((size_t)B * T * stage_pad(c, 0));
+    t.mlp = cv.floats((size_t)B * 5 * 1024);
     size_t rows = (size_t)T;
     for (int i = 0; i < c.n_stages; ++i) {
-        t.upin_s[i] = i == 0 ? t.h0_s : take((size_t)B * rows * stage_pad(c, i));
+        t.upin_s[i] = i == 0 ? t.h0_s : cv.floats<char>((size_t)B * rows * stage_pad(c, i));
         rows *= c.upsample_scales[i];
         const size_t se = (size_t)B * rows * stage_pad(c, i + 1);
-        t.u_s[i] = take(se);
+        t.u_s[i] = cv.floats<char>(se);
         for (int j = 0; j < c.n_blocks; ++j)
             for (int d = 0; d < c.n_dilations[j]; ++d) {
-                t.xt_s[i][j][d] = take(se);
-                t.x_s[i][j][d] = d + 1 < c.n_dilations[j] ? take(se) : nullptr;
+                t.xt_s[i][j][d] = cv.floats<char>(se);
+                t.x_s[i][j][d] = d + 1 < c.n_dilations[j] ? cv.floats<char>(se) : nullptr;
             }
         if (i + 1 == c.n_stages)
-            for (int j = 0; j < std::max(3, c.n_blocks); ++j) t.fin[j] = reinterpret_cast<float*>(take(se));
+            for (int j = 0; j < std::max(3, c.n_blocks); ++j) t.fin[j] = cv.floats(se);
     }
-    t.bytes = off;
+    t.bytes = cv.bytes();
     return t;
 }
 
@@ -827,21 +822,16 @@ static BwdWs plan_bwd(const hificar_handle* h, int B, int T, void* base) {
     BwdWs w;
     w.accumulate = false;
     w.defer = nullptr;
-    size_t off = 0;
-    auto take = [&](size_t elems) {
-        float* p = base ? reinterpret_cast<float*>(static_cast<char*>(base) + off) : nullptr;
-        off += round_up_sz(elems * sizeof(float), 1024);
-        return p;
-    };
+    Carver cv(base, 1024);
     const hificar_config& c = h->cfg;
     const size_t se = stage_elems(h, B, T);
-    for (int j = 0; j < kMaxBlk; ++j) w.dx[j] = j < std::max(3, c.n_blocks) ? take(se) : nullptr;
-    for (int j = 0; j < kMaxBlk; ++j) w.g1[j] = j < std::max(3, c.n_blocks) ? take(se) : nullptr;
-    w.du = take(se);
-    w.dm[0] = take(se);
-    w.dm[1] = take(se);
-    w.dh0 = take((size_t)B * T * stage_pad(c, 0));
-    w.dxin = take((size_t)B * T * round_up(c.in_channels, 32));
+    for (int j = 0; j < kMaxBlk; ++j) w.dx[j] = j < std::max(3, c.n_blocks) ? cv.floats(se) : nullptr;
+    for (int j = 0; j < kMaxBlk; ++j) w.g1[j] = j < std::max(3, c.n_blocks) ? cv.floats(se) : nullptr;
+    w.du = cv.floats(se);
+    w.dm[0] = cv.floats(se);
+    w.dm[1] = cv.floats(se);
+    w.dh0 = cv.floats((size_t)B * T * stage_pad(c, 0));
+    w.dxin = cv.floats((size_t)B * T * round_up(c.in_channels, 32));
     // weight / bias gradient partials: every layer has its own piece (the reductions of a whole pass run as ONE launch at its end, flush_reduce)
     size_t pe = wgrad_partial_elems(h, h->input_conv, B, T), ce = wgrad_colsum_elems(h, h->input_conv, B, T);
     size_t rows = (size_t)T;
@@ -863,17 +853,17 @@ static BwdWs plan_bwd(const hificar_handle* h, int B, int T, void* base) {
             }
     }
     w.partial_elems = pe;
-    w.partial = take(pe);
+    w.partial = cv.floats(pe);
     w.colsum_elems = ce;
-    w.colsum = take(ce);
-    w.mlp_delta = take((size_t)B * 5 * 512);
-    w.dfeat = take((size_t)B * 512);
+    w.colsum = cv.floats(ce);
+    w.mlp_delta = cv.floats((size_t)B * 5 * 512);
+    w.dfeat = cv.floats((size_t)B * 512);
     w.outp_elems = (size_t)B * kOutSplit * ((size_t)c.kernel_size * round_up(h->c_last, 32) + 1);
-    w.outp = take(w.outp_elems);
-    w.dspk = c.use_spk_id ? take((size_t)B * c.in_channels) : nullptr;
-    w.dwin = c.use_ph_loss ? take((size_t)B * T * stage_pad(c, c.n_stages)) : nullptr;
-    w.php = c.use_ph_loss ? take((size_t)B * T * c.num_ph * (stage_channels(c, c.n_stages) + 1)) : nullptr;
-    w.bytes = off;
+    w.outp = cv.floats(w.outp_elems);
+    w.dspk = c.use_spk_id ? cv.floats((size_t)B * c.in_channels) : nullptr;
+    w.dwin = c.use_ph_loss ? cv.floats((size_t)B * T * stage_pad(c, c.n_stages)) : nullptr;
+    w.php = c.use_ph_loss ? cv.floats((size_t)B * T * c.num_ph * (stage_channels(c, c.n_stages) + 1)) : nullptr;
+    w.bytes = cv.bytes();
     return w;
 }
 

@@ -34,8 +34,7 @@ struct XfmrTrain;  // hificar_xfmr_train.hip.inc
 struct hificar_xfmr {
     hificar_xfmr_config cfg;
     hificar_engine eng;
-    std::map<std::string, std::vector<int64_t>> expected;
-    std::map<std::string, HostTensor> tensors;
+    WeightIntake weights;
     ConvLayer c1[3], c2[3], rp, w_in, w_out;
     std::vector<XfmrEncLayer> enc;  // sized once, in hificar_xfmr_create (launch plans are keyed by the layers' addresses)
     int cin_pad = 0;
@@ -44,11 +43,7 @@ struct hificar_xfmr {
     // forward goes by `precision` alone)
     int train_precision = HIFICAR_PREC_F32;
     bool finalized = false;
-    struct Tap {
-        float* dst;
-        size_t cap;
-    };
-    std::map<std::string, Tap> taps;
+    TapTable taps;
     XfmrTrain* train = nullptr;  // built by the first training entry point
     int train_failed = HIFICAR_OK;
 };
@@ -155,33 +150,33 @@ extern "C" int hificar_xfmr_create(const hificar_xfmr_config* cfg, hificar_xfmr*
     g->cin_pad = round_up(c.in_channels, 32);
     for (int i = 0; i < 3; ++i) {
         const std::string b = "conv_blocks." + std::to_string(i) + ".";
-        g->expected[b + "conv1.weight"] = {F, i == 0 ? C : F, 3};
-        g->expected[b + "conv2.weight"] = {F, F, 3};
-        for (const char* m : {"conv1", "conv2", "bn1", "bn2"}) g->expected[b + m + ".bias"] = {F};
+        g->weights.expected[b + "conv1.weight"] = {F, i == 0 ? C : F, 3};
+        g->weights.expected[b + "conv2.weight"] = {F, F, 3};
+        for (const char* m : {"conv1", "conv2", "bn1", "bn2"}) g->weights.expected[b + m + ".bias"] = {F};
         for (const char* m : {"bn1", "bn2"})
-            for (const char* t : {".weight", ".running_mean", ".running_var"}) g->expected[b + m + t] = {F};
+            for (const char* t : {".weight", ".running_mean", ".running_var"}) g->weights.expected[b + m + t] = {F};
         if (i == 0 && C != F) {  // (pytorch_layers.py:108-112: the 1 x 1 path exists when the block changes the width)
-            g->expected[b + "residual_path.weight"] = {F, C, 1};
-            g->expected[b + "residual_path.bias"] = {F};
-            for (const char* t : {".weight", ".bias", ".running_mean", ".running_var"}) g->expected[b + "res_norm" + t] = {F};
+            g->weights.expected[b + "residual_path.weight"] = {F, C, 1};
+            g->weights.expected[b + "residual_path.bias"] = {F};
+            for (const char* t : {".weight", ".bias", ".running_mean", ".running_var"}) g->weights.expected[b + "res_norm" + t] = {F};
         }
     }
-    g->expected["w_raw_in.weight"] = {F, F};
-    g->expected["w_raw_in.bias"] = {F};
+    g->weights.expected["w_raw_in.weight"] = {F, F};
+    g->weights.expected["w_raw_in.bias"] = {F};
     for (int l = 0; l < c.elayers; ++l) {
         const std::string b = "transformer.layers." + std::to_string(l) + ".";
-        for (const char* w : {"w_q", "w_k", "w_v"}) g->expected[b + "self_attn." + w] = {kXfmrHeads, F, d};
-        g->expected[b + "self_attn.w_o"] = {kXfmrHeads, d, F};
-        g->expected[b + "self_attn.relative_positional.embeddings"] = {kXfmrHeads, kXfmrTab, d, 1};
-        g->expected[b + "linear1.weight"] = {kXfmrFF, F};
-        g->expected[b + "linear1.bias"] = {kXfmrFF};
-        g->expected[b + "linear2.weight"] = {F, kXfmrFF};
-        g->expected[b + "linear2.bias"] = {F};
+        for (const char* w : {"w_q", "w_k", "w_v"}) g->weights.expected[b + "self_attn." + w] = {kXfmrHeads, F, d};
+        g->weights.expected[b + "self_attn.w_o"] = {kXfmrHeads, d, F};
+        g->weights.expected[b + "self_attn.relative_positional.embeddings"] = {kXfmrHeads, kXfmrTab, d, 1};
+        g->weights.expected[b + "linear1.weight"] = {kXfmrFF, F};
+        g->weights.expected[b + "linear1.bias"] = {kXfmrFF};
+        g->weights.expected[b + "linear2.weight"] = {F, kXfmrFF};
+        g->weights.expected[b + "linear2.bias"] = {F};
         for (const char* n : {"norm1", "norm2"})
-            for (const char* t : {".weight", ".bias"}) g->expected[b + n + t] = {F};
+            for (const char* t : {".weight", ".bias"}) g->weights.expected[b + n + t] = {F};
     }
-    g->expected["w_out.weight"] = {O, F};
-    g->expected["w_out.bias"] = {O};
+    g->weights.expected["w_out.weight"] = {O, F};
+    g->weights.expected["w_out.bias"] = {O};
     g->enc.resize((size_t)c.elayers);
     const int Fi = c.hidden_dim;
     int rc = HIFICAR_OK;
@@ -221,22 +216,7 @@ extern "C" hificar_engine* hificar_xfmr_engine(hificar_xfmr* g) { return g ? &g-
 extern "C" int hificar_xfmr_set_weight(hificar_xfmr* g, const char* name, const float* data, const int64_t* shape, int ndim) {
     if (!g || !name || !data || !shape) return fail(HIFICAR_E_INVALID, "hificar_xfmr_set_weight: null argument");
     if (g->finalized) return fail(HIFICAR_E_STATE, "hificar_xfmr_set_weight(%s) after hificar_xfmr_finalize", name);
-    auto it = g->expected.find(name);
-    if (it == g->expected.end()) return fail(HIFICAR_E_INVALID, "unexpected tensor name '%s' for this configuration", name);
-    std::vector<int64_t> s(shape, shape + ndim);
-    if (s != it->second) {
-        std::string want, got;
-        for (auto v : it->second) want += std::to_string(v) + ",";
-        for (auto v : s) got += std::to_string(v) + ",";
-        return fail(HIFICAR_E_INVALID, "size mismatch for %s: expected (%s) got (%s)", name, want.c_str(), got.c_str());
-    }
-    size_t n = 1;
-    for (auto v : s) n *= (size_t)v;
-    HostTensor t;
-    t.shape = s;
-    t.data.assign(data, data + n);
-    g->tensors[name] = std::move(t);
-    return HIFICAR_OK;
+    return g->weights.set(name, data, shape, ndim);
 }
 
 // bias and weight fragments of one layer, in the engine's arithmetic only (h->precision is set before the first pack): one resident copy
@@ -262,9 +242,9 @@ extern "C" int hificar_xfmr_set_precision(hificar_xfmr* g, int precision) {
 
 // Conv1d followed by an eval-mode BatchNorm1d as one conv: y = (W x + b - mean) * gamma / sqrt(var + 1e-5) + beta, folded in double
 static int xfmr_pack_folded(hificar_xfmr* g, ConvLayer& L, const std::string& conv, const std::string& bn) {
-    const HostTensor& W = g->tensors.at(conv + ".weight");
-    const std::vector<float>&b = g->tensors.at(conv + ".bias").data, &gm = g->tensors.at(bn + ".weight").data, &bt = g->tensors.at(bn + ".bias").data,
-                     &mu = g->tensors.at(bn + ".running_mean").data, &var = g->tensors.at(bn + ".running_var").data;
+    const HostTensor& W = g->weights.at(conv + ".weight");
+    const std::vector<float>&b = g->weights.data(conv + ".bias"), &gm = g->weights.data(bn + ".weight"), &bt = g->weights.data(bn + ".bias"),
+                     &mu = g->weights.data(bn + ".running_mean"), &var = g->weights.data(bn + ".running_var");
     HostTensor Wf;
     Wf.shape = W.shape;
     Wf.data.resize(W.data.size());
@@ -289,8 +269,7 @@ static hipError_t xfmr_attn_attr() {
 extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
     if (!g) return fail(HIFICAR_E_INVALID, "hificar_xfmr_finalize: null handle");
     if (g->finalized) return HIFICAR_OK;
-    for (auto& kv : g->expected)
-        if (!g->tensors.count(kv.first)) return fail(HIFICAR_E_STATE, "Missing key(s) in state_dict: \"%s\"", kv.first.c_str());
+    if (const int missing = g->weights.check_complete()) return missing;
     hificar_engine* h = &g->eng;
     const int F = g->cfg.hidden_dim, d = F / kXfmrHeads;
     int rc;
@@ -301,13 +280,8 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
         if ((rc = xfmr_pack_folded(g, g->c2[i], b + "conv2", b + "bn2")) != HIFICAR_OK) return rc;
     }
     if (g->rp.cout && (rc = xfmr_pack_folded(g, g->rp, "conv_blocks.0.residual_path", "conv_blocks.0.res_norm")) != HIFICAR_OK) return rc;
-    auto linear = [&](ConvLayer& L, const std::string& name) {
-        HostTensor W = g->tensors.at(name + ".weight");
-        W.shape.push_back(1);
-        return xfmr_pack(h, L, W, &g->tensors.at(name + ".bias").data);
-    };
-    if ((rc = linear(g->w_in, "w_raw_in")) != HIFICAR_OK) return rc;
-    if ((rc = linear(g->w_out, "w_out")) != HIFICAR_OK) return rc;
+    if ((rc = pack_linear(h, g->w_in, g->weights, "w_raw_in")) != HIFICAR_OK) return rc;
+    if ((rc = pack_linear(h, g->w_out, g->weights, "w_out")) != HIFICAR_OK) return rc;
     for (int l = 0; l < g->cfg.elayers; ++l) {
         const std::string b = "transformer.layers." + std::to_string(l) + ".";
         XfmrEncLayer& E = g->enc[(size_t)l];
@@ -317,7 +291,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
             W.data.resize((size_t)3 * F * F);
             int s = 0;
             for (const char* w : {"w_q", "w_k", "w_v"}) {
-                const std::vector<float>& src = g->tensors.at(b + "self_attn." + w).data;
+                const std::vector<float>& src = g->weights.data(b + "self_attn." + w);
                 for (int hh = 0; hh < kXfmrHeads; ++hh)
                     for (int f = 0; f < F; ++f)
                         for (int a = 0; a < d; ++a) W.data[((size_t)(s * kXfmrHeads + hh) * d + a) * F + f] = src[((size_t)hh * F + f) * d + a];
@@ -326,7 +300,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
             if ((rc = xfmr_pack(h, E.qkv, W, nullptr)) != HIFICAR_OK) return rc;
         }
         {   // out = einsum('bhta,haf->tbf', o, w_o) (:228): row f of the GEMM's weight is w_o[:, :, f] over (h, a)
-            const std::vector<float>& src = g->tensors.at(b + "self_attn.w_o").data;
+            const std::vector<float>& src = g->weights.data(b + "self_attn.w_o");
             HostTensor W;
             W.shape = {F, F, 1};
             W.data.resize((size_t)F * F);
@@ -334,11 +308,11 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
                 for (int f = 0; f < F; ++f) W.data[(size_t)f * F + k] = src[(size_t)k * F + f];
             if ((rc = xfmr_pack(h, E.wo, W, nullptr)) != HIFICAR_OK) return rc;
         }
-        if ((rc = linear(E.l1, b + "linear1")) != HIFICAR_OK) return rc;
-        if ((rc = linear(E.l2, b + "linear2")) != HIFICAR_OK) return rc;
-        if ((rc = upload(h, g->tensors.at(b + "self_attn.relative_positional.embeddings").data, &E.d_emb)) != HIFICAR_OK) return rc;
+        if ((rc = pack_linear(h, E.l1, g->weights, b + "linear1")) != HIFICAR_OK) return rc;
+        if ((rc = pack_linear(h, E.l2, g->weights, b + "linear2")) != HIFICAR_OK) return rc;
+        if ((rc = upload(h, g->weights.data(b + "self_attn.relative_positional.embeddings"), &E.d_emb)) != HIFICAR_OK) return rc;
         if (xfmr_arith(g->precision).a) {  // the tables as the attention's MFMA operand: split once, padded to whole 16-row tiles
-            const std::vector<float>& src = g->tensors.at(b + "self_attn.relative_positional.embeddings").data;
+            const std::vector<float>& src = g->weights.data(b + "self_attn.relative_positional.embeddings");
             const size_t half = (size_t)kXfmrHeads * kXfmrTabPad * d;
             std::vector<uint16_t> t16(2 * half, 0);
             for (int hh = 0; hh < kXfmrHeads; ++hh)
@@ -357,7 +331,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
         }
         int i = 0;
         for (const char* n : {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"})
-            if ((rc = upload(h, g->tensors.at(b + n).data, &E.d_ln[i++])) != HIFICAR_OK) return rc;
+            if ((rc = upload(h, g->weights.data(b + n), &E.d_ln[i++])) != HIFICAR_OK) return rc;
     }
     HIP_TRY(xfmr_for_every_d([](auto D) { return xfmr_attn_attr<D()>(); }));
     if (xfmr_arith(g->precision).a) HIP_TRY(xfmr_for_every_d([](auto D) { return xfmr_attn16_attr<D()>(); }));
@@ -367,7 +341,7 @@ extern "C" int hificar_xfmr_finalize(hificar_xfmr* g) {
     h->use_pair = false;
     h->ksplit = 0;  // one accumulation order for every launch shape: an utterance's result does not depend on what it is batched with
     HIP_TRY(hipDeviceSynchronize());
-    g->tensors.clear();  // (g->expected stays: the training entry points go by it)
+    g->weights.clear_staged();  // (g->weights.expected stays: the training entry points go by it)
     g->finalized = true;
     return HIFICAR_OK;
 }
@@ -381,17 +355,14 @@ struct XfmrWorkspace {
 
 static XfmrWorkspace xfmr_plan_workspace(const hificar_xfmr* g, int B, int T, void* base) {
     const size_t rows = round_up_sz((size_t)std::max(B, 0) * (size_t)std::max(T, 0), 256);  // whole tiles of slack behind the last row
-    const size_t xb = round_up_sz(rows * g->cin_pad * sizeof(float), 256);
-    const size_t rb = round_up_sz(rows * g->cfg.hidden_dim * sizeof(float), 256);
-    const size_t wb = round_up_sz(rows * kXfmrFF * sizeof(float), 256);
     XfmrWorkspace w;
-    char* p = static_cast<char*>(base);
-    w.xin = reinterpret_cast<float*>(p);
+    Carver cv(base, 256);
+    w.xin = cv.floats(rows * g->cin_pad);
     // bf16x3: split rows take a fp32 row's bytes, and the layer input and norm1's output exist in both formats at once: two more row buffers
     const int nr = xfmr_x3(g) ? 5 : 3;
-    for (int i = 0; i < 5; ++i) w.r[i] = i < nr ? reinterpret_cast<float*>(p + xb + i * rb) : nullptr;
-    w.wide = reinterpret_cast<float*>(p + xb + nr * rb);
-    w.bytes = xb + nr * rb + wb;
+    for (int i = 0; i < 5; ++i) w.r[i] = i < nr ? cv.floats(rows * g->cfg.hidden_dim) : nullptr;
+    w.wide = cv.floats(rows * kXfmrFF);
+    w.bytes = cv.bytes();
     return w;
 }
 
@@ -404,25 +375,17 @@ extern "C" size_t hificar_xfmr_workspace_bytes(const hificar_xfmr* g, int B, int
 // "w_raw_in", "layers.<n>.norm1" (the attention sub-block's output), "layers.<n>" (the layer's output).  name = NULL: forget all; dst = NULL: forget one.
 extern "C" int hificar_xfmr_debug_tap(hificar_xfmr* g, const char* name, float* dst, size_t capacity) {
     if (!g) return fail(HIFICAR_E_INVALID, "null handle");
-    if (!name) {
-        g->taps.clear();
-        return HIFICAR_OK;
-    }
-    if (!dst) {
-        g->taps.erase(name);
-        return HIFICAR_OK;
-    }
-    if (xfmr_x3(g) && std::string(name) == "conv_blocks")
+    if (name && dst && xfmr_x3(g) && std::string(name) == "conv_blocks")
         return fail(HIFICAR_E_INVALID, "debug tap 'conv_blocks': a bf16x3 handle holds the conv blocks' output as split bf16 rows only, not as fp32 rows");
-    g->taps[name] = {dst, capacity};
+    g->taps.set(name, dst, capacity);
     return HIFICAR_OK;
 }
 
 static int xfmr_emit_tap(hificar_xfmr* g, const std::string& name, const float* rows, size_t floats, hipStream_t stream) {
-    auto it = g->taps.find(name);
-    if (it == g->taps.end()) return HIFICAR_OK;
-    if (it->second.cap < floats) return fail(HIFICAR_E_INVALID, "debug tap '%s' needs %zu floats, buffer has %zu", name.c_str(), floats, it->second.cap);
-    HIP_TRY(hipMemcpyAsync(it->second.dst, rows, floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    float* dst;
+    const int rc = g->taps.find(name, floats, &dst);
+    if (rc != HIFICAR_OK || !dst) return rc;
+    HIP_TRY(hipMemcpyAsync(dst, rows, floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
     return HIFICAR_OK;
 }
 
@@ -446,19 +409,17 @@ static int xfmr_forward_run(hificar_xfmr* g, const float* x, const int32_t* leng
     rg.seq_len = lengths;
     rg.frames = T;
     const bool x3 = xfmr_x3(g), a16 = xfmr_arith(g->precision).a;
-    if (x3 && g->taps.count("conv_blocks")) return fail(HIFICAR_E_INVALID, "debug tap 'conv_blocks': a bf16x3 handle holds these rows as split bf16 rows only");
+    if (x3 && g->taps.wanted("conv_blocks")) return fail(HIFICAR_E_INVALID, "debug tap 'conv_blocks': a bf16x3 handle holds these rows as split bf16 rows only");
     // one launch of one layer: xs -> y (fp32) and / or ys (the activated copy: ReLU, or with slope 1 the identity), + res.  xs and ys are fp32
     // rows in exact fp32 and split rows in bf16x3; res_relu (bf16x3): res holds the rows before their ReLU
     auto conv = [&](const ConvLayer& L, const float* xs, const float* res, float* y, float* ys, float slope = 0.f, bool res_relu = false) {
-        const ConvLayer* ls[1] = {&L};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(xs);
-        io[0].res = res;
-        io[0].y = y;
-        io[0].ys = reinterpret_cast<char*>(ys);
-        io[0].res_relu = res_relu;
-        return launch_conv(h, ls, 1, B, T, io, slope, rg, stream);
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(xs);
+        io.res = res;
+        io.y = y;
+        io.ys = reinterpret_cast<char*>(ys);
+        io.res_relu = res_relu;
+        return launch_conv1(h, L, B, T, io, slope, rg, stream);
     };
     // dst: the fp32 rows; dst_s (bf16x3): the same rows as split rows, the next GEMM's input
     auto layer_norm = [&](const float* src, const float* gamma, const float* beta, float* dst, float* dst_s) {
@@ -592,12 +553,11 @@ extern "C" int hificar_xfmr_forward(hificar_xfmr* g, const float* x, const int32
         for (int b = 0; b < B; ++b)
             if (lengths_host[b] < 0 || lengths_host[b] > T)
                 return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward: lengths[%d]=%d outside 0 .. T=%d", b, lengths_host[b], T);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
     const XfmrWorkspace ws = xfmr_plan_workspace(g, B, T, workspace);
-    if (workspace_bytes < ws.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
+    int rc;
+    if ((rc = check_workspace(nullptr, workspace, workspace_bytes, ws.bytes)) != HIFICAR_OK) return rc;
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     return xfmr_forward_run(g, x, lengths, out, B, T, ws, stream, nullptr);
 }
@@ -611,13 +571,12 @@ struct XfmrLowWorkspace {
 };
 
 static XfmrLowWorkspace xfmr_plan_workspace_lowrate(const hificar_xfmr* g, int B, int Tl, int factor, void* base) {
-    const size_t main = xfmr_plan_workspace(g, B, Tl * factor, nullptr).bytes;
-    const size_t sb = round_up_sz((size_t)std::max(B, 0) * 2 * sizeof(double), 256), lb = round_up_sz((size_t)std::max(B, 0) * sizeof(int), 256);
     XfmrLowWorkspace w;
-    char* p = static_cast<char*>(base);
-    w.stats = reinterpret_cast<double*>(p + main);
-    w.lens = reinterpret_cast<int*>(p + main + sb);
-    w.bytes = main + sb + lb;
+    Carver cv(base, 256);
+    cv.take<char>(xfmr_plan_workspace(g, B, Tl * factor, nullptr).bytes);  // (the forward's own buffers, carved by xfmr_plan_workspace)
+    w.stats = cv.take<double>((size_t)std::max(B, 0) * 2 * sizeof(double));
+    w.lens = cv.take<int>((size_t)std::max(B, 0) * sizeof(int));
+    w.bytes = cv.bytes();
     return w;
 }
 
@@ -643,9 +602,9 @@ extern "C" int hificar_xfmr_forward_lowrate(hificar_xfmr* g, const float* x, con
         for (int b = 0; b < B; ++b)
             if (lengths_host[b] < 0 || lengths_host[b] > Tl)
                 return fail(HIFICAR_E_INVALID, "hificar_xfmr_forward_lowrate: lengths[%d]=%d outside 0 .. Tl=%d", b, lengths_host[b], Tl);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256) return fail(HIFICAR_E_INVALID, "workspace must be a 256-byte aligned device pointer");
     const XfmrLowWorkspace lw = xfmr_plan_workspace_lowrate(g, B, Tl, factor, workspace);
-    if (workspace_bytes < lw.bytes) return fail(HIFICAR_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, lw.bytes);
+    int rc;
+    if ((rc = check_workspace(nullptr, workspace, workspace_bytes, lw.bytes)) != HIFICAR_OK) return rc;
     // (every argument above is checked without the device: a handle that was never finalized is told so last)
     if (!g->finalized) return fail(HIFICAR_E_STATE, "hificar_xfmr_forward_lowrate before hificar_xfmr_finalize");
     if (factor == 1 && !zscore) return hificar_xfmr_forward(g, x, lengths, lengths_host, out, B, Tl, workspace, workspace_bytes, stream_);
@@ -653,7 +612,6 @@ extern "C" int hificar_xfmr_forward_lowrate(hificar_xfmr* g, const float* x, con
     const XfmrWorkspace ws = xfmr_plan_workspace(g, B, T, workspace);
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc;
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
     XfmrFront fe;
     fe.Tl = Tl;

@@ -164,7 +164,7 @@ static int xfmr_train_build(hificar_xfmr* g, XfmrTrain* ts) {
     const int F = g->cfg.hidden_dim, C = g->cfg.in_channels, E = g->cfg.elayers;
     const bool has_rp = g->rp.cout != 0;
     FeatureParamTable& tab = ts->tab;
-    auto add = [&](const std::string& name, bool trainable) { tab.add(g->expected, name, trainable); };
+    auto add = [&](const std::string& name, bool trainable) { tab.add(g->weights.expected, name, trainable); };
     // state_dict order: a module's weight and bias lie back to back (the (d gamma | d beta) pairs are reduced as one row of 2 F)
     for (int i = 0; i < 3; ++i) {
         const std::string b = "conv_blocks." + std::to_string(i) + ".";
@@ -357,7 +357,7 @@ extern "C" int hificar_xfmr_set_parameters_device(hificar_xfmr* g, const char* c
     hificar_engine* h = &g->eng;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if ((rc = enter_stream(h, stream)) != HIFICAR_OK) return rc;
-    if ((rc = feature_upload(g->expected, ts->tab, names, data, n, "hificar_xfmr_set_parameters_device", stream)) != HIFICAR_OK) return rc;
+    if ((rc = feature_upload(g->weights.expected, ts->tab, names, data, n, "hificar_xfmr_set_parameters_device", stream)) != HIFICAR_OK) return rc;
     if ((rc = xfmr_repack(g, stream)) != HIFICAR_OK) return rc;
     ts->have_params = true;
     return HIFICAR_OK;
@@ -493,41 +493,36 @@ struct XfmrTape {
 static XfmrTape xfmr_plan_tape(const hificar_xfmr* g, int B, int T, void* base, int Mp = 0) {
     const size_t rows = Mp ? (size_t)Mp : feature_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;  // (Mp: a multiple of 256 already, as the eval path's rows)
     const int nbn = g->rp.cout ? 7 : 6;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? static_cast<char*>(base) + off : nullptr;
-        off += round_up_sz(bytes, 256);
-        return reinterpret_cast<float*>(p);
-    };
+    Carver cv(base, 256);
     XfmrTape t;
-    t.hdr = reinterpret_cast<BigruTapeHeader*>(take(256));
-    t.xin = take(rows * g->cin_pad * 4);
+    t.hdr = cv.take<BigruTapeHeader>(256);
+    t.xin = cv.floats(rows * g->cin_pad);
     for (int j = 0; j < 7; ++j) {
-        t.y[j] = j < nbn ? take(rows * F * 4) : nullptr;
-        t.stats[j] = j < nbn ? take(3 * F * 4) : nullptr;
+        t.y[j] = j < nbn ? cv.floats(rows * F) : nullptr;
+        t.stats[j] = j < nbn ? cv.floats(3 * F) : nullptr;
     }
     for (int i = 0; i < 3; ++i) {
-        t.a1[i] = take(rows * F * 4);
-        t.bo[i] = take(rows * F * 4);
+        t.a1[i] = cv.floats(rows * F);
+        t.bo[i] = cv.floats(rows * F);
     }
     const int E = g->cfg.elayers;
     t.X.resize((size_t)E + 1);
     t.L.resize((size_t)E);
-    for (int l = 0; l <= E; ++l) t.X[(size_t)l] = take(rows * F * 4);
+    for (int l = 0; l <= E; ++l) t.X[(size_t)l] = cv.floats(rows * F);
     for (int l = 0; l < E; ++l) {
         XfmrTapeLayer& L = t.L[(size_t)l];
-        L.qkv = take(rows * 3 * F * 4);
-        L.o = take(rows * F * 4);
-        L.lse = take(rows * kXfmrHeads * 4);
-        L.p1 = take(rows * F * 4);
-        L.n1 = take(rows * F * 4);
-        L.hid = take(rows * kXfmrFF * 4);
-        L.p2 = take(rows * F * 4);
+        L.qkv = cv.floats(rows * 3 * F);
+        L.o = cv.floats(rows * F);
+        L.lse = cv.floats(rows * kXfmrHeads);
+        L.p1 = cv.floats(rows * F);
+        L.n1 = cv.floats(rows * F);
+        L.hid = cv.floats(rows * kXfmrFF);
+        L.p2 = cv.floats(rows * F);
     }
-    t.lens = reinterpret_cast<int*>(take((size_t)B * 4));
-    t.row0 = Mp ? reinterpret_cast<int*>(take(((size_t)B + 1) * 4)) : nullptr;
-    t.pad_row = Mp ? reinterpret_cast<int*>(take((size_t)Mp * 4)) : nullptr;
-    t.bytes = off;
+    t.lens = cv.take<int>((size_t)B * sizeof(int));
+    t.row0 = Mp ? cv.take<int>(((size_t)B + 1) * sizeof(int)) : nullptr;
+    t.pad_row = Mp ? cv.take<int>((size_t)Mp * sizeof(int)) : nullptr;
+    t.bytes = cv.bytes();
     return t;
 }
 
@@ -556,24 +551,19 @@ struct XfmrTrainWs {
 static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void* base, int Mp = 0) {
     const int M = Mp ? Mp : B * T;
     const size_t rows = Mp ? (size_t)Mp : feature_train_rows(B, T), F = (size_t)g->cfg.hidden_dim;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? static_cast<char*>(base) + off : nullptr;
-        off += round_up_sz(bytes, 256);
-        return reinterpret_cast<float*>(p);
-    };
+    Carver cv(base, 256);
     XfmrTrainWs w;
-    w.t1 = take(rows * F * 4);
-    w.res = take(rows * F * 4);
-    for (int i = 0; i < 3; ++i) w.d[i] = take(rows * F * 4);
-    w.wide = take(rows * kXfmrFF * 4);
-    w.gw = take(rows * kXfmrFF * 4);
-    for (int i = 0; i < 2; ++i) w.dxr[i] = take(rows * g->cin_pad * 4);
-    w.ds = take(rows * kXfmrHeads * kXfmrBand * 4);
-    w.pd = take(rows * kXfmrHeads * kXfmrBand * 4);
-    w.rowstats = take(rows * 2 * 4);
-    w.colpart = take((size_t)((M + kXfmrColRows - 1) / kXfmrColRows) * 2 * F * 4);
-    w.embpart = take((size_t)((M + kXfmrEmbRows - 1) / kXfmrEmbRows) * kXfmrTab * F * 4);
+    w.t1 = cv.floats(rows * F);
+    w.res = cv.floats(rows * F);
+    for (int i = 0; i < 3; ++i) w.d[i] = cv.floats(rows * F);
+    w.wide = cv.floats(rows * kXfmrFF);
+    w.gw = cv.floats(rows * kXfmrFF);
+    for (int i = 0; i < 2; ++i) w.dxr[i] = cv.floats(rows * g->cin_pad);
+    w.ds = cv.floats(rows * kXfmrHeads * kXfmrBand);
+    w.pd = cv.floats(rows * kXfmrHeads * kXfmrBand);
+    w.rowstats = cv.floats(rows * 2);
+    w.colpart = cv.floats((size_t)((M + kXfmrColRows - 1) / kXfmrColRows) * 2 * F);
+    w.embpart = cv.floats((size_t)((M + kXfmrEmbRows - 1) / kXfmrEmbRows) * kXfmrTab * F);
     w.partial_elems = w.colsum_elems = 0;
     if (g->train) {
         const hificar_engine* h = &g->eng;
@@ -594,14 +584,14 @@ static XfmrTrainWs xfmr_plan_train_ws(const hificar_xfmr* g, int B, int T, void*
             one(L.l2, 1, M);
         }
     }
-    w.partial = take(w.partial_elems * 4);
-    w.colsum = take(w.colsum_elems * 4);
-    w.light = reinterpret_cast<char*>(take(xfmr_plan_tape(g, B, T, nullptr, Mp).bytes));
+    w.partial = cv.floats(w.partial_elems);
+    w.colsum = cv.floats(w.colsum_elems);
+    w.light = cv.take<char>(xfmr_plan_tape(g, B, T, nullptr, Mp).bytes);
     // (last: everything in front of it lies where the fp32 arithmetic has it)
-    w.split = xfmr_train_x3(g) ? reinterpret_cast<char*>(take(rows * kXfmrFF * 4)) : nullptr;
+    w.split = xfmr_train_x3(g) ? cv.floats<char>(rows * kXfmrFF) : nullptr;
     for (char*& s : w.split_t)  // (behind it: a bf16x3 workspace is a prefix of the bf16x3w one; bf16x3wa's and bf16x3wac's are bf16x3w's)
-        s = xfmr_train_w(g) ? reinterpret_cast<char*>(take((size_t)split_t_bytes((long long)rows, kXfmrFF))) : nullptr;
-    w.bytes = off;
+        s = xfmr_train_w(g) ? cv.take<char>((size_t)split_t_bytes((long long)rows, kXfmrFF)) : nullptr;
+    w.bytes = cv.bytes();
     return w;
 }
 
@@ -650,8 +640,7 @@ static int xfmr_train_check(hificar_xfmr* g, const char* what, int B, int T, voi
         return fail(HIFICAR_E_INVALID, "%s: tape and workspace must be 256-byte aligned device pointers", what);
     const size_t tb = xfmr_plan_tape(g, B, T, nullptr, Mp).bytes, wb = xfmr_plan_train_ws(g, B, T, nullptr, Mp).bytes;
     if (tape && tape_bytes < tb) return fail(HIFICAR_E_WORKSPACE, "%s: tape too small: %zu < %zu", what, tape_bytes, tb);
-    if (workspace_bytes < wb) return fail(HIFICAR_E_WORKSPACE, "%s: workspace too small: %zu < %zu", what, workspace_bytes, wb);
-    return HIFICAR_OK;
+    return check_workspace_size(what, workspace_bytes, wb);
 }
 
 // The launches both passes are made of
@@ -671,25 +660,23 @@ struct XfmrTrainCtx {
     unsigned ew_grid(long long n) const { return (unsigned)std::min<long long>((n / 4 + 255) / 256, 4096); }
     // one launch of one layer over B sequences of T rows (K = 3: the sequences' own ends) or, seq = false, over the B T rows as one
     int conv(const ConvLayer& L, const float* xs, const float* res, float* y, float* ys, bool seq = true) const {
-        const ConvLayer* ls[1] = {&L};
-        ConvIO io[1];
-        io[0] = ConvIO();
-        io[0].xs = reinterpret_cast<const char*>(xs);
-        io[0].res = res;
-        io[0].y = y;
-        io[0].ys = reinterpret_cast<char*>(ys);
+        ConvIO io{};
+        io.xs = reinterpret_cast<const char*>(xs);
+        io.res = res;
+        io.y = y;
+        io.ys = reinterpret_cast<char*>(ys);
         const Ragged rg;
-        if (!x3()) return seq && !packed() ? launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream) : launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream);
+        if (!x3()) return seq && !packed() ? launch_conv1(h, L, B, T, io, 0.f, rg, stream) : launch_conv1(h, L, 1, M, io, 0.f, rg, stream);
         // bf16x3: the operand as split rows, the layer's bf16 twin in the engine's bf16x3 kernels.  Their activated copy is split rows, so a
         // ReLU'd fp32 copy (linear1's hidden rows) is the fp32 output ReLU'd in place.
         if (!L.d_w16 || !ws->split || (y && ys)) return fail(HIFICAR_E_INVALID, "internal: bf16x3 training launch of %s", L.name.c_str());
         int rc;
         if ((rc = split_rows(xs, L.cin_pad)) != HIFICAR_OK) return rc;
-        io[0].xs = ws->split;
-        io[0].ys = nullptr;
-        if (ys) io[0].y = ys;
+        io.xs = ws->split;
+        io.ys = nullptr;
+        if (ys) io.y = ys;
         h->precision = HIFICAR_PREC_BF16X3;  // (part of the plan key: these launches' plans are their own)
-        rc = seq && !packed() ? launch_conv(h, ls, 1, B, T, io, 0.f, rg, stream) : launch_conv(h, ls, 1, 1, M, io, 0.f, rg, stream);
+        rc = seq && !packed() ? launch_conv1(h, L, B, T, io, 0.f, rg, stream) : launch_conv1(h, L, 1, M, io, 0.f, rg, stream);
         h->precision = HIFICAR_PREC_F32;
         if (rc != HIFICAR_OK || !ys) return rc;
         return gate(ys, ys, ys, (long long)M * L.cout_pad, -1);
@@ -900,20 +887,19 @@ static int xfmr_forward_train_impl(hificar_xfmr* g, const char* what, const floa
     // a tap of a ragged forward: the rows of padded frames are zeros (a GEMM's output there is finite, not zero); of a packed forward: the
     // rows go back to the padded (B, T, width) layout, zeros on padded frames
     auto tap = [&](const std::string& name, const float* rows, int width) -> int {
-        auto it = g->taps.find(name);
-        if (it == g->taps.end()) return HIFICAR_OK;
+        float* dst;
+        const int rc2 = g->taps.find(name, (size_t)(Mp ? B * T : M) * width, &dst);
+        if (rc2 != HIFICAR_OK || !dst) return rc2;
         if (Mp) {
-            const size_t floats = (size_t)B * T * width;
-            if (it->second.cap < floats) return fail(HIFICAR_E_INVALID, "debug tap '%s' needs %zu floats, buffer has %zu", name.c_str(), floats, it->second.cap);
             hipLaunchKernelGGL(xfmr_unpack_rows_kernel, dim3((unsigned)std::min<long long>(((long long)T * (width / 4) + 255) / 256, 64), (unsigned)B), dim3(256),
-                               0, stream, rows, it->second.dst, width, tp.lens, tp.row0, T);
+                               0, stream, rows, dst, width, tp.lens, tp.row0, T);
             HIP_TRY(hipGetLastError());
             return HIFICAR_OK;
         }
-        int rc2 = xfmr_emit_tap(g, name, rows, (size_t)M * width, stream);
-        if (rc2 != HIFICAR_OK || !lengths) return rc2;
+        HIP_TRY(hipMemcpyAsync(dst, rows, (size_t)M * width * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (!lengths) return HIFICAR_OK;
         hipLaunchKernelGGL(bigru_zero_pad_kernel, dim3((unsigned)std::min<long long>(((long long)T * (width / 4) + 255) / 256, 8), (unsigned)B), dim3(256), 0,
-                           stream, it->second.dst, width, tp.lens, T);
+                           stream, dst, width, tp.lens, T);
         HIP_TRY(hipGetLastError());
         return HIFICAR_OK;
     };
