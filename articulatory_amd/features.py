@@ -21,15 +21,18 @@ import numpy as np
 import torch
 
 from . import _native
+from ._owner import NativeOwner, current_stream, scratch
 from .models import _feature_model
 from .utils.mel import mel_filterbank
 
 
-class _SpeechFeature(torch.nn.Module):
+class _SpeechFeature(NativeOwner, torch.nn.Module):
     """What ``MFCC`` and ``LogMel`` share: the native handle (made on first use, never shared by copies or pickles), the grow-only workspace
     and the call."""
 
     _NAME = None
+    _DESTROY = "hificar_feat_destroy"
+    _NATIVE = {"_handle": None, "_handle_dev": None, "_workspace_buf": None}
 
     def _init_native(self, cfg, melmat, channels):
         if cfg.fft_size < 32 or cfg.fft_size % 32:
@@ -41,7 +44,7 @@ class _SpeechFeature(torch.nn.Module):
         self._cfg = cfg
         self.melmat = np.ascontiguousarray(melmat, dtype=np.float32)
         self.channels = channels
-        self._lib = self._handle = self._handle_dev = self._workspace_buf = None
+        self._reset_native()
 
     @property
     def fft_size(self):
@@ -72,24 +75,6 @@ class _SpeechFeature(torch.nn.Module):
         if self._handle is None:
             raise RuntimeError(f"{self._NAME}.engine: no native handle yet; run a forward first")
         return ctypes.c_void_p(self._lib.hificar_feat_engine(self._handle))
-
-    def _invalidate(self):
-        handle, lib = self.__dict__.get("_handle"), self.__dict__.get("_lib")
-        self.__dict__["_handle"] = None
-        self.__dict__["_workspace_buf"] = None
-        if handle is not None and lib is not None:
-            lib.hificar_feat_destroy(handle)
-
-    def __del__(self):
-        try:
-            self._invalidate()
-        except Exception:
-            pass
-
-    def __getstate__(self):  # copies and pickles never share a native handle
-        state = self.__dict__.copy()
-        state["_handle"] = state["_lib"] = state["_handle_dev"] = state["_workspace_buf"] = None
-        return state
 
     def forward(self, wav, lengths=None):
         """wav: (B, L) or (L,) float tensor on the device; lengths: B sample counts in 0 < l <= L, or None (every utterance has L).
@@ -130,17 +115,11 @@ class _SpeechFeature(torch.nn.Module):
             n = int(lib.hificar_feat_workspace_bytes(handle, B, L))
             if n == 0:
                 raise RuntimeError(f"{name}: B={B}, L={L} out of range (B frames n_fft < 2^31, B <= 65535)")
-            ws = self._workspace_buf
-            if ws is None or ws.device != y.device or ws.numel() < n + 256:
-                # work already enqueued on the old buffer keeps it alive through the caching allocator's stream ordering
-                ws = torch.empty(int((n + 256) * 1.25) if ws is not None else n + 256, dtype=torch.uint8, device=y.device)
-                self._workspace_buf = ws
-            off = (-ws.data_ptr()) % 256
+            ws_ptr, ws_bytes = scratch(self, "_workspace_buf", n, y.device)
             out = torch.empty((B, self.channels, T), dtype=torch.float32, device=y.device)
             frames = torch.empty((B,), dtype=torch.int32, device=y.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            rc = lib.hificar_feat_forward(handle, y.data_ptr(), lens[0], lens[1], out.data_ptr(), frames.data_ptr(), B, L, ws.data_ptr() + off,
-                                          ws.numel() - off, stream)
+            rc = lib.hificar_feat_forward(handle, y.data_ptr(), lens[0], lens[1], out.data_ptr(), frames.data_ptr(), B, L, ws_ptr, ws_bytes,
+                                          current_stream())
         _native.check(rc, "hificar_feat_forward")
         del keep
         return out, frames
@@ -414,10 +393,9 @@ class HuBERT(_feature_model.NativeFeatureModel):
             n = int(self._fn("_workspace_bytes")(handle, B, L))
             if n == 0:
                 raise RuntimeError(f"{name}: B={B}, L={L} out of range (B <= 65535, B frames max(3 hidden, intermediate) < 2^31)")
-            ws_ptr, ws_bytes = self._scratch("_workspace_buf", n)
+            ws_ptr, ws_bytes = scratch(self, "_workspace_buf", n, self._device)
             out = torch.empty((B, self.config["hidden_size"], T), dtype=torch.float32, device=y.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self._call("_forward", handle, y.data_ptr(), lens[0], lens[1], out.data_ptr(), B, L, layer, ws_ptr, ws_bytes, stream)
+            self._call("_forward", handle, y.data_ptr(), lens[0], lens[1], out.data_ptr(), B, L, layer, ws_ptr, ws_bytes, current_stream())
         del keep
         return out, frames
 
@@ -510,7 +488,7 @@ def ssl_encoder_class(directory):
     return WavLM if model_type == "wavlm" else HuBERT
 
 
-class LinearHead(torch.nn.Module):
+class LinearHead(NativeOwner, torch.nn.Module):
     """``y = coef x + intercept`` over device features: (B, H, T) -> (B, out, T), the fitted linear regression the reference's
     ``egs/ema/voc1/local/linear_inference.py`` applies to ``hidden_states[9]`` of ``wavlm_large``.  It runs in ``libhificar.so`` as the one-tap
     GEMM every ``Linear`` of this package is (``hificar_linear_*`` of include/hificar.h; exact fp32 only — the regression is tiny): every
@@ -522,6 +500,10 @@ class LinearHead(torch.nn.Module):
         ema = head(feats, frames)                                       # (B, out, Tmax)
 
     ``coef``: (out, H), ``intercept``: (out,) — sklearn's ``coef_`` / ``intercept_`` (a 1-D ``coef_`` is one output)."""
+
+    _DESTROY = "hificar_linear_destroy"
+    _ENGINE = "hificar_linear_engine"
+    _NATIVE = {"_handle": None, "_handle_key": None, "_workspace_buf": None}
 
     def __init__(self, coef, intercept):
         super().__init__()
@@ -535,7 +517,7 @@ class LinearHead(torch.nn.Module):
                              f"1 .. {_native.LINEAR_MAX_OUT} out)")
         self.register_buffer("coef", coef.contiguous().clone())
         self.register_buffer("intercept", intercept.contiguous().clone())
-        self._lib = self._handle = self._handle_key = self._workspace_buf = None
+        self._reset_native()
 
     in_features = property(lambda self: self.coef.shape[1])
     out_features = property(lambda self: self.coef.shape[0])
@@ -563,23 +545,6 @@ class LinearHead(torch.nn.Module):
         coef = coef.reshape(1, -1) if coef.ndim == 1 else coef
         return cls(coef, np.broadcast_to(np.asarray(reg.intercept_, dtype=np.float64).reshape(-1), (coef.shape[0],)))
 
-    def _invalidate(self):
-        handle, lib = self.__dict__.get("_handle"), self.__dict__.get("_lib")
-        self.__dict__["_handle"] = self.__dict__["_handle_key"] = self.__dict__["_workspace_buf"] = None
-        if handle is not None and lib is not None:
-            lib.hificar_linear_destroy(handle)
-
-    def __del__(self):
-        try:
-            self._invalidate()
-        except Exception:
-            pass
-
-    def __getstate__(self):  # copies and pickles never share a native handle
-        state = self.__dict__.copy()
-        state["_handle"] = state["_lib"] = state["_handle_key"] = state["_workspace_buf"] = None
-        return state
-
     def _native_handle(self):
         key = (self.coef.device, self.coef.data_ptr(), self.coef._version, self.intercept.data_ptr(), self.intercept._version)
         if self._handle is not None and self._handle_key != key:
@@ -593,11 +558,6 @@ class LinearHead(torch.nn.Module):
                               "hificar_linear_create")
             self._handle, self._handle_key = handle, key
         return self._handle
-
-    def engine(self):
-        """The engine handle for ``hificar_profile_begin`` / ``hificar_profile_end``."""
-        handle = self._native_handle()
-        return ctypes.c_void_p(self._lib.hificar_linear_engine(handle))
 
     def forward(self, feats, lengths=None):
         """feats: (B, H, T) float tensor on the device; lengths: B frame counts in 0 .. T (a device int32 tensor — ``frames`` as ``WavLM``
@@ -626,16 +586,10 @@ class LinearHead(torch.nn.Module):
             n = int(lib.hificar_linear_workspace_bytes(handle, B, T))
             if n == 0:
                 raise RuntimeError(f"LinearHead: B={B}, T={T} out of range (B <= 65535, B T max(in, out) < 2^31)")
-            ws = self._workspace_buf
-            if ws is None or ws.device != x.device or ws.numel() < n + 256:
-                # work already enqueued on the old buffer keeps it alive through the caching allocator's stream ordering
-                ws = torch.empty(int((n + 256) * 1.25) if ws is not None else n + 256, dtype=torch.uint8, device=x.device)
-                self._workspace_buf = ws
-            off = (-ws.data_ptr()) % 256
+            ws_ptr, ws_bytes = scratch(self, "_workspace_buf", n, x.device)
             out = torch.empty((B, self.out_features, T), dtype=torch.float32, device=x.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            rc = lib.hificar_linear_forward(handle, x.data_ptr(), None if lens is None else lens.data_ptr(), out.data_ptr(), B, T, ws.data_ptr() + off,
-                                            ws.numel() - off, stream)
+            rc = lib.hificar_linear_forward(handle, x.data_ptr(), None if lens is None else lens.data_ptr(), out.data_ptr(), B, T, ws_ptr, ws_bytes,
+                                            current_stream())
         _native.check(rc, "hificar_linear_forward")
         del lens
         return out

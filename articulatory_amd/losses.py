@@ -80,6 +80,7 @@ import ctypes  # noqa: E402
 import numpy as np  # noqa: E402
 
 from . import _native  # noqa: E402
+from ._owner import NativeOwner, aligned, current_stream  # noqa: E402
 from .utils.mel import mel_filterbank  # noqa: E402
 
 
@@ -93,14 +94,12 @@ class _MelLossFunction(torch.autograd.Function):
         yr = y.detach().to(torch.float32).contiguous()
         need = y_hat.requires_grad
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             wsb = int(lib.hificar_mel_workspace_bytes(handle, B, T))
-            ws = torch.empty(wsb // 4 + 64, dtype=torch.float32, device=dev)
-            woff = ((-ws.data_ptr()) % 256) // 4
+            ws, ws_ptr = aligned(wsb, dev, torch.float32)
             value = torch.empty(1, dtype=torch.float32, device=dev)
             dy = torch.empty_like(yh) if need else None
             rc = lib.hificar_mel_loss(handle, yh.data_ptr(), yr.data_ptr(), B, T, value.data_ptr(), dy.data_ptr() if need else None,
-                                      ws.data_ptr() + 4 * woff, wsb, stream)
+                                      ws_ptr, wsb, current_stream())
         _native.check(rc, "hificar_mel_loss")
         ctx.dy = dy
         ctx.shape = y_hat.shape
@@ -113,7 +112,23 @@ class _MelLossFunction(torch.autograd.Function):
         return None, (dy * g).view(ctx.shape) if dy is not None else None, None
 
 
-class MelSpectrogramLoss(torch.nn.Module):
+class _MelOwner(NativeOwner, torch.nn.Module):
+    """What the loss modules share: one ``hificar_mel_*`` handle over ``self._cfg`` and ``self.melmat``, made on first use."""
+
+    _DESTROY = "hificar_mel_destroy"
+
+    def _native_handle(self, dev):
+        if self._handle is None:
+            self._lib = _native.load_library()
+            handle = ctypes.c_void_p()
+            with torch.cuda.device(dev):
+                _native.check(self._lib.hificar_mel_create(ctypes.byref(self._cfg), self.melmat.ctypes.data_as(ctypes.c_void_p), ctypes.byref(handle)),
+                              "hificar_mel_create")
+            self._handle = handle
+        return self._handle
+
+
+class MelSpectrogramLoss(_MelOwner):
     """Mel-spectrogram loss, constructor arguments as the reference's (mel_loss.py:117-132).  MI355X-native (no CPU fallback)."""
 
     def __init__(self, fs=22050, fft_size=1024, hop_size=256, win_length=None, window="hann", num_mels=80, fmin=80, fmax=7600, center=True,
@@ -134,26 +149,7 @@ class MelSpectrogramLoss(torch.nn.Module):
             raise ValueError(f"melmat must be ({num_mels}, {fft_size // 2 + 1}), got {self.melmat.shape}")
         self._cfg = _native.HificarMelConfig(fft_size, hop_size, fft_size if win_length is None else win_length, num_mels, eps,
                                              0 if log_base is None else int(log_base), 0)
-        self._lib = self._handle = None
-
-    def _native_handle(self, dev):
-        if self._handle is None:
-            self._lib = _native.load_library()
-            handle = ctypes.c_void_p()
-            with torch.cuda.device(dev):
-                _native.check(self._lib.hificar_mel_create(ctypes.byref(self._cfg), self.melmat.ctypes.data_as(ctypes.c_void_p), ctypes.byref(handle)),
-                              "hificar_mel_create")
-            self._handle = handle
-        return self._handle
-
-    def __del__(self):
-        handle, lib = self.__dict__.get("_handle"), self.__dict__.get("_lib")
-        if handle is not None and lib is not None:
-            self.__dict__["_handle"] = None
-            try:
-                lib.hificar_mel_destroy(handle)
-            except Exception:
-                pass
+        self._reset_native()
 
     def forward(self, y_hat, y):
         """y_hat, y: (B, 1, T) -> scalar (mel_loss.py:152-166)."""
@@ -177,14 +173,12 @@ class _StftLossFunction(torch.autograd.Function):
         yh = y_hat.detach().to(torch.float32).contiguous()
         yr = y.detach().to(torch.float32).contiguous()
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             wsb = int(lib.hificar_mel_workspace_bytes(handle, B, T))
-            ws = torch.empty(wsb // 4 + 64, dtype=torch.float32, device=dev)
-            woff = ((-ws.data_ptr()) % 256) // 4
+            ws, ws_ptr = aligned(wsb, dev, torch.float32)
             values = torch.empty(2, dtype=torch.float32, device=dev)
-            rc = lib.hificar_stft_loss_forward(handle, yh.data_ptr(), yr.data_ptr(), B, T, values.data_ptr(), ws.data_ptr() + 4 * woff, wsb, stream)
+            rc = lib.hificar_stft_loss_forward(handle, yh.data_ptr(), yr.data_ptr(), B, T, values.data_ptr(), ws_ptr, wsb, current_stream())
         _native.check(rc, "hificar_stft_loss_forward")
-        ctx.module, ctx.ws, ctx.woff, ctx.wsb, ctx.BT = module, ws, woff, wsb, (B, T)
+        ctx.module, ctx.ws, ctx.ws_ptr, ctx.wsb, ctx.BT = module, ws, ws_ptr, wsb, (B, T)  # (the backward reads what the forward left in ws)
         return values[0], values[1]
 
     @staticmethod
@@ -193,16 +187,15 @@ class _StftLossFunction(torch.autograd.Function):
         B, T = ctx.BT
         dev = ctx.ws.device
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             gw = torch.stack([g_sc, g_mag]).to(torch.float32).contiguous()
             dy = torch.empty((B, T), dtype=torch.float32, device=dev)
-            rc = module._lib.hificar_stft_loss_backward(module._handle, B, T, gw.data_ptr(), dy.data_ptr(), ctx.ws.data_ptr() + 4 * ctx.woff, ctx.wsb, stream)
+            rc = module._lib.hificar_stft_loss_backward(module._handle, B, T, gw.data_ptr(), dy.data_ptr(), ctx.ws_ptr, ctx.wsb, current_stream())
         _native.check(rc, "hificar_stft_loss_backward")
         ctx.ws = None
         return None, dy, None
 
 
-class STFTLoss(torch.nn.Module):
+class STFTLoss(_MelOwner):
     """One resolution (stft_loss.py:87-125): (spectral convergence, log STFT magnitude).  MI355X-native."""
 
     def __init__(self, fft_size=1024, shift_size=120, win_length=600, window="hann_window"):
@@ -210,10 +203,8 @@ class STFTLoss(torch.nn.Module):
         if window != "hann_window":
             raise NotImplementedError("STFTLoss: only window='hann_window' is built")
         self._cfg = _native.HificarMelConfig(fft_size, shift_size, win_length, 0, 1e-7, 0, 1)  # clamp(re^2 + im^2, 1e-7), stft_loss.py:40
-        self._lib = self._handle = None
+        self._reset_native()
 
-    _native_handle = MelSpectrogramLoss._native_handle
-    __del__ = MelSpectrogramLoss.__del__
     melmat = np.zeros((1, 1), np.float32)  # (unused in this mode)
 
     def forward(self, x, y):

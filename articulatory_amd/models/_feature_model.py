@@ -1,8 +1,8 @@
 """``NativeFeatureModel`` — what ``BiGRU`` and ``Transformer`` share: the feature-to-feature models whose modules only HOLD parameters while
 the arithmetic runs in ``libhificar.so`` behind one native handle (``hificar_bigru_*`` / ``hificar_xfmr_*`` of include/hificar.h).
 
-Here, once: the handle's state and lifecycle (creation from the host copies, the device hand-over ``*_set_parameters_device`` once a handle
-has trained, invalidation, copies and pickles), the grow-only scratch buffers, the eval-mode input checks and the whole ``forward_lowrate``,
+Here, once: the handle's state over ``_owner.NativeOwner``'s lifecycle (creation from the host copies, the device hand-over
+``*_set_parameters_device`` once a handle has trained, when it is invalidated), the eval-mode input checks and the whole ``forward_lowrate``,
 the gradient layout, and the parts of the training step that do not depend on the model: the shape refusals, the dropout offset, the
 autograd node's bookkeeping and the running-statistics update.  A model supplies ``_PREFIX`` / ``_NAME``, its parameter holders, ``_device``,
 ``_make_config``, ``_batch_norms``, ``_stats_shape``, its training workspace and the entry points its training step calls.
@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from .._owner import ABSENT, NativeOwner, create_handle, current_stream, scratch
 
 
 def register_stats(module, stats):
@@ -78,7 +79,7 @@ def _tape_backward(ctx, dout, launch, skip=()):
     dout = dout.to(torch.float32).contiguous()
     dx = torch.empty((B, module._params["in_channels"], T), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = current_stream()
         grads = torch.empty(int(module._fn("_grad_floats")(handle)), dtype=torch.float32, device=dev)
         tail = (ctx.tape.data_ptr() + ctx.toff, ctx.tape.numel() - ctx.toff, grads.data_ptr(), dx.data_ptr() if dx is not None else None)
         launch(handle, dout.data_ptr(), B, T, tail, stream)
@@ -89,35 +90,32 @@ def _tape_backward(ctx, dout, launch, skip=()):
     return (None, dx, None, None, None, None, *gw)
 
 
-class NativeFeatureModel(torch.nn.Module):
+class NativeFeatureModel(NativeOwner, torch.nn.Module):
     """Base of ``BiGRU`` and ``Transformer``; see the module's docstring."""
 
     _PREFIX = None     # the C entry points' prefix: "hificar_bigru" / "hificar_xfmr"
     _NAME = None       # the class name in messages
-    _TRANSIENT = {}    # the model's own fields that only hold during a training forward, with their idle values
+    _DESTROY = property(lambda self: self._PREFIX + "_destroy")
+    _ENGINE = property(lambda self: self._PREFIX + "_engine")
+    # _on_device: the handle's weights are refreshed from device tensors (set once a training forward ran on it); _dirty: an optimizer
+    # stepped since the last hand-over (fused optimizers do not bump Parameter._version)
+    _NATIVE = {"_handle": None, "_workspace_buf": None, "_train_ws_buf": None, "_sig": None, "_on_device": False, "_dirty": False,
+               "_grad_info": ABSENT}
+    # _lens: the lengths of the ragged training forward under way (forward_padded); a model adds its own fields that only hold during a
+    # training forward, with their idle values
+    _PROCESS = {"_lib": None, "_lens": None}
+    _WATCHED = True
     _LOWRATE_TRAINING = ""  # how forward_lowrate's refusal in train() mode ends
     _LOWRATE_RANGE = ""     # what _workspace's refusal of a low-rate shape adds
 
     def _init_native(self):
         """The handle's state.  Called by the model's ``__init__`` once its parameters exist: the dropout seed is drawn from torch's
         generator behind their initialisation."""
-        self._handle = None
-        self._lib = None
-        self._workspace_buf = None
-        self._sig = None
-        self._train_ws_buf = None
-        self._on_device = False  # the handle's weights are refreshed from device tensors (set once a training forward ran on it)
-        self._dirty = False      # an optimizer stepped since the last hand-over (fused optimizers do not bump Parameter._version)
+        self._reset_native()
         self._steps_seen = 0     # optimizer steps noticed so far
         self._calls = 0          # training forwards so far: the dropout generator's offset
-        self._lens = None        # the lengths of the ragged training forward under way (forward_padded)
-        for k, v in self._TRANSIENT.items():
-            setattr(self, k, v)
         # drawn from torch's generator (after the parameters): torch.manual_seed makes a training run repeatable
         self._dropout_seed = int(torch.randint(0, 2 ** 62, (1,), device="cpu").item())  # (the CPU generator, also under torch.device("meta"))
-        from ..utils.optim_hook import watch
-
-        watch(self)  # fused optimizers do not bump Parameter._version: every optimizer.step() over these parameters marks them stale
 
     def _fn(self, suffix):
         return getattr(self._lib, self._PREFIX + suffix)
@@ -163,38 +161,6 @@ class NativeFeatureModel(torch.nn.Module):
             ts += [bn.running_mean, bn.running_var]
         return tuple((t.data_ptr(), t._version) for t in ts)
 
-    def _invalidate(self):
-        h = self.__dict__.get("_handle")
-        if h is not None and self._lib is not None:
-            self._fn("_destroy")(h)
-        self._handle = None
-        self._workspace_buf = None
-        self._train_ws_buf = None
-        self._sig = None
-        self._on_device = False
-        self._dirty = False
-
-    def __del__(self):
-        try:
-            self._invalidate()
-        except Exception:
-            pass
-
-    def __getstate__(self):  # copies and pickles never share a native handle, nor a training forward under way
-        state = self.__dict__.copy()
-        for k in ("_handle", "_lib", "_workspace_buf", "_sig", "_train_ws_buf", "_lens"):
-            state[k] = None
-        state.update(self._TRANSIENT)
-        state["_on_device"] = state["_dirty"] = False
-        state.pop("_grad_info", None)
-        return state
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        from ..utils.optim_hook import watch
-
-        watch(self)  # a copy trains with its own optimizer
-
     def load_state_dict(self, state_dict, strict=True, **kw):
         out = super().load_state_dict(state_dict, strict=strict, **kw)
         self._invalidate()
@@ -221,8 +187,7 @@ class NativeFeatureModel(torch.nn.Module):
         arr = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
         ptrs = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
         with torch.cuda.device(self._device()):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self._call("_set_parameters_device", self._handle, arr, ptrs, len(held), stream)
+            self._call("_set_parameters_device", self._handle, arr, ptrs, len(held), current_stream())
         self._on_device = True
         self._dirty = False
         self._sig = self._signature()
@@ -248,34 +213,15 @@ class NativeFeatureModel(torch.nn.Module):
             raise RuntimeError("%s: parameters are on %s; the forward only exists as HIP kernels (move the model to a MI355X with "
                                ".to('cuda')). There is no CPU fallback." % (self._NAME, dev))
         self._lib = _native.load_library()
-        handle = ctypes.c_void_p()
         with torch.cuda.device(dev):
             cfg = self._make_config()
-            self._call("_create", ctypes.byref(cfg), ctypes.byref(handle))
-            try:
-                for name, t in self.native_state().items():
-                    shape = (ctypes.c_int64 * t.dim())(*t.shape)
-                    self._call("_set_weight", handle, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim())
-                self._finalize_handle(handle)
-            except Exception:
-                self._fn("_destroy")(handle)
-                raise
+            handle = create_handle(self._lib, self._PREFIX, lambda h: self._call("_create", ctypes.byref(cfg), ctypes.byref(h)),
+                                   self.native_state(), self._finalize_handle)
         self._handle = handle
         self._sig = self._signature()
         if train:
             self._send_parameters()
         return handle
-
-    def _scratch(self, attr, n):
-        """(pointer, bytes) of the grow-only scratch buffer kept in ``self.<attr>``: at least ``n`` bytes from a 256-byte boundary."""
-        n += 256
-        ws = getattr(self, attr)
-        if ws is None or ws.numel() < n:
-            # work already enqueued on the old buffer keeps it alive through the caching allocator's stream ordering
-            ws = torch.empty(int(n * 1.25) if ws is not None else n, dtype=torch.uint8, device=self._device())
-            setattr(self, attr, ws)
-        off = (-ws.data_ptr()) % 256
-        return ws.data_ptr() + off, ws.numel() - off
 
     def _workspace(self, B, T, factor=None):
         """One grow-only scratch buffer per model for the eval forward (hificar_*_workspace_bytes; ``factor``: T low-rate frames,
@@ -286,12 +232,7 @@ class NativeFeatureModel(torch.nn.Module):
             n = self._fn("_workspace_bytes_lowrate")(self._handle, B, T, factor)
             if n == 0:
                 raise RuntimeError(f"{self._NAME}.forward_lowrate: B={B}, Tl={T}, interp_factor={factor} out of range{self._LOWRATE_RANGE}")
-        return self._scratch("_workspace_buf", n)
-
-    def engine(self):
-        """The engine handle for ``hificar_profile_begin`` / ``hificar_profile_end`` (per-kernel device times; tools/*_bench.py)."""
-        handle = self._native_handle()  # first: it is what loads self._lib
-        return ctypes.c_void_p(self._fn("_engine")(handle))
+        return scratch(self, "_workspace_buf", n, self._device)
 
     @staticmethod
     def _check_lengths(lengths, B, T, device):
@@ -329,8 +270,7 @@ class NativeFeatureModel(torch.nn.Module):
         out = torch.empty((B, self._params["out_channels"], (factor or 1) * T), dtype=torch.float32, device=c.device)
         with torch.cuda.device(c.device):
             ws_ptr, ws_bytes = self._workspace(B, T, factor=factor)
-            stream = torch.cuda.current_stream().cuda_stream
-            self._call("_" + what, handle, c.data_ptr(), lens[0], lens[1], out.data_ptr(), B, T, *low, ws_ptr, ws_bytes, ctypes.c_void_p(stream))
+            self._call("_" + what, handle, c.data_ptr(), lens[0], lens[1], out.data_ptr(), B, T, *low, ws_ptr, ws_bytes, current_stream())
         return out
 
     def forward_lowrate(self, x, lengths=None, interp_factor=1, zscore=False):
@@ -397,7 +337,7 @@ class NativeFeatureModel(torch.nn.Module):
         finally:
             self._lens = None
             for k in under_way:
-                setattr(self, "_" + k, self._TRANSIENT["_" + k])
+                setattr(self, "_" + k, self._PROCESS["_" + k])
         with torch.no_grad():  # torch.nn.BatchNorm1d: momentum 0.1, the running variance takes the UNBIASED batch variance (n: the valid frames)
             per_bn = stats.view(-1, 2, stats.shape[-1])  # (number of batch norms, mean | biased variance, channels)
             for j, bn in enumerate(self._batch_norms()):

@@ -23,12 +23,12 @@ makes them; ``forward_padded(mels, lengths)`` trains on whole utterances of uneq
 masks: each sequence swept over its own frames, batch statistics, loss and gradients over the valid frames only).
 """
 
-import ctypes
 import math
 
 import torch
 
 from .. import _native
+from .._owner import aligned, current_stream, scratch
 from ._feature_model import NativeFeatureModel, _grad_layout, _tape_backward, _tape_forward  # noqa: F401  (_grad_layout: imported from here too)
 
 FC1_DIM = 128  # pytorch_models.py:32-33
@@ -98,7 +98,7 @@ class BiGRU(NativeFeatureModel):
 
     _PREFIX = "hificar_bigru"
     _NAME = "BiGRU"
-    _TRANSIENT = {"_low": None}  # (interp_factor, zscore) of the low-rate training forward under way (forward_lowrate_train)
+    _PROCESS = {**NativeFeatureModel._PROCESS, "_low": None}  # (interp_factor, zscore) of the low-rate training forward under way
     _LOWRATE_TRAINING = "to train on low-rate inputs call forward_lowrate_train"
 
     def __init__(self, in_channels=80, hidden_size=256, dropout=0.3, out_channels=1,
@@ -156,7 +156,7 @@ class BiGRU(NativeFeatureModel):
             n = self._lib.hificar_bigru_train_workspace_bytes_lowrate(self._handle, B, T, factor)
             if n == 0:
                 raise RuntimeError(f"BiGRU.forward_lowrate_train: B={B}, Tl={T}, interp_factor={factor} out of range")
-        return self._scratch("_train_ws_buf", n)
+        return scratch(self, "_train_ws_buf", n, self._device)
 
     def _run_forward_train(self, x, p, seed, offset, keep_tape, lens=None, low=None):
         """hificar_bigru_forward_train (lens = (host, device) int32 lengths: hificar_bigru_forward_train_ragged; low = (interp_factor, zscore):
@@ -167,12 +167,12 @@ class BiGRU(NativeFeatureModel):
         f = 1 if low is None else low[0]
         dev = x.device
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = current_stream()
             tape, toff = None, 0
             if keep_tape:
                 n = lib.hificar_bigru_tape_bytes(handle, B, T) if low is None else lib.hificar_bigru_tape_bytes_lowrate(handle, B, T, f)
-                tape = torch.empty(n + 256, dtype=torch.uint8, device=dev)
-                toff = (-tape.data_ptr()) % 256
+                tape, ptr = aligned(n, dev)
+                toff = ptr - tape.data_ptr()
             out = torch.empty((B, self._params["out_channels"], f * T), dtype=torch.float32, device=dev)
             stats = torch.empty(self._stats_shape(), dtype=torch.float32, device=dev)
             ws_ptr, ws_bytes = self._train_workspace(B, T, factor=None if low is None else f)

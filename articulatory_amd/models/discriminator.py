@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from .. import _native
+from .._owner import ABSENT, NativeOwner, aligned, current_stream
 from ..utils.buckets import raw_grad_views
 from ..utils.synth import disc_params, period_disc_layers, scale_disc_layers
 from .hifigan import _ConvParams, _send_parameters
@@ -52,11 +53,10 @@ class _DiscFunction(torch.autograd.Function):
         dev = x.device
         x = x.detach().to(torch.float32).contiguous()
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = current_stream()
             held = _send_parameters(module, "hificar_disc_set_parameters_device", names, params, stream)
             nbytes = int(lib.hificar_disc_tape_bytes(handle, B, T))
-            tape = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device=dev)
-            toff = ((-tape.data_ptr()) % 256) // 4
+            tape, toff = _aligned(nbytes // 4, dev)
             rc = lib.hificar_disc_forward(handle, x.data_ptr(), B, T, tape.data_ptr() + 4 * toff, nbytes, stream)
         _native.check(rc, "hificar_disc_forward")
         outs = []
@@ -81,12 +81,11 @@ class _DiscFunction(torch.autograd.Function):
         keep = [None if g is None else g.to(torch.float32).contiguous() for g in douts]
         ptrs = (ctypes.c_void_p * len(keep))(*[None if g is None else g.data_ptr() for g in keep])
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = current_stream()
             grads = torch.zeros(int(lib.hificar_disc_grad_floats(handle)), dtype=torch.float32, device=dev) if need_p else None
             dx = torch.empty((B, 1, T), dtype=torch.float32, device=dev) if need_x else None
             wsb = int(lib.hificar_disc_backward_workspace_bytes(handle, B, T))
-            ws = torch.empty(wsb // 4 + 64, dtype=torch.float32, device=dev)
-            woff = ((-ws.data_ptr()) % 256) // 4
+            ws, woff = _aligned(wsb // 4, dev)
             rc = lib.hificar_disc_backward(handle, ptrs, B, T, ctx.tape.data_ptr() + 4 * ctx.toff, ctx.nbytes,
                                            grads.data_ptr() if need_p else None, dx.data_ptr() if need_x else None,
                                            ws.data_ptr() + 4 * woff, wsb, stream)
@@ -110,8 +109,8 @@ class _DiscFunction(torch.autograd.Function):
 
 def _aligned(nfloats, dev):
     """(tensor, float offset of its first 256-byte aligned element)."""
-    t = torch.empty(nfloats + 64, dtype=torch.float32, device=dev)
-    return t, ((-t.data_ptr()) % 256) // 4
+    t, ptr = aligned(4 * nfloats, dev, torch.float32)
+    return t, (ptr - t.data_ptr()) // 4
 
 
 class _Pass:
@@ -152,7 +151,7 @@ class _GeneratorLossFunction(torch.autograd.Function):
         B, _, T = y_fake.shape
         dev = y_fake.device
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = current_stream()
             _send_parameters(module, "hificar_disc_set_parameters_device", names, params, stream)
             fake = _Pass(module, y_fake, stream)
             real = module._real_pass(y_real, params, stream) if y_real is not None else None
@@ -176,7 +175,7 @@ class _GeneratorLossFunction(torch.autograd.Function):
         if not ctx.needs_input_grad[1]:
             return (None,) * (5 + len(ctx.needs_input_grad) - 5)
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = current_stream()
             dx = torch.empty((B, 1, T), dtype=torch.float32, device=dev)
             wsb = int(lib.hificar_disc_backward_workspace_bytes(handle, B, T))
             ws, woff = _aligned(wsb // 4, dev)
@@ -204,7 +203,7 @@ class _DiscriminatorLossFunction(torch.autograd.Function):
         B, _, T = y_fake.shape
         dev = y_fake.device
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = current_stream()
             held = _send_parameters(module, "hificar_disc_set_parameters_device", names, params, stream)
             passes, douts, vals = [], [], []
             for mode, y in ((1, y_fake), (2, y_real)):
@@ -233,7 +232,7 @@ class _DiscriminatorLossFunction(torch.autograd.Function):
         if any(t._version != v for t, v in zip(ctx.params, ctx.versions)):
             raise RuntimeError("a discriminator parameter was modified in place between forward and backward")
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = current_stream()
             wsb = int(lib.hificar_disc_backward_workspace_bytes(handle, B, T))
             ws, woff = _aligned(wsb // 4, dev)
             nfold = int(lib.hificar_disc_grad_floats(handle))
@@ -339,7 +338,7 @@ def _slope(sub_params):
     return float(sub_params.get("nonlinear_activation_params", {"negative_slope": 0.1}).get("negative_slope", 0.01))
 
 
-class HiFiGANMultiScaleMultiPeriodDiscriminator(torch.nn.Module):
+class HiFiGANMultiScaleMultiPeriodDiscriminator(NativeOwner, torch.nn.Module):
     """HiFi-GAN multi-scale + multi-period discriminator (MI355X-native forward and backward).  Constructor arguments as the
     reference's (hifigan.py:744-781)."""
 
@@ -408,12 +407,7 @@ class HiFiGANMultiScaleMultiPeriodDiscriminator(torch.nn.Module):
             subs = getattr(self, layout).discriminators
             del self.msd, self.mpd
             self.discriminators = subs
-        self._lib = self._handle = None
-        self._grad_sync = None
-        self._info_cache = {}
-        from ..utils.optim_hook import watch
-
-        watch(self)  # fused optimizers do not bump Parameter._version: every optimizer.step() over these parameters calls invalidate_parameters()
+        self._reset_native()
 
     # ------------------------------------------------------------------ native handle
     def _config(self):
@@ -440,23 +434,11 @@ class HiFiGANMultiScaleMultiPeriodDiscriminator(torch.nn.Module):
     # lists / side stream and the gradient-sync wiring stay behind; the copy registers with the optimizer post-step hook itself
     # per-process state a copy must not carry: native handles, ctypes arrays (``_raw_cnames``: c_char_p arrays cannot be pickled), the held copy of the
     # parameters last sent to the device (``_sent_held``: a second 70 M floats), cached passes / streams / events
-    _EPHEMERAL = ("_handle", "_lib", "_grad_sync", "_info_cache", "_sent_sig", "_sent_held", "_raw_cnames", "_real_cache", "_early_real", "_gside_done",
-                  "_raw_cache", "_early_stream")
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        for k in self._EPHEMERAL:
-            state.pop(k, None)
-        return state
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        d = self.__dict__
-        d["_handle"] = d["_lib"] = d["_grad_sync"] = None
-        d["_info_cache"] = {}
-        from ..utils.optim_hook import watch
-
-        watch(self)
+    _DESTROY = "hificar_disc_destroy"
+    _NATIVE = {"_handle": None, "_info_cache": {}, "_sent_sig": ABSENT, "_sent_held": ABSENT, "_real_cache": ABSENT, "_early_real": ABSENT,
+               "_gside_done": ABSENT}
+    _PROCESS = {"_lib": None, "_grad_sync": None, "_raw_cnames": ABSENT, "_raw_cache": ABSENT, "_early_stream": ABSENT}
+    _WATCHED = True
 
     def _native_handle(self):
         if self._handle is None:
@@ -471,15 +453,6 @@ class HiFiGANMultiScaleMultiPeriodDiscriminator(torch.nn.Module):
                 _native.check(self._lib.hificar_disc_create(ctypes.byref(cfg), ctypes.byref(handle)), "hificar_disc_create")
             self._handle = handle
         return self._handle
-
-    def __del__(self):
-        handle, lib = self.__dict__.get("_handle"), self.__dict__.get("_lib")
-        if handle is not None and lib is not None:
-            self.__dict__["_handle"] = None  # (not setattr: torch's Module.__setattr__ may be half torn down at interpreter exit)
-            try:
-                lib.hificar_disc_destroy(handle)
-            except Exception:
-                pass
 
     def _output_infos(self, B, T):
         key = (B, T)

@@ -115,13 +115,7 @@ class GBlockGenerator(_NativeGenerator):
             self.apply_weight_norm()
         else:
             self.reset_parameters()
-        self._handle = None
-        self._workspaces = {}
-        self._lib = None
-        self._grad_sync = None
-        from ..utils.optim_hook import watch
-
-        watch(self)
+        self._reset_native()
 
     def _create_handle(self, lib, handle):
         cfg = _native.make_gblock_config(self._params, _native.PRECISIONS[self.precision])

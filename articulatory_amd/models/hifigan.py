@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from .._owner import ABSENT, NativeOwner, aligned, create_handle, current_stream, scratch
 from ..utils.buckets import raw_grad_views
 from ._feature_model import register_stats
 
@@ -161,10 +162,10 @@ class _GeneratorFunction(torch.autograd.Function):
         B, _, T = c.shape
         dev = c.device
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = current_stream()
             held = _send_parameters(module, "hificar_set_parameters_device", names, params, stream)
-            tape = torch.empty(lib.hificar_tape_bytes(handle, B, T) + 256, dtype=torch.uint8, device=dev)
-            toff = (-tape.data_ptr()) % 256
+            tape, tape_ptr = aligned(lib.hificar_tape_bytes(handle, B, T), dev)
+            toff = tape_ptr - tape.data_ptr()
             out = torch.empty((B, 1, T * module.hop), dtype=torch.float32, device=dev)
             ph_out = torch.empty((B, module._params["num_ph"], T), dtype=torch.float32, device=dev) if module.use_ph_loss else None
             ws_ptr, ws_bytes = module._workspace(B, T)
@@ -203,9 +204,8 @@ class _GeneratorFunction(torch.autograd.Function):
         dar = torch.empty((B, 1, p["ar_input"]), dtype=torch.float32, device=dev) if need_ar else None
         with torch.cuda.device(dev):
             grads = torch.zeros(int(lib.hificar_grad_floats(handle)), dtype=torch.float32, device=dev)
-            ws = torch.empty(lib.hificar_backward_workspace_bytes(handle, B, T) + 256, dtype=torch.uint8, device=dev)
-            woff = (-ws.data_ptr()) % 256
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            ws, ws_ptr = aligned(lib.hificar_backward_workspace_bytes(handle, B, T), dev)
+            stream = current_stream()
             raw = torch.zeros(int(lib.hificar_raw_grad_floats(handle)), dtype=torch.float32, device=dev)
             reducer = cb = None
             if module._grad_sync is not None:
@@ -228,7 +228,7 @@ class _GeneratorFunction(torch.autograd.Function):
                                                spk_id.data_ptr() if spk_id is not None else None, ph.data_ptr() if ph is not None else None,
                                                B, T, ctx.tape.data_ptr() + ctx.toff, ctx.tape.numel() - ctx.toff, grads.data_ptr(),
                                                dc.data_ptr() if dc is not None else None, dar.data_ptr() if dar is not None else None,
-                                               ws.data_ptr() + woff, ws.numel() - woff, stream)
+                                               ws_ptr, ws.numel() - (ws_ptr - ws.data_ptr()), stream)
             finally:
                 if cb is not None:
                     lib.hificar_set_bucket_callback(handle, _native.BUCKET_FN(), None)
@@ -257,7 +257,7 @@ class _NoGraph(torch.autograd.Function):
                            "(a graph whenever gradients are enabled), before the forward whose gradients you need.")
 
 
-class _NativeGenerator(torch.nn.Module):
+class _NativeGenerator(NativeOwner, torch.nn.Module):
     """What the generator classes of this package share: parameter plumbing (weight norm, folded state, the raw-parameter hand-over), the
     libhificar handle, workspaces, the inference / AR-synthesis / autograd entry points.  A subclass builds the parameter-holder modules with
     the reference's names in ``__init__``, fills ``self._params`` and implements ``_create_handle``."""
@@ -323,42 +323,12 @@ class _NativeGenerator(torch.nn.Module):
     # the workspaces, the cached parameter lists (they would point at the ORIGINAL's tensors) and the gradient-sync wiring stay behind, and
     # the copy registers with the optimizer post-step hook itself — a deep-copied generator trained with a fused optimizer (no
     # Parameter._version bump) would otherwise keep running on the weights it was copied with.
-    _EPHEMERAL = ("_handle", "_lib", "_workspaces", "_grad_slots", "_grad_sync", "_param_sig", "_plist_cache", "_plist_epoch", "_raw_cache", "_sent_sig",
-                  "_sent_held", "_raw_cnames")
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        for k in self._EPHEMERAL:
-            state.pop(k, None)
-        return state
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        d = self.__dict__
-        d["_handle"] = d["_lib"] = d["_grad_slots"] = d["_grad_sync"] = d["_param_sig"] = d["_plist_cache"] = d["_raw_cache"] = None
-        d["_workspaces"] = {}
-        from ..utils.optim_hook import watch
-
-        watch(self)
+    _DESTROY = "hificar_destroy"
+    _NATIVE = {"_handle": None, "_workspace_buf": None, "_grad_slots": None, "_plist_cache": None, "_sent_sig": ABSENT, "_sent_held": ABSENT}
+    _PROCESS = {"_lib": None, "_grad_sync": None, "_param_sig": None, "_plist_epoch": ABSENT, "_raw_cache": None, "_raw_cnames": ABSENT}
+    _WATCHED = True
 
     # ------------------------------------------------------------------ native handle
-    def _invalidate(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and self._lib is not None:
-            self._lib.hificar_destroy(h)
-        self._handle = None
-        self._workspaces = {}
-        self._grad_slots = None
-        self.__dict__["_plist_cache"] = None
-        self.__dict__.pop("_sent_sig", None)
-        self.__dict__.pop("_sent_held", None)
-
-    def __del__(self):
-        try:
-            self._invalidate()
-        except Exception:
-            pass
-
     def refresh_native(self):
         """Re-upload weights after an in-place parameter edit (e.g. ``p.data.copy_``)."""
         self._invalidate()
@@ -405,7 +375,7 @@ class _NativeGenerator(torch.nn.Module):
                     names, tensors = self._raw_parameters()
                     dev = self._device()
                     with torch.no_grad(), torch.cuda.device(dev):
-                        _send_parameters(self, "hificar_set_parameters_device", names, tensors, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+                        _send_parameters(self, "hificar_set_parameters_device", names, tensors, current_stream())
                     self._param_sig = self._param_signature()
                     return self._handle
                 self._invalidate()
@@ -418,18 +388,9 @@ class _NativeGenerator(torch.nn.Module):
                 "(move the model to a MI355X with .to('cuda')). There is no CPU fallback." % (type(self).__name__, dev))
         lib = _native.load_library()
         self._lib = lib
-        handle = ctypes.c_void_p()
         with torch.cuda.device(dev):
-            self._create_handle(lib, handle)
-            try:
-                for name, t in self.folded_state().items():
-                    shape = (ctypes.c_int64 * t.dim())(*t.shape)
-                    _native.check(lib.hificar_set_weight(handle, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim()),
-                                  "hificar_set_weight")
-                _native.check(lib.hificar_finalize(handle), "hificar_finalize")
-            except Exception:
-                lib.hificar_destroy(handle)
-                raise
+            handle = create_handle(lib, "hificar", lambda h: self._create_handle(lib, h), self.folded_state(),
+                                   lambda h: _native.check(lib.hificar_finalize(h), "hificar_finalize"))
         self._handle = handle
         self._param_sig = self._param_signature()
         return handle
@@ -437,14 +398,7 @@ class _NativeGenerator(torch.nn.Module):
     def _workspace(self, B, T):
         """One grow-only scratch buffer per model (the library plans its layout per call): a dataset of many distinct
         utterance lengths re-uses it instead of allocating per shape."""
-        n = self._lib.hificar_workspace_bytes(self._handle, B, T) + 256
-        ws = self._workspaces.get("buf")
-        if ws is None or ws.numel() < n:
-            # work already enqueued on the old buffer keeps it alive through the caching allocator's stream ordering
-            ws = torch.empty(int(n * 1.25) if ws is not None else n, dtype=torch.uint8, device=self._device())
-            self._workspaces["buf"] = ws
-        off = (-ws.data_ptr()) % 256
-        return ws.data_ptr() + off, ws.numel() - off
+        return scratch(self, "_workspace_buf", self._lib.hificar_workspace_bytes(self._handle, B, T), self._device)
 
     def macs(self, B, T):
         """Algorithmic multiply-accumulates of one forward of B x T frames (SURVEY.md §8d constant)."""
@@ -627,12 +581,12 @@ class _NativeGenerator(torch.nn.Module):
         ph_out = torch.zeros((B, self._params["num_ph"], T), dtype=torch.float32, device=c.device) if self.use_ph_loss else None
         with torch.cuda.device(c.device):
             ws_ptr, ws_bytes = self._workspace(B, T)
-            stream = torch.cuda.current_stream().cuda_stream
+            stream = current_stream()
             rc = self._lib.hificar_forward_cond(handle, c.data_ptr(), ar.data_ptr() if self.use_ar else None,
                                                 spk_id.data_ptr() if self.use_spk_id else None, ph.data_ptr() if self.use_ph else None,
                                                 lengths.data_ptr() if lengths is not None else None, out.data_ptr(),
                                                 ph_out.data_ptr() if ph_out is not None else None,
-                                                B, T, ws_ptr, ws_bytes, ctypes.c_void_p(stream))
+                                                B, T, ws_ptr, ws_bytes, stream)
         _native.check(rc, "hificar_forward")
         if trainable:  # eval mode with trainable parameters: no tape was kept — say so if somebody calls backward on this
             out = _NoGraph.apply(out, type(self).__name__, next(p for p in self._plist() if p.requires_grad))
@@ -684,15 +638,15 @@ class _NativeGenerator(torch.nn.Module):
             out = torch.zeros((B, T * self.hop), dtype=torch.float32, device=c.device)
         with torch.cuda.device(c.device):
             ws_ptr, ws_bytes = self._workspace(B, min(int(chunk_frames), T))
-            stream = torch.cuda.current_stream().cuda_stream
+            stream = current_stream()
             lens = (lengths.data_ptr(), lengths_host.data_ptr()) if lengths is not None else (None, None)
             if spk_id is None and ph is None:  # (a conditioned model is refused here: its error names hificar_forward_cond)
                 rc = self._lib.hificar_ar_loop_ragged(handle, c.data_ptr(), *lens, out.data_ptr(), B, T, int(chunk_frames), ws_ptr,
-                                                      ws_bytes, ctypes.c_void_p(stream))
+                                                      ws_bytes, stream)
             else:
                 rc = self._lib.hificar_ar_loop_cond(handle, c.data_ptr(), spk_id.data_ptr() if spk_id is not None else None,
                                                     ph.data_ptr() if ph is not None else None, *lens, out.data_ptr(), B, T,
-                                                    int(chunk_frames), ws_ptr, ws_bytes, ctypes.c_void_p(stream))
+                                                    int(chunk_frames), ws_ptr, ws_bytes, stream)
         _native.check(rc, "hificar_ar_loop")
         return out
 
@@ -715,15 +669,15 @@ class _NativeGenerator(torch.nn.Module):
         batch = max(1, min(int(batch), N))
         with torch.cuda.device(c.device):
             ws_ptr, ws_bytes = self._workspace(batch, min(int(chunk_frames), T))
-            stream = torch.cuda.current_stream().cuda_stream
+            stream = current_stream()
             if spk_id is None and ph is None:
                 rc = self._lib.hificar_ar_loop_packed(handle, c.data_ptr(), lengths_host.data_ptr(), out.data_ptr(), N, T,
-                                                      int(chunk_frames), batch, ws_ptr, ws_bytes, ctypes.c_void_p(stream))
+                                                      int(chunk_frames), batch, ws_ptr, ws_bytes, stream)
             else:
                 rc = self._lib.hificar_ar_loop_packed_cond(handle, c.data_ptr(), spk_id.data_ptr() if spk_id is not None else None,
                                                            ph.data_ptr() if ph is not None else None, lengths_host.data_ptr(),
                                                            out.data_ptr(), N, T, int(chunk_frames), batch, ws_ptr, ws_bytes,
-                                                           ctypes.c_void_p(stream))
+                                                           stream)
         _native.check(rc, "hificar_ar_loop_packed")
         return out
 
@@ -866,13 +820,7 @@ class HiFiGANGenerator(_NativeGenerator):
         else:
             self.reset_parameters()
 
-        self._handle = None
-        self._workspaces = {}
-        self._lib = None
-        self._grad_sync = None
-        from ..utils.optim_hook import watch
-
-        watch(self)  # fused optimizers do not bump Parameter._version: every optimizer.step() over these parameters invalidates the hand-over
+        self._reset_native()
 
     def _tap_shape(self, name, B, T, Tb):
         """(buffer shape, valid rows or None) of a debug tap; Tb = the launch's bucket of frames."""

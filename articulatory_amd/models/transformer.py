@@ -62,12 +62,12 @@ keywords are accepted and unused, as in the reference.
 ``lengths=`` in eval mode is this package's addition: a ragged batch in which every utterance's result is that of running it alone.
 """
 
-import ctypes
 import math
 
 import torch
 
 from .. import _native
+from .._owner import aligned, current_stream, scratch
 from ._feature_model import NativeFeatureModel, _grad_layout, _tape_backward, _tape_forward  # noqa: F401  (_grad_layout: imported from here too)
 from .bigru import _BatchNormParams, _LinearParams
 
@@ -192,7 +192,7 @@ class Transformer(NativeFeatureModel, metaclass=_PrecisionKeyword):
     _PREFIX = "hificar_xfmr"
     _NAME = "Transformer"
     # whether the ragged training forward under way is the packed form; this batch's statistics, for inspection
-    _TRANSIENT = {"_packed": False, "_last_stats": None}
+    _PROCESS = {**NativeFeatureModel._PROCESS, "_packed": False, "_last_stats": None}
     _LOWRATE_TRAINING = "training on low-rate inputs is not built"
     _LOWRATE_RANGE = " (B factor Tl 3072 < 2^31)"
 
@@ -318,7 +318,7 @@ class Transformer(NativeFeatureModel, metaclass=_PrecisionKeyword):
             n = self._lib.hificar_xfmr_train_workspace_bytes(self._handle, B, T)
         else:
             n = self._lib.hificar_xfmr_train_workspace_bytes_packed(self._handle, B, packed_rows)
-        return self._scratch("_train_ws_buf", n)
+        return scratch(self, "_train_ws_buf", n, self._device)
 
     def _run_forward_train(self, x, p, seed, offset, keep_tape, lens=None, packed=False):
         """hificar_xfmr_forward_train (lens = (host, device) int32 lengths: hificar_xfmr_forward_train_ragged, or, packed,
@@ -328,12 +328,12 @@ class Transformer(NativeFeatureModel, metaclass=_PrecisionKeyword):
         dev = x.device
         mp = self._packed_rows(lens[0], B, T) if packed else None
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = current_stream()
             tape, toff = None, 0
             if keep_tape:
                 nbytes = lib.hificar_xfmr_tape_bytes_packed(handle, B, mp) if packed else lib.hificar_xfmr_tape_bytes(handle, B, T)
-                tape = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-                toff = (-tape.data_ptr()) % 256
+                tape, ptr = aligned(nbytes, dev)
+                toff = ptr - tape.data_ptr()
             out = torch.empty((B, self._params["out_channels"], T), dtype=torch.float32, device=dev)
             stats = torch.empty(self._stats_shape(), dtype=torch.float32, device=dev)
             ws_ptr, ws_bytes = self._train_workspace(B, T, mp)

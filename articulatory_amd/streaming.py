@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _native
+from ._owner import current_stream
 
 
 class _Session:
@@ -259,16 +260,16 @@ class StreamingSynthesizer:
         out = torch.empty((n, self.hop * self.chunk_frames), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             ws_ptr, ws_bytes = m._workspace(n, self.chunk_frames)
-            stream = torch.cuda.current_stream().cuda_stream
+            stream = current_stream()
             if self.use_spk_id or self.use_ph:
                 rc = m._lib.hificar_ar_step_cond(handle, self._feat.data_ptr(), self._feat.stride(0), self._feat.stride(1),
                                                  self._spk.data_ptr() if self.use_spk_id else None,
                                                  self._ph.data_ptr() if self.use_ph else None, self._ph.stride(0) if self.use_ph else 0,
                                                  table.ctypes.data_as(ctypes.c_void_p), n, self.chunk_frames, self._ctx.data_ptr(),
-                                                 self.sched.max_sessions, out.data_ptr(), ws_ptr, ws_bytes, ctypes.c_void_p(stream))
+                                                 self.sched.max_sessions, out.data_ptr(), ws_ptr, ws_bytes, stream)
             else:
                 rc = m._lib.hificar_ar_step(handle, self._feat.data_ptr(), self._feat.stride(0), self._feat.stride(1),
                                             table.ctypes.data_as(ctypes.c_void_p), n, self.chunk_frames, self._ctx.data_ptr(),
-                                            self.sched.max_sessions, out.data_ptr(), ws_ptr, ws_bytes, ctypes.c_void_p(stream))
+                                            self.sched.max_sessions, out.data_ptr(), ws_ptr, ws_bytes, stream)
         _native.check(rc, "hificar_ar_step")
         return out

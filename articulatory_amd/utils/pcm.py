@@ -1,10 +1,9 @@
 """Device-side float -> PCM_16 conversion (C ABI: hificar_pcm16)."""
 
-import ctypes
-
 import torch
 
 from .. import _native
+from .._owner import current_stream
 
 
 def pcm16(y: torch.Tensor) -> torch.Tensor:
@@ -17,6 +16,6 @@ def pcm16(y: torch.Tensor) -> torch.Tensor:
     x = y.to(torch.float32).contiguous()
     out = torch.empty(x.shape, dtype=torch.int16, device=x.device)
     with torch.cuda.device(x.device):
-        rc = lib.hificar_pcm16(x.data_ptr(), out.data_ptr(), x.numel(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = lib.hificar_pcm16(x.data_ptr(), out.data_ptr(), x.numel(), current_stream())
     _native.check(rc, "hificar_pcm16")
     return out
